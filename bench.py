@@ -13,14 +13,27 @@ ordered kernels, and `roofline.kernel_ms` the dominant kernel alone.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
   python bench.py --gpus N ...          (no WORLD_SIZE in the environment: bench.py starts the N ranks
-                                         itself -- it re-executes under torch.distributed.run on 127.0.0.1)
+                                         itself -- it runs torch.distributed.run on 127.0.0.1 as a child)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Methodology: after W warm-up steps, `--regions` R (default 11) timed regions of
-EXACTLY K steps each, every one bracketed by barrier + device synchronise, the maximum over ranks taken
+A plain run measures the headline alone: set-up, W warm-up steps, ONE timed region of exactly K steps, the
+parity check of what that region coded, the optional `--dump-outputs DIR`, the line.  Everything else below
+(more regions, clocks, per-kernel figures, rooflines from PMC / live microbenchmarks, the other configurations,
+host-to-host, the CPU baseline, the multi-rank exchange regions) runs with `--full`:
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller (as float
+.npy files, under 64 MB in all; the inputs are seeded, so two builds can be compared output for output):
+`sizes.npy` (bytes of every frame's JPEG), `stream_checksums.npy` (per frame, the sum over the whole stream of
+byte x (position mod 65521 + 1), exact in float64), `stream_sample.npy` (per frame, the bytes at the fixed
+seeded positions of `stream_sample_positions.npy`, -1 past the end of that frame's stream).
+
+Methodology: after W warm-up steps, `--regions` R (default 1; 11 with `--full`) timed
+regions of EXACTLY K steps each, every one bracketed by barrier + device synchronise, the maximum over ranks taken
 per region; `ms_per_step` / `value` are the MEDIAN region, `ms_per_step_min` / `_max` the spread, and
-`clocks`: the shader clock a probe wave measures WHILE the last region runs (`shader_mhz_under_load`: the chip clocks
+(`--full`) `clocks`: the shader clock a probe wave measures WHILE the last region runs (`shader_mhz_under_load`: the chip clocks
 down under this kernel's sustained VALU load) and right behind the first and the last region (cycle counter against the
 device's 100 MHz counter: sjpeg_hip_debug_shader_clock) and what sysfs reports for sclk / mclk while they run -- on
 these boxes the sysfs sclk lags and shows ~100 MHz, the measured figure is the one to read (boxes differ by a few per cent).
@@ -344,8 +357,8 @@ def device_clocks(index=0):
 
 def launch_ranks(args):
     """`--gpus N` with N > 1 and no torch.distributed environment: this process becomes the launcher --
-    one rank per GPU under torch.distributed.run on 127.0.0.1 with the same arguments; rank 0 of the
-    started world prints the line.  Refuses more ranks than devices."""
+    one rank per GPU under torch.distributed.run on 127.0.0.1 (a child process) with the same arguments; rank 0
+    of the started world prints the line.  Refuses more ranks than devices."""
     import socket
     if not args.launch_check:
         import torch
@@ -358,7 +371,9 @@ def launch_ranks(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child process, not an exec: this process may already have initialised the HIP runtime above
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 def launch_check(world, rank):
@@ -445,6 +460,29 @@ def c4_region(sj, torch, eng, rank, world, steps, regions, digests, fence, max_o
             "check": "rank 0: streams of the last step, host-side concatenation in frame order, MD5 db599667..."}
 
 
+def dump_outputs(outdir, sizes, coded, budget=48 << 20, seed=20251015):
+    """--dump-outputs: what the last timed step returned to its caller, as float .npy files under `budget` bytes in
+    all -- the size of every frame's JPEG, a position-weighted checksum of every whole stream (exact in float64),
+    and the bytes of every stream at the same seeded positions (drawn once from [0, longest stream), -1 past the
+    end of a shorter one)."""
+    os.makedirs(outdir, exist_ok=True)
+    n = len(coded)
+    longest = max((len(c) for c in coded), default=0)
+    take = min(longest, budget // (4 * max(n, 1) + 8))
+    pos = np.sort(np.random.default_rng(seed).choice(longest, take, replace=False)) if take else np.zeros(0, np.int64)
+    sample = np.full((n, take), -1.0, np.float32)
+    sums = np.zeros(n, np.float64)
+    for k, c in enumerate(coded):
+        b = np.frombuffer(c, np.uint8)
+        sums[k] = float(np.dot(b.astype(np.int64), np.arange(len(b), dtype=np.int64) % 65521 + 1))
+        inside = pos < len(b)
+        sample[k, inside] = b[pos[inside]]
+    np.save(os.path.join(outdir, "sizes.npy"), np.asarray(sizes, np.float64))
+    np.save(os.path.join(outdir, "stream_checksums.npy"), sums)
+    np.save(os.path.join(outdir, "stream_sample.npy"), sample)
+    np.save(os.path.join(outdir, "stream_sample_positions.npy"), pos.astype(np.float64))
+
+
 def emit(res):
     """The ONE JSON line, last on stdout: RCCL prints a version banner through C stdio, which would
     otherwise be flushed behind it at exit."""
@@ -468,8 +506,15 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--exchange", action="store_true",
                     help="N = 1 only: run the `with_gather` region too (RCCL with a single rank: packing + self-gather)")
-    ap.add_argument("--regions", type=int, default=11,
-                    help="timed regions of --steps steps each; the line carries the median region and the spread")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each (default 1; 11 with --full); the line carries the median "
+                         "region and the spread")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: clocks, per-kernel timing and "
+                         "rooflines, the other configurations, host-to-host, the CPU baseline, the exchange regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (sizes, per-frame stream checksums "
+                         "and a fixed seeded sample of the streams) as DIR/<name>.npy")
     ap.add_argument("--timed-only", action="store_true",
                     help="stop after the timed regions and the parity check: no per-kernel timing calls, no ordered "
                          "steps, no other configurations -- the run tools/profile_gpu.sh traces to compare the "
@@ -480,6 +525,8 @@ def main():
                     help="1 (default): the timed steps run in the engine's pipelined mode (the stitch kernels of "
                          "step i on the engine's own stream, under K1 of step i + 1); 0: ordered calls")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 11 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.regions < 1:
         raise SystemExit("bench.py: --gpus, --steps and --regions must be positive")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -558,9 +605,12 @@ def main():
     fence()
     # (the clocks are read while the steps of a region are queued on the device -- between regions it idles and
     # the shader clock drops to ~100 MHz within microseconds; the read costs the host ~0.1 ms, the device nothing)
-    clocks = {} if rank == 0 else None
-    probe_stream = torch.cuda.Stream() if rank == 0 else None
-    if rank == 0:
+    # (a plain run measures the headline alone; --full adds the clocks, per-kernel figures and everything after them)
+    extras = args.full and not args.timed_only
+    probe = rank == 0 and args.full
+    clocks = {} if probe else None
+    probe_stream = torch.cuda.Stream() if probe else None
+    if probe:
         device_clocks(local)                      # (finds the sysfs files: outside the timed regions)
     region_s = []
     for reg in range(args.regions):               # every region: EXACTLY --steps steps between two fences
@@ -568,9 +618,9 @@ def main():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             encode()
-        if rank == 0 and reg in (0, args.regions - 1):
+        if probe and reg in (0, args.regions - 1):
             clocks["first_region" if reg == 0 else "last_region"] = device_clocks(local)
-        if rank == 0 and reg == args.regions - 1:
+        if probe and reg == args.regions - 1:
             # the shader clock UNDER this load: a probe wave on a side stream while the region's steps are queued and
             # running (K1 leaves half of a CU's wave slots free); 20 us of one wave, the host waits for it only
             try:
@@ -583,7 +633,7 @@ def main():
                 pass
         fence()
         region_s.append(max_over_ranks(time.perf_counter() - t0))
-        if rank == 0 and reg in (0, args.regions - 1):
+        if probe and reg in (0, args.regions - 1):
             # outside the timed region, right behind its last kernel: the shader clock as a wave measures it
             # (the sysfs figure above lags and shows ~100 MHz whenever it samples an empty queue)
             try:
@@ -597,6 +647,8 @@ def main():
     # what the timed steps left behind is what gets checked (fence() waited for the engine's stream too)
     sz = sizes.cpu().numpy()
     coded = [bytes(out[k, :int(sz[k])].cpu().numpy()) for k in range(F)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sz, coded)
 
     scratch_piped = eng.scratch_bytes()
     algo_bytes = 3.0 * W * H * F
@@ -604,7 +656,7 @@ def main():
     traffic = valu_per_wave = waves = None
     stream_gbps, rates = None, None
     scan_ms_piped = []
-    if not args.timed_only:
+    if extras:
         if args.pipelined:
             # ---- dominant-kernel duration IN THE MODE OF THE HEADLINE: HIP events on the engine's launch
             # stream around K1 while the stitch kernels of the previous step run beside it on the engine's side stream --
@@ -642,7 +694,7 @@ def main():
     achieved = algo_bytes / scan_avg if scan_avg else None
 
     # ---- what a read-only stream kernel reaches on this device (context for `peak`) ----------
-    if rank == 0 and not args.timed_only:
+    if rank == 0 and extras:
         try:
             import ctypes as C
             L = sj.lib()
@@ -736,7 +788,7 @@ def main():
         res["config"]["pipelined"] = bool(args.pipelined)
         if ordered_ms is not None:
             res["ms_per_step_ordered"] = round(ordered_ms, 4)
-        if args.pipelined and not args.timed_only:   # what the strictly ordered mode holds (one set of segment buffers)
+        if args.pipelined and extras:   # what the strictly ordered mode holds (one set of segment buffers)
             e2 = sj.Engine(local)
             e2.encode_frames(frames, tables, header, sj.YUV_420, out=outs[0], sizes=sizes_b[0], out_stride=out_stride)
             torch.cuda.synchronize()
@@ -748,7 +800,7 @@ def main():
     # ---- N > 1: the same steps with the exchange step of config #4 inside a second timed region ----
     # The headline line is complete at this point.  A watchdog prints it anyway if the exchange (RCCL
     # on a node this code has not met before) does not come back: the metric must not be lost with it.
-    if exchange and not args.timed_only:
+    if exchange and (args.full or args.exchange) and not args.timed_only:
         import threading
         from sjpeg_amd.dist import exchange_loop
 
@@ -858,7 +910,7 @@ def main():
             if isinstance(c4, dict) and c4.get("bit_exact") is False:
                 parity = False
     if rank == 0:
-        if world == 1 and not args.no_other_configs and not args.timed_only:
+        if world == 1 and not args.no_other_configs and extras:
             del frames
             torch.cuda.empty_cache()
             oc = {}
@@ -926,7 +978,7 @@ def main():
                 res["host_to_host"] = {"error": repr(exc)}
             if any(isinstance(v, dict) and v.get("bit_exact") is False for v in oc.values()):
                 parity = False
-        if not args.no_cpu_baseline and world == 1 and not args.timed_only:
+        if not args.no_cpu_baseline and world == 1 and extras:
             res["cpu_baseline"] = cpu_baseline(host)
         if not parity:
             res["value"] = 0.0

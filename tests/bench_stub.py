@@ -2,7 +2,7 @@
 VERDICT r05 #6): the first 8-GPU run of `bench.py --gpus N` must not be the first time its N > 1 code runs at all.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P \
-           tests/bench_stub.py --gpus 2 --steps 1 --warmup 0 --regions 1 --frames 2 --no-cpu-baseline
+           tests/bench_stub.py --gpus 2 --steps 1 --warmup 0 --regions 1 --frames 2 --no-cpu-baseline --full
 
 Everything bench.py does between "import torch" and the JSON line runs as written -- process group, fences, max over
 ranks, the timed regions, the packed-output exchange loop (sjpeg_amd.dist on torch.distributed), the local sinks,

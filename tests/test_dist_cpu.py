@@ -255,8 +255,8 @@ def test_exchange_loop_with_packed_output_and_the_root_in_place():
 
 def test_bench_launcher_starts_the_world_it_was_asked_for():
     """`python bench.py --gpus 2` without a torch.distributed environment must start two ranks by itself
-    (the flag was parsed and ignored).  --launch-check takes the launcher's exact path -- re-exec
-    under torch.distributed.run on 127.0.0.1 -- and meets on gloo instead of touching a device."""
+    (the flag was parsed and ignored).  --launch-check takes the launcher's exact path -- a child
+    torch.distributed.run on 127.0.0.1 -- and meets on gloo instead of touching a device."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -289,7 +289,7 @@ def test_bench_two_ranks_end_to_end_with_a_stand_in_device():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "tests", "bench_stub.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--regions", "2", "--frames", "3", "--input", "noise", "--no-cpu-baseline"],
+                        "--regions", "2", "--frames", "3", "--input", "noise", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -307,6 +307,39 @@ def test_bench_two_ranks_end_to_end_with_a_stand_in_device():
     assert c4["encode_only"]["mpix_s"] > 0 and c4["with_gather"]["mpix_s"] > 0
     m = d["multi_gpu_model"]
     assert m["quote_beside_value"] == "with_local_sink" and m["rooted_gather_ceiling_per_peer_mpix_s"] > 0
+
+
+def test_bench_dump_outputs_with_a_stand_in_device(tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, the stand-in device of tests/bench_stub.py): what the last timed step
+    returned, as float arrays -- the sizes and checksums of the oracle's streams --, and the same files again from a
+    second run with the same arguments."""
+    import json
+    import subprocess
+    from oracle import orc, synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_stub.py"), "--gpus", "1", "--steps", "2",
+                            "--warmup", "1", "--frames", "3", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["regions"] == 1 and "other_configs" not in line and "cpu_baseline" not in line
+        got = {n: np.load(d / f"{n}.npy") for n in ("sizes", "stream_checksums", "stream_sample", "stream_sample_positions")}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        dumps.append(got)
+    o = orc.oracle()
+    want = [o.encode(synth.g_struct(64, 48, 7654321 + k), 75.0, orc.YUV_420) for k in range(3)]
+    assert dumps[0]["sizes"].tolist() == [len(c) for c in want]
+    for k, c in enumerate(want):
+        b = np.frombuffer(c, np.uint8).astype(np.int64)
+        assert dumps[0]["stream_checksums"][k] == float(np.dot(b, np.arange(len(b)) % 65521 + 1))
+        pos = dumps[0]["stream_sample_positions"].astype(np.int64)
+        inside = pos < len(c)
+        assert (dumps[0]["stream_sample"][k][inside] == b[pos[inside]]).all() and (dumps[0]["stream_sample"][k][~inside] == -1).all()
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 # ---- one frame over several ranks: exchange of band bit strings (SURVEY.md section 8e) -------------

@@ -1065,12 +1065,12 @@ def test_sharp_yuv_wide_and_1080p(oracle):
 
 @pytest.fixture(scope="module")
 def risk_table():
-    """The trained table lives in the reference (src/score_7.cc); tests read it out of the built
-    reference (oracle/_ref travels to the GPU box) and hand it to the library at run time."""
-    from oracle import refso
-    if not refso.available():
-        pytest.skip("oracle/_ref/libsjpeg_ref.so not built: no riskiness table to install")
-    tab = refso.ref().sharpness_table()
+    """The trained table of the reference (src/score_7.cc), as the package ships it (sjpeg_amd/csrc/riskiness.bin,
+    pinned by tests/test_host.py and checked against the reference build wherever there is one), handed to the
+    library at run time."""
+    with open(os.path.join(sj.CSRC, "riskiness.bin"), "rb") as f:
+        tab = f.read()
+    assert len(tab) == 117649
     sj.set_riskiness_table(tab)
     return tab
 

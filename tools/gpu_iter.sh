@@ -6,7 +6,7 @@ set -u
 TAG=${1:-iter}; MODE=${2:-full}
 OUT=gpurun_out/r05/$TAG; mkdir -p $OUT
 python -m pytest tests -m gpu -x -q 2>&1 | grep -v "amdgpu.ids\|^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" | tail -4 | tee $OUT/gputests.txt
-python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench.json
+python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench.json
 python - <<PY | tee $OUT/bench_key.txt
 import json
 d = json.loads(open("$OUT/bench.json").read())

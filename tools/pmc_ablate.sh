@@ -12,7 +12,7 @@ for A in $1; do
            "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INST_LEVEL_LDS SQ_IFETCH SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS_ATOMIC" \
            "SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_LDS_UNALIGNED_STALL SQ_LEVEL_WAVES SQ_IFETCH_LEVEL SQ_INSTS_VALU_INT64 SQ_ACTIVE_INST_VMEM SQ_INSTS_SMEM"; do
     G=$((G+1)); tag=g$G
-    SJPEG_HIP_ABLATE=$A rocprofv3 --kernel-trace --output-format csv --pmc $P -d $OUT/a${A}_$tag -o pmc -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/a${A}_$tag.log 2>&1
+    SJPEG_HIP_ABLATE=$A rocprofv3 --kernel-trace --output-format csv --pmc $P -d $OUT/a${A}_$tag -o pmc -- python $OLDPWD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/a${A}_$tag.log 2>&1
   done
 done
 python - <<PY

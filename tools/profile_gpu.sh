@@ -6,7 +6,7 @@ TAG=${1:-r01}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $PWD/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-other-configs"
+CMD="python $PWD/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-other-configs"
 ROOT=$PWD
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
@@ -15,7 +15,7 @@ for f in $(find $OUT/trace -name "*kernel_stats.csv"); do cp $f $OUT/kernel_stat
 # regions x steps dispatches of every kernel in the trace ARE the timed regions (settling and warm-up calls lie
 # in front of them) -- their mean is what ms_per_step is made of.
 STEPS=20; REGIONS=5
-rocprofv3 --kernel-trace --output-format csv -d $OUT/timed -o timed -- python $ROOT/bench.py --timed-only --steps $STEPS --regions $REGIONS > $OUT/timed.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/timed -o timed -- python $ROOT/bench.py --full --timed-only --steps $STEPS --regions $REGIONS > $OUT/timed.log 2>&1
 python - <<PY
 import csv, glob, collections
 out = "$OUT"; n = $STEPS * $REGIONS
@@ -41,7 +41,7 @@ with open(out + "/timed_region_kernel_stats.csv", "w") as f:
             b["ms_per_step"], b["ms_per_step_min"], b["ms_per_step_max"], b["value"], b["bit_exact"]))
 print(open(out + "/timed_region_kernel_stats.csv").read())
 PY
-PMC_CMD="python $ROOT/bench.py --timed-only --steps 3 --warmup 1 --regions 1"
+PMC_CMD="python $ROOT/bench.py --full --timed-only --steps 3 --warmup 1 --regions 1"
 pmc() {  # name counters...
   local name=$1; shift
   rocprofv3 --kernel-trace --output-format csv --pmc "$@" -d $OUT/pmc_$name -o pmc -- $PMC_CMD > $OUT/pmc_$name.log 2>&1

@@ -6,6 +6,7 @@
 set -u
 TAG=${1:-r05}
 mkdir -p gpurun_out/$TAG
+OUT=${OUT:-bench_runs/$TAG}; mkdir -p $OUT   # the two bench lines
 bash tools/profile_gpu.sh $TAG > gpurun_out/$TAG/profile_gpu.log 2>&1
 bash tools/pmc_phases.sh ${TAG}_struct "0 1 2 3" > gpurun_out/$TAG/pmc_phases_struct.txt 2>&1
 PHASE_CMD="python $PWD/tools/profile_workload.py c2noise 3" bash tools/pmc_phases.sh ${TAG}_noise "0 1 2 3" > gpurun_out/$TAG/pmc_phases_noise.txt 2>&1
@@ -20,6 +21,6 @@ for job in "trellis1080 trellis_time.py 1920 1080 10" "trellis4k trellis_time.py
   grep "ms  " gpurun_out/$TAG/$1.log > gpurun_out/prof_$TAG/$1_line.txt
 done
 python tools/sharp_batch_time.py 2>/dev/null | grep batch > gpurun_out/prof_$TAG/sharp_batches.txt
-python bench.py > gpurun_out/$TAG/final_bench.json 2> gpurun_out/$TAG/final_bench.err
-python bench.py --gpus 1 --exchange --no-cpu-baseline --no-other-configs > gpurun_out/$TAG/exchange_n1.json 2> gpurun_out/$TAG/exchange_n1.err
-tail -c 600 gpurun_out/$TAG/final_bench.json
+python bench.py --full > $OUT/final_bench.json 2> $OUT/final_bench.err
+python bench.py --full --gpus 1 --exchange --no-cpu-baseline --no-other-configs > $OUT/exchange_n1.json 2> $OUT/exchange_n1.err
+tail -c 600 $OUT/final_bench.json

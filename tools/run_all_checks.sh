@@ -31,4 +31,4 @@ if command -v hipcc >/dev/null 2>&1 || [ -x /opt/rocm/bin/hipcc ]; then
   make -s -C sjpeg_amd/csrc || exit 1
   ls -a sjpeg_amd/csrc | grep config_
 fi
-N=1 run python bench.py --no-cpu-baseline
+N=1 run python bench.py --full --no-cpu-baseline
