@@ -364,6 +364,36 @@ int sjpeg_hip_scan_symbol_stats_multi(sjpeg_hip_engine* engine, const sjpeg_hip_
                                       const sjpeg_hip_scan_tables* tables /*[nframes]*/,
                                       uint32_t* d_freq, void* stream);
 
+/* A RAGGED batch: pictures of different sizes in one call -- a gallery's thumbnails, an upload queue, a dataset being
+ * re-encoded.  Frame f has its own planes, row strides, width and height (1..65535 each) and its own place in d_out:
+ * [out_offset, out_offset + out_capacity).  The frames share the source format, the yuv_mode and method 0 (fixed
+ * quantizer, default Huffman codes); tables_per_frame = 0: tables[0] codes every frame, 1: frame f is coded with
+ * tables[f] (per-frame quality).  headers / header_offsets[nframes + 1] as sjpeg_hip_encode_scan_multi() (both NULL:
+ * no headers).  The bytes of frame f are what sjpeg_hip_encode_scan_src() makes of that picture alone.
+ *   d_sizes[f] = frame f's size, or 0 when it does not fit its out_capacity (every other frame is still exact; nothing
+ *   is written outside any frame's range).  sjpeg_hip_frame_bound() gives a capacity every frame fits.
+ *   Asynchronous on `stream`.  In pipelined mode the call runs ordered, behind the engine's stitch stream.  A batch
+ *   whose scratch would pass SJPEG_HIP_SCRATCH_LIMIT_BYTES goes in several launches of consecutive frames.
+ *   SJPEG_HIP_EINVAL (the message names the frame) for: nframes outside 1..65535, a format that does not match
+ *   yuv_mode, a null plane, |row_stride| below a row of the plane, bad dimensions, header offsets that do not ascend,
+ *   out_offset + out_capacity past 2^64, and tables with SJPEG_HIP_QUANT_TRELLIS, _KEEP, _REPLAY or
+ *   SJPEG_HIP_RESTART_MARKERS (not taken here).
+ * The scratch is laid out frame after frame by prefix sums -- sized by each frame's own capacity, not nframes times
+ * the largest -- and every kernel runs a flat grid over the batch's total work. */
+typedef struct sjpeg_hip_ragged_frame {
+  const void* plane[3];        /* DEVICE pointers, laid out as `format` says (as sjpeg_hip_source) */
+  int64_t row_stride[3];       /* bytes between rows of each plane; may be negative */
+  int32_t width, height;       /* 1..65535 each */
+  uint64_t out_offset;         /* where this frame's JPEG starts in d_out */
+  uint64_t out_capacity;       /* bytes it may take, e.g. sjpeg_hip_frame_bound(width, height, yuv_mode, header bytes) */
+} sjpeg_hip_ragged_frame;
+
+int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                const sjpeg_hip_scan_tables* tables, int tables_per_frame,
+                                const void* headers, const size_t* header_offsets /*[nframes+1]*/,
+                                int append_eoi, void* d_out, uint64_t* d_sizes, void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

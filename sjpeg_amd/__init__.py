@@ -104,6 +104,12 @@ def make_source(fmt, planes):
     return s, planes[0].shape[0]
 
 
+class RaggedFrame(C.Structure):
+    """struct sjpeg_hip_ragged_frame (include/sjpeg_hip.h): one picture of a ragged batch."""
+    _fields_ = [("plane", C.c_void_p * 3), ("row_stride", C.c_int64 * 3), ("width", C.c_int32),
+                ("height", C.c_int32), ("out_offset", C.c_uint64), ("out_capacity", C.c_uint64)]
+
+
 class HuffmanSpec(C.Structure):
     """struct sjpeg_hip_huffman_spec (include/sjpeg_hip.h)."""
     _fields_ = [("bits", C.c_uint8 * 16), ("syms", C.c_uint8 * 256), ("nsyms", C.c_int32)]
@@ -228,6 +234,10 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_engine_last_scan_ms.argtypes = [C.c_void_p]
     L.sjpeg_hip_engine_last_total_ms.restype = C.c_float
     L.sjpeg_hip_engine_last_total_ms.argtypes = [C.c_void_p]
+    L.sjpeg_hip_encode_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
+                                              C.c_int, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    L.sjpeg_hip_encode_ragged_src.restype = C.c_int
     _lib = L
     return L
 
@@ -258,7 +268,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_restart_interval", "sjpeg_hip_header_add_restart", "sjpeg_hip_encode_intervals_src",
     "sjpeg_hip_comm_unique_id", "sjpeg_hip_comm_create", "sjpeg_hip_comm_create_local", "sjpeg_hip_comm_adopt", "sjpeg_hip_comm_destroy",
     "sjpeg_hip_comm_rank", "sjpeg_hip_comm_world", "sjpeg_hip_gather_rows", "sjpeg_hip_gather_bytes",
-    "sjpeg_hip_gather_streams", "sjpeg_hip_encode_scan_packed_src",
+    "sjpeg_hip_gather_streams", "sjpeg_hip_encode_scan_packed_src", "sjpeg_hip_encode_ragged_src",
 ]
 
 
@@ -892,6 +902,131 @@ class Engine:
         if rc != 0:
             raise SjpegError(f"sjpeg_hip_scan_coeffs: {lib().sjpeg_hip_last_error().decode()}")
         return coeffs
+
+    def encode_ragged(self, fmt, planes_per_frame, dims, yuv_mode, tables, headers=None, append_eoi=True,
+                      capacities=None, out=None, offsets=None, sizes=None):
+        """sjpeg_hip_encode_ragged_src: pictures of different sizes in one call.  planes_per_frame[k]: the CUDA uint8
+        tensors of frame k laid out as `fmt` says ([rows, row_bytes] each, any row stride), or (device address of
+        row 0, row stride in bytes) pairs -- a negative stride codes rows stored bottom-up;
+        dims[k] = (w, h).  tables: one ScanTables for every frame, or a list of one per frame (per-frame quality).
+        headers: None or one header (bytes) per frame.  capacities[k] (default: frame_bound) are the bytes frame k may
+        take.  Returns (out, sizes, offsets): out a flat uint8 CUDA tensor, frame k's JPEG at out[offsets[k]:
+        offsets[k] + sizes[k]], sizes an int64 CUDA tensor (0: the frame did not fit), offsets a list of ints.
+        Asynchronous on the current torch stream."""
+        import torch
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(tables, (list, tuple))
+        if per_frame and len(tables) != n:
+            raise SjpegError("encode_ragged: one ScanTables per frame")
+        if headers is not None and len(headers) != n:
+            raise SjpegError("encode_ragged: one header per frame")
+        frames = (RaggedFrame * n)()
+        if capacities is None:
+            capacities = [frame_bound(w, h, yuv_mode, 0 if headers is None else len(headers[k]))
+                          for k, (w, h) in enumerate(dims)]
+        if offsets is None:
+            offsets, at = [], 0
+            for c in capacities:
+                offsets.append(at)
+                at += (int(c) + 15) & ~15
+            total = at
+        else:
+            total = max(int(o) + int(c) for o, c in zip(offsets, capacities))
+        dev = next((p.device for fr in planes_per_frame for p in fr if not isinstance(p, tuple)),
+                   torch.device("cuda", torch.cuda.current_device()))
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if sizes is None:
+            sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        for k in range(n):
+            fr = frames[k]
+            for i, p in enumerate(planes_per_frame[k]):
+                if isinstance(p, tuple):                 # (device address of row 0, row stride): bottom-up rows too
+                    fr.plane[i], fr.row_stride[i] = int(p[0]), int(p[1])
+                else:
+                    fr.plane[i] = p.data_ptr()
+                    fr.row_stride[i] = p.stride(0) * p.element_size()
+            fr.width, fr.height = int(dims[k][0]), int(dims[k][1])
+            fr.out_offset, fr.out_capacity = int(offsets[k]), int(capacities[k])
+        if per_frame:
+            tarr = (ScanTables * n)(*tables)
+        else:
+            tarr = (ScanTables * 1)(tables)
+        if headers is not None:
+            hoffs = (C.c_size_t * (n + 1))()
+            for i, hd in enumerate(headers):
+                hoffs[i + 1] = hoffs[i] + len(hd)
+            blob, hp = b"".join(headers), hoffs
+        else:
+            blob, hp = None, None
+        self._chk(lib().sjpeg_hip_encode_ragged_src(self._h, fmt, yuv_mode, n, frames, C.cast(tarr, C.c_void_p),
+                                                    int(per_frame), blob, C.cast(hp, C.c_void_p) if hp else None,
+                                                    int(append_eoi), out.data_ptr(), sizes.data_ptr(),
+                                                    self._stream()),
+                  "sjpeg_hip_encode_ragged_src")
+        return out, sizes, list(offsets)
+
+
+def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None):
+    """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
+    uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
+    quality is one float or one per image.  Method 0; frame k's bytes are what encode_device makes of it alone."""
+    import torch
+    images = list(images)
+    if not images:
+        raise SjpegError("encode_images: no images")
+    dev = None
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda:
+            raise SjpegError(f"encode_images: image {k} is not a CUDA tensor")
+        if im.dtype != torch.uint8:
+            raise SjpegError(f"encode_images: image {k} is {im.dtype}, not torch.uint8")
+        if im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+            raise SjpegError(f"encode_images: image {k} must be [H, W, 3] packed RGB (stride 1 over the channels, "
+                             f"3 over x)")
+        if dev is None:
+            dev = im.device
+        elif im.device != dev:
+            raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
+    n = len(images)
+    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    if len(qs) != n:
+        raise SjpegError("encode_images: one quality per image")
+    eng = engine or Engine(dev.index or 0)
+    made = {}
+    tables, headers = [], []
+    for k, im in enumerate(images):
+        q = float(qs[k])
+        if q not in made:
+            made[q] = make_tables(quality=q)
+        t, qm = made[q]
+        tables.append(t)
+        headers.append(make_header(int(im.shape[1]), int(im.shape[0]), yuv_mode, qm))
+    per_frame = len(made) > 1
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    with torch.cuda.device(dev):
+        out, sizes, offs = eng.encode_ragged(SRC_RGB, planes, dims, yuv_mode, tables if per_frame else tables[0],
+                                             headers)
+        eng.wait()                               # (pipelined mode: the output is complete after this)
+        return _fetch_ragged(out, sizes, offs)
+
+
+def _fetch_ragged(out, sizes, offsets):
+    """The JPEGs of a ragged call as byte strings: one pinned staging buffer, one synchronisation."""
+    import torch
+    sz = sizes.cpu().numpy()
+    if (sz <= 0).any():
+        raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % int(np.argmax(sz <= 0)))
+    at = np.concatenate([[0], np.cumsum(sz)]).astype(np.int64)
+    stage = torch.empty(int(at[-1]), dtype=torch.uint8, pin_memory=True)
+    for k in range(len(sz)):
+        stage[int(at[k]):int(at[k + 1])].copy_(out[int(offsets[k]):int(offsets[k]) + int(sz[k])], non_blocking=True)
+    torch.cuda.synchronize()
+    host = stage.numpy()
+    return [host[int(at[k]):int(at[k + 1])].tobytes() for k in range(len(sz))]
 
 
 def encode_device_method(frames, quality=75.0, yuv_mode=YUV_420, method=4, engine=None, quant=None,

@@ -54,6 +54,8 @@ static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 
 // source classes the colour phase is specialised for
 enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2 };
 
+struct RaggedFrame;
+
 struct ScanArgs {
   const uint8_t* plane[3];      // packed colour / gray: [0]; planar YUV: Y, U, V; NV12/NV21: Y, UV
   long long row_stride[3], frame_stride[3];
@@ -83,7 +85,46 @@ struct ScanArgs {
   // counters for K3 -- clear_per of the frame's clear_n, from index seg * clear_per on (NULL: K2 does it)
   uint32_t* clear_ff;
   uint32_t clear_per, clear_n;
+  // ragged launches (kKindEncodeRagged, sjpeg_hip_encode_ragged_src): one descriptor per frame, and the frame of
+  // every workgroup of the launch's flat grid (NULL otherwise)
+  const RaggedFrame* rframes;
+  const uint32_t* rmap;
 };
+
+// One frame of a ragged launch, built on the host (scan_engine.hip, "ragged batches"): its geometry, its planes and
+// where its share of every scratch array starts.  The bases count from the launch's first frame.
+struct alignas(16) RaggedFrame {
+  const uint8_t* plane[3];
+  long long row_stride[3];
+  unsigned long long pool_base, ubuf_base;      // words
+  unsigned long long out_offset, out_capacity;  // bytes of d_out
+  int W, H, mb_w, n_mcus, nseg, has_clip;
+  uint32_t seg_base;       // first segment (seg_nbits, seg_words, seg_xbase); its seg_off row starts at seg_base + frame
+  uint32_t pool_words, ubuf_words;
+  uint32_t chunk_base, max_chunks;              // chunk_ff / chunk_off
+  uint32_t place_base;     // first workgroup of K3 (four segments each)
+  uint32_t stuff_base, stuff_wgs;               // first workgroup of K5, and how many stride over the frame's chunks
+};
+
+// K1's view of the frame a ragged workgroup codes: ScanArgs with the frame's own geometry and planes, every scratch
+// pointer moved to the frame's base -- the kernel then runs as frame 0 of a uniform launch.  Two dependent scalar loads
+// (map, then descriptor) per workgroup; *seg = the segment inside the frame.
+__device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg) {
+  const uint32_t f = in.rmap[blockIdx.x];
+  const RaggedFrame& d = in.rframes[f];
+  ScanArgs v = in;
+  for (int i = 0; i < 3; ++i) { v.plane[i] = d.plane[i]; v.row_stride[i] = d.row_stride[i]; v.frame_stride[i] = 0; }
+  v.W = d.W; v.H = d.H; v.mb_w = d.mb_w; v.n_mcus = d.n_mcus; v.nseg = d.nseg; v.has_clip = d.has_clip;
+  v.tables = in.tables + f * in.tables_stride;
+  v.seg_words = in.seg_words + static_cast<size_t>(d.seg_base) * in.slot_words;
+  v.seg_nbits = in.seg_nbits + d.seg_base;
+  v.seg_xbase = in.seg_xbase + d.seg_base;
+  v.pool = in.pool + d.pool_base;
+  v.pool_words = d.pool_words;
+  v.pool_ctr = in.pool_ctr + 2 * f;
+  *seg = static_cast<int>(blockIdx.x - d.seg_base);
+  return v;
+}
 
 // LDS carve of K1 (bytes, all offsets multiples of 16): the block slots, then the region R behind them.
 // Two layouts.  ROOMY (every kind, every mode): 256 slots, an 8 KiB bit window that also takes the tables of

@@ -36,6 +36,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <type_traits>
 #include <string>
@@ -214,6 +215,10 @@ struct sjpeg_hip_engine {
   int set = 0;                                   // buffer set of the NEXT call
   hipEvent_t k1_done = nullptr, side_done = nullptr, k3_done[2] = {nullptr, nullptr};
   bool k3_pending[2] = {false, false}, side_pending = false;
+  // ragged batches (sjpeg_hip_encode_ragged_src): the call's frame descriptors, tables, workgroup -> frame maps, header
+  // offsets and header bytes, uploaded as one blob -- buffers of its own, so that nothing the uniform calls hold or
+  // upload on the stitch stream is touched
+  DevBuf<uint4> ragged;
   // side_done is recorded LAZILY, by whoever is about to wait on it (side_mark): an event record is a packet in the
   // queue and about 5 us of host time, and a loop of pipelined calls needs none -- one frame per call was bound by the
   // HOST at five event calls per call (36-46 us against 35 of device time, `tools/one_frame_piped.py`)
@@ -653,7 +658,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   }
   e->tables.release(); e->header.release(); e->seg_words.release(); e->seg_nbits.release(); e->pool.release(); e->pool_ctr.release(); e->seg_xbase.release(); e->replay.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
-  e->frame_flags.release();
+  e->frame_flags.release(); e->ragged.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -677,7 +682,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->seg_words2.release(); e->seg_nbits2.release(); e->pool2.release(); e->pool_ctr2.release(); e->seg_xbase2.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->replay.release();
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
-  e->frame_flags.release();
+  e->frame_flags.release(); e->ragged.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -781,7 +786,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   for (auto* l : e->lane) if (l != nullptr) lanes += sjpeg_hip_engine_scratch_bytes(l);
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
-         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2);
+         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -1156,7 +1161,7 @@ static int encode_scan_one(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int
   }
 
   if (!s.fused_k2) {
-    hipLaunchKernelGGL(scan_seg_offsets, dim3(nframes), dim3(kThreads), 0, hs, s);
+    hipLaunchKernelGGL(scan_seg_offsets<>, dim3(nframes), dim3(kThreads), 0, hs, s);
     HIP_TRY(hipGetLastError());
   }
   dbg_mark("encode: K2 launched");
@@ -1169,7 +1174,7 @@ static int encode_scan_one(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int
   else hipLaunchKernelGGL(place_segments<0>, dim3((g.nseg * s.subs + 3) / 4, nframes), dim3(kThreads), 0, hs, s);
   HIP_TRY(hipGetLastError());
   if (!s.fused_k4) {
-    hipLaunchKernelGGL(scan_chunk_offsets, dim3(nframes), dim3(kThreads), 0, hs, s);
+    hipLaunchKernelGGL(scan_chunk_offsets<>, dim3(nframes), dim3(kThreads), 0, hs, s);
     HIP_TRY(hipGetLastError());
   }
   e->ctr_clean_at[set] = a.pool_ctr; e->ctr_clean_n[set] = static_cast<size_t>(nframes);
@@ -1298,6 +1303,271 @@ int sjpeg_hip_scan_symbol_stats_multi(sjpeg_hip_engine* e, const sjpeg_hip_sourc
   return scan_statistics(e, src, width, height, yuv_mode, nframes, tables, false, d_freq, stream, true);
 }
 
+// ==== ragged batches: pictures of different sizes in one call ====================================================
+// Every frame has its own geometry, planes, output place and capacity; they share the source format, the yuv_mode and
+// method 0.  The segment scratch is laid out frame after frame by prefix sums (a frame takes what ITS capacity asks,
+// seg_plan), every kernel runs a flat grid over the launch's total work, and a workgroup finds its frame in a
+// workgroup -> frame map built here beside the descriptors (RaggedFrame, scan_device.h).  A batch whose scratch would
+// pass the engine's limit goes in several launches over consecutive frame ranges.  DESIGN.md section 4.
+namespace {
+
+struct RaggedLaunch {
+  int f0, nf;
+  uint32_t segs, place_wgs, stuff_wgs, chunks;
+  size_t pool_words, ubuf_words;
+  size_t k1_map, place_map, stuff_map;     // where the launch's maps start in the u32 part of the blob
+};
+
+inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
+
+}  // namespace
+
+int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables,
+                                int tables_per_frame, const void* headers, const size_t* header_offsets,
+                                int append_eoi, void* d_out, uint64_t* d_sizes, void* stream) {
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: engine == NULL");
+  if (frames == nullptr || tables == nullptr || d_out == nullptr || d_sizes == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: frames, tables, d_out or d_sizes == NULL");
+  }
+  if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: nframes must be 1..65535");
+  if ((headers == nullptr) != (header_offsets == nullptr)) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: headers and header_offsets go together");
+  }
+  const int ntab = tables_per_frame ? nframes : 1;
+  constexpr uint32_t kNotRagged = SJPEG_HIP_QUANT_TRELLIS | SJPEG_HIP_QUANT_KEEP | SJPEG_HIP_QUANT_REPLAY | SJPEG_HIP_RESTART_MARKERS;
+  for (int t = 0; t < ntab; ++t) {
+    if (tables[t].flags & kNotRagged) {
+      return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: tables[" + std::to_string(t) +
+                                        "]: trellis, keep / replay and restart-marker flags are not taken by ragged batches");
+    }
+  }
+  // the layout of the format (as prepare_scan): planes, source class, the kernel's per-format fields
+  ScanArgs a;
+  memset(&a, 0, sizeof(a));
+  int cls = kSrcPlanes, nplanes = 1, implied = 0;
+  switch (format) {
+    case SJPEG_HIP_SRC_RGB: cls = kSrcRgb24; break;
+    case SJPEG_HIP_SRC_BGRA: cls = kSrcRgbx32; a.rsh = 16; a.bsh = 0; break;
+    case SJPEG_HIP_SRC_RGBA: cls = kSrcRgbx32; a.rsh = 0; a.bsh = 16; break;
+    case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
+    case SJPEG_HIP_SRC_YUV444: nplanes = 3; implied = SJPEG_HIP_YUV444; a.cstep = 1; break;
+    case SJPEG_HIP_SRC_YUV420: nplanes = 3; implied = SJPEG_HIP_YUV420; a.cstep = 1; break;
+    case SJPEG_HIP_SRC_NV12:
+    case SJPEG_HIP_SRC_NV21:
+      nplanes = 2; implied = SJPEG_HIP_YUV420; a.cstep = 2;
+      a.uoff = (format == SJPEG_HIP_SRC_NV12) ? 0 : 1;
+      a.voff = 1 - a.uoff;
+      break;
+    default: return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: unknown source format");
+  }
+  if (yuv_mode != SJPEG_HIP_YUV420 && yuv_mode != SJPEG_HIP_YUV444 && yuv_mode != SJPEG_HIP_YUV400) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: bad yuv_mode");
+  }
+  if (implied != 0 && yuv_mode != implied) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: yuv_mode does not match the source format");
+  size_t header_size = 0;
+  if (header_offsets != nullptr) {
+    for (int f = 0; f <= nframes; ++f) {
+      if (header_offsets[f] > 0xffffffffu || (f > 0 && header_offsets[f] < header_offsets[f - 1])) {
+        return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: header_offsets[" + std::to_string(f) + "] must ascend (below 4 GiB)");
+      }
+    }
+    header_size = header_offsets[nframes];
+  }
+  // per frame: checks, geometry, scratch plan
+  std::vector<FrameGeo> geo(nframes);
+  std::vector<SegPlan> plan(nframes);
+  std::vector<uint32_t> max_chunks(nframes);
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    const std::string who = "sjpeg_hip_encode_ragged_src: frame " + std::to_string(f) + ": ";
+    if (!frame_geo(fr.width, fr.height, yuv_mode, &geo[f])) {
+      return fail(SJPEG_HIP_EINVAL, who + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
+    }
+    const int64_t W = fr.width, cw = (W + 1) / 2;
+    int64_t need[3] = {W, W, W};
+    if (format == SJPEG_HIP_SRC_RGB) need[0] = 3 * W;
+    else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
+    else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
+    else if (format == SJPEG_HIP_SRC_NV12 || format == SJPEG_HIP_SRC_NV21) need[1] = 2 * cw;
+    for (int i = 0; i < nplanes; ++i) {
+      if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, who + "null plane pointer");
+      const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
+      if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, who + "|row_stride| smaller than a row of the plane");
+    }
+    if (fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, who + "out_offset + out_capacity overflows");
+    plan[f] = seg_plan(geo[f], fr.out_capacity > 0 ? static_cast<size_t>(fr.out_capacity) : 1);
+    max_chunks[f] = static_cast<uint32_t>((plan[f].ubuf_words + kChunkWords - 1) / kChunkWords);
+  }
+
+  // launches over consecutive frame ranges, each inside the engine's scratch limit (one frame at least); the blob's
+  // maps: K1 one entry per segment, K3 one per workgroup of four segments, K5 one per workgroup
+  std::vector<RaggedLaunch> launches;
+  size_t map_words = 0;
+  {
+    RaggedLaunch cur = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t slot_max = 0;
+    auto bytes_of = [](size_t segs, uint32_t slot, size_t pool, size_t ubuf) { return (segs * slot + pool + ubuf) * sizeof(uint32_t); };
+    for (int f = 0; f < nframes; ++f) {
+      const uint32_t slot = std::max(slot_max, plan[f].slot_words);
+      const size_t pool_f = (static_cast<size_t>(plan[f].pool_words) + 3) & ~size_t(3);
+      if (cur.nf > 0 && (bytes_of(static_cast<size_t>(cur.segs) + geo[f].nseg, slot, cur.pool_words + pool_f, cur.ubuf_words + plan[f].ubuf_words) > e->scratch_limit ||
+                         static_cast<size_t>(cur.segs) + geo[f].nseg > (1u << 30))) {
+        launches.push_back(cur);
+        cur = {f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        slot_max = 0;
+      }
+      slot_max = std::max(slot_max, plan[f].slot_words);
+      cur.nf += 1;
+      cur.segs += static_cast<uint32_t>(geo[f].nseg);
+      cur.pool_words += pool_f;
+      cur.ubuf_words += plan[f].ubuf_words;
+      cur.chunks += max_chunks[f];
+    }
+    launches.push_back(cur);
+    for (RaggedLaunch& l : launches) {
+      l.place_wgs = l.stuff_wgs = 0;
+      uint32_t gx = 4096u / static_cast<uint32_t>(l.nf);           // K5 workgroups per frame, as a uniform launch of nf frames
+      if (gx < 64) gx = 64;
+      for (int f = l.f0; f < l.f0 + l.nf; ++f) {
+        l.place_wgs += static_cast<uint32_t>((geo[f].nseg + 3) / 4);
+        l.stuff_wgs += std::min(gx, max_chunks[f]);
+      }
+      l.k1_map = map_words; l.place_map = l.k1_map + l.segs; l.stuff_map = l.place_map + l.place_wgs;
+      map_words = l.stuff_map + l.stuff_wgs;
+    }
+  }
+
+  // the blob: descriptors | digested tables | maps | header offsets | header bytes
+  const size_t off_tab = align16(sizeof(RaggedFrame) * nframes);
+  const size_t off_map = off_tab + sizeof(DevTables) * ntab;
+  const size_t off_hoff = align16(off_map + map_words * sizeof(uint32_t));
+  const size_t off_hdr = align16(off_hoff + (header_offsets != nullptr ? (static_cast<size_t>(nframes) + 1) * sizeof(uint32_t) : 0));
+  const size_t blob_bytes = align16(off_hdr + header_size);
+  std::vector<uint4> blob(blob_bytes / 16);
+  uint8_t* const hb = reinterpret_cast<uint8_t*>(blob.data());
+  RaggedFrame* const desc = reinterpret_cast<RaggedFrame*>(hb);
+  for (int t = 0; t < ntab; ++t) digest_tables(tables + t, reinterpret_cast<DevTables*>(hb + off_tab) + t);
+  uint32_t* const maps = reinterpret_cast<uint32_t*>(hb + off_map);
+  std::vector<uint32_t> slot_of(launches.size());
+  for (size_t li = 0; li < launches.size(); ++li) {
+    const RaggedLaunch& l = launches[li];
+    uint32_t slot = 0;
+    for (int f = l.f0; f < l.f0 + l.nf; ++f) slot = std::max(slot, plan[f].slot_words);
+    slot_of[li] = slot;
+    uint32_t seg = 0, place = 0, stuff = 0, chunk = 0;
+    unsigned long long pool = 0, ubuf = 0;
+    uint32_t gx = 4096u / static_cast<uint32_t>(l.nf);
+    if (gx < 64) gx = 64;
+    for (int f = l.f0; f < l.f0 + l.nf; ++f) {
+      const sjpeg_hip_ragged_frame& fr = frames[f];
+      const FrameGeo& g = geo[f];
+      RaggedFrame& d = desc[f];
+      for (int i = 0; i < 3; ++i) {
+        const int p = (nplanes == 2 && i == 2) ? 1 : i;            // interleaved chroma: U and V walk the same plane
+        d.plane[i] = p < nplanes ? static_cast<const uint8_t*>(fr.plane[p]) : nullptr;
+        d.row_stride[i] = p < nplanes ? fr.row_stride[p] : 0;
+      }
+      d.W = fr.width; d.H = fr.height; d.mb_w = g.mb_w; d.n_mcus = g.n_mcus; d.nseg = g.nseg;
+      d.has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
+      d.seg_base = seg; d.pool_base = pool; d.pool_words = plan[f].pool_words;
+      d.ubuf_base = ubuf; d.ubuf_words = static_cast<uint32_t>(plan[f].ubuf_words);
+      d.chunk_base = chunk; d.max_chunks = max_chunks[f];
+      d.out_offset = fr.out_offset; d.out_capacity = fr.out_capacity;
+      d.place_base = place;
+      d.stuff_base = stuff; d.stuff_wgs = std::min(gx, max_chunks[f]);
+      const uint32_t fl = static_cast<uint32_t>(f - l.f0);
+      for (int k = 0; k < g.nseg; ++k) maps[l.k1_map + seg + k] = fl;
+      for (int k = 0; k < (g.nseg + 3) / 4; ++k) maps[l.place_map + place + k] = fl;
+      for (uint32_t k = 0; k < d.stuff_wgs; ++k) maps[l.stuff_map + stuff + k] = fl;
+      seg += static_cast<uint32_t>(g.nseg); place += static_cast<uint32_t>((g.nseg + 3) / 4); stuff += d.stuff_wgs;
+      chunk += max_chunks[f];
+      pool += (static_cast<unsigned long long>(plan[f].pool_words) + 3) & ~3ull;
+      ubuf += plan[f].ubuf_words;
+    }
+  }
+  if (header_offsets != nullptr) {
+    uint32_t* const ho = reinterpret_cast<uint32_t*>(hb + off_hoff);
+    for (int f = 0; f <= nframes; ++f) ho[f] = static_cast<uint32_t>(header_offsets[f]);
+    if (header_size > 0) memcpy(hb + off_hdr, headers, header_size);
+  }
+
+  // scratch for the largest launch
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc0 = order_on_stream(e, st)) return rc0;
+  if (e->side_pending) {                             // (pipelined mode: the call runs ordered, behind the engine's stitch)
+    if (int rcm = side_mark(e)) return rcm;
+    HIP_TRY(hipStreamWaitEvent(st, e->side_done, 0));
+  }
+  size_t n_segs = 0, n_words = 0, n_pool = 0, n_ubuf = 0, n_chunks = 0, n_f = 0, n_off = 0;
+  for (size_t li = 0; li < launches.size(); ++li) {
+    const RaggedLaunch& l = launches[li];
+    n_segs = std::max(n_segs, static_cast<size_t>(l.segs));
+    n_words = std::max(n_words, static_cast<size_t>(l.segs) * slot_of[li]);
+    n_pool = std::max(n_pool, l.pool_words);
+    n_ubuf = std::max(n_ubuf, l.ubuf_words);
+    n_chunks = std::max(n_chunks, static_cast<size_t>(l.chunks));
+    n_f = std::max(n_f, static_cast<size_t>(l.nf));
+    n_off = std::max(n_off, static_cast<size_t>(l.segs) + l.nf);
+  }
+  int rc;
+  if ((rc = e->ragged.ensure(blob.size())) || (rc = e->seg_nbits.ensure(n_segs)) || (rc = e->seg_words.ensure(n_words)) ||
+      (rc = e->pool.ensure(n_pool)) || (rc = e->pool_ctr.ensure(2 * n_f)) || (rc = e->seg_xbase.ensure(n_segs)) ||
+      (rc = e->seg_off.ensure(n_off)) || (rc = e->ubuf.ensure(n_ubuf)) || (rc = e->chunk_ff.ensure(n_chunks)) ||
+      (rc = e->chunk_off.ensure(n_chunks)) || (rc = e->frame_flags.ensure(n_f))) {
+    return rc;
+  }
+  if ((rc = upload(e, e->ragged.p, blob.data(), blob_bytes, st))) return rc;
+  if ((rc = sync_uploads(e, st))) return rc;
+  const uint8_t* const db = reinterpret_cast<const uint8_t*>(e->ragged.p);
+  const uint32_t* const dmaps = reinterpret_cast<const uint32_t*>(db + off_map);
+  e->ctr_clean_at[0] = e->ctr_clean_at[1] = nullptr;   // (the pool counters are this call's now; its K2s leave them at zero)
+  e->last_nseg = e->last_nframes = 0;                  // (sjpeg_hip_engine_entropy_bits: not after a ragged call)
+  if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
+  for (size_t li = 0; li < launches.size(); ++li) {
+    const RaggedLaunch& l = launches[li];
+    HIP_TRY(hipMemsetAsync(e->pool_ctr.p, 0, static_cast<size_t>(l.nf) * 2 * sizeof(uint32_t), st));
+    a.tables = reinterpret_cast<const DevTables*>(db + off_tab) + (tables_per_frame ? l.f0 : 0);
+    a.tables_stride = tables_per_frame ? 1 : 0;
+    a.seg_words = e->seg_words.p; a.slot_words = slot_of[li];
+    a.seg_nbits = e->seg_nbits.p; a.seg_xbase = e->seg_xbase.p;
+    a.pool = e->pool.p; a.pool_ctr = e->pool_ctr.p;
+    a.ablate = e->ablate;
+    a.rframes = reinterpret_cast<const RaggedFrame*>(db) + l.f0;
+    a.rmap = dmaps + l.k1_map;
+    if ((rc = launch_scan<kKindEncodeRagged>(yuv_mode, cls, dim3(l.segs), st, a))) return rc;
+    if (e->timing && li + 1 == launches.size()) HIP_TRY(hipEventRecord(e->ev[1], st));
+    StitchArgs s{};
+    s.nframes = l.nf;
+    s.seg_nbits = e->seg_nbits.p; s.seg_off = e->seg_off.p;
+    s.seg_words = e->seg_words.p; s.slot_words = slot_of[li];
+    s.pool = e->pool.p; s.seg_xbase = e->seg_xbase.p; s.pool_ctr = e->pool_ctr.p;
+    s.ubuf = e->ubuf.p; s.chunk_ff = e->chunk_ff.p; s.chunk_off = e->chunk_off.p;
+    s.header = db + off_hdr; s.header_size = 0;
+    s.hdr_off = header_offsets != nullptr ? reinterpret_cast<const uint32_t*>(db + off_hoff) + l.f0 : nullptr;
+    s.append_eoi = append_eoi;
+    s.out = static_cast<uint8_t*>(d_out);
+    s.sizes = reinterpret_cast<unsigned long long*>(d_sizes) + l.f0;
+    s.subs = 1; s.wide_subs = 0;
+    s.frame_flags = e->frame_flags.p;
+    s.rframes = a.rframes; s.rmap_place = dmaps + l.place_map; s.rmap_stuff = dmaps + l.stuff_map;
+    hipLaunchKernelGGL(scan_seg_offsets<true>, dim3(l.nf), dim3(kThreads), 0, st, s);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((place_segments<0, true>), dim3(l.place_wgs), dim3(kThreads), 0, st, s);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(scan_chunk_offsets<true>, dim3(l.nf), dim3(kThreads), 0, st, s);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((stuff_chunks<0, true>), dim3(l.stuff_wgs), dim3(kThreads), 0, st, s);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->timing) {
+    HIP_TRY(hipEventRecord(e->ev[2], st));
+    e->ev_valid = true;
+  }
+  return 0;
+}
+
 // ---- one frame over several GPUs: bands of consecutive segments ----------
 
 int sjpeg_hip_segment_count(int width, int height, int yuv_mode) {
@@ -1374,7 +1644,7 @@ int sjpeg_hip_encode_band_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, 
   if (tables->flags & SJPEG_HIP_QUANT_TRELLIS) rc = launch_scan<kKindEncodeTrellis>(yuv_mode, cls, dim3(nloc, 1), st, a);
   else rc = launch_scan<kKindEncode>(yuv_mode, cls, dim3(nloc, 1), st, a);
   if (rc) return rc;
-  hipLaunchKernelGGL(scan_seg_offsets, dim3(1), dim3(kThreads), 0, st, s);
+  hipLaunchKernelGGL(scan_seg_offsets<>, dim3(1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(place_segments<false>, dim3((nloc + 3) / 4, 1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
@@ -1422,12 +1692,12 @@ int sjpeg_hip_stitch_bands(sjpeg_hip_engine* e, int nbands, const uint32_t* d_wo
   const uint32_t per_wave = kSpec * kPlaceLanes;
   s.subs = static_cast<uint32_t>((band_stride_words + per_wave - 1) / per_wave);
   e->last_nseg = nbands; e->last_nframes = 1;
-  hipLaunchKernelGGL(scan_seg_offsets, dim3(1), dim3(kThreads), 0, st, s);
+  hipLaunchKernelGGL(scan_seg_offsets<>, dim3(1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
   const uint32_t units = static_cast<uint32_t>(nbands) * s.subs;
   hipLaunchKernelGGL(place_segments<false>, dim3((units + 3) / 4, 1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(scan_chunk_offsets, dim3(1), dim3(kThreads), 0, st, s);
+  hipLaunchKernelGGL(scan_chunk_offsets<>, dim3(1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
   uint32_t gx = 4096u;
   if (gx > max_chunks) gx = max_chunks;

@@ -30,7 +30,8 @@
 enum { kKindEncode = 0, kKindTap = 1, kKindHisto = 2, kKindStats = 3, kKindError = 4,
        kKindEncodeTrellis = 5, kKindStatsTrellis = 6,     // the same two with trellis quantization
        kKindEncodeReplay = 7,     // entropy-code the coefficients a statistics pass left behind
-       kKindStatsCoef = 8 };      // statistics from the DCT coefficients a histogram pass left behind
+       kKindStatsCoef = 8,        // statistics from the DCT coefficients a histogram pass left behind
+       kKindEncodeRagged = 9 };   // the encode kind over frames of different sizes (flat grid, per-frame descriptors)
 constexpr int kHistoWords = 2 * 64 * 32;          // words of u8 counters [2][64][128] a workgroup bins one segment into (LDS)
 // The histogram kind is PERSISTENT: a workgroup bins the segments seg, seg + gridDim.x, ... of its frame and leaves ONE
 // partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).
@@ -74,16 +75,20 @@ __device__ __forceinline__ void race_point(int code, int n) {
 #define SJPEG_HISTO_WGS 3          // workgroups per CU the histogram kind is compiled for (A/B: 4)
 #endif
 template <int MODE, int KINDX, int SRC>
-constexpr bool kCompactLds = (KINDX == kKindEncode || KINDX == kKindEncodeReplay || KINDX == kKindStats || KINDX == kKindStatsCoef);
+constexpr bool kCompactLds = (KINDX == kKindEncode || KINDX == kKindEncodeReplay || KINDX == kKindStats || KINDX == kKindStatsCoef ||
+                              KINDX == kKindEncodeRagged);
 
 template <int MODE, int KINDX, int SRC>
-__global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a) {
+__global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
+  // The ragged kind is the encode kind but for its prologue: its workgroup's frame and segment come from the launch's
+  // segment -> frame map, the frame's geometry and scratch bases from its descriptor (ragged_scan_view)
+  constexpr bool RAGGED = (KINDX == kKindEncodeRagged);
   constexpr bool TRELLIS = (KINDX == kKindEncodeTrellis || KINDX == kKindStatsTrellis);
   constexpr bool REPLAY = (KINDX == kKindEncodeReplay);
   // the block's unquantized coefficients come from the histogram pass of the same call (the adaptive methods run
   // one before they know the quantizer): no second colour conversion / DCT
   constexpr bool COEF = (KINDX == kKindStatsCoef);
-  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay) ? kKindEncode : (KINDX == kKindStatsTrellis || COEF) ? kKindStats : KINDX;
+  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || RAGGED) ? kKindEncode : (KINDX == kKindStatsTrellis || COEF) ? kKindStats : KINDX;
   constexpr bool COMPACT = kCompactLds<MODE, KINDX, SRC>;
   // The statistics kinds (but the trellis one) count a block's symbols straight out of the thread's registers, zig-zag
   // position by position -- no entries in LDS, no parts, no sort, no walk (below, "kKindStats, direct")
@@ -113,7 +118,10 @@ __global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcR
   typedef uint16_t __attribute__((may_alias)) u16_may_alias;
 
   const int tid = threadIdx.x;
-  const int frame = blockIdx.y;
+  int seg0 = blockIdx.x;
+  // (a copy, not a reference: the other kinds read the kernel argument as before -- the same code to the instruction)
+  const ScanArgs a = RAGGED ? ragged_scan_view(a_in, &seg0) : a_in;
+  const int frame = RAGGED ? 0 : blockIdx.y;
   // the histogram kind's 16-bit counters, two to a register: the 8-bit counters of words 16 * tid .. 16 * tid + 15 of
   // the LDS histogram (overflow words not counted), bytes 0 / 2 in the even and bytes 1 / 3 in the odd register (no
   // other kind has them)
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcR
     for (int i = 0; i < 32; ++i) hacc[i] = 0;
   }
   // every kind but the histogram takes ONE trip (gridDim.x = the frame's segments); the body ends with a return
-  for (int seg = blockIdx.x;; seg += gridDim.x) {
+  for (int seg = seg0;; seg += gridDim.x) {
   auto stamp = [&](int k) {
     if (a.stamps != nullptr && tid == 0) {
       a.stamps[(static_cast<size_t>(frame) * a.nseg + seg) * 8 + k] =

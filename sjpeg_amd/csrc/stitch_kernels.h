@@ -45,7 +45,33 @@ struct StitchArgs {
   // workgroup leaves the total and the overrun flag behind for K5, whose first workgroup then zeroes the pool's counters;
   // K1 has cleared the frame's 0xFF counters): no K2 launch either -- K1, K3, K5
   int fused_k2;
+  // ragged launches: the frames' descriptors (scan_device.h) and the workgroup -> frame maps of K3 and K5 (else NULL)
+  const RaggedFrame* rframes = nullptr;
+  const uint32_t* rmap_place = nullptr;
+  const uint32_t* rmap_stuff = nullptr;
 };
+
+// The stitch kernels' view of frame f of a ragged launch: its segment count, output place and capacity, every scratch
+// pointer moved to the frame's base -- the kernel then runs as frame 0 of a uniform launch (no fused forms, no packed
+// output, no bands).
+__device__ __forceinline__ StitchArgs ragged_stitch_view(const StitchArgs& in, uint32_t f) {
+  const RaggedFrame& d = in.rframes[f];
+  StitchArgs v = in;
+  v.nseg = d.nseg; v.nframes = 1;
+  v.seg_nbits = in.seg_nbits + d.seg_base;
+  v.seg_off = in.seg_off + d.seg_base + f;
+  v.seg_words = in.seg_words + static_cast<size_t>(d.seg_base) * in.slot_words;
+  v.pool = in.pool + d.pool_base; v.pool_words = d.pool_words;
+  v.seg_xbase = in.seg_xbase + d.seg_base;
+  v.pool_ctr = in.pool_ctr + 2 * f;
+  v.ubuf = in.ubuf + d.ubuf_base; v.ubuf_words = d.ubuf_words;
+  v.chunk_ff = in.chunk_ff + d.chunk_base; v.chunk_off = in.chunk_off + d.chunk_base; v.max_chunks = d.max_chunks;
+  if (in.hdr_off != nullptr) v.hdr_off = in.hdr_off + f;
+  v.out = in.out + d.out_offset; v.out_stride = d.out_capacity;
+  v.sizes = in.sizes + f;
+  v.frame_flags = in.frame_flags + f;
+  return v;
+}
 // (frame_flags is written by K2 -- or by K3's first workgroup when K2 runs inside K3 -- from pool_ctr, and only when
 // BOTH are there: a call with flags but no pool has no overrun to report, and nothing wrote the flags -- ADVICE r05)
 __device__ __forceinline__ bool frame_overran(const StitchArgs& a, int frame) {
@@ -53,9 +79,11 @@ __device__ __forceinline__ bool frame_overran(const StitchArgs& a, int frame) {
   return a.frame_flags != nullptr ? a.frame_flags[frame] != 0u : a.pool_ctr[2 * frame + 1] != 0u;
 }
 
-__global__ __launch_bounds__(kThreads) void scan_seg_offsets(const StitchArgs a) {
+template <bool RAGGED = false>
+__global__ __launch_bounds__(kThreads) void scan_seg_offsets(const StitchArgs a_in) {
   __shared__ uint32_t scratch[16];
-  const int frame = blockIdx.x;
+  const StitchArgs a = RAGGED ? ragged_stitch_view(a_in, blockIdx.x) : a_in;
+  const int frame = RAGGED ? 0 : blockIdx.x;
   const uint32_t* nb = a.seg_nbits + static_cast<size_t>(frame) * a.nseg;
   unsigned long long* off = a.seg_off + static_cast<size_t>(frame) * (a.nseg + 1);
   // (a band is shorter than 2^32 bits: sjpeg_hip_stitch_bands checks its capacity)
@@ -151,15 +179,19 @@ constexpr int kWideSpec = 3;                                // wide form: specul
 struct __attribute__((packed, aligned(4))) Words4 { uint32_t w[4]; };   // 16 bytes at any word address
 constexpr int kFusedSegs = 2048;                            // K2 inside K3: frames of up to 2048 segments (FUSED = 1)
 constexpr int kFusedSegsBig = 16384;                        // FUSED = 2, ONE large frame (8K 4:4:4 = 6172 segments): sums on demand
-template <int FUSED>
-__global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a) {
+template <int FUSED, bool RAGGED = false>
+__global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a_in) {
   __shared__ uint32_t off_lds[FUSED == 1 ? kFusedSegs + 1 : 16];   // (32 bits: a fused frame has less than 2^32 bits of stream)
   __shared__ uint32_t scratch_k2[16];
-  const int frame = blockIdx.y;
+  // ragged: the frame of this workgroup of the flat grid from the map, its first workgroup from the descriptor
+  const uint32_t rf = RAGGED ? a_in.rmap_place[blockIdx.x] : 0u;
+  const uint32_t bx = RAGGED ? blockIdx.x - a_in.rframes[rf].place_base : blockIdx.x;
+  const StitchArgs a = RAGGED ? ragged_stitch_view(a_in, rf) : a_in;
+  const int frame = RAGGED ? 0 : blockIdx.y;
   const uint32_t* const nb_f = a.seg_nbits + static_cast<size_t>(frame) * a.nseg;
   // FUSED = 2: the first segment this workgroup places; off_lds[0..7] = offsets of segments sc_first .. sc_first + 7,
   // off_lds[8] = the frame's total
-  const int sc_first = static_cast<int>((blockIdx.x * (kThreads / 64)) / a.subs);
+  const int sc_first = static_cast<int>((bx * (kThreads / 64)) / a.subs);
   if (FUSED == 1) {
     // K2's scan, by every workgroup for itself (eight lengths per thread, one scan; the sums stay below 2^32: such a
     // frame has at most 8 MiB of stream); the loads go out with the speculative ones below
@@ -178,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a) {
     for (int j = 0; j < kRun; ++j) { off_lds[i0 + j] = at; at += v[j]; }
     if (threadIdx.x == 0) {
       off_lds[a.nseg] = total;
-      if (blockIdx.x == 0) {
+      if (bx == 0) {
         a.seg_off[static_cast<size_t>(frame) * (a.nseg + 1) + a.nseg] = total;      // (K5 reads the total here)
         if (a.frame_flags != nullptr && a.pool_ctr != nullptr) a.frame_flags[frame] = a.pool_ctr[2 * frame + 1];
       }
@@ -207,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a) {
     }
     if (threadIdx.x == 8) {
       off_lds[8] = all_total;
-      if (blockIdx.x == 0) {
+      if (bx == 0) {
         a.seg_off[static_cast<size_t>(frame) * (a.nseg + 1) + a.nseg] = all_total;  // (K5 reads the total here)
         if (a.frame_flags != nullptr && a.pool_ctr != nullptr) a.frame_flags[frame] = a.pool_ctr[2 * frame + 1];
       }
@@ -216,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a) {
   }
   // a wave takes words [sub * kSpec * 64, ...) of one segment; normal segments have one wave
   // (subs == 1, the loop below takes the rare longer rest), whole bands are cut into many
-  const uint32_t unit = blockIdx.x * (kThreads / kPlaceLanes) + (threadIdx.x >> 6);
+  const uint32_t unit = bx * (kThreads / kPlaceLanes) + (threadIdx.x >> 6);
   const int sc0 = static_cast<int>(unit / a.subs);
   const uint32_t ibase = (unit % a.subs) * (a.wide_subs ? kWideSpec * 256u : kSpec * kPlaceLanes);
   if (sc0 >= a.nseg) return;
@@ -465,9 +497,11 @@ __device__ __forceinline__ uint8_t* frame_out(const StitchArgs& a, int frame) {
 // ------------------------------------------------------------------------------------
 // K4: per frame, exclusive scan of per-chunk 0xFF counts; final stream size
 
-__global__ __launch_bounds__(kThreads) void scan_chunk_offsets(const StitchArgs a) {
+template <bool RAGGED = false>
+__global__ __launch_bounds__(kThreads) void scan_chunk_offsets(const StitchArgs a_in) {
   __shared__ uint32_t scratch[16];
-  const int frame = blockIdx.x;
+  const StitchArgs a = RAGGED ? ragged_stitch_view(a_in, blockIdx.x) : a_in;
+  const int frame = RAGGED ? 0 : blockIdx.x;
   const unsigned long long T = a.seg_off[static_cast<size_t>(frame) * (a.nseg + 1) + a.nseg];
   const unsigned long long U = (T + 7) >> 3;
   unsigned long long nch64 = (U + kChunkBytes - 1) / kChunkBytes;
@@ -566,14 +600,18 @@ __global__ __launch_bounds__(kThreads) void pack_frame_edges(const StitchArgs a)
 // ds_write2_b32 instead of the sixteen byte stores of the general path, which the others keep.
 constexpr uint32_t kFusedChunks = 2048;                     // K4 inside K5: frames of up to 8 MiB of un-stuffed stream (FUSED = 1)
 constexpr uint32_t kFusedChunksBig = 1u << 17;              // FUSED = 2, ONE large frame of up to 512 MiB of stream: sums on demand
-template <int FUSED>
-__global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a) {
+template <int FUSED, bool RAGGED = false>
+__global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a_in) {
   constexpr uint32_t kCapChunks = FUSED == 2 ? kFusedChunksBig : kFusedChunks;
   __shared__ uint32_t scratch[16];
   __shared__ __attribute__((aligned(16))) uint8_t stage[2 * kChunkBytes + 64];
   __shared__ uint32_t fused_off[FUSED == 1 ? kFusedChunks : 1];   // FUSED = 1: 0xFF bytes in front of every chunk of the frame
   uint32_t big_off = 0;                                      // FUSED = 2: 0xFF bytes in front of this workgroup's chunk at hand
-  const int frame = blockIdx.y;
+  // ragged: the frame from the map; the frame's own workgroups (bx of gdx_of(), below) stride over its chunks
+  const uint32_t rf = RAGGED ? a_in.rmap_stuff[blockIdx.x] : 0u;
+  const uint32_t bx = RAGGED ? blockIdx.x - a_in.rframes[rf].stuff_base : blockIdx.x;
+  const StitchArgs a = RAGGED ? ragged_stitch_view(a_in, rf) : a_in;
+  const int frame = RAGGED ? 0 : blockIdx.y;
   const unsigned long long T = a.seg_off[static_cast<size_t>(frame) * (a.nseg + 1) + a.nseg];
   const unsigned long long U = (T + 7) >> 3;
   const uint32_t nchunks = static_cast<uint32_t>((U + kChunkBytes - 1) / kChunkBytes);
@@ -608,7 +646,7 @@ __global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a) {
       for (uint32_t i = threadIdx.x; i < nch; i += kThreads) {
         const uint32_t v = ff[i];
         all += v;
-        front += i < blockIdx.x ? v : 0u;
+        front += i < bx ? v : 0u;
       }
       (void)wg_exclusive_scan<kThreads>(front, scratch, &big_off);
       (void)wg_exclusive_scan<kThreads>(all, scratch, &total);
@@ -616,7 +654,7 @@ __global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a) {
     const unsigned long long body = U + total;
     const unsigned long long size = hsize + body + (a.append_eoi ? 2 : 0);
     const bool fits = nchunks <= kCapChunks && size <= a.out_stride && ((U + 3) >> 2) + 1 <= a.ubuf_words && !frame_overran(a, frame);
-    if (blockIdx.x == 0) {
+    if (bx == 0) {
       if (threadIdx.x == 0) a.sizes[frame] = fits ? size : 0ull;
       if (a.fused_k2 && a.pool_ctr != nullptr && threadIdx.x == 0) {    // (K3, their last reader, is through)
         const_cast<uint32_t*>(a.pool_ctr)[2 * frame] = 0u;
@@ -655,16 +693,18 @@ __global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a) {
   uint32_t behind_next;
   int valid_next;
   unsigned long long off_next;
-  fetch(blockIdx.x, &q_next, &behind_next, &valid_next, &off_next);
-  for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+  // (read where it is used, as gridDim.x was: the uniform forms keep their code)
+  auto gdx_of = [&]() -> uint32_t { return RAGGED ? a_in.rframes[rf].stuff_wgs : gridDim.x; };
+  fetch(bx, &q_next, &behind_next, &valid_next, &off_next);
+  for (uint32_t chunk = bx; chunk < nchunks; chunk += gdx_of()) {
     const uint4 q = q_next;
     const uint32_t behind = behind_next;
     const int valid = valid_next;
     const unsigned long long chunk_off = FUSED == 2 ? static_cast<unsigned long long>(big_off) : off_next;
-    fetch(chunk + gridDim.x, &q_next, &behind_next, &valid_next, &off_next);
-    if (FUSED == 2 && chunk + gridDim.x < nchunks) {          // (uniform) the counts between this chunk and the next one
+    fetch(chunk + gdx_of(), &q_next, &behind_next, &valid_next, &off_next);
+    if (FUSED == 2 && chunk + gdx_of() < nchunks) {           // (uniform) the counts between this chunk and the next one
       uint32_t mine = 0, step;
-      for (uint32_t i = chunk + threadIdx.x; i < chunk + gridDim.x; i += kThreads) mine += ff_f[i];
+      for (uint32_t i = chunk + threadIdx.x; i < chunk + gdx_of(); i += kThreads) mine += ff_f[i];
       (void)wg_exclusive_scan<kThreads>(mine, scratch, &step);
       big_off += step;
     }
