@@ -367,7 +367,7 @@ int sjpeg_hip_scan_symbol_stats_multi(sjpeg_hip_engine* engine, const sjpeg_hip_
 /* A RAGGED batch: pictures of different sizes in one call -- a gallery's thumbnails, an upload queue, a dataset being
  * re-encoded.  Frame f has its own planes, row strides, width and height (1..65535 each) and its own place in d_out:
  * [out_offset, out_offset + out_capacity).  The frames share the source format, the yuv_mode and method 0 (fixed
- * quantizer, default Huffman codes); tables_per_frame = 0: tables[0] codes every frame, 1: frame f is coded with
+ * quantizer, default Huffman codes; the other methods: sjpeg_hip_encode_ragged_batch_src below); tables_per_frame = 0: tables[0] codes every frame, 1: frame f is coded with
  * tables[f] (per-frame quality).  headers / header_offsets[nframes + 1] as sjpeg_hip_encode_scan_multi() (both NULL:
  * no headers).  The bytes of frame f are what sjpeg_hip_encode_scan_src() makes of that picture alone.
  *   d_sizes[f] = frame f's size, or 0 when it does not fit its out_capacity (every other frame is still exact; nothing
@@ -393,6 +393,39 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mo
                                 const sjpeg_hip_scan_tables* tables, int tables_per_frame,
                                 const void* headers, const size_t* header_offsets /*[nframes+1]*/,
                                 int append_eoi, void* d_out, uint64_t* d_sizes, void* stream);
+
+/* The two analysis passes over a ragged batch (frames[] as above; out_offset / out_capacity are ignored).
+ *   sjpeg_hip_scan_histogram_ragged_src: d_hist[nframes][2][64][128] (uint32), frame f's what
+ *   sjpeg_hip_scan_histogram_src() makes of that picture alone.  sjpeg_hip_scan_symbol_stats_ragged_src:
+ *   d_freq[nframes][2][272] (uint32), frame f's what sjpeg_hip_scan_symbol_stats_src() makes of that picture alone with
+ *   tables[f] (tables_per_frame = 1) or tables[0] (0).  Asynchronous on `stream`; in pipelined mode they run ordered.
+ *   The partials of a batch that would pass SJPEG_HIP_SCRATCH_LIMIT_BYTES go in several launches of consecutive frames.
+ *   SJPEG_HIP_EINVAL (the message names the frame) as sjpeg_hip_encode_ragged_src(). */
+int sjpeg_hip_scan_histogram_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, uint32_t* d_hist,
+                                        void* stream);
+int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                           const sjpeg_hip_scan_tables* tables, int tables_per_frame,
+                                           uint32_t* d_freq, void* stream);
+
+/* A RAGGED batch with the reference's per-picture analysis, methods 0..6: the defaults (method 4) of SjpegCompress()
+ * over pictures of different sizes.  Complete JPEGs, EOI included: frame f's bytes are what
+ * sjpeg_hip_encode_batch_src() makes of that picture alone with the starting matrix quant[f] (quant_per_frame = 1:
+ * per-frame quality) or quant[0] (0), and the same min_quant, q_bias, method and qdelta limits.  Frame f goes to
+ * [out_offset, out_offset + out_capacity) of d_out; d_sizes[f] = 0 when it does not fit (nothing written, the others
+ * exact) -- sjpeg_hip_frame_bound(w, h, yuv_mode, 2048) is always enough.  The engine builds every frame's header from
+ * its own size, adapted matrices and optimised codes.  Method 0 is one sjpeg_hip_encode_ragged_src() call.
+ *   The host waits where sjpeg_hip_encode_batch_src() does -- for the adapted matrices (methods 3..6), for the symbol
+ *   counts (1, 2, 4, 5, 6) --; the encode is asynchronous on `stream`.  In pipelined mode the call runs ordered.
+ *   SJPEG_HIP_EINVAL: every check of sjpeg_hip_encode_ragged_src(), a NULL quant, a method outside 0..6 (the trellis
+ *   methods go through the host API) and qdelta_max outside -12..12. */
+int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                      const uint8_t (*quant)[2][64], int quant_per_frame,
+                                      const uint8_t* min_quant /*[2][64] or NULL*/, int q_bias, int method,
+                                      int qdelta_max_luma, int qdelta_max_chroma,
+                                      void* d_out, uint64_t* d_sizes, void* stream);
 
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that

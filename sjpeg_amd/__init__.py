@@ -238,6 +238,16 @@ def lib() -> C.CDLL:
                                               C.c_int, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
     L.sjpeg_hip_encode_ragged_src.restype = C.c_int
+    L.sjpeg_hip_scan_histogram_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                      C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_scan_histogram_ragged_src.restype = C.c_int
+    L.sjpeg_hip_scan_symbol_stats_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_scan_symbol_stats_ragged_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_batch_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_encode_ragged_batch_src.restype = C.c_int
     _lib = L
     return L
 
@@ -269,6 +279,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_comm_unique_id", "sjpeg_hip_comm_create", "sjpeg_hip_comm_create_local", "sjpeg_hip_comm_adopt", "sjpeg_hip_comm_destroy",
     "sjpeg_hip_comm_rank", "sjpeg_hip_comm_world", "sjpeg_hip_gather_rows", "sjpeg_hip_gather_bytes",
     "sjpeg_hip_gather_streams", "sjpeg_hip_encode_scan_packed_src", "sjpeg_hip_encode_ragged_src",
+    "sjpeg_hip_scan_histogram_ragged_src", "sjpeg_hip_scan_symbol_stats_ragged_src", "sjpeg_hip_encode_ragged_batch_src",
 ]
 
 
@@ -913,7 +924,6 @@ class Engine:
         take.  Returns (out, sizes, offsets): out a flat uint8 CUDA tensor, frame k's JPEG at out[offsets[k]:
         offsets[k] + sizes[k]], sizes an int64 CUDA tensor (0: the frame did not fit), offsets a list of ints.
         Asynchronous on the current torch stream."""
-        import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged: one entry of planes_per_frame and dims per frame, at least one frame")
@@ -922,34 +932,10 @@ class Engine:
             raise SjpegError("encode_ragged: one ScanTables per frame")
         if headers is not None and len(headers) != n:
             raise SjpegError("encode_ragged: one header per frame")
-        frames = (RaggedFrame * n)()
         if capacities is None:
             capacities = [frame_bound(w, h, yuv_mode, 0 if headers is None else len(headers[k]))
                           for k, (w, h) in enumerate(dims)]
-        if offsets is None:
-            offsets, at = [], 0
-            for c in capacities:
-                offsets.append(at)
-                at += (int(c) + 15) & ~15
-            total = at
-        else:
-            total = max(int(o) + int(c) for o, c in zip(offsets, capacities))
-        dev = next((p.device for fr in planes_per_frame for p in fr if not isinstance(p, tuple)),
-                   torch.device("cuda", torch.cuda.current_device()))
-        if out is None:
-            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        if sizes is None:
-            sizes = torch.zeros(n, dtype=torch.int64, device=dev)
-        for k in range(n):
-            fr = frames[k]
-            for i, p in enumerate(planes_per_frame[k]):
-                if isinstance(p, tuple):                 # (device address of row 0, row stride): bottom-up rows too
-                    fr.plane[i], fr.row_stride[i] = int(p[0]), int(p[1])
-                else:
-                    fr.plane[i] = p.data_ptr()
-                    fr.row_stride[i] = p.stride(0) * p.element_size()
-            fr.width, fr.height = int(dims[k][0]), int(dims[k][1])
-            fr.out_offset, fr.out_capacity = int(offsets[k]), int(capacities[k])
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         if per_frame:
             tarr = (ScanTables * n)(*tables)
         else:
@@ -968,15 +954,125 @@ class Engine:
                   "sjpeg_hip_encode_ragged_src")
         return out, sizes, list(offsets)
 
+    def scan_histogram_ragged(self, fmt, planes_per_frame, dims, yuv_mode):
+        """sjpeg_hip_scan_histogram_ragged_src: the adaptive-quantization histograms of pictures of different sizes in
+        one call (planes_per_frame, dims as encode_ragged).  Returns an int32 CUDA tensor [F, 2, 64, 128] (uint32 counts),
+        frame k's what scan_histogram_source makes of it alone.  Asynchronous on the current torch stream."""
+        import torch
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        out = torch.zeros((len(dims), 2, 64, 128), dtype=torch.int32, device=_ragged_device(planes_per_frame))
+        self._chk(lib().sjpeg_hip_scan_histogram_ragged_src(self._h, fmt, yuv_mode, len(dims), frames, out.data_ptr(),
+                                                            self._stream()),
+                  "sjpeg_hip_scan_histogram_ragged_src")
+        return out
 
-def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None):
+    def scan_symbol_stats_ragged(self, fmt, planes_per_frame, dims, yuv_mode, tables):
+        """sjpeg_hip_scan_symbol_stats_ragged_src: the symbol counts of pictures of different sizes in one call, with one
+        ScanTables for every frame or a list of one per frame.  Returns an int32 CUDA tensor [F, 2, 272] (uint32 counts),
+        frame k's what scan_symbol_stats_source makes of it alone.  Asynchronous on the current torch stream."""
+        import torch
+        n = len(dims)
+        per_frame = isinstance(tables, (list, tuple))
+        if per_frame and len(tables) != n:
+            raise SjpegError("scan_symbol_stats_ragged: one ScanTables per frame")
+        tarr = (ScanTables * n)(*tables) if per_frame else (ScanTables * 1)(tables)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        out = torch.zeros((n, 2, 272), dtype=torch.int32, device=_ragged_device(planes_per_frame))
+        self._chk(lib().sjpeg_hip_scan_symbol_stats_ragged_src(self._h, fmt, yuv_mode, n, frames, C.cast(tarr, C.c_void_p),
+                                                               int(per_frame), out.data_ptr(), self._stream()),
+                  "sjpeg_hip_scan_symbol_stats_ragged_src")
+        return out
+
+    def encode_ragged_batch(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
+                            dmax_luma=12, dmax_chroma=1, capacities=None, out=None, offsets=None, sizes=None):
+        """sjpeg_hip_encode_ragged_batch_src: the reference's per-picture analysis (methods 0..6) over pictures of
+        different sizes in one call -- complete JPEGs.  planes_per_frame, dims, capacities, offsets, out, sizes as
+        encode_ragged (capacities default: frame_bound(w, h, yuv_mode, 2048)); quant: one [2][64] starting matrix for
+        every frame or a list of one per frame.  Frame k's bytes are what encode_batch makes of it alone.  Returns (out,
+        sizes, offsets) as encode_ragged; the host waits inside for the analysis, the encode is asynchronous."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged_batch: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(quant, (list, tuple))
+        if per_frame and len(quant) != n:
+            raise SjpegError("encode_ragged_batch: one starting matrix per frame")
+        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+        if capacities is None:
+            capacities = [frame_bound(w, h, yuv_mode, 2048) for (w, h) in dims]
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
+        self._chk(lib().sjpeg_hip_encode_ragged_batch_src(self._h, fmt, yuv_mode, n, frames, q.ctypes.data, int(per_frame),
+                                                          mq.ctypes.data if mq is not None else None, q_bias, int(method),
+                                                          dmax_luma, dmax_chroma, out.data_ptr(), sizes.data_ptr(),
+                                                          self._stream()),
+                  "sjpeg_hip_encode_ragged_batch_src")
+        return out, sizes, list(offsets)
+
+
+def _ragged_device(planes_per_frame):
+    import torch
+    return next((p.device for fr in planes_per_frame for p in fr if not isinstance(p, tuple)),
+                torch.device("cuda", torch.cuda.current_device()))
+
+
+def _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes):
+    """The sjpeg_hip_ragged_frame array of a ragged call (planes_per_frame, dims as Engine.encode_ragged) and, where
+    capacities are given, its output: offsets (default: the capacities back to back, 16-byte aligned), out and sizes
+    (made on the pictures' device where None).  Returns (frames, out, sizes, offsets)."""
+    import torch
+    n = len(dims)
+    if n == 0 or len(planes_per_frame) != n:
+        raise SjpegError("ragged call: one entry of planes_per_frame and dims per frame, at least one frame")
+    frames = (RaggedFrame * n)()
+    if capacities is not None:
+        if offsets is None:
+            offsets, at = [], 0
+            for c in capacities:
+                offsets.append(at)
+                at += (int(c) + 15) & ~15
+            total = at
+        else:
+            total = max(int(o) + int(c) for o, c in zip(offsets, capacities))
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if sizes is None:
+            sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+    for k in range(n):
+        fr = frames[k]
+        for i, p in enumerate(planes_per_frame[k]):
+            if isinstance(p, tuple):                 # (device address of row 0, row stride): bottom-up rows too
+                fr.plane[i], fr.row_stride[i] = int(p[0]), int(p[1])
+            else:
+                fr.plane[i] = p.data_ptr()
+                fr.row_stride[i] = p.stride(0) * p.element_size()
+        fr.width, fr.height = int(dims[k][0]), int(dims[k][1])
+        if capacities is not None:
+            fr.out_offset, fr.out_capacity = int(offsets[k]), int(capacities[k])
+    return frames, out, sizes, offsets
+
+
+def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
+                  dmax_luma=12, dmax_chroma=1):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
-    quality is one float or one per image.  Method 0; frame k's bytes are what encode_device makes of it alone."""
+    quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
+    alone.  Methods 1..6 (4: the reference's defaults) with min_quant, q_bias and the qdelta limits: what
+    encode_device_method makes of it alone."""
     import torch
+    method = int(method)
+    if method in (7, 8):
+        raise SjpegError("encode_images: trellis methods 7 and 8 go through the host API (SjpegEncode / sjpeg::Encode)")
+    if method < 0 or method > 8:
+        raise SjpegError(f"encode_images: method {method} is not one of 0..6")
     images = list(images)
     if not images:
         raise SjpegError("encode_images: no images")
+    n = len(images)
+    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    if len(qs) != n:
+        raise SjpegError("encode_images: one quality per image")
     dev = None
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
@@ -990,11 +1086,22 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None):
             dev = im.device
         elif im.device != dev:
             raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
-    n = len(images)
-    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
-    if len(qs) != n:
-        raise SjpegError("encode_images: one quality per image")
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
+    if method != 0:
+        made = {}
+        for q in qs:
+            if float(q) not in made:
+                m = np.zeros((2, 64), np.uint8)
+                lib().sjpeg_hip_quality_matrices(float(q), m.ctypes.data)
+                made[float(q)] = m
+        quant = [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
+        with torch.cuda.device(dev):
+            out, sizes, offs = eng.encode_ragged_batch(SRC_RGB, planes, dims, yuv_mode, quant, method, min_quant, q_bias,
+                                                       dmax_luma, dmax_chroma)
+            eng.wait()                           # (pipelined mode: the output is complete after this)
+            return _fetch_ragged(out, sizes, offs)
     made = {}
     tables, headers = [], []
     for k, im in enumerate(images):
@@ -1005,8 +1112,6 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None):
         tables.append(t)
         headers.append(make_header(int(im.shape[1]), int(im.shape[0]), yuv_mode, qm))
     per_frame = len(made) > 1
-    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     with torch.cuda.device(dev):
         out, sizes, offs = eng.encode_ragged(SRC_RGB, planes, dims, yuv_mode, tables if per_frame else tables[0],
                                              headers)

@@ -104,12 +104,17 @@ struct alignas(16) RaggedFrame {
   uint32_t chunk_base, max_chunks;              // chunk_ff / chunk_off
   uint32_t place_base;     // first workgroup of K3 (four segments each)
   uint32_t stuff_base, stuff_wgs;               // first workgroup of K5, and how many stride over the frame's chunks
+  // histogram launches (kKindHistoRagged) count persistent groups where the others count segments: seg_base is the
+  // frame's first group (and partial), hgroups how many it has -- its stride over its segments
+  uint32_t hgroups;
 };
+static_assert(sizeof(RaggedFrame) == 144, "RaggedFrame: hgroups lies in what was the padding");
 
 // K1's view of the frame a ragged workgroup codes: ScanArgs with the frame's own geometry and planes, every scratch
 // pointer moved to the frame's base -- the kernel then runs as frame 0 of a uniform launch.  Two dependent scalar loads
-// (map, then descriptor) per workgroup; *seg = the segment inside the frame.
-__device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg) {
+// (map, then descriptor) per workgroup; *seg = the segment inside the frame.  partial_words: words of the per-segment
+// partial (the statistics kind: kStatsWords; 0: the partials stay where they are).
+__device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg, int partial_words = 0) {
   const uint32_t f = in.rmap[blockIdx.x];
   const RaggedFrame& d = in.rframes[f];
   ScanArgs v = in;
@@ -123,6 +128,16 @@ __device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* se
   v.pool_words = d.pool_words;
   v.pool_ctr = in.pool_ctr + 2 * f;
   *seg = static_cast<int>(blockIdx.x - d.seg_base);
+  if (partial_words != 0) v.partial = in.partial + static_cast<size_t>(d.seg_base) * partial_words;
+  return v;
+}
+
+// The histogram kind's view (kKindHistoRagged): its launch's map has an entry per persistent GROUP, and seg_base counts
+// groups (RaggedFrame).  *seg = the group inside the frame, its first segment; *groups = the frame's group count, its
+// stride over the segments.  The partials stay where they are: group blockIdx.x of the launch leaves partial blockIdx.x.
+__device__ __forceinline__ ScanArgs ragged_histo_view(const ScanArgs& in, int* seg, int* groups) {
+  ScanArgs v = ragged_scan_view(in, seg);
+  *groups = static_cast<int>(in.rframes[in.rmap[blockIdx.x]].hgroups);
   return v;
 }
 

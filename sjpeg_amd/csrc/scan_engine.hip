@@ -904,9 +904,9 @@ static int scan_statistics(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int
   if (histogram) {
     static_assert(kThreads == kScanThreads, "reduce_partials16: a thread per thread of the scan kernel");
     // (the partials of a launch lie back to back: frame f of this launch at f * groups * kHistoPartialWords)
-    hipLaunchKernelGGL(reduce_partials16, grid, dim3(kThreads), 0, rs, reinterpret_cast<const uint4*>(partial), groups, d_out);
+    hipLaunchKernelGGL(reduce_partials16<>, grid, dim3(kThreads), 0, rs, reinterpret_cast<const uint4*>(partial), groups, d_out);
   } else {
-    hipLaunchKernelGGL(reduce_partials, grid, dim3(kThreads), 0, rs, partial, g.nseg, words, d_out);
+    hipLaunchKernelGGL(reduce_partials<>, grid, dim3(kThreads), 0, rs, partial, g.nseg, words, d_out);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1320,12 +1320,79 @@ struct RaggedLaunch {
 
 inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
 
+// The source format of a ragged call (as prepare_scan): the kernel's per-format fields in *a (zeroed first), the source
+// class and the number of planes.  who: the entry point, for the messages.
+int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a, int* cls, int* nplanes) {
+  memset(a, 0, sizeof(*a));
+  int implied = 0;
+  *cls = kSrcPlanes; *nplanes = 1;
+  switch (format) {
+    case SJPEG_HIP_SRC_RGB: *cls = kSrcRgb24; break;
+    case SJPEG_HIP_SRC_BGRA: *cls = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
+    case SJPEG_HIP_SRC_RGBA: *cls = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
+    case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
+    case SJPEG_HIP_SRC_YUV444: *nplanes = 3; implied = SJPEG_HIP_YUV444; a->cstep = 1; break;
+    case SJPEG_HIP_SRC_YUV420: *nplanes = 3; implied = SJPEG_HIP_YUV420; a->cstep = 1; break;
+    case SJPEG_HIP_SRC_NV12:
+    case SJPEG_HIP_SRC_NV21:
+      *nplanes = 2; implied = SJPEG_HIP_YUV420; a->cstep = 2;
+      a->uoff = (format == SJPEG_HIP_SRC_NV12) ? 0 : 1;
+      a->voff = 1 - a->uoff;
+      break;
+    default: return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  }
+  if (yuv_mode != SJPEG_HIP_YUV420 && yuv_mode != SJPEG_HIP_YUV444 && yuv_mode != SJPEG_HIP_YUV400) {
+    return fail(SJPEG_HIP_EINVAL, who + ": bad yuv_mode");
+  }
+  if (implied != 0 && yuv_mode != implied) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format");
+  return 0;
+}
+
+// Every frame of a ragged call checked (the message names the frame); its geometry into (*geo)[f].  out_ranges: the
+// frames' output ranges are checked too (the encodes; the analysis passes ignore them).
+int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes, int nframes,
+                  const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo) {
+  geo->resize(nframes);
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    const std::string w = who + ": frame " + std::to_string(f) + ": ";
+    if (!frame_geo(fr.width, fr.height, yuv_mode, &(*geo)[f])) {
+      return fail(SJPEG_HIP_EINVAL, w + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
+    }
+    const int64_t W = fr.width, cw = (W + 1) / 2;
+    int64_t need[3] = {W, W, W};
+    if (format == SJPEG_HIP_SRC_RGB) need[0] = 3 * W;
+    else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
+    else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
+    else if (format == SJPEG_HIP_SRC_NV12 || format == SJPEG_HIP_SRC_NV21) need[1] = 2 * cw;
+    for (int i = 0; i < nplanes; ++i) {
+      if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, w + "null plane pointer");
+      const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
+      if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, w + "|row_stride| smaller than a row of the plane");
+    }
+    if (out_ranges && fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, w + "out_offset + out_capacity overflows");
+  }
+  return 0;
+}
+
+// a frame's planes and geometry in its descriptor
+void ragged_geometry(const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, int nplanes, RaggedFrame* d) {
+  for (int i = 0; i < 3; ++i) {
+    const int p = (nplanes == 2 && i == 2) ? 1 : i;            // interleaved chroma: U and V walk the same plane
+    d->plane[i] = p < nplanes ? static_cast<const uint8_t*>(fr.plane[p]) : nullptr;
+    d->row_stride[i] = p < nplanes ? fr.row_stride[p] : 0;
+  }
+  d->W = fr.width; d->H = fr.height; d->mb_w = g.mb_w; d->n_mcus = g.n_mcus; d->nseg = g.nseg;
+  d->has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
+}
+
 }  // namespace
 
 int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                 const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables,
                                 int tables_per_frame, const void* headers, const size_t* header_offsets,
                                 int append_eoi, void* d_out, uint64_t* d_sizes, void* stream) {
+  static const std::string kWhoEncode = "sjpeg_hip_encode_ragged_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: engine == NULL");
   if (frames == nullptr || tables == nullptr || d_out == nullptr || d_sizes == nullptr) {
     return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: frames, tables, d_out or d_sizes == NULL");
@@ -1344,27 +1411,8 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   }
   // the layout of the format (as prepare_scan): planes, source class, the kernel's per-format fields
   ScanArgs a;
-  memset(&a, 0, sizeof(a));
-  int cls = kSrcPlanes, nplanes = 1, implied = 0;
-  switch (format) {
-    case SJPEG_HIP_SRC_RGB: cls = kSrcRgb24; break;
-    case SJPEG_HIP_SRC_BGRA: cls = kSrcRgbx32; a.rsh = 16; a.bsh = 0; break;
-    case SJPEG_HIP_SRC_RGBA: cls = kSrcRgbx32; a.rsh = 0; a.bsh = 16; break;
-    case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
-    case SJPEG_HIP_SRC_YUV444: nplanes = 3; implied = SJPEG_HIP_YUV444; a.cstep = 1; break;
-    case SJPEG_HIP_SRC_YUV420: nplanes = 3; implied = SJPEG_HIP_YUV420; a.cstep = 1; break;
-    case SJPEG_HIP_SRC_NV12:
-    case SJPEG_HIP_SRC_NV21:
-      nplanes = 2; implied = SJPEG_HIP_YUV420; a.cstep = 2;
-      a.uoff = (format == SJPEG_HIP_SRC_NV12) ? 0 : 1;
-      a.voff = 1 - a.uoff;
-      break;
-    default: return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: unknown source format");
-  }
-  if (yuv_mode != SJPEG_HIP_YUV420 && yuv_mode != SJPEG_HIP_YUV444 && yuv_mode != SJPEG_HIP_YUV400) {
-    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: bad yuv_mode");
-  }
-  if (implied != 0 && yuv_mode != implied) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: yuv_mode does not match the source format");
+  int cls = kSrcPlanes, nplanes = 1;
+  if (int rcf = ragged_format(kWhoEncode, format, yuv_mode, &a, &cls, &nplanes)) return rcf;
   size_t header_size = 0;
   if (header_offsets != nullptr) {
     for (int f = 0; f <= nframes; ++f) {
@@ -1375,27 +1423,12 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
     header_size = header_offsets[nframes];
   }
   // per frame: checks, geometry, scratch plan
-  std::vector<FrameGeo> geo(nframes);
+  std::vector<FrameGeo> geo;
+  if (int rcg = ragged_frames(kWhoEncode, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rcg;
   std::vector<SegPlan> plan(nframes);
   std::vector<uint32_t> max_chunks(nframes);
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
-    const std::string who = "sjpeg_hip_encode_ragged_src: frame " + std::to_string(f) + ": ";
-    if (!frame_geo(fr.width, fr.height, yuv_mode, &geo[f])) {
-      return fail(SJPEG_HIP_EINVAL, who + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
-    }
-    const int64_t W = fr.width, cw = (W + 1) / 2;
-    int64_t need[3] = {W, W, W};
-    if (format == SJPEG_HIP_SRC_RGB) need[0] = 3 * W;
-    else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
-    else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
-    else if (format == SJPEG_HIP_SRC_NV12 || format == SJPEG_HIP_SRC_NV21) need[1] = 2 * cw;
-    for (int i = 0; i < nplanes; ++i) {
-      if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, who + "null plane pointer");
-      const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
-      if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, who + "|row_stride| smaller than a row of the plane");
-    }
-    if (fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, who + "out_offset + out_capacity overflows");
     plan[f] = seg_plan(geo[f], fr.out_capacity > 0 ? static_cast<size_t>(fr.out_capacity) : 1);
     max_chunks[f] = static_cast<uint32_t>((plan[f].ubuf_words + kChunkWords - 1) / kChunkWords);
   }
@@ -1463,13 +1496,7 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
       const sjpeg_hip_ragged_frame& fr = frames[f];
       const FrameGeo& g = geo[f];
       RaggedFrame& d = desc[f];
-      for (int i = 0; i < 3; ++i) {
-        const int p = (nplanes == 2 && i == 2) ? 1 : i;            // interleaved chroma: U and V walk the same plane
-        d.plane[i] = p < nplanes ? static_cast<const uint8_t*>(fr.plane[p]) : nullptr;
-        d.row_stride[i] = p < nplanes ? fr.row_stride[p] : 0;
-      }
-      d.W = fr.width; d.H = fr.height; d.mb_w = g.mb_w; d.n_mcus = g.n_mcus; d.nseg = g.nseg;
-      d.has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
+      ragged_geometry(fr, g, nplanes, &d);
       d.seg_base = seg; d.pool_base = pool; d.pool_words = plan[f].pool_words;
       d.ubuf_base = ubuf; d.ubuf_words = static_cast<uint32_t>(plan[f].ubuf_words);
       d.chunk_base = chunk; d.max_chunks = max_chunks[f];
@@ -1566,6 +1593,168 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
     e->ev_valid = true;
   }
   return 0;
+}
+
+namespace {
+
+// The two analysis passes over a ragged batch: the histogram (kKindHistoRagged, persistent groups) or the symbol
+// statistics (kKindStatsRagged, a workgroup per segment) of frames [0, nframes), then their ragged reduce --
+// d_out[f] = [2][64][128] or [2][272] words, what the uniform pass makes of frame f alone.  The frames have been checked
+// (ragged_frames); `a` holds the format's fields (ragged_format).  The partials of a launch stay inside the engine's
+// scratch limit: a larger batch goes in several launches over consecutive frames.
+int ragged_analysis(sjpeg_hip_engine* e, bool histogram, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+                    const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
+                    const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st) {
+  const size_t part_words = histogram ? kHistoPartialWords : kStatsWords;     // a partial: one group's / one segment's
+  const int words = histogram ? 2 * 64 * 128 : kStatsWords;                  // a frame's result
+  // The histogram's groups.  A frame's group count is its own: as many as the uniform launch's 3 x CU slots give it in
+  // whole trips over the batch's segments -- at least ceil(nseg / 256) (16-bit counters), at most one per segment.
+  const long long slots = e->histo_slots > 0 ? e->histo_slots : 3ll * e->cu_count;
+  long long all_segs = 0;
+  for (int f = 0; f < nframes; ++f) all_segs += geo[f].nseg;
+  const long long trips = std::max(1ll, (all_segs + slots - 1) / slots);
+  std::vector<uint32_t> units(nframes);        // K1 workgroups of a frame: groups (histogram) or segments
+  for (int f = 0; f < nframes; ++f) {
+    const int nseg = geo[f].nseg;
+    int g = nseg;
+    if (histogram) {
+      g = static_cast<int>((nseg + trips - 1) / trips);
+      g = std::max(g, (nseg + kHistoMaxSegsPerGroup - 1) / kHistoMaxSegsPerGroup);
+      g = std::min(g, nseg);
+    }
+    units[f] = static_cast<uint32_t>(g);
+  }
+  // launches: consecutive frames whose partials fit the limit (one frame at least)
+  struct Launch { int f0, nf; uint32_t units, max_units; size_t map; };
+  std::vector<Launch> launches;
+  {
+    Launch cur = {0, 0, 0, 0, 0};
+    for (int f = 0; f < nframes; ++f) {
+      const size_t more = static_cast<size_t>(cur.units) + units[f];
+      if (cur.nf > 0 && (more * part_words * sizeof(uint32_t) > e->scratch_limit || more > (1u << 30))) {
+        launches.push_back(cur);
+        cur = {f, 0, 0, 0, 0};
+      }
+      cur.nf += 1;
+      cur.units += units[f];
+      cur.max_units = std::max(cur.max_units, units[f]);
+    }
+    launches.push_back(cur);
+  }
+  // the blob: descriptors | digested tables (statistics) | the launches' workgroup -> frame maps
+  const int ntab = histogram ? 0 : (tables_per_frame ? nframes : 1);
+  const size_t off_tab = align16(sizeof(RaggedFrame) * nframes);
+  const size_t off_map = off_tab + sizeof(DevTables) * ntab;
+  size_t map_words = 0;
+  for (Launch& l : launches) { l.map = map_words; map_words += l.units; }
+  const size_t blob_bytes = align16(off_map + map_words * sizeof(uint32_t));
+  std::vector<uint4> blob(blob_bytes / 16);
+  uint8_t* const hb = reinterpret_cast<uint8_t*>(blob.data());
+  RaggedFrame* const desc = reinterpret_cast<RaggedFrame*>(hb);
+  for (int t = 0; t < ntab; ++t) digest_tables(tables + t, reinterpret_cast<DevTables*>(hb + off_tab) + t);
+  uint32_t* const maps = reinterpret_cast<uint32_t*>(hb + off_map);
+  for (const Launch& l : launches) {
+    uint32_t base = 0;
+    for (int f = l.f0; f < l.f0 + l.nf; ++f) {
+      RaggedFrame& d = desc[f];
+      ragged_geometry(frames[f], geo[f], nplanes, &d);
+      d.seg_base = base;                       // (the histogram: its first group -- and partial -- in the launch)
+      d.hgroups = histogram ? units[f] : 0u;
+      for (uint32_t k = 0; k < units[f]; ++k) maps[l.map + base + k] = static_cast<uint32_t>(f - l.f0);
+      base += units[f];
+    }
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc0 = order_on_stream(e, st)) return rc0;
+  if (e->side_pending) {                             // (pipelined mode: the call runs ordered, behind the engine's stitch)
+    if (int rcm = side_mark(e)) return rcm;
+    HIP_TRY(hipStreamWaitEvent(st, e->side_done, 0));
+  }
+  size_t n_part = 0;
+  for (const Launch& l : launches) n_part = std::max(n_part, static_cast<size_t>(l.units) * part_words);
+  int rc;
+  if ((rc = e->ragged.ensure(blob.size())) || (rc = e->partial.ensure(n_part))) return rc;
+  if ((rc = upload(e, e->ragged.p, blob.data(), blob_bytes, st))) return rc;
+  if ((rc = sync_uploads(e, st))) return rc;
+  const uint8_t* const db = reinterpret_cast<const uint8_t*>(e->ragged.p);
+  for (const Launch& l : launches) {
+    a.tables = histogram ? nullptr : reinterpret_cast<const DevTables*>(db + off_tab) + (tables_per_frame ? l.f0 : 0);
+    a.tables_stride = tables_per_frame ? 1 : 0;
+    a.partial = e->partial.p;
+    a.ablate = e->ablate;
+    a.rframes = reinterpret_cast<const RaggedFrame*>(db) + l.f0;
+    a.rmap = reinterpret_cast<const uint32_t*>(db + off_map) + l.map;
+    if (histogram) rc = launch_scan<kKindHistoRagged>(yuv_mode, cls, dim3(l.units), st, a);
+    else rc = launch_scan<kKindStatsRagged>(yuv_mode, cls, dim3(l.units), st, a);
+    if (rc) return rc;
+    // the reduce: slices of the partials as the uniform pass takes them (scan_statistics), for the launch's largest frame
+    uint32_t* const out = d_out + static_cast<size_t>(l.f0) * words;
+    const int xblocks = histogram ? 32 : (words + kThreads - 1) / kThreads;
+    int slices = std::min(32, 4096 / (xblocks * l.nf));
+    if (histogram) slices = std::min(slices, static_cast<int>((l.max_units + 255) / 256));
+    else if (l.max_units < 64) slices = 1;
+    slices = std::max(slices, 1);
+    if (!(histogram && slices == 1)) {               // (one slice stores, several add)
+      HIP_TRY(hipMemsetAsync(out, 0, static_cast<size_t>(l.nf) * words * sizeof(uint32_t), st));
+    }
+    const dim3 grid(xblocks, l.nf, slices);
+    if (histogram) {
+      hipLaunchKernelGGL((reduce_partials16<true, const RaggedFrame*>), grid, dim3(kThreads), 0, st, reinterpret_cast<const uint4*>(e->partial.p), 0, out, a.rframes);
+    } else {
+      hipLaunchKernelGGL((reduce_partials<true, const RaggedFrame*>), grid, dim3(kThreads), 0, st, e->partial.p, 0, words, out, a.rframes);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+// the checks every ragged analysis entry point starts with; the format's fields in *a, the frames' geometry in *geo
+int ragged_analysis_args(const std::string& who, sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                         const sjpeg_hip_ragged_frame* frames, const void* d_out, ScanArgs* a, int* cls, int* nplanes,
+                         std::vector<FrameGeo>* geo) {
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || d_out == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": frames or the output == NULL");
+  if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (int rc = ragged_format(who, format, yuv_mode, a, cls, nplanes)) return rc;
+  return ragged_frames(who, format, yuv_mode, *nplanes, nframes, frames, false, geo);
+}
+
+}  // namespace
+
+int sjpeg_hip_scan_histogram_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames, uint32_t* d_hist, void* stream) {
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_analysis_args("sjpeg_hip_scan_histogram_ragged_src", e, format, yuv_mode, nframes, frames, d_hist, &a, &cls, &nplanes, &geo)) return rc;
+  try {
+    return ragged_analysis(e, true, yuv_mode, cls, a, nplanes, nframes, frames, geo, nullptr, 0, d_hist, static_cast<hipStream_t>(stream));
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables,
+                                           int tables_per_frame, uint32_t* d_freq, void* stream) {
+  static const std::string who = "sjpeg_hip_scan_symbol_stats_ragged_src";
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &nplanes, &geo)) return rc;
+  if (tables == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": tables == NULL");
+  constexpr uint32_t kNotRagged = SJPEG_HIP_QUANT_TRELLIS | SJPEG_HIP_QUANT_KEEP | SJPEG_HIP_QUANT_REPLAY | SJPEG_HIP_RESTART_MARKERS;
+  for (int t = 0; t < (tables_per_frame ? nframes : 1); ++t) {
+    if (tables[t].flags & kNotRagged) {
+      return fail(SJPEG_HIP_EINVAL, who + ": tables[" + std::to_string(t) +
+                                        "]: trellis, keep / replay and restart-marker flags are not taken by ragged batches");
+    }
+  }
+  try {
+    return ragged_analysis(e, false, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, d_freq, static_cast<hipStream_t>(stream));
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
 }
 
 // ---- one frame over several GPUs: bands of consecutive segments ----------
@@ -1711,13 +1900,14 @@ namespace {
 int adapt_decide(const int64_t* d_sums, const int32_t* d_totlast, int nframes, const uint8_t quant[2][64], int ntables,
                  int qdelta_max_luma, int qdelta_max_chroma, uint8_t* d_quant_out, hipStream_t st) {
   DecideArgs a;
+  a.quant_f = nullptr;
   a.sums = reinterpret_cast<const long long*>(d_sums);
   a.totlast = d_totlast;
   a.quant_out = d_quant_out;
   memcpy(a.quant_in, quant, sizeof(a.quant_in));
   a.last_step[0] = qdelta_max_luma + 12;
   a.last_step[1] = qdelta_max_chroma + 12;
-  hipLaunchKernelGGL(adapt_decide_kernel, dim3(ntables, nframes), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(adapt_decide_kernel<>, dim3(ntables, nframes), dim3(64), 0, st, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1741,12 +1931,13 @@ int sjpeg_hip_adapt_sums(const uint32_t* d_hist, int nframes, const uint8_t quan
     return fail(SJPEG_HIP_EINVAL, "null argument or bad nframes");
   }
   AdaptArgs a;
+  a.quant_f = nullptr;
   a.hist = d_hist;
   a.sums = reinterpret_cast<long long*>(d_sums);
   a.totlast = d_totlast;
   memcpy(a.quant, quant, sizeof(a.quant));
   if (min_quant != nullptr) memcpy(a.min_quant, min_quant, sizeof(a.min_quant)); else memset(a.min_quant, 1, sizeof(a.min_quant));
-  hipLaunchKernelGGL(adapt_sums_kernel, dim3(64, 2, nframes), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(adapt_sums_kernel<>, dim3(64, 2, nframes), dim3(64), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2226,6 +2417,173 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
       mark("encode launched", p);
     }
     return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ---- a ragged batch with the reference's per-picture analysis (methods 0..6) ----
+// The flow of sjpeg_hip_encode_batch_src over frames of different sizes: the ragged histogram, the adaptation kernels with
+// a starting matrix per frame, one read-back and wait; the tables; the ragged statistics, one read-back and wait; the
+// Huffman codes and the headers on the host; the ragged encode.  No lanes, no parts, no coefficients kept between passes.
+int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                      int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                      int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                      void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_batch_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || quant_in == nullptr || d_out == nullptr || d_sizes == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, quant, d_out or d_sizes == NULL");
+  }
+  if (method < 0 || method > 6) return fail(SJPEG_HIP_EINVAL, who + ": methods 0..6 (trellis goes through the host API)");
+  if (qdelta_max_luma < -12 || qdelta_max_luma > 12 || qdelta_max_chroma < -12 || qdelta_max_chroma > 12) {
+    return fail(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
+  }
+  if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  ScanArgs a;
+  int cls = kSrcPlanes, nplanes = 1;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
+  if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
+  try {
+    const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3);
+    const int ntab = yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = static_cast<size_t>(nframes);
+    // every frame's starting matrices and tables, as sjpeg_hip_encode_batch_src makes them of its one matrix
+    std::vector<sjpeg_hip_scan_tables> tables(n);
+    std::vector<uint8_t> quant(n * 128);
+    for (size_t f = 0; f < n; ++f) {
+      uint8_t* const q = &quant[f * 128];
+      memcpy(q, quant_in[quant_per_frame ? f : 0], 128);
+      memset(&tables[f], 0, sizeof(tables[f]));
+      sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(q), min_quant, q_bias, &tables[f]);
+      sjpeg_hip_default_huffman(&tables[f]);
+    }
+    static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
+    const auto t_start = std::chrono::steady_clock::now();
+    auto mark = [&](const char* what) {
+      if (batch_debug) fprintf(stderr, "ragged %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
+    };
+    constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
+    constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
+    constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
+    // the analysis goes in chunks of consecutive frames whose scratch -- the pass's partials (the histogram's at most one
+    // per segment) and the per-frame results -- stays inside the engine's limit
+    auto chunks_of = [&](size_t per_seg, size_t per_frame) {
+      std::vector<std::pair<size_t, size_t>> c;      // (first frame, frames)
+      size_t f0 = 0, bytes = 0;
+      for (size_t f = 0; f < n; ++f) {
+        const size_t b = static_cast<size_t>(geo[f].nseg) * per_seg + per_frame;
+        if (f > f0 && bytes + b > e->scratch_limit) { c.emplace_back(f0, f - f0); f0 = f; bytes = 0; }
+        bytes += b;
+      }
+      c.emplace_back(f0, n - f0);
+      return c;
+    };
+    BatchScratch& sc = g_batch;
+    if (sc.device != e->device) { if (sc.device >= 0) { (void)hipSetDevice(sc.device); sc.Drop(); } sc.device = e->device; }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!sc.EnsurePinned(n * (adaptive ? 128 : 0) + (optimize ? n * kFreq : 0) + 16) || !sc.EnsureEvents()) {
+      return fail(SJPEG_HIP_ENOMEM, "hipHostMalloc / hipEventCreate(batch scratch) failed");
+    }
+    uint8_t* const h_q = static_cast<uint8_t*>(sc.h_pinned);                     // [n][128]
+    uint8_t* const h_freq = h_q + (adaptive ? n * 128 : 0);                       // [n][kFreq]
+    auto read_back = [&](void* h_dst, const void* d_src, size_t bytes) -> int {
+      void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
+      return copy_by_kernel(dv, d_src, bytes, st, hipMemcpyDeviceToHost, d_src, h_dst);
+    };
+    if (adaptive) {
+      // 1. histograms, the adaptation with each frame's own starting matrices, the adapted matrices back
+      const auto chunks = chunks_of(kHistoPartialWords * sizeof(uint32_t), kHist + kSums + kTot);
+      size_t most = 0;
+      for (const auto& c : chunks) most = std::max(most, c.second);
+      // d_sums: [chunk][kSums] | [chunk][kTot] | the starting matrices [n][128] | the adapted ones [n][128]
+      if (!sc.Ensure(&sc.d_hist, &sc.hist_cap, most * kHist) || !sc.Ensure(&sc.d_sums, &sc.sums_cap, most * (kSums + kTot) + n * 256)) {
+        return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
+      }
+      uint8_t* const d_qs = static_cast<uint8_t*>(sc.d_sums) + most * (kSums + kTot);
+      uint8_t* const d_qa = d_qs + n * 128;
+      if (int rc = order_on_stream(e, st)) return rc;
+      if (int rc = upload(e, d_qs, quant.data(), n * 128, st)) return rc;
+      if (int rc = sync_uploads(e, st)) return rc;
+      for (const auto& c : chunks) {
+        uint32_t* const d_hist = static_cast<uint32_t*>(sc.d_hist);
+        if (int rc = ragged_analysis(e, true, yuv_mode, cls, a, nplanes, static_cast<int>(c.second), frames + c.first,
+                                     std::vector<FrameGeo>(geo.begin() + c.first, geo.begin() + c.first + c.second),
+                                     nullptr, 0, d_hist, st)) return rc;
+        AdaptArgs s;
+        s.hist = d_hist;
+        s.sums = static_cast<long long*>(sc.d_sums);
+        s.totlast = reinterpret_cast<int*>(static_cast<uint8_t*>(sc.d_sums) + c.second * kSums);
+        memset(s.quant, 0, sizeof(s.quant));
+        if (min_quant != nullptr) memcpy(s.min_quant, min_quant, sizeof(s.min_quant)); else memset(s.min_quant, 1, sizeof(s.min_quant));
+        s.quant_f = d_qs + c.first * 128;
+        hipLaunchKernelGGL(adapt_sums_kernel<true>, dim3(64, 2, c.second), dim3(64), 0, st, s);
+        HIP_TRY(hipGetLastError());
+        DecideArgs d;
+        d.sums = s.sums; d.totlast = s.totlast;
+        d.quant_out = d_qa + c.first * 128;
+        memset(d.quant_in, 0, sizeof(d.quant_in));
+        d.last_step[0] = qdelta_max_luma + 12;
+        d.last_step[1] = qdelta_max_chroma + 12;
+        d.quant_f = s.quant_f;
+        hipLaunchKernelGGL(adapt_decide_kernel<true>, dim3(ntab, c.second), dim3(64), 0, st, d);
+        HIP_TRY(hipGetLastError());
+      }
+      if (int rc = read_back(h_q, d_qa, n * 128)) return rc;
+      HIP_TRY(hipEventRecord(sc.pass_done, st));
+      mark("hist launched");
+      HIP_TRY(hipEventSynchronize(sc.pass_done));
+      mark("matrices here");
+      // 2. the tables of the adapted matrices
+      for (size_t f = 0; f < n; ++f) {
+        memcpy(&quant[f * 128], h_q + f * 128, static_cast<size_t>(ntab) * 64);
+        sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
+      }
+    }
+    std::vector<sjpeg_hip_huffman_spec> specs(optimize ? n * 4 : 0);
+    if (optimize) {
+      // 3. the symbol counts with each frame's tables, back to the host
+      const auto chunks = chunks_of(kStatsWords * sizeof(uint32_t), kFreq);
+      size_t most = 0;
+      for (const auto& c : chunks) most = std::max(most, c.second);
+      if (!sc.Ensure(&sc.d_freq, &sc.freq_cap, most * kFreq)) return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
+      for (const auto& c : chunks) {
+        uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
+        if (int rc = ragged_analysis(e, false, yuv_mode, cls, a, nplanes, static_cast<int>(c.second), frames + c.first,
+                                     std::vector<FrameGeo>(geo.begin() + c.first, geo.begin() + c.first + c.second),
+                                     &tables[c.first], 1, d_freq, st)) return rc;
+        if (int rc = read_back(h_freq + c.first * kFreq, d_freq, c.second * kFreq)) return rc;
+      }
+      HIP_TRY(hipEventRecord(sc.pass_done, st));
+      mark("stats launched");
+      HIP_TRY(hipEventSynchronize(sc.pass_done));
+      mark("counts here");
+      // 4. the optimised codes (the host's share that grows with the batch)
+      for (size_t f = 0; f < n; ++f) {
+        sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(h_freq + f * kFreq), yuv_mode, &specs[f * 4], &tables[f]);
+      }
+    }
+    // 4. (all methods) the headers, each frame's own
+    std::vector<uint8_t> headers;
+    std::vector<size_t> offs(n + 1, 0);
+    uint8_t one[2048];
+    for (size_t f = 0; f < n; ++f) {
+      const size_t hs = sjpeg_hip_make_header_ex(frames[f].width, frames[f].height, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
+                                                 optimize ? &specs[f * 4] : nullptr, one, sizeof(one));
+      if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
+      headers.insert(headers.end(), one, one + hs);
+      offs[f + 1] = headers.size();
+    }
+    mark("tables built");
+    // 5. the ragged encode (method 0: its one call), asynchronous on the stream
+    const bool one_table = !quant_per_frame && !adaptive && !optimize;
+    const int rc = sjpeg_hip_encode_ragged_src(e, format, yuv_mode, nframes, frames, tables.data(), one_table ? 0 : 1,
+                                               headers.data(), offs.data(), /*append_eoi=*/1, d_out, d_sizes, stream);
+    mark("encode launched");
+    return rc;
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }

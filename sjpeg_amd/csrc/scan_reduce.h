@@ -3,16 +3,26 @@
 // Part of the single translation unit scan_engine.hip: included there inside its anonymous
 // namespace, after <hip/hip_runtime.h> and sjpeg_hip.h; not a stand-alone header.
 // ------------------------------------------------------------------------------------
+// The ragged forms of the two reduces take the launch's frame descriptors as one more argument; the uniform forms have
+// none (an empty pack: their arguments, and their code, are what they were).
+__device__ __forceinline__ const RaggedFrame* ragged_arg() { return nullptr; }
+__device__ __forceinline__ const RaggedFrame* ragged_arg(const RaggedFrame* rframes) { return rframes; }
+
 // Sums the per-workgroup partial symbol counts of one frame (statistics kinds): out[frame][i] = sum over segments.
-__global__ __launch_bounds__(kThreads) void reduce_partials(const uint32_t* part, int nseg, int words, uint32_t* out) {
+// RAGGED (kKindStatsRagged): frame blockIdx.y of the launch has its own segment count and its partials start at its
+// first segment (RaggedFrame: nseg, seg_base) -- the rest is the uniform kernel's.
+template <bool RAGGED = false, typename... R>
+__global__ __launch_bounds__(kThreads) void reduce_partials(const uint32_t* part, int nseg_in, int words, uint32_t* out, R... rf) {
+  const RaggedFrame* const rframes = ragged_arg(rf...);
   // blockIdx.z = slice of the segments: a thread adds up its slice (independent loads, unrolled)
   // and the slices meet in the output with atomics (cleared by the caller).
   const int frame = blockIdx.y;
+  const int nseg = RAGGED ? rframes[frame].nseg : nseg_in;
   const int w = blockIdx.x * kThreads + threadIdx.x;
   if (w >= words) return;
   const int per = (nseg + gridDim.z - 1) / gridDim.z;
   const int s0 = blockIdx.z * per, s1 = min(nseg, s0 + per);
-  const uint32_t* src = part + static_cast<size_t>(frame) * nseg * words + w;
+  const uint32_t* src = part + (RAGGED ? static_cast<size_t>(rframes[frame].seg_base) * words : static_cast<size_t>(frame) * nseg * words) + w;
   uint32_t sum = 0;
 #pragma unroll 8
   for (int s = s0; s < s1; ++s) sum += src[static_cast<size_t>(s) * words];
@@ -26,16 +36,21 @@ __global__ __launch_bounds__(kThreads) void reduce_partials(const uint32_t* part
 // out[frame][table][position][bin].  A workgroup takes 64 threads' worth of one piece, its four waves a quarter of the
 // groups each (independent loads, sixteen in flight) and meet in LDS: no atomics, and `out` needs no clearing -- unless
 // the launch has slices (blockIdx.z: one big frame with a thousand partials), which meet with atomics in a cleared `out`.
-__global__ __launch_bounds__(kThreads) void reduce_partials16(const uint4* part, int groups, uint32_t* out) {
+// RAGGED (kKindHistoRagged): frame blockIdx.y of the launch has its own group count and its partials start at its first
+// group (RaggedFrame: hgroups, seg_base); a frame with fewer groups than the launch has slices leaves the extra ones empty.
+template <bool RAGGED = false, typename... R>
+__global__ __launch_bounds__(kThreads) void reduce_partials16(const uint4* part, int groups_in, uint32_t* out, R... rf) {
+  const RaggedFrame* const rframes = ragged_arg(rf...);
   __shared__ uint32_t red[3][8][64];
   const int frame = blockIdx.y;
+  const int groups = RAGGED ? static_cast<int>(rframes[frame].hgroups) : groups_in;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = blockIdx.x >> 2, t = (blockIdx.x & 3) * 64 + lane;   // piece, thread of the scan kernel
   const int per_slice = (groups + gridDim.z - 1) / gridDim.z;
   const int s0 = blockIdx.z * per_slice, s1 = min(groups, s0 + per_slice);
   const int per = (s1 - s0 + 3) >> 2;
   const int g0 = s0 + wave * per, g1 = min(s1, g0 + per);
-  const uint4* src = part + (static_cast<size_t>(frame) * groups * 8 + j) * 256 + t;
+  const uint4* src = part + ((RAGGED ? static_cast<size_t>(rframes[frame].seg_base) * 8 : static_cast<size_t>(frame) * groups * 8) + j) * 256 + t;
   uint32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 16
   for (int g = g0; g < g1; ++g) {
@@ -88,7 +103,9 @@ struct AdaptArgs {
   long long* sums;                  // [nframes][2][64][25][2]: bits, distortion (INT64_MIN = not a candidate)
   int* totlast;                     // [nframes][2][64][2]: population, highest occupied bin + 1
   uint8_t quant[2][64], min_quant[2][64];
+  const uint8_t* quant_f;           // PER_FRAME: the starting matrices [nframes][2][64], device-resident (else unused)
 };
+template <bool PER_FRAME = false>
 __global__ __launch_bounds__(64) void adapt_sums_kernel(const AdaptArgs a) {
   // one wave per (frame, table, position): the 128 bins go to LDS once (two per lane; population and
   // highest occupied bin by a wave reduction), then lane d < 25 walks them for its candidate step
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(64) void adapt_sums_kernel(const AdaptArgs a) {
   const size_t cell = (static_cast<size_t>(frame) * 2 + idx) * 64 + pos;
   if (delta == 0) { a.totlast[cell * 2] = total; a.totlast[cell * 2 + 1] = last; }
   if (delta >= 25) return;
-  const int dq = static_cast<int>(a.quant[idx][pos]) + (delta - 12);
+  const int dq = static_cast<int>(PER_FRAME ? a.quant_f[cell] : a.quant[idx][pos]) + (delta - 12);
   long long bsum = 0, dsum = 0;
   if (dq < static_cast<int>(a.min_quant[idx][pos]) || dq > 255) {
     dsum = static_cast<long long>(0x8000000000000000ull);
@@ -143,7 +160,9 @@ struct DecideArgs {
   uint8_t* quant_out;               // [nframes][2][64]: the adapted matrices (tables the launch does not run keep quant_in)
   uint8_t quant_in[2][64];
   int last_step[2];                 // qdelta_max of the table - kQDeltaMin
+  const uint8_t* quant_f;           // PER_FRAME: the starting matrices [nframes][2][64], device-resident (else unused)
 };
+template <bool PER_FRAME = false>
 __global__ __launch_bounds__(64) void adapt_decide_kernel(const DecideArgs a) {
   __shared__ double cov_d[64], cov_r[64];
   __shared__ double lam;
@@ -199,7 +218,7 @@ __global__ __launch_bounds__(64) void adapt_decide_kernel(const DecideArgs a) {
     lam = lambda;
   }
   __syncthreads();
-  int q = a.quant_in[idx][pos];
+  int q = PER_FRAME ? a.quant_f[cell] : a.quant_in[idx][pos];
   if (live) {
     const double lambda = lam;
     float best = 3.402823466e+38f;

@@ -31,10 +31,12 @@ enum { kKindEncode = 0, kKindTap = 1, kKindHisto = 2, kKindStats = 3, kKindError
        kKindEncodeTrellis = 5, kKindStatsTrellis = 6,     // the same two with trellis quantization
        kKindEncodeReplay = 7,     // entropy-code the coefficients a statistics pass left behind
        kKindStatsCoef = 8,        // statistics from the DCT coefficients a histogram pass left behind
-       kKindEncodeRagged = 9 };   // the encode kind over frames of different sizes (flat grid, per-frame descriptors)
+       kKindEncodeRagged = 9,     // the encode kind over frames of different sizes (flat grid, per-frame descriptors)
+       kKindHistoRagged = 10, kKindStatsRagged = 11 };   // the histogram and statistics kinds over such frames
 constexpr int kHistoWords = 2 * 64 * 32;          // words of u8 counters [2][64][128] a workgroup bins one segment into (LDS)
 // The histogram kind is PERSISTENT: a workgroup bins the segments seg, seg + gridDim.x, ... of its frame and leaves ONE
-// partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).
+// partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).  (The ragged
+// form strides by its frame's own group count instead of gridDim.x: ragged_histo_view.)
 constexpr int kHistoPartialWords = 2 * kHistoWords;
 constexpr int kHistoMaxSegsPerGroup = 256;        // 246 blocks a segment at most: 16 bits hold 266 of them
 // LDS of the histogram kind behind P1 (over the block slots): 256 staged half blocks of 64 + 16 bytes, then the 8-bit
@@ -76,26 +78,29 @@ __device__ __forceinline__ void race_point(int code, int n) {
 #endif
 template <int MODE, int KINDX, int SRC>
 constexpr bool kCompactLds = (KINDX == kKindEncode || KINDX == kKindEncodeReplay || KINDX == kKindStats || KINDX == kKindStatsCoef ||
-                              KINDX == kKindEncodeRagged);
+                              KINDX == kKindEncodeRagged || KINDX == kKindStatsRagged);
 
 template <int MODE, int KINDX, int SRC>
-__global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
-  // The ragged kind is the encode kind but for its prologue: its workgroup's frame and segment come from the launch's
-  // segment -> frame map, the frame's geometry and scratch bases from its descriptor (ragged_scan_view)
-  constexpr bool RAGGED = (KINDX == kKindEncodeRagged);
+__global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kKindHistoRagged) && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
+  // The ragged kinds are the encode, histogram and statistics kinds but for their prologue: a workgroup's frame and
+  // segment come from the launch's workgroup -> frame map, the frame's geometry and scratch bases from its descriptor
+  // (ragged_scan_view; the histogram's persistent groups: ragged_histo_view)
+  constexpr bool HISTO_RAGGED = (KINDX == kKindHistoRagged);
+  constexpr bool RAGGED = (KINDX == kKindEncodeRagged || HISTO_RAGGED || KINDX == kKindStatsRagged);
   constexpr bool TRELLIS = (KINDX == kKindEncodeTrellis || KINDX == kKindStatsTrellis);
   constexpr bool REPLAY = (KINDX == kKindEncodeReplay);
   // the block's unquantized coefficients come from the histogram pass of the same call (the adaptive methods run
   // one before they know the quantizer): no second colour conversion / DCT
   constexpr bool COEF = (KINDX == kKindStatsCoef);
-  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || RAGGED) ? kKindEncode : (KINDX == kKindStatsTrellis || COEF) ? kKindStats : KINDX;
+  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || KINDX == kKindEncodeRagged) ? kKindEncode
+                       : (KINDX == kKindStatsTrellis || COEF || KINDX == kKindStatsRagged) ? kKindStats : HISTO_RAGGED ? kKindHisto : KINDX;
   constexpr bool COMPACT = kCompactLds<MODE, KINDX, SRC>;
   // The statistics kinds (but the trellis one) count a block's symbols straight out of the thread's registers, zig-zag
   // position by position -- no entries in LDS, no parts, no sort, no walk (below, "kKindStats, direct")
 #ifndef SJPEG_STATS_DIRECT
 #define SJPEG_STATS_DIRECT 1
 #endif
-  constexpr bool DIRECT = SJPEG_STATS_DIRECT && (KINDX == kKindStats || KINDX == kKindStatsCoef);
+  constexpr bool DIRECT = SJPEG_STATS_DIRECT && (KINDX == kKindStats || KINDX == kKindStatsCoef || KINDX == kKindStatsRagged);
   using L = Lds<COMPACT>;
   constexpr int kWinWords = L::kWinWords;
   using G = Geo<MODE>;
@@ -118,10 +123,14 @@ __global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcR
   typedef uint16_t __attribute__((may_alias)) u16_may_alias;
 
   const int tid = threadIdx.x;
-  int seg0 = blockIdx.x;
+  int seg0 = blockIdx.x, hgroups = 0;
   // (a copy, not a reference: the other kinds read the kernel argument as before -- the same code to the instruction)
-  const ScanArgs a = RAGGED ? ragged_scan_view(a_in, &seg0) : a_in;
+  const ScanArgs a = HISTO_RAGGED ? ragged_histo_view(a_in, &seg0, &hgroups)
+                     : RAGGED ? ragged_scan_view(a_in, &seg0, KINDX == kKindStatsRagged ? kStatsWords : 0) : a_in;
   const int frame = RAGGED ? 0 : blockIdx.y;
+  // the histogram kind's stride over its frame's segments: the launch's groups per frame, or (ragged) the frame's own
+  // (read where it is used, as gridDim.x was: the uniform kinds keep their code)
+  auto gdx_of = [&]() -> int { return HISTO_RAGGED ? hgroups : static_cast<int>(gridDim.x); };
   // the histogram kind's 16-bit counters, two to a register: the 8-bit counters of words 16 * tid .. 16 * tid + 15 of
   // the LDS histogram (overflow words not counted), bytes 0 / 2 in the even and bytes 1 / 3 in the odd register (no
   // other kind has them)
@@ -131,7 +140,7 @@ __global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcR
     for (int i = 0; i < 32; ++i) hacc[i] = 0;
   }
   // every kind but the histogram takes ONE trip (gridDim.x = the frame's segments); the body ends with a return
-  for (int seg = seg0;; seg += gridDim.x) {
+  for (int seg = seg0;; seg += gdx_of()) {
   auto stamp = [&](int k) {
     if (a.stamps != nullptr && tid == 0) {
       a.stamps[(static_cast<size_t>(frame) * a.nseg + seg) * 8 + k] =
@@ -675,8 +684,9 @@ __global__ __launch_bounds__(kScanThreads, ((KINDX == kKindHisto && SRC == kSrcR
       }
     }
     stamp(6);
-    if (seg + static_cast<int>(gridDim.x) >= a.nseg) {
+    if (seg + gdx_of() >= a.nseg) {
       // this workgroup's partial, [8][256] pieces of 16 bytes: a store instruction of a wave covers 1 KiB in one piece
+      // (ragged: frame is 0 and the launch's partials lie in the order of its groups -- blockIdx.x is this one's)
       uint4* const dst = reinterpret_cast<uint4*>(a.partial) + (static_cast<size_t>(frame) * gridDim.x + blockIdx.x) * (kHistoPartialWords / 4) + tid;
 #pragma unroll
       for (int j = 0; j < 8; ++j) dst[j * kScanThreads] = make_uint4(hacc[4 * j], hacc[4 * j + 1], hacc[4 * j + 2], hacc[4 * j + 3]);
