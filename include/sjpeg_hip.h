@@ -427,6 +427,48 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* engine, int format, int 
                                       int qdelta_max_luma, int qdelta_max_chroma,
                                       void* d_out, uint64_t* d_sizes, void* stream);
 
+/* ---- ragged batches with the reference's SJPEG_YUV_AUTO decision and the sharp conversion ----
+ * sjpeg_hip_riskiness_ragged_src: d_sums[nframes][3] (device), frame f's what sjpeg_hip_riskiness_sums() makes of that
+ *   picture alone (all zero for a 1 x N or N x 1 frame).  format: RGB, BGRA or RGBA; frames[] as above, out_offset /
+ *   out_capacity ignored; any row stride, negative ones too.  d_table: the 117649-byte table in device memory, or NULL:
+ *   the table SjpegRiskiness() uses (installed, SJPEG_HIP_RISKINESS_TABLE, riskiness.bin beside the library; the
+ *   engine keeps a device copy).  Asynchronous on `stream`.
+ * sjpeg_hip_riskiness_verdict: SjpegRiskiness' arithmetic (src/jpeg_tools.cc:212-236) on one frame's three sums, host
+ *   only: the SjpegYUVMode it decides; *risk (if not NULL) the score 0..100.
+ * sjpeg_hip_sharp_yuv_ragged: the sharp conversion of every frame into its own tightly packed planes d_y[f] (width x
+ *   height), d_u[f], d_v[f] (((width+1)/2) x ((height+1)/2)) -- host arrays of device pointers --, each frame's bytes
+ *   those of sjpeg_hip_sharp_yuv() for that picture alone.  d_workspace: sjpeg_hip_sharp_ragged_workspace() bytes of
+ *   device memory.  Asynchronous on `stream` only; the sweeps' launches never hold more workgroups than the device holds
+ *   at once.
+ * sjpeg_hip_encode_ragged_auto_src: sjpeg_hip_encode_ragged_batch_src() with the SjpegYUVMode of EncoderParam:
+ *   SJPEG_YUV_AUTO (0): the riskiness of every frame decides its mode (420, sharp 420, 444 or 400), as
+ *   SjpegEncode(..., SJPEG_YUV_AUTO) decides it for that picture alone; SJPEG_YUV_SHARP (2): every frame goes through
+ *   the sharp conversion; 1, 3, 4 (= SJPEG_HIP_YUV420 / 444 / 400): exactly sjpeg_hip_encode_ragged_batch_src().
+ *   AUTO and SHARP take RGB, BGRA or RGBA sources.  modes[f] (host, or NULL): the SjpegYUVMode frame f was coded with.
+ *   Frame f's bytes are what SjpegEncode(picture, q, method, yuv_mode) makes of it alone; d_sizes[f] and the output
+ *   ranges are in the caller's frame order; sjpeg_hip_frame_bound(w, h, SJPEG_HIP_YUV444, 2048) is always enough.
+ *   Host waits: the riskiness sums (AUTO only), then those of sjpeg_hip_encode_ragged_batch_src() once over all modes.
+ *   The sharp planes and workspace count against SJPEG_HIP_SCRATCH_LIMIT_BYTES: past it, the call goes in parts of
+ *   consecutive frames.  SJPEG_HIP_EINVAL for every check of sjpeg_hip_encode_ragged_batch_src(), yuv_mode outside
+ *   0..4, AUTO or SHARP with another source format, methods outside 0..6. */
+int sjpeg_hip_riskiness_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                   const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                   const uint8_t* d_table /*or NULL*/, uint64_t* d_sums /*[nframes][3]*/,
+                                   void* stream);
+int sjpeg_hip_riskiness_verdict(const uint64_t sums[3], int width, int height, float* risk);
+size_t sjpeg_hip_sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames);
+int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* engine, int format, int nframes,
+                               const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                               uint8_t* const* d_y, uint8_t* const* d_u, uint8_t* const* d_v,
+                               void* d_workspace, size_t workspace_size, void* stream);
+int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const uint8_t (*quant)[2][64], int quant_per_frame,
+                                     const uint8_t* min_quant /*[2][64] or NULL*/, int q_bias, int method,
+                                     int qdelta_max_luma, int qdelta_max_chroma,
+                                     void* d_out, uint64_t* d_sizes, int* modes /*[nframes], host, or NULL*/,
+                                     void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -248,6 +248,20 @@ def lib() -> C.CDLL:
                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]
     L.sjpeg_hip_encode_ragged_batch_src.restype = C.c_int
+    L.sjpeg_hip_riskiness_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_riskiness_ragged_src.restype = C.c_int
+    L.sjpeg_hip_riskiness_verdict.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.sjpeg_hip_riskiness_verdict.restype = C.c_int
+    L.sjpeg_hip_sharp_ragged_workspace.argtypes = [C.c_int, C.POINTER(RaggedFrame)]
+    L.sjpeg_hip_sharp_ragged_workspace.restype = C.c_size_t
+    L.sjpeg_hip_sharp_yuv_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sjpeg_hip_sharp_yuv_ragged.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_auto_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_encode_ragged_auto_src.restype = C.c_int
     _lib = L
     return L
 
@@ -280,6 +294,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_comm_rank", "sjpeg_hip_comm_world", "sjpeg_hip_gather_rows", "sjpeg_hip_gather_bytes",
     "sjpeg_hip_gather_streams", "sjpeg_hip_encode_scan_packed_src", "sjpeg_hip_encode_ragged_src",
     "sjpeg_hip_scan_histogram_ragged_src", "sjpeg_hip_scan_symbol_stats_ragged_src", "sjpeg_hip_encode_ragged_batch_src",
+    "sjpeg_hip_riskiness_ragged_src", "sjpeg_hip_riskiness_verdict", "sjpeg_hip_sharp_ragged_workspace",
+    "sjpeg_hip_sharp_yuv_ragged", "sjpeg_hip_encode_ragged_auto_src",
 ]
 
 
@@ -1009,6 +1025,85 @@ class Engine:
                   "sjpeg_hip_encode_ragged_batch_src")
         return out, sizes, list(offsets)
 
+    def riskiness_ragged(self, fmt, planes_per_frame, dims, table=None):
+        """sjpeg_hip_riskiness_ragged_src: the three riskiness sums of pictures of different sizes in one call (fmt:
+        SRC_RGB / SRC_BGRA / SRC_RGBA; planes_per_frame, dims as encode_ragged).  table: the 117649-byte score table
+        (bytes or a CUDA uint8 tensor; default None: the table SjpegRiskiness uses -- set_riskiness_table,
+        SJPEG_HIP_RISKINESS_TABLE, riskiness.bin beside the library).  Returns an int64 CUDA tensor [F, 3],
+        frame k's what sjpeg_hip_riskiness_sums makes of it alone.  Asynchronous on the current torch stream."""
+        import torch
+        dev = _ragged_device(planes_per_frame)
+        d_table = None
+        if table is not None:
+            d_table = table if isinstance(table, torch.Tensor) else \
+                torch.frombuffer(bytearray(table), dtype=torch.uint8).to(dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        sums = torch.zeros((len(dims), 3), dtype=torch.int64, device=dev)
+        self._chk(lib().sjpeg_hip_riskiness_ragged_src(self._h, fmt, len(dims), frames,
+                                                       d_table.data_ptr() if d_table is not None else None,
+                                                       sums.data_ptr(), self._stream()),
+                  "sjpeg_hip_riskiness_ragged_src")
+        return sums
+
+    def sharp_yuv_ragged(self, fmt, planes_per_frame, dims):
+        """sjpeg_hip_sharp_yuv_ragged: the sharp conversion of pictures of different sizes in one call.  Returns a list
+        of (y [H, W], u [ch, cw], v [ch, cw]) uint8 CUDA tensors, frame k's what sharp_yuv makes of it alone.
+        Asynchronous on the current torch stream."""
+        import torch
+        n = len(dims)
+        dev = _ragged_device(planes_per_frame)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        planes = []
+        for (w, h) in dims:
+            cw, ch = (w + 1) // 2, (h + 1) // 2
+            planes.append((torch.empty((h, w), dtype=torch.uint8, device=dev),
+                           torch.empty((ch, cw), dtype=torch.uint8, device=dev),
+                           torch.empty((ch, cw), dtype=torch.uint8, device=dev)))
+        ptrs = [(C.c_void_p * n)(*[p[i].data_ptr() for p in planes]) for i in range(3)]
+        wsz = lib().sjpeg_hip_sharp_ragged_workspace(n, frames)
+        work = torch.empty(max(int(wsz), 16), dtype=torch.uint8, device=dev)
+        self._chk(lib().sjpeg_hip_sharp_yuv_ragged(self._h, fmt, n, frames, ptrs[0], ptrs[1], ptrs[2], work.data_ptr(),
+                                                   wsz, self._stream()),
+                  "sjpeg_hip_sharp_yuv_ragged")
+        self._keep = (work, planes)                  # (alive until the stream has used them)
+        return planes
+
+    def encode_ragged_auto(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
+                           dmax_luma=12, dmax_chroma=1, capacities=None, out=None, offsets=None, sizes=None):
+        """sjpeg_hip_encode_ragged_auto_src: encode_ragged_batch with the SjpegYUVMode of EncoderParam -- YUV_AUTO (the
+        riskiness of every frame decides), YUV_SHARP, or YUV_420 / 444 / 400 (= encode_ragged_batch).  Frame k's bytes
+        are what SjpegEncode(picture, q, method, yuv_mode) makes of it alone.  capacities default:
+        frame_bound(w, h, YUV_444, 2048).  Returns (out, sizes, offsets, modes): modes[k] the SjpegYUVMode frame k was
+        coded with (YUV_SHARP for sharp frames).  The host waits inside for the analysis; the encode is asynchronous."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged_auto: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(quant, (list, tuple))
+        if per_frame and len(quant) != n:
+            raise SjpegError("encode_ragged_auto: one starting matrix per frame")
+        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+        if capacities is None:
+            capacities = [frame_bound(w, h, YUV_444, 2048) for (w, h) in dims]
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
+        modes = (C.c_int * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_auto_src(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data,
+                                                         int(per_frame), mq.ctypes.data if mq is not None else None,
+                                                         q_bias, int(method), dmax_luma, dmax_chroma, out.data_ptr(),
+                                                         sizes.data_ptr(), modes, self._stream()),
+                  "sjpeg_hip_encode_ragged_auto_src")
+        return out, sizes, list(offsets), [int(m) for m in modes]
+
+
+def riskiness_verdict(sums, w, h):
+    """sjpeg_hip_riskiness_verdict: (SjpegYUVMode, risk) of one frame's three riskiness sums (SjpegRiskiness'
+    arithmetic, host only)."""
+    arr = (C.c_uint64 * 3)(*[int(x) for x in sums])
+    risk = C.c_float(0)
+    mode = lib().sjpeg_hip_riskiness_verdict(arr, int(w), int(h), C.byref(risk))
+    return int(mode), float(risk.value)
+
 
 def _ragged_device(planes_per_frame):
     import torch
@@ -1066,9 +1161,16 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
         raise SjpegError("encode_images: trellis methods 7 and 8 go through the host API (SjpegEncode / sjpeg::Encode)")
     if method < 0 or method > 8:
         raise SjpegError(f"encode_images: method {method} is not one of 0..6")
+    yuv_mode = int(yuv_mode)
+    if yuv_mode < 0 or yuv_mode > 4:
+        raise SjpegError(f"encode_images: yuv_mode {yuv_mode} is not one of 0..4 (SjpegYUVMode)")
     images = list(images)
     if not images:
         raise SjpegError("encode_images: no images")
+    if yuv_mode in (YUV_AUTO, YUV_SHARP):
+        for k, im in enumerate(images):
+            if len(getattr(im, "shape", ())) != 3 or im.shape[2] != 3:
+                raise SjpegError(f"encode_images: image {k}: YUV_AUTO and YUV_SHARP take RGB pictures [H, W, 3]")
     n = len(images)
     qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
     if len(qs) != n:
@@ -1089,17 +1191,16 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
     dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
-    if method != 0:
-        made = {}
-        for q in qs:
-            if float(q) not in made:
-                m = np.zeros((2, 64), np.uint8)
-                lib().sjpeg_hip_quality_matrices(float(q), m.ctypes.data)
-                made[float(q)] = m
-        quant = [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
+    if yuv_mode in (YUV_AUTO, YUV_SHARP):
         with torch.cuda.device(dev):
-            out, sizes, offs = eng.encode_ragged_batch(SRC_RGB, planes, dims, yuv_mode, quant, method, min_quant, q_bias,
-                                                       dmax_luma, dmax_chroma)
+            out, sizes, offs, _ = eng.encode_ragged_auto(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                                         min_quant, q_bias, dmax_luma, dmax_chroma)
+            eng.wait()                           # (pipelined mode: the output is complete after this)
+            return _fetch_ragged(out, sizes, offs)
+    if method != 0:
+        with torch.cuda.device(dev):
+            out, sizes, offs = eng.encode_ragged_batch(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                                       min_quant, q_bias, dmax_luma, dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
     made = {}
@@ -1117,6 +1218,43 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
                                              headers)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return _fetch_ragged(out, sizes, offs)
+
+
+def _quality_quant(qs):
+    """The starting matrices of the qualities qs: one [2][64] matrix when they are all equal, else a list."""
+    made = {}
+    for q in qs:
+        if float(q) not in made:
+            m = np.zeros((2, 64), np.uint8)
+            lib().sjpeg_hip_quality_matrices(float(q), m.ctypes.data)
+            made[float(q)] = m
+    return [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
+
+
+def compress_images(images, quality=75.0, engine=None):
+    """The batch SjpegCompress(): JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each
+    what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call."""
+    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4)
+
+
+def riskiness_images(images, engine=None):
+    """[(SjpegYUVMode, risk)] of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each what SjpegRiskiness says
+    of it alone, from one ragged riskiness call."""
+    import torch
+    images = list(images)
+    if not images:
+        raise SjpegError("riskiness_images: no images")
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
+                im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+            raise SjpegError(f"riskiness_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+    dev = images[0].device
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    eng = engine or Engine(dev.index or 0)
+    with torch.cuda.device(dev):
+        sums = eng.riskiness_ragged(SRC_RGB, planes, dims).cpu().numpy()
+    return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
 
 
 def _fetch_ragged(out, sizes, offsets):

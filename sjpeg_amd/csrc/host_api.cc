@@ -140,6 +140,11 @@ bool LoadRiskTableFromEnv() {                      // under g_risk_mutex
   return false;
 }
 
+const char* const kNoRiskTable =
+    "the riskiness score table was not found: SJPEG_YUV_AUTO / SjpegCompress / SjpegRiskiness need "
+    "riskiness.bin (shipped next to libsjpeg_amd.so; a copy of the library installed elsewhere needs it "
+    "beside it, the file named by SJPEG_HIP_RISKINESS_TABLE, or sjpeg_hip_set_riskiness_table())";
+
 // SjpegRiskiness' arithmetic on the three sums (src/jpeg_tools.cc:212-236)
 SjpegYUVMode RiskVerdict(uint64_t score_sum, uint64_t score_num, uint64_t gray_num, int width, int height,
                          float* risk) {
@@ -239,11 +244,7 @@ struct DeviceContext {
   // the caller's riskiness table on this device; false (with the reason) if none was supplied
   bool EnsureRiskTable() {
     std::lock_guard<std::mutex> lock(g_risk_mutex);
-    if (!LoadRiskTableFromEnv()) {
-      return Fail("the riskiness score table was not found: SJPEG_YUV_AUTO / SjpegCompress / SjpegRiskiness need "
-                  "riskiness.bin (shipped next to libsjpeg_amd.so; a copy of the library installed elsewhere needs it "
-                  "beside it, the file named by SJPEG_HIP_RISKINESS_TABLE, or sjpeg_hip_set_riskiness_table())");
-    }
+    if (!LoadRiskTableFromEnv()) return Fail(kNoRiskTable);
     if (risk_generation == g_risk_generation) return true;
     if (d_risk == nullptr && hipMalloc(&d_risk, SJPEG_HIP_RISKINESS_TABLE_SIZE) != hipSuccess) return Fail("hipMalloc failed");
     if (d_sums == nullptr && hipMalloc(reinterpret_cast<void**>(&d_sums), 3 * sizeof(uint64_t)) != hipSuccess) return Fail("hipMalloc failed");
@@ -1168,6 +1169,14 @@ int sjpeg_hip_set_riskiness_table(const uint8_t* table, size_t size) {
   return 0;
 }
 
+int sjpeg_hip_riskiness_verdict(const uint64_t sums[3], int width, int height, float* risk) {
+  if (sums == nullptr || width <= 0 || height <= 0) {
+    if (risk != nullptr) *risk = -1.f;
+    return SJPEG_YUV_AUTO;
+  }
+  return RiskVerdict(sums[0], sums[1], sums[2], width, height, risk);
+}
+
 int sjpeg_hip_has_riskiness_table(void) {
   std::lock_guard<std::mutex> lock(g_risk_mutex);
   return LoadRiskTableFromEnv() ? 1 : 0;
@@ -1245,3 +1254,20 @@ bool SjpegCompress(const uint8_t* rgb, int width, int height, float quality, std
   param.SetQuality(quality);
   return sjpeg::Encode(rgb, width, height, 3 * width, param, output);
 }
+
+namespace sjpeg_internal {
+
+// The riskiness table for the engine's device copy (sjpeg_hip_encode_ragged_auto_src), found where the host API finds
+// it: false (with the host API's message) when there is none; *table gets a copy when the installed table is not the
+// one of *generation.
+bool RiskTableSnapshot(int* generation, std::vector<uint8_t>* table, std::string* err) {
+  std::lock_guard<std::mutex> lock(g_risk_mutex);
+  if (!LoadRiskTableFromEnv()) { *err = kNoRiskTable; return false; }
+  if (*generation != g_risk_generation) {
+    *table = g_risk_table;
+    *generation = g_risk_generation;
+  }
+  return true;
+}
+
+}  // namespace sjpeg_internal

@@ -8,8 +8,10 @@
 // riskiness.bin (riskiness.NOTICE), or comes from sjpeg_hip_set_riskiness_table / SJPEG_HIP_RISKINESS_TABLE.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "sjpeg_hip.h"
+#include "ragged_aux.h"
 
 namespace {
 
@@ -49,36 +51,31 @@ __global__ __launch_bounds__(256) void risk_scan(const RiskArgs a) {
   const int rows = a.H - 1;                                    // positions (i, j), j = 1 .. H - 1 (the row below)
   const int per = (rows + static_cast<int>(gridDim.y) - 1) / static_cast<int>(gridDim.y);
   const int j0 = 1 + static_cast<int>(blockIdx.y) * per, j1 = min(j0 + per, a.H);
-  unsigned long long s_sum = 0;
-  uint32_t s_num = 0, g_num = 0;
-  if (i < a.W - 1 && j0 < j1) {
-    const uint8_t* row = a.rgb + frame * a.frame_stride + static_cast<long long>(j0 - 1) * a.row_stride;
-    const long long o0 = static_cast<long long>(i) * a.pix_step, o1 = o0 + a.pix_step;
-    int idx0 = yuv_index(row + o0, a.r_off, a.g_off, a.b_off);
-    constexpr int gray = (kCells / 2) * (1 + kCells) * kCells;
-    constexpr int gray_min = gray - gray % kCells;             // idx = y + 7 * (u + 7 * v): neutral chroma <=> [gray_min, gray_min + 7)
-    for (int j = j0; j < j1; ++j) {
-      const int idx1 = yuv_index(row + o1, a.r_off, a.g_off, a.b_off);
-      row += a.row_stride;
-      const int idx2 = yuv_index(row + o0, a.r_off, a.g_off, a.b_off);
-      const int score = a.table[idx0 + kCells3 * idx1] + a.table[idx0 + kCells3 * idx2] + a.table[idx1 + kCells3 * idx2];
-      if (score > kNoiseLevel) { s_sum += static_cast<unsigned long long>(score); ++s_num; }
-      g_num += (idx0 >= gray_min && idx0 < gray_min + kCells) ? 1u : 0u;
-      idx0 = idx2;
-    }
+#include "risk_scan_body.inc"
+}
+
+// The ragged form: a flat grid over the batch's workgroups; a workgroup finds its frame by a binary search over the
+// frames' first workgroups, then runs the same body on a copy of the arguments rebased to that frame.
+__global__ __launch_bounds__(256) void risk_scan_ragged(const RiskArgs common, const sjpeg_internal::RiskFrame* frames, int nframes) {
+  __shared__ unsigned long long part[4][3];
+  const unsigned wg = blockIdx.x;
+  int lo = 0, hi = nframes - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (frames[mid].wg_base <= wg) lo = mid; else hi = mid - 1;
   }
-  unsigned long long n_sum = s_num, gn_sum = g_num;
-  for (int d = 32; d > 0; d >>= 1) {
-    s_sum += __shfl_down(s_sum, d, 64); n_sum += __shfl_down(n_sum, d, 64); gn_sum += __shfl_down(gn_sum, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    part[threadIdx.x >> 6][0] = s_sum; part[threadIdx.x >> 6][1] = n_sum; part[threadIdx.x >> 6][2] = gn_sum;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-    if (v) atomicAdd(&a.out[static_cast<size_t>(frame) * 3 + threadIdx.x], v);
-  }
+  const sjpeg_internal::RiskFrame d = frames[lo];
+  RiskArgs a = common;
+  a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.W = d.W; a.H = d.H;
+  a.out = common.out + static_cast<size_t>(lo) * 3;
+  const unsigned local = wg - d.wg_base;
+  const int frame = 0;
+  const int i = (local % static_cast<unsigned>(d.cols)) * 256 + threadIdx.x;
+  const int rows = a.H - 1;
+  const int per = (rows + d.bands - 1) / d.bands;
+  const int j0 = 1 + static_cast<int>(local / static_cast<unsigned>(d.cols)) * per, j1 = min(j0 + per, a.H);
+#include "risk_scan_body.inc"
 }
 
 }  // namespace
@@ -90,12 +87,7 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
     return SJPEG_HIP_EINVAL;
   }
   RiskArgs a;
-  switch (src->format) {
-    case SJPEG_HIP_SRC_RGB: a.pix_step = 3; a.r_off = 0; a.g_off = 1; a.b_off = 2; break;
-    case SJPEG_HIP_SRC_BGRA: a.pix_step = 4; a.r_off = 2; a.g_off = 1; a.b_off = 0; break;
-    case SJPEG_HIP_SRC_RGBA: a.pix_step = 4; a.r_off = 0; a.g_off = 1; a.b_off = 2; break;
-    default: return SJPEG_HIP_EINVAL;
-  }
+  if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   a.rgb = static_cast<const uint8_t*>(src->plane[0]);
   a.row_stride = src->row_stride[0]; a.frame_stride = src->frame_stride[0];
@@ -108,3 +100,20 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
   hipLaunchKernelGGL(risk_scan, dim3((width - 1 + 255) / 256, bands, nframes), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : SJPEG_HIP_ERUNTIME;
 }
+
+namespace sjpeg_internal {
+
+int risk_ragged_launch(int format, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
+                       const uint8_t* d_table, uint64_t* d_sums, hipStream_t st) {
+  RiskArgs a;
+  memset(&a, 0, sizeof(a));
+  if (!sjpeg_internal::rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
+  a.table = d_table;
+  a.out = reinterpret_cast<unsigned long long*>(d_sums);
+  if (hipMemsetAsync(d_sums, 0, static_cast<size_t>(nframes) * 3 * sizeof(uint64_t), st) != hipSuccess) return SJPEG_HIP_ERUNTIME;
+  if (total_wgs == 0) return 0;                                // every frame 1 x N or N x 1
+  hipLaunchKernelGGL(risk_scan_ragged, dim3(total_wgs), dim3(256), 0, st, a, d_frames, nframes);
+  return hipGetLastError() == hipSuccess ? 0 : SJPEG_HIP_ERUNTIME;
+}
+
+}  // namespace sjpeg_internal

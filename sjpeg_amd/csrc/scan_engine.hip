@@ -42,8 +42,10 @@
 #include <string>
 #include <chrono>
 #include <vector>
+#include <functional>
 
 #include "sjpeg_hip.h"
+#include "ragged_aux.h"
 
 namespace {
 
@@ -219,6 +221,13 @@ struct sjpeg_hip_engine {
   // offsets and header bytes, uploaded as one blob -- buffers of its own, so that nothing the uniform calls hold or
   // upload on the stitch stream is touched
   DevBuf<uint4> ragged;
+  // ragged calls with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP (sjpeg_hip_encode_ragged_auto_src): the riskiness table of this
+  // device (uploaded again when sjpeg_hip_set_riskiness_table changes it), the riskiness descriptors and sums, the sizes
+  // of the mode groups before they go back to the caller's order, and the sharp frames' planes and workspace
+  DevBuf<uint8_t> risk_table;
+  int risk_generation = -1;
+  DevBuf<uint4> auto_buf;
+  DevBuf<uint4> sharp_arena;
   // side_done is recorded LAZILY, by whoever is about to wait on it (side_mark): an event record is a packet in the
   // queue and about 5 us of host time, and a loop of pipelined calls needs none -- one frame per call was bound by the
   // HOST at five event calls per call (36-46 us against 35 of device time, `tools/one_frame_piped.py`)
@@ -659,6 +668,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->tables.release(); e->header.release(); e->seg_words.release(); e->seg_nbits.release(); e->pool.release(); e->pool_ctr.release(); e->seg_xbase.release(); e->replay.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
+  e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -683,6 +693,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->replay.release();
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
+  e->auto_buf.release(); e->sharp_arena.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -786,7 +797,8 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   for (auto* l : e->lane) if (l != nullptr) lanes += sjpeg_hip_engine_scratch_bytes(l);
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
-         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged);
+         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) +
+         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -2426,6 +2438,237 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
 // The flow of sjpeg_hip_encode_batch_src over frames of different sizes: the ragged histogram, the adaptation kernels with
 // a starting matrix per frame, one read-back and wait; the tables; the ragged statistics, one read-back and wait; the
 // Huffman codes and the headers on the host; the ragged encode.  No lanes, no parts, no coefficients kept between passes.
+// The frames come in MODE GROUPS (sjpeg_hip_encode_ragged_auto_src: RGB 4:2:0, 4:4:4, 4:0:0 and the sharp frames' planar
+// 4:2:0 -- K1 is templated on the mode, so a group is a grid of its own): every pass runs over all groups before its
+// one wait, so the host waits do not grow with the number of groups.  sjpeg_hip_encode_ragged_batch_src is one group.
+namespace {
+
+struct RaggedGroup {
+  int format = 0, yuv_mode = 0;                   // SJPEG_HIP_SRC_*, SJPEG_HIP_YUV*
+  std::vector<sjpeg_hip_ragged_frame> frames;     // in group order
+  std::vector<int> index;                         // the caller's number of each frame
+  ScanArgs a;                                     // the format's fields (ragged_format)
+  int cls = kSrcPlanes, nplanes = 1;
+  std::vector<FrameGeo> geo;
+};
+
+__global__ __launch_bounds__(256) void scatter_sizes_kernel(const unsigned long long* sizes, const uint32_t* index, int n,
+                                                            unsigned long long* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[index[i]] = sizes[i];
+}
+
+// The method 0..6 flow over the groups (their frames checked, their format fields and geometry set).  d_sizes: the
+// caller's sizes; with more than one group, or frames out of the caller's order, the groups' sizes land in the engine's
+// auto_buf first and one kernel scatters them.  last_ready (may be empty): enqueues what the LAST group's frames are
+// made of (the sharp conversion), right in front of the first kernel that reads them -- behind the other groups' first
+// pass, so that the few uploads between it and the pass's wait never have to wait for it on the host (the engine's
+// staging ring holds four uploads).
+int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector<RaggedGroup>& groups,
+                        const uint8_t (*quant_in)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias,
+                        int method, int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                        hipStream_t st, const std::function<int()>& last_ready = {}) {
+  const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3);
+  size_t n = 0;
+  std::vector<size_t> gbase;
+  for (const RaggedGroup& g : groups) { gbase.push_back(n); n += g.frames.size(); }
+  if (n == 0) return 0;
+  bool last_made = !last_ready;
+  auto ready = [&](size_t gi) -> int {
+    if (last_made || gi + 1 != groups.size()) return 0;
+    last_made = true;
+    return last_ready();
+  };
+  // every frame's starting matrices and tables, as sjpeg_hip_encode_batch_src makes them of its one matrix; frame k of
+  // group g is frame gbase[g] + k of the call here
+  std::vector<sjpeg_hip_scan_tables> tables(n);
+  std::vector<uint8_t> quant(n * 128);
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    for (size_t k = 0; k < groups[gi].frames.size(); ++k) {
+      const size_t f = gbase[gi] + k;
+      uint8_t* const q = &quant[f * 128];
+      memcpy(q, quant_in[quant_per_frame ? groups[gi].index[k] : 0], 128);
+      memset(&tables[f], 0, sizeof(tables[f]));
+      sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(q), min_quant, q_bias, &tables[f]);
+      sjpeg_hip_default_huffman(&tables[f]);
+    }
+  }
+  static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
+  const auto t_start = std::chrono::steady_clock::now();
+  auto mark = [&](const char* what) {
+    if (batch_debug) fprintf(stderr, "ragged %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
+  };
+  constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
+  constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
+  constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
+  // the analysis goes in chunks of consecutive frames of a group whose scratch -- the pass's partials (the histogram's
+  // at most one per segment) and the per-frame results -- stays inside the engine's limit
+  auto chunks_of = [&](const RaggedGroup& g, size_t per_seg, size_t per_frame) {
+    std::vector<std::pair<size_t, size_t>> c;      // (first frame, frames)
+    const size_t ng = g.frames.size();
+    size_t f0 = 0, bytes = 0;
+    for (size_t f = 0; f < ng; ++f) {
+      const size_t b = static_cast<size_t>(g.geo[f].nseg) * per_seg + per_frame;
+      if (f > f0 && bytes + b > e->scratch_limit) { c.emplace_back(f0, f - f0); f0 = f; bytes = 0; }
+      bytes += b;
+    }
+    c.emplace_back(f0, ng - f0);
+    return c;
+  };
+  BatchScratch& sc = g_batch;
+  if (sc.device != e->device) { if (sc.device >= 0) { (void)hipSetDevice(sc.device); sc.Drop(); } sc.device = e->device; }
+  HIP_TRY(hipSetDevice(e->device));
+  if (!sc.EnsurePinned(n * (adaptive ? 128 : 0) + (optimize ? n * kFreq : 0) + 16) || !sc.EnsureEvents()) {
+    return fail(SJPEG_HIP_ENOMEM, "hipHostMalloc / hipEventCreate(batch scratch) failed");
+  }
+  uint8_t* const h_q = static_cast<uint8_t*>(sc.h_pinned);                     // [n][128]
+  uint8_t* const h_freq = h_q + (adaptive ? n * 128 : 0);                       // [n][kFreq]
+  auto read_back = [&](void* h_dst, const void* d_src, size_t bytes) -> int {
+    void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
+    return copy_by_kernel(dv, d_src, bytes, st, hipMemcpyDeviceToHost, d_src, h_dst);
+  };
+  if (adaptive) {
+    // 1. histograms, the adaptation with each frame's own starting matrices, the adapted matrices back
+    std::vector<std::vector<std::pair<size_t, size_t>>> chunks;
+    size_t most = 0;
+    for (const RaggedGroup& g : groups) {
+      chunks.push_back(chunks_of(g, kHistoPartialWords * sizeof(uint32_t), kHist + kSums + kTot));
+      for (const auto& c : chunks.back()) most = std::max(most, c.second);
+    }
+    // d_sums: [chunk][kSums] | [chunk][kTot] | the starting matrices [n][128] | the adapted ones [n][128]
+    if (!sc.Ensure(&sc.d_hist, &sc.hist_cap, most * kHist) || !sc.Ensure(&sc.d_sums, &sc.sums_cap, most * (kSums + kTot) + n * 256)) {
+      return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
+    }
+    uint8_t* const d_qs = static_cast<uint8_t*>(sc.d_sums) + most * (kSums + kTot);
+    uint8_t* const d_qa = d_qs + n * 128;
+    if (int rc = order_on_stream(e, st)) return rc;
+    if (int rc = upload(e, d_qs, quant.data(), n * 128, st)) return rc;
+    if (int rc = sync_uploads(e, st)) return rc;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const RaggedGroup& g = groups[gi];
+      const int ntab = g.yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
+      if (int rc = ready(gi)) return rc;
+      for (const auto& c : chunks[gi]) {
+        uint32_t* const d_hist = static_cast<uint32_t*>(sc.d_hist);
+        if (int rc = ragged_analysis(e, true, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+                                     std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
+                                     nullptr, 0, d_hist, st)) return rc;
+        AdaptArgs s;
+        s.hist = d_hist;
+        s.sums = static_cast<long long*>(sc.d_sums);
+        s.totlast = reinterpret_cast<int*>(static_cast<uint8_t*>(sc.d_sums) + c.second * kSums);
+        memset(s.quant, 0, sizeof(s.quant));
+        if (min_quant != nullptr) memcpy(s.min_quant, min_quant, sizeof(s.min_quant)); else memset(s.min_quant, 1, sizeof(s.min_quant));
+        s.quant_f = d_qs + (gbase[gi] + c.first) * 128;
+        hipLaunchKernelGGL(adapt_sums_kernel<true>, dim3(64, 2, c.second), dim3(64), 0, st, s);
+        HIP_TRY(hipGetLastError());
+        DecideArgs d;
+        d.sums = s.sums; d.totlast = s.totlast;
+        d.quant_out = d_qa + (gbase[gi] + c.first) * 128;
+        memset(d.quant_in, 0, sizeof(d.quant_in));
+        d.last_step[0] = qdelta_max_luma + 12;
+        d.last_step[1] = qdelta_max_chroma + 12;
+        d.quant_f = s.quant_f;
+        hipLaunchKernelGGL(adapt_decide_kernel<true>, dim3(ntab, c.second), dim3(64), 0, st, d);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    if (int rc = read_back(h_q, d_qa, n * 128)) return rc;
+    HIP_TRY(hipEventRecord(sc.pass_done, st));
+    mark("hist launched");
+    HIP_TRY(hipEventSynchronize(sc.pass_done));
+    mark("matrices here");
+    // 2. the tables of the adapted matrices
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const int ntab = groups[gi].yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
+      for (size_t f = gbase[gi]; f < gbase[gi] + groups[gi].frames.size(); ++f) {
+        memcpy(&quant[f * 128], h_q + f * 128, static_cast<size_t>(ntab) * 64);
+        sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
+      }
+    }
+  }
+  std::vector<sjpeg_hip_huffman_spec> specs(optimize ? n * 4 : 0);
+  if (optimize) {
+    // 3. the symbol counts with each frame's tables, back to the host
+    std::vector<std::vector<std::pair<size_t, size_t>>> chunks;
+    size_t most = 0;
+    for (const RaggedGroup& g : groups) {
+      chunks.push_back(chunks_of(g, kStatsWords * sizeof(uint32_t), kFreq));
+      for (const auto& c : chunks.back()) most = std::max(most, c.second);
+    }
+    if (!sc.Ensure(&sc.d_freq, &sc.freq_cap, most * kFreq)) return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const RaggedGroup& g = groups[gi];
+      if (int rc = ready(gi)) return rc;
+      for (const auto& c : chunks[gi]) {
+        uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
+        if (int rc = ragged_analysis(e, false, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+                                     std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
+                                     &tables[gbase[gi] + c.first], 1, d_freq, st)) return rc;
+        if (int rc = read_back(h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;
+      }
+    }
+    HIP_TRY(hipEventRecord(sc.pass_done, st));
+    mark("stats launched");
+    HIP_TRY(hipEventSynchronize(sc.pass_done));
+    mark("counts here");
+    // 4. the optimised codes (the host's share that grows with the batch)
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      for (size_t f = gbase[gi]; f < gbase[gi] + groups[gi].frames.size(); ++f) {
+        sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(h_freq + f * kFreq), groups[gi].yuv_mode, &specs[f * 4], &tables[f]);
+      }
+    }
+  }
+  // where the groups' sizes go: the caller's array when there is one group in the caller's order, else auto_buf
+  bool in_order = groups.size() == 1;
+  for (size_t k = 0; in_order && k < groups[0].index.size(); ++k) in_order = groups[0].index[k] == static_cast<int>(k);
+  unsigned long long* d_gsizes = reinterpret_cast<unsigned long long*>(d_sizes);
+  uint32_t* d_index = nullptr;
+  if (!in_order) {
+    if (int rc = e->auto_buf.ensure((n * 12 + 15) / 16 + 1)) return rc;
+    d_gsizes = reinterpret_cast<unsigned long long*>(e->auto_buf.p);
+    d_index = reinterpret_cast<uint32_t*>(d_gsizes + n);
+    std::vector<uint32_t> index(n);
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      for (size_t k = 0; k < groups[gi].index.size(); ++k) index[gbase[gi] + k] = static_cast<uint32_t>(groups[gi].index[k]);
+    }
+    if (int rc = upload(e, d_index, index.data(), n * 4, st)) return rc;
+    if (int rc = sync_uploads(e, st)) return rc;
+  }
+  // 4. (all methods) the headers, each frame's own; 5. the ragged encode of every group, asynchronous on the stream
+  const bool one_table = !quant_per_frame && !adaptive && !optimize;
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    RaggedGroup& g = groups[gi];
+    const size_t ng = g.frames.size();
+    std::vector<uint8_t> headers;
+    std::vector<size_t> offs(ng + 1, 0);
+    uint8_t one[2048];
+    for (size_t k = 0; k < ng; ++k) {
+      const size_t f = gbase[gi] + k;
+      const size_t hs = sjpeg_hip_make_header_ex(g.frames[k].width, g.frames[k].height, g.yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
+                                                 optimize ? &specs[f * 4] : nullptr, one, sizeof(one));
+      if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
+      headers.insert(headers.end(), one, one + hs);
+      offs[k + 1] = headers.size();
+    }
+    if (gi + 1 == groups.size()) mark("tables built");
+    if (int rc = ready(gi)) return rc;
+    const int rc = sjpeg_hip_encode_ragged_src(e, g.format, g.yuv_mode, static_cast<int>(ng), g.frames.data(), &tables[gbase[gi]],
+                                               one_table ? 0 : 1, headers.data(), offs.data(), /*append_eoi=*/1, d_out,
+                                               reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st);
+    if (rc) return rc;
+  }
+  if (!in_order) {
+    hipLaunchKernelGGL(scatter_sizes_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st,
+                       d_gsizes, d_index, static_cast<int>(n), reinterpret_cast<unsigned long long*>(d_sizes));
+    HIP_TRY(hipGetLastError());
+  }
+  mark("encode launched");
+  return 0;
+}
+
+}  // namespace
+
 int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                       const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
                                       int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
@@ -2441,149 +2684,299 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_m
     return fail(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
   }
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  ScanArgs a;
-  int cls = kSrcPlanes, nplanes = 1;
-  std::vector<FrameGeo> geo;
-  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
-  if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
+  std::vector<RaggedGroup> groups(1);
+  RaggedGroup& g = groups[0];
+  if (int rc = ragged_format(who, format, yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
+  if (int rc = ragged_frames(who, format, yuv_mode, g.nplanes, nframes, frames, true, &g.geo)) return rc;
   try {
-    const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3);
-    const int ntab = yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
+    g.format = format; g.yuv_mode = yuv_mode;
+    g.frames.assign(frames, frames + nframes);
+    g.index.resize(nframes);
+    for (int f = 0; f < nframes; ++f) g.index[f] = f;
+    return ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
+                               qdelta_max_chroma, d_out, d_sizes, static_cast<hipStream_t>(stream));
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ---- ragged batches with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP ----
+namespace {
+
+// SjpegYUVMode (include/sjpeg.h); 1, 3 and 4 are SJPEG_HIP_YUV420 / 444 / 400
+enum { SJPEG_YUV_AUTO_ = 0, SJPEG_YUV_420_ = 1, SJPEG_YUV_SHARP_ = 2, SJPEG_YUV_444_ = 3, SJPEG_YUV_400_ = 4 };
+
+// the engine's upload for the sharp conversion's descriptors (sharp_yuv.hip)
+int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStream_t st) {
+  sjpeg_hip_engine* const e = static_cast<sjpeg_hip_engine*>(ctx);
+  if (int rc = upload(e, d_dst, src, bytes, st)) return rc;
+  return sync_uploads(e, st);
+}
+
+// every frame of an RGB / BGRA / RGBA ragged call checked (the message names the frame)
+int rgb_ragged_frames(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames) {
+  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA) {
+    return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA sources");
+  }
+  if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  std::vector<FrameGeo> geo;
+  return ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, false, &geo);
+}
+
+// the ragged riskiness: descriptors into auto_buf (which holds nframes * 3 sums behind them as well), then the launch;
+// d_sums == NULL: the sums go to auto_buf, *sums_at says where
+int risk_ragged(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const uint8_t* d_table,
+                uint64_t* d_sums, hipStream_t st, uint64_t** sums_at) {
+  std::vector<sjpeg_internal::RiskFrame> desc(nframes);
+  unsigned long long total = 0;
+  for (int f = 0; f < nframes; ++f) {
+    sjpeg_internal::RiskFrame& d = desc[f];
+    memset(&d, 0, sizeof(d));
+    d.rgb = static_cast<const uint8_t*>(frames[f].plane[0]);
+    d.row_stride = frames[f].row_stride[0];
+    sjpeg_internal::risk_frame_plan(frames[f].width, frames[f].height, &d);
+    d.wg_base = static_cast<unsigned>(total);
+    total += static_cast<unsigned long long>(d.bands) * static_cast<unsigned long long>(d.cols);
+  }
+  if (total > 0x7fffffffull) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_ragged_src: the batch has too many workgroups");
+  const size_t desc_bytes = align16(sizeof(sjpeg_internal::RiskFrame) * nframes);
+  const size_t need = (desc_bytes + static_cast<size_t>(nframes) * 24 + 15) / 16;
+  if (int rc = e->auto_buf.ensure(std::max(need, e->auto_buf.cap))) return rc;
+  uint8_t* const base = reinterpret_cast<uint8_t*>(e->auto_buf.p);
+  if (d_sums == nullptr) d_sums = reinterpret_cast<uint64_t*>(base + desc_bytes);
+  if (sums_at != nullptr) *sums_at = d_sums;
+  if (int rc = upload(e, base, desc.data(), sizeof(sjpeg_internal::RiskFrame) * nframes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (sjpeg_internal::risk_ragged_launch(format, reinterpret_cast<const sjpeg_internal::RiskFrame*>(base), nframes,
+                                         static_cast<unsigned>(total), d_table, d_sums, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, std::string("risk_scan_ragged launch failed: ") + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
+}
+
+// the call is ordered behind the engine's earlier work (another stream, pipelined mode's stitch stream)
+int ragged_ordered(sjpeg_hip_engine* e, hipStream_t st) {
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = order_on_stream(e, st)) return rc;
+  if (e->side_pending) {
+    if (int rc = side_mark(e)) return rc;
+    HIP_TRY(hipStreamWaitEvent(st, e->side_done, 0));
+  }
+  return 0;
+}
+
+}  // namespace
+
+}  // extern "C"
+
+namespace sjpeg_internal {
+bool RiskTableSnapshot(int* generation, std::vector<uint8_t>* table, std::string* err);   // host_api.cc
+}
+
+extern "C" {
+
+// The riskiness table the host API uses (installed, SJPEG_HIP_RISKINESS_TABLE, riskiness.bin beside the library), in the
+// engine's device copy: uploaded once, and again when sjpeg_hip_set_riskiness_table() changes it.
+static int engine_risk_table(sjpeg_hip_engine* e, const std::string& who, hipStream_t st, const uint8_t** d_table) {
+  std::string err;
+  std::vector<uint8_t> tab;
+  int gen = e->risk_table.p != nullptr ? e->risk_generation : -1;
+  if (!sjpeg_internal::RiskTableSnapshot(&gen, &tab, &err)) return fail(SJPEG_HIP_EINVAL, who + ": " + err);
+  if (!tab.empty()) {
+    if (int rc = e->risk_table.ensure(SJPEG_HIP_RISKINESS_TABLE_SIZE)) return rc;
+    if (int rc = upload(e, e->risk_table.p, tab.data(), SJPEG_HIP_RISKINESS_TABLE_SIZE, st)) return rc;
+    if (int rc = sync_uploads(e, st)) return rc;
+    e->risk_generation = gen;
+  }
+  *d_table = e->risk_table.p;
+  return 0;
+}
+
+int sjpeg_hip_riskiness_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                   const uint8_t* d_table, uint64_t* d_sums, void* stream) {
+  static const std::string who = "sjpeg_hip_riskiness_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || d_sums == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": frames or d_sums == NULL");
+  try {
+    if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t n = static_cast<size_t>(nframes);
-    // every frame's starting matrices and tables, as sjpeg_hip_encode_batch_src makes them of its one matrix
-    std::vector<sjpeg_hip_scan_tables> tables(n);
-    std::vector<uint8_t> quant(n * 128);
-    for (size_t f = 0; f < n; ++f) {
-      uint8_t* const q = &quant[f * 128];
-      memcpy(q, quant_in[quant_per_frame ? f : 0], 128);
-      memset(&tables[f], 0, sizeof(tables[f]));
-      sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(q), min_quant, q_bias, &tables[f]);
-      sjpeg_hip_default_huffman(&tables[f]);
+    if (int rc = ragged_ordered(e, st)) return rc;
+    if (d_table == nullptr) {                        // the table the host API uses
+      if (int rc = engine_risk_table(e, who, st, &d_table)) return rc;
+    }
+    return risk_ragged(e, format, nframes, frames, d_table, d_sums, st, nullptr);
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                               uint8_t* const* d_y, uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace,
+                               size_t workspace_size, void* stream) {
+  static const std::string who = "sjpeg_hip_sharp_yuv_ragged";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  try {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::string err;
+    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA) {
+      return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA sources");
+    }
+    if (int rc = ragged_ordered(e, st)) return rc;
+    if (int rc = sjpeg_internal::sharp_ragged_run(format, nframes, frames, d_y, d_u, d_v, d_workspace, workspace_size, st,
+                                                  engine_upload, e, &err)) {
+      return fail(rc, who + ": " + err);
+    }
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// The flow: the ragged riskiness and ONE read-back (AUTO only), the verdicts on the host, the sharp frames converted into
+// the engine's planes arena, then the method 0..6 flow over up to four mode groups (ragged_batch_groups).  The sharp
+// planes and workspace count against the scratch limit: past it the call goes in parts of consecutive frames.
+int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                     int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                     int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                     int* modes, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_auto_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
+  if (yuv_mode != SJPEG_YUV_AUTO_ && yuv_mode != SJPEG_YUV_SHARP_) {
+    const int rc = sjpeg_hip_encode_ragged_batch_src(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant,
+                                                     q_bias, method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream);
+    if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
+    return rc;
+  }
+  if (frames == nullptr || quant_in == nullptr || d_out == nullptr || d_sizes == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, quant, d_out or d_sizes == NULL");
+  }
+  if (method < 0 || method > 6) return fail(SJPEG_HIP_EINVAL, who + ": methods 0..6 (trellis goes through the host API)");
+  if (qdelta_max_luma < -12 || qdelta_max_luma > 12 || qdelta_max_chroma < -12 || qdelta_max_chroma > 12) {
+    return fail(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
+  }
+  try {
+    if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
+    {
+      std::vector<FrameGeo> geo;                   // (the output ranges)
+      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
     }
     static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
     const auto t_start = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
-      if (batch_debug) fprintf(stderr, "ragged %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
+      if (batch_debug) fprintf(stderr, "auto   %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
     };
-    constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
-    constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
-    constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
-    // the analysis goes in chunks of consecutive frames whose scratch -- the pass's partials (the histogram's at most one
-    // per segment) and the per-frame results -- stays inside the engine's limit
-    auto chunks_of = [&](size_t per_seg, size_t per_frame) {
-      std::vector<std::pair<size_t, size_t>> c;      // (first frame, frames)
+    const size_t n = static_cast<size_t>(nframes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = ragged_ordered(e, st)) return rc;
+    // the auto_buf of the whole call, once: riskiness descriptors and sums, then the groups' sizes and frame numbers
+    if (int rc = e->auto_buf.ensure(std::max((align16(sizeof(sjpeg_internal::RiskFrame) * n) + n * 24 + 15) / 16 + 1, (n * 12 + 15) / 16 + 1))) return rc;
+    std::vector<int> mode(n, SJPEG_YUV_SHARP_);
+    if (yuv_mode == SJPEG_YUV_AUTO_) {
+      // 1. the riskiness of every frame (the table on this device, uploaded again when it changed), one read-back
+      const uint8_t* d_table = nullptr;
+      if (int rc = engine_risk_table(e, who, st, &d_table)) return rc;
+      uint64_t* d_sums = nullptr;
+      if (int rc = risk_ragged(e, format, nframes, frames, d_table, nullptr, st, &d_sums)) return rc;
+      std::vector<uint64_t> sums(n * 3);
+      HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, n * 24, hipMemcpyDeviceToHost, st));
+      mark("risk launched");
+      HIP_TRY(hipStreamSynchronize(st));
+      mark("sums here");
+      // 2. the verdicts, as the host API makes them
+      for (size_t f = 0; f < n; ++f) mode[f] = sjpeg_hip_riskiness_verdict(&sums[f * 3], frames[f].width, frames[f].height, nullptr);
+    }
+    if (modes != nullptr) for (size_t f = 0; f < n; ++f) modes[f] = mode[f];
+    // parts of consecutive frames whose sharp planes and workspace stay inside the scratch limit (one frame at least)
+    auto planes_bytes = [](const sjpeg_hip_ragged_frame& fr) {
+      const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+      return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
+    };
+    std::vector<std::pair<size_t, size_t>> parts;    // [first, end)
+    size_t arena = 0;
+    {
       size_t f0 = 0, bytes = 0;
+      std::vector<sjpeg_hip_ragged_frame> sharp;
+      auto close = [&](size_t end) {
+        const size_t ws = sharp.empty() ? 0 : sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
+        size_t planes = 0;
+        for (const auto& fr : sharp) planes += planes_bytes(fr);
+        arena = std::max(arena, align16(planes) + ws);
+        parts.emplace_back(f0, end);
+        sharp.clear();
+      };
       for (size_t f = 0; f < n; ++f) {
-        const size_t b = static_cast<size_t>(geo[f].nseg) * per_seg + per_frame;
-        if (f > f0 && bytes + b > e->scratch_limit) { c.emplace_back(f0, f - f0); f0 = f; bytes = 0; }
+        if (mode[f] != SJPEG_YUV_SHARP_) continue;
+        const size_t b = planes_bytes(frames[f]) + sjpeg_internal::sharp_ragged_workspace(1, &frames[f]);
+        if (!sharp.empty() && bytes + b > e->scratch_limit) { close(f); f0 = f; bytes = 0; }
+        sharp.push_back(frames[f]);
         bytes += b;
       }
-      c.emplace_back(f0, n - f0);
-      return c;
-    };
-    BatchScratch& sc = g_batch;
-    if (sc.device != e->device) { if (sc.device >= 0) { (void)hipSetDevice(sc.device); sc.Drop(); } sc.device = e->device; }
-    HIP_TRY(hipSetDevice(e->device));
-    if (!sc.EnsurePinned(n * (adaptive ? 128 : 0) + (optimize ? n * kFreq : 0) + 16) || !sc.EnsureEvents()) {
-      return fail(SJPEG_HIP_ENOMEM, "hipHostMalloc / hipEventCreate(batch scratch) failed");
+      close(n);
     }
-    uint8_t* const h_q = static_cast<uint8_t*>(sc.h_pinned);                     // [n][128]
-    uint8_t* const h_freq = h_q + (adaptive ? n * 128 : 0);                       // [n][kFreq]
-    auto read_back = [&](void* h_dst, const void* d_src, size_t bytes) -> int {
-      void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
-      return copy_by_kernel(dv, d_src, bytes, st, hipMemcpyDeviceToHost, d_src, h_dst);
-    };
-    if (adaptive) {
-      // 1. histograms, the adaptation with each frame's own starting matrices, the adapted matrices back
-      const auto chunks = chunks_of(kHistoPartialWords * sizeof(uint32_t), kHist + kSums + kTot);
-      size_t most = 0;
-      for (const auto& c : chunks) most = std::max(most, c.second);
-      // d_sums: [chunk][kSums] | [chunk][kTot] | the starting matrices [n][128] | the adapted ones [n][128]
-      if (!sc.Ensure(&sc.d_hist, &sc.hist_cap, most * kHist) || !sc.Ensure(&sc.d_sums, &sc.sums_cap, most * (kSums + kTot) + n * 256)) {
-        return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
-      }
-      uint8_t* const d_qs = static_cast<uint8_t*>(sc.d_sums) + most * (kSums + kTot);
-      uint8_t* const d_qa = d_qs + n * 128;
-      if (int rc = order_on_stream(e, st)) return rc;
-      if (int rc = upload(e, d_qs, quant.data(), n * 128, st)) return rc;
-      if (int rc = sync_uploads(e, st)) return rc;
-      for (const auto& c : chunks) {
-        uint32_t* const d_hist = static_cast<uint32_t*>(sc.d_hist);
-        if (int rc = ragged_analysis(e, true, yuv_mode, cls, a, nplanes, static_cast<int>(c.second), frames + c.first,
-                                     std::vector<FrameGeo>(geo.begin() + c.first, geo.begin() + c.first + c.second),
-                                     nullptr, 0, d_hist, st)) return rc;
-        AdaptArgs s;
-        s.hist = d_hist;
-        s.sums = static_cast<long long*>(sc.d_sums);
-        s.totlast = reinterpret_cast<int*>(static_cast<uint8_t*>(sc.d_sums) + c.second * kSums);
-        memset(s.quant, 0, sizeof(s.quant));
-        if (min_quant != nullptr) memcpy(s.min_quant, min_quant, sizeof(s.min_quant)); else memset(s.min_quant, 1, sizeof(s.min_quant));
-        s.quant_f = d_qs + c.first * 128;
-        hipLaunchKernelGGL(adapt_sums_kernel<true>, dim3(64, 2, c.second), dim3(64), 0, st, s);
-        HIP_TRY(hipGetLastError());
-        DecideArgs d;
-        d.sums = s.sums; d.totlast = s.totlast;
-        d.quant_out = d_qa + c.first * 128;
-        memset(d.quant_in, 0, sizeof(d.quant_in));
-        d.last_step[0] = qdelta_max_luma + 12;
-        d.last_step[1] = qdelta_max_chroma + 12;
-        d.quant_f = s.quant_f;
-        hipLaunchKernelGGL(adapt_decide_kernel<true>, dim3(ntab, c.second), dim3(64), 0, st, d);
-        HIP_TRY(hipGetLastError());
-      }
-      if (int rc = read_back(h_q, d_qa, n * 128)) return rc;
-      HIP_TRY(hipEventRecord(sc.pass_done, st));
-      mark("hist launched");
-      HIP_TRY(hipEventSynchronize(sc.pass_done));
-      mark("matrices here");
-      // 2. the tables of the adapted matrices
-      for (size_t f = 0; f < n; ++f) {
-        memcpy(&quant[f * 128], h_q + f * 128, static_cast<size_t>(ntab) * 64);
-        sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
-      }
+    if (arena > 0) {
+      if (int rc = e->sharp_arena.ensure(arena / 16 + 1)) return rc;
     }
-    std::vector<sjpeg_hip_huffman_spec> specs(optimize ? n * 4 : 0);
-    if (optimize) {
-      // 3. the symbol counts with each frame's tables, back to the host
-      const auto chunks = chunks_of(kStatsWords * sizeof(uint32_t), kFreq);
-      size_t most = 0;
-      for (const auto& c : chunks) most = std::max(most, c.second);
-      if (!sc.Ensure(&sc.d_freq, &sc.freq_cap, most * kFreq)) return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
-      for (const auto& c : chunks) {
-        uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
-        if (int rc = ragged_analysis(e, false, yuv_mode, cls, a, nplanes, static_cast<int>(c.second), frames + c.first,
-                                     std::vector<FrameGeo>(geo.begin() + c.first, geo.begin() + c.first + c.second),
-                                     &tables[c.first], 1, d_freq, st)) return rc;
-        if (int rc = read_back(h_freq + c.first * kFreq, d_freq, c.second * kFreq)) return rc;
+    for (const auto& part : parts) {
+      // 3. the sharp frames of the part go into the arena: Y, U, V tightly packed, then the workspace
+      std::vector<sjpeg_hip_ragged_frame> sharp;
+      std::vector<uint8_t*> py, pu, pv;
+      uint8_t* at = reinterpret_cast<uint8_t*>(e->sharp_arena.p);
+      for (size_t f = part.first; f < part.second; ++f) {
+        if (mode[f] != SJPEG_YUV_SHARP_) continue;
+        const sjpeg_hip_ragged_frame& fr = frames[f];
+        const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+        sharp.push_back(fr);
+        py.push_back(at); at += align16(static_cast<size_t>(fr.width) * fr.height);
+        pu.push_back(at); at += align16(cw * ch);
+        pv.push_back(at); at += align16(cw * ch);
       }
-      HIP_TRY(hipEventRecord(sc.pass_done, st));
-      mark("stats launched");
-      HIP_TRY(hipEventSynchronize(sc.pass_done));
-      mark("counts here");
-      // 4. the optimised codes (the host's share that grows with the batch)
-      for (size_t f = 0; f < n; ++f) {
-        sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(h_freq + f * kFreq), yuv_mode, &specs[f * 4], &tables[f]);
+      // (enqueued by ragged_batch_groups in front of the first kernel that reads the sharp group, its last)
+      auto convert = [&]() -> int {
+        uint8_t* const ws = reinterpret_cast<uint8_t*>(e->sharp_arena.p) + align16(static_cast<size_t>(at - reinterpret_cast<uint8_t*>(e->sharp_arena.p)));
+        const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
+        std::string err;
+        if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), py.data(), pu.data(),
+                                                      pv.data(), ws, wsz, st, engine_upload, e, &err)) {
+          return fail(rc, who + ": " + err);
+        }
+        mark("sharp launched");
+        return 0;
+      };
+      // 4. the mode groups: RGB 4:2:0, 4:4:4, 4:0:0, then the sharp frames as planar 4:2:0
+      std::vector<RaggedGroup> groups;
+      const int kinds[4] = {SJPEG_YUV_420_, SJPEG_YUV_444_, SJPEG_YUV_400_, SJPEG_YUV_SHARP_};
+      for (int kind : kinds) {
+        RaggedGroup g;
+        g.format = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_SRC_YUV420 : format;
+        g.yuv_mode = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_YUV420 : kind;     // (SjpegYUVMode 1, 3, 4 = SJPEG_HIP_YUV*)
+        size_t k = 0;
+        for (size_t f = part.first; f < part.second; ++f) {
+          if (mode[f] != SJPEG_YUV_SHARP_) {
+            if (mode[f] == kind) { g.frames.push_back(frames[f]); g.index.push_back(static_cast<int>(f)); }
+            continue;
+          }
+          if (kind != SJPEG_YUV_SHARP_) continue;
+          sjpeg_hip_ragged_frame fr = frames[f];
+          const int64_t cw = (static_cast<int64_t>(fr.width) + 1) / 2;
+          fr.plane[0] = py[k]; fr.plane[1] = pu[k]; fr.plane[2] = pv[k];
+          fr.row_stride[0] = fr.width; fr.row_stride[1] = cw; fr.row_stride[2] = cw;
+          ++k;
+          g.frames.push_back(fr);
+          g.index.push_back(static_cast<int>(f));
+        }
+        if (g.frames.empty()) continue;
+        if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
+        if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
+        groups.push_back(std::move(g));
       }
+      if (int rc = ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
+                                       qdelta_max_chroma, d_out, d_sizes, st,
+                                       sharp.empty() ? std::function<int()>() : std::function<int()>(convert))) return rc;
     }
-    // 4. (all methods) the headers, each frame's own
-    std::vector<uint8_t> headers;
-    std::vector<size_t> offs(n + 1, 0);
-    uint8_t one[2048];
-    for (size_t f = 0; f < n; ++f) {
-      const size_t hs = sjpeg_hip_make_header_ex(frames[f].width, frames[f].height, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
-                                                 optimize ? &specs[f * 4] : nullptr, one, sizeof(one));
-      if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
-      headers.insert(headers.end(), one, one + hs);
-      offs[f + 1] = headers.size();
-    }
-    mark("tables built");
-    // 5. the ragged encode (method 0: its one call), asynchronous on the stream
-    const bool one_table = !quant_per_frame && !adaptive && !optimize;
-    const int rc = sjpeg_hip_encode_ragged_src(e, format, yuv_mode, nframes, frames, tables.data(), one_table ? 0 : 1,
-                                               headers.data(), offs.data(), /*append_eoi=*/1, d_out, d_sizes, stream);
-    mark("encode launched");
-    return rc;
+    mark("call done");
+    return 0;
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }

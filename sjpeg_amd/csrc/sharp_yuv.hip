@@ -23,9 +23,11 @@
 #include <string.h>
 
 #include <mutex>
+#include <vector>
 #include <string>
 
 #include "sjpeg_hip.h"
+#include "ragged_aux.h"
 
 namespace {
 
@@ -103,39 +105,7 @@ __device__ __forceinline__ void eval_group(const uint32_t* g2l, const uint32_t* 
 __global__ __launch_bounds__(256) void sharp_import(const SharpArgs a) {
   const int frame = blockIdx.z;
   const int c = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
-  if (c >= a.uv_w) return;
-  const uint8_t* base = a.rgb + frame * a.frame_stride;
-  int px[2][2][3];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int yy = min(2 * ry + r, a.H - 1);                 // bottom replication
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int xx = min(2 * c + cc, a.W - 1);               // right replication
-      const uint8_t* p = base + yy * a.row_stride + static_cast<long long>(xx) * a.pix_step;
-      px[r][cc][0] = (p[a.r_off] << kSfix) | (1 << kSfix >> 1);
-      px[r][cc][1] = (p[a.g_off] << kSfix) | (1 << kSfix >> 1);
-      px[r][cc][2] = (p[a.b_off] << kSfix) | (1 << kSfix >> 1);
-    }
-  }
-  int wt[2][2], uv[3];
-  eval_group(a.tab->g2l, a.tab->l2g, px, wt, uv);
-  const size_t yo = static_cast<size_t>(frame) * a.w * a.h;
-  const size_t uo = (static_cast<size_t>(frame) * a.uv_h + ry) * 3 * a.uv_w;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const size_t o = yo + static_cast<size_t>(2 * ry + r) * a.w + 2 * c + cc;
-      a.best_y[o] = static_cast<uint16_t>(gray(px[r][cc][0], px[r][cc][1], px[r][cc][2]));   // StoreGray
-      a.target_y[o] = static_cast<uint16_t>(wt[r][cc]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a.target_uv[uo + k * a.uv_w + c] = static_cast<int16_t>(uv[k]);
-    a.best_uv[uo + k * a.uv_w + c] = static_cast<int16_t>(uv[k]);
-  }
+#include "sharp_import_body.inc"
 }
 
 // Race stress build (make STRESS=1|2): SHARP_RACE_POINT(n) holds the waves w with (w & 3) == k of the
@@ -694,295 +664,122 @@ __global__ __launch_bounds__(kStripThreads) void sharp_sweeps_strips(const Sharp
   __shared__ int16_t above[2][3][kStripThreads];    // the updated row above, ping-pong
   const int strip = blockIdx.x, nstrips = gridDim.x, t = blockIdx.y, tid = threadIdx.x;
   const int frame = a.frame0 + blockIdx.z;
-  for (int i = tid; i <= kMaxY; i += kStripThreads) g2l[i] = a.tab->g2l[i];
-  if (tid < kGammaTab + 2) l2g[tid] = a.tab->l2g[tid];
-  const int w = a.w, h = a.h, uv_w = a.uv_w, uv_h = a.uv_h;
-  const size_t ysz = static_cast<size_t>(w) * h, usz = static_cast<size_t>(uv_h) * 3 * uv_w;
-  const int pin = t % 3, pout = (t + 1) % 3;
-  const uint16_t* const in_y = a.best_y + (static_cast<size_t>(pin) * a.nframes + frame) * ysz;
-  uint16_t* const out_y = a.best_y + (static_cast<size_t>(pout) * a.nframes + frame) * ysz;
-  const int16_t* const in_uv = a.best_uv + (static_cast<size_t>(pin) * a.nframes + frame) * usz;
-  int16_t* const out_uv = a.best_uv + (static_cast<size_t>(pout) * a.nframes + frame) * usz;
-  const uint16_t* const target_y = a.target_y + static_cast<size_t>(frame) * ysz;
-  const int16_t* const target_uv = a.target_uv + static_cast<size_t>(frame) * usz;
-  uint32_t* const ctrl = a.ctrl + static_cast<size_t>(frame) * a.ctrl_words;
-  uint32_t* const progress = ctrl + 32;             // [4][nstrips]
-  const unsigned long long threshold = static_cast<unsigned long long>(3.0 * w * h);
-  const int own0 = strip * kStripOwn, own1 = own0 + kStripOwn < uv_w ? own0 + kStripOwn : uv_w;
-  const int c = own0 - kStripHalo + tid;            // this thread's chroma column
-  const bool live = c >= 0 && c < uv_w;
-  const bool owned = c >= own0 && c < own1;
-  // the neighbours' places in the LDS row (a column at the picture's edge is its own neighbour, as in the reference;
-  // one at the workgroup's edge has none -- it is the first to go invalid, whatever it reads)
-  const int tl = (c > 0 && tid > 0) ? tid - 1 : tid, tr = (c < uv_w - 1 && tid < kStripThreads - 1) ? tid + 1 : tid;
-  const int s_lo = strip > 0 ? strip - 1 : 0, s_hi = strip < nstrips - 1 ? strip + 1 : strip;
-
-  struct RowData { int uv[3][3]; uint32_t wy[2], ty[2]; int tuv[3]; };
-  auto load_uv = [&](int row, int (&dst)[3][3]) {
-    const int cl = c > 0 ? c - 1 : 0, cr = c < uv_w - 1 ? c + 1 : uv_w - 1;
-    const int16_t* r = in_uv + static_cast<size_t>(row) * 3 * uv_w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { dst[k][0] = r[k * uv_w + cl]; dst[k][1] = r[k * uv_w + c]; dst[k][2] = r[k * uv_w + cr]; }
-  };
-  auto load_rest = [&](int ry, RowData& d) {
-    d.wy[0] = reinterpret_cast<const uint32_t*>(in_y + static_cast<size_t>(2 * ry) * w)[c];
-    d.wy[1] = reinterpret_cast<const uint32_t*>(in_y + static_cast<size_t>(2 * ry + 1) * w)[c];
-    d.ty[0] = reinterpret_cast<const uint32_t*>(target_y + static_cast<size_t>(2 * ry) * w)[c];
-    d.ty[1] = reinterpret_cast<const uint32_t*>(target_y + static_cast<size_t>(2 * ry + 1) * w)[c];
-    const int16_t* tu = target_uv + static_cast<size_t>(ry) * 3 * uv_w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d.tuv[k] = tu[k * uv_w + c];
-  };
-  // Waits until strips s_lo .. s_hi of sweep `tt` have all finished `want` row pairs (visible here), or a sweep has been
-  // named the final one (returns -1).  Returns the least of the three counters.
-  auto wait_strips = [&](int tt, int want, bool self_too) -> int {
-    if (tid == 0) {
-      int seen = 0x7fffffff;
-      for (int s = s_lo; s <= s_hi && seen >= 0; ++s) {
-        if (!self_too && s == strip) continue;
-        for (;;) {
-          // (relaxed looks: an acquire load is a load AND a cache invalidate, per look and waiting workgroup; the one
-          // acquire that matters is the fence behind the barrier below)
-          if (__hip_atomic_load(&ctrl[16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { seen = -1; break; }
-          const int p = static_cast<int>(__hip_atomic_load(&progress[tt * nstrips + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-          if (p >= want) { seen = p < seen ? p : seen; break; }
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      go = seen;
-    }
-    __syncthreads();
-    const int g = go;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // every wave's loads behind this see the producers' rows
-    __syncthreads();                                // (`go` is rewritten by the next call)
-    return g;
-  };
-  constexpr int kAhead = 16;
-  int known = t == 0 ? uv_h : 0;                    // row pairs of the sweep before known to be done in all three strips
-  auto wait_for = [&](int need) -> bool {
-    if (need > uv_h) need = uv_h;
-    if (known >= need) return true;
-    const int g = wait_strips(t - 1, need + kAhead < uv_h ? need + kAhead : uv_h, true);
-    if (g < 0) return false;
-    known = g;
-    return true;
-  };
-  SHARP_RACE_POINT(40);
-  __syncthreads();
-  if (tid == 0 && strip == 0) ctrl[18 + 2 * t] = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
-  unsigned long long diff = 0;
-  bool wanted = wait_for(3);
-  if (wanted) {
-    // (a step is shorter than a trip to memory now: what a row pair needs is asked for TWO steps ahead)
-    RowData now, ahead, ahead2;
-    int nxt[3][3];
-    if (live) {
-      load_uv(0, now.uv);
-      load_rest(0, now);
-      load_uv(uv_h > 1 ? 1 : 0, nxt);
-      if (uv_h > 1) { load_rest(1, ahead); load_uv(uv_h > 2 ? 2 : 1, ahead.uv); }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) above[0][k][tid] = static_cast<int16_t>(now.uv[k][1]);   // row pair 0: "above" is the row itself
-    }
-    SHARP_RACE_POINT(42);
-    __syncthreads();
-    for (int ry = 0; ry < uv_h; ++ry) {
-      const int pp = ry & 1;
-      SHARP_RACE_POINT(43);
-      if (ry > 0 && (ry % kStripHalo) == 0 && nstrips > 1) {
-        // the strips of this sweep meet: the halo's row above comes from the neighbours' output (row ry - 1)
-        SHARP_RACE_POINT(47);
-        if (wait_strips(t, ry, false) < 0) { wanted = false; break; }
-        if (live && !owned) {
-          const int16_t* const r = out_uv + static_cast<size_t>(ry - 1) * 3 * uv_w;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) above[pp][k][tid] = r[k * uv_w + c];       // (behind wait_strips' acquire)
-        }
-        __syncthreads();
-      }
-      if (ry + 2 < uv_h) {
-        wanted = wait_for(ry + 4);
-        if (!wanted) break;
-        if (live) {
-          load_rest(ry + 2, ahead2);
-          load_uv(ry + 3 < uv_h ? ry + 3 : ry + 2, ahead2.uv);     // becomes `nxt` two steps on
-        }
-      }
-      if (live) {
-        const int wy[2][2] = {{static_cast<int>(now.wy[0] & 0xffffu), static_cast<int>(now.wy[0] >> 16)},
-                              {static_cast<int>(now.wy[1] & 0xffffu), static_cast<int>(now.wy[1] >> 16)}};
-        const int ty[2][2] = {{static_cast<int>(now.ty[0] & 0xffffu), static_cast<int>(now.ty[0] >> 16)},
-                              {static_cast<int>(now.ty[1] & 0xffffu), static_cast<int>(now.ty[1] >> 16)}};
-        int px[2][2][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int A = now.uv[k][1], Al = now.uv[k][0], Ar = now.uv[k][2];
-          const int P = above[pp][k][tid], Pl = above[pp][k][tl], Pr = above[pp][k][tr];
-          const bool has_next = ry + 1 < uv_h;
-          const int N = has_next ? nxt[k][1] : A, Nl = has_next ? nxt[k][0] : Al, Nr = has_next ? nxt[k][2] : Ar;
-          int up0, up1, dn0, dn1;
-          if (c == 0) { up0 = (A * 3 + P + 2) >> 2; dn0 = (A * 3 + N + 2) >> 2; }
-          else { up0 = (A * 9 + Al * 3 + P * 3 + Pl + 8) >> 4; dn0 = (A * 9 + Al * 3 + N * 3 + Nl + 8) >> 4; }
-          if (c == uv_w - 1) { up1 = (A * 3 + P + 2) >> 2; dn1 = (A * 3 + N + 2) >> 2; }
-          else { up1 = (A * 9 + Ar * 3 + P * 3 + Pr + 8) >> 4; dn1 = (A * 9 + Ar * 3 + N * 3 + Nr + 8) >> 4; }
-          px[0][0][k] = clip_y(wy[0][0] + up0); px[0][1][k] = clip_y(wy[0][1] + up1);
-          px[1][0][k] = clip_y(wy[1][0] + dn0); px[1][1][k] = clip_y(wy[1][1] + dn1);
-        }
-        int wt[2][2], uv[3];
-        eval_group(g2l, l2g, px, wt, uv);
-        uint32_t newy[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          int ny[2];
-#pragma unroll
-          for (int cc = 0; cc < 2; ++cc) {
-            const int d = ty[r][cc] - wt[r][cc];
-            ny[cc] = clip_y(wy[r][cc] + d);
-            if (owned) diff += static_cast<unsigned long long>(d < 0 ? -d : d);
-          }
-          newy[r] = static_cast<uint32_t>(ny[0]) | (static_cast<uint32_t>(ny[1]) << 16);
-        }
-        // (the rows go out as agent-scope stores -- write-through, `sc1` -- so that publishing them needs no release
-        // fence: that is an L2 write-back of whatever is dirty, per workgroup and hand-over, and with twenty times the
-        // workgroups of the one-per-sweep kernel it halved the throughput of a batch)
-        if (owned) {
-          __hip_atomic_store(&reinterpret_cast<uint32_t*>(out_y + static_cast<size_t>(2 * ry) * w)[c], newy[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&reinterpret_cast<uint32_t*>(out_y + static_cast<size_t>(2 * ry + 1) * w)[c], newy[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int16_t nv = static_cast<int16_t>(now.uv[k][1] + (now.tuv[k] - uv[k]));
-          if (owned) __hip_atomic_store(&out_uv[static_cast<size_t>(ry) * 3 * uv_w + k * uv_w + c], nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          above[pp ^ 1][k][tid] = nv;
-        }
-      }
-      SHARP_RACE_POINT(44);
-      // hand-over (to the next sweep, and to the neighbour strips of this one): every wave's stores are acknowledged in
-      // front of the barrier (written through, see above), the counter behind it is a store of the same kind
-      const bool hand_over = (ry & 7) == 7 || ry + 1 == uv_h;
-      if (hand_over) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      }
-      SHARP_RACE_POINT(45);
-      if (hand_over && tid == 0) {
-        __hip_atomic_store(&progress[t * nstrips + strip], static_cast<uint32_t>(ry + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { now.uv[k][q] = nxt[k][q]; nxt[k][q] = ahead.uv[k][q]; ahead.uv[k][q] = ahead2.uv[k][q]; }
-        now.tuv[k] = ahead.tuv[k]; ahead.tuv[k] = ahead2.tuv[k];
-      }
-      now.wy[0] = ahead.wy[0]; now.wy[1] = ahead.wy[1];
-      now.ty[0] = ahead.ty[0]; now.ty[1] = ahead.ty[1];
-      ahead.wy[0] = ahead2.wy[0]; ahead.wy[1] = ahead2.wy[1];
-      ahead.ty[0] = ahead2.ty[0]; ahead.ty[1] = ahead2.ty[1];
-    }
-  }
-  if (tid == 0 && strip == 0) ctrl[19 + 2 * t] = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
-  if (!wanted) return;                              // (uniform: an earlier sweep is the final one)
-  // exit test (:660-666): the sweep's sum of |dW| over the picture = the strips' sums; the last strip to arrive takes it
-  for (int d = 32; d > 0; d >>= 1) diff += __shfl_down(diff, d, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = diff;
-  SHARP_RACE_POINT(46);
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long mine = 0;
-    for (int i = 0; i < kStripThreads / 64; ++i) mine += red[i];
-    unsigned long long* const sum_t = reinterpret_cast<unsigned long long*>(ctrl + 8 + 2 * t);
-    __hip_atomic_fetch_add(sum_t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t arrived = __hip_atomic_fetch_add(&ctrl[t], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (arrived + 1u == static_cast<uint32_t>(nstrips)) {
-      const unsigned long long sum = __hip_atomic_load(sum_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      bool cancelled = false;
-      unsigned long long prev = ~0ull;
-      if (t > 0) {
-        while (__hip_atomic_load(&ctrl[4 + t - 1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-          if (__hip_atomic_load(&ctrl[16], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-          __builtin_amdgcn_s_sleep(4);
-        }
-        cancelled = __hip_atomic_load(&ctrl[16], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        prev = __hip_atomic_load(reinterpret_cast<unsigned long long*>(ctrl + 8 + 2 * (t - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (!cancelled) {
-        const bool stop = t > 0 && (sum < threshold || sum > prev);
-        if (stop || t == 3) {
-          ctrl[17] = static_cast<uint32_t>(t);
-          __hip_atomic_store(&ctrl[16], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __hip_atomic_store(&ctrl[4 + t], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
+#include "sharp_strips_body.inc"
 }
 
 // ---- back to 8-bit planes (:543-575; this file's own -11058 / -5328 constants)
 __global__ __launch_bounds__(256) void sharp_export(const SharpArgs a) {
   const int frame = blockIdx.z;
   const int c = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
-  if (c >= a.uv_w) return;
-  // (pipelined sweeps: the plane the last sweep that counts wrote)
-  const int plane = a.nplanes == 3 ? static_cast<int>((a.ctrl[static_cast<size_t>(frame) * a.ctrl_words + 17] + 1u) % 3u) : 0;
-  const size_t pf = static_cast<size_t>(plane) * a.nframes + frame;
-  const size_t uo = (pf * a.uv_h + ry) * 3 * a.uv_w;
-  const int r = a.best_uv[uo + c], g = a.best_uv[uo + a.uv_w + c], b = a.best_uv[uo + 2 * a.uv_w + c];
-  const int rnd = 1 << 18 >> 1;
-  const int cw = (a.W + 1) >> 1;
-  if (c < cw && ry < ((a.H + 1) >> 1)) {
-    uint8_t* up = a.u + frame * a.uv_frame_stride + static_cast<size_t>(ry) * cw;
-    uint8_t* vp = a.v + frame * a.uv_frame_stride + static_cast<size_t>(ry) * cw;
-    up[c] = static_cast<uint8_t>(clip8(128 + ((-11058 * r - 21709 * g + 32768 * b + rnd) >> 18)));
-    vp[c] = static_cast<uint8_t>(clip8(128 + ((32768 * r - 27439 * g - 5328 * b + rnd) >> 18)));
-  }
-  const size_t yo = pf * a.w * a.h;
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr) {
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int x = 2 * c + cc, y = 2 * ry + rr;
-      if (x < a.W && y < a.H) {
-        const int Wv = a.best_y[yo + static_cast<size_t>(y) * a.w + x];
-        a.y[frame * a.y_frame_stride + static_cast<size_t>(y) * a.W + x] =
-            static_cast<uint8_t>(clip8((19595 * (r + Wv) + 38469 * (g + Wv) + 7471 * (b + Wv) + rnd) >> 18));
-      }
-    }
-  }
+#include "sharp_export_body.inc"
 }
 
 // ---- pictures too small for the iterative conversion (:57-100,674-690): plain averaging
 __global__ __launch_bounds__(64) void sharp_small(const SharpArgs a) {
   const int frame = blockIdx.x;
-  const uint8_t* base = a.rgb + frame * a.frame_stride;
-  const int cw = (a.W + 1) >> 1, ch = (a.H + 1) >> 1;
-  for (int i = threadIdx.x; i < a.W * a.H; i += 64) {
-    const int x = i % a.W, y = i / a.W;
-    const uint8_t* p = base + y * a.row_stride + static_cast<long long>(x) * a.pix_step;
-    const int v = 19595 * p[a.r_off] + 38469 * p[a.g_off] + 7471 * p[a.b_off];
-    a.y[frame * a.y_frame_stride + i] = static_cast<uint8_t>((v + (1 << 16 >> 1)) >> 16);
+#include "sharp_small_body.inc"
+}
+
+// ---- ragged batches (sjpeg_hip_sharp_yuv_ragged): pictures of different sizes in one call.  Every kernel has a ragged
+// form that differs from its uniform twin in the prologue only: a workgroup of the flat grid finds its frame (a binary
+// search over the frames' first workgroups), then runs the uniform kernel's body (the *_body.inc files) on a
+// copy of SharpArgs rebased to that frame -- nframes = 1, the frame's own sizes, its workspace block, control words
+// and output planes.
+struct SharpFrame {
+  const uint8_t* rgb;
+  long long row_stride;
+  uint8_t* y; uint8_t* u; uint8_t* v;           // tightly packed planes
+  uint8_t* block;                               // the frame's workspace block (sharp_small frames: none)
+  uint32_t* ctrl;                               // its 32 + 4 * nstrips control words
+  int W, H, nstrips, gx;                        // gx: 256-column groups of a chroma row
+  unsigned io_base;                             // its first workgroup of the import / export grid
+  unsigned strip_base;                          // its first workgroup of its strips launch
+};
+
+__host__ __device__ __forceinline__ size_t sharp_align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// the bytes of a frame's workspace block: what sjpeg_hip_sharp_workspace() gives one picture, less tables and control
+__host__ __device__ __forceinline__ size_t sharp_block_bytes(int W, int H) {
+  const size_t w = (static_cast<size_t>(W) + 1) & ~size_t(1), h = (static_cast<size_t>(H) + 1) & ~size_t(1);
+  return 4 * sharp_align256(w * h * 2) + 4 * sharp_align256(3 * (w / 2) * (h / 2) * 2) + sharp_align256(3 * (w / 2) * 2);
+}
+
+__device__ __forceinline__ SharpArgs sharp_rebase(const SharpArgs& common, const SharpFrame& d) {
+  SharpArgs a = common;
+  a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.W = d.W; a.H = d.H;
+  a.w = (d.W + 1) & ~1; a.h = (d.H + 1) & ~1; a.uv_w = a.w >> 1; a.uv_h = a.h >> 1;
+  const size_t ysz = sharp_align256(static_cast<size_t>(a.w) * a.h * 2), usz = sharp_align256(static_cast<size_t>(3) * a.uv_w * a.uv_h * 2);
+  uint8_t* p = d.block;
+  a.best_y = reinterpret_cast<uint16_t*>(p); p += 3 * ysz;
+  a.target_y = reinterpret_cast<uint16_t*>(p); p += ysz;
+  a.best_uv = reinterpret_cast<int16_t*>(p); p += 3 * usz;
+  a.target_uv = reinterpret_cast<int16_t*>(p); p += usz;
+  a.row_uv = reinterpret_cast<int16_t*>(p);
+  a.ctrl = d.ctrl; a.ctrl_words = 32 + 4 * d.nstrips;
+  a.nframes = 1; a.nplanes = 3; a.frame0 = 0;
+  a.y = d.y; a.u = d.u; a.v = d.v;
+  a.y_frame_stride = 0; a.uv_frame_stride = 0;
+  return a;
+}
+
+// the last frame of frames[lo, hi] whose first workgroup (base_of) is at or before wg
+template <bool kStrips>
+__device__ __forceinline__ int sharp_find(const SharpFrame* frames, int lo, int hi, unsigned wg) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((kStrips ? frames[mid].strip_base : frames[mid].io_base) <= wg) lo = mid; else hi = mid - 1;
   }
-  for (int i = threadIdx.x; i < cw * ch; i += 64) {
-    const int cx = i % cw, cy = i / cw;
-    const int y0 = 2 * cy, y1 = min(2 * cy + 1, a.H - 1);
-    const int x0 = 2 * cx, x1 = 2 * cx + 1;
-    const uint8_t* p00 = base + y0 * a.row_stride + static_cast<long long>(x0) * a.pix_step;
-    const uint8_t* p10 = base + y1 * a.row_stride + static_cast<long long>(x0) * a.pix_step;
-    int r, g, b;
-    if (x1 < a.W) {
-      const uint8_t* p01 = p00 + a.pix_step;
-      const uint8_t* p11 = p10 + a.pix_step;
-      r = p00[a.r_off] + p01[a.r_off] + p10[a.r_off] + p11[a.r_off];
-      g = p00[a.g_off] + p01[a.g_off] + p10[a.g_off] + p11[a.g_off];
-      b = p00[a.b_off] + p01[a.b_off] + p10[a.b_off] + p11[a.b_off];
-    } else {
-      r = 2 * (p00[a.r_off] + p10[a.r_off]); g = 2 * (p00[a.g_off] + p10[a.g_off]); b = 2 * (p00[a.b_off] + p10[a.b_off]);
-    }
-    const int rnd = 1 << 18 >> 1;
-    a.u[frame * a.uv_frame_stride + i] = static_cast<uint8_t>(clip8(128 + ((-11058 * r - 21709 * g + 32768 * b + rnd) >> 18)));
-    a.v[frame * a.uv_frame_stride + i] = static_cast<uint8_t>(clip8(128 + ((32768 * r - 27439 * g - 5328 * b + rnd) >> 18)));
-  }
+  return lo;
+}
+
+// frames[0, nbig): the import and export grids, gx * uv_h workgroups a frame
+__global__ __launch_bounds__(256) void sharp_import_ragged(const SharpArgs common, const SharpFrame* frames, int nbig) {
+  const SharpFrame& d = frames[sharp_find<false>(frames, 0, nbig - 1, blockIdx.x)];
+  const SharpArgs a = sharp_rebase(common, d);
+  const unsigned local = blockIdx.x - d.io_base;
+  const int frame = 0;
+  const int c = (local % static_cast<unsigned>(d.gx)) * 256 + threadIdx.x, ry = local / static_cast<unsigned>(d.gx);
+#include "sharp_import_body.inc"
+}
+
+__global__ __launch_bounds__(256) void sharp_export_ragged(const SharpArgs common, const SharpFrame* frames, int nbig) {
+  const SharpFrame& d = frames[sharp_find<false>(frames, 0, nbig - 1, blockIdx.x)];
+  const SharpArgs a = sharp_rebase(common, d);
+  const unsigned local = blockIdx.x - d.io_base;
+  const int frame = 0;
+  const int c = (local % static_cast<unsigned>(d.gx)) * 256 + threadIdx.x, ry = local / static_cast<unsigned>(d.gx);
+#include "sharp_export_body.inc"
+}
+
+// frames[f0, f1) of one launch, 4 * nstrips workgroups a frame in the uniform grid's order (strip fastest, then sweep):
+// a workgroup only waits for workgroups of a smaller index or for its neighbour strips, and the launch holds no more
+// workgroups than are resident at once
+__global__ __launch_bounds__(kStripThreads) void sharp_sweeps_strips_ragged(const SharpArgs common, const SharpFrame* frames, int f0, int f1) {
+  __shared__ uint32_t g2l[kMaxY + 1];
+  __shared__ uint32_t l2g[kGammaTab + 2];
+  __shared__ unsigned long long red[kStripThreads / 64];
+  __shared__ int go;
+  __shared__ int16_t above[2][3][kStripThreads];    // the updated row above, ping-pong
+  const SharpFrame& d = frames[sharp_find<true>(frames, f0, f1 - 1, blockIdx.x)];
+  const SharpArgs a = sharp_rebase(common, d);
+  const unsigned local = blockIdx.x - d.strip_base;
+  const int nstrips = d.nstrips, strip = local % static_cast<unsigned>(nstrips), t = local / static_cast<unsigned>(nstrips);
+  const int tid = threadIdx.x;
+  const int frame = 0;
+#include "sharp_strips_body.inc"
+}
+
+// frames[0, n): pictures of at most 4 pixels in either dimension, a workgroup each
+__global__ __launch_bounds__(64) void sharp_small_ragged(const SharpArgs common, const SharpFrame* frames) {
+  const SharpFrame& d = frames[blockIdx.x];
+  SharpArgs a = common;
+  a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.W = d.W; a.H = d.H;
+  a.y = d.y; a.u = d.u; a.v = d.v;
+  a.y_frame_stride = 0; a.uv_frame_stride = 0;
+  const int frame = 0;
+#include "sharp_small_body.inc"
 }
 
 GammaTables g_tables;
@@ -1039,11 +836,8 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
   if (workspace_size < sjpeg_hip_sharp_workspace(width, height, nframes) || nframes > 65535) return SJPEG_HIP_EINVAL;
   SharpArgs a;
   memset(&a, 0, sizeof(a));
-  switch (src->format) {
-    case SJPEG_HIP_SRC_RGB: a.pix_step = 3; a.r_off = 0; a.g_off = 1; a.b_off = 2; break;
-    case SJPEG_HIP_SRC_BGRA: a.pix_step = 4; a.r_off = 2; a.g_off = 1; a.b_off = 0; break;
-    case SJPEG_HIP_SRC_RGBA: a.pix_step = 4; a.r_off = 0; a.g_off = 1; a.b_off = 2; break;
-    default: return SJPEG_HIP_EINVAL;                // the sharp conversion starts from RGB
+  if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
+    return SJPEG_HIP_EINVAL;                         // the sharp conversion starts from RGB
   }
   const int64_t st_abs = src->row_stride[0] < 0 ? -src->row_stride[0] : src->row_stride[0];
   if (st_abs < static_cast<int64_t>(a.pix_step) * width) return SJPEG_HIP_EINVAL;
@@ -1147,3 +941,137 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
 }
 
 }  // extern "C"
+
+namespace sjpeg_internal {
+
+// workspace: gamma tables | descriptors | every frame's control words | the frames' blocks
+size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames) {
+  if (nframes <= 0 || nframes > 65535 || frames == nullptr) return 0;
+  size_t ctrl = 0, blocks = 0;
+  for (int f = 0; f < nframes; ++f) {
+    const int W = frames[f].width, H = frames[f].height;
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return 0;
+    if (W <= 4 || H <= 4) continue;
+    const int uv_w = ((W + 1) & ~1) >> 1;
+    ctrl += 32 + 4 * static_cast<size_t>((uv_w + kStripOwn - 1) / kStripOwn);
+    blocks += sharp_block_bytes(W, H);
+  }
+  return align256(sizeof(GammaTables)) + align256(sizeof(SharpFrame) * nframes) + align256(ctrl * 4) + blocks;
+}
+
+int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
+                     uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
+                     hipStream_t st, UploadFn up, void* up_ctx, std::string* err) {
+  SharpArgs a;
+  memset(&a, 0, sizeof(a));
+  if (!rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
+    *err = "the sharp conversion takes RGB, BGRA or RGBA sources";
+    return SJPEG_HIP_EINVAL;
+  }
+  if (nframes < 1 || nframes > 65535) { *err = "nframes must be 1..65535"; return SJPEG_HIP_EINVAL; }
+  if (frames == nullptr || d_y == nullptr || d_u == nullptr || d_v == nullptr || d_workspace == nullptr) {
+    *err = "frames, d_y, d_u, d_v or d_workspace == NULL";
+    return SJPEG_HIP_EINVAL;
+  }
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    const std::string w = "frame " + std::to_string(f) + ": ";
+    if (fr.width <= 0 || fr.height <= 0 || fr.width > 65535 || fr.height > 65535) {
+      *err = w + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height);
+      return SJPEG_HIP_EINVAL;
+    }
+    if (fr.plane[0] == nullptr || d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
+    const int64_t st_abs = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
+    if (st_abs < static_cast<int64_t>(a.pix_step) * fr.width) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
+  }
+  if (workspace_size < sharp_ragged_workspace(nframes, frames)) { *err = "workspace_size below sjpeg_hip_sharp_ragged_workspace()"; return SJPEG_HIP_EINVAL; }
+#ifdef SJPEG_HIP_PRIO_STRESS
+  if (const char* ab = getenv("SJPEG_HIP_ABLATE")) a.stress = atoi(ab);
+#endif
+  std::call_once(g_tables_once, build_tables);
+  // the descriptors: the frames of the iterative conversion first, then the small ones
+  std::vector<int> order;
+  for (int f = 0; f < nframes; ++f) if (frames[f].width > 4 && frames[f].height > 4) order.push_back(f);
+  const int nbig = static_cast<int>(order.size());
+  for (int f = 0; f < nframes; ++f) if (frames[f].width <= 4 || frames[f].height <= 4) order.push_back(f);
+  const size_t off_desc = align256(sizeof(GammaTables)), off_ctrl = off_desc + align256(sizeof(SharpFrame) * nframes);
+  size_t ctrl_words = 0;
+  for (int k = 0; k < nbig; ++k) {
+    const int uv_w = ((frames[order[k]].width + 1) & ~1) >> 1;
+    ctrl_words += 32 + 4 * static_cast<size_t>((uv_w + kStripOwn - 1) / kStripOwn);
+  }
+  uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
+  std::vector<uint8_t> blob(off_ctrl);
+  memcpy(blob.data(), &g_tables, sizeof(GammaTables));
+  SharpFrame* const desc = reinterpret_cast<SharpFrame*>(blob.data() + off_desc);
+  uint8_t* block = ws + off_ctrl + align256(ctrl_words * 4);
+  uint32_t* ctrl = reinterpret_cast<uint32_t*>(ws + off_ctrl);
+  unsigned io = 0;
+  for (int k = 0; k < nframes; ++k) {
+    const int f = order[k];
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    SharpFrame& d = desc[k];
+    memset(&d, 0, sizeof(d));
+    d.rgb = static_cast<const uint8_t*>(fr.plane[0]); d.row_stride = fr.row_stride[0];
+    d.y = d_y[f]; d.u = d_u[f]; d.v = d_v[f];
+    d.W = fr.width; d.H = fr.height;
+    if (k >= nbig) continue;
+    const int uv_w = ((fr.width + 1) & ~1) >> 1, uv_h = ((fr.height + 1) & ~1) >> 1;
+    d.nstrips = (uv_w + kStripOwn - 1) / kStripOwn;
+    d.gx = (uv_w + 255) / 256;
+    d.block = block; block += sharp_block_bytes(fr.width, fr.height);
+    d.ctrl = ctrl; ctrl += 32 + 4 * d.nstrips;
+    d.io_base = io; io += static_cast<unsigned>(d.gx) * static_cast<unsigned>(uv_h);
+  }
+  // the strips launches: consecutive frames, no more workgroups a launch than the uniform call allows one (kSlots:
+  // three quarters of what the device holds at once -- of the uniform kernel and of this one, the fewer)
+  static const int kSlotsRagged = [] {
+    if (const char* e = getenv("SJPEG_HIP_SHARP_SLOTS")) { const int v = atoi(e); if (v > 0) return v; }
+    int dev = 0, cus = 0, per_cu = 0, per_cu_ragged = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sharp_sweeps_strips, kStripThreads, 0) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_ragged, sharp_sweeps_strips_ragged, kStripThreads, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      return 16;
+    }
+    const int all = cus * (per_cu < per_cu_ragged ? per_cu : per_cu_ragged);
+    return all < 32 ? 16 : all / 4 * 3;
+  }();
+  std::vector<std::pair<int, int>> launches;         // (first, end) in desc[]
+  {
+    int f0 = 0;
+    unsigned used = 0;
+    for (int k = 0; k < nbig; ++k) {
+      const unsigned wgs = 4u * static_cast<unsigned>(desc[k].nstrips);
+      if (k > f0 && used + wgs > static_cast<unsigned>(kSlotsRagged)) { launches.emplace_back(f0, k); f0 = k; used = 0; }
+      desc[k].strip_base = used;
+      used += wgs;
+    }
+    if (nbig > 0) launches.emplace_back(f0, nbig);
+  }
+  if (int rc = up(up_ctx, ws, blob.data(), blob.size(), st)) { *err = "descriptor upload failed"; return rc; }
+  a.tab = reinterpret_cast<const GammaTables*>(ws);
+  const SharpFrame* const d_desc = reinterpret_cast<const SharpFrame*>(ws + off_desc);
+  if (nbig > 0) {
+    if (hipMemsetAsync(ws + off_ctrl, 0, ctrl_words * 4, st) != hipSuccess) { *err = "hipMemsetAsync failed"; return SJPEG_HIP_ERUNTIME; }
+    hipLaunchKernelGGL(sharp_import_ragged, dim3(io), dim3(256), 0, st, a, d_desc, nbig);
+    for (const auto& l : launches) {
+      const unsigned wgs = desc[l.second - 1].strip_base + 4u * static_cast<unsigned>(desc[l.second - 1].nstrips);
+      hipLaunchKernelGGL(sharp_sweeps_strips_ragged, dim3(wgs), dim3(kStripThreads), 0, st, a, d_desc, l.first, l.second);
+    }
+    hipLaunchKernelGGL(sharp_export_ragged, dim3(io), dim3(256), 0, st, a, d_desc, nbig);
+  }
+  if (getenv("SJPEG_HIP_SHARP_DEBUG") != nullptr) {   // (measurement aid: how the strips went out)
+    fprintf(stderr, "sharp ragged: %d frames, %d small, %zu strips launches of at most %d workgroups\n", nframes,
+            nframes - nbig, launches.size(), kSlotsRagged);
+  }
+  if (nbig < nframes) hipLaunchKernelGGL(sharp_small_ragged, dim3(nframes - nbig), dim3(64), 0, st, a, d_desc + nbig);
+  if (hipGetLastError() != hipSuccess) { *err = "kernel launch failed"; return SJPEG_HIP_ERUNTIME; }
+  return 0;
+}
+
+}  // namespace sjpeg_internal
+
+extern "C" size_t sjpeg_hip_sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames) {
+  return sjpeg_internal::sharp_ragged_workspace(nframes, frames);
+}
