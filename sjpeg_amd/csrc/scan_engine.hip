@@ -1961,11 +1961,16 @@ int sjpeg_hip_adapt_sums(const uint32_t* d_hist, int nframes, const uint8_t quan
 // device pass and the per-picture float / Huffman work on the host in between.
 namespace {
 constexpr int kAdaptDeltas = 25;      // candidate steps -12 .. +12 (jpeg_host.h)
+// a frame's share of the batch scratch: its histogram, its adaptation sums and totals, its symbol counts
+constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
+constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
+constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
+
 struct BatchScratch {                 // per host thread: device scratch of sjpeg_hip_encode_batch_src
   void* d_hist = nullptr; size_t hist_cap = 0;
   void* d_sums = nullptr; size_t sums_cap = 0;
   void* d_freq = nullptr; size_t freq_cap = 0;
-  void* h_pinned = nullptr; size_t pinned_cap = 0;   // where the device's sums / counts land on the host
+  void* h_pinned = nullptr; size_t pinned_cap = 0;   // where the device's matrices / counts land on the host
   void* d_pinned = nullptr;                          // ... as the device addresses it
   int device = -1;
   void Drop() {
@@ -1973,7 +1978,6 @@ struct BatchScratch {                 // per host thread: device scratch of sjpe
     if (d_sums) (void)hipFree(d_sums);
     if (d_freq) (void)hipFree(d_freq);
     if (h_pinned) (void)hipHostFree(h_pinned);
-    for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     if (pass_done) (void)hipEventDestroy(pass_done);
     if (call_begin) (void)hipEventDestroy(call_begin);
     pass_done = nullptr; call_begin = nullptr;
@@ -1981,10 +1985,9 @@ struct BatchScratch {                 // per host thread: device scratch of sjpe
     job_ev.clear();
     d_hist = d_sums = d_freq = h_pinned = d_pinned = nullptr; hist_cap = sums_cap = freq_cap = pinned_cap = 0;
   }
-  hipEvent_t ev[12] = {};                        // behind the read-backs of a part: sums [0..7] (two halves a part), counts [8..11]
   hipEvent_t pass_done = nullptr;
   hipEvent_t call_begin = nullptr;                 // on the call's stream before anything of the call: the early uploads wait for it
-  std::vector<hipEvent_t> job_ev;                  // one per job of a batch coded in lanes
+  std::vector<hipEvent_t> job_ev;                  // one per part or job: behind its last read-back
   bool EnsureJobEvents(size_t n) {
     while (job_ev.size() < n) {
       hipEvent_t e = nullptr;
@@ -1994,9 +1997,6 @@ struct BatchScratch {                 // per host thread: device scratch of sjpe
     return true;
   }
   bool EnsureEvents() {
-    for (auto& e : ev) {
-      if (e == nullptr && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; return false; }
-    }
     if (pass_done == nullptr && hipEventCreateWithFlags(&pass_done, hipEventDisableTiming) != hipSuccess) { pass_done = nullptr; return false; }
     if (call_begin == nullptr && hipEventCreateWithFlags(&call_begin, hipEventDisableTiming) != hipSuccess) { call_begin = nullptr; return false; }
     return true;
@@ -2011,6 +2011,11 @@ struct BatchScratch {                 // per host thread: device scratch of sjpe
     if (hipHostGetDevicePointer(&d_pinned, h_pinned, 0) != hipSuccess) { (void)hipGetLastError(); d_pinned = nullptr; }
     return true;
   }
+  // device -> h_dst in the pinned block, on stream s: a kernel writes it over the bus (no runtime copy: stage_copy_kernel)
+  int ReadBack(hipStream_t s, void* h_dst, const void* d_src, size_t bytes) const {
+    void* const dv = d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(h_pinned));
+    return copy_by_kernel(dv, d_src, bytes, s, hipMemcpyDeviceToHost, d_src, h_dst);
+  }
   ~BatchScratch() { if (device >= 0) { (void)hipSetDevice(device); Drop(); } }
   bool Ensure(void** p, size_t* cap, size_t need) {
     if (need <= *cap) return true;
@@ -2022,6 +2027,134 @@ struct BatchScratch {                 // per host thread: device scratch of sjpe
   }
 };
 thread_local BatchScratch g_batch;
+
+// frames f0 .. f0 + nf - 1 take the adapted matrices that came back to h_q ([frame][128]), and the tables of them
+void adopt_matrices(const uint8_t* h_q, size_t f0, size_t nf, int yuv_mode, const uint8_t* min_quant, int q_bias,
+                    uint8_t* quant, sjpeg_hip_scan_tables* tables) {
+  const size_t ntab = yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
+  for (size_t f = f0; f < f0 + nf; ++f) {
+    memcpy(&quant[f * 128], h_q + f * 128, ntab * 64);
+    sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
+  }
+}
+
+// the headers of frames f0 .. f0 + nf - 1 back to back, frame f0 + k's at (*offs)[k] .. (*offs)[k + 1]; dims(k) is its
+// width and height.  quant: [frame][128]; specs: [frame][4], or NULL for the default codes
+int batch_headers(const std::string& who, const std::function<std::pair<int, int>(size_t)>& dims, size_t f0, size_t nf, int yuv_mode, const uint8_t* quant,
+                  const sjpeg_hip_huffman_spec* specs, std::vector<uint8_t>* headers, std::vector<size_t>* offs) {
+  headers->clear();
+  offs->assign(nf + 1, 0);
+  uint8_t one[2048];
+  for (size_t k = 0; k < nf; ++k) {
+    const size_t f = f0 + k;
+    const std::pair<int, int> wh = dims(k);
+    const size_t hs = sjpeg_hip_make_header_ex(wh.first, wh.second, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(quant + f * 128),
+                                               specs != nullptr ? specs + f * 4 : nullptr, one, sizeof(one));
+    if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
+    headers->insert(headers->end(), one, one + hs);
+    (*offs)[k + 1] = headers->size();
+  }
+  return 0;
+}
+
+// One call of sjpeg_hip_encode_batch_src: its arguments, and what its steps hand each other frame by frame
+struct BatchCall {
+  const sjpeg_hip_source* src;
+  int width, height, yuv_mode;
+  size_t n;
+  const uint8_t* min_quant;
+  int q_bias, qdelta_max_luma, qdelta_max_chroma;
+  bool optimize;
+  uint8_t* d_out; size_t out_stride; uint64_t* d_sizes;
+  BatchScratch& sc;
+  uint8_t* h_q;                                  // [n][128]: the adapted matrices come back here (sc's pinned block) ...
+  uint8_t* h_freq;                               // ... and [n][kFreq]: the symbol counts
+  uint8_t q_start[2][64];                        // the matrices every frame starts from
+  std::vector<uint8_t> quant;                    // [n][128]: every frame's own, adapted range by range
+  std::vector<sjpeg_hip_scan_tables> tables;     // [n]
+  std::vector<sjpeg_hip_huffman_spec> specs;     // [n][4]: the optimised codes
+  std::vector<uint8_t> headers;                  // one range's at a time (batch_headers)
+  std::vector<size_t> offs;
+};
+
+// frames f0 .. f0 + nf - 1 of a call -- a part, or a job of a lane -- and where their steps go
+struct FrameRange {
+  size_t f0, nf;
+  sjpeg_hip_engine* e;                           // runs the passes
+  hipStream_t pass;                              // ... on this stream
+  hipStream_t side;                              // the analysis sums and the read-backs
+  hipEvent_t ev;                                 // behind the range's latest read-back
+};
+
+sjpeg_hip_source range_source(const BatchCall& b, size_t f0) {
+  sjpeg_hip_source s = *b.src;
+  for (int i = 0; i < 3; ++i) {
+    if (s.plane[i] != nullptr) s.plane[i] = static_cast<const uint8_t*>(s.plane[i]) + static_cast<int64_t>(f0) * s.frame_stride[i];
+  }
+  return s;
+}
+
+// The five steps of a range; the first, third and fifth end with launches, and the second and fourth need what the
+// event behind the previous one's read-back brought.
+// 1. the histogram pass, the analysis sums, the regression on the device (adapt_decide_kernel) -- 128 bytes a frame come
+// back instead of the sums' 52 KB, and the host has no float work between the range's histogram pass and its statistics
+// launch
+int range_analysis(BatchCall& b, const FrameRange& r) {
+  const sjpeg_hip_source ps = range_source(b, r.f0);
+  const int nf = static_cast<int>(r.nf);
+  uint32_t* const d_hist = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b.sc.d_hist) + r.f0 * kHist);
+  if (int rc = sjpeg_hip_scan_histogram_src(r.e, &ps, b.width, b.height, b.yuv_mode, nf, d_hist, r.pass)) return rc;
+  uint8_t* const d_grp = static_cast<uint8_t*>(b.sc.d_sums) + r.f0 * (kSums + kTot);      // [nf][kSums] then [nf][kTot]
+  int64_t* const d_sums = reinterpret_cast<int64_t*>(d_grp);
+  int32_t* const d_tot = reinterpret_cast<int32_t*>(d_grp + r.nf * kSums);
+  if (int rc = sjpeg_hip_adapt_sums(d_hist, nf, b.q_start, b.min_quant, d_sums, d_tot, r.side)) return rc;
+  uint8_t* const d_q = static_cast<uint8_t*>(b.sc.d_sums) + b.n * (kSums + kTot) + r.f0 * 128;
+  if (int rc = adapt_decide(d_sums, d_tot, nf, b.q_start, b.yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2, b.qdelta_max_luma,
+                            b.qdelta_max_chroma, d_q, r.side)) return rc;
+  if (int rc = b.sc.ReadBack(r.side, b.h_q + r.f0 * 128, d_q, r.nf * 128)) return rc;
+  HIP_TRY(hipEventRecord(r.ev, r.side));
+  return 0;
+}
+
+// 2. the adapted matrices and their tables
+void range_adopt(BatchCall& b, const FrameRange& r) {
+  adopt_matrices(b.h_q, r.f0, r.nf, b.yuv_mode, b.min_quant, b.q_bias, b.quant.data(), b.tables.data());
+}
+
+// 3. the statistics pass -- it leaves its quantized blocks behind (144 B each) and the encode pass replays them: no second
+// colour conversion / DCT / quantization (the reference's stored run/levels, src/enc.cc:121-129,374-386) -- and the
+// symbol counts back
+int range_statistics(BatchCall& b, const FrameRange& r) {
+  for (size_t f = r.f0; f < r.f0 + r.nf; ++f) b.tables[f].flags |= SJPEG_HIP_QUANT_KEEP;
+  r.e->coefs_use = r.e->coefs_keep;
+  const sjpeg_hip_source ps = range_source(b, r.f0);
+  uint32_t* const d_freq = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b.sc.d_freq) + r.f0 * kFreq);
+  if (int rc = sjpeg_hip_scan_symbol_stats_multi(r.e, &ps, b.width, b.height, b.yuv_mode, static_cast<int>(r.nf), &b.tables[r.f0],
+                                                 d_freq, r.pass)) return rc;
+  if (int rc = b.sc.ReadBack(r.side, b.h_freq + r.f0 * kFreq, d_freq, r.nf * kFreq)) return rc;
+  dbg_mark("batch: counts read back");
+  HIP_TRY(hipEventRecord(r.ev, r.side));
+  dbg_mark("batch: event recorded");
+  return 0;
+}
+
+// 4. the optimised Huffman codes
+void range_codes(BatchCall& b, const FrameRange& r) {
+  for (size_t f = r.f0; f < r.f0 + r.nf; ++f) {
+    b.tables[f].flags = (b.tables[f].flags & ~SJPEG_HIP_QUANT_KEEP) | SJPEG_HIP_QUANT_REPLAY;
+    sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(b.h_freq + f * kFreq), b.yuv_mode, &b.specs[f * 4], &b.tables[f]);
+  }
+}
+
+// 5. the headers and the encode pass
+int range_encode(BatchCall& b, const FrameRange& r) {
+  static const std::string who = "sjpeg_hip_encode_batch_src";
+  if (int rc = batch_headers(who, [&](size_t) { return std::make_pair(b.width, b.height); }, r.f0, r.nf, b.yuv_mode,
+                             b.quant.data(), b.optimize ? b.specs.data() : nullptr, &b.headers, &b.offs)) return rc;
+  const sjpeg_hip_source ps = range_source(b, r.f0);
+  return sjpeg_hip_encode_scan_multi(r.e, &ps, b.width, b.height, b.yuv_mode, static_cast<int>(r.nf), &b.tables[r.f0], b.headers.data(),
+                                     b.offs.data(), /*append_eoi=*/1, b.d_out + r.f0 * b.out_stride, b.out_stride, b.d_sizes + r.f0, r.pass);
+}
 
 }  // namespace
 
@@ -2048,54 +2181,25 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
     if (sc.device != device) { if (sc.device >= 0) { (void)hipSetDevice(sc.device); sc.Drop(); } sc.device = device; }
     HIP_TRY(hipSetDevice(device));
     const size_t n = static_cast<size_t>(nframes);
-    std::vector<sjpeg_hip_scan_tables> tables(n);
-    std::vector<uint8_t> quant(n * 128);
-    {
-      sjpeg_hip_scan_tables t0;
-      memset(&t0, 0, sizeof(t0));
-      uint8_t q0[2][64];
-      memcpy(q0, quant_in, sizeof(q0));
-      sjpeg_hip_finalize_quant(q0, min_quant, q_bias, &t0);
-      sjpeg_hip_default_huffman(&t0);
-      for (size_t f = 0; f < n; ++f) { tables[f] = t0; memcpy(&quant[f * 128], q0, 128); }
-    }
-    // The batch is coded in PARTS (two halves from 24 frames on): every device pass of a part is one
-    // launch, and the host analysis a part needs between two passes -- the reference's float regression
-    // per frame (10 us), its Huffman table builder (10 us) -- runs while the device is busy with the
-    // other part's pass instead of leaving it idle (a quarter of the call for 32 4K frames).  Everything
-    // goes to the caller's stream in order; the host waits on events behind the read-backs only.
-    constexpr int kMaxParts = 4;
-    static const int parts_env = getenv("SJPEG_HIP_BATCH_PARTS") ? atoi(getenv("SJPEG_HIP_BATCH_PARTS")) : 0;   // (experiments)
-    // (measured: 32 4K frames 1.84 -> 1.61 ms in two parts, 16 frames 1.13 -> 1.21: parts of fewer than a dozen
-    // frames lose more to their smaller launches than the overlap gives)
-    // (round 5, with the persistent histogram kind, early uploads and the fit on the device: 4K frames -- 8 frames 0.40 ms
-    // in one part, 0.44 in two; 12 frames 0.54 / 0.55; 16 frames 0.68 / 0.66; 20 frames 0.80 / 0.79; 24 frames 0.99 / 0.89:
-    // two parts from 125 Mpixels on.  With the regression on the host it was 80: 12 frames 0.64 / 0.57)
-    const bool big = n >= 2 && static_cast<double>(n) * width * height >= 125e6;
-    int nparts = ((n >= 24 || big) && (adaptive || optimize)) ? 2 : 1;
-    if (parts_env >= 1 && parts_env <= kMaxParts && (adaptive || optimize) && n >= static_cast<size_t>(parts_env)) nparts = parts_env;
-    size_t part_lo[kMaxParts + 1];
-    for (int p = 0; p <= kMaxParts; ++p) {               // (the larger parts first: the engine scratch is sized once)
-      part_lo[p] = p >= nparts ? n : (n * p + nparts - 1) / nparts;
-    }
-    constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
-    constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
-    constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
     if (adaptive && (!sc.Ensure(&sc.d_hist, &sc.hist_cap, n * kHist) || !sc.Ensure(&sc.d_sums, &sc.sums_cap, n * (kSums + kTot + 128)))) {
       return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
     }
     if (optimize && !sc.Ensure(&sc.d_freq, &sc.freq_cap, n * kFreq)) return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
-    if (!sc.EnsurePinned(n * (kSums + kTot + kFreq)) || !sc.EnsureEvents()) return fail(SJPEG_HIP_ENOMEM, "hipHostMalloc / hipEventCreate(batch scratch) failed");
-    // (a part's sums and totals lie back to back -- [nf][kSums] then [nf][kTot] at f0 * (kSums + kTot) --: ONE read-back)
-    uint8_t* const h_sums = static_cast<uint8_t*>(sc.h_pinned);
-    uint8_t* const h_freq = h_sums + n * (kSums + kTot);                          // [n][kFreq]
-    auto part_source = [&](size_t f0) {
-      sjpeg_hip_source s = *src;
-      for (int i = 0; i < 3; ++i) {
-        if (s.plane[i] != nullptr) s.plane[i] = static_cast<const uint8_t*>(s.plane[i]) + static_cast<int64_t>(f0) * s.frame_stride[i];
-      }
-      return s;
-    };
+    if (!sc.EnsurePinned(n * (128 + kFreq)) || !sc.EnsureEvents()) return fail(SJPEG_HIP_ENOMEM, "hipHostMalloc / hipEventCreate(batch scratch) failed");
+    uint8_t* const h_q = static_cast<uint8_t*>(sc.h_pinned);
+    BatchCall b{src, width, height, yuv_mode, n, min_quant, q_bias, qdelta_max_luma, qdelta_max_chroma, optimize,
+                static_cast<uint8_t*>(d_out), out_stride, d_sizes, sc, h_q, h_q + n * 128};
+    {
+      sjpeg_hip_scan_tables t0;
+      memset(&t0, 0, sizeof(t0));
+      memcpy(b.q_start, quant_in, sizeof(b.q_start));
+      sjpeg_hip_finalize_quant(b.q_start, min_quant, q_bias, &t0);
+      sjpeg_hip_default_huffman(&t0);
+      b.tables.assign(n, t0);
+      b.quant.resize(n * 128);
+      for (size_t f = 0; f < n; ++f) memcpy(&b.quant[f * 128], b.q_start, 128);
+      b.specs.resize(optimize ? n * 4 : 0);
+    }
     // ---- LANES (round 6): jobs of about eight 4K frames, each a complete sequence of passes, on up to four streams at once
     // (sjpeg_hip_engine::lane).  One host thread drives them: a job's next step is taken when the event behind its
     // read-back has passed (polled -- the caller would block in hipEventSynchronize otherwise), whichever job that is.
@@ -2104,13 +2208,11 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
     const double total_px = static_cast<double>(n) * width * height;
     size_t njobs = static_cast<size_t>(total_px / job_px + 0.5);
     if (getenv("SJPEG_HIP_BATCH_JOB_MPIX") == nullptr) njobs = total_px >= 90e6 ? 2 : 1;     // (the sweep: DESIGN.md section 4)
-    static const int njobs_env = getenv("SJPEG_HIP_BATCH_NJOBS") ? atoi(getenv("SJPEG_HIP_BATCH_NJOBS")) : 0;   // (experiments)
-    if (njobs_env > 0) njobs = static_cast<size_t>(njobs_env);
     if (njobs > n) njobs = n;
     if (njobs > 64) njobs = 64;
     // (method 0 in lanes: 0.817 against 0.808 ms for 32 4K frames -- one K1 launch fills the chip by itself, and calls
     // back to back overlap their stitch with the next K1 anyway)
-    if (lanes_env != 0 && njobs >= 2 && (adaptive || optimize) && !engine->is_lane && parts_env == 0) {
+    if (lanes_env != 0 && njobs >= 2 && (adaptive || optimize) && !engine->is_lane) {
       const int nlanes = static_cast<int>(std::min<size_t>(njobs, lanes_env > 0 ? std::min(lanes_env, static_cast<int>(sjpeg_hip_engine::kLanes)) : sjpeg_hip_engine::kLanes));
       if (nlanes == 4 && engine->batch_lane3 == nullptr) HIP_TRY(hipStreamCreateWithFlags(&engine->batch_lane3, hipStreamNonBlocking));
       hipStream_t lane_st[sjpeg_hip_engine::kLanes] = {st, engine->batch_side, engine->batch_up, engine->batch_lane3};
@@ -2132,90 +2234,35 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
       if (int rco = order_on_stream(engine, st)) return rco;
       HIP_TRY(hipEventRecord(engine->lane_in, st));
       for (int l = 1; l < nlanes; ++l) HIP_TRY(hipStreamWaitEvent(lane_st[l], engine->lane_in, 0));
-      struct LanesGuard {                            // the child engines address whole calls again when this returns
-        sjpeg_hip_engine** e; int n;
-        ~LanesGuard() { for (int l = 1; l < n; ++l) if (e[l]) { e[l]->coefs_keep = e[l]->coefs_use = false; } }
-      } lanes_guard{lane_e, nlanes};
-      const bool keep_coefs = adaptive && optimize && getenv("SJPEG_HIP_NO_COEF_KEEP") == nullptr;
-      for (int l = 0; l < nlanes; ++l) lane_e[l]->coefs_keep = keep_coefs;
-      std::vector<sjpeg_hip_huffman_spec> jspecs(optimize ? n * 4 : 0);
-      struct Job { size_t f0, nf; int lane; int phase; };   // phase: 0 not started, 1 sums on their way, 2 counts on their way, 3 encode launched
-      std::vector<Job> jobs(njobs);
-      for (size_t j = 0; j < njobs; ++j) jobs[j] = Job{(n * j) / njobs, (n * (j + 1)) / njobs - (n * j) / njobs, static_cast<int>(j % static_cast<size_t>(nlanes)), 0};
-      const int ntab = yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
-      // (the matrices every frame starts from: quant[] itself is adapted frame by frame while later jobs still start)
-      uint8_t q_start[2][64];
-      memcpy(q_start, &quant[0], sizeof(q_start));
-      auto read_back_on = [&](hipStream_t s2, void* h_dst, const void* d_src, size_t bytes) -> int {
-        void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
-        return copy_by_kernel(dv, d_src, bytes, s2, hipMemcpyDeviceToHost, d_src, h_dst);
-      };
-      std::vector<uint8_t> jheaders;
-      std::vector<size_t> joffs;
-      // the three steps of a job; each ends with the launch of a pass (and of the read-back the next step waits for)
-      auto step_encode = [&](Job& jb) -> int {
-        sjpeg_hip_engine* const e = lane_e[jb.lane];
-        jheaders.clear();
-        joffs.assign(jb.nf + 1, 0);
-        uint8_t one[2048];
-        for (size_t f = jb.f0; f < jb.f0 + jb.nf; ++f) {
-          const size_t hs = sjpeg_hip_make_header_ex(width, height, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
-                                                     optimize ? &jspecs[f * 4] : nullptr, one, sizeof(one));
-          if (hs == 0) return fail(SJPEG_HIP_EINVAL, "header generation failed");
-          jheaders.insert(jheaders.end(), one, one + hs);
-          joffs[f - jb.f0 + 1] = jheaders.size();
-        }
-        const sjpeg_hip_source ps = part_source(jb.f0);
-        const int rc = sjpeg_hip_encode_scan_multi(e, &ps, width, height, yuv_mode, static_cast<int>(jb.nf), &tables[jb.f0], jheaders.data(),
-                                                   joffs.data(), /*append_eoi=*/1, static_cast<uint8_t*>(d_out) + jb.f0 * out_stride,
-                                                   out_stride, d_sizes + jb.f0, lane_st[jb.lane]);
-        jb.phase = 3;
-        return rc;
-      };
-      auto step_stats = [&](Job& jb, size_t j) -> int {
-        if (!optimize) return step_encode(jb);
-        sjpeg_hip_engine* const e = lane_e[jb.lane];
-        for (size_t f = jb.f0; f < jb.f0 + jb.nf; ++f) tables[f].flags |= SJPEG_HIP_QUANT_KEEP;
-        e->coefs_use = e->coefs_keep;
-        const sjpeg_hip_source ps = part_source(jb.f0);
-        uint32_t* const d_freq = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(sc.d_freq) + jb.f0 * kFreq);
-        if (int rc = sjpeg_hip_scan_symbol_stats_multi(e, &ps, width, height, yuv_mode, static_cast<int>(jb.nf), &tables[jb.f0], d_freq, lane_st[jb.lane])) return rc;
-        if (int rc = read_back_on(lane_st[jb.lane], h_freq + jb.f0 * kFreq, d_freq, jb.nf * kFreq)) return rc;
-        HIP_TRY(hipEventRecord(sc.job_ev[j], lane_st[jb.lane]));
-        jb.phase = 2;
-        return 0;
-      };
-      auto step_start = [&](Job& jb, size_t j) -> int {
-        if (!adaptive) return step_stats(jb, j);
-        sjpeg_hip_engine* const e = lane_e[jb.lane];
-        hipStream_t const js = lane_st[jb.lane];
-        const sjpeg_hip_source ps = part_source(jb.f0);
-        uint32_t* const d_hist = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(sc.d_hist) + jb.f0 * kHist);
-        if (int rc = sjpeg_hip_scan_histogram_src(e, &ps, width, height, yuv_mode, static_cast<int>(jb.nf), d_hist, js)) return rc;
-        uint8_t* const d_grp = static_cast<uint8_t*>(sc.d_sums) + jb.f0 * (kSums + kTot);      // [nf][kSums] then [nf][kTot]
-        if (int rc = sjpeg_hip_adapt_sums(d_hist, static_cast<int>(jb.nf), q_start, min_quant,
-                                          reinterpret_cast<int64_t*>(d_grp), reinterpret_cast<int32_t*>(d_grp + jb.nf * kSums), js)) return rc;
-        uint8_t* const d_q = static_cast<uint8_t*>(sc.d_sums) + n * (kSums + kTot) + jb.f0 * 128;
-        if (int rc = adapt_decide(reinterpret_cast<const int64_t*>(d_grp), reinterpret_cast<const int32_t*>(d_grp + jb.nf * kSums), static_cast<int>(jb.nf),
-                                  q_start, ntab, qdelta_max_luma, qdelta_max_chroma, d_q, js)) return rc;
-        if (int rc = read_back_on(js, h_sums + jb.f0 * 128, d_q, jb.nf * 128)) return rc;
-        HIP_TRY(hipEventRecord(sc.job_ev[j], js));
-        jb.phase = 1;
-        return 0;
-      };
-      auto step_after = [&](Job& jb, size_t j) -> int {       // the event of phase 1 / 2 has passed
-        if (jb.phase == 1) {
-          for (size_t f = jb.f0; f < jb.f0 + jb.nf; ++f) {
-            memcpy(&quant[f * 128], h_sums + f * 128, static_cast<size_t>(ntab) * 64);
-            sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
+      // however the call ends from here on, failed or thrown: the caller's stream ends behind every lane (what was launched
+      // reads the caller's buffers), and the child engines address whole calls again
+      struct LanesGuard {
+        sjpeg_hip_engine* e; const hipStream_t* st; int n;
+        ~LanesGuard() {
+          for (int l = 1; l < n; ++l) {
+            if (hipEventRecord(e->lane_done[l], st[l]) == hipSuccess) (void)hipStreamWaitEvent(st[0], e->lane_done[l], 0);
+            else (void)hipStreamSynchronize(st[l]);
+            e->lane[l]->coefs_keep = e->lane[l]->coefs_use = false;
           }
-          return step_stats(jb, j);
         }
-        for (size_t f = jb.f0; f < jb.f0 + jb.nf; ++f) {
-          tables[f].flags = (tables[f].flags & ~SJPEG_HIP_QUANT_KEEP) | SJPEG_HIP_QUANT_REPLAY;
-          sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(h_freq + f * kFreq), yuv_mode, &jspecs[f * 4], &tables[f]);
-        }
-        return step_encode(jb);
+      } lanes_guard{engine, lane_st, nlanes};
+      for (int l = 0; l < nlanes; ++l) lane_e[l]->coefs_keep = adaptive && optimize;
+      std::vector<FrameRange> jobs(njobs);
+      std::vector<int> phase(njobs, 0);     // 0 not started, 1 matrices on their way, 2 counts on their way, 3 encode launched
+      for (size_t j = 0; j < njobs; ++j) {
+        const size_t l = j % static_cast<size_t>(nlanes);
+        jobs[j] = FrameRange{(n * j) / njobs, (n * (j + 1)) / njobs - (n * j) / njobs, lane_e[l], lane_st[l], lane_st[l], sc.job_ev[j]};
+      }
+      // a job's next step: at its start, or when the event behind its read-back has passed
+      auto advance = [&](size_t j) -> int {
+        const FrameRange& r = jobs[j];
+        int& ph = phase[j];
+        if (ph == 0 && adaptive) { ph = 1; return range_analysis(b, r); }
+        if (ph == 1) range_adopt(b, r);
+        if (ph < 2 && optimize) { ph = 2; return range_statistics(b, r); }
+        if (ph == 2) range_codes(b, r);
+        ph = 3;
+        return range_encode(b, r);
       };
       static const bool lanes_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;    // (measurement aid: the host's timeline on stderr)
       const auto t_lanes = std::chrono::steady_clock::now();
@@ -2232,16 +2279,10 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
         for (int l = 0; l < nlanes && rc_lanes == 0; ++l) {
           const size_t ls = static_cast<size_t>(l);
           if (lane_busy[ls] < 0) {
-            // (SJPEG_HIP_BATCH_STAGGER=1, an experiment that lost: job j starts only when job j - 1 has launched its statistics
-            // pass, so that a histogram pass runs beside another KIND of pass instead of beside its twin -- 1.35 against 1.00 ms
-            // for 32 4K frames: the persistent histogram launch leaves the other kernel one workgroup per CU.  Default: all lanes
-            // start at once.)
-            static const int stagger = getenv("SJPEG_HIP_BATCH_STAGGER") ? atoi(getenv("SJPEG_HIP_BATCH_STAGGER")) : 0;
-            const bool held = stagger != 0 && lane_next[ls] < njobs && lane_next[ls] > 0 && jobs[lane_next[ls] - 1].phase < (stagger == 2 ? 3 : 2);
-            if (lane_next[ls] < njobs && !held) {      // (a lane's jobs follow each other: the engine's scratch is one job's)
+            if (lane_next[ls] < njobs) {      // (a lane's jobs follow each other: the engine's scratch is one job's)
               lane_busy[ls] = static_cast<long long>(lane_next[ls]);
               lane_next[ls] += static_cast<size_t>(nlanes);
-              rc_lanes = step_start(jobs[static_cast<size_t>(lane_busy[ls])], static_cast<size_t>(lane_busy[ls]));
+              rc_lanes = advance(static_cast<size_t>(lane_busy[ls]));
               lmark("started", static_cast<size_t>(lane_busy[ls]));
               moved = true;
             }
@@ -2249,9 +2290,9 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
             const size_t j = static_cast<size_t>(lane_busy[ls]);
             const hipError_t q = hipEventQuery(sc.job_ev[j]);
             if (q == hipSuccess) {
-              lmark(jobs[j].phase == 1 ? "sums here" : "counts here", j);
-              rc_lanes = step_after(jobs[j], j);
-              lmark(jobs[j].phase == 2 ? "statistics launched" : "encode launched", j);
+              lmark(phase[j] == 1 ? "sums here" : "counts here", j);
+              rc_lanes = advance(j);
+              lmark(phase[j] == 2 ? "statistics launched" : "encode launched", j);
               moved = true;
             } else if (q != hipErrorNotReady) {
               (void)hipGetLastError();
@@ -2260,17 +2301,24 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
               (void)hipGetLastError();
             }
           }
-          if (rc_lanes == 0 && lane_busy[ls] >= 0 && jobs[static_cast<size_t>(lane_busy[ls])].phase == 3) { lane_busy[ls] = -1; ++done; moved = true; }
+          if (rc_lanes == 0 && lane_busy[ls] >= 0 && phase[static_cast<size_t>(lane_busy[ls])] == 3) { lane_busy[ls] = -1; ++done; moved = true; }
         }
         if (!moved) __builtin_ia32_pause();
       }
-      // the caller's stream ends behind every lane, failed call or not (what was launched reads the caller's buffers)
-      for (int l = 1; l < nlanes; ++l) {
-        if (hipEventRecord(engine->lane_done[l], lane_st[l]) == hipSuccess) (void)hipStreamWaitEvent(st, engine->lane_done[l], 0);
-        else (void)hipStreamSynchronize(lane_st[l]);
-      }
       return rc_lanes;
     }
+    // ---- PARTS (round 5; two halves from 24 frames on): every device pass of a part is one launch, and the host analysis
+    // a part needs between two passes -- the Huffman table builder (10 us a frame) -- runs while the device is busy with
+    // the other part's pass instead of leaving it idle.  Everything goes to the caller's stream in order; the host waits
+    // on events behind the read-backs only.
+    // (measured: 32 4K frames 1.84 -> 1.61 ms in two parts, 16 frames 1.13 -> 1.21: parts of fewer than a dozen
+    // frames lose more to their smaller launches than the overlap gives)
+    // (round 5, with the persistent histogram kind, early uploads and the fit on the device: 4K frames -- 8 frames 0.40 ms
+    // in one part, 0.44 in two; 12 frames 0.54 / 0.55; 16 frames 0.68 / 0.66; 20 frames 0.80 / 0.79; 24 frames 0.99 / 0.89:
+    // two parts from 125 Mpixels on.  With the regression on the host it was 80: 12 frames 0.64 / 0.57)
+    const bool big = n >= 2 && static_cast<double>(n) * width * height >= 125e6;
+    const int nparts = ((n >= 24 || big) && (adaptive || optimize)) ? 2 : 1;
+    if (!sc.EnsureJobEvents(static_cast<size_t>(nparts))) return fail(SJPEG_HIP_ENOMEM, "hipEventCreate(batch scratch) failed");
     // (in parts: the sums of a part and their read-back go to the side stream, behind the pass that made
     // the partials, so that the next part's pass starts right behind this one's)
     hipStream_t rs = st;
@@ -2278,66 +2326,31 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
       engine->reduce_stream = engine->batch_side; engine->reduce_ev = sc.pass_done;
       engine->replay_total = nframes;
       rs = engine->batch_side;
-      static const bool late_uploads = getenv("SJPEG_HIP_LATE_UPLOADS") != nullptr;       // (A/B: uploads in the call's own stream)
-      if (!late_uploads) {
-        // The early uploads overwrite what the PREVIOUS call's kernels may still be reading -- its per-frame tables (K1 on
-        // its stream), its headers and header offsets (the stitch kernels; the engine's side stream in pipelined mode).  An
-        // adaptive call's first upload follows a host wait on its own histogram pass, which sits behind that work on the
-        // call's stream; a call with optimised tables alone (methods 1, 2) uploads at once, and the side stream is behind
-        // nobody's wait: the upload stream is put behind both before anything goes to it (two asynchronous
-        // method-1 batches back to back: test_back_to_back_batches_without_a_host_wait).
-        if (int rco = order_on_stream(engine, st)) return rco;
-        HIP_TRY(hipEventRecord(sc.call_begin, st));
-        HIP_TRY(hipStreamWaitEvent(engine->batch_up, sc.call_begin, 0));
-        if (engine->side_pending) {
-          if (int rcs = side_mark(engine)) return rcs;
-          HIP_TRY(hipStreamWaitEvent(engine->batch_up, engine->side_done, 0));
-        }
-        engine->up_stream = engine->batch_up;
+      // The early uploads overwrite what the PREVIOUS call's kernels may still be reading -- its per-frame tables (K1 on
+      // its stream), its headers and header offsets (the stitch kernels; the engine's side stream in pipelined mode).  An
+      // adaptive call's first upload follows a host wait on its own histogram pass, which sits behind that work on the
+      // call's stream; a call with optimised tables alone (methods 1, 2) uploads at once, and the side stream is behind
+      // nobody's wait: the upload stream is put behind both before anything goes to it (two asynchronous
+      // method-1 batches back to back: test_back_to_back_batches_without_a_host_wait).
+      if (int rco = order_on_stream(engine, st)) return rco;
+      HIP_TRY(hipEventRecord(sc.call_begin, st));
+      HIP_TRY(hipStreamWaitEvent(engine->batch_up, sc.call_begin, 0));
+      if (engine->side_pending) {
+        if (int rcs = side_mark(engine)) return rcs;
+        HIP_TRY(hipStreamWaitEvent(engine->batch_up, engine->side_done, 0));
       }
+      engine->up_stream = engine->batch_up;
     }
-    // device -> the pinned block, on the side stream: a kernel writes it over the bus (no runtime copy: stage_copy_kernel)
-    auto read_back = [&](void* h_dst, const void* d_src, size_t bytes) -> int {
-      void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
-      return copy_by_kernel(dv, d_src, bytes, rs, hipMemcpyDeviceToHost, d_src, h_dst);
-    };
-    static const int groups_env = getenv("SJPEG_HIP_SUMS_GROUPS") ? atoi(getenv("SJPEG_HIP_SUMS_GROUPS")) : 0;   // (A/B: 1 = one group a part)
-    static const bool device_decide = getenv("SJPEG_HIP_HOST_REGRESSION") == nullptr;   // (A/B: the float half of the analysis on the host)
-    // (two groups pay when the HOST fits the steps -- it fits the first half while the second is on its way; with the fit on
-    // the device the second group's launches only lengthen the chain: 1.150 against 1.141 ms)
-    auto sums_groups = [&](size_t nf) -> int { return (groups_env == 1 || nf < 8 || (device_decide && groups_env != 2)) ? 1 : 2; };
-    static const bool no_coefs = getenv("SJPEG_HIP_NO_COEF_KEEP") != nullptr;       // (A/B: every pass from the pixels)
-    engine->coefs_keep = adaptive && optimize && !no_coefs;
+    engine->coefs_keep = adaptive && optimize;
+    std::vector<FrameRange> parts(static_cast<size_t>(nparts));
+    for (int p = 0; p < nparts; ++p) {               // (the larger parts first: the engine scratch is sized once)
+      const size_t f0 = (n * p + nparts - 1) / nparts;
+      parts[p] = FrameRange{f0, (n * (p + 1) + nparts - 1) / nparts - f0, engine, st, rs, sc.job_ev[p]};
+    }
     if (adaptive) {
-      for (int p = 0; p < nparts; ++p) {
-        const size_t f0 = part_lo[p], nf = part_lo[p + 1] - f0;
-        const sjpeg_hip_source ps = part_source(f0);
-        uint32_t* const d_hist = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(sc.d_hist) + f0 * kHist);
-        engine->replay_first = static_cast<int>(f0);
-        int rc = sjpeg_hip_scan_histogram_src(engine, &ps, width, height, yuv_mode, static_cast<int>(nf), d_hist, stream);
-        if (rc != 0) return rc;
-        // the analysis sums in TWO groups, each with its read-back and event: the host fits the first half of the part
-        // while the second is still on its way (what comes back between a part's histogram pass and its statistics
-        // launch is on the critical path of the call: the device waits for that launch)
-        for (int h = 0; h < sums_groups(nf); ++h) {
-          const size_t g0 = f0 + (nf * h) / sums_groups(nf), gn = f0 + (nf * (h + 1)) / sums_groups(nf) - g0;
-          uint8_t* const d_grp = static_cast<uint8_t*>(sc.d_sums) + g0 * (kSums + kTot);      // [gn][kSums] then [gn][kTot]
-          rc = sjpeg_hip_adapt_sums(d_hist + (g0 - f0) * (kHist / sizeof(uint32_t)), static_cast<int>(gn), reinterpret_cast<const uint8_t(*)[64]>(&quant[0]), min_quant,
-                                    reinterpret_cast<int64_t*>(d_grp), reinterpret_cast<int32_t*>(d_grp + gn * kSums), rs);
-          if (rc != 0) return rc;
-          if (device_decide) {
-            // the regression too (adapt_decide_kernel): 128 bytes a frame come back instead of 52 KB, and the host's 7 us a frame
-            // between a part's histogram pass and its statistics launch are gone
-            uint8_t* const d_q = static_cast<uint8_t*>(sc.d_sums) + n * (kSums + kTot) + g0 * 128;
-            if ((rc = adapt_decide(reinterpret_cast<const int64_t*>(d_grp), reinterpret_cast<const int32_t*>(d_grp + gn * kSums), static_cast<int>(gn),
-                                   reinterpret_cast<const uint8_t(*)[64]>(&quant[0]), yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2,
-                                   qdelta_max_luma, qdelta_max_chroma, d_q, rs))) return rc;
-            if (int rcc = read_back(h_sums + g0 * 128, d_q, gn * 128)) return rcc;
-          } else {
-            if (int rcc = read_back(h_sums + g0 * (kSums + kTot), d_grp, gn * (kSums + kTot))) return rcc;
-          }
-          HIP_TRY(hipEventRecord(sc.ev[2 * p + h], rs));
-        }
+      for (const FrameRange& r : parts) {
+        engine->replay_first = static_cast<int>(r.f0);
+        if (int rc = range_analysis(b, r)) return rc;
       }
     }
     static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
@@ -2348,84 +2361,35 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
                                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_epoch).count());
     };
     mark("hist launched", -1);
-    std::vector<sjpeg_hip_huffman_spec> specs(optimize ? n * 4 : 0);
-    // (part p's regression runs while the device works on the histogram of part p + 1 / the statistics of part p - 1)
+    // (part p's matrices are adopted while the device works on the histogram of part p + 1 / the statistics of part p - 1)
     for (int p = 0; p < nparts; ++p) {
-      const size_t f0 = part_lo[p], nf = part_lo[p + 1] - f0;
+      const FrameRange& r = parts[p];
       if (adaptive) {
-        for (int h = 0; h < sums_groups(nf); ++h) {
-          const size_t g0 = f0 + (nf * h) / sums_groups(nf), gn = f0 + (nf * (h + 1)) / sums_groups(nf) - g0;
-          mark("wait sums", p);
-          HIP_TRY(hipEventSynchronize(sc.ev[2 * p + h]));
-          mark("sums here", p);
-          const uint8_t* const grp = h_sums + g0 * (kSums + kTot);
-          if (device_decide) {
-            const int ntab = yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
-            for (size_t f = g0; f < g0 + gn; ++f) {
-              memcpy(&quant[f * 128], h_sums + f * 128, static_cast<size_t>(ntab) * 64);
-              sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
-            }
-            continue;
-          }
-          for (size_t f = g0; f < g0 + gn; ++f) {
-            sjpeg_hip_adapt_quant_sums(reinterpret_cast<const int64_t*>(grp + (f - g0) * kSums),
-                                       reinterpret_cast<const int32_t*>(grp + gn * kSums + (f - g0) * kTot), yuv_mode,
-                                       reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias,
-                                       qdelta_max_luma, qdelta_max_chroma, &tables[f]);
-          }
-        }
+        mark("wait sums", p);
+        HIP_TRY(hipEventSynchronize(r.ev));
+        mark("sums here", p);
+        range_adopt(b, r);
       }
       mark("adapted", p);
       if (optimize) {
-        // the statistics pass leaves its quantized blocks behind (144 B each) and the encode pass
-        // replays them: no second colour conversion / DCT / quantization (the reference's stored
-        // run/levels, src/enc.cc:121-129,374-386)
-        for (size_t f = f0; f < f0 + nf; ++f) tables[f].flags |= SJPEG_HIP_QUANT_KEEP;
-        engine->replay_total = nframes; engine->replay_first = static_cast<int>(f0);
-        engine->coefs_use = engine->coefs_keep;
-        const sjpeg_hip_source ps = part_source(f0);
-        uint32_t* const d_freq = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(sc.d_freq) + f0 * kFreq);
-        const int rc = sjpeg_hip_scan_symbol_stats_multi(engine, &ps, width, height, yuv_mode, static_cast<int>(nf), &tables[f0], d_freq, stream);
-        if (rc != 0) return rc;
-        if (int rcc = read_back(h_freq + f0 * kFreq, d_freq, nf * kFreq)) return rcc;
-        dbg_mark("batch: counts read back");
-        HIP_TRY(hipEventRecord(sc.ev[2 * kMaxParts + p], rs));
-        dbg_mark("batch: event recorded");
+        engine->replay_total = nframes; engine->replay_first = static_cast<int>(r.f0);
+        if (int rc = range_statistics(b, r)) return rc;
         mark("stats launched", p);
       }
     }
     // (part p's table builder runs while the device counts the symbols of part p + 1 / codes part p - 1)
-    std::vector<uint8_t> headers;
-    std::vector<size_t> offs;
     for (int p = 0; p < nparts; ++p) {
-      const size_t f0 = part_lo[p], nf = part_lo[p + 1] - f0;
+      const FrameRange& r = parts[p];
       if (optimize) {
         mark("wait freq", p);
-        HIP_TRY(hipEventSynchronize(sc.ev[2 * kMaxParts + p]));
+        HIP_TRY(hipEventSynchronize(r.ev));
         mark("freq here", p);
-        for (size_t f = f0; f < f0 + nf; ++f) {
-          tables[f].flags = (tables[f].flags & ~SJPEG_HIP_QUANT_KEEP) | SJPEG_HIP_QUANT_REPLAY;
-          sjpeg_hip_optimize_huffman(reinterpret_cast<const uint32_t*>(h_freq + f * kFreq), yuv_mode, &specs[f * 4], &tables[f]);
-        }
-        engine->replay_total = nframes; engine->replay_first = static_cast<int>(f0);
+        range_codes(b, r);
+        engine->replay_total = nframes; engine->replay_first = static_cast<int>(r.f0);
       }
       mark("tables built", p);
-      headers.clear();
-      offs.assign(nf + 1, 0);
-      uint8_t one[2048];
-      for (size_t f = f0; f < f0 + nf; ++f) {
-        const size_t hs = sjpeg_hip_make_header_ex(width, height, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
-                                                   optimize ? &specs[f * 4] : nullptr, one, sizeof(one));
-        if (hs == 0) return fail(SJPEG_HIP_EINVAL, "header generation failed");
-        headers.insert(headers.end(), one, one + hs);
-        offs[f - f0 + 1] = headers.size();
-      }
-      const sjpeg_hip_source ps = part_source(f0);
-      if (engine->replay_total > 0) engine->replay_first = static_cast<int>(f0);     // (where this part's tables / headers lie)
-      const int rc_enc = sjpeg_hip_encode_scan_multi(engine, &ps, width, height, yuv_mode, static_cast<int>(nf), &tables[f0], headers.data(),
-                                                     offs.data(), /*append_eoi=*/1, static_cast<uint8_t*>(d_out) + f0 * out_stride,
-                                                     out_stride, d_sizes + f0, stream);
-      if (rc_enc != 0) return rc_enc;
+      if (engine->replay_total > 0) engine->replay_first = static_cast<int>(r.f0);     // (where this part's tables / headers lie)
+      if (int rc = range_encode(b, r)) return rc;
       mark("encode launched", p);
     }
     return 0;
@@ -2498,9 +2462,6 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
   auto mark = [&](const char* what) {
     if (batch_debug) fprintf(stderr, "ragged %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
   };
-  constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
-  constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
-  constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
   // the analysis goes in chunks of consecutive frames of a group whose scratch -- the pass's partials (the histogram's
   // at most one per segment) and the per-frame results -- stays inside the engine's limit
   auto chunks_of = [&](const RaggedGroup& g, size_t per_seg, size_t per_frame) {
@@ -2523,10 +2484,6 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
   }
   uint8_t* const h_q = static_cast<uint8_t*>(sc.h_pinned);                     // [n][128]
   uint8_t* const h_freq = h_q + (adaptive ? n * 128 : 0);                       // [n][kFreq]
-  auto read_back = [&](void* h_dst, const void* d_src, size_t bytes) -> int {
-    void* const dv = sc.d_pinned == nullptr ? nullptr : static_cast<uint8_t*>(sc.d_pinned) + (static_cast<uint8_t*>(h_dst) - static_cast<uint8_t*>(sc.h_pinned));
-    return copy_by_kernel(dv, d_src, bytes, st, hipMemcpyDeviceToHost, d_src, h_dst);
-  };
   if (adaptive) {
     // 1. histograms, the adaptation with each frame's own starting matrices, the adapted matrices back
     std::vector<std::vector<std::pair<size_t, size_t>>> chunks;
@@ -2573,18 +2530,14 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
         HIP_TRY(hipGetLastError());
       }
     }
-    if (int rc = read_back(h_q, d_qa, n * 128)) return rc;
+    if (int rc = sc.ReadBack(st, h_q, d_qa, n * 128)) return rc;
     HIP_TRY(hipEventRecord(sc.pass_done, st));
     mark("hist launched");
     HIP_TRY(hipEventSynchronize(sc.pass_done));
     mark("matrices here");
     // 2. the tables of the adapted matrices
     for (size_t gi = 0; gi < groups.size(); ++gi) {
-      const int ntab = groups[gi].yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
-      for (size_t f = gbase[gi]; f < gbase[gi] + groups[gi].frames.size(); ++f) {
-        memcpy(&quant[f * 128], h_q + f * 128, static_cast<size_t>(ntab) * 64);
-        sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(&quant[f * 128]), min_quant, q_bias, &tables[f]);
-      }
+      adopt_matrices(h_q, gbase[gi], groups[gi].frames.size(), groups[gi].yuv_mode, min_quant, q_bias, quant.data(), tables.data());
     }
   }
   std::vector<sjpeg_hip_huffman_spec> specs(optimize ? n * 4 : 0);
@@ -2605,7 +2558,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
         if (int rc = ragged_analysis(e, false, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      &tables[gbase[gi] + c.first], 1, d_freq, st)) return rc;
-        if (int rc = read_back(h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;
+        if (int rc = sc.ReadBack(st, h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;
       }
     }
     HIP_TRY(hipEventRecord(sc.pass_done, st));
@@ -2641,16 +2594,9 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
     RaggedGroup& g = groups[gi];
     const size_t ng = g.frames.size();
     std::vector<uint8_t> headers;
-    std::vector<size_t> offs(ng + 1, 0);
-    uint8_t one[2048];
-    for (size_t k = 0; k < ng; ++k) {
-      const size_t f = gbase[gi] + k;
-      const size_t hs = sjpeg_hip_make_header_ex(g.frames[k].width, g.frames[k].height, g.yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(&quant[f * 128]),
-                                                 optimize ? &specs[f * 4] : nullptr, one, sizeof(one));
-      if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
-      headers.insert(headers.end(), one, one + hs);
-      offs[k + 1] = headers.size();
-    }
+    std::vector<size_t> offs;
+    if (int rc = batch_headers(who, [&](size_t k) { return std::make_pair(g.frames[k].width, g.frames[k].height); }, gbase[gi], ng,
+                               g.yuv_mode, quant.data(), optimize ? specs.data() : nullptr, &headers, &offs)) return rc;
     if (gi + 1 == groups.size()) mark("tables built");
     if (int rc = ready(gi)) return rc;
     const int rc = sjpeg_hip_encode_ragged_src(e, g.format, g.yuv_mode, static_cast<int>(ng), g.frames.data(), &tables[gbase[gi]],

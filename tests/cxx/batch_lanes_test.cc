@@ -2,7 +2,7 @@
 // with every analysis method, against the host API's single-picture encode of the same frame (SjpegEncode: another code
 // path of the library, byte-identical by contract).  Built twice by tools/san_engine.sh: as is, and against a library
 // whose engine (scan_engine.hip's host half: buffers, streams, child engines, the lanes' state machine) is compiled with
-// AddressSanitizer.  The environment decides how the batch is cut (SJPEG_HIP_BATCH_JOB_MPIX / _LANES / _NJOBS).
+// AddressSanitizer.  The environment decides how the batch is cut (SJPEG_HIP_BATCH_JOB_MPIX / _LANES).
 //   batch_lanes_test [rounds]
 #include <hip/hip_runtime.h>
 
