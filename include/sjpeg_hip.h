@@ -469,6 +469,62 @@ int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* engine, int format, int y
                                      void* d_out, uint64_t* d_sizes, int* modes /*[nframes], host, or NULL*/,
                                      void* stream);
 
+/* ---- ragged batches searched to a per-picture target size or PSNR ----
+ * The two measurements of the reference's multi-pass search (Encoder::LoopScan, src/dichotomy.cc:113-205) over a ragged
+ * batch (frames[] as above, out_offset / out_capacity ignored; tables[f] with tables_per_frame = 1, else tables[0]):
+ * sjpeg_hip_scan_quant_error_ragged_src: d_err[nframes] (device), frame f's what sjpeg_hip_scan_quant_error_src() makes
+ *   of that picture alone (QuantizeError summed as Encoder::ComputePSNR does).  Asynchronous on `stream`.
+ * sjpeg_hip_scan_counted_bits_ragged_src: d_bits[nframes] (device), what the reference's BitCounter reports for frame f's
+ *   scan with its tables (src/bit_writer.h:292-365): the entropy bits plus 8 for every 0xFF among the COMPLETED bytes
+ *   (the 1-padded last byte does not count).  The ragged encode without its output: the segment scratch is planned
+ *   from the host API's first capacity; a frame whose segments overflow that plan is counted again with its
+ *   sjpeg_hip_frame_bound() plan in a second launch of only those frames.  One host wait (which frames overflowed), and
+ *   one more after a recount; a frame past even its worst-case plan is SJPEG_HIP_ERUNTIME, naming it.
+ * Both refuse trellis, keep / replay and restart flags, split into several launches under
+ * SJPEG_HIP_SCRATCH_LIMIT_BYTES, run ordered in pipelined mode and name the offending frame in sjpeg_hip_last_error().
+ *
+ * sjpeg_hip_encode_ragged_search_src: sjpeg_hip_encode_ragged_batch_src() with the search.  Frame f's bytes are what
+ *   the reference's sjpeg::Encode() makes of that picture alone with its starting matrices quant[f] (quant[0] when
+ *   quant_per_frame = 0), min_quant, q_bias, the qdelta limits, Huffman_compress = (method not in {0, 3}),
+ *   adaptive_quantization = (method >= 3) and search[f] (search[0] when search_per_frame = 0).  q_out[f] / value_out[f]
+ *   (host, or NULL): the SearchHook's best_q and best_result after the call, -1 for a frame that was not searched
+ *   (passes <= 1).  A call in which no frame is searched is sjpeg_hip_encode_ragged_batch_src().
+ *   Every pass is one launch over the frames still searching: the adaptation of their kept histograms to the pass's
+ *   matrices (methods 3..6), then one measurement -- symbol statistics (size, optimised codes), counted bits (size,
+ *   methods 0 and 3) or the quantization error (PSNR).  Host waits per pass: two for methods 3..6 (matrices back,
+ *   measurements back), one otherwise; a count that overflowed its first plan adds one.  These are per SEARCH: the
+ *   frames with size targets and those with PSNR targets are searched one after the other, and so are the parts
+ *   below, so a call with both kinds of target, or in P parts, waits up to twice, or P times, as often.  A frame leaves
+ *   the search when its SearchHook is done.  The frames are then coded with their best matrices, without further adaptation, by
+ *   the method 1 (optimised codes) or 0 flow of sjpeg_hip_encode_ragged_batch_src().  The kept histograms and the
+ *   partials count against SJPEG_HIP_SCRATCH_LIMIT_BYTES: past it the call goes in parts of consecutive frames, each a
+ *   complete search.  yuv_mode: 1, 3 or 4.  SJPEG_HIP_EINVAL for every check of sjpeg_hip_encode_ragged_batch_src(), a
+ *   NULL search, target_mode other than 1 or 2 and a non-finite target_value. */
+typedef struct sjpeg_hip_search {
+  int32_t target_mode;   /* 1 = size in bytes (EncoderParam::TARGET_SIZE), 2 = PSNR in dB (TARGET_PSNR) */
+  float target_value;
+  int32_t passes;        /* clamped to 1..20 (src/api.cc:169); a frame with passes <= 1 is not searched */
+  float tolerance;       /* percent, as EncoderParam::tolerance (default 1) */
+  float qmin, qmax;      /* as EncoderParam (defaults 0, 100) */
+} sjpeg_hip_search;
+
+int sjpeg_hip_scan_quant_error_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                          const sjpeg_hip_scan_tables* tables, int tables_per_frame,
+                                          uint64_t* d_err /*[nframes]*/, void* stream);
+int sjpeg_hip_scan_counted_bits_ragged_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                           const sjpeg_hip_scan_tables* tables, int tables_per_frame,
+                                           uint64_t* d_bits /*[nframes]*/, void* stream);
+int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                       const uint8_t (*quant)[2][64], int quant_per_frame,
+                                       const uint8_t* min_quant /*[2][64] or NULL*/, int q_bias, int method,
+                                       int qdelta_max_luma, int qdelta_max_chroma,
+                                       const sjpeg_hip_search* search, int search_per_frame,
+                                       float* q_out /*[nframes], host, or NULL*/, float* value_out /*[nframes], host, or NULL*/,
+                                       void* d_out, uint64_t* d_sizes, void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -110,6 +110,14 @@ class RaggedFrame(C.Structure):
                 ("height", C.c_int32), ("out_offset", C.c_uint64), ("out_capacity", C.c_uint64)]
 
 
+class SearchParams(C.Structure):
+    """struct sjpeg_hip_search (include/sjpeg_hip.h): the multi-pass search of one picture of a ragged batch --
+    target_mode 1 (size in bytes) or 2 (PSNR in dB), target_value, passes (1..20; <= 1: no search), tolerance (percent),
+    qmin, qmax."""
+    _fields_ = [("target_mode", C.c_int32), ("target_value", C.c_float), ("passes", C.c_int32),
+                ("tolerance", C.c_float), ("qmin", C.c_float), ("qmax", C.c_float)]
+
+
 class HuffmanSpec(C.Structure):
     """struct sjpeg_hip_huffman_spec (include/sjpeg_hip.h)."""
     _fields_ = [("bits", C.c_uint8 * 16), ("syms", C.c_uint8 * 256), ("nsyms", C.c_int32)]
@@ -262,6 +270,17 @@ def lib() -> C.CDLL:
                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sjpeg_hip_encode_ragged_auto_src.restype = C.c_int
+    L.sjpeg_hip_scan_quant_error_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_scan_quant_error_ragged_src.restype = C.c_int
+    L.sjpeg_hip_scan_counted_bits_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_scan_counted_bits_ragged_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_search_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.POINTER(SearchParams), C.c_int, C.POINTER(C.c_float),
+                                                     C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_encode_ragged_search_src.restype = C.c_int
     _lib = L
     return L
 
@@ -296,6 +315,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_scan_histogram_ragged_src", "sjpeg_hip_scan_symbol_stats_ragged_src", "sjpeg_hip_encode_ragged_batch_src",
     "sjpeg_hip_riskiness_ragged_src", "sjpeg_hip_riskiness_verdict", "sjpeg_hip_sharp_ragged_workspace",
     "sjpeg_hip_sharp_yuv_ragged", "sjpeg_hip_encode_ragged_auto_src",
+    "sjpeg_hip_scan_quant_error_ragged_src", "sjpeg_hip_scan_counted_bits_ragged_src", "sjpeg_hip_encode_ragged_search_src",
 ]
 
 
@@ -1025,6 +1045,75 @@ class Engine:
                   "sjpeg_hip_encode_ragged_batch_src")
         return out, sizes, list(offsets)
 
+    def _ragged_tables(self, n, tables, what):
+        per_frame = isinstance(tables, (list, tuple))
+        if per_frame and len(tables) != n:
+            raise SjpegError(f"{what}: one ScanTables per frame")
+        return ((ScanTables * n)(*tables) if per_frame else (ScanTables * 1)(tables)), per_frame
+
+    def scan_quant_error_ragged(self, fmt, planes_per_frame, dims, yuv_mode, tables):
+        """sjpeg_hip_scan_quant_error_ragged_src: the quantization error of pictures of different sizes in one call, with
+        one ScanTables for every frame or a list of one per frame.  Returns an int64 CUDA tensor [F] (uint64 totals),
+        frame k's what scan_quant_error_source makes of it alone.  Asynchronous on the current torch stream."""
+        import torch
+        n = len(dims)
+        tarr, per_frame = self._ragged_tables(n, tables, "scan_quant_error_ragged")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        out = torch.zeros(n, dtype=torch.int64, device=_ragged_device(planes_per_frame))
+        self._chk(lib().sjpeg_hip_scan_quant_error_ragged_src(self._h, fmt, yuv_mode, n, frames, C.cast(tarr, C.c_void_p),
+                                                              int(per_frame), out.data_ptr(), self._stream()),
+                  "sjpeg_hip_scan_quant_error_ragged_src")
+        return out
+
+    def scan_counted_bits_ragged(self, fmt, planes_per_frame, dims, yuv_mode, tables):
+        """sjpeg_hip_scan_counted_bits_ragged_src: what the reference's BitCounter reports for the scan of each picture
+        with its tables (entropy bits + 8 per 0xFF among the completed bytes), pictures of different sizes in one call.
+        Returns an int64 CUDA tensor [F].  The host waits inside once (which frames overflowed the first plan)."""
+        import torch
+        n = len(dims)
+        tarr, per_frame = self._ragged_tables(n, tables, "scan_counted_bits_ragged")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        out = torch.zeros(n, dtype=torch.int64, device=_ragged_device(planes_per_frame))
+        self._chk(lib().sjpeg_hip_scan_counted_bits_ragged_src(self._h, fmt, yuv_mode, n, frames, C.cast(tarr, C.c_void_p),
+                                                               int(per_frame), out.data_ptr(), self._stream()),
+                  "sjpeg_hip_scan_counted_bits_ragged_src")
+        return out
+
+    def encode_ragged_search(self, fmt, planes_per_frame, dims, yuv_mode, quant, search, method=4, min_quant=None,
+                             q_bias=0x78, dmax_luma=12, dmax_chroma=1, capacities=None, out=None, offsets=None,
+                             sizes=None):
+        """sjpeg_hip_encode_ragged_search_src: encode_ragged_batch with the reference's multi-pass search to a target
+        size (bytes) or PSNR (dB) per picture.  search: one SearchParams (or dict of its fields) for every frame, or a
+        list of one per frame.  Frame k's bytes are what sjpeg::Encode makes of it alone with its starting matrix,
+        Huffman_compress = method not in (0, 3), adaptive_quantization = method >= 3 and its search fields.  Returns
+        (out, sizes, offsets, q, value): q[k] / value[k] the SearchHook's best q and result, -1 where the frame was not
+        searched (passes <= 1).  The host waits inside once or twice per pass; the final encode is asynchronous."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged_search: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(quant, (list, tuple))
+        if per_frame and len(quant) != n:
+            raise SjpegError("encode_ragged_search: one starting matrix per frame")
+        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+        search_per_frame = isinstance(search, (list, tuple))
+        if search_per_frame and len(search) != n:
+            raise SjpegError("encode_ragged_search: one search per frame")
+        sp = [_search_params(x) for x in (search if search_per_frame else [search])]
+        sarr = (SearchParams * len(sp))(*sp)
+        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+        if capacities is None:
+            capacities = [frame_bound(w, h, yuv_mode, 2048) for (w, h) in dims]
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
+        q_out, v_out = (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_search_src(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data,
+                                                           int(per_frame), mq.ctypes.data if mq is not None else None,
+                                                           q_bias, int(method), dmax_luma, dmax_chroma, sarr,
+                                                           int(search_per_frame), q_out, v_out, out.data_ptr(),
+                                                           sizes.data_ptr(), self._stream()),
+                  "sjpeg_hip_encode_ragged_search_src")
+        return out, sizes, list(offsets), [float(x) for x in q_out], [float(x) for x in v_out]
+
     def riskiness_ragged(self, fmt, planes_per_frame, dims, table=None):
         """sjpeg_hip_riskiness_ragged_src: the three riskiness sums of pictures of different sizes in one call (fmt:
         SRC_RGB / SRC_BGRA / SRC_RGBA; planes_per_frame, dims as encode_ragged).  table: the 117649-byte score table
@@ -1096,6 +1185,18 @@ class Engine:
         return out, sizes, list(offsets), [int(m) for m in modes]
 
 
+TARGET_SIZE, TARGET_PSNR = 1, 2      # sjpeg_hip_search.target_mode (EncoderParam::TargetMode)
+
+
+def _search_params(x):
+    """A SearchParams of a SearchParams or a dict of its fields (defaults: passes 10, tolerance 1, qmin 0, qmax 100)."""
+    if isinstance(x, SearchParams):
+        return x
+    d = dict(x)
+    return SearchParams(int(d["target_mode"]), float(d["target_value"]), int(d.get("passes", 10)),
+                        float(d.get("tolerance", 1.0)), float(d.get("qmin", 0.0)), float(d.get("qmax", 100.0)))
+
+
 def riskiness_verdict(sums, w, h):
     """sjpeg_hip_riskiness_verdict: (SjpegYUVMode, risk) of one frame's three riskiness sums (SjpegRiskiness'
     arithmetic, host only)."""
@@ -1149,13 +1250,30 @@ def _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes):
 
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
-                  dmax_luma=12, dmax_chroma=1):
+                  dmax_luma=12, dmax_chroma=1, target_size=None, target_psnr=None, passes=10, tolerance=1.0, qmin=0.0,
+                  qmax=100.0):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
     quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
     alone.  Methods 1..6 (4: the reference's defaults) with min_quant, q_bias and the qdelta limits: what
-    encode_device_method makes of it alone."""
+    encode_device_method makes of it alone.
+
+    target_size (bytes) or target_psnr (dB), one value or one per image, at most one of the two: the reference's
+    multi-pass search (sjpeg::Encode with EncoderParam.target_mode / target_value / passes / tolerance / qmin / qmax)
+    per picture, the quality its starting point -- Engine.encode_ragged_search.  passes defaults to 10, as the
+    reference's command-line tool uses when a target is given; EncoderParam's own default of 1 means no search.  Not
+    with YUV_AUTO / YUV_SHARP or the trellis methods 7 and 8.  With neither target, nothing changes."""
     import torch
+    if target_size is not None and target_psnr is not None:
+        raise SjpegError("encode_images: give target_size or target_psnr, not both")
+    target = target_size if target_size is not None else target_psnr
+    if target is not None:
+        if int(method) in (7, 8):
+            raise SjpegError("encode_images: a target size or PSNR is searched with methods 0..6, not the trellis "
+                             "methods 7 and 8")
+        if int(yuv_mode) in (YUV_AUTO, YUV_SHARP):
+            raise SjpegError("encode_images: a target size or PSNR takes YUV_420, YUV_444 or YUV_400, not YUV_AUTO "
+                             "or YUV_SHARP")
     method = int(method)
     if method in (7, 8):
         raise SjpegError("encode_images: trellis methods 7 and 8 go through the host API (SjpegEncode / sjpeg::Encode)")
@@ -1191,6 +1309,18 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
     dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
+    if target is not None:
+        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
+        if len(ts) != n:
+            raise SjpegError("encode_images: one target per image")
+        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
+        search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+        with torch.cuda.device(dev):
+            out, sizes, offs, _, _ = eng.encode_ragged_search(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs),
+                                                              search, method, min_quant, q_bias, dmax_luma,
+                                                              dmax_chroma)
+            eng.wait()                           # (pipelined mode: the output is complete after this)
+            return _fetch_ragged(out, sizes, offs)
     if yuv_mode in (YUV_AUTO, YUV_SHARP):
         with torch.cuda.device(dev):
             out, sizes, offs, _ = eng.encode_ragged_auto(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,

@@ -274,11 +274,7 @@ struct DeviceContext {
       const char* v = getenv("SJPEG_HIP_HOST_FIRST_CAPACITY");
       return v != nullptr && strcmp(v, "bound") == 0;
     }();
-    if (worst) return bound;
-    const size_t px = static_cast<size_t>(W) * static_cast<size_t>(H);
-    const size_t samples = mode == SJPEG_HIP_YUV444 ? 3 * px : mode == SJPEG_HIP_YUV400 ? px : px + px / 2;
-    const size_t cap = header + 65536 + samples / 2;
-    return cap < bound ? cap : bound;
+    return worst ? bound : sjpeg_host::FirstCapacity(W, H, mode, header, bound);
   }
   // Gives the device memory this thread's context caches (pixels, stream, planes, engine scratch)
   // back; the next encode allocates what it needs again.
@@ -666,28 +662,9 @@ bool Encoder::RunImpl() {
           memcpy(pass_specs, popt, sizeof(pass_specs));
         }
         // HeaderSize() with the reference's own accounting (src/dichotomy.cc:210-241)
-        size_t size = 20 + meta_.app_markers.size();
-        if (!meta_.exif.empty()) size += 8 + meta_.exif.size();
-        if (!meta_.iccp.empty()) {
-          const size_t kMax = 0xffff - 12 - 4;
-          size += ((meta_.iccp.size() - 1) / kMax + 1) * (12 + 4 + 2) + meta_.iccp.size();
-        }
-        if (!meta_.xmp.empty()) size += 2 + 2 + 29 + meta_.xmp.size();
-        size += ntables * 65 + 2 + 2;
-        size += 8 + 3 * nb_comps + 2;
-        size += 6 + 2 * nb_comps + 2;
-        size += 2;
-        for (int t = 0; t < ntables; ++t) size += (2 + 3 + 16 + pdc[t]->nsyms) + (2 + 3 + 16 + pac[t]->nsyms);
-        size *= 8;
+        size_t size = sjpeg_host::SearchHeaderBits(nb_comps, ntables, pdc, pac, &meta_);
         if (optimize) {                              // EntropySize(), src/entropy.cc:230-245
-          for (int t = 0; t < ntables; ++t) {
-            for (int len = 0; len < 12; ++len) {
-              if (freq[t][256 + len]) size += static_cast<size_t>(freq[t][256 + len]) * ((tables.dc_codes[t][len] & 0xff) + len);
-            }
-            for (int sym = 0; sym < 256; ++sym) {
-              if (freq[t][sym]) size += static_cast<size_t>(freq[t][sym]) * ((tables.ac_codes[t][sym] & 0xff) + (sym & 0x0f));
-            }
-          }
+          size += sjpeg_host::EntropyBits(freq, ntables, &tables);
         } else {
           // BitCounter (src/bit_writer.h:292-365): coded bits + 8 per 0xFF among COMPLETED bytes.
           // One real coding pass gives both: entropy bits, and the escapes through the size.
@@ -723,11 +700,7 @@ bool Encoder::RunImpl() {
           return FailHip("sjpeg_hip_scan_quant_error");
         }
         if (!ctx.ToHost(&err, ctx.d_stats, sizeof(err))) return Fail("error pass failed");
-        sjpeg_host::FrameLayout L;
-        sjpeg_host::LayoutFor(mode, &L);
-        const uint64_t nb_mbs = static_cast<uint64_t>((W_ + L.block_w - 1) / L.block_w) * ((H_ + L.block_h - 1) / L.block_h);
-        const uint64_t n = 64ull * nb_mbs * L.mcu_blocks;
-        result = (err > 0 && n > 0) ? 4.3429448f * log(n / (err / 255. / 255.)) : 99.f;
+        result = sjpeg_host::SearchPSNR(err, W_, H_, mode);
       }
       last_is_best = (p == 0 || fabs(result - hook->target) < best);
       if (last_is_best) {

@@ -340,6 +340,54 @@ bool AppendHeaders(int W, int H, int yuv_mode, const uint8_t quant[2][64],
   return true;
 }
 
+size_t SearchHeaderBits(int nb_comps, int ntables, const HuffSpec* const dc[2], const HuffSpec* const ac[2],
+                        const Metadata* meta) {
+  size_t size = 20;
+  if (meta != nullptr) {
+    size += meta->app_markers.size();
+    if (!meta->exif.empty()) size += 8 + meta->exif.size();
+    if (!meta->iccp.empty()) {
+      const size_t kMax = 0xffff - 12 - 4;
+      size += ((meta->iccp.size() - 1) / kMax + 1) * (12 + 4 + 2) + meta->iccp.size();
+    }
+    if (!meta->xmp.empty()) size += 2 + 2 + 29 + meta->xmp.size();
+  }
+  size += ntables * 65 + 2 + 2;
+  size += 8 + 3 * nb_comps + 2;
+  size += 6 + 2 * nb_comps + 2;
+  size += 2;
+  for (int t = 0; t < ntables; ++t) size += (2 + 3 + 16 + dc[t]->nsyms) + (2 + 3 + 16 + ac[t]->nsyms);
+  return size * 8;
+}
+
+uint64_t EntropyBits(const uint32_t freq[2][272], int ntables, const sjpeg_hip_scan_tables* tables) {
+  uint64_t size = 0;
+  for (int t = 0; t < ntables; ++t) {
+    for (int len = 0; len < 12; ++len) {
+      if (freq[t][256 + len]) size += static_cast<uint64_t>(freq[t][256 + len]) * ((tables->dc_codes[t][len] & 0xff) + len);
+    }
+    for (int sym = 0; sym < 256; ++sym) {
+      if (freq[t][sym]) size += static_cast<uint64_t>(freq[t][sym]) * ((tables->ac_codes[t][sym] & 0xff) + (sym & 0x0f));
+    }
+  }
+  return size;
+}
+
+size_t FirstCapacity(int W, int H, int yuv_mode, size_t header, size_t bound) {
+  const size_t px = static_cast<size_t>(W) * static_cast<size_t>(H);
+  const size_t samples = yuv_mode == SJPEG_HIP_YUV444 ? 3 * px : yuv_mode == SJPEG_HIP_YUV400 ? px : px + px / 2;
+  const size_t cap = header + 65536 + samples / 2;
+  return cap < bound ? cap : bound;
+}
+
+float SearchPSNR(uint64_t err, int W, int H, int yuv_mode) {
+  FrameLayout L;
+  LayoutFor(yuv_mode, &L);
+  const uint64_t nb_mbs = static_cast<uint64_t>((W + L.block_w - 1) / L.block_w) * ((H + L.block_h - 1) / L.block_h);
+  const uint64_t n = 64ull * nb_mbs * L.mcu_blocks;
+  return (err > 0 && n > 0) ? 4.3429448f * log(n / (err / 255. / 255.)) : 99.f;
+}
+
 }  // namespace sjpeg_host
 
 // ------------------------------------------------------------------------------------------

@@ -80,6 +80,20 @@ void AdaptQuantMatrices(const uint32_t hist[2][64][128], int nb_comps, uint8_t q
 // reference: BuildOptimalTable, src/entropy.cc:254-430.  freq[size] -> DHT spec.
 void BuildOptimalSpec(const uint32_t* freq, int size, HuffSpec* out);
 
+// ---- the measurements of the multi-pass search (reference Encoder::LoopScan, src/dichotomy.cc:113-323), shared by
+// the host API and the ragged batch search ----
+// HeaderSize() (src/dichotomy.cc:210-241) in bits: the headers with these codes' symbol counts and meta (or NULL)
+size_t SearchHeaderBits(int nb_comps, int ntables, const HuffSpec* const dc[2], const HuffSpec* const ac[2],
+                        const Metadata* meta);
+// EntropySize() (src/entropy.cc:230-245): the bits of the symbols counted in freq[t] ([2][272]: 256 AC, then the DC
+// sizes) coded with the tables' codes
+uint64_t EntropyBits(const uint32_t freq[2][272], int ntables, const sjpeg_hip_scan_tables* tables);
+// The output capacity of a first coding attempt: 65536 bytes plus half a byte per sample, never above bound (the
+// worst case).  A frame that does not fit is coded again against bound.
+size_t FirstCapacity(int W, int H, int yuv_mode, size_t header, size_t bound);
+// GetPSNR() as ComputePSNR (src/dichotomy.cc:295-323): err over 64 samples per block of the picture's MCUs
+float SearchPSNR(uint64_t err, int W, int H, int yuv_mode);
+
 }  // namespace sjpeg_host
 
 #endif  // SJPEG_AMD_JPEG_HOST_H_

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "sjpeg_hip.h"
 
@@ -50,5 +51,28 @@ size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames)
 int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err);
+
+// ---- the search over a ragged batch (ragged_search.cc) and what it takes from the engine (scan_engine.hip)
+int set_error(int code, const std::string& msg);          // sjpeg_hip_last_error() of the calling thread
+size_t engine_scratch_limit(const sjpeg_hip_engine* e);   // SJPEG_HIP_SCRATCH_LIMIT_BYTES
+int engine_device(const sjpeg_hip_engine* e);
+// n sizes of engine-owned device memory (the search's sub-calls leave their sizes there, queued on the call's stream)
+int engine_search_sizes(sjpeg_hip_engine* e, size_t n, uint64_t** d_sizes);
+// the checks of a ragged encode's format, yuv_mode and frames (output ranges included); the message names the frame
+int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames);
+// the counted bits of frames[0, nframes) with the first plan, no host wait: ~0 for a frame that overflowed it (checked
+// as sjpeg_hip_scan_counted_bits_ragged_src)
+int counted_bits_first(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
+                       const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint64_t* d_bits, hipStream_t st);
+// ... and frames[which[k]] counted again with their worst-case plan into d_bits[which[k]]
+int counted_bits_recount(sjpeg_hip_engine* e, int format, int yuv_mode, const sjpeg_hip_ragged_frame* frames,
+                         const sjpeg_hip_scan_tables* tables, int tables_per_frame, const std::vector<int>& which,
+                         uint64_t* d_bits, hipStream_t st);
+// AnalyseHisto's device half (adapt_sums_kernel, adapt_decide_kernel) over n consecutive frames: hist [n][2][64][128],
+// each from its own starting matrices d_quant_in[n][128]; the adapted ones into d_quant_out[n][128].  d_sums / d_totlast:
+// n frames' worth of scratch.
+int adapt_ragged(const uint32_t* d_hist, const uint8_t* d_quant_in, int n, const uint8_t* min_quant, int ntab,
+                 int qdelta_max_luma, int qdelta_max_chroma, int64_t* d_sums, int32_t* d_totlast, uint8_t* d_quant_out,
+                 hipStream_t st);
 
 }  // namespace sjpeg_internal

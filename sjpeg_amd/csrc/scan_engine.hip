@@ -45,6 +45,7 @@
 #include <functional>
 
 #include "sjpeg_hip.h"
+#include "jpeg_host.h"
 #include "ragged_aux.h"
 
 namespace {
@@ -228,6 +229,9 @@ struct sjpeg_hip_engine {
   int risk_generation = -1;
   DevBuf<uint4> auto_buf;
   DevBuf<uint4> sharp_arena;
+  // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
+  // order -- the engine's, as everything a call leaves queued on its stream
+  DevBuf<uint64_t> search_sizes;
   // side_done is recorded LAZILY, by whoever is about to wait on it (side_mark): an event record is a packet in the
   // queue and about 5 us of host time, and a loop of pipelined calls needs none -- one frame per call was bound by the
   // HOST at five event calls per call (36-46 us against 35 of device time, `tools/one_frame_piped.py`)
@@ -668,7 +672,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->tables.release(); e->header.release(); e->seg_words.release(); e->seg_nbits.release(); e->pool.release(); e->pool_ctr.release(); e->seg_xbase.release(); e->replay.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
-  e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release();
+  e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -693,7 +697,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->replay.release();
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
-  e->auto_buf.release(); e->sharp_arena.release();
+  e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -798,7 +802,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
          b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) +
-         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena);
+         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -937,7 +941,7 @@ int sjpeg_hip_scan_quant_error_src(sjpeg_hip_engine* e, const sjpeg_hip_source* 
   if ((rc = e->partial.ensure(static_cast<size_t>(nframes) * g.nseg * 2))) return rc;
   a.partial = e->partial.p;
   if ((rc = launch_scan<kKindError>(yuv_mode, cls, dim3(g.nseg, nframes), st, a))) return rc;
-  hipLaunchKernelGGL(reduce_error, dim3(nframes), dim3(kThreads), 0, st,
+  hipLaunchKernelGGL(reduce_error<>, dim3(nframes), dim3(kThreads), 0, st,
                      reinterpret_cast<const unsigned long long*>(e->partial.p), g.nseg,
                      reinterpret_cast<unsigned long long*>(d_err));
   HIP_TRY(hipGetLastError());
@@ -1398,6 +1402,12 @@ void ragged_geometry(const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, int np
   d->has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
 }
 
+int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+                  const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
+                  const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
+                  const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
+                  hipStream_t st, unsigned long long* d_bits);
+
 }  // namespace
 
 int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
@@ -1434,9 +1444,28 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
     }
     header_size = header_offsets[nframes];
   }
-  // per frame: checks, geometry, scratch plan
+  // per frame: checks, geometry
   std::vector<FrameGeo> geo;
   if (int rcg = ragged_frames(kWhoEncode, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rcg;
+  try {
+    return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, headers, header_offsets,
+                         header_size, append_eoi, d_out, d_sizes, static_cast<hipStream_t>(stream), nullptr);
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+namespace {
+
+// The ragged encode of checked frames (ragged_frames, ragged_format): K1 kKindEncodeRagged, K2 .. K5.  d_bits != NULL:
+// a count without output (sjpeg_hip_scan_counted_bits_ragged_src) -- K1 .. K3, then counted_bits_ragged instead of
+// K4 and K5, no header, nothing written to d_out or d_sizes; the frames' out_capacity plans the segment scratch only.
+int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+                  const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
+                  const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
+                  const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
+                  hipStream_t st, unsigned long long* d_bits) {
+  const int ntab = tables_per_frame ? nframes : 1;
   std::vector<SegPlan> plan(nframes);
   std::vector<uint32_t> max_chunks(nframes);
   for (int f = 0; f < nframes; ++f) {
@@ -1532,7 +1561,6 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   }
 
   // scratch for the largest launch
-  hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(e->device));
   if (int rc0 = order_on_stream(e, st)) return rc0;
   if (e->side_pending) {                             // (pipelined mode: the call runs ordered, behind the engine's stitch)
@@ -1587,7 +1615,7 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
     s.hdr_off = header_offsets != nullptr ? reinterpret_cast<const uint32_t*>(db + off_hoff) + l.f0 : nullptr;
     s.append_eoi = append_eoi;
     s.out = static_cast<uint8_t*>(d_out);
-    s.sizes = reinterpret_cast<unsigned long long*>(d_sizes) + l.f0;
+    s.sizes = d_sizes != nullptr ? reinterpret_cast<unsigned long long*>(d_sizes) + l.f0 : nullptr;
     s.subs = 1; s.wide_subs = 0;
     s.frame_flags = e->frame_flags.p;
     s.rframes = a.rframes; s.rmap_place = dmaps + l.place_map; s.rmap_stuff = dmaps + l.stuff_map;
@@ -1595,6 +1623,11 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((place_segments<0, true>), dim3(l.place_wgs), dim3(kThreads), 0, st, s);
     HIP_TRY(hipGetLastError());
+    if (d_bits != nullptr) {
+      hipLaunchKernelGGL(counted_bits_ragged, dim3(l.nf), dim3(kThreads), 0, st, s, d_bits + l.f0);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
     hipLaunchKernelGGL(scan_chunk_offsets<true>, dim3(l.nf), dim3(kThreads), 0, st, s);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((stuff_chunks<0, true>), dim3(l.stuff_wgs), dim3(kThreads), 0, st, s);
@@ -1607,18 +1640,21 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   return 0;
 }
 
-namespace {
+enum RaggedPass { kPassHisto, kPassStats, kPassError };
 
-// The two analysis passes over a ragged batch: the histogram (kKindHistoRagged, persistent groups) or the symbol
-// statistics (kKindStatsRagged, a workgroup per segment) of frames [0, nframes), then their ragged reduce --
-// d_out[f] = [2][64][128] or [2][272] words, what the uniform pass makes of frame f alone.  The frames have been checked
-// (ragged_frames); `a` holds the format's fields (ragged_format).  The partials of a launch stay inside the engine's
-// scratch limit: a larger batch goes in several launches over consecutive frames.
-int ragged_analysis(sjpeg_hip_engine* e, bool histogram, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+// The analysis passes over a ragged batch: the histogram (kKindHistoRagged, persistent groups), the symbol statistics
+// (kKindStatsRagged, a workgroup per segment) or the quantization error (kKindErrorRagged, a workgroup per segment) of
+// frames [0, nframes), then their ragged reduce -- d_out[f] = [2][64][128] or [2][272] words, or one 64-bit total: what
+// the uniform pass makes of frame f alone.  The frames have been checked (ragged_frames); `a` holds the format's fields
+// (ragged_format).  The partials of a launch stay inside the engine's scratch limit: a larger batch goes in several
+// launches over consecutive frames.
+int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
                     const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                     const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st) {
-  const size_t part_words = histogram ? kHistoPartialWords : kStatsWords;     // a partial: one group's / one segment's
-  const int words = histogram ? 2 * 64 * 128 : kStatsWords;                  // a frame's result
+  const bool histogram = pass == kPassHisto, error = pass == kPassError;
+  // a partial: one group's / one segment's; a frame's result (words)
+  const size_t part_words = histogram ? kHistoPartialWords : error ? 2 : kStatsWords;
+  const int words = histogram ? 2 * 64 * 128 : error ? 2 : kStatsWords;
   // The histogram's groups.  A frame's group count is its own: as many as the uniform launch's 3 x CU slots give it in
   // whole trips over the batch's segments -- at least ceil(nseg / 256) (16-bit counters), at most one per segment.
   const long long slots = e->histo_slots > 0 ? e->histo_slots : 3ll * e->cu_count;
@@ -1697,8 +1733,16 @@ int ragged_analysis(sjpeg_hip_engine* e, bool histogram, int yuv_mode, int cls, 
     a.rframes = reinterpret_cast<const RaggedFrame*>(db) + l.f0;
     a.rmap = reinterpret_cast<const uint32_t*>(db + off_map) + l.map;
     if (histogram) rc = launch_scan<kKindHistoRagged>(yuv_mode, cls, dim3(l.units), st, a);
+    else if (error) rc = launch_scan<kKindErrorRagged>(yuv_mode, cls, dim3(l.units), st, a);
     else rc = launch_scan<kKindStatsRagged>(yuv_mode, cls, dim3(l.units), st, a);
     if (rc) return rc;
+    if (error) {                                     // one workgroup per frame sums its segments' partials
+      hipLaunchKernelGGL((reduce_error<true, const RaggedFrame*>), dim3(l.nf), dim3(kThreads), 0, st,
+                         reinterpret_cast<const unsigned long long*>(e->partial.p), 0,
+                         reinterpret_cast<unsigned long long*>(d_out) + l.f0, a.rframes);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
     // the reduce: slices of the partials as the uniform pass takes them (scan_statistics), for the launch's largest frame
     uint32_t* const out = d_out + static_cast<size_t>(l.f0) * words;
     const int xblocks = histogram ? 32 : (words + kThreads - 1) / kThreads;
@@ -1740,7 +1784,7 @@ int sjpeg_hip_scan_histogram_ragged_src(sjpeg_hip_engine* e, int format, int yuv
   std::vector<FrameGeo> geo;
   if (int rc = ragged_analysis_args("sjpeg_hip_scan_histogram_ragged_src", e, format, yuv_mode, nframes, frames, d_hist, &a, &cls, &nplanes, &geo)) return rc;
   try {
-    return ragged_analysis(e, true, yuv_mode, cls, a, nplanes, nframes, frames, geo, nullptr, 0, d_hist, static_cast<hipStream_t>(stream));
+    return ragged_analysis(e, kPassHisto, yuv_mode, cls, a, nplanes, nframes, frames, geo, nullptr, 0, d_hist, static_cast<hipStream_t>(stream));
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
@@ -1763,11 +1807,196 @@ int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* e, int format, int 
     }
   }
   try {
-    return ragged_analysis(e, false, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, d_freq, static_cast<hipStream_t>(stream));
+    return ragged_analysis(e, kPassStats, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, d_freq, static_cast<hipStream_t>(stream));
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
 }
+
+namespace {
+
+// the tables of a ragged analysis or count: present, and none with a flag ragged batches do not take
+int ragged_tables_ok(const std::string& who, const sjpeg_hip_scan_tables* tables, int ntab) {
+  if (tables == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": tables == NULL");
+  constexpr uint32_t kNotRagged = SJPEG_HIP_QUANT_TRELLIS | SJPEG_HIP_QUANT_KEEP | SJPEG_HIP_QUANT_REPLAY | SJPEG_HIP_RESTART_MARKERS;
+  for (int t = 0; t < ntab; ++t) {
+    if (tables[t].flags & kNotRagged) {
+      return fail(SJPEG_HIP_EINVAL, who + ": tables[" + std::to_string(t) +
+                                        "]: trellis, keep / replay and restart-marker flags are not taken by ragged batches");
+    }
+  }
+  return 0;
+}
+
+// The segment scratch a count plans for a frame: the host API's first capacity for its size pass, or the frame's worst
+// case (sjpeg_hip_frame_bound)
+size_t count_capacity(int W, int H, int yuv_mode, bool bound) {
+  const size_t worst = sjpeg_hip_frame_bound(W, H, yuv_mode, 0);
+  return bound ? worst : sjpeg_host::FirstCapacity(W, H, yuv_mode, 0, worst);
+}
+
+// the counted bits of checked frames, no host wait: ~0 for a frame that did not fit the plan
+int counted_bits_launch(sjpeg_hip_engine* e, int yuv_mode, int cls, const ScanArgs& a, int nplanes, int nframes,
+                        const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
+                        const sjpeg_hip_scan_tables* tables, int tables_per_frame, bool bound, uint64_t* d_bits,
+                        hipStream_t st) {
+  std::vector<sjpeg_hip_ragged_frame> planned(frames, frames + nframes);
+  for (sjpeg_hip_ragged_frame& fr : planned) {
+    fr.out_offset = 0;
+    fr.out_capacity = count_capacity(fr.width, fr.height, yuv_mode, bound);
+  }
+  return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, planned.data(), geo, tables, tables_per_frame, nullptr, nullptr,
+                       0, 0, nullptr, nullptr, st, reinterpret_cast<unsigned long long*>(d_bits));
+}
+
+int counted_bits_args(const std::string& who, sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                      const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, int tables_per_frame,
+                      const uint64_t* d_bits, ScanArgs* a, int* cls, int* nplanes, std::vector<FrameGeo>* geo) {
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_bits, a, cls, nplanes, geo)) return rc;
+  return ragged_tables_ok(who, tables, tables_per_frame ? nframes : 1);
+}
+
+}  // namespace
+
+int sjpeg_hip_scan_quant_error_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables,
+                                          int tables_per_frame, uint64_t* d_err, void* stream) {
+  static const std::string who = "sjpeg_hip_scan_quant_error_ragged_src";
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_err, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_tables_ok(who, tables, tables_per_frame ? nframes : 1)) return rc;
+  try {
+    return ragged_analysis(e, kPassError, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame,
+                           reinterpret_cast<uint32_t*>(d_err), static_cast<hipStream_t>(stream));
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+int sjpeg_hip_scan_counted_bits_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables,
+                                           int tables_per_frame, uint64_t* d_bits, void* stream) {
+  static const std::string who = "sjpeg_hip_scan_counted_bits_ragged_src";
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &nplanes, &geo)) {
+    return rc;
+  }
+  try {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = counted_bits_launch(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st)) return rc;
+    // the frames whose segments overflowed the first plan: counted again, with their worst case, in one more launch
+    std::vector<uint64_t> got(nframes);
+    HIP_TRY(hipMemcpyAsync(got.data(), d_bits, nframes * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<int> again;
+    for (int f = 0; f < nframes; ++f) if (got[f] == ~0ull) again.push_back(f);
+    if (again.empty()) return 0;
+    if (int rc = sjpeg_internal::counted_bits_recount(e, format, yuv_mode, frames, tables, tables_per_frame, again, d_bits, st)) {
+      return rc;
+    }
+    // (a count is never silently wrong: a frame past even its worst-case plan is an error, as in the host API)
+    HIP_TRY(hipMemcpyAsync(got.data(), d_bits, nframes * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int f : again) {
+      if (got[f] == ~0ull) return fail(SJPEG_HIP_ERUNTIME, who + ": frame " + std::to_string(f) + ": the count overran its worst-case plan");
+    }
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+}  // extern "C"
+
+namespace sjpeg_internal {
+
+int counted_bits_recount(sjpeg_hip_engine* e, int format, int yuv_mode, const sjpeg_hip_ragged_frame* frames,
+                         const sjpeg_hip_scan_tables* tables, int tables_per_frame, const std::vector<int>& which,
+                         uint64_t* d_bits, hipStream_t st) {
+  static const std::string who = "sjpeg_hip_scan_counted_bits_ragged_src";
+  const int n = static_cast<int>(which.size());
+  std::vector<sjpeg_hip_ragged_frame> sub(n);
+  std::vector<sjpeg_hip_scan_tables> subt(tables_per_frame ? n : 1);
+  for (int k = 0; k < n; ++k) {
+    sub[k] = frames[which[k]];
+    if (tables_per_frame) subt[k] = tables[which[k]];
+  }
+  if (!tables_per_frame) subt[0] = tables[0];
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, n, sub.data(), d_bits, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = e->auto_buf.ensure((static_cast<size_t>(n) * 8 + 15) / 16)) return rc;
+  uint64_t* const tmp = reinterpret_cast<uint64_t*>(e->auto_buf.p);
+  if (int rc = counted_bits_launch(e, yuv_mode, cls, a, nplanes, n, sub.data(), geo, subt.data(), tables_per_frame, true, tmp, st)) return rc;
+  for (int k = 0; k < n; ++k) {
+    HIP_TRY(hipMemcpyAsync(d_bits + which[k], tmp + k, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
+int counted_bits_first(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
+                       const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint64_t* d_bits, hipStream_t st) {
+  static const std::string who = "sjpeg_hip_scan_counted_bits_ragged_src";
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &nplanes, &geo)) {
+    return rc;
+  }
+  return counted_bits_launch(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st);
+}
+
+int set_error(int code, const std::string& msg) { return fail(code, msg); }
+
+int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames) {
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
+  return ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo);
+}
+size_t engine_scratch_limit(const sjpeg_hip_engine* e) { return e->scratch_limit; }
+int engine_device(const sjpeg_hip_engine* e) { return e->device; }
+
+int engine_search_sizes(sjpeg_hip_engine* e, size_t n, uint64_t** d_sizes) {
+  if (int rc = e->search_sizes.ensure(n)) return rc;
+  *d_sizes = e->search_sizes.p;
+  return 0;
+}
+
+// adapt_sums_kernel / adapt_decide_kernel over n consecutive frames, each from its own starting matrices
+int adapt_ragged(const uint32_t* d_hist, const uint8_t* d_quant_in, int n, const uint8_t* min_quant, int ntab,
+                 int qdelta_max_luma, int qdelta_max_chroma, int64_t* d_sums, int32_t* d_totlast, uint8_t* d_quant_out,
+                 hipStream_t st) {
+  AdaptArgs s;
+  s.hist = d_hist;
+  s.sums = reinterpret_cast<long long*>(d_sums);
+  s.totlast = d_totlast;
+  memset(s.quant, 0, sizeof(s.quant));
+  if (min_quant != nullptr) memcpy(s.min_quant, min_quant, sizeof(s.min_quant)); else memset(s.min_quant, 1, sizeof(s.min_quant));
+  s.quant_f = d_quant_in;
+  hipLaunchKernelGGL(adapt_sums_kernel<true>, dim3(64, 2, n), dim3(64), 0, st, s);
+  HIP_TRY(hipGetLastError());
+  DecideArgs d;
+  d.sums = s.sums; d.totlast = s.totlast;
+  d.quant_out = d_quant_out;
+  memset(d.quant_in, 0, sizeof(d.quant_in));
+  d.last_step[0] = qdelta_max_luma + 12;
+  d.last_step[1] = qdelta_max_chroma + 12;
+  d.quant_f = d_quant_in;
+  hipLaunchKernelGGL(adapt_decide_kernel<true>, dim3(ntab, n), dim3(64), 0, st, d);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace sjpeg_internal
+
+extern "C" {
 
 // ---- one frame over several GPUs: bands of consecutive segments ----------
 
@@ -2507,7 +2736,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       if (int rc = ready(gi)) return rc;
       for (const auto& c : chunks[gi]) {
         uint32_t* const d_hist = static_cast<uint32_t*>(sc.d_hist);
-        if (int rc = ragged_analysis(e, true, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+        if (int rc = ragged_analysis(e, kPassHisto, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      nullptr, 0, d_hist, st)) return rc;
         AdaptArgs s;
@@ -2555,7 +2784,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       if (int rc = ready(gi)) return rc;
       for (const auto& c : chunks[gi]) {
         uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
-        if (int rc = ragged_analysis(e, false, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+        if (int rc = ragged_analysis(e, kPassStats, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      &tables[gbase[gi] + c.first], 1, d_freq, st)) return rc;
         if (int rc = sc.ReadBack(st, h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;

@@ -81,12 +81,19 @@ __global__ __launch_bounds__(kThreads) void reduce_partials16(const uint4* part,
   }
 }
 
-__global__ __launch_bounds__(kThreads) void reduce_error(const unsigned long long* part, int nseg,
-                                                        unsigned long long* out) {
+// The quantization-error total of each frame: out[frame] = the sum of its segments' partials.
+// RAGGED (kKindErrorRagged): frame blockIdx.x of the launch has its own segment count and its partials start at its
+// first segment (RaggedFrame: nseg, seg_base).
+template <bool RAGGED = false, typename... R>
+__global__ __launch_bounds__(kThreads) void reduce_error(const unsigned long long* part, int nseg_in,
+                                                        unsigned long long* out, R... rf) {
+  const RaggedFrame* const rframes = ragged_arg(rf...);
   __shared__ unsigned long long red[kThreads / 64];
   const int frame = blockIdx.x;
+  const int nseg = RAGGED ? rframes[frame].nseg : nseg_in;
+  const unsigned long long* const src = part + (RAGGED ? static_cast<size_t>(rframes[frame].seg_base) : static_cast<size_t>(frame) * nseg);
   unsigned long long sum = 0;
-  for (int s = threadIdx.x; s < nseg; s += kThreads) sum += part[static_cast<size_t>(frame) * nseg + s];
+  for (int s = threadIdx.x; s < nseg; s += kThreads) sum += src[s];
   for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
   __syncthreads();

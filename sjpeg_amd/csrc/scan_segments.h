@@ -32,7 +32,8 @@ enum { kKindEncode = 0, kKindTap = 1, kKindHisto = 2, kKindStats = 3, kKindError
        kKindEncodeReplay = 7,     // entropy-code the coefficients a statistics pass left behind
        kKindStatsCoef = 8,        // statistics from the DCT coefficients a histogram pass left behind
        kKindEncodeRagged = 9,     // the encode kind over frames of different sizes (flat grid, per-frame descriptors)
-       kKindHistoRagged = 10, kKindStatsRagged = 11 };   // the histogram and statistics kinds over such frames
+       kKindHistoRagged = 10, kKindStatsRagged = 11,      // the histogram and statistics kinds over such frames
+       kKindErrorRagged = 12 };   // ... and the quantization-error kind (one 64-bit partial per segment)
 constexpr int kHistoWords = 2 * 64 * 32;          // words of u8 counters [2][64][128] a workgroup bins one segment into (LDS)
 // The histogram kind is PERSISTENT: a workgroup bins the segments seg, seg + gridDim.x, ... of its frame and leaves ONE
 // partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).  (The ragged
@@ -86,14 +87,15 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
   // segment come from the launch's workgroup -> frame map, the frame's geometry and scratch bases from its descriptor
   // (ragged_scan_view; the histogram's persistent groups: ragged_histo_view)
   constexpr bool HISTO_RAGGED = (KINDX == kKindHistoRagged);
-  constexpr bool RAGGED = (KINDX == kKindEncodeRagged || HISTO_RAGGED || KINDX == kKindStatsRagged);
+  constexpr bool RAGGED = (KINDX == kKindEncodeRagged || HISTO_RAGGED || KINDX == kKindStatsRagged || KINDX == kKindErrorRagged);
   constexpr bool TRELLIS = (KINDX == kKindEncodeTrellis || KINDX == kKindStatsTrellis);
   constexpr bool REPLAY = (KINDX == kKindEncodeReplay);
   // the block's unquantized coefficients come from the histogram pass of the same call (the adaptive methods run
   // one before they know the quantizer): no second colour conversion / DCT
   constexpr bool COEF = (KINDX == kKindStatsCoef);
   constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || KINDX == kKindEncodeRagged) ? kKindEncode
-                       : (KINDX == kKindStatsTrellis || COEF || KINDX == kKindStatsRagged) ? kKindStats : HISTO_RAGGED ? kKindHisto : KINDX;
+                       : (KINDX == kKindStatsTrellis || COEF || KINDX == kKindStatsRagged) ? kKindStats : HISTO_RAGGED ? kKindHisto
+                       : KINDX == kKindErrorRagged ? kKindError : KINDX;
   constexpr bool COMPACT = kCompactLds<MODE, KINDX, SRC>;
   // The statistics kinds (but the trellis one) count a block's symbols straight out of the thread's registers, zig-zag
   // position by position -- no entries in LDS, no parts, no sort, no walk (below, "kKindStats, direct")
@@ -126,7 +128,8 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
   int seg0 = blockIdx.x, hgroups = 0;
   // (a copy, not a reference: the other kinds read the kernel argument as before -- the same code to the instruction)
   const ScanArgs a = HISTO_RAGGED ? ragged_histo_view(a_in, &seg0, &hgroups)
-                     : RAGGED ? ragged_scan_view(a_in, &seg0, KINDX == kKindStatsRagged ? kStatsWords : 0) : a_in;
+                     : RAGGED ? ragged_scan_view(a_in, &seg0, KINDX == kKindStatsRagged ? kStatsWords : KINDX == kKindErrorRagged ? 2 : 0)
+                     : a_in;
   const int frame = RAGGED ? 0 : blockIdx.y;
   // the histogram kind's stride over its frame's segments: the launch's groups per frame, or (ragged) the frame's own
   // (read where it is used, as gridDim.x was: the uniform kinds keep their code)

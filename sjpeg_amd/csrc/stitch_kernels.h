@@ -805,3 +805,33 @@ __global__ __launch_bounds__(kThreads) void patch_restart_markers(const StitchAr
     dst[1] = static_cast<uint8_t>(0xd0 + ((s + a.seg_first) & 7));
   }
 }
+
+// After K1..K3 of a ragged launch without output (sjpeg_hip_scan_counted_bits_ragged_src): what the reference's
+// BitCounter reports for frame blockIdx.x (src/bit_writer.h:292-365) -- the coded bits plus 8 for every 0xFF among the
+// COMPLETED bytes.  K3 has counted the 0xFF bytes of the frame's chunks over all U bytes, the 1-padded last one
+// included: that one is taken off again when the frame ends inside a byte.  A frame whose segments did not fit the
+// plan (pool overrun, or a stream longer than its ubuf) gets ~0: the caller counts it again with a larger plan.
+__global__ __launch_bounds__(kThreads) void counted_bits_ragged(const StitchArgs a_in, unsigned long long* bits) {
+  __shared__ unsigned long long red[kThreads / 64];
+  const StitchArgs a = ragged_stitch_view(a_in, blockIdx.x);
+  const unsigned long long T = a.seg_off[a.nseg];
+  const unsigned long long U = (T + 7) >> 3;
+  const bool fits = ((U + 3) >> 2) + 1 <= a.ubuf_words && !frame_overran(a, 0);
+  unsigned long long nch = (U + kChunkBytes - 1) / kChunkBytes;
+  if (nch > a.max_chunks) nch = a.max_chunks;
+  unsigned long long ff = 0;
+  if (fits) {
+    for (unsigned long long i = threadIdx.x; i < nch; i += kThreads) ff += a.chunk_ff[i];
+  }
+  for (int d = 32; d > 0; d >>= 1) ff += __shfl_xor(ff, d, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ff;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!fits) { bits[blockIdx.x] = ~0ull; return; }
+  ff = red[0] + red[1] + red[2] + red[3];
+  if ((T & 7) != 0) {                                // the padded last byte: not a completed one
+    const uint32_t w = a.ubuf[(U - 1) >> 2];
+    if (((w >> (24 - 8 * ((U - 1) & 3))) & 0xffu) == 0xffu) --ff;
+  }
+  bits[blockIdx.x] = T + 8 * ff;
+}
