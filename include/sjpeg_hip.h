@@ -419,7 +419,7 @@ int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* engine, int format,
  *   The host waits where sjpeg_hip_encode_batch_src() does -- for the adapted matrices (methods 3..6), for the symbol
  *   counts (1, 2, 4, 5, 6) --; the encode is asynchronous on `stream`.  In pipelined mode the call runs ordered.
  *   SJPEG_HIP_EINVAL: every check of sjpeg_hip_encode_ragged_src(), a NULL quant, a method outside 0..6 (the trellis
- *   methods go through the host API) and qdelta_max outside -12..12. */
+ *   methods go through sjpeg_hip_encode_ragged_trellis_src() or the host API) and qdelta_max outside -12..12. */
 int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
                                       const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
                                       const uint8_t (*quant)[2][64], int quant_per_frame,
@@ -468,6 +468,27 @@ int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* engine, int format, int y
                                      int qdelta_max_luma, int qdelta_max_chroma,
                                      void* d_out, uint64_t* d_sizes, int* modes /*[nframes], host, or NULL*/,
                                      void* stream);
+
+/* ---- ragged batches with trellis quantization: the reference's methods 7 (= 4 + trellis) and 8 (= 6 + trellis) ----
+ * sjpeg_hip_encode_ragged_trellis_src: the arguments, output contract and host waits of
+ *   sjpeg_hip_encode_ragged_auto_src(); frame f's bytes are what SjpegEncode(picture, q, method, yuv_mode) makes of it
+ *   alone.  yuv_mode 1 / 3 / 4 with any source layout; 0 (SJPEG_YUV_AUTO) and 2 (SJPEG_YUV_SHARP) with RGB, BGRA or RGBA.
+ *   The flow per picture is Encoder::Encode's (src/enc.cc:121-129, 323-372): histogram and adapted matrices, then ONE
+ *   trellis quantization (src/quantize.cc:325-457) in the statistics pass, its rate priced with the standard AC code
+ *   lengths, then the optimised codes and an encode pass that REPLAYS the quantized blocks the statistics pass kept --
+ *   no pixel read, no second trellis.  The kept blocks are engine scratch, 36 864 bytes a segment
+ *   (sjpeg_hip_segment_count()), laid out by the frames' prefix sums; together with the sharp planes they count against
+ *   SJPEG_HIP_SCRATCH_LIMIT_BYTES: past it the call goes in parts of consecutive frames, each a complete flow with its
+ *   own waits.  sjpeg_hip_engine_trim() gives them back.  Asynchronous encode on `stream`, ordered in pipelined mode.
+ *   SJPEG_HIP_EINVAL (the frame named): every check of sjpeg_hip_encode_ragged_auto_src(), and a method other than 7
+ *   or 8 (methods 0..6 are that call's). */
+int sjpeg_hip_encode_ragged_trellis_src(sjpeg_hip_engine* engine, int format, int yuv_mode, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                        const uint8_t (*quant)[2][64], int quant_per_frame,
+                                        const uint8_t* min_quant /*[2][64] or NULL*/, int q_bias, int method /*7 or 8*/,
+                                        int qdelta_max_luma, int qdelta_max_chroma,
+                                        void* d_out, uint64_t* d_sizes, int* modes /*[nframes], host, or NULL*/,
+                                        void* stream);
 
 /* ---- ragged batches searched to a per-picture target size or PSNR ----
  * The two measurements of the reference's multi-pass search (Encoder::LoopScan, src/dichotomy.cc:113-205) over a ragged

@@ -281,6 +281,8 @@ def lib() -> C.CDLL:
                                                      C.POINTER(SearchParams), C.c_int, C.POINTER(C.c_float),
                                                      C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
     L.sjpeg_hip_encode_ragged_search_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_trellis_src.argtypes = list(L.sjpeg_hip_encode_ragged_auto_src.argtypes)
+    L.sjpeg_hip_encode_ragged_trellis_src.restype = C.c_int
     _lib = L
     return L
 
@@ -316,6 +318,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_riskiness_ragged_src", "sjpeg_hip_riskiness_verdict", "sjpeg_hip_sharp_ragged_workspace",
     "sjpeg_hip_sharp_yuv_ragged", "sjpeg_hip_encode_ragged_auto_src",
     "sjpeg_hip_scan_quant_error_ragged_src", "sjpeg_hip_scan_counted_bits_ragged_src", "sjpeg_hip_encode_ragged_search_src",
+    "sjpeg_hip_encode_ragged_trellis_src",
 ]
 
 
@@ -1164,12 +1167,29 @@ class Engine:
         are what SjpegEncode(picture, q, method, yuv_mode) makes of it alone.  capacities default:
         frame_bound(w, h, YUV_444, 2048).  Returns (out, sizes, offsets, modes): modes[k] the SjpegYUVMode frame k was
         coded with (YUV_SHARP for sharp frames).  The host waits inside for the analysis; the encode is asynchronous."""
+        return self._encode_ragged_modes("encode_ragged_auto", "sjpeg_hip_encode_ragged_auto_src", fmt, planes_per_frame,
+                                         dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma,
+                                         capacities, out, offsets, sizes)
+
+    def encode_ragged_trellis(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=7, min_quant=None, q_bias=0x78,
+                              dmax_luma=12, dmax_chroma=1, capacities=None, out=None, offsets=None, sizes=None):
+        """sjpeg_hip_encode_ragged_trellis_src: the reference's trellis methods 7 (= 4 + trellis) and 8 (= 6 + trellis)
+        over a ragged batch.  Arguments and result as encode_ragged_auto: any SjpegYUVMode (YUV_AUTO and YUV_SHARP for
+        RGB / BGRA / RGBA sources), frame k's bytes what SjpegEncode(picture, q, method, yuv_mode) makes of it alone.
+        The trellis runs once per picture: the statistics pass keeps its quantized blocks in the engine's scratch
+        (36 864 bytes a segment, counted against SJPEG_HIP_SCRATCH_LIMIT_BYTES) and the encode pass replays them."""
+        return self._encode_ragged_modes("encode_ragged_trellis", "sjpeg_hip_encode_ragged_trellis_src", fmt,
+                                         planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                                         dmax_chroma, capacities, out, offsets, sizes)
+
+    def _encode_ragged_modes(self, who, symbol, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias,
+                             dmax_luma, dmax_chroma, capacities, out, offsets, sizes):
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
-            raise SjpegError("encode_ragged_auto: one entry of planes_per_frame and dims per frame, at least one frame")
+            raise SjpegError(f"{who}: one entry of planes_per_frame and dims per frame, at least one frame")
         per_frame = isinstance(quant, (list, tuple))
         if per_frame and len(quant) != n:
-            raise SjpegError("encode_ragged_auto: one starting matrix per frame")
+            raise SjpegError(f"{who}: one starting matrix per frame")
         q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
                                  else np.asarray(quant, np.uint8).reshape(1, 2, 64))
         mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
@@ -1177,11 +1197,10 @@ class Engine:
             capacities = [frame_bound(w, h, YUV_444, 2048) for (w, h) in dims]
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         modes = (C.c_int * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_auto_src(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data,
-                                                         int(per_frame), mq.ctypes.data if mq is not None else None,
-                                                         q_bias, int(method), dmax_luma, dmax_chroma, out.data_ptr(),
-                                                         sizes.data_ptr(), modes, self._stream()),
-                  "sjpeg_hip_encode_ragged_auto_src")
+        self._chk(getattr(lib(), symbol)(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data, int(per_frame),
+                                         mq.ctypes.data if mq is not None else None, q_bias, int(method), dmax_luma,
+                                         dmax_chroma, out.data_ptr(), sizes.data_ptr(), modes, self._stream()),
+                  symbol)
         return out, sizes, list(offsets), [int(m) for m in modes]
 
 
@@ -1251,7 +1270,7 @@ def _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes):
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
                   dmax_luma=12, dmax_chroma=1, target_size=None, target_psnr=None, passes=10, tolerance=1.0, qmin=0.0,
-                  qmax=100.0):
+                  qmax=100.0, use_trellis=False):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
     quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
@@ -1262,11 +1281,20 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     multi-pass search (sjpeg::Encode with EncoderParam.target_mode / target_value / passes / tolerance / qmin / qmax)
     per picture, the quality its starting point -- Engine.encode_ragged_search.  passes defaults to 10, as the
     reference's command-line tool uses when a target is given; EncoderParam's own default of 1 means no search.  Not
-    with YUV_AUTO / YUV_SHARP or the trellis methods 7 and 8.  With neither target, nothing changes."""
+    with YUV_AUTO / YUV_SHARP or the trellis methods 7 and 8.  With neither target, nothing changes.
+
+    use_trellis=True: EncoderParam::use_trellis as the reference maps it (src/api.cc:155-157) -- method 4 becomes 7,
+    method 6 becomes 8, and the pictures go through Engine.encode_ragged_trellis: frame k's bytes are what
+    SjpegEncode(picture, quality, 7 or 8, yuv_mode) makes of it alone.  With any other method the reference ignores
+    the flag, and so does this call.  Not together with a target.  (method=7 / 8 without the keyword is refused as
+    before; with it they are taken as they are.)"""
     import torch
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
     target = target_size if target_size is not None else target_psnr
+    if use_trellis and target is not None:
+        raise SjpegError("encode_images: a target size or PSNR is not searched with the trellis (use_trellis): that "
+                         "search prices every pass with the pass's own codes")
     if target is not None:
         if int(method) in (7, 8):
             raise SjpegError("encode_images: a target size or PSNR is searched with methods 0..6, not the trellis "
@@ -1275,10 +1303,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             raise SjpegError("encode_images: a target size or PSNR takes YUV_420, YUV_444 or YUV_400, not YUV_AUTO "
                              "or YUV_SHARP")
     method = int(method)
-    if method in (7, 8):
+    if method in (7, 8) and not use_trellis:
         raise SjpegError("encode_images: trellis methods 7 and 8 go through the host API (SjpegEncode / sjpeg::Encode)")
     if method < 0 or method > 8:
         raise SjpegError(f"encode_images: method {method} is not one of 0..6")
+    if use_trellis:
+        method = {4: 7, 6: 8}.get(method, method)
     yuv_mode = int(yuv_mode)
     if yuv_mode < 0 or yuv_mode > 4:
         raise SjpegError(f"encode_images: yuv_mode {yuv_mode} is not one of 0..4 (SjpegYUVMode)")
@@ -1321,6 +1351,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
                                                               dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
+    if method >= 7:
+        with torch.cuda.device(dev):
+            out, sizes, offs, _ = eng.encode_ragged_trellis(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                                            min_quant, q_bias, dmax_luma, dmax_chroma)
+            eng.wait()                           # (pipelined mode: the output is complete after this)
+            return _fetch_ragged(out, sizes, offs)
     if yuv_mode in (YUV_AUTO, YUV_SHARP):
         with torch.cuda.device(dev):
             out, sizes, offs, _ = eng.encode_ragged_auto(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
@@ -1361,10 +1397,11 @@ def _quality_quant(qs):
     return [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
 
 
-def compress_images(images, quality=75.0, engine=None):
+def compress_images(images, quality=75.0, engine=None, use_trellis=False):
     """The batch SjpegCompress(): JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each
-    what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call."""
-    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4)
+    what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call.  use_trellis=True: with
+    EncoderParam::use_trellis, i.e. what SjpegEncode(picture, quality, 7, SJPEG_YUV_AUTO) makes of it."""
+    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis)
 
 
 def riskiness_images(images, engine=None):

@@ -113,8 +113,11 @@ static_assert(sizeof(RaggedFrame) == 144, "RaggedFrame: hgroups lies in what was
 // K1's view of the frame a ragged workgroup codes: ScanArgs with the frame's own geometry and planes, every scratch
 // pointer moved to the frame's base -- the kernel then runs as frame 0 of a uniform launch.  Two dependent scalar loads
 // (map, then descriptor) per workgroup; *seg = the segment inside the frame.  partial_words: words of the per-segment
-// partial (the statistics kind: kStatsWords; 0: the partials stay where they are).
-__device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg, int partial_words = 0) {
+// partial (the statistics kind: kStatsWords; 0: the partials stay where they are).  kept: the launch keeps or replays
+// quantized blocks (kKindStatsTrellisRagged, kKindEncodeReplayRagged) -- `replay` moves to the frame's first segment too,
+// kKeptSegWords a segment.
+constexpr size_t kKeptSegWords = static_cast<size_t>(kScanThreads) * 36;      // 9 rows of 16 bytes per thread: 36 864 bytes
+__device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg, int partial_words = 0, bool kept = false) {
   const uint32_t f = in.rmap[blockIdx.x];
   const RaggedFrame& d = in.rframes[f];
   ScanArgs v = in;
@@ -129,6 +132,7 @@ __device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* se
   v.pool_ctr = in.pool_ctr + 2 * f;
   *seg = static_cast<int>(blockIdx.x - d.seg_base);
   if (partial_words != 0) v.partial = in.partial + static_cast<size_t>(d.seg_base) * partial_words;
+  if (kept) v.replay = in.replay + static_cast<size_t>(d.seg_base) * kKeptSegWords;
   return v;
 }
 

@@ -1406,7 +1406,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
-                  hipStream_t st, unsigned long long* d_bits);
+                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept = nullptr);
 
 }  // namespace
 
@@ -1460,11 +1460,13 @@ namespace {
 // The ragged encode of checked frames (ragged_frames, ragged_format): K1 kKindEncodeRagged, K2 .. K5.  d_bits != NULL:
 // a count without output (sjpeg_hip_scan_counted_bits_ragged_src) -- K1 .. K3, then counted_bits_ragged instead of
 // K4 and K5, no header, nothing written to d_out or d_sizes; the frames' out_capacity plans the segment scratch only.
+// kept != NULL: K1 is kKindEncodeReplayRagged -- it codes the blocks a trellis statistics pass over the same frames left
+// at `kept` (ragged_analysis, kPassStatsTrellis: kKeptSegWords a segment, in the order of the frames) and reads no pixel.
 int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
-                  hipStream_t st, unsigned long long* d_bits) {
+                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept) {
   const int ntab = tables_per_frame ? nframes : 1;
   std::vector<SegPlan> plan(nframes);
   std::vector<uint32_t> max_chunks(nframes);
@@ -1592,6 +1594,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
   e->ctr_clean_at[0] = e->ctr_clean_at[1] = nullptr;   // (the pool counters are this call's now; its K2s leave them at zero)
   e->last_nseg = e->last_nframes = 0;                  // (sjpeg_hip_engine_entropy_bits: not after a ragged call)
   if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
+  size_t segs_before = 0;                              // segments of the call's frames in front of the launch's (kept blocks)
   for (size_t li = 0; li < launches.size(); ++li) {
     const RaggedLaunch& l = launches[li];
     HIP_TRY(hipMemsetAsync(e->pool_ctr.p, 0, static_cast<size_t>(l.nf) * 2 * sizeof(uint32_t), st));
@@ -1603,7 +1606,14 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     a.ablate = e->ablate;
     a.rframes = reinterpret_cast<const RaggedFrame*>(db) + l.f0;
     a.rmap = dmaps + l.k1_map;
-    if ((rc = launch_scan<kKindEncodeRagged>(yuv_mode, cls, dim3(l.segs), st, a))) return rc;
+    if (kept != nullptr) {
+      a.replay = kept + segs_before * kKeptSegWords;
+      rc = launch_scan_src<kKindEncodeReplayRagged, kSrcRgb24>(yuv_mode, dim3(l.segs), st, a);   // (reads no pixel)
+      segs_before += l.segs;
+    } else {
+      rc = launch_scan<kKindEncodeRagged>(yuv_mode, cls, dim3(l.segs), st, a);
+    }
+    if (rc) return rc;
     if (e->timing && li + 1 == launches.size()) HIP_TRY(hipEventRecord(e->ev[1], st));
     StitchArgs s{};
     s.nframes = l.nf;
@@ -1640,18 +1650,22 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
   return 0;
 }
 
-enum RaggedPass { kPassHisto, kPassStats, kPassError };
+enum RaggedPass { kPassHisto, kPassStats, kPassError, kPassStatsTrellis };
 
 // The analysis passes over a ragged batch: the histogram (kKindHistoRagged, persistent groups), the symbol statistics
 // (kKindStatsRagged, a workgroup per segment) or the quantization error (kKindErrorRagged, a workgroup per segment) of
 // frames [0, nframes), then their ragged reduce -- d_out[f] = [2][64][128] or [2][272] words, or one 64-bit total: what
 // the uniform pass makes of frame f alone.  The frames have been checked (ragged_frames); `a` holds the format's fields
 // (ragged_format).  The partials of a launch stay inside the engine's scratch limit: a larger batch goes in several
-// launches over consecutive frames.
+// launches over consecutive frames.  kPassStatsTrellis: the statistics with trellis quantization (kKindStatsTrellisRagged;
+// tables with SJPEG_HIP_QUANT_TRELLIS); its quantized blocks stay behind at `kept`, kKeptSegWords a segment in the order
+// of the frames, whatever the launches -- for ragged_encode to replay.
 int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
                     const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
-                    const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st) {
-  const bool histogram = pass == kPassHisto, error = pass == kPassError;
+                    const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st,
+                    uint32_t* kept = nullptr) {
+  const bool histogram = pass == kPassHisto, error = pass == kPassError, trellis = pass == kPassStatsTrellis;
+  if (trellis && kept == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: the ragged trellis statistics keep their blocks");
   // a partial: one group's / one segment's; a frame's result (words)
   const size_t part_words = histogram ? kHistoPartialWords : error ? 2 : kStatsWords;
   const int words = histogram ? 2 * 64 * 128 : error ? 2 : kStatsWords;
@@ -1734,7 +1748,10 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
     a.rmap = reinterpret_cast<const uint32_t*>(db + off_map) + l.map;
     if (histogram) rc = launch_scan<kKindHistoRagged>(yuv_mode, cls, dim3(l.units), st, a);
     else if (error) rc = launch_scan<kKindErrorRagged>(yuv_mode, cls, dim3(l.units), st, a);
-    else rc = launch_scan<kKindStatsRagged>(yuv_mode, cls, dim3(l.units), st, a);
+    else if (trellis) {
+      a.replay = kept + l.map * kKeptSegWords;       // (a workgroup per segment: the launch's map starts at its first segment's number)
+      rc = launch_scan<kKindStatsTrellisRagged>(yuv_mode, cls, dim3(l.units), st, a);
+    } else rc = launch_scan<kKindStatsRagged>(yuv_mode, cls, dim3(l.units), st, a);
     if (rc) return rc;
     if (error) {                                     // one workgroup per frame sums its segments' partials
       hipLaunchKernelGGL((reduce_error<true, const RaggedFrame*>), dim3(l.nf), dim3(kThreads), 0, st,
@@ -2630,7 +2647,10 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
 // ---- a ragged batch with the reference's per-picture analysis (methods 0..6) ----
 // The flow of sjpeg_hip_encode_batch_src over frames of different sizes: the ragged histogram, the adaptation kernels with
 // a starting matrix per frame, one read-back and wait; the tables; the ragged statistics, one read-back and wait; the
-// Huffman codes and the headers on the host; the ragged encode.  No lanes, no parts, no coefficients kept between passes.
+// Huffman codes and the headers on the host; the ragged encode.  No lanes, no parts, no coefficients kept between passes
+// -- but for methods 7 and 8 (sjpeg_hip_encode_ragged_trellis_src), the reference's trellis: their statistics step
+// quantizes with the trellis, priced with the standard AC code lengths, and leaves its blocks in the engine's `replay`
+// buffer (group after group, frame after frame, kKeptSegWords a segment); their encode step replays them.
 // The frames come in MODE GROUPS (sjpeg_hip_encode_ragged_auto_src: RGB 4:2:0, 4:4:4, 4:0:0 and the sharp frames' planar
 // 4:2:0 -- K1 is templated on the mode, so a group is a grid of its own): every pass runs over all groups before its
 // one wait, so the host waits do not grow with the number of groups.  sjpeg_hip_encode_ragged_batch_src is one group.
@@ -2661,11 +2681,21 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
                         const uint8_t (*quant_in)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias,
                         int method, int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
                         hipStream_t st, const std::function<int()>& last_ready = {}) {
-  const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3);
+  const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3), trellis = method >= 7;
   size_t n = 0;
   std::vector<size_t> gbase;
   for (const RaggedGroup& g : groups) { gbase.push_back(n); n += g.frames.size(); }
   if (n == 0) return 0;
+  // (trellis) the first kept segment of every group, and of every frame inside its group
+  std::vector<size_t> gkept;
+  std::vector<std::vector<size_t>> fkept(groups.size());
+  size_t kept_segs = 0;
+  for (size_t gi = 0; trellis && gi < groups.size(); ++gi) {
+    gkept.push_back(kept_segs);
+    size_t at = 0;
+    for (const FrameGeo& fg : groups[gi].geo) { fkept[gi].push_back(at); at += static_cast<size_t>(fg.nseg); }
+    kept_segs += at;
+  }
   bool last_made = !last_ready;
   auto ready = [&](size_t gi) -> int {
     if (last_made || gi + 1 != groups.size()) return 0;
@@ -2684,6 +2714,14 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       memset(&tables[f], 0, sizeof(tables[f]));
       sjpeg_hip_finalize_quant(reinterpret_cast<uint8_t(*)[64]>(q), min_quant, q_bias, &tables[f]);
       sjpeg_hip_default_huffman(&tables[f]);
+      if (trellis) {
+        // the rate of the trellis is priced with the STANDARD AC code lengths (InitCodes(true), src/enc.cc:330-334),
+        // whatever codes the stream ends with
+        tables[f].flags |= SJPEG_HIP_QUANT_TRELLIS;
+        for (int t = 0; t < 2; ++t) {
+          for (int sym = 0; sym < 256; ++sym) tables[f].trellis_len[t][sym] = static_cast<uint8_t>(tables[f].ac_codes[t][sym] & 0xff);
+        }
+      }
     }
   }
   static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
@@ -2779,14 +2817,20 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       for (const auto& c : chunks.back()) most = std::max(most, c.second);
     }
     if (!sc.Ensure(&sc.d_freq, &sc.freq_cap, most * kFreq)) return fail(SJPEG_HIP_ENOMEM, "hipMalloc(batch scratch) failed");
+    if (trellis) {
+      if (int rc = e->replay.ensure(kept_segs * kKeptSegWords)) return rc;
+      e->replay_w = e->replay_h = e->replay_mode = e->replay_nframes = 0;      // (no uniform call's kept blocks any more)
+    }
     for (size_t gi = 0; gi < groups.size(); ++gi) {
       const RaggedGroup& g = groups[gi];
       if (int rc = ready(gi)) return rc;
       for (const auto& c : chunks[gi]) {
         uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
-        if (int rc = ragged_analysis(e, kPassStats, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+        if (int rc = ragged_analysis(e, trellis ? kPassStatsTrellis : kPassStats, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second),
+                                     g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
-                                     &tables[gbase[gi] + c.first], 1, d_freq, st)) return rc;
+                                     &tables[gbase[gi] + c.first], 1, d_freq, st,
+                                     trellis ? e->replay.p + (gkept[gi] + fkept[gi][c.first]) * kKeptSegWords : nullptr)) return rc;
         if (int rc = sc.ReadBack(st, h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;
       }
     }
@@ -2828,9 +2872,13 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
                                g.yuv_mode, quant.data(), optimize ? specs.data() : nullptr, &headers, &offs)) return rc;
     if (gi + 1 == groups.size()) mark("tables built");
     if (int rc = ready(gi)) return rc;
-    const int rc = sjpeg_hip_encode_ragged_src(e, g.format, g.yuv_mode, static_cast<int>(ng), g.frames.data(), &tables[gbase[gi]],
-                                               one_table ? 0 : 1, headers.data(), offs.data(), /*append_eoi=*/1, d_out,
-                                               reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st);
+    const int rc = trellis ? ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
+                                           1, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, d_out,
+                                           reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
+                                           e->replay.p + gkept[gi] * kKeptSegWords)
+                           : sjpeg_hip_encode_ragged_src(e, g.format, g.yuv_mode, static_cast<int>(ng), g.frames.data(), &tables[gbase[gi]],
+                                                         one_table ? 0 : 1, headers.data(), offs.data(), /*append_eoi=*/1, d_out,
+                                                         reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st);
     if (rc) return rc;
   }
   if (!in_order) {
@@ -3007,9 +3055,144 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
   }
 }
 
-// The flow: the ragged riskiness and ONE read-back (AUTO only), the verdicts on the host, the sharp frames converted into
-// the engine's planes arena, then the method 0..6 flow over up to four mode groups (ragged_batch_groups).  The sharp
-// planes and workspace count against the scratch limit: past it the call goes in parts of consecutive frames.
+// The flow of the ragged calls that take a SjpegYUVMode (frames, format and arguments checked): the ragged riskiness and ONE
+// read-back (AUTO only), the verdicts on the host, the sharp frames converted into the engine's planes arena, then the
+// method's flow over up to four mode groups (ragged_batch_groups; a fixed mode 1 / 3 / 4 is one group of the caller's
+// format).  The sharp planes and workspace -- and, methods 7 and 8, the kept blocks of the trellis, 36 864 bytes a segment
+// -- count against the scratch limit: past it the call goes in parts of consecutive frames, each a complete flow.
+static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
+                             const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64], int quant_per_frame,
+                             const uint8_t* min_quant, int q_bias, int method, int qdelta_max_luma, int qdelta_max_chroma,
+                             void* d_out, uint64_t* d_sizes, int* modes, void* stream) {
+  const bool trellis = method >= 7;
+  static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
+  const auto t_start = std::chrono::steady_clock::now();
+  auto mark = [&](const char* what) {
+    if (batch_debug) fprintf(stderr, "auto   %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
+  };
+  const size_t n = static_cast<size_t>(nframes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ragged_ordered(e, st)) return rc;
+  // the auto_buf of the whole call, once: riskiness descriptors and sums, then the groups' sizes and frame numbers
+  if (int rc = e->auto_buf.ensure(std::max((align16(sizeof(sjpeg_internal::RiskFrame) * n) + n * 24 + 15) / 16 + 1, (n * 12 + 15) / 16 + 1))) return rc;
+  std::vector<int> mode(n, yuv_mode == SJPEG_YUV_AUTO_ ? SJPEG_YUV_SHARP_ : yuv_mode);
+  if (yuv_mode == SJPEG_YUV_AUTO_) {
+    // 1. the riskiness of every frame (the table on this device, uploaded again when it changed), one read-back
+    const uint8_t* d_table = nullptr;
+    if (int rc = engine_risk_table(e, who, st, &d_table)) return rc;
+    uint64_t* d_sums = nullptr;
+    if (int rc = risk_ragged(e, format, nframes, frames, d_table, nullptr, st, &d_sums)) return rc;
+    std::vector<uint64_t> sums(n * 3);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, n * 24, hipMemcpyDeviceToHost, st));
+    mark("risk launched");
+    HIP_TRY(hipStreamSynchronize(st));
+    mark("sums here");
+    // 2. the verdicts, as the host API makes them
+    for (size_t f = 0; f < n; ++f) mode[f] = sjpeg_hip_riskiness_verdict(&sums[f * 3], frames[f].width, frames[f].height, nullptr);
+  }
+  if (modes != nullptr) for (size_t f = 0; f < n; ++f) modes[f] = mode[f];
+  // parts of consecutive frames whose sharp planes and workspace (and kept blocks, with the trellis) stay inside the
+  // scratch limit (one frame at least)
+  auto planes_bytes = [](const sjpeg_hip_ragged_frame& fr) {
+    const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+    return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
+  };
+  std::vector<std::pair<size_t, size_t>> parts;    // [first, end)
+  size_t arena = 0;
+  {
+    size_t f0 = 0, bytes = 0, counted = 0;         // (counted: frames of the open part that take any of it)
+    std::vector<sjpeg_hip_ragged_frame> sharp;
+    auto kept_bytes = [&](size_t f) -> size_t {
+      FrameGeo g;
+      const int m = mode[f] == SJPEG_YUV_444_ ? SJPEG_HIP_YUV444 : mode[f] == SJPEG_YUV_400_ ? SJPEG_HIP_YUV400 : SJPEG_HIP_YUV420;
+      return frame_geo(frames[f].width, frames[f].height, m, &g) ? static_cast<size_t>(g.nseg) * kKeptSegWords * sizeof(uint32_t) : 0;
+    };
+    auto close = [&](size_t end) {
+      const size_t ws = sharp.empty() ? 0 : sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
+      size_t planes = 0;
+      for (const auto& fr : sharp) planes += planes_bytes(fr);
+      arena = std::max(arena, align16(planes) + ws);
+      parts.emplace_back(f0, end);
+      sharp.clear();
+      counted = 0;
+    };
+    for (size_t f = 0; f < n; ++f) {
+      const bool is_sharp = mode[f] == SJPEG_YUV_SHARP_;
+      if (!is_sharp && !trellis) continue;
+      const size_t b = (is_sharp ? planes_bytes(frames[f]) + sjpeg_internal::sharp_ragged_workspace(1, &frames[f]) : 0) +
+                       (trellis ? kept_bytes(f) : 0);
+      if (counted > 0 && bytes + b > e->scratch_limit) { close(f); f0 = f; bytes = 0; }
+      if (is_sharp) sharp.push_back(frames[f]);
+      ++counted;
+      bytes += b;
+    }
+    close(n);
+  }
+  if (arena > 0) {
+    if (int rc = e->sharp_arena.ensure(arena / 16 + 1)) return rc;
+  }
+  for (const auto& part : parts) {
+    // 3. the sharp frames of the part go into the arena: Y, U, V tightly packed, then the workspace
+    std::vector<sjpeg_hip_ragged_frame> sharp;
+    std::vector<uint8_t*> py, pu, pv;
+    uint8_t* at = reinterpret_cast<uint8_t*>(e->sharp_arena.p);
+    for (size_t f = part.first; f < part.second; ++f) {
+      if (mode[f] != SJPEG_YUV_SHARP_) continue;
+      const sjpeg_hip_ragged_frame& fr = frames[f];
+      const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+      sharp.push_back(fr);
+      py.push_back(at); at += align16(static_cast<size_t>(fr.width) * fr.height);
+      pu.push_back(at); at += align16(cw * ch);
+      pv.push_back(at); at += align16(cw * ch);
+    }
+    // (enqueued by ragged_batch_groups in front of the first kernel that reads the sharp group, its last)
+    auto convert = [&]() -> int {
+      uint8_t* const ws = reinterpret_cast<uint8_t*>(e->sharp_arena.p) + align16(static_cast<size_t>(at - reinterpret_cast<uint8_t*>(e->sharp_arena.p)));
+      const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
+      std::string err;
+      if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), py.data(), pu.data(),
+                                                    pv.data(), ws, wsz, st, engine_upload, e, &err)) {
+        return fail(rc, who + ": " + err);
+      }
+      mark("sharp launched");
+      return 0;
+    };
+    // 4. the mode groups: 4:2:0, 4:4:4, 4:0:0 of the caller's format, then the sharp frames as planar 4:2:0
+    std::vector<RaggedGroup> groups;
+    const int kinds[4] = {SJPEG_YUV_420_, SJPEG_YUV_444_, SJPEG_YUV_400_, SJPEG_YUV_SHARP_};
+    for (int kind : kinds) {
+      RaggedGroup g;
+      g.format = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_SRC_YUV420 : format;
+      g.yuv_mode = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_YUV420 : kind;     // (SjpegYUVMode 1, 3, 4 = SJPEG_HIP_YUV*)
+      size_t k = 0;
+      for (size_t f = part.first; f < part.second; ++f) {
+        if (mode[f] != SJPEG_YUV_SHARP_) {
+          if (mode[f] == kind) { g.frames.push_back(frames[f]); g.index.push_back(static_cast<int>(f)); }
+          continue;
+        }
+        if (kind != SJPEG_YUV_SHARP_) continue;
+        sjpeg_hip_ragged_frame fr = frames[f];
+        const int64_t cw = (static_cast<int64_t>(fr.width) + 1) / 2;
+        fr.plane[0] = py[k]; fr.plane[1] = pu[k]; fr.plane[2] = pv[k];
+        fr.row_stride[0] = fr.width; fr.row_stride[1] = cw; fr.row_stride[2] = cw;
+        ++k;
+        g.frames.push_back(fr);
+        g.index.push_back(static_cast<int>(f));
+      }
+      if (g.frames.empty()) continue;
+      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
+      if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
+      groups.push_back(std::move(g));
+    }
+    if (int rc = ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
+                                     qdelta_max_chroma, d_out, d_sizes, st,
+                                     sharp.empty() ? std::function<int()>() : std::function<int()>(convert))) return rc;
+  }
+  mark("call done");
+  return 0;
+}
+
+// sjpeg_hip.h; the flow: ragged_modes_flow
 int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                      const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
                                      int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
@@ -3037,121 +3220,44 @@ int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mo
       std::vector<FrameGeo> geo;                   // (the output ranges)
       if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
     }
-    static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
-    const auto t_start = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-      if (batch_debug) fprintf(stderr, "auto   %-18s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
-    };
-    const size_t n = static_cast<size_t>(nframes);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = ragged_ordered(e, st)) return rc;
-    // the auto_buf of the whole call, once: riskiness descriptors and sums, then the groups' sizes and frame numbers
-    if (int rc = e->auto_buf.ensure(std::max((align16(sizeof(sjpeg_internal::RiskFrame) * n) + n * 24 + 15) / 16 + 1, (n * 12 + 15) / 16 + 1))) return rc;
-    std::vector<int> mode(n, SJPEG_YUV_SHARP_);
-    if (yuv_mode == SJPEG_YUV_AUTO_) {
-      // 1. the riskiness of every frame (the table on this device, uploaded again when it changed), one read-back
-      const uint8_t* d_table = nullptr;
-      if (int rc = engine_risk_table(e, who, st, &d_table)) return rc;
-      uint64_t* d_sums = nullptr;
-      if (int rc = risk_ragged(e, format, nframes, frames, d_table, nullptr, st, &d_sums)) return rc;
-      std::vector<uint64_t> sums(n * 3);
-      HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, n * 24, hipMemcpyDeviceToHost, st));
-      mark("risk launched");
-      HIP_TRY(hipStreamSynchronize(st));
-      mark("sums here");
-      // 2. the verdicts, as the host API makes them
-      for (size_t f = 0; f < n; ++f) mode[f] = sjpeg_hip_riskiness_verdict(&sums[f * 3], frames[f].width, frames[f].height, nullptr);
+    return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
+                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream);
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// Methods 7 and 8 over a ragged batch (sjpeg_hip.h): ragged_modes_flow with the trellis steps of ragged_batch_groups.
+int sjpeg_hip_encode_ragged_trellis_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                        int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                        int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                        int* modes, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_trellis_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
+  if (frames == nullptr || quant_in == nullptr || d_out == nullptr || d_sizes == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, quant, d_out or d_sizes == NULL");
+  }
+  if (method != 7 && method != 8) return fail(SJPEG_HIP_EINVAL, who + ": methods 7 and 8 (the others: sjpeg_hip_encode_ragged_auto_src)");
+  if (qdelta_max_luma < -12 || qdelta_max_luma > 12 || qdelta_max_chroma < -12 || qdelta_max_chroma > 12) {
+    return fail(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
+  }
+  try {
+    if (yuv_mode == SJPEG_YUV_AUTO_ || yuv_mode == SJPEG_YUV_SHARP_) {
+      if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
+      std::vector<FrameGeo> geo;                   // (the output ranges)
+      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
+    } else {
+      if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+      ScanArgs a;
+      int cls = 0, nplanes = 0;
+      std::vector<FrameGeo> geo;
+      if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
+      if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
     }
-    if (modes != nullptr) for (size_t f = 0; f < n; ++f) modes[f] = mode[f];
-    // parts of consecutive frames whose sharp planes and workspace stay inside the scratch limit (one frame at least)
-    auto planes_bytes = [](const sjpeg_hip_ragged_frame& fr) {
-      const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
-      return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
-    };
-    std::vector<std::pair<size_t, size_t>> parts;    // [first, end)
-    size_t arena = 0;
-    {
-      size_t f0 = 0, bytes = 0;
-      std::vector<sjpeg_hip_ragged_frame> sharp;
-      auto close = [&](size_t end) {
-        const size_t ws = sharp.empty() ? 0 : sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
-        size_t planes = 0;
-        for (const auto& fr : sharp) planes += planes_bytes(fr);
-        arena = std::max(arena, align16(planes) + ws);
-        parts.emplace_back(f0, end);
-        sharp.clear();
-      };
-      for (size_t f = 0; f < n; ++f) {
-        if (mode[f] != SJPEG_YUV_SHARP_) continue;
-        const size_t b = planes_bytes(frames[f]) + sjpeg_internal::sharp_ragged_workspace(1, &frames[f]);
-        if (!sharp.empty() && bytes + b > e->scratch_limit) { close(f); f0 = f; bytes = 0; }
-        sharp.push_back(frames[f]);
-        bytes += b;
-      }
-      close(n);
-    }
-    if (arena > 0) {
-      if (int rc = e->sharp_arena.ensure(arena / 16 + 1)) return rc;
-    }
-    for (const auto& part : parts) {
-      // 3. the sharp frames of the part go into the arena: Y, U, V tightly packed, then the workspace
-      std::vector<sjpeg_hip_ragged_frame> sharp;
-      std::vector<uint8_t*> py, pu, pv;
-      uint8_t* at = reinterpret_cast<uint8_t*>(e->sharp_arena.p);
-      for (size_t f = part.first; f < part.second; ++f) {
-        if (mode[f] != SJPEG_YUV_SHARP_) continue;
-        const sjpeg_hip_ragged_frame& fr = frames[f];
-        const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
-        sharp.push_back(fr);
-        py.push_back(at); at += align16(static_cast<size_t>(fr.width) * fr.height);
-        pu.push_back(at); at += align16(cw * ch);
-        pv.push_back(at); at += align16(cw * ch);
-      }
-      // (enqueued by ragged_batch_groups in front of the first kernel that reads the sharp group, its last)
-      auto convert = [&]() -> int {
-        uint8_t* const ws = reinterpret_cast<uint8_t*>(e->sharp_arena.p) + align16(static_cast<size_t>(at - reinterpret_cast<uint8_t*>(e->sharp_arena.p)));
-        const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
-        std::string err;
-        if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), py.data(), pu.data(),
-                                                      pv.data(), ws, wsz, st, engine_upload, e, &err)) {
-          return fail(rc, who + ": " + err);
-        }
-        mark("sharp launched");
-        return 0;
-      };
-      // 4. the mode groups: RGB 4:2:0, 4:4:4, 4:0:0, then the sharp frames as planar 4:2:0
-      std::vector<RaggedGroup> groups;
-      const int kinds[4] = {SJPEG_YUV_420_, SJPEG_YUV_444_, SJPEG_YUV_400_, SJPEG_YUV_SHARP_};
-      for (int kind : kinds) {
-        RaggedGroup g;
-        g.format = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_SRC_YUV420 : format;
-        g.yuv_mode = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_YUV420 : kind;     // (SjpegYUVMode 1, 3, 4 = SJPEG_HIP_YUV*)
-        size_t k = 0;
-        for (size_t f = part.first; f < part.second; ++f) {
-          if (mode[f] != SJPEG_YUV_SHARP_) {
-            if (mode[f] == kind) { g.frames.push_back(frames[f]); g.index.push_back(static_cast<int>(f)); }
-            continue;
-          }
-          if (kind != SJPEG_YUV_SHARP_) continue;
-          sjpeg_hip_ragged_frame fr = frames[f];
-          const int64_t cw = (static_cast<int64_t>(fr.width) + 1) / 2;
-          fr.plane[0] = py[k]; fr.plane[1] = pu[k]; fr.plane[2] = pv[k];
-          fr.row_stride[0] = fr.width; fr.row_stride[1] = cw; fr.row_stride[2] = cw;
-          ++k;
-          g.frames.push_back(fr);
-          g.index.push_back(static_cast<int>(f));
-        }
-        if (g.frames.empty()) continue;
-        if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
-        if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
-        groups.push_back(std::move(g));
-      }
-      if (int rc = ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
-                                       qdelta_max_chroma, d_out, d_sizes, st,
-                                       sharp.empty() ? std::function<int()>() : std::function<int()>(convert))) return rc;
-    }
-    mark("call done");
-    return 0;
+    return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
+                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream);
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }

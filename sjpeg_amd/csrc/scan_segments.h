@@ -33,7 +33,9 @@ enum { kKindEncode = 0, kKindTap = 1, kKindHisto = 2, kKindStats = 3, kKindError
        kKindStatsCoef = 8,        // statistics from the DCT coefficients a histogram pass left behind
        kKindEncodeRagged = 9,     // the encode kind over frames of different sizes (flat grid, per-frame descriptors)
        kKindHistoRagged = 10, kKindStatsRagged = 11,      // the histogram and statistics kinds over such frames
-       kKindErrorRagged = 12 };   // ... and the quantization-error kind (one 64-bit partial per segment)
+       kKindErrorRagged = 12,     // ... and the quantization-error kind (one 64-bit partial per segment)
+       kKindStatsTrellisRagged = 13,     // the trellis statistics kind over such frames: its blocks stay behind ...
+       kKindEncodeReplayRagged = 14 };   // ... for the replay kind over the same frames (kept blocks at the frame's seg_base)
 constexpr int kHistoWords = 2 * 64 * 32;          // words of u8 counters [2][64][128] a workgroup bins one segment into (LDS)
 // The histogram kind is PERSISTENT: a workgroup bins the segments seg, seg + gridDim.x, ... of its frame and leaves ONE
 // partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).  (The ragged
@@ -79,7 +81,7 @@ __device__ __forceinline__ void race_point(int code, int n) {
 #endif
 template <int MODE, int KINDX, int SRC>
 constexpr bool kCompactLds = (KINDX == kKindEncode || KINDX == kKindEncodeReplay || KINDX == kKindStats || KINDX == kKindStatsCoef ||
-                              KINDX == kKindEncodeRagged || KINDX == kKindStatsRagged);
+                              KINDX == kKindEncodeRagged || KINDX == kKindStatsRagged || KINDX == kKindEncodeReplayRagged);
 
 template <int MODE, int KINDX, int SRC>
 __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kKindHistoRagged) && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
@@ -87,14 +89,17 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
   // segment come from the launch's workgroup -> frame map, the frame's geometry and scratch bases from its descriptor
   // (ragged_scan_view; the histogram's persistent groups: ragged_histo_view)
   constexpr bool HISTO_RAGGED = (KINDX == kKindHistoRagged);
-  constexpr bool RAGGED = (KINDX == kKindEncodeRagged || HISTO_RAGGED || KINDX == kKindStatsRagged || KINDX == kKindErrorRagged);
-  constexpr bool TRELLIS = (KINDX == kKindEncodeTrellis || KINDX == kKindStatsTrellis);
-  constexpr bool REPLAY = (KINDX == kKindEncodeReplay);
+  // (the trellis statistics and the replay over ragged frames: the two kinds that share kept blocks -- their view moves
+  // `replay` to the frame's base as well)
+  constexpr bool KEEP_RAGGED = (KINDX == kKindStatsTrellisRagged || KINDX == kKindEncodeReplayRagged);
+  constexpr bool RAGGED = (KINDX == kKindEncodeRagged || HISTO_RAGGED || KINDX == kKindStatsRagged || KINDX == kKindErrorRagged || KEEP_RAGGED);
+  constexpr bool TRELLIS = (KINDX == kKindEncodeTrellis || KINDX == kKindStatsTrellis || KINDX == kKindStatsTrellisRagged);
+  constexpr bool REPLAY = (KINDX == kKindEncodeReplay || KINDX == kKindEncodeReplayRagged);
   // the block's unquantized coefficients come from the histogram pass of the same call (the adaptive methods run
   // one before they know the quantizer): no second colour conversion / DCT
   constexpr bool COEF = (KINDX == kKindStatsCoef);
-  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || KINDX == kKindEncodeRagged) ? kKindEncode
-                       : (KINDX == kKindStatsTrellis || COEF || KINDX == kKindStatsRagged) ? kKindStats : HISTO_RAGGED ? kKindHisto
+  constexpr int KIND = (KINDX == kKindEncodeTrellis || KINDX == kKindEncodeReplay || KINDX == kKindEncodeRagged || KINDX == kKindEncodeReplayRagged) ? kKindEncode
+                       : (KINDX == kKindStatsTrellis || COEF || KINDX == kKindStatsRagged || KINDX == kKindStatsTrellisRagged) ? kKindStats : HISTO_RAGGED ? kKindHisto
                        : KINDX == kKindErrorRagged ? kKindError : KINDX;
   constexpr bool COMPACT = kCompactLds<MODE, KINDX, SRC>;
   // The statistics kinds (but the trellis one) count a block's symbols straight out of the thread's registers, zig-zag
@@ -128,6 +133,7 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
   int seg0 = blockIdx.x, hgroups = 0;
   // (a copy, not a reference: the other kinds read the kernel argument as before -- the same code to the instruction)
   const ScanArgs a = HISTO_RAGGED ? ragged_histo_view(a_in, &seg0, &hgroups)
+                     : KEEP_RAGGED ? ragged_scan_view(a_in, &seg0, KINDX == kKindStatsTrellisRagged ? kStatsWords : 0, true)
                      : RAGGED ? ragged_scan_view(a_in, &seg0, KINDX == kKindStatsRagged ? kStatsWords : KINDX == kKindErrorRagged ? 2 : 0)
                      : a_in;
   const int frame = RAGGED ? 0 : blockIdx.y;
