@@ -546,6 +546,57 @@ int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* engine, int format, int
                                        float* q_out /*[nframes], host, or NULL*/, float* value_out /*[nframes], host, or NULL*/,
                                        void* d_out, uint64_t* d_sizes, void* stream);
 
+/* ---- ragged batches into ONE packed buffer: the frames back to back ---------------------
+ * sjpeg_hip_encode_ragged_packed_src: any of the ragged encodes above, with the frames written back to back into
+ * d_packed instead of each into a slot [out_offset, out_offset + out_capacity) sized before it is coded.  It goes where
+ * the same arguments go in the unpacked calls and refuses what those refuse, with their messages:
+ *   params->search != NULL          sjpeg_hip_encode_ragged_search_src (yuv_mode 1 / 3 / 4, methods 0..6)
+ *   method 7 or 8                   sjpeg_hip_encode_ragged_trellis_src
+ *   otherwise                       sjpeg_hip_encode_ragged_auto_src (yuv_mode 1 / 3 / 4: ..._batch_src)
+ * Frame f's bytes are exactly those of that call.  frames[f].out_offset is ignored; frames[f].out_capacity is the most
+ * frame f may take and still plans its segment scratch.  modes / q_out / value_out (host, each may be NULL): as in the
+ * unpacked calls; a flow that has no modes reports yuv_mode, one without a search -1 for q and value.
+ * Also SJPEG_HIP_EINVAL: a NULL engine, params, frames, d_packed, d_offsets or d_sizes; d_packed not a multiple of 16.
+ * Layout:
+ *   - d_sizes[f] and d_offsets[f] are indexed by the caller's frame number.  Frame f lies at d_packed + d_offsets[f],
+ *     a multiple of 16; the bytes between its end and the next multiple of 16 are zero.
+ *   - The frames lie back to back in the order the flow codes them.  That IS the caller's order (offsets ascending: the
+ *     format sjpeg_hip_gather_streams takes) whenever the call codes its frames as one group: yuv_mode 1 / 3 / 4 or
+ *     SJPEG_YUV_SHARP, and either no frame searched or every frame searched (whatever their targets: the searches run
+ *     per kind of target, the final encode over all of them).  With SJPEG_YUV_AUTO the frames lie grouped by the mode
+ *     each was given (4:2:0, 4:4:4, 4:0:0, sharp), and in a search of only some frames the ones that are not searched
+ *     (passes <= 1) come first, then the searched ones; the caller's order inside each group.  Launches over
+ *     SJPEG_HIP_SCRATCH_LIMIT_BYTES do not change this; a call cut into parts is grouped inside each part, so a
+ *     one-group call keeps the caller's order there too.
+ *   - A frame that did not fit its own out_capacity has size 0 and takes no room.  A frame whose padded end would pass
+ *     packed_capacity has size 0 and is not written, bit 63 of d_offsets[nframes] (SJPEG_HIP_PACKED_OVERFLOW) is set,
+ *     and every frame coded after it is dropped as well; the low 63 bits then hold the capacity that would have been
+ *     enough.  Without overflow d_offsets[nframes] is the number of bytes used.  Nothing is written outside
+ *     [d_packed, d_packed + packed_capacity).
+ *   - d_offsets[f] of a frame with size 0 is not a place in the buffer: a frame dropped for lack of room holds the start
+ *     it would have had, which can lie past packed_capacity, and a frame that failed its own out_capacity holds the
+ *     start of the frame coded after it.  Use d_offsets[f] only where d_sizes[f] != 0.
+ * Placement is device work on the caller's stream (a cursor in engine memory that the call zeroes and every launch,
+ * group and part of it advances): no host wait is added, and in pipelined mode the call runs ordered. */
+typedef struct sjpeg_hip_ragged_params {
+  int32_t yuv_mode;                 /* SjpegYUVMode 0..4 */
+  int32_t method;                   /* 0..8 */
+  const uint8_t (*quant)[2][64];    /* starting matrices */
+  int32_t quant_per_frame;
+  const uint8_t* min_quant;         /* [2][64] or NULL */
+  int32_t q_bias, qdelta_max_luma, qdelta_max_chroma;
+  const sjpeg_hip_search* search;   /* NULL: no search */
+  int32_t search_per_frame;
+} sjpeg_hip_ragged_params;
+
+int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                       const sjpeg_hip_ragged_params* params,
+                                       void* d_packed, size_t packed_capacity,
+                                       uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                       int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                       void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -118,6 +118,17 @@ class SearchParams(C.Structure):
                 ("tolerance", C.c_float), ("qmin", C.c_float), ("qmax", C.c_float)]
 
 
+class RaggedParams(C.Structure):
+    """struct sjpeg_hip_ragged_params (include/sjpeg_hip.h): what sjpeg_hip_encode_ragged_packed_src codes its frames
+    with -- the arguments of the unpacked ragged encodes in one structure."""
+    _fields_ = [("yuv_mode", C.c_int32), ("method", C.c_int32), ("quant", C.c_void_p), ("quant_per_frame", C.c_int32),
+                ("min_quant", C.c_void_p), ("q_bias", C.c_int32), ("qdelta_max_luma", C.c_int32),
+                ("qdelta_max_chroma", C.c_int32), ("search", C.POINTER(SearchParams)), ("search_per_frame", C.c_int32)]
+
+
+PACKED_OVERFLOW = 1 << 63        # SJPEG_HIP_PACKED_OVERFLOW: bit 63 of offsets[nframes]
+
+
 class HuffmanSpec(C.Structure):
     """struct sjpeg_hip_huffman_spec (include/sjpeg_hip.h)."""
     _fields_ = [("bits", C.c_uint8 * 16), ("syms", C.c_uint8 * 256), ("nsyms", C.c_int32)]
@@ -283,6 +294,11 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_encode_ragged_search_src.restype = C.c_int
     L.sjpeg_hip_encode_ragged_trellis_src.argtypes = list(L.sjpeg_hip_encode_ragged_auto_src.argtypes)
     L.sjpeg_hip_encode_ragged_trellis_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_packed_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                     C.POINTER(RaggedParams), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float),
+                                                     C.POINTER(C.c_float), C.c_void_p]
+    L.sjpeg_hip_encode_ragged_packed_src.restype = C.c_int
     _lib = L
     return L
 
@@ -318,7 +334,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_riskiness_ragged_src", "sjpeg_hip_riskiness_verdict", "sjpeg_hip_sharp_ragged_workspace",
     "sjpeg_hip_sharp_yuv_ragged", "sjpeg_hip_encode_ragged_auto_src",
     "sjpeg_hip_scan_quant_error_ragged_src", "sjpeg_hip_scan_counted_bits_ragged_src", "sjpeg_hip_encode_ragged_search_src",
-    "sjpeg_hip_encode_ragged_trellis_src",
+    "sjpeg_hip_encode_ragged_trellis_src", "sjpeg_hip_encode_ragged_packed_src",
 ]
 
 
@@ -1203,6 +1219,69 @@ class Engine:
                   symbol)
         return out, sizes, list(offsets), [int(m) for m in modes]
 
+    def encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
+                             dmax_luma=12, dmax_chroma=1, search=None, capacities=None, packed_capacity=None, out=None):
+        """sjpeg_hip_encode_ragged_packed_src: any ragged encode (encode_ragged_batch / _auto / _trellis / _search by
+        the same arguments) with the frames written back to back into ONE buffer -- each at a multiple of 16, zero
+        padding, the format Comm.gather_streams takes.  capacities: the most each frame may take (default:
+        frame_bound(w, h, mode, 2048), mode YUV_444 for YUV_AUTO / YUV_SHARP); packed_capacity: bytes of `out`
+        (default: len(out), or the capacities' sum, which always fits); out: a uint8 CUDA tensor at a multiple of 16.
+        Returns (out, sizes, offsets, modes) -- sizes [n] and offsets [n + 1] int64 CUDA tensors (views of one tensor)
+        by the caller's frame numbers, offsets[n] the bytes used, or with PACKED_OVERFLOW (bit 63: the int64 is
+        negative) the bytes a second try needs; a frame that was dropped has size 0 -- and, with a search,
+        (..., q, value) as encode_ragged_search.  The encode is asynchronous on the current torch stream."""
+        out, meta, modes, q_out, v_out = self._encode_ragged_packed(fmt, planes_per_frame, dims, yuv_mode, quant, method,
+                                                                    min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                                                    capacities, packed_capacity, out)
+        n = len(dims)
+        res = (out, meta[:n], meta[n:], modes)
+        return res if search is None else res + (q_out, v_out)
+
+    def _encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                              dmax_chroma, search, capacities, packed_capacity, out):
+        """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home)."""
+        import torch
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged_packed: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(quant, (list, tuple))
+        if per_frame and len(quant) != n:
+            raise SjpegError("encode_ragged_packed: one starting matrix per frame")
+        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+        sarr, search_per_frame = None, False
+        if search is not None:
+            search_per_frame = isinstance(search, (list, tuple))
+            if search_per_frame and len(search) != n:
+                raise SjpegError("encode_ragged_packed: one search per frame")
+            sp = [_search_params(x) for x in (search if search_per_frame else [search])]
+            sarr = (SearchParams * len(sp))(*sp)
+        if capacities is None:
+            bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+            capacities = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+        if len(capacities) != n:
+            raise SjpegError("encode_ragged_packed: one capacity per frame")
+        dev = _ragged_device(planes_per_frame)
+        if packed_capacity is None:
+            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
+        packed_capacity = int(packed_capacity)
+        if out is None:
+            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+            raise SjpegError("encode_ragged_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_packed_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
+                                                           packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(),
+                                                           modes, q_out, v_out, self._stream()),
+                  "sjpeg_hip_encode_ragged_packed_src")
+        return out, meta, list(modes), list(q_out), list(v_out)
+
 
 TARGET_SIZE, TARGET_PSNR = 1, 2      # sjpeg_hip_search.target_mode (EncoderParam::TargetMode)
 
@@ -1270,7 +1349,7 @@ def _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes):
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
                   dmax_luma=12, dmax_chroma=1, target_size=None, target_psnr=None, passes=10, tolerance=1.0, qmin=0.0,
-                  qmax=100.0, use_trellis=False):
+                  qmax=100.0, use_trellis=False, packed=False):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
     quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
@@ -1287,7 +1366,13 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     method 6 becomes 8, and the pictures go through Engine.encode_ragged_trellis: frame k's bytes are what
     SjpegEncode(picture, quality, 7 or 8, yuv_mode) makes of it alone.  With any other method the reference ignores
     the flag, and so does this call.  Not together with a target.  (method=7 / 8 without the keyword is refused as
-    before; with it they are taken as they are.)"""
+    before; with it they are taken as they are.)
+
+    packed=True: the same list of bytes through Engine.encode_ragged_packed -- the JPEGs back to back in one pool and
+    ONE device-to-host copy of it instead of one per picture.  The first pool is small (per picture 2048 bytes of
+    header allowance plus half a byte per sample, at least 64 KiB for the call); the pictures a full pool dropped are
+    coded again in a second packed call whose pool always fits (packed_stats() counts those).  The default keeps the
+    unpacked path."""
     import torch
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
@@ -1339,12 +1424,22 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
     dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
+    search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
         if len(ts) != n:
             raise SjpegError("encode_images: one target per image")
         mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
         search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+    if packed:
+        # (the unpacked method 0 path with a fixed sampling and no target codes with the tables of the quality alone --
+        # make_tables: no min_quant, the default bias --, so the packed one does too)
+        plain0 = method == 0 and search is None and yuv_mode not in (YUV_AUTO, YUV_SHARP)
+        with torch.cuda.device(dev):
+            return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                         None if plain0 else min_quant, 0x78 if plain0 else q_bias,
+                                         dmax_luma, dmax_chroma, search)
+    if target is not None:
         with torch.cuda.device(dev):
             out, sizes, offs, _, _ = eng.encode_ragged_search(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs),
                                                               search, method, min_quant, q_bias, dmax_luma,
@@ -1397,11 +1492,12 @@ def _quality_quant(qs):
     return [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
 
 
-def compress_images(images, quality=75.0, engine=None, use_trellis=False):
+def compress_images(images, quality=75.0, engine=None, use_trellis=False, packed=False):
     """The batch SjpegCompress(): JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each
     what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call.  use_trellis=True: with
-    EncoderParam::use_trellis, i.e. what SjpegEncode(picture, quality, 7, SJPEG_YUV_AUTO) makes of it."""
-    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis)
+    EncoderParam::use_trellis, i.e. what SjpegEncode(picture, quality, 7, SJPEG_YUV_AUTO) makes of it.  packed=True:
+    through the packed call and one device-to-host copy, as encode_images."""
+    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis, packed=packed)
 
 
 def riskiness_images(images, engine=None):
@@ -1422,6 +1518,65 @@ def riskiness_images(images, engine=None):
     with torch.cuda.device(dev):
         sums = eng.riskiness_ragged(SRC_RGB, planes, dims).cpu().numpy()
     return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
+
+
+_packed_stats = {"calls": 0, "retries": 0}
+
+
+def packed_stats():
+    """Counters of encode_images(packed=True): calls, and how many of them needed the second packed call."""
+    return dict(_packed_stats)
+
+
+def _first_pool(dims, yuv_mode):
+    """The first pool of encode_images(packed=True): per picture 2048 bytes of header allowance plus half a byte per
+    sample (the host API's first capacity without its 64 KiB per picture), each rounded up to 16; at least 64 KiB."""
+    total = 0
+    for (w, h) in dims:
+        px = w * h
+        samples = 3 * px if yuv_mode in (YUV_444, YUV_AUTO) else px if yuv_mode == YUV_400 else px + px // 2
+        total += (2048 + samples // 2 + 15) & ~15
+    return max(total, 65536)
+
+
+def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search):
+    """encode_images through the packed call: a small first pool, one copy of sizes and offsets, one of the pool; the
+    pictures a full pool dropped go through a second packed call whose pool is the sum of their bounds."""
+    import torch
+    n = len(dims)
+    _packed_stats["calls"] += 1
+    bound_mode = YUV_444 if yuv_mode in (YUV_AUTO, YUV_SHARP) else yuv_mode
+    bounds = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+
+    def run(which, pool):
+        m = len(which)
+        out, meta, _, _, _ = eng._encode_ragged_packed(
+            SRC_RGB, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
+            [quant[k] for k in which] if isinstance(quant, list) else quant, method, min_quant, q_bias, dmax_luma,
+            dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None)
+        eng.wait()                               # (pipelined mode: the output is complete after this)
+        meta = meta.cpu().numpy()                # sizes and offsets together
+        sz, off, end = meta[:m], meta[m:2 * m], int(meta[2 * m])
+        over = end < 0                           # (bit 63 of the int64)
+        top = max((int(off[i] + sz[i]) for i in range(m) if sz[i] > 0), default=0)
+        stage = torch.empty(max(top, 1), dtype=torch.uint8, pin_memory=True)
+        stage[:top].copy_(out[:top], non_blocking=True)      # the ONE copy of the pictures
+        torch.cuda.synchronize()
+        host = stage.numpy()
+        return [host[int(off[i]):int(off[i] + sz[i])].tobytes() if sz[i] > 0 else None for i in range(m)], over
+
+    got, over = run(list(range(n)), _first_pool(dims, yuv_mode))
+    again = [k for k in range(n) if got[k] is None]
+    if again and not over:
+        raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % again[0])
+    if again:
+        _packed_stats["retries"] += 1
+        more, _ = run(again, sum((bounds[k] + 15) & ~15 for k in again))
+        for k, b in zip(again, more):
+            if b is None:
+                raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % k)
+            got[k] = b
+    return got
 
 
 def _fetch_ragged(out, sizes, offsets):

@@ -52,6 +52,28 @@ int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* fram
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err);
 
+// ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
+// lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
+// out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's
+// cursor.  A flow that codes a SUBSET or a reordering of its frames hands down a copy whose `index` names the caller's
+// frame of each frame it passes on.
+struct PackedSink {
+  void* base;                    // d_packed, a multiple of 16
+  uint64_t capacity;             // bytes behind it
+  uint64_t* d_offsets;           // [nframes + 1], the caller's frame numbers; [nframes]: the cursor (bit 63: overflow)
+  int nframes;                   // of the packed call
+  const int* index;              // the caller's number of each frame handed to the flow (NULL: its own position)
+};
+// the entry points' flows with a sink (the public functions pass NULL); scan_engine.hip and ragged_search.cc
+int ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
+                      const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                      int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, void* stream,
+                      const PackedSink* sink);
+int ragged_search_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
+                       const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                       int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search, int search_per_frame,
+                       float* q_out, float* value_out, void* d_out, uint64_t* d_sizes, void* stream, const PackedSink* sink);
+
 // ---- the search over a ragged batch (ragged_search.cc) and what it takes from the engine (scan_engine.hip)
 int set_error(int code, const std::string& msg);          // sjpeg_hip_last_error() of the calling thread
 size_t engine_scratch_limit(const sjpeg_hip_engine* e);   // SJPEG_HIP_SCRATCH_LIMIT_BYTES

@@ -222,12 +222,14 @@ int search_part(sjpeg_hip_engine* e, const std::string& who, int format, int yuv
 
 }  // namespace
 
-int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+// sjpeg_hip_encode_ragged_search_src; sink != NULL: the frames go to the packed buffer (ragged_aux.h) in the order the
+// sub-calls code them -- the frames that are not searched, then every part's searched ones
+int sjpeg_internal::ragged_search_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                        const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64],
                                        int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
                                        int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search,
                                        int search_per_frame, float* q_out, float* value_out, void* d_out,
-                                       uint64_t* d_sizes, void* stream) {
+                                       uint64_t* d_sizes, void* stream, const PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_search_src";
   if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (search == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": search == NULL");
@@ -260,8 +262,8 @@ int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_
       if (value_out != nullptr) value_out[f] = -1.f;
     }
     if (searched.empty()) {
-      return sjpeg_hip_encode_ragged_batch_src(e, format, yuv_mode, nframes, frames, quant, quant_per_frame, min_quant, q_bias,
-                                               method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream);
+      return sjpeg_internal::ragged_batch_flow(e, format, yuv_mode, nframes, frames, quant, quant_per_frame, min_quant, q_bias,
+                                               method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream, sink);
     }
     if (hipSetDevice(sjpeg_internal::engine_device(e)) != hipSuccess) return hip_fail(who, "hipSetDevice");
     const bool adaptive = method >= 3;
@@ -273,9 +275,18 @@ int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_
       std::vector<sjpeg_hip_ragged_frame> sub;
       for (int f : which) sub.push_back(frames[f]);
       uint64_t* const d_sub = d_sub_sizes;
-      if (int rc = sjpeg_hip_encode_ragged_batch_src(e, format, yuv_mode, static_cast<int>(which.size()), sub.data(),
+      // (packed output: the sub-call's frame k is the caller's which[k])
+      sjpeg_internal::PackedSink sub_sink;
+      std::vector<int> sub_index;
+      if (sink != nullptr) {
+        sub_sink = *sink;
+        for (int f : which) sub_index.push_back(sink->index != nullptr ? sink->index[f] : f);
+        sub_sink.index = sub_index.data();
+      }
+      if (int rc = sjpeg_internal::ragged_batch_flow(e, format, yuv_mode, static_cast<int>(which.size()), sub.data(),
                                                      reinterpret_cast<const uint8_t(*)[2][64]>(q), 1, min_quant, q_bias, m,
-                                                     qdelta_max_luma, qdelta_max_chroma, d_out, d_sub, stream)) {
+                                                     qdelta_max_luma, qdelta_max_chroma, d_out, d_sub, stream,
+                                                     sink != nullptr ? &sub_sink : nullptr)) {
         return rc;
       }
       return scatter_sizes(who, d_sub, which, d_sizes, st);
@@ -358,4 +369,15 @@ int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_
   } catch (...) {
     return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
   }
+}
+
+int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64],
+                                       int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                       int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search,
+                                       int search_per_frame, float* q_out, float* value_out, void* d_out,
+                                       uint64_t* d_sizes, void* stream) {
+  return sjpeg_internal::ragged_search_flow(e, format, yuv_mode, nframes, frames, quant, quant_per_frame, min_quant, q_bias,
+                                            method, qdelta_max_luma, qdelta_max_chroma, search, search_per_frame, q_out,
+                                            value_out, d_out, d_sizes, stream, nullptr);
 }

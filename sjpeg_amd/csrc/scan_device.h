@@ -98,6 +98,9 @@ struct alignas(16) RaggedFrame {
   long long row_stride[3];
   unsigned long long pool_base, ubuf_base;      // words
   unsigned long long out_offset, out_capacity;  // bytes of d_out
+  // (packed output, sjpeg_hip_encode_ragged_packed_src: the DEVICE copy of out_offset is written by place_ragged_frames
+  // between K4 and K5 of the launch -- the ragged K5 and pack_ragged_edges read the frame's start here.  The blob that
+  // holds the descriptors must stay writable device memory and must not be uploaded again between those kernels.)
   int W, H, mb_w, n_mcus, nseg, has_clip;
   uint32_t seg_base;       // first segment (seg_nbits, seg_words, seg_xbase); its seg_off row starts at seg_base + frame
   uint32_t pool_words, ubuf_words;

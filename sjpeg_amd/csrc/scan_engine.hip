@@ -232,6 +232,9 @@ struct sjpeg_hip_engine {
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;
+  // packed output of a ragged call (sjpeg_hip_encode_ragged_packed_src): where the next frame starts -- zeroed once by
+  // the call, advanced by place_ragged_frames of every launch, group and part of it (bit 63: a frame was dropped)
+  DevBuf<unsigned long long> pack_cursor;
   // side_done is recorded LAZILY, by whoever is about to wait on it (side_mark): an event record is a packet in the
   // queue and about 5 us of host time, and a loop of pipelined calls needs none -- one frame per call was bound by the
   // HOST at five event calls per call (36-46 us against 35 of device time, `tools/one_frame_piped.py`)
@@ -672,7 +675,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->tables.release(); e->header.release(); e->seg_words.release(); e->seg_nbits.release(); e->pool.release(); e->pool_ctr.release(); e->seg_xbase.release(); e->replay.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
-  e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release();
+  e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -697,7 +700,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->replay.release();
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release();
-  e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release();
+  e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -802,7 +805,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
          b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) +
-         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes);
+         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -1406,7 +1409,8 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
-                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept = nullptr);
+                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept = nullptr,
+                  const sjpeg_internal::PackedSink* sink = nullptr);
 
 }  // namespace
 
@@ -1462,12 +1466,16 @@ namespace {
 // K4 and K5, no header, nothing written to d_out or d_sizes; the frames' out_capacity plans the segment scratch only.
 // kept != NULL: K1 is kKindEncodeReplayRagged -- it codes the blocks a trellis statistics pass over the same frames left
 // at `kept` (ragged_analysis, kPassStatsTrellis: kKeptSegWords a segment, in the order of the frames) and reads no pixel.
+// sink != NULL: packed output -- d_out and the frames' out_offset are not used; per launch K4 leaves the sizes only,
+// place_ragged_frames puts the launch's frames behind the engine's cursor (each start into its descriptor, where K5
+// takes it from, and into the caller's offsets), pack_ragged_edges writes header, EOI and padding (stitch_kernels.h).
 int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
-                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept) {
+                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept, const sjpeg_internal::PackedSink* sink) {
   const int ntab = tables_per_frame ? nframes : 1;
+  if (sink != nullptr && (d_bits != nullptr || d_sizes == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: packed output needs the sizes");
   std::vector<SegPlan> plan(nframes);
   std::vector<uint32_t> max_chunks(nframes);
   for (int f = 0; f < nframes; ++f) {
@@ -1514,12 +1522,13 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     }
   }
 
-  // the blob: descriptors | digested tables | maps | header offsets | header bytes
+  // the blob: descriptors | digested tables | maps | header offsets | header bytes | (packed) the caller's frame numbers
   const size_t off_tab = align16(sizeof(RaggedFrame) * nframes);
   const size_t off_map = off_tab + sizeof(DevTables) * ntab;
   const size_t off_hoff = align16(off_map + map_words * sizeof(uint32_t));
   const size_t off_hdr = align16(off_hoff + (header_offsets != nullptr ? (static_cast<size_t>(nframes) + 1) * sizeof(uint32_t) : 0));
-  const size_t blob_bytes = align16(off_hdr + header_size);
+  const size_t off_pidx = align16(off_hdr + header_size);
+  const size_t blob_bytes = align16(off_pidx + (sink != nullptr ? static_cast<size_t>(nframes) * sizeof(uint32_t) : 0));
   std::vector<uint4> blob(blob_bytes / 16);
   uint8_t* const hb = reinterpret_cast<uint8_t*>(blob.data());
   RaggedFrame* const desc = reinterpret_cast<RaggedFrame*>(hb);
@@ -1561,6 +1570,10 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     for (int f = 0; f <= nframes; ++f) ho[f] = static_cast<uint32_t>(header_offsets[f]);
     if (header_size > 0) memcpy(hb + off_hdr, headers, header_size);
   }
+  if (sink != nullptr) {
+    uint32_t* const pi = reinterpret_cast<uint32_t*>(hb + off_pidx);
+    for (int f = 0; f < nframes; ++f) pi[f] = static_cast<uint32_t>(sink->index != nullptr ? sink->index[f] : f);
+  }
 
   // scratch for the largest launch
   HIP_TRY(hipSetDevice(e->device));
@@ -1587,6 +1600,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
       (rc = e->chunk_off.ensure(n_chunks)) || (rc = e->frame_flags.ensure(n_f))) {
     return rc;
   }
+  if (sink != nullptr && e->pack_cursor.p == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: packed output without its cursor");
   if ((rc = upload(e, e->ragged.p, blob.data(), blob_bytes, st))) return rc;
   if ((rc = sync_uploads(e, st))) return rc;
   const uint8_t* const db = reinterpret_cast<const uint8_t*>(e->ragged.p);
@@ -1624,7 +1638,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     s.header = db + off_hdr; s.header_size = 0;
     s.hdr_off = header_offsets != nullptr ? reinterpret_cast<const uint32_t*>(db + off_hoff) + l.f0 : nullptr;
     s.append_eoi = append_eoi;
-    s.out = static_cast<uint8_t*>(d_out);
+    s.out = static_cast<uint8_t*>(sink != nullptr ? sink->base : d_out);
     s.sizes = d_sizes != nullptr ? reinterpret_cast<unsigned long long*>(d_sizes) + l.f0 : nullptr;
     s.subs = 1; s.wide_subs = 0;
     s.frame_flags = e->frame_flags.p;
@@ -1635,6 +1649,28 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     HIP_TRY(hipGetLastError());
     if (d_bits != nullptr) {
       hipLaunchKernelGGL(counted_bits_ragged, dim3(l.nf), dim3(kThreads), 0, st, s, d_bits + l.f0);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    if (sink != nullptr) {
+      // K4 with pack_off set leaves the size only (what it points at is never read: the starts go into the descriptors)
+      StitchArgs s4 = s;
+      s4.pack_off = e->pack_cursor.p;
+      hipLaunchKernelGGL(scan_chunk_offsets<true>, dim3(l.nf), dim3(kThreads), 0, st, s4);
+      HIP_TRY(hipGetLastError());
+      PackArgs p;
+      p.nframes = l.nf; p.total = static_cast<uint32_t>(sink->nframes);
+      p.sizes = s.sizes;
+      p.rframes = const_cast<RaggedFrame*>(s.rframes);
+      p.index = reinterpret_cast<const uint32_t*>(db + off_pidx) + l.f0;
+      p.offsets = reinterpret_cast<unsigned long long*>(sink->d_offsets);
+      p.capacity = sink->capacity;
+      p.cursor = e->pack_cursor.p;
+      hipLaunchKernelGGL(place_ragged_frames, dim3(1), dim3(kThreads), 0, st, p);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL((stuff_chunks<0, true>), dim3(l.stuff_wgs), dim3(kThreads), 0, st, s);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(pack_ragged_edges, dim3(l.nf), dim3(kThreads), 0, st, s);
       HIP_TRY(hipGetLastError());
       continue;
     }
@@ -2680,7 +2716,8 @@ __global__ __launch_bounds__(256) void scatter_sizes_kernel(const unsigned long 
 int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector<RaggedGroup>& groups,
                         const uint8_t (*quant_in)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias,
                         int method, int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
-                        hipStream_t st, const std::function<int()>& last_ready = {}) {
+                        hipStream_t st, const std::function<int()>& last_ready = {},
+                        const sjpeg_internal::PackedSink* sink = nullptr) {
   const bool adaptive = method >= 3, optimize = (method != 0) && (method != 3), trellis = method >= 7;
   size_t n = 0;
   std::vector<size_t> gbase;
@@ -2872,6 +2909,17 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
                                g.yuv_mode, quant.data(), optimize ? specs.data() : nullptr, &headers, &offs)) return rc;
     if (gi + 1 == groups.size()) mark("tables built");
     if (int rc = ready(gi)) return rc;
+    if (sink != nullptr) {               // packed output: the group's frames under the caller's numbers
+      sjpeg_internal::PackedSink gs = *sink;
+      std::vector<int> gidx(ng);
+      for (size_t k = 0; k < ng; ++k) gidx[k] = sink->index != nullptr ? sink->index[g.index[k]] : g.index[k];
+      gs.index = gidx.data();
+      if (int rc = ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
+                                 (trellis || !one_table) ? 1 : 0, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, nullptr,
+                                 reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
+                                 trellis ? e->replay.p + gkept[gi] * kKeptSegWords : nullptr, &gs)) return rc;
+      continue;
+    }
     const int rc = trellis ? ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
                                            1, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, d_out,
                                            reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
@@ -2892,11 +2940,14 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
 
 }  // namespace
 
-int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+}  // extern "C"
+
+// sjpeg_hip_encode_ragged_batch_src; sink != NULL: packed output (ragged_aux.h)
+int sjpeg_internal::ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                       const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
                                       int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
                                       int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
-                                      void* stream) {
+                                      void* stream, const PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_batch_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (frames == nullptr || quant_in == nullptr || d_out == nullptr || d_sizes == nullptr) {
@@ -2917,10 +2968,21 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_m
     g.index.resize(nframes);
     for (int f = 0; f < nframes; ++f) g.index[f] = f;
     return ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
-                               qdelta_max_chroma, d_out, d_sizes, static_cast<hipStream_t>(stream));
+                               qdelta_max_chroma, d_out, d_sizes, static_cast<hipStream_t>(stream), {}, sink);
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
+}
+
+extern "C" {
+
+int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                      int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                      int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                      void* stream) {
+  return sjpeg_internal::ragged_batch_flow(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias,
+                                           method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream, nullptr);
 }
 
 // ---- ragged batches with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP ----
@@ -3063,7 +3125,8 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
 static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
                              const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64], int quant_per_frame,
                              const uint8_t* min_quant, int q_bias, int method, int qdelta_max_luma, int qdelta_max_chroma,
-                             void* d_out, uint64_t* d_sizes, int* modes, void* stream) {
+                             void* d_out, uint64_t* d_sizes, int* modes, void* stream,
+                             const sjpeg_internal::PackedSink* sink = nullptr) {
   const bool trellis = method >= 7;
   static const bool batch_debug = getenv("SJPEG_HIP_BATCH_DEBUG") != nullptr;      // (measurement aid: host timeline on stderr)
   const auto t_start = std::chrono::steady_clock::now();
@@ -3186,24 +3249,24 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
     }
     if (int rc = ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
                                      qdelta_max_chroma, d_out, d_sizes, st,
-                                     sharp.empty() ? std::function<int()>() : std::function<int()>(convert))) return rc;
+                                     sharp.empty() ? std::function<int()>() : std::function<int()>(convert), sink)) return rc;
   }
   mark("call done");
   return 0;
 }
 
 // sjpeg_hip.h; the flow: ragged_modes_flow
-int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
-                                     const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
-                                     int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
-                                     int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
-                                     int* modes, void* stream) {
+static int ragged_auto_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                            const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                            int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                            int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                            int* modes, void* stream, const sjpeg_internal::PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_auto_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
   if (yuv_mode != SJPEG_YUV_AUTO_ && yuv_mode != SJPEG_YUV_SHARP_) {
-    const int rc = sjpeg_hip_encode_ragged_batch_src(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant,
-                                                     q_bias, method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream);
+    const int rc = sjpeg_internal::ragged_batch_flow(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant,
+                                                     q_bias, method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream, sink);
     if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
     return rc;
   }
@@ -3221,18 +3284,27 @@ int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mo
       if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
     }
     return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
-                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream);
+                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, sink);
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
 }
 
+int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                     int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                     int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                     int* modes, void* stream) {
+  return ragged_auto_flow(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
+                          qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, nullptr);
+}
+
 // Methods 7 and 8 over a ragged batch (sjpeg_hip.h): ragged_modes_flow with the trellis steps of ragged_batch_groups.
-int sjpeg_hip_encode_ragged_trellis_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
-                                        const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
-                                        int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
-                                        int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
-                                        int* modes, void* stream) {
+static int ragged_trellis_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                               const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                               int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                               int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                               int* modes, void* stream, const sjpeg_internal::PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_trellis_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
@@ -3257,7 +3329,65 @@ int sjpeg_hip_encode_ragged_trellis_src(sjpeg_hip_engine* e, int format, int yuv
       if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
     }
     return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
-                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream);
+                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, sink);
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_trellis_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant_in)[2][64],
+                                        int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                        int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes,
+                                        int* modes, void* stream) {
+  return ragged_trellis_flow(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
+                             qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, nullptr);
+}
+
+// One packed buffer for every ragged flow (sjpeg_hip.h): the frames back to back, each at a multiple of 16 -- the format
+// sjpeg_hip_gather_streams takes.  The flows are the unpacked entry points' (their checks, their messages); the sink
+// (ragged_aux.h) goes down to ragged_encode, whose launches place their frames behind the engine's cursor.
+int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                       const sjpeg_hip_ragged_params* params, void* d_packed, size_t packed_capacity,
+                                       uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                       void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_packed_src";
+  // (every argument check of this function comes before `e` is touched: the tests without a GPU rely on it)
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr || d_packed == nullptr || d_sizes == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, d_packed or d_sizes == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return fail(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  try {
+    std::vector<sjpeg_hip_ragged_frame> fr(frames, frames + nframes);
+    for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = ragged_ordered(e, st)) return rc;
+    if (int rc = e->pack_cursor.ensure(1)) return rc;
+    HIP_TRY(hipMemsetAsync(e->pack_cursor.p, 0, sizeof(unsigned long long), st));
+    const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+    const sjpeg_hip_ragged_params& p = *params;
+    if (p.search != nullptr) {
+      const int rc = sjpeg_internal::ragged_search_flow(e, format, p.yuv_mode, nframes, fr.data(), p.quant, p.quant_per_frame,
+                                                        p.min_quant, p.q_bias, p.method, p.qdelta_max_luma, p.qdelta_max_chroma,
+                                                        p.search, p.search_per_frame, q_out, value_out, d_packed, d_sizes, stream, &sink);
+      if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = p.yuv_mode;
+      return rc;
+    }
+    for (int f = 0; f < nframes; ++f) {
+      if (q_out != nullptr) q_out[f] = -1.f;
+      if (value_out != nullptr) value_out[f] = -1.f;
+    }
+    if (p.method == 7 || p.method == 8) {
+      return ragged_trellis_flow(e, format, p.yuv_mode, nframes, fr.data(), p.quant, p.quant_per_frame, p.min_quant, p.q_bias,
+                                 p.method, p.qdelta_max_luma, p.qdelta_max_chroma, d_packed, d_sizes, modes, stream, &sink);
+    }
+    return ragged_auto_flow(e, format, p.yuv_mode, nframes, fr.data(), p.quant, p.quant_per_frame, p.min_quant, p.q_bias,
+                            p.method, p.qdelta_max_luma, p.qdelta_max_chroma, d_packed, d_sizes, modes, stream, &sink);
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }

@@ -28,6 +28,9 @@ struct StitchArgs {
   unsigned long long* sizes;
   // packed output (sjpeg_hip_encode_scan_packed_src): frame f starts at out + pack_off[f], a multiple of 16, the
   // frames back to back; NULL: at out + f * out_stride.  out_stride stays the bytes a frame may take.
+  // (ragged launches with packed output depend on this field too: their K4 is the ragged form launched with pack_off
+  // set to a DUMMY non-null pointer, for the "size only, no header" return alone.  The ragged forms must never index
+  // it: ragged_encode() passes it to K4 only, and K5 / the edges kernel take the start from the frame's descriptor.)
   unsigned long long* pack_off = nullptr;
   const unsigned long long* seg_nbits64;   // band stitch: lengths as uint64 (else NULL)
   unsigned long long* total_bits_out;      // band encode: where the bit count of the band goes (else NULL)
@@ -581,6 +584,82 @@ __global__ __launch_bounds__(kThreads) void pack_frame_edges(const StitchArgs a)
   const uint32_t hoff = a.hdr_off ? a.hdr_off[frame] : 0u;
   const uint32_t hsize = a.hdr_off ? a.hdr_off[frame + 1] - hoff : a.header_size;
   uint8_t* const dst = a.out + a.pack_off[frame];
+  for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
+  if (threadIdx.x == 0 && a.append_eoi) { dst[size - 2] = 0xff; dst[size - 1] = 0xd9; }
+  const uint32_t pad = static_cast<uint32_t>((16u - (size & 15u)) & 15u);
+  if (threadIdx.x < pad) dst[size + threadIdx.x] = 0;
+}
+
+// K4b of a ragged launch with packed output (sjpeg_hip_encode_ragged_packed_src): the frames of ALL launches, groups and
+// parts of a call lie back to back in one buffer, so the scan starts from a cursor in engine memory that the call zeroes
+// once and every launch advances.  One workgroup; a thread owns a run of eight frames per round, as in K2 and K4 (one
+// scan per 2048 frames: a launch of 65 535 frames takes 32 rounds).  K4 (the unchanged ragged form: with pack_off set it
+// leaves the size only) has written the sizes as coded.  A frame whose padded end passes the capacity is dropped: its
+// size becomes 0, which K5 and the edges kernel skip; the scan goes on over the sizes as coded, so every later frame is
+// dropped too and the cursor ends at the bytes the call needs.  The start of every frame goes into its descriptor's
+// out_offset -- the ragged K5 then writes there without a form of its own -- and to the caller's offsets at the caller's
+// frame number.  Bit 63 of the cursor (SJPEG_HIP_PACKED_OVERFLOW) is sticky: a frame was dropped.
+struct PackArgs {
+  int nframes;                       // of the launch
+  uint32_t total;                    // of the call: offsets[total] takes the cursor
+  unsigned long long* sizes;         // [nframes], from K4
+  RaggedFrame* rframes;              // [nframes]: out_offset <- the frame's start
+  const uint32_t* index;             // [nframes]: the caller's number of each frame
+  unsigned long long* offsets;       // the caller's [total + 1]
+  unsigned long long capacity;       // bytes of the packed buffer
+  unsigned long long* cursor;
+};
+
+__global__ __launch_bounds__(kThreads) void place_ragged_frames(const PackArgs p) {
+  __shared__ uint32_t scratch[16];
+  constexpr int kRun = 8;
+  constexpr unsigned long long kOverflow = 1ull << 63;
+  const unsigned long long cursor_in = *p.cursor;
+  unsigned long long running = cursor_in & ~kOverflow;
+  int dropped = 0;
+  for (int base = 0; base < p.nframes; base += kThreads * kRun) {
+    const int i0 = base + static_cast<int>(threadIdx.x) * kRun;
+    unsigned long long v[kRun], mine = 0;                    // in units of 16 bytes
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) {
+      v[j] = (i0 + j < p.nframes) ? (p.sizes[i0 + j] + 15ull) >> 4 : 0ull;
+      mine += v[j];
+    }
+    // (a frame's stream is addressed with 32-bit word counts, so eight frames stay below 2^34 units: scanned as two
+    // halves, like K2's bands)
+    uint32_t total_lo, total_hi;
+    const uint32_t ex_lo = wg_exclusive_scan<kThreads>(static_cast<uint32_t>(mine & 0xffffffu), scratch, &total_lo);
+    const uint32_t ex_hi = wg_exclusive_scan<kThreads>(static_cast<uint32_t>(mine >> 24), scratch, &total_hi);
+    unsigned long long at = running + ((ex_lo + (static_cast<unsigned long long>(ex_hi) << 24)) << 4);
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) {
+      if (i0 + j < p.nframes) {
+        const unsigned long long bytes = v[j] << 4;
+        if (bytes != 0ull && at + bytes > p.capacity) { p.sizes[i0 + j] = 0ull; dropped = 1; }
+        p.rframes[i0 + j].out_offset = at;
+        p.offsets[p.index[i0 + j]] = at;
+      }
+      at += v[j] << 4;
+    }
+    running += (total_lo + (static_cast<unsigned long long>(total_hi) << 24)) << 4;
+  }
+  const int any = __syncthreads_or(dropped);                 // (every thread has read the cursor: the scans' barriers)
+  if (threadIdx.x == 0) {
+    const unsigned long long out = running | (cursor_in & kOverflow) | (any ? kOverflow : 0ull);
+    *p.cursor = out;
+    p.offsets[p.total] = out;
+  }
+}
+
+// ... and the edges of the launch's frames, one workgroup each, as pack_frame_edges: header (the frame's own), EOI, zero
+// bytes up to the next multiple of 16 -- at the start place_ragged_frames left in the descriptor
+__global__ __launch_bounds__(kThreads) void pack_ragged_edges(const StitchArgs a) {
+  const int frame = blockIdx.x;
+  const unsigned long long size = a.sizes[frame];
+  if (size == 0) return;
+  const uint32_t hoff = a.hdr_off ? a.hdr_off[frame] : 0u;
+  const uint32_t hsize = a.hdr_off ? a.hdr_off[frame + 1] - hoff : a.header_size;
+  uint8_t* const dst = a.out + a.rframes[frame].out_offset;
   for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
   if (threadIdx.x == 0 && a.append_eoi) { dst[size - 2] = 0xff; dst[size - 1] = 0xd9; }
   const uint32_t pad = static_cast<uint32_t>((16u - (size & 15u)) & 15u);
