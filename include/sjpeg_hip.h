@@ -597,6 +597,63 @@ int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* engine, int format, int
                                        int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                        void* stream);
 
+/* ---- ragged batches with EVERY combination of sjpeg_hip_ragged_params: the search with any sampling and the trellis ----
+ * sjpeg_hip_encode_ragged_full_src: yuv_mode 0..4, method 0..8, search NULL or not (per frame or shared), in one call.
+ *   Frame f's bytes are what the reference's sjpeg::Encode() makes of that picture alone with yuv_mode as given,
+ *   Huffman_compress = (method not in {0, 3}), adaptive_quantization = (method >= 3), use_trellis = (method >= 7) and
+ *   search[f].  Frame f goes to [out_offset, out_offset + out_capacity) of d_out; modes / q_out / value_out (host, each
+ *   may be NULL) as in sjpeg_hip_encode_ragged_packed_src.  A frame with passes <= 1 is coded by the unsearched flow of
+ *   the same method and mode and reports -1 in q_out / value_out.
+ *   What an older entry point takes is handed to its flow and gives its bytes: no frame searched --
+ *   sjpeg_hip_encode_ragged_auto_src / _trellis_src; a search with yuv_mode 1 / 3 / 4 and methods 0..6 --
+ *   sjpeg_hip_encode_ragged_search_src.  The flow of this call covers a search (some frame with passes > 1) with
+ *   SJPEG_YUV_AUTO or SJPEG_YUV_SHARP, with method 7 or 8, or both -- Encoder::LoopScan (src/dichotomy.cc:113-205) with
+ *   the mode decision of src/encoders.cc:549-551 in front and, for the trellis, StoreRunLevels (src/dichotomy.cc:80-111):
+ *   - SJPEG_YUV_AUTO: one ragged riskiness and one wait, then the verdicts: the frames stand in mode groups (4:2:0, 4:4:4,
+ *     4:0:0 of the caller's format, sharp).  The sharp frames (all frames under SJPEG_YUV_SHARP) are converted ONCE into
+ *     planar 4:2:0 planes in engine scratch and searched as a SJPEG_HIP_SRC_YUV420 group.
+ *   - Every pass launches over ALL groups, then waits: the host waits per pass are those of
+ *     sjpeg_hip_encode_ragged_search_src (two for methods 3..8, one otherwise, one more after a recount), per kind of
+ *     target and per part, whatever the number of groups.
+ *   - Methods 7 and 8 with a size target: each pass's statistics launch quantizes with the trellis and keeps its blocks;
+ *     frame f is priced with ITS accumulated rate table -- the standard AC lengths, and after every pass the lengths of the
+ *     symbols that pass's optimised AC tables have (InitCodes(true), src/dichotomy.cc:86,152, src/entropy.cc:116-128).
+ *     With a PSNR target the passes measure the plain quantization error (ComputePSNR does not use the trellis).
+ *   - The end (src/dichotomy.cc:178-201): a size-searched trellis frame whose last pass was its best is NOT quantized
+ *     again -- its stream replays the blocks that pass kept, with the codes that pass compiled.  Every other trellis frame
+ *     gets one more trellis statistics pass with its best matrices (no adaptation) and its rate table as it stands, then
+ *     the replay.  Frames of methods 0..6 end as in sjpeg_hip_encode_ragged_search_src: method 1 or 0 with the best
+ *     matrices, over all groups at once.
+ *   - A frame's kept blocks (36 864 bytes a segment) lie at ONE place for the whole part, whichever frames a launch
+ *     covers; the replay covers all trellis frames of a group in one launch.  The kept histograms, the sharp planes and
+ *     workspace and the kept blocks count against SJPEG_HIP_SCRATCH_LIMIT_BYTES: past it the call goes in parts of
+ *     consecutive searched frames, each a complete search.
+ *   AUTO and SHARP take RGB, BGRA or RGBA sources.  SJPEG_HIP_EINVAL (the message names the argument or the frame): a
+ *   NULL engine, params, frames, d_out, d_sizes or params->quant; nframes outside 1..65535; yuv_mode outside 0..4; method
+ *   outside 0..8; qdelta_max outside -12..12; a target_mode other than 1 or 2 or a non-finite target_value in any search
+ *   entry; and every frame check of sjpeg_hip_encode_ragged_src.  No per-picture metadata, no restart markers.
+ * sjpeg_hip_encode_ragged_full_packed_src: the same call into ONE packed buffer -- the arguments and the layout contract
+ *   of sjpeg_hip_encode_ragged_packed_src.  A searched SJPEG_YUV_AUTO call lays its frames out as that contract says:
+ *   the frames that are not searched first, then (per part) the searched ones grouped by the mode each was given.
+ * sjpeg_hip_engine_search_stats: counters of the engine's most recent _full_ call that took the flow above (all zero
+ *   after a call that was handed to an older flow).  Host values; the call does not synchronise.
+ *   [0] most passes any frame ran, [1] measurement launches (one per group and pass; recounts too), [2] host waits of the
+ *   call (those of the unsearched frames' flow and of the method 1 ending counted as documented for one part), [3] frames
+ *   whose stream replays the blocks their own last search pass kept, [4] frames quantized once more after the search,
+ *   [5] trellis statistics launches. */
+int sjpeg_hip_encode_ragged_full_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                     int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_full_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                            const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                            const sjpeg_hip_ragged_params* params,
+                                            void* d_packed, size_t packed_capacity,
+                                            uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                            int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                            void* stream);
+int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* engine, uint64_t stats[6]);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

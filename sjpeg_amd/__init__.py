@@ -299,6 +299,14 @@ def lib() -> C.CDLL:
                                                      C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                                      C.POINTER(C.c_float), C.c_void_p]
     L.sjpeg_hip_encode_ragged_packed_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_full_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame),
+                                                   C.POINTER(RaggedParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
+    L.sjpeg_hip_encode_ragged_full_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_full_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_full_packed_src.restype = C.c_int
+    L.sjpeg_hip_engine_search_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.sjpeg_hip_engine_search_stats.restype = C.c_int
     _lib = L
     return L
 
@@ -335,6 +343,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_sharp_yuv_ragged", "sjpeg_hip_encode_ragged_auto_src",
     "sjpeg_hip_scan_quant_error_ragged_src", "sjpeg_hip_scan_counted_bits_ragged_src", "sjpeg_hip_encode_ragged_search_src",
     "sjpeg_hip_encode_ragged_trellis_src", "sjpeg_hip_encode_ragged_packed_src",
+    "sjpeg_hip_encode_ragged_full_src", "sjpeg_hip_encode_ragged_full_packed_src", "sjpeg_hip_engine_search_stats",
 ]
 
 
@@ -1238,8 +1247,10 @@ class Engine:
         return res if search is None else res + (q_out, v_out)
 
     def _encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
-                              dmax_chroma, search, capacities, packed_capacity, out):
-        """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home)."""
+                              dmax_chroma, search, capacities, packed_capacity, out,
+                              symbol="sjpeg_hip_encode_ragged_packed_src"):
+        """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home).
+        symbol: that entry point, or its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments)."""
         import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
@@ -1276,11 +1287,66 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_packed_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
-                                                           packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(),
-                                                           modes, q_out, v_out, self._stream()),
-                  "sjpeg_hip_encode_ragged_packed_src")
+        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, C.byref(params), out.data_ptr(), packed_capacity,
+                                         meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
+                  symbol)
         return out, meta, list(modes), list(q_out), list(v_out)
+
+    def encode_ragged_full(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
+                           dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None, offsets=None, sizes=None):
+        """sjpeg_hip_encode_ragged_full_src: every combination of SjpegYUVMode 0..4, method 0..8 and a search (None, one
+        SearchParams / dict, or a list of one per frame) in one ragged call.  Frame k's bytes are what the reference's
+        sjpeg::Encode() makes of that picture alone.  What encode_ragged_batch / _auto / _trellis / _search take goes to
+        their flows; a search with YUV_AUTO / YUV_SHARP, with method 7 or 8, or both, is this call's own.  Returns
+        (out, sizes, offsets, modes, q, value): q / value -1 for a frame that was not searched (passes <= 1)."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n:
+            raise SjpegError("encode_ragged_full: one entry of planes_per_frame and dims per frame, at least one frame")
+        per_frame = isinstance(quant, (list, tuple))
+        if per_frame and len(quant) != n:
+            raise SjpegError("encode_ragged_full: one starting matrix per frame")
+        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+        sarr, search_per_frame = None, False
+        if search is not None:
+            search_per_frame = isinstance(search, (list, tuple))
+            if search_per_frame and len(search) != n:
+                raise SjpegError("encode_ragged_full: one search per frame")
+            sp = [_search_params(x) for x in (search if search_per_frame else [search])]
+            sarr = (SearchParams * len(sp))(*sp)
+        if capacities is None:
+            bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+            capacities = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_full_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
+                                                         sizes.data_ptr(), modes, q_out, v_out, self._stream()),
+                  "sjpeg_hip_encode_ragged_full_src")
+        return out, sizes, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+
+    def encode_ragged_full_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None,
+                                  q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                                  packed_capacity=None, out=None):
+        """sjpeg_hip_encode_ragged_full_packed_src: encode_ragged_full into ONE packed buffer, with the arguments and
+        the layout of encode_ragged_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        out, meta, modes, q_out, v_out = self._encode_ragged_packed(
+            fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+            capacities, packed_capacity, out, symbol="sjpeg_hip_encode_ragged_full_packed_src")
+        n = len(dims)
+        return out, meta[:n], meta[n:], modes, q_out, v_out
+
+    def search_stats(self):
+        """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
+        _full_packed call -- [most passes any frame ran, measurement launches, host waits, frames whose stream replays
+        the blocks their own last search pass kept, frames quantized once more after the search, trellis statistics
+        launches].  No synchronisation."""
+        arr = (C.c_uint64 * 6)()
+        self._chk(lib().sjpeg_hip_engine_search_stats(self._h, arr), "sjpeg_hip_engine_search_stats")
+        return [int(x) for x in arr]
 
 
 TARGET_SIZE, TARGET_PSNR = 1, 2      # sjpeg_hip_search.target_mode (EncoderParam::TargetMode)
@@ -1481,6 +1547,68 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
         return _fetch_ragged(out, sizes, offs)
 
 
+def encode_images_full(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_trellis=False, target_size=None,
+                       target_psnr=None, passes=10, tolerance=1.0, qmin=0.0, qmax=100.0, min_quant=None, q_bias=0x78,
+                       dmax_luma=12, dmax_chroma=1, engine=None, packed=False):
+    """JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each what the reference's
+    sjpeg::Encode() makes of it alone with these EncoderParam fields -- ANY combination of them, in one ragged call
+    (Engine.encode_ragged_full).  The defaults are those of EncoderParam / SjpegCompress: quality 75, SJPEG_YUV_AUTO,
+    method 4.  use_trellis maps method 4 to 7 and 6 to 8 (src/api.cc:155-157).  target_size (bytes) or target_psnr (dB),
+    one value or one per image, at most one of the two: the multi-pass search per picture with passes / tolerance /
+    qmin / qmax -- with YUV_AUTO, YUV_SHARP and the trellis too, which encode_images refuses.  packed=True: through
+    Engine.encode_ragged_full_packed and the two-pool scheme of encode_images (packed_stats() counts it)."""
+    import torch
+    if target_size is not None and target_psnr is not None:
+        raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
+    target = target_size if target_size is not None else target_psnr
+    method = int(method)
+    if method < 0 or method > 8:
+        raise SjpegError(f"encode_images_full: method {method} is not one of 0..8")
+    if use_trellis:
+        method = {4: 7, 6: 8}.get(method, method)
+    yuv_mode = int(yuv_mode)
+    if yuv_mode < 0 or yuv_mode > 4:
+        raise SjpegError(f"encode_images_full: yuv_mode {yuv_mode} is not one of 0..4 (SjpegYUVMode)")
+    images = list(images)
+    if not images:
+        raise SjpegError("encode_images_full: no images")
+    n = len(images)
+    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    if len(qs) != n:
+        raise SjpegError("encode_images_full: one quality per image")
+    dev = None
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda:
+            raise SjpegError(f"encode_images_full: image {k} is not a CUDA tensor")
+        if im.dtype != torch.uint8:
+            raise SjpegError(f"encode_images_full: image {k} is {im.dtype}, not torch.uint8")
+        if im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+            raise SjpegError(f"encode_images_full: image {k} must be [H, W, 3] packed RGB (stride 1 over the channels, "
+                             f"3 over x)")
+        if dev is None:
+            dev = im.device
+        elif im.device != dev:
+            raise SjpegError(f"encode_images_full: image {k} is on {im.device}, image 0 on {dev}")
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    eng = engine or Engine(dev.index or 0)
+    search = None
+    if target is not None:
+        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
+        if len(ts) != n:
+            raise SjpegError("encode_images_full: one target per image")
+        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
+        search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+    with torch.cuda.device(dev):
+        if packed:
+            return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method, min_quant, q_bias,
+                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src")
+        out, sizes, offs, _, _, _ = eng.encode_ragged_full(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                                           min_quant, q_bias, dmax_luma, dmax_chroma, search)
+        eng.wait()                               # (pipelined mode: the output is complete after this)
+        return _fetch_ragged(out, sizes, offs)
+
+
 def _quality_quant(qs):
     """The starting matrices of the qualities qs: one [2][64] matrix when they are all equal, else a list."""
     made = {}
@@ -1539,7 +1667,8 @@ def _first_pool(dims, yuv_mode):
     return max(total, 65536)
 
 
-def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search):
+def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                          symbol="sjpeg_hip_encode_ragged_packed_src"):
     """encode_images through the packed call: a small first pool, one copy of sizes and offsets, one of the pool; the
     pictures a full pool dropped go through a second packed call whose pool is the sum of their bounds."""
     import torch
@@ -1553,7 +1682,8 @@ def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant,
         out, meta, _, _, _ = eng._encode_ragged_packed(
             SRC_RGB, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
             [quant[k] for k in which] if isinstance(quant, list) else quant, method, min_quant, q_bias, dmax_luma,
-            dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None)
+            dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None,
+            symbol)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         meta = meta.cpu().numpy()                # sizes and offsets together
         sz, off, end = meta[:m], meta[m:2 * m], int(meta[2 * m])

@@ -97,4 +97,40 @@ int adapt_ragged(const uint32_t* d_hist, const uint8_t* d_quant_in, int n, const
                  int qdelta_max_luma, int qdelta_max_chroma, int64_t* d_sums, int32_t* d_totlast, uint8_t* d_quant_out,
                  hipStream_t st);
 
+
+// ---- the search with any sampling and with the trellis (ragged_full.cc: sjpeg_hip_encode_ragged_full_src) and what it
+// takes from the engine (scan_engine.hip)
+// the unsearched flow of a SjpegYUVMode and method 0..8 (sjpeg_hip_encode_ragged_auto_src / _trellis_src), with a sink
+int ragged_unsearched_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
+                           const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                           int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, int* modes, void* stream,
+                           const PackedSink* sink);
+// a mode group of a call: frames of one source format and sampling (the sharp frames: planar 4:2:0 in engine scratch)
+struct ModeGroup {
+  int format = 0, yuv_mode = 0;                   // SJPEG_HIP_SRC_*, SJPEG_HIP_YUV*
+  std::vector<sjpeg_hip_ragged_frame> frames;
+  std::vector<int> index;                         // the caller's number of each frame
+};
+// the method 0..6 flow of sjpeg_hip_encode_ragged_batch_src over several groups at once (every pass over all groups, then
+// its one wait); quant[index], d_sizes[index]
+int ragged_groups_flow(sjpeg_hip_engine* e, const std::string& who, const std::vector<ModeGroup>& groups,
+                       const uint8_t (*quant)[2][64], const uint8_t* min_quant, int q_bias, int method, int qdelta_max_luma,
+                       int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, void* stream, const PackedSink* sink);
+// the engine's kept blocks (kKeptSegWords a segment) for `segs` segments; its arena (the sharp planes); the counters of
+// sjpeg_hip_engine_search_stats; the packed cursor zeroed on the stream
+int engine_kept_blocks(sjpeg_hip_engine* e, size_t segs);
+int engine_arena(sjpeg_hip_engine* e, size_t bytes, uint8_t** p);
+uint64_t* engine_full_stats(sjpeg_hip_engine* e);
+int engine_pack_begin(sjpeg_hip_engine* e, void* stream);
+// the trellis statistics of frames[0, n) with tables[f] (SJPEG_HIP_QUANT_TRELLIS; trellis_len: the frame's rate table):
+// d_freq[n][2][272]; frame f's quantized blocks stay kept_base[f] segments into the engine's kept blocks
+int trellis_stats_ragged(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
+                         const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, const uint32_t* kept_base,
+                         uint32_t* d_freq, hipStream_t st);
+// ... and the encode that replays them with tables[f]'s codes (complete JPEGs: headers, EOI)
+int replay_encode_ragged(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
+                         const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, const uint32_t* kept_base,
+                         const void* headers, const size_t* header_offsets, void* d_out, uint64_t* d_sizes, hipStream_t st,
+                         const PackedSink* sink);
+
 }  // namespace sjpeg_internal

@@ -110,15 +110,18 @@ struct alignas(16) RaggedFrame {
   // histogram launches (kKindHistoRagged) count persistent groups where the others count segments: seg_base is the
   // frame's first group (and partial), hgroups how many it has -- its stride over its segments
   uint32_t hgroups;
+  // the kinds that keep or replay quantized blocks (kKindStatsTrellisRagged, kKindEncodeReplayRagged): the frame's first
+  // kept segment, counted from the launch's `replay` -- a place of its own, whichever frames a launch covers
+  uint32_t kept_base;
 };
-static_assert(sizeof(RaggedFrame) == 144, "RaggedFrame: hgroups lies in what was the padding");
+static_assert(sizeof(RaggedFrame) == 144, "RaggedFrame: hgroups and kept_base lie in what was the padding");
 
 // K1's view of the frame a ragged workgroup codes: ScanArgs with the frame's own geometry and planes, every scratch
 // pointer moved to the frame's base -- the kernel then runs as frame 0 of a uniform launch.  Two dependent scalar loads
 // (map, then descriptor) per workgroup; *seg = the segment inside the frame.  partial_words: words of the per-segment
 // partial (the statistics kind: kStatsWords; 0: the partials stay where they are).  kept: the launch keeps or replays
-// quantized blocks (kKindStatsTrellisRagged, kKindEncodeReplayRagged) -- `replay` moves to the frame's first segment too,
-// kKeptSegWords a segment.
+// quantized blocks (kKindStatsTrellisRagged, kKindEncodeReplayRagged) -- `replay` moves to the frame's kept_base,
+// kKeptSegWords a segment: one more field of the descriptor the workgroup loads anyway, wave-uniform.
 constexpr size_t kKeptSegWords = static_cast<size_t>(kScanThreads) * 36;      // 9 rows of 16 bytes per thread: 36 864 bytes
 __device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* seg, int partial_words = 0, bool kept = false) {
   const uint32_t f = in.rmap[blockIdx.x];
@@ -135,7 +138,7 @@ __device__ __forceinline__ ScanArgs ragged_scan_view(const ScanArgs& in, int* se
   v.pool_ctr = in.pool_ctr + 2 * f;
   *seg = static_cast<int>(blockIdx.x - d.seg_base);
   if (partial_words != 0) v.partial = in.partial + static_cast<size_t>(d.seg_base) * partial_words;
-  if (kept) v.replay = in.replay + static_cast<size_t>(d.seg_base) * kKeptSegWords;
+  if (kept) v.replay = in.replay + static_cast<size_t>(d.kept_base) * kKeptSegWords;
   return v;
 }
 

@@ -235,6 +235,8 @@ struct sjpeg_hip_engine {
   // packed output of a ragged call (sjpeg_hip_encode_ragged_packed_src): where the next frame starts -- zeroed once by
   // the call, advanced by place_ragged_frames of every launch, group and part of it (bit 63: a frame was dropped)
   DevBuf<unsigned long long> pack_cursor;
+  // what the most recent sjpeg_hip_encode_ragged_full_*_src call cost (sjpeg_hip_engine_search_stats): host values
+  uint64_t full_stats[6] = {0, 0, 0, 0, 0, 0};
   // side_done is recorded LAZILY, by whoever is about to wait on it (side_mark): an event record is a packet in the
   // queue and about 5 us of host time, and a loop of pipelined calls needs none -- one frame per call was bound by the
   // HOST at five event calls per call (36-46 us against 35 of device time, `tools/one_frame_piped.py`)
@@ -1410,7 +1412,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
                   hipStream_t st, unsigned long long* d_bits, uint32_t* kept = nullptr,
-                  const sjpeg_internal::PackedSink* sink = nullptr);
+                  const sjpeg_internal::PackedSink* sink = nullptr, const uint32_t* kept_base = nullptr);
 
 }  // namespace
 
@@ -1464,8 +1466,9 @@ namespace {
 // The ragged encode of checked frames (ragged_frames, ragged_format): K1 kKindEncodeRagged, K2 .. K5.  d_bits != NULL:
 // a count without output (sjpeg_hip_scan_counted_bits_ragged_src) -- K1 .. K3, then counted_bits_ragged instead of
 // K4 and K5, no header, nothing written to d_out or d_sizes; the frames' out_capacity plans the segment scratch only.
-// kept != NULL: K1 is kKindEncodeReplayRagged -- it codes the blocks a trellis statistics pass over the same frames left
-// at `kept` (ragged_analysis, kPassStatsTrellis: kKeptSegWords a segment, in the order of the frames) and reads no pixel.
+// kept != NULL: K1 is kKindEncodeReplayRagged -- it codes the blocks a trellis statistics pass left at `kept` and reads no
+// pixel; frame f's lie kept_base[f] segments behind `kept`, kKeptSegWords a segment (ragged_analysis, kPassStatsTrellis:
+// the same table, so a frame's blocks have one place whichever frames a launch covers).
 // sink != NULL: packed output -- d_out and the frames' out_offset are not used; per launch K4 leaves the sizes only,
 // place_ragged_frames puts the launch's frames behind the engine's cursor (each start into its descriptor, where K5
 // takes it from, and into the caller's offsets), pack_ragged_edges writes header, EOI and padding (stitch_kernels.h).
@@ -1473,8 +1476,10 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
-                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept, const sjpeg_internal::PackedSink* sink) {
+                  hipStream_t st, unsigned long long* d_bits, uint32_t* kept, const sjpeg_internal::PackedSink* sink,
+                  const uint32_t* kept_base) {
   const int ntab = tables_per_frame ? nframes : 1;
+  if (kept != nullptr && kept_base == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: the ragged replay takes its frames' kept bases");
   if (sink != nullptr && (d_bits != nullptr || d_sizes == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: packed output needs the sizes");
   std::vector<SegPlan> plan(nframes);
   std::vector<uint32_t> max_chunks(nframes);
@@ -1554,6 +1559,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
       d.chunk_base = chunk; d.max_chunks = max_chunks[f];
       d.out_offset = fr.out_offset; d.out_capacity = fr.out_capacity;
       d.place_base = place;
+      d.kept_base = kept != nullptr ? kept_base[f] : 0u;
       d.stuff_base = stuff; d.stuff_wgs = std::min(gx, max_chunks[f]);
       const uint32_t fl = static_cast<uint32_t>(f - l.f0);
       for (int k = 0; k < g.nseg; ++k) maps[l.k1_map + seg + k] = fl;
@@ -1608,7 +1614,6 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
   e->ctr_clean_at[0] = e->ctr_clean_at[1] = nullptr;   // (the pool counters are this call's now; its K2s leave them at zero)
   e->last_nseg = e->last_nframes = 0;                  // (sjpeg_hip_engine_entropy_bits: not after a ragged call)
   if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
-  size_t segs_before = 0;                              // segments of the call's frames in front of the launch's (kept blocks)
   for (size_t li = 0; li < launches.size(); ++li) {
     const RaggedLaunch& l = launches[li];
     HIP_TRY(hipMemsetAsync(e->pool_ctr.p, 0, static_cast<size_t>(l.nf) * 2 * sizeof(uint32_t), st));
@@ -1621,9 +1626,8 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
     a.rframes = reinterpret_cast<const RaggedFrame*>(db) + l.f0;
     a.rmap = dmaps + l.k1_map;
     if (kept != nullptr) {
-      a.replay = kept + segs_before * kKeptSegWords;
+      a.replay = kept;                                 // (every frame's own place: RaggedFrame::kept_base)
       rc = launch_scan_src<kKindEncodeReplayRagged, kSrcRgb24>(yuv_mode, dim3(l.segs), st, a);   // (reads no pixel)
-      segs_before += l.segs;
     } else {
       rc = launch_scan<kKindEncodeRagged>(yuv_mode, cls, dim3(l.segs), st, a);
     }
@@ -1694,14 +1698,14 @@ enum RaggedPass { kPassHisto, kPassStats, kPassError, kPassStatsTrellis };
 // the uniform pass makes of frame f alone.  The frames have been checked (ragged_frames); `a` holds the format's fields
 // (ragged_format).  The partials of a launch stay inside the engine's scratch limit: a larger batch goes in several
 // launches over consecutive frames.  kPassStatsTrellis: the statistics with trellis quantization (kKindStatsTrellisRagged;
-// tables with SJPEG_HIP_QUANT_TRELLIS); its quantized blocks stay behind at `kept`, kKeptSegWords a segment in the order
-// of the frames, whatever the launches -- for ragged_encode to replay.
+// tables with SJPEG_HIP_QUANT_TRELLIS); its quantized blocks stay behind at `kept`, frame f's kept_base[f] segments in
+// (kKeptSegWords a segment), whatever the launches and whichever frames the call covers -- for ragged_encode to replay.
 int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
                     const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                     const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st,
-                    uint32_t* kept = nullptr) {
+                    uint32_t* kept = nullptr, const uint32_t* kept_base = nullptr) {
   const bool histogram = pass == kPassHisto, error = pass == kPassError, trellis = pass == kPassStatsTrellis;
-  if (trellis && kept == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: the ragged trellis statistics keep their blocks");
+  if (trellis && (kept == nullptr || kept_base == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: the ragged trellis statistics keep their blocks");
   // a partial: one group's / one segment's; a frame's result (words)
   const size_t part_words = histogram ? kHistoPartialWords : error ? 2 : kStatsWords;
   const int words = histogram ? 2 * 64 * 128 : error ? 2 : kStatsWords;
@@ -1758,6 +1762,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
       ragged_geometry(frames[f], geo[f], nplanes, &d);
       d.seg_base = base;                       // (the histogram: its first group -- and partial -- in the launch)
       d.hgroups = histogram ? units[f] : 0u;
+      d.kept_base = trellis ? kept_base[f] : 0u;
       for (uint32_t k = 0; k < units[f]; ++k) maps[l.map + base + k] = static_cast<uint32_t>(f - l.f0);
       base += units[f];
     }
@@ -1785,7 +1790,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
     if (histogram) rc = launch_scan<kKindHistoRagged>(yuv_mode, cls, dim3(l.units), st, a);
     else if (error) rc = launch_scan<kKindErrorRagged>(yuv_mode, cls, dim3(l.units), st, a);
     else if (trellis) {
-      a.replay = kept + l.map * kKeptSegWords;       // (a workgroup per segment: the launch's map starts at its first segment's number)
+      a.replay = kept;                               // (every frame's own place: RaggedFrame::kept_base)
       rc = launch_scan<kKindStatsTrellisRagged>(yuv_mode, cls, dim3(l.units), st, a);
     } else rc = launch_scan<kKindStatsRagged>(yuv_mode, cls, dim3(l.units), st, a);
     if (rc) return rc;
@@ -2020,6 +2025,49 @@ int engine_search_sizes(sjpeg_hip_engine* e, size_t n, uint64_t** d_sizes) {
   if (int rc = e->search_sizes.ensure(n)) return rc;
   *d_sizes = e->search_sizes.p;
   return 0;
+}
+
+uint64_t* engine_full_stats(sjpeg_hip_engine* e) { return e->full_stats; }
+
+int engine_kept_blocks(sjpeg_hip_engine* e, size_t segs) {
+  if (int rc = e->replay.ensure(segs * kKeptSegWords)) return rc;
+  e->replay_w = e->replay_h = e->replay_mode = e->replay_nframes = 0;      // (no uniform call's kept blocks any more)
+  return 0;
+}
+
+int engine_arena(sjpeg_hip_engine* e, size_t bytes, uint8_t** p) {
+  if (int rc = e->sharp_arena.ensure(bytes / 16 + 1)) return rc;
+  *p = reinterpret_cast<uint8_t*>(e->sharp_arena.p);
+  return 0;
+}
+
+int trellis_stats_ragged(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
+                         const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, const uint32_t* kept_base,
+                         uint32_t* d_freq, hipStream_t st) {
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &nplanes, &geo)) return rc;
+  for (int f = 0; f < nframes; ++f) {                // (the kept blocks of every frame lie inside the engine's buffer)
+    if ((static_cast<size_t>(kept_base[f]) + geo[f].nseg) * kKeptSegWords > e->replay.cap) return fail(SJPEG_HIP_EINVAL, who + ": internal: kept base past the kept blocks");
+  }
+  return ragged_analysis(e, kPassStatsTrellis, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, 1, d_freq, st, e->replay.p, kept_base);
+}
+
+int replay_encode_ragged(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
+                         const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, const uint32_t* kept_base,
+                         const void* headers, const size_t* header_offsets, void* d_out, uint64_t* d_sizes, hipStream_t st,
+                         const PackedSink* sink) {
+  ScanArgs a;
+  int cls = 0, nplanes = 0;
+  std::vector<FrameGeo> geo;
+  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
+  if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
+  for (int f = 0; f < nframes; ++f) {
+    if ((static_cast<size_t>(kept_base[f]) + geo[f].nseg) * kKeptSegWords > e->replay.cap) return fail(SJPEG_HIP_EINVAL, who + ": internal: kept base past the kept blocks");
+  }
+  return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, 1, headers, header_offsets, header_offsets[nframes],
+                       /*append_eoi=*/1, d_out, d_sizes, st, nullptr, e->replay.p, sink, kept_base);
 }
 
 // adapt_sums_kernel / adapt_decide_kernel over n consecutive frames, each from its own starting matrices
@@ -2724,15 +2772,14 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
   for (const RaggedGroup& g : groups) { gbase.push_back(n); n += g.frames.size(); }
   if (n == 0) return 0;
   // (trellis) the first kept segment of every group, and of every frame inside its group
-  std::vector<size_t> gkept;
-  std::vector<std::vector<size_t>> fkept(groups.size());
+  // (trellis) every frame's first kept segment: the prefix sums over the groups' frames, handed to the statistics and the
+  // replay through the one table both kinds address the kept blocks by
+  std::vector<std::vector<uint32_t>> fkept(groups.size());
   size_t kept_segs = 0;
   for (size_t gi = 0; trellis && gi < groups.size(); ++gi) {
-    gkept.push_back(kept_segs);
-    size_t at = 0;
-    for (const FrameGeo& fg : groups[gi].geo) { fkept[gi].push_back(at); at += static_cast<size_t>(fg.nseg); }
-    kept_segs += at;
+    for (const FrameGeo& fg : groups[gi].geo) { fkept[gi].push_back(static_cast<uint32_t>(kept_segs)); kept_segs += static_cast<size_t>(fg.nseg); }
   }
+  if (kept_segs > 0xffffffffull) return fail(SJPEG_HIP_EINVAL, who + ": too many segments for the kept blocks");
   bool last_made = !last_ready;
   auto ready = [&](size_t gi) -> int {
     if (last_made || gi + 1 != groups.size()) return 0;
@@ -2867,7 +2914,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
                                      g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      &tables[gbase[gi] + c.first], 1, d_freq, st,
-                                     trellis ? e->replay.p + (gkept[gi] + fkept[gi][c.first]) * kKeptSegWords : nullptr)) return rc;
+                                     trellis ? e->replay.p : nullptr, trellis ? &fkept[gi][c.first] : nullptr)) return rc;
         if (int rc = sc.ReadBack(st, h_freq + (gbase[gi] + c.first) * kFreq, d_freq, c.second * kFreq)) return rc;
       }
     }
@@ -2917,13 +2964,13 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       if (int rc = ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
                                  (trellis || !one_table) ? 1 : 0, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, nullptr,
                                  reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
-                                 trellis ? e->replay.p + gkept[gi] * kKeptSegWords : nullptr, &gs)) return rc;
+                                 trellis ? e->replay.p : nullptr, &gs, trellis ? fkept[gi].data() : nullptr)) return rc;
       continue;
     }
     const int rc = trellis ? ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
                                            1, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, d_out,
                                            reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
-                                           e->replay.p + gkept[gi] * kKeptSegWords)
+                                           e->replay.p, nullptr, fkept[gi].data())
                            : sjpeg_hip_encode_ragged_src(e, g.format, g.yuv_mode, static_cast<int>(ng), g.frames.data(), &tables[gbase[gi]],
                                                          one_table ? 0 : 1, headers.data(), offs.data(), /*append_eoi=*/1, d_out,
                                                          reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st);
@@ -3392,6 +3439,52 @@ int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* e, int format, int nfra
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
 }
+
+}  // extern "C"
+
+// what sjpeg_hip_encode_ragged_full_src (ragged_full.cc) takes from the flows above
+int sjpeg_internal::ragged_unsearched_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64], int quant_per_frame,
+                                           const uint8_t* min_quant, int q_bias, int method, int qdelta_max_luma,
+                                           int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, int* modes, void* stream,
+                                           const PackedSink* sink) {
+  return (method == 7 || method == 8 ? ragged_trellis_flow : ragged_auto_flow)(e, format, yuv_mode, nframes, frames, quant, quant_per_frame,
+                                                                              min_quant, q_bias, method, qdelta_max_luma,
+                                                                              qdelta_max_chroma, d_out, d_sizes, modes, stream, sink);
+}
+
+int sjpeg_internal::ragged_groups_flow(sjpeg_hip_engine* e, const std::string& who, const std::vector<ModeGroup>& mode_groups,
+                                       const uint8_t (*quant)[2][64], const uint8_t* min_quant, int q_bias, int method,
+                                       int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, void* stream,
+                                       const PackedSink* sink) {
+  try {
+    std::vector<RaggedGroup> groups;
+    for (const ModeGroup& m : mode_groups) {
+      if (m.frames.empty()) continue;
+      RaggedGroup g;
+      g.format = m.format; g.yuv_mode = m.yuv_mode; g.frames = m.frames; g.index = m.index;
+      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
+      if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
+      groups.push_back(std::move(g));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = ragged_ordered(e, st)) return rc;
+    return ragged_batch_groups(e, who, groups, quant, 1, min_quant, q_bias, method, qdelta_max_luma, qdelta_max_chroma, d_out,
+                               d_sizes, st, {}, sink);
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+int sjpeg_internal::engine_pack_begin(sjpeg_hip_engine* e, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ragged_ordered(e, st)) return rc;
+  if (int rc = e->pack_cursor.ensure(1)) return rc;
+  HIP_TRY(hipMemsetAsync(e->pack_cursor.p, 0, sizeof(unsigned long long), st));
+  return 0;
+}
+
+extern "C" {
 
 // ---- exchange step of the multi-device batch path: the coded frames of one call, back to back ----
 // (BASELINE.json config #4; the reference is single-threaded and has no counterpart.)  One

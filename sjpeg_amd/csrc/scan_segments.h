@@ -35,7 +35,7 @@ enum { kKindEncode = 0, kKindTap = 1, kKindHisto = 2, kKindStats = 3, kKindError
        kKindHistoRagged = 10, kKindStatsRagged = 11,      // the histogram and statistics kinds over such frames
        kKindErrorRagged = 12,     // ... and the quantization-error kind (one 64-bit partial per segment)
        kKindStatsTrellisRagged = 13,     // the trellis statistics kind over such frames: its blocks stay behind ...
-       kKindEncodeReplayRagged = 14 };   // ... for the replay kind over the same frames (kept blocks at the frame's seg_base)
+       kKindEncodeReplayRagged = 14 };   // ... for the replay kind over the same frames (kept blocks at the frame's kept_base)
 constexpr int kHistoWords = 2 * 64 * 32;          // words of u8 counters [2][64][128] a workgroup bins one segment into (LDS)
 // The histogram kind is PERSISTENT: a workgroup bins the segments seg, seg + gridDim.x, ... of its frame and leaves ONE
 // partial behind -- 16-bit counters, two words per word of 8-bit ones (scan_reduce.h reduce_partials16).  (The ragged
