@@ -101,8 +101,18 @@ enum {
   SJPEG_HIP_SRC_YUV444 = 4,    /* 3 full-size planes      -> 444 */
   SJPEG_HIP_SRC_YUV420 = 5,    /* Y + subsampled U, V     -> 420 */
   SJPEG_HIP_SRC_NV12 = 6,      /* Y + interleaved U,V     -> 420 */
-  SJPEG_HIP_SRC_NV21 = 7       /* Y + interleaved V,U     -> 420 */
+  SJPEG_HIP_SRC_NV21 = 7,      /* Y + interleaved V,U     -> 420 */
+  SJPEG_HIP_SRC_RGB_PLANAR = 8 /* 3 full-size planes R,G,B -> any of 420 / 444 / 400 */
 };
+/* SJPEG_HIP_SRC_RGB_PLANAR (channel-first pictures: a [3, H, W] or [N, 3, H, W] array, or any crop of one):
+ * plane[0..2] are R, G, B, each width x height bytes; the bytes produced are those of the same pixels handed over
+ * as SJPEG_HIP_SRC_RGB.  ONE PITCH, THREE BASES: row_stride[1] and row_stride[2] must equal row_stride[0] (and, in a
+ * sjpeg_hip_source, frame_stride[1] and frame_stride[2] must equal frame_stride[0]); |row_stride| >= width; negative
+ * strides work as for every other layout.  A mismatch is SJPEG_HIP_EINVAL -- the message names the stride and, in
+ * ragged calls, the frame.  The rule lets the three planes share one per-thread offset: the kernels address
+ * G and B as R's address plus a uniform 64-bit distance, plane[1] - plane[0] and plane[2] - plane[0].
+ * Taken by every entry point that takes a `format` or a sjpeg_hip_source, SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, the
+ * riskiness and the sharp conversion included (there it counts as an RGB source beside RGB, BGRA and RGBA). */
 typedef struct sjpeg_hip_source {
   int32_t format;              /* SJPEG_HIP_SRC_* */
   int32_t reserved;            /* 0 */
@@ -226,7 +236,7 @@ int sjpeg_hip_engine_entropy_bits(sjpeg_hip_engine* engine, uint64_t* bits, int 
 
 /* ---- SJPEG_YUV_SHARP: the iterative sharp RGB -> YUV 4:2:0 conversion -----------------------------
  * Replaces sjpeg::ApplySharpYUVConversion (src/yuv_convert.cc:674-697; the pre-pass of
- * EncoderSharp420, src/encoders.cc:512-541).  `src` is packed RGB / BGRA / RGBA in device memory;
+ * EncoderSharp420, src/encoders.cc:512-541).  `src` is packed RGB / BGRA / RGBA or planar RGB in device memory;
  * the result is three tightly packed 8-bit planes per frame: Y width x height, U and V
  * ((width+1)/2) x ((height+1)/2), frames y_frame_stride / uv_frame_stride bytes apart -- exactly
  * what a SJPEG_HIP_SRC_YUV420 source of sjpeg_hip_encode_scan_src() then takes.  The row pairs of
@@ -429,7 +439,7 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* engine, int format, int 
 
 /* ---- ragged batches with the reference's SJPEG_YUV_AUTO decision and the sharp conversion ----
  * sjpeg_hip_riskiness_ragged_src: d_sums[nframes][3] (device), frame f's what sjpeg_hip_riskiness_sums() makes of that
- *   picture alone (all zero for a 1 x N or N x 1 frame).  format: RGB, BGRA or RGBA; frames[] as above, out_offset /
+ *   picture alone (all zero for a 1 x N or N x 1 frame).  format: RGB, BGRA, RGBA or planar RGB; frames[] as above, out_offset /
  *   out_capacity ignored; any row stride, negative ones too.  d_table: the 117649-byte table in device memory, or NULL:
  *   the table SjpegRiskiness() uses (installed, SJPEG_HIP_RISKINESS_TABLE, riskiness.bin beside the library; the
  *   engine keeps a device copy).  Asynchronous on `stream`.
@@ -444,7 +454,7 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* engine, int format, int 
  *   SJPEG_YUV_AUTO (0): the riskiness of every frame decides its mode (420, sharp 420, 444 or 400), as
  *   SjpegEncode(..., SJPEG_YUV_AUTO) decides it for that picture alone; SJPEG_YUV_SHARP (2): every frame goes through
  *   the sharp conversion; 1, 3, 4 (= SJPEG_HIP_YUV420 / 444 / 400): exactly sjpeg_hip_encode_ragged_batch_src().
- *   AUTO and SHARP take RGB, BGRA or RGBA sources.  modes[f] (host, or NULL): the SjpegYUVMode frame f was coded with.
+ *   AUTO and SHARP take RGB, BGRA, RGBA or planar RGB sources.  modes[f] (host, or NULL): the SjpegYUVMode frame f was coded with.
  *   Frame f's bytes are what SjpegEncode(picture, q, method, yuv_mode) makes of it alone; d_sizes[f] and the output
  *   ranges are in the caller's frame order; sjpeg_hip_frame_bound(w, h, SJPEG_HIP_YUV444, 2048) is always enough.
  *   Host waits: the riskiness sums (AUTO only), then those of sjpeg_hip_encode_ragged_batch_src() once over all modes.
@@ -472,7 +482,8 @@ int sjpeg_hip_encode_ragged_auto_src(sjpeg_hip_engine* engine, int format, int y
 /* ---- ragged batches with trellis quantization: the reference's methods 7 (= 4 + trellis) and 8 (= 6 + trellis) ----
  * sjpeg_hip_encode_ragged_trellis_src: the arguments, output contract and host waits of
  *   sjpeg_hip_encode_ragged_auto_src(); frame f's bytes are what SjpegEncode(picture, q, method, yuv_mode) makes of it
- *   alone.  yuv_mode 1 / 3 / 4 with any source layout; 0 (SJPEG_YUV_AUTO) and 2 (SJPEG_YUV_SHARP) with RGB, BGRA or RGBA.
+ *   alone.  yuv_mode 1 / 3 / 4 with any source layout; 0 (SJPEG_YUV_AUTO) and 2 (SJPEG_YUV_SHARP) with RGB, BGRA or RGBA
+ *   (packed) or planar RGB.
  *   The flow per picture is Encoder::Encode's (src/enc.cc:121-129, 323-372): histogram and adapted matrices, then ONE
  *   trellis quantization (src/quantize.cc:325-457) in the statistics pass, its rate priced with the standard AC code
  *   lengths, then the optimised codes and an encode pass that REPLAYS the quantized blocks the statistics pass kept --
@@ -628,7 +639,8 @@ int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* engine, int format, int
  *     covers; the replay covers all trellis frames of a group in one launch.  The kept histograms, the sharp planes and
  *     workspace and the kept blocks count against SJPEG_HIP_SCRATCH_LIMIT_BYTES: past it the call goes in parts of
  *     consecutive searched frames, each a complete search.
- *   AUTO and SHARP take RGB, BGRA or RGBA sources.  SJPEG_HIP_EINVAL (the message names the argument or the frame): a
+ *   AUTO and SHARP take RGB, BGRA or RGBA (packed) or planar RGB sources.
+ *   SJPEG_HIP_EINVAL (the message names the argument or the frame): a
  *   NULL engine, params, frames, d_out, d_sizes or params->quant; nframes outside 1..65535; yuv_mode outside 0..4; method
  *   outside 0..8; qdelta_max outside -12..12; a target_mode other than 1 or 2 or a non-finite target_value in any search
  *   entry; and every frame check of sjpeg_hip_encode_ragged_src.  No per-picture metadata, no restart markers.

@@ -40,6 +40,7 @@ RESTART_MARKERS = 8      # optional restart-marker mode (sjpeg_hip.h): not the r
 
 
 SRC_RGB, SRC_BGRA, SRC_RGBA, SRC_GRAY, SRC_YUV444, SRC_YUV420, SRC_NV12, SRC_NV21 = range(8)
+SRC_RGB_PLANAR = 8       # R, G and B planes of one pitch (channel-first pictures): sjpeg_hip.h
 _IMPLIED_MODE = {SRC_GRAY: YUV_400, SRC_YUV444: YUV_444, SRC_YUV420: YUV_420, SRC_NV12: YUV_420,
                  SRC_NV21: YUV_420}
 
@@ -93,13 +94,20 @@ def band_bound(w, h, yuv_mode, seg_begin, seg_end):
 
 def make_source(fmt, planes):
     """planes: CUDA uint8 tensors [F, rows, row_bytes] (one per plane of the layout).
-    Returns (Source, nframes); the tensors must outlive the calls that use it."""
+    Returns (Source, nframes); the tensors must outlive the calls that use it.
+    SRC_RGB_PLANAR: planes = (R, G, B), the [N, H, W] views x[:, 0], x[:, 1], x[:, 2] of an [N, 3, H, W] tensor (or of
+    any crop of one): the three share their row and frame strides.
+    With that layout a dimension of size 1 is never stepped over, so whatever stride torch reports for it is not looked
+    at: a one-pixel-wide plane passes with any stride(2), and a one-row plane is handed over with its width as the row
+    stride (the views of a 1 x 1 batch made from a transposed array report such strides).  The other layouts are
+    checked and handed over as they always were."""
     s = Source()
     s.format = fmt
+    planar = fmt == SRC_RGB_PLANAR
     for i, t in enumerate(planes):
-        assert t.is_cuda and t.dim() == 3 and t.stride(2) == 1
+        assert t.is_cuda and t.dim() == 3 and (t.stride(2) == 1 or (planar and t.shape[2] == 1))
         s.plane[i] = t.data_ptr()
-        s.row_stride[i] = t.stride(1)
+        s.row_stride[i] = t.shape[2] if planar and t.shape[1] == 1 else t.stride(1)
         s.frame_stride[i] = t.stride(0)
     return s, planes[0].shape[0]
 
@@ -1413,9 +1421,41 @@ def _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes):
     return frames, out, sizes, offsets
 
 
+def _check_layout(who, layout):
+    if layout not in ("hwc", "chw"):
+        raise SjpegError(f"{who}: layout {layout!r} is not 'hwc' ([H, W, 3]) or 'chw' ([3, H, W])")
+    return layout == "chw"
+
+
+def _chw_planes(who, images):
+    """The planes, dims and device of a layout="chw" call: every image a CUDA uint8 tensor [3, H, W] with stride 1 over
+    x (any row stride: crops of a larger tensor work) -- SRC_RGB_PLANAR, its R, G and B planes im[0], im[1], im[2]."""
+    import torch
+    dev = None
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda:
+            raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
+        if im.dtype != torch.uint8:
+            raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
+        if im.dim() != 3 or im.shape[0] != 3 or im.shape[1] < 1 or im.shape[2] < 1 or \
+                (im.stride(2) != 1 and im.shape[2] > 1):
+            raise SjpegError(f"{who}: image {k} must be [3, H, W] planar RGB with layout='chw' (stride 1 over x; its "
+                             f"shape is {tuple(im.shape)}, its strides {tuple(im.stride())})")
+        if dev is None:
+            dev = im.device
+        elif im.device != dev:
+            raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {dev}")
+    # ((address, row stride) pairs; torch reports any stride for a dimension of size 1, so a one-pixel-wide picture
+    # passes with any stride(2), and a one-row picture is handed over with its width as the row stride)
+    planes = [[(im.data_ptr() + c * im.stride(0), im.stride(1) if im.shape[1] > 1 else im.shape[2])
+               for c in range(3)] for im in images]
+    dims = [(int(im.shape[2]), int(im.shape[1])) for im in images]
+    return planes, dims, dev
+
+
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
                   dmax_luma=12, dmax_chroma=1, target_size=None, target_psnr=None, passes=10, tolerance=1.0, qmin=0.0,
-                  qmax=100.0, use_trellis=False, packed=False):
+                  qmax=100.0, use_trellis=False, packed=False, layout="hwc"):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
     quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
@@ -1438,8 +1478,14 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     ONE device-to-host copy of it instead of one per picture.  The first pool is small (per picture 2048 bytes of
     header allowance plus half a byte per sample, at least 64 KiB for the call); the pictures a full pool dropped are
     coded again in a second packed call whose pool always fits (packed_stats() counts those).  The default keeps the
-    unpacked path."""
+    unpacked path.
+
+    layout="chw": every image is a CUDA uint8 tensor [3, H_k, W_k] instead -- channel-first, as torch stores pictures --
+    with stride 1 over x and any row stride (a crop of a larger tensor works); the pictures go in as SRC_RGB_PLANAR,
+    without a repack, and the bytes are those of the same pixels handed over as [H, W, 3].  A call has one layout; the
+    keyword is explicit because [3, W, 3] is both."""
     import torch
+    chw = _check_layout("encode_images", layout)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
     target = target_size if target_size is not None else target_psnr
@@ -1466,7 +1512,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     images = list(images)
     if not images:
         raise SjpegError("encode_images: no images")
-    if yuv_mode in (YUV_AUTO, YUV_SHARP):
+    if yuv_mode in (YUV_AUTO, YUV_SHARP) and not chw:
         for k, im in enumerate(images):
             if len(getattr(im, "shape", ())) != 3 or im.shape[2] != 3:
                 raise SjpegError(f"encode_images: image {k}: YUV_AUTO and YUV_SHARP take RGB pictures [H, W, 3]")
@@ -1475,7 +1521,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     if len(qs) != n:
         raise SjpegError("encode_images: one quality per image")
     dev = None
-    for k, im in enumerate(images):
+    for k, im in enumerate(() if chw else images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"encode_images: image {k} is not a CUDA tensor")
         if im.dtype != torch.uint8:
@@ -1487,8 +1533,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             dev = im.device
         elif im.device != dev:
             raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
-    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    fmt = SRC_RGB_PLANAR if chw else SRC_RGB
+    if chw:
+        planes, dims, dev = _chw_planes("encode_images", images)
+    else:
+        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
     search = None
     if target is not None:
@@ -1504,29 +1554,29 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
         with torch.cuda.device(dev):
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method,
                                          None if plain0 else min_quant, 0x78 if plain0 else q_bias,
-                                         dmax_luma, dmax_chroma, search)
+                                         dmax_luma, dmax_chroma, search, fmt=fmt)
     if target is not None:
         with torch.cuda.device(dev):
-            out, sizes, offs, _, _ = eng.encode_ragged_search(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs),
+            out, sizes, offs, _, _ = eng.encode_ragged_search(fmt, planes, dims, yuv_mode, _quality_quant(qs),
                                                               search, method, min_quant, q_bias, dmax_luma,
                                                               dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
     if method >= 7:
         with torch.cuda.device(dev):
-            out, sizes, offs, _ = eng.encode_ragged_trellis(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+            out, sizes, offs, _ = eng.encode_ragged_trellis(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
                                                             min_quant, q_bias, dmax_luma, dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
     if yuv_mode in (YUV_AUTO, YUV_SHARP):
         with torch.cuda.device(dev):
-            out, sizes, offs, _ = eng.encode_ragged_auto(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+            out, sizes, offs, _ = eng.encode_ragged_auto(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
                                                          min_quant, q_bias, dmax_luma, dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
     if method != 0:
         with torch.cuda.device(dev):
-            out, sizes, offs = eng.encode_ragged_batch(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+            out, sizes, offs = eng.encode_ragged_batch(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
                                                        min_quant, q_bias, dmax_luma, dmax_chroma)
             eng.wait()                           # (pipelined mode: the output is complete after this)
             return _fetch_ragged(out, sizes, offs)
@@ -1538,10 +1588,10 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             made[q] = make_tables(quality=q)
         t, qm = made[q]
         tables.append(t)
-        headers.append(make_header(int(im.shape[1]), int(im.shape[0]), yuv_mode, qm))
+        headers.append(make_header(dims[k][0], dims[k][1], yuv_mode, qm))
     per_frame = len(made) > 1
     with torch.cuda.device(dev):
-        out, sizes, offs = eng.encode_ragged(SRC_RGB, planes, dims, yuv_mode, tables if per_frame else tables[0],
+        out, sizes, offs = eng.encode_ragged(fmt, planes, dims, yuv_mode, tables if per_frame else tables[0],
                                              headers)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return _fetch_ragged(out, sizes, offs)
@@ -1556,8 +1606,27 @@ def encode_images_full(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_tr
     method 4.  use_trellis maps method 4 to 7 and 6 to 8 (src/api.cc:155-157).  target_size (bytes) or target_psnr (dB),
     one value or one per image, at most one of the two: the multi-pass search per picture with passes / tolerance /
     qmin / qmax -- with YUV_AUTO, YUV_SHARP and the trellis too, which encode_images refuses.  packed=True: through
-    Engine.encode_ragged_full_packed and the two-pool scheme of encode_images (packed_stats() counts it)."""
+    Engine.encode_ragged_full_packed and the two-pool scheme of encode_images (packed_stats() counts it).
+    Channel-first pictures [3, H_k, W_k]: encode_images_full_chw, the same call with layout="chw" of encode_images (this
+    function's parameter list is pinned as it is)."""
+    return _encode_images_full("hwc", images, quality, yuv_mode, method, use_trellis, target_size, target_psnr, passes,
+                               tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed)
+
+
+def encode_images_full_chw(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_trellis=False, target_size=None,
+                           target_psnr=None, passes=10, tolerance=1.0, qmin=0.0, qmax=100.0, min_quant=None, q_bias=0x78,
+                           dmax_luma=12, dmax_chroma=1, engine=None, packed=False):
+    """encode_images_full of channel-first pictures: every image a CUDA uint8 tensor [3, H_k, W_k] with stride 1 over x
+    and any row stride, as encode_images(layout="chw") takes them -- SRC_RGB_PLANAR, no repack; the bytes are those of
+    the same pixels handed to encode_images_full as [H, W, 3]."""
+    return _encode_images_full("chw", images, quality, yuv_mode, method, use_trellis, target_size, target_psnr, passes,
+                               tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed)
+
+
+def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, target_size, target_psnr, passes,
+                        tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed):
     import torch
+    chw = _check_layout("encode_images_full", layout)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
     target = target_size if target_size is not None else target_psnr
@@ -1577,7 +1646,7 @@ def encode_images_full(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_tr
     if len(qs) != n:
         raise SjpegError("encode_images_full: one quality per image")
     dev = None
-    for k, im in enumerate(images):
+    for k, im in enumerate(() if chw else images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"encode_images_full: image {k} is not a CUDA tensor")
         if im.dtype != torch.uint8:
@@ -1589,8 +1658,12 @@ def encode_images_full(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_tr
             dev = im.device
         elif im.device != dev:
             raise SjpegError(f"encode_images_full: image {k} is on {im.device}, image 0 on {dev}")
-    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    fmt = SRC_RGB_PLANAR if chw else SRC_RGB
+    if chw:
+        planes, dims, dev = _chw_planes("encode_images_full", images)
+    else:
+        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
     search = None
     if target is not None:
@@ -1602,8 +1675,8 @@ def encode_images_full(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_tr
     with torch.cuda.device(dev):
         if packed:
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method, min_quant, q_bias,
-                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src")
-        out, sizes, offs, _, _, _ = eng.encode_ragged_full(SRC_RGB, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src", fmt=fmt)
+        out, sizes, offs, _, _, _ = eng.encode_ragged_full(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
                                                            min_quant, q_bias, dmax_luma, dmax_chroma, search)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return _fetch_ragged(out, sizes, offs)
@@ -1620,21 +1693,31 @@ def _quality_quant(qs):
     return [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
 
 
-def compress_images(images, quality=75.0, engine=None, use_trellis=False, packed=False):
+def compress_images(images, quality=75.0, engine=None, use_trellis=False, packed=False, layout="hwc"):
     """The batch SjpegCompress(): JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each
     what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call.  use_trellis=True: with
     EncoderParam::use_trellis, i.e. what SjpegEncode(picture, quality, 7, SJPEG_YUV_AUTO) makes of it.  packed=True:
-    through the packed call and one device-to-host copy, as encode_images."""
-    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis, packed=packed)
+    through the packed call and one device-to-host copy, as encode_images.  layout="chw": the pictures are
+    [3, H_k, W_k] instead, as encode_images takes them."""
+    return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis, packed=packed,
+                         layout=layout)
 
 
-def riskiness_images(images, engine=None):
+def riskiness_images(images, engine=None, layout="hwc"):
     """[(SjpegYUVMode, risk)] of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each what SjpegRiskiness says
-    of it alone, from one ragged riskiness call."""
+    of it alone, from one ragged riskiness call.  layout="chw": the pictures are [3, H_k, W_k] instead, as encode_images
+    takes them."""
     import torch
+    chw = _check_layout("riskiness_images", layout)
     images = list(images)
     if not images:
         raise SjpegError("riskiness_images: no images")
+    if chw:
+        planes, dims, dev = _chw_planes("riskiness_images", images)
+        eng = engine or Engine(dev.index or 0)
+        with torch.cuda.device(dev):
+            sums = eng.riskiness_ragged(SRC_RGB_PLANAR, planes, dims).cpu().numpy()
+        return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
                 im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
@@ -1668,7 +1751,7 @@ def _first_pool(dims, yuv_mode):
 
 
 def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                          symbol="sjpeg_hip_encode_ragged_packed_src"):
+                          symbol="sjpeg_hip_encode_ragged_packed_src", fmt=SRC_RGB):
     """encode_images through the packed call: a small first pool, one copy of sizes and offsets, one of the pool; the
     pictures a full pool dropped go through a second packed call whose pool is the sum of their bounds."""
     import torch
@@ -1680,7 +1763,7 @@ def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant,
     def run(which, pool):
         m = len(which)
         out, meta, _, _, _ = eng._encode_ragged_packed(
-            SRC_RGB, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
+            fmt, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
             [quant[k] for k in which] if isinstance(quant, list) else quant, method, min_quant, q_bias, dmax_luma,
             dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None,
             symbol)

@@ -12,15 +12,36 @@
 
 namespace sjpeg_internal {
 
-// the channel layout of a packed RGB / BGRA / RGBA source (the riskiness stencil and the sharp conversion start from
-// these); false for any other format
-inline bool rgb_layout(int format, int* pix_step, int* r_off, int* g_off, int* b_off) {
+// the channel layout of a packed RGB / BGRA / RGBA or planar RGB source (the riskiness stencil and the sharp conversion
+// start from these); false for any other format.  The offsets count from plane[0]: planar RGB is pix_step 1 with G and
+// B a whole plane away -- its g_off and b_off are the picture's own (rgb_frame_offsets), hence 64 bits.
+inline bool rgb_layout(int format, int* pix_step, long long* r_off, long long* g_off, long long* b_off) {
   switch (format) {
     case SJPEG_HIP_SRC_RGB: *pix_step = 3; *r_off = 0; *g_off = 1; *b_off = 2; return true;
     case SJPEG_HIP_SRC_BGRA: *pix_step = 4; *r_off = 2; *g_off = 1; *b_off = 0; return true;
     case SJPEG_HIP_SRC_RGBA: *pix_step = 4; *r_off = 0; *g_off = 1; *b_off = 2; return true;
+    case SJPEG_HIP_SRC_RGB_PLANAR: *pix_step = 1; *r_off = 0; *g_off = 0; *b_off = 0; return true;
     default: return false;
   }
+}
+// g_off and b_off of one picture (or of a uniform batch) of such a source: the layout's, or (planar RGB) the distances of
+// its G and B planes from its R plane
+inline void rgb_frame_offsets(int format, const void* const* plane, long long* g_off, long long* b_off) {
+  int step = 0;
+  long long r = 0;
+  if (!rgb_layout(format, &step, &r, g_off, b_off) || format != SJPEG_HIP_SRC_RGB_PLANAR) return;
+  *g_off = static_cast<const uint8_t*>(plane[1]) - static_cast<const uint8_t*>(plane[0]);
+  *b_off = static_cast<const uint8_t*>(plane[2]) - static_cast<const uint8_t*>(plane[0]);
+}
+// what is wrong with the planes of a planar RGB picture (one pitch, three bases: sjpeg_hip.h), or NULL;
+// frame_stride is NULL where the call has none (one picture of a ragged batch)
+inline const char* rgb_planar_fault(const void* const* plane, const int64_t* row_stride, const int64_t* frame_stride) {
+  if (plane[1] == nullptr || plane[2] == nullptr) return "null plane pointer";
+  if (row_stride[1] != row_stride[0]) return "row_stride[1] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
+  if (row_stride[2] != row_stride[0]) return "row_stride[2] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
+  if (frame_stride != nullptr && frame_stride[1] != frame_stride[0]) return "frame_stride[1] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
+  if (frame_stride != nullptr && frame_stride[2] != frame_stride[0]) return "frame_stride[2] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
+  return nullptr;
 }
 
 // ---- ragged riskiness: one descriptor per frame; a workgroup finds its frame by a binary search over wg_base
@@ -30,6 +51,7 @@ struct RiskFrame {
   int W, H;
   int bands, cols;                       // the frame's workgroups: cols x bands (none when W or H < 2)
   unsigned wg_base, pad;                 // its first workgroup in the flat grid
+  long long g_off, b_off;                // where G and B lie from R (rgb_frame_offsets)
 };
 
 // the frame's workgroups: bands of at least 16 rows, at most 64 of them; 256 columns each

@@ -22,7 +22,7 @@ constexpr int kNoiseLevel = 4;
 __device__ __forceinline__ uint32_t clip8(int v) { return v < 0 ? 0u : v > 255 ? 255u : static_cast<uint32_t>(v); }
 __device__ __forceinline__ uint32_t cell(uint32_t v) { return (v * (0x0101u * (kCells - 1))) >> 16; }   // ~ v * 6 / 255
 
-__device__ __forceinline__ int yuv_index(const uint8_t* p, int ro, int go, int bo) {   // colors_rgb.cc:1104-1112
+__device__ __forceinline__ int yuv_index(const uint8_t* p, long long ro, long long go, long long bo) {   // colors_rgb.cc:1104-1112
   const int r = p[ro], g = p[go], b = p[bo];
   const uint32_t y = cell(static_cast<uint32_t>((19595 * r + 38469 * g + 7471 * b + 32768) >> 16));
   const uint32_t u = cell(clip8(128 + ((-11059 * r - 21709 * g + 32768 * b + 32768) >> 16)));
@@ -33,7 +33,8 @@ __device__ __forceinline__ int yuv_index(const uint8_t* p, int ro, int go, int b
 struct RiskArgs {
   const uint8_t* rgb;
   long long row_stride, frame_stride;
-  int pix_step, r_off, g_off, b_off;
+  int pix_step;
+  long long r_off, g_off, b_off;                  // (64 bits: the planes of planar RGB lie anywhere)
   int W, H;
   const uint8_t* table;                           // [343 * 343]
   unsigned long long* out;                        // [nframes][3]: score_sum, score_num, gray_num
@@ -67,6 +68,7 @@ __global__ __launch_bounds__(256) void risk_scan_ragged(const RiskArgs common, c
   const sjpeg_internal::RiskFrame d = frames[lo];
   RiskArgs a = common;
   a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.g_off = d.g_off; a.b_off = d.b_off;
   a.W = d.W; a.H = d.H;
   a.out = common.out + static_cast<size_t>(lo) * 3;
   const unsigned local = wg - d.wg_base;
@@ -88,6 +90,12 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
   }
   RiskArgs a;
   if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
+  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
+    if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
+    const int64_t st_abs = src->row_stride[0] < 0 ? -src->row_stride[0] : src->row_stride[0];
+    if (st_abs < width) return SJPEG_HIP_EINVAL;
+    sjpeg_internal::rgb_frame_offsets(src->format, src->plane, &a.g_off, &a.b_off);
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   a.rgb = static_cast<const uint8_t*>(src->plane[0]);
   a.row_stride = src->row_stride[0]; a.frame_stride = src->frame_stride[0];

@@ -52,12 +52,16 @@ constexpr int kTablesA16 = 72, kTablesB16 = 216;      // uint4 per group
 static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 3456 + 512, "DevTables layout");
 
 // source classes the colour phase is specialised for
-enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2 };
+// (kSrcRgbPlanar: R, G and B planes of one pitch -- SJPEG_HIP_SRC_RGB_PLANAR; the others: one packed plane, or YUV planes)
+enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2, kSrcRgbPlanar = 3 };
+// raw dwords of a row of 8 pixels, and bytes between pixels of a row, of the classes the colour phase converts
+template <int SRC> constexpr int kSrcRowWords = (SRC == kSrcRgbx32) ? 8 : 6;
+template <int SRC> constexpr int kSrcPixelBytes = (SRC == kSrcRgb24) ? 3 : (SRC == kSrcRgbPlanar) ? 1 : 4;
 
 struct RaggedFrame;
 
 struct ScanArgs {
-  const uint8_t* plane[3];      // packed colour / gray: [0]; planar YUV: Y, U, V; NV12/NV21: Y, UV
+  const uint8_t* plane[3];      // packed colour / gray: [0]; planar YUV: Y, U, V; NV12/NV21: Y, UV; planar RGB: R, G, B
   long long row_stride[3], frame_stride[3];
   int rsh, bsh;                 // kSrcRgbx32: bit position of R and B inside a pixel dword (0 / 16)
   int cstep, uoff, voff;        // kSrcPlanes: bytes per chroma sample (2 = interleaved) and U/V offsets
@@ -554,12 +558,34 @@ __device__ __forceinline__ void load_row8(const uint8_t* frame, long long row_st
 }
 
 // Raw dwords of 8 consecutive pixels of row y (coordinates clamp to the picture): 6 dwords for
-// packed RGB, 8 for the 4-byte layouts.
+// packed RGB, 8 for the 4-byte layouts, 6 for planar RGB -- two of R, two of G, two of B.
+// (planar RGB: frame_px is the frame's R plane; G and B lie dg and db bytes from it, whichever the row -- the
+// planes share their pitch)
 template <int SRC>
 __device__ __forceinline__ void load_px8(const ScanArgs& a, const uint8_t* frame_px, int x0, int y,
-                                         bool inside, uint32_t* w) {
+                                         bool inside, uint32_t* w, long long dg = 0, long long db = 0) {
   if (SRC == kSrcRgb24) {
     load_row8(frame_px, a.row_stride[0], a.W, a.H, x0, y, inside, w);
+  } else if (SRC == kSrcRgbPlanar) {
+    if (inside) {
+      const uint8_t* p = frame_px + y * a.row_stride[0] + x0;
+      __builtin_memcpy(w, p, 8);
+      __builtin_memcpy(w + 2, p + dg, 8);
+      __builtin_memcpy(w + 4, p + db, 8);
+    } else {
+      const int yy = y < a.H ? y : a.H - 1;
+      const uint8_t* row = frame_px + yy * a.row_stride[0];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) w[k] = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int xx = (x0 + i) < a.W ? (x0 + i) : a.W - 1;
+        const uint8_t* p = row + xx;
+        w[i >> 2] |= static_cast<uint32_t>(p[0]) << (8 * (i & 3));
+        w[2 + (i >> 2)] |= static_cast<uint32_t>(p[dg]) << (8 * (i & 3));
+        w[4 + (i >> 2)] |= static_cast<uint32_t>(p[db]) << (8 * (i & 3));
+      }
+    }
   } else {
     // 4 bytes per pixel (BGRA / RGBA, alpha ignored: src/colors_rgb.cc:882-1025)
     if (inside) {
@@ -593,6 +619,18 @@ __device__ __forceinline__ void unpack_px8(const ScanArgs& a, const uint32_t* w,
       const int o = 6 * j + 2, d = o >> 2, sl = o & 3;              // b at bytes o and o + 3
       const uint32_t sel = sl | 0x0c00u | (static_cast<uint32_t>(sl + 3) << 16) | 0x0c000000u;
       bb[j] = __builtin_amdgcn_perm(w[d + 1 < 6 ? d + 1 : 5], w[d], sel);
+    }
+  } else if (SRC == kSrcRgbPlanar) {
+    // w[0..1]: eight bytes of R, w[2..3]: of G, w[4..5]: of B -- still one permute per register
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t sl = i & 3;                                     // r from the R dword, g from the G dword
+      rg[i] = __builtin_amdgcn_perm(w[2 + (i >> 2)], w[i >> 2], sl | 0x0c00u | ((4u + sl) << 16) | 0x0c000000u);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t sl = (2 * j) & 3;                               // b at bytes sl and sl + 1 of one B dword
+      bb[j] = __builtin_amdgcn_perm(0u, w[4 + (j >> 1)], sl | 0x0c00u | ((sl + 1u) << 16) | 0x0c000000u);
     }
   } else {
     const uint32_t rs = static_cast<uint32_t>(a.rsh) >> 3, bs = static_cast<uint32_t>(a.bsh) >> 3;

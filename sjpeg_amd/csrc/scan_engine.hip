@@ -321,6 +321,7 @@ int launch_scan(int mode, int src_class, dim3 grid, hipStream_t st, const ScanAr
   switch (src_class) {
     case kSrcRgb24: return launch_scan_src<KIND, kSrcRgb24>(mode, grid, st, a);
     case kSrcRgbx32: return launch_scan_src<KIND, kSrcRgbx32>(mode, grid, st, a);
+    case kSrcRgbPlanar: return launch_scan_src<KIND, kSrcRgbPlanar>(mode, grid, st, a);
     default: return launch_scan_src<KIND, kSrcPlanes>(mode, grid, st, a);
   }
 }
@@ -501,6 +502,7 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     case SJPEG_HIP_SRC_RGB: need[0] = 3ll * W; *src_class = kSrcRgb24; break;
     case SJPEG_HIP_SRC_BGRA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
     case SJPEG_HIP_SRC_RGBA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
+    case SJPEG_HIP_SRC_RGB_PLANAR: need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcRgbPlanar; break;
     case SJPEG_HIP_SRC_GRAY: need[0] = W; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444:
       need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV444;
@@ -527,6 +529,17 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     a->plane[i] = static_cast<const uint8_t*>(src->plane[i]);
     a->row_stride[i] = src->row_stride[i];
     a->frame_stride[i] = src->frame_stride[i];
+  }
+  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
+    // one pitch, three bases (sjpeg_hip.h): the kernels reach G and B at a uniform distance from R
+    for (int i = 1; i < 3; ++i) {
+      if (src->row_stride[i] != src->row_stride[0]) {
+        return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: row_stride[" + std::to_string(i) + "] must equal row_stride[0]");
+      }
+      if (src->frame_stride[i] != src->frame_stride[0]) {
+        return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: frame_stride[" + std::to_string(i) + "] must equal frame_stride[0]");
+      }
+    }
   }
   if (nplanes == 2) {          // interleaved chroma: U and V walk the same plane
     a->plane[2] = a->plane[1]; a->row_stride[2] = a->row_stride[1]; a->frame_stride[2] = a->frame_stride[1];
@@ -1351,6 +1364,7 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
     case SJPEG_HIP_SRC_RGB: *cls = kSrcRgb24; break;
     case SJPEG_HIP_SRC_BGRA: *cls = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
     case SJPEG_HIP_SRC_RGBA: *cls = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
+    case SJPEG_HIP_SRC_RGB_PLANAR: *cls = kSrcRgbPlanar; *nplanes = 3; break;
     case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444: *nplanes = 3; implied = SJPEG_HIP_YUV444; a->cstep = 1; break;
     case SJPEG_HIP_SRC_YUV420: *nplanes = 3; implied = SJPEG_HIP_YUV420; a->cstep = 1; break;
@@ -1374,6 +1388,7 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
 int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes, int nframes,
                   const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo) {
   geo->resize(nframes);
+  if (format == SJPEG_HIP_SRC_RGB_PLANAR) nplanes = 3;           // (whatever the caller counts: R, G and B are all read)
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
     const std::string w = who + ": frame " + std::to_string(f) + ": ";
@@ -1390,6 +1405,10 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
       if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, w + "null plane pointer");
       const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
       if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, w + "|row_stride| smaller than a row of the plane");
+      // planar RGB: one pitch, three bases (sjpeg_hip.h)
+      if (format == SJPEG_HIP_SRC_RGB_PLANAR && fr.row_stride[i] != fr.row_stride[0]) {
+        return fail(SJPEG_HIP_EINVAL, w + "row_stride[" + std::to_string(i) + "] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)");
+      }
     }
     if (out_ranges && fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, w + "out_offset + out_capacity overflows");
   }
@@ -3045,10 +3064,10 @@ int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStre
   return sync_uploads(e, st);
 }
 
-// every frame of an RGB / BGRA / RGBA ragged call checked (the message names the frame)
+// every frame of an RGB / BGRA / RGBA / planar RGB ragged call checked (the message names the frame)
 int rgb_ragged_frames(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames) {
-  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA) {
-    return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA sources");
+  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && format != SJPEG_HIP_SRC_RGB_PLANAR) {
+    return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA (packed) or planar RGB sources");
   }
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   std::vector<FrameGeo> geo;
@@ -3066,6 +3085,7 @@ int risk_ragged(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ra
     memset(&d, 0, sizeof(d));
     d.rgb = static_cast<const uint8_t*>(frames[f].plane[0]);
     d.row_stride = frames[f].row_stride[0];
+    sjpeg_internal::rgb_frame_offsets(format, frames[f].plane, &d.g_off, &d.b_off);
     sjpeg_internal::risk_frame_plan(frames[f].width, frames[f].height, &d);
     d.wg_base = static_cast<unsigned>(total);
     total += static_cast<unsigned long long>(d.bands) * static_cast<unsigned long long>(d.cols);
@@ -3150,8 +3170,8 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
   try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::string err;
-    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA) {
-      return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA sources");
+    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && format != SJPEG_HIP_SRC_RGB_PLANAR) {
+      return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources");
     }
     if (int rc = ragged_ordered(e, st)) return rc;
     if (int rc = sjpeg_internal::sharp_ragged_run(format, nframes, frames, d_y, d_u, d_v, d_workspace, workspace_size, st,

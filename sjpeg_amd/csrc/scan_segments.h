@@ -73,8 +73,8 @@ __device__ __forceinline__ void race_point(int code, int n) {
 // (the histogram kind is compiled for the THREE persistent workgroups per CU it runs as: 168 registers.  Held to the 128
 // of four per CU -- what rounds 4 and 5 shipped, from when it ran four -- it spilt ten registers' worth of loop-invariant
 // values that every segment reloaded from private memory: pass 0.217 -> 0.204 ms per 16 4K frames, the default-parameter
-// calls 2-2.5 % (round 6).  Packed RGB only: ROCm 7.2's clang crashes in its register allocator on the 4-byte-pixel
-// instantiation with the smaller LDS block)
+// calls 2-2.5 % (round 6).  Packed and planar RGB only -- the two classes whose row of 8 pixels is six raw dwords:
+// ROCm 7.2's clang crashes in its register allocator on the 4-byte-pixel instantiation with the smaller LDS block)
 // the compact LDS layout (scan_device.h): four workgroups per CU
 #ifndef SJPEG_HISTO_WGS
 #define SJPEG_HISTO_WGS 3          // workgroups per CU the histogram kind is compiled for (A/B: 4)
@@ -83,8 +83,12 @@ template <int MODE, int KINDX, int SRC>
 constexpr bool kCompactLds = (KINDX == kKindEncode || KINDX == kKindEncodeReplay || KINDX == kKindStats || KINDX == kKindStatsCoef ||
                               KINDX == kKindEncodeRagged || KINDX == kKindStatsRagged || KINDX == kKindEncodeReplayRagged);
 
+// the histogram kinds compiled for SJPEG_HISTO_WGS workgroups per CU, with the smaller LDS block (above)
 template <int MODE, int KINDX, int SRC>
-__global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kKindHistoRagged) && SRC == kSrcRgb24) ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
+constexpr bool kHistoThree = (KINDX == kKindHisto || KINDX == kKindHistoRagged) && (SRC == kSrcRgb24 || SRC == kSrcRgbPlanar);
+
+template <int MODE, int KINDX, int SRC>
+__global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPEG_HISTO_WGS : (kCompactLds<MODE, KINDX, SRC> ? 4 : 1))) void scan_segments(const ScanArgs a_in) {
   // The ragged kinds are the encode, histogram and statistics kinds but for their prologue: a workgroup's frame and
   // segment come from the launch's workgroup -> frame map, the frame's geometry and scratch bases from its descriptor
   // (ragged_scan_view; the histogram's persistent groups: ragged_histo_view)
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
   static_assert(2 * 4 * G::kSegMcus * BPM <= L::kListBytes, "the part list holds four parts of every coded block");
   // static, not `extern __shared__`: the address of a dynamic block is resolved after instruction
   // selection and leaves a `+ 0` in ~65 address computations of this kernel
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(KIND == kKindStats && !COMPACT) ? kLdsBytesStats : (KIND == kKindHisto && SRC == kSrcRgb24) ? kHistoLdsBytes : L::kLdsBytes];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[(KIND == kKindStats && !COMPACT) ? kLdsBytesStats : kHistoThree<MODE, KINDX, SRC> ? kHistoLdsBytes : L::kLdsBytes];
   static_assert(kHistoLdsBytes >= kSamplesBytes && kHistoLdsBytes <= L::kLdsBytes && 4 * kHistoLdsBytes <= 160 * 1024, "histogram kind: slots, then staging + bins");
   uint32_t* const win = reinterpret_cast<uint32_t*>(smem + L::kOffWin);
   uint4* const lq = reinterpret_cast<uint4*>(smem + L::kOffQ);
@@ -266,7 +270,11 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
     }
     const int x0 = mb_x * PX + xs * 8;
     const uint32_t k7471 = 7471u, k32768 = 32768u;             // multiplier operands (low halves)
-    constexpr int kNW = (SRC == kSrcRgb24) ? 6 : 8;             // dwords per 8 pixels
+    constexpr int kNW = kSrcRowWords<SRC>;                      // dwords per 8 pixels (planar RGB: 2 + 2 + 2)
+    // planar RGB: the G and B planes lie a uniform distance from R's, the same in every row and frame (one pitch, equal
+    // frame strides: checked on the host) -- a thread's offset into the R plane is its offset into all three
+    const long long dg = (SRC == kSrcRgbPlanar) ? a.plane[1] - a.plane[0] : 0;
+    const long long db = (SRC == kSrcRgbPlanar) ? a.plane[2] - a.plane[0] : 0;
 #ifndef SJPEG_HISTO_BATCH
 #define SJPEG_HISTO_BATCH 2
 #endif
@@ -281,7 +289,7 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
     constexpr bool INTERIOR = decltype(interior_tag)::value;
     bool tables_staged = false;
     // interior copy: the strip's row pointer advances by a uniform step (no 64-bit multiply per row)
-    constexpr int kBpp = (SRC == kSrcRgb24) ? 3 : 4;
+    constexpr int kBpp = kSrcPixelBytes<SRC>;
     const long long rs = a.row_stride[0];
     const uint8_t* prow = frame_px + static_cast<long long>(mb_y * PX + yp0 * kRowsPerStrip) * rs + kBpp * x0;
     const long long pstep = static_cast<long long>(ngroups * kRowsPerStrip) * rs;      // uniform
@@ -296,11 +304,19 @@ __global__ __launch_bounds__(kScanThreads, (((KINDX == kKindHisto || KINDX == kK
           const int y0 = mb_y * PX + yp * kRowsPerStrip;
           if (INTERIOR) {
 #pragma unroll
-            for (int r = 0; r < kRowsPerStrip; ++r) __builtin_memcpy(raw[it][r], prow + r * rs, kNW * 4);
+            for (int r = 0; r < kRowsPerStrip; ++r) {
+              if (SRC == kSrcRgbPlanar) {
+                __builtin_memcpy(raw[it][r], prow + r * rs, 8);
+                __builtin_memcpy(raw[it][r] + 2, prow + (r * rs + dg), 8);
+                __builtin_memcpy(raw[it][r] + 4, prow + (r * rs + db), 8);
+              } else {
+                __builtin_memcpy(raw[it][r], prow + r * rs, kNW * 4);
+              }
+            }
           } else {
             const bool inside = (x0 + 8 <= a.W) && (y0 + kRowsPerStrip <= a.H);
 #pragma unroll
-            for (int r = 0; r < kRowsPerStrip; ++r) load_px8<SRC>(a, frame_px, x0, y0 + r, inside, raw[it][r]);
+            for (int r = 0; r < kRowsPerStrip; ++r) load_px8<SRC>(a, frame_px, x0, y0 + r, inside, raw[it][r], dg, db);
           }
         }
         prow += pstep;

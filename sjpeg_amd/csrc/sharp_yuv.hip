@@ -45,7 +45,8 @@ struct GammaTables {
 struct SharpArgs {
   const uint8_t* rgb;
   long long row_stride, frame_stride;
-  int pix_step, r_off, g_off, b_off;              // bytes per pixel and channel positions
+  int pix_step;                                   // bytes per pixel ...
+  long long r_off, g_off, b_off;                  // ... and channel positions (planar RGB: its G and B planes, from R's)
   int W, H, w, h, uv_w, uv_h;                     // w, h: padded to even
   const GammaTables* tab;
   uint16_t* best_y;  uint16_t* target_y;          // [nframes][h][w]
@@ -688,6 +689,7 @@ __global__ __launch_bounds__(64) void sharp_small(const SharpArgs a) {
 struct SharpFrame {
   const uint8_t* rgb;
   long long row_stride;
+  long long g_off, b_off;                       // where G and B lie from R (rgb_frame_offsets)
   uint8_t* y; uint8_t* u; uint8_t* v;           // tightly packed planes
   uint8_t* block;                               // the frame's workspace block (sharp_small frames: none)
   uint32_t* ctrl;                               // its 32 + 4 * nstrips control words
@@ -707,6 +709,7 @@ __host__ __device__ __forceinline__ size_t sharp_block_bytes(int W, int H) {
 __device__ __forceinline__ SharpArgs sharp_rebase(const SharpArgs& common, const SharpFrame& d) {
   SharpArgs a = common;
   a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.g_off = d.g_off; a.b_off = d.b_off;
   a.W = d.W; a.H = d.H;
   a.w = (d.W + 1) & ~1; a.h = (d.H + 1) & ~1; a.uv_w = a.w >> 1; a.uv_h = a.h >> 1;
   const size_t ysz = sharp_align256(static_cast<size_t>(a.w) * a.h * 2), usz = sharp_align256(static_cast<size_t>(3) * a.uv_w * a.uv_h * 2);
@@ -775,6 +778,7 @@ __global__ __launch_bounds__(64) void sharp_small_ragged(const SharpArgs common,
   const SharpFrame& d = frames[blockIdx.x];
   SharpArgs a = common;
   a.rgb = d.rgb; a.row_stride = d.row_stride; a.frame_stride = 0;
+  a.g_off = d.g_off; a.b_off = d.b_off;
   a.W = d.W; a.H = d.H;
   a.y = d.y; a.u = d.u; a.v = d.v;
   a.y_frame_stride = 0; a.uv_frame_stride = 0;
@@ -841,6 +845,10 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
   }
   const int64_t st_abs = src->row_stride[0] < 0 ? -src->row_stride[0] : src->row_stride[0];
   if (st_abs < static_cast<int64_t>(a.pix_step) * width) return SJPEG_HIP_EINVAL;
+  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
+    if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
+    sjpeg_internal::rgb_frame_offsets(src->format, src->plane, &a.g_off, &a.b_off);
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   a.rgb = static_cast<const uint8_t*>(src->plane[0]);
   a.row_stride = src->row_stride[0]; a.frame_stride = src->frame_stride[0];
@@ -965,7 +973,7 @@ int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* fram
   SharpArgs a;
   memset(&a, 0, sizeof(a));
   if (!rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
-    *err = "the sharp conversion takes RGB, BGRA or RGBA sources";
+    *err = "the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources";
     return SJPEG_HIP_EINVAL;
   }
   if (nframes < 1 || nframes > 65535) { *err = "nframes must be 1..65535"; return SJPEG_HIP_EINVAL; }
@@ -983,6 +991,9 @@ int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* fram
     if (fr.plane[0] == nullptr || d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
     const int64_t st_abs = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
     if (st_abs < static_cast<int64_t>(a.pix_step) * fr.width) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
+    if (format == SJPEG_HIP_SRC_RGB_PLANAR) {
+      if (const char* fault = rgb_planar_fault(fr.plane, fr.row_stride, nullptr)) { *err = w + fault; return SJPEG_HIP_EINVAL; }
+    }
   }
   if (workspace_size < sharp_ragged_workspace(nframes, frames)) { *err = "workspace_size below sjpeg_hip_sharp_ragged_workspace()"; return SJPEG_HIP_EINVAL; }
 #ifdef SJPEG_HIP_PRIO_STRESS
@@ -1013,6 +1024,7 @@ int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* fram
     SharpFrame& d = desc[k];
     memset(&d, 0, sizeof(d));
     d.rgb = static_cast<const uint8_t*>(fr.plane[0]); d.row_stride = fr.row_stride[0];
+    rgb_frame_offsets(format, fr.plane, &d.g_off, &d.b_off);
     d.y = d_y[f]; d.u = d_u[f]; d.v = d_v[f];
     d.W = fr.width; d.H = fr.height;
     if (k >= nbig) continue;
