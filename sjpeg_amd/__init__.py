@@ -1065,14 +1065,8 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_batch: one entry of planes_per_frame and dims per frame, at least one frame")
-        per_frame = isinstance(quant, (list, tuple))
-        if per_frame and len(quant) != n:
-            raise SjpegError("encode_ragged_batch: one starting matrix per frame")
-        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
-                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
-        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
-        if capacities is None:
-            capacities = [frame_bound(w, h, yuv_mode, 2048) for (w, h) in dims]
+        q, per_frame, mq, _, _, capacities = _ragged_args("encode_ragged_batch", n, quant, min_quant, None, yuv_mode,
+                                                          capacities, dims)
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         self._chk(lib().sjpeg_hip_encode_ragged_batch_src(self._h, fmt, yuv_mode, n, frames, q.ctypes.data, int(per_frame),
                                                           mq.ctypes.data if mq is not None else None, q_bias, int(method),
@@ -1127,19 +1121,8 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_search: one entry of planes_per_frame and dims per frame, at least one frame")
-        per_frame = isinstance(quant, (list, tuple))
-        if per_frame and len(quant) != n:
-            raise SjpegError("encode_ragged_search: one starting matrix per frame")
-        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
-                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
-        search_per_frame = isinstance(search, (list, tuple))
-        if search_per_frame and len(search) != n:
-            raise SjpegError("encode_ragged_search: one search per frame")
-        sp = [_search_params(x) for x in (search if search_per_frame else [search])]
-        sarr = (SearchParams * len(sp))(*sp)
-        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
-        if capacities is None:
-            capacities = [frame_bound(w, h, yuv_mode, 2048) for (w, h) in dims]
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_search", n, quant, min_quant,
+                                                                            search, yuv_mode, capacities, dims)
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         q_out, v_out = (C.c_float * n)(), (C.c_float * n)()
         self._chk(lib().sjpeg_hip_encode_ragged_search_src(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data,
@@ -1220,14 +1203,7 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError(f"{who}: one entry of planes_per_frame and dims per frame, at least one frame")
-        per_frame = isinstance(quant, (list, tuple))
-        if per_frame and len(quant) != n:
-            raise SjpegError(f"{who}: one starting matrix per frame")
-        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
-                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
-        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
-        if capacities is None:
-            capacities = [frame_bound(w, h, YUV_444, 2048) for (w, h) in dims]
+        q, per_frame, mq, _, _, capacities = _ragged_args(who, n, quant, min_quant, None, YUV_444, capacities, dims)
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         modes = (C.c_int * n)()
         self._chk(getattr(lib(), symbol)(self._h, fmt, int(yuv_mode), n, frames, q.ctypes.data, int(per_frame),
@@ -1263,22 +1239,9 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_packed: one entry of planes_per_frame and dims per frame, at least one frame")
-        per_frame = isinstance(quant, (list, tuple))
-        if per_frame and len(quant) != n:
-            raise SjpegError("encode_ragged_packed: one starting matrix per frame")
-        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
-                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
-        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
-        sarr, search_per_frame = None, False
-        if search is not None:
-            search_per_frame = isinstance(search, (list, tuple))
-            if search_per_frame and len(search) != n:
-                raise SjpegError("encode_ragged_packed: one search per frame")
-            sp = [_search_params(x) for x in (search if search_per_frame else [search])]
-            sarr = (SearchParams * len(sp))(*sp)
-        if capacities is None:
-            bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-            capacities = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_packed", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
         if len(capacities) != n:
             raise SjpegError("encode_ragged_packed: one capacity per frame")
         dev = _ragged_device(planes_per_frame)
@@ -1310,22 +1273,9 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_full: one entry of planes_per_frame and dims per frame, at least one frame")
-        per_frame = isinstance(quant, (list, tuple))
-        if per_frame and len(quant) != n:
-            raise SjpegError("encode_ragged_full: one starting matrix per frame")
-        q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
-                                 else np.asarray(quant, np.uint8).reshape(1, 2, 64))
-        mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
-        sarr, search_per_frame = None, False
-        if search is not None:
-            search_per_frame = isinstance(search, (list, tuple))
-            if search_per_frame and len(search) != n:
-                raise SjpegError("encode_ragged_full: one search per frame")
-            sp = [_search_params(x) for x in (search if search_per_frame else [search])]
-            sarr = (SearchParams * len(sp))(*sp)
-        if capacities is None:
-            bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-            capacities = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_full", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
         params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
@@ -1358,6 +1308,29 @@ class Engine:
 
 
 TARGET_SIZE, TARGET_PSNR = 1, 2      # sjpeg_hip_search.target_mode (EncoderParam::TargetMode)
+
+
+def _ragged_args(who, n, quant, min_quant, search, yuv_mode, capacities, dims):
+    """What the ragged batch calls hand to the library: the starting matrices ([1][2][64], or with a list [n][2][64])
+    and whether there is one per frame; min_quant [2][64] or None; the SearchParams array (None without a search) and
+    whether there is one per frame; the capacities (default: frame_bound(w, h, yuv_mode, 2048)).  who: the caller, for
+    its error texts."""
+    per_frame = isinstance(quant, (list, tuple))
+    if per_frame and len(quant) != n:
+        raise SjpegError(f"{who}: one starting matrix per frame")
+    q = np.ascontiguousarray(np.stack([np.asarray(m, np.uint8).reshape(2, 64) for m in quant]) if per_frame
+                             else np.asarray(quant, np.uint8).reshape(1, 2, 64))
+    mq = None if min_quant is None else np.ascontiguousarray(min_quant, np.uint8).reshape(2, 64)
+    sarr, search_per_frame = None, False
+    if search is not None:
+        search_per_frame = isinstance(search, (list, tuple))
+        if search_per_frame and len(search) != n:
+            raise SjpegError(f"{who}: one search per frame")
+        sp = [_search_params(x) for x in (search if search_per_frame else [search])]
+        sarr = (SearchParams * len(sp))(*sp)
+    if capacities is None:
+        capacities = [frame_bound(w, h, yuv_mode, 2048) for (w, h) in dims]
+    return q, per_frame, mq, sarr, search_per_frame, capacities
 
 
 def _search_params(x):

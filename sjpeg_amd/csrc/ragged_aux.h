@@ -1,5 +1,6 @@
-// ragged_aux.h -- what the ragged riskiness and sharp conversions (riskiness.hip, sharp_yuv.hip) share with the
-// engine's ragged entry points (scan_engine.hip).  Internal: not part of include/sjpeg_hip.h.
+// ragged_aux.h -- what the ragged riskiness and sharp conversions (riskiness.hip, sharp_yuv.hip) and the search
+// (ragged_full.cc) share with the engine's ragged entry points (scan_engine.hip).  Internal: not part of
+// include/sjpeg_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -8,9 +9,54 @@
 #include <string>
 #include <vector>
 
+#include "jpeg_host.h"
 #include "sjpeg_hip.h"
 
 namespace sjpeg_internal {
+
+// ---- sizes and mode helpers the ragged flows share (scan_engine.hip, ragged_full.cc)
+// a frame's share of device scratch: its kept histogram, its adaptation sums and totals (adapt_sums_kernel: [2][64]
+// [deltas][2] int64, [2][64][2] int32), its symbol counts; a segment's partial of the statistics pass and its kept blocks
+// (9 rows of 16 bytes for each of the workgroup's 256 threads: scan_engine.hip asserts it against scan_device.h's
+// kKeptSegWords)
+constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
+constexpr size_t kSums = 2 * 64 * sjpeg_host::kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
+constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t), kStatsPartial = kFreq;
+constexpr size_t kKeptSegBytes = 256 * 9 * 16;
+
+// SjpegYUVMode (include/sjpeg.h); 1, 3 and 4 are SJPEG_HIP_YUV420 / 444 / 400
+enum { kYuvAuto = 0, kYuv420 = 1, kYuvSharp = 2, kYuv444 = 3, kYuv400 = 4 };
+// The mode groups of a call, in the order they are coded: 4:2:0, 4:4:4, 4:0:0 of the caller's format, then the sharp
+// frames as planar 4:2:0.  What a group's frames are read as, and the sampling a frame of a mode is coded with:
+constexpr int kGroupKinds[4] = {kYuv420, kYuv444, kYuv400, kYuvSharp};
+inline int group_format(int kind, int format) { return kind == kYuvSharp ? SJPEG_HIP_SRC_YUV420 : format; }
+inline int hip_yuv_mode(int mode) { return mode == kYuv444 ? SJPEG_HIP_YUV444 : mode == kYuv400 ? SJPEG_HIP_YUV400 : SJPEG_HIP_YUV420; }
+
+inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
+// the planar 4:2:0 planes of a sharp frame: Y, U, V, each at a multiple of 16
+inline size_t planes_bytes(const sjpeg_hip_ragged_frame& fr) {
+  const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+  return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
+}
+// The sharp frames of a part in an arena: the planes of frame after frame tightly packed, then the workspace.  planar[k]
+// becomes sharp[k] read as planar 4:2:0 from there (plane[0..2], row_stride[0..2]), yuv[c][k] its plane c; returns where
+// the workspace starts.
+inline uint8_t* place_sharp_planes(uint8_t* arena, const std::vector<sjpeg_hip_ragged_frame>& sharp,
+                                   std::vector<sjpeg_hip_ragged_frame>* planar, std::vector<uint8_t*> yuv[3]) {
+  uint8_t* at = arena;
+  *planar = sharp;
+  for (sjpeg_hip_ragged_frame& fr : *planar) {
+    const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
+    const size_t bytes[3] = {static_cast<size_t>(fr.width) * fr.height, cw * ch, cw * ch};
+    for (int c = 0; c < 3; ++c) {
+      yuv[c].push_back(at);
+      fr.plane[c] = at;
+      fr.row_stride[c] = static_cast<int64_t>(c == 0 ? fr.width : cw);
+      at += align16(bytes[c]);
+    }
+  }
+  return at;
+}
 
 // the channel layout of a packed RGB / BGRA / RGBA or planar RGB source (the riskiness stencil and the sharp conversion
 // start from these); false for any other format.  The offsets count from plane[0]: planar RGB is pix_step 1 with G and
@@ -86,7 +132,7 @@ struct PackedSink {
   int nframes;                   // of the packed call
   const int* index;              // the caller's number of each frame handed to the flow (NULL: its own position)
 };
-// the entry points' flows with a sink (the public functions pass NULL); scan_engine.hip and ragged_search.cc
+// the entry points' flows with a sink (the public functions pass NULL); scan_engine.hip and ragged_full.cc
 int ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
                       const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
                       int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, void* stream,
@@ -96,7 +142,7 @@ int ragged_search_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframe
                        int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search, int search_per_frame,
                        float* q_out, float* value_out, void* d_out, uint64_t* d_sizes, void* stream, const PackedSink* sink);
 
-// ---- the search over a ragged batch (ragged_search.cc) and what it takes from the engine (scan_engine.hip)
+// ---- the search over a ragged batch (ragged_full.cc) and what it takes from the engine (scan_engine.hip)
 int set_error(int code, const std::string& msg);          // sjpeg_hip_last_error() of the calling thread
 size_t engine_scratch_limit(const sjpeg_hip_engine* e);   // SJPEG_HIP_SCRATCH_LIMIT_BYTES
 int engine_device(const sjpeg_hip_engine* e);
@@ -119,9 +165,7 @@ int adapt_ragged(const uint32_t* d_hist, const uint8_t* d_quant_in, int n, const
                  int qdelta_max_luma, int qdelta_max_chroma, int64_t* d_sums, int32_t* d_totlast, uint8_t* d_quant_out,
                  hipStream_t st);
 
-
-// ---- the search with any sampling and with the trellis (ragged_full.cc: sjpeg_hip_encode_ragged_full_src) and what it
-// takes from the engine (scan_engine.hip)
+// ... and, for any sampling and the trellis (sjpeg_hip_encode_ragged_full_src):
 // the unsearched flow of a SjpegYUVMode and method 0..8 (sjpeg_hip_encode_ragged_auto_src / _trellis_src), with a sink
 int ragged_unsearched_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
                            const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,

@@ -1,10 +1,15 @@
-// ragged_full.cc -- sjpeg_hip_encode_ragged_full_src / _full_packed_src: the reference's sjpeg::Encode(EncoderParam) over a
-// ragged batch with EVERY combination of SjpegYUVMode 0..4, method 0..8 and a search per frame.  What the older entry
-// points take goes to their flows unchanged; new here is the search (Encoder::LoopScan, src/dichotomy.cc:113-205) together
-// with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, with the trellis methods 7 and 8 (each size pass one trellis quantization,
-// src/dichotomy.cc:80-111 StoreRunLevels), or both.  The host part is host_api.cc's Encoder::Run, batched: the frames of a
-// part stand in MODE GROUPS (4:2:0, 4:4:4, 4:0:0 of the caller's format, the sharp frames as planar 4:2:0), every pass
-// launches over all groups and then waits once.  DESIGN.md section 4.
+// ragged_full.cc -- the reference's multi-pass search (Encoder::LoopScan, src/dichotomy.cc:113-205) over a ragged batch:
+// sjpeg_hip_encode_ragged_search_src (one sampling, methods 0..6) and sjpeg_hip_encode_ragged_full_src / _full_packed_src
+// (sjpeg::Encode(EncoderParam) with EVERY combination of SjpegYUVMode 0..4, method 0..8 and a search per frame: also
+// SJPEG_YUV_AUTO / SJPEG_YUV_SHARP and the trellis methods 7 and 8, each size pass one trellis quantization,
+// src/dichotomy.cc:80-111 StoreRunLevels).  The entry points differ in their checks and messages; the search is ONE flow.
+// The host API runs it one picture at a time (host_api.cc, Encoder::Run); here the frames of a part stand in MODE GROUPS
+// (4:2:0, 4:4:4, 4:0:0 of the caller's format, the sharp frames as planar 4:2:0; a fixed sampling is one group), every
+// pass launches over all groups and then waits once for what it measured.  Per frame, one sjpeg::SearchHook does the
+// float arithmetic of the search (Setup / NextMatrix / Update); the measurements are the ones the host API prices a pass
+// with (jpeg_host.h: SearchHeaderBits, EntropyBits, SearchPSNR).  The device passes are the engine's ragged ones:
+// histogram (kept for the whole search), adaptation, symbol statistics, counted bits, quantization error.  DESIGN.md
+// section 4.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -20,17 +25,7 @@
 
 namespace {
 
-using sjpeg_internal::set_error;
-
-constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);      // a frame's kept histogram
-constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);            // a frame's symbol counts
-constexpr size_t kStatsPartial = 2 * 272 * sizeof(uint32_t);    // a segment's partial of the statistics pass
-constexpr size_t kKeptSegBytes = 36864;                         // a segment's kept blocks (scan_device.h: kKeptSegWords)
-constexpr size_t kAdaptSumsBytes = 2 * 64 * sjpeg_host::kAdaptDeltas * 2 * sizeof(int64_t);
-constexpr size_t kAdaptTotBytes = 2 * 64 * 2 * sizeof(int32_t);
-
-// SjpegYUVMode (include/sjpeg.h); 1, 3 and 4 are SJPEG_HIP_YUV420 / 444 / 400
-enum { kYuvAuto = 0, kYuv420 = 1, kYuvSharp = 2, kYuv444 = 3, kYuv400 = 4 };
+using namespace sjpeg_internal;      // (the shared sizes, SjpegYUVMode and the mode groups: ragged_aux.h)
 
 // device scratch of the calling thread, kept between calls: everything in it is read back before the call returns
 struct FullScratch {
@@ -51,8 +46,6 @@ struct FullScratch {
   ~FullScratch() { if (p != nullptr) { (void)hipSetDevice(device); (void)hipFree(p); } }
 };
 thread_local FullScratch g_full;
-
-inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
 
 // one searched frame of a part: its hook, the loop state of Encoder::LoopScan and (trellis) the encoder's live rate table
 struct Frame {
@@ -179,7 +172,7 @@ int search_kind(const Call& c, std::vector<Frame>& s, const std::vector<Group>& 
             const size_t k0 = active[i0];
             return sjpeg_internal::adapt_ragged(c.d_hist + k0 * (kHist / 4), c.d_qin + k0 * 128, static_cast<int>(i1 - i0), c.min_quant,
                                                 groups[s[k0].group].ntab, c.qdelta_max_luma, c.qdelta_max_chroma,
-                                                c.d_sums + k0 * (kAdaptSumsBytes / 8), c.d_tot + k0 * (kAdaptTotBytes / 4),
+                                                c.d_sums + k0 * (kSums / 8), c.d_tot + k0 * (kTot / 4),
                                                 c.d_qout + k0 * 128, c.st);
           })) return rc;
       if (int rc = read_back(c, h_q.data(), c.d_qout, h_q.size())) return rc;                    // (wait 1: the matrices)
@@ -192,13 +185,13 @@ int search_kind(const Call& c, std::vector<Frame>& s, const std::vector<Group>& 
     afr.clear(); atab.clear(); akept.clear();
     for (int k : active) {
       afr.push_back(s[k].fr);
-      sjpeg_hip_scan_tables t = s[k].tables;
+      atab.push_back(s[k].tables);
+      sjpeg_hip_scan_tables& t = atab.back();
       if (for_size) sjpeg_hip_default_huffman(&t);
       if (trellis_pass) {                                    // priced with the frame's accumulated rate table
         t.flags |= SJPEG_HIP_QUANT_TRELLIS;
         memcpy(t.trellis_len, s[k].rate, sizeof(s[k].rate));
       }
-      atab.push_back(t);
       akept.push_back(s[k].kept_base);
     }
     const int na = static_cast<int>(active.size());
@@ -373,62 +366,32 @@ int finish_trellis(const Call& c, std::vector<Frame>& s, const std::vector<Group
   return scatter_sizes(who, d_sub, which, d_sizes, c.st);
 }
 
-int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-              const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
-              void* stream, const sjpeg_internal::PackedSink* sink) {
-  const sjpeg_hip_ragged_params& P = *params;
+// the passes of frame f's search after the clamp of src/api.cc:169 (1: the frame is not searched)
+int passes_of(const sjpeg_hip_ragged_params& P, int f) {
+  return P.search == nullptr ? 1 : std::min(std::max(static_cast<int>(P.search[P.search_per_frame ? f : 0].passes), 1), 20);
+}
+
+// The flow behind every entry point of this file (arguments checked): the frames that are not searched go to the
+// unsearched flow of the same method and mode, the searched ones through the passes, in parts.  stats: the six counters
+// of sjpeg_hip_engine_search_stats.  sink != NULL: the frames go to the packed buffer (ragged_aux.h) in the order the
+// sub-calls code them -- the frames that are not searched, then every part's searched ones.
+int search_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                const sjpeg_hip_ragged_params& P, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                void* stream, const PackedSink* sink, uint64_t* stats) {
   const int yuv_mode = P.yuv_mode, method = P.method;
-  // ---- the checks, all of them before the engine is touched
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return set_error(SJPEG_HIP_EINVAL, who + ": params->yuv_mode outside 0..4 (SjpegYUVMode)");
-  if (method < 0 || method > 8) return set_error(SJPEG_HIP_EINVAL, who + ": params->method outside 0..8");
-  if (P.qdelta_max_luma < -12 || P.qdelta_max_luma > 12 || P.qdelta_max_chroma < -12 || P.qdelta_max_chroma > 12) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": params->qdelta_max outside -12 .. 12");
-  }
-  if (P.quant == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params->quant == NULL");
-  const bool by_mode = yuv_mode == kYuvAuto || yuv_mode == kYuvSharp;
-  if (by_mode && format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA &&
-      format != SJPEG_HIP_SRC_RGB_PLANAR) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO and SJPEG_YUV_SHARP take RGB, BGRA or RGBA (packed) or planar RGB sources");
-  }
-  for (int k = 0; P.search != nullptr && k < (P.search_per_frame ? nframes : 1); ++k) {
-    const sjpeg_hip_search& sp = P.search[k];
-    if (sp.target_mode != 1 && sp.target_mode != 2) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "] (frame " + std::to_string(k) +
-                                             "): target_mode must be 1 (size) or 2 (PSNR)");
-    }
-    if (!std::isfinite(sp.target_value)) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "] (frame " + std::to_string(k) + "): the target is not finite");
-    }
-  }
-  if (int rc = sjpeg_internal::ragged_check(who, format, by_mode ? SJPEG_HIP_YUV444 : yuv_mode, nframes, frames)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (sink != nullptr) { if (int rc = sjpeg_internal::engine_pack_begin(e, stream)) return rc; }
   try {
-    // which frames are searched (passes > 1 after the clamp of src/api.cc:169)
     std::vector<int> searched, plain;
     for (int f = 0; f < nframes; ++f) {
-      const int passes = P.search != nullptr ? P.search[P.search_per_frame ? f : 0].passes : 1;
-      (std::min(std::max(passes, 1), 20) > 1 ? searched : plain).push_back(f);
+      (passes_of(P, f) > 1 ? searched : plain).push_back(f);
       if (q_out != nullptr) q_out[f] = -1.f;
       if (value_out != nullptr) value_out[f] = -1.f;
     }
-    uint64_t* const stats = sjpeg_internal::engine_full_stats(e);
-    memset(stats, 0, 6 * sizeof(uint64_t));
-    // ---- the ground of the older entry points: their flows, their bytes
     if (searched.empty()) {
       return sjpeg_internal::ragged_unsearched_flow(e, format, yuv_mode, nframes, frames, P.quant, P.quant_per_frame, P.min_quant,
                                                     P.q_bias, method, P.qdelta_max_luma, P.qdelta_max_chroma, d_out, d_sizes, modes,
                                                     stream, sink);
     }
-    if (!by_mode && method <= 6) {
-      const int rc = sjpeg_internal::ragged_search_flow(e, format, yuv_mode, nframes, frames, P.quant, P.quant_per_frame, P.min_quant,
-                                                        P.q_bias, method, P.qdelta_max_luma, P.qdelta_max_chroma, P.search,
-                                                        P.search_per_frame, q_out, value_out, d_out, d_sizes, stream, sink);
-      if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
-      return rc;
-    }
-    // ---- the new ground: a search with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, with the trellis, or both
     const int dev = sjpeg_internal::engine_device(e);
     if (hipSetDevice(dev) != hipSuccess) return hip_fail(who, "hipSetDevice");
     Call c;
@@ -448,12 +411,9 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
       for (size_t f = 0; f < n_all; ++f) mode[f] = sjpeg_hip_riskiness_verdict(&sums[f * 3], frames[f].width, frames[f].height, nullptr);
     }
     if (modes != nullptr) for (size_t f = 0; f < n_all; ++f) modes[f] = mode[f];
-    auto hip_mode = [&](int f) { return mode[f] == kYuv444 ? SJPEG_HIP_YUV444 : mode[f] == kYuv400 ? SJPEG_HIP_YUV400 : SJPEG_HIP_YUV420; };
-    auto planes_bytes = [](const sjpeg_hip_ragged_frame& fr) {
-      const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
-      return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
-    };
-    // 2. the frames that are not searched: the unsearched flow of the same method and mode, its own waits
+    // 2. the frames that are not searched: the unsearched flow of the same method and mode, its own waits.  Its sizes go
+    // through engine memory to the caller's places (the encode and the copies are still queued on the stream when the call
+    // returns: never thread-local scratch)
     if (!plain.empty()) {
       std::vector<sjpeg_hip_ragged_frame> sub;
       std::vector<uint8_t> q(plain.size() * 128);
@@ -477,7 +437,7 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
     // 3. parts of consecutive searched frames whose kept scratch -- histograms, partials, sharp planes and workspace, kept
     // blocks -- stays inside the engine's limit
     const size_t limit = sjpeg_internal::engine_scratch_limit(e);
-    const size_t per_frame = (c.adaptive ? kHist : 0) + 256 + kAdaptSumsBytes + kAdaptTotBytes + kFreq;
+    const size_t per_frame = (c.adaptive ? kHist : 0) + 256 + kSums + kTot + kFreq;
     std::vector<std::pair<size_t, size_t>> parts;       // (first in `searched`, count)
     size_t most = 0, most_arena = 0, most_kept = 0;
     {
@@ -497,7 +457,7 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
       for (size_t k = 0; k < searched.size(); ++k) {
         const int f = searched[k];
         const sjpeg_hip_ragged_frame& fr = frames[f];
-        const int nseg = std::max(sjpeg_hip_segment_count(fr.width, fr.height, hip_mode(f)), 1);
+        const int nseg = std::max(sjpeg_hip_segment_count(fr.width, fr.height, hip_yuv_mode(mode[f])), 1);
         const bool is_sharp = mode[f] == kYuvSharp;
         const size_t b = per_frame + static_cast<size_t>(nseg) * kStatsPartial +
                          (is_sharp ? planes_bytes(fr) + sjpeg_internal::sharp_ragged_workspace(1, &fr) : 0) +
@@ -520,11 +480,11 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
       // 4. the part's mode groups, its frames in group order: that order is their slot in every scratch array
       std::vector<Frame> s;
       std::vector<Group> groups;
-      const int kinds[4] = {kYuv420, kYuv444, kYuv400, kYuvSharp};
-      for (int kind : kinds) {
+      s.reserve(pt.second);
+      for (int kind : kGroupKinds) {
         Group g;
-        g.format = kind == kYuvSharp ? SJPEG_HIP_SRC_YUV420 : format;
-        g.yuv_mode = kind == kYuvSharp ? SJPEG_HIP_YUV420 : kind;            // (SjpegYUVMode 1, 3, 4 = SJPEG_HIP_YUV*)
+        g.format = group_format(kind, format);
+        g.yuv_mode = hip_yuv_mode(kind);
         g.ntab = g.yuv_mode == SJPEG_HIP_YUV400 ? 1 : 2;
         g.nb_comps = g.yuv_mode == SJPEG_HIP_YUV400 ? 1 : 3;
         g.first = static_cast<int>(s.size());
@@ -540,41 +500,33 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
         g.count = static_cast<int>(s.size()) - g.first;
         if (g.count > 0) groups.push_back(g);
       }
-      // the sharp frames, converted ONCE into planar 4:2:0 planes in the engine's arena (Y, U, V tightly packed, then the
-      // workspace); the kept bases: prefix sums over the part's frames, fixed until its replay
+      // the kept bases: prefix sums over the part's frames, fixed until its replay; the sharp frames (the part's last
+      // group), converted ONCE into planar 4:2:0 planes in the engine's arena
       {
-        std::vector<sjpeg_hip_ragged_frame> sharp;
-        std::vector<uint8_t*> py, pu, pv;
-        uint8_t* at = d_arena;
+        std::vector<sjpeg_hip_ragged_frame> sharp, planar;
+        std::vector<uint8_t*> yuv[3];
         uint32_t kept = 0;
         for (Frame& fs : s) {
-          const Group& g = groups[fs.group];
           if (c.trellis) {
             fs.kept_base = kept;
-            kept += static_cast<uint32_t>(std::max(sjpeg_hip_segment_count(fs.fr.width, fs.fr.height, g.yuv_mode), 1));
+            kept += static_cast<uint32_t>(std::max(sjpeg_hip_segment_count(fs.fr.width, fs.fr.height, groups[fs.group].yuv_mode), 1));
           }
-          if (mode[fs.index] != kYuvSharp) continue;
-          const size_t cw = (static_cast<size_t>(fs.fr.width) + 1) / 2, ch = (static_cast<size_t>(fs.fr.height) + 1) / 2;
-          sharp.push_back(fs.fr);
-          py.push_back(at); at += align16(static_cast<size_t>(fs.fr.width) * fs.fr.height);
-          pu.push_back(at); at += align16(cw * ch);
-          pv.push_back(at); at += align16(cw * ch);
-          fs.fr.plane[0] = py.back(); fs.fr.plane[1] = pu.back(); fs.fr.plane[2] = pv.back();
-          fs.fr.row_stride[0] = fs.fr.width; fs.fr.row_stride[1] = fs.fr.row_stride[2] = static_cast<int64_t>(cw);
+          if (mode[fs.index] == kYuvSharp) sharp.push_back(fs.fr);
         }
         if (!sharp.empty()) {
-          uint8_t* const ws = d_arena + align16(static_cast<size_t>(at - d_arena));
+          uint8_t* const ws = place_sharp_planes(d_arena, sharp, &planar, yuv);
           const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
           if (static_cast<size_t>(ws - d_arena) + wsz > most_arena) return set_error(SJPEG_HIP_ERUNTIME, who + ": internal: the sharp planes pass their arena");
-          if (int rc = sjpeg_hip_sharp_yuv_ragged(e, format, static_cast<int>(sharp.size()), sharp.data(), py.data(), pu.data(), pv.data(),
-                                                  ws, wsz, stream)) return rc;
+          if (int rc = sjpeg_hip_sharp_yuv_ragged(e, format, static_cast<int>(sharp.size()), sharp.data(), yuv[0].data(), yuv[1].data(),
+                                                  yuv[2].data(), ws, wsz, stream)) return rc;
+          for (size_t k = 0; k < planar.size(); ++k) s[s.size() - planar.size() + k].fr = planar[k];
         }
       }
       // the hooks
       for (Frame& fs : s) {
         const int f = fs.index;
         const sjpeg_hip_search& sp = P.search[P.search_per_frame ? f : 0];
-        fs.passes = std::min(std::max(static_cast<int>(sp.passes), 1), 20);
+        fs.passes = passes_of(P, f);
         sjpeg::EncoderParam param;
         param.SetQuantization(P.quant[P.quant_per_frame ? f : 0]);
         param.target_mode = sp.target_mode == 1 ? sjpeg::EncoderParam::TARGET_SIZE : sjpeg::EncoderParam::TARGET_PSNR;
@@ -592,8 +544,8 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
       c.d_qin = base + (c.adaptive ? static_cast<size_t>(n) * kHist : 0);
       c.d_qout = c.d_qin + static_cast<size_t>(n) * 128;
       c.d_sums = reinterpret_cast<int64_t*>(c.d_qout + static_cast<size_t>(n) * 128);
-      c.d_tot = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(c.d_sums) + static_cast<size_t>(n) * kAdaptSumsBytes);
-      c.d_meas = reinterpret_cast<uint8_t*>(c.d_tot) + static_cast<size_t>(n) * kAdaptTotBytes;
+      c.d_tot = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(c.d_sums) + static_cast<size_t>(n) * kSums);
+      c.d_meas = reinterpret_cast<uint8_t*>(c.d_tot) + static_cast<size_t>(n) * kTot;
       std::vector<sjpeg_hip_ragged_frame> gfr;
       for (const Group& g : groups) {
         if (!c.adaptive) break;
@@ -638,9 +590,102 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
   }
 }
 
+// sjpeg_hip_encode_ragged_full_src / _full_packed_src
+int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+              const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+              void* stream, const sjpeg_internal::PackedSink* sink) {
+  const sjpeg_hip_ragged_params& P = *params;
+  const int yuv_mode = P.yuv_mode, method = P.method;
+  // ---- the checks, all of them before the engine is touched
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return set_error(SJPEG_HIP_EINVAL, who + ": params->yuv_mode outside 0..4 (SjpegYUVMode)");
+  if (method < 0 || method > 8) return set_error(SJPEG_HIP_EINVAL, who + ": params->method outside 0..8");
+  if (P.qdelta_max_luma < -12 || P.qdelta_max_luma > 12 || P.qdelta_max_chroma < -12 || P.qdelta_max_chroma > 12) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": params->qdelta_max outside -12 .. 12");
+  }
+  if (P.quant == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params->quant == NULL");
+  const bool by_mode = yuv_mode == kYuvAuto || yuv_mode == kYuvSharp;
+  if (by_mode && format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA &&
+      format != SJPEG_HIP_SRC_RGB_PLANAR) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO and SJPEG_YUV_SHARP take RGB, BGRA or RGBA (packed) or planar RGB sources");
+  }
+  for (int k = 0; P.search != nullptr && k < (P.search_per_frame ? nframes : 1); ++k) {
+    const sjpeg_hip_search& sp = P.search[k];
+    if (sp.target_mode != 1 && sp.target_mode != 2) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "] (frame " + std::to_string(k) +
+                                             "): target_mode must be 1 (size) or 2 (PSNR)");
+    }
+    if (!std::isfinite(sp.target_value)) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "] (frame " + std::to_string(k) + "): the target is not finite");
+    }
+  }
+  if (int rc = sjpeg_internal::ragged_check(who, format, by_mode ? SJPEG_HIP_YUV444 : yuv_mode, nframes, frames)) return rc;
+  if (sink != nullptr) { if (int rc = sjpeg_internal::engine_pack_begin(e, stream)) return rc; }
+  uint64_t* const stats = sjpeg_internal::engine_full_stats(e);
+  memset(stats, 0, 6 * sizeof(uint64_t));
+  // a search on the ground of sjpeg_hip_encode_ragged_search_src: that entry point's messages, and the counters stay zero
+  bool any_searched = false;
+  for (int f = 0; f < nframes; ++f) any_searched = any_searched || passes_of(P, f) > 1;
+  if (any_searched && !by_mode && method <= 6) {
+    const int rc = sjpeg_internal::ragged_search_flow(e, format, yuv_mode, nframes, frames, P.quant, P.quant_per_frame, P.min_quant,
+                                                      P.q_bias, method, P.qdelta_max_luma, P.qdelta_max_chroma, P.search,
+                                                      P.search_per_frame, q_out, value_out, d_out, d_sizes, stream, sink);
+    if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
+    return rc;
+  }
+  return search_flow(who, e, format, nframes, frames, P, d_out, d_sizes, modes, q_out, value_out, stream, sink, stats);
+}
+
 }  // namespace
 
+// sjpeg_hip_encode_ragged_search_src (sink != NULL: packed output): one sampling, methods 0..6 -- its own checks and
+// messages, then the flow above with one mode group of the caller's format.  The engine's counters are the _full_
+// calls': this one counts into an array of its own.
+int sjpeg_internal::ragged_search_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64],
+                                       int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                       int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search,
+                                       int search_per_frame, float* q_out, float* value_out, void* d_out,
+                                       uint64_t* d_sizes, void* stream, const PackedSink* sink) {
+  static const std::string who = "sjpeg_hip_encode_ragged_search_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (search == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": search == NULL");
+  if (frames == nullptr || quant == nullptr || d_out == nullptr || d_sizes == nullptr) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": frames, quant, d_out or d_sizes == NULL");
+  }
+  if (method < 0 || method > 6) return set_error(SJPEG_HIP_EINVAL, who + ": methods 0..6 (trellis goes through the host API)");
+  if (qdelta_max_luma < -12 || qdelta_max_luma > 12 || qdelta_max_chroma < -12 || qdelta_max_chroma > 12) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
+  }
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  for (int k = 0; k < (search_per_frame ? nframes : 1); ++k) {
+    const sjpeg_hip_search& sp = search[k];
+    if (sp.target_mode != 1 && sp.target_mode != 2) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "]: target_mode must be 1 (size) or 2 (PSNR)");
+    }
+    if (!std::isfinite(sp.target_value)) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "]: the target is not finite");
+    }
+  }
+  if (int rc = sjpeg_internal::ragged_check(who, format, yuv_mode, nframes, frames)) return rc;
+  const sjpeg_hip_ragged_params P = {yuv_mode, method, quant, quant_per_frame, min_quant, q_bias, qdelta_max_luma, qdelta_max_chroma,
+                                     search, search_per_frame};
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+  return search_flow(who, e, format, nframes, frames, P, d_out, d_sizes, nullptr, q_out, value_out, stream, sink, stats);
+}
+
 extern "C" {
+
+int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64],
+                                       int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
+                                       int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search,
+                                       int search_per_frame, float* q_out, float* value_out, void* d_out,
+                                       uint64_t* d_sizes, void* stream) {
+  return sjpeg_internal::ragged_search_flow(e, format, yuv_mode, nframes, frames, quant, quant_per_frame, min_quant, q_bias,
+                                            method, qdelta_max_luma, qdelta_max_chroma, search, search_per_frame, q_out,
+                                            value_out, d_out, d_sizes, stream, nullptr);
+}
 
 int sjpeg_hip_encode_ragged_full_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
                                      const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes,

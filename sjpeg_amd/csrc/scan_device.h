@@ -169,7 +169,7 @@ __device__ __forceinline__ ScanArgs ragged_histo_view(const ScanArgs& in, int* s
 template <bool COMPACT> struct Lds;
 template <> struct Lds<false> {
   static constexpr int kSlots = kScanThreads;
-  static constexpr int kSamplesBytes = kSlots * kSlotBytes;      // 36864
+  static constexpr int kSamplesBytes = kSlots * kSlotBytes;      // 36 864
   static constexpr int kWinWords = 2048;                         // LDS bit window, 32-bit MSB-first words (8 KiB)
   static constexpr int kOffWin = kSamplesBytes;
   // The quantizer table (1 KiB) and the DC codes are only read before the bit window is first

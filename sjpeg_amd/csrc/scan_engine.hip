@@ -48,6 +48,8 @@
 #include "jpeg_host.h"
 #include "ragged_aux.h"
 
+using namespace sjpeg_internal;      // (the shared sizes, SjpegYUVMode and the mode groups)
+
 namespace {
 
 #include "scan_device.h"
@@ -1352,8 +1354,6 @@ struct RaggedLaunch {
   size_t k1_map, place_map, stuff_map;     // where the launch's maps start in the u32 part of the blob
 };
 
-inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
-
 // The source format of a ragged call (as prepare_scan): the kernel's per-format fields in *a (zeroed first), the source
 // class and the number of planes.  who: the entry point, for the messages.
 int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a, int* cls, int* nplanes) {
@@ -2309,11 +2309,8 @@ int sjpeg_hip_adapt_sums(const uint32_t* d_hist, int nframes, const uint8_t quan
 // SinglePassScanOptimized, headers, the scan), done for nframes pictures with one launch per
 // device pass and the per-picture float / Huffman work on the host in between.
 namespace {
-constexpr int kAdaptDeltas = 25;      // candidate steps -12 .. +12 (jpeg_host.h)
-// a frame's share of the batch scratch: its histogram, its adaptation sums and totals, its symbol counts
-constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
-constexpr size_t kSums = 2 * 64 * kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
-constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t);
+// (a frame's share of the batch scratch -- kHist, kSums, kTot, kFreq: ragged_aux.h)
+static_assert(sjpeg_internal::kKeptSegBytes == kKeptSegWords * sizeof(uint32_t), "a segment's kept blocks");
 
 struct BatchScratch {                 // per host thread: device scratch of sjpeg_hip_encode_batch_src
   void* d_hist = nullptr; size_t hist_cap = 0;
@@ -3054,9 +3051,6 @@ int sjpeg_hip_encode_ragged_batch_src(sjpeg_hip_engine* e, int format, int yuv_m
 // ---- ragged batches with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP ----
 namespace {
 
-// SjpegYUVMode (include/sjpeg.h); 1, 3 and 4 are SJPEG_HIP_YUV420 / 444 / 400
-enum { SJPEG_YUV_AUTO_ = 0, SJPEG_YUV_420_ = 1, SJPEG_YUV_SHARP_ = 2, SJPEG_YUV_444_ = 3, SJPEG_YUV_400_ = 4 };
-
 // the engine's upload for the sharp conversion's descriptors (sharp_yuv.hip)
 int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStream_t st) {
   sjpeg_hip_engine* const e = static_cast<sjpeg_hip_engine*>(ctx);
@@ -3205,8 +3199,8 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
   if (int rc = ragged_ordered(e, st)) return rc;
   // the auto_buf of the whole call, once: riskiness descriptors and sums, then the groups' sizes and frame numbers
   if (int rc = e->auto_buf.ensure(std::max((align16(sizeof(sjpeg_internal::RiskFrame) * n) + n * 24 + 15) / 16 + 1, (n * 12 + 15) / 16 + 1))) return rc;
-  std::vector<int> mode(n, yuv_mode == SJPEG_YUV_AUTO_ ? SJPEG_YUV_SHARP_ : yuv_mode);
-  if (yuv_mode == SJPEG_YUV_AUTO_) {
+  std::vector<int> mode(n, yuv_mode == kYuvAuto ? kYuvSharp : yuv_mode);
+  if (yuv_mode == kYuvAuto) {
     // 1. the riskiness of every frame (the table on this device, uploaded again when it changed), one read-back
     const uint8_t* d_table = nullptr;
     if (int rc = engine_risk_table(e, who, st, &d_table)) return rc;
@@ -3223,10 +3217,6 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
   if (modes != nullptr) for (size_t f = 0; f < n; ++f) modes[f] = mode[f];
   // parts of consecutive frames whose sharp planes and workspace (and kept blocks, with the trellis) stay inside the
   // scratch limit (one frame at least)
-  auto planes_bytes = [](const sjpeg_hip_ragged_frame& fr) {
-    const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
-    return align16(static_cast<size_t>(fr.width) * fr.height) + 2 * align16(cw * ch);
-  };
   std::vector<std::pair<size_t, size_t>> parts;    // [first, end)
   size_t arena = 0;
   {
@@ -3234,8 +3224,7 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
     std::vector<sjpeg_hip_ragged_frame> sharp;
     auto kept_bytes = [&](size_t f) -> size_t {
       FrameGeo g;
-      const int m = mode[f] == SJPEG_YUV_444_ ? SJPEG_HIP_YUV444 : mode[f] == SJPEG_YUV_400_ ? SJPEG_HIP_YUV400 : SJPEG_HIP_YUV420;
-      return frame_geo(frames[f].width, frames[f].height, m, &g) ? static_cast<size_t>(g.nseg) * kKeptSegWords * sizeof(uint32_t) : 0;
+      return frame_geo(frames[f].width, frames[f].height, hip_yuv_mode(mode[f]), &g) ? static_cast<size_t>(g.nseg) * kKeptSegBytes : 0;
     };
     auto close = [&](size_t end) {
       const size_t ws = sharp.empty() ? 0 : sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
@@ -3247,7 +3236,7 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
       counted = 0;
     };
     for (size_t f = 0; f < n; ++f) {
-      const bool is_sharp = mode[f] == SJPEG_YUV_SHARP_;
+      const bool is_sharp = mode[f] == kYuvSharp;
       if (!is_sharp && !trellis) continue;
       const size_t b = (is_sharp ? planes_bytes(frames[f]) + sjpeg_internal::sharp_ragged_workspace(1, &frames[f]) : 0) +
                        (trellis ? kept_bytes(f) : 0);
@@ -3263,25 +3252,16 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
   }
   for (const auto& part : parts) {
     // 3. the sharp frames of the part go into the arena: Y, U, V tightly packed, then the workspace
-    std::vector<sjpeg_hip_ragged_frame> sharp;
-    std::vector<uint8_t*> py, pu, pv;
-    uint8_t* at = reinterpret_cast<uint8_t*>(e->sharp_arena.p);
-    for (size_t f = part.first; f < part.second; ++f) {
-      if (mode[f] != SJPEG_YUV_SHARP_) continue;
-      const sjpeg_hip_ragged_frame& fr = frames[f];
-      const size_t cw = (static_cast<size_t>(fr.width) + 1) / 2, ch = (static_cast<size_t>(fr.height) + 1) / 2;
-      sharp.push_back(fr);
-      py.push_back(at); at += align16(static_cast<size_t>(fr.width) * fr.height);
-      pu.push_back(at); at += align16(cw * ch);
-      pv.push_back(at); at += align16(cw * ch);
-    }
+    std::vector<sjpeg_hip_ragged_frame> sharp, planar;
+    std::vector<uint8_t*> yuv[3];
+    for (size_t f = part.first; f < part.second; ++f) if (mode[f] == kYuvSharp) sharp.push_back(frames[f]);
+    uint8_t* const ws = place_sharp_planes(reinterpret_cast<uint8_t*>(e->sharp_arena.p), sharp, &planar, yuv);
     // (enqueued by ragged_batch_groups in front of the first kernel that reads the sharp group, its last)
     auto convert = [&]() -> int {
-      uint8_t* const ws = reinterpret_cast<uint8_t*>(e->sharp_arena.p) + align16(static_cast<size_t>(at - reinterpret_cast<uint8_t*>(e->sharp_arena.p)));
       const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
       std::string err;
-      if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), py.data(), pu.data(),
-                                                    pv.data(), ws, wsz, st, engine_upload, e, &err)) {
+      if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), yuv[0].data(), yuv[1].data(),
+                                                    yuv[2].data(), ws, wsz, st, engine_upload, e, &err)) {
         return fail(rc, who + ": " + err);
       }
       mark("sharp launched");
@@ -3289,24 +3269,13 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
     };
     // 4. the mode groups: 4:2:0, 4:4:4, 4:0:0 of the caller's format, then the sharp frames as planar 4:2:0
     std::vector<RaggedGroup> groups;
-    const int kinds[4] = {SJPEG_YUV_420_, SJPEG_YUV_444_, SJPEG_YUV_400_, SJPEG_YUV_SHARP_};
-    for (int kind : kinds) {
+    for (int kind : kGroupKinds) {
       RaggedGroup g;
-      g.format = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_SRC_YUV420 : format;
-      g.yuv_mode = kind == SJPEG_YUV_SHARP_ ? SJPEG_HIP_YUV420 : kind;     // (SjpegYUVMode 1, 3, 4 = SJPEG_HIP_YUV*)
-      size_t k = 0;
+      g.format = group_format(kind, format);
+      g.yuv_mode = hip_yuv_mode(kind);
       for (size_t f = part.first; f < part.second; ++f) {
-        if (mode[f] != SJPEG_YUV_SHARP_) {
-          if (mode[f] == kind) { g.frames.push_back(frames[f]); g.index.push_back(static_cast<int>(f)); }
-          continue;
-        }
-        if (kind != SJPEG_YUV_SHARP_) continue;
-        sjpeg_hip_ragged_frame fr = frames[f];
-        const int64_t cw = (static_cast<int64_t>(fr.width) + 1) / 2;
-        fr.plane[0] = py[k]; fr.plane[1] = pu[k]; fr.plane[2] = pv[k];
-        fr.row_stride[0] = fr.width; fr.row_stride[1] = cw; fr.row_stride[2] = cw;
-        ++k;
-        g.frames.push_back(fr);
+        if (mode[f] != kind) continue;
+        g.frames.push_back(kind == kYuvSharp ? planar[g.frames.size()] : frames[f]);
         g.index.push_back(static_cast<int>(f));
       }
       if (g.frames.empty()) continue;
@@ -3330,8 +3299,8 @@ static int ragged_auto_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int n
                             int* modes, void* stream, const sjpeg_internal::PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_auto_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
-  if (yuv_mode != SJPEG_YUV_AUTO_ && yuv_mode != SJPEG_YUV_SHARP_) {
+  if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
+  if (yuv_mode != kYuvAuto && yuv_mode != kYuvSharp) {
     const int rc = sjpeg_internal::ragged_batch_flow(e, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant,
                                                      q_bias, method, qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, stream, sink);
     if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
@@ -3374,7 +3343,7 @@ static int ragged_trellis_flow(sjpeg_hip_engine* e, int format, int yuv_mode, in
                                int* modes, void* stream, const sjpeg_internal::PackedSink* sink) {
   static const std::string who = "sjpeg_hip_encode_ragged_trellis_src";
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (yuv_mode < SJPEG_YUV_AUTO_ || yuv_mode > SJPEG_YUV_400_) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
+  if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode outside 0..4 (SjpegYUVMode)");
   if (frames == nullptr || quant_in == nullptr || d_out == nullptr || d_sizes == nullptr) {
     return fail(SJPEG_HIP_EINVAL, who + ": frames, quant, d_out or d_sizes == NULL");
   }
@@ -3383,7 +3352,7 @@ static int ragged_trellis_flow(sjpeg_hip_engine* e, int format, int yuv_mode, in
     return fail(SJPEG_HIP_EINVAL, who + ": qdelta_max outside -12 .. 12");
   }
   try {
-    if (yuv_mode == SJPEG_YUV_AUTO_ || yuv_mode == SJPEG_YUV_SHARP_) {
+    if (yuv_mode == kYuvAuto || yuv_mode == kYuvSharp) {
       if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
       std::vector<FrameGeo> geo;                   // (the output ranges)
       if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
@@ -3462,7 +3431,7 @@ int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* e, int format, int nfra
 
 }  // extern "C"
 
-// what sjpeg_hip_encode_ragged_full_src (ragged_full.cc) takes from the flows above
+// what the search (ragged_full.cc) takes from the flows above
 int sjpeg_internal::ragged_unsearched_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                            const sjpeg_hip_ragged_frame* frames, const uint8_t (*quant)[2][64], int quant_per_frame,
                                            const uint8_t* min_quant, int q_bias, int method, int qdelta_max_luma,

@@ -227,6 +227,40 @@ def test_split_launches(monkeypatch):
     small.close()
 
 
+@pytest.mark.parametrize("method", [0, 3, 4])
+def test_both_kinds_an_unsearched_frame_and_parts_in_one_call(monkeypatch, oracle, method):
+    """Size and PSNR targets, a frame that is not searched and a part split in one call: every frame is the oracle's,
+    the split call equals the unsplit one, and the packed twin codes the unsearched frame first.  (On the oracle, with
+    these targets, frames 0 and 4 -- size -- and 1 and 5 -- PSNR -- still change between 3 and 4 passes, whatever the
+    method: no search here stops at its first pass.)"""
+    dims = [(1, 1), (17, 13), (48, 40), (136, 104), (250, 130), (136, 104)]
+    imgs = [_content(k, w, h) for k, (w, h) in enumerate(dims)]
+    q75 = [len(oracle.encode_method(im, 75.0, sj.YUV_420, method)) for im in imgs]
+    search = [_search(1, q75[k] * 0.5, passes=4) if k % 2 == 0 else _search(2, 38.0, passes=4) for k in range(len(imgs))]
+    search[2].passes = 1
+    want = [_want(oracle, im, 75.0, sj.YUV_420, method, search[k]) for k, im in enumerate(imgs)]
+    args = (sj.SRC_RGB, _dev(imgs), dims, sj.YUV_420, _quant(75.0))
+    eng = sj.Engine(0)
+    whole = eng.encode_ragged_search(*args, search, method)
+    whole_bytes = _frames(*whole[:3])
+    out, sizes, offsets, _, pq, pvalue = eng.encode_ragged_packed(*args, method, search=search)
+    off, sz, host = offsets.cpu().tolist(), sizes.cpu().tolist(), out.cpu().numpy()
+    eng.close()
+    monkeypatch.setenv("SJPEG_HIP_SCRATCH_LIMIT_BYTES", "1")      # (every searched frame a part of its own)
+    small = sj.Engine(0)
+    split = small.encode_ragged_search(*args, search, method)
+    split_bytes = _frames(*split[:3])
+    small.close()
+    for k in range(len(imgs)):
+        assert whole_bytes[k] == want[k], (method, k)
+    assert split_bytes == whole_bytes and split[3:] == whole[3:]
+    q, value = whole[3:]
+    assert [k for k in range(len(imgs)) if q[k] == -1.0] == [2] and [k for k in range(len(imgs)) if value[k] == -1.0] == [2]
+    assert off[2] == 0 and all(off[k] > 0 for k in range(len(imgs)) if k != 2)
+    assert [host[off[k]:off[k] + sz[k]].tobytes() for k in range(len(imgs))] == want
+    assert (pq, pvalue) == (q, value)
+
+
 def test_capacity(engine, oracle):
     imgs = [_content(k, w, h) for k, (w, h) in enumerate([(64, 64), (250, 130), (97, 61), (640, 480)])]
     search = _search(1, 6000.0)
