@@ -102,7 +102,10 @@ enum {
   SJPEG_HIP_SRC_YUV420 = 5,    /* Y + subsampled U, V     -> 420 */
   SJPEG_HIP_SRC_NV12 = 6,      /* Y + interleaved U,V     -> 420 */
   SJPEG_HIP_SRC_NV21 = 7,      /* Y + interleaved V,U     -> 420 */
-  SJPEG_HIP_SRC_RGB_PLANAR = 8 /* 3 full-size planes R,G,B -> any of 420 / 444 / 400 */
+  SJPEG_HIP_SRC_RGB_PLANAR = 8, /* 3 full-size planes R,G,B -> any of 420 / 444 / 400 */
+  SJPEG_HIP_SRC_RGB_PLANAR_F32 = 9,   /* the same planes of float elements (below): fp32 ... */
+  SJPEG_HIP_SRC_RGB_PLANAR_F16 = 10,  /* ... IEEE half ... */
+  SJPEG_HIP_SRC_RGB_PLANAR_BF16 = 11  /* ... bfloat16 */
 };
 /* SJPEG_HIP_SRC_RGB_PLANAR (channel-first pictures: a [3, H, W] or [N, 3, H, W] array, or any crop of one):
  * plane[0..2] are R, G, B, each width x height bytes; the bytes produced are those of the same pixels handed over
@@ -112,7 +115,24 @@ enum {
  * ragged calls, the frame.  The rule lets the three planes share one per-thread offset: the kernels address
  * G and B as R's address plus a uniform 64-bit distance, plane[1] - plane[0] and plane[2] - plane[0].
  * Taken by every entry point that takes a `format` or a sjpeg_hip_source, SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, the
- * riskiness and the sharp conversion included (there it counts as an RGB source beside RGB, BGRA and RGBA). */
+ * riskiness and the sharp conversion included (there it counts as an RGB source beside RGB, BGRA and RGBA).
+ *
+ * SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 (what a network puts out: channel-first float tensors, values in 0..1
+ * or -1..1): the layout and the one-pitch rule of SJPEG_HIP_SRC_RGB_PLANAR with elements of 4 or 2 bytes.  Strides
+ * stay in BYTES and may be negative; |row_stride| >= width * element size; plane pointers, row strides and frame
+ * strides must be multiples of the element size -- the only alignment the kernels assume, so a crop of a wider
+ * tensor at an odd column works.  A violation is SJPEG_HIP_EINVAL before any device work; the message names the
+ * stride or plane and, in ragged calls, the frame.  A sample x becomes the byte the encoder sees by
+ *     t  = fmaf((float)x, scale, bias)           ONE fp32 rounding; (float)x is exact for half and bfloat16
+ *     u8 = isnan(t) ? 0 : (uint8) rint(min(max(t, 0), 255))       round half to even; +-inf saturate
+ * with the engine's pixel transform (scale, bias) -- sjpeg_hip_engine_set_pixel_transform(), 255 and 0 by default --
+ * and the JPEG bytes are exactly those of the uint8 picture so defined handed over as SJPEG_HIP_SRC_RGB_PLANAR.
+ * (It is the fused multiply-add: a host-side restatement must use fmaf, not a product rounded before the sum.)  The
+ * conversion happens in the kernels' loader: no uint8 copy of the batch is made.
+ * Taken by every entry point that has an engine and takes a `format` or a sjpeg_hip_source, in all three samplings,
+ * SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, sjpeg_hip_riskiness_ragged_src and sjpeg_hip_sharp_yuv_ragged included.  The two
+ * calls without an engine, sjpeg_hip_riskiness_sums and sjpeg_hip_sharp_yuv, have no transform to read and refuse the
+ * three formats (SJPEG_HIP_EINVAL; the message names the ragged call to use). */
 typedef struct sjpeg_hip_source {
   int32_t format;              /* SJPEG_HIP_SRC_* */
   int32_t reserved;            /* 0 */
@@ -355,6 +375,14 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
  * wait for the engine's stream first).  Off by default; switching it off drains the engine.  (The
  * engine's stream is made by the first call that switches the mode on: do that early too.) */
 int sjpeg_hip_engine_set_pipelined(sjpeg_hip_engine* engine, int on);
+
+/* The pixel transform of the float source formats (SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16, above): a sample x is
+ * coded as the byte rint(clamp(fmaf(x, scale, bias), 0, 255)).  255 and 0 when the engine is made (values in 0..1);
+ * 127.5 and 127.5 take values in -1..1.  Engine state: sticky until set again, inherited by everything a call runs on
+ * the engine's behalf, ignored by every other format.  A non-finite scale or bias is SJPEG_HIP_EINVAL and changes
+ * nothing.  Not ordered on any stream: it holds for the calls made after it. */
+int sjpeg_hip_engine_set_pixel_transform(sjpeg_hip_engine* engine, float scale, float bias);
+int sjpeg_hip_engine_get_pixel_transform(const sjpeg_hip_engine* engine, float* scale, float* bias);
 int sjpeg_hip_engine_wait(sjpeg_hip_engine* engine, void* stream);
 
 /* A batch whose frames each carry their OWN tables and header -- what a batch of the reference's

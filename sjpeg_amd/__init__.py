@@ -41,6 +41,10 @@ RESTART_MARKERS = 8      # optional restart-marker mode (sjpeg_hip.h): not the r
 
 SRC_RGB, SRC_BGRA, SRC_RGBA, SRC_GRAY, SRC_YUV444, SRC_YUV420, SRC_NV12, SRC_NV21 = range(8)
 SRC_RGB_PLANAR = 8       # R, G and B planes of one pitch (channel-first pictures): sjpeg_hip.h
+# ... and the same planes of float elements, turned into bytes by the engine's pixel transform as they are read
+SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16 = 9, 10, 11
+_PLANAR_RGB = (SRC_RGB_PLANAR, SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16)
+_FLOAT_ELEMENT_BYTES = {SRC_RGB_PLANAR_F32: 4, SRC_RGB_PLANAR_F16: 2, SRC_RGB_PLANAR_BF16: 2}
 _IMPLIED_MODE = {SRC_GRAY: YUV_400, SRC_YUV444: YUV_444, SRC_YUV420: YUV_420, SRC_NV12: YUV_420,
                  SRC_NV21: YUV_420}
 
@@ -95,6 +99,8 @@ def band_bound(w, h, yuv_mode, seg_begin, seg_end):
 def make_source(fmt, planes):
     """planes: CUDA uint8 tensors [F, rows, row_bytes] (one per plane of the layout).
     Returns (Source, nframes); the tensors must outlive the calls that use it.
+    SRC_RGB_PLANAR_F32 / _F16 / _BF16: planes = (R, G, B) as for SRC_RGB_PLANAR, of torch.float32 / float16 / bfloat16;
+    the strides go in as bytes, and the engine's pixel transform (Engine.set_pixel_transform) makes the bytes.
     SRC_RGB_PLANAR: planes = (R, G, B), the [N, H, W] views x[:, 0], x[:, 1], x[:, 2] of an [N, 3, H, W] tensor (or of
     any crop of one): the three share their row and frame strides.
     With that layout a dimension of size 1 is never stepped over, so whatever stride torch reports for it is not looked
@@ -103,13 +109,45 @@ def make_source(fmt, planes):
     checked and handed over as they always were."""
     s = Source()
     s.format = fmt
-    planar = fmt == SRC_RGB_PLANAR
+    planar = fmt in _PLANAR_RGB
+    esz = _FLOAT_ELEMENT_BYTES.get(fmt, 1)
     for i, t in enumerate(planes):
         assert t.is_cuda and t.dim() == 3 and (t.stride(2) == 1 or (planar and t.shape[2] == 1))
+        assert esz == 1 or t.dtype == _float_dtypes()[fmt]
         s.plane[i] = t.data_ptr()
-        s.row_stride[i] = t.shape[2] if planar and t.shape[1] == 1 else t.stride(1)
-        s.frame_stride[i] = t.stride(0)
+        s.row_stride[i] = (t.shape[2] if planar and t.shape[1] == 1 else t.stride(1)) * esz
+        s.frame_stride[i] = t.stride(0) * esz
     return s, planes[0].shape[0]
+
+
+def _float_dtypes():
+    import torch
+    return {SRC_RGB_PLANAR_F32: torch.float32, SRC_RGB_PLANAR_F16: torch.float16, SRC_RGB_PLANAR_BF16: torch.bfloat16}
+
+
+class FloatPixels:
+    """Float pictures for the calls that take layout="chw" (encode_images, compress_images, riskiness_images) and for
+    encode_images_full_chw, as their `images`: a sequence of CUDA tensors [3, H_k, W_k] of ONE dtype -- torch.float32,
+    float16 or bfloat16 --, stride 1 over x, any row stride.  A sample x is coded as the byte
+    rint(clamp(fma(x, scale, bias), 0, 255)) (ties to even, NaN -> 0): scale 255, bias 0 for values in 0..1, 127.5 and
+    127.5 for -1..1.  The conversion happens inside the encoder's loader -- no uint8 copy of the batch is made --, and the
+    JPEGs are those of the uint8 pictures so defined.  The call sets the engine's pixel transform (it stays set) and
+    passes SRC_RGB_PLANAR_F32 / _F16 / _BF16."""
+
+    def __init__(self, images, scale=255.0, bias=0.0):
+        self.images = list(images)
+        self.scale, self.bias = float(scale), float(bias)
+        if not (np.isfinite(self.scale) and np.isfinite(self.bias)):
+            raise SjpegError("FloatPixels: scale and bias must be finite")
+
+
+def _float_pixels(who, images, chw):
+    """(the images of a call, its FloatPixels or None)"""
+    if not isinstance(images, FloatPixels):
+        return images, None
+    if not chw:
+        raise SjpegError(f"{who}: FloatPixels are channel-first pictures [3, H, W]: pass layout='chw'")
+    return images.images, images
 
 
 class RaggedFrame(C.Structure):
@@ -228,6 +266,10 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_encode_batch_src.restype = C.c_int
     L.sjpeg_hip_engine_set_pipelined.argtypes = [C.c_void_p, C.c_int]
     L.sjpeg_hip_engine_set_pipelined.restype = C.c_int
+    L.sjpeg_hip_engine_set_pixel_transform.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.sjpeg_hip_engine_set_pixel_transform.restype = C.c_int
+    L.sjpeg_hip_engine_get_pixel_transform.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.sjpeg_hip_engine_get_pixel_transform.restype = C.c_int
     L.sjpeg_hip_engine_wait.argtypes = [C.c_void_p, C.c_void_p]
     L.sjpeg_hip_engine_wait.restype = C.c_int
     L.sjpeg_hip_encode_scan_multi.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -334,7 +376,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_scan_symbol_stats_src", "sjpeg_hip_scan_quant_error_src", "sjpeg_hip_engine_entropy_bits",
     "sjpeg_hip_engine_trim", "sjpeg_hip_host_trim",
     "sjpeg_hip_encode_scan_multi", "sjpeg_hip_scan_symbol_stats_multi",
-    "sjpeg_hip_engine_set_pipelined", "sjpeg_hip_engine_wait", "sjpeg_hip_encode_batch_src",
+    "sjpeg_hip_engine_set_pipelined", "sjpeg_hip_engine_set_pixel_transform", "sjpeg_hip_engine_get_pixel_transform",
+    "sjpeg_hip_engine_wait", "sjpeg_hip_encode_batch_src",
     "sjpeg_hip_optimize_huffman", "sjpeg_hip_make_header_ex", "sjpeg_hip_make_header_meta",
     "sjpeg_hip_sharp_workspace", "sjpeg_hip_sharp_yuv",
     "sjpeg_hip_set_riskiness_table", "sjpeg_hip_has_riskiness_table", "sjpeg_hip_riskiness_sums",
@@ -708,6 +751,18 @@ class Engine:
         """Back-to-back encode calls overlap (stitch of call i under K1 of call i + 1); outputs are
         complete after wait() or a device synchronisation (include/sjpeg_hip.h)."""
         self._chk(lib().sjpeg_hip_engine_set_pipelined(self._h, int(on)), "sjpeg_hip_engine_set_pipelined")
+
+    def set_pixel_transform(self, scale=255.0, bias=0.0):
+        """The transform of the float source formats (SRC_RGB_PLANAR_F32 / _F16 / _BF16): a sample x is coded as the
+        byte rint(clamp(fma(x, scale, bias), 0, 255)).  Sticky; every other format ignores it."""
+        self._chk(lib().sjpeg_hip_engine_set_pixel_transform(self._h, float(scale), float(bias)),
+                  "sjpeg_hip_engine_set_pixel_transform")
+
+    def pixel_transform(self):
+        s, b = C.c_float(), C.c_float()
+        self._chk(lib().sjpeg_hip_engine_get_pixel_transform(self._h, C.byref(s), C.byref(b)),
+                  "sjpeg_hip_engine_get_pixel_transform")
+        return s.value, b.value
 
     def wait(self):
         """Makes the current torch stream wait for everything the engine has in flight."""
@@ -1400,16 +1455,27 @@ def _check_layout(who, layout):
     return layout == "chw"
 
 
-def _chw_planes(who, images):
-    """The planes, dims and device of a layout="chw" call: every image a CUDA uint8 tensor [3, H, W] with stride 1 over
-    x (any row stride: crops of a larger tensor work) -- SRC_RGB_PLANAR, its R, G and B planes im[0], im[1], im[2]."""
+def _chw_planes(who, images, fp=None):
+    """The planes, dims, device and format of a layout="chw" call: every image a CUDA uint8 tensor [3, H, W] with stride
+    1 over x (any row stride: crops of a larger tensor work) -- SRC_RGB_PLANAR, its R, G and B planes im[0], im[1],
+    im[2].  fp (the call's FloatPixels): float tensors of one dtype instead, SRC_RGB_PLANAR_F32 / _F16 / _BF16."""
     import torch
     dev = None
+    fmt, esz = SRC_RGB_PLANAR, 1
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
-        if im.dtype != torch.uint8:
-            raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
+        if fp is None:
+            if im.dtype != torch.uint8:
+                raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
+        else:
+            kinds = {d: f for f, d in _float_dtypes().items()}
+            if im.dtype not in kinds:
+                raise SjpegError(f"{who}: image {k} is {im.dtype}: FloatPixels take torch.float32, torch.float16 or "
+                                 f"torch.bfloat16")
+            if k > 0 and im.dtype != images[0].dtype:
+                raise SjpegError(f"{who}: image {k} is {im.dtype}, image 0 {images[0].dtype}: one dtype per call")
+            fmt, esz = kinds[im.dtype], im.element_size()
         if im.dim() != 3 or im.shape[0] != 3 or im.shape[1] < 1 or im.shape[2] < 1 or \
                 (im.stride(2) != 1 and im.shape[2] > 1):
             raise SjpegError(f"{who}: image {k} must be [3, H, W] planar RGB with layout='chw' (stride 1 over x; its "
@@ -1420,10 +1486,11 @@ def _chw_planes(who, images):
             raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {dev}")
     # ((address, row stride) pairs; torch reports any stride for a dimension of size 1, so a one-pixel-wide picture
     # passes with any stride(2), and a one-row picture is handed over with its width as the row stride)
-    planes = [[(im.data_ptr() + c * im.stride(0), im.stride(1) if im.shape[1] > 1 else im.shape[2])
+    # (strides in bytes: esz is the element size, 1 for uint8)
+    planes = [[(im.data_ptr() + c * im.stride(0) * esz, (im.stride(1) if im.shape[1] > 1 else im.shape[2]) * esz)
                for c in range(3)] for im in images]
     dims = [(int(im.shape[2]), int(im.shape[1])) for im in images]
-    return planes, dims, dev
+    return planes, dims, dev, fmt
 
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
@@ -1456,9 +1523,11 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     layout="chw": every image is a CUDA uint8 tensor [3, H_k, W_k] instead -- channel-first, as torch stores pictures --
     with stride 1 over x and any row stride (a crop of a larger tensor works); the pictures go in as SRC_RGB_PLANAR,
     without a repack, and the bytes are those of the same pixels handed over as [H, W, 3].  A call has one layout; the
-    keyword is explicit because [3, W, 3] is both."""
+    keyword is explicit because [3, W, 3] is both.  With layout="chw", images may be a FloatPixels: float32, float16
+    or bfloat16 pictures [3, H_k, W_k], converted to bytes inside the encoder (SRC_RGB_PLANAR_F32 / _F16 / _BF16)."""
     import torch
     chw = _check_layout("encode_images", layout)
+    images, fp = _float_pixels("encode_images", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
     target = target_size if target_size is not None else target_psnr
@@ -1506,13 +1575,15 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             dev = im.device
         elif im.device != dev:
             raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
-    fmt = SRC_RGB_PLANAR if chw else SRC_RGB
+    fmt = SRC_RGB
     if chw:
-        planes, dims, dev = _chw_planes("encode_images", images)
+        planes, dims, dev, fmt = _chw_planes("encode_images", images, fp)
     else:
         planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
         dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -1600,6 +1671,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
                         tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed):
     import torch
     chw = _check_layout("encode_images_full", layout)
+    images, fp = _float_pixels("encode_images_full", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
     target = target_size if target_size is not None else target_psnr
@@ -1631,13 +1703,15 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
             dev = im.device
         elif im.device != dev:
             raise SjpegError(f"encode_images_full: image {k} is on {im.device}, image 0 on {dev}")
-    fmt = SRC_RGB_PLANAR if chw else SRC_RGB
+    fmt = SRC_RGB
     if chw:
-        planes, dims, dev = _chw_planes("encode_images_full", images)
+        planes, dims, dev, fmt = _chw_planes("encode_images_full", images, fp)
     else:
         planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
         dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
     eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -1682,14 +1756,17 @@ def riskiness_images(images, engine=None, layout="hwc"):
     takes them."""
     import torch
     chw = _check_layout("riskiness_images", layout)
+    images, fp = _float_pixels("riskiness_images", images, chw)
     images = list(images)
     if not images:
         raise SjpegError("riskiness_images: no images")
     if chw:
-        planes, dims, dev = _chw_planes("riskiness_images", images)
+        planes, dims, dev, fmt = _chw_planes("riskiness_images", images, fp)
         eng = engine or Engine(dev.index or 0)
+        if fp is not None:
+            eng.set_pixel_transform(fp.scale, fp.bias)
         with torch.cuda.device(dev):
-            sums = eng.riskiness_ragged(SRC_RGB_PLANAR, planes, dims).cpu().numpy()
+            sums = eng.riskiness_ragged(fmt, planes, dims).cpu().numpy()
         return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \

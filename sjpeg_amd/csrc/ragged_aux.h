@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "jpeg_host.h"
+#include "pixel_elem.h"
 #include "sjpeg_hip.h"
 
 namespace sjpeg_internal {
@@ -67,6 +68,10 @@ inline bool rgb_layout(int format, int* pix_step, long long* r_off, long long* g
     case SJPEG_HIP_SRC_BGRA: *pix_step = 4; *r_off = 2; *g_off = 1; *b_off = 0; return true;
     case SJPEG_HIP_SRC_RGBA: *pix_step = 4; *r_off = 0; *g_off = 1; *b_off = 2; return true;
     case SJPEG_HIP_SRC_RGB_PLANAR: *pix_step = 1; *r_off = 0; *g_off = 0; *b_off = 0; return true;
+    // (float planes: a pixel step of one element; the kernels read the samples through pixel_elem.h)
+    case SJPEG_HIP_SRC_RGB_PLANAR_F32: *pix_step = 4; *r_off = 0; *g_off = 0; *b_off = 0; return true;
+    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
+    case SJPEG_HIP_SRC_RGB_PLANAR_BF16: *pix_step = 2; *r_off = 0; *g_off = 0; *b_off = 0; return true;
     default: return false;
   }
 }
@@ -75,7 +80,7 @@ inline bool rgb_layout(int format, int* pix_step, long long* r_off, long long* g
 inline void rgb_frame_offsets(int format, const void* const* plane, long long* g_off, long long* b_off) {
   int step = 0;
   long long r = 0;
-  if (!rgb_layout(format, &step, &r, g_off, b_off) || format != SJPEG_HIP_SRC_RGB_PLANAR) return;
+  if (!rgb_layout(format, &step, &r, g_off, b_off) || !is_rgb_planar(format)) return;
   *g_off = static_cast<const uint8_t*>(plane[1]) - static_cast<const uint8_t*>(plane[0]);
   *b_off = static_cast<const uint8_t*>(plane[2]) - static_cast<const uint8_t*>(plane[0]);
 }
@@ -88,6 +93,21 @@ inline const char* rgb_planar_fault(const void* const* plane, const int64_t* row
   if (frame_stride != nullptr && frame_stride[1] != frame_stride[0]) return "frame_stride[1] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
   if (frame_stride != nullptr && frame_stride[2] != frame_stride[0]) return "frame_stride[2] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
   return nullptr;
+}
+// what is wrong with the addresses of a float-planar picture (SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: planes and
+// strides are multiples of the element size -- all the alignment the kernels assume), or empty; nplanes: how many of
+// plane[] and the strides the caller has checked for presence
+inline std::string rgb_float_fault(int format, const void* const* plane, const int64_t* row_stride, const int64_t* frame_stride,
+                                   int nplanes = 3) {
+  const int64_t esz = elem_bytes(elem_kind(format));
+  if (esz == 1) return std::string();
+  const std::string tail = " must be a multiple of the element size (" + std::to_string(esz) + " bytes)";
+  for (int i = 0; i < nplanes; ++i) {
+    if (reinterpret_cast<uintptr_t>(plane[i]) % static_cast<uintptr_t>(esz) != 0) return "plane[" + std::to_string(i) + "]" + tail;
+    if (row_stride[i] % esz != 0) return "row_stride[" + std::to_string(i) + "]" + tail;
+    if (frame_stride != nullptr && frame_stride[i] % esz != 0) return "frame_stride[" + std::to_string(i) + "]" + tail;
+  }
+  return std::string();
 }
 
 // ---- ragged riskiness: one descriptor per frame; a workgroup finds its frame by a binary search over wg_base
@@ -110,13 +130,14 @@ inline void risk_frame_plan(int W, int H, RiskFrame* d) {
 }
 
 // d_sums[nframes][3] zeroed, then the flat grid of total_wgs workgroups over d_frames[nframes] (device memory)
-int risk_ragged_launch(int format, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
+// (pscale, pbias: the engine's pixel transform, read by the float formats alone)
+int risk_ragged_launch(int format, float pscale, float pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
                        const uint8_t* d_table, uint64_t* d_sums, hipStream_t st);
 
 // ---- ragged sharp conversion (sjpeg_hip_sharp_yuv_ragged); the descriptors go into the workspace through `up`
 using UploadFn = int (*)(void* ctx, void* d_dst, const void* src, size_t bytes, hipStream_t st);
 size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames);
-int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
+int sharp_ragged_run(int format, float pscale, float pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err);
 

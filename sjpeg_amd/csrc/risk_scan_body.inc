@@ -1,19 +1,20 @@
 // risk_scan_body.inc -- the body of risk_scan (riskiness.hip) and of its ragged twin risk_scan_ragged, included
 // INSIDE each kernel behind its prologue. It uses the kernel's names: `a` (RiskArgs of the frame), `frame`, `i` (the
-// column), `j0`, `j1` (the rows of the band) and the LDS array `part`. (Textual, not a __device__ function: the
+// column), `j0`, `j1` (the rows of the band), the LDS array `part` and the macro RISK_INDEX(p), the cell index of the
+// pixel at p (the uniform kernel: yuv_index of its bytes; the ragged one: through the element load). (Textual, not a __device__ function: the
 // uniform kernel then reads its arguments exactly as before and compiles to the same code.)
   unsigned long long s_sum = 0;
   uint32_t s_num = 0, g_num = 0;
   if (i < a.W - 1 && j0 < j1) {
     const uint8_t* row = a.rgb + frame * a.frame_stride + static_cast<long long>(j0 - 1) * a.row_stride;
     const long long o0 = static_cast<long long>(i) * a.pix_step, o1 = o0 + a.pix_step;
-    int idx0 = yuv_index(row + o0, a.r_off, a.g_off, a.b_off);
+    int idx0 = RISK_INDEX(row + o0);
     constexpr int gray = (kCells / 2) * (1 + kCells) * kCells;
     constexpr int gray_min = gray - gray % kCells;             // idx = y + 7 * (u + 7 * v): neutral chroma <=> [gray_min, gray_min + 7)
     for (int j = j0; j < j1; ++j) {
-      const int idx1 = yuv_index(row + o1, a.r_off, a.g_off, a.b_off);
+      const int idx1 = RISK_INDEX(row + o1);
       row += a.row_stride;
-      const int idx2 = yuv_index(row + o0, a.r_off, a.g_off, a.b_off);
+      const int idx2 = RISK_INDEX(row + o0);
       const int score = a.table[idx0 + kCells3 * idx1] + a.table[idx0 + kCells3 * idx2] + a.table[idx1 + kCells3 * idx2];
       if (score > kNoiseLevel) { s_sum += static_cast<unsigned long long>(score); ++s_num; }
       g_num += (idx0 >= gray_min && idx0 < gray_min + kCells) ? 1u : 0u;

@@ -30,6 +30,15 @@ __device__ __forceinline__ int yuv_index(const uint8_t* p, long long ro, long lo
   return static_cast<int>(y + u * kCells + v * kCells * kCells);
 }
 
+// the ragged form's samples: bytes as they are, or float elements through the engine's pixel transform (pixel_elem.h)
+__device__ __forceinline__ int yuv_index_elem(const uint8_t* p, long long ro, long long go, long long bo, int kind, float s, float t) {
+  if (kind == sjpeg_internal::kElemU8) return yuv_index(p, ro, go, bo);
+  const uint8_t px[3] = {static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + ro, kind, s, t)),
+                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + go, kind, s, t)),
+                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + bo, kind, s, t))};
+  return yuv_index(px, 0, 1, 2);
+}
+
 struct RiskArgs {
   const uint8_t* rgb;
   long long row_stride, frame_stride;
@@ -38,6 +47,8 @@ struct RiskArgs {
   int W, H;
   const uint8_t* table;                           // [343 * 343]
   unsigned long long* out;                        // [nframes][3]: score_sum, score_num, gray_num
+  int ekind;                                      // ragged form: element kind (pixel_elem.h) and the pixel transform
+  float pscale, pbias;
 };
 
 // One workgroup = 256 columns x a BAND of rows (the grid's y dimension cuts the picture into at most 64 bands): a
@@ -52,7 +63,9 @@ __global__ __launch_bounds__(256) void risk_scan(const RiskArgs a) {
   const int rows = a.H - 1;                                    // positions (i, j), j = 1 .. H - 1 (the row below)
   const int per = (rows + static_cast<int>(gridDim.y) - 1) / static_cast<int>(gridDim.y);
   const int j0 = 1 + static_cast<int>(blockIdx.y) * per, j1 = min(j0 + per, a.H);
+#define RISK_INDEX(p) yuv_index(p, a.r_off, a.g_off, a.b_off)
 #include "risk_scan_body.inc"
+#undef RISK_INDEX
 }
 
 // The ragged form: a flat grid over the batch's workgroups; a workgroup finds its frame by a binary search over the
@@ -77,7 +90,9 @@ __global__ __launch_bounds__(256) void risk_scan_ragged(const RiskArgs common, c
   const int rows = a.H - 1;
   const int per = (rows + d.bands - 1) / d.bands;
   const int j0 = 1 + static_cast<int>(local / static_cast<unsigned>(d.cols)) * per, j1 = min(j0 + per, a.H);
+#define RISK_INDEX(p) yuv_index_elem(p, a.r_off, a.g_off, a.b_off, a.ekind, a.pscale, a.pbias)
 #include "risk_scan_body.inc"
+#undef RISK_INDEX
 }
 
 }  // namespace
@@ -89,6 +104,12 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
     return SJPEG_HIP_EINVAL;
   }
   RiskArgs a;
+  memset(&a, 0, sizeof(a));
+  // (no engine, no pixel transform: float planes go through sjpeg_hip_riskiness_ragged_src)
+  if (sjpeg_internal::is_float_planar(src->format)) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_sums: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
+                                                       "pixel transform: use sjpeg_hip_riskiness_ragged_src");
+  }
   if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
   if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
     if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
@@ -111,11 +132,12 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
 
 namespace sjpeg_internal {
 
-int risk_ragged_launch(int format, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
+int risk_ragged_launch(int format, float pscale, float pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
                        const uint8_t* d_table, uint64_t* d_sums, hipStream_t st) {
   RiskArgs a;
   memset(&a, 0, sizeof(a));
   if (!sjpeg_internal::rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
+  a.ekind = elem_kind(format); a.pscale = pscale; a.pbias = pbias;
   a.table = d_table;
   a.out = reinterpret_cast<unsigned long long*>(d_sums);
   if (hipMemsetAsync(d_sums, 0, static_cast<size_t>(nframes) * 3 * sizeof(uint64_t), st) != hipSuccess) return SJPEG_HIP_ERUNTIME;

@@ -53,10 +53,16 @@ static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 
 
 // source classes the colour phase is specialised for
 // (kSrcRgbPlanar: R, G and B planes of one pitch -- SJPEG_HIP_SRC_RGB_PLANAR; the others: one packed plane, or YUV planes)
-enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2, kSrcRgbPlanar = 3 };
+// (kSrcRgbPlanarF: the same three planes of fp32, half or bfloat16 elements -- SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 /
+// _BF16, ONE class for the three: the element kind is a wave-uniform field of the arguments (ScanArgs::pkind).  The
+// loader turns the elements into bytes as it reads them (pixel_elem.h), so a row of 8 pixels is the planar class's six
+// raw dwords and everything behind the loader is shared with it)
+enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2, kSrcRgbPlanar = 3, kSrcRgbPlanarF = 4 };
 // raw dwords of a row of 8 pixels, and bytes between pixels of a row, of the classes the colour phase converts
+// (kSrcRgbPlanarF: the bytes between pixels are ScanArgs::pesz, 4 or 2)
 template <int SRC> constexpr int kSrcRowWords = (SRC == kSrcRgbx32) ? 8 : 6;
 template <int SRC> constexpr int kSrcPixelBytes = (SRC == kSrcRgb24) ? 3 : (SRC == kSrcRgbPlanar) ? 1 : 4;
+template <int SRC> constexpr bool kSrcIsPlanarRgb = (SRC == kSrcRgbPlanar || SRC == kSrcRgbPlanarF);
 
 struct RaggedFrame;
 
@@ -93,6 +99,10 @@ struct ScanArgs {
   // every workgroup of the launch's flat grid (NULL otherwise)
   const RaggedFrame* rframes;
   const uint32_t* rmap;
+  // kSrcRgbPlanarF: the engine's pixel transform (byte = fmaf(x, pscale, pbias), rounded to even and saturated), the
+  // element kind (pixel_elem.h) and its size in bytes; every other class ignores them
+  float pscale, pbias;
+  int pkind, pesz;
 };
 
 // One frame of a ragged launch, built on the host (scan_engine.hip, "ragged batches"): its geometry, its planes and
@@ -558,7 +568,7 @@ __device__ __forceinline__ void load_row8(const uint8_t* frame, long long row_st
 }
 
 // Raw dwords of 8 consecutive pixels of row y (coordinates clamp to the picture): 6 dwords for
-// packed RGB, 8 for the 4-byte layouts, 6 for planar RGB -- two of R, two of G, two of B.
+// packed RGB, 8 for the 4-byte layouts, 6 for planar RGB (bytes or floats) -- two of R, two of G, two of B.
 // (planar RGB: frame_px is the frame's R plane; G and B lie dg and db bytes from it, whichever the row -- the
 // planes share their pitch)
 template <int SRC>
@@ -566,6 +576,29 @@ __device__ __forceinline__ void load_px8(const ScanArgs& a, const uint8_t* frame
                                          bool inside, uint32_t* w, long long dg = 0, long long db = 0) {
   if (SRC == kSrcRgb24) {
     load_row8(frame_px, a.row_stride[0], a.W, a.H, x0, y, inside, w);
+  } else if (SRC == kSrcRgbPlanarF) {
+    // float elements: converted to bytes as they are read, the planar class's dwords from here on
+    const int kind = a.pkind;
+    const long long esz = a.pesz;
+    if (inside) {
+      const uint8_t* p = frame_px + y * a.row_stride[0] + esz * x0;
+      sjpeg_internal::elem_load8(p, kind, a.pscale, a.pbias, w);
+      sjpeg_internal::elem_load8(p + dg, kind, a.pscale, a.pbias, w + 2);
+      sjpeg_internal::elem_load8(p + db, kind, a.pscale, a.pbias, w + 4);
+    } else {
+      const int yy = y < a.H ? y : a.H - 1;
+      const uint8_t* row = frame_px + yy * a.row_stride[0];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) w[k] = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int xx = (x0 + i) < a.W ? (x0 + i) : a.W - 1;
+        const uint8_t* p = row + esz * xx;
+        w[i >> 2] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p, kind, a.pscale, a.pbias)) << (8 * (i & 3));
+        w[2 + (i >> 2)] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + dg, kind, a.pscale, a.pbias)) << (8 * (i & 3));
+        w[4 + (i >> 2)] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + db, kind, a.pscale, a.pbias)) << (8 * (i & 3));
+      }
+    }
   } else if (SRC == kSrcRgbPlanar) {
     if (inside) {
       const uint8_t* p = frame_px + y * a.row_stride[0] + x0;
@@ -620,7 +653,7 @@ __device__ __forceinline__ void unpack_px8(const ScanArgs& a, const uint32_t* w,
       const uint32_t sel = sl | 0x0c00u | (static_cast<uint32_t>(sl + 3) << 16) | 0x0c000000u;
       bb[j] = __builtin_amdgcn_perm(w[d + 1 < 6 ? d + 1 : 5], w[d], sel);
     }
-  } else if (SRC == kSrcRgbPlanar) {
+  } else if (kSrcIsPlanarRgb<SRC>) {
     // w[0..1]: eight bytes of R, w[2..3]: of G, w[4..5]: of B -- still one permute per register
 #pragma unroll
     for (int i = 0; i < 8; ++i) {

@@ -191,6 +191,9 @@ struct sjpeg_hip_engine {
   hipStream_t batch_lane3 = nullptr;
   hipEvent_t lane_in = nullptr, lane_done[kLanes] = {nullptr, nullptr, nullptr, nullptr};
   bool is_lane = false;                // a child engine: no streams or lanes of its own
+  // the pixel transform of the float source formats (sjpeg_hip_engine_set_pixel_transform): byte = fmaf(x, scale, bias),
+  // rounded to even and saturated; sticky, read by no other format; the lanes take the parent's with every call
+  float pscale = 255.0f, pbias = 0.0f;
   DevBuf<unsigned long long> seg_off, chunk_off, stamps;
   DevBuf<uint32_t> hdr_off;
   bool want_stamps = false;
@@ -324,6 +327,8 @@ int launch_scan(int mode, int src_class, dim3 grid, hipStream_t st, const ScanAr
     case kSrcRgb24: return launch_scan_src<KIND, kSrcRgb24>(mode, grid, st, a);
     case kSrcRgbx32: return launch_scan_src<KIND, kSrcRgbx32>(mode, grid, st, a);
     case kSrcRgbPlanar: return launch_scan_src<KIND, kSrcRgbPlanar>(mode, grid, st, a);
+    // (float planes; the kinds that read no pixel have no twin of their own: the byte-planar class's code serves)
+    case kSrcRgbPlanarF: return launch_scan_src<KIND, (KIND == kKindEncodeReplay || KIND == kKindStatsCoef) ? kSrcRgbPlanar : kSrcRgbPlanarF>(mode, grid, st, a);
     default: return launch_scan_src<KIND, kSrcPlanes>(mode, grid, st, a);
   }
 }
@@ -505,6 +510,12 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     case SJPEG_HIP_SRC_BGRA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
     case SJPEG_HIP_SRC_RGBA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
     case SJPEG_HIP_SRC_RGB_PLANAR: need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcRgbPlanar; break;
+    case SJPEG_HIP_SRC_RGB_PLANAR_F32:
+    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
+    case SJPEG_HIP_SRC_RGB_PLANAR_BF16:
+      a->pkind = sjpeg_internal::elem_kind(src->format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
+      need[0] = need[1] = need[2] = static_cast<int64_t>(a->pesz) * W; nplanes = 3; *src_class = kSrcRgbPlanarF;
+      break;
     case SJPEG_HIP_SRC_GRAY: need[0] = W; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444:
       need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV444;
@@ -532,7 +543,7 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     a->row_stride[i] = src->row_stride[i];
     a->frame_stride[i] = src->frame_stride[i];
   }
-  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
+  if (sjpeg_internal::is_rgb_planar(src->format)) {
     // one pitch, three bases (sjpeg_hip.h): the kernels reach G and B at a uniform distance from R
     for (int i = 1; i < 3; ++i) {
       if (src->row_stride[i] != src->row_stride[0]) {
@@ -542,7 +553,11 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
         return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: frame_stride[" + std::to_string(i) + "] must equal frame_stride[0]");
       }
     }
+    // float planes: addresses and strides in whole elements
+    const std::string efault = sjpeg_internal::rgb_float_fault(src->format, src->plane, src->row_stride, src->frame_stride);
+    if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: " + efault);
   }
+  a->pscale = e->pscale; a->pbias = e->pbias;     // (read by the float class alone)
   if (nplanes == 2) {          // interleaved chroma: U and V walk the same plane
     a->plane[2] = a->plane[1]; a->row_stride[2] = a->row_stride[1]; a->frame_stride[2] = a->frame_stride[1];
   }
@@ -735,6 +750,23 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->k3_pending[0] = e->k3_pending[1] = e->side_pending = e->side_recorded = false;
   e->last_stream_valid = false;
   e->ev_valid = false;
+  return 0;
+}
+
+int sjpeg_hip_engine_set_pixel_transform(sjpeg_hip_engine* e, float scale, float bias) {
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_set_pixel_transform: engine == NULL");
+  if (!(scale - scale == 0.0f) || !(bias - bias == 0.0f)) {      // (neither NaN nor an infinity)
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_set_pixel_transform: scale and bias must be finite");
+  }
+  e->pscale = scale; e->pbias = bias;
+  return 0;
+}
+
+int sjpeg_hip_engine_get_pixel_transform(const sjpeg_hip_engine* e, float* scale, float* bias) {
+  if (e == nullptr || scale == nullptr || bias == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_get_pixel_transform: engine, scale or bias == NULL");
+  }
+  *scale = e->pscale; *bias = e->pbias;
   return 0;
 }
 
@@ -1365,6 +1397,12 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
     case SJPEG_HIP_SRC_BGRA: *cls = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
     case SJPEG_HIP_SRC_RGBA: *cls = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
     case SJPEG_HIP_SRC_RGB_PLANAR: *cls = kSrcRgbPlanar; *nplanes = 3; break;
+    case SJPEG_HIP_SRC_RGB_PLANAR_F32:
+    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
+    case SJPEG_HIP_SRC_RGB_PLANAR_BF16:       // (the engine's pixel transform: ragged_encode / ragged_analysis put it in)
+      *cls = kSrcRgbPlanarF; *nplanes = 3;
+      a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
+      break;
     case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444: *nplanes = 3; implied = SJPEG_HIP_YUV444; a->cstep = 1; break;
     case SJPEG_HIP_SRC_YUV420: *nplanes = 3; implied = SJPEG_HIP_YUV420; a->cstep = 1; break;
@@ -1388,7 +1426,9 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
 int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes, int nframes,
                   const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo) {
   geo->resize(nframes);
-  if (format == SJPEG_HIP_SRC_RGB_PLANAR) nplanes = 3;           // (whatever the caller counts: R, G and B are all read)
+  const bool planar_rgb = sjpeg_internal::is_rgb_planar(format);
+  const int64_t esz = sjpeg_internal::elem_bytes(sjpeg_internal::elem_kind(format));     // (1 but for the float planes)
+  if (planar_rgb) nplanes = 3;                                   // (whatever the caller counts: R, G and B are all read)
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
     const std::string w = who + ": frame " + std::to_string(f) + ": ";
@@ -1396,7 +1436,7 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
       return fail(SJPEG_HIP_EINVAL, w + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
     }
     const int64_t W = fr.width, cw = (W + 1) / 2;
-    int64_t need[3] = {W, W, W};
+    int64_t need[3] = {esz * W, esz * W, esz * W};
     if (format == SJPEG_HIP_SRC_RGB) need[0] = 3 * W;
     else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
     else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
@@ -1406,9 +1446,13 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
       const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
       if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, w + "|row_stride| smaller than a row of the plane");
       // planar RGB: one pitch, three bases (sjpeg_hip.h)
-      if (format == SJPEG_HIP_SRC_RGB_PLANAR && fr.row_stride[i] != fr.row_stride[0]) {
+      if (planar_rgb && fr.row_stride[i] != fr.row_stride[0]) {
         return fail(SJPEG_HIP_EINVAL, w + "row_stride[" + std::to_string(i) + "] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)");
       }
+    }
+    if (esz != 1) {                                              // float planes: addresses and strides in whole elements
+      const std::string efault = sjpeg_internal::rgb_float_fault(format, fr.plane, fr.row_stride, nullptr);
+      if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, w + efault);
     }
     if (out_ranges && fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, w + "out_offset + out_capacity overflows");
   }
@@ -1497,6 +1541,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
                   hipStream_t st, unsigned long long* d_bits, uint32_t* kept, const sjpeg_internal::PackedSink* sink,
                   const uint32_t* kept_base) {
+  a.pscale = e->pscale; a.pbias = e->pbias;       // (the float class's pixel transform)
   const int ntab = tables_per_frame ? nframes : 1;
   if (kept != nullptr && kept_base == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: the ragged replay takes its frames' kept bases");
   if (sink != nullptr && (d_bits != nullptr || d_sizes == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: packed output needs the sizes");
@@ -1724,6 +1769,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
                     const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st,
                     uint32_t* kept = nullptr, const uint32_t* kept_base = nullptr) {
   const bool histogram = pass == kPassHisto, error = pass == kPassError, trellis = pass == kPassStatsTrellis;
+  a.pscale = e->pscale; a.pbias = e->pbias;       // (the float class's pixel transform)
   if (trellis && (kept == nullptr || kept_base == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: the ragged trellis statistics keep their blocks");
   // a partial: one group's / one segment's; a frame's result (words)
   const size_t part_words = histogram ? kHistoPartialWords : error ? 2 : kStatsWords;
@@ -2573,6 +2619,7 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
         }
         if (engine->lane_done[l] == nullptr) HIP_TRY(hipEventCreateWithFlags(&engine->lane_done[l], hipEventDisableTiming));
         lane_e[l] = engine->lane[l];
+        lane_e[l]->pscale = engine->pscale; lane_e[l]->pbias = engine->pbias;
       }
       if (engine->lane_in == nullptr) HIP_TRY(hipEventCreateWithFlags(&engine->lane_in, hipEventDisableTiming));
       if (!sc.EnsureJobEvents(njobs)) return fail(SJPEG_HIP_ENOMEM, "hipEventCreate(batch scratch) failed");
@@ -3060,7 +3107,7 @@ int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStre
 
 // every frame of an RGB / BGRA / RGBA / planar RGB ragged call checked (the message names the frame)
 int rgb_ragged_frames(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames) {
-  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && format != SJPEG_HIP_SRC_RGB_PLANAR) {
+  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format)) {
     return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA (packed) or planar RGB sources");
   }
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
@@ -3093,7 +3140,7 @@ int risk_ragged(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ra
   if (sums_at != nullptr) *sums_at = d_sums;
   if (int rc = upload(e, base, desc.data(), sizeof(sjpeg_internal::RiskFrame) * nframes, st)) return rc;
   if (int rc = sync_uploads(e, st)) return rc;
-  if (sjpeg_internal::risk_ragged_launch(format, reinterpret_cast<const sjpeg_internal::RiskFrame*>(base), nframes,
+  if (sjpeg_internal::risk_ragged_launch(format, e->pscale, e->pbias, reinterpret_cast<const sjpeg_internal::RiskFrame*>(base), nframes,
                                          static_cast<unsigned>(total), d_table, d_sums, st) != 0) {
     return fail(SJPEG_HIP_ERUNTIME, std::string("risk_scan_ragged launch failed: ") + hipGetErrorString(hipGetLastError()));
   }
@@ -3164,11 +3211,11 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
   try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::string err;
-    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && format != SJPEG_HIP_SRC_RGB_PLANAR) {
+    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format)) {
       return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources");
     }
     if (int rc = ragged_ordered(e, st)) return rc;
-    if (int rc = sjpeg_internal::sharp_ragged_run(format, nframes, frames, d_y, d_u, d_v, d_workspace, workspace_size, st,
+    if (int rc = sjpeg_internal::sharp_ragged_run(format, e->pscale, e->pbias, nframes, frames, d_y, d_u, d_v, d_workspace, workspace_size, st,
                                                   engine_upload, e, &err)) {
       return fail(rc, who + ": " + err);
     }
@@ -3260,7 +3307,7 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
     auto convert = [&]() -> int {
       const size_t wsz = sjpeg_internal::sharp_ragged_workspace(static_cast<int>(sharp.size()), sharp.data());
       std::string err;
-      if (int rc = sjpeg_internal::sharp_ragged_run(format, static_cast<int>(sharp.size()), sharp.data(), yuv[0].data(), yuv[1].data(),
+      if (int rc = sjpeg_internal::sharp_ragged_run(format, e->pscale, e->pbias, static_cast<int>(sharp.size()), sharp.data(), yuv[0].data(), yuv[1].data(),
                                                     yuv[2].data(), ws, wsz, st, engine_upload, e, &err)) {
         return fail(rc, who + ": " + err);
       }

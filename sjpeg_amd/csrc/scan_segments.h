@@ -273,8 +273,8 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
     constexpr int kNW = kSrcRowWords<SRC>;                      // dwords per 8 pixels (planar RGB: 2 + 2 + 2)
     // planar RGB: the G and B planes lie a uniform distance from R's, the same in every row and frame (one pitch, equal
     // frame strides: checked on the host) -- a thread's offset into the R plane is its offset into all three
-    const long long dg = (SRC == kSrcRgbPlanar) ? a.plane[1] - a.plane[0] : 0;
-    const long long db = (SRC == kSrcRgbPlanar) ? a.plane[2] - a.plane[0] : 0;
+    const long long dg = kSrcIsPlanarRgb<SRC> ? a.plane[1] - a.plane[0] : 0;
+    const long long db = kSrcIsPlanarRgb<SRC> ? a.plane[2] - a.plane[0] : 0;
 #ifndef SJPEG_HISTO_BATCH
 #define SJPEG_HISTO_BATCH 2
 #endif
@@ -289,7 +289,8 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
     constexpr bool INTERIOR = decltype(interior_tag)::value;
     bool tables_staged = false;
     // interior copy: the strip's row pointer advances by a uniform step (no 64-bit multiply per row)
-    constexpr int kBpp = kSrcPixelBytes<SRC>;
+    // (float planes: the element size is a uniform field, 4 or 2)
+    const int kBpp = (SRC == kSrcRgbPlanarF) ? a.pesz : kSrcPixelBytes<SRC>;
     const long long rs = a.row_stride[0];
     const uint8_t* prow = frame_px + static_cast<long long>(mb_y * PX + yp0 * kRowsPerStrip) * rs + kBpp * x0;
     const long long pstep = static_cast<long long>(ngroups * kRowsPerStrip) * rs;      // uniform
@@ -305,7 +306,12 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
           if (INTERIOR) {
 #pragma unroll
             for (int r = 0; r < kRowsPerStrip; ++r) {
-              if (SRC == kSrcRgbPlanar) {
+              if (SRC == kSrcRgbPlanarF) {
+                // converted as the loads land: the prefetch buffer stays six dwords a row
+                sjpeg_internal::elem_load8(prow + r * rs, a.pkind, a.pscale, a.pbias, raw[it][r]);
+                sjpeg_internal::elem_load8(prow + (r * rs + dg), a.pkind, a.pscale, a.pbias, raw[it][r] + 2);
+                sjpeg_internal::elem_load8(prow + (r * rs + db), a.pkind, a.pscale, a.pbias, raw[it][r] + 4);
+              } else if (SRC == kSrcRgbPlanar) {
                 __builtin_memcpy(raw[it][r], prow + r * rs, 8);
                 __builtin_memcpy(raw[it][r] + 2, prow + (r * rs + dg), 8);
                 __builtin_memcpy(raw[it][r] + 4, prow + (r * rs + db), 8);

@@ -63,6 +63,8 @@ struct SharpArgs {
   uint8_t* y; uint8_t* u; uint8_t* v;
   long long y_frame_stride, uv_frame_stride;
   int stress;                                     // race stress builds only (SJPEG_HIP_ABLATE), else 0
+  int ekind;                                      // ragged form: element kind (pixel_elem.h) and the pixel transform
+  float pscale, pbias;
 };
 
 __device__ __forceinline__ uint32_t lin2gamma(const uint32_t* l2g, uint32_t value) {   // :158-171
@@ -106,7 +108,9 @@ __device__ __forceinline__ void eval_group(const uint32_t* g2l, const uint32_t* 
 __global__ __launch_bounds__(256) void sharp_import(const SharpArgs a) {
   const int frame = blockIdx.z;
   const int c = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
+#define SHARP_PX(p, off) (p)[off]
 #include "sharp_import_body.inc"
+#undef SHARP_PX
 }
 
 // Race stress build (make STRESS=1|2): SHARP_RACE_POINT(n) holds the waves w with (w & 3) == k of the
@@ -678,7 +682,9 @@ __global__ __launch_bounds__(256) void sharp_export(const SharpArgs a) {
 // ---- pictures too small for the iterative conversion (:57-100,674-690): plain averaging
 __global__ __launch_bounds__(64) void sharp_small(const SharpArgs a) {
   const int frame = blockIdx.x;
+#define SHARP_PX(p, off) (p)[off]
 #include "sharp_small_body.inc"
+#undef SHARP_PX
 }
 
 // ---- ragged batches (sjpeg_hip_sharp_yuv_ragged): pictures of different sizes in one call.  Every kernel has a ragged
@@ -743,7 +749,10 @@ __global__ __launch_bounds__(256) void sharp_import_ragged(const SharpArgs commo
   const unsigned local = blockIdx.x - d.io_base;
   const int frame = 0;
   const int c = (local % static_cast<unsigned>(d.gx)) * 256 + threadIdx.x, ry = local / static_cast<unsigned>(d.gx);
+  // (the ragged form's samples: bytes as they are, or float elements through the engine's pixel transform)
+#define SHARP_PX(p, off) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale, a.pbias)
 #include "sharp_import_body.inc"
+#undef SHARP_PX
 }
 
 __global__ __launch_bounds__(256) void sharp_export_ragged(const SharpArgs common, const SharpFrame* frames, int nbig) {
@@ -783,7 +792,9 @@ __global__ __launch_bounds__(64) void sharp_small_ragged(const SharpArgs common,
   a.y = d.y; a.u = d.u; a.v = d.v;
   a.y_frame_stride = 0; a.uv_frame_stride = 0;
   const int frame = 0;
+#define SHARP_PX(p, off) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale, a.pbias)
 #include "sharp_small_body.inc"
+#undef SHARP_PX
 }
 
 GammaTables g_tables;
@@ -840,6 +851,10 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
   if (workspace_size < sjpeg_hip_sharp_workspace(width, height, nframes) || nframes > 65535) return SJPEG_HIP_EINVAL;
   SharpArgs a;
   memset(&a, 0, sizeof(a));
+  if (sjpeg_internal::is_float_planar(src->format)) {   // (no engine, no pixel transform)
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_sharp_yuv: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
+                                                       "pixel transform: use sjpeg_hip_sharp_yuv_ragged");
+  }
   if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
     return SJPEG_HIP_EINVAL;                         // the sharp conversion starts from RGB
   }
@@ -967,11 +982,12 @@ size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames)
   return align256(sizeof(GammaTables)) + align256(sizeof(SharpFrame) * nframes) + align256(ctrl * 4) + blocks;
 }
 
-int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
+int sharp_ragged_run(int format, float pscale, float pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err) {
   SharpArgs a;
   memset(&a, 0, sizeof(a));
+  a.ekind = elem_kind(format); a.pscale = pscale; a.pbias = pbias;
   if (!rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
     *err = "the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources";
     return SJPEG_HIP_EINVAL;
@@ -991,8 +1007,10 @@ int sharp_ragged_run(int format, int nframes, const sjpeg_hip_ragged_frame* fram
     if (fr.plane[0] == nullptr || d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
     const int64_t st_abs = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
     if (st_abs < static_cast<int64_t>(a.pix_step) * fr.width) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
-    if (format == SJPEG_HIP_SRC_RGB_PLANAR) {
+    if (is_rgb_planar(format)) {
       if (const char* fault = rgb_planar_fault(fr.plane, fr.row_stride, nullptr)) { *err = w + fault; return SJPEG_HIP_EINVAL; }
+      const std::string efault = rgb_float_fault(format, fr.plane, fr.row_stride, nullptr);
+      if (!efault.empty()) { *err = w + efault; return SJPEG_HIP_EINVAL; }
     }
   }
   if (workspace_size < sharp_ragged_workspace(nframes, frames)) { *err = "workspace_size below sjpeg_hip_sharp_ragged_workspace()"; return SJPEG_HIP_EINVAL; }
