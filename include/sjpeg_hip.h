@@ -105,7 +105,13 @@ enum {
   SJPEG_HIP_SRC_RGB_PLANAR = 8, /* 3 full-size planes R,G,B -> any of 420 / 444 / 400 */
   SJPEG_HIP_SRC_RGB_PLANAR_F32 = 9,   /* the same planes of float elements (below): fp32 ... */
   SJPEG_HIP_SRC_RGB_PLANAR_F16 = 10,  /* ... IEEE half ... */
-  SJPEG_HIP_SRC_RGB_PLANAR_BF16 = 11  /* ... bfloat16 */
+  SJPEG_HIP_SRC_RGB_PLANAR_BF16 = 11, /* ... bfloat16 */
+  /* one plane of interleaved float pixels (below): 3 elements a pixel, R, G, B -> any of 420 / 444 / 400 */
+  SJPEG_HIP_SRC_RGB_F32 = 12, SJPEG_HIP_SRC_RGB_F16 = 13, SJPEG_HIP_SRC_RGB_BF16 = 14,
+  /* ... 4 elements a pixel, R, G, B and a fourth that is never read */
+  SJPEG_HIP_SRC_RGBA_F32 = 15, SJPEG_HIP_SRC_RGBA_F16 = 16, SJPEG_HIP_SRC_RGBA_BF16 = 17,
+  /* one plane, 1 float element a pixel -> 400 */
+  SJPEG_HIP_SRC_GRAY_F32 = 18, SJPEG_HIP_SRC_GRAY_F16 = 19, SJPEG_HIP_SRC_GRAY_BF16 = 20
 };
 /* SJPEG_HIP_SRC_RGB_PLANAR (channel-first pictures: a [3, H, W] or [N, 3, H, W] array, or any crop of one):
  * plane[0..2] are R, G, B, each width x height bytes; the bytes produced are those of the same pixels handed over
@@ -125,14 +131,30 @@ enum {
  * stride or plane and, in ragged calls, the frame.  A sample x becomes the byte the encoder sees by
  *     t  = fmaf((float)x, scale, bias)           ONE fp32 rounding; (float)x is exact for half and bfloat16
  *     u8 = isnan(t) ? 0 : (uint8) rint(min(max(t, 0), 255))       round half to even; +-inf saturate
- * with the engine's pixel transform (scale, bias) -- sjpeg_hip_engine_set_pixel_transform(), 255 and 0 by default --
+ * with the engine's pixel transform (scale, bias) of the sample's channel -- sjpeg_hip_engine_set_pixel_transform() /
+ * _transform3(), 255 and 0 by default --
  * and the JPEG bytes are exactly those of the uint8 picture so defined handed over as SJPEG_HIP_SRC_RGB_PLANAR.
  * (It is the fused multiply-add: a host-side restatement must use fmaf, not a product rounded before the sum.)  The
  * conversion happens in the kernels' loader: no uint8 copy of the batch is made.
  * Taken by every entry point that has an engine and takes a `format` or a sjpeg_hip_source, in all three samplings,
  * SJPEG_YUV_AUTO / SJPEG_YUV_SHARP, sjpeg_hip_riskiness_ragged_src and sjpeg_hip_sharp_yuv_ragged included.  The two
  * calls without an engine, sjpeg_hip_riskiness_sums and sjpeg_hip_sharp_yuv, have no transform to read and refuse the
- * three formats (SJPEG_HIP_EINVAL; the message names the ragged call to use). */
+ * three formats (SJPEG_HIP_EINVAL; the message names the ragged call to use).
+ *
+ * SJPEG_HIP_SRC_RGB_F32 / _F16 / _BF16, SJPEG_HIP_SRC_RGBA_F32 / _F16 / _BF16 (channels-last tensors, a renderer's
+ * RGBA16F, any [H, W, 3] or [H, W, 4] float array) and SJPEG_HIP_SRC_GRAY_F32 / _F16 / _BF16 (depth maps, masks,
+ * [H, W] floats): ONE plane, plane[0], of float elements; a pixel is `step` = 3, 4 or 1 elements from the next and its
+ * first `channels` = 3, 3 or 1 elements are read -- R, G, B, or the gray value.  plane[1] and plane[2] are ignored, as
+ * for SJPEG_HIP_SRC_RGB.  Strides are in BYTES and may be negative; plane[0], row strides and frame strides are
+ * multiples of the element size, the only alignment assumed; |row_stride| >= ((width - 1) * step + channels) * element
+ * size.  The kernels never read an element that is not a used sample of a pixel of the picture: in particular not the
+ * fourth element of a row's last pixel, so x[..., 1:4] of an ARGB tensor is a legal RGBA source although its last
+ * "alpha" lies outside the allocation.  A violation is SJPEG_HIP_EINVAL before any device work; the message names the
+ * stride or plane and, in ragged calls, the frame.  Samples become bytes as above, channel c = 0, 1, 2 for R, G, B
+ * through scale[c] and bias[c], gray through channel 0; the JPEG bytes are exactly those of the uint8 picture so
+ * defined handed over as SJPEG_HIP_SRC_RGB (the gray formats: as SJPEG_HIP_SRC_GRAY, yuv_mode 4:0:0 only).
+ * Taken where the planar float formats are; the gray ones are refused where SJPEG_HIP_SRC_GRAY is (SJPEG_YUV_AUTO /
+ * SJPEG_YUV_SHARP, the riskiness, the sharp conversion), and the two calls without an engine refuse all nine. */
 typedef struct sjpeg_hip_source {
   int32_t format;              /* SJPEG_HIP_SRC_* */
   int32_t reserved;            /* 0 */
@@ -383,6 +405,12 @@ int sjpeg_hip_engine_set_pipelined(sjpeg_hip_engine* engine, int on);
  * nothing.  Not ordered on any stream: it holds for the calls made after it. */
 int sjpeg_hip_engine_set_pixel_transform(sjpeg_hip_engine* engine, float scale, float bias);
 int sjpeg_hip_engine_get_pixel_transform(const sjpeg_hip_engine* engine, float* scale, float* bias);
+/* The same transform per channel: a sample x of channel c (0, 1, 2 = R, G, B; gray: 0) is coded as the byte
+ * rint(clamp(fmaf(x, scale[c], bias[c]), 0, 255)) -- pictures normalised with a per-channel mean and std go in with
+ * scale[c] = 255 * std[c], bias[c] = 255 * mean[c].  Read by every float source format.  The call above sets the three
+ * channels alike and its getter reports channel 0.  A non-finite entry is SJPEG_HIP_EINVAL and changes nothing. */
+int sjpeg_hip_engine_set_pixel_transform3(sjpeg_hip_engine* engine, const float scale[3], const float bias[3]);
+int sjpeg_hip_engine_get_pixel_transform3(const sjpeg_hip_engine* engine, float scale[3], float bias[3]);
 int sjpeg_hip_engine_wait(sjpeg_hip_engine* engine, void* stream);
 
 /* A batch whose frames each carry their OWN tables and header -- what a batch of the reference's

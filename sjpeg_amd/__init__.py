@@ -43,10 +43,16 @@ SRC_RGB, SRC_BGRA, SRC_RGBA, SRC_GRAY, SRC_YUV444, SRC_YUV420, SRC_NV12, SRC_NV2
 SRC_RGB_PLANAR = 8       # R, G and B planes of one pitch (channel-first pictures): sjpeg_hip.h
 # ... and the same planes of float elements, turned into bytes by the engine's pixel transform as they are read
 SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16 = 9, 10, 11
+# ONE plane of float elements: interleaved pixels of 3 (R, G, B) or 4 elements (R, G, B and one that is never read) --
+# channels-last tensors, [H, W, 3] and [H, W, 4] float arrays --, and gray pictures ([1, H, W], [H, W]; YUV_400)
+SRC_RGB_F32, SRC_RGB_F16, SRC_RGB_BF16 = 12, 13, 14
+SRC_RGBA_F32, SRC_RGBA_F16, SRC_RGBA_BF16 = 15, 16, 17
+SRC_GRAY_F32, SRC_GRAY_F16, SRC_GRAY_BF16 = 18, 19, 20
 _PLANAR_RGB = (SRC_RGB_PLANAR, SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16)
-_FLOAT_ELEMENT_BYTES = {SRC_RGB_PLANAR_F32: 4, SRC_RGB_PLANAR_F16: 2, SRC_RGB_PLANAR_BF16: 2}
+_FLOAT_ELEMENT_BYTES = {f: (4, 2, 2)[(f - SRC_RGB_PLANAR_F32) % 3] for f in range(SRC_RGB_PLANAR_F32, SRC_GRAY_BF16 + 1)}
+_GRAY_FLOAT = (SRC_GRAY_F32, SRC_GRAY_F16, SRC_GRAY_BF16)
 _IMPLIED_MODE = {SRC_GRAY: YUV_400, SRC_YUV444: YUV_444, SRC_YUV420: YUV_420, SRC_NV12: YUV_420,
-                 SRC_NV21: YUV_420}
+                 SRC_NV21: YUV_420, SRC_GRAY_F32: YUV_400, SRC_GRAY_F16: YUV_400, SRC_GRAY_BF16: YUV_400}
 
 
 class Source(C.Structure):
@@ -101,6 +107,8 @@ def make_source(fmt, planes):
     Returns (Source, nframes); the tensors must outlive the calls that use it.
     SRC_RGB_PLANAR_F32 / _F16 / _BF16: planes = (R, G, B) as for SRC_RGB_PLANAR, of torch.float32 / float16 / bfloat16;
     the strides go in as bytes, and the engine's pixel transform (Engine.set_pixel_transform) makes the bytes.
+    SRC_RGB_F* / SRC_RGBA_F* / SRC_GRAY_F*: one plane [F, H, W * step] of the float dtype (step 3, 4 or 1 elements a
+    pixel), stride(2) == 1; the strides go in as bytes.
     SRC_RGB_PLANAR: planes = (R, G, B), the [N, H, W] views x[:, 0], x[:, 1], x[:, 2] of an [N, 3, H, W] tensor (or of
     any crop of one): the three share their row and frame strides.
     With that layout a dimension of size 1 is never stepped over, so whatever stride torch reports for it is not looked
@@ -122,23 +130,49 @@ def make_source(fmt, planes):
 
 def _float_dtypes():
     import torch
-    return {SRC_RGB_PLANAR_F32: torch.float32, SRC_RGB_PLANAR_F16: torch.float16, SRC_RGB_PLANAR_BF16: torch.bfloat16}
+    return {f: (torch.float32, torch.float16, torch.bfloat16)[(f - SRC_RGB_PLANAR_F32) % 3] for f in _FLOAT_ELEMENT_BYTES}
+
+
+def _three(who, what, v):
+    """v as three floats: one value for the three channels alike, or a sequence of three (R, G, B)"""
+    vs = [v] * 3 if isinstance(v, (int, float, np.floating, np.integer)) else list(v)
+    if len(vs) != 3:
+        raise SjpegError(f"{who}: {what} is one value or a sequence of three (R, G, B), not of {len(vs)}")
+    vs = [float(x) for x in vs]
+    if not all(np.isfinite(x) for x in vs):
+        raise SjpegError(f"{who}: scale and bias must be finite" if what in ("scale", "bias") else f"{who}: {what} must be finite")
+    return tuple(vs)
 
 
 class FloatPixels:
     """Float pictures for the calls that take layout="chw" (encode_images, compress_images, riskiness_images) and for
     encode_images_full_chw, as their `images`: a sequence of CUDA tensors [3, H_k, W_k] of ONE dtype -- torch.float32,
-    float16 or bfloat16 --, stride 1 over x, any row stride.  A sample x is coded as the byte
-    rint(clamp(fma(x, scale, bias), 0, 255)) (ties to even, NaN -> 0): scale 255, bias 0 for values in 0..1, 127.5 and
-    127.5 for -1..1.  The conversion happens inside the encoder's loader -- no uint8 copy of the batch is made --, and the
-    JPEGs are those of the uint8 pictures so defined.  The call sets the engine's pixel transform (it stays set) and
-    passes SRC_RGB_PLANAR_F32 / _F16 / _BF16."""
+    float16 or bfloat16 --, any row stride.  The pictures are LOGICALLY channel-first; their strides choose the format,
+    one per call:
+      stride(2) == 1                           planes (SRC_RGB_PLANAR_F32 / _F16 / _BF16): a contiguous [3, H, W]
+      stride(0) == 1, stride(2) == 3 or 4      interleaved (SRC_RGB_F* / SRC_RGBA_F*): a slice of a channels_last
+                                               batch, hwc.permute(2, 0, 1), rgba.permute(2, 0, 1)[:3]
+      [1, H, W] or [H, W], stride(-1) == 1     gray (SRC_GRAY_F*): YUV_400 only
+    A sample x of channel c is coded as the byte rint(clamp(fma(x, scale[c], bias[c]), 0, 255)) (ties to even, NaN ->
+    0): scale 255, bias 0 for values in 0..1, 127.5 and 127.5 for -1..1; scale and bias are one value each or three
+    (R, G, B; gray uses the first) -- FloatPixels.normalized makes them from a mean and a std.  The conversion happens
+    inside the encoder's loader -- no uint8 copy of the batch is made, no .contiguous() --, and the JPEGs are those of
+    the uint8 pictures so defined.  The call sets the engine's pixel transform (it stays set)."""
 
     def __init__(self, images, scale=255.0, bias=0.0):
         self.images = list(images)
-        self.scale, self.bias = float(scale), float(bias)
-        if not (np.isfinite(self.scale) and np.isfinite(self.bias)):
-            raise SjpegError("FloatPixels: scale and bias must be finite")
+        self.scale3, self.bias3 = _three("FloatPixels", "scale", scale), _three("FloatPixels", "bias", bias)
+        # (one value given: one value kept, as ever)
+        self.scale = self.scale3[0] if self.scale3 == (self.scale3[0],) * 3 else self.scale3
+        self.bias = self.bias3[0] if self.bias3 == (self.bias3[0],) * 3 else self.bias3
+
+    @classmethod
+    def normalized(cls, images, mean, std):
+        """Pictures normalised as (u8 / 255 - mean[c]) / std[c], the way classification pipelines store them: coded
+        with scale[c] = 255 * std[c] and bias[c] = 255 * mean[c], computed in float64 and rounded once to float32.
+        mean and std: one value each, or three."""
+        mean, std = _three("FloatPixels.normalized", "mean", mean), _three("FloatPixels.normalized", "std", std)
+        return cls(images, [float(np.float32(255.0 * s)) for s in std], [float(np.float32(255.0 * m)) for m in mean])
 
 
 def _float_pixels(who, images, chw):
@@ -270,6 +304,10 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_engine_set_pixel_transform.restype = C.c_int
     L.sjpeg_hip_engine_get_pixel_transform.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sjpeg_hip_engine_get_pixel_transform.restype = C.c_int
+    L.sjpeg_hip_engine_set_pixel_transform3.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.sjpeg_hip_engine_set_pixel_transform3.restype = C.c_int
+    L.sjpeg_hip_engine_get_pixel_transform3.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.sjpeg_hip_engine_get_pixel_transform3.restype = C.c_int
     L.sjpeg_hip_engine_wait.argtypes = [C.c_void_p, C.c_void_p]
     L.sjpeg_hip_engine_wait.restype = C.c_int
     L.sjpeg_hip_encode_scan_multi.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -377,6 +415,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_engine_trim", "sjpeg_hip_host_trim",
     "sjpeg_hip_encode_scan_multi", "sjpeg_hip_scan_symbol_stats_multi",
     "sjpeg_hip_engine_set_pipelined", "sjpeg_hip_engine_set_pixel_transform", "sjpeg_hip_engine_get_pixel_transform",
+    "sjpeg_hip_engine_set_pixel_transform3", "sjpeg_hip_engine_get_pixel_transform3",
     "sjpeg_hip_engine_wait", "sjpeg_hip_encode_batch_src",
     "sjpeg_hip_optimize_huffman", "sjpeg_hip_make_header_ex", "sjpeg_hip_make_header_meta",
     "sjpeg_hip_sharp_workspace", "sjpeg_hip_sharp_yuv",
@@ -753,10 +792,18 @@ class Engine:
         self._chk(lib().sjpeg_hip_engine_set_pipelined(self._h, int(on)), "sjpeg_hip_engine_set_pipelined")
 
     def set_pixel_transform(self, scale=255.0, bias=0.0):
-        """The transform of the float source formats (SRC_RGB_PLANAR_F32 / _F16 / _BF16): a sample x is coded as the
-        byte rint(clamp(fma(x, scale, bias), 0, 255)).  Sticky; every other format ignores it."""
-        self._chk(lib().sjpeg_hip_engine_set_pixel_transform(self._h, float(scale), float(bias)),
-                  "sjpeg_hip_engine_set_pixel_transform")
+        """The transform of the float source formats: a sample x of channel c is coded as the byte
+        rint(clamp(fma(x, scale[c], bias[c]), 0, 255)).  scale and bias: one value each for the three channels alike,
+        or a sequence of three (R, G, B; gray pictures use the first).  Sticky: it holds until it is set again."""
+        s3, b3 = _three("Engine.set_pixel_transform", "scale", scale), _three("Engine.set_pixel_transform", "bias", bias)
+        self._chk(lib().sjpeg_hip_engine_set_pixel_transform3(self._h, (C.c_float * 3)(*s3), (C.c_float * 3)(*b3)),
+                  "sjpeg_hip_engine_set_pixel_transform3")
+
+    def pixel_transform3(self):
+        """((scale R, G, B), (bias R, G, B)) as the engine holds them"""
+        s, b = (C.c_float * 3)(), (C.c_float * 3)()
+        self._chk(lib().sjpeg_hip_engine_get_pixel_transform3(self._h, s, b), "sjpeg_hip_engine_get_pixel_transform3")
+        return tuple(s), tuple(b)
 
     def pixel_transform(self):
         s, b = C.c_float(), C.c_float()
@@ -1455,13 +1502,37 @@ def _check_layout(who, layout):
     return layout == "chw"
 
 
+def _chw_kinds(im, floats):
+    """How a layout="chw" picture may be read: a subset of "planar", "rgb" / "rgba" (interleaved, 3 / 4 elements a
+    pixel) and "gray" (float pictures only), empty when it is none of them.  A dimension of size 1 is never stepped
+    over, so whatever stride torch reports for it is not looked at: a one-pixel-wide picture is planar with any
+    stride(2), and interleaved as well when its channels lie next to each other."""
+    st, sh = im.stride(), im.shape
+    if im.dim() == 3 and sh[0] == 3 and sh[1] >= 1 and sh[2] >= 1:
+        kinds = []
+        if st[2] == 1 or sh[2] == 1:
+            kinds.append("planar")
+        if st[0] == 1 and (st[2] == 3 or sh[2] == 1):
+            kinds.append("rgb")
+        if st[0] == 1 and (st[2] == 4 or sh[2] == 1):
+            kinds.append("rgba")
+        return kinds
+    if floats and im.dim() in (2, 3) and (im.dim() == 2 or sh[0] == 1) and sh[-2] >= 1 and sh[-1] >= 1 and \
+            (st[-1] == 1 or sh[-1] == 1):
+        return ["gray"]
+    return []
+
+
 def _chw_planes(who, images, fp=None):
     """The planes, dims, device and format of a layout="chw" call: every image a CUDA uint8 tensor [3, H, W] with stride
     1 over x (any row stride: crops of a larger tensor work) -- SRC_RGB_PLANAR, its R, G and B planes im[0], im[1],
-    im[2].  fp (the call's FloatPixels): float tensors of one dtype instead, SRC_RGB_PLANAR_F32 / _F16 / _BF16."""
+    im[2] -- or with stride 1 over the channels and 3 or 4 over x (a slice of a channels_last batch, a permuted
+    [H, W, 3] or [H, W, 4] array) -- SRC_RGB / SRC_RGBA, one plane.  fp (the call's FloatPixels): float tensors of one
+    dtype instead, SRC_RGB_PLANAR_F* / SRC_RGB_F* / SRC_RGBA_F*, or gray pictures [1, H, W] / [H, W], SRC_GRAY_F*.  A call
+    has one format: every image lies as image 0 does."""
     import torch
     dev = None
-    fmt, esz = SRC_RGB_PLANAR, 1
+    esz, kind0, dt = 1, None, 0
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
@@ -1469,17 +1540,24 @@ def _chw_planes(who, images, fp=None):
             if im.dtype != torch.uint8:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
         else:
-            kinds = {d: f for f, d in _float_dtypes().items()}
-            if im.dtype not in kinds:
+            by_dtype = {d: f for f, d in _float_dtypes().items() if f in _PLANAR_RGB}
+            if im.dtype not in by_dtype:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}: FloatPixels take torch.float32, torch.float16 or "
                                  f"torch.bfloat16")
             if k > 0 and im.dtype != images[0].dtype:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}, image 0 {images[0].dtype}: one dtype per call")
-            fmt, esz = kinds[im.dtype], im.element_size()
-        if im.dim() != 3 or im.shape[0] != 3 or im.shape[1] < 1 or im.shape[2] < 1 or \
-                (im.stride(2) != 1 and im.shape[2] > 1):
+            dt, esz = by_dtype[im.dtype] - SRC_RGB_PLANAR_F32, im.element_size()
+        kinds = _chw_kinds(im, fp is not None)
+        if not kinds:
             raise SjpegError(f"{who}: image {k} must be [3, H, W] planar RGB with layout='chw' (stride 1 over x; its "
-                             f"shape is {tuple(im.shape)}, its strides {tuple(im.stride())})")
+                             f"shape is {tuple(im.shape)}, its strides {tuple(im.stride())})" +
+                             ("" if fp is None else "; or [3, H, W] with stride 1 over the channels and 3 or 4 over x; "
+                                                    "or gray [1, H, W] / [H, W]"))
+        both = kinds if kind0 is None else [x for x in kind0 if x in kinds]
+        if not both:
+            raise SjpegError(f"{who}: image {k} lies in memory as {kinds[0]!r} (shape {tuple(im.shape)}, strides "
+                             f"{tuple(im.stride())}), the images before it as {kind0[0]!r}: one format per call")
+        kind0 = both
         if dev is None:
             dev = im.device
         elif im.device != dev:
@@ -1487,10 +1565,27 @@ def _chw_planes(who, images, fp=None):
     # ((address, row stride) pairs; torch reports any stride for a dimension of size 1, so a one-pixel-wide picture
     # passes with any stride(2), and a one-row picture is handed over with its width as the row stride)
     # (strides in bytes: esz is the element size, 1 for uint8)
-    planes = [[(im.data_ptr() + c * im.stride(0) * esz, (im.stride(1) if im.shape[1] > 1 else im.shape[2]) * esz)
-               for c in range(3)] for im in images]
-    dims = [(int(im.shape[2]), int(im.shape[1])) for im in images]
+    kind0 = kind0[0] if kind0 else "planar"          # (planar before interleaved where a call could be read as both)
+    if kind0 == "planar":
+        fmt = SRC_RGB_PLANAR if fp is None else SRC_RGB_PLANAR_F32 + dt
+        planes = [[(im.data_ptr() + c * im.stride(0) * esz, (im.stride(1) if im.shape[1] > 1 else im.shape[2]) * esz)
+                   for c in range(3)] for im in images]
+    elif kind0 == "gray":
+        fmt = SRC_GRAY_F32 + dt
+        planes = [[(im.data_ptr(), (im.stride(-2) if im.shape[-2] > 1 else im.shape[-1]) * esz)] for im in images]
+    else:
+        step = 3 if kind0 == "rgb" else 4
+        fmt = {"rgb": SRC_RGB, "rgba": SRC_RGBA}[kind0] if fp is None else (SRC_RGB_F32 if step == 3 else SRC_RGBA_F32) + dt
+        planes = [[(im.data_ptr(), (im.stride(1) if im.shape[1] > 1 else im.shape[2] * step) * esz)] for im in images]
+    dims = [(int(im.shape[-1]), int(im.shape[-2])) for im in images]
     return planes, dims, dev, fmt
+
+
+def _gray_mode(who, fmt, yuv_mode):
+    """gray float pictures are coded in YUV_400 and nothing else"""
+    if fmt in _GRAY_FLOAT and int(yuv_mode) != YUV_400:
+        raise SjpegError(f"{who}: gray FloatPixels ([1, H, W] or [H, W]) are coded with yuv_mode=YUV_400 only, not "
+                         f"{int(yuv_mode)} (YUV_AUTO and YUV_SHARP take RGB pictures)")
 
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
@@ -1523,8 +1618,10 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     layout="chw": every image is a CUDA uint8 tensor [3, H_k, W_k] instead -- channel-first, as torch stores pictures --
     with stride 1 over x and any row stride (a crop of a larger tensor works); the pictures go in as SRC_RGB_PLANAR,
     without a repack, and the bytes are those of the same pixels handed over as [H, W, 3].  A call has one layout; the
-    keyword is explicit because [3, W, 3] is both.  With layout="chw", images may be a FloatPixels: float32, float16
-    or bfloat16 pictures [3, H_k, W_k], converted to bytes inside the encoder (SRC_RGB_PLANAR_F32 / _F16 / _BF16)."""
+    keyword is explicit because [3, W, 3] is both.  A [3, H_k, W_k] picture that lies channels-last in memory -- stride
+    1 over the channels, 3 or 4 over x: x[k] of a torch.channels_last batch, hwc.permute(2, 0, 1) -- goes in as SRC_RGB /
+    SRC_RGBA, again without a copy.  With layout="chw", images may be a FloatPixels: float32, float16 or bfloat16
+    pictures, planar, channels-last or gray, converted to bytes inside the encoder (see FloatPixels)."""
     import torch
     chw = _check_layout("encode_images", layout)
     images, fp = _float_pixels("encode_images", images, chw)
@@ -1578,6 +1675,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     fmt = SRC_RGB
     if chw:
         planes, dims, dev, fmt = _chw_planes("encode_images", images, fp)
+        _gray_mode("encode_images", fmt, yuv_mode)
     else:
         planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
         dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
@@ -1706,6 +1804,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     fmt = SRC_RGB
     if chw:
         planes, dims, dev, fmt = _chw_planes("encode_images_full", images, fp)
+        _gray_mode("encode_images_full", fmt, yuv_mode)
     else:
         planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
         dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
@@ -1762,6 +1861,7 @@ def riskiness_images(images, engine=None, layout="hwc"):
         raise SjpegError("riskiness_images: no images")
     if chw:
         planes, dims, dev, fmt = _chw_planes("riskiness_images", images, fp)
+        _gray_mode("riskiness_images", fmt, YUV_AUTO)
         eng = engine or Engine(dev.index or 0)
         if fp is not None:
             eng.set_pixel_transform(fp.scale, fp.bias)

@@ -1,5 +1,5 @@
-// pixel_elem.h -- float picture elements (SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16): how one sample becomes the
-// byte the encoder sees.  The contract (sjpeg_hip.h):
+// pixel_elem.h -- float picture elements (SJPEG_HIP_SRC_RGB_PLANAR_F*, _RGB_F*, _RGBA_F*, _GRAY_F*): how one sample
+// becomes the byte the encoder sees.  The contract (sjpeg_hip.h), scale and bias being those of the sample's channel:
 //   t  = fmaf((float)x, scale, bias)                 ONE fp32 rounding; (float)x is exact for half and bfloat16
 //   u8 = isnan(t) ? 0 : (uint8) rint(min(max(t, 0), 255))          round half to even; +-inf saturate
 // On gfx950 that is v_fma_f32 (v_fma_mix_f32 straight from a half) and v_cvt_pk_u8_f32, which rounds to nearest even,
@@ -18,17 +18,24 @@ namespace sjpeg_internal {
 // element kinds of a source: bytes as they are, or floats through the engine's pixel transform
 enum { kElemU8 = 0, kElemF32 = 1, kElemF16 = 2, kElemBF16 = 3 };
 
+// (the float formats come in threes: fp32, half, bfloat16 -- planar 9..11, RGB 12..14, RGBA 15..17, gray 18..20)
+inline bool is_float_format(int format) { return format >= SJPEG_HIP_SRC_RGB_PLANAR_F32 && format <= SJPEG_HIP_SRC_GRAY_BF16; }
 inline int elem_kind(int format) {
-  switch (format) {
-    case SJPEG_HIP_SRC_RGB_PLANAR_F32: return kElemF32;
-    case SJPEG_HIP_SRC_RGB_PLANAR_F16: return kElemF16;
-    case SJPEG_HIP_SRC_RGB_PLANAR_BF16: return kElemBF16;
-    default: return kElemU8;
-  }
+  return is_float_format(format) ? kElemF32 + (format - SJPEG_HIP_SRC_RGB_PLANAR_F32) % 3 : kElemU8;
 }
 inline int elem_bytes(int kind) { return kind == kElemF32 ? 4 : kind == kElemU8 ? 1 : 2; }
-inline bool is_float_planar(int format) { return elem_kind(format) != kElemU8; }
+inline bool is_float_planar(int format) { return format >= SJPEG_HIP_SRC_RGB_PLANAR_F32 && format <= SJPEG_HIP_SRC_RGB_PLANAR_BF16; }
 inline bool is_rgb_planar(int format) { return format == SJPEG_HIP_SRC_RGB_PLANAR || is_float_planar(format); }
+// one plane of interleaved float pixels (R, G, B and, with a step of 4, an element that is never read) / of gray floats
+inline bool is_float_packed(int format) { return format >= SJPEG_HIP_SRC_RGB_F32 && format <= SJPEG_HIP_SRC_RGBA_BF16; }
+inline bool is_float_gray(int format) { return format >= SJPEG_HIP_SRC_GRAY_F32 && format <= SJPEG_HIP_SRC_GRAY_BF16; }
+// elements from one pixel of a row to the next, and the elements of a pixel that are read
+inline int elem_step(int format) { return !is_float_packed(format) ? 1 : format >= SJPEG_HIP_SRC_RGBA_F32 ? 4 : 3; }
+inline int elem_channels(int format) { return is_float_gray(format) ? 1 : 3; }
+// bytes of a row of `width` pixels of a one-plane float format, up to the last element that is read
+inline int64_t elem_row_bytes(int format, int64_t width) {
+  return ((width - 1) * elem_step(format) + elem_channels(format)) * elem_bytes(elem_kind(format));
+}
 
 #if defined(__HIPCC__)
 // fmaf(x, scale, bias) as byte `pos` (0..3, a constant) of `old`
@@ -67,6 +74,42 @@ __device__ __forceinline__ void elem_load8(const uint8_t* p, int kind, float sca
     }
   }
   w[0] = lo; w[1] = hi;
+}
+
+// eight interleaved pixels at p, STEP (3 or 4) elements each, R G B first: 8 * STEP elements in one piece -- but for
+// the last pixel's fourth, which may lie outside the allocation (31 elements, not 32) -- as the planar class's six
+// dwords, w[0..1] R, w[2..3] G, w[4..5] B; channel c through scale[c], bias[c]
+template <int STEP>
+__device__ __forceinline__ void elem_load8x3(const uint8_t* p, int kind, const float* scale, const float* bias, uint32_t* w) {
+  constexpr int kN = 8 * STEP - (STEP == 4 ? 1 : 0);
+  uint32_t o[6] = {0, 0, 0, 0, 0, 0};
+  if (kind == kElemF32) {
+    float f[kN];
+    __builtin_memcpy(f, p, 4 * kN);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        o[2 * c + (i >> 2)] = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(f[i * STEP + c], scale[c], bias[c]), static_cast<uint32_t>(i & 3), o[2 * c + (i >> 2)]);
+      }
+    }
+  } else {
+    uint32_t h[4 * STEP];
+    h[4 * STEP - 1] = 0;
+    __builtin_memcpy(h, p, 2 * kN);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int k = i * STEP + c;
+        const uint32_t hw = h[k >> 1];
+        const float x = (kind == kElemF16) ? ((k & 1) ? elem_f16_hi(hw) : elem_f16_lo(hw)) : ((k & 1) ? elem_bf16_hi(hw) : elem_bf16_lo(hw));
+        o[2 * c + (i >> 2)] = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(x, scale[c], bias[c]), static_cast<uint32_t>(i & 3), o[2 * c + (i >> 2)]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) w[k] = o[k];
 }
 
 // one element at p as a float (kind: one of the float kinds)

@@ -72,8 +72,15 @@ inline bool rgb_layout(int format, int* pix_step, long long* r_off, long long* g
     case SJPEG_HIP_SRC_RGB_PLANAR_F32: *pix_step = 4; *r_off = 0; *g_off = 0; *b_off = 0; return true;
     case SJPEG_HIP_SRC_RGB_PLANAR_F16:
     case SJPEG_HIP_SRC_RGB_PLANAR_BF16: *pix_step = 2; *r_off = 0; *g_off = 0; *b_off = 0; return true;
-    default: return false;
+    default: break;
   }
+  // (interleaved float pixels: step elements a pixel, G and B one and two elements behind R -- all in bytes)
+  if (is_float_packed(format)) {
+    const int esz = elem_bytes(elem_kind(format));
+    *pix_step = elem_step(format) * esz; *r_off = 0; *g_off = esz; *b_off = 2 * esz;
+    return true;
+  }
+  return false;
 }
 // g_off and b_off of one picture (or of a uniform batch) of such a source: the layout's, or (planar RGB) the distances of
 // its G and B planes from its R plane
@@ -94,9 +101,9 @@ inline const char* rgb_planar_fault(const void* const* plane, const int64_t* row
   if (frame_stride != nullptr && frame_stride[2] != frame_stride[0]) return "frame_stride[2] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
   return nullptr;
 }
-// what is wrong with the addresses of a float-planar picture (SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: planes and
-// strides are multiples of the element size -- all the alignment the kernels assume), or empty; nplanes: how many of
-// plane[] and the strides the caller has checked for presence
+// what is wrong with the addresses of a picture of float elements (planes and strides are multiples of the element size
+// -- all the alignment the kernels assume), or empty; nplanes: how many of plane[] and the strides are looked at (3 for
+// the planar formats, 1 for the one-plane ones)
 inline std::string rgb_float_fault(int format, const void* const* plane, const int64_t* row_stride, const int64_t* frame_stride,
                                    int nplanes = 3) {
   const int64_t esz = elem_bytes(elem_kind(format));
@@ -130,14 +137,14 @@ inline void risk_frame_plan(int W, int H, RiskFrame* d) {
 }
 
 // d_sums[nframes][3] zeroed, then the flat grid of total_wgs workgroups over d_frames[nframes] (device memory)
-// (pscale, pbias: the engine's pixel transform, read by the float formats alone)
-int risk_ragged_launch(int format, float pscale, float pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
+// (pscale[3], pbias[3]: the engine's pixel transform per channel, read by the float formats alone)
+int risk_ragged_launch(int format, const float* pscale, const float* pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
                        const uint8_t* d_table, uint64_t* d_sums, hipStream_t st);
 
 // ---- ragged sharp conversion (sjpeg_hip_sharp_yuv_ragged); the descriptors go into the workspace through `up`
 using UploadFn = int (*)(void* ctx, void* d_dst, const void* src, size_t bytes, hipStream_t st);
 size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames);
-int sharp_ragged_run(int format, float pscale, float pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
+int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err);
 

@@ -31,11 +31,11 @@ __device__ __forceinline__ int yuv_index(const uint8_t* p, long long ro, long lo
 }
 
 // the ragged form's samples: bytes as they are, or float elements through the engine's pixel transform (pixel_elem.h)
-__device__ __forceinline__ int yuv_index_elem(const uint8_t* p, long long ro, long long go, long long bo, int kind, float s, float t) {
+__device__ __forceinline__ int yuv_index_elem(const uint8_t* p, long long ro, long long go, long long bo, int kind, const float* s, const float* t) {
   if (kind == sjpeg_internal::kElemU8) return yuv_index(p, ro, go, bo);
-  const uint8_t px[3] = {static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + ro, kind, s, t)),
-                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + go, kind, s, t)),
-                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + bo, kind, s, t))};
+  const uint8_t px[3] = {static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + ro, kind, s[0], t[0])),
+                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + go, kind, s[1], t[1])),
+                         static_cast<uint8_t>(sjpeg_internal::elem_load_u8(p + bo, kind, s[2], t[2]))};
   return yuv_index(px, 0, 1, 2);
 }
 
@@ -48,7 +48,7 @@ struct RiskArgs {
   const uint8_t* table;                           // [343 * 343]
   unsigned long long* out;                        // [nframes][3]: score_sum, score_num, gray_num
   int ekind;                                      // ragged form: element kind (pixel_elem.h) and the pixel transform
-  float pscale, pbias;
+  float pscale[3], pbias[3];                      // (per channel R, G, B)
 };
 
 // One workgroup = 256 columns x a BAND of rows (the grid's y dimension cuts the picture into at most 64 bands): a
@@ -110,6 +110,10 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
     return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_sums: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
                                                        "pixel transform: use sjpeg_hip_riskiness_ragged_src");
   }
+  if (sjpeg_internal::is_float_format(src->format)) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_sums: SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F* need an engine's "
+                                                       "pixel transform: use sjpeg_hip_riskiness_ragged_src");
+  }
   if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
   if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
     if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
@@ -132,12 +136,13 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
 
 namespace sjpeg_internal {
 
-int risk_ragged_launch(int format, float pscale, float pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
+int risk_ragged_launch(int format, const float* pscale, const float* pbias, const RiskFrame* d_frames, int nframes, unsigned total_wgs,
                        const uint8_t* d_table, uint64_t* d_sums, hipStream_t st) {
   RiskArgs a;
   memset(&a, 0, sizeof(a));
   if (!sjpeg_internal::rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
-  a.ekind = elem_kind(format); a.pscale = pscale; a.pbias = pbias;
+  a.ekind = elem_kind(format);
+  for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
   a.table = d_table;
   a.out = reinterpret_cast<unsigned long long*>(d_sums);
   if (hipMemsetAsync(d_sums, 0, static_cast<size_t>(nframes) * 3 * sizeof(uint64_t), st) != hipSuccess) return SJPEG_HIP_ERUNTIME;

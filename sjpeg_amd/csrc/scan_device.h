@@ -56,10 +56,15 @@ static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 
 // (kSrcRgbPlanarF: the same three planes of fp32, half or bfloat16 elements -- SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 /
 // _BF16, ONE class for the three: the element kind is a wave-uniform field of the arguments (ScanArgs::pkind).  The
 // loader turns the elements into bytes as it reads them (pixel_elem.h), so a row of 8 pixels is the planar class's six
-// raw dwords and everything behind the loader is shared with it)
+// raw dwords and everything behind the loader is shared with it.  The class also serves the ONE-plane float formats
+// through three more uniform fields: interleaved pixels -- SJPEG_HIP_SRC_RGB_F* / _RGBA_F*, ScanArgs::pstep = 3 or 4
+// elements a pixel, G and B one and two elements behind R, so the "planes" are plane[0] + pesz and + 2 * pesz -- and
+// gray -- SJPEG_HIP_SRC_GRAY_F*, ScanArgs::pone, a HOST-side flag: the three "planes" are the one plane and the three
+// channels' transform is channel 0's, so the plane's bytes are R, G and B alike, whose luma is the gray value itself:
+// (19595 + 38469 + 7471) v + 32768 >> 16 = v for v = 0..255)
 enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2, kSrcRgbPlanar = 3, kSrcRgbPlanarF = 4 };
 // raw dwords of a row of 8 pixels, and bytes between pixels of a row, of the classes the colour phase converts
-// (kSrcRgbPlanarF: the bytes between pixels are ScanArgs::pesz, 4 or 2)
+// (kSrcRgbPlanarF: the bytes between pixels are ScanArgs::pesz * ScanArgs::pstep)
 template <int SRC> constexpr int kSrcRowWords = (SRC == kSrcRgbx32) ? 8 : 6;
 template <int SRC> constexpr int kSrcPixelBytes = (SRC == kSrcRgb24) ? 3 : (SRC == kSrcRgbPlanar) ? 1 : 4;
 template <int SRC> constexpr bool kSrcIsPlanarRgb = (SRC == kSrcRgbPlanar || SRC == kSrcRgbPlanarF);
@@ -99,10 +104,12 @@ struct ScanArgs {
   // every workgroup of the launch's flat grid (NULL otherwise)
   const RaggedFrame* rframes;
   const uint32_t* rmap;
-  // kSrcRgbPlanarF: the engine's pixel transform (byte = fmaf(x, pscale, pbias), rounded to even and saturated), the
-  // element kind (pixel_elem.h) and its size in bytes; every other class ignores them
-  float pscale, pbias;
-  int pkind, pesz;
+  // kSrcRgbPlanarF: the engine's pixel transform per channel R, G, B (byte = fmaf(x, pscale[c], pbias[c]), rounded to
+  // even and saturated), the element kind (pixel_elem.h), its size in bytes, the elements between the pixels of a row
+  // (1: planes; 3 / 4: interleaved) and whether there is one gray plane (read on the host alone: it makes the three
+  // planes one and the three channels' transform channel 0's); every other class ignores them
+  float pscale[3], pbias[3];
+  int pkind, pesz, pstep, pone;
 };
 
 // One frame of a ragged launch, built on the host (scan_engine.hip, "ragged batches"): its geometry, its planes and
@@ -567,6 +574,23 @@ __device__ __forceinline__ void load_row8(const uint8_t* frame, long long row_st
   }
 }
 
+// kSrcRgbPlanarF: eight whole pixels from p (the R sample of the first) as the planar class's six dwords -- the three
+// planes, or one pass over 8 * pstep interleaved elements.  Both branches are uniform.  (One gray plane needs no branch:
+// the host hands it over as three planes at the same address with channel 0's transform in all three channels.  A
+// branch that copied the R dwords into G and B instead put the whole prefetch buffer of the colour phase into private
+// memory, 80 bytes a row in flight: profiles/HISTORY.md.)
+__device__ __forceinline__ void load_float_row8(const ScanArgs& a, const uint8_t* p, long long dg, long long db, uint32_t* w) {
+  if (a.pstep == 3) {
+    sjpeg_internal::elem_load8x3<3>(p, a.pkind, a.pscale, a.pbias, w);
+  } else if (a.pstep == 4) {
+    sjpeg_internal::elem_load8x3<4>(p, a.pkind, a.pscale, a.pbias, w);
+  } else {
+    sjpeg_internal::elem_load8(p, a.pkind, a.pscale[0], a.pbias[0], w);
+    sjpeg_internal::elem_load8(p + dg, a.pkind, a.pscale[1], a.pbias[1], w + 2);
+    sjpeg_internal::elem_load8(p + db, a.pkind, a.pscale[2], a.pbias[2], w + 4);
+  }
+}
+
 // Raw dwords of 8 consecutive pixels of row y (coordinates clamp to the picture): 6 dwords for
 // packed RGB, 8 for the 4-byte layouts, 6 for planar RGB (bytes or floats) -- two of R, two of G, two of B.
 // (planar RGB: frame_px is the frame's R plane; G and B lie dg and db bytes from it, whichever the row -- the
@@ -579,12 +603,9 @@ __device__ __forceinline__ void load_px8(const ScanArgs& a, const uint8_t* frame
   } else if (SRC == kSrcRgbPlanarF) {
     // float elements: converted to bytes as they are read, the planar class's dwords from here on
     const int kind = a.pkind;
-    const long long esz = a.pesz;
+    const long long pxb = static_cast<long long>(a.pesz * a.pstep);      // bytes between pixels
     if (inside) {
-      const uint8_t* p = frame_px + y * a.row_stride[0] + esz * x0;
-      sjpeg_internal::elem_load8(p, kind, a.pscale, a.pbias, w);
-      sjpeg_internal::elem_load8(p + dg, kind, a.pscale, a.pbias, w + 2);
-      sjpeg_internal::elem_load8(p + db, kind, a.pscale, a.pbias, w + 4);
+      load_float_row8(a, frame_px + y * a.row_stride[0] + pxb * x0, dg, db, w);
     } else {
       const int yy = y < a.H ? y : a.H - 1;
       const uint8_t* row = frame_px + yy * a.row_stride[0];
@@ -593,10 +614,13 @@ __device__ __forceinline__ void load_px8(const ScanArgs& a, const uint8_t* frame
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int xx = (x0 + i) < a.W ? (x0 + i) : a.W - 1;
-        const uint8_t* p = row + esz * xx;
-        w[i >> 2] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p, kind, a.pscale, a.pbias)) << (8 * (i & 3));
-        w[2 + (i >> 2)] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + dg, kind, a.pscale, a.pbias)) << (8 * (i & 3));
-        w[4 + (i >> 2)] |= static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + db, kind, a.pscale, a.pbias)) << (8 * (i & 3));
+        const uint8_t* p = row + pxb * xx;
+        const uint32_t r = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p, kind, a.pscale[0], a.pbias[0]));
+        const uint32_t g = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + dg, kind, a.pscale[1], a.pbias[1]));
+        const uint32_t b = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(p + db, kind, a.pscale[2], a.pbias[2]));
+        w[i >> 2] |= r << (8 * (i & 3));
+        w[2 + (i >> 2)] |= g << (8 * (i & 3));
+        w[4 + (i >> 2)] |= b << (8 * (i & 3));
       }
     }
   } else if (SRC == kSrcRgbPlanar) {

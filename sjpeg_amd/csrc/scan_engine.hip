@@ -193,7 +193,7 @@ struct sjpeg_hip_engine {
   bool is_lane = false;                // a child engine: no streams or lanes of its own
   // the pixel transform of the float source formats (sjpeg_hip_engine_set_pixel_transform): byte = fmaf(x, scale, bias),
   // rounded to even and saturated; sticky, read by no other format; the lanes take the parent's with every call
-  float pscale = 255.0f, pbias = 0.0f;
+  float pscale[3] = {255.0f, 255.0f, 255.0f}, pbias[3] = {0.0f, 0.0f, 0.0f};
   DevBuf<unsigned long long> seg_off, chunk_off, stamps;
   DevBuf<uint32_t> hdr_off;
   bool want_stamps = false;
@@ -490,6 +490,23 @@ SegPlan seg_plan(const FrameGeo& g, size_t budget_bytes) {
   return p;
 }
 
+// the engine's pixel transform into a launch's arguments (a->pone, one gray plane read as R, G and B: channel 0's thrice)
+void put_transform(const sjpeg_hip_engine* e, ScanArgs* a) {
+  for (int c = 0; c < 3; ++c) { a->pscale[c] = e->pscale[a->pone ? 0 : c]; a->pbias[c] = e->pbias[a->pone ? 0 : c]; }
+}
+// the float class's fields of a one-plane float format (SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*)
+void float_format_fields(int format, ScanArgs* a) {
+  a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
+  a->pstep = sjpeg_internal::elem_step(format); a->pone = sjpeg_internal::is_float_gray(format) ? 1 : 0;
+}
+// ... and its three "planes" from the one it has: G and B one and two elements behind R (gray: all three the same),
+// one pitch -- what the float class's loader takes
+void float_one_plane(const ScanArgs& a, const uint8_t** plane, long long* row_stride) {
+  plane[1] = plane[0] + (a.pone ? 0 : a.pesz);
+  plane[2] = plane[0] + (a.pone ? 0 : 2 * a.pesz);
+  row_stride[1] = row_stride[2] = row_stride[0];
+}
+
 int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
                  int W, int H, int mode, int nframes, const sjpeg_hip_scan_tables* tables,
                  hipStream_t st, FrameGeo* g, ScanArgs* a, int* src_class, bool per_frame_tables = false,
@@ -515,6 +532,15 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     case SJPEG_HIP_SRC_RGB_PLANAR_BF16:
       a->pkind = sjpeg_internal::elem_kind(src->format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
       need[0] = need[1] = need[2] = static_cast<int64_t>(a->pesz) * W; nplanes = 3; *src_class = kSrcRgbPlanarF;
+      a->pstep = 1;
+      break;
+    case SJPEG_HIP_SRC_RGB_F32: case SJPEG_HIP_SRC_RGB_F16: case SJPEG_HIP_SRC_RGB_BF16:
+    case SJPEG_HIP_SRC_RGBA_F32: case SJPEG_HIP_SRC_RGBA_F16: case SJPEG_HIP_SRC_RGBA_BF16:
+    case SJPEG_HIP_SRC_GRAY_F32: case SJPEG_HIP_SRC_GRAY_F16: case SJPEG_HIP_SRC_GRAY_BF16:
+      // one plane of float elements, served by the float class (float_one_plane below makes its three "planes")
+      float_format_fields(src->format, a);
+      need[0] = sjpeg_internal::elem_row_bytes(src->format, W); *src_class = kSrcRgbPlanarF;
+      if (a->pone) implied = SJPEG_HIP_YUV400;
       break;
     case SJPEG_HIP_SRC_GRAY: need[0] = W; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444:
@@ -557,7 +583,13 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     const std::string efault = sjpeg_internal::rgb_float_fault(src->format, src->plane, src->row_stride, src->frame_stride);
     if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: " + efault);
   }
-  a->pscale = e->pscale; a->pbias = e->pbias;     // (read by the float class alone)
+  if (sjpeg_internal::is_float_packed(src->format) || sjpeg_internal::is_float_gray(src->format)) {
+    const std::string efault = sjpeg_internal::rgb_float_fault(src->format, src->plane, src->row_stride, src->frame_stride, 1);
+    if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*: " + efault);
+    float_one_plane(*a, a->plane, a->row_stride);
+    a->frame_stride[1] = a->frame_stride[2] = a->frame_stride[0];
+  }
+  put_transform(e, a);                            // (read by the float class alone)
   if (nplanes == 2) {          // interleaved chroma: U and V walk the same plane
     a->plane[2] = a->plane[1]; a->row_stride[2] = a->row_stride[1]; a->frame_stride[2] = a->frame_stride[1];
   }
@@ -758,7 +790,29 @@ int sjpeg_hip_engine_set_pixel_transform(sjpeg_hip_engine* e, float scale, float
   if (!(scale - scale == 0.0f) || !(bias - bias == 0.0f)) {      // (neither NaN nor an infinity)
     return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_set_pixel_transform: scale and bias must be finite");
   }
-  e->pscale = scale; e->pbias = bias;
+  for (int c = 0; c < 3; ++c) { e->pscale[c] = scale; e->pbias[c] = bias; }
+  return 0;
+}
+
+int sjpeg_hip_engine_set_pixel_transform3(sjpeg_hip_engine* e, const float scale[3], const float bias[3]) {
+  if (e == nullptr || scale == nullptr || bias == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_set_pixel_transform3: engine, scale or bias == NULL");
+  }
+  for (int c = 0; c < 3; ++c) {
+    if (!(scale[c] - scale[c] == 0.0f) || !(bias[c] - bias[c] == 0.0f)) {      // (neither NaN nor an infinity)
+      return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_set_pixel_transform3: scale[" + std::to_string(c) + "] and bias[" +
+                                        std::to_string(c) + "] must be finite");
+    }
+  }
+  for (int c = 0; c < 3; ++c) { e->pscale[c] = scale[c]; e->pbias[c] = bias[c]; }
+  return 0;
+}
+
+int sjpeg_hip_engine_get_pixel_transform3(const sjpeg_hip_engine* e, float scale[3], float bias[3]) {
+  if (e == nullptr || scale == nullptr || bias == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_get_pixel_transform3: engine, scale or bias == NULL");
+  }
+  for (int c = 0; c < 3; ++c) { scale[c] = e->pscale[c]; bias[c] = e->pbias[c]; }
   return 0;
 }
 
@@ -766,7 +820,7 @@ int sjpeg_hip_engine_get_pixel_transform(const sjpeg_hip_engine* e, float* scale
   if (e == nullptr || scale == nullptr || bias == nullptr) {
     return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_get_pixel_transform: engine, scale or bias == NULL");
   }
-  *scale = e->pscale; *bias = e->pbias;
+  *scale = e->pscale[0]; *bias = e->pbias[0];        // (channel 0: sjpeg_hip_engine_get_pixel_transform3 has all three)
   return 0;
 }
 
@@ -1401,7 +1455,14 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
     case SJPEG_HIP_SRC_RGB_PLANAR_F16:
     case SJPEG_HIP_SRC_RGB_PLANAR_BF16:       // (the engine's pixel transform: ragged_encode / ragged_analysis put it in)
       *cls = kSrcRgbPlanarF; *nplanes = 3;
-      a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
+      a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind); a->pstep = 1;
+      break;
+    case SJPEG_HIP_SRC_RGB_F32: case SJPEG_HIP_SRC_RGB_F16: case SJPEG_HIP_SRC_RGB_BF16:
+    case SJPEG_HIP_SRC_RGBA_F32: case SJPEG_HIP_SRC_RGBA_F16: case SJPEG_HIP_SRC_RGBA_BF16:
+    case SJPEG_HIP_SRC_GRAY_F32: case SJPEG_HIP_SRC_GRAY_F16: case SJPEG_HIP_SRC_GRAY_BF16:
+      // one plane of float elements, served by the float class (ragged_geometry makes its three "planes")
+      *cls = kSrcRgbPlanarF; float_format_fields(format, a);
+      if (a->pone) implied = SJPEG_HIP_YUV400;
       break;
     case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
     case SJPEG_HIP_SRC_YUV444: *nplanes = 3; implied = SJPEG_HIP_YUV444; a->cstep = 1; break;
@@ -1441,6 +1502,7 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
     else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
     else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
     else if (format == SJPEG_HIP_SRC_NV12 || format == SJPEG_HIP_SRC_NV21) need[1] = 2 * cw;
+    else if (!planar_rgb && esz != 1) need[0] = sjpeg_internal::elem_row_bytes(format, W);    // (one plane of float pixels)
     for (int i = 0; i < nplanes; ++i) {
       if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, w + "null plane pointer");
       const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
@@ -1451,7 +1513,7 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
       }
     }
     if (esz != 1) {                                              // float planes: addresses and strides in whole elements
-      const std::string efault = sjpeg_internal::rgb_float_fault(format, fr.plane, fr.row_stride, nullptr);
+      const std::string efault = sjpeg_internal::rgb_float_fault(format, fr.plane, fr.row_stride, nullptr, planar_rgb ? 3 : 1);
       if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, w + efault);
     }
     if (out_ranges && fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, w + "out_offset + out_capacity overflows");
@@ -1460,12 +1522,14 @@ int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes,
 }
 
 // a frame's planes and geometry in its descriptor
-void ragged_geometry(const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, int nplanes, RaggedFrame* d) {
+// (a: the format's fields -- a one-plane float format's frame gets the three "planes" of the float class)
+void ragged_geometry(const ScanArgs& a, const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, int nplanes, RaggedFrame* d) {
   for (int i = 0; i < 3; ++i) {
     const int p = (nplanes == 2 && i == 2) ? 1 : i;            // interleaved chroma: U and V walk the same plane
     d->plane[i] = p < nplanes ? static_cast<const uint8_t*>(fr.plane[p]) : nullptr;
     d->row_stride[i] = p < nplanes ? fr.row_stride[p] : 0;
   }
+  if (a.pkind != sjpeg_internal::kElemU8 && nplanes == 1) float_one_plane(a, d->plane, d->row_stride);
   d->W = fr.width; d->H = fr.height; d->mb_w = g.mb_w; d->n_mcus = g.n_mcus; d->nseg = g.nseg;
   d->has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
 }
@@ -1541,7 +1605,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
                   hipStream_t st, unsigned long long* d_bits, uint32_t* kept, const sjpeg_internal::PackedSink* sink,
                   const uint32_t* kept_base) {
-  a.pscale = e->pscale; a.pbias = e->pbias;       // (the float class's pixel transform)
+  put_transform(e, &a);                           // (the float class's pixel transform)
   const int ntab = tables_per_frame ? nframes : 1;
   if (kept != nullptr && kept_base == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: the ragged replay takes its frames' kept bases");
   if (sink != nullptr && (d_bits != nullptr || d_sizes == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: packed output needs the sizes");
@@ -1617,7 +1681,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
       const sjpeg_hip_ragged_frame& fr = frames[f];
       const FrameGeo& g = geo[f];
       RaggedFrame& d = desc[f];
-      ragged_geometry(fr, g, nplanes, &d);
+      ragged_geometry(a, fr, g, nplanes, &d);
       d.seg_base = seg; d.pool_base = pool; d.pool_words = plan[f].pool_words;
       d.ubuf_base = ubuf; d.ubuf_words = static_cast<uint32_t>(plan[f].ubuf_words);
       d.chunk_base = chunk; d.max_chunks = max_chunks[f];
@@ -1769,7 +1833,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
                     const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st,
                     uint32_t* kept = nullptr, const uint32_t* kept_base = nullptr) {
   const bool histogram = pass == kPassHisto, error = pass == kPassError, trellis = pass == kPassStatsTrellis;
-  a.pscale = e->pscale; a.pbias = e->pbias;       // (the float class's pixel transform)
+  put_transform(e, &a);                           // (the float class's pixel transform)
   if (trellis && (kept == nullptr || kept_base == nullptr)) return fail(SJPEG_HIP_EINVAL, "internal: the ragged trellis statistics keep their blocks");
   // a partial: one group's / one segment's; a frame's result (words)
   const size_t part_words = histogram ? kHistoPartialWords : error ? 2 : kStatsWords;
@@ -1824,7 +1888,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
     uint32_t base = 0;
     for (int f = l.f0; f < l.f0 + l.nf; ++f) {
       RaggedFrame& d = desc[f];
-      ragged_geometry(frames[f], geo[f], nplanes, &d);
+      ragged_geometry(a, frames[f], geo[f], nplanes, &d);
       d.seg_base = base;                       // (the histogram: its first group -- and partial -- in the launch)
       d.hgroups = histogram ? units[f] : 0u;
       d.kept_base = trellis ? kept_base[f] : 0u;
@@ -2619,7 +2683,7 @@ int sjpeg_hip_encode_batch_src(sjpeg_hip_engine* engine, const sjpeg_hip_source*
         }
         if (engine->lane_done[l] == nullptr) HIP_TRY(hipEventCreateWithFlags(&engine->lane_done[l], hipEventDisableTiming));
         lane_e[l] = engine->lane[l];
-        lane_e[l]->pscale = engine->pscale; lane_e[l]->pbias = engine->pbias;
+        for (int c = 0; c < 3; ++c) { lane_e[l]->pscale[c] = engine->pscale[c]; lane_e[l]->pbias[c] = engine->pbias[c]; }
       }
       if (engine->lane_in == nullptr) HIP_TRY(hipEventCreateWithFlags(&engine->lane_in, hipEventDisableTiming));
       if (!sc.EnsureJobEvents(njobs)) return fail(SJPEG_HIP_ENOMEM, "hipEventCreate(batch scratch) failed");
@@ -3107,7 +3171,8 @@ int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStre
 
 // every frame of an RGB / BGRA / RGBA / planar RGB ragged call checked (the message names the frame)
 int rgb_ragged_frames(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames) {
-  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format)) {
+  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format) &&
+      !sjpeg_internal::is_float_packed(format)) {
     return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA (packed) or planar RGB sources");
   }
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
@@ -3211,7 +3276,8 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
   try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::string err;
-    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format)) {
+    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format) &&
+      !sjpeg_internal::is_float_packed(format)) {
       return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources");
     }
     if (int rc = ragged_ordered(e, st)) return rc;

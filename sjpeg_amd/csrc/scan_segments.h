@@ -289,8 +289,8 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
     constexpr bool INTERIOR = decltype(interior_tag)::value;
     bool tables_staged = false;
     // interior copy: the strip's row pointer advances by a uniform step (no 64-bit multiply per row)
-    // (float planes: the element size is a uniform field, 4 or 2)
-    const int kBpp = (SRC == kSrcRgbPlanarF) ? a.pesz : kSrcPixelBytes<SRC>;
+    // (float elements: their size and the elements between pixels are uniform fields)
+    const int kBpp = (SRC == kSrcRgbPlanarF) ? a.pesz * a.pstep : kSrcPixelBytes<SRC>;
     const long long rs = a.row_stride[0];
     const uint8_t* prow = frame_px + static_cast<long long>(mb_y * PX + yp0 * kRowsPerStrip) * rs + kBpp * x0;
     const long long pstep = static_cast<long long>(ngroups * kRowsPerStrip) * rs;      // uniform
@@ -308,9 +308,7 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
             for (int r = 0; r < kRowsPerStrip; ++r) {
               if (SRC == kSrcRgbPlanarF) {
                 // converted as the loads land: the prefetch buffer stays six dwords a row
-                sjpeg_internal::elem_load8(prow + r * rs, a.pkind, a.pscale, a.pbias, raw[it][r]);
-                sjpeg_internal::elem_load8(prow + (r * rs + dg), a.pkind, a.pscale, a.pbias, raw[it][r] + 2);
-                sjpeg_internal::elem_load8(prow + (r * rs + db), a.pkind, a.pscale, a.pbias, raw[it][r] + 4);
+                load_float_row8(a, prow + r * rs, dg, db, raw[it][r]);
               } else if (SRC == kSrcRgbPlanar) {
                 __builtin_memcpy(raw[it][r], prow + r * rs, 8);
                 __builtin_memcpy(raw[it][r] + 2, prow + (r * rs + dg), 8);

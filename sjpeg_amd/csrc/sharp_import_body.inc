@@ -1,6 +1,6 @@
 // sharp_import_body.inc -- the body of sharp_import, included INSIDE the uniform kernel and its ragged twin
 // (sharp_yuv.hip) behind their prologues. Textual, not a __device__ function: the uniform kernel then reads its
-// arguments exactly as before and compiles to the same code. SHARP_PX(p, off): the sample at p + off, 0..255 (the
+// arguments exactly as before and compiles to the same code. SHARP_PX(p, off, c): the sample of channel c at p + off, 0..255 (the
 // uniform kernel: the byte there; the ragged one: through the element load of pixel_elem.h). Names: `a` (SharpArgs of the frame), `frame`, `c`, `ry`.
   if (c >= a.uv_w) return;
   const uint8_t* base = a.rgb + frame * a.frame_stride;
@@ -12,9 +12,9 @@
     for (int cc = 0; cc < 2; ++cc) {
       const int xx = min(2 * c + cc, a.W - 1);               // right replication
       const uint8_t* p = base + yy * a.row_stride + static_cast<long long>(xx) * a.pix_step;
-      px[r][cc][0] = (SHARP_PX(p, a.r_off) << kSfix) | (1 << kSfix >> 1);
-      px[r][cc][1] = (SHARP_PX(p, a.g_off) << kSfix) | (1 << kSfix >> 1);
-      px[r][cc][2] = (SHARP_PX(p, a.b_off) << kSfix) | (1 << kSfix >> 1);
+      px[r][cc][0] = (SHARP_PX(p, a.r_off, 0) << kSfix) | (1 << kSfix >> 1);
+      px[r][cc][1] = (SHARP_PX(p, a.g_off, 1) << kSfix) | (1 << kSfix >> 1);
+      px[r][cc][2] = (SHARP_PX(p, a.b_off, 2) << kSfix) | (1 << kSfix >> 1);
     }
   }
   int wt[2][2], uv[3];

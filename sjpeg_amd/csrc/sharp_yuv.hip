@@ -64,7 +64,7 @@ struct SharpArgs {
   long long y_frame_stride, uv_frame_stride;
   int stress;                                     // race stress builds only (SJPEG_HIP_ABLATE), else 0
   int ekind;                                      // ragged form: element kind (pixel_elem.h) and the pixel transform
-  float pscale, pbias;
+  float pscale[3], pbias[3];                      // (per channel R, G, B)
 };
 
 __device__ __forceinline__ uint32_t lin2gamma(const uint32_t* l2g, uint32_t value) {   // :158-171
@@ -108,7 +108,7 @@ __device__ __forceinline__ void eval_group(const uint32_t* g2l, const uint32_t* 
 __global__ __launch_bounds__(256) void sharp_import(const SharpArgs a) {
   const int frame = blockIdx.z;
   const int c = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
-#define SHARP_PX(p, off) (p)[off]
+#define SHARP_PX(p, off, c) (p)[off]
 #include "sharp_import_body.inc"
 #undef SHARP_PX
 }
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(256) void sharp_export(const SharpArgs a) {
 // ---- pictures too small for the iterative conversion (:57-100,674-690): plain averaging
 __global__ __launch_bounds__(64) void sharp_small(const SharpArgs a) {
   const int frame = blockIdx.x;
-#define SHARP_PX(p, off) (p)[off]
+#define SHARP_PX(p, off, c) (p)[off]
 #include "sharp_small_body.inc"
 #undef SHARP_PX
 }
@@ -750,7 +750,7 @@ __global__ __launch_bounds__(256) void sharp_import_ragged(const SharpArgs commo
   const int frame = 0;
   const int c = (local % static_cast<unsigned>(d.gx)) * 256 + threadIdx.x, ry = local / static_cast<unsigned>(d.gx);
   // (the ragged form's samples: bytes as they are, or float elements through the engine's pixel transform)
-#define SHARP_PX(p, off) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale, a.pbias)
+#define SHARP_PX(p, off, c) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale[c], a.pbias[c])
 #include "sharp_import_body.inc"
 #undef SHARP_PX
 }
@@ -792,7 +792,7 @@ __global__ __launch_bounds__(64) void sharp_small_ragged(const SharpArgs common,
   a.y = d.y; a.u = d.u; a.v = d.v;
   a.y_frame_stride = 0; a.uv_frame_stride = 0;
   const int frame = 0;
-#define SHARP_PX(p, off) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale, a.pbias)
+#define SHARP_PX(p, off, c) sjpeg_internal::elem_load_u8((p) + (off), a.ekind, a.pscale[c], a.pbias[c])
 #include "sharp_small_body.inc"
 #undef SHARP_PX
 }
@@ -853,6 +853,10 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
   memset(&a, 0, sizeof(a));
   if (sjpeg_internal::is_float_planar(src->format)) {   // (no engine, no pixel transform)
     return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_sharp_yuv: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
+                                                       "pixel transform: use sjpeg_hip_sharp_yuv_ragged");
+  }
+  if (sjpeg_internal::is_float_format(src->format)) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_sharp_yuv: SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F* need an engine's "
                                                        "pixel transform: use sjpeg_hip_sharp_yuv_ragged");
   }
   if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
@@ -982,12 +986,13 @@ size_t sharp_ragged_workspace(int nframes, const sjpeg_hip_ragged_frame* frames)
   return align256(sizeof(GammaTables)) + align256(sizeof(SharpFrame) * nframes) + align256(ctrl * 4) + blocks;
 }
 
-int sharp_ragged_run(int format, float pscale, float pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
+int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nframes, const sjpeg_hip_ragged_frame* frames, uint8_t* const* d_y,
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err) {
   SharpArgs a;
   memset(&a, 0, sizeof(a));
-  a.ekind = elem_kind(format); a.pscale = pscale; a.pbias = pbias;
+  a.ekind = elem_kind(format);
+  for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
   if (!rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
     *err = "the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources";
     return SJPEG_HIP_EINVAL;
@@ -1006,10 +1011,14 @@ int sharp_ragged_run(int format, float pscale, float pbias, int nframes, const s
     }
     if (fr.plane[0] == nullptr || d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
     const int64_t st_abs = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
-    if (st_abs < static_cast<int64_t>(a.pix_step) * fr.width) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
+    const int64_t row_need = is_float_packed(format) ? elem_row_bytes(format, fr.width) : static_cast<int64_t>(a.pix_step) * fr.width;
+    if (st_abs < row_need) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
     if (is_rgb_planar(format)) {
       if (const char* fault = rgb_planar_fault(fr.plane, fr.row_stride, nullptr)) { *err = w + fault; return SJPEG_HIP_EINVAL; }
       const std::string efault = rgb_float_fault(format, fr.plane, fr.row_stride, nullptr);
+      if (!efault.empty()) { *err = w + efault; return SJPEG_HIP_EINVAL; }
+    } else if (is_float_packed(format)) {
+      const std::string efault = rgb_float_fault(format, fr.plane, fr.row_stride, nullptr, 1);
       if (!efault.empty()) { *err = w + efault; return SJPEG_HIP_EINVAL; }
     }
   }
