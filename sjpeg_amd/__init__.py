@@ -48,11 +48,24 @@ SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16 = 9, 10, 11
 SRC_RGB_F32, SRC_RGB_F16, SRC_RGB_BF16 = 12, 13, 14
 SRC_RGBA_F32, SRC_RGBA_F16, SRC_RGBA_BF16 = 15, 16, 17
 SRC_GRAY_F32, SRC_GRAY_F16, SRC_GRAY_BF16 = 18, 19, 20
-_PLANAR_RGB = (SRC_RGB_PLANAR, SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16)
-_FLOAT_ELEMENT_BYTES = {f: (4, 2, 2)[(f - SRC_RGB_PLANAR_F32) % 3] for f in range(SRC_RGB_PLANAR_F32, SRC_GRAY_BF16 + 1)}
-_GRAY_FLOAT = (SRC_GRAY_F32, SRC_GRAY_F16, SRC_GRAY_BF16)
-_IMPLIED_MODE = {SRC_GRAY: YUV_400, SRC_YUV444: YUV_444, SRC_YUV420: YUV_420, SRC_NV12: YUV_420,
-                 SRC_NV21: YUV_420, SRC_GRAY_F32: YUV_400, SRC_GRAY_F16: YUV_400, SRC_GRAY_BF16: YUV_400}
+# What a format is, once (the library's table: sjpeg_amd/csrc/source_layout.h) -- format: (planes read, elements from a
+# pixel to the next, how many of them are read, the elements' torch dtype by name or None for bytes, the yuv_mode the
+# format implies or None, the name layout="chw" pictures of that memory layout go by or None)
+_FORMATS = {SRC_RGB: (1, 3, 3, None, None, "rgb"), SRC_BGRA: (1, 4, 4, None, None, None), SRC_RGBA: (1, 4, 4, None, None, "rgba"),
+            SRC_GRAY: (1, 1, 1, None, YUV_400, None), SRC_YUV444: (3, 1, 1, None, YUV_444, None), SRC_YUV420: (3, 1, 1, None, YUV_420, None),
+            SRC_NV12: (2, 1, 1, None, YUV_420, None), SRC_NV21: (2, 1, 1, None, YUV_420, None), SRC_RGB_PLANAR: (3, 1, 1, None, None, "planar")}
+for _k, _dt in enumerate(("float32", "float16", "bfloat16")):
+    _FORMATS.update({(SRC_RGB_PLANAR_F32, SRC_RGB_PLANAR_F16, SRC_RGB_PLANAR_BF16)[_k]: (3, 1, 1, _dt, None, "planar"),
+                     (SRC_RGB_F32, SRC_RGB_F16, SRC_RGB_BF16)[_k]: (1, 3, 3, _dt, None, "rgb"),
+                     (SRC_RGBA_F32, SRC_RGBA_F16, SRC_RGBA_BF16)[_k]: (1, 4, 3, _dt, None, "rgba"),
+                     (SRC_GRAY_F32, SRC_GRAY_F16, SRC_GRAY_BF16)[_k]: (1, 1, 1, _dt, YUV_400, "gray")})
+_DTYPE_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2}
+_PLANAR_RGB = tuple(f for f, row in _FORMATS.items() if row[5] == "planar")
+_FLOAT_ELEMENT_BYTES = {f: _DTYPE_BYTES[row[3]] for f, row in _FORMATS.items() if row[3] is not None}
+_GRAY_FLOAT = tuple(f for f, row in _FORMATS.items() if row[5] == "gray")
+_IMPLIED_MODE = {f: row[4] for f, row in _FORMATS.items() if row[4] is not None}
+# (chw name, dtype name or None) -> format
+_CHW_FORMAT = {(row[5], row[3]): f for f, row in _FORMATS.items() if row[5] is not None}
 
 
 class Source(C.Structure):
@@ -67,7 +80,7 @@ def sharp_yuv(fmt, frames):
     import torch
     assert frames.is_cuda and frames.dim() == 3
     f, h, row_bytes = frames.shape
-    bpp = 3 if fmt == SRC_RGB else 4
+    bpp = _FORMATS[fmt][1]
     w = row_bytes // bpp
     cw, ch = (w + 1) // 2, (h + 1) // 2
     src, _ = make_source(fmt, [frames])
@@ -130,7 +143,7 @@ def make_source(fmt, planes):
 
 def _float_dtypes():
     import torch
-    return {f: (torch.float32, torch.float16, torch.bfloat16)[(f - SRC_RGB_PLANAR_F32) % 3] for f in _FLOAT_ELEMENT_BYTES}
+    return {f: getattr(torch, _FORMATS[f][3]) for f in _FLOAT_ELEMENT_BYTES}
 
 
 def _three(who, what, v):
@@ -1532,7 +1545,7 @@ def _chw_planes(who, images, fp=None):
     has one format: every image lies as image 0 does."""
     import torch
     dev = None
-    esz, kind0, dt = 1, None, 0
+    esz, kind0, dt = 1, None, None                   # (dt: the float dtype by name; None: bytes)
     for k, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
@@ -1540,13 +1553,13 @@ def _chw_planes(who, images, fp=None):
             if im.dtype != torch.uint8:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
         else:
-            by_dtype = {d: f for f, d in _float_dtypes().items() if f in _PLANAR_RGB}
+            by_dtype = {getattr(torch, name): name for name in _DTYPE_BYTES}
             if im.dtype not in by_dtype:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}: FloatPixels take torch.float32, torch.float16 or "
                                  f"torch.bfloat16")
             if k > 0 and im.dtype != images[0].dtype:
                 raise SjpegError(f"{who}: image {k} is {im.dtype}, image 0 {images[0].dtype}: one dtype per call")
-            dt, esz = by_dtype[im.dtype] - SRC_RGB_PLANAR_F32, im.element_size()
+            dt, esz = by_dtype[im.dtype], im.element_size()
         kinds = _chw_kinds(im, fp is not None)
         if not kinds:
             raise SjpegError(f"{who}: image {k} must be [3, H, W] planar RGB with layout='chw' (stride 1 over x; its "
@@ -1566,16 +1579,14 @@ def _chw_planes(who, images, fp=None):
     # passes with any stride(2), and a one-row picture is handed over with its width as the row stride)
     # (strides in bytes: esz is the element size, 1 for uint8)
     kind0 = kind0[0] if kind0 else "planar"          # (planar before interleaved where a call could be read as both)
+    fmt = _CHW_FORMAT[(kind0, dt)]
     if kind0 == "planar":
-        fmt = SRC_RGB_PLANAR if fp is None else SRC_RGB_PLANAR_F32 + dt
         planes = [[(im.data_ptr() + c * im.stride(0) * esz, (im.stride(1) if im.shape[1] > 1 else im.shape[2]) * esz)
                    for c in range(3)] for im in images]
     elif kind0 == "gray":
-        fmt = SRC_GRAY_F32 + dt
         planes = [[(im.data_ptr(), (im.stride(-2) if im.shape[-2] > 1 else im.shape[-1]) * esz)] for im in images]
     else:
-        step = 3 if kind0 == "rgb" else 4
-        fmt = {"rgb": SRC_RGB, "rgba": SRC_RGBA}[kind0] if fp is None else (SRC_RGB_F32 if step == 3 else SRC_RGBA_F32) + dt
+        step = _FORMATS[fmt][1]
         planes = [[(im.data_ptr(), (im.stride(1) if im.shape[1] > 1 else im.shape[2] * step) * esz)] for im in images]
     dims = [(int(im.shape[-1]), int(im.shape[-2])) for im in images]
     return planes, dims, dev, fmt

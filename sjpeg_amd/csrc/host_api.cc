@@ -23,6 +23,7 @@
 #include "jpeg_host.h"
 #include "sjpeg.h"
 #include "sjpeg_hip.h"
+#include "source_layout.h"
 
 using sjpeg_host::HuffSpec;
 
@@ -421,9 +422,9 @@ bool Encoder::Run() {
 bool Encoder::RunImpl() {
   sink_->Reset();                                                   // src/enc.cc:90
   if (W_ > 65535 || H_ > 65535) return Fail("dimension > 65535");   // src/enc.cc:406
-  if (src_.format == SJPEG_HIP_SRC_GRAY) yuv_mode_ = SJPEG_YUV_400;                 // src/encoders.cc:256-276
-  else if (src_.format == SJPEG_HIP_SRC_YUV444) yuv_mode_ = SJPEG_YUV_444;          // :384-419
-  else if (src_.format >= SJPEG_HIP_SRC_YUV420) yuv_mode_ = SJPEG_YUV_420;          // :281-344, :442-490
+  const sjpeg_internal::SourceLayout& L = *sjpeg_internal::source_layout(src_.format);   // (a HostSource names a byte format)
+  // a YUV or gray source says its sampling (src/encoders.cc:256-276, :281-344, :384-419, :442-490), a SjpegYUVMode value
+  if (L.implied != 0) yuv_mode_ = static_cast<SjpegYUVMode>(L.implied);
   if (yuv_mode_ != SJPEG_YUV_AUTO && yuv_mode_ != SJPEG_YUV_420 && yuv_mode_ != SJPEG_YUV_SHARP &&
       yuv_mode_ != SJPEG_YUV_444 && yuv_mode_ != SJPEG_YUV_400) {
     return Fail("unknown yuv_mode");                                 // src/encoders.cc:553-567
@@ -454,28 +455,12 @@ bool Encoder::RunImpl() {
   memset(&dsrc, 0, sizeof(dsrc));
   dsrc.format = src_.format;
   {
-    const size_t cw = (static_cast<size_t>(W_) + 1) / 2, ch = (static_cast<size_t>(H_) + 1) / 2;
+    const size_t ch = (static_cast<size_t>(H_) + 1) / 2;
     size_t row_bytes[3] = {0, 0, 0}, rows[3] = {0, 0, 0};
-    int nplanes = 1;
-    switch (src_.format) {
-      case SJPEG_HIP_SRC_RGB: row_bytes[0] = 3 * static_cast<size_t>(W_); rows[0] = H_; break;
-      case SJPEG_HIP_SRC_BGRA:
-      case SJPEG_HIP_SRC_RGBA: row_bytes[0] = 4 * static_cast<size_t>(W_); rows[0] = H_; break;
-      case SJPEG_HIP_SRC_GRAY: row_bytes[0] = W_; rows[0] = H_; break;
-      case SJPEG_HIP_SRC_YUV444:
-        nplanes = 3;
-        for (int i = 0; i < 3; ++i) { row_bytes[i] = W_; rows[i] = H_; }
-        break;
-      case SJPEG_HIP_SRC_YUV420:
-        nplanes = 3;
-        row_bytes[0] = W_; rows[0] = H_;
-        row_bytes[1] = row_bytes[2] = cw; rows[1] = rows[2] = ch;
-        break;
-      default:   // NV12 / NV21
-        nplanes = 2;
-        row_bytes[0] = W_; rows[0] = H_;
-        row_bytes[1] = 2 * cw; rows[1] = ch;
-        break;
+    const int nplanes = L.planes;
+    for (int i = 0; i < nplanes; ++i) {
+      row_bytes[i] = static_cast<size_t>(sjpeg_internal::row_bytes(L, i, W_));
+      rows[i] = L.plane[i].chroma ? ch : static_cast<size_t>(H_);
     }
     size_t offset[3] = {0, 0, 0}, pitch[3] = {0, 0, 0}, total = 0;
     for (int i = 0; i < nplanes; ++i) {

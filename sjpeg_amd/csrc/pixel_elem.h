@@ -18,25 +18,6 @@ namespace sjpeg_internal {
 // element kinds of a source: bytes as they are, or floats through the engine's pixel transform
 enum { kElemU8 = 0, kElemF32 = 1, kElemF16 = 2, kElemBF16 = 3 };
 
-// (the float formats come in threes: fp32, half, bfloat16 -- planar 9..11, RGB 12..14, RGBA 15..17, gray 18..20)
-inline bool is_float_format(int format) { return format >= SJPEG_HIP_SRC_RGB_PLANAR_F32 && format <= SJPEG_HIP_SRC_GRAY_BF16; }
-inline int elem_kind(int format) {
-  return is_float_format(format) ? kElemF32 + (format - SJPEG_HIP_SRC_RGB_PLANAR_F32) % 3 : kElemU8;
-}
-inline int elem_bytes(int kind) { return kind == kElemF32 ? 4 : kind == kElemU8 ? 1 : 2; }
-inline bool is_float_planar(int format) { return format >= SJPEG_HIP_SRC_RGB_PLANAR_F32 && format <= SJPEG_HIP_SRC_RGB_PLANAR_BF16; }
-inline bool is_rgb_planar(int format) { return format == SJPEG_HIP_SRC_RGB_PLANAR || is_float_planar(format); }
-// one plane of interleaved float pixels (R, G, B and, with a step of 4, an element that is never read) / of gray floats
-inline bool is_float_packed(int format) { return format >= SJPEG_HIP_SRC_RGB_F32 && format <= SJPEG_HIP_SRC_RGBA_BF16; }
-inline bool is_float_gray(int format) { return format >= SJPEG_HIP_SRC_GRAY_F32 && format <= SJPEG_HIP_SRC_GRAY_BF16; }
-// elements from one pixel of a row to the next, and the elements of a pixel that are read
-inline int elem_step(int format) { return !is_float_packed(format) ? 1 : format >= SJPEG_HIP_SRC_RGBA_F32 ? 4 : 3; }
-inline int elem_channels(int format) { return is_float_gray(format) ? 1 : 3; }
-// bytes of a row of `width` pixels of a one-plane float format, up to the last element that is read
-inline int64_t elem_row_bytes(int format, int64_t width) {
-  return ((width - 1) * elem_step(format) + elem_channels(format)) * elem_bytes(elem_kind(format));
-}
-
 #if defined(__HIPCC__)
 // fmaf(x, scale, bias) as byte `pos` (0..3, a constant) of `old`
 template <int POS>

@@ -12,6 +12,7 @@
 #include "jpeg_host.h"
 #include "pixel_elem.h"
 #include "sjpeg_hip.h"
+#include "source_layout.h"
 
 namespace sjpeg_internal {
 
@@ -59,64 +60,6 @@ inline uint8_t* place_sharp_planes(uint8_t* arena, const std::vector<sjpeg_hip_r
   return at;
 }
 
-// the channel layout of a packed RGB / BGRA / RGBA or planar RGB source (the riskiness stencil and the sharp conversion
-// start from these); false for any other format.  The offsets count from plane[0]: planar RGB is pix_step 1 with G and
-// B a whole plane away -- its g_off and b_off are the picture's own (rgb_frame_offsets), hence 64 bits.
-inline bool rgb_layout(int format, int* pix_step, long long* r_off, long long* g_off, long long* b_off) {
-  switch (format) {
-    case SJPEG_HIP_SRC_RGB: *pix_step = 3; *r_off = 0; *g_off = 1; *b_off = 2; return true;
-    case SJPEG_HIP_SRC_BGRA: *pix_step = 4; *r_off = 2; *g_off = 1; *b_off = 0; return true;
-    case SJPEG_HIP_SRC_RGBA: *pix_step = 4; *r_off = 0; *g_off = 1; *b_off = 2; return true;
-    case SJPEG_HIP_SRC_RGB_PLANAR: *pix_step = 1; *r_off = 0; *g_off = 0; *b_off = 0; return true;
-    // (float planes: a pixel step of one element; the kernels read the samples through pixel_elem.h)
-    case SJPEG_HIP_SRC_RGB_PLANAR_F32: *pix_step = 4; *r_off = 0; *g_off = 0; *b_off = 0; return true;
-    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
-    case SJPEG_HIP_SRC_RGB_PLANAR_BF16: *pix_step = 2; *r_off = 0; *g_off = 0; *b_off = 0; return true;
-    default: break;
-  }
-  // (interleaved float pixels: step elements a pixel, G and B one and two elements behind R -- all in bytes)
-  if (is_float_packed(format)) {
-    const int esz = elem_bytes(elem_kind(format));
-    *pix_step = elem_step(format) * esz; *r_off = 0; *g_off = esz; *b_off = 2 * esz;
-    return true;
-  }
-  return false;
-}
-// g_off and b_off of one picture (or of a uniform batch) of such a source: the layout's, or (planar RGB) the distances of
-// its G and B planes from its R plane
-inline void rgb_frame_offsets(int format, const void* const* plane, long long* g_off, long long* b_off) {
-  int step = 0;
-  long long r = 0;
-  if (!rgb_layout(format, &step, &r, g_off, b_off) || !is_rgb_planar(format)) return;
-  *g_off = static_cast<const uint8_t*>(plane[1]) - static_cast<const uint8_t*>(plane[0]);
-  *b_off = static_cast<const uint8_t*>(plane[2]) - static_cast<const uint8_t*>(plane[0]);
-}
-// what is wrong with the planes of a planar RGB picture (one pitch, three bases: sjpeg_hip.h), or NULL;
-// frame_stride is NULL where the call has none (one picture of a ragged batch)
-inline const char* rgb_planar_fault(const void* const* plane, const int64_t* row_stride, const int64_t* frame_stride) {
-  if (plane[1] == nullptr || plane[2] == nullptr) return "null plane pointer";
-  if (row_stride[1] != row_stride[0]) return "row_stride[1] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
-  if (row_stride[2] != row_stride[0]) return "row_stride[2] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
-  if (frame_stride != nullptr && frame_stride[1] != frame_stride[0]) return "frame_stride[1] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
-  if (frame_stride != nullptr && frame_stride[2] != frame_stride[0]) return "frame_stride[2] must equal frame_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)";
-  return nullptr;
-}
-// what is wrong with the addresses of a picture of float elements (planes and strides are multiples of the element size
-// -- all the alignment the kernels assume), or empty; nplanes: how many of plane[] and the strides are looked at (3 for
-// the planar formats, 1 for the one-plane ones)
-inline std::string rgb_float_fault(int format, const void* const* plane, const int64_t* row_stride, const int64_t* frame_stride,
-                                   int nplanes = 3) {
-  const int64_t esz = elem_bytes(elem_kind(format));
-  if (esz == 1) return std::string();
-  const std::string tail = " must be a multiple of the element size (" + std::to_string(esz) + " bytes)";
-  for (int i = 0; i < nplanes; ++i) {
-    if (reinterpret_cast<uintptr_t>(plane[i]) % static_cast<uintptr_t>(esz) != 0) return "plane[" + std::to_string(i) + "]" + tail;
-    if (row_stride[i] % esz != 0) return "row_stride[" + std::to_string(i) + "]" + tail;
-    if (frame_stride != nullptr && frame_stride[i] % esz != 0) return "frame_stride[" + std::to_string(i) + "]" + tail;
-  }
-  return std::string();
-}
-
 // ---- ragged riskiness: one descriptor per frame; a workgroup finds its frame by a binary search over wg_base
 struct RiskFrame {
   const uint8_t* rgb;                    // row 0
@@ -124,7 +67,7 @@ struct RiskFrame {
   int W, H;
   int bands, cols;                       // the frame's workgroups: cols x bands (none when W or H < 2)
   unsigned wg_base, pad;                 // its first workgroup in the flat grid
-  long long g_off, b_off;                // where G and B lie from R (rgb_frame_offsets)
+  long long g_off, b_off;                // where G and B lie from R (layout_rgb_offsets)
 };
 
 // the frame's workgroups: bands of at least 16 rows, at most 64 of them; 256 columns each

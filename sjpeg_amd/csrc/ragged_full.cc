@@ -605,8 +605,8 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
   }
   if (P.quant == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params->quant == NULL");
   const bool by_mode = yuv_mode == kYuvAuto || yuv_mode == kYuvSharp;
-  if (by_mode && format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA &&
-      !is_rgb_planar(format) && !is_float_packed(format)) {
+  const SourceLayout* const L = source_layout(format);
+  if (by_mode && (L == nullptr || !L->rgb_like)) {
     return set_error(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO and SJPEG_YUV_SHARP take RGB, BGRA or RGBA (packed) or planar RGB sources");
   }
   for (int k = 0; P.search != nullptr && k < (P.search_per_frame ? nframes : 1); ++k) {

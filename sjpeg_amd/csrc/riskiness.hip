@@ -106,21 +106,17 @@ extern "C" int sjpeg_hip_riskiness_sums(const sjpeg_hip_source* src, int width, 
   RiskArgs a;
   memset(&a, 0, sizeof(a));
   // (no engine, no pixel transform: float planes go through sjpeg_hip_riskiness_ragged_src)
-  if (sjpeg_internal::is_float_planar(src->format)) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_sums: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
-                                                       "pixel transform: use sjpeg_hip_riskiness_ragged_src");
+  const sjpeg_internal::SourceLayout* const L = sjpeg_internal::source_layout(src->format);
+  if (L != nullptr && L->kind != sjpeg_internal::kElemU8) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, std::string("sjpeg_hip_riskiness_sums: ") +
+                                                           (L->one_pitch ? "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16" : "SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*") +
+                                                           " need an engine's pixel transform: use sjpeg_hip_riskiness_ragged_src");
   }
-  if (sjpeg_internal::is_float_format(src->format)) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_riskiness_sums: SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F* need an engine's "
-                                                       "pixel transform: use sjpeg_hip_riskiness_ragged_src");
-  }
-  if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
-  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
-    if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
-    const int64_t st_abs = src->row_stride[0] < 0 ? -src->row_stride[0] : src->row_stride[0];
-    if (st_abs < width) return SJPEG_HIP_EINVAL;
-    sjpeg_internal::rgb_frame_offsets(src->format, src->plane, &a.g_off, &a.b_off);
-  }
+  if (L == nullptr || !L->rgb_like) return SJPEG_HIP_EINVAL;
+  const bool faulty = sjpeg_internal::layout_fault(*L, width, src->plane, src->row_stride, src->frame_stride, sjpeg_internal::kUniformChecks).rule != 0;
+  if (L->one_pitch && faulty) return SJPEG_HIP_EINVAL;      // (the packed formats' strides are the caller's word here, as ever)
+  a.pix_step = L->pix_step; a.r_off = L->r_off;
+  sjpeg_internal::layout_rgb_offsets(*L, src->plane, &a.g_off, &a.b_off);
   hipStream_t st = static_cast<hipStream_t>(stream);
   a.rgb = static_cast<const uint8_t*>(src->plane[0]);
   a.row_stride = src->row_stride[0]; a.frame_stride = src->frame_stride[0];
@@ -140,8 +136,10 @@ int risk_ragged_launch(int format, const float* pscale, const float* pbias, cons
                        const uint8_t* d_table, uint64_t* d_sums, hipStream_t st) {
   RiskArgs a;
   memset(&a, 0, sizeof(a));
-  if (!sjpeg_internal::rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) return SJPEG_HIP_EINVAL;
-  a.ekind = elem_kind(format);
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr || !L->rgb_like) return SJPEG_HIP_EINVAL;
+  a.pix_step = L->pix_step; a.r_off = L->r_off; a.g_off = L->g_off; a.b_off = L->b_off;   // (g_off, b_off: the frames' own are read)
+  a.ekind = L->kind;
   for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
   a.table = d_table;
   a.out = reinterpret_cast<unsigned long long*>(d_sums);

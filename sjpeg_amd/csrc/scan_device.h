@@ -62,7 +62,7 @@ static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 
 // gray -- SJPEG_HIP_SRC_GRAY_F*, ScanArgs::pone, a HOST-side flag: the three "planes" are the one plane and the three
 // channels' transform is channel 0's, so the plane's bytes are R, G and B alike, whose luma is the gray value itself:
 // (19595 + 38469 + 7471) v + 32768 >> 16 = v for v = 0..255)
-enum { kSrcRgb24 = 0, kSrcRgbx32 = 1, kSrcPlanes = 2, kSrcRgbPlanar = 3, kSrcRgbPlanarF = 4 };
+// (kSrcRgb24, kSrcRgbx32, kSrcPlanes, kSrcRgbPlanar, kSrcRgbPlanarF: source_layout.h, where every format gets its class)
 // raw dwords of a row of 8 pixels, and bytes between pixels of a row, of the classes the colour phase converts
 // (kSrcRgbPlanarF: the bytes between pixels are ScanArgs::pesz * ScanArgs::pstep)
 template <int SRC> constexpr int kSrcRowWords = (SRC == kSrcRgbx32) ? 8 : 6;

@@ -494,17 +494,10 @@ SegPlan seg_plan(const FrameGeo& g, size_t budget_bytes) {
 void put_transform(const sjpeg_hip_engine* e, ScanArgs* a) {
   for (int c = 0; c < 3; ++c) { a->pscale[c] = e->pscale[a->pone ? 0 : c]; a->pbias[c] = e->pbias[a->pone ? 0 : c]; }
 }
-// the float class's fields of a one-plane float format (SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*)
-void float_format_fields(int format, ScanArgs* a) {
-  a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
-  a->pstep = sjpeg_internal::elem_step(format); a->pone = sjpeg_internal::is_float_gray(format) ? 1 : 0;
-}
-// ... and its three "planes" from the one it has: G and B one and two elements behind R (gray: all three the same),
-// one pitch -- what the float class's loader takes
-void float_one_plane(const ScanArgs& a, const uint8_t** plane, long long* row_stride) {
-  plane[1] = plane[0] + (a.pone ? 0 : a.pesz);
-  plane[2] = plane[0] + (a.pone ? 0 : 2 * a.pesz);
-  row_stride[1] = row_stride[2] = row_stride[0];
+// a format's fields of a launch's arguments (the float class's stay zero for the byte formats, which ignore them)
+void layout_args(const SourceLayout& L, ScanArgs* a) {
+  a->rsh = L.rsh; a->bsh = L.bsh; a->cstep = L.cstep; a->uoff = L.uoff; a->voff = L.voff;
+  if (L.kind != kElemU8) { a->pkind = L.kind; a->pesz = L.esz; a->pstep = L.pstep; a->pone = L.pone; }
 }
 
 int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
@@ -516,83 +509,28 @@ int prepare_scan(sjpeg_hip_engine* e, const sjpeg_hip_source* src,
     return fail(SJPEG_HIP_EINVAL, "null argument or nframes <= 0");
   }
   if (!frame_geo(W, H, mode, g)) return fail(SJPEG_HIP_EINVAL, "bad dimensions or yuv_mode");
-  // per-plane minimum row size and the colour mode each layout implies
+  // the format's row (source_layout.h): the colour mode it implies, what its planes and strides must keep
   // (reference argument checks: src/api.cc:35-36,205-206,260; src/encoders.cc:352-355,427-432)
-  const int64_t cw = (W + 1) / 2;
-  int64_t need[3] = {0, 0, 0};
-  int nplanes = 1, implied = 0;
   memset(a, 0, sizeof(*a));
-  switch (src->format) {
-    case SJPEG_HIP_SRC_RGB: need[0] = 3ll * W; *src_class = kSrcRgb24; break;
-    case SJPEG_HIP_SRC_BGRA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
-    case SJPEG_HIP_SRC_RGBA: need[0] = 4ll * W; *src_class = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
-    case SJPEG_HIP_SRC_RGB_PLANAR: need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcRgbPlanar; break;
-    case SJPEG_HIP_SRC_RGB_PLANAR_F32:
-    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
-    case SJPEG_HIP_SRC_RGB_PLANAR_BF16:
-      a->pkind = sjpeg_internal::elem_kind(src->format); a->pesz = sjpeg_internal::elem_bytes(a->pkind);
-      need[0] = need[1] = need[2] = static_cast<int64_t>(a->pesz) * W; nplanes = 3; *src_class = kSrcRgbPlanarF;
-      a->pstep = 1;
-      break;
-    case SJPEG_HIP_SRC_RGB_F32: case SJPEG_HIP_SRC_RGB_F16: case SJPEG_HIP_SRC_RGB_BF16:
-    case SJPEG_HIP_SRC_RGBA_F32: case SJPEG_HIP_SRC_RGBA_F16: case SJPEG_HIP_SRC_RGBA_BF16:
-    case SJPEG_HIP_SRC_GRAY_F32: case SJPEG_HIP_SRC_GRAY_F16: case SJPEG_HIP_SRC_GRAY_BF16:
-      // one plane of float elements, served by the float class (float_one_plane below makes its three "planes")
-      float_format_fields(src->format, a);
-      need[0] = sjpeg_internal::elem_row_bytes(src->format, W); *src_class = kSrcRgbPlanarF;
-      if (a->pone) implied = SJPEG_HIP_YUV400;
-      break;
-    case SJPEG_HIP_SRC_GRAY: need[0] = W; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV400; break;
-    case SJPEG_HIP_SRC_YUV444:
-      need[0] = need[1] = need[2] = W; nplanes = 3; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV444;
-      a->cstep = 1;
-      break;
-    case SJPEG_HIP_SRC_YUV420:
-      need[0] = W; need[1] = need[2] = cw; nplanes = 3; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV420;
-      a->cstep = 1;
-      break;
-    case SJPEG_HIP_SRC_NV12:
-    case SJPEG_HIP_SRC_NV21:
-      need[0] = W; need[1] = 2 * cw; nplanes = 2; *src_class = kSrcPlanes; implied = SJPEG_HIP_YUV420;
-      a->cstep = 2;
-      a->uoff = (src->format == SJPEG_HIP_SRC_NV12) ? 0 : 1;
-      a->voff = 1 - a->uoff;
-      break;
-    default: return fail(SJPEG_HIP_EINVAL, "unknown source format");
+  const SourceLayout* const L = source_layout(src->format);
+  if (L == nullptr) return fail(SJPEG_HIP_EINVAL, "unknown source format");
+  *src_class = L->cls;
+  layout_args(*L, a);
+  if (L->implied != 0 && mode != L->implied) return fail(SJPEG_HIP_EINVAL, "yuv_mode does not match the source format");
+  const LayoutFault fault = layout_fault(*L, W, src->plane, src->row_stride, src->frame_stride, kUniformChecks);
+  switch (fault.rule) {
+    case kFaultNone: break;
+    case kFaultRowPitch:      // one pitch, three bases (sjpeg_hip.h): the kernels reach G and B at a uniform distance from R
+      return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: row_stride[" + std::to_string(fault.index) + "] must equal row_stride[0]");
+    case kFaultFramePitch:
+      return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: frame_stride[" + std::to_string(fault.index) + "] must equal frame_stride[0]");
+    case kFaultElemPlane: case kFaultElemRow: case kFaultElemFrame:      // float elements: addresses and strides in whole elements
+      return fail(SJPEG_HIP_EINVAL, std::string(L->one_pitch ? "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: " : "SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*: ") +
+                                        layout_fault_text(*L, fault));
+    default: return fail(SJPEG_HIP_EINVAL, layout_fault_text(*L, fault));
   }
-  if (implied != 0 && mode != implied) return fail(SJPEG_HIP_EINVAL, "yuv_mode does not match the source format");
-  for (int i = 0; i < nplanes; ++i) {
-    if (src->plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, "null plane pointer");
-    const int64_t st_abs = src->row_stride[i] < 0 ? -src->row_stride[i] : src->row_stride[i];
-    if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, "|row_stride| smaller than a row of the plane");
-    a->plane[i] = static_cast<const uint8_t*>(src->plane[i]);
-    a->row_stride[i] = src->row_stride[i];
-    a->frame_stride[i] = src->frame_stride[i];
-  }
-  if (sjpeg_internal::is_rgb_planar(src->format)) {
-    // one pitch, three bases (sjpeg_hip.h): the kernels reach G and B at a uniform distance from R
-    for (int i = 1; i < 3; ++i) {
-      if (src->row_stride[i] != src->row_stride[0]) {
-        return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: row_stride[" + std::to_string(i) + "] must equal row_stride[0]");
-      }
-      if (src->frame_stride[i] != src->frame_stride[0]) {
-        return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR: frame_stride[" + std::to_string(i) + "] must equal frame_stride[0]");
-      }
-    }
-    // float planes: addresses and strides in whole elements
-    const std::string efault = sjpeg_internal::rgb_float_fault(src->format, src->plane, src->row_stride, src->frame_stride);
-    if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16: " + efault);
-  }
-  if (sjpeg_internal::is_float_packed(src->format) || sjpeg_internal::is_float_gray(src->format)) {
-    const std::string efault = sjpeg_internal::rgb_float_fault(src->format, src->plane, src->row_stride, src->frame_stride, 1);
-    if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, "SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*: " + efault);
-    float_one_plane(*a, a->plane, a->row_stride);
-    a->frame_stride[1] = a->frame_stride[2] = a->frame_stride[0];
-  }
+  layout_planes(*L, src->plane, src->row_stride, src->frame_stride, a->plane, a->row_stride, a->frame_stride);
   put_transform(e, a);                            // (read by the float class alone)
-  if (nplanes == 2) {          // interleaved chroma: U and V walk the same plane
-    a->plane[2] = a->plane[1]; a->row_stride[2] = a->row_stride[1]; a->frame_stride[2] = a->frame_stride[1];
-  }
   if (nframes > 65535) return fail(SJPEG_HIP_EINVAL, "nframes > 65535");
   dbg_mark("prepare: begin");
   HIP_TRY(hipSetDevice(e->device));
@@ -1441,100 +1379,47 @@ struct RaggedLaunch {
 };
 
 // The source format of a ragged call (as prepare_scan): the kernel's per-format fields in *a (zeroed first), the source
-// class and the number of planes.  who: the entry point, for the messages.
-int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a, int* cls, int* nplanes) {
+// class and the format's row.  who: the entry point, for the messages.
+int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a, int* cls, const SourceLayout** layout) {
   memset(a, 0, sizeof(*a));
-  int implied = 0;
-  *cls = kSrcPlanes; *nplanes = 1;
-  switch (format) {
-    case SJPEG_HIP_SRC_RGB: *cls = kSrcRgb24; break;
-    case SJPEG_HIP_SRC_BGRA: *cls = kSrcRgbx32; a->rsh = 16; a->bsh = 0; break;
-    case SJPEG_HIP_SRC_RGBA: *cls = kSrcRgbx32; a->rsh = 0; a->bsh = 16; break;
-    case SJPEG_HIP_SRC_RGB_PLANAR: *cls = kSrcRgbPlanar; *nplanes = 3; break;
-    case SJPEG_HIP_SRC_RGB_PLANAR_F32:
-    case SJPEG_HIP_SRC_RGB_PLANAR_F16:
-    case SJPEG_HIP_SRC_RGB_PLANAR_BF16:       // (the engine's pixel transform: ragged_encode / ragged_analysis put it in)
-      *cls = kSrcRgbPlanarF; *nplanes = 3;
-      a->pkind = sjpeg_internal::elem_kind(format); a->pesz = sjpeg_internal::elem_bytes(a->pkind); a->pstep = 1;
-      break;
-    case SJPEG_HIP_SRC_RGB_F32: case SJPEG_HIP_SRC_RGB_F16: case SJPEG_HIP_SRC_RGB_BF16:
-    case SJPEG_HIP_SRC_RGBA_F32: case SJPEG_HIP_SRC_RGBA_F16: case SJPEG_HIP_SRC_RGBA_BF16:
-    case SJPEG_HIP_SRC_GRAY_F32: case SJPEG_HIP_SRC_GRAY_F16: case SJPEG_HIP_SRC_GRAY_BF16:
-      // one plane of float elements, served by the float class (ragged_geometry makes its three "planes")
-      *cls = kSrcRgbPlanarF; float_format_fields(format, a);
-      if (a->pone) implied = SJPEG_HIP_YUV400;
-      break;
-    case SJPEG_HIP_SRC_GRAY: implied = SJPEG_HIP_YUV400; break;
-    case SJPEG_HIP_SRC_YUV444: *nplanes = 3; implied = SJPEG_HIP_YUV444; a->cstep = 1; break;
-    case SJPEG_HIP_SRC_YUV420: *nplanes = 3; implied = SJPEG_HIP_YUV420; a->cstep = 1; break;
-    case SJPEG_HIP_SRC_NV12:
-    case SJPEG_HIP_SRC_NV21:
-      *nplanes = 2; implied = SJPEG_HIP_YUV420; a->cstep = 2;
-      a->uoff = (format == SJPEG_HIP_SRC_NV12) ? 0 : 1;
-      a->voff = 1 - a->uoff;
-      break;
-    default: return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
-  }
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  *cls = L->cls; *layout = L;
+  layout_args(*L, a);                          // (the engine's pixel transform: ragged_encode / ragged_analysis put it in)
   if (yuv_mode != SJPEG_HIP_YUV420 && yuv_mode != SJPEG_HIP_YUV444 && yuv_mode != SJPEG_HIP_YUV400) {
     return fail(SJPEG_HIP_EINVAL, who + ": bad yuv_mode");
   }
-  if (implied != 0 && yuv_mode != implied) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format");
+  if (L->implied != 0 && yuv_mode != L->implied) return fail(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format");
   return 0;
 }
 
-// Every frame of a ragged call checked (the message names the frame); its geometry into (*geo)[f].  out_ranges: the
-// frames' output ranges are checked too (the encodes; the analysis passes ignore them).
-int ragged_frames(const std::string& who, int format, int yuv_mode, int nplanes, int nframes,
+// Every frame of a ragged call of a known format checked (the message names the frame); its geometry into (*geo)[f].
+// out_ranges: the frames' output ranges are checked too (the encodes; the analysis passes ignore them).
+int ragged_frames(const std::string& who, int format, int yuv_mode, int nframes,
                   const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo) {
   geo->resize(nframes);
-  const bool planar_rgb = sjpeg_internal::is_rgb_planar(format);
-  const int64_t esz = sjpeg_internal::elem_bytes(sjpeg_internal::elem_kind(format));     // (1 but for the float planes)
-  if (planar_rgb) nplanes = 3;                                   // (whatever the caller counts: R, G and B are all read)
+  const SourceLayout& L = *source_layout(format);
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
     const std::string w = who + ": frame " + std::to_string(f) + ": ";
     if (!frame_geo(fr.width, fr.height, yuv_mode, &(*geo)[f])) {
       return fail(SJPEG_HIP_EINVAL, w + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
     }
-    const int64_t W = fr.width, cw = (W + 1) / 2;
-    int64_t need[3] = {esz * W, esz * W, esz * W};
-    if (format == SJPEG_HIP_SRC_RGB) need[0] = 3 * W;
-    else if (format == SJPEG_HIP_SRC_BGRA || format == SJPEG_HIP_SRC_RGBA) need[0] = 4 * W;
-    else if (format == SJPEG_HIP_SRC_YUV420) need[1] = need[2] = cw;
-    else if (format == SJPEG_HIP_SRC_NV12 || format == SJPEG_HIP_SRC_NV21) need[1] = 2 * cw;
-    else if (!planar_rgb && esz != 1) need[0] = sjpeg_internal::elem_row_bytes(format, W);    // (one plane of float pixels)
-    for (int i = 0; i < nplanes; ++i) {
-      if (fr.plane[i] == nullptr) return fail(SJPEG_HIP_EINVAL, w + "null plane pointer");
-      const int64_t st_abs = fr.row_stride[i] < 0 ? -fr.row_stride[i] : fr.row_stride[i];
-      if (st_abs < need[i]) return fail(SJPEG_HIP_EINVAL, w + "|row_stride| smaller than a row of the plane");
-      // planar RGB: one pitch, three bases (sjpeg_hip.h)
-      if (planar_rgb && fr.row_stride[i] != fr.row_stride[0]) {
-        return fail(SJPEG_HIP_EINVAL, w + "row_stride[" + std::to_string(i) + "] must equal row_stride[0] (SJPEG_HIP_SRC_RGB_PLANAR)");
-      }
-    }
-    if (esz != 1) {                                              // float planes: addresses and strides in whole elements
-      const std::string efault = sjpeg_internal::rgb_float_fault(format, fr.plane, fr.row_stride, nullptr, planar_rgb ? 3 : 1);
-      if (!efault.empty()) return fail(SJPEG_HIP_EINVAL, w + efault);
-    }
+    const LayoutFault fault = layout_fault(L, fr.width, fr.plane, fr.row_stride, nullptr, kRaggedChecks);
+    if (fault.rule != kFaultNone) return fail(SJPEG_HIP_EINVAL, w + layout_fault_text(L, fault));
     if (out_ranges && fr.out_capacity > UINT64_MAX - fr.out_offset) return fail(SJPEG_HIP_EINVAL, w + "out_offset + out_capacity overflows");
   }
   return 0;
 }
 
-// a frame's planes and geometry in its descriptor
-// (a: the format's fields -- a one-plane float format's frame gets the three "planes" of the float class)
-void ragged_geometry(const ScanArgs& a, const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, int nplanes, RaggedFrame* d) {
-  for (int i = 0; i < 3; ++i) {
-    const int p = (nplanes == 2 && i == 2) ? 1 : i;            // interleaved chroma: U and V walk the same plane
-    d->plane[i] = p < nplanes ? static_cast<const uint8_t*>(fr.plane[p]) : nullptr;
-    d->row_stride[i] = p < nplanes ? fr.row_stride[p] : 0;
-  }
-  if (a.pkind != sjpeg_internal::kElemU8 && nplanes == 1) float_one_plane(a, d->plane, d->row_stride);
+// a frame's planes (the kernels' three out of the caller's: layout_planes) and geometry in its descriptor
+void ragged_geometry(const SourceLayout& L, const sjpeg_hip_ragged_frame& fr, const FrameGeo& g, RaggedFrame* d) {
+  layout_planes(L, fr.plane, fr.row_stride, nullptr, d->plane, d->row_stride, nullptr);
   d->W = fr.width; d->H = fr.height; d->mb_w = g.mb_w; d->n_mcus = g.n_mcus; d->nseg = g.nseg;
   d->has_clip = (fr.width % g.px != 0) || (fr.height % g.px != 0);
 }
 
-int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const SourceLayout* layout, int nframes,
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
@@ -1566,8 +1451,9 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   }
   // the layout of the format (as prepare_scan): planes, source class, the kernel's per-format fields
   ScanArgs a;
-  int cls = kSrcPlanes, nplanes = 1;
-  if (int rcf = ragged_format(kWhoEncode, format, yuv_mode, &a, &cls, &nplanes)) return rcf;
+  int cls = kSrcPlanes;
+  const SourceLayout* layout = nullptr;
+  if (int rcf = ragged_format(kWhoEncode, format, yuv_mode, &a, &cls, &layout)) return rcf;
   size_t header_size = 0;
   if (header_offsets != nullptr) {
     for (int f = 0; f <= nframes; ++f) {
@@ -1579,9 +1465,9 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   }
   // per frame: checks, geometry
   std::vector<FrameGeo> geo;
-  if (int rcg = ragged_frames(kWhoEncode, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rcg;
+  if (int rcg = ragged_frames(kWhoEncode, format, yuv_mode, nframes, frames, true, &geo)) return rcg;
   try {
-    return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, headers, header_offsets,
+    return ragged_encode(e, yuv_mode, cls, a, layout, nframes, frames, geo, tables, tables_per_frame, headers, header_offsets,
                          header_size, append_eoi, d_out, d_sizes, static_cast<hipStream_t>(stream), nullptr);
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
@@ -1599,7 +1485,7 @@ namespace {
 // sink != NULL: packed output -- d_out and the frames' out_offset are not used; per launch K4 leaves the sizes only,
 // place_ragged_frames puts the launch's frames behind the engine's cursor (each start into its descriptor, where K5
 // takes it from, and into the caller's offsets), pack_ragged_edges writes header, EOI and padding (stitch_kernels.h).
-int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const SourceLayout* layout, int nframes,
                   const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                   const sjpeg_hip_scan_tables* tables, int tables_per_frame, const void* headers,
                   const size_t* header_offsets, size_t header_size, int append_eoi, void* d_out, uint64_t* d_sizes,
@@ -1681,7 +1567,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, int np
       const sjpeg_hip_ragged_frame& fr = frames[f];
       const FrameGeo& g = geo[f];
       RaggedFrame& d = desc[f];
-      ragged_geometry(a, fr, g, nplanes, &d);
+      ragged_geometry(*layout, fr, g, &d);
       d.seg_base = seg; d.pool_base = pool; d.pool_words = plan[f].pool_words;
       d.ubuf_base = ubuf; d.ubuf_words = static_cast<uint32_t>(plan[f].ubuf_words);
       d.chunk_base = chunk; d.max_chunks = max_chunks[f];
@@ -1828,7 +1714,7 @@ enum RaggedPass { kPassHisto, kPassStats, kPassError, kPassStatsTrellis };
 // launches over consecutive frames.  kPassStatsTrellis: the statistics with trellis quantization (kKindStatsTrellisRagged;
 // tables with SJPEG_HIP_QUANT_TRELLIS); its quantized blocks stay behind at `kept`, frame f's kept_base[f] segments in
 // (kKeptSegWords a segment), whatever the launches and whichever frames the call covers -- for ragged_encode to replay.
-int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls, ScanArgs a, int nplanes, int nframes,
+int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls, ScanArgs a, const SourceLayout* layout, int nframes,
                     const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                     const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint32_t* d_out, hipStream_t st,
                     uint32_t* kept = nullptr, const uint32_t* kept_base = nullptr) {
@@ -1888,7 +1774,7 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
     uint32_t base = 0;
     for (int f = l.f0; f < l.f0 + l.nf; ++f) {
       RaggedFrame& d = desc[f];
-      ragged_geometry(a, frames[f], geo[f], nplanes, &d);
+      ragged_geometry(*layout, frames[f], geo[f], &d);
       d.seg_base = base;                       // (the histogram: its first group -- and partial -- in the launch)
       d.hgroups = histogram ? units[f] : 0u;
       d.kept_base = trellis ? kept_base[f] : 0u;
@@ -1953,13 +1839,13 @@ int ragged_analysis(sjpeg_hip_engine* e, RaggedPass pass, int yuv_mode, int cls,
 
 // the checks every ragged analysis entry point starts with; the format's fields in *a, the frames' geometry in *geo
 int ragged_analysis_args(const std::string& who, sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
-                         const sjpeg_hip_ragged_frame* frames, const void* d_out, ScanArgs* a, int* cls, int* nplanes,
+                         const sjpeg_hip_ragged_frame* frames, const void* d_out, ScanArgs* a, int* cls, const SourceLayout** layout,
                          std::vector<FrameGeo>* geo) {
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (frames == nullptr || d_out == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": frames or the output == NULL");
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (int rc = ragged_format(who, format, yuv_mode, a, cls, nplanes)) return rc;
-  return ragged_frames(who, format, yuv_mode, *nplanes, nframes, frames, false, geo);
+  if (int rc = ragged_format(who, format, yuv_mode, a, cls, layout)) return rc;
+  return ragged_frames(who, format, yuv_mode, nframes, frames, false, geo);
 }
 
 }  // namespace
@@ -1967,11 +1853,12 @@ int ragged_analysis_args(const std::string& who, sjpeg_hip_engine* e, int format
 int sjpeg_hip_scan_histogram_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                                         const sjpeg_hip_ragged_frame* frames, uint32_t* d_hist, void* stream) {
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_analysis_args("sjpeg_hip_scan_histogram_ragged_src", e, format, yuv_mode, nframes, frames, d_hist, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_analysis_args("sjpeg_hip_scan_histogram_ragged_src", e, format, yuv_mode, nframes, frames, d_hist, &a, &cls, &layout, &geo)) return rc;
   try {
-    return ragged_analysis(e, kPassHisto, yuv_mode, cls, a, nplanes, nframes, frames, geo, nullptr, 0, d_hist, static_cast<hipStream_t>(stream));
+    return ragged_analysis(e, kPassHisto, yuv_mode, cls, a, layout, nframes, frames, geo, nullptr, 0, d_hist, static_cast<hipStream_t>(stream));
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
@@ -1982,9 +1869,10 @@ int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* e, int format, int 
                                            int tables_per_frame, uint32_t* d_freq, void* stream) {
   static const std::string who = "sjpeg_hip_scan_symbol_stats_ragged_src";
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &layout, &geo)) return rc;
   if (tables == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": tables == NULL");
   constexpr uint32_t kNotRagged = SJPEG_HIP_QUANT_TRELLIS | SJPEG_HIP_QUANT_KEEP | SJPEG_HIP_QUANT_REPLAY | SJPEG_HIP_RESTART_MARKERS;
   for (int t = 0; t < (tables_per_frame ? nframes : 1); ++t) {
@@ -1994,7 +1882,7 @@ int sjpeg_hip_scan_symbol_stats_ragged_src(sjpeg_hip_engine* e, int format, int 
     }
   }
   try {
-    return ragged_analysis(e, kPassStats, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, d_freq, static_cast<hipStream_t>(stream));
+    return ragged_analysis(e, kPassStats, yuv_mode, cls, a, layout, nframes, frames, geo, tables, tables_per_frame, d_freq, static_cast<hipStream_t>(stream));
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
@@ -2023,7 +1911,7 @@ size_t count_capacity(int W, int H, int yuv_mode, bool bound) {
 }
 
 // the counted bits of checked frames, no host wait: ~0 for a frame that did not fit the plan
-int counted_bits_launch(sjpeg_hip_engine* e, int yuv_mode, int cls, const ScanArgs& a, int nplanes, int nframes,
+int counted_bits_launch(sjpeg_hip_engine* e, int yuv_mode, int cls, const ScanArgs& a, const SourceLayout* layout, int nframes,
                         const sjpeg_hip_ragged_frame* frames, const std::vector<FrameGeo>& geo,
                         const sjpeg_hip_scan_tables* tables, int tables_per_frame, bool bound, uint64_t* d_bits,
                         hipStream_t st) {
@@ -2032,14 +1920,14 @@ int counted_bits_launch(sjpeg_hip_engine* e, int yuv_mode, int cls, const ScanAr
     fr.out_offset = 0;
     fr.out_capacity = count_capacity(fr.width, fr.height, yuv_mode, bound);
   }
-  return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, planned.data(), geo, tables, tables_per_frame, nullptr, nullptr,
+  return ragged_encode(e, yuv_mode, cls, a, layout, nframes, planned.data(), geo, tables, tables_per_frame, nullptr, nullptr,
                        0, 0, nullptr, nullptr, st, reinterpret_cast<unsigned long long*>(d_bits));
 }
 
 int counted_bits_args(const std::string& who, sjpeg_hip_engine* e, int format, int yuv_mode, int nframes,
                       const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, int tables_per_frame,
-                      const uint64_t* d_bits, ScanArgs* a, int* cls, int* nplanes, std::vector<FrameGeo>* geo) {
-  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_bits, a, cls, nplanes, geo)) return rc;
+                      const uint64_t* d_bits, ScanArgs* a, int* cls, const SourceLayout** layout, std::vector<FrameGeo>* geo) {
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_bits, a, cls, layout, geo)) return rc;
   return ragged_tables_ok(who, tables, tables_per_frame ? nframes : 1);
 }
 
@@ -2050,12 +1938,13 @@ int sjpeg_hip_scan_quant_error_ragged_src(sjpeg_hip_engine* e, int format, int y
                                           int tables_per_frame, uint64_t* d_err, void* stream) {
   static const std::string who = "sjpeg_hip_scan_quant_error_ragged_src";
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_err, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_err, &a, &cls, &layout, &geo)) return rc;
   if (int rc = ragged_tables_ok(who, tables, tables_per_frame ? nframes : 1)) return rc;
   try {
-    return ragged_analysis(e, kPassError, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame,
+    return ragged_analysis(e, kPassError, yuv_mode, cls, a, layout, nframes, frames, geo, tables, tables_per_frame,
                            reinterpret_cast<uint32_t*>(d_err), static_cast<hipStream_t>(stream));
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
@@ -2067,14 +1956,15 @@ int sjpeg_hip_scan_counted_bits_ragged_src(sjpeg_hip_engine* e, int format, int 
                                            int tables_per_frame, uint64_t* d_bits, void* stream) {
   static const std::string who = "sjpeg_hip_scan_counted_bits_ragged_src";
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &nplanes, &geo)) {
+  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &layout, &geo)) {
     return rc;
   }
   try {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = counted_bits_launch(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st)) return rc;
+    if (int rc = counted_bits_launch(e, yuv_mode, cls, a, layout, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st)) return rc;
     // the frames whose segments overflowed the first plan: counted again, with their worst case, in one more launch
     std::vector<uint64_t> got(nframes);
     HIP_TRY(hipMemcpyAsync(got.data(), d_bits, nframes * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -2114,12 +2004,13 @@ int counted_bits_recount(sjpeg_hip_engine* e, int format, int yuv_mode, const sj
   }
   if (!tables_per_frame) subt[0] = tables[0];
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, n, sub.data(), d_bits, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, n, sub.data(), d_bits, &a, &cls, &layout, &geo)) return rc;
   if (int rc = e->auto_buf.ensure((static_cast<size_t>(n) * 8 + 15) / 16)) return rc;
   uint64_t* const tmp = reinterpret_cast<uint64_t*>(e->auto_buf.p);
-  if (int rc = counted_bits_launch(e, yuv_mode, cls, a, nplanes, n, sub.data(), geo, subt.data(), tables_per_frame, true, tmp, st)) return rc;
+  if (int rc = counted_bits_launch(e, yuv_mode, cls, a, layout, n, sub.data(), geo, subt.data(), tables_per_frame, true, tmp, st)) return rc;
   for (int k = 0; k < n; ++k) {
     HIP_TRY(hipMemcpyAsync(d_bits + which[k], tmp + k, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   }
@@ -2130,22 +2021,24 @@ int counted_bits_first(sjpeg_hip_engine* e, int format, int yuv_mode, int nframe
                        const sjpeg_hip_scan_tables* tables, int tables_per_frame, uint64_t* d_bits, hipStream_t st) {
   static const std::string who = "sjpeg_hip_scan_counted_bits_ragged_src";
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &nplanes, &geo)) {
+  if (int rc = counted_bits_args(who, e, format, yuv_mode, nframes, frames, tables, tables_per_frame, d_bits, &a, &cls, &layout, &geo)) {
     return rc;
   }
-  return counted_bits_launch(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st);
+  return counted_bits_launch(e, yuv_mode, cls, a, layout, nframes, frames, geo, tables, tables_per_frame, false, d_bits, st);
 }
 
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
 
 int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames) {
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
-  return ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo);
+  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &layout)) return rc;
+  return ragged_frames(who, format, yuv_mode, nframes, frames, true, &geo);
 }
 size_t engine_scratch_limit(const sjpeg_hip_engine* e) { return e->scratch_limit; }
 int engine_device(const sjpeg_hip_engine* e) { return e->device; }
@@ -2174,13 +2067,14 @@ int trellis_stats_ragged(sjpeg_hip_engine* e, const std::string& who, int format
                          const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_scan_tables* tables, const uint32_t* kept_base,
                          uint32_t* d_freq, hipStream_t st) {
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &nplanes, &geo)) return rc;
+  if (int rc = ragged_analysis_args(who, e, format, yuv_mode, nframes, frames, d_freq, &a, &cls, &layout, &geo)) return rc;
   for (int f = 0; f < nframes; ++f) {                // (the kept blocks of every frame lie inside the engine's buffer)
     if ((static_cast<size_t>(kept_base[f]) + geo[f].nseg) * kKeptSegWords > e->replay.cap) return fail(SJPEG_HIP_EINVAL, who + ": internal: kept base past the kept blocks");
   }
-  return ragged_analysis(e, kPassStatsTrellis, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, 1, d_freq, st, e->replay.p, kept_base);
+  return ragged_analysis(e, kPassStatsTrellis, yuv_mode, cls, a, layout, nframes, frames, geo, tables, 1, d_freq, st, e->replay.p, kept_base);
 }
 
 int replay_encode_ragged(sjpeg_hip_engine* e, const std::string& who, int format, int yuv_mode, int nframes,
@@ -2188,14 +2082,15 @@ int replay_encode_ragged(sjpeg_hip_engine* e, const std::string& who, int format
                          const void* headers, const size_t* header_offsets, void* d_out, uint64_t* d_sizes, hipStream_t st,
                          const PackedSink* sink) {
   ScanArgs a;
-  int cls = 0, nplanes = 0;
+  int cls = 0;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
-  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
-  if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
+  if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &layout)) return rc;
+  if (int rc = ragged_frames(who, format, yuv_mode, nframes, frames, true, &geo)) return rc;
   for (int f = 0; f < nframes; ++f) {
     if ((static_cast<size_t>(kept_base[f]) + geo[f].nseg) * kKeptSegWords > e->replay.cap) return fail(SJPEG_HIP_EINVAL, who + ": internal: kept base past the kept blocks");
   }
-  return ragged_encode(e, yuv_mode, cls, a, nplanes, nframes, frames, geo, tables, 1, headers, header_offsets, header_offsets[nframes],
+  return ragged_encode(e, yuv_mode, cls, a, layout, nframes, frames, geo, tables, 1, headers, header_offsets, header_offsets[nframes],
                        /*append_eoi=*/1, d_out, d_sizes, st, nullptr, e->replay.p, sink, kept_base);
 }
 
@@ -2872,7 +2767,8 @@ struct RaggedGroup {
   std::vector<sjpeg_hip_ragged_frame> frames;     // in group order
   std::vector<int> index;                         // the caller's number of each frame
   ScanArgs a;                                     // the format's fields (ragged_format)
-  int cls = kSrcPlanes, nplanes = 1;
+  int cls = kSrcPlanes;
+  const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
 };
 
@@ -2985,7 +2881,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       if (int rc = ready(gi)) return rc;
       for (const auto& c : chunks[gi]) {
         uint32_t* const d_hist = static_cast<uint32_t*>(sc.d_hist);
-        if (int rc = ragged_analysis(e, kPassHisto, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second), g.frames.data() + c.first,
+        if (int rc = ragged_analysis(e, kPassHisto, g.yuv_mode, g.cls, g.a, g.layout, static_cast<int>(c.second), g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      nullptr, 0, d_hist, st)) return rc;
         AdaptArgs s;
@@ -3037,7 +2933,7 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       if (int rc = ready(gi)) return rc;
       for (const auto& c : chunks[gi]) {
         uint32_t* const d_freq = static_cast<uint32_t*>(sc.d_freq);
-        if (int rc = ragged_analysis(e, trellis ? kPassStatsTrellis : kPassStats, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(c.second),
+        if (int rc = ragged_analysis(e, trellis ? kPassStatsTrellis : kPassStats, g.yuv_mode, g.cls, g.a, g.layout, static_cast<int>(c.second),
                                      g.frames.data() + c.first,
                                      std::vector<FrameGeo>(g.geo.begin() + c.first, g.geo.begin() + c.first + c.second),
                                      &tables[gbase[gi] + c.first], 1, d_freq, st,
@@ -3088,13 +2984,13 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
       std::vector<int> gidx(ng);
       for (size_t k = 0; k < ng; ++k) gidx[k] = sink->index != nullptr ? sink->index[g.index[k]] : g.index[k];
       gs.index = gidx.data();
-      if (int rc = ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
+      if (int rc = ragged_encode(e, g.yuv_mode, g.cls, g.a, g.layout, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
                                  (trellis || !one_table) ? 1 : 0, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, nullptr,
                                  reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
                                  trellis ? e->replay.p : nullptr, &gs, trellis ? fkept[gi].data() : nullptr)) return rc;
       continue;
     }
-    const int rc = trellis ? ragged_encode(e, g.yuv_mode, g.cls, g.a, g.nplanes, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
+    const int rc = trellis ? ragged_encode(e, g.yuv_mode, g.cls, g.a, g.layout, static_cast<int>(ng), g.frames.data(), g.geo, &tables[gbase[gi]],
                                            1, headers.data(), offs.data(), offs[ng], /*append_eoi=*/1, d_out,
                                            reinterpret_cast<uint64_t*>(d_gsizes + gbase[gi]), st, nullptr,
                                            e->replay.p, nullptr, fkept[gi].data())
@@ -3134,8 +3030,8 @@ int sjpeg_internal::ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_m
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   std::vector<RaggedGroup> groups(1);
   RaggedGroup& g = groups[0];
-  if (int rc = ragged_format(who, format, yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
-  if (int rc = ragged_frames(who, format, yuv_mode, g.nplanes, nframes, frames, true, &g.geo)) return rc;
+  if (int rc = ragged_format(who, format, yuv_mode, &g.a, &g.cls, &g.layout)) return rc;
+  if (int rc = ragged_frames(who, format, yuv_mode, nframes, frames, true, &g.geo)) return rc;
   try {
     g.format = format; g.yuv_mode = yuv_mode;
     g.frames.assign(frames, frames + nframes);
@@ -3169,15 +3065,15 @@ int engine_upload(void* ctx, void* d_dst, const void* src, size_t bytes, hipStre
   return sync_uploads(e, st);
 }
 
-// every frame of an RGB / BGRA / RGBA / planar RGB ragged call checked (the message names the frame)
+// every frame of a ragged call of an RGB-like format (source_layout.h) checked (the message names the frame)
 int rgb_ragged_frames(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames) {
-  if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format) &&
-      !sjpeg_internal::is_float_packed(format)) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr || !L->rgb_like) {
     return fail(SJPEG_HIP_EINVAL, who + ": SJPEG_YUV_AUTO, SJPEG_YUV_SHARP and the riskiness take RGB, BGRA or RGBA (packed) or planar RGB sources");
   }
   if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   std::vector<FrameGeo> geo;
-  return ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, false, &geo);
+  return ragged_frames(who, format, SJPEG_HIP_YUV444, nframes, frames, false, &geo);
 }
 
 // the ragged riskiness: descriptors into auto_buf (which holds nframes * 3 sums behind them as well), then the launch;
@@ -3191,7 +3087,7 @@ int risk_ragged(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ra
     memset(&d, 0, sizeof(d));
     d.rgb = static_cast<const uint8_t*>(frames[f].plane[0]);
     d.row_stride = frames[f].row_stride[0];
-    sjpeg_internal::rgb_frame_offsets(format, frames[f].plane, &d.g_off, &d.b_off);
+    layout_rgb_offsets(*source_layout(format), frames[f].plane, &d.g_off, &d.b_off);
     sjpeg_internal::risk_frame_plan(frames[f].width, frames[f].height, &d);
     d.wg_base = static_cast<unsigned>(total);
     total += static_cast<unsigned long long>(d.bands) * static_cast<unsigned long long>(d.cols);
@@ -3276,8 +3172,8 @@ int sjpeg_hip_sharp_yuv_ragged(sjpeg_hip_engine* e, int format, int nframes, con
   try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::string err;
-    if (format != SJPEG_HIP_SRC_RGB && format != SJPEG_HIP_SRC_BGRA && format != SJPEG_HIP_SRC_RGBA && !sjpeg_internal::is_rgb_planar(format) &&
-      !sjpeg_internal::is_float_packed(format)) {
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr || !L->rgb_like) {
       return fail(SJPEG_HIP_EINVAL, who + ": the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources");
     }
     if (int rc = ragged_ordered(e, st)) return rc;
@@ -3392,8 +3288,8 @@ static int ragged_modes_flow(sjpeg_hip_engine* e, const std::string& who, int fo
         g.index.push_back(static_cast<int>(f));
       }
       if (g.frames.empty()) continue;
-      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
-      if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
+      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.layout)) return rc;
+      if (int rc = ragged_frames(who, g.format, g.yuv_mode, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
       groups.push_back(std::move(g));
     }
     if (int rc = ragged_batch_groups(e, who, groups, quant_in, quant_per_frame, min_quant, q_bias, method, qdelta_max_luma,
@@ -3430,7 +3326,7 @@ static int ragged_auto_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int n
     if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
     {
       std::vector<FrameGeo> geo;                   // (the output ranges)
-      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
+      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, nframes, frames, true, &geo)) return rc;
     }
     return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
                              qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, sink);
@@ -3468,14 +3364,15 @@ static int ragged_trellis_flow(sjpeg_hip_engine* e, int format, int yuv_mode, in
     if (yuv_mode == kYuvAuto || yuv_mode == kYuvSharp) {
       if (int rc = rgb_ragged_frames(who, format, nframes, frames)) return rc;
       std::vector<FrameGeo> geo;                   // (the output ranges)
-      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, 1, nframes, frames, true, &geo)) return rc;
+      if (int rc = ragged_frames(who, format, SJPEG_HIP_YUV444, nframes, frames, true, &geo)) return rc;
     } else {
       if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
       ScanArgs a;
-      int cls = 0, nplanes = 0;
+      int cls = 0;
+      const SourceLayout* layout = nullptr;
       std::vector<FrameGeo> geo;
-      if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &nplanes)) return rc;
-      if (int rc = ragged_frames(who, format, yuv_mode, nplanes, nframes, frames, true, &geo)) return rc;
+      if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &layout)) return rc;
+      if (int rc = ragged_frames(who, format, yuv_mode, nframes, frames, true, &geo)) return rc;
     }
     return ragged_modes_flow(e, who, format, yuv_mode, nframes, frames, quant_in, quant_per_frame, min_quant, q_bias, method,
                              qdelta_max_luma, qdelta_max_chroma, d_out, d_sizes, modes, stream, sink);
@@ -3565,8 +3462,8 @@ int sjpeg_internal::ragged_groups_flow(sjpeg_hip_engine* e, const std::string& w
       if (m.frames.empty()) continue;
       RaggedGroup g;
       g.format = m.format; g.yuv_mode = m.yuv_mode; g.frames = m.frames; g.index = m.index;
-      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.nplanes)) return rc;
-      if (int rc = ragged_frames(who, g.format, g.yuv_mode, g.nplanes, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
+      if (int rc = ragged_format(who, g.format, g.yuv_mode, &g.a, &g.cls, &g.layout)) return rc;
+      if (int rc = ragged_frames(who, g.format, g.yuv_mode, static_cast<int>(g.frames.size()), g.frames.data(), true, &g.geo)) return rc;
       groups.push_back(std::move(g));
     }
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -695,7 +695,7 @@ __global__ __launch_bounds__(64) void sharp_small(const SharpArgs a) {
 struct SharpFrame {
   const uint8_t* rgb;
   long long row_stride;
-  long long g_off, b_off;                       // where G and B lie from R (rgb_frame_offsets)
+  long long g_off, b_off;                       // where G and B lie from R (layout_rgb_offsets)
   uint8_t* y; uint8_t* u; uint8_t* v;           // tightly packed planes
   uint8_t* block;                               // the frame's workspace block (sharp_small frames: none)
   uint32_t* ctrl;                               // its 32 + 4 * nstrips control words
@@ -851,23 +851,16 @@ int sjpeg_hip_sharp_yuv(const sjpeg_hip_source* src, int width, int height, int 
   if (workspace_size < sjpeg_hip_sharp_workspace(width, height, nframes) || nframes > 65535) return SJPEG_HIP_EINVAL;
   SharpArgs a;
   memset(&a, 0, sizeof(a));
-  if (sjpeg_internal::is_float_planar(src->format)) {   // (no engine, no pixel transform)
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_sharp_yuv: SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16 need an engine's "
-                                                       "pixel transform: use sjpeg_hip_sharp_yuv_ragged");
+  const sjpeg_internal::SourceLayout* const L = sjpeg_internal::source_layout(src->format);
+  if (L != nullptr && L->kind != sjpeg_internal::kElemU8) {   // (no engine, no pixel transform)
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, std::string("sjpeg_hip_sharp_yuv: ") +
+                                                           (L->one_pitch ? "SJPEG_HIP_SRC_RGB_PLANAR_F32 / _F16 / _BF16" : "SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F*") +
+                                                           " need an engine's pixel transform: use sjpeg_hip_sharp_yuv_ragged");
   }
-  if (sjpeg_internal::is_float_format(src->format)) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_sharp_yuv: SJPEG_HIP_SRC_RGB_F* / _RGBA_F* / _GRAY_F* need an engine's "
-                                                       "pixel transform: use sjpeg_hip_sharp_yuv_ragged");
-  }
-  if (!sjpeg_internal::rgb_layout(src->format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
-    return SJPEG_HIP_EINVAL;                         // the sharp conversion starts from RGB
-  }
-  const int64_t st_abs = src->row_stride[0] < 0 ? -src->row_stride[0] : src->row_stride[0];
-  if (st_abs < static_cast<int64_t>(a.pix_step) * width) return SJPEG_HIP_EINVAL;
-  if (src->format == SJPEG_HIP_SRC_RGB_PLANAR) {
-    if (sjpeg_internal::rgb_planar_fault(src->plane, src->row_stride, src->frame_stride) != nullptr) return SJPEG_HIP_EINVAL;
-    sjpeg_internal::rgb_frame_offsets(src->format, src->plane, &a.g_off, &a.b_off);
-  }
+  if (L == nullptr || !L->rgb_like) return SJPEG_HIP_EINVAL;   // the sharp conversion starts from RGB
+  if (sjpeg_internal::layout_fault(*L, width, src->plane, src->row_stride, src->frame_stride, sjpeg_internal::kUniformChecks).rule != 0) return SJPEG_HIP_EINVAL;
+  a.pix_step = L->pix_step; a.r_off = L->r_off;
+  sjpeg_internal::layout_rgb_offsets(*L, src->plane, &a.g_off, &a.b_off);
   hipStream_t st = static_cast<hipStream_t>(stream);
   a.rgb = static_cast<const uint8_t*>(src->plane[0]);
   a.row_stride = src->row_stride[0]; a.frame_stride = src->frame_stride[0];
@@ -991,12 +984,14 @@ int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nf
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err) {
   SharpArgs a;
   memset(&a, 0, sizeof(a));
-  a.ekind = elem_kind(format);
   for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
-  if (!rgb_layout(format, &a.pix_step, &a.r_off, &a.g_off, &a.b_off)) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr || !L->rgb_like) {
     *err = "the sharp conversion takes RGB, BGRA or RGBA (packed) or planar RGB sources";
     return SJPEG_HIP_EINVAL;
   }
+  a.ekind = L->kind;
+  a.pix_step = L->pix_step; a.r_off = L->r_off; a.g_off = L->g_off; a.b_off = L->b_off;   // (g_off, b_off: the frames' own are read)
   if (nframes < 1 || nframes > 65535) { *err = "nframes must be 1..65535"; return SJPEG_HIP_EINVAL; }
   if (frames == nullptr || d_y == nullptr || d_u == nullptr || d_v == nullptr || d_workspace == nullptr) {
     *err = "frames, d_y, d_u, d_v or d_workspace == NULL";
@@ -1009,18 +1004,9 @@ int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nf
       *err = w + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height);
       return SJPEG_HIP_EINVAL;
     }
-    if (fr.plane[0] == nullptr || d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
-    const int64_t st_abs = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
-    const int64_t row_need = is_float_packed(format) ? elem_row_bytes(format, fr.width) : static_cast<int64_t>(a.pix_step) * fr.width;
-    if (st_abs < row_need) { *err = w + "|row_stride| smaller than a row of the plane"; return SJPEG_HIP_EINVAL; }
-    if (is_rgb_planar(format)) {
-      if (const char* fault = rgb_planar_fault(fr.plane, fr.row_stride, nullptr)) { *err = w + fault; return SJPEG_HIP_EINVAL; }
-      const std::string efault = rgb_float_fault(format, fr.plane, fr.row_stride, nullptr);
-      if (!efault.empty()) { *err = w + efault; return SJPEG_HIP_EINVAL; }
-    } else if (is_float_packed(format)) {
-      const std::string efault = rgb_float_fault(format, fr.plane, fr.row_stride, nullptr, 1);
-      if (!efault.empty()) { *err = w + efault; return SJPEG_HIP_EINVAL; }
-    }
+    if (d_y[f] == nullptr || d_u[f] == nullptr || d_v[f] == nullptr) { *err = w + "null plane pointer"; return SJPEG_HIP_EINVAL; }
+    const LayoutFault fault = layout_fault(*L, fr.width, fr.plane, fr.row_stride, nullptr, kSharpChecks);
+    if (fault.rule != kFaultNone) { *err = w + layout_fault_text(*L, fault); return SJPEG_HIP_EINVAL; }
   }
   if (workspace_size < sharp_ragged_workspace(nframes, frames)) { *err = "workspace_size below sjpeg_hip_sharp_ragged_workspace()"; return SJPEG_HIP_EINVAL; }
 #ifdef SJPEG_HIP_PRIO_STRESS
@@ -1051,7 +1037,7 @@ int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nf
     SharpFrame& d = desc[k];
     memset(&d, 0, sizeof(d));
     d.rgb = static_cast<const uint8_t*>(fr.plane[0]); d.row_stride = fr.row_stride[0];
-    rgb_frame_offsets(format, fr.plane, &d.g_off, &d.b_off);
+    layout_rgb_offsets(*L, fr.plane, &d.g_off, &d.b_off);
     d.y = d_y[f]; d.u = d_u[f]; d.v = d_v[f];
     d.W = fr.width; d.H = fr.height;
     if (k >= nbig) continue;

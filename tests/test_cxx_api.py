@@ -172,3 +172,13 @@ def test_cxx_batch_entry_against_the_host_api(tmp_path):
         env.update(extra)
         r = subprocess.run([exe, "8"], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0 and "mismatches: 0" in r.stdout, (extra, r.stdout[-500:], r.stderr[-1500:])
+
+
+def test_source_layout_plane_arithmetic(tmp_path):
+    """CPU: tests/cxx/source_layout_test.cc -- what sjpeg_amd/csrc/source_layout.h makes of every format's planes and
+    strides (either sign, with and without frame strides), its G and B offsets and row sizes, against literals."""
+    exe = os.path.join(str(tmp_path), "source_layout_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", sj.CSRC,
+                           os.path.join(ROOT, "tests", "cxx", "source_layout_test.cc"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "21 formats ok" in r.stdout, r.stdout + r.stderr
