@@ -699,7 +699,8 @@ int sjpeg_hip_encode_ragged_packed_src(sjpeg_hip_engine* engine, int format, int
  *   SJPEG_HIP_EINVAL (the message names the argument or the frame): a
  *   NULL engine, params, frames, d_out, d_sizes or params->quant; nframes outside 1..65535; yuv_mode outside 0..4; method
  *   outside 0..8; qdelta_max outside -12..12; a target_mode other than 1 or 2 or a non-finite target_value in any search
- *   entry; and every frame check of sjpeg_hip_encode_ragged_src.  No per-picture metadata, no restart markers.
+ *   entry; and every frame check of sjpeg_hip_encode_ragged_src.  No restart markers.  Per-picture metadata:
+ *   sjpeg_hip_encode_ragged_full_meta_src, below.
  * sjpeg_hip_encode_ragged_full_packed_src: the same call into ONE packed buffer -- the arguments and the layout contract
  *   of sjpeg_hip_encode_ragged_packed_src.  A searched SJPEG_YUV_AUTO call lays its frames out as that contract says:
  *   the frames that are not searched first, then (per part) the searched ones grouped by the mode each was given.
@@ -721,6 +722,45 @@ int sjpeg_hip_encode_ragged_full_packed_src(sjpeg_hip_engine* engine, int format
                                             int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                             void* stream);
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* engine, uint64_t stats[6]);
+
+/* ---- ragged batches whose pictures carry metadata: EXIF, ICC profile, XMP, raw APP markers ----
+ * sjpeg_hip_metadata_size (host only): *size = the bytes sjpeg_hip_make_header_meta() puts between SOI + APP0 (20 bytes)
+ *   and the DQT segment for this metadata; 0 for NULL or all-empty metadata.  SJPEG_HIP_EINVAL, sjpeg_hip_last_error()
+ *   naming the member, for what the reference refuses (src/headers.cc:72-180) -- EXIF whose APP1 segment would pass
+ *   0xFFFF bytes, an ICC profile of 256 chunks or more, an XMP packet too long for one APP1 segment (above 65 504
+ *   bytes) without a well-formed xmpNote:HasExtendedXMP=" note in front of the split point, or above 2^31 bytes -- and
+ *   for a NULL pointer with a non-zero size.
+ * sjpeg_hip_encode_ragged_full_meta_src / _full_meta_packed_src: sjpeg_hip_encode_ragged_full_src / _full_packed_src with
+ *   `meta`, a HOST array (sjpeg_hip_metadata, with sjpeg_hip_make_header_meta below): frame f carries meta[f]
+ *   (meta_per_frame = 1) or meta[0] (0).  meta == NULL is exactly the call without metadata.
+ *   Frame f's bytes are what the reference's sjpeg::Encode() makes of that picture alone with the EncoderParam the _full_
+ *   call describes plus app_markers, exif, iccp, xmp and xmp_split_point of its metadata.  Without a size target those
+ *   are the bytes of the same call without metadata with the metadata segments inserted behind byte 20.  A size search
+ *   counts the metadata into the size it aims at, as Encoder::HeaderSize() does (src/dichotomy.cc:210-241), and may so
+ *   choose another quality; a PSNR search is not affected.  modes, q_out, value_out, d_sizes, the frame order of a packed
+ *   buffer, the host waits and sjpeg_hip_engine_search_stats keep their meaning.
+ *   Invalid metadata in any frame is SJPEG_HIP_EINVAL before any device work; the message names the entry, the frame and
+ *   the member.  sjpeg_hip_frame_bound(w, h, SJPEG_HIP_YUV444, 2048 + sjpeg_hip_metadata_size()) is always enough for a
+ *   frame; one that does not fit its out_capacity reports size 0, nothing is written outside any frame's range and the
+ *   others stay exact.  The headers of one launch are staged in engine scratch (sjpeg_hip_engine_scratch_bytes,
+ *   sjpeg_hip_engine_trim): they count against SJPEG_HIP_SCRATCH_LIMIT_BYTES and stay below 4 GiB, a larger batch goes
+ *   in more launches.  A header above 2048 bytes is placed with 16-byte stores. */
+struct sjpeg_hip_metadata;
+int sjpeg_hip_metadata_size(const struct sjpeg_hip_metadata* meta, size_t* size);
+int sjpeg_hip_encode_ragged_full_meta_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                          const sjpeg_hip_ragged_params* params,
+                                          const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                          void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                          int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                 const sjpeg_hip_ragged_params* params,
+                                                 const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                 void* d_packed, size_t packed_capacity,
+                                                 uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                 int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                 void* stream);
 
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that

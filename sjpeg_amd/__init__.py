@@ -408,6 +408,14 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_encode_ragged_full_packed_src.restype = C.c_int
     L.sjpeg_hip_engine_search_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.sjpeg_hip_engine_search_stats.restype = C.c_int
+    L.sjpeg_hip_metadata_size.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.sjpeg_hip_metadata_size.restype = C.c_int
+    full = list(L.sjpeg_hip_encode_ragged_full_src.argtypes)
+    L.sjpeg_hip_encode_ragged_full_meta_src.argtypes = full[:5] + [C.c_void_p, C.c_int] + full[5:]
+    L.sjpeg_hip_encode_ragged_full_meta_src.restype = C.c_int
+    full = list(L.sjpeg_hip_encode_ragged_full_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes = full[:5] + [C.c_void_p, C.c_int] + full[5:]
+    L.sjpeg_hip_encode_ragged_full_meta_packed_src.restype = C.c_int
     _lib = L
     return L
 
@@ -447,6 +455,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_scan_quant_error_ragged_src", "sjpeg_hip_scan_counted_bits_ragged_src", "sjpeg_hip_encode_ragged_search_src",
     "sjpeg_hip_encode_ragged_trellis_src", "sjpeg_hip_encode_ragged_packed_src",
     "sjpeg_hip_encode_ragged_full_src", "sjpeg_hip_encode_ragged_full_packed_src", "sjpeg_hip_engine_search_stats",
+    "sjpeg_hip_metadata_size", "sjpeg_hip_encode_ragged_full_meta_src", "sjpeg_hip_encode_ragged_full_meta_packed_src",
 ]
 
 
@@ -769,6 +778,60 @@ def make_header_meta(w, h, yuv_mode, quant, specs=None, app_markers=b"", exif=b"
                                              C.c_void_p, C.c_size_t]
     n = L.sjpeg_hip_make_header_meta(w, h, yuv_mode, q.ctypes.data, specs, C.byref(m), buf.ctypes.data, cap)
     return buf[:n].tobytes() if n else None
+
+
+class PictureMetadata:
+    """The metadata one picture carries into its JPEG, as the reference's EncoderParam holds it: raw application
+    markers (verbatim), EXIF, an ICC profile, XMP, and where a long XMP packet is split (0: the default)."""
+
+    def __init__(self, app_markers=b"", exif=b"", iccp=b"", xmp=b"", xmp_split_point=0):
+        self.app_markers, self.exif, self.iccp, self.xmp = bytes(app_markers), bytes(exif), bytes(iccp), bytes(xmp)
+        self.xmp_split_point = int(xmp_split_point)
+        self._size = None
+
+    def _struct(self):
+        return Metadata(self.app_markers or None, len(self.app_markers), self.exif or None, len(self.exif),
+                        self.iccp or None, len(self.iccp), self.xmp or None, len(self.xmp), self.xmp_split_point)
+
+    def size(self) -> int:
+        """sjpeg_hip_metadata_size: the bytes these segments take behind SOI + APP0; SjpegError for metadata the
+        reference refuses.  Worked out once: the object's bytes do not change."""
+        if self._size is None:
+            n = C.c_size_t(0)
+            m = self._struct()
+            if lib().sjpeg_hip_metadata_size(C.byref(m), C.byref(n)) != 0:
+                raise SjpegError(lib().sjpeg_hip_last_error().decode())
+            self._size = int(n.value)
+        return self._size
+
+
+def _metadata_args(who, n, metadata):
+    """What a ragged call hands to the library for `metadata` -- None, one PictureMetadata for all n pictures or a
+    sequence of one per picture (None entries: no metadata): (the sjpeg_hip_metadata array or None, whether there is one
+    per frame, every frame's metadata size, every frame's PictureMetadata or None).  The array points into the objects'
+    bytes: they stay alive in the fourth result."""
+    if metadata is None:
+        return None, 0, [0] * n, [None] * n
+    if isinstance(metadata, (str, bytes)):
+        raise SjpegError(f"{who}: metadata is a PictureMetadata or a sequence of them (layout is passed by keyword)")
+    per_frame = not isinstance(metadata, PictureMetadata)
+    items = list(metadata) if per_frame else [metadata]
+    if per_frame and len(items) != n:
+        raise SjpegError(f"{who}: one metadata entry per image")
+    items = [PictureMetadata() if m is None else m for m in items]
+    for k, m in enumerate(items):
+        if not isinstance(m, PictureMetadata):
+            raise SjpegError(f"{who}: metadata entry {k} is not a PictureMetadata")
+    sizes = []
+    for k, m in enumerate(items):
+        try:
+            sizes.append(m.size())
+        except SjpegError as e:
+            raise SjpegError(f"{who}: metadata entry {k}: {e}") from None
+    arr = (Metadata * len(items))(*[m._struct() for m in items])
+    if not per_frame:
+        sizes, items = sizes * n, items * n
+    return arr, int(per_frame), sizes, items
 
 
 def frame_bound(w, h, yuv_mode, header_size) -> int:
@@ -1347,14 +1410,18 @@ class Engine:
 
     def _encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                               dmax_chroma, search, capacities, packed_capacity, out,
-                              symbol="sjpeg_hip_encode_ragged_packed_src"):
+                              symbol="sjpeg_hip_encode_ragged_packed_src", metadata=None):
         """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home).
-        symbol: that entry point, or its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments)."""
+        symbol: that entry point, or its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments); with
+        metadata (as encode_ragged_full takes it) the twin's sjpeg_hip_encode_ragged_full_meta_packed_src."""
         import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_packed: one entry of planes_per_frame and dims per frame, at least one frame")
         bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_packed", n, metadata)
+        if marr is not None and capacities is None:
+            capacities = [frame_bound(w, h, bound_mode, 2048 + msizes[k]) for k, (w, h) in enumerate(dims)]
         q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_packed", n, quant, min_quant,
                                                                             search, bound_mode, capacities, dims)
         if len(capacities) != n:
@@ -1373,22 +1440,35 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, C.byref(params), out.data_ptr(), packed_capacity,
-                                         meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-                  symbol)
+        if marr is not None:
+            symbol = "sjpeg_hip_encode_ragged_full_meta_packed_src"
+            rc = lib().sjpeg_hip_encode_ragged_full_meta_packed_src(
+                self._h, fmt, n, frames, C.byref(params), C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(),
+                packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream())
+        else:
+            rc = getattr(lib(), symbol)(self._h, fmt, n, frames, C.byref(params), out.data_ptr(), packed_capacity,
+                                        meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream())
+        self._chk(rc, symbol)
         return out, meta, list(modes), list(q_out), list(v_out)
 
     def encode_ragged_full(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
-                           dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None, offsets=None, sizes=None):
+                           dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None, offsets=None, sizes=None,
+                           metadata=None):
         """sjpeg_hip_encode_ragged_full_src: every combination of SjpegYUVMode 0..4, method 0..8 and a search (None, one
         SearchParams / dict, or a list of one per frame) in one ragged call.  Frame k's bytes are what the reference's
         sjpeg::Encode() makes of that picture alone.  What encode_ragged_batch / _auto / _trellis / _search take goes to
         their flows; a search with YUV_AUTO / YUV_SHARP, with method 7 or 8, or both, is this call's own.  Returns
-        (out, sizes, offsets, modes, q, value): q / value -1 for a frame that was not searched (passes <= 1)."""
+        (out, sizes, offsets, modes, q, value): q / value -1 for a frame that was not searched (passes <= 1).
+        metadata: None, one PictureMetadata for every picture or a sequence of one per picture (None entries: none) --
+        sjpeg_hip_encode_ragged_full_meta_src: each JPEG carries its EXIF, ICC profile, XMP and APP markers as the
+        reference writes them, a size search counts them, and the default capacities make room for them."""
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_full: one entry of planes_per_frame and dims per frame, at least one frame")
         bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_full", n, metadata)
+        if marr is not None and capacities is None:
+            capacities = [frame_bound(w, h, bound_mode, 2048 + msizes[k]) for k, (w, h) in enumerate(dims)]
         q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_full", n, quant, min_quant,
                                                                             search, bound_mode, capacities, dims)
         frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
@@ -1396,19 +1476,26 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_full_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
-                                                         sizes.data_ptr(), modes, q_out, v_out, self._stream()),
-                  "sjpeg_hip_encode_ragged_full_src")
+        if marr is not None:
+            self._chk(lib().sjpeg_hip_encode_ragged_full_meta_src(self._h, fmt, n, frames, C.byref(params),
+                                                                  C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(),
+                                                                  sizes.data_ptr(), modes, q_out, v_out, self._stream()),
+                      "sjpeg_hip_encode_ragged_full_meta_src")
+        else:
+            self._chk(lib().sjpeg_hip_encode_ragged_full_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
+                                                             sizes.data_ptr(), modes, q_out, v_out, self._stream()),
+                      "sjpeg_hip_encode_ragged_full_src")
         return out, sizes, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
 
     def encode_ragged_full_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None,
                                   q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
-                                  packed_capacity=None, out=None):
+                                  packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_full_packed_src: encode_ragged_full into ONE packed buffer, with the arguments and
-        the layout of encode_ragged_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        the layout of encode_ragged_packed.  Returns (out, sizes, offsets, modes, q, value).  metadata: as
+        encode_ragged_full (sjpeg_hip_encode_ragged_full_meta_packed_src)."""
         out, meta, modes, q_out, v_out = self._encode_ragged_packed(
             fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-            capacities, packed_capacity, out, symbol="sjpeg_hip_encode_ragged_full_packed_src")
+            capacities, packed_capacity, out, symbol="sjpeg_hip_encode_ragged_full_packed_src", metadata=metadata)
         n = len(dims)
         return out, meta[:n], meta[n:], modes, q_out, v_out
 
@@ -1601,7 +1688,7 @@ def _gray_mode(who, fmt, yuv_mode):
 
 def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0, min_quant=None, q_bias=0x78,
                   dmax_luma=12, dmax_chroma=1, target_size=None, target_psnr=None, passes=10, tolerance=1.0, qmin=0.0,
-                  qmax=100.0, use_trellis=False, packed=False, layout="hwc"):
+                  qmax=100.0, use_trellis=False, packed=False, metadata=None, layout="hwc"):
     """JPEGs (list of bytes) of device-resident pictures of any sizes in ONE ragged call: images is a sequence of CUDA
     uint8 tensors [H_k, W_k, 3] on one device (packed RGB: stride 1 over the channels, 3 over x; any row stride);
     quality is one float or one per image.  method 0 (the default): frame k's bytes are what encode_device makes of it
@@ -1632,7 +1719,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     keyword is explicit because [3, W, 3] is both.  A [3, H_k, W_k] picture that lies channels-last in memory -- stride
     1 over the channels, 3 or 4 over x: x[k] of a torch.channels_last batch, hwc.permute(2, 0, 1) -- goes in as SRC_RGB /
     SRC_RGBA, again without a copy.  With layout="chw", images may be a FloatPixels: float32, float16 or bfloat16
-    pictures, planar, channels-last or gray, converted to bytes inside the encoder (see FloatPixels)."""
+    pictures, planar, channels-last or gray, converted to bytes inside the encoder (see FloatPixels).
+
+    metadata: None, one PictureMetadata for every picture or a sequence of one per picture (None entries: none): each
+    JPEG carries its EXIF, ICC profile, XMP and APP markers as the reference writes them (EncoderParam's fields), a
+    target_size counts them, and the output buffers make room for them.  (It stands in front of layout, which stays
+    the last parameter: pass layout by keyword.)"""
     import torch
     chw = _check_layout("encode_images", layout)
     images, fp = _float_pixels("encode_images", images, chw)
@@ -1700,6 +1792,15 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             raise SjpegError("encode_images: one target per image")
         mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
         search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+    _, _, _, metas = _metadata_args("encode_images", n, metadata)
+    if metadata is not None and not packed and not (method == 0 and target is None and yuv_mode not in (YUV_AUTO, YUV_SHARP)):
+        # (every flow below but the method 0 call with ready headers: the one call that takes them all, with metadata)
+        with torch.cuda.device(dev):
+            out, sizes, offs, _, _, _ = eng.encode_ragged_full(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
+                                                               min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                                               metadata=metadata)
+            eng.wait()                           # (pipelined mode: the output is complete after this)
+            return _fetch_ragged(out, sizes, offs)
     if packed:
         # (the unpacked method 0 path with a fixed sampling and no target codes with the tables of the quality alone --
         # make_tables: no min_quant, the default bias --, so the packed one does too)
@@ -1707,7 +1808,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
         with torch.cuda.device(dev):
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method,
                                          None if plain0 else min_quant, 0x78 if plain0 else q_bias,
-                                         dmax_luma, dmax_chroma, search, fmt=fmt)
+                                         dmax_luma, dmax_chroma, search, fmt=fmt, metadata=metadata)
     if target is not None:
         with torch.cuda.device(dev):
             out, sizes, offs, _, _ = eng.encode_ragged_search(fmt, planes, dims, yuv_mode, _quality_quant(qs),
@@ -1741,7 +1842,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             made[q] = make_tables(quality=q)
         t, qm = made[q]
         tables.append(t)
-        headers.append(make_header(dims[k][0], dims[k][1], yuv_mode, qm))
+        if metas[k] is None:
+            headers.append(make_header(dims[k][0], dims[k][1], yuv_mode, qm))
+        else:
+            m = metas[k]
+            headers.append(make_header_meta(dims[k][0], dims[k][1], yuv_mode, qm, None, m.app_markers, m.exif, m.iccp, m.xmp,
+                                            m.xmp_split_point))
     per_frame = len(made) > 1
     with torch.cuda.device(dev):
         out, sizes, offs = eng.encode_ragged(fmt, planes, dims, yuv_mode, tables if per_frame else tables[0],
@@ -1776,8 +1882,21 @@ def encode_images_full_chw(images, quality=75.0, yuv_mode=YUV_AUTO, method=4, us
                                tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed)
 
 
+def encode_images_full_meta(images, metadata, layout="hwc", **params):
+    """encode_images_full (layout="hwc") or encode_images_full_chw ("chw") with metadata: None, one PictureMetadata for
+    every picture or a sequence of one per picture (None entries: none), as encode_images takes it.  params: the
+    keywords of encode_images_full.  (Those two functions' parameter lists are pinned as they are; this is their
+    metadata form.)"""
+    import inspect
+    sig = list(inspect.signature(encode_images_full).parameters.values())[1:]      # (its names and defaults, in its order)
+    for k in params:
+        if k not in [p.name for p in sig]:
+            raise TypeError(f"encode_images_full_meta: unexpected keyword {k!r}")
+    return _encode_images_full(layout, images, *[params.get(p.name, p.default) for p in sig], metadata=metadata)
+
+
 def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, target_size, target_psnr, passes,
-                        tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed):
+                        tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed, metadata=None):
     import torch
     chw = _check_layout("encode_images_full", layout)
     images, fp = _float_pixels("encode_images_full", images, chw)
@@ -1832,9 +1951,11 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     with torch.cuda.device(dev):
         if packed:
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method, min_quant, q_bias,
-                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src", fmt=fmt)
+                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src", fmt=fmt,
+                                         metadata=metadata)
         out, sizes, offs, _, _, _ = eng.encode_ragged_full(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
-                                                           min_quant, q_bias, dmax_luma, dmax_chroma, search)
+                                                           min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                                           metadata=metadata)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return _fetch_ragged(out, sizes, offs)
 
@@ -1850,14 +1971,14 @@ def _quality_quant(qs):
     return [made[float(q)] for q in qs] if len(made) > 1 else made[float(qs[0])]
 
 
-def compress_images(images, quality=75.0, engine=None, use_trellis=False, packed=False, layout="hwc"):
+def compress_images(images, quality=75.0, engine=None, use_trellis=False, packed=False, metadata=None, layout="hwc"):
     """The batch SjpegCompress(): JPEGs (list of bytes) of device-resident RGB pictures [H_k, W_k, 3] of any sizes, each
     what SjpegCompress (method 4, SJPEG_YUV_AUTO) makes of it alone, in one ragged call.  use_trellis=True: with
     EncoderParam::use_trellis, i.e. what SjpegEncode(picture, quality, 7, SJPEG_YUV_AUTO) makes of it.  packed=True:
     through the packed call and one device-to-host copy, as encode_images.  layout="chw": the pictures are
-    [3, H_k, W_k] instead, as encode_images takes them."""
+    [3, H_k, W_k] instead, as encode_images takes them.  metadata: what every picture carries, as encode_images."""
     return encode_images(images, quality, YUV_AUTO, engine=engine, method=4, use_trellis=use_trellis, packed=packed,
-                         layout=layout)
+                         metadata=metadata, layout=layout)
 
 
 def riskiness_images(images, engine=None, layout="hwc"):
@@ -1912,14 +2033,15 @@ def _first_pool(dims, yuv_mode):
 
 
 def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                          symbol="sjpeg_hip_encode_ragged_packed_src", fmt=SRC_RGB):
+                          symbol="sjpeg_hip_encode_ragged_packed_src", fmt=SRC_RGB, metadata=None):
     """encode_images through the packed call: a small first pool, one copy of sizes and offsets, one of the pool; the
     pictures a full pool dropped go through a second packed call whose pool is the sum of their bounds."""
     import torch
     n = len(dims)
     _packed_stats["calls"] += 1
     bound_mode = YUV_444 if yuv_mode in (YUV_AUTO, YUV_SHARP) else yuv_mode
-    bounds = [frame_bound(w, h, bound_mode, 2048) for (w, h) in dims]
+    _, _, msizes, metas = _metadata_args("encode_images", n, metadata)
+    bounds = [frame_bound(w, h, bound_mode, 2048 + msizes[k]) for k, (w, h) in enumerate(dims)]
 
     def run(which, pool):
         m = len(which)
@@ -1927,7 +2049,7 @@ def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant,
             fmt, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
             [quant[k] for k in which] if isinstance(quant, list) else quant, method, min_quant, q_bias, dmax_luma,
             dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None,
-            symbol)
+            symbol, None if metadata is None else [metas[k] for k in which])
         eng.wait()                               # (pipelined mode: the output is complete after this)
         meta = meta.cpu().numpy()                # sizes and offsets together
         sz, off, end = meta[:m], meta[m:2 * m], int(meta[2 * m])
@@ -1939,7 +2061,7 @@ def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant,
         host = stage.numpy()
         return [host[int(off[i]):int(off[i] + sz[i])].tobytes() if sz[i] > 0 else None for i in range(m)], over
 
-    got, over = run(list(range(n)), _first_pool(dims, yuv_mode))
+    got, over = run(list(range(n)), _first_pool(dims, yuv_mode) + sum((s + 15) & ~15 for s in msizes))
     again = [k for k in range(n) if got[k] is None]
     if again and not over:
         raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % again[0])

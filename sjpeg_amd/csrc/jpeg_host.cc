@@ -264,45 +264,80 @@ static bool AppendXmp(const std::string& xmp, uint16_t xmp_split, std::vector<ui
   return true;
 }
 
+// the metadata segments, in the reference's order (headers.cc:63-180)
+bool AppendMetadata(const Metadata& meta, std::vector<uint8_t>* o, const char** field) {
+  const char* unused;
+  if (field == nullptr) field = &unused;
+  // raw application markers, verbatim (headers.cc:63-70)
+  if (!meta.app_markers.empty()) PutBytes(o, meta.app_markers.data(), meta.app_markers.size());
+  // EXIF in one APP1 (headers.cc:72-85)
+  if (!meta.exif.empty()) {
+    const size_t seg = meta.exif.size() + 6 + 2;
+    if (seg > 0xffff) { *field = "exif"; return false; }
+    Put16(o, 0xffe1); Put16(o, static_cast<uint32_t>(seg));
+    PutBytes(o, "Exif\0\0", 6);
+    PutBytes(o, meta.exif.data(), meta.exif.size());
+  }
+  // ICC profile in numbered APP2 chunks (headers.cc:87-113)
+  if (!meta.iccp.empty()) {
+    const size_t kMax = 0xffff - 12 - 4;
+    const size_t nchunks = (meta.iccp.size() + kMax - 1) / kMax;
+    if (nchunks >= 256) { *field = "iccp"; return false; }
+    size_t pos = 0;
+    for (size_t seq = 1; pos < meta.iccp.size(); ++seq) {
+      const size_t n = std::min(kMax, meta.iccp.size() - pos);
+      Put16(o, 0xffe2); Put16(o, static_cast<uint32_t>(n + 12 + 4));
+      PutBytes(o, "ICC_PROFILE", 12);
+      o->push_back(static_cast<uint8_t>(seq));
+      o->push_back(static_cast<uint8_t>(nchunks));
+      PutBytes(o, meta.iccp.data() + pos, n);
+      pos += n;
+    }
+  }
+  // XMP: a single APP1 when it fits (headers.cc:162-180), else main + extension chunks
+  if (!meta.xmp.empty() && !AppendXmp(meta.xmp, meta.xmp_split, o)) { *field = "xmp"; return false; }
+  return true;
+}
+
+bool MetadataFromC(const sjpeg_hip_metadata* m, Metadata* meta, std::vector<uint8_t>* block, const char** field) {
+  const char* unused;
+  if (field == nullptr) field = &unused;
+  *meta = Metadata();
+  block->clear();
+  if (m == nullptr) return true;
+  struct Member { const void* p; size_t n; std::string* to; const char* name; };
+  const Member members[4] = {{m->app_markers, m->app_markers_size, &meta->app_markers, "app_markers"},
+                             {m->exif, m->exif_size, &meta->exif, "exif"},
+                             {m->iccp, m->iccp_size, &meta->iccp, "iccp"},
+                             {m->xmp, m->xmp_size, &meta->xmp, "xmp"}};
+  for (const Member& mb : members) {
+    if (mb.n == 0) continue;
+    if (mb.p == nullptr) { *field = mb.name; return false; }
+    mb.to->assign(static_cast<const char*>(mb.p), mb.n);
+  }
+  meta->xmp_split = m->xmp_split_point;
+  return AppendMetadata(*meta, block, field);
+}
+
 bool AppendHeaders(int W, int H, int yuv_mode, const uint8_t quant[2][64],
                    const HuffSpec* dc[2], const HuffSpec* ac[2], const Metadata* meta,
                    std::vector<uint8_t>* o) {
+  if (meta == nullptr) return AppendHeadersBlock(W, H, yuv_mode, quant, dc, ac, nullptr, 0, o);
+  std::vector<uint8_t> block;
+  if (!AppendMetadata(*meta, &block, nullptr)) return false;
+  return AppendHeadersBlock(W, H, yuv_mode, quant, dc, ac, block.data(), block.size(), o);
+}
+
+bool AppendHeadersBlock(int W, int H, int yuv_mode, const uint8_t quant[2][64],
+                        const HuffSpec* const dc[2], const HuffSpec* const ac[2], const uint8_t* block, size_t block_size,
+                        std::vector<uint8_t>* o) {
   FrameLayout L;
   if (!LayoutFor(yuv_mode, &L)) return false;
   // SOI + JFIF APP0: v1.01, density 1:1 (no units), no thumbnail (headers.cc:48-55)
   static const uint8_t kJfif[20] = {0xff, 0xd8, 0xff, 0xe0, 0x00, 0x10, 'J', 'F', 'I', 'F',
                                     0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
   PutBytes(o, kJfif, sizeof(kJfif));
-  if (meta != nullptr) {
-    // raw application markers, verbatim (headers.cc:63-70)
-    if (!meta->app_markers.empty()) PutBytes(o, meta->app_markers.data(), meta->app_markers.size());
-    // EXIF in one APP1 (headers.cc:72-85)
-    if (!meta->exif.empty()) {
-      const size_t seg = meta->exif.size() + 6 + 2;
-      if (seg > 0xffff) return false;
-      Put16(o, 0xffe1); Put16(o, static_cast<uint32_t>(seg));
-      PutBytes(o, "Exif\0\0", 6);
-      PutBytes(o, meta->exif.data(), meta->exif.size());
-    }
-    // ICC profile in numbered APP2 chunks (headers.cc:87-113)
-    if (!meta->iccp.empty()) {
-      const size_t kMax = 0xffff - 12 - 4;
-      const size_t nchunks = (meta->iccp.size() + kMax - 1) / kMax;
-      if (nchunks >= 256) return false;
-      size_t pos = 0;
-      for (size_t seq = 1; pos < meta->iccp.size(); ++seq) {
-        const size_t n = std::min(kMax, meta->iccp.size() - pos);
-        Put16(o, 0xffe2); Put16(o, static_cast<uint32_t>(n + 12 + 4));
-        PutBytes(o, "ICC_PROFILE", 12);
-        o->push_back(static_cast<uint8_t>(seq));
-        o->push_back(static_cast<uint8_t>(nchunks));
-        PutBytes(o, meta->iccp.data() + pos, n);
-        pos += n;
-      }
-    }
-    // XMP: a single APP1 when it fits (headers.cc:162-180), else main + extension chunks
-    if (!meta->xmp.empty() && !AppendXmp(meta->xmp, meta->xmp_split, o)) return false;
-  }
+  if (block_size > 0) PutBytes(o, block, block_size);
   // DQT, 8-bit precision, zig-zag order (headers.cc:182-196)
   const int nq = (yuv_mode == SJPEG_HIP_YUV400) ? 1 : 2;
   Put16(o, 0xffdb); Put16(o, nq * 65 + 2);

@@ -58,6 +58,16 @@ struct Metadata {
 bool AppendHeaders(int W, int H, int yuv_mode, const uint8_t quant[2][64],
                    const HuffSpec* dc[2], const HuffSpec* ac[2], const Metadata* meta,
                    std::vector<uint8_t>* out);
+// The metadata segments alone: what AppendHeaders puts between SOI + APP0 (20 bytes) and DQT.  False for what the
+// reference refuses; *field (may be NULL) then names the member: "exif", "iccp" or "xmp".
+bool AppendMetadata(const Metadata& meta, std::vector<uint8_t>* out, const char** field);
+// The C-ABI's metadata as Metadata and as its segments (AppendMetadata).  NULL is no metadata.  False, *field naming
+// the member, for what the reference refuses and for a NULL pointer with a non-zero size.
+bool MetadataFromC(const sjpeg_hip_metadata* m, Metadata* meta, std::vector<uint8_t>* block, const char** field);
+// AppendHeaders with the metadata segments made beforehand (block_size 0: none)
+bool AppendHeadersBlock(int W, int H, int yuv_mode, const uint8_t quant[2][64],
+                        const HuffSpec* const dc[2], const HuffSpec* const ac[2], const uint8_t* block, size_t block_size,
+                        std::vector<uint8_t>* out);
 
 }  // namespace sjpeg_host
 

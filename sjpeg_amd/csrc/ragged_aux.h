@@ -103,6 +103,34 @@ struct PackedSink {
   int nframes;                   // of the packed call
   const int* index;              // the caller's number of each frame handed to the flow (NULL: its own position)
 };
+// ---- per-picture metadata of a ragged call (sjpeg_hip_encode_ragged_full_meta_src): the call's entries, checked and
+// turned into their segments before any device work.  The engine holds a pointer to it for the length of the call
+// (engine_meta); every place that builds a frame's header, and the size search, asks it for the frame's entry.  `index`
+// is PackedSink::index again: a flow that codes a subset of its frames points it at the caller's number of each frame
+// it passes on.
+struct FrameMeta {
+  sjpeg_host::Metadata meta;       // what the search counts (SearchHeaderBits)
+  std::vector<uint8_t> block;      // its segments: the bytes behind SOI + APP0
+};
+struct MetaCtx {
+  std::vector<FrameMeta> entries;  // one for all frames, or one per frame
+  int per_frame = 0;
+  const int* index = nullptr;
+  const FrameMeta& of(int f) const { return entries[per_frame ? (index != nullptr ? index[f] : f) : 0]; }
+};
+// the metadata of the call the engine is running (NULL: none), and setting it
+MetaCtx* engine_meta(const sjpeg_hip_engine* e);
+void engine_set_meta(sjpeg_hip_engine* e, MetaCtx* ctx);
+// frame f's entry (f: as the flow at hand numbers its frames), or NULL without metadata
+inline const FrameMeta* frame_meta(const sjpeg_hip_engine* e, int f) {
+  const MetaCtx* const c = engine_meta(e);
+  return c != nullptr ? &c->of(f) : nullptr;
+}
+// A frame's header behind *headers: SOI + APP0, the frame's metadata segments, DQT, SOF0, DHT (specs[4], or NULL for
+// the default codes), SOS
+bool append_frame_header(int width, int height, int yuv_mode, const uint8_t quant[2][64], const sjpeg_hip_huffman_spec* specs,
+                         const FrameMeta* fm, std::vector<uint8_t>* headers);
+
 // the entry points' flows with a sink (the public functions pass NULL); scan_engine.hip and ragged_full.cc
 int ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
                       const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,

@@ -87,6 +87,12 @@ struct Call {
   int32_t* d_tot;
 };
 
+// what HeaderSize() counts of frame f's metadata (NULL: the call has none)
+const sjpeg_host::Metadata* frame_metadata(const sjpeg_hip_engine* e, int f) {
+  const sjpeg_internal::FrameMeta* const fm = sjpeg_internal::frame_meta(e, f);
+  return fm != nullptr ? &fm->meta : nullptr;
+}
+
 int hip_fail(const std::string& who, const char* what) {
   const hipError_t err = hipGetLastError();
   return set_error(err == hipErrorOutOfMemory ? SJPEG_HIP_ENOMEM : SJPEG_HIP_ERUNTIME,
@@ -249,7 +255,7 @@ int search_kind(const Call& c, std::vector<Frame>& s, const std::vector<Group>& 
           const uint32_t* const freq = reinterpret_cast<const uint32_t*>(h_meas.data() + static_cast<size_t>(i) * kFreq);
           sjpeg_hip_optimize_huffman(freq, g.yuv_mode, specs, &atab[i]);
           for (int t = 0; t < g.ntab; ++t) { dc[t] = &specs[t]; ac[t] = &specs[2 + t]; }
-          size = sjpeg_host::SearchHeaderBits(g.nb_comps, g.ntab, dc, ac, nullptr);
+          size = sjpeg_host::SearchHeaderBits(g.nb_comps, g.ntab, dc, ac, frame_metadata(c.e, f.index));
           size += sjpeg_host::EntropyBits(reinterpret_cast<const uint32_t(*)[272]>(freq), g.ntab, &atab[i]);
           if (trellis_pass) {
             // InitCodes(true) after CompileEntropyStats (src/dichotomy.cc:152, src/entropy.cc:116-128): the lengths of the
@@ -265,7 +271,7 @@ int search_kind(const Call& c, std::vector<Frame>& s, const std::vector<Group>& 
           }
         } else {
           for (int t = 0; t < g.ntab; ++t) { dc[t] = &sjpeg_host::DefaultHuff(0, t); ac[t] = &sjpeg_host::DefaultHuff(1, t); }
-          size = sjpeg_host::SearchHeaderBits(g.nb_comps, g.ntab, dc, ac, nullptr);
+          size = sjpeg_host::SearchHeaderBits(g.nb_comps, g.ntab, dc, ac, frame_metadata(c.e, f.index));
           size += h_vals[i];
         }
         result = size / 8.f;
@@ -345,13 +351,12 @@ int finish_trellis(const Call& c, std::vector<Frame>& s, const std::vector<Group
     std::vector<sjpeg_hip_ragged_frame> gfr;
     std::vector<uint32_t> gkept;
     std::vector<int> gidx;
-    uint8_t one[2048];
     for (int k = g.first; k < g.first + g.count; ++k) {
-      const size_t hs = sjpeg_hip_make_header_ex(s[k].fr.width, s[k].fr.height, g.yuv_mode,
-                                                 reinterpret_cast<const uint8_t(*)[64]>(&best[static_cast<size_t>(k) * 128]),
-                                                 &specs[static_cast<size_t>(k) * 4], one, sizeof(one));
-      if (hs == 0) return set_error(SJPEG_HIP_EINVAL, who + ": header generation failed");
-      headers.insert(headers.end(), one, one + hs);
+      if (!sjpeg_internal::append_frame_header(s[k].fr.width, s[k].fr.height, g.yuv_mode,
+                                               reinterpret_cast<const uint8_t(*)[64]>(&best[static_cast<size_t>(k) * 128]),
+                                               &specs[static_cast<size_t>(k) * 4], sjpeg_internal::frame_meta(c.e, s[k].index), &headers)) {
+        return set_error(SJPEG_HIP_EINVAL, who + ": header generation failed");
+      }
       offs[k - g.first + 1] = headers.size();
       gfr.push_back(s[k].fr);
       gkept.push_back(s[k].kept_base);
@@ -427,6 +432,12 @@ int search_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfr
       if (sink != nullptr) { sub_sink = *sink; sub_sink.index = sub_index.data(); }
       uint64_t* d_sub = nullptr;
       if (int rc = sjpeg_internal::engine_search_sizes(e, n_all, &d_sub)) return rc;
+      // (that flow numbers its frames 0 .. plain.size() - 1: their metadata is found under the caller's numbers)
+      struct MetaIndex {
+        sjpeg_internal::MetaCtx* m;
+        MetaIndex(sjpeg_internal::MetaCtx* ctx, const int* index) : m(ctx) { if (m != nullptr) m->index = index; }
+        ~MetaIndex() { if (m != nullptr) m->index = nullptr; }
+      } meta_index(sjpeg_internal::engine_meta(e), plain.data());
       if (int rc = sjpeg_internal::ragged_unsearched_flow(e, format, yuv_mode, static_cast<int>(plain.size()), sub.data(),
                                                           reinterpret_cast<const uint8_t(*)[2][64]>(q.data()), 1, P.min_quant, P.q_bias,
                                                           method, P.qdelta_max_luma, P.qdelta_max_chroma, d_out, d_sub, nullptr, stream,
@@ -636,6 +647,41 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
   return search_flow(who, e, format, nframes, frames, P, d_out, d_sizes, modes, q_out, value_out, stream, sink, stats);
 }
 
+// what is wrong with a metadata member (jpeg_host.h: MetadataFromC names it), in words
+std::string meta_fault(const char* field) {
+  const std::string f = field;
+  if (f == "exif") return "exif: NULL with a size, or its APP1 segment would pass 65535 bytes (at most 65527 bytes of EXIF)";
+  if (f == "iccp") return "iccp: NULL with a size, or a profile of 256 chunks or more (at most 255 x 65519 bytes)";
+  if (f == "xmp") {
+    return "xmp: NULL with a size, or a packet above 65504 bytes (one APP1 segment) without a well-formed xmpNote:HasExtendedXMP=\" note in front of "
+           "the split point, or above 2^31 bytes";
+  }
+  return f + ": NULL with a non-zero size";
+}
+
+// The call's metadata -- one entry, or one per frame -- checked and turned into segments, before any device work
+int check_metadata(const std::string& who, int nframes, const sjpeg_hip_metadata* meta, int meta_per_frame, sjpeg_internal::MetaCtx* ctx) {
+  ctx->per_frame = meta_per_frame ? 1 : 0;
+  ctx->entries.resize(meta_per_frame ? static_cast<size_t>(nframes) : 1);
+  for (size_t k = 0; k < ctx->entries.size(); ++k) {
+    const char* field = "";
+    if (!sjpeg_host::MetadataFromC(&meta[k], &ctx->entries[k].meta, &ctx->entries[k].block, &field)) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": meta[" + std::to_string(k) + "] (frame " + std::to_string(k) + "): " + meta_fault(field));
+    }
+    if (ctx->entries[k].block.size() > 0xffffffffull - 4096) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": meta[" + std::to_string(k) + "] (frame " + std::to_string(k) + "): the metadata must stay below 4 GiB");
+    }
+  }
+  return 0;
+}
+
+// the engine carries the call's metadata while the call runs
+struct MetaScope {
+  sjpeg_hip_engine* e;
+  MetaScope(sjpeg_hip_engine* engine, sjpeg_internal::MetaCtx* ctx) : e(engine) { sjpeg_internal::engine_set_meta(e, ctx); }
+  ~MetaScope() { sjpeg_internal::engine_set_meta(e, nullptr); }
+};
+
 }  // namespace
 
 // sjpeg_hip_encode_ragged_search_src (sink != NULL: packed output): one sampling, methods 0..6 -- its own checks and
@@ -719,6 +765,73 @@ int sjpeg_hip_encode_ragged_full_packed_src(sjpeg_hip_engine* e, int format, int
     for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
     const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
     // (full_flow zeroes the engine's cursor behind its checks: they come before the engine is touched)
+    return full_flow(who, e, format, nframes, fr.data(), params, d_packed, d_sizes, modes, q_out, value_out, stream, &sink);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_metadata_size(const sjpeg_hip_metadata* meta, size_t* size) {
+  static const std::string who = "sjpeg_hip_metadata_size";
+  if (size == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": size == NULL");
+  *size = 0;
+  try {
+    sjpeg_internal::FrameMeta fm;
+    const char* field = "";
+    if (!sjpeg_host::MetadataFromC(meta, &fm.meta, &fm.block, &field)) return set_error(SJPEG_HIP_EINVAL, who + ": " + meta_fault(field));
+    *size = fm.block.size();
+    return 0;
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_full_meta_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                          void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  if (meta == nullptr) return sjpeg_hip_encode_ragged_full_src(e, format, nframes, frames, params, d_out, d_sizes, modes, q_out, value_out, stream);
+  static const std::string who = "sjpeg_hip_encode_ragged_full_meta_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  try {
+    sjpeg_internal::MetaCtx ctx;
+    if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc;
+    const MetaScope scope(e, &ctx);
+    return full_flow(who, e, format, nframes, frames, params, d_out, d_sizes, modes, q_out, value_out, stream, nullptr);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta,
+                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  if (meta == nullptr) {
+    return sjpeg_hip_encode_ragged_full_packed_src(e, format, nframes, frames, params, d_packed, packed_capacity, d_offsets, d_sizes,
+                                                   modes, q_out, value_out, stream);
+  }
+  static const std::string who = "sjpeg_hip_encode_ragged_full_meta_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  try {
+    sjpeg_internal::MetaCtx ctx;
+    if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc;
+    std::vector<sjpeg_hip_ragged_frame> fr(frames, frames + nframes);
+    for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
+    const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+    const MetaScope scope(e, &ctx);
     return full_flow(who, e, format, nframes, fr.data(), params, d_packed, d_sizes, modes, q_out, value_out, stream, &sink);
   } catch (...) {
     return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");

@@ -227,6 +227,11 @@ struct sjpeg_hip_engine {
   // offsets and header bytes, uploaded as one blob -- buffers of its own, so that nothing the uniform calls hold or
   // upload on the stitch stream is touched
   DevBuf<uint4> ragged;
+  // ... but the header bytes: a frame with metadata has a header of up to megabytes, so the headers of ONE launch at a
+  // time are staged here (counted against the scratch limit; below 4 GiB: the kernels address them with 32-bit offsets)
+  DevBuf<uint4> hdr_stage;
+  // the metadata of the ragged call the engine is running (ragged_aux.h; NULL: none)
+  sjpeg_internal::MetaCtx* meta = nullptr;
   // ragged calls with SJPEG_YUV_AUTO / SJPEG_YUV_SHARP (sjpeg_hip_encode_ragged_auto_src): the riskiness table of this
   // device (uploaded again when sjpeg_hip_set_riskiness_table changes it), the riskiness descriptors and sums, the sizes
   // of the mode groups before they go back to the caller's order, and the sharp frames' planes and workspace
@@ -676,7 +681,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   }
   e->tables.release(); e->header.release(); e->seg_words.release(); e->seg_nbits.release(); e->pool.release(); e->pool_ctr.release(); e->seg_xbase.release(); e->replay.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
-  e->frame_flags.release(); e->ragged.release();
+  e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
@@ -701,7 +706,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->seg_words2.release(); e->seg_nbits2.release(); e->pool2.release(); e->pool_ctr2.release(); e->seg_xbase2.release();
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->replay.release();
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
-  e->frame_flags.release(); e->ragged.release();
+  e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
@@ -845,7 +850,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   for (auto* l : e->lane) if (l != nullptr) lanes += sjpeg_hip_engine_scratch_bytes(l);
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
-         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) +
+         b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) + b(e->hdr_stage) +
          b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor);
 }
 
@@ -1376,6 +1381,8 @@ struct RaggedLaunch {
   uint32_t segs, place_wgs, stuff_wgs, chunks;
   size_t pool_words, ubuf_words;
   size_t k1_map, place_map, stuff_map;     // where the launch's maps start in the u32 part of the blob
+  size_t hdr_bytes;                        // its frames' headers: staged launch by launch (sjpeg_hip_engine::hdr_stage)
+  size_t hoff;                             // where its nf + 1 header offsets start in the blob's offsets
 };
 
 // The source format of a ragged call (as prepare_scan): the kernel's per-format fields in *a (zeroed first), the source
@@ -1457,7 +1464,8 @@ int sjpeg_hip_encode_ragged_src(sjpeg_hip_engine* e, int format, int yuv_mode, i
   size_t header_size = 0;
   if (header_offsets != nullptr) {
     for (int f = 0; f <= nframes; ++f) {
-      if (header_offsets[f] > 0xffffffffu || (f > 0 && header_offsets[f] < header_offsets[f - 1])) {
+      // (a launch addresses its staged headers with 32-bit offsets: one header stays below 4 GiB, the launches are cut)
+      if (f > 0 && (header_offsets[f] < header_offsets[f - 1] || header_offsets[f] - header_offsets[f - 1] > 0xffffffffu)) {
         return fail(SJPEG_HIP_EINVAL, "sjpeg_hip_encode_ragged_src: header_offsets[" + std::to_string(f) + "] must ascend (below 4 GiB)");
       }
     }
@@ -1508,18 +1516,22 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const 
   std::vector<RaggedLaunch> launches;
   size_t map_words = 0;
   {
-    RaggedLaunch cur = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    RaggedLaunch cur = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // (the fields not named: zero)
     uint32_t slot_max = 0;
     auto bytes_of = [](size_t segs, uint32_t slot, size_t pool, size_t ubuf) { return (segs * slot + pool + ubuf) * sizeof(uint32_t); };
     for (int f = 0; f < nframes; ++f) {
       const uint32_t slot = std::max(slot_max, plan[f].slot_words);
       const size_t pool_f = (static_cast<size_t>(plan[f].pool_words) + 3) & ~size_t(3);
-      if (cur.nf > 0 && (bytes_of(static_cast<size_t>(cur.segs) + geo[f].nseg, slot, cur.pool_words + pool_f, cur.ubuf_words + plan[f].ubuf_words) > e->scratch_limit ||
-                         static_cast<size_t>(cur.segs) + geo[f].nseg > (1u << 30))) {
+      // (the staged headers are scratch like the rest, and one launch's stay below 4 GiB: 32-bit offsets)
+      const size_t hdr_f = header_offsets != nullptr ? header_offsets[f + 1] - header_offsets[f] : 0;
+      if (cur.nf > 0 && (bytes_of(static_cast<size_t>(cur.segs) + geo[f].nseg, slot, cur.pool_words + pool_f, cur.ubuf_words + plan[f].ubuf_words) +
+                                 cur.hdr_bytes + hdr_f > e->scratch_limit ||
+                         static_cast<size_t>(cur.segs) + geo[f].nseg > (1u << 30) || cur.hdr_bytes + hdr_f > 0xffffffffull)) {
         launches.push_back(cur);
         cur = {f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         slot_max = 0;
       }
+      cur.hdr_bytes += hdr_f;
       slot_max = std::max(slot_max, plan[f].slot_words);
       cur.nf += 1;
       cur.segs += static_cast<uint32_t>(geo[f].nseg);
@@ -1538,15 +1550,19 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const 
       }
       l.k1_map = map_words; l.place_map = l.k1_map + l.segs; l.stuff_map = l.place_map + l.place_wgs;
       map_words = l.stuff_map + l.stuff_wgs;
+      l.hoff = static_cast<size_t>(l.f0) + static_cast<size_t>(&l - launches.data());     // (nf + 1 offsets a launch)
     }
   }
 
-  // the blob: descriptors | digested tables | maps | header offsets | header bytes | (packed) the caller's frame numbers
+  // the blob: descriptors | digested tables | maps | header offsets (per launch: its nf + 1, from the first of its
+  // headers) | header bytes (a call of ONE launch: they travel with the blob, no upload of their own; a call of several
+  // stages each launch's in hdr_stage) | (packed) the caller's frame numbers
+  const bool hdr_in_blob = launches.size() == 1;
   const size_t off_tab = align16(sizeof(RaggedFrame) * nframes);
   const size_t off_map = off_tab + sizeof(DevTables) * ntab;
   const size_t off_hoff = align16(off_map + map_words * sizeof(uint32_t));
-  const size_t off_hdr = align16(off_hoff + (header_offsets != nullptr ? (static_cast<size_t>(nframes) + 1) * sizeof(uint32_t) : 0));
-  const size_t off_pidx = align16(off_hdr + header_size);
+  const size_t off_hdr = align16(off_hoff + (header_offsets != nullptr ? (static_cast<size_t>(nframes) + launches.size()) * sizeof(uint32_t) : 0));
+  const size_t off_pidx = align16(off_hdr + (hdr_in_blob ? launches[0].hdr_bytes : 0));
   const size_t blob_bytes = align16(off_pidx + (sink != nullptr ? static_cast<size_t>(nframes) * sizeof(uint32_t) : 0));
   std::vector<uint4> blob(blob_bytes / 16);
   uint8_t* const hb = reinterpret_cast<uint8_t*>(blob.data());
@@ -1585,10 +1601,14 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const 
       ubuf += plan[f].ubuf_words;
     }
   }
+  size_t n_hdr = 0;
   if (header_offsets != nullptr) {
     uint32_t* const ho = reinterpret_cast<uint32_t*>(hb + off_hoff);
-    for (int f = 0; f <= nframes; ++f) ho[f] = static_cast<uint32_t>(header_offsets[f]);
-    if (header_size > 0) memcpy(hb + off_hdr, headers, header_size);
+    for (const RaggedLaunch& l : launches) {
+      for (int k = 0; k <= l.nf; ++k) ho[l.hoff + k] = static_cast<uint32_t>(header_offsets[l.f0 + k] - header_offsets[l.f0]);
+      if (!hdr_in_blob) n_hdr = std::max(n_hdr, l.hdr_bytes);
+    }
+    if (hdr_in_blob && launches[0].hdr_bytes > 0) memcpy(hb + off_hdr, static_cast<const uint8_t*>(headers) + header_offsets[0], launches[0].hdr_bytes);
   }
   if (sink != nullptr) {
     uint32_t* const pi = reinterpret_cast<uint32_t*>(hb + off_pidx);
@@ -1617,7 +1637,7 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const 
   if ((rc = e->ragged.ensure(blob.size())) || (rc = e->seg_nbits.ensure(n_segs)) || (rc = e->seg_words.ensure(n_words)) ||
       (rc = e->pool.ensure(n_pool)) || (rc = e->pool_ctr.ensure(2 * n_f)) || (rc = e->seg_xbase.ensure(n_segs)) ||
       (rc = e->seg_off.ensure(n_off)) || (rc = e->ubuf.ensure(n_ubuf)) || (rc = e->chunk_ff.ensure(n_chunks)) ||
-      (rc = e->chunk_off.ensure(n_chunks)) || (rc = e->frame_flags.ensure(n_f))) {
+      (rc = e->chunk_off.ensure(n_chunks)) || (rc = e->frame_flags.ensure(n_f)) || (n_hdr > 0 && (rc = e->hdr_stage.ensure(n_hdr / 16 + 1)))) {
     return rc;
   }
   if (sink != nullptr && e->pack_cursor.p == nullptr) return fail(SJPEG_HIP_EINVAL, "internal: packed output without its cursor");
@@ -1647,14 +1667,19 @@ int ragged_encode(sjpeg_hip_engine* e, int yuv_mode, int cls, ScanArgs a, const 
     }
     if (rc) return rc;
     if (e->timing && li + 1 == launches.size()) HIP_TRY(hipEventRecord(e->ev[1], st));
+    // the launch's headers: behind the stitch kernels of the launch in front, which read theirs from the same place
+    if (!hdr_in_blob && l.hdr_bytes > 0 && d_bits == nullptr) {
+      if ((rc = upload(e, e->hdr_stage.p, static_cast<const uint8_t*>(headers) + header_offsets[l.f0], l.hdr_bytes, st))) return rc;
+      if ((rc = sync_uploads(e, st))) return rc;
+    }
     StitchArgs s{};
     s.nframes = l.nf;
     s.seg_nbits = e->seg_nbits.p; s.seg_off = e->seg_off.p;
     s.seg_words = e->seg_words.p; s.slot_words = slot_of[li];
     s.pool = e->pool.p; s.seg_xbase = e->seg_xbase.p; s.pool_ctr = e->pool_ctr.p;
     s.ubuf = e->ubuf.p; s.chunk_ff = e->chunk_ff.p; s.chunk_off = e->chunk_off.p;
-    s.header = db + off_hdr; s.header_size = 0;
-    s.hdr_off = header_offsets != nullptr ? reinterpret_cast<const uint32_t*>(db + off_hoff) + l.f0 : nullptr;
+    s.header = hdr_in_blob ? db + off_hdr : reinterpret_cast<const uint8_t*>(e->hdr_stage.p); s.header_size = 0;
+    s.hdr_off = header_offsets != nullptr ? reinterpret_cast<const uint32_t*>(db + off_hoff) + l.hoff : nullptr;
     s.append_eoi = append_eoi;
     s.out = static_cast<uint8_t*>(sink != nullptr ? sink->base : d_out);
     s.sizes = d_sizes != nullptr ? reinterpret_cast<unsigned long long*>(d_sizes) + l.f0 : nullptr;
@@ -2032,6 +2057,22 @@ int counted_bits_first(sjpeg_hip_engine* e, int format, int yuv_mode, int nframe
 
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
 
+MetaCtx* engine_meta(const sjpeg_hip_engine* e) { return e->meta; }
+void engine_set_meta(sjpeg_hip_engine* e, MetaCtx* ctx) { e->meta = ctx; }
+
+bool append_frame_header(int width, int height, int yuv_mode, const uint8_t quant[2][64], const sjpeg_hip_huffman_spec* specs,
+                         const FrameMeta* fm, std::vector<uint8_t>* headers) {
+  if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
+  const sjpeg_host::HuffSpec* dc[2] = {&sjpeg_host::DefaultHuff(0, 0), &sjpeg_host::DefaultHuff(0, 1)};
+  const sjpeg_host::HuffSpec* ac[2] = {&sjpeg_host::DefaultHuff(1, 0), &sjpeg_host::DefaultHuff(1, 1)};
+  if (specs != nullptr) {
+    const int ntables = (yuv_mode == SJPEG_HIP_YUV400) ? 1 : 2;
+    for (int t = 0; t < ntables; ++t) { dc[t] = &specs[t]; ac[t] = &specs[2 + t]; }
+  }
+  return sjpeg_host::AppendHeadersBlock(width, height, yuv_mode, quant, dc, ac, fm != nullptr ? fm->block.data() : nullptr,
+                                        fm != nullptr ? fm->block.size() : 0, headers);
+}
+
 int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames) {
   ScanArgs a;
   int cls = 0;
@@ -2390,19 +2431,20 @@ void adopt_matrices(const uint8_t* h_q, size_t f0, size_t nf, int yuv_mode, cons
 }
 
 // the headers of frames f0 .. f0 + nf - 1 back to back, frame f0 + k's at (*offs)[k] .. (*offs)[k + 1]; dims(k) is its
-// width and height.  quant: [frame][128]; specs: [frame][4], or NULL for the default codes
+// width and height.  quant: [frame][128]; specs: [frame][4], or NULL for the default codes; meta (may be empty): meta(k)
+// is its metadata, or NULL
 int batch_headers(const std::string& who, const std::function<std::pair<int, int>(size_t)>& dims, size_t f0, size_t nf, int yuv_mode, const uint8_t* quant,
-                  const sjpeg_hip_huffman_spec* specs, std::vector<uint8_t>* headers, std::vector<size_t>* offs) {
+                  const sjpeg_hip_huffman_spec* specs, std::vector<uint8_t>* headers, std::vector<size_t>* offs,
+                  const std::function<const sjpeg_internal::FrameMeta*(size_t)>& meta = {}) {
   headers->clear();
   offs->assign(nf + 1, 0);
-  uint8_t one[2048];
   for (size_t k = 0; k < nf; ++k) {
     const size_t f = f0 + k;
     const std::pair<int, int> wh = dims(k);
-    const size_t hs = sjpeg_hip_make_header_ex(wh.first, wh.second, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(quant + f * 128),
-                                               specs != nullptr ? specs + f * 4 : nullptr, one, sizeof(one));
-    if (hs == 0) return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
-    headers->insert(headers->end(), one, one + hs);
+    if (!sjpeg_internal::append_frame_header(wh.first, wh.second, yuv_mode, reinterpret_cast<const uint8_t(*)[64]>(quant + f * 128),
+                                             specs != nullptr ? specs + f * 4 : nullptr, meta ? meta(k) : nullptr, headers)) {
+      return fail(SJPEG_HIP_EINVAL, who + ": header generation failed");
+    }
     (*offs)[k + 1] = headers->size();
   }
   return 0;
@@ -2976,7 +3018,8 @@ int ragged_batch_groups(sjpeg_hip_engine* e, const std::string& who, std::vector
     std::vector<uint8_t> headers;
     std::vector<size_t> offs;
     if (int rc = batch_headers(who, [&](size_t k) { return std::make_pair(g.frames[k].width, g.frames[k].height); }, gbase[gi], ng,
-                               g.yuv_mode, quant.data(), optimize ? specs.data() : nullptr, &headers, &offs)) return rc;
+                               g.yuv_mode, quant.data(), optimize ? specs.data() : nullptr, &headers, &offs,
+                               [&](size_t k) { return sjpeg_internal::frame_meta(e, g.index[k]); })) return rc;
     if (gi + 1 == groups.size()) mark("tables built");
     if (int rc = ready(gi)) return rc;
     if (sink != nullptr) {               // packed output: the group's frames under the caller's numbers

@@ -493,6 +493,24 @@ __global__ __launch_bounds__(kThreads) void place_segments(const StitchArgs a_in
   if (ff_chunk != 0xffffffffu) ff_flush();
 }
 
+// A header longer than kWideHeader bytes -- a frame that carries metadata: an EXIF block, an ICC profile of a megabyte --
+// placed by the whole workgroup with 16-byte stores to the destination's aligned addresses: bytes up to the first of
+// them, bytes behind the last.  The source is read 16 bytes at a time at whatever alignment it has (as pixel_elem.h
+// reads its elements).  Shorter headers keep the byte loop of their kernel; the choice is uniform over the workgroup.
+constexpr uint32_t kWideHeader = 2048;
+__device__ __forceinline__ void place_wide_header(uint8_t* dst, const uint8_t* src, uint32_t hsize) {
+  const uint32_t head = static_cast<uint32_t>((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);    // (< hsize)
+  if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+  const uint32_t n16 = (hsize - head) >> 4;
+  for (uint32_t i = threadIdx.x; i < n16; i += kThreads) {
+    uint4 v;
+    __builtin_memcpy(&v, src + head + 16u * i, 16);
+    *reinterpret_cast<uint4*>(dst + head + 16u * i) = v;
+  }
+  const uint32_t done = head + (n16 << 4);
+  if (threadIdx.x < hsize - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
+}
+
 __device__ __forceinline__ uint8_t* frame_out(const StitchArgs& a, int frame) {
   return a.pack_off != nullptr ? a.out + a.pack_off[frame] : a.out + static_cast<size_t>(frame) * a.out_stride;
 }
@@ -555,7 +573,8 @@ __global__ __launch_bounds__(kThreads) void scan_chunk_offsets(const StitchArgs 
   }
   // header bytes in front of the entropy segment
   if (fits) {
-    for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
+    if (hsize > kWideHeader) place_wide_header(dst, a.header + hoff, hsize);
+    else for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
   }
 }
 
@@ -584,7 +603,8 @@ __global__ __launch_bounds__(kThreads) void pack_frame_edges(const StitchArgs a)
   const uint32_t hoff = a.hdr_off ? a.hdr_off[frame] : 0u;
   const uint32_t hsize = a.hdr_off ? a.hdr_off[frame + 1] - hoff : a.header_size;
   uint8_t* const dst = a.out + a.pack_off[frame];
-  for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
+  if (hsize > kWideHeader) place_wide_header(dst, a.header + hoff, hsize);
+  else for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
   if (threadIdx.x == 0 && a.append_eoi) { dst[size - 2] = 0xff; dst[size - 1] = 0xd9; }
   const uint32_t pad = static_cast<uint32_t>((16u - (size & 15u)) & 15u);
   if (threadIdx.x < pad) dst[size + threadIdx.x] = 0;
@@ -660,7 +680,8 @@ __global__ __launch_bounds__(kThreads) void pack_ragged_edges(const StitchArgs a
   const uint32_t hoff = a.hdr_off ? a.hdr_off[frame] : 0u;
   const uint32_t hsize = a.hdr_off ? a.hdr_off[frame + 1] - hoff : a.header_size;
   uint8_t* const dst = a.out + a.rframes[frame].out_offset;
-  for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
+  if (hsize > kWideHeader) place_wide_header(dst, a.header + hoff, hsize);
+  else for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
   if (threadIdx.x == 0 && a.append_eoi) { dst[size - 2] = 0xff; dst[size - 1] = 0xd9; }
   const uint32_t pad = static_cast<uint32_t>((16u - (size & 15u)) & 15u);
   if (threadIdx.x < pad) dst[size + threadIdx.x] = 0;
@@ -742,7 +763,8 @@ __global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a_in) 
       if (fits) {
         uint8_t* const dst = a.out + static_cast<size_t>(frame) * a.out_stride;
         if (threadIdx.x == 0 && a.append_eoi) { dst[hsize + body] = 0xff; dst[hsize + body + 1] = 0xd9; }
-        for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
+        if (hsize > kWideHeader) place_wide_header(dst, a.header + hoff, hsize);
+        else for (uint32_t i = threadIdx.x; i < hsize; i += kThreads) dst[i] = a.header[hoff + i];
       }
     }
     if (!fits) return;                                      // (uniform over the frame's workgroups)
