@@ -762,6 +762,75 @@ int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* engine, int f
                                                  int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                  void* stream);
 
+/* ---- pictures reduced inside the ragged call: thumbnails and pyramid levels ----
+ * A thumbnail service, a srcset or DeepZoom pyramid, a dataset preview: each picture at 1/2, 1/4 or 1/8 of its size.
+ * Frame f has a factor s = factors[f] in 1..SJPEG_HIP_REDUCE_MAX.  Its reduced picture is w' = (W + s - 1) / s by
+ * h' = (H + s - 1) / s; sample (x', y', c) is
+ *     sum = the sum over dy < s, dx < s of b(min(x' * s + dx, W - 1), min(y' * s + dy, H - 1), c)
+ *     out = (sum + s * s / 2) / (s * s)                        integer arithmetic, exact: round half up
+ * where b is the byte the encoder sees at that source pixel today: R, G, B of the packed and planar byte formats (alpha
+ * is not part of it), the float formats through the engine's pixel transform (above), the gray value of the gray
+ * formats.  Edges replicate the last column and row: a 17-wide picture at s = 8 gives 3 columns, the last made of one
+ * source column.  s = 1 is the identity.  THE CONTRACT: the JPEG of a reduced frame is byte for byte what the same call
+ * makes of the uint8 picture so defined handed over as SJPEG_HIP_SRC_RGB (the gray formats: SJPEG_HIP_SRC_GRAY, yuv_mode
+ * 4:0:0 only).  Formats: every RGB-like one (RGB, BGRA, RGBA, planar RGB, all their float forms) and the four gray ones;
+ * strides of either sign, element-only alignment, and no element read that is not a used sample of a pixel of the
+ * picture, as everywhere.  The planar and semi-planar YUV formats (YUV444, YUV420, NV12, NV21) are not reduced: with a
+ * factor above 1 they are SJPEG_HIP_EINVAL, the message names the format.
+ * A pyramid is the same picture listed several times, with factors 1, 2, 4, 8 (every level reads the source again).
+ *
+ * sjpeg_hip_reduced_size (host only): w' and h'.  SJPEG_HIP_EINVAL for a factor outside 1..8 or dimensions outside
+ *   1..65535.
+ * sjpeg_hip_reduce_ragged_bytes (host only): the bytes the reduced pictures of a batch take, 0 on bad arguments
+ *   (factors NULL: all 1).  THE LAYOUT: interleaved uint8 R, G, B (one gray plane for the gray formats); a picture's rows
+ *   are its row bytes rounded up to a multiple of 4 apart, every picture starts at a multiple of 16 from the buffer's
+ *   start, frame after frame in the caller's order.  The padding behind a row and behind a picture may hold anything
+ *   and lies inside the buffer.  (So the kernel stores whole dwords; beside the sources it is their size divided by
+ *   s * s, plus that padding.)
+ * sjpeg_hip_reduce_ragged_src: ONE launch over the batch's tiles into d_reduced (a multiple of 16, reduced_bytes
+ *   behind it), asynchronous on `stream` and ordered as every engine call is, pipelined mode included.  It fills
+ *   reduced_frames[f] (host) with plane[0], row_stride[0], w' and h' -- out_offset / out_capacity are copied from
+ *   frames[f] -- and sets *reduced_format to SJPEG_HIP_SRC_RGB or SJPEG_HIP_SRC_GRAY: the pair goes to any ragged entry.
+ *   It takes an engine because the float formats read its pixel transform.  SJPEG_HIP_EINVAL before any device work, the
+ *   frame named as the ragged entries name it: a factor outside 1..8, a YUV-plane format, reduced_bytes below
+ *   sjpeg_hip_reduce_ragged_bytes(), and every frame check of sjpeg_hip_encode_ragged_src.
+ * sjpeg_hip_encode_ragged_reduced_src / _reduced_packed_src: the arguments and the output contract of
+ *   sjpeg_hip_encode_ragged_full_meta_src / _full_meta_packed_src, plus `factors` (host, uint8[nframes]).
+ *   factors == NULL or every factor 1: exactly that call on the caller's frames, any format; no copy, no kernel.
+ *   Otherwise every frame goes through the reduce kernel into engine memory -- the frames with s = 1 too: they are
+ *   copied or converted, which the formats' own contracts make byte-exact, so that ONE inner call codes the batch as one
+ *   group of one format: frame order, packed layout, modes, q_out, value_out, the host waits and
+ *   sjpeg_hip_engine_search_stats are those of that call on the reduced pictures (SJPEG_YUV_AUTO decides on the REDUCED
+ *   picture).  out_capacity is the caller's: sjpeg_hip_frame_bound(w', h', SJPEG_HIP_YUV444, 2048 + metadata) is always
+ *   enough.  The reduced pictures live in engine memory of their own, one allocation (not the arena of the sharp planes),
+ *   counted by sjpeg_hip_engine_scratch_bytes and released by sjpeg_hip_engine_trim; a failure to get it is
+ *   SJPEG_HIP_ENOMEM naming the bytes.  A later call on the engine writes them behind everything the earlier one queued
+ *   (the engine's ordering between streams; two calls on one stream are ordered by it).  SJPEG_HIP_EINVAL before any
+ *   device work: the checks above, gray with a yuv_mode other than 4:0:0, and every check of the inner call. */
+#define SJPEG_HIP_REDUCE_MAX 8
+int sjpeg_hip_reduced_size(int width, int height, int factor, int* reduced_width, int* reduced_height);
+size_t sjpeg_hip_reduce_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const uint8_t* factors /*host uint8[nframes], or NULL*/);
+int sjpeg_hip_reduce_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                const uint8_t* factors /*host uint8[nframes]*/, void* d_reduced, size_t reduced_bytes,
+                                sjpeg_hip_ragged_frame* reduced_frames /*host out [nframes]*/, int* reduced_format,
+                                void* stream);
+int sjpeg_hip_encode_ragged_reduced_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                        const sjpeg_hip_ragged_params* params, const uint8_t* factors /*host uint8[nframes], or NULL*/,
+                                        const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                        void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                        int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                               const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                               const sjpeg_hip_ragged_params* params, const uint8_t* factors /*host uint8[nframes], or NULL*/,
+                                               const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                               void* d_packed, size_t packed_capacity,
+                                               uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                               int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                               void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

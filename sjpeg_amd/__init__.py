@@ -197,6 +197,51 @@ def _float_pixels(who, images, chw):
     return images.images, images
 
 
+REDUCE_MAX = 8                   # SJPEG_HIP_REDUCE_MAX
+
+
+class Reduced:
+    """Pictures to be coded at 1/factor of their size -- thumbnails, the levels of a srcset or DeepZoom pyramid, dataset
+    previews -- as the `images` of encode_images, compress_images, encode_images_full, encode_images_full_chw and
+    encode_images_full_meta: Reduced(images, factor) with `images` what those calls take (a sequence of CUDA tensors, or
+    a FloatPixels with layout="chw") and `factor` one int in 1..8 or one per picture.  Picture k becomes
+    (W + s - 1) // s by (H + s - 1) // s: every sample the average of an s x s box of the bytes the encoder sees today
+    (float pictures: after the pixel transform), rounded half up, the last column and row replicated at the edges -- one
+    launch of the reduce kernel for the whole batch, no torch call and no float intermediate per picture -- and its JPEG
+    is byte for byte that of the uint8 picture so defined (reduce_images returns those).  Everything else of the call
+    -- layout, packed, metadata, targets, the trellis, YUV_AUTO -- works on the reduced pictures.  Factors that are all 1
+    change nothing.  A pyramid is the same picture listed several times: Reduced([im] * 4, [1, 2, 4, 8])."""
+
+    def __init__(self, images, factor):
+        self.images = images
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        if not isinstance(images, FloatPixels):
+            self.images = inner
+        n = len(inner)
+        fs = list(factor) if isinstance(factor, (list, tuple, np.ndarray)) else [factor] * n
+        if len(fs) != n:
+            raise SjpegError(f"Reduced: {len(fs)} factors for {n} pictures: one factor, or one per picture")
+        for k, f in enumerate(fs):
+            if not isinstance(f, (int, np.integer)) or f < 1 or f > REDUCE_MAX:
+                raise SjpegError(f"Reduced: picture {k}: factor {f!r} is not an int in 1..{REDUCE_MAX}")
+        self.factors = [int(f) for f in fs]
+
+
+def _reduced(images):
+    """(the images of a call without their Reduced wrapper, the factors or None when there is nothing to reduce)"""
+    if not isinstance(images, Reduced):
+        return images, None
+    return images.images, (images.factors if any(f != 1 for f in images.factors) else None)
+
+
+def reduced_size(w, h, factor):
+    """sjpeg_hip_reduced_size: (w', h') of a w x h picture reduced by factor (1..8)."""
+    rw, rh = C.c_int(0), C.c_int(0)
+    if lib().sjpeg_hip_reduced_size(int(w), int(h), int(factor), C.byref(rw), C.byref(rh)) != 0:
+        raise SjpegError("sjpeg_hip_reduced_size: " + lib().sjpeg_hip_last_error().decode())
+    return int(rw.value), int(rh.value)
+
+
 class RaggedFrame(C.Structure):
     """struct sjpeg_hip_ragged_frame (include/sjpeg_hip.h): one picture of a ragged batch."""
     _fields_ = [("plane", C.c_void_p * 3), ("row_stride", C.c_int64 * 3), ("width", C.c_int32),
@@ -416,6 +461,19 @@ def lib() -> C.CDLL:
     full = list(L.sjpeg_hip_encode_ragged_full_packed_src.argtypes)
     L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes = full[:5] + [C.c_void_p, C.c_int] + full[5:]
     L.sjpeg_hip_encode_ragged_full_meta_packed_src.restype = C.c_int
+    L.sjpeg_hip_reduced_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sjpeg_hip_reduced_size.restype = C.c_int
+    L.sjpeg_hip_reduce_ragged_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p]
+    L.sjpeg_hip_reduce_ragged_bytes.restype = C.c_size_t
+    L.sjpeg_hip_reduce_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.POINTER(RaggedFrame), C.POINTER(C.c_int), C.c_void_p]
+    L.sjpeg_hip_reduce_ragged_src.restype = C.c_int
+    full = list(L.sjpeg_hip_encode_ragged_full_meta_src.argtypes)
+    L.sjpeg_hip_encode_ragged_reduced_src.argtypes = full[:5] + [C.c_void_p] + full[5:]
+    L.sjpeg_hip_encode_ragged_reduced_src.restype = C.c_int
+    full = list(L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes = full[:5] + [C.c_void_p] + full[5:]
+    L.sjpeg_hip_encode_ragged_reduced_packed_src.restype = C.c_int
     _lib = L
     return L
 
@@ -456,6 +514,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_trellis_src", "sjpeg_hip_encode_ragged_packed_src",
     "sjpeg_hip_encode_ragged_full_src", "sjpeg_hip_encode_ragged_full_packed_src", "sjpeg_hip_engine_search_stats",
     "sjpeg_hip_metadata_size", "sjpeg_hip_encode_ragged_full_meta_src", "sjpeg_hip_encode_ragged_full_meta_packed_src",
+    "sjpeg_hip_reduced_size", "sjpeg_hip_reduce_ragged_bytes", "sjpeg_hip_reduce_ragged_src",
+    "sjpeg_hip_encode_ragged_reduced_src", "sjpeg_hip_encode_ragged_reduced_packed_src",
 ]
 
 
@@ -1499,6 +1559,111 @@ class Engine:
         n = len(dims)
         return out, meta[:n], meta[n:], modes, q_out, v_out
 
+    def reduce_ragged(self, fmt, planes_per_frame, dims, factors, out=None):
+        """sjpeg_hip_reduce_ragged_src: the pictures of a ragged batch (fmt, planes_per_frame, dims as encode_ragged; any
+        RGB-like or gray format) reduced by factors[k] (1..8) in one launch.  Returns (reduced_fmt, pictures, buf):
+        SRC_RGB with uint8 CUDA tensors [h', w', 3], or SRC_GRAY with [h', w'] -- views of the one buffer buf (rows
+        padded to a multiple of 4 bytes, pictures at multiples of 16), which any ragged entry takes as its planes.  out:
+        a uint8 CUDA tensor to reduce into (at a multiple of 16, at least the bytes needed).  Asynchronous on the current
+        torch stream."""
+        import torch
+        n = len(dims)
+        if len(factors) != n:
+            raise SjpegError("reduce_ragged: one factor per frame")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        fac = (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
+        need = lib().sjpeg_hip_reduce_ragged_bytes(fmt, n, frames, C.cast(fac, C.c_void_p))
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise SjpegError("reduce_ragged: out must be a contiguous uint8 CUDA tensor")
+        reduced = (RaggedFrame * n)()
+        rfmt = C.c_int(-1)
+        # (a batch the library refuses has need == 0: the call below says why)
+        self._chk(lib().sjpeg_hip_reduce_ragged_src(self._h, fmt, n, frames, C.cast(fac, C.c_void_p), out.data_ptr(),
+                                                    int(out.numel()) if need else 0, reduced, C.byref(rfmt), self._stream()),
+                  "sjpeg_hip_reduce_ragged_src")
+        pics = []
+        for r in reduced:
+            # (as_strided counts from the start of the storage: `out` may be a slice of a larger tensor)
+            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
+            if rfmt.value == SRC_RGB:
+                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
+            else:
+                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
+        return int(rfmt.value), pics, out
+
+    def encode_ragged_reduced(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
+                              q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
+                              offsets=None, sizes=None, metadata=None):
+        """sjpeg_hip_encode_ragged_reduced_src: encode_ragged_full of the pictures reduced by factors[k] (1..8; None:
+        all 1) inside the call -- the reduce kernel into engine memory, then one inner call over the reduced pictures.
+        Frame k's bytes are those encode_ragged_full makes of the reduced uint8 picture (Engine.reduce_ragged returns
+        it).  dims are the SOURCE sizes; the default capacities are the bounds of the reduced ones.  Returns
+        (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
+            raise SjpegError("encode_ragged_reduced: one entry of planes_per_frame, dims and factors per frame, at least one frame")
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_reduced", n, metadata)
+        fac = None if factors is None else (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
+        if capacities is None:
+            capacities = [frame_bound(-(-w // max(min(int(f), REDUCE_MAX), 1)), -(-h // max(min(int(f), REDUCE_MAX), 1)), bound_mode,
+                                      2048 + msizes[k])
+                          for k, ((w, h), f) in enumerate(zip(dims, factors if factors is not None else [1] * n))]
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_reduced", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_reduced_src(
+            self._h, fmt, n, frames, C.byref(params), None if fac is None else C.cast(fac, C.c_void_p),
+            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), sizes.data_ptr(), modes,
+            q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_reduced_src")
+        return out, sizes, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+
+    def encode_ragged_reduced_packed(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
+                                     q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                                     packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_reduced_packed_src: encode_ragged_reduced into ONE packed buffer, with the arguments
+        and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        import torch
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
+            raise SjpegError("encode_ragged_reduced_packed: one entry of planes_per_frame, dims and factors per frame, at least one frame")
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_reduced_packed", n, metadata)
+        fac = None if factors is None else (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
+        if capacities is None:
+            capacities = [frame_bound(-(-w // max(min(int(f), REDUCE_MAX), 1)), -(-h // max(min(int(f), REDUCE_MAX), 1)), bound_mode,
+                                      2048 + msizes[k])
+                          for k, ((w, h), f) in enumerate(zip(dims, factors if factors is not None else [1] * n))]
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_reduced_packed", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
+        dev = _ragged_device(planes_per_frame)
+        if packed_capacity is None:
+            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
+        packed_capacity = int(packed_capacity)
+        if out is None:
+            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+            raise SjpegError("encode_ragged_reduced_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_reduced_packed_src(
+            self._h, fmt, n, frames, C.byref(params), None if fac is None else C.cast(fac, C.c_void_p),
+            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), packed_capacity,
+            meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
+            "sjpeg_hip_encode_ragged_reduced_packed_src")
+        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
         _full_packed call -- [most passes any frame ran, measurement launches, host waits, frames whose stream replays
@@ -1727,6 +1892,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     the last parameter: pass layout by keyword.)"""
     import torch
     chw = _check_layout("encode_images", layout)
+    images, factors = _reduced(images)
     images, fp = _float_pixels("encode_images", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
@@ -1785,6 +1951,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
+    if factors is not None:
+        # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
+        with torch.cuda.device(dev):
+            fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
+        planes = [[p] for p in reduced_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -1899,6 +2071,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
                         tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed, metadata=None):
     import torch
     chw = _check_layout("encode_images_full", layout)
+    images, factors = _reduced(images)
     images, fp = _float_pixels("encode_images_full", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
@@ -1941,6 +2114,12 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
+    if factors is not None:
+        # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
+        with torch.cuda.device(dev):
+            fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
+        planes = [[p] for p in reduced_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -1987,6 +2166,9 @@ def riskiness_images(images, engine=None, layout="hwc"):
     takes them."""
     import torch
     chw = _check_layout("riskiness_images", layout)
+    if isinstance(images, Reduced):
+        raise SjpegError("riskiness_images: Reduced pictures are not taken: reduce first -- "
+                         "riskiness_images(reduce_images(images, factor)) -- the verdict is that of the reduced picture")
     images, fp = _float_pixels("riskiness_images", images, chw)
     images = list(images)
     if not images:
@@ -2011,6 +2193,42 @@ def riskiness_images(images, engine=None, layout="hwc"):
     with torch.cuda.device(dev):
         sums = eng.riskiness_ragged(SRC_RGB, planes, dims).cpu().numpy()
     return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
+
+
+def reduce_images(images, factor, engine=None, layout="hwc"):
+    """The reduced uint8 pictures Reduced(images, factor) codes, as views of ONE device buffer, from one launch of the
+    reduce kernel: images as encode_images takes them (layout="hwc": CUDA uint8 tensors [H_k, W_k, 3]; "chw": channel-first
+    uint8 tensors or a FloatPixels), factor one int in 1..8 or one per picture.  Returns uint8 CUDA tensors
+    [h'_k, w'_k, 3] (layout="chw": [3, h'_k, w'_k], channels-last in memory, which the layout="chw" calls take as they
+    are; gray FloatPixels: [h'_k, w'_k]).  Rows are padded to a multiple of 4 bytes: the views are not contiguous.  The
+    pixel transform of a FloatPixels is set on the engine (it stays set)."""
+    import torch
+    chw = _check_layout("reduce_images", layout)
+    red = Reduced(images, factor)
+    images, fp = _float_pixels("reduce_images", red.images, chw)
+    images = list(images)
+    if not images:
+        raise SjpegError("reduce_images: no images")
+    if chw:
+        planes, dims, dev, fmt = _chw_planes("reduce_images", images, fp)
+    else:
+        for k, im in enumerate(images):
+            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
+                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+                raise SjpegError(f"reduce_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+            if im.device != images[0].device:
+                raise SjpegError(f"reduce_images: image {k} is on {im.device}, image 0 on {images[0].device}")
+        dev, fmt = images[0].device, SRC_RGB
+        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    with torch.cuda.device(dev):
+        rfmt, pics, _ = eng.reduce_ragged(fmt, planes, dims, red.factors)
+        if engine is None:
+            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
+    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
 
 
 _packed_stats = {"calls": 0, "retries": 0}

@@ -91,6 +91,41 @@ int sharp_ragged_run(int format, const float* pscale, const float* pbias, int nf
                      uint8_t* const* d_u, uint8_t* const* d_v, void* d_workspace, size_t workspace_size,
                      hipStream_t st, UploadFn up, void* up_ctx, std::string* err);
 
+// ---- ragged reduction (sjpeg_hip_reduce_ragged_src, reduce.hip): one descriptor per frame; a workgroup finds its frame
+// by a binary search over tile_base.  A tile is 256 consecutive GROUPS of the frame in row-major order, a group four
+// reduced pixels side by side (12 bytes of interleaved RGB, or 4 of gray: whole dwords of the reduced row).
+struct ReduceFrame {
+  const uint8_t* src;                    // plane 0, row 0
+  long long row_stride;                  // may be negative
+  long long off[3];                      // where R, G and B (gray: the value, thrice) lie from src (layout_rgb_offsets)
+  uint8_t* dst;                          // the reduced picture: a multiple of 16
+  int W, H, w2, h2;                      // the source's and the reduced picture's size
+  int s, groups;                         // the factor; groups a reduced row: (w2 + 3) / 4
+  unsigned dst_stride, tile_base;        // bytes between reduced rows; the frame's first workgroup in the flat grid
+};
+// A batch's reduction planned on the host, before any device work: the descriptors (dst: the picture's place from the
+// buffer's start), the reduced format (SJPEG_HIP_SRC_RGB or _GRAY), the bytes the pictures take and the grid.
+struct ReducePlan {
+  int format = 0, reduced_format = 0;
+  std::vector<ReduceFrame> frames;
+  size_t bytes = 0;
+  unsigned tiles = 0;
+};
+// Checks the format (an RGB-like or gray one) and the factors (1..8 each; NULL: all 1), then plans; the message names
+// the frame.  The frames' planes and strides are the caller's to check (ragged_check).
+int reduce_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const uint8_t* factors,
+                ReducePlan* plan);
+// the reduced pictures as frames of plan.reduced_format at `base` (out_offset / out_capacity: the source frames')
+void reduce_plan_frames(const ReducePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
+// the flat grid over d_frames[nframes] (device memory, dst already absolute)
+int reduce_ragged_launch(int format, const float* pscale, const float* pbias, const ReduceFrame* d_frames, int nframes, unsigned tiles,
+                         hipStream_t st);
+// The engine's half (scan_engine.hip): the call ordered behind the engine's earlier work, the descriptors uploaded, the
+// kernel launched on `stream`.  d_reduced == NULL: into the engine's own memory for reduced pictures -- one allocation
+// of plan.bytes, apart from the arena of the sharp planes, counted by sjpeg_hip_engine_scratch_bytes and released by
+// sjpeg_hip_engine_trim; *base says where.
+int engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base, void* stream);
+
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
 // out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's

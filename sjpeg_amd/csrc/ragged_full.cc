@@ -601,13 +601,9 @@ int search_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfr
   }
 }
 
-// sjpeg_hip_encode_ragged_full_src / _full_packed_src
-int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-              const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
-              void* stream, const sjpeg_internal::PackedSink* sink) {
-  const sjpeg_hip_ragged_params& P = *params;
+// the checks of sjpeg_hip_encode_ragged_full_src / _full_packed_src: host only, the engine is not touched
+int full_checks(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_ragged_params& P) {
   const int yuv_mode = P.yuv_mode, method = P.method;
-  // ---- the checks, all of them before the engine is touched
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return set_error(SJPEG_HIP_EINVAL, who + ": params->yuv_mode outside 0..4 (SjpegYUVMode)");
   if (method < 0 || method > 8) return set_error(SJPEG_HIP_EINVAL, who + ": params->method outside 0..8");
@@ -630,7 +626,18 @@ int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfram
       return set_error(SJPEG_HIP_EINVAL, who + ": search[" + std::to_string(k) + "] (frame " + std::to_string(k) + "): the target is not finite");
     }
   }
-  if (int rc = sjpeg_internal::ragged_check(who, format, by_mode ? SJPEG_HIP_YUV444 : yuv_mode, nframes, frames)) return rc;
+  return sjpeg_internal::ragged_check(who, format, by_mode ? SJPEG_HIP_YUV444 : yuv_mode, nframes, frames);
+}
+
+// sjpeg_hip_encode_ragged_full_src / _full_packed_src
+int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+              const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+              void* stream, const sjpeg_internal::PackedSink* sink) {
+  const sjpeg_hip_ragged_params& P = *params;
+  const int yuv_mode = P.yuv_mode, method = P.method;
+  // ---- the checks, all of them before the engine is touched
+  if (int rc = full_checks(who, format, nframes, frames, P)) return rc;
+  const bool by_mode = yuv_mode == kYuvAuto || yuv_mode == kYuvSharp;
   if (sink != nullptr) { if (int rc = sjpeg_internal::engine_pack_begin(e, stream)) return rc; }
   uint64_t* const stats = sjpeg_internal::engine_full_stats(e);
   memset(stats, 0, 6 * sizeof(uint64_t));
@@ -836,6 +843,102 @@ int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* e, int format
   } catch (...) {
     return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
   }
+}
+
+// ---- the _full_meta_ calls on pictures reduced inside the call (reduce.hip): thumbnails and pyramid levels ----
+// factors NULL or all 1: exactly the _full_meta_ call on the caller's frames.  Otherwise every check first, host only;
+// then the reduce kernel into the engine's own memory for reduced pictures and ONE inner flow over them, read as
+// SJPEG_HIP_SRC_RGB or _GRAY -- one group, one format: frame order, packed layout, modes, q_out, value_out, the host
+// waits and the search counters are that flow's.
+static bool all_ones(const uint8_t* factors, int nframes) {
+  for (int f = 0; factors != nullptr && f < nframes; ++f) if (factors[f] != 1) return false;
+  return true;
+}
+
+static int reduced_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                        const sjpeg_hip_ragged_params* params, const uint8_t* factors, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                        void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
+                        const sjpeg_internal::PackedSink* sink) {
+  try {
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    sjpeg_internal::ReducePlan plan;
+    if (int rc = sjpeg_internal::reduce_plan(who, format, nframes, frames, factors, &plan)) return rc;
+    const int y = params->yuv_mode;
+    if (L->implied != 0 && y != L->implied) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format (gray pictures are coded 4:0:0 only)");
+    }
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    // (the inner flow's own checks on the reduced pictures, standing at a placeholder address until there is memory)
+    std::vector<sjpeg_hip_ragged_frame> reduced(static_cast<size_t>(nframes));
+    sjpeg_internal::reduce_plan_frames(plan, frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), reduced.data());
+    if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : reduced) f.out_offset = 0;   // (ignored: the placement kernel says where a frame goes)
+    if (int rc = full_checks(who, plan.reduced_format, nframes, reduced.data(), *params)) return rc;
+    sjpeg_internal::MetaCtx ctx;
+    if (meta != nullptr) { if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc; }
+    // ---- device work
+    uint8_t* base = nullptr;
+    if (int rc = sjpeg_internal::engine_reduce(e, who, plan, nullptr, &base, stream)) return rc;
+    sjpeg_internal::reduce_plan_frames(plan, frames, base, reduced.data());
+    if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : reduced) f.out_offset = 0;
+    const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
+    return full_flow(who, e, plan.reduced_format, nframes, reduced.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_reduced_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                        const sjpeg_hip_ragged_params* params, const uint8_t* factors,
+                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                        int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_reduced_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  for (int f = 0; factors != nullptr && f < nframes; ++f) {
+    if (factors[f] < 1 || factors[f] > SJPEG_HIP_REDUCE_MAX) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": factor " + std::to_string(factors[f]) + " is not one of 1..8");
+    }
+  }
+  if (all_ones(factors, nframes)) {
+    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                                                 value_out, stream);
+  }
+  return reduced_flow(who, e, format, nframes, frames, params, factors, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+                      stream, nullptr);
+}
+
+int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                               const sjpeg_hip_ragged_params* params, const uint8_t* factors,
+                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                               float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_reduced_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  for (int f = 0; factors != nullptr && f < nframes; ++f) {
+    if (factors[f] < 1 || factors[f] > SJPEG_HIP_REDUCE_MAX) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": factor " + std::to_string(factors[f]) + " is not one of 1..8");
+    }
+  }
+  if (all_ones(factors, nframes)) {
+    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
+                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
+  }
+  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+  return reduced_flow(who, e, format, nframes, frames, params, factors, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
+                      stream, &sink);
 }
 
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {

@@ -239,6 +239,11 @@ struct sjpeg_hip_engine {
   int risk_generation = -1;
   DevBuf<uint4> auto_buf;
   DevBuf<uint4> sharp_arena;
+  // reduced pictures (sjpeg_hip_encode_ragged_reduced_src): the uint8 pictures the reduce kernel makes for the inner
+  // encode, ONE allocation of their own -- not the arena above, which the inner flow lays its sharp planes and kept
+  // blocks out in --, and the kernel's frame descriptors.  A later call writes them behind everything the earlier one
+  // queued: the engine's ordering, as for every scratch buffer.
+  DevBuf<uint4> reduced, reduce_desc;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;
@@ -683,6 +688,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
+  e->reduced.release(); e->reduce_desc.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -708,6 +714,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
+  e->reduced.release(); e->reduce_desc.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -851,7 +858,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
          b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) + b(e->hdr_stage) +
-         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor);
+         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor) + b(e->reduced) + b(e->reduce_desc);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -3526,7 +3533,63 @@ int sjpeg_internal::engine_pack_begin(sjpeg_hip_engine* e, void* stream) {
   return 0;
 }
 
+// ---- ragged reduction (reduce.hip): the engine's half
+int sjpeg_internal::engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base,
+                                  void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ragged_ordered(e, st)) return rc;
+  if (d_reduced == nullptr) {
+    if (e->reduced.ensure(plan.bytes / 16 + 1) != 0) {
+      return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(plan.bytes) + " bytes of reduced pictures");
+    }
+    d_reduced = reinterpret_cast<uint8_t*>(e->reduced.p);
+  }
+  if (base != nullptr) *base = d_reduced;
+  std::vector<ReduceFrame> desc = plan.frames;
+  for (ReduceFrame& d : desc) d.dst = d_reduced + reinterpret_cast<uintptr_t>(d.dst);
+  const size_t desc_bytes = sizeof(ReduceFrame) * desc.size();
+  if (int rc = e->reduce_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (int rc = upload(e, e->reduce_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (reduce_ragged_launch(plan.format, e->pscale, e->pbias, reinterpret_cast<const ReduceFrame*>(e->reduce_desc.p),
+                           static_cast<int>(desc.size()), plan.tiles, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, who + ": reduce_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
+}
+
 extern "C" {
+
+// Pictures of a ragged batch reduced by their factors into the caller's buffer (sjpeg_hip.h): one launch of reduce.hip's
+// kernel.  Every check comes before `e` is touched.
+int sjpeg_hip_reduce_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const uint8_t* factors, void* d_reduced, size_t reduced_bytes,
+                                sjpeg_hip_ragged_frame* reduced_frames, int* reduced_format, void* stream) {
+  static const std::string who = "sjpeg_hip_reduce_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || factors == nullptr || d_reduced == nullptr || reduced_frames == nullptr || reduced_format == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, factors, d_reduced, reduced_frames or reduced_format == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_reduced) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_reduced must be a multiple of 16");
+  try {
+    sjpeg_internal::ReducePlan plan;
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    if (int rc = sjpeg_internal::reduce_plan(who, format, nframes, frames, factors, &plan)) return rc;
+    if (reduced_bytes < plan.bytes) {
+      return fail(SJPEG_HIP_EINVAL, who + ": reduced_bytes " + std::to_string(reduced_bytes) + " is below the " + std::to_string(plan.bytes) +
+                                        " bytes the reduced pictures take (sjpeg_hip_reduce_ragged_bytes)");
+    }
+    if (int rc = sjpeg_internal::engine_reduce(e, who, plan, static_cast<uint8_t*>(d_reduced), nullptr, stream)) return rc;
+    sjpeg_internal::reduce_plan_frames(plan, frames, static_cast<uint8_t*>(d_reduced), reduced_frames);
+    *reduced_format = plan.reduced_format;
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
 
 // ---- exchange step of the multi-device batch path: the coded frames of one call, back to back ----
 // (BASELINE.json config #4; the reference is single-threaded and has no counterpart.)  One
