@@ -49,7 +49,7 @@ def call_key(name, args, kwargs):
 
 
 # the Ref methods the tests call, and the two entry points of its .lib they call directly
-METHODS = ("encode", "encode_param", "encode_src", "encode_search", "get_block", "fdct")
+METHODS = ("encode", "encode_param", "encode_src", "encode_search", "get_block", "fdct", "riskiness", "compress")
 
 
 def _estimate_quality_key(ptr, chroma):
@@ -75,7 +75,8 @@ class Answer:
 
 
 def describe(v):
-    """What is stored of an answer: ints as they are, bytes / arrays by size (dtype, shape) and MD5."""
+    """What is stored of an answer: ints as they are, bytes / arrays by size (dtype, shape) and MD5, a riskiness
+    answer (SjpegYUVMode, risk) as the mode and the risk's float.hex()."""
     if v is None:
         return {"kind": "none"}
     if isinstance(v, (bytes, bytearray)):
@@ -85,6 +86,8 @@ def describe(v):
         return {"kind": "array", "dtype": a.dtype.str, "shape": list(a.shape), "md5": hashlib.md5(a.tobytes()).hexdigest()}
     if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
         return {"kind": "int", "value": int(v)}
+    if isinstance(v, tuple) and len(v) == 2 and isinstance(v[0], (int, np.integer)) and isinstance(v[1], float):
+        return {"kind": "riskiness", "mode": int(v[0]), "risk": float(v[1]).hex()}
     return {"kind": "other", "repr": repr(v)}
 
 
@@ -114,6 +117,8 @@ class Replay:
             return None
         if rec["kind"] == "int":
             return rec["value"]
+        if rec["kind"] == "riskiness":
+            return int(rec["mode"]), float.fromhex(rec["risk"])      # (the tuple refso.Ref.riskiness returns)
         return Answer(rec)
 
     def __getattr__(self, name):
