@@ -2,10 +2,15 @@
 // becomes the byte the encoder sees.  The contract (sjpeg_hip.h), scale and bias being those of the sample's channel:
 //   t  = fmaf((float)x, scale, bias)                 ONE fp32 rounding; (float)x is exact for half and bfloat16
 //   u8 = isnan(t) ? 0 : (uint8) rint(min(max(t, 0), 255))          round half to even; +-inf saturate
-// On gfx950 that is v_fma_f32 (v_fma_mix_f32 straight from a half) and v_cvt_pk_u8_f32, which rounds to nearest even,
-// saturates and turns NaN into 0 while it puts the byte into its place in a dword (tests/test_float_pixels.py holds
-// it to the ties).  The scan kernels' loader (scan_device.h), the ragged riskiness and the ragged sharp conversion
-// all convert through these helpers.
+// On gfx950 that is v_fma_f32 (v_fma_mix_f32 straight from a half) and v_cvt_pk_u8_f32, which alone rounds to nearest
+// even, saturates and turns NaN into 0 while it puts the byte into its place in a dword (seen on an MI355X: no
+// v_rndne_f32 and no NaN select is needed in front of it; subnormal inputs are kept).  What holds the helpers
+// to the contract: tests/float_contract.py computes it exactly (the product and sum unrounded, then ONE rounding to
+// fp32) and tests/test_float_contract.py compares every helper with it bit for bit -- on every float16 and bfloat16
+// bit pattern and 65 536 float32 ones, under transforms on which two roundings, flushed subnormals, ties away from
+// zero, truncation and a NaN that is not 0 each change bytes (the runs: profiles/HISTORY.md, "The float pixel
+// transform held to its contract").  The scan kernels' loader (scan_device.h),
+// the ragged riskiness, the ragged sharp conversion and the reduce kernel all convert through these helpers.
 #ifndef SJPEG_AMD_PIXEL_ELEM_H_
 #define SJPEG_AMD_PIXEL_ELEM_H_
 
