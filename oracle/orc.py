@@ -100,6 +100,10 @@ class Oracle:
         lib.orc_build_optimal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.orc_adapt_quant.argtypes = [C.c_void_p, C.c_int, C.POINTER(Quantizer), C.c_int, C.c_int,
                                         C.c_int]
+        lib.orc_build_huffman.restype = C.c_int
+        lib.orc_build_huffman.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.orc_trellis_block.restype = C.c_int
+        lib.orc_trellis_block.argtypes = [C.c_void_p, C.POINTER(Quantizer), C.c_void_p, C.c_void_p]
 
     def finalize_quant(self, quant64, min_quant64=None, q_bias=0x78) -> Quantizer:
         q = Quantizer()
@@ -243,6 +247,24 @@ class Oracle:
         syms = np.zeros(256, np.uint8)
         n = self.lib.orc_build_optimal(f.ctypes.data, size, bits.ctypes.data, syms.ctypes.data)
         return bits, syms[:n].copy(), n
+
+    def build_huffman(self, bits, syms, size):
+        """canonical codes (code << 16 | length) of a JPEG table description; `size` entries, 0 = no code"""
+        b = np.ascontiguousarray(bits, np.uint8)
+        s = np.ascontiguousarray(syms, np.uint8)
+        assert b.size == 16 and int(b.sum()) == s.size
+        tab = np.zeros(size, np.uint32)
+        self.lib.orc_build_huffman(b.ctypes.data, s.ctypes.data, tab.ctypes.data)
+        return tab
+
+    def trellis_block(self, coeffs64, quantizer: Quantizer, ac_codes256):
+        """orc_trellis_block: the trellis-quantized zig-zag levels of one block of DCT coefficients (natural order, as
+        fdct() leaves them), its rate priced with ac_codes256 (code << 16 | length)"""
+        c = np.ascontiguousarray(coeffs64, np.int16).reshape(64)
+        ac = np.ascontiguousarray(ac_codes256, np.uint32).reshape(256)
+        zz = np.zeros(64, np.int16)
+        self.lib.orc_trellis_block(c.ctypes.data, C.byref(quantizer), ac.ctypes.data, zz.ctypes.data)
+        return zz
 
     def adapt_quant(self, hist, nb_comps, quant, min_quant=None, q_bias=0x78, dmax_luma=12,
                     dmax_chroma=1):

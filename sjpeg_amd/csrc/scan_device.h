@@ -201,7 +201,7 @@ template <> struct Lds<false> {
   static constexpr int kOffHist = kOffWin + 4400;                // u32 [32]: the sort's bins
   static constexpr int kOffList = kOffWin + 4672;                // u16 [1024]: block | quarter << 8
   static constexpr int kListBytes = 2048;
-  static constexpr int kOffDcw = kOffWin + 6720;                 // u32 [256]: DC code words (length << 24 | bits)
+  static constexpr int kOffDcw = kOffWin + 6720;                 // u32 [256]: DC code words (length << 27 | bits)
   static constexpr int kOffAc = kOffWin + kWinWords * 4 + 16;    // +1 spare word (16 B keeps alignment)
   static constexpr int kOffAcm = kOffAc + 2 * 256 * 4;           // uint32[2][16][10]: merged code words of the lean walk
   static constexpr int kOffZrl = kOffAcm + 2 * 160 * 4;          // uint4[2][4]: ZRL patterns

@@ -1109,14 +1109,16 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
       pred = (e & 0x8000u) ? -mag : mag;
     }
   }
-  uint32_t dc_word = 0;                            // dc_len << 24 | dc_bits (<= 22); 0 = emits nothing
+  // (len + n) << 27 | code << n | suffix, 0 = emits nothing: a baseline table may give a DC size a code of 16 bits, and a
+  // size of 11 puts 11 more behind it -- 27 bits of payload, and a length of at most 27 in the five bits above them
+  uint32_t dc_word = 0;
   if (emits) {
     const int diff = dc_val - pred;
     const int ad = diff < 0 ? -diff : diff;
     const int n = 32 - __clz(ad);                 // 0 for diff == 0 (clz(0) == 32)
     const uint32_t suffix = static_cast<uint32_t>(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u);
     const uint32_t code = ldc[tbl * 12 + n];
-    dc_word = (((code & 0xffu) + n) << 24) | ((code >> 16) << n) | suffix;
+    dc_word = (((code & 0xffu) + n) << 27) | ((code >> 16) << n) | suffix;
   }
   // What a part's walk needs to know of its block, one word per quarter q in the slot's tail: the quarter's
   // non-zero mask (bits 0..15), the run in front of its first symbol, ZRLs included (bits 16..21; the walk splits
@@ -1125,7 +1127,7 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
   // would work the same out of the two 32-bit masks with a dozen selects.  The word is read by the ONE thread
   // that walks the part, which then stores the part's bit length over it: the lengths need no array of their
   // own, and a quarter without a part keeps its mask -- zero -- as its length.  The DC code word
-  // (length << 24 | bits) goes to an array by block.
+  // (length << 27 | bits) goes to an array by block.
   if (KIND == kKindEncode) {
     const uint32_t p1 = 32u - static_cast<uint32_t>(__clz(nzq[0] | 1u));            // position after the last non-zero below quarter 1 (1 = none)
     const uint32_t p2 = 32u - static_cast<uint32_t>(__clz(nz_lo | 1u));
@@ -1150,7 +1152,7 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
     }
   } else {
     // (the statistics kind counts a part's symbols out of the two whole masks)
-    if (has_slot) *reinterpret_cast<uint4*>(tail) = make_uint4(nz_lo, nz_hi, dc_word | (static_cast<uint32_t>(tbl) << 30), 0u);
+    if (has_slot) *reinterpret_cast<uint4*>(tail) = make_uint4(nz_lo, nz_hi, 0u, 0u);
   }
 
   // kKindStats: [2][272] counters, 256 AC then 16 DC, in TWO copies picked by lane parity: the lanes of a
@@ -1331,7 +1333,7 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
       if (t >= 32u) { put_word(acc | (bits >> s5)); acc = P; } else { acc |= P; }
       fill = s5;
     };
-    if (q == 0u) append(dcword & 0xffffffu, (dcword >> 24) & 31u);
+    if (q == 0u) append(dcword & 0x07ffffffu, dcword >> 27);
     const uint32_t zrl = ac[0xf0];
     while (m) {
       const int i = __builtin_ctz(m);
@@ -1391,8 +1393,8 @@ __global__ __launch_bounds__(kScanThreads, (kHistoThree<MODE, KINDX, SRC> ? SJPE
     const uint32_t wp0 = slot_off + 32u * q;       // the quarter: 16 entries, then up to 8 words
     uint32_t wp = wp0;                             // byte offset of the next word
     if (q == 0u) {
-      fill = (dcword >> 24) & 31u;
-      acc = __builtin_amdgcn_alignbit(dcword & 0xffffffu, 0u, fill);   // DC bits << (32 - fill)
+      fill = dcword >> 27;
+      acc = __builtin_amdgcn_alignbit(dcword & 0x07ffffffu, 0u, fill);   // DC bits << (32 - fill)
     }
     // positions are local to the quarter from here on; the ZRLs of the first run are taken out of it
     // (only the first symbol of a part can have a run of 16 or more, and never in quarter 0)
