@@ -831,6 +831,68 @@ int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* engine, int for
                                                int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                void* stream);
 
+/* ---- pictures resized inside the ragged call: thumbnails that fit a box ----
+ * What a thumbnail service, a srcset or a dataset preview asks for is a fixed box -- "fit in 256 x 256", "320 wide" --,
+ * which the integer factors above do not give.  Frame f of W x H is resized to w' x h' = sizes[f], 1 <= w' <= W and
+ * 1 <= h' <= H: smaller or equal on each axis, never larger.  The result is the EXACT area average, in integers.  Along
+ * x both pictures lie on a grid of W * w' units: source column x covers [x * w', (x + 1) * w'), output column x' covers
+ * [x' * W, (x' + 1) * W), and
+ *     wx(x', x) = max(0, min((x + 1) * w', (x' + 1) * W) - max(x * w', x' * W))        (over x it sums to W)
+ *     wy(y', y)   the same with H and h'                                                (over y it sums to H)
+ *     S   = the sum over y of wy(y', y) * the sum over x of wx(x', x) * b(x, y, c)      (64 bits: S <= 255 W H < 2^40)
+ *     out = (2 S + W H) / (2 W H)                       integer division, exact: round half up
+ * where b is the byte the encoder sees at that source pixel today, as for the reduced pictures above: R, G, B of the
+ * byte formats, the float formats through the engine's pixel transform, the gray value of the gray formats.  The weights
+ * cover the source exactly, so no edge is replicated; an output sample reads at most ceil(W / w') + 1 columns of
+ * ceil(H / h') + 1 rows.  w' = W and h' = H is the identity; W = s w' and H = s h' is the reduction by s above, byte
+ * for byte.  THE CONTRACT: the JPEG of a resized frame is byte for byte what the same call makes of the uint8 picture so
+ * defined handed over as SJPEG_HIP_SRC_RGB (the gray formats: SJPEG_HIP_SRC_GRAY, yuv_mode 4:0:0 only).  Formats, strides,
+ * alignment and the elements read: as for the reduced pictures; the YUV-plane formats are not resized (SJPEG_HIP_EINVAL,
+ * the message names the format).
+ *
+ * sjpeg_hip_fit_size (host only, integers): the size of a W x H picture fitted into a box bw x bh (each 1..65535),
+ *   keeping its shape: (W, H) when W <= bw and H <= bh -- never larger --; else, when W * bh >= H * bw, w' = bw and
+ *   h' = max(1, (H * bw + W / 2) / W); else h' = bh and w' = max(1, (W * bh + H / 2) / H).  SJPEG_HIP_EINVAL for
+ *   dimensions or a box outside 1..65535.
+ * sjpeg_hip_resize_ragged_bytes (host only): the bytes the resized pictures of a batch take, 0 on bad arguments
+ *   (sizes: host int32[nframes][2] = (w', h'); NULL: every frame at its own size).  THE LAYOUT is that of the reduced
+ *   pictures: rows padded to whole dwords, every picture at a multiple of 16, frame after frame.
+ * sjpeg_hip_resize_ragged_src: ONE launch over the batch's tiles into d_resized (a multiple of 16, resized_bytes behind
+ *   it), with the arguments, the ordering, the pipelined-mode behaviour and the outputs of sjpeg_hip_reduce_ragged_src.
+ *   SJPEG_HIP_EINVAL before any device work, the frame named: a size below 1 or above the source's, a YUV-plane format,
+ *   resized_bytes below sjpeg_hip_resize_ragged_bytes(), and every frame check of sjpeg_hip_encode_ragged_src.
+ * sjpeg_hip_encode_ragged_resized_src / _resized_packed_src: the arguments and the output contract of
+ *   sjpeg_hip_encode_ragged_full_meta_src / _full_meta_packed_src, plus `sizes`.  sizes == NULL or every size its
+ *   frame's own: exactly that call on the caller's frames, any format; no copy, no kernel.  Otherwise every frame goes
+ *   through the resize kernel into engine memory -- the memory of the reduced pictures: counted by
+ *   sjpeg_hip_engine_scratch_bytes, released by sjpeg_hip_engine_trim, SJPEG_HIP_ENOMEM naming the bytes when it cannot
+ *   be had -- and ONE inner call codes the batch, as for the reduced calls (SJPEG_YUV_AUTO decides on the RESIZED
+ *   picture).  out_capacity is the caller's: sjpeg_hip_frame_bound(w', h', SJPEG_HIP_YUV444, 2048 + metadata) is always
+ *   enough.  SJPEG_HIP_EINVAL before any device work: the checks above, gray with a yuv_mode other than 4:0:0, NULL
+ *   arguments, and every check of the inner call. */
+int sjpeg_hip_fit_size(int width, int height, int box_width, int box_height, int* fitted_width, int* fitted_height);
+size_t sjpeg_hip_resize_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/);
+int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                const int32_t (*sizes)[2] /*host int32[nframes][2]*/, void* d_resized, size_t resized_bytes,
+                                sjpeg_hip_ragged_frame* resized_frames /*host out [nframes]*/, int* resized_format,
+                                void* stream);
+int sjpeg_hip_encode_ragged_resized_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                        const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                        void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                        int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                               const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                               const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                               const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                               void* d_packed, size_t packed_capacity,
+                                               uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                               int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                               void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

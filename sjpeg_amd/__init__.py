@@ -213,6 +213,8 @@ class Reduced:
     change nothing.  A pyramid is the same picture listed several times: Reduced([im] * 4, [1, 2, 4, 8])."""
 
     def __init__(self, images, factor):
+        if type(images).__name__ == "Resized":
+            raise SjpegError("Reduced: the pictures are Resized already: resize the pictures themselves, once")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -240,6 +242,86 @@ def reduced_size(w, h, factor):
     if lib().sjpeg_hip_reduced_size(int(w), int(h), int(factor), C.byref(rw), C.byref(rh)) != 0:
         raise SjpegError("sjpeg_hip_reduced_size: " + lib().sjpeg_hip_last_error().decode())
     return int(rw.value), int(rh.value)
+
+
+def fit_size(w, h, box):
+    """sjpeg_hip_fit_size: the size of a w x h picture fitted into box = (bw, bh) with its shape kept, in integers; a
+    picture that fits already keeps its size (never larger)."""
+    try:
+        bw, bh = box
+    except (TypeError, ValueError):
+        raise SjpegError(f"fit_size: box {box!r} is not a pair (width, height)")
+    fw, fh = C.c_int(0), C.c_int(0)
+    if lib().sjpeg_hip_fit_size(int(w), int(h), int(bw), int(bh), C.byref(fw), C.byref(fh)) != 0:
+        raise SjpegError("sjpeg_hip_fit_size: " + lib().sjpeg_hip_last_error().decode())
+    return int(fw.value), int(fh.value)
+
+
+def _picture_size(im, chw):
+    """(w, h) of a picture as a call with this layout reads its shape (gray float pictures: [H, W])"""
+    shape = tuple(getattr(im, "shape", ()))
+    if len(shape) == 2:
+        return int(shape[1]), int(shape[0])
+    if len(shape) != 3:
+        raise SjpegError("Resized.fit: a picture is a tensor [H, W, 3], [3, H, W] or [H, W]")
+    return (int(shape[2]), int(shape[1])) if chw else (int(shape[1]), int(shape[0]))
+
+
+class Resized:
+    """Pictures to be coded at a size of the caller's choice, each side at most the source's -- thumbnails that fit a
+    box, "320 wide", "the longer side 1024" -- wherever Reduced is taken: Resized(images, sizes) with `images` what
+    encode_images, compress_images, encode_images_full, encode_images_full_chw and encode_images_full_meta take and
+    `sizes` one (w, h) or one per picture.  Picture k becomes w x h: every sample the exact area average of the bytes
+    the encoder sees today (float pictures: after the pixel transform), in integers, rounded half up -- one launch of
+    the resize kernel for the whole batch, no torch call and no float intermediate per picture -- and its JPEG is byte
+    for byte that of the uint8 picture so defined (resize_images returns those).  Sizes equal to the pictures' own
+    change nothing.  Resized.fit(images, box) fits every picture into one box."""
+
+    def __init__(self, images, sizes):
+        if isinstance(images, (Reduced, Resized)):
+            raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
+        self.images = images
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        if not isinstance(images, FloatPixels):
+            self.images = inner
+        n = len(inner)
+        one = isinstance(sizes, (list, tuple, np.ndarray)) and len(sizes) == 2 and \
+            all(isinstance(v, (int, np.integer)) for v in sizes)
+        ss = [tuple(sizes)] * n if one else list(sizes) if isinstance(sizes, (list, tuple, np.ndarray)) else None
+        if ss is None or len(ss) != n:
+            raise SjpegError(f"Resized: sizes for {n} pictures: one (w, h), or one per picture")
+        self.sizes = []
+        for k, wh in enumerate(ss):
+            if not isinstance(wh, (list, tuple, np.ndarray)) or len(wh) != 2 or \
+                    not all(isinstance(v, (int, np.integer)) and 1 <= v <= 65535 for v in wh):
+                raise SjpegError(f"Resized: picture {k}: size {wh!r} is not a pair of ints (w, h) in 1..65535")
+            self.sizes.append((int(wh[0]), int(wh[1])))
+
+    @classmethod
+    def fit(cls, images, box, layout="hwc"):
+        """Resized(images, sizes) with every picture fitted into box = (bw, bh) by fit_size; layout says how the
+        pictures' shapes are read ("hwc": [H, W, 3]; "chw": [3, H, W]; a FloatPixels is read as "chw")."""
+        if isinstance(images, (Reduced, Resized)):
+            raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
+        chw = isinstance(images, FloatPixels) or _check_layout("Resized.fit", layout)
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        return cls(images, [fit_size(*_picture_size(im, chw), box) for im in inner])
+
+
+def _resized(images):
+    """(the images of a call without their Resized wrapper, the sizes or None for pictures that are not Resized)"""
+    if not isinstance(images, Resized):
+        return images, None
+    return images.images, images.sizes
+
+
+def _sizes_array(who, sizes):
+    """sizes as the C entries take them: int32 [n][2], values clamped into int32 (the library names a bad one)"""
+    try:
+        arr = np.asarray([[int(w), int(h)] for (w, h) in sizes], dtype=np.int64).reshape(len(sizes), 2)
+    except (TypeError, ValueError):
+        raise SjpegError(f"{who}: sizes are pairs of ints (w, h), one per frame")
+    return np.ascontiguousarray(np.clip(arr, -2**31, 2**31 - 1).astype(np.int32))
 
 
 class RaggedFrame(C.Structure):
@@ -474,6 +556,16 @@ def lib() -> C.CDLL:
     full = list(L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes)
     L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes = full[:5] + [C.c_void_p] + full[5:]
     L.sjpeg_hip_encode_ragged_reduced_packed_src.restype = C.c_int
+    L.sjpeg_hip_fit_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sjpeg_hip_fit_size.restype = C.c_int
+    L.sjpeg_hip_resize_ragged_bytes.argtypes = list(L.sjpeg_hip_reduce_ragged_bytes.argtypes)
+    L.sjpeg_hip_resize_ragged_bytes.restype = C.c_size_t
+    L.sjpeg_hip_resize_ragged_src.argtypes = list(L.sjpeg_hip_reduce_ragged_src.argtypes)
+    L.sjpeg_hip_resize_ragged_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_resized_src.argtypes = list(L.sjpeg_hip_encode_ragged_reduced_src.argtypes)
+    L.sjpeg_hip_encode_ragged_resized_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_resized_packed_src.restype = C.c_int
     _lib = L
     return L
 
@@ -516,6 +608,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_metadata_size", "sjpeg_hip_encode_ragged_full_meta_src", "sjpeg_hip_encode_ragged_full_meta_packed_src",
     "sjpeg_hip_reduced_size", "sjpeg_hip_reduce_ragged_bytes", "sjpeg_hip_reduce_ragged_src",
     "sjpeg_hip_encode_ragged_reduced_src", "sjpeg_hip_encode_ragged_reduced_packed_src",
+    "sjpeg_hip_fit_size", "sjpeg_hip_resize_ragged_bytes", "sjpeg_hip_resize_ragged_src",
+    "sjpeg_hip_encode_ragged_resized_src", "sjpeg_hip_encode_ragged_resized_packed_src",
 ]
 
 
@@ -1664,6 +1758,105 @@ class Engine:
             "sjpeg_hip_encode_ragged_reduced_packed_src")
         return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
 
+    def resize_ragged(self, fmt, planes_per_frame, dims, sizes, out=None):
+        """sjpeg_hip_resize_ragged_src: the pictures of a ragged batch (fmt, planes_per_frame, dims as encode_ragged; any
+        RGB-like or gray format) resized to sizes[k] = (w, h), each side 1..the source's, in one launch.  Returns
+        (resized_fmt, pictures, buf) as reduce_ragged does, with the same layout of buf; out as there."""
+        import torch
+        n = len(dims)
+        if len(sizes) != n:
+            raise SjpegError("resize_ragged: one size per frame")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        arr = _sizes_array("resize_ragged", sizes)
+        need = lib().sjpeg_hip_resize_ragged_bytes(fmt, n, frames, arr.ctypes.data)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise SjpegError("resize_ragged: out must be a contiguous uint8 CUDA tensor")
+        resized = (RaggedFrame * n)()
+        rfmt = C.c_int(-1)
+        # (a batch the library refuses has need == 0: the call below says why)
+        self._chk(lib().sjpeg_hip_resize_ragged_src(self._h, fmt, n, frames, arr.ctypes.data, out.data_ptr(),
+                                                    int(out.numel()) if need else 0, resized, C.byref(rfmt), self._stream()),
+                  "sjpeg_hip_resize_ragged_src")
+        pics = []
+        for r in resized:
+            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
+            if rfmt.value == SRC_RGB:
+                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
+            else:
+                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
+        return int(rfmt.value), pics, out
+
+    def encode_ragged_resized(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
+                              q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
+                              offsets=None, sizes_out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_resized_src: encode_ragged_full of the pictures resized to sizes[k] = (w, h) (None:
+        their own sizes) inside the call -- the resize kernel into engine memory, then one inner call over the resized
+        pictures.  Frame k's bytes are those encode_ragged_full makes of the resized uint8 picture (Engine.resize_ragged
+        returns it).  dims are the SOURCE sizes; the default capacities are the bounds of the resized ones; sizes_out:
+        the `sizes` tensor of encode_ragged_full.  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
+            raise SjpegError("encode_ragged_resized: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_resized", n, metadata)
+        arr = None if sizes is None else _sizes_array("encode_ragged_resized", sizes)
+        if capacities is None:
+            capacities = [frame_bound(min(max(int(w), 1), 65535), min(max(int(h), 1), 65535), bound_mode, 2048 + msizes[k])
+                          for k, (w, h) in enumerate(dims if arr is None else arr.tolist())]
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_resized", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
+        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes_out)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_resized_src(
+            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), sizes_out.data_ptr(), modes,
+            q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_resized_src")
+        return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+
+    def encode_ragged_resized_packed(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
+                                     q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                                     packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_resized_packed_src: encode_ragged_resized into ONE packed buffer, with the arguments
+        and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        import torch
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
+            raise SjpegError("encode_ragged_resized_packed: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_resized_packed", n, metadata)
+        arr = None if sizes is None else _sizes_array("encode_ragged_resized_packed", sizes)
+        if capacities is None:
+            capacities = [frame_bound(min(max(int(w), 1), 65535), min(max(int(h), 1), 65535), bound_mode, 2048 + msizes[k])
+                          for k, (w, h) in enumerate(dims if arr is None else arr.tolist())]
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_resized_packed", n, quant, min_quant,
+                                                                            search, bound_mode, capacities, dims)
+        dev = _ragged_device(planes_per_frame)
+        if packed_capacity is None:
+            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
+        packed_capacity = int(packed_capacity)
+        if out is None:
+            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+            raise SjpegError("encode_ragged_resized_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_resized_packed_src(
+            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), packed_capacity,
+            meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
+            "sjpeg_hip_encode_ragged_resized_packed_src")
+        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
         _full_packed call -- [most passes any frame ran, measurement launches, host waits, frames whose stream replays
@@ -1893,6 +2086,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     import torch
     chw = _check_layout("encode_images", layout)
     images, factors = _reduced(images)
+    images, new_sizes = _resized(images)
     images, fp = _float_pixels("encode_images", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images: give target_size or target_psnr, not both")
@@ -1957,6 +2151,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
         planes = [[p] for p in reduced_pictures]
         dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
+    if new_sizes is not None and new_sizes != dims:
+        # (Resized: as Reduced, through the resize kernel)
+        with torch.cuda.device(dev):
+            fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
+        planes = [[p] for p in resized_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -2072,6 +2272,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     import torch
     chw = _check_layout("encode_images_full", layout)
     images, factors = _reduced(images)
+    images, new_sizes = _resized(images)
     images, fp = _float_pixels("encode_images_full", images, chw)
     if target_size is not None and target_psnr is not None:
         raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
@@ -2120,6 +2321,12 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
             fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
         planes = [[p] for p in reduced_pictures]
         dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
+    if new_sizes is not None and new_sizes != dims:
+        # (Resized: as Reduced, through the resize kernel)
+        with torch.cuda.device(dev):
+            fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
+        planes = [[p] for p in resized_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
     search = None
     if target is not None:
         ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
@@ -2169,6 +2376,9 @@ def riskiness_images(images, engine=None, layout="hwc"):
     if isinstance(images, Reduced):
         raise SjpegError("riskiness_images: Reduced pictures are not taken: reduce first -- "
                          "riskiness_images(reduce_images(images, factor)) -- the verdict is that of the reduced picture")
+    if isinstance(images, Resized):
+        raise SjpegError("riskiness_images: Resized pictures are not taken: resize first -- "
+                         "riskiness_images(resize_images(images, sizes)) -- the verdict is that of the resized picture")
     images, fp = _float_pixels("riskiness_images", images, chw)
     images = list(images)
     if not images:
@@ -2226,6 +2436,42 @@ def reduce_images(images, factor, engine=None, layout="hwc"):
         eng.set_pixel_transform(fp.scale, fp.bias)
     with torch.cuda.device(dev):
         rfmt, pics, _ = eng.reduce_ragged(fmt, planes, dims, red.factors)
+        if engine is None:
+            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
+    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+
+
+def resize_images(images, sizes, engine=None, layout="hwc"):
+    """The resized uint8 pictures Resized(images, sizes) codes, as views of ONE device buffer, from one launch of the
+    resize kernel: images as encode_images takes them (layout="hwc": CUDA uint8 tensors [H_k, W_k, 3]; "chw":
+    channel-first uint8 tensors or a FloatPixels), sizes one (w, h) or one per picture.  Returns what reduce_images
+    returns: uint8 CUDA tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k], channels-last in memory; gray FloatPixels:
+    [h_k, w_k]), rows padded to a multiple of 4 bytes.  The pixel transform of a FloatPixels is set on the engine (it
+    stays set)."""
+    import torch
+    chw = _check_layout("resize_images", layout)
+    res = Resized(images, sizes)
+    images, fp = _float_pixels("resize_images", res.images, chw)
+    images = list(images)
+    if not images:
+        raise SjpegError("resize_images: no images")
+    if chw:
+        planes, dims, dev, fmt = _chw_planes("resize_images", images, fp)
+    else:
+        for k, im in enumerate(images):
+            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
+                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+                raise SjpegError(f"resize_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+            if im.device != images[0].device:
+                raise SjpegError(f"resize_images: image {k} is on {im.device}, image 0 on {images[0].device}")
+        dev, fmt = images[0].device, SRC_RGB
+        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    with torch.cuda.device(dev):
+        rfmt, pics, _ = eng.resize_ragged(fmt, planes, dims, res.sizes)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics

@@ -126,6 +126,38 @@ int reduce_ragged_launch(int format, const float* pscale, const float* pbias, co
 // sjpeg_hip_engine_trim; *base says where.
 int engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base, void* stream);
 
+// ---- ragged resize (sjpeg_hip_resize_ragged_src, resize.hip): one descriptor per frame; a workgroup finds its frame by
+// a binary search over tile_base.  A tile is tw x th samples of the resized picture (tw a power of two in 4..256: a
+// tile's row starts at a whole dword of the resized row), the frame's tiles in row-major order; 256 / tw lanes share a
+// column of it.  The resized pictures lie in their buffer as the reduced ones do (reduce_round.h).
+struct ResizeFrame {
+  const uint8_t* src;                    // plane 0, row 0
+  long long row_stride;                  // may be negative
+  long long off[3];                      // where R, G and B (gray: the value, thrice) lie from src (layout_rgb_offsets)
+  uint8_t* dst;                          // the resized picture: a multiple of 16
+  int W, H, w2, h2;                      // the source's and the resized picture's size
+  int tw, th;                            // the tile
+  unsigned tiles_x, dst_stride;          // tiles a row of tiles; bytes between resized rows
+  unsigned tile_base, pad;               // the frame's first workgroup in the flat grid
+};
+struct ResizePlan {
+  int format = 0, resized_format = 0;
+  std::vector<ResizeFrame> frames;
+  size_t bytes = 0;
+  unsigned tiles = 0;
+};
+// Checks the sizes (sizes[f] = (w', h'), 1..the source's each; NULL: every frame at its own size) and the format (an
+// RGB-like or gray one), then plans; the message names the frame.  The frames' planes and strides are the caller's to
+// check (ragged_check).
+int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                ResizePlan* plan);
+void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
+int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
+                         hipStream_t st);
+// The engine's half (scan_engine.hip), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
+// pictures (the two kinds of call share it and its descriptors' buffer).
+int engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base, void* stream);
+
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
 // out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's

@@ -855,6 +855,52 @@ static bool all_ones(const uint8_t* factors, int nframes) {
   return true;
 }
 
+extern "C++" {
+// what the flow below asks of a plan (ReducePlan, ResizePlan): the format of its pictures, the pictures as frames at
+// `base`, and the engine's half
+static int made_format(const sjpeg_internal::ReducePlan& p) { return p.reduced_format; }
+static int made_format(const sjpeg_internal::ResizePlan& p) { return p.resized_format; }
+static void made_frames(const sjpeg_internal::ReducePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
+  sjpeg_internal::reduce_plan_frames(p, frames, base, out);
+}
+static void made_frames(const sjpeg_internal::ResizePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
+  sjpeg_internal::resize_plan_frames(p, frames, base, out);
+}
+static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::ReducePlan& p, uint8_t** base, void* stream) {
+  return sjpeg_internal::engine_reduce(e, who, p, nullptr, base, stream);
+}
+static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::ResizePlan& p, uint8_t** base, void* stream) {
+  return sjpeg_internal::engine_resize(e, who, p, nullptr, base, stream);
+}
+
+// the rest of a call whose pictures are planned (reduced or resized): the remaining checks, then the device work
+template <class Plan>
+static int planned_flow(const std::string& who, sjpeg_hip_engine* e, const SourceLayout* L, const Plan& plan, int format, int nframes,
+                        const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta,
+                        int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
+                        const sjpeg_internal::PackedSink* sink) {
+  const int y = params->yuv_mode;
+  if (L->implied != 0 && y != L->implied) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format (gray pictures are coded 4:0:0 only)");
+  }
+  if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+  // (the inner flow's own checks on the made pictures, standing at a placeholder address until there is memory)
+  std::vector<sjpeg_hip_ragged_frame> made(static_cast<size_t>(nframes));
+  made_frames(plan, frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), made.data());
+  if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : made) f.out_offset = 0;   // (ignored: the placement kernel says where a frame goes)
+  if (int rc = full_checks(who, made_format(plan), nframes, made.data(), *params)) return rc;
+  sjpeg_internal::MetaCtx ctx;
+  if (meta != nullptr) { if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc; }
+  // ---- device work
+  uint8_t* base = nullptr;
+  if (int rc = make_pictures(e, who, plan, &base, stream)) return rc;
+  made_frames(plan, frames, base, made.data());
+  if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : made) f.out_offset = 0;
+  const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
+  return full_flow(who, e, made_format(plan), nframes, made.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
+}
+}  // extern "C++"
+
 static int reduced_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
                         const sjpeg_hip_ragged_params* params, const uint8_t* factors, const sjpeg_hip_metadata* meta, int meta_per_frame,
                         void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
@@ -864,25 +910,8 @@ static int reduced_flow(const std::string& who, sjpeg_hip_engine* e, int format,
     if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
     sjpeg_internal::ReducePlan plan;
     if (int rc = sjpeg_internal::reduce_plan(who, format, nframes, frames, factors, &plan)) return rc;
-    const int y = params->yuv_mode;
-    if (L->implied != 0 && y != L->implied) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format (gray pictures are coded 4:0:0 only)");
-    }
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    // (the inner flow's own checks on the reduced pictures, standing at a placeholder address until there is memory)
-    std::vector<sjpeg_hip_ragged_frame> reduced(static_cast<size_t>(nframes));
-    sjpeg_internal::reduce_plan_frames(plan, frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), reduced.data());
-    if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : reduced) f.out_offset = 0;   // (ignored: the placement kernel says where a frame goes)
-    if (int rc = full_checks(who, plan.reduced_format, nframes, reduced.data(), *params)) return rc;
-    sjpeg_internal::MetaCtx ctx;
-    if (meta != nullptr) { if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc; }
-    // ---- device work
-    uint8_t* base = nullptr;
-    if (int rc = sjpeg_internal::engine_reduce(e, who, plan, nullptr, &base, stream)) return rc;
-    sjpeg_internal::reduce_plan_frames(plan, frames, base, reduced.data());
-    if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : reduced) f.out_offset = 0;
-    const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
-    return full_flow(who, e, plan.reduced_format, nframes, reduced.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
+    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+                        stream, sink);
   } catch (...) {
     return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
   }
@@ -938,6 +967,75 @@ int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* e, int format, 
   }
   const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
   return reduced_flow(who, e, format, nframes, frames, params, factors, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
+                      stream, &sink);
+}
+
+// ---- ... and on pictures resized inside the call (resize.hip): thumbnails that fit a box ----
+// sizes NULL or every size its frame's own: exactly the _full_meta_ call on the caller's frames.  Otherwise as the
+// reduced calls: every check first, host only; the resize kernel into the engine's memory; ONE inner flow.
+static bool all_own_size(const int32_t (*sizes)[2], int nframes, const sjpeg_hip_ragged_frame* frames) {
+  for (int f = 0; sizes != nullptr && f < nframes; ++f) {
+    if (sizes[f][0] != frames[f].width || sizes[f][1] != frames[f].height) return false;
+  }
+  return true;
+}
+
+static int resized_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const sjpeg_hip_metadata* meta, int meta_per_frame,
+                        void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
+                        const sjpeg_internal::PackedSink* sink) {
+  try {
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    sjpeg_internal::ResizePlan plan;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, &plan)) return rc;
+    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+                        stream, sink);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                        int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_resized_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (all_own_size(sizes, nframes, frames)) {
+    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                                                 value_out, stream);
+  }
+  return resized_flow(who, e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+                      stream, nullptr);
+}
+
+int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                               const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                               float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_resized_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (all_own_size(sizes, nframes, frames)) {
+    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
+                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
+  }
+  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+  return resized_flow(who, e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
                       stream, &sink);
 }
 

@@ -1,0 +1,340 @@
+// resize.hip -- pictures of a ragged batch resized to any smaller size on gfx950: thumbnails that fit a box, in ONE
+// launch in front of the ragged encodes (sjpeg_hip_resize_ragged_src, sjpeg_hip_encode_ragged_resized_src; sjpeg_hip.h).
+//
+// Reference: none -- the reference codes the picture it is given (src/enc.cc:391-448).  The contract is on the bytes:
+// a sample of frame f's resized picture is the exact area average of the source bytes its cell covers, rounded half up
+// (resize_math.h: integers only, one right answer); a source byte is what the encoder sees there today (pixel_elem.h for
+// floats).
+//
+// Shape: a flat grid over the batch's tiles, a workgroup one tile of tw x th resized samples of one frame, found by a
+// binary search over the frames' first tiles -- so the sizes, the format's fields and the element kind are
+// wave-uniform.  The workgroup walks the source rows its tile covers from the top.  It STAGES the segment of several
+// rows that the tile's columns span in LDS -- a wave a row, adjacent lanes adjacent dwords of it (bytes at a row's last
+// 1..3 bytes, elements for the floats, which land there as bytes) --, then P = 256 / tw adjacent lanes share a column:
+// lane p adds the weighted bytes of every P-th source column of the cell (adjacent lanes read adjacent staged pixels),
+// a butterfly of shuffles makes the row's horizontal sum (32 bits: at most 255 W), and lane 0 of the column adds it,
+// weighted, to the 64-bit sums of the resized row at hand -- a source row touches at most two.  A finished row is
+// rounded into the tile's bytes in LDS; the tile leaves as whole dwords.  tw follows the ratio (P about W / w'), so a
+// lane has about one source pixel a row at any ratio; a segment too long for the LDS is staged in chunks, a row at a
+// time.  Neighbouring tiles share one source column and row.  No atomics.  DESIGN.md section 4.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "pixel_elem.h"
+#include "ragged_aux.h"
+#include "reduce_round.h"
+#include "resize_math.h"
+#include "sjpeg_hip.h"
+#include "source_layout.h"
+
+namespace {
+
+using sjpeg_internal::ResizeFrame;
+using sjpeg_internal::resize_count;
+using sjpeg_internal::resize_first;
+using sjpeg_internal::resize_weight;
+
+// how a row's segment is staged
+enum { kResizePacked = 0, kResizePlanes = 1, kResizeElems = 2 };
+
+constexpr unsigned kStageBytes = 16384;          // staged source rows
+constexpr int kTileRowsMax = 16;                 // th
+constexpr unsigned kTileBytes = kTileRowsMax * 256 * 3;
+
+struct ResizeArgs {
+  const ResizeFrame* frames;
+  int nframes;
+  int cls;                       // kResize*
+  int kind;                      // kElem* (pixel_elem.h)
+  int pix_step;                  // bytes from a pixel to the next
+  int channels;                  // 3, or 1 for the gray formats
+  float pscale[3], pbias[3];     // the engine's pixel transform (float formats)
+};
+
+// The pictures lie in device memory (reduce.hip says why this is said); a source dword is aligned like a byte.
+typedef uint32_t __attribute__((aligned(1))) Dword1;
+typedef const __attribute__((address_space(1))) Dword1* GlobalDwords;
+typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
+typedef __attribute__((address_space(1))) uint32_t* GlobalOut;
+
+__device__ __forceinline__ unsigned align4(unsigned n) { return (n + 3u) & ~3u; }
+
+// nb bytes of a source row at g into LDS at l (a multiple of 4), by the `lanes` threads of which this is `lane`: whole
+// dwords, the last 1..3 bytes one by one -- every byte read is one of the nb
+__device__ __forceinline__ void stage_bytes(const uint8_t* g, uint8_t* l, unsigned nb, unsigned lane, unsigned lanes) {
+  const unsigned nd = nb >> 2;
+  GlobalDwords const gd = (GlobalDwords)(g);
+  uint32_t* const ld = reinterpret_cast<uint32_t*>(l);
+  for (unsigned i = lane; i < nd; i += lanes) ld[i] = gd[i];
+  const unsigned i = (nd << 2) + lane;
+  if (i < nb) l[i] = ((GlobalBytes)(g))[i];
+}
+
+__global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+  __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
+  const unsigned wg = blockIdx.x, tid = threadIdx.x;
+  int flo = 0, fhi = a.nframes - 1;
+  while (flo < fhi) {
+    const int mid = (flo + fhi + 1) >> 1;
+    if (a.frames[mid].tile_base <= wg) flo = mid; else fhi = mid - 1;
+  }
+  const ResizeFrame d = a.frames[flo];
+  const uint32_t W = d.W, H = d.H, w2 = d.w2, h2 = d.h2;
+  const unsigned t = wg - d.tile_base, tyi = t / d.tiles_x, txi = t - tyi * d.tiles_x;
+  const uint32_t ox0 = txi * d.tw, oy0 = tyi * d.th;
+  const uint32_t tw = min(static_cast<uint32_t>(d.tw), w2 - ox0), th = min(static_cast<uint32_t>(d.th), h2 - oy0);
+  const unsigned P = 256u / static_cast<unsigned>(d.tw);          // lanes a column: a power of two, 1..64
+  const unsigned j = tid / P, p = tid & (P - 1u);
+  const bool col = j < tw;
+  const unsigned channels = a.channels;
+  // my cell's source columns; the tile's segment of a source row and its source rows
+  const uint32_t cx0 = col ? resize_first(ox0 + j, W, w2) : 0u, cx1 = col ? cx0 + resize_count(ox0 + j, W, w2) : 0u;
+  const uint32_t xs = resize_first(ox0, W, w2), xe = resize_first(ox0 + tw - 1u, W, w2) + resize_count(ox0 + tw - 1u, W, w2);
+  const uint32_t ys = resize_first(oy0, H, h2), ye = resize_first(oy0 + th - 1u, H, h2) + resize_count(oy0 + th - 1u, H, h2);
+  // The staged rows: packed pixels as they lie in memory, else a run of bytes per channel; `cap` pixels fit, a longer
+  // segment goes in chunks of a single row
+  const bool packed = a.cls == kResizePacked;
+  const unsigned lstep = packed ? a.pix_step : 1u;
+  const unsigned cap = packed ? kStageBytes / lstep : (kStageBytes / channels) & ~3u;
+  const unsigned seg = xe - xs, clen_max = min(seg, cap);
+  const unsigned cpitch = packed ? 0u : align4(clen_max);
+  const unsigned rpitch = packed ? align4(clen_max * lstep) : cpitch * channels;
+  const unsigned R = seg > cap ? 1u : kStageBytes / rpitch;
+  unsigned coff[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) coff[c] = packed ? static_cast<unsigned>(d.off[c]) : static_cast<unsigned>(c) * cpitch;
+  // who stages what: a wave a row, or the whole workgroup the one row of a chunk
+  const unsigned slanes = R == 1u ? 256u : 64u, slane = tid & (slanes - 1u), srow = tid / slanes, srows = 256u / slanes;
+
+  const unsigned tpitch = align4(static_cast<unsigned>(d.tw) * channels);
+  for (unsigned i = tid; i < th * tpitch / 4u; i += 256u) reinterpret_cast<uint32_t*>(tile)[i] = 0u;   // (the rows' padding)
+
+  uint32_t h[3] = {0u, 0u, 0u};
+  uint64_t acc[3] = {0ull, 0ull, 0ull};
+  uint32_t yo = oy0;                                               // the resized row the sums belong to
+  for (uint32_t yb = ys; yb < ye; yb += R) {
+    const unsigned nr = min(R, ye - yb);
+    for (uint32_t xc = xs; xc < xe; xc += cap) {
+      const unsigned clen = min(cap, xe - xc);
+      for (unsigned r = srow; r < nr; r += srows) {
+        const uint8_t* const row = d.src + static_cast<long long>(yb + r) * d.row_stride;
+        uint8_t* const l = stage + r * rpitch;
+        if (packed) {
+          stage_bytes(row + static_cast<long long>(xc) * lstep, l, clen * lstep, slane, slanes);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            if (c >= static_cast<int>(channels)) continue;
+            if (a.cls == kResizePlanes) {
+              stage_bytes(row + d.off[c] + xc, l + c * cpitch, clen, slane, slanes);
+              continue;
+            }
+            // the float formats element by element: never an element that is not a used sample of a pixel of the picture
+            for (unsigned k = slane; k < clen; k += slanes) {
+              l[c * cpitch + k] = static_cast<uint8_t>(sjpeg_internal::elem_load_u8(
+                  row + d.off[c] + static_cast<long long>(xc + k) * a.pix_step, a.kind, a.pscale[c], a.pbias[c]));
+            }
+          }
+        }
+      }
+      __syncthreads();
+      const uint32_t lo = max(cx0, xc), hi = min(cx1, xc + clen);
+      const bool first = xc == xs, last = xc + clen == xe;
+      for (unsigned r = 0; r < nr; ++r) {
+        if (first) { h[0] = 0u; h[1] = 0u; h[2] = 0u; }            // (several chunks: nr == 1, h goes from chunk to chunk)
+        for (uint32_t x = lo + p; x < hi; x += P) {
+          const uint32_t w = resize_weight(ox0 + j, x, W, w2);
+          const uint8_t* const px = stage + r * rpitch + (x - xc) * lstep;
+          h[0] += w * px[coff[0]];
+          if (channels == 3u) { h[1] += w * px[coff[1]]; h[2] += w * px[coff[2]]; }
+        }
+        if (!last) continue;
+        for (unsigned m = P >> 1; m != 0u; m >>= 1) {
+          h[0] += __shfl_xor(h[0], m);
+          if (channels == 3u) { h[1] += __shfl_xor(h[1], m); h[2] += __shfl_xor(h[2], m); }
+        }
+        if (col && p == 0u) {
+          // source row y into the resized row at hand; the row that ends it may begin the next
+          const uint32_t y = yb + r;
+          const uint32_t wy = resize_weight(yo, y, H, h2);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += static_cast<uint64_t>(wy) * h[c];
+          if ((y + 1u) * h2 >= (yo + 1u) * H) {
+            uint8_t* const o = tile + (yo - oy0) * tpitch + j * channels;
+            o[0] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[0], W, H));
+            if (channels == 3u) {
+              o[1] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[1], W, H));
+              o[2] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[2], W, H));
+            }
+            ++yo;
+            const uint32_t wn = yo < oy0 + th ? resize_weight(yo, y, H, h2) : 0u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] = static_cast<uint64_t>(wn) * h[c];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // the tile as whole dwords of the resized rows: its first byte is a multiple of 4 (tw is), its last dword may reach
+  // into the row's padding, never past it
+  const unsigned ndw = (tw * channels + 3u) >> 2;
+  for (unsigned i = tid; i < th * ndw; i += 256u) {
+    const unsigned r = i / ndw, k = i - r * ndw;
+    uint8_t* const out = d.dst + static_cast<size_t>(oy0 + r) * d.dst_stride + static_cast<size_t>(ox0) * channels;
+    ((GlobalOut)(out))[k] = reinterpret_cast<const uint32_t*>(tile + r * tpitch)[k];
+  }
+}
+
+const char* yuv_format_name(int format) {
+  switch (format) {
+    case SJPEG_HIP_SRC_YUV444: return "SJPEG_HIP_SRC_YUV444";
+    case SJPEG_HIP_SRC_YUV420: return "SJPEG_HIP_SRC_YUV420";
+    case SJPEG_HIP_SRC_NV12: return "SJPEG_HIP_SRC_NV12";
+    case SJPEG_HIP_SRC_NV21: return "SJPEG_HIP_SRC_NV21";
+    default: return "this format";
+  }
+}
+
+// a format the kernel reads: every RGB-like row of the table and the gray ones
+bool resizable(const sjpeg_internal::SourceLayout& L) { return L.rgb_like || (L.planes == 1 && L.implied == SJPEG_HIP_YUV400); }
+
+}  // namespace
+
+namespace sjpeg_internal {
+
+int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                ResizePlan* plan) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    const std::string frame = who + ": frame " + std::to_string(f) + ": ";
+    if (fr.width < 1 || fr.height < 1 || fr.width > 65535 || fr.height > 65535) {
+      return set_error(SJPEG_HIP_EINVAL, frame + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
+    }
+    if (sizes == nullptr) continue;
+    const std::string size = "size " + std::to_string(sizes[f][0]) + "x" + std::to_string(sizes[f][1]);
+    if (sizes[f][0] < 1 || sizes[f][1] < 1) return set_error(SJPEG_HIP_EINVAL, frame + size + " is below 1x1");
+    if (sizes[f][0] > fr.width || sizes[f][1] > fr.height) {
+      return set_error(SJPEG_HIP_EINVAL, frame + size + " is above the source's " + std::to_string(fr.width) + "x" + std::to_string(fr.height) +
+                                             " (pictures are made smaller, never larger)");
+    }
+  }
+  if (!resizable(*L)) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not resized (a size other than the source's takes an RGB-like or a gray format)");
+  }
+  const int channels = L->rgb_like ? 3 : 1;
+  plan->format = format;
+  plan->resized_format = channels == 3 ? SJPEG_HIP_SRC_RGB : SJPEG_HIP_SRC_GRAY;
+  plan->frames.assign(static_cast<size_t>(nframes), ResizeFrame());
+  size_t at = 0;
+  unsigned long long tiles = 0;
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    ResizeFrame& d = plan->frames[f];
+    memset(&d, 0, sizeof(d));
+    const uint8_t* planes[3];
+    long long rows[3];
+    layout_planes(*L, fr.plane, fr.row_stride, nullptr, planes, rows, nullptr);
+    d.src = static_cast<const uint8_t*>(fr.plane[0]);
+    d.row_stride = rows[0];
+    long long g = 0, b = 0;
+    if (channels == 3) layout_rgb_offsets(*L, fr.plane, &g, &b);
+    d.off[0] = channels == 3 ? L->r_off : 0; d.off[1] = g; d.off[2] = b;
+    d.W = fr.width; d.H = fr.height;
+    d.w2 = sizes != nullptr ? sizes[f][0] : fr.width; d.h2 = sizes != nullptr ? sizes[f][1] : fr.height;
+    // P lanes a column, the largest power of two up to 64 that W / w' holds: a lane has about one source pixel a row.
+    // th: about 64 source rows a tile, so that the row two tiles share is one in 64.
+    int P = 1;
+    while (P < 64 && 2 * P <= d.W / d.w2) P *= 2;
+    d.tw = 256 / P;
+    const int th = static_cast<int>((64ll * d.h2 + d.H - 1) / d.H);
+    d.th = th < 1 ? 1 : th > 16 ? 16 : th;
+    d.tiles_x = static_cast<unsigned>((d.w2 + d.tw - 1) / d.tw);
+    d.dst_stride = static_cast<unsigned>(reduced_row_stride(d.w2, channels));
+    d.dst = reinterpret_cast<uint8_t*>(at);                       // (from the buffer's start: engine_resize adds it)
+    d.tile_base = static_cast<unsigned>(tiles);
+    at += reduced_picture_bytes(d.w2, d.h2, channels);
+    tiles += static_cast<unsigned long long>(d.tiles_x) * static_cast<unsigned long long>((d.h2 + d.th - 1) / d.th);
+    if (tiles > 0x7fffffffull) return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": the batch has too many tiles for one launch");
+  }
+  plan->bytes = at;
+  plan->tiles = static_cast<unsigned>(tiles);
+  return 0;
+}
+
+void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
+  for (size_t f = 0; f < plan.frames.size(); ++f) {
+    const ResizeFrame& d = plan.frames[f];
+    sjpeg_hip_ragged_frame r;
+    memset(&r, 0, sizeof(r));
+    r.plane[0] = base + reinterpret_cast<uintptr_t>(d.dst);
+    r.row_stride[0] = static_cast<int64_t>(d.dst_stride);
+    r.width = d.w2; r.height = d.h2;
+    r.out_offset = frames[f].out_offset; r.out_capacity = frames[f].out_capacity;
+    out[f] = r;
+  }
+}
+
+int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
+                         hipStream_t st) {
+  const SourceLayout& L = *source_layout(format);
+  ResizeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frames = d_frames;
+  a.nframes = nframes;
+  a.kind = L.kind;
+  a.channels = L.rgb_like ? 3 : 1;
+  a.pix_step = L.plane[0].step * L.esz;
+  a.cls = L.kind != kElemU8 ? kResizeElems : (L.one_pitch || a.channels == 1) ? kResizePlanes : kResizePacked;
+  for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
+  hipLaunchKernelGGL(resize_ragged_kernel, dim3(tiles), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace sjpeg_internal
+
+extern "C" {
+
+int sjpeg_hip_fit_size(int width, int height, int box_width, int box_height, int* fitted_width, int* fitted_height) {
+  static const std::string who = "sjpeg_hip_fit_size";
+  if (fitted_width == nullptr || fitted_height == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": fitted_width or fitted_height == NULL");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
+  }
+  if (box_width < 1 || box_height < 1 || box_width > 65535 || box_height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad box " + std::to_string(box_width) + "x" + std::to_string(box_height));
+  }
+  const long long W = width, H = height, bw = box_width, bh = box_height;
+  long long w = W, h = H;
+  if (W > bw || H > bh) {
+    if (W * bh >= H * bw) {
+      w = bw; h = (H * bw + W / 2) / W;
+    } else {
+      h = bh; w = (W * bh + H / 2) / H;
+    }
+  }
+  *fitted_width = static_cast<int>(w < 1 ? 1 : w);
+  *fitted_height = static_cast<int>(h < 1 ? 1 : h);
+  return 0;
+}
+
+size_t sjpeg_hip_resize_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2]) {
+  if (frames == nullptr) return 0;
+  try {
+    sjpeg_internal::ResizePlan plan;
+    if (sjpeg_internal::resize_plan("sjpeg_hip_resize_ragged_bytes", format, nframes, frames, sizes, &plan) != 0) return 0;
+    return plan.bytes;
+  } catch (...) {
+    return 0;
+  }
+}
+
+}  // extern "C"

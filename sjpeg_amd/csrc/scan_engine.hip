@@ -239,8 +239,8 @@ struct sjpeg_hip_engine {
   int risk_generation = -1;
   DevBuf<uint4> auto_buf;
   DevBuf<uint4> sharp_arena;
-  // reduced pictures (sjpeg_hip_encode_ragged_reduced_src): the uint8 pictures the reduce kernel makes for the inner
-  // encode, ONE allocation of their own -- not the arena above, which the inner flow lays its sharp planes and kept
+  // reduced or resized pictures (sjpeg_hip_encode_ragged_reduced_src, _resized_src): the uint8 pictures the reduce or the
+  // resize kernel makes for the inner encode, ONE allocation of their own -- not the arena above, which the inner flow lays its sharp planes and kept
   // blocks out in --, and the kernel's frame descriptors.  A later call writes them behind everything the earlier one
   // queued: the engine's ordering, as for every scratch buffer.
   DevBuf<uint4> reduced, reduce_desc;
@@ -3533,29 +3533,48 @@ int sjpeg_internal::engine_pack_begin(sjpeg_hip_engine* e, void* stream) {
   return 0;
 }
 
-// ---- ragged reduction (reduce.hip): the engine's half
-int sjpeg_internal::engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base,
-                                  void* stream) {
+// ---- ragged reduction and resize (reduce.hip, resize.hip): the engine's half.  The two share the engine's memory for
+// the pictures they make and for their descriptors; `launch` starts the kernel over the uploaded descriptors.
+template <class Frame, class Launch>
+static int engine_make_pictures(sjpeg_hip_engine* e, const std::string& who, const char* what, std::vector<Frame> desc, size_t bytes,
+                                uint8_t* d_pictures, uint8_t** base, void* stream, Launch launch) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = ragged_ordered(e, st)) return rc;
-  if (d_reduced == nullptr) {
-    if (e->reduced.ensure(plan.bytes / 16 + 1) != 0) {
-      return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(plan.bytes) + " bytes of reduced pictures");
+  if (d_pictures == nullptr) {
+    if (e->reduced.ensure(bytes / 16 + 1) != 0) {
+      return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(bytes) + " bytes of " + what + " pictures");
     }
-    d_reduced = reinterpret_cast<uint8_t*>(e->reduced.p);
+    d_pictures = reinterpret_cast<uint8_t*>(e->reduced.p);
   }
-  if (base != nullptr) *base = d_reduced;
-  std::vector<ReduceFrame> desc = plan.frames;
-  for (ReduceFrame& d : desc) d.dst = d_reduced + reinterpret_cast<uintptr_t>(d.dst);
-  const size_t desc_bytes = sizeof(ReduceFrame) * desc.size();
+  if (base != nullptr) *base = d_pictures;
+  for (Frame& d : desc) d.dst = d_pictures + reinterpret_cast<uintptr_t>(d.dst);
+  const size_t desc_bytes = sizeof(Frame) * desc.size();
   if (int rc = e->reduce_desc.ensure(desc_bytes / 16 + 1)) return rc;
   if (int rc = upload(e, e->reduce_desc.p, desc.data(), desc_bytes, st)) return rc;
   if (int rc = sync_uploads(e, st)) return rc;
-  if (reduce_ragged_launch(plan.format, e->pscale, e->pbias, reinterpret_cast<const ReduceFrame*>(e->reduce_desc.p),
-                           static_cast<int>(desc.size()), plan.tiles, st) != 0) {
-    return fail(SJPEG_HIP_ERUNTIME, who + ": reduce_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
-  }
-  return 0;
+  return launch(reinterpret_cast<const Frame*>(e->reduce_desc.p), static_cast<int>(desc.size()), st);
+}
+
+int sjpeg_internal::engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base,
+                                  void* stream) {
+  return engine_make_pictures(e, who, "reduced", plan.frames, plan.bytes, d_reduced, base, stream,
+                              [&](const ReduceFrame* d_frames, int n, hipStream_t st) {
+    if (reduce_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": reduce_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
+int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base,
+                                  void* stream) {
+  return engine_make_pictures(e, who, "resized", plan.frames, plan.bytes, d_resized, base, stream,
+                              [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
+    if (resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
 }
 
 extern "C" {
@@ -3585,6 +3604,36 @@ int sjpeg_hip_reduce_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
     if (int rc = sjpeg_internal::engine_reduce(e, who, plan, static_cast<uint8_t*>(d_reduced), nullptr, stream)) return rc;
     sjpeg_internal::reduce_plan_frames(plan, frames, static_cast<uint8_t*>(d_reduced), reduced_frames);
     *reduced_format = plan.reduced_format;
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ... and resized to their sizes (resize.hip), with the same order of checks
+int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const int32_t (*sizes)[2], void* d_resized, size_t resized_bytes,
+                                sjpeg_hip_ragged_frame* resized_frames, int* resized_format, void* stream) {
+  static const std::string who = "sjpeg_hip_resize_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || sizes == nullptr || d_resized == nullptr || resized_frames == nullptr || resized_format == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, sizes, d_resized, resized_frames or resized_format == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_resized) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_resized must be a multiple of 16");
+  try {
+    sjpeg_internal::ResizePlan plan;
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, &plan)) return rc;
+    if (resized_bytes < plan.bytes) {
+      return fail(SJPEG_HIP_EINVAL, who + ": resized_bytes " + std::to_string(resized_bytes) + " is below the " + std::to_string(plan.bytes) +
+                                        " bytes the resized pictures take (sjpeg_hip_resize_ragged_bytes)");
+    }
+    if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_resized), nullptr, stream)) return rc;
+    sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_resized), resized_frames);
+    *resized_format = plan.resized_format;
     return 0;
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
