@@ -893,6 +893,77 @@ int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* engine, int for
                                                int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                void* stream);
 
+/* ---- pictures turned upright inside the ragged call: EXIF orientation ----
+ * A phone stores the sensor's rows as they come and records the rotation in EXIF tag 0x0112, Orientation, 1..8 (6: the
+ * usual portrait photo); a thumbnail that ignores the tag lies on its side.  Let R be frame f's resized picture, w x h:
+ * exactly what sjpeg_hip_resize_ragged_src defines above for sizes[f] = (w, h) -- `sizes` stay in the STORED orientation,
+ * sizes == NULL: every frame at its own size.  For orientations[f] = o the upright picture U is w x h for o in 1..4 and
+ * h x w for o in 5..8, and U(x, y) = R(sx, sy):
+ *     o  meaning                                  sx         sy
+ *     1  as stored                                x          y
+ *     2  mirrored left-right                      w - 1 - x  y
+ *     3  rotated 180                              w - 1 - x  h - 1 - y
+ *     4  mirrored top-bottom                      x          h - 1 - y
+ *     5  transposed                               y          x
+ *     6  rotated 90 clockwise to show             y          h - 1 - x
+ *     7  transverse                               w - 1 - y  h - 1 - x
+ *     8  rotated 90 counter-clockwise to show     w - 1 - y  x
+ * Exact area averaging commutes with the eight symmetries, so "resize, then turn" has one right answer; it costs the
+ * stores of the small picture (the resize kernel stores every finished tile where it lands in U), not a pass over the
+ * source.  THE CONTRACT: the JPEG of an oriented frame is byte for byte what the same call makes of the uint8 picture U
+ * handed over as SJPEG_HIP_SRC_RGB (the gray formats: SJPEG_HIP_SRC_GRAY, 4:0:0 only); SJPEG_YUV_AUTO decides on U.
+ * Formats, strides of either sign and the elements read: those of the resize.  The YUV-plane formats are not oriented:
+ * an orientation other than 1 on one of them is SJPEG_HIP_EINVAL, the message names the format.
+ *
+ * sjpeg_hip_oriented_size (host only): (*ow, *oh) = the size of U for a stored width x height (1..65535 each) and an
+ *   orientation 1..8; SJPEG_HIP_EINVAL otherwise.
+ * sjpeg_hip_orient_ragged_bytes (host only): the bytes the upright pictures of a batch take, 0 on bad arguments (sizes
+ *   and orientations: each may be NULL -- own sizes, all 1).  THE LAYOUT is that of the resized pictures with U's size:
+ *   rows of align4(width of U * channels) bytes, every picture at a multiple of 16, frame after frame.  Row and picture
+ *   padding may hold anything.  orientations == NULL: the value of sjpeg_hip_resize_ragged_bytes.
+ * sjpeg_hip_orient_ragged_src: ONE launch, resize and orientation together, into d_out (a multiple of 16, `bytes` behind
+ *   it) with the arguments, the ordering and the pipelined-mode behaviour of sjpeg_hip_resize_ragged_src; out_frames
+ *   are U's (width, height, row stride), *out_format SJPEG_HIP_SRC_RGB or _GRAY.  SJPEG_HIP_EINVAL before any device
+ *   work, the frame named: the resize's checks, and an orientation outside 1..8.
+ * sjpeg_hip_encode_ragged_oriented_src / _oriented_packed_src: the resized entries plus `orientations` (host
+ *   uint8[nframes], or NULL).  NULL or all 1: exactly the resized call on the same arguments -- so NV12 at its own sizes
+ *   still passes through to the _full_meta_ call.  Otherwise the kernel runs into the engine memory of the reduced and
+ *   resized pictures (counted by sjpeg_hip_engine_scratch_bytes, released by sjpeg_hip_engine_trim), then ONE inner call.
+ *   out_capacity: sjpeg_hip_frame_bound of U's size, SJPEG_HIP_YUV444, 2048 + metadata is always enough.
+ * sjpeg_hip_exif_orientation (host only): 1..8 from IFD0 tag 0x0112 of an EXIF payload as sjpeg_hip_metadata.exif takes
+ *   it (the TIFF header first; a leading "Exif\0\0" is skipped), both byte orders; the tag must be one SHORT.  0 for
+ *   anything else: no tag, a value outside 1..8, truncated or malformed bytes.  Never reads outside [exif, exif + size).
+ * sjpeg_hip_exif_reset_orientation (host only): sets that value to 1 in place and returns the old value, or 0 with
+ *   nothing changed -- for a service that bakes the rotation in and keeps the EXIF: a viewer would turn the picture a
+ *   second time. */
+int sjpeg_hip_oriented_size(int width, int height, int orientation, int* ow, int* oh);
+size_t sjpeg_hip_orient_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                     const uint8_t* orientations /*host [nframes], or NULL*/);
+int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                         const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                         const uint8_t* orientations /*host [nframes], or NULL*/,
+                                         const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                         void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                         int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity,
+                                                uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                void* stream);
+int sjpeg_hip_exif_orientation(const uint8_t* exif, size_t size);
+int sjpeg_hip_exif_reset_orientation(uint8_t* exif, size_t size);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -215,6 +215,8 @@ class Reduced:
     def __init__(self, images, factor):
         if type(images).__name__ == "Resized":
             raise SjpegError("Reduced: the pictures are Resized already: resize the pictures themselves, once")
+        if type(images).__name__ == "Oriented":
+            raise SjpegError("Reduced: the pictures are Oriented already: Oriented takes the sizes itself")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -280,6 +282,8 @@ class Resized:
     def __init__(self, images, sizes):
         if isinstance(images, (Reduced, Resized)):
             raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
+        if type(images).__name__ == "Oriented":
+            raise SjpegError("Resized: the pictures are Oriented already: Oriented takes the sizes itself")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -303,6 +307,8 @@ class Resized:
         pictures' shapes are read ("hwc": [H, W, 3]; "chw": [3, H, W]; a FloatPixels is read as "chw")."""
         if isinstance(images, (Reduced, Resized)):
             raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
+        if type(images).__name__ == "Oriented":
+            raise SjpegError("Resized: the pictures are Oriented already: Oriented takes the sizes itself")
         chw = isinstance(images, FloatPixels) or _check_layout("Resized.fit", layout)
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         return cls(images, [fit_size(*_picture_size(im, chw), box) for im in inner])
@@ -322,6 +328,120 @@ def _sizes_array(who, sizes):
     except (TypeError, ValueError):
         raise SjpegError(f"{who}: sizes are pairs of ints (w, h), one per frame")
     return np.ascontiguousarray(np.clip(arr, -2**31, 2**31 - 1).astype(np.int32))
+
+
+def oriented_size(w, h, orientation):
+    """sjpeg_hip_oriented_size: (w, h) of the upright picture of a stored w x h one with EXIF orientation 1..8: swapped
+    for 5..8."""
+    ow, oh = C.c_int(0), C.c_int(0)
+    if lib().sjpeg_hip_oriented_size(int(w), int(h), int(orientation), C.byref(ow), C.byref(oh)) != 0:
+        raise SjpegError("sjpeg_hip_oriented_size: " + lib().sjpeg_hip_last_error().decode())
+    return int(ow.value), int(oh.value)
+
+
+def exif_orientation(exif) -> int:
+    """sjpeg_hip_exif_orientation: 1..8 from IFD0 tag 0x0112 of an EXIF payload as PictureMetadata.exif holds it (a
+    leading b"Exif\\0\\0" is skipped; both byte orders); 0 for anything else -- no tag, not one SHORT, a value outside
+    1..8, truncated or malformed bytes."""
+    b = bytes(exif)
+    return int(lib().sjpeg_hip_exif_orientation(b, len(b)))
+
+
+def exif_reset_orientation(exif) -> bytes:
+    """sjpeg_hip_exif_reset_orientation on a copy: the payload with its Orientation set to 1 (unchanged where
+    exif_orientation is 0) -- for pictures whose rotation is baked in and whose EXIF is kept."""
+    b = bytes(exif)
+    if not b:
+        return b
+    buf = (C.c_uint8 * len(b)).from_buffer_copy(b)
+    lib().sjpeg_hip_exif_reset_orientation(buf, len(b))
+    return bytes(buf)
+
+
+class Oriented:
+    """Pictures to be coded upright -- and, with `sizes`, resized in the same launch -- wherever Resized is taken:
+    Oriented(images, orientations, sizes=None) with `images` what encode_images, compress_images, encode_images_full,
+    encode_images_full_chw and encode_images_full_meta take, `orientations` one EXIF Orientation (tag 0x0112, 1..8) or
+    one per picture, and `sizes` None (every picture at its own size), one (w, h) or one per picture, in the STORED
+    orientation as Resized takes them.  Picture k is resized as Resized defines it and every finished tile stored where
+    it lands in the upright picture (w x h for 1..4, h x w for 5..8): one launch for the batch, no rot90 / flip /
+    contiguous() per picture, and its JPEG is byte for byte that of the upright uint8 picture (orient_images returns
+    those).  Orientations that are all 1 are Resized(images, sizes)."""
+
+    def __init__(self, images, orientations, sizes=None):
+        if isinstance(images, (Reduced, Resized, Oriented)):
+            raise SjpegError("Oriented: the pictures are Reduced, Resized or Oriented already: Oriented takes the sizes itself, once")
+        self.images = images
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        if not isinstance(images, FloatPixels):
+            self.images = inner
+        n = len(inner)
+        os_ = list(orientations) if isinstance(orientations, (list, tuple, np.ndarray)) else [orientations] * n
+        if len(os_) != n:
+            raise SjpegError(f"Oriented: {len(os_)} orientations for {n} pictures: one orientation, or one per picture")
+        for k, o in enumerate(os_):
+            if not isinstance(o, (int, np.integer)) or o < 1 or o > 8:
+                raise SjpegError(f"Oriented: picture {k}: orientation {o!r} is not an int in 1..8 (EXIF tag 0x0112)")
+        self.orientations = [int(o) for o in os_]
+        self.sizes = None if sizes is None else Resized(images, sizes).sizes
+
+    @classmethod
+    def fit(cls, images, orientations, box, layout="hwc"):
+        """Oriented(images, orientations, sizes) with every UPRIGHT picture fitted into box = (bw, bh) by fit_size: for
+        the orientations 5..8 the stored picture is fitted into (bh, bw).  layout as Resized.fit."""
+        plain = cls(images, orientations)
+        chw = isinstance(images, FloatPixels) or _check_layout("Oriented.fit", layout)
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        try:
+            bw, bh = box
+        except (TypeError, ValueError):
+            raise SjpegError(f"fit_size: box {box!r} is not a pair (width, height)")
+        sizes = [fit_size(*_picture_size(im, chw), (bh, bw) if o >= 5 else (bw, bh)) for im, o in zip(inner, plain.orientations)]
+        return cls(images, plain.orientations, sizes)
+
+    @classmethod
+    def from_metadata(cls, images, metadata, box=None, layout="hwc"):
+        """(Oriented, metadata): every picture's orientation read from its PictureMetadata.exif (exif_orientation; 0 --
+        no tag, no EXIF, no entry -- is taken as 1), the pictures fitted into `box` as Oriented.fit does when one is
+        given; the metadata returned are copies whose Orientation is reset to 1, to be handed to the encode with the
+        Oriented: a viewer must not turn the upright picture a second time.  metadata: one PictureMetadata for all
+        pictures or one per picture (None entries: none)."""
+        inner = images.images if isinstance(images, FloatPixels) else list(images)
+        n = len(inner)
+        items = [metadata] * n if isinstance(metadata, PictureMetadata) or metadata is None else list(metadata)
+        if len(items) != n:
+            raise SjpegError("Oriented.from_metadata: one metadata entry per image")
+        orientations, reset = [], []
+        for k, m in enumerate(items):
+            if m is None:
+                orientations.append(1); reset.append(None)
+                continue
+            if not isinstance(m, PictureMetadata):
+                raise SjpegError(f"Oriented.from_metadata: metadata entry {k} is not a PictureMetadata")
+            orientations.append(exif_orientation(m.exif) or 1)
+            reset.append(PictureMetadata(m.app_markers, exif_reset_orientation(m.exif), m.iccp, m.xmp, m.xmp_split_point))
+        made = cls(images, orientations) if box is None else cls.fit(images, orientations, box, layout)
+        return made, reset
+
+
+def _oriented(images):
+    """(the images of a call without their Oriented wrapper -- a Resized where it has sizes --, the orientations or None
+    when nothing is turned)"""
+    if not isinstance(images, Oriented):
+        return images, None
+    turned = images.orientations if any(o != 1 for o in images.orientations) else None
+    return (images.images if images.sizes is None else Resized(images.images, images.sizes)), turned
+
+
+def _orientations_array(who, n, orientations):
+    """orientations as the C entries take them: uint8 [n], values clamped into a byte (the library names a bad one)"""
+    try:
+        vals = [int(o) for o in orientations]
+    except (TypeError, ValueError):
+        raise SjpegError(f"{who}: orientations are ints 1..8, one per frame")
+    if len(vals) != n:
+        raise SjpegError(f"{who}: one orientation per frame")
+    return np.ascontiguousarray(np.clip(np.asarray(vals, dtype=np.int64), 0, 255).astype(np.uint8))
 
 
 class RaggedFrame(C.Structure):
@@ -566,6 +686,23 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_encode_ragged_resized_src.restype = C.c_int
     L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes)
     L.sjpeg_hip_encode_ragged_resized_packed_src.restype = C.c_int
+    L.sjpeg_hip_oriented_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sjpeg_hip_oriented_size.restype = C.c_int
+    L.sjpeg_hip_orient_ragged_bytes.argtypes = list(L.sjpeg_hip_resize_ragged_bytes.argtypes) + [C.c_void_p]
+    L.sjpeg_hip_orient_ragged_bytes.restype = C.c_size_t
+    plain = list(L.sjpeg_hip_resize_ragged_src.argtypes)
+    L.sjpeg_hip_orient_ragged_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
+    L.sjpeg_hip_orient_ragged_src.restype = C.c_int
+    plain = list(L.sjpeg_hip_encode_ragged_resized_src.argtypes)
+    L.sjpeg_hip_encode_ragged_oriented_src.argtypes = plain[:6] + [C.c_void_p] + plain[6:]
+    L.sjpeg_hip_encode_ragged_oriented_src.restype = C.c_int
+    plain = list(L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes = plain[:6] + [C.c_void_p] + plain[6:]
+    L.sjpeg_hip_encode_ragged_oriented_packed_src.restype = C.c_int
+    L.sjpeg_hip_exif_orientation.argtypes = [C.c_void_p, C.c_size_t]
+    L.sjpeg_hip_exif_orientation.restype = C.c_int
+    L.sjpeg_hip_exif_reset_orientation.argtypes = [C.c_void_p, C.c_size_t]
+    L.sjpeg_hip_exif_reset_orientation.restype = C.c_int
     _lib = L
     return L
 
@@ -610,6 +747,9 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_reduced_src", "sjpeg_hip_encode_ragged_reduced_packed_src",
     "sjpeg_hip_fit_size", "sjpeg_hip_resize_ragged_bytes", "sjpeg_hip_resize_ragged_src",
     "sjpeg_hip_encode_ragged_resized_src", "sjpeg_hip_encode_ragged_resized_packed_src",
+    "sjpeg_hip_oriented_size", "sjpeg_hip_orient_ragged_bytes", "sjpeg_hip_orient_ragged_src",
+    "sjpeg_hip_encode_ragged_oriented_src", "sjpeg_hip_encode_ragged_oriented_packed_src",
+    "sjpeg_hip_exif_orientation", "sjpeg_hip_exif_reset_orientation",
 ]
 
 
@@ -1857,6 +1997,114 @@ class Engine:
             "sjpeg_hip_encode_ragged_resized_packed_src")
         return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
 
+    def orient_ragged(self, fmt, planes_per_frame, dims, sizes, orientations, out=None):
+        """sjpeg_hip_orient_ragged_src: the pictures of a ragged batch resized to sizes[k] = (w, h) (None: their own
+        sizes; the STORED orientation) and turned upright by orientations[k] (EXIF 1..8; None: all 1) in one launch.
+        Returns (fmt, pictures, buf) as resize_ragged does: picture k is [h, w, 3] or [h, w] for 1..4, [w, h, ...] for
+        5..8.  Row and picture padding of buf may hold anything."""
+        import torch
+        n = len(dims)
+        if sizes is not None and len(sizes) != n:
+            raise SjpegError("orient_ragged: one size per frame")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        arr = None if sizes is None else _sizes_array("orient_ragged", sizes)
+        oarr = None if orientations is None else _orientations_array("orient_ragged", n, orientations)
+        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
+        need = lib().sjpeg_hip_orient_ragged_bytes(fmt, n, frames, sp, op)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise SjpegError("orient_ragged: out must be a contiguous uint8 CUDA tensor")
+        made = (RaggedFrame * n)()
+        rfmt = C.c_int(-1)
+        # (a batch the library refuses has need == 0: the call below says why)
+        self._chk(lib().sjpeg_hip_orient_ragged_src(self._h, fmt, n, frames, sp, op, out.data_ptr(),
+                                                    int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()),
+                  "sjpeg_hip_orient_ragged_src")
+        pics = []
+        for r in made:
+            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
+            if rfmt.value == SRC_RGB:
+                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
+            else:
+                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
+        return int(rfmt.value), pics, out
+
+    def _oriented_args(self, who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
+                       capacities, metadata):
+        """what the two oriented encodes share: the arrays, and the default capacities -- the bounds of the UPRIGHT sizes"""
+        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
+            raise SjpegError(f"{who}: one entry of planes_per_frame, dims, sizes and orientations per frame, at least one frame")
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args(who, n, metadata)
+        arr = None if sizes is None else _sizes_array(who, sizes)
+        oarr = None if orientations is None else _orientations_array(who, n, orientations)
+        if capacities is None:
+            capacities = []
+            for k, (w, h) in enumerate(dims if arr is None else arr.tolist()):
+                w, h = min(max(int(w), 1), 65535), min(max(int(h), 1), 65535)
+                if oarr is not None and oarr[k] >= 5:
+                    w, h = h, w
+                capacities.append(frame_bound(w, h, bound_mode, 2048 + msizes[k]))
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args(who, n, quant, min_quant, search, bound_mode,
+                                                                            capacities, dims)
+        return marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities
+
+    def encode_ragged_oriented(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
+                               min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                               out=None, offsets=None, sizes_out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_oriented_src: encode_ragged_resized plus orientations[k] (EXIF 1..8; None: all 1) --
+        the pictures resized and turned upright by the one kernel launch, then one inner call over the upright
+        pictures.  Frame k's bytes are those encode_ragged_full makes of the upright uint8 picture (Engine.orient_ragged
+        returns it).  sizes are in the STORED orientation (None: the pictures' own); the default capacities are the
+        bounds of the upright sizes.  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
+        n = len(dims)
+        marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
+            "encode_ragged_oriented", n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
+            capacities, metadata)
+        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes_out)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_oriented_src(
+            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
+            out.data_ptr(), sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_oriented_src")
+        return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+
+    def encode_ragged_oriented_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
+                                      min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
+                                      capacities=None, packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_oriented_packed_src: encode_ragged_oriented into ONE packed buffer, with the
+        arguments and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        import torch
+        n = len(dims)
+        marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
+            "encode_ragged_oriented_packed", n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant,
+            search, capacities, metadata)
+        dev = _ragged_device(planes_per_frame)
+        if packed_capacity is None:
+            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
+        packed_capacity = int(packed_capacity)
+        if out is None:
+            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+            raise SjpegError("encode_ragged_oriented_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        self._chk(lib().sjpeg_hip_encode_ragged_oriented_packed_src(
+            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
+            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
+            "sjpeg_hip_encode_ragged_oriented_packed_src")
+        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
         _full_packed call -- [most passes any frame ran, measurement launches, host waits, frames whose stream replays
@@ -2085,6 +2333,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     the last parameter: pass layout by keyword.)"""
     import torch
     chw = _check_layout("encode_images", layout)
+    images, orients = _oriented(images)
     images, factors = _reduced(images)
     images, new_sizes = _resized(images)
     images, fp = _float_pixels("encode_images", images, chw)
@@ -2151,7 +2400,13 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
             fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
         planes = [[p] for p in reduced_pictures]
         dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
-    if new_sizes is not None and new_sizes != dims:
+    if orients is not None:
+        # (Oriented: resized and turned upright by the one launch)
+        with torch.cuda.device(dev):
+            fmt, resized_pictures, _ = eng.orient_ragged(fmt, planes, dims, new_sizes, orients)
+        planes = [[p] for p in resized_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
+    elif new_sizes is not None and new_sizes != dims:
         # (Resized: as Reduced, through the resize kernel)
         with torch.cuda.device(dev):
             fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
@@ -2271,6 +2526,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
                         tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed, metadata=None):
     import torch
     chw = _check_layout("encode_images_full", layout)
+    images, orients = _oriented(images)
     images, factors = _reduced(images)
     images, new_sizes = _resized(images)
     images, fp = _float_pixels("encode_images_full", images, chw)
@@ -2321,7 +2577,13 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
             fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
         planes = [[p] for p in reduced_pictures]
         dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
-    if new_sizes is not None and new_sizes != dims:
+    if orients is not None:
+        # (Oriented: resized and turned upright by the one launch)
+        with torch.cuda.device(dev):
+            fmt, resized_pictures, _ = eng.orient_ragged(fmt, planes, dims, new_sizes, orients)
+        planes = [[p] for p in resized_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
+    elif new_sizes is not None and new_sizes != dims:
         # (Resized: as Reduced, through the resize kernel)
         with torch.cuda.device(dev):
             fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
@@ -2379,6 +2641,9 @@ def riskiness_images(images, engine=None, layout="hwc"):
     if isinstance(images, Resized):
         raise SjpegError("riskiness_images: Resized pictures are not taken: resize first -- "
                          "riskiness_images(resize_images(images, sizes)) -- the verdict is that of the resized picture")
+    if isinstance(images, Oriented):
+        raise SjpegError("riskiness_images: Oriented pictures are not taken: turn them first -- "
+                         "riskiness_images(orient_images(images, orientations)) -- the verdict is that of the upright picture")
     images, fp = _float_pixels("riskiness_images", images, chw)
     images = list(images)
     if not images:
@@ -2472,6 +2737,40 @@ def resize_images(images, sizes, engine=None, layout="hwc"):
         eng.set_pixel_transform(fp.scale, fp.bias)
     with torch.cuda.device(dev):
         rfmt, pics, _ = eng.resize_ragged(fmt, planes, dims, res.sizes)
+        if engine is None:
+            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
+    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+
+
+def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
+    """The upright uint8 pictures Oriented(images, orientations, sizes) codes, as views of ONE device buffer, from one
+    launch of the resize kernel: images, sizes (None: the pictures' own), engine and layout as resize_images takes them,
+    orientations one EXIF Orientation 1..8 or one per picture.  Returns what resize_images returns, picture k being
+    [h_k, w_k, 3] for the orientations 1..4 and [w_k, h_k, 3] for 5..8 (layout="chw": channel-first views)."""
+    import torch
+    chw = _check_layout("orient_images", layout)
+    ori = Oriented(images, orientations, sizes)
+    images, fp = _float_pixels("orient_images", ori.images, chw)
+    images = list(images)
+    if not images:
+        raise SjpegError("orient_images: no images")
+    if chw:
+        planes, dims, dev, fmt = _chw_planes("orient_images", images, fp)
+    else:
+        for k, im in enumerate(images):
+            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
+                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+                raise SjpegError(f"orient_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+            if im.device != images[0].device:
+                raise SjpegError(f"orient_images: image {k} is on {im.device}, image 0 on {images[0].device}")
+        dev, fmt = images[0].device, SRC_RGB
+        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    with torch.cuda.device(dev):
+        rfmt, pics, _ = eng.orient_ragged(fmt, planes, dims, ori.sizes, ori.orientations)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics

@@ -138,7 +138,7 @@ struct ResizeFrame {
   int W, H, w2, h2;                      // the source's and the resized picture's size
   int tw, th;                            // the tile
   unsigned tiles_x, dst_stride;          // tiles a row of tiles; bytes between resized rows
-  unsigned tile_base, pad;               // the frame's first workgroup in the flat grid
+  unsigned tile_base, orient;            // the frame's first workgroup in the flat grid; its EXIF orientation, 1..8
 };
 struct ResizePlan {
   int format = 0, resized_format = 0;
@@ -148,9 +148,11 @@ struct ResizePlan {
 };
 // Checks the sizes (sizes[f] = (w', h'), 1..the source's each; NULL: every frame at its own size) and the format (an
 // RGB-like or gray one), then plans; the message names the frame.  The frames' planes and strides are the caller's to
-// check (ragged_check).
+// check (ragged_check).  orientations (NULL: all 1): each 1..8, checked with the sizes; the picture in the buffer is
+// then the upright one of orient_math.h -- h' x w' for 5..8 --, and resize_plan_frames reports that size.  An
+// orientation other than 1 takes a format the kernel reads, as a size other than the source's does.
 int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                ResizePlan* plan);
+                const uint8_t* orientations, ResizePlan* plan);
 void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
 int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
                          hipStream_t st);

@@ -981,14 +981,15 @@ static bool all_own_size(const int32_t (*sizes)[2], int nframes, const sjpeg_hip
 }
 
 static int resized_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const sjpeg_hip_metadata* meta, int meta_per_frame,
+                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                        const sjpeg_hip_metadata* meta, int meta_per_frame,
                         void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
                         const sjpeg_internal::PackedSink* sink) {
   try {
     const SourceLayout* const L = source_layout(format);
     if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
     sjpeg_internal::ResizePlan plan;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, &plan)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
     return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
                         stream, sink);
   } catch (...) {
@@ -1011,7 +1012,7 @@ int sjpeg_hip_encode_ragged_resized_src(sjpeg_hip_engine* e, int format, int nfr
     return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
                                                  value_out, stream);
   }
-  return resized_flow(who, e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+  return resized_flow(who, e, format, nframes, frames, params, sizes, nullptr, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
                       stream, nullptr);
 }
 
@@ -1035,8 +1036,67 @@ int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* e, int format, 
                                                         d_offsets, d_sizes, modes, q_out, value_out, stream);
   }
   const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-  return resized_flow(who, e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
+  return resized_flow(who, e, format, nframes, frames, params, sizes, nullptr, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
                       stream, &sink);
+}
+
+// ---- ... and turned upright by their EXIF orientations in the same launch (orient_math.h) ----
+// orientations NULL or all 1: exactly the resized call on the same arguments (so any format at its own sizes still
+// passes through to the _full_meta_ call).  Otherwise the resized flow with the orientations in its plan: the kernel
+// stores every tile where it lands in the upright picture, and the ONE inner flow codes the upright pictures.
+// (-1: every orientation is 1..8; else the first frame whose is not)
+static int bad_orientation(const uint8_t* orientations, int nframes) {
+  for (int f = 0; orientations != nullptr && f < nframes; ++f) if (orientations[f] < 1 || orientations[f] > 8) return f;
+  return -1;
+}
+static int orientation_error(const std::string& who, const uint8_t* orientations, int f) {
+  return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": orientation " + std::to_string(orientations[f]) +
+                                         " is not one of 1..8 (EXIF tag 0x0112)");
+}
+
+int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                         int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_oriented_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
+  if (all_ones(orientations, nframes)) {
+    return sjpeg_hip_encode_ragged_resized_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                                               value_out, stream);
+  }
+  return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                      value_out, stream, nullptr);
+}
+
+int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_oriented_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
+  if (all_ones(orientations, nframes)) {
+    return sjpeg_hip_encode_ragged_resized_packed_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_packed,
+                                                      packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
+  }
+  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+  return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
+                      value_out, stream, &sink);
 }
 
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {

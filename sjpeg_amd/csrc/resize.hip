@@ -17,6 +17,11 @@
 // rounded into the tile's bytes in LDS; the tile leaves as whole dwords.  tw follows the ratio (P about W / w'), so a
 // lane has about one source pixel a row at any ratio; a segment too long for the LDS is staged in chunks, a row at a
 // time.  Neighbouring tiles share one source column and row.  No atomics.  DESIGN.md section 4.
+//
+// A frame with an EXIF orientation other than 1 (sjpeg_hip_orient_ragged_src; orient_math.h) differs in the store
+// alone: its finished tile lands mirrored or transposed in the upright picture.  A tile's span of a destination row
+// then starts at any byte and may meet its neighbour's inside a dword, so a workgroup stores the bytes of its own
+// samples and no other byte, the rows' padding included: whole dwords inside the span, single bytes at its two ends.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -24,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "orient_math.h"
 #include "pixel_elem.h"
 #include "ragged_aux.h"
 #include "reduce_round.h"
@@ -43,7 +49,7 @@ enum { kResizePacked = 0, kResizePlanes = 1, kResizeElems = 2 };
 
 constexpr unsigned kStageBytes = 16384;          // staged source rows
 constexpr int kTileRowsMax = 16;                 // th
-constexpr unsigned kTileBytes = kTileRowsMax * 256 * 3;
+constexpr unsigned kTileBytes = kTileRowsMax * (256 * 3 + 4);   // (a transposing frame's rows: one dword of pitch more)
 
 struct ResizeArgs {
   const ResizeFrame* frames;
@@ -60,6 +66,7 @@ typedef uint32_t __attribute__((aligned(1))) Dword1;
 typedef const __attribute__((address_space(1))) Dword1* GlobalDwords;
 typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
 typedef __attribute__((address_space(1))) uint32_t* GlobalOut;
+typedef __attribute__((address_space(1))) uint8_t* GlobalOutBytes;
 
 __device__ __forceinline__ unsigned align4(unsigned n) { return (n + 3u) & ~3u; }
 
@@ -111,7 +118,11 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
   // who stages what: a wave a row, or the whole workgroup the one row of a chunk
   const unsigned slanes = R == 1u ? 256u : 64u, slane = tid & (slanes - 1u), srow = tid / slanes, srows = 256u / slanes;
 
-  const unsigned tpitch = align4(static_cast<unsigned>(d.tw) * channels);
+  // the tile's rows in LDS, whole dwords; a transposing frame reads a destination row down a column of them, so its
+  // pitch is an odd number of dwords: the th <= 16 rows of a column lie in th different banks
+  const int orient = static_cast<int>(d.orient);
+  const bool transposed = sjpeg_internal::orient_transposes(orient);
+  const unsigned tpitch = align4(static_cast<unsigned>(d.tw) * channels) | (transposed ? 4u : 0u);
   for (unsigned i = tid; i < th * tpitch / 4u; i += 256u) reinterpret_cast<uint32_t*>(tile)[i] = 0u;   // (the rows' padding)
 
   uint32_t h[3] = {0u, 0u, 0u};
@@ -183,11 +194,47 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
   }
   // the tile as whole dwords of the resized rows: its first byte is a multiple of 4 (tw is), its last dword may reach
   // into the row's padding, never past it
-  const unsigned ndw = (tw * channels + 3u) >> 2;
-  for (unsigned i = tid; i < th * ndw; i += 256u) {
-    const unsigned r = i / ndw, k = i - r * ndw;
-    uint8_t* const out = d.dst + static_cast<size_t>(oy0 + r) * d.dst_stride + static_cast<size_t>(ox0) * channels;
-    ((GlobalOut)(out))[k] = reinterpret_cast<const uint32_t*>(tile + r * tpitch)[k];
+  if (orient <= 1) {
+    const unsigned ndw = (tw * channels + 3u) >> 2;
+    for (unsigned i = tid; i < th * ndw; i += 256u) {
+      const unsigned r = i / ndw, k = i - r * ndw;
+      uint8_t* const out = d.dst + static_cast<size_t>(oy0 + r) * d.dst_stride + static_cast<size_t>(ox0) * channels;
+      ((GlobalOut)(out))[k] = reinterpret_cast<const uint32_t*>(tile + r * tpitch)[k];
+    }
+    return;
+  }
+  // A turned frame: the tile is a rectangle of the upright picture too -- nrows rows of nsamp samples from (ux0, uy0),
+  // the lower of its two opposite corners' places there.  Adjacent lanes store adjacent bytes or dwords of a destination
+  // row and read them along a row of the tile (mirrored or not) or down a column of it; every byte stored is a sample's
+  // of this tile.
+  uint32_t ax, ay, bx, by;
+  sjpeg_internal::orient_upright(ox0, oy0, w2, h2, orient, &ax, &ay);
+  sjpeg_internal::orient_upright(ox0 + tw - 1u, oy0 + th - 1u, w2, h2, orient, &bx, &by);
+  const uint32_t ux0 = min(ax, bx), uy0 = min(ay, by);
+  const bool flipx = ax > bx, flipy = ay > by;
+  const unsigned nsamp = transposed ? th : tw, nrows = transposed ? tw : th, span = nsamp * channels;
+  // byte k of the tile's span of its destination row q
+  auto span_byte = [&](unsigned q, unsigned k) -> uint32_t {
+    const unsigned s = channels == 3u ? k / 3u : k, c = k - s * channels;
+    const unsigned along = flipx ? nsamp - 1u - s : s, across = flipy ? nrows - 1u - q : q;
+    const unsigned r = transposed ? along : across, jj = transposed ? across : along;
+    return tile[r * tpitch + jj * channels + c];
+  };
+  // Dwords inside the span, bytes at its two ends.  The pictures start at multiples of 16 and their rows are whole
+  // dwords apart, so the span's phase is the same in every row: `head` bytes up to the first dword boundary, nd whole
+  // dwords -- every byte of them a sample of this tile --, `tail` bytes behind them.
+  const unsigned head = min((4u - ((ux0 * channels) & 3u)) & 3u, span), nd = (span - head) >> 2, tail = (span - head) & 3u;
+  const unsigned units = head + nd + tail;
+  for (unsigned i = tid; i < nrows * units; i += 256u) {
+    const unsigned q = i / units, u = i - q * units;
+    uint8_t* const out = d.dst + static_cast<size_t>(uy0 + q) * d.dst_stride + static_cast<size_t>(ux0) * channels;
+    if (u >= head && u < head + nd) {
+      const unsigned k = head + ((u - head) << 2);
+      *((GlobalOut)(out + k)) = span_byte(q, k) | (span_byte(q, k + 1u) << 8) | (span_byte(q, k + 2u) << 16) | (span_byte(q, k + 3u) << 24);
+    } else {
+      const unsigned k = u < head ? u : head + (nd << 2) + (u - head - nd);
+      ((GlobalOutBytes)(out))[k] = static_cast<uint8_t>(span_byte(q, k));
+    }
   }
 }
 
@@ -209,16 +256,21 @@ bool resizable(const sjpeg_internal::SourceLayout& L) { return L.rgb_like || (L.
 namespace sjpeg_internal {
 
 int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                ResizePlan* plan) {
+                const uint8_t* orientations, ResizePlan* plan) {
   const SourceLayout* const L = source_layout(format);
   if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  bool turned = false;
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
     const std::string frame = who + ": frame " + std::to_string(f) + ": ";
     if (fr.width < 1 || fr.height < 1 || fr.width > 65535 || fr.height > 65535) {
       return set_error(SJPEG_HIP_EINVAL, frame + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
     }
+    if (orientations != nullptr && (orientations[f] < 1 || orientations[f] > 8)) {
+      return set_error(SJPEG_HIP_EINVAL, frame + "orientation " + std::to_string(orientations[f]) + " is not one of 1..8 (EXIF tag 0x0112)");
+    }
+    turned = turned || (orientations != nullptr && orientations[f] != 1);
     if (sizes == nullptr) continue;
     const std::string size = "size " + std::to_string(sizes[f][0]) + "x" + std::to_string(sizes[f][1]);
     if (sizes[f][0] < 1 || sizes[f][1] < 1) return set_error(SJPEG_HIP_EINVAL, frame + size + " is below 1x1");
@@ -226,6 +278,9 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
       return set_error(SJPEG_HIP_EINVAL, frame + size + " is above the source's " + std::to_string(fr.width) + "x" + std::to_string(fr.height) +
                                              " (pictures are made smaller, never larger)");
     }
+  }
+  if (!resizable(*L) && turned) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not oriented (an orientation other than 1 takes an RGB-like or a gray format)");
   }
   if (!resizable(*L)) {
     return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not resized (a size other than the source's takes an RGB-like or a gray format)");
@@ -258,10 +313,14 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
     const int th = static_cast<int>((64ll * d.h2 + d.H - 1) / d.H);
     d.th = th < 1 ? 1 : th > 16 ? 16 : th;
     d.tiles_x = static_cast<unsigned>((d.w2 + d.tw - 1) / d.tw);
-    d.dst_stride = static_cast<unsigned>(reduced_row_stride(d.w2, channels));
+    // the picture in the buffer is the UPRIGHT one: h' x w' for the orientations that transpose
+    d.orient = orientations != nullptr ? orientations[f] : 1u;
+    uint32_t uw, uh;
+    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
+    d.dst_stride = static_cast<unsigned>(reduced_row_stride(static_cast<int>(uw), channels));
     d.dst = reinterpret_cast<uint8_t*>(at);                       // (from the buffer's start: engine_resize adds it)
     d.tile_base = static_cast<unsigned>(tiles);
-    at += reduced_picture_bytes(d.w2, d.h2, channels);
+    at += reduced_picture_bytes(static_cast<int>(uw), static_cast<int>(uh), channels);
     tiles += static_cast<unsigned long long>(d.tiles_x) * static_cast<unsigned long long>((d.h2 + d.th - 1) / d.th);
     if (tiles > 0x7fffffffull) return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": the batch has too many tiles for one launch");
   }
@@ -277,7 +336,9 @@ void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* fr
     memset(&r, 0, sizeof(r));
     r.plane[0] = base + reinterpret_cast<uintptr_t>(d.dst);
     r.row_stride[0] = static_cast<int64_t>(d.dst_stride);
-    r.width = d.w2; r.height = d.h2;
+    uint32_t uw, uh;
+    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
+    r.width = static_cast<int32_t>(uw); r.height = static_cast<int32_t>(uh);
     r.out_offset = frames[f].out_offset; r.out_capacity = frames[f].out_capacity;
     out[f] = r;
   }
@@ -330,7 +391,35 @@ size_t sjpeg_hip_resize_ragged_bytes(int format, int nframes, const sjpeg_hip_ra
   if (frames == nullptr) return 0;
   try {
     sjpeg_internal::ResizePlan plan;
-    if (sjpeg_internal::resize_plan("sjpeg_hip_resize_ragged_bytes", format, nframes, frames, sizes, &plan) != 0) return 0;
+    if (sjpeg_internal::resize_plan("sjpeg_hip_resize_ragged_bytes", format, nframes, frames, sizes, nullptr, &plan) != 0) return 0;
+    return plan.bytes;
+  } catch (...) {
+    return 0;
+  }
+}
+
+int sjpeg_hip_oriented_size(int width, int height, int orientation, int* ow, int* oh) {
+  static const std::string who = "sjpeg_hip_oriented_size";
+  if (ow == nullptr || oh == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": ow or oh == NULL");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
+  }
+  if (orientation < 1 || orientation > 8) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": orientation " + std::to_string(orientation) + " is not one of 1..8 (EXIF tag 0x0112)");
+  }
+  uint32_t uw, uh;
+  sjpeg_internal::oriented_size(static_cast<uint32_t>(width), static_cast<uint32_t>(height), orientation, &uw, &uh);
+  *ow = static_cast<int>(uw);
+  *oh = static_cast<int>(uh);
+  return 0;
+}
+
+size_t sjpeg_hip_orient_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                                     const uint8_t* orientations) {
+  if (frames == nullptr) return 0;
+  try {
+    sjpeg_internal::ResizePlan plan;
+    if (sjpeg_internal::resize_plan("sjpeg_hip_orient_ragged_bytes", format, nframes, frames, sizes, orientations, &plan) != 0) return 0;
     return plan.bytes;
   } catch (...) {
     return 0;

@@ -3626,7 +3626,7 @@ int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
     if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
     if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
     if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, &plan)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, nullptr, &plan)) return rc;
     if (resized_bytes < plan.bytes) {
       return fail(SJPEG_HIP_EINVAL, who + ": resized_bytes " + std::to_string(resized_bytes) + " is below the " + std::to_string(plan.bytes) +
                                         " bytes the resized pictures take (sjpeg_hip_resize_ragged_bytes)");
@@ -3634,6 +3634,37 @@ int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
     if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_resized), nullptr, stream)) return rc;
     sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_resized), resized_frames);
     *resized_format = plan.resized_format;
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ... and resized, then turned upright by their EXIF orientations, in the same ONE launch (orient_math.h): the checks
+// of the resize in its order, the orientations with the sizes
+int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
+                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_orient_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, d_out, out_frames or out_format == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
+  try {
+    sjpeg_internal::ResizePlan plan;
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
+    if (out_bytes < plan.bytes) {
+      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
+                                        " bytes the oriented pictures take (sjpeg_hip_orient_ragged_bytes)");
+    }
+    if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
+    sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
+    *out_format = plan.resized_format;
     return 0;
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
