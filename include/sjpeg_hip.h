@@ -964,6 +964,77 @@ int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* engine, int fo
 int sjpeg_hip_exif_orientation(const uint8_t* exif, size_t size);
 int sjpeg_hip_exif_reset_orientation(uint8_t* exif, size_t size);
 
+/* ---- decoded video resized and turned inside the ragged call: NV12, NV21 and planar YUV ----
+ * NV12 is what a GPU video decoder writes, so the pictures most likely to lie in device memory in front of this encoder
+ * are decoded frames: poster frames, contact sheets, scrubbing previews.  The entries above make ONE interleaved plane
+ * and refuse the four YUV-plane formats (SJPEG_HIP_SRC_YUV444, _YUV420, _NV12, _NV21); the ones below take exactly those
+ * four and make THREE planes.  Frame f of W x H has a luma plane W x H and chroma planes CW x CH: CW = W, CH = H for
+ * SJPEG_HIP_SRC_YUV444, else CW = (W + 1) / 2, CH = (H + 1) / 2, as the encoder reads them; U and V of NV12 / NV21 are
+ * the even and odd bytes of plane 1 (NV21: V first).  sizes[f] = (w', h'), 1 <= w' <= W and 1 <= h' <= H, in the STORED
+ * orientation; the resized chroma size is cw' = w', ch' = h' for 4:4:4, else cw' = (w' + 1) / 2, ch' = (h' + 1) / 2 --
+ * never above the source's.
+ *   Resize.  Every plane is resized as a gray picture of its own by the exact area average defined for
+ *     sjpeg_hip_resize_ragged_src above: Y from W x H to w' x h', U and V from CW x CH to cw' x ch'.
+ *   Orientation.  orientations[f] = o in 1..8 turns every plane as a picture of its own by the table above.  The upright
+ *     picture is w' x h' for 1..4 and h' x w' for 5..8; its chroma planes are the turned cw' x ch' planes, whose size is
+ *     the one the upright luma's implies.
+ *   Odd sizes.  For even W, H, w', h' the chroma grid covers exactly the luma's extent before and after the resize and
+ *     the turn.  For an odd one the last chroma sample stands for a half-covered pair, and a per-plane average or
+ *     mirror then displaces chroma by less than one chroma sample -- at a picture's edge, which every decoder
+ *     tolerates.  The bytes still have one right answer: the per-plane definition above.
+ *   Output.  Always planar: SJPEG_HIP_SRC_YUV420 for SJPEG_HIP_SRC_YUV420, _NV12 and _NV21 (U and V de-interleaved,
+ *     NV21's order put right), SJPEG_HIP_SRC_YUV444 for SJPEG_HIP_SRC_YUV444.  THE LAYOUT: for frame after frame Y,
+ *     then U, then V; every plane at a multiple of 16 from the buffer's start, its rows align4(plane width) bytes
+ *     apart -- the layout of the reduced pictures, per plane.  Padding may hold anything and lies inside the buffer.
+ * THE CONTRACT: the JPEG of a frame is byte for byte what sjpeg_hip_encode_ragged_full_meta_src makes of the three
+ * planes so defined handed over in the output format.  yuv_mode is the format's own, 4:2:0 or 4:4:4; anything else is
+ * the inner call's "yuv_mode does not match the source format".
+ *
+ * sjpeg_hip_yuv_plane_size (host only): the size of plane 0..2 (Y, U, V) of a width x height picture (1..65535 each)
+ *   in one of the four formats; SJPEG_HIP_EINVAL for any other format, the message names it.
+ * sjpeg_hip_resize_ragged_yuv_bytes (host only): the bytes the made planes of a batch take, 0 on bad arguments (the
+ *   last error says which); sizes and orientations: each may be NULL -- own sizes, all 1.
+ * sjpeg_hip_resize_ragged_yuv_src: ONE launch over the tiles of every plane of every frame, resize and turn together,
+ *   into d_out (a multiple of 16, `bytes` behind it), with the argument checks, the ordering and the pipelined-mode
+ *   behaviour of sjpeg_hip_orient_ragged_src.  out_frames[f]: the three planes, their row strides and the upright width
+ *   and height; *out_format as above.  The UV plane of NV12 / NV21 is read once.
+ * sjpeg_hip_encode_ragged_yuv_resized_src / _yuv_resized_packed_src: the arguments and the output contract of
+ *   sjpeg_hip_encode_ragged_oriented_src / _oriented_packed_src.  Every size its frame's own and every orientation 1
+ *   (or both NULL): exactly the _full_meta_ call on the caller's frames, no kernel, no copy.  Otherwise the kernel
+ *   writes into the engine memory of the reduced and resized pictures (counted by sjpeg_hip_engine_scratch_bytes,
+ *   released by sjpeg_hip_engine_trim, SJPEG_HIP_ENOMEM naming the bytes when it cannot be had), then ONE inner call.
+ *   out_capacity is the caller's: sjpeg_hip_frame_bound of the upright size with the format's mode, 2048 + metadata,
+ *   is always enough.
+ * SJPEG_HIP_EINVAL before any device work, the frame named as the ragged entries do: an RGB-like or gray format (the
+ *   message names it and points at sjpeg_hip_orient_ragged_src), a size below 1 or above the source's, an orientation
+ *   outside 1..8, `bytes` below sjpeg_hip_resize_ragged_yuv_bytes, a d_out that is not a multiple of 16, NULL
+ *   arguments, and every frame check of sjpeg_hip_encode_ragged_src for the format. */
+int sjpeg_hip_yuv_plane_size(int format, int width, int height, int plane, int* plane_width, int* plane_height);
+size_t sjpeg_hip_resize_ragged_yuv_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                         const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                         const uint8_t* orientations /*host [nframes], or NULL*/);
+int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                    const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                    const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                    const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                    sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_yuv_resized_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                            const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                            const uint8_t* orientations /*host [nframes], or NULL*/,
+                                            const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                            void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                            int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                   const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                   const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                   const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                   const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity,
+                                                   uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                   int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                   void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -339,6 +339,15 @@ def oriented_size(w, h, orientation):
     return int(ow.value), int(oh.value)
 
 
+def yuv_plane_size(fmt, w, h, plane):
+    """sjpeg_hip_yuv_plane_size: (w, h) of plane 0..2 (Y, U, V) of a w x h picture in SRC_YUV444, SRC_YUV420, SRC_NV12
+    or SRC_NV21, as the encoder reads it: the chroma planes of the 4:2:0 formats are (w + 1) // 2 by (h + 1) // 2."""
+    pw, ph = C.c_int(0), C.c_int(0)
+    if lib().sjpeg_hip_yuv_plane_size(int(fmt), int(w), int(h), int(plane), C.byref(pw), C.byref(ph)) != 0:
+        raise SjpegError("sjpeg_hip_yuv_plane_size: " + lib().sjpeg_hip_last_error().decode())
+    return int(pw.value), int(ph.value)
+
+
 def exif_orientation(exif) -> int:
     """sjpeg_hip_exif_orientation: 1..8 from IFD0 tag 0x0112 of an EXIF payload as PictureMetadata.exif holds it (a
     leading b"Exif\\0\\0" is skipped; both byte orders); 0 for anything else -- no tag, not one SHORT, a value outside
@@ -699,6 +708,16 @@ def lib() -> C.CDLL:
     plain = list(L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes)
     L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes = plain[:6] + [C.c_void_p] + plain[6:]
     L.sjpeg_hip_encode_ragged_oriented_packed_src.restype = C.c_int
+    L.sjpeg_hip_yuv_plane_size.restype = C.c_int
+    L.sjpeg_hip_yuv_plane_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sjpeg_hip_resize_ragged_yuv_bytes.restype = C.c_size_t
+    L.sjpeg_hip_resize_ragged_yuv_bytes.argtypes = list(L.sjpeg_hip_orient_ragged_bytes.argtypes)
+    L.sjpeg_hip_resize_ragged_yuv_src.restype = C.c_int
+    L.sjpeg_hip_resize_ragged_yuv_src.argtypes = list(L.sjpeg_hip_orient_ragged_src.argtypes)
+    L.sjpeg_hip_encode_ragged_yuv_resized_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_yuv_resized_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_src.argtypes)
+    L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
     L.sjpeg_hip_exif_orientation.argtypes = [C.c_void_p, C.c_size_t]
     L.sjpeg_hip_exif_orientation.restype = C.c_int
     L.sjpeg_hip_exif_reset_orientation.argtypes = [C.c_void_p, C.c_size_t]
@@ -750,6 +769,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_oriented_size", "sjpeg_hip_orient_ragged_bytes", "sjpeg_hip_orient_ragged_src",
     "sjpeg_hip_encode_ragged_oriented_src", "sjpeg_hip_encode_ragged_oriented_packed_src",
     "sjpeg_hip_exif_orientation", "sjpeg_hip_exif_reset_orientation",
+    "sjpeg_hip_yuv_plane_size", "sjpeg_hip_resize_ragged_yuv_bytes", "sjpeg_hip_resize_ragged_yuv_src",
+    "sjpeg_hip_encode_ragged_yuv_resized_src", "sjpeg_hip_encode_ragged_yuv_resized_packed_src",
 ]
 
 
@@ -2059,19 +2080,26 @@ class Engine:
         pictures.  Frame k's bytes are those encode_ragged_full makes of the upright uint8 picture (Engine.orient_ragged
         returns it).  sizes are in the STORED orientation (None: the pictures' own); the default capacities are the
         bounds of the upright sizes.  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
+        return self._encode_oriented("encode_ragged_oriented", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant,
+                                     method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
+                                     sizes_out, metadata)
+
+    def _encode_oriented(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant,
+                         q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets, sizes_out, metadata):
+        """the oriented encode and the one of the YUV-plane formats: one argument list, two entries (sjpeg_hip_<who>_src)"""
         n = len(dims)
         marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
-            "encode_ragged_oriented", n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
+            who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
             capacities, metadata)
         frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes_out)
         params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_oriented_src(
+        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
             self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_oriented_src")
+            out.data_ptr(), sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), f"sjpeg_hip_{who}_src")
         return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
 
     def encode_ragged_oriented_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
@@ -2079,10 +2107,17 @@ class Engine:
                                       capacities=None, packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_oriented_packed_src: encode_ragged_oriented into ONE packed buffer, with the
         arguments and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
+        return self._encode_oriented_packed("encode_ragged_oriented_packed", fmt, planes_per_frame, dims, sizes, orientations,
+                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                            capacities, packed_capacity, out, metadata)
+
+    def _encode_oriented_packed(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method,
+                                min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, packed_capacity, out, metadata):
+        """... and their packed forms (sjpeg_hip_<who>_src)"""
         import torch
         n = len(dims)
         marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
-            "encode_ragged_oriented_packed", n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant,
+            who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant,
             search, capacities, metadata)
         dev = _ragged_device(planes_per_frame)
         if packed_capacity is None:
@@ -2091,19 +2126,78 @@ class Engine:
         if out is None:
             out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
         if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError("encode_ragged_oriented_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
         meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
         params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_oriented_packed_src(
+        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
             self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
             out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-            "sjpeg_hip_encode_ragged_oriented_packed_src")
+            f"sjpeg_hip_{who}_src")
         return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+
+    def resize_ragged_yuv(self, fmt, planes_per_frame, dims, sizes, orientations=None, out=None):
+        """sjpeg_hip_resize_ragged_yuv_src: decoded video frames (fmt SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444;
+        planes_per_frame[k] = [y, uv] or [y, u, v], dims[k] = (w, h) as encode_ragged) resized to sizes[k] = (w, h) (None:
+        their own; the STORED orientation) and turned upright by orientations[k] (EXIF 1..8; None: all 1), every plane
+        as a picture of its own, in one launch.  Returns (out_fmt, pictures, buf): SRC_YUV420 or SRC_YUV444 -- always
+        planar --, picture k a tuple (y, u, v) of uint8 views into buf ([h, w] each; rows padded to a multiple of 4
+        bytes, planes at multiples of 16), which any ragged entry takes as its planes.  out as resize_ragged."""
+        import torch
+        n = len(dims)
+        if sizes is not None and len(sizes) != n:
+            raise SjpegError("resize_ragged_yuv: one size per frame")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        arr = None if sizes is None else _sizes_array("resize_ragged_yuv", sizes)
+        oarr = None if orientations is None else _orientations_array("resize_ragged_yuv", n, orientations)
+        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
+        need = lib().sjpeg_hip_resize_ragged_yuv_bytes(fmt, n, frames, sp, op)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise SjpegError("resize_ragged_yuv: out must be a contiguous uint8 CUDA tensor")
+        made = (RaggedFrame * n)()
+        rfmt = C.c_int(-1)
+        # (a batch the library refuses has need == 0: the call below says why)
+        self._chk(lib().sjpeg_hip_resize_ragged_yuv_src(self._h, fmt, n, frames, sp, op, out.data_ptr(),
+                                                        int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()),
+                  "sjpeg_hip_resize_ragged_yuv_src")
+        pics = []
+        for r in made:
+            planes = []
+            for c in range(3):
+                pw, ph = yuv_plane_size(rfmt.value, r.width, r.height, c)
+                at = out.storage_offset() + int(r.plane[c]) - out.data_ptr()
+                planes.append(out.as_strided((ph, pw), (int(r.row_stride[c]), 1), at))
+            pics.append(tuple(planes))
+        return int(rfmt.value), pics, out
+
+    def encode_ragged_yuv_resized(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
+                                  min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                                  out=None, offsets=None, sizes_out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_yuv_resized_src: encode_ragged_full of decoded video frames (the four formats of
+        resize_ragged_yuv) resized and turned upright inside the call, with the arguments and the returns of
+        encode_ragged_oriented.  Frame k's bytes are those encode_ragged_full makes of the three planes
+        Engine.resize_ragged_yuv returns, handed over in its out_fmt; yuv_mode is the format's own (YUV_420, or YUV_444
+        for SRC_YUV444).  sizes None or the frames' own and orientations None or all 1: exactly encode_ragged_full on
+        the caller's frames."""
+        return self._encode_oriented("encode_ragged_yuv_resized", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode,
+                                     quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
+                                     sizes_out, metadata)
+
+    def encode_ragged_yuv_resized_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
+                                         min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
+                                         capacities=None, packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_yuv_resized_packed_src: encode_ragged_yuv_resized into ONE packed buffer, with the
+        arguments and the returns of encode_ragged_oriented_packed."""
+        return self._encode_oriented_packed("encode_ragged_yuv_resized_packed", fmt, planes_per_frame, dims, sizes, orientations,
+                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                            capacities, packed_capacity, out, metadata)
 
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
@@ -2777,6 +2871,80 @@ def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
 
 
 _packed_stats = {"calls": 0, "retries": 0}
+
+
+def encode_yuv_frames(frames, fmt=SRC_NV12, sizes=None, box=None, orientations=None, quality=75.0, method=4,
+                      target_size=None, target_psnr=None, packed=False, metadata=None, engine=None):
+    """The thumbnail call for decoded video: JPEGs (list of bytes) of device-resident frames in one of the YUV-plane
+    formats -- frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 ([H, W] and [(H + 1) // 2, 2 * ((W + 1) // 2)] uint8 CUDA
+    tensors) or (y, u, v) for SRC_YUV420 / SRC_YUV444 --, each resized to sizes[k] = (w, h) or fitted into box = (bw, bh)
+    (fit_size; the box is the UPRIGHT one) and turned upright by orientations (one EXIF value 1..8 or one per frame),
+    in one ragged call with no colour conversion: the frames are coded 4:2:0 (SRC_YUV444: 4:4:4) as they are sampled.
+    quality: one value or one per frame; target_size / target_psnr: a per-frame search as encode_images_full;
+    packed=True: through the packed entry and one device-to-host copy; metadata: as encode_images."""
+    import torch
+    who = "encode_yuv_frames"
+    frames = [tuple(fr) for fr in frames]
+    n = len(frames)
+    if n == 0:
+        raise SjpegError(f"{who}: no frames")
+    nplanes = 2 if fmt in (SRC_NV12, SRC_NV21) else 3 if fmt in (SRC_YUV420, SRC_YUV444) else 0
+    if nplanes == 0:
+        raise SjpegError(f"{who}: fmt {fmt} is not SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444")
+    for k, fr in enumerate(frames):
+        if len(fr) != nplanes:
+            raise SjpegError(f"{who}: frame {k} has {len(fr)} planes, the format takes {nplanes}")
+        for p in fr:
+            if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 2 or p.stride(1) != 1:
+                raise SjpegError(f"{who}: frame {k}: a plane is a uint8 CUDA tensor [rows, bytes] with stride 1 along a row")
+    dims = [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames]
+    if sizes is not None and box is not None:
+        raise SjpegError(f"{who}: give sizes or box, not both")
+    if orientations is not None and not isinstance(orientations, (list, tuple, np.ndarray)):
+        orientations = [orientations] * n
+    if orientations is not None:
+        orientations = [int(o) for o in _orientations_array(who, n, orientations)]
+    if box is not None:
+        try:
+            bw, bh = box
+        except (TypeError, ValueError):
+            raise SjpegError(f"{who}: box {box!r} is not a pair (width, height)")
+        sizes = [fit_size(w, h, (bh, bw) if orientations is not None and orientations[k] >= 5 else (bw, bh))
+                 for k, (w, h) in enumerate(dims)]
+    if target_size is not None and target_psnr is not None:
+        raise SjpegError(f"{who}: give target_size or target_psnr, not both")
+    target = target_size if target_size is not None else target_psnr
+    search = None
+    if target is not None:
+        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
+        if len(ts) != n:
+            raise SjpegError(f"{who}: one target per frame")
+        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
+        search = [SearchParams(mode, float(t), 10, 1.0, 0.0, 100.0) for t in ts]
+    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    if len(qs) != n:
+        raise SjpegError(f"{who}: one quality per frame")
+    yuv_mode = YUV_444 if fmt == SRC_YUV444 else YUV_420
+    planes = [list(fr) for fr in frames]
+    dev = frames[0][0].device
+    eng = engine or Engine(dev.index or 0)
+    with torch.cuda.device(dev):
+        if packed:
+            out, sz, offs, _, _, _ = eng.encode_ragged_yuv_resized_packed(fmt, planes, dims, sizes, orientations, yuv_mode,
+                                                                          _quality_quant(qs), method, search=search,
+                                                                          metadata=metadata)
+            eng.wait()
+            meta = torch.cat([sz, offs]).cpu().numpy()
+            sz, offs = meta[:n], meta[n:2 * n]
+            if (sz <= 0).any():
+                raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % int(np.argmax(sz <= 0)))
+            top = int(max(offs[k] + sz[k] for k in range(n)))
+            host = out[:top].cpu().numpy()                    # the ONE copy of the pictures
+            return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(n)]
+        out, sz, offs, _, _, _ = eng.encode_ragged_yuv_resized(fmt, planes, dims, sizes, orientations, yuv_mode,
+                                                               _quality_quant(qs), method, search=search, metadata=metadata)
+        eng.wait()                               # (pipelined mode: the output is complete after this)
+        return _fetch_ragged(out, sz, offs)
 
 
 def packed_stats():

@@ -140,6 +140,18 @@ struct ResizeFrame {
   unsigned tiles_x, dst_stride;          // tiles a row of tiles; bytes between resized rows
   unsigned tile_base, orient;            // the frame's first workgroup in the flat grid; its EXIF orientation, 1..8
 };
+// The tile of a picture W x H -> w2 x h2 (set in d): P lanes a column, the largest power of two up to 64 that W / w'
+// holds, so that a lane has about one source pixel a row; th: about 64 source rows a tile, so that the row two tiles
+// share is one in 64.  Returns the picture's tiles.
+inline unsigned long long resize_tile_rule(ResizeFrame* d) {
+  int P = 1;
+  while (P < 64 && 2 * P <= d->W / d->w2) P *= 2;
+  d->tw = 256 / P;
+  const int th = static_cast<int>((64ll * d->h2 + d->H - 1) / d->H);
+  d->th = th < 1 ? 1 : th > 16 ? 16 : th;
+  d->tiles_x = static_cast<unsigned>((d->w2 + d->tw - 1) / d->tw);
+  return static_cast<unsigned long long>(d->tiles_x) * static_cast<unsigned long long>((d->h2 + d->th - 1) / d->th);
+}
 struct ResizePlan {
   int format = 0, resized_format = 0;
   std::vector<ResizeFrame> frames;
@@ -159,6 +171,45 @@ int resize_ragged_launch(int format, const float* pscale, const float* pbias, co
 // The engine's half (scan_engine.hip), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
 // pictures (the two kinds of call share it and its descriptors' buffer).
 int engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base, void* stream);
+
+// ---- ragged resize of the YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src; yuv_resize_plan.cc, resize.hip): one
+// descriptor per PLANE of a frame -- Y, U, V of the planar formats, each a one-channel picture of its own; Y and the
+// UV plane of NV12 / NV21, a picture of two-byte pixels that is staged once and leaves as two planes.  The flat grid
+// runs over the tiles of every plane of every frame; a workgroup finds its plane by the binary search over tile_base.
+struct YuvPlane {
+  ResizeFrame r;                         // the plane as a picture: W, H, w2, h2, the tile and dst_stride are the PLANE's
+                                         // (channels == 2: off[0], off[1] say where U and V lie in a pair; dst is U's)
+  uint8_t* dst2;                         // channels == 2: V's plane, laid out as U's
+  int channels, frame;                   // 1 or 2; the frame the plane belongs to
+};
+struct YuvResizePlan {
+  int format = 0, resized_format = 0;    // the caller's; SJPEG_HIP_SRC_YUV420 or _YUV444, always planar
+  int nframes = 0;
+  std::vector<YuvPlane> planes;          // frame after frame
+  size_t bytes = 0;
+  unsigned tiles = 0;
+};
+// the size of plane 0..2 of a width x height picture of a YUV-plane format, as the encoder reads it
+inline void yuv_plane_dims(const SourceLayout& L, int width, int height, int plane, int* pw, int* ph) {
+  const bool half = plane > 0 && L.implied == SJPEG_HIP_YUV420;
+  *pw = half ? (width + 1) / 2 : width;
+  *ph = half ? (height + 1) / 2 : height;
+}
+// the format's name where it is one of the table, for the messages that refuse it
+const char* source_format_name(int format);
+// 0 for one of the four YUV-plane formats, else SJPEG_HIP_EINVAL: the format named, the entries that take it pointed at
+int yuv_format_check(const std::string& who, int format);
+// Checks the format (one of the four YUV-plane ones: anything else is refused by name), the sizes and the orientations
+// as resize_plan does, then plans: every plane by resize_plan's tw / th rule, the planes of frame after frame Y, U, V
+// in reduce_round.h's layout, each turned as a picture of its own.  The frames' planes and strides are the caller's to
+// check (ragged_check).
+int yuv_resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                    const uint8_t* orientations, YuvResizePlan* plan);
+// the made pictures as frames of plan.resized_format at `base`: three planes, their strides, the upright size
+void yuv_resize_plan_frames(const YuvResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
+int yuv_resize_ragged_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
+// the engine's half, as engine_resize
+int engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
 
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own

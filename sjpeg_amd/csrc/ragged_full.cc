@@ -872,6 +872,16 @@ static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpe
 static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::ResizePlan& p, uint8_t** base, void* stream) {
   return sjpeg_internal::engine_resize(e, who, p, nullptr, base, stream);
 }
+// ... and of a YuvResizePlan, whose pictures are three planes; the words behind a refused yuv_mode
+static int made_format(const sjpeg_internal::YuvResizePlan& p) { return p.resized_format; }
+static void made_frames(const sjpeg_internal::YuvResizePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
+  sjpeg_internal::yuv_resize_plan_frames(p, frames, base, out);
+}
+static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::YuvResizePlan& p, uint8_t** base, void* stream) {
+  return sjpeg_internal::engine_yuv_resize(e, who, p, nullptr, base, stream);
+}
+template <class Plan> static const char* mode_hint(const Plan&) { return " (gray pictures are coded 4:0:0 only)"; }
+static const char* mode_hint(const sjpeg_internal::YuvResizePlan&) { return ""; }
 
 // the rest of a call whose pictures are planned (reduced or resized): the remaining checks, then the device work
 template <class Plan>
@@ -881,7 +891,7 @@ static int planned_flow(const std::string& who, sjpeg_hip_engine* e, const Sourc
                         const sjpeg_internal::PackedSink* sink) {
   const int y = params->yuv_mode;
   if (L->implied != 0 && y != L->implied) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format (gray pictures are coded 4:0:0 only)");
+    return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + mode_hint(plan));
   }
   if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
   // (the inner flow's own checks on the made pictures, standing at a placeholder address until there is memory)
@@ -1097,6 +1107,72 @@ int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format,
   const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
   return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
                       value_out, stream, &sink);
+}
+
+// ---- ... and on decoded video: NV12, NV21 and planar YUV resized and turned plane by plane (yuv_resize_plan.cc) ----
+// Every size the frame's own and every orientation 1 (or both NULL): exactly the _full_meta_ call on the caller's
+// frames.  Otherwise the flow of the oriented calls with a plan of planes: the kernel makes Y, U and V of every frame
+// in the engine's memory, and the ONE inner flow codes them as planar 4:2:0 or 4:4:4.
+static int yuv_resized_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                            const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out,
+                            float* value_out, void* stream, const sjpeg_internal::PackedSink* sink) {
+  try {
+    const SourceLayout* const L = source_layout(format);
+    sjpeg_internal::YuvResizePlan plan;
+    if (int rc = sjpeg_internal::yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
+    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
+                        stream, sink);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_yuv_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                            const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                            int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_yuv_resized_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
+  if (all_ones(orientations, nframes) && all_own_size(sizes, nframes, frames)) {
+    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                                                 value_out, stream);
+  }
+  return yuv_resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
+                          value_out, stream, nullptr);
+}
+
+int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                   const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                   const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                   int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_yuv_resized_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
+  if (all_ones(orientations, nframes) && all_own_size(sizes, nframes, frames)) {
+    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
+                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
+  }
+  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
+  return yuv_resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
+                          value_out, stream, &sink);
 }
 
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {

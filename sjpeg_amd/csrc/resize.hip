@@ -22,6 +22,11 @@
 // alone: its finished tile lands mirrored or transposed in the upright picture.  A tile's span of a destination row
 // then starts at any byte and may meet its neighbour's inside a dword, so a workgroup stores the bytes of its own
 // samples and no other byte, the rows' padding included: whole dwords inside the span, single bytes at its two ends.
+//
+// The YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src; yuv_resize_plan.cc) run the kernel's second instantiation:
+// the flat grid over the tiles of every PLANE of every frame, each plane resized and turned as a gray picture of its
+// own.  The UV plane of NV12 / NV21 is a packed picture of two-byte pixels: staged once, summed as two channels, its
+// finished tile stored as two planes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -40,6 +45,7 @@
 namespace {
 
 using sjpeg_internal::ResizeFrame;
+using sjpeg_internal::YuvPlane;
 using sjpeg_internal::resize_count;
 using sjpeg_internal::resize_first;
 using sjpeg_internal::resize_weight;
@@ -81,16 +87,35 @@ __device__ __forceinline__ void stage_bytes(const uint8_t* g, uint8_t* l, unsign
   if (i < nb) l[i] = ((GlobalBytes)(g))[i];
 }
 
-__global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) {
+// The YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src): the grid runs over the tiles of every PLANE of every frame,
+// and what is launch-wide above -- class, channels, pixel step -- is the plane's: Y, and U and V of the planar formats,
+// one-channel planes; the UV plane of NV12 / NV21 a packed picture of two-byte pixels.
+struct YuvResizeArgs {
+  const YuvPlane* planes;
+  int nplanes;
+};
+template <bool kYuv> struct ResizeArgsOf { typedef ResizeArgs type; };
+template <> struct ResizeArgsOf<true> { typedef YuvResizeArgs type; };
+__device__ __forceinline__ int desc_count(const ResizeArgs& a) { return a.nframes; }
+__device__ __forceinline__ int desc_count(const YuvResizeArgs& a) { return a.nplanes; }
+__device__ __forceinline__ const ResizeFrame& desc_at(const ResizeArgs& a, int i) { return a.frames[i]; }
+__device__ __forceinline__ const ResizeFrame& desc_at(const YuvResizeArgs& a, int i) { return a.planes[i].r; }
+
+// kYuv false: the RGB-like and gray formats, a descriptor a frame.  kYuv true: the YUV-plane formats, a descriptor a
+// plane; what differs is decided at compile time, so either instantiation holds its own work alone.  A two-channel
+// plane is staged ONCE, as the packed pixels it is, summed as two channels and rounded into a tile of pairs; the tile
+// leaves as two planes, U to the descriptor's dst and V to its dst2, each by the turned store's rule.
+template <bool kYuv>
+__global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv>::type a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
   const unsigned wg = blockIdx.x, tid = threadIdx.x;
-  int flo = 0, fhi = a.nframes - 1;
+  int flo = 0, fhi = desc_count(a) - 1;
   while (flo < fhi) {
     const int mid = (flo + fhi + 1) >> 1;
-    if (a.frames[mid].tile_base <= wg) flo = mid; else fhi = mid - 1;
+    if (desc_at(a, mid).tile_base <= wg) flo = mid; else fhi = mid - 1;
   }
-  const ResizeFrame d = a.frames[flo];
+  const ResizeFrame d = desc_at(a, flo);
   const uint32_t W = d.W, H = d.H, w2 = d.w2, h2 = d.h2;
   const unsigned t = wg - d.tile_base, tyi = t / d.tiles_x, txi = t - tyi * d.tiles_x;
   const uint32_t ox0 = txi * d.tw, oy0 = tyi * d.th;
@@ -98,15 +123,27 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
   const unsigned P = 256u / static_cast<unsigned>(d.tw);          // lanes a column: a power of two, 1..64
   const unsigned j = tid / P, p = tid & (P - 1u);
   const bool col = j < tw;
-  const unsigned channels = a.channels;
+  unsigned channels;
+  int cls, pix_step;
+  if constexpr (kYuv) {
+    channels = a.planes[flo].channels;
+    cls = channels == 2u ? kResizePacked : kResizePlanes;
+    pix_step = 2;
+  } else {
+    channels = a.channels;
+    cls = a.cls;
+    pix_step = a.pix_step;
+  }
+  // the channels past the first: all three of an RGB-like picture, U and V of a packed pair
+  const bool three = !kYuv && channels == 3u, two = kYuv && channels == 2u;
   // my cell's source columns; the tile's segment of a source row and its source rows
   const uint32_t cx0 = col ? resize_first(ox0 + j, W, w2) : 0u, cx1 = col ? cx0 + resize_count(ox0 + j, W, w2) : 0u;
   const uint32_t xs = resize_first(ox0, W, w2), xe = resize_first(ox0 + tw - 1u, W, w2) + resize_count(ox0 + tw - 1u, W, w2);
   const uint32_t ys = resize_first(oy0, H, h2), ye = resize_first(oy0 + th - 1u, H, h2) + resize_count(oy0 + th - 1u, H, h2);
   // The staged rows: packed pixels as they lie in memory, else a run of bytes per channel; `cap` pixels fit, a longer
   // segment goes in chunks of a single row
-  const bool packed = a.cls == kResizePacked;
-  const unsigned lstep = packed ? a.pix_step : 1u;
+  const bool packed = cls == kResizePacked;
+  const unsigned lstep = packed ? pix_step : 1u;
   const unsigned cap = packed ? kStageBytes / lstep : (kStageBytes / channels) & ~3u;
   const unsigned seg = xe - xs, clen_max = min(seg, cap);
   const unsigned cpitch = packed ? 0u : align4(clen_max);
@@ -141,14 +178,16 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             if (c >= static_cast<int>(channels)) continue;
-            if (a.cls == kResizePlanes) {
+            if (kYuv || cls == kResizePlanes) {
               stage_bytes(row + d.off[c] + xc, l + c * cpitch, clen, slane, slanes);
               continue;
             }
             // the float formats element by element: never an element that is not a used sample of a pixel of the picture
-            for (unsigned k = slane; k < clen; k += slanes) {
-              l[c * cpitch + k] = static_cast<uint8_t>(sjpeg_internal::elem_load_u8(
-                  row + d.off[c] + static_cast<long long>(xc + k) * a.pix_step, a.kind, a.pscale[c], a.pbias[c]));
+            if constexpr (!kYuv) {
+              for (unsigned k = slane; k < clen; k += slanes) {
+                l[c * cpitch + k] = static_cast<uint8_t>(sjpeg_internal::elem_load_u8(
+                    row + d.off[c] + static_cast<long long>(xc + k) * a.pix_step, a.kind, a.pscale[c], a.pbias[c]));
+              }
             }
           }
         }
@@ -162,12 +201,14 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
           const uint32_t w = resize_weight(ox0 + j, x, W, w2);
           const uint8_t* const px = stage + r * rpitch + (x - xc) * lstep;
           h[0] += w * px[coff[0]];
-          if (channels == 3u) { h[1] += w * px[coff[1]]; h[2] += w * px[coff[2]]; }
+          if (three) { h[1] += w * px[coff[1]]; h[2] += w * px[coff[2]]; }
+          if (two) h[1] += w * px[coff[1]];
         }
         if (!last) continue;
         for (unsigned m = P >> 1; m != 0u; m >>= 1) {
           h[0] += __shfl_xor(h[0], m);
-          if (channels == 3u) { h[1] += __shfl_xor(h[1], m); h[2] += __shfl_xor(h[2], m); }
+          if (three) { h[1] += __shfl_xor(h[1], m); h[2] += __shfl_xor(h[2], m); }
+          if (two) h[1] += __shfl_xor(h[1], m);
         }
         if (col && p == 0u) {
           // source row y into the resized row at hand; the row that ends it may begin the next
@@ -178,10 +219,11 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
           if ((y + 1u) * h2 >= (yo + 1u) * H) {
             uint8_t* const o = tile + (yo - oy0) * tpitch + j * channels;
             o[0] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[0], W, H));
-            if (channels == 3u) {
+            if (three) {
               o[1] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[1], W, H));
               o[2] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[2], W, H));
             }
+            if (two) o[1] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[1], W, H));
             ++yo;
             const uint32_t wn = yo < oy0 + th ? resize_weight(yo, y, H, h2) : 0u;
 #pragma unroll
@@ -194,7 +236,7 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
   }
   // the tile as whole dwords of the resized rows: its first byte is a multiple of 4 (tw is), its last dword may reach
   // into the row's padding, never past it
-  if (orient <= 1) {
+  if (orient <= 1 && !two) {
     const unsigned ndw = (tw * channels + 3u) >> 2;
     for (unsigned i = tid; i < th * ndw; i += 256u) {
       const unsigned r = i / ndw, k = i - r * ndw;
@@ -212,28 +254,37 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const ResizeArgs a) 
   sjpeg_internal::orient_upright(ox0 + tw - 1u, oy0 + th - 1u, w2, h2, orient, &bx, &by);
   const uint32_t ux0 = min(ax, bx), uy0 = min(ay, by);
   const bool flipx = ax > bx, flipy = ay > by;
-  const unsigned nsamp = transposed ? th : tw, nrows = transposed ? tw : th, span = nsamp * channels;
-  // byte k of the tile's span of its destination row q
-  auto span_byte = [&](unsigned q, unsigned k) -> uint32_t {
-    const unsigned s = channels == 3u ? k / 3u : k, c = k - s * channels;
-    const unsigned along = flipx ? nsamp - 1u - s : s, across = flipy ? nrows - 1u - q : q;
-    const unsigned r = transposed ? along : across, jj = transposed ? across : along;
-    return tile[r * tpitch + jj * channels + c];
-  };
+  // (a packed pair's tile leaves as two planes of one-byte samples: `och` bytes a sample where it lands, channel c0 of
+  // the tile's `channels` first; else the sample's bytes as they lie in the tile)
+  const unsigned och = kYuv ? 1u : channels;
+  const unsigned nsamp = transposed ? th : tw, nrows = transposed ? tw : th, span = nsamp * och;
   // Dwords inside the span, bytes at its two ends.  The pictures start at multiples of 16 and their rows are whole
   // dwords apart, so the span's phase is the same in every row: `head` bytes up to the first dword boundary, nd whole
   // dwords -- every byte of them a sample of this tile --, `tail` bytes behind them.
-  const unsigned head = min((4u - ((ux0 * channels) & 3u)) & 3u, span), nd = (span - head) >> 2, tail = (span - head) & 3u;
+  const unsigned head = min((4u - ((ux0 * och) & 3u)) & 3u, span), nd = (span - head) >> 2, tail = (span - head) & 3u;
   const unsigned units = head + nd + tail;
-  for (unsigned i = tid; i < nrows * units; i += 256u) {
-    const unsigned q = i / units, u = i - q * units;
-    uint8_t* const out = d.dst + static_cast<size_t>(uy0 + q) * d.dst_stride + static_cast<size_t>(ux0) * channels;
-    if (u >= head && u < head + nd) {
-      const unsigned k = head + ((u - head) << 2);
-      *((GlobalOut)(out + k)) = span_byte(q, k) | (span_byte(q, k + 1u) << 8) | (span_byte(q, k + 2u) << 16) | (span_byte(q, k + 3u) << 24);
-    } else {
-      const unsigned k = u < head ? u : head + (nd << 2) + (u - head - nd);
-      ((GlobalOutBytes)(out))[k] = static_cast<uint8_t>(span_byte(q, k));
+  for (unsigned c0 = 0; c0 < (kYuv ? channels : 1u); ++c0) {
+    // byte k of the tile's span of its destination row q
+    auto span_byte = [&](unsigned q, unsigned k) -> uint32_t {
+      const unsigned s = och == 3u ? k / 3u : k, c = k - s * och;
+      const unsigned along = flipx ? nsamp - 1u - s : s, across = flipy ? nrows - 1u - q : q;
+      const unsigned r = transposed ? along : across, jj = transposed ? across : along;
+      return tile[r * tpitch + jj * channels + (kYuv ? c0 : c)];
+    };
+    uint8_t* dst = d.dst;
+    if constexpr (kYuv) {
+      if (c0 != 0u) dst = a.planes[flo].dst2;
+    }
+    for (unsigned i = tid; i < nrows * units; i += 256u) {
+      const unsigned q = i / units, u = i - q * units;
+      uint8_t* const out = dst + static_cast<size_t>(uy0 + q) * d.dst_stride + static_cast<size_t>(ux0) * och;
+      if (u >= head && u < head + nd) {
+        const unsigned k = head + ((u - head) << 2);
+        *((GlobalOut)(out + k)) = span_byte(q, k) | (span_byte(q, k + 1u) << 8) | (span_byte(q, k + 2u) << 16) | (span_byte(q, k + 3u) << 24);
+      } else {
+        const unsigned k = u < head ? u : head + (nd << 2) + (u - head - nd);
+        ((GlobalOutBytes)(out))[k] = static_cast<uint8_t>(span_byte(q, k));
+      }
     }
   }
 }
@@ -305,14 +356,7 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
     d.off[0] = channels == 3 ? L->r_off : 0; d.off[1] = g; d.off[2] = b;
     d.W = fr.width; d.H = fr.height;
     d.w2 = sizes != nullptr ? sizes[f][0] : fr.width; d.h2 = sizes != nullptr ? sizes[f][1] : fr.height;
-    // P lanes a column, the largest power of two up to 64 that W / w' holds: a lane has about one source pixel a row.
-    // th: about 64 source rows a tile, so that the row two tiles share is one in 64.
-    int P = 1;
-    while (P < 64 && 2 * P <= d.W / d.w2) P *= 2;
-    d.tw = 256 / P;
-    const int th = static_cast<int>((64ll * d.h2 + d.H - 1) / d.H);
-    d.th = th < 1 ? 1 : th > 16 ? 16 : th;
-    d.tiles_x = static_cast<unsigned>((d.w2 + d.tw - 1) / d.tw);
+    const unsigned long long frame_tiles = resize_tile_rule(&d);
     // the picture in the buffer is the UPRIGHT one: h' x w' for the orientations that transpose
     d.orient = orientations != nullptr ? orientations[f] : 1u;
     uint32_t uw, uh;
@@ -321,7 +365,7 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
     d.dst = reinterpret_cast<uint8_t*>(at);                       // (from the buffer's start: engine_resize adds it)
     d.tile_base = static_cast<unsigned>(tiles);
     at += reduced_picture_bytes(static_cast<int>(uw), static_cast<int>(uh), channels);
-    tiles += static_cast<unsigned long long>(d.tiles_x) * static_cast<unsigned long long>((d.h2 + d.th - 1) / d.th);
+    tiles += frame_tiles;
     if (tiles > 0x7fffffffull) return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": the batch has too many tiles for one launch");
   }
   plan->bytes = at;
@@ -356,7 +400,15 @@ int resize_ragged_launch(int format, const float* pscale, const float* pbias, co
   a.pix_step = L.plane[0].step * L.esz;
   a.cls = L.kind != kElemU8 ? kResizeElems : (L.one_pitch || a.channels == 1) ? kResizePlanes : kResizePacked;
   for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
-  hipLaunchKernelGGL(resize_ragged_kernel, dim3(tiles), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(resize_ragged_kernel<false>, dim3(tiles), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int yuv_resize_ragged_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st) {
+  YuvResizeArgs a;
+  a.planes = d_planes;
+  a.nplanes = nplanes;
+  hipLaunchKernelGGL(resize_ragged_kernel<true>, dim3(tiles), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

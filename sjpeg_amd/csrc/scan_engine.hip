@@ -3535,6 +3535,13 @@ int sjpeg_internal::engine_pack_begin(sjpeg_hip_engine* e, void* stream) {
 
 // ---- ragged reduction and resize (reduce.hip, resize.hip): the engine's half.  The two share the engine's memory for
 // the pictures they make and for their descriptors; `launch` starts the kernel over the uploaded descriptors.
+template <class Frame>
+static void picture_rebase(Frame& d, uint8_t* base) { d.dst = base + reinterpret_cast<uintptr_t>(d.dst); }
+static void picture_rebase(sjpeg_internal::YuvPlane& p, uint8_t* base) {
+  p.r.dst = base + reinterpret_cast<uintptr_t>(p.r.dst);
+  if (p.channels == 2) p.dst2 = base + reinterpret_cast<uintptr_t>(p.dst2);
+}
+
 template <class Frame, class Launch>
 static int engine_make_pictures(sjpeg_hip_engine* e, const std::string& who, const char* what, std::vector<Frame> desc, size_t bytes,
                                 uint8_t* d_pictures, uint8_t** base, void* stream, Launch launch) {
@@ -3547,7 +3554,7 @@ static int engine_make_pictures(sjpeg_hip_engine* e, const std::string& who, con
     d_pictures = reinterpret_cast<uint8_t*>(e->reduced.p);
   }
   if (base != nullptr) *base = d_pictures;
-  for (Frame& d : desc) d.dst = d_pictures + reinterpret_cast<uintptr_t>(d.dst);
+  for (Frame& d : desc) picture_rebase(d, d_pictures);
   const size_t desc_bytes = sizeof(Frame) * desc.size();
   if (int rc = e->reduce_desc.ensure(desc_bytes / 16 + 1)) return rc;
   if (int rc = upload(e, e->reduce_desc.p, desc.data(), desc_bytes, st)) return rc;
@@ -3571,6 +3578,18 @@ int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, c
   return engine_make_pictures(e, who, "resized", plan.frames, plan.bytes, d_resized, base, stream,
                               [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
     if (resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
+// ... and of the YUV-plane formats: a descriptor per plane, the kernel's other instantiation
+int sjpeg_internal::engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base,
+                                      void* stream) {
+  return engine_make_pictures(e, who, "resized", plan.planes, plan.bytes, d_out, base, stream,
+                              [&](const YuvPlane* d_planes, int n, hipStream_t st) {
+    if (yuv_resize_ragged_launch(d_planes, n, plan.tiles, st) != 0) {
       return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
     }
     return 0;
@@ -3664,6 +3683,37 @@ int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
     }
     if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
     sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
+    *out_format = plan.resized_format;
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ... and the YUV-plane formats: every plane resized and turned as a picture of its own, still ONE launch; the checks
+// of the oriented entry in its order
+int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                    const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
+                                    sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_resize_ragged_yuv_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, d_out, out_frames or out_format == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
+  try {
+    sjpeg_internal::YuvResizePlan plan;
+    if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
+    const SourceLayout* const L = source_layout(format);
+    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    if (int rc = sjpeg_internal::yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
+    if (out_bytes < plan.bytes) {
+      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
+                                        " bytes the resized planes take (sjpeg_hip_resize_ragged_yuv_bytes)");
+    }
+    if (int rc = sjpeg_internal::engine_yuv_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
+    sjpeg_internal::yuv_resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
     *out_format = plan.resized_format;
     return 0;
   } catch (...) {
