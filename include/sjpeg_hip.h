@@ -1035,6 +1035,99 @@ int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* engine, int
                                                    int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                    void* stream);
 
+/* ---- contact sheets: a batch resized, turned and placed into grid pictures ----
+ * A storyboard sprite sheet behind a video scrub bar, a contact sheet, a grid of a network's outputs: ONE JPEG of N
+ * thumbnails in a grid, plus the rectangle of each.  The entries below make the thumbnails of the sections above and
+ * store each straight into its rectangle of a sheet -- no thumbnail exists a second time.
+ *   Sheet size.  SW = 2 * margin + cols * cell_width + (cols - 1) * gutter, SH the same down the rows; both 1..65535.
+ *   Cells and sheets.  Frame f goes to sheet f / (cols * rows), there to cell k = f % (cols * rows): column
+ *     i = k % cols, row j = k / cols, the cell's origin cx = margin + i * (cell_width + gutter), cy the same with j and
+ *     cell_height.  nsheets = ceil(nframes / (cols * rows)), at most 65535; all sheets of a call have one size; the
+ *     unused cells of the last sheet are background.
+ *   The thumbnail of frame f is exactly the picture that exists already: for the RGB-like and gray formats that of
+ *     sjpeg_hip_orient_ragged_src, for the four YUV-plane formats the three planes of sjpeg_hip_resize_ragged_yuv_src,
+ *     made for sizes[f] (the STORED orientation) and orientations[f].  sizes == NULL: the frame is fitted into its
+ *     cell, sizes[f] = sjpeg_hip_fit_size(W, H, box) with box = (cell_width, cell_height) for the orientations 1..4 and
+ *     (cell_height, cell_width) for 5..8 -- never larger: a picture smaller than its cell stays as it is.
+ *   Placement.  uw x uh, the thumbnail's UPRIGHT size, must not exceed the cell; x0 = cx + (cell_width - uw) / 2,
+ *     y0 = cy + (cell_height - uh) / 2 (integer division: the spare sample is on the right and at the bottom).
+ *   4:2:0 (SJPEG_HIP_SRC_YUV420, _NV12, _NV21).  margin, gutter, cell_width and cell_height must be even, and the
+ *     centring offset is rounded down to even: x0 = cx + (((cell_width - uw) / 2) & ~1), y0 likewise.  The chroma planes
+ *     of the thumbnail land at (x0 / 2, y0 / 2) in a chroma sheet of SW / 2 x SH / 2.  They always fit their half
+ *     cell: with e = x0 - cx <= (cell_width - uw) / 2 and cell_width even, e / 2 + ceil(uw / 2) <=
+ *     floor((cell_width - uw) / 2) + ceil(uw / 2) = cell_width / 2.  SJPEG_HIP_SRC_YUV444 has no evenness rule: all
+ *     three planes land at (x0, y0).
+ *   Bytes.  A sheet is `background` everywhere except in those rectangles, which hold the thumbnails' bytes.
+ *     background is given in the bytes the encoder sees (R, G, B; the gray formats: [0]; the YUV-plane formats: Y, U, V)
+ *     and does not pass through the engine's pixel transform.
+ *   THE LAYOUT is that of the resized pictures, per sheet: one interleaved SJPEG_HIP_SRC_RGB / _GRAY plane, or the Y, U,
+ *     V planes of SJPEG_HIP_SRC_YUV420 / _YUV444; rows align4 bytes apart, every plane at a multiple of 16, the sheets
+ *     one after another.  Row padding holds background or anything, plane padding anything.
+ * THE CONTRACT: the JPEG of a sheet is byte for byte what sjpeg_hip_encode_ragged_full_meta_src makes of the sheet so
+ * defined, handed over in the output format.  SJPEG_YUV_AUTO decides on the sheet; the gray formats take 4:0:0 only,
+ * the YUV-plane formats their own mode.
+ *
+ * sjpeg_hip_sheet_size (host only): checks the sheet for the format and gives its size.  SJPEG_HIP_EINVAL, the field
+ *   named: a value out of range, reserved != 0, a sheet size above 65535, an odd value with a 4:2:0 format.
+ * sjpeg_hip_sheet_places (host only; reads no device memory): places[f] = (sheet, x0, y0, uw, uh) -- the #xywh=
+ *   numbers of a storyboard.
+ * sjpeg_hip_sheet_ragged_bytes (host only): the bytes the sheets of a call take, 0 on bad arguments (the last error
+ *   says which).
+ * sjpeg_hip_sheet_ragged_src: the uint8 sheets into d_out (a multiple of 16, `bytes` behind it): a background fill in
+ *   whole dwords, then ONE launch of the resize kernel over every thumbnail's tiles, both on `stream` -- stream order is
+ *   the only ordering relied on.  sheet_frames[s]: sheet s as a frame of *out_format (planes, row strides, SW x SH).
+ *   Ordering and pipelined-mode behaviour: those of sjpeg_hip_orient_ragged_src.
+ * sjpeg_hip_encode_ragged_sheet_src / _sheet_packed_src: the arguments of the _oriented_ / _yuv_resized_ entries plus
+ *   `sheet`; ONE set of entries serves both families of formats.  The frames' out_offset and out_capacity are ignored:
+ *   sheet s is written at d_out + s * out_stride with capacity out_stride (sjpeg_hip_frame_bound of SW x SH is always
+ *   enough); the packed entry has the packed contract of sjpeg_hip_encode_ragged_packed_src over nsheets pictures.
+ *   Both fill d_sizes[nsheets].  params, meta, modes, q_out and value_out count SHEETS where the other entries count
+ *   frames: quant_per_frame and search_per_frame mean per sheet, meta is [nsheets], [1] or NULL.  The sheets go into
+ *   the engine memory of the reduced and resized pictures (counted by sjpeg_hip_engine_scratch_bytes, released by
+ *   sjpeg_hip_engine_trim, SJPEG_HIP_ENOMEM naming the bytes); ONE inner call then codes all sheets.
+ * SJPEG_HIP_EINVAL before any device work: the sheet checks above; every check of the orient / yuv-resize plans, the
+ *   frame named; a thumbnail larger than its cell (the frame, both sizes and the orientation named); `bytes` below
+ *   sjpeg_hip_sheet_ragged_bytes; a d_out that is not a multiple of 16; NULL arguments; out_stride below 1; every check
+ *   of the inner call. */
+typedef struct sjpeg_hip_sheet {
+  int32_t cols, rows;               /* cells a sheet: each >= 1 */
+  int32_t cell_width, cell_height;  /* each 1..65535 */
+  int32_t gutter, margin;           /* between cells / around them: each 0..65535 */
+  uint8_t background[3];            /* R, G, B; gray formats: [0]; YUV-plane formats: Y, U, V */
+  uint8_t reserved;                 /* 0 */
+} sjpeg_hip_sheet;
+int sjpeg_hip_sheet_size(const sjpeg_hip_sheet* sheet, int format, int* width, int* height);
+int sjpeg_hip_sheet_places(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                           const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                           const uint8_t* orientations /*host [nframes], or NULL*/, int32_t (*places)[5] /*host out [nframes]*/);
+size_t sjpeg_hip_sheet_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                    const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                    const uint8_t* orientations /*host [nframes], or NULL*/);
+int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                               const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_sheet* sheet,
+                               const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                               const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                               sjpeg_hip_ragged_frame* sheet_frames /*host out [nsheets]*/, int* nsheets, int* out_format,
+                               void* stream);
+int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                      const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                      const uint8_t* orientations /*host [nframes], or NULL*/,
+                                      const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                      void* d_out, size_t out_stride, uint64_t* d_sizes /*[nsheets]*/,
+                                      int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                             const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                             const uint8_t* orientations /*host [nframes], or NULL*/,
+                                             const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                             void* d_packed, size_t packed_capacity,
+                                             uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
+                                             int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
+                                             void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

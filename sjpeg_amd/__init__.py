@@ -453,6 +453,73 @@ def _orientations_array(who, n, orientations):
     return np.ascontiguousarray(np.clip(np.asarray(vals, dtype=np.int64), 0, 255).astype(np.uint8))
 
 
+class _SheetStruct(C.Structure):
+    """struct sjpeg_hip_sheet (include/sjpeg_hip.h)"""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("cell_width", C.c_int32), ("cell_height", C.c_int32),
+                ("gutter", C.c_int32), ("margin", C.c_int32), ("background", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class Sheet:
+    """A contact sheet's grid (struct sjpeg_hip_sheet): cols x rows cells of cell = (cell_width, cell_height), `gutter`
+    samples between cells and `margin` around them, `background` three bytes as the encoder sees them -- (R, G, B); gray
+    pictures: [0]; YUV frames: (Y, U, V).  Frame f of a call goes to sheet f // (cols * rows), cell f % (cols * rows) in
+    row-major order, centred in its cell (the spare sample on the right and at the bottom)."""
+
+    def __init__(self, cols, rows, cell, gutter=0, margin=0, background=(0, 0, 0)):
+        try:
+            cw, ch = cell
+            bg = [int(b) for b in background]
+        except (TypeError, ValueError):
+            raise SjpegError("Sheet: cell is a pair (width, height), background three bytes")
+        if len(bg) != 3 or any(b < 0 or b > 255 for b in bg):
+            raise SjpegError(f"Sheet: background {background!r} is not three bytes 0..255")
+        self.cols, self.rows, self.cell, self.gutter, self.margin = int(cols), int(rows), (int(cw), int(ch)), int(gutter), int(margin)
+        self.background = tuple(bg)
+
+    def _struct(self):
+        clamp = lambda v: min(max(int(v), -2**31), 2**31 - 1)        # (the library names a bad value)
+        return _SheetStruct(clamp(self.cols), clamp(self.rows), clamp(self.cell[0]), clamp(self.cell[1]), clamp(self.gutter),
+                            clamp(self.margin), (C.c_uint8 * 3)(*self.background), 0)
+
+
+def _sheet_struct(who, sheet):
+    if not isinstance(sheet, Sheet):
+        raise SjpegError(f"{who}: sheet is not a Sheet")
+    return sheet._struct()
+
+
+def sheet_size(sheet, fmt=SRC_RGB):
+    """sjpeg_hip_sheet_size: (SW, SH) of a Sheet for pictures of format fmt, after its checks (the 4:2:0 formats take
+    even cells, gutter and margin)."""
+    w, h = C.c_int(0), C.c_int(0)
+    st = _sheet_struct("sheet_size", sheet)
+    if lib().sjpeg_hip_sheet_size(C.byref(st), int(fmt), C.byref(w), C.byref(h)) != 0:
+        raise SjpegError(lib().sjpeg_hip_last_error().decode())
+    return int(w.value), int(h.value)
+
+
+def sheet_places(sheet, dims, fmt=SRC_RGB, sizes=None, orientations=None):
+    """sjpeg_hip_sheet_places: [(sheet, x0, y0, uw, uh)] of pictures of dims[k] = (w, h) -- the #xywh= numbers of a
+    storyboard.  sizes[k] = (w, h) in the STORED orientation (None: every picture fitted into its cell), orientations
+    EXIF 1..8 (None: all 1).  Host only: no device memory is read."""
+    n = len(dims)
+    if n == 0:
+        raise SjpegError("sheet_places: no pictures")
+    frames = (RaggedFrame * n)()
+    for k, (w, h) in enumerate(dims):
+        frames[k].width, frames[k].height = int(w), int(h)
+    arr = None if sizes is None else _sizes_array("sheet_places", sizes)
+    oarr = None if orientations is None else _orientations_array("sheet_places", n, orientations)
+    if arr is not None and len(arr) != n:
+        raise SjpegError("sheet_places: one size per picture")
+    st = _sheet_struct("sheet_places", sheet)
+    out = np.zeros((n, 5), np.int32)
+    if lib().sjpeg_hip_sheet_places(int(fmt), n, frames, C.addressof(st), None if arr is None else arr.ctypes.data,
+                                    None if oarr is None else oarr.ctypes.data, out.ctypes.data) != 0:
+        raise SjpegError(lib().sjpeg_hip_last_error().decode())
+    return [tuple(int(v) for v in row) for row in out]
+
+
 class RaggedFrame(C.Structure):
     """struct sjpeg_hip_ragged_frame (include/sjpeg_hip.h): one picture of a ragged batch."""
     _fields_ = [("plane", C.c_void_p * 3), ("row_stride", C.c_int64 * 3), ("width", C.c_int32),
@@ -718,6 +785,22 @@ def lib() -> C.CDLL:
     L.sjpeg_hip_encode_ragged_yuv_resized_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_src.argtypes)
     L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.restype = C.c_int
     L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
+    L.sjpeg_hip_sheet_size.restype = C.c_int
+    L.sjpeg_hip_sheet_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sjpeg_hip_sheet_places.restype = C.c_int
+    L.sjpeg_hip_sheet_places.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_sheet_ragged_bytes.restype = C.c_size_t
+    L.sjpeg_hip_sheet_ragged_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_sheet_ragged_src.restype = C.c_int
+    L.sjpeg_hip_sheet_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.POINTER(RaggedFrame), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.c_void_p]
+    plain = list(L.sjpeg_hip_encode_ragged_oriented_src.argtypes)           # (..., d_out, d_sizes, ...)
+    L.sjpeg_hip_encode_ragged_sheet_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_sheet_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:10] + [C.c_size_t] + plain[10:]
+    plain = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
+    L.sjpeg_hip_encode_ragged_sheet_packed_src.restype = C.c_int
+    L.sjpeg_hip_encode_ragged_sheet_packed_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
     L.sjpeg_hip_exif_orientation.argtypes = [C.c_void_p, C.c_size_t]
     L.sjpeg_hip_exif_orientation.restype = C.c_int
     L.sjpeg_hip_exif_reset_orientation.argtypes = [C.c_void_p, C.c_size_t]
@@ -771,6 +854,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_exif_orientation", "sjpeg_hip_exif_reset_orientation",
     "sjpeg_hip_yuv_plane_size", "sjpeg_hip_resize_ragged_yuv_bytes", "sjpeg_hip_resize_ragged_yuv_src",
     "sjpeg_hip_encode_ragged_yuv_resized_src", "sjpeg_hip_encode_ragged_yuv_resized_packed_src",
+    "sjpeg_hip_sheet_size", "sjpeg_hip_sheet_places", "sjpeg_hip_sheet_ragged_bytes", "sjpeg_hip_sheet_ragged_src",
+    "sjpeg_hip_encode_ragged_sheet_src", "sjpeg_hip_encode_ragged_sheet_packed_src",
 ]
 
 
@@ -2199,6 +2284,133 @@ class Engine:
                                             yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
                                             capacities, packed_capacity, out, metadata)
 
+    def sheet_ragged(self, fmt, planes_per_frame, dims, sheet, sizes=None, orientations=None, out=None):
+        """sjpeg_hip_sheet_ragged_src: the pictures of a ragged batch (any format the resize entries take, the YUV-plane
+        ones included) resized to sizes[k] (None: fitted into their cells), turned upright by orientations[k] and stored
+        into their cells of contact sheets of the Sheet `sheet`: a background fill and one launch of the resize kernel.
+        Returns (out_fmt, sheets, buf): sheet s a uint8 view into buf -- [SH, SW, 3] (SRC_RGB), [SH, SW] (SRC_GRAY) or a
+        tuple (y, u, v) of planes (SRC_YUV420 / SRC_YUV444) --, rows padded to a multiple of 4 bytes.  out: a contiguous
+        uint8 CUDA tensor of at least sjpeg_hip_sheet_ragged_bytes bytes at a multiple of 16 (None: made here)."""
+        import torch
+        who = "sheet_ragged"
+        n = len(dims)
+        if sizes is not None and len(sizes) != n:
+            raise SjpegError(f"{who}: one size per frame")
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        st = _sheet_struct(who, sheet)
+        arr = None if sizes is None else _sizes_array(who, sizes)
+        oarr = None if orientations is None else _orientations_array(who, n, orientations)
+        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
+        need = lib().sjpeg_hip_sheet_ragged_bytes(fmt, n, frames, C.addressof(st), sp, op)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor")
+        per = max(int(sheet.cols) * int(sheet.rows), 1)
+        made = (RaggedFrame * max((n + per - 1) // per, 1))()
+        ns, rfmt = C.c_int(0), C.c_int(-1)
+        # (a batch the library refuses has need == 0: the call below says why)
+        self._chk(lib().sjpeg_hip_sheet_ragged_src(self._h, fmt, n, frames, C.addressof(st), sp, op, out.data_ptr(),
+                                                   int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt),
+                                                   self._stream()), "sjpeg_hip_sheet_ragged_src")
+        sheets = []
+        for r in list(made)[:ns.value]:
+            at = [out.storage_offset() + int(r.plane[c] or 0) - out.data_ptr() for c in range(3)]
+            if rfmt.value == SRC_RGB:
+                sheets.append(out.as_strided((r.height, r.width, 3), (int(r.row_stride[0]), 3, 1), at[0]))
+            elif rfmt.value == SRC_GRAY:
+                sheets.append(out.as_strided((r.height, r.width), (int(r.row_stride[0]), 1), at[0]))
+            else:
+                planes = []
+                for c in range(3):
+                    pw, ph = yuv_plane_size(rfmt.value, r.width, r.height, c)
+                    planes.append(out.as_strided((ph, pw), (int(r.row_stride[c]), 1), at[c]))
+                sheets.append(tuple(planes))
+        return int(rfmt.value), sheets, out
+
+    def _sheet_args(self, who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search,
+                    metadata):
+        """what the two sheet encodes share: the arrays (params and metadata count SHEETS), the sheets' number and bound"""
+        n = len(dims)
+        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
+            raise SjpegError(f"{who}: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
+        st = _sheet_struct(who, sheet)
+        sw, sh = sheet_size(sheet, fmt)
+        ns = (n + sheet.cols * sheet.rows - 1) // (sheet.cols * sheet.rows)
+        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args(who, ns, metadata)
+        capacity = frame_bound(sw, sh, bound_mode, 2048 + max(msizes))
+        q, per_frame, mq, sarr, search_per_frame, _ = _ragged_args(who, ns, quant, min_quant, search, bound_mode, [capacity] * ns,
+                                                                   [(sw, sh)] * ns)
+        arr = None if sizes is None else _sizes_array(who, sizes)
+        oarr = None if orientations is None else _orientations_array(who, n, orientations)
+        return st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame
+
+    def encode_ragged_sheet(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
+                            min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, out_stride=None, out=None,
+                            metadata=None):
+        """sjpeg_hip_encode_ragged_sheet_src: the JPEGs of the contact sheets Engine.sheet_ragged makes of the same
+        arguments, each byte for byte what encode_ragged_full makes of that sheet.  quant, search and metadata are one
+        for all or one per SHEET; yuv_mode any SjpegYUVMode for RGB-like pictures (YUV_AUTO decides on the sheet), YUV_400
+        for gray ones, the format's own for YUV frames.  Sheet s is written at out[s * out_stride:] (default: the bound
+        of a sheet).  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full, one entry per sheet."""
+        import torch
+        who = "encode_ragged_sheet"
+        st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
+            who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search, metadata)
+        n = len(dims)
+        out_stride = (capacity + 15) & ~15 if out_stride is None else int(out_stride)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < out_stride * ns:
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of out_stride bytes a sheet")
+        sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
+        self._chk(lib().sjpeg_hip_encode_ragged_sheet_src(
+            self._h, fmt, n, frames, C.byref(params), C.addressof(st), None if arr is None else arr.ctypes.data,
+            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
+            out.data_ptr(), out_stride, sizes_out.data_ptr(), modes, q_out, v_out, self._stream()),
+            "sjpeg_hip_encode_ragged_sheet_src")
+        return out, sizes_out, [s * out_stride for s in range(ns)], [int(m) for m in modes], list(q_out), list(v_out)
+
+    def encode_ragged_sheet_packed(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
+                                   min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
+                                   packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_sheet_packed_src: encode_ragged_sheet into ONE packed buffer, the sheets back to back,
+        with the layout of encode_ragged_full_packed over the sheets.  Returns (out, sizes, offsets, modes, q, value):
+        sizes [nsheets] and offsets [nsheets + 1] device tensors."""
+        import torch
+        who = "encode_ragged_sheet_packed"
+        st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
+            who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search, metadata)
+        n = len(dims)
+        dev = _ragged_device(planes_per_frame)
+        if packed_capacity is None:
+            packed_capacity = int(out.numel()) if out is not None else ns * ((capacity + 15) & ~15)
+        packed_capacity = int(packed_capacity)
+        if out is None:
+            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+        meta = torch.zeros(2 * ns + 1, dtype=torch.int64, device=dev)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
+        self._chk(lib().sjpeg_hip_encode_ragged_sheet_packed_src(
+            self._h, fmt, n, frames, C.byref(params), C.addressof(st), None if arr is None else arr.ctypes.data,
+            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
+            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), modes, q_out, v_out, self._stream()),
+            "sjpeg_hip_encode_ragged_sheet_packed_src")
+        return out, meta[:ns], meta[ns:], list(modes), list(q_out), list(v_out)
+
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
         _full_packed call -- [most passes any frame ran, measurement launches, host waits, frames whose stream replays
@@ -2868,6 +3080,148 @@ def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+
+
+def _sheet_pictures(who, images, layout):
+    """(planes, dims, device, format, FloatPixels or None) of the pictures a sheet call takes: those of resize_images"""
+    import torch
+    chw = _check_layout(who, layout)
+    if isinstance(images, (Reduced, Resized, Oriented)):
+        raise SjpegError(f"{who}: Reduced, Resized and Oriented pictures are not taken: give sizes and orientations to the call")
+    images, fp = _float_pixels(who, images, chw)
+    images = list(images)
+    if not images:
+        raise SjpegError(f"{who}: no images")
+    if chw:
+        planes, dims, dev, fmt = _chw_planes(who, images, fp)
+        return planes, dims, dev, fmt, fp
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
+                im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+            raise SjpegError(f"{who}: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+        if im.device != images[0].device:
+            raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {images[0].device}")
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    return planes, dims, images[0].device, SRC_RGB, fp
+
+
+def _per_picture(who, n, orientations):
+    if orientations is not None and not isinstance(orientations, (list, tuple, np.ndarray)):
+        orientations = [orientations] * n
+    return None if orientations is None else [int(o) for o in _orientations_array(who, n, orientations)]
+
+
+def make_sheets(images, sheet, sizes=None, orientations=None, engine=None, layout="hwc"):
+    """The uint8 contact sheets of a batch, as views of ONE device buffer: images as resize_images takes them
+    (layout="hwc": CUDA uint8 tensors [H_k, W_k, 3]; "chw": channel-first uint8 tensors or a FloatPixels -- a network's
+    [N, 3, H, W] float output), each resized to sizes[k] = (w, h) in the stored orientation (None: fitted into its cell,
+    never enlarged), turned upright by orientations (one EXIF value 1..8 or one per picture) and stored centred into its
+    cell of the Sheet -- a background fill and one launch, no thumbnail made a second time.  Returns uint8 CUDA tensors
+    [SH, SW, 3] (gray FloatPixels: [SH, SW]), rows padded to a multiple of 4 bytes; sheet_places gives the rectangles."""
+    import torch
+    who = "make_sheets"
+    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout)
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    with torch.cuda.device(dev):
+        _, sheets, _ = eng.sheet_ragged(fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations))
+        if engine is None:
+            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
+    return sheets
+
+
+def _sheet_search(who, ns, target_size, target_psnr):
+    if target_size is not None and target_psnr is not None:
+        raise SjpegError(f"{who}: give target_size or target_psnr, not both")
+    target = target_size if target_size is not None else target_psnr
+    if target is None:
+        return None
+    ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * ns
+    if len(ts) != ns:
+        raise SjpegError(f"{who}: one target per sheet")
+    mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
+    return [SearchParams(mode, float(t), 10, 1.0, 0.0, 100.0) for t in ts]
+
+
+def _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, quality, method, use_trellis,
+                   target_size, target_psnr, packed, metadata):
+    """the rest of encode_sheets / encode_yuv_sheets: (list of JPEG bytes, places)"""
+    import torch
+    n = len(dims)
+    places = sheet_places(sheet, dims, fmt, sizes, orientations)
+    ns = places[-1][0] + 1
+    method = int(method)
+    if use_trellis:
+        method = {4: 7, 6: 8}.get(method, method)
+    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * ns
+    if len(qs) != ns:
+        raise SjpegError(f"{who}: one quality per sheet")
+    search = _sheet_search(who, ns, target_size, target_psnr)
+    with torch.cuda.device(dev):
+        if packed:
+            out, sz, offs, _, _, _ = eng.encode_ragged_sheet_packed(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
+                                                                    _quality_quant(qs), method, search=search, metadata=metadata)
+            eng.wait()
+            meta = torch.cat([sz, offs]).cpu().numpy()
+            sz, offs = meta[:ns], meta[ns:2 * ns]
+            if (sz <= 0).any():
+                raise SjpegError("sheet %d did not fit its output capacity (the device reported size 0)" % int(np.argmax(sz <= 0)))
+            top = int(max(offs[k] + sz[k] for k in range(ns)))
+            host = out[:top].cpu().numpy()                    # the ONE copy of the sheets
+            return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(ns)], places
+        out, sz, offs, _, _, _ = eng.encode_ragged_sheet(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
+                                                         _quality_quant(qs), method, search=search, metadata=metadata)
+        eng.wait()                               # (pipelined mode: the output is complete after this)
+        return _fetch_ragged(out, sz, offs), places
+
+
+def encode_sheets(images, sheet, sizes=None, orientations=None, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_trellis=False,
+                  target_size=None, target_psnr=None, packed=False, metadata=None, layout="hwc", engine=None):
+    """The contact-sheet call: (JPEGs, places) -- the JPEGs (list of bytes, one per sheet) of the sheets make_sheets makes
+    of the same pictures, each byte for byte what encode_images_full makes of that sheet, and places[k] = (sheet, x, y, w,
+    h), the rectangle of picture k (a storyboard's #xywh=).  quality, target_size / target_psnr and metadata: one for all
+    sheets or one per SHEET; yuv_mode as encode_images_full (YUV_AUTO decides on the sheet; gray FloatPixels: YUV_400);
+    use_trellis maps method 4 to 7 and 6 to 8; packed=True: through the packed entry and one device-to-host copy."""
+    who = "encode_sheets"
+    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout)
+    _gray_mode(who, fmt, int(yuv_mode))
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    return _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations), int(yuv_mode),
+                          quality, method, use_trellis, target_size, target_psnr, packed, metadata)
+
+
+def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations=None, quality=75.0, method=4,
+                      target_size=None, target_psnr=None, packed=False, metadata=None, engine=None):
+    """encode_sheets for decoded video, shaped like encode_yuv_frames: frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 or
+    (y, u, v) for SRC_YUV420 / SRC_YUV444, each resized plane by plane (sizes None: fitted into its cell), turned and
+    stored into its cell -- chroma at half the luma's place for the 4:2:0 formats, whose Sheet takes even cells, gutter
+    and margin; background is (Y, U, V).  No colour conversion: the sheets are coded 4:2:0 (SRC_YUV444: 4:4:4).
+    Returns (JPEGs, places) as encode_sheets -- the storyboard behind a scrub bar in one call."""
+    import torch
+    who = "encode_yuv_sheets"
+    frames = [tuple(fr) for fr in frames]
+    n = len(frames)
+    if n == 0:
+        raise SjpegError(f"{who}: no frames")
+    nplanes = 2 if fmt in (SRC_NV12, SRC_NV21) else 3 if fmt in (SRC_YUV420, SRC_YUV444) else 0
+    if nplanes == 0:
+        raise SjpegError(f"{who}: fmt {fmt} is not SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444")
+    for k, fr in enumerate(frames):
+        if len(fr) != nplanes:
+            raise SjpegError(f"{who}: frame {k} has {len(fr)} planes, the format takes {nplanes}")
+        for p in fr:
+            if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 2 or p.stride(1) != 1:
+                raise SjpegError(f"{who}: frame {k}: a plane is a uint8 CUDA tensor [rows, bytes] with stride 1 along a row")
+    dims = [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames]
+    dev = frames[0][0].device
+    eng = engine or Engine(dev.index or 0)
+    return _encode_sheets(who, eng, dev, fmt, [list(fr) for fr in frames], dims, sheet, sizes, _per_picture(who, n, orientations),
+                          YUV_444 if fmt == SRC_YUV444 else YUV_420, quality, method, False, target_size, target_psnr, packed,
+                          metadata)
 
 
 _packed_stats = {"calls": 0, "retries": 0}

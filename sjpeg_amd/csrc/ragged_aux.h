@@ -211,6 +211,50 @@ int yuv_resize_ragged_launch(const YuvPlane* d_planes, int nplanes, unsigned til
 // the engine's half, as engine_resize
 int engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
 
+// ---- contact sheets (sjpeg_hip_sheet_ragged_src; sheet_plan.cc, resize.hip): the thumbnails of the two plans above,
+// each stored into its rectangle of a larger picture.  A PLACED descriptor's dst (and dst2) is the thumbnail's first
+// sample inside its sheet plane and its dst_stride the sheet plane's; kResizePlaced in its `orient` says so.  The
+// kernel's placed instantiations read such descriptors: every tile leaves by the exact-span store, whose phase comes
+// from the address the span starts at.
+constexpr unsigned kResizePlaced = 0x100u;
+// The background of a call's sheets: sheet s at s * sheet_bytes from the buffer's start, its plane c `off[c]` behind
+// that -- rows[c] rows of row_dwords[c] dwords, dword k of a row pattern[c][k % 3] (an RGB row: a 12-byte pattern
+// whose phase restarts at each row; a one-byte plane: three equal dwords).
+struct SheetFill {
+  size_t sheet_bytes = 0;
+  int nsheets = 0, nplanes = 0;          // 1 (interleaved RGB, gray) or 3 (Y, U, V)
+  size_t off[3] = {0, 0, 0};
+  unsigned rows[3] = {0, 0, 0}, row_dwords[3] = {0, 0, 0};
+  uint32_t pattern[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+};
+struct SheetPlace { int32_t sheet, x0, y0, uw, uh; };   // sjpeg_hip_sheet_places: the #xywh= numbers of a storyboard
+struct SheetPlan {
+  int format = 0, out_format = 0;        // the caller's; SJPEG_HIP_SRC_RGB, _GRAY, _YUV420 or _YUV444
+  bool yuv = false;                      // which of the two plans holds the (placed) descriptors
+  int nframes = 0, nsheets = 0, width = 0, height = 0;
+  ResizePlan rgb;
+  YuvResizePlan planes;
+  std::vector<SheetPlace> places;        // [nframes]
+  SheetFill fill;
+  size_t bytes = 0;                      // nsheets * fill.sheet_bytes
+};
+// the sheet's fields checked for the format (ranges, `reserved`, the size, evenness for a 4:2:0 format: the field is
+// named); its size
+int sheet_check(const std::string& who, const sjpeg_hip_sheet* sheet, int format, int* width, int* height);
+// The sheet checked, the thumbnails planned by resize_plan / yuv_resize_plan (sizes == NULL: each fitted into its
+// cell) -- their checks, their tile rule, their descriptors --, every thumbnail held to its cell, then each descriptor
+// rewritten to its place.
+int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_sheet* sheet,
+               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan);
+// the sheets as frames of plan.out_format at `base` (out_offset, out_capacity: 0)
+void sheet_plan_frames(const SheetPlan& plan, uint8_t* base, sjpeg_hip_ragged_frame* out /*[nsheets]*/);
+int sheet_fill_launch(const SheetFill& fill, uint8_t* base, hipStream_t st);
+int resize_ragged_placed_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
+                                hipStream_t st);
+int yuv_resize_ragged_placed_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
+// the engine's half, as engine_resize: the background fill, then the placed resize, both on `stream`
+int engine_sheet(sjpeg_hip_engine* e, const std::string& who, const SheetPlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
+
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
 // out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's

@@ -1175,6 +1175,95 @@ int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* e, int form
                           value_out, stream, &sink);
 }
 
+// ---- ... and on contact sheets: the batch resized, turned and placed into grid pictures (sheet_plan.cc) ----
+// Every check first, host only; the background fill and the placed resize into the engine's memory for reduced and
+// resized pictures; ONE inner flow over the SHEETS, read as the plan's output format.  params, meta, modes, q_out and
+// value_out count sheets.  sink == NULL: sheet s at d_out + s * out_stride, capacity out_stride.
+static int sheet_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
+                      uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream, sjpeg_internal::PackedSink* sink) {
+  try {
+    sjpeg_internal::SheetPlan plan;
+    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan)) return rc;
+    const SourceLayout* const L = source_layout(format);
+    if (L->implied != 0 && params->yuv_mode != L->implied) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + (plan.yuv ? "" : " (gray pictures are coded 4:0:0 only)"));
+    }
+    // (the source frames' output ranges are not read: the sheets' are the call's)
+    std::vector<sjpeg_hip_ragged_frame> src(frames, frames + nframes);
+    for (sjpeg_hip_ragged_frame& f : src) { f.out_offset = 0; f.out_capacity = 0; }
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, src.data())) return rc;
+    const int ns = plan.nsheets;
+    if (sink == nullptr && out_stride > UINT64_MAX / static_cast<uint64_t>(ns)) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": out_stride * nsheets overflows");
+    }
+    sjpeg_internal::MetaCtx ctx;
+    if (meta != nullptr) { if (int rc = check_metadata(who, ns, meta, meta_per_frame, &ctx)) return rc; }
+    auto made_sheets = [&](uint8_t* base, std::vector<sjpeg_hip_ragged_frame>* made) {
+      made->resize(static_cast<size_t>(ns));
+      sjpeg_internal::sheet_plan_frames(plan, base, made->data());
+      for (int k = 0; k < ns; ++k) {
+        (*made)[k].out_offset = sink != nullptr ? 0 : static_cast<uint64_t>(k) * out_stride;
+        // (packed: a sheet may take what is always enough for it)
+        const size_t header = 2048 + (meta != nullptr && !ctx.entries.empty() ? ctx.of(k).block.size() : 0);
+        (*made)[k].out_capacity = sink != nullptr ? sjpeg_hip_frame_bound(plan.width, plan.height, SJPEG_HIP_YUV444, header) : out_stride;
+      }
+    };
+    // (the inner flow's own checks on the sheets, standing at a placeholder address until there is memory)
+    std::vector<sjpeg_hip_ragged_frame> made;
+    made_sheets(reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), &made);
+    if (int rc = full_checks(who, plan.out_format, ns, made.data(), *params)) return rc;
+    if (sink != nullptr) sink->nframes = ns;
+    // ---- device work
+    uint8_t* base = nullptr;
+    if (int rc = sjpeg_internal::engine_sheet(e, who, plan, nullptr, &base, stream)) return rc;
+    made_sheets(base, &made);
+    const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
+    return full_flow(who, e, plan.out_format, ns, made.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                      size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (sheet == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": sheet == NULL");
+  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (out_stride < 1) return set_error(SJPEG_HIP_EINVAL, who + ": out_stride must be at least 1");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_out, out_stride, d_sizes,
+                    modes, q_out, value_out, stream, nullptr);
+}
+
+int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                             int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                             uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_packed_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (sheet == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": sheet == NULL");
+  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
+  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};   // (nframes: the sheets', set by the flow)
+  return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_packed, 0, d_sizes, modes,
+                    q_out, value_out, stream, &sink);
+}
+
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {
   if (e == nullptr || stats == nullptr) return set_error(SJPEG_HIP_EINVAL, "sjpeg_hip_engine_search_stats: engine or stats == NULL");
   memcpy(stats, sjpeg_internal::engine_full_stats(e), 6 * sizeof(uint64_t));

@@ -27,6 +27,9 @@
 // the flat grid over the tiles of every PLANE of every frame, each plane resized and turned as a gray picture of its
 // own.  The UV plane of NV12 / NV21 is a packed picture of two-byte pixels: staged once, summed as two channels, its
 // finished tile stored as two planes.
+//
+// Contact sheets (sjpeg_hip_sheet_ragged_src; sheet_plan.cc): sheet_fill_kernel writes the sheets' background, then the
+// kernel's PLACED instantiations store every thumbnail's tiles into its rectangle of a sheet plane.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -105,7 +108,11 @@ __device__ __forceinline__ const ResizeFrame& desc_at(const YuvResizeArgs& a, in
 // plane; what differs is decided at compile time, so either instantiation holds its own work alone.  A two-channel
 // plane is staged ONCE, as the packed pixels it is, summed as two channels and rounded into a tile of pairs; the tile
 // leaves as two planes, U to the descriptor's dst and V to its dst2, each by the turned store's rule.
-template <bool kYuv>
+// kPlaced: the descriptors are PLACED ones (ragged_aux.h: contact sheets) -- dst is the picture's first sample inside
+// a larger plane, so every tile, an unturned frame's too, leaves by the exact-span store: the whole-dword store
+// reaches into what is row padding in a picture of its own and is the next cell or the gutter in a sheet.  A
+// compile-time flag: the unplaced instantiations hold what they held before there were sheets.
+template <bool kYuv, bool kPlaced>
 __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv>::type a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
 
   // the tile's rows in LDS, whole dwords; a transposing frame reads a destination row down a column of them, so its
   // pitch is an odd number of dwords: the th <= 16 rows of a column lie in th different banks
-  const int orient = static_cast<int>(d.orient);
+  const int orient = static_cast<int>(kPlaced ? d.orient & ~sjpeg_internal::kResizePlaced : d.orient);
   const bool transposed = sjpeg_internal::orient_transposes(orient);
   const unsigned tpitch = align4(static_cast<unsigned>(d.tw) * channels) | (transposed ? 4u : 0u);
   for (unsigned i = tid; i < th * tpitch / 4u; i += 256u) reinterpret_cast<uint32_t*>(tile)[i] = 0u;   // (the rows' padding)
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   }
   // the tile as whole dwords of the resized rows: its first byte is a multiple of 4 (tw is), its last dword may reach
   // into the row's padding, never past it
-  if (orient <= 1 && !two) {
+  if (!kPlaced && orient <= 1 && !two) {
     const unsigned ndw = (tw * channels + 3u) >> 2;
     for (unsigned i = tid; i < th * ndw; i += 256u) {
       const unsigned r = i / ndw, k = i - r * ndw;
@@ -260,8 +267,12 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   const unsigned nsamp = transposed ? th : tw, nrows = transposed ? tw : th, span = nsamp * och;
   // Dwords inside the span, bytes at its two ends.  The pictures start at multiples of 16 and their rows are whole
   // dwords apart, so the span's phase is the same in every row: `head` bytes up to the first dword boundary, nd whole
-  // dwords -- every byte of them a sample of this tile --, `tail` bytes behind them.
-  const unsigned head = min((4u - ((ux0 * och) & 3u)) & 3u, span), nd = (span - head) >> 2, tail = (span - head) & 3u;
+  // dwords -- every byte of them a sample of this tile --, `tail` bytes behind them.  A placed picture starts at any
+  // byte of its sheet plane, so its phase is taken from the address the span starts at, the low two bits of
+  // dst + ux0 * och; the sheet planes start at multiples of 16 and their rows are whole dwords apart, so the phase is
+  // still the same in every row of a tile -- and the same for dst2: V's sheet plane is laid out as U's, 16 bytes a step.
+  const unsigned lead = kPlaced ? static_cast<unsigned>(reinterpret_cast<uintptr_t>(d.dst)) & 3u : 0u;
+  const unsigned head = min((4u - ((lead + ux0 * och) & 3u)) & 3u, span), nd = (span - head) >> 2, tail = (span - head) & 3u;
   const unsigned units = head + nd + tail;
   for (unsigned c0 = 0; c0 < (kYuv ? channels : 1u); ++c0) {
     // byte k of the tile's span of its destination row q
@@ -289,107 +300,42 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   }
 }
 
-const char* yuv_format_name(int format) {
-  switch (format) {
-    case SJPEG_HIP_SRC_YUV444: return "SJPEG_HIP_SRC_YUV444";
-    case SJPEG_HIP_SRC_YUV420: return "SJPEG_HIP_SRC_YUV420";
-    case SJPEG_HIP_SRC_NV12: return "SJPEG_HIP_SRC_NV12";
-    case SJPEG_HIP_SRC_NV21: return "SJPEG_HIP_SRC_NV21";
-    default: return "this format";
+// The background of a call's sheets (sjpeg_hip_sheet_ragged_src), launched on the call's stream in front of the placed
+// resize: every sample of every sheet plane in whole dwords, row padding included -- a plane's rows are whole dwords
+// apart, so its rows * row_dwords dwords lie back to back from its start, a multiple of 16, and end inside the plane.
+// Dword k of a row is pattern[k % 3]: an RGB row is a 12-byte pattern whose phase restarts at each row.  A grid-stride
+// loop over the dwords of all sheets; adjacent lanes store adjacent dwords.
+struct SheetFillArgs {
+  uint8_t* base;
+  unsigned long long sheet_bytes, per_sheet, total;    // from a sheet to the next; dwords a sheet, and of all sheets
+  unsigned long long first[3], off[3];                 // plane c: its first dword among the sheet's, its place in the sheet
+  unsigned row_dwords[3];
+  uint32_t pattern[3][3];
+  int nplanes;
+};
+
+__global__ __launch_bounds__(256) void sheet_fill_kernel(const SheetFillArgs a) {
+  for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < a.total; i += gridDim.x * 256ull) {
+    const unsigned long long s = i / a.per_sheet;
+    unsigned long long r = i - s * a.per_sheet;
+    const int c = a.nplanes == 3 ? (r >= a.first[2] ? 2 : r >= a.first[1] ? 1 : 0) : 0;
+    r -= c == 2 ? a.first[2] : c == 1 ? a.first[1] : 0ull;
+    const unsigned rd = c == 2 ? a.row_dwords[2] : c == 1 ? a.row_dwords[1] : a.row_dwords[0];
+    const unsigned k = static_cast<unsigned>(r % rd) % 3u;
+    const uint32_t p0 = c == 2 ? a.pattern[2][0] : c == 1 ? a.pattern[1][0] : a.pattern[0][0];
+    const uint32_t p1 = c == 2 ? a.pattern[2][1] : c == 1 ? a.pattern[1][1] : a.pattern[0][1];
+    const uint32_t p2 = c == 2 ? a.pattern[2][2] : c == 1 ? a.pattern[1][2] : a.pattern[0][2];
+    uint8_t* const plane = a.base + s * a.sheet_bytes + (c == 2 ? a.off[2] : c == 1 ? a.off[1] : a.off[0]);
+    ((GlobalOut)(plane))[r] = k == 2u ? p2 : k == 1u ? p1 : p0;
   }
 }
-
-// a format the kernel reads: every RGB-like row of the table and the gray ones
-bool resizable(const sjpeg_internal::SourceLayout& L) { return L.rgb_like || (L.planes == 1 && L.implied == SJPEG_HIP_YUV400); }
 
 }  // namespace
 
 namespace sjpeg_internal {
 
-int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                const uint8_t* orientations, ResizePlan* plan) {
-  const SourceLayout* const L = source_layout(format);
-  if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  bool turned = false;
-  for (int f = 0; f < nframes; ++f) {
-    const sjpeg_hip_ragged_frame& fr = frames[f];
-    const std::string frame = who + ": frame " + std::to_string(f) + ": ";
-    if (fr.width < 1 || fr.height < 1 || fr.width > 65535 || fr.height > 65535) {
-      return set_error(SJPEG_HIP_EINVAL, frame + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
-    }
-    if (orientations != nullptr && (orientations[f] < 1 || orientations[f] > 8)) {
-      return set_error(SJPEG_HIP_EINVAL, frame + "orientation " + std::to_string(orientations[f]) + " is not one of 1..8 (EXIF tag 0x0112)");
-    }
-    turned = turned || (orientations != nullptr && orientations[f] != 1);
-    if (sizes == nullptr) continue;
-    const std::string size = "size " + std::to_string(sizes[f][0]) + "x" + std::to_string(sizes[f][1]);
-    if (sizes[f][0] < 1 || sizes[f][1] < 1) return set_error(SJPEG_HIP_EINVAL, frame + size + " is below 1x1");
-    if (sizes[f][0] > fr.width || sizes[f][1] > fr.height) {
-      return set_error(SJPEG_HIP_EINVAL, frame + size + " is above the source's " + std::to_string(fr.width) + "x" + std::to_string(fr.height) +
-                                             " (pictures are made smaller, never larger)");
-    }
-  }
-  if (!resizable(*L) && turned) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not oriented (an orientation other than 1 takes an RGB-like or a gray format)");
-  }
-  if (!resizable(*L)) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not resized (a size other than the source's takes an RGB-like or a gray format)");
-  }
-  const int channels = L->rgb_like ? 3 : 1;
-  plan->format = format;
-  plan->resized_format = channels == 3 ? SJPEG_HIP_SRC_RGB : SJPEG_HIP_SRC_GRAY;
-  plan->frames.assign(static_cast<size_t>(nframes), ResizeFrame());
-  size_t at = 0;
-  unsigned long long tiles = 0;
-  for (int f = 0; f < nframes; ++f) {
-    const sjpeg_hip_ragged_frame& fr = frames[f];
-    ResizeFrame& d = plan->frames[f];
-    memset(&d, 0, sizeof(d));
-    const uint8_t* planes[3];
-    long long rows[3];
-    layout_planes(*L, fr.plane, fr.row_stride, nullptr, planes, rows, nullptr);
-    d.src = static_cast<const uint8_t*>(fr.plane[0]);
-    d.row_stride = rows[0];
-    long long g = 0, b = 0;
-    if (channels == 3) layout_rgb_offsets(*L, fr.plane, &g, &b);
-    d.off[0] = channels == 3 ? L->r_off : 0; d.off[1] = g; d.off[2] = b;
-    d.W = fr.width; d.H = fr.height;
-    d.w2 = sizes != nullptr ? sizes[f][0] : fr.width; d.h2 = sizes != nullptr ? sizes[f][1] : fr.height;
-    const unsigned long long frame_tiles = resize_tile_rule(&d);
-    // the picture in the buffer is the UPRIGHT one: h' x w' for the orientations that transpose
-    d.orient = orientations != nullptr ? orientations[f] : 1u;
-    uint32_t uw, uh;
-    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
-    d.dst_stride = static_cast<unsigned>(reduced_row_stride(static_cast<int>(uw), channels));
-    d.dst = reinterpret_cast<uint8_t*>(at);                       // (from the buffer's start: engine_resize adds it)
-    d.tile_base = static_cast<unsigned>(tiles);
-    at += reduced_picture_bytes(static_cast<int>(uw), static_cast<int>(uh), channels);
-    tiles += frame_tiles;
-    if (tiles > 0x7fffffffull) return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": the batch has too many tiles for one launch");
-  }
-  plan->bytes = at;
-  plan->tiles = static_cast<unsigned>(tiles);
-  return 0;
-}
-
-void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
-  for (size_t f = 0; f < plan.frames.size(); ++f) {
-    const ResizeFrame& d = plan.frames[f];
-    sjpeg_hip_ragged_frame r;
-    memset(&r, 0, sizeof(r));
-    r.plane[0] = base + reinterpret_cast<uintptr_t>(d.dst);
-    r.row_stride[0] = static_cast<int64_t>(d.dst_stride);
-    uint32_t uw, uh;
-    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
-    r.width = static_cast<int32_t>(uw); r.height = static_cast<int32_t>(uh);
-    r.out_offset = frames[f].out_offset; r.out_capacity = frames[f].out_capacity;
-    out[f] = r;
-  }
-}
-
-int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
-                         hipStream_t st) {
+static int resize_launch(bool placed, int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes,
+                         unsigned tiles, hipStream_t st) {
   const SourceLayout& L = *source_layout(format);
   ResizeArgs a;
   memset(&a, 0, sizeof(a));
@@ -400,82 +346,57 @@ int resize_ragged_launch(int format, const float* pscale, const float* pbias, co
   a.pix_step = L.plane[0].step * L.esz;
   a.cls = L.kind != kElemU8 ? kResizeElems : (L.one_pitch || a.channels == 1) ? kResizePlanes : kResizePacked;
   for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
-  hipLaunchKernelGGL(resize_ragged_kernel<false>, dim3(tiles), dim3(256), 0, st, a);
+  if (placed) {
+    hipLaunchKernelGGL((resize_ragged_kernel<false, true>), dim3(tiles), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((resize_ragged_kernel<false, false>), dim3(tiles), dim3(256), 0, st, a);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
+                         hipStream_t st) {
+  return resize_launch(false, format, pscale, pbias, d_frames, nframes, tiles, st);
+}
+int resize_ragged_placed_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
+                                hipStream_t st) {
+  return resize_launch(true, format, pscale, pbias, d_frames, nframes, tiles, st);
 }
 
 int yuv_resize_ragged_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st) {
   YuvResizeArgs a;
   a.planes = d_planes;
   a.nplanes = nplanes;
-  hipLaunchKernelGGL(resize_ragged_kernel<true>, dim3(tiles), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((resize_ragged_kernel<true, false>), dim3(tiles), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int yuv_resize_ragged_placed_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st) {
+  YuvResizeArgs a;
+  a.planes = d_planes;
+  a.nplanes = nplanes;
+  hipLaunchKernelGGL((resize_ragged_kernel<true, true>), dim3(tiles), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int sheet_fill_launch(const SheetFill& fill, uint8_t* base, hipStream_t st) {
+  SheetFillArgs a;
+  a.base = base;
+  a.sheet_bytes = fill.sheet_bytes;
+  a.nplanes = fill.nplanes;
+  unsigned long long at = 0;
+  for (int c = 0; c < 3; ++c) {
+    a.first[c] = at;
+    a.off[c] = fill.off[c];
+    a.row_dwords[c] = c < fill.nplanes ? fill.row_dwords[c] : 1u;
+    for (int k = 0; k < 3; ++k) a.pattern[c][k] = fill.pattern[c][k];
+    if (c < fill.nplanes) at += static_cast<unsigned long long>(fill.rows[c]) * fill.row_dwords[c];
+  }
+  a.per_sheet = at;
+  a.total = at * static_cast<unsigned long long>(fill.nsheets);
+  const unsigned long long blocks = (a.total + 255ull) / 256ull;
+  hipLaunchKernelGGL(sheet_fill_kernel, dim3(static_cast<unsigned>(blocks < (1ull << 20) ? blocks : (1ull << 20))), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace sjpeg_internal
-
-extern "C" {
-
-int sjpeg_hip_fit_size(int width, int height, int box_width, int box_height, int* fitted_width, int* fitted_height) {
-  static const std::string who = "sjpeg_hip_fit_size";
-  if (fitted_width == nullptr || fitted_height == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": fitted_width or fitted_height == NULL");
-  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
-  }
-  if (box_width < 1 || box_height < 1 || box_width > 65535 || box_height > 65535) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad box " + std::to_string(box_width) + "x" + std::to_string(box_height));
-  }
-  const long long W = width, H = height, bw = box_width, bh = box_height;
-  long long w = W, h = H;
-  if (W > bw || H > bh) {
-    if (W * bh >= H * bw) {
-      w = bw; h = (H * bw + W / 2) / W;
-    } else {
-      h = bh; w = (W * bh + H / 2) / H;
-    }
-  }
-  *fitted_width = static_cast<int>(w < 1 ? 1 : w);
-  *fitted_height = static_cast<int>(h < 1 ? 1 : h);
-  return 0;
-}
-
-size_t sjpeg_hip_resize_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2]) {
-  if (frames == nullptr) return 0;
-  try {
-    sjpeg_internal::ResizePlan plan;
-    if (sjpeg_internal::resize_plan("sjpeg_hip_resize_ragged_bytes", format, nframes, frames, sizes, nullptr, &plan) != 0) return 0;
-    return plan.bytes;
-  } catch (...) {
-    return 0;
-  }
-}
-
-int sjpeg_hip_oriented_size(int width, int height, int orientation, int* ow, int* oh) {
-  static const std::string who = "sjpeg_hip_oriented_size";
-  if (ow == nullptr || oh == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": ow or oh == NULL");
-  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
-  }
-  if (orientation < 1 || orientation > 8) {
-    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": orientation " + std::to_string(orientation) + " is not one of 1..8 (EXIF tag 0x0112)");
-  }
-  uint32_t uw, uh;
-  sjpeg_internal::oriented_size(static_cast<uint32_t>(width), static_cast<uint32_t>(height), orientation, &uw, &uh);
-  *ow = static_cast<int>(uw);
-  *oh = static_cast<int>(uh);
-  return 0;
-}
-
-size_t sjpeg_hip_orient_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                                     const uint8_t* orientations) {
-  if (frames == nullptr) return 0;
-  try {
-    sjpeg_internal::ResizePlan plan;
-    if (sjpeg_internal::resize_plan("sjpeg_hip_orient_ragged_bytes", format, nframes, frames, sizes, orientations, &plan) != 0) return 0;
-    return plan.bytes;
-  } catch (...) {
-    return 0;
-  }
-}
-
-}  // extern "C"

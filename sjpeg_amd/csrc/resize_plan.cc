@@ -1,0 +1,186 @@
+// resize_plan.cc -- the host half of the ragged resize of the RGB-like and gray formats (sjpeg_hip_resize_ragged_src,
+// sjpeg_hip_orient_ragged_src; sjpeg_hip.h): the fitted and the upright size, the checks of the sizes and orientations,
+// and the plan -- one descriptor per frame -- that resize.hip's kernel runs over.  Plain C++, no device work: a host
+// compiler reads it as it is (tests/cxx/sheet_plan_test.cc), like yuv_resize_plan.cc beside it.
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "orient_math.h"
+#include "ragged_aux.h"
+#include "reduce_round.h"
+#include "sjpeg_hip.h"
+#include "source_layout.h"
+
+namespace {
+
+using sjpeg_internal::ResizeFrame;
+
+const char* yuv_format_name(int format) {
+  switch (format) {
+    case SJPEG_HIP_SRC_YUV444: return "SJPEG_HIP_SRC_YUV444";
+    case SJPEG_HIP_SRC_YUV420: return "SJPEG_HIP_SRC_YUV420";
+    case SJPEG_HIP_SRC_NV12: return "SJPEG_HIP_SRC_NV12";
+    case SJPEG_HIP_SRC_NV21: return "SJPEG_HIP_SRC_NV21";
+    default: return "this format";
+  }
+}
+
+// a format the kernel reads: every RGB-like row of the table and the gray ones
+bool resizable(const sjpeg_internal::SourceLayout& L) { return L.rgb_like || (L.planes == 1 && L.implied == SJPEG_HIP_YUV400); }
+
+}  // namespace
+
+namespace sjpeg_internal {
+
+int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                const uint8_t* orientations, ResizePlan* plan) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  bool turned = false;
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    const std::string frame = who + ": frame " + std::to_string(f) + ": ";
+    if (fr.width < 1 || fr.height < 1 || fr.width > 65535 || fr.height > 65535) {
+      return set_error(SJPEG_HIP_EINVAL, frame + "bad dimensions " + std::to_string(fr.width) + "x" + std::to_string(fr.height));
+    }
+    if (orientations != nullptr && (orientations[f] < 1 || orientations[f] > 8)) {
+      return set_error(SJPEG_HIP_EINVAL, frame + "orientation " + std::to_string(orientations[f]) + " is not one of 1..8 (EXIF tag 0x0112)");
+    }
+    turned = turned || (orientations != nullptr && orientations[f] != 1);
+    if (sizes == nullptr) continue;
+    const std::string size = "size " + std::to_string(sizes[f][0]) + "x" + std::to_string(sizes[f][1]);
+    if (sizes[f][0] < 1 || sizes[f][1] < 1) return set_error(SJPEG_HIP_EINVAL, frame + size + " is below 1x1");
+    if (sizes[f][0] > fr.width || sizes[f][1] > fr.height) {
+      return set_error(SJPEG_HIP_EINVAL, frame + size + " is above the source's " + std::to_string(fr.width) + "x" + std::to_string(fr.height) +
+                                             " (pictures are made smaller, never larger)");
+    }
+  }
+  if (!resizable(*L) && turned) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not oriented (an orientation other than 1 takes an RGB-like or a gray format)");
+  }
+  if (!resizable(*L)) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + yuv_format_name(format) + " pictures are not resized (a size other than the source's takes an RGB-like or a gray format)");
+  }
+  const int channels = L->rgb_like ? 3 : 1;
+  plan->format = format;
+  plan->resized_format = channels == 3 ? SJPEG_HIP_SRC_RGB : SJPEG_HIP_SRC_GRAY;
+  plan->frames.assign(static_cast<size_t>(nframes), ResizeFrame());
+  size_t at = 0;
+  unsigned long long tiles = 0;
+  for (int f = 0; f < nframes; ++f) {
+    const sjpeg_hip_ragged_frame& fr = frames[f];
+    ResizeFrame& d = plan->frames[f];
+    memset(&d, 0, sizeof(d));
+    const uint8_t* planes[3];
+    long long rows[3];
+    layout_planes(*L, fr.plane, fr.row_stride, nullptr, planes, rows, nullptr);
+    d.src = static_cast<const uint8_t*>(fr.plane[0]);
+    d.row_stride = rows[0];
+    long long g = 0, b = 0;
+    if (channels == 3) layout_rgb_offsets(*L, fr.plane, &g, &b);
+    d.off[0] = channels == 3 ? L->r_off : 0; d.off[1] = g; d.off[2] = b;
+    d.W = fr.width; d.H = fr.height;
+    d.w2 = sizes != nullptr ? sizes[f][0] : fr.width; d.h2 = sizes != nullptr ? sizes[f][1] : fr.height;
+    const unsigned long long frame_tiles = resize_tile_rule(&d);
+    // the picture in the buffer is the UPRIGHT one: h' x w' for the orientations that transpose
+    d.orient = orientations != nullptr ? orientations[f] : 1u;
+    uint32_t uw, uh;
+    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
+    d.dst_stride = static_cast<unsigned>(reduced_row_stride(static_cast<int>(uw), channels));
+    d.dst = reinterpret_cast<uint8_t*>(at);                       // (from the buffer's start: engine_resize adds it)
+    d.tile_base = static_cast<unsigned>(tiles);
+    at += reduced_picture_bytes(static_cast<int>(uw), static_cast<int>(uh), channels);
+    tiles += frame_tiles;
+    if (tiles > 0x7fffffffull) return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": the batch has too many tiles for one launch");
+  }
+  plan->bytes = at;
+  plan->tiles = static_cast<unsigned>(tiles);
+  return 0;
+}
+
+void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
+  for (size_t f = 0; f < plan.frames.size(); ++f) {
+    const ResizeFrame& d = plan.frames[f];
+    sjpeg_hip_ragged_frame r;
+    memset(&r, 0, sizeof(r));
+    r.plane[0] = base + reinterpret_cast<uintptr_t>(d.dst);
+    r.row_stride[0] = static_cast<int64_t>(d.dst_stride);
+    uint32_t uw, uh;
+    oriented_size(static_cast<uint32_t>(d.w2), static_cast<uint32_t>(d.h2), static_cast<int>(d.orient), &uw, &uh);
+    r.width = static_cast<int32_t>(uw); r.height = static_cast<int32_t>(uh);
+    r.out_offset = frames[f].out_offset; r.out_capacity = frames[f].out_capacity;
+    out[f] = r;
+  }
+}
+
+}  // namespace sjpeg_internal
+
+extern "C" {
+
+int sjpeg_hip_fit_size(int width, int height, int box_width, int box_height, int* fitted_width, int* fitted_height) {
+  static const std::string who = "sjpeg_hip_fit_size";
+  if (fitted_width == nullptr || fitted_height == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": fitted_width or fitted_height == NULL");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
+  }
+  if (box_width < 1 || box_height < 1 || box_width > 65535 || box_height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad box " + std::to_string(box_width) + "x" + std::to_string(box_height));
+  }
+  const long long W = width, H = height, bw = box_width, bh = box_height;
+  long long w = W, h = H;
+  if (W > bw || H > bh) {
+    if (W * bh >= H * bw) {
+      w = bw; h = (H * bw + W / 2) / W;
+    } else {
+      h = bh; w = (W * bh + H / 2) / H;
+    }
+  }
+  *fitted_width = static_cast<int>(w < 1 ? 1 : w);
+  *fitted_height = static_cast<int>(h < 1 ? 1 : h);
+  return 0;
+}
+
+size_t sjpeg_hip_resize_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2]) {
+  if (frames == nullptr) return 0;
+  try {
+    sjpeg_internal::ResizePlan plan;
+    if (sjpeg_internal::resize_plan("sjpeg_hip_resize_ragged_bytes", format, nframes, frames, sizes, nullptr, &plan) != 0) return 0;
+    return plan.bytes;
+  } catch (...) {
+    return 0;
+  }
+}
+
+int sjpeg_hip_oriented_size(int width, int height, int orientation, int* ow, int* oh) {
+  static const std::string who = "sjpeg_hip_oriented_size";
+  if (ow == nullptr || oh == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": ow or oh == NULL");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(width) + "x" + std::to_string(height));
+  }
+  if (orientation < 1 || orientation > 8) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": orientation " + std::to_string(orientation) + " is not one of 1..8 (EXIF tag 0x0112)");
+  }
+  uint32_t uw, uh;
+  sjpeg_internal::oriented_size(static_cast<uint32_t>(width), static_cast<uint32_t>(height), orientation, &uw, &uh);
+  *ow = static_cast<int>(uw);
+  *oh = static_cast<int>(uh);
+  return 0;
+}
+
+size_t sjpeg_hip_orient_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                                     const uint8_t* orientations) {
+  if (frames == nullptr) return 0;
+  try {
+    sjpeg_internal::ResizePlan plan;
+    if (sjpeg_internal::resize_plan("sjpeg_hip_orient_ragged_bytes", format, nframes, frames, sizes, orientations, &plan) != 0) return 0;
+    return plan.bytes;
+  } catch (...) {
+    return 0;
+  }
+}
+
+}  // extern "C"

@@ -3596,6 +3596,41 @@ int sjpeg_internal::engine_yuv_resize(sjpeg_hip_engine* e, const std::string& wh
   });
 }
 
+// ... and of the contact sheets (sheet_plan.cc): the background of every sheet, then the placed descriptors of either
+// plan, both on the call's stream -- stream order is the only ordering relied on
+int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, const SheetPlan& plan, uint8_t* d_out, uint8_t** base,
+                                 void* stream) {
+  uint8_t* sheets = nullptr;
+  auto fill = [&](hipStream_t st) {
+    if (sheet_fill_launch(plan.fill, sheets, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": sheet_fill_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  };
+  int rc;
+  if (plan.yuv) {
+    rc = engine_make_pictures(e, who, "sheet", plan.planes.planes, plan.bytes, d_out, &sheets, stream,
+                              [&](const YuvPlane* d_planes, int n, hipStream_t st) {
+      if (int rcf = fill(st)) return rcf;
+      if (yuv_resize_ragged_placed_launch(d_planes, n, plan.planes.tiles, st) != 0) {
+        return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+      }
+      return 0;
+    });
+  } else {
+    rc = engine_make_pictures(e, who, "sheet", plan.rgb.frames, plan.bytes, d_out, &sheets, stream,
+                              [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
+      if (int rcf = fill(st)) return rcf;
+      if (resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st) != 0) {
+        return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+      }
+      return 0;
+    });
+  }
+  if (base != nullptr) *base = sheets;
+  return rc;
+}
+
 extern "C" {
 
 // Pictures of a ragged batch reduced by their factors into the caller's buffer (sjpeg_hip.h): one launch of reduce.hip's
@@ -3715,6 +3750,38 @@ int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes
     if (int rc = sjpeg_internal::engine_yuv_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
     sjpeg_internal::yuv_resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
     *out_format = plan.resized_format;
+    return 0;
+  } catch (...) {
+    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ... and resized, turned and placed into contact sheets (sheet_plan.cc): one set of entries for both families of
+// formats; every check before `e` is touched
+int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                               const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                               size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (frames == nullptr || sheet == nullptr || d_out == nullptr || sheet_frames == nullptr || nsheets == nullptr || out_format == nullptr) {
+    return fail(SJPEG_HIP_EINVAL, who + ": frames, sheet, d_out, sheet_frames, nsheets or out_format == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
+  try {
+    sjpeg_internal::SheetPlan plan;
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
+    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan)) return rc;
+    if (out_bytes < plan.bytes) {
+      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
+                                        " bytes the sheets take (sjpeg_hip_sheet_ragged_bytes)");
+    }
+    if (int rc = sjpeg_internal::engine_sheet(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
+    sjpeg_internal::sheet_plan_frames(plan, static_cast<uint8_t*>(d_out), sheet_frames);
+    *nsheets = plan.nsheets;
+    *out_format = plan.out_format;
     return 0;
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
