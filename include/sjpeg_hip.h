@@ -1128,6 +1128,105 @@ int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* engine, int forma
                                              int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
                                              void* stream);
 
+/* ---- alpha flattened inside the ragged call: RGBA pictures over a background ----
+ * PNG and WebP uploads, logos, product cut-outs, a renderer's [H, W, 4] RGBA16F, a matting network's colour plus
+ * matte: pictures with an alpha channel, which JPEG has not.  The entries above drop the fourth sample and code
+ * whatever colour lies under transparent pixels.  The entries below lay every pixel over a background first -- in the
+ * resize kernel's loader, so no flattened copy of the source exists -- and then do what the oriented and sheet entries
+ * do.
+ *   Alpha formats: SJPEG_HIP_SRC_BGRA, _RGBA, _RGBA_F32, _RGBA_F16, _RGBA_BF16; the fourth byte or element of a pixel
+ *     is its alpha.
+ *   For a pixel of such a frame, s_c is the byte the encoder sees there today in channel c (the float formats: through
+ *     the engine's pixel transform of channel c) and a its alpha byte: the stored byte, or for the float formats
+ *     rint(clamp(fmaf(x, alpha_scale, alpha_bias), 0, 255)), NaN -> 0 -- the element rule of the float formats with
+ *     the flatten's own scale and bias (255, 0 for alpha in 0..1).  alpha_scale and alpha_bias are ignored for the
+ *     byte formats; for the float formats they must be finite.
+ *   Straight alpha (premultiplied = 0):  b_c = (a * s_c + (255 - a) * bg_c + 127) / 255, integer division: round to
+ *     nearest, and 255 is odd, so there are no ties; a = 255 gives s_c and a = 0 gives bg_c exactly.
+ *   Premultiplied alpha (premultiplied = 1):  b_c = min(255, s_c + ((255 - a) * bg_c + 127) / 255).
+ *   background is given in the bytes the encoder sees (R, G, B) and does not pass through the pixel transform.
+ * THE CONTRACT: the flattened picture F of a frame is the uint8 RGB picture of the b_c, W x H.  A flattened call makes,
+ * byte for byte, what the corresponding call above makes of F handed over as SJPEG_HIP_SRC_RGB: same sizes, same
+ * orientations, same sheet, same params.  Flatten comes first; the exact area average, the turn and the placement
+ * follow on bytes as they are defined above -- "composite the picture, then thumbnail it", two roundings on purpose.
+ * Elements read: under flatten the fourth element of every pixel IS read, so a row of the float RGBA formats must hold
+ * it: |row_stride| >= width * 4 * element size.  The x[..., 1:4]-of-ARGB view that the unflattened float RGBA formats
+ * allow (its last pixel's fourth element lies outside the tensor) is therefore not a legal flattened source.  Nothing
+ * else about strides and alignment changes: either sign, element-only alignment.
+ *
+ * sjpeg_hip_flatten_ragged_src: sjpeg_hip_orient_ragged_src plus `flatten` (not NULL): its arguments, ordering,
+ *   pipelined-mode behaviour, output layout and size (sjpeg_hip_orient_ragged_bytes), ONE launch.  sizes == NULL and
+ *   orientations == NULL is the flatten alone: F itself.  *out_format is always SJPEG_HIP_SRC_RGB.
+ * sjpeg_hip_encode_ragged_flattened_src / _flattened_packed_src: the _oriented_ / _oriented_packed_ entries plus
+ *   `flatten`.  flatten == NULL: exactly the oriented call on the same arguments, any format.  Otherwise EVERY frame
+ *   goes through the kernel, also at its own size with orientation 1 -- there is no pass-through: the inner call never
+ *   sees the alpha format -- into the engine memory of the reduced and resized pictures (counted by
+ *   sjpeg_hip_engine_scratch_bytes, released by sjpeg_hip_engine_trim, SJPEG_HIP_ENOMEM naming the bytes), then ONE
+ *   inner _full_meta_ call as SJPEG_HIP_SRC_RGB: SJPEG_YUV_AUTO, the search and the metadata act on the flattened,
+ *   resized, upright picture.
+ * sjpeg_hip_sheet_ragged_flat_src (flatten not NULL), sjpeg_hip_encode_ragged_sheet_flat_src / _sheet_flat_packed_src
+ *   (flatten == NULL: exactly the sheet call): the three sheet entries plus `flatten`.  The flatten's background and
+ *   the sheet's are independent fields.  sjpeg_hip_sheet_places and sjpeg_hip_sheet_ragged_bytes serve as they are: a
+ *   flattened sheet has the places and the bytes of the same call on SJPEG_HIP_SRC_RGB frames.
+ * SJPEG_HIP_EINVAL before any device work, the frame named as the ragged entries name it: a flatten with a format that
+ *   has no alpha (the message names the format: the YUV-plane, gray, RGB and planar formats all fall here);
+ *   premultiplied above 1; a float format's alpha_scale or alpha_bias that is not finite; a float row too short for its
+ *   alpha (the message says "alpha"); and every check the corresponding unflattened entry makes. */
+typedef struct sjpeg_hip_flatten {
+  uint8_t background[3];          /* R, G, B in the bytes the encoder sees; not passed through the pixel transform */
+  uint8_t premultiplied;          /* 0: straight alpha; 1: the colour samples are already multiplied by alpha; else EINVAL */
+  float alpha_scale, alpha_bias;  /* float formats: the alpha sample's transform; 255, 0 for alpha in 0..1 */
+} sjpeg_hip_flatten;
+int sjpeg_hip_flatten_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten,
+                                 const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                 const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                 sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_flattened_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                          const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                          const uint8_t* orientations /*host [nframes], or NULL*/,
+                                          const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                          void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                          int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_flattened_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                 const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                 const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                 const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                 void* d_packed, size_t packed_capacity,
+                                                 uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                 int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                 void* stream);
+int sjpeg_hip_sheet_ragged_flat_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                    const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_sheet* sheet,
+                                    const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                    const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                    sjpeg_hip_ragged_frame* sheet_frames /*host out [nsheets]*/, int* nsheets, int* out_format,
+                                    void* stream);
+int sjpeg_hip_encode_ragged_sheet_flat_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                           const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                           const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                           const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                           const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                           const uint8_t* orientations /*host [nframes], or NULL*/,
+                                           const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                           void* d_out, size_t out_stride, uint64_t* d_sizes /*[nsheets]*/,
+                                           int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                  const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                                  const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                  const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                  const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                  const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                  const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                                  void* d_packed, size_t packed_capacity,
+                                                  uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
+                                                  int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
+                                                  void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

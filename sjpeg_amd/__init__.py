@@ -217,6 +217,8 @@ class Reduced:
             raise SjpegError("Reduced: the pictures are Resized already: resize the pictures themselves, once")
         if type(images).__name__ == "Oriented":
             raise SjpegError("Reduced: the pictures are Oriented already: Oriented takes the sizes itself")
+        if type(images).__name__ == "Flattened":
+            raise SjpegError("Reduced: the pictures are Flattened already: Flattened takes the sizes itself")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -282,8 +284,8 @@ class Resized:
     def __init__(self, images, sizes):
         if isinstance(images, (Reduced, Resized)):
             raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
-        if type(images).__name__ == "Oriented":
-            raise SjpegError("Resized: the pictures are Oriented already: Oriented takes the sizes itself")
+        if type(images).__name__ in ("Oriented", "Flattened"):
+            raise SjpegError(f"Resized: the pictures are {type(images).__name__} already: {type(images).__name__} takes the sizes itself")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -307,8 +309,8 @@ class Resized:
         pictures' shapes are read ("hwc": [H, W, 3]; "chw": [3, H, W]; a FloatPixels is read as "chw")."""
         if isinstance(images, (Reduced, Resized)):
             raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
-        if type(images).__name__ == "Oriented":
-            raise SjpegError("Resized: the pictures are Oriented already: Oriented takes the sizes itself")
+        if type(images).__name__ in ("Oriented", "Flattened"):
+            raise SjpegError(f"Resized: the pictures are {type(images).__name__} already: {type(images).__name__} takes the sizes itself")
         chw = isinstance(images, FloatPixels) or _check_layout("Resized.fit", layout)
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         return cls(images, [fit_size(*_picture_size(im, chw), box) for im in inner])
@@ -380,6 +382,8 @@ class Oriented:
     def __init__(self, images, orientations, sizes=None):
         if isinstance(images, (Reduced, Resized, Oriented)):
             raise SjpegError("Oriented: the pictures are Reduced, Resized or Oriented already: Oriented takes the sizes itself, once")
+        if type(images).__name__ == "Flattened":
+            raise SjpegError("Oriented: the pictures are Flattened already: Flattened takes the orientations and the sizes itself")
         self.images = images
         inner = images.images if isinstance(images, FloatPixels) else list(images)
         if not isinstance(images, FloatPixels):
@@ -451,6 +455,120 @@ def _orientations_array(who, n, orientations):
     if len(vals) != n:
         raise SjpegError(f"{who}: one orientation per frame")
     return np.ascontiguousarray(np.clip(np.asarray(vals, dtype=np.int64), 0, 255).astype(np.uint8))
+
+
+class _FlattenStruct(C.Structure):
+    """struct sjpeg_hip_flatten (include/sjpeg_hip.h)"""
+    _fields_ = [("background", C.c_uint8 * 3), ("premultiplied", C.c_uint8), ("alpha_scale", C.c_float), ("alpha_bias", C.c_float)]
+
+
+class Flatten:
+    """How pictures with an alpha channel are laid over a background (struct sjpeg_hip_flatten): `background` three
+    bytes (R, G, B) as the encoder sees them; premultiplied False for straight alpha -- b = (a s + (255 - a) bg + 127)
+    // 255 --, True where the colour samples are multiplied by alpha already -- b = min(255, s + ((255 - a) bg + 127)
+    // 255); alpha_scale and alpha_bias turn a float picture's alpha sample into the byte a as FloatPixels turns a
+    colour sample into s (255 and 0 for alpha in 0..1; bytes ignore them)."""
+
+    def __init__(self, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0):
+        try:
+            bg = [int(b) for b in background]
+        except (TypeError, ValueError):
+            raise SjpegError(f"Flatten: background {background!r} is not three bytes 0..255")
+        if len(bg) != 3 or any(b < 0 or b > 255 for b in bg):
+            raise SjpegError(f"Flatten: background {background!r} is not three bytes 0..255")
+        if not isinstance(premultiplied, (bool, int, np.integer)) or int(premultiplied) not in (0, 1):
+            raise SjpegError(f"Flatten: premultiplied {premultiplied!r} is not False (straight alpha) or True")
+        try:
+            sc, bi = float(alpha_scale), float(alpha_bias)
+        except (TypeError, ValueError):
+            raise SjpegError("Flatten: alpha_scale and alpha_bias are floats")
+        if not (np.isfinite(sc) and np.isfinite(bi)):
+            raise SjpegError("Flatten: alpha_scale and alpha_bias must be finite")
+        self.background, self.premultiplied, self.alpha_scale, self.alpha_bias = tuple(bg), bool(premultiplied), sc, bi
+
+    def _struct(self):
+        return _FlattenStruct((C.c_uint8 * 3)(*self.background), int(self.premultiplied), self.alpha_scale, self.alpha_bias)
+
+
+def _flatten_struct(who, flatten):
+    if not isinstance(flatten, Flatten):
+        raise SjpegError(f"{who}: flatten is not a Flatten")
+    return flatten._struct()
+
+
+class Flattened:
+    """Pictures with an alpha channel to be coded over a background -- PNG and WebP uploads, logos, cut-outs, a
+    renderer's RGBA16F, a matting network's colour plus matte -- wherever Oriented is taken: Flattened(images,
+    background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0, orientations=None, sizes=None)
+    with `images` a sequence of CUDA uint8 tensors [H_k, W_k, 4] (R, G, B, alpha; stride 1 over the channels, 4 over x,
+    any row stride) or a FloatPixels of float tensors [H_k, W_k, 4] laid out the same way, and layout="hwc" (there is
+    no channel-first alpha format).  Every pixel is laid over `background` as Flatten defines it, inside the resize
+    kernel's loader; the picture is then resized to sizes[k] and turned upright by orientations[k] as Oriented defines
+    it, in the same ONE launch, and its JPEG is byte for byte that of the flattened, resized, upright uint8 picture
+    (flatten_images returns those).  Flatten comes first: "composite, then thumbnail"."""
+
+    def __init__(self, images, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0,
+                 orientations=None, sizes=None):
+        if isinstance(images, (Reduced, Resized, Oriented, Flattened)):
+            raise SjpegError("Flattened: the pictures are Reduced, Resized, Oriented or Flattened already: Flattened takes the "
+                             "orientations and the sizes itself, once")
+        self.flatten = Flatten(background, premultiplied, alpha_scale, alpha_bias)
+        self.fp = images if isinstance(images, FloatPixels) else None
+        self.images = list(images.images if self.fp is not None else images)
+        shaped = Oriented(self.images, 1 if orientations is None else orientations, sizes)
+        self.orientations = None if orientations is None else shaped.orientations
+        self.sizes = shaped.sizes
+
+    @classmethod
+    def fit(cls, images, box, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0,
+            orientations=None, layout="hwc"):
+        """Flattened(images, ..., sizes) with every UPRIGHT picture fitted into box = (bw, bh) by fit_size, as
+        Oriented.fit does."""
+        if _check_layout("Flattened.fit", layout):
+            raise SjpegError("Flattened.fit: layout='chw' has no alpha format: Flattened takes [H, W, 4] pictures, layout='hwc'")
+        plain = cls(images, background, premultiplied, alpha_scale, alpha_bias, orientations)
+        sizes = Oriented.fit(plain.images, 1 if orientations is None else plain.orientations, box).sizes
+        return cls(images, background, premultiplied, alpha_scale, alpha_bias, orientations, sizes)
+
+
+def _flattened(who, images, chw):
+    """(the pictures of a call without their Flattened wrapper, the Flattened or None)"""
+    if not isinstance(images, Flattened):
+        return images, None
+    if chw:
+        raise SjpegError(f"{who}: layout='chw' has no alpha format: Flattened takes [H, W, 4] pictures, layout='hwc'")
+    return images.images, images
+
+
+def _alpha_pictures(who, images, fp):
+    """(planes, dims, device, format) of pictures with an alpha channel: CUDA uint8 tensors [H, W, 4] -- SRC_RGBA -- or,
+    with fp (the call's FloatPixels), float tensors [H, W, 4] of one dtype -- SRC_RGBA_F32 / _F16 / _BF16; stride 1 over
+    the channels and 4 over x, any row stride (crops of a wider tensor, bottom-up views)"""
+    import torch
+    images = list(images)
+    if not images:
+        raise SjpegError(f"{who}: no images")
+    by_dtype = {getattr(torch, name): name for name in _DTYPE_BYTES}
+    planes, dims = [], []
+    for k, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or not im.is_cuda:
+            raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
+        if fp is None and im.dtype != torch.uint8:
+            raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8 (float pictures: a FloatPixels)")
+        if fp is not None and (im.dtype not in by_dtype or im.dtype != images[0].dtype):
+            raise SjpegError(f"{who}: image {k} is {im.dtype}: FloatPixels take torch.float32, torch.float16 or torch.bfloat16, "
+                             f"one dtype per call")
+        if im.dim() != 3 or im.shape[2] != 4 or im.shape[0] < 1 or im.shape[1] < 1 or im.stride(2) != 1 or \
+                (im.stride(1) != 4 and im.shape[1] > 1):
+            raise SjpegError(f"{who}: image {k} must be [H, W, 4] packed RGBA (stride 1 over the channels, 4 over x): a "
+                             f"flattened picture has an alpha channel")
+        if im.device != images[0].device:
+            raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {images[0].device}")
+        esz = im.element_size()
+        planes.append([(im.data_ptr(), (im.stride(0) if im.shape[0] > 1 else im.shape[1] * 4) * esz)])
+        dims.append((int(im.shape[1]), int(im.shape[0])))
+    fmt = SRC_RGBA if fp is None else _CHW_FORMAT[("rgba", by_dtype[images[0].dtype])]
+    return planes, dims, images[0].device, fmt
 
 
 class _SheetStruct(C.Structure):
@@ -801,6 +919,20 @@ def lib() -> C.CDLL:
     plain = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
     L.sjpeg_hip_encode_ragged_sheet_packed_src.restype = C.c_int
     L.sjpeg_hip_encode_ragged_sheet_packed_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
+    # (the flattened entries: the oriented and sheet ones plus `flatten`)
+    plain = list(L.sjpeg_hip_orient_ragged_src.argtypes)
+    L.sjpeg_hip_flatten_ragged_src.restype = C.c_int
+    L.sjpeg_hip_flatten_ragged_src.argtypes = plain[:4] + [C.c_void_p] + plain[4:]
+    for packed in ("", "_packed"):
+        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_oriented{packed}_src").argtypes)
+        fn = getattr(L, f"sjpeg_hip_encode_ragged_flattened{packed}_src")
+        fn.restype, fn.argtypes = C.c_int, plain[:5] + [C.c_void_p] + plain[5:]
+        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_sheet{packed}_src").argtypes)
+        fn = getattr(L, f"sjpeg_hip_encode_ragged_sheet_flat{packed}_src")
+        fn.restype, fn.argtypes = C.c_int, plain[:6] + [C.c_void_p] + plain[6:]
+    plain = list(L.sjpeg_hip_sheet_ragged_src.argtypes)
+    L.sjpeg_hip_sheet_ragged_flat_src.restype = C.c_int
+    L.sjpeg_hip_sheet_ragged_flat_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
     L.sjpeg_hip_exif_orientation.argtypes = [C.c_void_p, C.c_size_t]
     L.sjpeg_hip_exif_orientation.restype = C.c_int
     L.sjpeg_hip_exif_reset_orientation.argtypes = [C.c_void_p, C.c_size_t]
@@ -856,6 +988,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_yuv_resized_src", "sjpeg_hip_encode_ragged_yuv_resized_packed_src",
     "sjpeg_hip_sheet_size", "sjpeg_hip_sheet_places", "sjpeg_hip_sheet_ragged_bytes", "sjpeg_hip_sheet_ragged_src",
     "sjpeg_hip_encode_ragged_sheet_src", "sjpeg_hip_encode_ragged_sheet_packed_src",
+    "sjpeg_hip_flatten_ragged_src", "sjpeg_hip_encode_ragged_flattened_src", "sjpeg_hip_encode_ragged_flattened_packed_src",
+    "sjpeg_hip_sheet_ragged_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_packed_src",
 ]
 
 
@@ -2108,26 +2242,41 @@ class Engine:
         sizes; the STORED orientation) and turned upright by orientations[k] (EXIF 1..8; None: all 1) in one launch.
         Returns (fmt, pictures, buf) as resize_ragged does: picture k is [h, w, 3] or [h, w] for 1..4, [w, h, ...] for
         5..8.  Row and picture padding of buf may hold anything."""
+        return self._orient_ragged("orient_ragged", fmt, planes_per_frame, dims, None, sizes, orientations, out)
+
+    def flatten_ragged(self, fmt, planes_per_frame, dims, flatten, sizes=None, orientations=None, out=None):
+        """sjpeg_hip_flatten_ragged_src: orient_ragged of pictures with an alpha channel (fmt SRC_BGRA, SRC_RGBA or
+        SRC_RGBA_F32 / _F16 / _BF16), every pixel laid over the Flatten `flatten`'s background as its row is staged --
+        flatten, resize and turn in ONE launch; sizes None and orientations None: the flattened pictures themselves.
+        Returns (SRC_RGB, pictures, buf) as orient_ragged."""
+        return self._orient_ragged("flatten_ragged", fmt, planes_per_frame, dims, _flatten_struct("flatten_ragged", flatten), sizes,
+                                   orientations, out)
+
+    def _orient_ragged(self, who, fmt, planes_per_frame, dims, flat, sizes, orientations, out):
+        """orient_ragged and flatten_ragged (flat: its struct sjpeg_hip_flatten): one argument list, two entries"""
         import torch
         n = len(dims)
         if sizes is not None and len(sizes) != n:
-            raise SjpegError("orient_ragged: one size per frame")
+            raise SjpegError(f"{who}: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        arr = None if sizes is None else _sizes_array("orient_ragged", sizes)
-        oarr = None if orientations is None else _orientations_array("orient_ragged", n, orientations)
+        arr = None if sizes is None else _sizes_array(who, sizes)
+        oarr = None if orientations is None else _orientations_array(who, n, orientations)
         sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
         need = lib().sjpeg_hip_orient_ragged_bytes(fmt, n, frames, sp, op)
         dev = _ragged_device(planes_per_frame)
         if out is None:
             out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError("orient_ragged: out must be a contiguous uint8 CUDA tensor")
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor")
         made = (RaggedFrame * n)()
         rfmt = C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(lib().sjpeg_hip_orient_ragged_src(self._h, fmt, n, frames, sp, op, out.data_ptr(),
-                                                    int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()),
-                  "sjpeg_hip_orient_ragged_src")
+        tail = (sp, op, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream())
+        if flat is None:
+            self._chk(lib().sjpeg_hip_orient_ragged_src(self._h, fmt, n, frames, *tail), "sjpeg_hip_orient_ragged_src")
+        else:
+            self._chk(lib().sjpeg_hip_flatten_ragged_src(self._h, fmt, n, frames, C.addressof(flat), *tail),
+                      "sjpeg_hip_flatten_ragged_src")
         pics = []
         for r in made:
             at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
@@ -2169,8 +2318,29 @@ class Engine:
                                      method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
                                      sizes_out, metadata)
 
+    def encode_ragged_flattened(self, fmt, planes_per_frame, dims, flatten, sizes, orientations, yuv_mode, quant, method=4,
+                                min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
+                                out=None, offsets=None, sizes_out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_flattened_src: encode_ragged_oriented of pictures with an alpha channel laid over the
+        Flatten `flatten`'s background in the same launch (None: exactly encode_ragged_oriented).  Frame k's bytes are
+        those encode_ragged_full makes of the uint8 picture Engine.flatten_ragged returns; YUV_AUTO, a search and the
+        metadata act on that picture.  Returns (out, sizes, offsets, modes, q, value)."""
+        return self._encode_oriented("encode_ragged_flattened", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant,
+                                     method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
+                                     sizes_out, metadata, flatten=flatten, flattened=True)
+
+    def encode_ragged_flattened_packed(self, fmt, planes_per_frame, dims, flatten, sizes, orientations, yuv_mode, quant, method=4,
+                                       min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
+                                       capacities=None, packed_capacity=None, out=None, metadata=None):
+        """sjpeg_hip_encode_ragged_flattened_packed_src: encode_ragged_flattened into ONE packed buffer, with the
+        arguments and the returns of encode_ragged_oriented_packed."""
+        return self._encode_oriented_packed("encode_ragged_flattened_packed", fmt, planes_per_frame, dims, sizes, orientations,
+                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                                            capacities, packed_capacity, out, metadata, flatten=flatten, flattened=True)
+
     def _encode_oriented(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant,
-                         q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets, sizes_out, metadata):
+                         q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets, sizes_out, metadata, flatten=None,
+                         flattened=False):
         """the oriented encode and the one of the YUV-plane formats: one argument list, two entries (sjpeg_hip_<who>_src)"""
         n = len(dims)
         marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
@@ -2181,8 +2351,11 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        # (the flattened entries: `flatten`, or NULL, behind params)
+        flat = None if flatten is None else _flatten_struct(who, flatten)
+        extra = [None if flat is None else C.addressof(flat)] if flattened else []
         self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
-            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            self._h, fmt, n, frames, C.byref(params), *extra, None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
             out.data_ptr(), sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), f"sjpeg_hip_{who}_src")
         return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
@@ -2197,7 +2370,8 @@ class Engine:
                                             capacities, packed_capacity, out, metadata)
 
     def _encode_oriented_packed(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method,
-                                min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, packed_capacity, out, metadata):
+                                min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, packed_capacity, out, metadata,
+                                flatten=None, flattened=False):
         """... and their packed forms (sjpeg_hip_<who>_src)"""
         import torch
         n = len(dims)
@@ -2218,8 +2392,10 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        flat = None if flatten is None else _flatten_struct(who, flatten)
+        extra = [None if flat is None else C.addressof(flat)] if flattened else []
         self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
-            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
+            self._h, fmt, n, frames, C.byref(params), *extra, None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
             out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
             f"sjpeg_hip_{who}_src")
@@ -2284,13 +2460,15 @@ class Engine:
                                             yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
                                             capacities, packed_capacity, out, metadata)
 
-    def sheet_ragged(self, fmt, planes_per_frame, dims, sheet, sizes=None, orientations=None, out=None):
+    def sheet_ragged(self, fmt, planes_per_frame, dims, sheet, sizes=None, orientations=None, out=None, flatten=None):
         """sjpeg_hip_sheet_ragged_src: the pictures of a ragged batch (any format the resize entries take, the YUV-plane
         ones included) resized to sizes[k] (None: fitted into their cells), turned upright by orientations[k] and stored
         into their cells of contact sheets of the Sheet `sheet`: a background fill and one launch of the resize kernel.
         Returns (out_fmt, sheets, buf): sheet s a uint8 view into buf -- [SH, SW, 3] (SRC_RGB), [SH, SW] (SRC_GRAY) or a
         tuple (y, u, v) of planes (SRC_YUV420 / SRC_YUV444) --, rows padded to a multiple of 4 bytes.  out: a contiguous
-        uint8 CUDA tensor of at least sjpeg_hip_sheet_ragged_bytes bytes at a multiple of 16 (None: made here)."""
+        uint8 CUDA tensor of at least sjpeg_hip_sheet_ragged_bytes bytes at a multiple of 16 (None: made here).
+        flatten (a Flatten; None: today's call): sjpeg_hip_sheet_ragged_flat_src -- pictures of an alpha format laid over
+        the flatten's background, which is a field of its own beside the sheet's."""
         import torch
         who = "sheet_ragged"
         n = len(dims)
@@ -2311,9 +2489,13 @@ class Engine:
         made = (RaggedFrame * max((n + per - 1) // per, 1))()
         ns, rfmt = C.c_int(0), C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(lib().sjpeg_hip_sheet_ragged_src(self._h, fmt, n, frames, C.addressof(st), sp, op, out.data_ptr(),
-                                                   int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt),
-                                                   self._stream()), "sjpeg_hip_sheet_ragged_src")
+        tail = (sp, op, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt), self._stream())
+        if flatten is None:
+            self._chk(lib().sjpeg_hip_sheet_ragged_src(self._h, fmt, n, frames, C.addressof(st), *tail), "sjpeg_hip_sheet_ragged_src")
+        else:
+            flat = _flatten_struct(who, flatten)
+            self._chk(lib().sjpeg_hip_sheet_ragged_flat_src(self._h, fmt, n, frames, C.addressof(st), C.addressof(flat), *tail),
+                      "sjpeg_hip_sheet_ragged_flat_src")
         sheets = []
         for r in list(made)[:ns.value]:
             at = [out.storage_offset() + int(r.plane[c] or 0) - out.data_ptr() for c in range(3)]
@@ -2349,12 +2531,13 @@ class Engine:
 
     def encode_ragged_sheet(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                             min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, out_stride=None, out=None,
-                            metadata=None):
+                            metadata=None, flatten=None):
         """sjpeg_hip_encode_ragged_sheet_src: the JPEGs of the contact sheets Engine.sheet_ragged makes of the same
         arguments, each byte for byte what encode_ragged_full makes of that sheet.  quant, search and metadata are one
         for all or one per SHEET; yuv_mode any SjpegYUVMode for RGB-like pictures (YUV_AUTO decides on the sheet), YUV_400
         for gray ones, the format's own for YUV frames.  Sheet s is written at out[s * out_stride:] (default: the bound
-        of a sheet).  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full, one entry per sheet."""
+        of a sheet).  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full, one entry per sheet.
+        flatten (a Flatten; None: today's call): sjpeg_hip_encode_ragged_sheet_flat_src, as sheet_ragged."""
         import torch
         who = "encode_ragged_sheet"
         st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
@@ -2372,19 +2555,21 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
-        self._chk(lib().sjpeg_hip_encode_ragged_sheet_src(
-            self._h, fmt, n, frames, C.byref(params), C.addressof(st), None if arr is None else arr.ctypes.data,
+        flat = None if flatten is None else _flatten_struct(who, flatten)
+        symbol = "sjpeg_hip_encode_ragged_sheet_src" if flat is None else "sjpeg_hip_encode_ragged_sheet_flat_src"
+        self._chk(getattr(lib(), symbol)(
+            self._h, fmt, n, frames, C.byref(params), C.addressof(st), *([] if flat is None else [C.addressof(flat)]),
+            None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), out_stride, sizes_out.data_ptr(), modes, q_out, v_out, self._stream()),
-            "sjpeg_hip_encode_ragged_sheet_src")
+            out.data_ptr(), out_stride, sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), symbol)
         return out, sizes_out, [s * out_stride for s in range(ns)], [int(m) for m in modes], list(q_out), list(v_out)
 
     def encode_ragged_sheet_packed(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                                    min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
-                                   packed_capacity=None, out=None, metadata=None):
+                                   packed_capacity=None, out=None, metadata=None, flatten=None):
         """sjpeg_hip_encode_ragged_sheet_packed_src: encode_ragged_sheet into ONE packed buffer, the sheets back to back,
         with the layout of encode_ragged_full_packed over the sheets.  Returns (out, sizes, offsets, modes, q, value):
-        sizes [nsheets] and offsets [nsheets + 1] device tensors."""
+        sizes [nsheets] and offsets [nsheets + 1] device tensors.  flatten: as encode_ragged_sheet."""
         import torch
         who = "encode_ragged_sheet_packed"
         st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
@@ -2404,11 +2589,13 @@ class Engine:
                               mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
                               sarr, int(search_per_frame))
         modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
-        self._chk(lib().sjpeg_hip_encode_ragged_sheet_packed_src(
-            self._h, fmt, n, frames, C.byref(params), C.addressof(st), None if arr is None else arr.ctypes.data,
+        flat = None if flatten is None else _flatten_struct(who, flatten)
+        symbol = "sjpeg_hip_encode_ragged_sheet_packed_src" if flat is None else "sjpeg_hip_encode_ragged_sheet_flat_packed_src"
+        self._chk(getattr(lib(), symbol)(
+            self._h, fmt, n, frames, C.byref(params), C.addressof(st), *([] if flat is None else [C.addressof(flat)]),
+            None if arr is None else arr.ctypes.data,
             None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-            "sjpeg_hip_encode_ragged_sheet_packed_src")
+            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), modes, q_out, v_out, self._stream()), symbol)
         return out, meta[:ns], meta[ns:], list(modes), list(q_out), list(v_out)
 
     def search_stats(self):
@@ -2639,6 +2826,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     the last parameter: pass layout by keyword.)"""
     import torch
     chw = _check_layout("encode_images", layout)
+    images, flat = _flattened("encode_images", images, chw)
     images, orients = _oriented(images)
     images, factors = _reduced(images)
     images, new_sizes = _resized(images)
@@ -2669,7 +2857,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     images = list(images)
     if not images:
         raise SjpegError("encode_images: no images")
-    if yuv_mode in (YUV_AUTO, YUV_SHARP) and not chw:
+    if yuv_mode in (YUV_AUTO, YUV_SHARP) and not chw and flat is None:
         for k, im in enumerate(images):
             if len(getattr(im, "shape", ())) != 3 or im.shape[2] != 3:
                 raise SjpegError(f"encode_images: image {k}: YUV_AUTO and YUV_SHARP take RGB pictures [H, W, 3]")
@@ -2678,7 +2866,7 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     if len(qs) != n:
         raise SjpegError("encode_images: one quality per image")
     dev = None
-    for k, im in enumerate(() if chw else images):
+    for k, im in enumerate(() if chw or flat is not None else images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"encode_images: image {k} is not a CUDA tensor")
         if im.dtype != torch.uint8:
@@ -2691,7 +2879,10 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
         elif im.device != dev:
             raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
     fmt = SRC_RGB
-    if chw:
+    if flat is not None:
+        fp = flat.fp
+        planes, dims, dev, fmt = _alpha_pictures("encode_images", images, fp)
+    elif chw:
         planes, dims, dev, fmt = _chw_planes("encode_images", images, fp)
         _gray_mode("encode_images", fmt, yuv_mode)
     else:
@@ -2700,6 +2891,12 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
+    if flat is not None:
+        # (Flattened: laid over the background, resized and turned upright by the one launch)
+        with torch.cuda.device(dev):
+            fmt, flat_pictures, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
+        planes = [[p] for p in flat_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in flat_pictures]
     if factors is not None:
         # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
         with torch.cuda.device(dev):
@@ -2832,6 +3029,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
                         tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed, metadata=None):
     import torch
     chw = _check_layout("encode_images_full", layout)
+    images, flat = _flattened("encode_images_full", images, chw)
     images, orients = _oriented(images)
     images, factors = _reduced(images)
     images, new_sizes = _resized(images)
@@ -2855,7 +3053,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     if len(qs) != n:
         raise SjpegError("encode_images_full: one quality per image")
     dev = None
-    for k, im in enumerate(() if chw else images):
+    for k, im in enumerate(() if chw or flat is not None else images):
         if not isinstance(im, torch.Tensor) or not im.is_cuda:
             raise SjpegError(f"encode_images_full: image {k} is not a CUDA tensor")
         if im.dtype != torch.uint8:
@@ -2868,7 +3066,10 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
         elif im.device != dev:
             raise SjpegError(f"encode_images_full: image {k} is on {im.device}, image 0 on {dev}")
     fmt = SRC_RGB
-    if chw:
+    if flat is not None:
+        fp = flat.fp
+        planes, dims, dev, fmt = _alpha_pictures("encode_images_full", images, fp)
+    elif chw:
         planes, dims, dev, fmt = _chw_planes("encode_images_full", images, fp)
         _gray_mode("encode_images_full", fmt, yuv_mode)
     else:
@@ -2877,6 +3078,12 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
+    if flat is not None:
+        # (Flattened: laid over the background, resized and turned upright by the one launch)
+        with torch.cuda.device(dev):
+            fmt, flat_pictures, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
+        planes = [[p] for p in flat_pictures]
+        dims = [(int(p.shape[1]), int(p.shape[0])) for p in flat_pictures]
     if factors is not None:
         # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
         with torch.cuda.device(dev):
@@ -2950,6 +3157,9 @@ def riskiness_images(images, engine=None, layout="hwc"):
     if isinstance(images, Oriented):
         raise SjpegError("riskiness_images: Oriented pictures are not taken: turn them first -- "
                          "riskiness_images(orient_images(images, orientations)) -- the verdict is that of the upright picture")
+    if isinstance(images, Flattened):
+        raise SjpegError("riskiness_images: Flattened pictures are not taken: flatten first -- "
+                         "riskiness_images(flatten_images(images, ...)) -- the verdict is that of the flattened picture")
     images, fp = _float_pixels("riskiness_images", images, chw)
     images = list(images)
     if not images:
@@ -3082,12 +3292,61 @@ def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
     return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
 
 
-def _sheet_pictures(who, images, layout):
-    """(planes, dims, device, format, FloatPixels or None) of the pictures a sheet call takes: those of resize_images"""
+def flatten_images(images, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0,
+                   orientations=None, sizes=None, engine=None, layout="hwc"):
+    """The flattened uint8 pictures Flattened(images, background, ...) codes, as views of ONE device buffer, from one
+    launch of the resize kernel: images CUDA uint8 tensors [H_k, W_k, 4] or a FloatPixels of float tensors [H_k, W_k, 4]
+    (R, G, B, alpha), the other arguments as Flattened takes them.  Returns uint8 CUDA tensors [h_k, w_k, 3] (upright:
+    [w_k, h_k, 3] for the orientations 5..8), rows padded to a multiple of 4 bytes."""
+    import torch
+    chw = _check_layout("flatten_images", layout)
+    flat = images if isinstance(images, Flattened) else Flattened(images, background, premultiplied, alpha_scale, alpha_bias,
+                                                                   orientations, sizes)
+    pictures, flat = _flattened("flatten_images", flat, chw)
+    planes, dims, dev, fmt = _alpha_pictures("flatten_images", pictures, flat.fp)
+    eng = engine or Engine(dev.index or 0)
+    if flat.fp is not None:
+        eng.set_pixel_transform(flat.fp.scale, flat.fp.bias)
+    with torch.cuda.device(dev):
+        _, pics, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
+        if engine is None:
+            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
+    return pics
+
+
+def _sheet_flatten(who, flatten, sheet):
+    """the Flatten of a sheet call: None (today's call); True -- over the sheet's own background; three bytes -- over
+    that background; a Flatten or a Flattened -- its description (a Flattened's pictures are not looked at)"""
+    if flatten is None or flatten is False:
+        return None
+    if flatten is True:
+        if not isinstance(sheet, Sheet):
+            raise SjpegError(f"{who}: sheet is not a Sheet")
+        return Flatten(sheet.background)
+    if isinstance(flatten, Flattened):
+        return flatten.flatten
+    if isinstance(flatten, Flatten):
+        return flatten
+    if isinstance(flatten, (tuple, list, np.ndarray)):
+        return Flatten(*flatten) if len(flatten) != 3 or isinstance(flatten[0], (tuple, list, np.ndarray)) else Flatten(tuple(flatten))
+    raise SjpegError(f"{who}: flatten is None, True (over the sheet's background), a background (R, G, B), a tuple "
+                     f"(background, premultiplied, alpha_scale, alpha_bias) or a Flatten")
+
+
+def _sheet_pictures(who, images, layout, flatten=None):
+    """(planes, dims, device, format, FloatPixels or None) of the pictures a sheet call takes: those of resize_images;
+    with a flatten, those of flatten_images"""
     import torch
     chw = _check_layout(who, layout)
-    if isinstance(images, (Reduced, Resized, Oriented)):
-        raise SjpegError(f"{who}: Reduced, Resized and Oriented pictures are not taken: give sizes and orientations to the call")
+    if isinstance(images, (Reduced, Resized, Oriented, Flattened)):
+        raise SjpegError(f"{who}: Reduced, Resized, Oriented and Flattened pictures are not taken: give sizes, orientations and "
+                         f"flatten to the call")
+    if flatten is not None:
+        if chw:
+            raise SjpegError(f"{who}: layout='chw' has no alpha format: flatten takes [H, W, 4] pictures, layout='hwc'")
+        fp = images if isinstance(images, FloatPixels) else None
+        planes, dims, dev, fmt = _alpha_pictures(who, images.images if fp is not None else images, fp)
+        return planes, dims, dev, fmt, fp
     images, fp = _float_pixels(who, images, chw)
     images = list(images)
     if not images:
@@ -3112,21 +3371,25 @@ def _per_picture(who, n, orientations):
     return None if orientations is None else [int(o) for o in _orientations_array(who, n, orientations)]
 
 
-def make_sheets(images, sheet, sizes=None, orientations=None, engine=None, layout="hwc"):
+def make_sheets(images, sheet, sizes=None, orientations=None, engine=None, layout="hwc", flatten=None):
     """The uint8 contact sheets of a batch, as views of ONE device buffer: images as resize_images takes them
     (layout="hwc": CUDA uint8 tensors [H_k, W_k, 3]; "chw": channel-first uint8 tensors or a FloatPixels -- a network's
     [N, 3, H, W] float output), each resized to sizes[k] = (w, h) in the stored orientation (None: fitted into its cell,
     never enlarged), turned upright by orientations (one EXIF value 1..8 or one per picture) and stored centred into its
     cell of the Sheet -- a background fill and one launch, no thumbnail made a second time.  Returns uint8 CUDA tensors
-    [SH, SW, 3] (gray FloatPixels: [SH, SW]), rows padded to a multiple of 4 bytes; sheet_places gives the rectangles."""
+    [SH, SW, 3] (gray FloatPixels: [SH, SW]), rows padded to a multiple of 4 bytes; sheet_places gives the rectangles.
+    flatten (default None: today's call): the pictures are [H_k, W_k, 4] RGBA (uint8 tensors, or a FloatPixels of float
+    ones) and are laid over a background first, as Flattened defines it -- True: over the sheet's own background;
+    (R, G, B): over that one; a Flatten: with every field of it."""
     import torch
     who = "make_sheets"
-    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout)
+    flatten = _sheet_flatten(who, flatten, sheet)
+    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout, flatten)
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
     with torch.cuda.device(dev):
-        _, sheets, _ = eng.sheet_ragged(fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations))
+        _, sheets, _ = eng.sheet_ragged(fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations), flatten=flatten)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return sheets
@@ -3146,7 +3409,7 @@ def _sheet_search(who, ns, target_size, target_psnr):
 
 
 def _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, quality, method, use_trellis,
-                   target_size, target_psnr, packed, metadata):
+                   target_size, target_psnr, packed, metadata, flatten=None):
     """the rest of encode_sheets / encode_yuv_sheets: (list of JPEG bytes, places)"""
     import torch
     n = len(dims)
@@ -3162,7 +3425,8 @@ def _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, orientations,
     with torch.cuda.device(dev):
         if packed:
             out, sz, offs, _, _, _ = eng.encode_ragged_sheet_packed(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
-                                                                    _quality_quant(qs), method, search=search, metadata=metadata)
+                                                                    _quality_quant(qs), method, search=search, metadata=metadata,
+                                                                    flatten=flatten)
             eng.wait()
             meta = torch.cat([sz, offs]).cpu().numpy()
             sz, offs = meta[:ns], meta[ns:2 * ns]
@@ -3172,26 +3436,29 @@ def _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, orientations,
             host = out[:top].cpu().numpy()                    # the ONE copy of the sheets
             return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(ns)], places
         out, sz, offs, _, _, _ = eng.encode_ragged_sheet(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
-                                                         _quality_quant(qs), method, search=search, metadata=metadata)
+                                                         _quality_quant(qs), method, search=search, metadata=metadata,
+                                                         flatten=flatten)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return _fetch_ragged(out, sz, offs), places
 
 
 def encode_sheets(images, sheet, sizes=None, orientations=None, quality=75.0, yuv_mode=YUV_AUTO, method=4, use_trellis=False,
-                  target_size=None, target_psnr=None, packed=False, metadata=None, layout="hwc", engine=None):
+                  target_size=None, target_psnr=None, packed=False, metadata=None, layout="hwc", engine=None, flatten=None):
     """The contact-sheet call: (JPEGs, places) -- the JPEGs (list of bytes, one per sheet) of the sheets make_sheets makes
     of the same pictures, each byte for byte what encode_images_full makes of that sheet, and places[k] = (sheet, x, y, w,
     h), the rectangle of picture k (a storyboard's #xywh=).  quality, target_size / target_psnr and metadata: one for all
     sheets or one per SHEET; yuv_mode as encode_images_full (YUV_AUTO decides on the sheet; gray FloatPixels: YUV_400);
-    use_trellis maps method 4 to 7 and 6 to 8; packed=True: through the packed entry and one device-to-host copy."""
+    use_trellis maps method 4 to 7 and 6 to 8; packed=True: through the packed entry and one device-to-host copy.
+    flatten: as make_sheets takes it -- RGBA pictures laid over a background first."""
     who = "encode_sheets"
-    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout)
+    flatten = _sheet_flatten(who, flatten, sheet)
+    planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout, flatten)
     _gray_mode(who, fmt, int(yuv_mode))
     eng = engine or Engine(dev.index or 0)
     if fp is not None:
         eng.set_pixel_transform(fp.scale, fp.bias)
     return _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations), int(yuv_mode),
-                          quality, method, use_trellis, target_size, target_psnr, packed, metadata)
+                          quality, method, use_trellis, target_size, target_psnr, packed, metadata, flatten)
 
 
 def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations=None, quality=75.0, method=4,

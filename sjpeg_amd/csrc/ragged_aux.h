@@ -157,19 +157,30 @@ struct ResizePlan {
   std::vector<ResizeFrame> frames;
   size_t bytes = 0;
   unsigned tiles = 0;
+  bool flat = false;                     // the frames are flattened as they are staged (the kernel's flat instantiations)
+  sjpeg_hip_flatten flatten = {};        // ... by this
 };
 // Checks the sizes (sizes[f] = (w', h'), 1..the source's each; NULL: every frame at its own size) and the format (an
 // RGB-like or gray one), then plans; the message names the frame.  The frames' planes and strides are the caller's to
 // check (ragged_check).  orientations (NULL: all 1): each 1..8, checked with the sizes; the picture in the buffer is
 // then the upright one of orient_math.h -- h' x w' for 5..8 --, and resize_plan_frames reports that size.  An
 // orientation other than 1 takes a format the kernel reads, as a size other than the source's does.
+// flatten (NULL: none): checked by flatten_check in front of the frames; every frame's row must then hold its last
+// alpha element (the message names the frame and "alpha"); the plan is marked flat -- an alpha format under flatten
+// goes through the kernel at any size and orientation, its resized format is SJPEG_HIP_SRC_RGB.
 int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                const uint8_t* orientations, ResizePlan* plan);
+                const uint8_t* orientations, ResizePlan* plan, const sjpeg_hip_flatten* flatten = nullptr);
+// 0 for a flatten the format takes, else SJPEG_HIP_EINVAL: a format without alpha (named), premultiplied above 1, a
+// float format's alpha transform that is not finite
+int flatten_check(const std::string& who, int format, const sjpeg_hip_flatten& flatten);
 void resize_plan_frames(const ResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
 int resize_ragged_launch(int format, const float* pscale, const float* pbias, const ResizeFrame* d_frames, int nframes, unsigned tiles,
                          hipStream_t st);
+// ... of a flat plan (placed: a sheet's descriptors)
+int resize_ragged_flat_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten& flatten,
+                              const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
 // The engine's half (scan_engine.hip), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
-// pictures (the two kinds of call share it and its descriptors' buffer).
+// pictures (the two kinds of call share it and its descriptors' buffer).  A flat plan runs the flat launch.
 int engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base, void* stream);
 
 // ---- ragged resize of the YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src; yuv_resize_plan.cc, resize.hip): one
@@ -243,9 +254,10 @@ struct SheetPlan {
 int sheet_check(const std::string& who, const sjpeg_hip_sheet* sheet, int format, int* width, int* height);
 // The sheet checked, the thumbnails planned by resize_plan / yuv_resize_plan (sizes == NULL: each fitted into its
 // cell) -- their checks, their tile rule, their descriptors --, every thumbnail held to its cell, then each descriptor
-// rewritten to its place.
+// rewritten to its place.  flatten (NULL: none): handed to resize_plan; a YUV-plane format has no alpha and is
+// refused by name.
 int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_sheet* sheet,
-               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan);
+               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten = nullptr);
 // the sheets as frames of plan.out_format at `base` (out_offset, out_capacity: 0)
 void sheet_plan_frames(const SheetPlan& plan, uint8_t* base, sjpeg_hip_ragged_frame* out /*[nsheets]*/);
 int sheet_fill_launch(const SheetFill& fill, uint8_t* base, hipStream_t st);

@@ -994,12 +994,12 @@ static int resized_flow(const std::string& who, sjpeg_hip_engine* e, int format,
                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
                         const sjpeg_hip_metadata* meta, int meta_per_frame,
                         void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
-                        const sjpeg_internal::PackedSink* sink) {
+                        const sjpeg_internal::PackedSink* sink, const sjpeg_hip_flatten* flatten = nullptr) {
   try {
     const SourceLayout* const L = source_layout(format);
     if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
     sjpeg_internal::ResizePlan plan;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan, flatten)) return rc;
     return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
                         stream, sink);
   } catch (...) {
@@ -1064,11 +1064,12 @@ static int orientation_error(const std::string& who, const uint8_t* orientations
                                          " is not one of 1..8 (EXIF tag 0x0112)");
 }
 
-int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
-                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                                         int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_oriented_src";
+// One body for the oriented entry and the flattened one (flatten != NULL: every frame goes through the kernel -- no
+// pass-through, the inner call never sees the alpha format).
+static int oriented_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                          const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                          int* modes, float* q_out, float* value_out, void* stream) {
   if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
   if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
@@ -1076,20 +1077,43 @@ int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nf
   if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (all_ones(orientations, nframes)) {
+  if (flatten == nullptr && all_ones(orientations, nframes)) {
     return sjpeg_hip_encode_ragged_resized_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
                                                value_out, stream);
   }
   return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                      value_out, stream, nullptr);
+                      value_out, stream, nullptr, flatten);
 }
 
-int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
-                                                const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                                                void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
-                                                int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_oriented_packed_src";
+int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                         int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_oriented_src";
+  return oriented_entry(who, e, format, nframes, frames, params, nullptr, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes,
+                        q_out, value_out, stream);
+}
+
+// ---- ... and flattened over a background in the same launch (flatten_math.h): RGBA pictures ----
+int sjpeg_hip_encode_ragged_flattened_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                          const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                          int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                          void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_flattened_src";
+  if (flatten == nullptr) {
+    return sjpeg_hip_encode_ragged_oriented_src(e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes,
+                                                modes, q_out, value_out, stream);
+  }
+  return oriented_entry(who, e, format, nframes, frames, params, flatten, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes,
+                        q_out, value_out, stream);
+}
+
+static int oriented_packed_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                 const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                 size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out,
+                                 float* value_out, void* stream) {
   if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
   if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
@@ -1100,13 +1124,37 @@ int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format,
   if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (all_ones(orientations, nframes)) {
+  if (flatten == nullptr && all_ones(orientations, nframes)) {
     return sjpeg_hip_encode_ragged_resized_packed_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_packed,
                                                       packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
   }
   const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
   return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
-                      value_out, stream, &sink);
+                      value_out, stream, &sink, flatten);
+}
+
+int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_oriented_packed_src";
+  return oriented_packed_entry(who, e, format, nframes, frames, params, nullptr, sizes, orientations, meta, meta_per_frame, d_packed,
+                               packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
+}
+
+int sjpeg_hip_encode_ragged_flattened_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                 const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_flattened_packed_src";
+  if (flatten == nullptr) {
+    return sjpeg_hip_encode_ragged_oriented_packed_src(e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed,
+                                                       packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
+  }
+  return oriented_packed_entry(who, e, format, nframes, frames, params, flatten, sizes, orientations, meta, meta_per_frame, d_packed,
+                               packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
 }
 
 // ---- ... and on decoded video: NV12, NV21 and planar YUV resized and turned plane by plane (yuv_resize_plan.cc) ----
@@ -1182,10 +1230,11 @@ int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* e, int form
 static int sheet_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
                       const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
                       const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
-                      uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream, sjpeg_internal::PackedSink* sink) {
+                      uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream, sjpeg_internal::PackedSink* sink,
+                      const sjpeg_hip_flatten* flatten) {
   try {
     sjpeg_internal::SheetPlan plan;
-    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan)) return rc;
+    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan, flatten)) return rc;
     const SourceLayout* const L = source_layout(format);
     if (L->implied != 0 && params->yuv_mode != L->implied) {
       return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + (plan.yuv ? "" : " (gray pictures are coded 4:0:0 only)"));
@@ -1226,11 +1275,11 @@ static int sheet_flow(const std::string& who, sjpeg_hip_engine* e, int format, i
   }
 }
 
-int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
-                                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
-                                      size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_src";
+// (one body for the sheet entries and the flattened ones, as for the oriented entries)
+static int sheet_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                       const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten,
+                       const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                       void* d_out, size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
   if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
   if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
@@ -1240,15 +1289,33 @@ int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nfram
   if (out_stride < 1) return set_error(SJPEG_HIP_EINVAL, who + ": out_stride must be at least 1");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_out, out_stride, d_sizes,
-                    modes, q_out, value_out, stream, nullptr);
+                    modes, q_out, value_out, stream, nullptr, flatten);
 }
 
-int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
-                                             const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
-                                             int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
-                                             uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_packed_src";
+int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                      size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_src";
+  return sheet_entry(who, e, format, nframes, frames, params, sheet, nullptr, sizes, orientations, meta, meta_per_frame, d_out, out_stride,
+                     d_sizes, modes, q_out, value_out, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                           const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                           const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                           const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
+                                           uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_flat_src";
+  return sheet_entry(flatten != nullptr ? who : "sjpeg_hip_encode_ragged_sheet_src", e, format, nframes, frames, params, sheet, flatten, sizes,
+                     orientations, meta, meta_per_frame, d_out, out_stride, d_sizes, modes, q_out, value_out, stream);
+}
+
+static int sheet_packed_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten,
+                              const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                              void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out,
+                              float* value_out, void* stream) {
   if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
   if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
@@ -1261,7 +1328,29 @@ int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, in
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};   // (nframes: the sheets', set by the flow)
   return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_packed, 0, d_sizes, modes,
-                    q_out, value_out, stream, &sink);
+                    q_out, value_out, stream, &sink, flatten);
+}
+
+int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                             int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                             uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_packed_src";
+  return sheet_packed_entry(who, e, format, nframes, frames, params, sheet, nullptr, sizes, orientations, meta, meta_per_frame, d_packed,
+                            packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                  const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                  const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                                  const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                  void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                  int* modes, float* q_out, float* value_out, void* stream) {
+  static const std::string who = "sjpeg_hip_encode_ragged_sheet_flat_packed_src";
+  return sheet_packed_entry(flatten != nullptr ? who : "sjpeg_hip_encode_ragged_sheet_packed_src", e, format, nframes, frames, params, sheet,
+                            flatten, sizes, orientations, meta, meta_per_frame, d_packed, packed_capacity, d_offsets, d_sizes, modes, q_out,
+                            value_out, stream);
 }
 
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {

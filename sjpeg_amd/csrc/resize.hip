@@ -30,6 +30,12 @@
 //
 // Contact sheets (sjpeg_hip_sheet_ragged_src; sheet_plan.cc): sheet_fill_kernel writes the sheets' background, then the
 // kernel's PLACED instantiations store every thumbnail's tiles into its rectangle of a sheet plane.
+//
+// Alpha flattening (sjpeg_hip_flatten_ragged_src; flatten_math.h): the FLAT instantiations lay every pixel of a BGRA /
+// RGBA / float RGBA frame over a background where the segment is staged -- a packed pixel in registers between the
+// global load and the LDS store, a float pixel as its four elements become bytes --, so the staged bytes are those of
+// the flattened picture and everything behind the stage is as it is for SJPEG_HIP_SRC_RGB.  The sums are over bytes
+// b <= 255 as before: the 32-bit and 64-bit bounds above hold unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -37,6 +43,7 @@
 #include <string>
 #include <vector>
 
+#include "flatten_math.h"
 #include "orient_math.h"
 #include "pixel_elem.h"
 #include "ragged_aux.h"
@@ -90,6 +97,30 @@ __device__ __forceinline__ void stage_bytes(const uint8_t* g, uint8_t* l, unsign
   if (i < nb) l[i] = ((GlobalBytes)(g))[i];
 }
 
+// The flat instantiations' arguments: the launch's flatten, wave-uniform like the rest
+struct FlatResizeArgs : ResizeArgs {
+  uint32_t bg[3];                // the background, R, G, B
+  int premultiplied;
+  float ascale, abias;           // the alpha sample's transform (float formats)
+};
+
+// npix four-byte pixels of a source row at g into LDS at l (a multiple of 4), flattened on the way: g is a pixel
+// boundary, so every dword is one pixel -- alpha its last byte, R, G and B at the bytes sh[c] / 8 -- and there is no
+// tail of single bytes: the count is of pixels.  The colour bytes are replaced, the alpha byte stays (nothing reads it).
+__device__ __forceinline__ void stage_pixels_flat(const uint8_t* g, uint8_t* l, unsigned npix, unsigned lane, unsigned lanes,
+                                                  const unsigned (&sh)[3], const FlatResizeArgs& a) {
+  GlobalDwords const gd = (GlobalDwords)(g);
+  uint32_t* const ld = reinterpret_cast<uint32_t*>(l);
+  const bool pre = a.premultiplied != 0;
+  for (unsigned i = lane; i < npix; i += lanes) {
+    const uint32_t v = gd[i], al = v >> 24;
+    uint32_t o = v & 0xff000000u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o |= sjpeg_internal::flatten_byte(al, (v >> sh[c]) & 255u, a.bg[c], pre) << sh[c];
+    ld[i] = o;
+  }
+}
+
 // The YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src): the grid runs over the tiles of every PLANE of every frame,
 // and what is launch-wide above -- class, channels, pixel step -- is the plane's: Y, and U and V of the planar formats,
 // one-channel planes; the UV plane of NV12 / NV21 a packed picture of two-byte pixels.
@@ -97,8 +128,9 @@ struct YuvResizeArgs {
   const YuvPlane* planes;
   int nplanes;
 };
-template <bool kYuv> struct ResizeArgsOf { typedef ResizeArgs type; };
-template <> struct ResizeArgsOf<true> { typedef YuvResizeArgs type; };
+template <bool kYuv, bool kFlat = false> struct ResizeArgsOf { typedef ResizeArgs type; };
+template <> struct ResizeArgsOf<true, false> { typedef YuvResizeArgs type; };
+template <> struct ResizeArgsOf<false, true> { typedef FlatResizeArgs type; };
 __device__ __forceinline__ int desc_count(const ResizeArgs& a) { return a.nframes; }
 __device__ __forceinline__ int desc_count(const YuvResizeArgs& a) { return a.nplanes; }
 __device__ __forceinline__ const ResizeFrame& desc_at(const ResizeArgs& a, int i) { return a.frames[i]; }
@@ -112,8 +144,12 @@ __device__ __forceinline__ const ResizeFrame& desc_at(const YuvResizeArgs& a, in
 // a larger plane, so every tile, an unturned frame's too, leaves by the exact-span store: the whole-dword store
 // reaches into what is row padding in a picture of its own and is the next cell or the gutter in a sheet.  A
 // compile-time flag: the unplaced instantiations hold what they held before there were sheets.
-template <bool kYuv, bool kPlaced>
-__global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv>::type a) {
+// kFlat: the frames are of an alpha format (BGRA / RGBA bytes: the packed class; float RGBA: the element class) and
+// are flattened as they are staged.  A compile-time flag again, with arguments of its own: the four instantiations
+// without it hold what they held before; there is no flat YUV instantiation.
+template <bool kYuv, bool kPlaced, bool kFlat = false>
+__global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv, kFlat>::type a) {
+  static_assert(!(kYuv && kFlat), "the YUV-plane formats have no alpha");
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
   const unsigned wg = blockIdx.x, tid = threadIdx.x;
@@ -179,7 +215,27 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
       for (unsigned r = srow; r < nr; r += srows) {
         const uint8_t* const row = d.src + static_cast<long long>(yb + r) * d.row_stride;
         uint8_t* const l = stage + r * rpitch;
-        if (packed) {
+        if constexpr (kFlat) {
+          if (packed) {
+            // (four-byte pixels: row + xc * 4 is a pixel boundary and l a multiple of 4)
+            const unsigned sh[3] = {coff[0] * 8u, coff[1] * 8u, coff[2] * 8u};
+            stage_pixels_flat(row + static_cast<long long>(xc) * 4, l, clen, slane, slanes, sh, a);
+          } else {
+            // float RGBA, a pixel at a time: its four elements, the colours through the pixel transform as ever and the
+            // alpha through the flatten's own, flattened into the three runs of bytes
+            const long long esz = a.pix_step >> 2;
+            const bool pre = a.premultiplied != 0;
+            for (unsigned k = slane; k < clen; k += slanes) {
+              const uint8_t* const px = row + static_cast<long long>(xc + k) * a.pix_step;
+              const uint32_t al = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(px + 3 * esz, a.kind, a.ascale, a.abias));
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                const uint32_t sc = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(px + d.off[c], a.kind, a.pscale[c], a.pbias[c]));
+                l[c * cpitch + k] = static_cast<uint8_t>(sjpeg_internal::flatten_byte(al, sc, a.bg[c], pre));
+              }
+            }
+          }
+        } else if (packed) {
           stage_bytes(row + static_cast<long long>(xc) * lstep, l, clen * lstep, slane, slanes);
         } else {
 #pragma unroll
@@ -350,6 +406,29 @@ static int resize_launch(bool placed, int format, const float* pscale, const flo
     hipLaunchKernelGGL((resize_ragged_kernel<false, true>), dim3(tiles), dim3(256), 0, st, a);
   } else {
     hipLaunchKernelGGL((resize_ragged_kernel<false, false>), dim3(tiles), dim3(256), 0, st, a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int resize_ragged_flat_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten& flatten,
+                              const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st) {
+  const SourceLayout& L = *source_layout(format);
+  FlatResizeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frames = d_frames;
+  a.nframes = nframes;
+  a.kind = L.kind;
+  a.channels = 3;
+  a.pix_step = L.plane[0].step * L.esz;                            // (four bytes or four elements: resize_plan checked it)
+  a.cls = L.kind != kElemU8 ? kResizeElems : kResizePacked;
+  for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; a.bg[c] = flatten.background[c]; }
+  a.premultiplied = flatten.premultiplied;
+  a.ascale = flatten.alpha_scale;
+  a.abias = flatten.alpha_bias;
+  if (placed) {
+    hipLaunchKernelGGL((resize_ragged_kernel<false, true, true>), dim3(tiles), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((resize_ragged_kernel<false, false, true>), dim3(tiles), dim3(256), 0, st, a);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -35,11 +36,29 @@ bool resizable(const sjpeg_internal::SourceLayout& L) { return L.rgb_like || (L.
 
 namespace sjpeg_internal {
 
+int flatten_check(const std::string& who, int format, const sjpeg_hip_flatten& flatten) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  // an alpha format: one plane of pixels of four bytes or elements, R, G, B and the alpha behind them
+  if (!(L->rgb_like && !L->one_pitch && L->plane[0].step == 4)) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": flatten: " + source_format_name(format) + " has no alpha channel (a flattened source is "
+                                           "SJPEG_HIP_SRC_BGRA, _RGBA or _RGBA_F32 / _F16 / _BF16)");
+  }
+  if (flatten.premultiplied > 1) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": flatten: premultiplied " + std::to_string(flatten.premultiplied) + " is not 0 (straight alpha) or 1");
+  }
+  if (L->kind != kElemU8 && !(std::isfinite(flatten.alpha_scale) && std::isfinite(flatten.alpha_bias))) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": flatten: alpha_scale and alpha_bias must be finite");
+  }
+  return 0;
+}
+
 int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                const uint8_t* orientations, ResizePlan* plan) {
+                const uint8_t* orientations, ResizePlan* plan, const sjpeg_hip_flatten* flatten) {
   const SourceLayout* const L = source_layout(format);
   if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (flatten != nullptr) { if (int rc = flatten_check(who, format, *flatten)) return rc; }
   bool turned = false;
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
@@ -51,6 +70,15 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
       return set_error(SJPEG_HIP_EINVAL, frame + "orientation " + std::to_string(orientations[f]) + " is not one of 1..8 (EXIF tag 0x0112)");
     }
     turned = turned || (orientations != nullptr && orientations[f] != 1);
+    if (flatten != nullptr) {
+      // the fourth element of every pixel is read: a row holds its last one (the float formats' rows may else end
+      // behind the last colour sample)
+      const long long row = 4ll * fr.width * L->esz, have = fr.row_stride[0] < 0 ? -fr.row_stride[0] : fr.row_stride[0];
+      if (have < row) {
+        return set_error(SJPEG_HIP_EINVAL, frame + "|row_stride| " + std::to_string(have) + " is below the " + std::to_string(row) +
+                                               " bytes of a row with its alpha (width * 4 * element size): a flattened source's alpha is read");
+      }
+    }
     if (sizes == nullptr) continue;
     const std::string size = "size " + std::to_string(sizes[f][0]) + "x" + std::to_string(sizes[f][1]);
     if (sizes[f][0] < 1 || sizes[f][1] < 1) return set_error(SJPEG_HIP_EINVAL, frame + size + " is below 1x1");
@@ -68,6 +96,8 @@ int resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip
   const int channels = L->rgb_like ? 3 : 1;
   plan->format = format;
   plan->resized_format = channels == 3 ? SJPEG_HIP_SRC_RGB : SJPEG_HIP_SRC_GRAY;
+  plan->flat = flatten != nullptr;
+  if (flatten != nullptr) plan->flatten = *flatten;
   plan->frames.assign(static_cast<size_t>(nframes), ResizeFrame());
   size_t at = 0;
   unsigned long long tiles = 0;

@@ -3577,7 +3577,9 @@ int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, c
                                   void* stream) {
   return engine_make_pictures(e, who, "resized", plan.frames, plan.bytes, d_resized, base, stream,
                               [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
-    if (resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st) != 0) {
+    const int rc = plan.flat ? resize_ragged_flat_launch(false, plan.format, e->pscale, e->pbias, plan.flatten, d_frames, n, plan.tiles, st)
+                             : resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st);
+    if (rc != 0) {
       return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
     }
     return 0;
@@ -3621,7 +3623,9 @@ int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, co
     rc = engine_make_pictures(e, who, "sheet", plan.rgb.frames, plan.bytes, d_out, &sheets, stream,
                               [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
       if (int rcf = fill(st)) return rcf;
-      if (resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st) != 0) {
+      const int rcl = plan.rgb.flat ? resize_ragged_flat_launch(true, plan.format, e->pscale, e->pbias, plan.rgb.flatten, d_frames, n, plan.rgb.tiles, st)
+                                    : resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st);
+      if (rcl != 0) {
         return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
       }
       return 0;
@@ -3695,11 +3699,11 @@ int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
 }
 
 // ... and resized, then turned upright by their EXIF orientations, in the same ONE launch (orient_math.h): the checks
-// of the resize in its order, the orientations with the sizes
-int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
-                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_orient_ragged_src";
+// of the resize in its order, the orientations with the sizes.  One body for the oriented entry and the flattened one
+// (sjpeg_hip_flatten_ragged_src: `flatten` goes into the plan, whose checks of it come with its others).
+static int orient_ragged_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                               const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                               size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
     return fail(SJPEG_HIP_EINVAL, who + ": frames, d_out, out_frames or out_format == NULL");
@@ -3711,7 +3715,7 @@ int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
     if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
     if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
     if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
+    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan, flatten)) return rc;
     if (out_bytes < plan.bytes) {
       return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
                                         " bytes the oriented pictures take (sjpeg_hip_orient_ragged_bytes)");
@@ -3723,6 +3727,23 @@ int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, co
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
+}
+
+int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
+                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_orient_ragged_src";
+  return orient_ragged_entry(who, e, format, nframes, frames, nullptr, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
+}
+
+// ... and flattened over a background as they are staged (flatten_math.h), still ONE launch
+int sjpeg_hip_flatten_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                 const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                                 size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_flatten_ragged_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (flatten == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
+  return orient_ragged_entry(who, e, format, nframes, frames, flatten, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
 }
 
 // ... and the YUV-plane formats: every plane resized and turned as a picture of its own, still ONE launch; the checks
@@ -3757,11 +3778,11 @@ int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes
 }
 
 // ... and resized, turned and placed into contact sheets (sheet_plan.cc): one set of entries for both families of
-// formats; every check before `e` is touched
-int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                               const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
-                               size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_sheet_ragged_src";
+// formats; every check before `e` is touched.  One body again for the sheet entry and the flattened one.
+static int sheet_ragged_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                              const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                              const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
+                              int* nsheets, int* out_format, void* stream) {
   if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
   if (frames == nullptr || sheet == nullptr || d_out == nullptr || sheet_frames == nullptr || nsheets == nullptr || out_format == nullptr) {
     return fail(SJPEG_HIP_EINVAL, who + ": frames, sheet, d_out, sheet_frames, nsheets or out_format == NULL");
@@ -3773,7 +3794,7 @@ int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, con
     if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
     if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
     if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan)) return rc;
+    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan, flatten)) return rc;
     if (out_bytes < plan.bytes) {
       return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
                                         " bytes the sheets take (sjpeg_hip_sheet_ragged_bytes)");
@@ -3786,6 +3807,25 @@ int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, con
   } catch (...) {
     return fail(SJPEG_HIP_ENOMEM, "out of host memory");
   }
+}
+
+int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                               const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                               size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_src";
+  return sheet_ragged_entry(who, e, format, nframes, frames, sheet, nullptr, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets,
+                            out_format, stream);
+}
+
+int sjpeg_hip_sheet_ragged_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                    const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                    const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
+                                    int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_flat_src";
+  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (flatten == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
+  return sheet_ragged_entry(who, e, format, nframes, frames, sheet, flatten, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets,
+                            out_format, stream);
 }
 
 // ---- exchange step of the multi-device batch path: the coded frames of one call, back to back ----

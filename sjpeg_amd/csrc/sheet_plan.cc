@@ -51,12 +51,13 @@ int sheet_check(const std::string& who, const sjpeg_hip_sheet* sheet, int format
 }
 
 int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_sheet* sheet,
-               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan) {
+               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten) {
   int SW = 0, SH = 0;
   if (int rc = sheet_check(who, sheet, format, &SW, &SH)) return rc;
   const SourceLayout* const L = source_layout(format);
   if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  if (flatten != nullptr) { if (int rc = flatten_check(who, format, *flatten)) return rc; }   // (a YUV-plane format falls here)
   const sjpeg_hip_sheet& s = *sheet;
   const bool yuv = L->cls == kSrcPlanes && L->planes >= 2;         // luma and chroma planes of bytes: the per-plane plan
   const bool half = L->implied == SJPEG_HIP_YUV420;
@@ -77,7 +78,7 @@ int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_
   if (yuv) {
     if (int rc = yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan->planes)) return rc;
   } else {
-    if (int rc = resize_plan(who, format, nframes, frames, sizes, orientations, &plan->rgb)) return rc;
+    if (int rc = resize_plan(who, format, nframes, frames, sizes, orientations, &plan->rgb, flatten)) return rc;
   }
   const int channels = yuv ? 1 : plan->rgb.resized_format == SJPEG_HIP_SRC_RGB ? 3 : 1;
   const long long per_sheet = 1ll * s.cols * s.rows;
