@@ -200,6 +200,23 @@ def _float_pixels(who, images, chw):
 REDUCE_MAX = 8                   # SJPEG_HIP_REDUCE_MAX
 
 
+def _per_picture(value, n):
+    """one value for all n pictures, or one per picture: the list"""
+    return list(value) if isinstance(value, (list, tuple, np.ndarray)) else [value] * n
+
+
+def _wrapper_of(images):
+    """the name of the wrapper the images of a call are in already -- Reduced, Resized, Oriented, Flattened --, or None"""
+    return next((c.__name__ for c in (Reduced, Resized, Oriented, Flattened) if isinstance(images, c)), None)
+
+
+def _wrapped(images):
+    """The opening the wrapper classes share: (what a wrapper keeps as its images -- a FloatPixels as it is, anything
+    else as a list --, the inner list of pictures, their number)"""
+    inner = images.images if isinstance(images, FloatPixels) else list(images)
+    return (images if isinstance(images, FloatPixels) else inner), inner, len(inner)
+
+
 class Reduced:
     """Pictures to be coded at 1/factor of their size -- thumbnails, the levels of a srcset or DeepZoom pyramid, dataset
     previews -- as the `images` of encode_images, compress_images, encode_images_full, encode_images_full_chw and
@@ -213,18 +230,13 @@ class Reduced:
     change nothing.  A pyramid is the same picture listed several times: Reduced([im] * 4, [1, 2, 4, 8])."""
 
     def __init__(self, images, factor):
-        if type(images).__name__ == "Resized":
+        already = _wrapper_of(images)
+        if already == "Resized":
             raise SjpegError("Reduced: the pictures are Resized already: resize the pictures themselves, once")
-        if type(images).__name__ == "Oriented":
-            raise SjpegError("Reduced: the pictures are Oriented already: Oriented takes the sizes itself")
-        if type(images).__name__ == "Flattened":
-            raise SjpegError("Reduced: the pictures are Flattened already: Flattened takes the sizes itself")
-        self.images = images
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
-        if not isinstance(images, FloatPixels):
-            self.images = inner
-        n = len(inner)
-        fs = list(factor) if isinstance(factor, (list, tuple, np.ndarray)) else [factor] * n
+        if already in ("Oriented", "Flattened"):
+            raise SjpegError(f"Reduced: the pictures are {already} already: {already} takes the sizes itself")
+        self.images, _, n = _wrapped(images)
+        fs = _per_picture(factor, n)
         if len(fs) != n:
             raise SjpegError(f"Reduced: {len(fs)} factors for {n} pictures: one factor, or one per picture")
         for k, f in enumerate(fs):
@@ -282,15 +294,8 @@ class Resized:
     change nothing.  Resized.fit(images, box) fits every picture into one box."""
 
     def __init__(self, images, sizes):
-        if isinstance(images, (Reduced, Resized)):
-            raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
-        if type(images).__name__ in ("Oriented", "Flattened"):
-            raise SjpegError(f"Resized: the pictures are {type(images).__name__} already: {type(images).__name__} takes the sizes itself")
-        self.images = images
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
-        if not isinstance(images, FloatPixels):
-            self.images = inner
-        n = len(inner)
+        self._refuse_wrapped(images)
+        self.images, _, n = _wrapped(images)
         one = isinstance(sizes, (list, tuple, np.ndarray)) and len(sizes) == 2 and \
             all(isinstance(v, (int, np.integer)) for v in sizes)
         ss = [tuple(sizes)] * n if one else list(sizes) if isinstance(sizes, (list, tuple, np.ndarray)) else None
@@ -303,17 +308,21 @@ class Resized:
                 raise SjpegError(f"Resized: picture {k}: size {wh!r} is not a pair of ints (w, h) in 1..65535")
             self.sizes.append((int(wh[0]), int(wh[1])))
 
+    @staticmethod
+    def _refuse_wrapped(images):
+        already = _wrapper_of(images)
+        if already in ("Reduced", "Resized"):
+            raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
+        if already is not None:
+            raise SjpegError(f"Resized: the pictures are {already} already: {already} takes the sizes itself")
+
     @classmethod
     def fit(cls, images, box, layout="hwc"):
         """Resized(images, sizes) with every picture fitted into box = (bw, bh) by fit_size; layout says how the
         pictures' shapes are read ("hwc": [H, W, 3]; "chw": [3, H, W]; a FloatPixels is read as "chw")."""
-        if isinstance(images, (Reduced, Resized)):
-            raise SjpegError("Resized: the pictures are Reduced or Resized already: resize the pictures themselves, once")
-        if type(images).__name__ in ("Oriented", "Flattened"):
-            raise SjpegError(f"Resized: the pictures are {type(images).__name__} already: {type(images).__name__} takes the sizes itself")
+        cls._refuse_wrapped(images)
         chw = isinstance(images, FloatPixels) or _check_layout("Resized.fit", layout)
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
-        return cls(images, [fit_size(*_picture_size(im, chw), box) for im in inner])
+        return cls(images, [fit_size(*_picture_size(im, chw), box) for im in _wrapped(images)[1]])
 
 
 def _resized(images):
@@ -380,16 +389,13 @@ class Oriented:
     those).  Orientations that are all 1 are Resized(images, sizes)."""
 
     def __init__(self, images, orientations, sizes=None):
-        if isinstance(images, (Reduced, Resized, Oriented)):
-            raise SjpegError("Oriented: the pictures are Reduced, Resized or Oriented already: Oriented takes the sizes itself, once")
-        if type(images).__name__ == "Flattened":
+        already = _wrapper_of(images)
+        if already == "Flattened":
             raise SjpegError("Oriented: the pictures are Flattened already: Flattened takes the orientations and the sizes itself")
-        self.images = images
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
-        if not isinstance(images, FloatPixels):
-            self.images = inner
-        n = len(inner)
-        os_ = list(orientations) if isinstance(orientations, (list, tuple, np.ndarray)) else [orientations] * n
+        if already is not None:
+            raise SjpegError("Oriented: the pictures are Reduced, Resized or Oriented already: Oriented takes the sizes itself, once")
+        self.images, _, n = _wrapped(images)
+        os_ = _per_picture(orientations, n)
         if len(os_) != n:
             raise SjpegError(f"Oriented: {len(os_)} orientations for {n} pictures: one orientation, or one per picture")
         for k, o in enumerate(os_):
@@ -404,12 +410,12 @@ class Oriented:
         the orientations 5..8 the stored picture is fitted into (bh, bw).  layout as Resized.fit."""
         plain = cls(images, orientations)
         chw = isinstance(images, FloatPixels) or _check_layout("Oriented.fit", layout)
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
         try:
             bw, bh = box
         except (TypeError, ValueError):
             raise SjpegError(f"fit_size: box {box!r} is not a pair (width, height)")
-        sizes = [fit_size(*_picture_size(im, chw), (bh, bw) if o >= 5 else (bw, bh)) for im, o in zip(inner, plain.orientations)]
+        sizes = [fit_size(*_picture_size(im, chw), (bh, bw) if o >= 5 else (bw, bh))
+                 for im, o in zip(_wrapped(images)[1], plain.orientations)]
         return cls(images, plain.orientations, sizes)
 
     @classmethod
@@ -419,8 +425,7 @@ class Oriented:
         given; the metadata returned are copies whose Orientation is reset to 1, to be handed to the encode with the
         Oriented: a viewer must not turn the upright picture a second time.  metadata: one PictureMetadata for all
         pictures or one per picture (None entries: none)."""
-        inner = images.images if isinstance(images, FloatPixels) else list(images)
-        n = len(inner)
+        n = _wrapped(images)[2]
         items = [metadata] * n if isinstance(metadata, PictureMetadata) or metadata is None else list(metadata)
         if len(items) != n:
             raise SjpegError("Oriented.from_metadata: one metadata entry per image")
@@ -509,7 +514,7 @@ class Flattened:
 
     def __init__(self, images, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0,
                  orientations=None, sizes=None):
-        if isinstance(images, (Reduced, Resized, Oriented, Flattened)):
+        if _wrapper_of(images) is not None:
             raise SjpegError("Flattened: the pictures are Reduced, Resized, Oriented or Flattened already: Flattened takes the "
                              "orientations and the sizes itself, once")
         self.flatten = Flatten(background, premultiplied, alpha_scale, alpha_bias)
@@ -1942,48 +1947,76 @@ class Engine:
         res = (out, meta[:n], meta[n:], modes)
         return res if search is None else res + (q_out, v_out)
 
+    def _full_call(self, who, n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities,
+                   metadata, factors=None, sizes=None, orientations=None, resized=False):
+        """What every full-style entry hands to the library, built once: the metadata array, the arrays of the factors,
+        sizes and orientations an entry takes, the default capacities -- the bounds of the pictures as they are CODED
+        (reduced by factors[k]; sizes[k], for an entry that resizes clamped into 1..65535; swapped for the orientations
+        5..8), each with room for its metadata; or what the function `capacities` makes of the metadata sizes --, the
+        quant, min_quant and search arrays, sjpeg_hip_ragged_params and the three result arrays.  n and dims count what
+        is coded with params (the sheets of a sheet entry).  The result keeps alive what the structures point into."""
+        bound_mode = _bound_mode(yuv_mode)
+        marr, meta_per_frame, msizes, mkeep = _metadata_args(who, n, metadata)
+        fac = None if factors is None else (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
+        arr, oarr = _shape_arrays(who, n, sizes, orientations)
+        if callable(capacities):
+            capacities = capacities(msizes)
+        if capacities is None:
+            capacities = []
+            for k, (w, h) in enumerate(dims if arr is None else arr.tolist()):
+                if factors is not None:
+                    f = max(min(int(factors[k]), REDUCE_MAX), 1)
+                    w, h = -(-w // f), -(-h // f)
+                if resized:
+                    w, h = min(max(int(w), 1), 65535), min(max(int(h), 1), 65535)
+                if oarr is not None and oarr[k] >= 5:
+                    w, h = h, w
+                capacities.append(frame_bound(w, h, bound_mode, 2048 + msizes[k]))
+        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args(who, n, quant, min_quant, search, bound_mode,
+                                                                            capacities, dims)
+        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
+                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
+                              sarr, int(search_per_frame))
+        return _FullCall(C.byref(params), None if fac is None else C.cast(fac, C.c_void_p), _address(arr), _address(oarr),
+                         (None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame), capacities,
+                         ((C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()), (params, q, mq, sarr, marr, mkeep, fac, arr, oarr))
+
+    def _unpacked(self, symbol, fmt, frames, call, special, out, sizes, offsets):
+        """the C call of an unpacked full-style entry and its return tuple; special: what stands between params and the
+        metadata in its argument list"""
+        self._chk(getattr(lib(), symbol)(self._h, fmt, len(frames), frames, call.params, *special, *call.meta, out.data_ptr(),
+                                         sizes.data_ptr(), *call.results, self._stream()), symbol)
+        return (out, sizes, list(offsets)) + call.answers()
+
+    def _packed(self, symbol, fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta):
+        """... of a packed one, with out, packed_capacity and meta as _packed_out made them: (out, meta -- sizes and
+        offsets as ONE tensor --, modes, q, value)"""
+        n = len(dims)
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, call.capacities, out, [0] * n, meta)   # (out_offset ignored)
+        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, call.params, *special, *call.meta, out.data_ptr(),
+                                         packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), *call.results,
+                                         self._stream()), symbol)
+        return (out, meta) + call.answers()
+
     def _encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                               dmax_chroma, search, capacities, packed_capacity, out,
                               symbol="sjpeg_hip_encode_ragged_packed_src", metadata=None):
         """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home).
         symbol: that entry point, or its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments); with
         metadata (as encode_ragged_full takes it) the twin's sjpeg_hip_encode_ragged_full_meta_packed_src."""
-        import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_packed: one entry of planes_per_frame and dims per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_packed", n, metadata)
-        if marr is not None and capacities is None:
-            capacities = [frame_bound(w, h, bound_mode, 2048 + msizes[k]) for k, (w, h) in enumerate(dims)]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_packed", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        if len(capacities) != n:
+        call = self._full_call("encode_ragged_packed", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                               dmax_chroma, search, capacities, metadata)
+        if len(call.capacities) != n:
             raise SjpegError("encode_ragged_packed: one capacity per frame")
-        dev = _ragged_device(planes_per_frame)
-        if packed_capacity is None:
-            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
-        packed_capacity = int(packed_capacity)
-        if out is None:
-            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError("encode_ragged_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
-        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        if marr is not None:
-            symbol = "sjpeg_hip_encode_ragged_full_meta_packed_src"
-            rc = lib().sjpeg_hip_encode_ragged_full_meta_packed_src(
-                self._h, fmt, n, frames, C.byref(params), C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(),
-                packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream())
+        if call.meta[0] is None:
+            call.meta = ()                       # (these entries have a form without the metadata arguments)
         else:
-            rc = getattr(lib(), symbol)(self._h, fmt, n, frames, C.byref(params), out.data_ptr(), packed_capacity,
-                                        meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream())
-        self._chk(rc, symbol)
-        return out, meta, list(modes), list(q_out), list(v_out)
+            symbol = "sjpeg_hip_encode_ragged_full_meta_packed_src"
+        out, packed_capacity, meta = _packed_out("encode_ragged_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
+        return self._packed(symbol, fmt, planes_per_frame, dims, call, (), out, packed_capacity, meta)
 
     def encode_ragged_full(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
                            dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None, offsets=None, sizes=None,
@@ -1999,27 +2032,13 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
             raise SjpegError("encode_ragged_full: one entry of planes_per_frame and dims per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_full", n, metadata)
-        if marr is not None and capacities is None:
-            capacities = [frame_bound(w, h, bound_mode, 2048 + msizes[k]) for k, (w, h) in enumerate(dims)]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_full", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        if marr is not None:
-            self._chk(lib().sjpeg_hip_encode_ragged_full_meta_src(self._h, fmt, n, frames, C.byref(params),
-                                                                  C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(),
-                                                                  sizes.data_ptr(), modes, q_out, v_out, self._stream()),
-                      "sjpeg_hip_encode_ragged_full_meta_src")
-        else:
-            self._chk(lib().sjpeg_hip_encode_ragged_full_src(self._h, fmt, n, frames, C.byref(params), out.data_ptr(),
-                                                             sizes.data_ptr(), modes, q_out, v_out, self._stream()),
-                      "sjpeg_hip_encode_ragged_full_src")
-        return out, sizes, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+        call = self._full_call("encode_ragged_full", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                               dmax_chroma, search, capacities, metadata)
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes)
+        symbol = "sjpeg_hip_encode_ragged_full_meta_src"
+        if call.meta[0] is None:
+            symbol, call.meta = "sjpeg_hip_encode_ragged_full_src", ()       # (the form without the metadata arguments)
+        return self._unpacked(symbol, fmt, frames, call, (), out, sizes, offsets)
 
     def encode_ragged_full_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None,
                                   q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2040,33 +2059,25 @@ class Engine:
         padded to a multiple of 4 bytes, pictures at multiples of 16), which any ragged entry takes as its planes.  out:
         a uint8 CUDA tensor to reduce into (at a multiple of 16, at least the bytes needed).  Asynchronous on the current
         torch stream."""
-        import torch
         n = len(dims)
         if len(factors) != n:
             raise SjpegError("reduce_ragged: one factor per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         fac = (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
-        need = lib().sjpeg_hip_reduce_ragged_bytes(fmt, n, frames, C.cast(fac, C.c_void_p))
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError("reduce_ragged: out must be a contiguous uint8 CUDA tensor")
-        reduced = (RaggedFrame * n)()
-        rfmt = C.c_int(-1)
+        return self._make_pictures("reduce_ragged", "reduce_ragged", fmt, planes_per_frame, frames, (C.cast(fac, C.c_void_p),), out)
+
+    def _make_pictures(self, who, bytes_stem, fmt, planes_per_frame, frames, special, out, flat=None):
+        """the C calls of a picture-making entry -- sjpeg_hip_<bytes_stem>_bytes, then sjpeg_hip_<who>_src -- and its
+        return tuple; special: the entry's own arrays (flat: the struct sjpeg_hip_flatten in front of them)"""
+        n = len(frames)
+        need = getattr(lib(), f"sjpeg_hip_{bytes_stem}_bytes")(fmt, n, frames, *special)
+        out = _made_out(who, planes_per_frame, need, out)
+        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(lib().sjpeg_hip_reduce_ragged_src(self._h, fmt, n, frames, C.cast(fac, C.c_void_p), out.data_ptr(),
-                                                    int(out.numel()) if need else 0, reduced, C.byref(rfmt), self._stream()),
-                  "sjpeg_hip_reduce_ragged_src")
-        pics = []
-        for r in reduced:
-            # (as_strided counts from the start of the storage: `out` may be a slice of a larger tensor)
-            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
-            if rfmt.value == SRC_RGB:
-                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
-            else:
-                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
-        return int(rfmt.value), pics, out
+        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
+            self._h, fmt, n, frames, *(() if flat is None else (C.addressof(flat),)), *special, out.data_ptr(),
+            int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()), f"sjpeg_hip_{who}_src")
+        return int(rfmt.value), _frame_views(out, made, rfmt.value), out
 
     def encode_ragged_reduced(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
                               q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
@@ -2079,95 +2090,35 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
             raise SjpegError("encode_ragged_reduced: one entry of planes_per_frame, dims and factors per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_reduced", n, metadata)
-        fac = None if factors is None else (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
-        if capacities is None:
-            capacities = [frame_bound(-(-w // max(min(int(f), REDUCE_MAX), 1)), -(-h // max(min(int(f), REDUCE_MAX), 1)), bound_mode,
-                                      2048 + msizes[k])
-                          for k, ((w, h), f) in enumerate(zip(dims, factors if factors is not None else [1] * n))]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_reduced", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_reduced_src(
-            self._h, fmt, n, frames, C.byref(params), None if fac is None else C.cast(fac, C.c_void_p),
-            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), sizes.data_ptr(), modes,
-            q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_reduced_src")
-        return out, sizes, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+        call = self._full_call("encode_ragged_reduced", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               capacities, metadata, factors=factors)
+        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes)
+        return self._unpacked("sjpeg_hip_encode_ragged_reduced_src", fmt, frames, call, (call.factors,), out, sizes, offsets)
 
     def encode_ragged_reduced_packed(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
                                      q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
                                      packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_reduced_packed_src: encode_ragged_reduced into ONE packed buffer, with the arguments
         and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
-        import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
             raise SjpegError("encode_ragged_reduced_packed: one entry of planes_per_frame, dims and factors per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_reduced_packed", n, metadata)
-        fac = None if factors is None else (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
-        if capacities is None:
-            capacities = [frame_bound(-(-w // max(min(int(f), REDUCE_MAX), 1)), -(-h // max(min(int(f), REDUCE_MAX), 1)), bound_mode,
-                                      2048 + msizes[k])
-                          for k, ((w, h), f) in enumerate(zip(dims, factors if factors is not None else [1] * n))]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_reduced_packed", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        dev = _ragged_device(planes_per_frame)
-        if packed_capacity is None:
-            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
-        packed_capacity = int(packed_capacity)
-        if out is None:
-            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError("encode_ragged_reduced_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
-        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_reduced_packed_src(
-            self._h, fmt, n, frames, C.byref(params), None if fac is None else C.cast(fac, C.c_void_p),
-            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), packed_capacity,
-            meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-            "sjpeg_hip_encode_ragged_reduced_packed_src")
-        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+        call = self._full_call("encode_ragged_reduced_packed", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               capacities, metadata, factors=factors)
+        out, packed_capacity, meta = _packed_out("encode_ragged_reduced_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
+        return _split_meta(n, *self._packed("sjpeg_hip_encode_ragged_reduced_packed_src", fmt, planes_per_frame, dims, call, (call.factors,), out,
+                                            packed_capacity, meta))
 
     def resize_ragged(self, fmt, planes_per_frame, dims, sizes, out=None):
         """sjpeg_hip_resize_ragged_src: the pictures of a ragged batch (fmt, planes_per_frame, dims as encode_ragged; any
         RGB-like or gray format) resized to sizes[k] = (w, h), each side 1..the source's, in one launch.  Returns
         (resized_fmt, pictures, buf) as reduce_ragged does, with the same layout of buf; out as there."""
-        import torch
         n = len(dims)
         if len(sizes) != n:
             raise SjpegError("resize_ragged: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         arr = _sizes_array("resize_ragged", sizes)
-        need = lib().sjpeg_hip_resize_ragged_bytes(fmt, n, frames, arr.ctypes.data)
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError("resize_ragged: out must be a contiguous uint8 CUDA tensor")
-        resized = (RaggedFrame * n)()
-        rfmt = C.c_int(-1)
-        # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(lib().sjpeg_hip_resize_ragged_src(self._h, fmt, n, frames, arr.ctypes.data, out.data_ptr(),
-                                                    int(out.numel()) if need else 0, resized, C.byref(rfmt), self._stream()),
-                  "sjpeg_hip_resize_ragged_src")
-        pics = []
-        for r in resized:
-            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
-            if rfmt.value == SRC_RGB:
-                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
-            else:
-                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
-        return int(rfmt.value), pics, out
+        return self._make_pictures("resize_ragged", "resize_ragged", fmt, planes_per_frame, frames, (arr.ctypes.data,), out)
 
     def encode_ragged_resized(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
                               q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
@@ -2180,62 +2131,24 @@ class Engine:
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError("encode_ragged_resized: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_resized", n, metadata)
-        arr = None if sizes is None else _sizes_array("encode_ragged_resized", sizes)
-        if capacities is None:
-            capacities = [frame_bound(min(max(int(w), 1), 65535), min(max(int(h), 1), 65535), bound_mode, 2048 + msizes[k])
-                          for k, (w, h) in enumerate(dims if arr is None else arr.tolist())]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_resized", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes_out)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_resized_src(
-            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
-            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), sizes_out.data_ptr(), modes,
-            q_out, v_out, self._stream()), "sjpeg_hip_encode_ragged_resized_src")
-        return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+        call = self._full_call("encode_ragged_resized", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               capacities, metadata, sizes=sizes, resized=True)
+        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes_out)
+        return self._unpacked("sjpeg_hip_encode_ragged_resized_src", fmt, frames, call, (call.sizes,), out, sizes_out, offsets)
 
     def encode_ragged_resized_packed(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
                                      q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
                                      packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_resized_packed_src: encode_ragged_resized into ONE packed buffer, with the arguments
         and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
-        import torch
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError("encode_ragged_resized_packed: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args("encode_ragged_resized_packed", n, metadata)
-        arr = None if sizes is None else _sizes_array("encode_ragged_resized_packed", sizes)
-        if capacities is None:
-            capacities = [frame_bound(min(max(int(w), 1), 65535), min(max(int(h), 1), 65535), bound_mode, 2048 + msizes[k])
-                          for k, (w, h) in enumerate(dims if arr is None else arr.tolist())]
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args("encode_ragged_resized_packed", n, quant, min_quant,
-                                                                            search, bound_mode, capacities, dims)
-        dev = _ragged_device(planes_per_frame)
-        if packed_capacity is None:
-            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
-        packed_capacity = int(packed_capacity)
-        if out is None:
-            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError("encode_ragged_resized_packed: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
-        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
-        self._chk(lib().sjpeg_hip_encode_ragged_resized_packed_src(
-            self._h, fmt, n, frames, C.byref(params), None if arr is None else arr.ctypes.data,
-            None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame, out.data_ptr(), packed_capacity,
-            meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-            "sjpeg_hip_encode_ragged_resized_packed_src")
-        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+        call = self._full_call("encode_ragged_resized_packed", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               capacities, metadata, sizes=sizes, resized=True)
+        out, packed_capacity, meta = _packed_out("encode_ragged_resized_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
+        return _split_meta(n, *self._packed("sjpeg_hip_encode_ragged_resized_packed_src", fmt, planes_per_frame, dims, call, (call.sizes,), out,
+                                            packed_capacity, meta))
 
     def orient_ragged(self, fmt, planes_per_frame, dims, sizes, orientations, out=None):
         """sjpeg_hip_orient_ragged_src: the pictures of a ragged batch resized to sizes[k] = (w, h) (None: their own
@@ -2254,57 +2167,21 @@ class Engine:
 
     def _orient_ragged(self, who, fmt, planes_per_frame, dims, flat, sizes, orientations, out):
         """orient_ragged and flatten_ragged (flat: its struct sjpeg_hip_flatten): one argument list, two entries"""
-        import torch
         n = len(dims)
         if sizes is not None and len(sizes) != n:
             raise SjpegError(f"{who}: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        arr = None if sizes is None else _sizes_array(who, sizes)
-        oarr = None if orientations is None else _orientations_array(who, n, orientations)
-        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
-        need = lib().sjpeg_hip_orient_ragged_bytes(fmt, n, frames, sp, op)
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor")
-        made = (RaggedFrame * n)()
-        rfmt = C.c_int(-1)
-        # (a batch the library refuses has need == 0: the call below says why)
-        tail = (sp, op, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream())
-        if flat is None:
-            self._chk(lib().sjpeg_hip_orient_ragged_src(self._h, fmt, n, frames, *tail), "sjpeg_hip_orient_ragged_src")
-        else:
-            self._chk(lib().sjpeg_hip_flatten_ragged_src(self._h, fmt, n, frames, C.addressof(flat), *tail),
-                      "sjpeg_hip_flatten_ragged_src")
-        pics = []
-        for r in made:
-            at, rs = out.storage_offset() + int(r.plane[0]) - out.data_ptr(), int(r.row_stride[0])
-            if rfmt.value == SRC_RGB:
-                pics.append(out.as_strided((r.height, r.width, 3), (rs, 3, 1), at))
-            else:
-                pics.append(out.as_strided((r.height, r.width), (rs, 1), at))
-        return int(rfmt.value), pics, out
+        arr, oarr = _shape_arrays(who, n, sizes, orientations)
+        return self._make_pictures(who, "orient_ragged", fmt, planes_per_frame, frames, (_address(arr), _address(oarr)), out, flat)
 
-    def _oriented_args(self, who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
-                       capacities, metadata):
-        """what the two oriented encodes share: the arrays, and the default capacities -- the bounds of the UPRIGHT sizes"""
+    def _oriented_call(self, who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
+                       dmax_luma, dmax_chroma, search, capacities, metadata):
+        """what the two oriented encodes share: their check, and the call with the bounds of the UPRIGHT sizes"""
+        n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError(f"{who}: one entry of planes_per_frame, dims, sizes and orientations per frame, at least one frame")
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args(who, n, metadata)
-        arr = None if sizes is None else _sizes_array(who, sizes)
-        oarr = None if orientations is None else _orientations_array(who, n, orientations)
-        if capacities is None:
-            capacities = []
-            for k, (w, h) in enumerate(dims if arr is None else arr.tolist()):
-                w, h = min(max(int(w), 1), 65535), min(max(int(h), 1), 65535)
-                if oarr is not None and oarr[k] >= 5:
-                    w, h = h, w
-                capacities.append(frame_bound(w, h, bound_mode, 2048 + msizes[k]))
-        q, per_frame, mq, sarr, search_per_frame, capacities = _ragged_args(who, n, quant, min_quant, search, bound_mode,
-                                                                            capacities, dims)
-        return marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities
+        return self._full_call(who, n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               capacities, metadata, sizes=sizes, orientations=orientations, resized=True)
 
     def encode_ragged_oriented(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2342,23 +2219,13 @@ class Engine:
                          q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets, sizes_out, metadata, flatten=None,
                          flattened=False):
         """the oriented encode and the one of the YUV-plane formats: one argument list, two entries (sjpeg_hip_<who>_src)"""
-        n = len(dims)
-        marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
-            who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant, search,
-            capacities, metadata)
-        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, capacities, out, offsets, sizes_out)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        call = self._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
+                                   dmax_luma, dmax_chroma, search, capacities, metadata)
+        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes_out)
         # (the flattened entries: `flatten`, or NULL, behind params)
         flat = None if flatten is None else _flatten_struct(who, flatten)
-        extra = [None if flat is None else C.addressof(flat)] if flattened else []
-        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
-            self._h, fmt, n, frames, C.byref(params), *extra, None if arr is None else arr.ctypes.data,
-            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), f"sjpeg_hip_{who}_src")
-        return out, sizes_out, list(offsets), [int(m) for m in modes], list(q_out), list(v_out)
+        special = ((None if flat is None else C.addressof(flat),) if flattened else ()) + (call.sizes, call.orientations)
+        return self._unpacked(f"sjpeg_hip_{who}_src", fmt, frames, call, special, out, sizes_out, offsets)
 
     def encode_ragged_oriented_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                       min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
@@ -2373,33 +2240,14 @@ class Engine:
                                 min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, packed_capacity, out, metadata,
                                 flatten=None, flattened=False):
         """... and their packed forms (sjpeg_hip_<who>_src)"""
-        import torch
+        call = self._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
+                                   dmax_luma, dmax_chroma, search, capacities, metadata)
         n = len(dims)
-        marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame, capacities = self._oriented_args(
-            who, n, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, min_quant,
-            search, capacities, metadata)
-        dev = _ragged_device(planes_per_frame)
-        if packed_capacity is None:
-            packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
-        packed_capacity = int(packed_capacity)
-        if out is None:
-            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
-        meta = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, capacities, out, [0] * n, meta)   # (out_offset ignored)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()
+        out, packed_capacity, meta = _packed_out(who, n, planes_per_frame, call.capacities, packed_capacity, out)
         flat = None if flatten is None else _flatten_struct(who, flatten)
-        extra = [None if flat is None else C.addressof(flat)] if flattened else []
-        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
-            self._h, fmt, n, frames, C.byref(params), *extra, None if arr is None else arr.ctypes.data,
-            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), modes, q_out, v_out, self._stream()),
-            f"sjpeg_hip_{who}_src")
-        return out, meta[:n], meta[n:], list(modes), list(q_out), list(v_out)
+        special = ((None if flat is None else C.addressof(flat),) if flattened else ()) + (call.sizes, call.orientations)
+        return _split_meta(n, *self._packed(f"sjpeg_hip_{who}_src", fmt, planes_per_frame, dims, call, special, out,
+                                            packed_capacity, meta))
 
     def resize_ragged_yuv(self, fmt, planes_per_frame, dims, sizes, orientations=None, out=None):
         """sjpeg_hip_resize_ragged_yuv_src: decoded video frames (fmt SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444;
@@ -2408,35 +2256,13 @@ class Engine:
         as a picture of its own, in one launch.  Returns (out_fmt, pictures, buf): SRC_YUV420 or SRC_YUV444 -- always
         planar --, picture k a tuple (y, u, v) of uint8 views into buf ([h, w] each; rows padded to a multiple of 4
         bytes, planes at multiples of 16), which any ragged entry takes as its planes.  out as resize_ragged."""
-        import torch
         n = len(dims)
         if sizes is not None and len(sizes) != n:
             raise SjpegError("resize_ragged_yuv: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        arr = None if sizes is None else _sizes_array("resize_ragged_yuv", sizes)
-        oarr = None if orientations is None else _orientations_array("resize_ragged_yuv", n, orientations)
-        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
-        need = lib().sjpeg_hip_resize_ragged_yuv_bytes(fmt, n, frames, sp, op)
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError("resize_ragged_yuv: out must be a contiguous uint8 CUDA tensor")
-        made = (RaggedFrame * n)()
-        rfmt = C.c_int(-1)
-        # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(lib().sjpeg_hip_resize_ragged_yuv_src(self._h, fmt, n, frames, sp, op, out.data_ptr(),
-                                                        int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()),
-                  "sjpeg_hip_resize_ragged_yuv_src")
-        pics = []
-        for r in made:
-            planes = []
-            for c in range(3):
-                pw, ph = yuv_plane_size(rfmt.value, r.width, r.height, c)
-                at = out.storage_offset() + int(r.plane[c]) - out.data_ptr()
-                planes.append(out.as_strided((ph, pw), (int(r.row_stride[c]), 1), at))
-            pics.append(tuple(planes))
-        return int(rfmt.value), pics, out
+        arr, oarr = _shape_arrays("resize_ragged_yuv", n, sizes, orientations)
+        return self._make_pictures("resize_ragged_yuv", "resize_ragged_yuv", fmt, planes_per_frame, frames,
+                                   (_address(arr), _address(oarr)), out)
 
     def encode_ragged_yuv_resized(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                   min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2469,65 +2295,49 @@ class Engine:
         uint8 CUDA tensor of at least sjpeg_hip_sheet_ragged_bytes bytes at a multiple of 16 (None: made here).
         flatten (a Flatten; None: today's call): sjpeg_hip_sheet_ragged_flat_src -- pictures of an alpha format laid over
         the flatten's background, which is a field of its own beside the sheet's."""
-        import torch
         who = "sheet_ragged"
         n = len(dims)
         if sizes is not None and len(sizes) != n:
             raise SjpegError(f"{who}: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         st = _sheet_struct(who, sheet)
-        arr = None if sizes is None else _sizes_array(who, sizes)
-        oarr = None if orientations is None else _orientations_array(who, n, orientations)
-        sp, op = None if arr is None else arr.ctypes.data, None if oarr is None else oarr.ctypes.data
-        need = lib().sjpeg_hip_sheet_ragged_bytes(fmt, n, frames, C.addressof(st), sp, op)
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor")
+        arr, oarr = _shape_arrays(who, n, sizes, orientations)
+        need = lib().sjpeg_hip_sheet_ragged_bytes(fmt, n, frames, C.addressof(st), _address(arr), _address(oarr))
+        out = _made_out(who, planes_per_frame, need, out)
         per = max(int(sheet.cols) * int(sheet.rows), 1)
         made = (RaggedFrame * max((n + per - 1) // per, 1))()
         ns, rfmt = C.c_int(0), C.c_int(-1)
+        flat = None if flatten is None else _flatten_struct(who, flatten)
+        symbol = "sjpeg_hip_sheet_ragged_src" if flat is None else "sjpeg_hip_sheet_ragged_flat_src"
         # (a batch the library refuses has need == 0: the call below says why)
-        tail = (sp, op, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt), self._stream())
-        if flatten is None:
-            self._chk(lib().sjpeg_hip_sheet_ragged_src(self._h, fmt, n, frames, C.addressof(st), *tail), "sjpeg_hip_sheet_ragged_src")
-        else:
-            flat = _flatten_struct(who, flatten)
-            self._chk(lib().sjpeg_hip_sheet_ragged_flat_src(self._h, fmt, n, frames, C.addressof(st), C.addressof(flat), *tail),
-                      "sjpeg_hip_sheet_ragged_flat_src")
-        sheets = []
-        for r in list(made)[:ns.value]:
-            at = [out.storage_offset() + int(r.plane[c] or 0) - out.data_ptr() for c in range(3)]
-            if rfmt.value == SRC_RGB:
-                sheets.append(out.as_strided((r.height, r.width, 3), (int(r.row_stride[0]), 3, 1), at[0]))
-            elif rfmt.value == SRC_GRAY:
-                sheets.append(out.as_strided((r.height, r.width), (int(r.row_stride[0]), 1), at[0]))
-            else:
-                planes = []
-                for c in range(3):
-                    pw, ph = yuv_plane_size(rfmt.value, r.width, r.height, c)
-                    planes.append(out.as_strided((ph, pw), (int(r.row_stride[c]), 1), at[c]))
-                sheets.append(tuple(planes))
-        return int(rfmt.value), sheets, out
+        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, C.addressof(st), *(() if flat is None else (C.addressof(flat),)),
+                                         _address(arr), _address(oarr), out.data_ptr(), int(out.numel()) if need else 0, made,
+                                         C.byref(ns), C.byref(rfmt), self._stream()), symbol)
+        return int(rfmt.value), _frame_views(out, list(made)[:ns.value], rfmt.value), out
 
-    def _sheet_args(self, who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search,
-                    metadata):
-        """what the two sheet encodes share: the arrays (params and metadata count SHEETS), the sheets' number and bound"""
+    def _sheet_call(self, who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method, min_quant,
+                    q_bias, dmax_luma, dmax_chroma, search, metadata):
+        """what the two sheet encodes share: the sheets' number and bound, the call (params and metadata count SHEETS),
+        and what stands behind params: the struct sjpeg_hip_sheet, the sizes and the orientations"""
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError(f"{who}: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
         st = _sheet_struct(who, sheet)
         sw, sh = sheet_size(sheet, fmt)
         ns = (n + sheet.cols * sheet.rows - 1) // (sheet.cols * sheet.rows)
-        bound_mode = YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
-        marr, meta_per_frame, msizes, mkeep = _metadata_args(who, ns, metadata)
-        capacity = frame_bound(sw, sh, bound_mode, 2048 + max(msizes))
-        q, per_frame, mq, sarr, search_per_frame, _ = _ragged_args(who, ns, quant, min_quant, search, bound_mode, [capacity] * ns,
-                                                                   [(sw, sh)] * ns)
-        arr = None if sizes is None else _sizes_array(who, sizes)
-        oarr = None if orientations is None else _orientations_array(who, n, orientations)
-        return st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame
+        call = self._full_call(who, ns, [(sw, sh)] * ns, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+                               lambda msizes: [frame_bound(sw, sh, _bound_mode(yuv_mode), 2048 + max(msizes))] * ns, metadata)
+        arr, oarr = _shape_arrays(who, n, sizes, orientations)
+        call.keep += (st, arr, oarr)
+        return ns, call, [C.addressof(st), _address(arr), _address(oarr)]
+
+    def _sheet_symbol(self, who, flatten, special):
+        """the entry of a sheet encode: with a Flatten, sjpeg_hip_<who>_flat..._src and its struct behind the sheet's"""
+        if flatten is None:
+            return f"sjpeg_hip_{who}_src", None
+        flat = _flatten_struct(who, flatten)
+        special.insert(1, C.addressof(flat))
+        return f"sjpeg_hip_{who}_src".replace("_sheet", "_sheet_flat"), flat
 
     def encode_ragged_sheet(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                             min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, out_stride=None, out=None,
@@ -2540,10 +2350,9 @@ class Engine:
         flatten (a Flatten; None: today's call): sjpeg_hip_encode_ragged_sheet_flat_src, as sheet_ragged."""
         import torch
         who = "encode_ragged_sheet"
-        st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
-            who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search, metadata)
-        n = len(dims)
-        out_stride = (capacity + 15) & ~15 if out_stride is None else int(out_stride)
+        ns, call, special = self._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method,
+                                             min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
+        out_stride = (call.capacities[0] + 15) & ~15 if out_stride is None else int(out_stride)
         dev = _ragged_device(planes_per_frame)
         if out is None:
             out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
@@ -2551,18 +2360,10 @@ class Engine:
             raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of out_stride bytes a sheet")
         sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
-        flat = None if flatten is None else _flatten_struct(who, flatten)
-        symbol = "sjpeg_hip_encode_ragged_sheet_src" if flat is None else "sjpeg_hip_encode_ragged_sheet_flat_src"
-        self._chk(getattr(lib(), symbol)(
-            self._h, fmt, n, frames, C.byref(params), C.addressof(st), *([] if flat is None else [C.addressof(flat)]),
-            None if arr is None else arr.ctypes.data,
-            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), out_stride, sizes_out.data_ptr(), modes, q_out, v_out, self._stream()), symbol)
-        return out, sizes_out, [s * out_stride for s in range(ns)], [int(m) for m in modes], list(q_out), list(v_out)
+        symbol, flat = self._sheet_symbol(who, flatten, special)
+        self._chk(getattr(lib(), symbol)(self._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(),
+                                         out_stride, sizes_out.data_ptr(), *call.results, self._stream()), symbol)
+        return (out, sizes_out, [s * out_stride for s in range(ns)]) + call.answers()
 
     def encode_ragged_sheet_packed(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                                    min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
@@ -2570,33 +2371,16 @@ class Engine:
         """sjpeg_hip_encode_ragged_sheet_packed_src: encode_ragged_sheet into ONE packed buffer, the sheets back to back,
         with the layout of encode_ragged_full_packed over the sheets.  Returns (out, sizes, offsets, modes, q, value):
         sizes [nsheets] and offsets [nsheets + 1] device tensors.  flatten: as encode_ragged_sheet."""
-        import torch
         who = "encode_ragged_sheet_packed"
-        st, ns, capacity, marr, meta_per_frame, mkeep, arr, oarr, q, per_frame, mq, sarr, search_per_frame = self._sheet_args(
-            who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, min_quant, search, metadata)
-        n = len(dims)
-        dev = _ragged_device(planes_per_frame)
-        if packed_capacity is None:
-            packed_capacity = int(out.numel()) if out is not None else ns * ((capacity + 15) & ~15)
-        packed_capacity = int(packed_capacity)
-        if out is None:
-            out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
-            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
-        meta = torch.zeros(2 * ns + 1, dtype=torch.int64, device=dev)
+        ns, call, special = self._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method,
+                                             min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
+        out, packed_capacity, meta = _packed_out(who, ns, planes_per_frame, call.capacities, packed_capacity, out)
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        params = RaggedParams(int(yuv_mode), int(method), q.ctypes.data, int(per_frame),
-                              mq.ctypes.data if mq is not None else None, int(q_bias), int(dmax_luma), int(dmax_chroma),
-                              sarr, int(search_per_frame))
-        modes, q_out, v_out = (C.c_int * ns)(), (C.c_float * ns)(), (C.c_float * ns)()
-        flat = None if flatten is None else _flatten_struct(who, flatten)
-        symbol = "sjpeg_hip_encode_ragged_sheet_packed_src" if flat is None else "sjpeg_hip_encode_ragged_sheet_flat_packed_src"
-        self._chk(getattr(lib(), symbol)(
-            self._h, fmt, n, frames, C.byref(params), C.addressof(st), *([] if flat is None else [C.addressof(flat)]),
-            None if arr is None else arr.ctypes.data,
-            None if oarr is None else oarr.ctypes.data, None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame,
-            out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), modes, q_out, v_out, self._stream()), symbol)
-        return out, meta[:ns], meta[ns:], list(modes), list(q_out), list(v_out)
+        symbol, flat = self._sheet_symbol(who, flatten, special)
+        self._chk(getattr(lib(), symbol)(self._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(),
+                                         packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), *call.results,
+                                         self._stream()), symbol)
+        return (out, meta[:ns], meta[ns:]) + call.answers()
 
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
@@ -2609,6 +2393,78 @@ class Engine:
 
 
 TARGET_SIZE, TARGET_PSNR = 1, 2      # sjpeg_hip_search.target_mode (EncoderParam::TargetMode)
+
+
+class _FullCall:
+    """what Engine._full_call built: params (a reference to sjpeg_hip_ragged_params), the addresses of the factors, sizes
+    and orientations (None: not given), meta = (the metadata array or None, whether there is one per frame), the
+    capacities, results = (modes, q, value) for the library to fill, and keep: everything those point into"""
+
+    def __init__(self, params, factors, sizes, orientations, meta, capacities, results, keep):
+        self.params, self.factors, self.sizes, self.orientations = params, factors, sizes, orientations
+        self.meta, self.capacities, self.results, self.keep = meta, capacities, results, keep
+
+    def answers(self):
+        """(modes, q, value) as lists, once the library has filled them"""
+        return tuple(list(r) for r in self.results)
+
+
+def _bound_mode(yuv_mode):
+    """the sampling a frame's bound is taken at: the largest, YUV_444, where the encoder chooses (YUV_AUTO, YUV_SHARP)"""
+    return YUV_444 if int(yuv_mode) in (YUV_AUTO, YUV_SHARP) else int(yuv_mode)
+
+
+def _address(arr):
+    return None if arr is None else arr.ctypes.data
+
+
+def _shape_arrays(who, n, sizes, orientations):
+    """(sizes, orientations) as the C entries take them, None for None"""
+    return (None if sizes is None else _sizes_array(who, sizes),
+            None if orientations is None else _orientations_array(who, n, orientations))
+
+
+def _packed_out(who, n, planes_per_frame, capacities, packed_capacity, out):
+    """The output of a packed call: (out, packed_capacity, the int64 tensor [2 n + 1] of sizes and offsets).
+    packed_capacity defaults to len(out), or to the capacities' sum, each rounded up to 16, which always fits."""
+    import torch
+    dev = _ragged_device(planes_per_frame)
+    if packed_capacity is None:
+        packed_capacity = int(out.numel()) if out is not None else sum((int(c) + 15) & ~15 for c in capacities)
+    packed_capacity = int(packed_capacity)
+    if out is None:
+        out = torch.empty(max(packed_capacity, 16), dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
+        raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
+    return out, packed_capacity, torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+
+
+def _split_meta(n, out, meta, *answers):
+    """a packed call's return tuple: sizes [n] and offsets [n + 1] as views of the one tensor"""
+    return (out, meta[:n], meta[n:]) + answers
+
+
+def _made_out(who, planes_per_frame, need, out):
+    """the buffer a picture-making call writes: the caller's, or one of `need` bytes on the pictures' device"""
+    import torch
+    dev = _ragged_device(planes_per_frame)
+    if out is None:
+        out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor")
+    return out
+
+
+def _frame_views(out, made, fmt):
+    """The pictures a picture-making call made, as views of `out`: [h, w, 3] (SRC_RGB), a tuple (y, u, v) of planes
+    (SRC_YUV420 / SRC_YUV444) or [h, w] (gray)."""
+    base = out.storage_offset() - out.data_ptr()     # (as_strided counts from the start of the storage: `out` may be a slice)
+    if fmt == SRC_RGB:
+        return [out.as_strided((r.height, r.width, 3), (int(r.row_stride[0]), 3, 1), base + int(r.plane[0])) for r in made]
+    if fmt in (SRC_YUV420, SRC_YUV444):
+        return [tuple(out.as_strided(yuv_plane_size(fmt, r.width, r.height, c)[::-1], (int(r.row_stride[c]), 1),
+                                     base + int(r.plane[c])) for c in range(3)) for r in made]
+    return [out.as_strided((r.height, r.width), (int(r.row_stride[0]), 1), base + int(r.plane[0])) for r in made]
 
 
 def _ragged_args(who, n, quant, min_quant, search, yuv_mode, capacities, dims):
@@ -2778,6 +2634,109 @@ def _chw_planes(who, images, fp=None):
     return planes, dims, dev, fmt
 
 
+def _pictures(who, images, chw, fp=None, alpha=False, fine=False):
+    """The one reader of a call's pictures: (planes, dims, device, format).  layout="hwc": CUDA uint8 tensors [H, W, 3] of
+    packed RGB on one device, each handed over as one plane of rows -- SRC_RGB; refused in the three sentences of
+    encode_images and encode_images_full (fine) or in the one of the other calls.  chw: what _chw_planes reads, with fp
+    the call's FloatPixels.  alpha: what _alpha_pictures reads."""
+    import torch
+    images = list(images)
+    if not images:
+        raise SjpegError(f"{who}: no images")
+    if alpha:
+        return _alpha_pictures(who, images, fp)
+    if chw:
+        return _chw_planes(who, images, fp)
+    dev = None
+    for k, im in enumerate(images):
+        if not (isinstance(im, torch.Tensor) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and
+                im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
+            if not fine:
+                raise SjpegError(f"{who}: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
+            if not isinstance(im, torch.Tensor) or not im.is_cuda:
+                raise SjpegError(f"{who}: image {k} is not a CUDA tensor")
+            if im.dtype != torch.uint8:
+                raise SjpegError(f"{who}: image {k} is {im.dtype}, not torch.uint8")
+            raise SjpegError(f"{who}: image {k} must be [H, W, 3] packed RGB (stride 1 over the channels, "
+                             f"3 over x)")
+        if dev is None:
+            dev = im.device
+        elif im.device != dev:
+            raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {dev}")
+    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
+    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+    return planes, dims, dev, SRC_RGB
+
+
+class _Shaping:
+    """What a call's wrappers ask for before the pictures are coded: flat (the Flattened), orients, factors, sizes (None:
+    nothing to do), fp (the FloatPixels whose transform the engine takes); every: launch the resize even where the
+    sizes are the pictures' own (the calls that return the pictures do)."""
+
+    def __init__(self, flat, orients, factors, sizes, fp):
+        self.flat, self.orients, self.factors, self.sizes, self.fp, self.every = flat, orients, factors, sizes, fp, False
+
+
+def _unwrap(who, images, chw):
+    """(the bare images of a call, the _Shaping its wrappers ask for): the one place where Flattened, Oriented, Reduced,
+    Resized and FloatPixels come off, in this order.  A new wrapper comes off here."""
+    images, flat = _flattened(who, images, chw)
+    images, orients = _oriented(images)
+    images, factors = _reduced(images)
+    images, sizes = _resized(images)
+    images, fp = _float_pixels(who, images, chw)
+    return images, _Shaping(flat, orients, factors, sizes, fp if flat is None else flat.fp)
+
+
+def _engine_for(engine, dev, fp=None):
+    """the caller's engine, or one made for the pictures' device; the transform of a FloatPixels is set on it"""
+    eng = engine or Engine(dev.index or 0)
+    if fp is not None:
+        eng.set_pixel_transform(fp.scale, fp.bias)
+    return eng
+
+
+def _shape(eng, dev, fmt, planes, dims, todo):
+    """Runs the one launch a _Shaping asks for -- flatten_ragged, reduce_ragged, orient_ragged or resize_ragged -- and
+    returns (fmt, planes, dims) of the uint8 pictures it made, for the rest of the call to code; they live until it
+    returns.  Nothing to do: the arguments as they came."""
+    import torch
+    with torch.cuda.device(dev):
+        if todo.flat is not None:
+            # (Flattened: laid over the background, resized and turned upright by the one launch)
+            fmt, made, _ = eng.flatten_ragged(fmt, planes, dims, todo.flat.flatten, todo.flat.sizes, todo.flat.orientations)
+        elif todo.factors is not None:
+            fmt, made, _ = eng.reduce_ragged(fmt, planes, dims, todo.factors)
+        elif todo.orients is not None:
+            # (Oriented: resized and turned upright by the one launch)
+            fmt, made, _ = eng.orient_ragged(fmt, planes, dims, todo.sizes, todo.orients)
+        elif todo.sizes is not None and (todo.every or todo.sizes != dims):
+            fmt, made, _ = eng.resize_ragged(fmt, planes, dims, todo.sizes)
+        else:
+            return fmt, planes, dims
+    return fmt, [[p] for p in made], [(int(p.shape[1]), int(p.shape[0])) for p in made]
+
+
+def _one_target(who, target_size, target_psnr):
+    """the target of a call -- its target_size or its target_psnr --, or None"""
+    if target_size is not None and target_psnr is not None:
+        raise SjpegError(f"{who}: give target_size or target_psnr, not both")
+    return target_size if target_size is not None else target_psnr
+
+
+def _target_search(who, what, n, target_size, target_psnr, passes=10, tolerance=1.0, qmin=0.0, qmax=100.0):
+    """The SearchParams of a call's target, one value or one per `what` (image, frame, sheet): a list of n, or None
+    without a target."""
+    target = target_size if target_size is not None else target_psnr
+    if target is None:
+        return None
+    ts = _per_picture(target, n)
+    if len(ts) != n:
+        raise SjpegError(f"{who}: one target per {what}")
+    mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
+    return [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+
+
 def _gray_mode(who, fmt, yuv_mode):
     """gray float pictures are coded in YUV_400 and nothing else"""
     if fmt in _GRAY_FLOAT and int(yuv_mode) != YUV_400:
@@ -2825,15 +2784,10 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     target_size counts them, and the output buffers make room for them.  (It stands in front of layout, which stays
     the last parameter: pass layout by keyword.)"""
     import torch
-    chw = _check_layout("encode_images", layout)
-    images, flat = _flattened("encode_images", images, chw)
-    images, orients = _oriented(images)
-    images, factors = _reduced(images)
-    images, new_sizes = _resized(images)
-    images, fp = _float_pixels("encode_images", images, chw)
-    if target_size is not None and target_psnr is not None:
-        raise SjpegError("encode_images: give target_size or target_psnr, not both")
-    target = target_size if target_size is not None else target_psnr
+    who = "encode_images"
+    chw = _check_layout(who, layout)
+    images, todo = _unwrap(who, images, chw)
+    target = _one_target(who, target_size, target_psnr)
     if use_trellis and target is not None:
         raise SjpegError("encode_images: a target size or PSNR is not searched with the trellis (use_trellis): that "
                          "search prices every pass with the pass's own codes")
@@ -2857,71 +2811,19 @@ def encode_images(images, quality=75.0, yuv_mode=YUV_420, engine=None, method=0,
     images = list(images)
     if not images:
         raise SjpegError("encode_images: no images")
-    if yuv_mode in (YUV_AUTO, YUV_SHARP) and not chw and flat is None:
+    if yuv_mode in (YUV_AUTO, YUV_SHARP) and not chw and todo.flat is None:
         for k, im in enumerate(images):
             if len(getattr(im, "shape", ())) != 3 or im.shape[2] != 3:
                 raise SjpegError(f"encode_images: image {k}: YUV_AUTO and YUV_SHARP take RGB pictures [H, W, 3]")
     n = len(images)
-    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    qs = _per_picture(quality, n)
     if len(qs) != n:
         raise SjpegError("encode_images: one quality per image")
-    dev = None
-    for k, im in enumerate(() if chw or flat is not None else images):
-        if not isinstance(im, torch.Tensor) or not im.is_cuda:
-            raise SjpegError(f"encode_images: image {k} is not a CUDA tensor")
-        if im.dtype != torch.uint8:
-            raise SjpegError(f"encode_images: image {k} is {im.dtype}, not torch.uint8")
-        if im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-            raise SjpegError(f"encode_images: image {k} must be [H, W, 3] packed RGB (stride 1 over the channels, "
-                             f"3 over x)")
-        if dev is None:
-            dev = im.device
-        elif im.device != dev:
-            raise SjpegError(f"encode_images: image {k} is on {im.device}, image 0 on {dev}")
-    fmt = SRC_RGB
-    if flat is not None:
-        fp = flat.fp
-        planes, dims, dev, fmt = _alpha_pictures("encode_images", images, fp)
-    elif chw:
-        planes, dims, dev, fmt = _chw_planes("encode_images", images, fp)
-        _gray_mode("encode_images", fmt, yuv_mode)
-    else:
-        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    if flat is not None:
-        # (Flattened: laid over the background, resized and turned upright by the one launch)
-        with torch.cuda.device(dev):
-            fmt, flat_pictures, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
-        planes = [[p] for p in flat_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in flat_pictures]
-    if factors is not None:
-        # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
-        with torch.cuda.device(dev):
-            fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
-        planes = [[p] for p in reduced_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
-    if orients is not None:
-        # (Oriented: resized and turned upright by the one launch)
-        with torch.cuda.device(dev):
-            fmt, resized_pictures, _ = eng.orient_ragged(fmt, planes, dims, new_sizes, orients)
-        planes = [[p] for p in resized_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
-    elif new_sizes is not None and new_sizes != dims:
-        # (Resized: as Reduced, through the resize kernel)
-        with torch.cuda.device(dev):
-            fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
-        planes = [[p] for p in resized_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
-    search = None
-    if target is not None:
-        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
-        if len(ts) != n:
-            raise SjpegError("encode_images: one target per image")
-        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
-        search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+    planes, dims, dev, fmt = _pictures(who, images, chw, todo.fp, alpha=todo.flat is not None, fine=True)
+    _gray_mode(who, fmt, yuv_mode)
+    eng = _engine_for(engine, dev, todo.fp)
+    fmt, planes, dims = _shape(eng, dev, fmt, planes, dims, todo)
+    search = _target_search(who, "image", n, target_size, target_psnr, passes, tolerance, qmin, qmax)
     _, _, _, metas = _metadata_args("encode_images", n, metadata)
     if metadata is not None and not packed and not (method == 0 and target is None and yuv_mode not in (YUV_AUTO, YUV_SHARP)):
         # (every flow below but the method 0 call with ready headers: the one call that takes them all, with metadata)
@@ -3028,15 +2930,10 @@ def encode_images_full_meta(images, metadata, layout="hwc", **params):
 def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, target_size, target_psnr, passes,
                         tolerance, qmin, qmax, min_quant, q_bias, dmax_luma, dmax_chroma, engine, packed, metadata=None):
     import torch
-    chw = _check_layout("encode_images_full", layout)
-    images, flat = _flattened("encode_images_full", images, chw)
-    images, orients = _oriented(images)
-    images, factors = _reduced(images)
-    images, new_sizes = _resized(images)
-    images, fp = _float_pixels("encode_images_full", images, chw)
-    if target_size is not None and target_psnr is not None:
-        raise SjpegError("encode_images_full: give target_size or target_psnr, not both")
-    target = target_size if target_size is not None else target_psnr
+    who = "encode_images_full"
+    chw = _check_layout(who, layout)
+    images, todo = _unwrap(who, images, chw)
+    _one_target(who, target_size, target_psnr)
     method = int(method)
     if method < 0 or method > 8:
         raise SjpegError(f"encode_images_full: method {method} is not one of 0..8")
@@ -3049,66 +2946,14 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     if not images:
         raise SjpegError("encode_images_full: no images")
     n = len(images)
-    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    qs = _per_picture(quality, n)
     if len(qs) != n:
         raise SjpegError("encode_images_full: one quality per image")
-    dev = None
-    for k, im in enumerate(() if chw or flat is not None else images):
-        if not isinstance(im, torch.Tensor) or not im.is_cuda:
-            raise SjpegError(f"encode_images_full: image {k} is not a CUDA tensor")
-        if im.dtype != torch.uint8:
-            raise SjpegError(f"encode_images_full: image {k} is {im.dtype}, not torch.uint8")
-        if im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-            raise SjpegError(f"encode_images_full: image {k} must be [H, W, 3] packed RGB (stride 1 over the channels, "
-                             f"3 over x)")
-        if dev is None:
-            dev = im.device
-        elif im.device != dev:
-            raise SjpegError(f"encode_images_full: image {k} is on {im.device}, image 0 on {dev}")
-    fmt = SRC_RGB
-    if flat is not None:
-        fp = flat.fp
-        planes, dims, dev, fmt = _alpha_pictures("encode_images_full", images, fp)
-    elif chw:
-        planes, dims, dev, fmt = _chw_planes("encode_images_full", images, fp)
-        _gray_mode("encode_images_full", fmt, yuv_mode)
-    else:
-        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    if flat is not None:
-        # (Flattened: laid over the background, resized and turned upright by the one launch)
-        with torch.cuda.device(dev):
-            fmt, flat_pictures, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
-        planes = [[p] for p in flat_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in flat_pictures]
-    if factors is not None:
-        # (Reduced: one launch makes the uint8 pictures the rest of the call codes; they live until it returns)
-        with torch.cuda.device(dev):
-            fmt, reduced_pictures, _ = eng.reduce_ragged(fmt, planes, dims, factors)
-        planes = [[p] for p in reduced_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in reduced_pictures]
-    if orients is not None:
-        # (Oriented: resized and turned upright by the one launch)
-        with torch.cuda.device(dev):
-            fmt, resized_pictures, _ = eng.orient_ragged(fmt, planes, dims, new_sizes, orients)
-        planes = [[p] for p in resized_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
-    elif new_sizes is not None and new_sizes != dims:
-        # (Resized: as Reduced, through the resize kernel)
-        with torch.cuda.device(dev):
-            fmt, resized_pictures, _ = eng.resize_ragged(fmt, planes, dims, new_sizes)
-        planes = [[p] for p in resized_pictures]
-        dims = [(int(p.shape[1]), int(p.shape[0])) for p in resized_pictures]
-    search = None
-    if target is not None:
-        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
-        if len(ts) != n:
-            raise SjpegError("encode_images_full: one target per image")
-        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
-        search = [SearchParams(mode, float(t), int(passes), float(tolerance), float(qmin), float(qmax)) for t in ts]
+    planes, dims, dev, fmt = _pictures(who, images, chw, todo.fp, alpha=todo.flat is not None, fine=True)
+    _gray_mode(who, fmt, yuv_mode)
+    eng = _engine_for(engine, dev, todo.fp)
+    fmt, planes, dims = _shape(eng, dev, fmt, planes, dims, todo)
+    search = _target_search(who, "image", n, target_size, target_psnr, passes, tolerance, qmin, qmax)
     with torch.cuda.device(dev):
         if packed:
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method, min_quant, q_bias,
@@ -3147,7 +2992,8 @@ def riskiness_images(images, engine=None, layout="hwc"):
     of it alone, from one ragged riskiness call.  layout="chw": the pictures are [3, H_k, W_k] instead, as encode_images
     takes them."""
     import torch
-    chw = _check_layout("riskiness_images", layout)
+    who = "riskiness_images"
+    chw = _check_layout(who, layout)
     if isinstance(images, Reduced):
         raise SjpegError("riskiness_images: Reduced pictures are not taken: reduce first -- "
                          "riskiness_images(reduce_images(images, factor)) -- the verdict is that of the reduced picture")
@@ -3160,29 +3006,12 @@ def riskiness_images(images, engine=None, layout="hwc"):
     if isinstance(images, Flattened):
         raise SjpegError("riskiness_images: Flattened pictures are not taken: flatten first -- "
                          "riskiness_images(flatten_images(images, ...)) -- the verdict is that of the flattened picture")
-    images, fp = _float_pixels("riskiness_images", images, chw)
-    images = list(images)
-    if not images:
-        raise SjpegError("riskiness_images: no images")
-    if chw:
-        planes, dims, dev, fmt = _chw_planes("riskiness_images", images, fp)
-        _gray_mode("riskiness_images", fmt, YUV_AUTO)
-        eng = engine or Engine(dev.index or 0)
-        if fp is not None:
-            eng.set_pixel_transform(fp.scale, fp.bias)
-        with torch.cuda.device(dev):
-            sums = eng.riskiness_ragged(fmt, planes, dims).cpu().numpy()
-        return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
-    for k, im in enumerate(images):
-        if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
-                im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-            raise SjpegError(f"riskiness_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
-    dev = images[0].device
-    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
+    images, fp = _float_pixels(who, images, chw)
+    planes, dims, dev, fmt = _pictures(who, images, chw, fp)
+    _gray_mode(who, fmt, YUV_AUTO)
+    eng = _engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
-        sums = eng.riskiness_ragged(SRC_RGB, planes, dims).cpu().numpy()
+        sums = eng.riskiness_ragged(fmt, planes, dims).cpu().numpy()
     return [riskiness_verdict(sums[k], w, h) for k, (w, h) in enumerate(dims)]
 
 
@@ -3193,33 +3022,9 @@ def reduce_images(images, factor, engine=None, layout="hwc"):
     [h'_k, w'_k, 3] (layout="chw": [3, h'_k, w'_k], channels-last in memory, which the layout="chw" calls take as they
     are; gray FloatPixels: [h'_k, w'_k]).  Rows are padded to a multiple of 4 bytes: the views are not contiguous.  The
     pixel transform of a FloatPixels is set on the engine (it stays set)."""
-    import torch
     chw = _check_layout("reduce_images", layout)
     red = Reduced(images, factor)
-    images, fp = _float_pixels("reduce_images", red.images, chw)
-    images = list(images)
-    if not images:
-        raise SjpegError("reduce_images: no images")
-    if chw:
-        planes, dims, dev, fmt = _chw_planes("reduce_images", images, fp)
-    else:
-        for k, im in enumerate(images):
-            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
-                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-                raise SjpegError(f"reduce_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
-            if im.device != images[0].device:
-                raise SjpegError(f"reduce_images: image {k} is on {im.device}, image 0 on {images[0].device}")
-        dev, fmt = images[0].device, SRC_RGB
-        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    with torch.cuda.device(dev):
-        rfmt, pics, _ = eng.reduce_ragged(fmt, planes, dims, red.factors)
-        if engine is None:
-            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
-    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+    return _made_images("reduce_images", red, engine, chw, factors=red.factors)
 
 
 def resize_images(images, sizes, engine=None, layout="hwc"):
@@ -3229,33 +3034,8 @@ def resize_images(images, sizes, engine=None, layout="hwc"):
     returns: uint8 CUDA tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k], channels-last in memory; gray FloatPixels:
     [h_k, w_k]), rows padded to a multiple of 4 bytes.  The pixel transform of a FloatPixels is set on the engine (it
     stays set)."""
-    import torch
     chw = _check_layout("resize_images", layout)
-    res = Resized(images, sizes)
-    images, fp = _float_pixels("resize_images", res.images, chw)
-    images = list(images)
-    if not images:
-        raise SjpegError("resize_images: no images")
-    if chw:
-        planes, dims, dev, fmt = _chw_planes("resize_images", images, fp)
-    else:
-        for k, im in enumerate(images):
-            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
-                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-                raise SjpegError(f"resize_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
-            if im.device != images[0].device:
-                raise SjpegError(f"resize_images: image {k} is on {im.device}, image 0 on {images[0].device}")
-        dev, fmt = images[0].device, SRC_RGB
-        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    with torch.cuda.device(dev):
-        rfmt, pics, _ = eng.resize_ragged(fmt, planes, dims, res.sizes)
-        if engine is None:
-            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
-    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+    return _made_images("resize_images", Resized(images, sizes), engine, chw, every=True)
 
 
 def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
@@ -3263,33 +3043,9 @@ def orient_images(images, orientations, sizes=None, engine=None, layout="hwc"):
     launch of the resize kernel: images, sizes (None: the pictures' own), engine and layout as resize_images takes them,
     orientations one EXIF Orientation 1..8 or one per picture.  Returns what resize_images returns, picture k being
     [h_k, w_k, 3] for the orientations 1..4 and [w_k, h_k, 3] for 5..8 (layout="chw": channel-first views)."""
-    import torch
     chw = _check_layout("orient_images", layout)
     ori = Oriented(images, orientations, sizes)
-    images, fp = _float_pixels("orient_images", ori.images, chw)
-    images = list(images)
-    if not images:
-        raise SjpegError("orient_images: no images")
-    if chw:
-        planes, dims, dev, fmt = _chw_planes("orient_images", images, fp)
-    else:
-        for k, im in enumerate(images):
-            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
-                    im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-                raise SjpegError(f"orient_images: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
-            if im.device != images[0].device:
-                raise SjpegError(f"orient_images: image {k} is on {im.device}, image 0 on {images[0].device}")
-        dev, fmt = images[0].device, SRC_RGB
-        planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-        dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    with torch.cuda.device(dev):
-        rfmt, pics, _ = eng.orient_ragged(fmt, planes, dims, ori.sizes, ori.orientations)
-        if engine is None:
-            torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
-    return [p.permute(2, 0, 1) for p in pics] if chw and rfmt == SRC_RGB else pics
+    return _made_images("orient_images", ori, engine, chw, orients=ori.orientations)
 
 
 def flatten_images(images, background=(255, 255, 255), premultiplied=False, alpha_scale=255.0, alpha_bias=0.0,
@@ -3298,20 +3054,27 @@ def flatten_images(images, background=(255, 255, 255), premultiplied=False, alph
     launch of the resize kernel: images CUDA uint8 tensors [H_k, W_k, 4] or a FloatPixels of float tensors [H_k, W_k, 4]
     (R, G, B, alpha), the other arguments as Flattened takes them.  Returns uint8 CUDA tensors [h_k, w_k, 3] (upright:
     [w_k, h_k, 3] for the orientations 5..8), rows padded to a multiple of 4 bytes."""
-    import torch
     chw = _check_layout("flatten_images", layout)
     flat = images if isinstance(images, Flattened) else Flattened(images, background, premultiplied, alpha_scale, alpha_bias,
                                                                    orientations, sizes)
-    pictures, flat = _flattened("flatten_images", flat, chw)
-    planes, dims, dev, fmt = _alpha_pictures("flatten_images", pictures, flat.fp)
-    eng = engine or Engine(dev.index or 0)
-    if flat.fp is not None:
-        eng.set_pixel_transform(flat.fp.scale, flat.fp.bias)
-    with torch.cuda.device(dev):
-        _, pics, _ = eng.flatten_ragged(fmt, planes, dims, flat.flatten, flat.sizes, flat.orientations)
-        if engine is None:
+    return _made_images("flatten_images", flat, engine, chw)
+
+
+def _made_images(who, wrapped, engine, chw, **always):
+    """reduce_images, resize_images, orient_images and flatten_images: the pictures the wrapper codes, from its one launch.
+    always: what the call hands to that launch even where it changes nothing (factors and orientations that are all 1,
+    sizes that are the pictures' own)."""
+    import torch
+    images, todo = _unwrap(who, wrapped, chw)
+    planes, dims, dev, fmt = _pictures(who, images, chw, todo.fp, alpha=todo.flat is not None)
+    eng = _engine_for(engine, dev, todo.fp)
+    vars(todo).update(always)
+    fmt, planes, _ = _shape(eng, dev, fmt, planes, dims, todo)
+    if engine is None:
+        with torch.cuda.device(dev):
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
-    return pics
+    pics = [p[0] for p in planes]
+    return [p.permute(2, 0, 1) for p in pics] if chw and fmt == SRC_RGB else pics
 
 
 def _sheet_flatten(who, flatten, sheet):
@@ -3336,39 +3099,23 @@ def _sheet_flatten(who, flatten, sheet):
 def _sheet_pictures(who, images, layout, flatten=None):
     """(planes, dims, device, format, FloatPixels or None) of the pictures a sheet call takes: those of resize_images;
     with a flatten, those of flatten_images"""
-    import torch
     chw = _check_layout(who, layout)
     if isinstance(images, (Reduced, Resized, Oriented, Flattened)):
         raise SjpegError(f"{who}: Reduced, Resized, Oriented and Flattened pictures are not taken: give sizes, orientations and "
                          f"flatten to the call")
+    if flatten is not None and chw:
+        raise SjpegError(f"{who}: layout='chw' has no alpha format: flatten takes [H, W, 4] pictures, layout='hwc'")
     if flatten is not None:
-        if chw:
-            raise SjpegError(f"{who}: layout='chw' has no alpha format: flatten takes [H, W, 4] pictures, layout='hwc'")
         fp = images if isinstance(images, FloatPixels) else None
-        planes, dims, dev, fmt = _alpha_pictures(who, images.images if fp is not None else images, fp)
-        return planes, dims, dev, fmt, fp
-    images, fp = _float_pixels(who, images, chw)
-    images = list(images)
-    if not images:
-        raise SjpegError(f"{who}: no images")
-    if chw:
-        planes, dims, dev, fmt = _chw_planes(who, images, fp)
-        return planes, dims, dev, fmt, fp
-    for k, im in enumerate(images):
-        if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or \
-                im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-            raise SjpegError(f"{who}: image {k} must be a CUDA uint8 tensor [H, W, 3] of packed RGB")
-        if im.device != images[0].device:
-            raise SjpegError(f"{who}: image {k} is on {im.device}, image 0 on {images[0].device}")
-    planes = [[im.as_strided((im.shape[0], im.shape[1] * 3), (im.stride(0), 1))] for im in images]
-    dims = [(int(im.shape[1]), int(im.shape[0])) for im in images]
-    return planes, dims, images[0].device, SRC_RGB, fp
+        images = images.images if fp is not None else images
+    else:
+        images, fp = _float_pixels(who, images, chw)
+    return _pictures(who, images, chw, fp, alpha=flatten is not None) + (fp,)
 
 
-def _per_picture(who, n, orientations):
-    if orientations is not None and not isinstance(orientations, (list, tuple, np.ndarray)):
-        orientations = [orientations] * n
-    return None if orientations is None else [int(o) for o in _orientations_array(who, n, orientations)]
+def _orientation_list(who, n, orientations):
+    """the orientations of a call -- None, one EXIF value or one per picture -- as a list of n ints, or None"""
+    return None if orientations is None else [int(o) for o in _orientations_array(who, n, _per_picture(orientations, n))]
 
 
 def make_sheets(images, sheet, sizes=None, orientations=None, engine=None, layout="hwc", flatten=None):
@@ -3385,56 +3132,35 @@ def make_sheets(images, sheet, sizes=None, orientations=None, engine=None, layou
     who = "make_sheets"
     flatten = _sheet_flatten(who, flatten, sheet)
     planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout, flatten)
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
+    eng = _engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
-        _, sheets, _ = eng.sheet_ragged(fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations), flatten=flatten)
+        _, sheets, _ = eng.sheet_ragged(fmt, planes, dims, sheet, sizes, _orientation_list(who, len(dims), orientations), flatten=flatten)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return sheets
-
-
-def _sheet_search(who, ns, target_size, target_psnr):
-    if target_size is not None and target_psnr is not None:
-        raise SjpegError(f"{who}: give target_size or target_psnr, not both")
-    target = target_size if target_size is not None else target_psnr
-    if target is None:
-        return None
-    ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * ns
-    if len(ts) != ns:
-        raise SjpegError(f"{who}: one target per sheet")
-    mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
-    return [SearchParams(mode, float(t), 10, 1.0, 0.0, 100.0) for t in ts]
 
 
 def _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, quality, method, use_trellis,
                    target_size, target_psnr, packed, metadata, flatten=None):
     """the rest of encode_sheets / encode_yuv_sheets: (list of JPEG bytes, places)"""
     import torch
-    n = len(dims)
     places = sheet_places(sheet, dims, fmt, sizes, orientations)
     ns = places[-1][0] + 1
     method = int(method)
     if use_trellis:
         method = {4: 7, 6: 8}.get(method, method)
-    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * ns
+    qs = _per_picture(quality, ns)
     if len(qs) != ns:
         raise SjpegError(f"{who}: one quality per sheet")
-    search = _sheet_search(who, ns, target_size, target_psnr)
+    _one_target(who, target_size, target_psnr)
+    search = _target_search(who, "sheet", ns, target_size, target_psnr)
     with torch.cuda.device(dev):
         if packed:
             out, sz, offs, _, _, _ = eng.encode_ragged_sheet_packed(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
                                                                     _quality_quant(qs), method, search=search, metadata=metadata,
                                                                     flatten=flatten)
             eng.wait()
-            meta = torch.cat([sz, offs]).cpu().numpy()
-            sz, offs = meta[:ns], meta[ns:2 * ns]
-            if (sz <= 0).any():
-                raise SjpegError("sheet %d did not fit its output capacity (the device reported size 0)" % int(np.argmax(sz <= 0)))
-            top = int(max(offs[k] + sz[k] for k in range(ns)))
-            host = out[:top].cpu().numpy()                    # the ONE copy of the sheets
-            return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(ns)], places
+            return _fetch_packed(out, sz, offs, ns, "sheet"), places
         out, sz, offs, _, _, _ = eng.encode_ragged_sheet(fmt, planes, dims, sheet, sizes, orientations, yuv_mode,
                                                          _quality_quant(qs), method, search=search, metadata=metadata,
                                                          flatten=flatten)
@@ -3454,25 +3180,17 @@ def encode_sheets(images, sheet, sizes=None, orientations=None, quality=75.0, yu
     flatten = _sheet_flatten(who, flatten, sheet)
     planes, dims, dev, fmt, fp = _sheet_pictures(who, images, layout, flatten)
     _gray_mode(who, fmt, int(yuv_mode))
-    eng = engine or Engine(dev.index or 0)
-    if fp is not None:
-        eng.set_pixel_transform(fp.scale, fp.bias)
-    return _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, _per_picture(who, len(dims), orientations), int(yuv_mode),
-                          quality, method, use_trellis, target_size, target_psnr, packed, metadata, flatten)
+    eng = _engine_for(engine, dev, fp)
+    return _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, _orientation_list(who, len(dims), orientations),
+                          int(yuv_mode), quality, method, use_trellis, target_size, target_psnr, packed, metadata, flatten)
 
 
-def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations=None, quality=75.0, method=4,
-                      target_size=None, target_psnr=None, packed=False, metadata=None, engine=None):
-    """encode_sheets for decoded video, shaped like encode_yuv_frames: frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 or
-    (y, u, v) for SRC_YUV420 / SRC_YUV444, each resized plane by plane (sizes None: fitted into its cell), turned and
-    stored into its cell -- chroma at half the luma's place for the 4:2:0 formats, whose Sheet takes even cells, gutter
-    and margin; background is (Y, U, V).  No colour conversion: the sheets are coded 4:2:0 (SRC_YUV444: 4:4:4).
-    Returns (JPEGs, places) as encode_sheets -- the storyboard behind a scrub bar in one call."""
+def _yuv_frames(who, frames, fmt):
+    """(planes, dims, device) of the frames a YUV call takes: frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 or (y, u, v)
+    for SRC_YUV420 / SRC_YUV444, every plane a uint8 CUDA tensor [rows, bytes] with stride 1 along a row"""
     import torch
-    who = "encode_yuv_sheets"
     frames = [tuple(fr) for fr in frames]
-    n = len(frames)
-    if n == 0:
+    if not frames:
         raise SjpegError(f"{who}: no frames")
     nplanes = 2 if fmt in (SRC_NV12, SRC_NV21) else 3 if fmt in (SRC_YUV420, SRC_YUV444) else 0
     if nplanes == 0:
@@ -3483,10 +3201,32 @@ def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations
         for p in fr:
             if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 2 or p.stride(1) != 1:
                 raise SjpegError(f"{who}: frame {k}: a plane is a uint8 CUDA tensor [rows, bytes] with stride 1 along a row")
-    dims = [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames]
-    dev = frames[0][0].device
-    eng = engine or Engine(dev.index or 0)
-    return _encode_sheets(who, eng, dev, fmt, [list(fr) for fr in frames], dims, sheet, sizes, _per_picture(who, n, orientations),
+    return [list(fr) for fr in frames], [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames], frames[0][0].device
+
+
+def _fetch_packed(out, sizes, offsets, n, what):
+    """The JPEGs of a packed call as byte strings: one copy of the sizes and offsets, ONE of the frames."""
+    import torch
+    meta = torch.cat([sizes, offsets]).cpu().numpy()
+    sz, offs = meta[:n], meta[n:2 * n]
+    if (sz <= 0).any():
+        raise SjpegError("%s %d did not fit its output capacity (the device reported size 0)" % (what, int(np.argmax(sz <= 0))))
+    top = int(max(offs[k] + sz[k] for k in range(n)))
+    host = out[:top].cpu().numpy()
+    return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(n)]
+
+
+def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations=None, quality=75.0, method=4,
+                      target_size=None, target_psnr=None, packed=False, metadata=None, engine=None):
+    """encode_sheets for decoded video, shaped like encode_yuv_frames: frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 or
+    (y, u, v) for SRC_YUV420 / SRC_YUV444, each resized plane by plane (sizes None: fitted into its cell), turned and
+    stored into its cell -- chroma at half the luma's place for the 4:2:0 formats, whose Sheet takes even cells, gutter
+    and margin; background is (Y, U, V).  No colour conversion: the sheets are coded 4:2:0 (SRC_YUV444: 4:4:4).
+    Returns (JPEGs, places) as encode_sheets -- the storyboard behind a scrub bar in one call."""
+    who = "encode_yuv_sheets"
+    planes, dims, dev = _yuv_frames(who, frames, fmt)
+    eng = _engine_for(engine, dev)
+    return _encode_sheets(who, eng, dev, fmt, planes, dims, sheet, sizes, _orientation_list(who, len(dims), orientations),
                           YUV_444 if fmt == SRC_YUV444 else YUV_420, quality, method, False, target_size, target_psnr, packed,
                           metadata)
 
@@ -3505,26 +3245,11 @@ def encode_yuv_frames(frames, fmt=SRC_NV12, sizes=None, box=None, orientations=N
     packed=True: through the packed entry and one device-to-host copy; metadata: as encode_images."""
     import torch
     who = "encode_yuv_frames"
-    frames = [tuple(fr) for fr in frames]
-    n = len(frames)
-    if n == 0:
-        raise SjpegError(f"{who}: no frames")
-    nplanes = 2 if fmt in (SRC_NV12, SRC_NV21) else 3 if fmt in (SRC_YUV420, SRC_YUV444) else 0
-    if nplanes == 0:
-        raise SjpegError(f"{who}: fmt {fmt} is not SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444")
-    for k, fr in enumerate(frames):
-        if len(fr) != nplanes:
-            raise SjpegError(f"{who}: frame {k} has {len(fr)} planes, the format takes {nplanes}")
-        for p in fr:
-            if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 2 or p.stride(1) != 1:
-                raise SjpegError(f"{who}: frame {k}: a plane is a uint8 CUDA tensor [rows, bytes] with stride 1 along a row")
-    dims = [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames]
+    planes, dims, dev = _yuv_frames(who, frames, fmt)
+    n = len(dims)
     if sizes is not None and box is not None:
         raise SjpegError(f"{who}: give sizes or box, not both")
-    if orientations is not None and not isinstance(orientations, (list, tuple, np.ndarray)):
-        orientations = [orientations] * n
-    if orientations is not None:
-        orientations = [int(o) for o in _orientations_array(who, n, orientations)]
+    orientations = _orientation_list(who, n, orientations)
     if box is not None:
         try:
             bw, bh = box
@@ -3532,36 +3257,20 @@ def encode_yuv_frames(frames, fmt=SRC_NV12, sizes=None, box=None, orientations=N
             raise SjpegError(f"{who}: box {box!r} is not a pair (width, height)")
         sizes = [fit_size(w, h, (bh, bw) if orientations is not None and orientations[k] >= 5 else (bw, bh))
                  for k, (w, h) in enumerate(dims)]
-    if target_size is not None and target_psnr is not None:
-        raise SjpegError(f"{who}: give target_size or target_psnr, not both")
-    target = target_size if target_size is not None else target_psnr
-    search = None
-    if target is not None:
-        ts = list(target) if isinstance(target, (list, tuple, np.ndarray)) else [target] * n
-        if len(ts) != n:
-            raise SjpegError(f"{who}: one target per frame")
-        mode = TARGET_SIZE if target_size is not None else TARGET_PSNR
-        search = [SearchParams(mode, float(t), 10, 1.0, 0.0, 100.0) for t in ts]
-    qs = list(quality) if isinstance(quality, (list, tuple, np.ndarray)) else [quality] * n
+    _one_target(who, target_size, target_psnr)
+    search = _target_search(who, "frame", n, target_size, target_psnr)
+    qs = _per_picture(quality, n)
     if len(qs) != n:
         raise SjpegError(f"{who}: one quality per frame")
     yuv_mode = YUV_444 if fmt == SRC_YUV444 else YUV_420
-    planes = [list(fr) for fr in frames]
-    dev = frames[0][0].device
-    eng = engine or Engine(dev.index or 0)
+    eng = _engine_for(engine, dev)
     with torch.cuda.device(dev):
         if packed:
             out, sz, offs, _, _, _ = eng.encode_ragged_yuv_resized_packed(fmt, planes, dims, sizes, orientations, yuv_mode,
                                                                           _quality_quant(qs), method, search=search,
                                                                           metadata=metadata)
             eng.wait()
-            meta = torch.cat([sz, offs]).cpu().numpy()
-            sz, offs = meta[:n], meta[n:2 * n]
-            if (sz <= 0).any():
-                raise SjpegError("frame %d did not fit its output capacity (the device reported size 0)" % int(np.argmax(sz <= 0)))
-            top = int(max(offs[k] + sz[k] for k in range(n)))
-            host = out[:top].cpu().numpy()                    # the ONE copy of the pictures
-            return [host[int(offs[k]):int(offs[k] + sz[k])].tobytes() for k in range(n)]
+            return _fetch_packed(out, sz, offs, n, "frame")
         out, sz, offs, _, _, _ = eng.encode_ragged_yuv_resized(fmt, planes, dims, sizes, orientations, yuv_mode,
                                                                _quality_quant(qs), method, search=search, metadata=metadata)
         eng.wait()                               # (pipelined mode: the output is complete after this)
