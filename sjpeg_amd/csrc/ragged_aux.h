@@ -374,4 +374,53 @@ int replay_encode_ragged(sjpeg_hip_engine* e, const std::string& who, int format
                          const void* headers, const size_t* header_offsets, void* d_out, uint64_t* d_sizes, hipStream_t st,
                          const PackedSink* sink);
 
+// ---- one description of a _full_ call (ragged_full.cc) and of the shaped calls on top of it (ragged_shaped.cc)
+// Where a call's streams and answers go: frame f at d_out + its out_offset (strided, the sheet entries: sheet s at
+// s * out_stride) -- or packed: d_out is d_packed, the frames back to back behind the engine's cursor.
+struct RaggedOut {
+  void* d_out;
+  uint64_t* d_sizes;
+  int* modes;
+  float *q_out, *value_out;
+  void* stream;
+  bool packed = false, strided = false;
+  size_t out_stride = 0, packed_capacity = 0;
+  uint64_t* d_offsets = nullptr;
+  RaggedOut strided_by(size_t stride) const { RaggedOut o = *this; o.strided = true; o.out_stride = stride; return o; }
+  RaggedOut packed_into(size_t capacity, uint64_t* offsets) const {          // (d_out is d_packed)
+    RaggedOut o = *this; o.packed = true; o.packed_capacity = capacity; o.d_offsets = offsets; return o;
+  }
+  PackedSink sink(int nframes) const { return {d_out, packed_capacity, d_offsets, nframes, nullptr}; }
+};
+// The call: whose name its messages carry, what it codes and with what.  A pass-through renames it and hands it on; a
+// flow that makes pictures hands on a copy with format, nframes and frames those of what it made.
+struct RaggedCall {
+  const std::string* who;
+  sjpeg_hip_engine* e;
+  int format, nframes;
+  const sjpeg_hip_ragged_frame* frames;
+  const sjpeg_hip_ragged_params* params;
+  const sjpeg_hip_metadata* meta;       // NULL: none
+  int meta_per_frame;
+  RaggedOut out;
+};
+// The checks every encode entry starts with, in the order its messages are recorded in (tests/golden/c_messages.json):
+// engine, params, d_offsets (packed), frames, the entry's sheet (has_sheet), d_out / d_packed, d_sizes, d_packed's
+// alignment and capacity, out_stride (strided), the YUV-plane format (yuv_only), nframes.  Host only.
+int encode_prologue(const RaggedCall& c, bool has_sheet = false, const void* sheet = nullptr, bool yuv_only = false);
+// the checks of a _full_ call behind its prologue (host only), and the call itself: full_checks again, then the search
+int full_checks(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_ragged_params& P);
+int full_flow(const RaggedCall& c);
+// the four sjpeg_hip_encode_ragged_full[_meta][_packed]_src entries: c.who is set here -- meta == NULL answers under
+// the name of the entry without metadata
+int full_entry(RaggedCall c);
+// The call's metadata -- one entry, or one per frame -- checked and turned into segments, before any device work
+int check_metadata(const std::string& who, int nframes, const sjpeg_hip_metadata* meta, int meta_per_frame, MetaCtx* ctx);
+// the engine carries the call's metadata (NULL: the call has none) while the call runs
+struct MetaScope {
+  sjpeg_hip_engine* e;
+  MetaScope(sjpeg_hip_engine* engine, MetaCtx* ctx) : e(ctx != nullptr ? engine : nullptr) { if (e != nullptr) engine_set_meta(e, ctx); }
+  ~MetaScope() { if (e != nullptr) engine_set_meta(e, nullptr); }
+};
+
 }  // namespace sjpeg_internal

@@ -1,5 +1,5 @@
 // ragged_full.cc -- the reference's multi-pass search (Encoder::LoopScan, src/dichotomy.cc:113-205) over a ragged batch:
-// sjpeg_hip_encode_ragged_search_src (one sampling, methods 0..6) and sjpeg_hip_encode_ragged_full_src / _full_packed_src
+// sjpeg_hip_encode_ragged_search_src (one sampling, methods 0..6) and sjpeg_hip_encode_ragged_full[_meta][_packed]_src
 // (sjpeg::Encode(EncoderParam) with EVERY combination of SjpegYUVMode 0..4, method 0..8 and a search per frame: also
 // SJPEG_YUV_AUTO / SJPEG_YUV_SHARP and the trellis methods 7 and 8, each size pass one trellis quantization,
 // src/dichotomy.cc:80-111 StoreRunLevels).  The entry points differ in their checks and messages; the search is ONE flow.
@@ -9,7 +9,7 @@
 // float arithmetic of the search (Setup / NextMatrix / Update); the measurements are the ones the host API prices a pass
 // with (jpeg_host.h: SearchHeaderBits, EntropyBits, SearchPSNR).  The device passes are the engine's ragged ones:
 // histogram (kept for the whole search), adaptation, symbol statistics, counted bits, quantization error.  DESIGN.md
-// section 4.
+// section 4.  The entries on pictures shaped inside the call (ragged_shaped.cc) end in full_flow() here.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -601,8 +601,23 @@ int search_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nfr
   }
 }
 
-// the checks of sjpeg_hip_encode_ragged_full_src / _full_packed_src: host only, the engine is not touched
-int full_checks(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_ragged_params& P) {
+// what is wrong with a metadata member (jpeg_host.h: MetadataFromC names it), in words
+std::string meta_fault(const char* field) {
+  const std::string f = field;
+  if (f == "exif") return "exif: NULL with a size, or its APP1 segment would pass 65535 bytes (at most 65527 bytes of EXIF)";
+  if (f == "iccp") return "iccp: NULL with a size, or a profile of 256 chunks or more (at most 255 x 65519 bytes)";
+  if (f == "xmp") {
+    return "xmp: NULL with a size, or a packet above 65504 bytes (one APP1 segment) without a well-formed xmpNote:HasExtendedXMP=\" note in front of "
+           "the split point, or above 2^31 bytes";
+  }
+  return f + ": NULL with a non-zero size";
+}
+
+}  // namespace
+
+// the checks of a _full_ call: host only, the engine is not touched
+int sjpeg_internal::full_checks(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const sjpeg_hip_ragged_params& P) {
   const int yuv_mode = P.yuv_mode, method = P.method;
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   if (yuv_mode < kYuvAuto || yuv_mode > kYuv400) return set_error(SJPEG_HIP_EINVAL, who + ": params->yuv_mode outside 0..4 (SjpegYUVMode)");
@@ -629,45 +644,53 @@ int full_checks(const std::string& who, int format, int nframes, const sjpeg_hip
   return sjpeg_internal::ragged_check(who, format, by_mode ? SJPEG_HIP_YUV444 : yuv_mode, nframes, frames);
 }
 
-// sjpeg_hip_encode_ragged_full_src / _full_packed_src
-int full_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-              const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
-              void* stream, const sjpeg_internal::PackedSink* sink) {
-  const sjpeg_hip_ragged_params& P = *params;
+int sjpeg_internal::encode_prologue(const RaggedCall& c, bool has_sheet, const void* sheet, bool yuv_only) {
+  // (every argument check comes before the engine is touched: the tests without a GPU rely on it)
+  const std::string& who = *c.who;
+  const RaggedOut& o = c.out;
+  if (c.e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (c.params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
+  if (o.packed && o.d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
+  if (c.frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
+  if (has_sheet && sheet == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": sheet == NULL");
+  if (o.d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + (o.packed ? ": d_packed == NULL" : ": d_out == NULL"));
+  if (o.d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
+  if (o.packed && (reinterpret_cast<uintptr_t>(o.d_out) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
+  if (o.packed && o.packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
+  if (o.strided && o.out_stride < 1) return set_error(SJPEG_HIP_EINVAL, who + ": out_stride must be at least 1");
+  if (yuv_only) { if (int rc = yuv_format_check(who, c.format)) return rc; }
+  if (c.nframes < 1 || c.nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+  return 0;
+}
+
+// A _full_ call behind its prologue: its checks, all of them before the engine is touched, then the search
+int sjpeg_internal::full_flow(const RaggedCall& c) {
+  const std::string& who = *c.who;
+  const sjpeg_hip_ragged_params& P = *c.params;
+  const RaggedOut& o = c.out;
   const int yuv_mode = P.yuv_mode, method = P.method;
-  // ---- the checks, all of them before the engine is touched
-  if (int rc = full_checks(who, format, nframes, frames, P)) return rc;
+  if (int rc = full_checks(who, c.format, c.nframes, c.frames, P)) return rc;
   const bool by_mode = yuv_mode == kYuvAuto || yuv_mode == kYuvSharp;
-  if (sink != nullptr) { if (int rc = sjpeg_internal::engine_pack_begin(e, stream)) return rc; }
-  uint64_t* const stats = sjpeg_internal::engine_full_stats(e);
+  const PackedSink packed = o.sink(c.nframes);
+  const PackedSink* const sink = o.packed ? &packed : nullptr;
+  if (sink != nullptr) { if (int rc = engine_pack_begin(c.e, o.stream)) return rc; }
+  uint64_t* const stats = engine_full_stats(c.e);
   memset(stats, 0, 6 * sizeof(uint64_t));
   // a search on the ground of sjpeg_hip_encode_ragged_search_src: that entry point's messages, and the counters stay zero
   bool any_searched = false;
-  for (int f = 0; f < nframes; ++f) any_searched = any_searched || passes_of(P, f) > 1;
+  for (int f = 0; f < c.nframes; ++f) any_searched = any_searched || passes_of(P, f) > 1;
   if (any_searched && !by_mode && method <= 6) {
-    const int rc = sjpeg_internal::ragged_search_flow(e, format, yuv_mode, nframes, frames, P.quant, P.quant_per_frame, P.min_quant,
-                                                      P.q_bias, method, P.qdelta_max_luma, P.qdelta_max_chroma, P.search,
-                                                      P.search_per_frame, q_out, value_out, d_out, d_sizes, stream, sink);
-    if (rc == 0 && modes != nullptr) for (int f = 0; f < nframes; ++f) modes[f] = yuv_mode;
+    const int rc = ragged_search_flow(c.e, c.format, yuv_mode, c.nframes, c.frames, P.quant, P.quant_per_frame, P.min_quant, P.q_bias, method,
+                                      P.qdelta_max_luma, P.qdelta_max_chroma, P.search, P.search_per_frame, o.q_out, o.value_out, o.d_out,
+                                      o.d_sizes, o.stream, sink);
+    if (rc == 0 && o.modes != nullptr) for (int f = 0; f < c.nframes; ++f) o.modes[f] = yuv_mode;
     return rc;
   }
-  return search_flow(who, e, format, nframes, frames, P, d_out, d_sizes, modes, q_out, value_out, stream, sink, stats);
-}
-
-// what is wrong with a metadata member (jpeg_host.h: MetadataFromC names it), in words
-std::string meta_fault(const char* field) {
-  const std::string f = field;
-  if (f == "exif") return "exif: NULL with a size, or its APP1 segment would pass 65535 bytes (at most 65527 bytes of EXIF)";
-  if (f == "iccp") return "iccp: NULL with a size, or a profile of 256 chunks or more (at most 255 x 65519 bytes)";
-  if (f == "xmp") {
-    return "xmp: NULL with a size, or a packet above 65504 bytes (one APP1 segment) without a well-formed xmpNote:HasExtendedXMP=\" note in front of "
-           "the split point, or above 2^31 bytes";
-  }
-  return f + ": NULL with a non-zero size";
+  return search_flow(who, c.e, c.format, c.nframes, c.frames, P, o.d_out, o.d_sizes, o.modes, o.q_out, o.value_out, o.stream, sink, stats);
 }
 
 // The call's metadata -- one entry, or one per frame -- checked and turned into segments, before any device work
-int check_metadata(const std::string& who, int nframes, const sjpeg_hip_metadata* meta, int meta_per_frame, sjpeg_internal::MetaCtx* ctx) {
+int sjpeg_internal::check_metadata(const std::string& who, int nframes, const sjpeg_hip_metadata* meta, int meta_per_frame, MetaCtx* ctx) {
   ctx->per_frame = meta_per_frame ? 1 : 0;
   ctx->entries.resize(meta_per_frame ? static_cast<size_t>(nframes) : 1);
   for (size_t k = 0; k < ctx->entries.size(); ++k) {
@@ -682,14 +705,29 @@ int check_metadata(const std::string& who, int nframes, const sjpeg_hip_metadata
   return 0;
 }
 
-// the engine carries the call's metadata while the call runs
-struct MetaScope {
-  sjpeg_hip_engine* e;
-  MetaScope(sjpeg_hip_engine* engine, sjpeg_internal::MetaCtx* ctx) : e(engine) { sjpeg_internal::engine_set_meta(e, ctx); }
-  ~MetaScope() { sjpeg_internal::engine_set_meta(e, nullptr); }
-};
-
-}  // namespace
+// The one body of sjpeg_hip_encode_ragged_full_src, _full_packed_src, _full_meta_src and _full_meta_packed_src: an
+// optional sink (c.out.packed) and an optional metadata (c.meta)
+int sjpeg_internal::full_entry(RaggedCall c) {
+  static const std::string names[2][2] = {{"sjpeg_hip_encode_ragged_full_src", "sjpeg_hip_encode_ragged_full_packed_src"},
+                                          {"sjpeg_hip_encode_ragged_full_meta_src", "sjpeg_hip_encode_ragged_full_meta_packed_src"}};
+  c.who = &names[c.meta != nullptr][c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  try {
+    MetaCtx ctx;
+    if (c.meta != nullptr) { if (int rc = check_metadata(*c.who, c.nframes, c.meta, c.meta_per_frame, &ctx)) return rc; }
+    std::vector<sjpeg_hip_ragged_frame> fr;
+    if (c.out.packed) {
+      fr.assign(c.frames, c.frames + c.nframes);
+      for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
+      c.frames = fr.data();
+    }
+    // (full_flow zeroes the engine's cursor behind its checks: they come before the engine is touched)
+    const MetaScope scope(c.e, c.meta != nullptr ? &ctx : nullptr);
+    return full_flow(c);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, *c.who + ": out of host memory");
+  }
+}
 
 // sjpeg_hip_encode_ragged_search_src (sink != NULL: packed output): one sampling, methods 0..6 -- its own checks and
 // messages, then the flow above with one mode group of the caller's format.  The engine's counters are the _full_
@@ -743,39 +781,31 @@ int sjpeg_hip_encode_ragged_search_src(sjpeg_hip_engine* e, int format, int yuv_
 int sjpeg_hip_encode_ragged_full_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
                                      const sjpeg_hip_ragged_params* params, void* d_out, uint64_t* d_sizes, int* modes,
                                      float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_full_src";
-  // (every argument check comes before `e` is touched: the tests without a GPU rely on it)
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  return full_flow(who, e, format, nframes, frames, params, d_out, d_sizes, modes, q_out, value_out, stream, nullptr);
+  return sjpeg_internal::full_entry({nullptr, e, format, nframes, frames, params, nullptr, 0,
+                                     {d_out, d_sizes, modes, q_out, value_out, stream}});
 }
 
 int sjpeg_hip_encode_ragged_full_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
                                             const sjpeg_hip_ragged_params* params, void* d_packed, size_t packed_capacity,
                                             uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
                                             void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_full_packed_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  try {
-    std::vector<sjpeg_hip_ragged_frame> fr(frames, frames + nframes);
-    for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
-    const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-    // (full_flow zeroes the engine's cursor behind its checks: they come before the engine is touched)
-    return full_flow(who, e, format, nframes, fr.data(), params, d_packed, d_sizes, modes, q_out, value_out, stream, &sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
+  return sjpeg_internal::full_entry({nullptr, e, format, nframes, frames, params, nullptr, 0,
+                                     sjpeg_internal::RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)});
+}
+
+int sjpeg_hip_encode_ragged_full_meta_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                          void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sjpeg_internal::full_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                                     {d_out, d_sizes, modes, q_out, value_out, stream}});
+}
+
+int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta,
+                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sjpeg_internal::full_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                                     sjpeg_internal::RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)});
 }
 
 int sjpeg_hip_metadata_size(const sjpeg_hip_metadata* meta, size_t* size) {
@@ -791,566 +821,6 @@ int sjpeg_hip_metadata_size(const sjpeg_hip_metadata* meta, size_t* size) {
   } catch (...) {
     return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
   }
-}
-
-int sjpeg_hip_encode_ragged_full_meta_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                                          void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  if (meta == nullptr) return sjpeg_hip_encode_ragged_full_src(e, format, nframes, frames, params, d_out, d_sizes, modes, q_out, value_out, stream);
-  static const std::string who = "sjpeg_hip_encode_ragged_full_meta_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  try {
-    sjpeg_internal::MetaCtx ctx;
-    if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc;
-    const MetaScope scope(e, &ctx);
-    return full_flow(who, e, format, nframes, frames, params, d_out, d_sizes, modes, q_out, value_out, stream, nullptr);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-int sjpeg_hip_encode_ragged_full_meta_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta,
-                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
-                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  if (meta == nullptr) {
-    return sjpeg_hip_encode_ragged_full_packed_src(e, format, nframes, frames, params, d_packed, packed_capacity, d_offsets, d_sizes,
-                                                   modes, q_out, value_out, stream);
-  }
-  static const std::string who = "sjpeg_hip_encode_ragged_full_meta_packed_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  try {
-    sjpeg_internal::MetaCtx ctx;
-    if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc;
-    std::vector<sjpeg_hip_ragged_frame> fr(frames, frames + nframes);
-    for (sjpeg_hip_ragged_frame& f : fr) f.out_offset = 0;       // (ignored: the placement kernel says where a frame goes)
-    const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-    const MetaScope scope(e, &ctx);
-    return full_flow(who, e, format, nframes, fr.data(), params, d_packed, d_sizes, modes, q_out, value_out, stream, &sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-// ---- the _full_meta_ calls on pictures reduced inside the call (reduce.hip): thumbnails and pyramid levels ----
-// factors NULL or all 1: exactly the _full_meta_ call on the caller's frames.  Otherwise every check first, host only;
-// then the reduce kernel into the engine's own memory for reduced pictures and ONE inner flow over them, read as
-// SJPEG_HIP_SRC_RGB or _GRAY -- one group, one format: frame order, packed layout, modes, q_out, value_out, the host
-// waits and the search counters are that flow's.
-static bool all_ones(const uint8_t* factors, int nframes) {
-  for (int f = 0; factors != nullptr && f < nframes; ++f) if (factors[f] != 1) return false;
-  return true;
-}
-
-extern "C++" {
-// what the flow below asks of a plan (ReducePlan, ResizePlan): the format of its pictures, the pictures as frames at
-// `base`, and the engine's half
-static int made_format(const sjpeg_internal::ReducePlan& p) { return p.reduced_format; }
-static int made_format(const sjpeg_internal::ResizePlan& p) { return p.resized_format; }
-static void made_frames(const sjpeg_internal::ReducePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
-  sjpeg_internal::reduce_plan_frames(p, frames, base, out);
-}
-static void made_frames(const sjpeg_internal::ResizePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
-  sjpeg_internal::resize_plan_frames(p, frames, base, out);
-}
-static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::ReducePlan& p, uint8_t** base, void* stream) {
-  return sjpeg_internal::engine_reduce(e, who, p, nullptr, base, stream);
-}
-static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::ResizePlan& p, uint8_t** base, void* stream) {
-  return sjpeg_internal::engine_resize(e, who, p, nullptr, base, stream);
-}
-// ... and of a YuvResizePlan, whose pictures are three planes; the words behind a refused yuv_mode
-static int made_format(const sjpeg_internal::YuvResizePlan& p) { return p.resized_format; }
-static void made_frames(const sjpeg_internal::YuvResizePlan& p, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out) {
-  sjpeg_internal::yuv_resize_plan_frames(p, frames, base, out);
-}
-static int make_pictures(sjpeg_hip_engine* e, const std::string& who, const sjpeg_internal::YuvResizePlan& p, uint8_t** base, void* stream) {
-  return sjpeg_internal::engine_yuv_resize(e, who, p, nullptr, base, stream);
-}
-template <class Plan> static const char* mode_hint(const Plan&) { return " (gray pictures are coded 4:0:0 only)"; }
-static const char* mode_hint(const sjpeg_internal::YuvResizePlan&) { return ""; }
-
-// the rest of a call whose pictures are planned (reduced or resized): the remaining checks, then the device work
-template <class Plan>
-static int planned_flow(const std::string& who, sjpeg_hip_engine* e, const SourceLayout* L, const Plan& plan, int format, int nframes,
-                        const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_ragged_params* params, const sjpeg_hip_metadata* meta,
-                        int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
-                        const sjpeg_internal::PackedSink* sink) {
-  const int y = params->yuv_mode;
-  if (L->implied != 0 && y != L->implied) {
-    return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + mode_hint(plan));
-  }
-  if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-  // (the inner flow's own checks on the made pictures, standing at a placeholder address until there is memory)
-  std::vector<sjpeg_hip_ragged_frame> made(static_cast<size_t>(nframes));
-  made_frames(plan, frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), made.data());
-  if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : made) f.out_offset = 0;   // (ignored: the placement kernel says where a frame goes)
-  if (int rc = full_checks(who, made_format(plan), nframes, made.data(), *params)) return rc;
-  sjpeg_internal::MetaCtx ctx;
-  if (meta != nullptr) { if (int rc = check_metadata(who, nframes, meta, meta_per_frame, &ctx)) return rc; }
-  // ---- device work
-  uint8_t* base = nullptr;
-  if (int rc = make_pictures(e, who, plan, &base, stream)) return rc;
-  made_frames(plan, frames, base, made.data());
-  if (sink != nullptr) for (sjpeg_hip_ragged_frame& f : made) f.out_offset = 0;
-  const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
-  return full_flow(who, e, made_format(plan), nframes, made.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
-}
-}  // extern "C++"
-
-static int reduced_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                        const sjpeg_hip_ragged_params* params, const uint8_t* factors, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                        void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
-                        const sjpeg_internal::PackedSink* sink) {
-  try {
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    sjpeg_internal::ReducePlan plan;
-    if (int rc = sjpeg_internal::reduce_plan(who, format, nframes, frames, factors, &plan)) return rc;
-    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
-                        stream, sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-int sjpeg_hip_encode_ragged_reduced_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                        const sjpeg_hip_ragged_params* params, const uint8_t* factors,
-                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                                        int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_reduced_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  for (int f = 0; factors != nullptr && f < nframes; ++f) {
-    if (factors[f] < 1 || factors[f] > SJPEG_HIP_REDUCE_MAX) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": factor " + std::to_string(factors[f]) + " is not one of 1..8");
-    }
-  }
-  if (all_ones(factors, nframes)) {
-    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                                                 value_out, stream);
-  }
-  return reduced_flow(who, e, format, nframes, frames, params, factors, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
-                      stream, nullptr);
-}
-
-int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                               const sjpeg_hip_ragged_params* params, const uint8_t* factors,
-                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
-                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
-                                               float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_reduced_packed_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  for (int f = 0; factors != nullptr && f < nframes; ++f) {
-    if (factors[f] < 1 || factors[f] > SJPEG_HIP_REDUCE_MAX) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": factor " + std::to_string(factors[f]) + " is not one of 1..8");
-    }
-  }
-  if (all_ones(factors, nframes)) {
-    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
-                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
-  }
-  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-  return reduced_flow(who, e, format, nframes, frames, params, factors, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
-                      stream, &sink);
-}
-
-// ---- ... and on pictures resized inside the call (resize.hip): thumbnails that fit a box ----
-// sizes NULL or every size its frame's own: exactly the _full_meta_ call on the caller's frames.  Otherwise as the
-// reduced calls: every check first, host only; the resize kernel into the engine's memory; ONE inner flow.
-static bool all_own_size(const int32_t (*sizes)[2], int nframes, const sjpeg_hip_ragged_frame* frames) {
-  for (int f = 0; sizes != nullptr && f < nframes; ++f) {
-    if (sizes[f][0] != frames[f].width || sizes[f][1] != frames[f].height) return false;
-  }
-  return true;
-}
-
-static int resized_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
-                        const sjpeg_hip_metadata* meta, int meta_per_frame,
-                        void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream,
-                        const sjpeg_internal::PackedSink* sink, const sjpeg_hip_flatten* flatten = nullptr) {
-  try {
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    sjpeg_internal::ResizePlan plan;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan, flatten)) return rc;
-    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
-                        stream, sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-int sjpeg_hip_encode_ragged_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
-                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                                        int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_resized_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (all_own_size(sizes, nframes, frames)) {
-    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                                                 value_out, stream);
-  }
-  return resized_flow(who, e, format, nframes, frames, params, sizes, nullptr, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
-                      stream, nullptr);
-}
-
-int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                               const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
-                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
-                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
-                                               float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_resized_packed_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (all_own_size(sizes, nframes, frames)) {
-    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
-                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
-  }
-  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-  return resized_flow(who, e, format, nframes, frames, params, sizes, nullptr, meta, meta_per_frame, d_packed, d_sizes, modes, q_out, value_out,
-                      stream, &sink);
-}
-
-// ---- ... and turned upright by their EXIF orientations in the same launch (orient_math.h) ----
-// orientations NULL or all 1: exactly the resized call on the same arguments (so any format at its own sizes still
-// passes through to the _full_meta_ call).  Otherwise the resized flow with the orientations in its plan: the kernel
-// stores every tile where it lands in the upright picture, and the ONE inner flow codes the upright pictures.
-// (-1: every orientation is 1..8; else the first frame whose is not)
-static int bad_orientation(const uint8_t* orientations, int nframes) {
-  for (int f = 0; orientations != nullptr && f < nframes; ++f) if (orientations[f] < 1 || orientations[f] > 8) return f;
-  return -1;
-}
-static int orientation_error(const std::string& who, const uint8_t* orientations, int f) {
-  return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": orientation " + std::to_string(orientations[f]) +
-                                         " is not one of 1..8 (EXIF tag 0x0112)");
-}
-
-// One body for the oriented entry and the flattened one (flatten != NULL: every frame goes through the kernel -- no
-// pass-through, the inner call never sees the alpha format).
-static int oriented_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
-                          const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                          int* modes, float* q_out, float* value_out, void* stream) {
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (flatten == nullptr && all_ones(orientations, nframes)) {
-    return sjpeg_hip_encode_ragged_resized_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                                               value_out, stream);
-  }
-  return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                      value_out, stream, nullptr, flatten);
-}
-
-int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
-                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                                         int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_oriented_src";
-  return oriented_entry(who, e, format, nframes, frames, params, nullptr, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes,
-                        q_out, value_out, stream);
-}
-
-// ---- ... and flattened over a background in the same launch (flatten_math.h): RGBA pictures ----
-int sjpeg_hip_encode_ragged_flattened_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
-                                          const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
-                                          int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
-                                          void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_flattened_src";
-  if (flatten == nullptr) {
-    return sjpeg_hip_encode_ragged_oriented_src(e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes,
-                                                modes, q_out, value_out, stream);
-  }
-  return oriented_entry(who, e, format, nframes, frames, params, flatten, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes,
-                        q_out, value_out, stream);
-}
-
-static int oriented_packed_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
-                                 const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
-                                 size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out,
-                                 float* value_out, void* stream) {
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (flatten == nullptr && all_ones(orientations, nframes)) {
-    return sjpeg_hip_encode_ragged_resized_packed_src(e, format, nframes, frames, params, sizes, meta, meta_per_frame, d_packed,
-                                                      packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
-  }
-  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-  return resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
-                      value_out, stream, &sink, flatten);
-}
-
-int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
-                                                const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                                                void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
-                                                int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_oriented_packed_src";
-  return oriented_packed_entry(who, e, format, nframes, frames, params, nullptr, sizes, orientations, meta, meta_per_frame, d_packed,
-                               packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
-}
-
-int sjpeg_hip_encode_ragged_flattened_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
-                                                 const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
-                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
-                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_flattened_packed_src";
-  if (flatten == nullptr) {
-    return sjpeg_hip_encode_ragged_oriented_packed_src(e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed,
-                                                       packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
-  }
-  return oriented_packed_entry(who, e, format, nframes, frames, params, flatten, sizes, orientations, meta, meta_per_frame, d_packed,
-                               packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
-}
-
-// ---- ... and on decoded video: NV12, NV21 and planar YUV resized and turned plane by plane (yuv_resize_plan.cc) ----
-// Every size the frame's own and every orientation 1 (or both NULL): exactly the _full_meta_ call on the caller's
-// frames.  Otherwise the flow of the oriented calls with a plan of planes: the kernel makes Y, U and V of every frame
-// in the engine's memory, and the ONE inner flow codes them as planar 4:2:0 or 4:4:4.
-static int yuv_resized_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
-                            const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out,
-                            float* value_out, void* stream, const sjpeg_internal::PackedSink* sink) {
-  try {
-    const SourceLayout* const L = source_layout(format);
-    sjpeg_internal::YuvResizePlan plan;
-    if (int rc = sjpeg_internal::yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
-    return planned_flow(who, e, L, plan, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out, value_out,
-                        stream, sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-int sjpeg_hip_encode_ragged_yuv_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
-                                            const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
-                                            int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_yuv_resized_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (all_ones(orientations, nframes) && all_own_size(sizes, nframes, frames)) {
-    return sjpeg_hip_encode_ragged_full_meta_src(e, format, nframes, frames, params, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                                                 value_out, stream);
-  }
-  return yuv_resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_out, d_sizes, modes, q_out,
-                          value_out, stream, nullptr);
-}
-
-int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                   const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
-                                                   const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                                                   void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
-                                                   int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_yuv_resized_packed_src";
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  if (const int f = bad_orientation(orientations, nframes); f >= 0) return orientation_error(who, orientations, f);
-  if (all_ones(orientations, nframes) && all_own_size(sizes, nframes, frames)) {
-    return sjpeg_hip_encode_ragged_full_meta_packed_src(e, format, nframes, frames, params, meta, meta_per_frame, d_packed, packed_capacity,
-                                                        d_offsets, d_sizes, modes, q_out, value_out, stream);
-  }
-  const sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};
-  return yuv_resized_flow(who, e, format, nframes, frames, params, sizes, orientations, meta, meta_per_frame, d_packed, d_sizes, modes, q_out,
-                          value_out, stream, &sink);
-}
-
-// ---- ... and on contact sheets: the batch resized, turned and placed into grid pictures (sheet_plan.cc) ----
-// Every check first, host only; the background fill and the placed resize into the engine's memory for reduced and
-// resized pictures; ONE inner flow over the SHEETS, read as the plan's output format.  params, meta, modes, q_out and
-// value_out count sheets.  sink == NULL: sheet s at d_out + s * out_stride, capacity out_stride.
-static int sheet_flow(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
-                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
-                      uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream, sjpeg_internal::PackedSink* sink,
-                      const sjpeg_hip_flatten* flatten) {
-  try {
-    sjpeg_internal::SheetPlan plan;
-    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan, flatten)) return rc;
-    const SourceLayout* const L = source_layout(format);
-    if (L->implied != 0 && params->yuv_mode != L->implied) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + (plan.yuv ? "" : " (gray pictures are coded 4:0:0 only)"));
-    }
-    // (the source frames' output ranges are not read: the sheets' are the call's)
-    std::vector<sjpeg_hip_ragged_frame> src(frames, frames + nframes);
-    for (sjpeg_hip_ragged_frame& f : src) { f.out_offset = 0; f.out_capacity = 0; }
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, src.data())) return rc;
-    const int ns = plan.nsheets;
-    if (sink == nullptr && out_stride > UINT64_MAX / static_cast<uint64_t>(ns)) {
-      return set_error(SJPEG_HIP_EINVAL, who + ": out_stride * nsheets overflows");
-    }
-    sjpeg_internal::MetaCtx ctx;
-    if (meta != nullptr) { if (int rc = check_metadata(who, ns, meta, meta_per_frame, &ctx)) return rc; }
-    auto made_sheets = [&](uint8_t* base, std::vector<sjpeg_hip_ragged_frame>* made) {
-      made->resize(static_cast<size_t>(ns));
-      sjpeg_internal::sheet_plan_frames(plan, base, made->data());
-      for (int k = 0; k < ns; ++k) {
-        (*made)[k].out_offset = sink != nullptr ? 0 : static_cast<uint64_t>(k) * out_stride;
-        // (packed: a sheet may take what is always enough for it)
-        const size_t header = 2048 + (meta != nullptr && !ctx.entries.empty() ? ctx.of(k).block.size() : 0);
-        (*made)[k].out_capacity = sink != nullptr ? sjpeg_hip_frame_bound(plan.width, plan.height, SJPEG_HIP_YUV444, header) : out_stride;
-      }
-    };
-    // (the inner flow's own checks on the sheets, standing at a placeholder address until there is memory)
-    std::vector<sjpeg_hip_ragged_frame> made;
-    made_sheets(reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), &made);
-    if (int rc = full_checks(who, plan.out_format, ns, made.data(), *params)) return rc;
-    if (sink != nullptr) sink->nframes = ns;
-    // ---- device work
-    uint8_t* base = nullptr;
-    if (int rc = sjpeg_internal::engine_sheet(e, who, plan, nullptr, &base, stream)) return rc;
-    made_sheets(base, &made);
-    const MetaScope scope(e, meta != nullptr ? &ctx : nullptr);
-    return full_flow(who, e, plan.out_format, ns, made.data(), params, d_out, d_sizes, modes, q_out, value_out, stream, sink);
-  } catch (...) {
-    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
-  }
-}
-
-// (one body for the sheet entries and the flattened ones, as for the oriented entries)
-static int sheet_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                       const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten,
-                       const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                       void* d_out, size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (sheet == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": sheet == NULL");
-  if (d_out == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_out == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if (out_stride < 1) return set_error(SJPEG_HIP_EINVAL, who + ": out_stride must be at least 1");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_out, out_stride, d_sizes,
-                    modes, q_out, value_out, stream, nullptr, flatten);
-}
-
-int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
-                                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
-                                      size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_src";
-  return sheet_entry(who, e, format, nframes, frames, params, sheet, nullptr, sizes, orientations, meta, meta_per_frame, d_out, out_stride,
-                     d_sizes, modes, q_out, value_out, stream);
-}
-
-int sjpeg_hip_encode_ragged_sheet_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                           const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
-                                           const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
-                                           const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
-                                           uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_flat_src";
-  return sheet_entry(flatten != nullptr ? who : "sjpeg_hip_encode_ragged_sheet_src", e, format, nframes, frames, params, sheet, flatten, sizes,
-                     orientations, meta, meta_per_frame, d_out, out_stride, d_sizes, modes, q_out, value_out, stream);
-}
-
-static int sheet_packed_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten,
-                              const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                              void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out,
-                              float* value_out, void* stream) {
-  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (params == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": params == NULL");
-  if (d_offsets == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_offsets == NULL");
-  if (frames == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": frames == NULL");
-  if (sheet == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": sheet == NULL");
-  if (d_packed == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed == NULL");
-  if (d_sizes == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": d_sizes == NULL");
-  if ((reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": d_packed must be a multiple of 16");
-  if (packed_capacity >= SJPEG_HIP_PACKED_OVERFLOW) return set_error(SJPEG_HIP_EINVAL, who + ": packed_capacity must be below 2^63");
-  if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-  sjpeg_internal::PackedSink sink = {d_packed, packed_capacity, d_offsets, nframes, nullptr};   // (nframes: the sheets', set by the flow)
-  return sheet_flow(who, e, format, nframes, frames, params, sheet, sizes, orientations, meta, meta_per_frame, d_packed, 0, d_sizes, modes,
-                    q_out, value_out, stream, &sink, flatten);
-}
-
-int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
-                                             const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
-                                             int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
-                                             uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_packed_src";
-  return sheet_packed_entry(who, e, format, nframes, frames, params, sheet, nullptr, sizes, orientations, meta, meta_per_frame, d_packed,
-                            packed_capacity, d_offsets, d_sizes, modes, q_out, value_out, stream);
-}
-
-int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                                  const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
-                                                  const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
-                                                  const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
-                                                  void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
-                                                  int* modes, float* q_out, float* value_out, void* stream) {
-  static const std::string who = "sjpeg_hip_encode_ragged_sheet_flat_packed_src";
-  return sheet_packed_entry(flatten != nullptr ? who : "sjpeg_hip_encode_ragged_sheet_packed_src", e, format, nframes, frames, params, sheet,
-                            flatten, sizes, orientations, meta, meta_per_frame, d_packed, packed_capacity, d_offsets, d_sizes, modes, q_out,
-                            value_out, stream);
 }
 
 int sjpeg_hip_engine_search_stats(sjpeg_hip_engine* e, uint64_t stats[6]) {

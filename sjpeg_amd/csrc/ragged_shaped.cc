@@ -1,0 +1,500 @@
+// ragged_shaped.cc -- the ragged entries on pictures that are SHAPED inside the call: reduced by a factor (reduce.hip),
+// resized to a size, turned upright by an EXIF orientation and flattened over a background (resize.hip), the same for
+// the YUV-plane formats (yuv_resize_plan.cc), and placed into contact sheets (sheet_plan.cc).  Per family a shape entry
+// -- the made pictures into the caller's buffer -- and an encode entry with its packed twin: the pictures into the
+// engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
+//
+// Every entry fills a call description (ragged_aux.h: RaggedCall, RaggedOut) and names a plan KIND below; the bodies
+// -- shape_body, planned_flow, sheet_flow -- are written once against those.  A route that needs no kernel (factors all
+// 1, sizes the frames' own, orientations all 1, no flatten) renames the call and hands the same description to the entry
+// of fewer arguments: the messages then carry that entry's name.  Every check comes before the engine is touched; their
+// order and texts are pinned by tests/golden/c_messages.json.  DESIGN.md, "The C layer's call description".
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "ragged_aux.h"
+#include "sjpeg_hip.h"
+
+namespace {
+
+using namespace sjpeg_internal;
+
+// what an entry asks for beyond its frames (NULL: not that), in this order
+struct Shape {
+  const uint8_t* factors = nullptr;
+  const int32_t (*sizes)[2] = nullptr;
+  const uint8_t* orientations = nullptr;
+  const sjpeg_hip_flatten* flatten = nullptr;
+  const sjpeg_hip_sheet* sheet = nullptr;
+};
+
+// ---- the plan kinds: the plan function, the format of what it makes, the made pictures as frames at `base` and how
+// many they are, the engine's half, and the hint behind a refused yuv_mode
+using Frame = sjpeg_hip_ragged_frame;
+struct PerFrameKind {                            // (one made picture per frame; the format is any the plan takes)
+  static constexpr bool yuv_only = false;
+  template <class P> static int count(const P&, int nframes) { return nframes; }
+  template <class P> static const char* mode_hint(const P&) { return " (gray pictures are coded 4:0:0 only)"; }
+};
+struct ReduceKind : PerFrameKind {
+  using Plan = ReducePlan;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return reduce_plan(who, format, n, fr, s.factors, p);
+  }
+  static int format(const Plan& p) { return p.reduced_format; }
+  static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { reduce_plan_frames(p, fr, base, out); }
+  static constexpr auto run = engine_reduce;
+};
+struct ResizeKind : PerFrameKind {               // (with optional orientations and flatten)
+  using Plan = ResizePlan;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return resize_plan(who, format, n, fr, s.sizes, s.orientations, p, s.flatten);
+  }
+  static int format(const Plan& p) { return p.resized_format; }
+  static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { resize_plan_frames(p, fr, base, out); }
+  static constexpr auto run = engine_resize;
+};
+struct YuvResizeKind : PerFrameKind {
+  using Plan = YuvResizePlan;
+  static constexpr bool yuv_only = true;         // (the format is checked by name, in front of nframes)
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return yuv_resize_plan(who, format, n, fr, s.sizes, s.orientations, p);
+  }
+  static int format(const Plan& p) { return p.resized_format; }
+  static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { yuv_resize_plan_frames(p, fr, base, out); }
+  static constexpr auto run = engine_yuv_resize;
+  static const char* mode_hint(const Plan&) { return ""; }
+};
+struct SheetKind : PerFrameKind {                // (its frames count sheets: out_offset and out_capacity 0)
+  using Plan = SheetPlan;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return sheet_plan(who, format, n, fr, s.sheet, s.sizes, s.orientations, p, s.flatten);
+  }
+  static int format(const Plan& p) { return p.out_format; }
+  static int count(const Plan& p, int) { return p.nsheets; }
+  static const char* mode_hint(const Plan& p) { return p.yuv ? "" : PerFrameKind::mode_hint(p); }
+  static void frames(const Plan& p, const Frame*, uint8_t* base, Frame* out) { sheet_plan_frames(p, base, out); }
+  static constexpr auto run = engine_sheet;
+};
+
+int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
+
+// ---- the shape entries: the made pictures into the caller's buffer
+// the words of an entry's messages: its mandatory pointers, its buffer, its size argument, what it makes and the _bytes
+// function that says how much that takes
+struct ShapeWords { const char *pointers, *buffer, *bytes, *made, *bytes_fn; };
+constexpr ShapeWords kOrientWords = {"frames, d_out, out_frames or out_format", "d_out", "bytes", "oriented pictures",
+                                     "sjpeg_hip_orient_ragged_bytes"};
+constexpr ShapeWords kSheetWords = {"frames, sheet, d_out, sheet_frames, nsheets or out_format", "d_out", "bytes", "sheets",
+                                    "sjpeg_hip_sheet_ragged_bytes"};
+
+// `missing`: one of the entry's mandatory pointers is NULL (the entry knows which it has); count: where the number of
+// made pictures goes (NULL: it is nframes)
+template <class K>
+int shape_body(const std::string& who, const ShapeWords& w, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+               const Shape& s, bool missing, void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames, int* count, int* out_format,
+               void* stream) {
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (missing || frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + w.pointers + " == NULL");
+  }
+  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return set_error(SJPEG_HIP_EINVAL, who + ": " + w.buffer + " must be a multiple of 16");
+  try {
+    typename K::Plan plan;
+    if (K::yuv_only) { if (int rc = yuv_format_check(who, format)) return rc; }
+    const SourceLayout* const L = source_layout(format);
+    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
+    if (int rc = ragged_check(who, format, source_mode(L), nframes, frames)) return rc;
+    if (int rc = K::plan(who, format, nframes, frames, s, &plan)) return rc;
+    if (bytes < plan.bytes) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": " + w.bytes + " " + std::to_string(bytes) + " is below the " + std::to_string(plan.bytes) +
+                                             " bytes the " + w.made + " take (" + w.bytes_fn + ")");
+    }
+    if (int rc = K::run(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
+    K::frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
+    if (count != nullptr) *count = K::count(plan, nframes);
+    *out_format = K::format(plan);
+    return 0;
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, "out of host memory");
+  }
+}
+
+// ---- the encode entries.  Their names by family: [0] the entry, [1] its packed twin
+#define SJPEG_ENTRY_NAMES(stem) {"sjpeg_hip_encode_ragged_" stem "_src", "sjpeg_hip_encode_ragged_" stem "_packed_src"}
+const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPEG_ENTRY_NAMES("resized"),
+                  kOriented[2] = SJPEG_ENTRY_NAMES("oriented"), kFlattened[2] = SJPEG_ENTRY_NAMES("flattened"),
+                  kYuvResized[2] = SJPEG_ENTRY_NAMES("yuv_resized"), kSheet[2] = SJPEG_ENTRY_NAMES("sheet"),
+                  kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat");
+#undef SJPEG_ENTRY_NAMES
+
+// a packed call's frames go where the placement kernel says: their out_offset is not read
+void unplace(const RaggedOut& o, std::vector<sjpeg_hip_ragged_frame>* made) {
+  if (o.packed) for (sjpeg_hip_ragged_frame& f : *made) f.out_offset = 0;
+}
+
+// The rest of a call whose pictures are planned (prologue done): the remaining checks -- the plan's, the yuv_mode, the
+// caller's frames, the inner flow's own on the made pictures (standing at a placeholder address until there is
+// memory), the metadata --, then the kernel into the engine's memory for made pictures and ONE inner flow over them,
+// read as the plan's format: frame order, packed layout, modes, q_out, value_out, the host waits and the search counters
+// are that flow's.
+template <class K>
+int planned_flow(const RaggedCall& c, const Shape& s) {
+  const std::string& who = *c.who;
+  try {
+    const SourceLayout* const L = source_layout(c.format);
+    if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+    typename K::Plan plan;
+    if (int rc = K::plan(who, c.format, c.nframes, c.frames, s, &plan)) return rc;
+    if (L->implied != 0 && c.params->yuv_mode != L->implied) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + K::mode_hint(plan));
+    }
+    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, c.frames)) return rc;
+    std::vector<sjpeg_hip_ragged_frame> made(static_cast<size_t>(c.nframes));
+    K::frames(plan, c.frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), made.data());
+    unplace(c.out, &made);
+    if (int rc = full_checks(who, K::format(plan), c.nframes, made.data(), *c.params)) return rc;
+    MetaCtx ctx;
+    if (c.meta != nullptr) { if (int rc = check_metadata(who, c.nframes, c.meta, c.meta_per_frame, &ctx)) return rc; }
+    // ---- device work
+    uint8_t* base = nullptr;
+    if (int rc = K::run(c.e, who, plan, nullptr, &base, c.out.stream)) return rc;
+    K::frames(plan, c.frames, base, made.data());
+    unplace(c.out, &made);
+    RaggedCall inner = c;
+    inner.format = K::format(plan); inner.frames = made.data();
+    const MetaScope scope(c.e, c.meta != nullptr ? &ctx : nullptr);
+    return full_flow(inner);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+// The contact sheets' flow differs: params, meta, modes, q_out and value_out count SHEETS, whose output ranges the flow
+// makes itself -- sheet s at d_out + s * out_stride with capacity out_stride, or packed with what is always enough.
+int sheet_flow(const RaggedCall& c, const Shape& s) {
+  const std::string& who = *c.who;
+  const RaggedOut& o = c.out;
+  try {
+    SheetPlan plan;
+    if (int rc = SheetKind::plan(who, c.format, c.nframes, c.frames, s, &plan)) return rc;
+    const SourceLayout* const L = source_layout(c.format);
+    if (L->implied != 0 && c.params->yuv_mode != L->implied) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + SheetKind::mode_hint(plan));
+    }
+    // (the source frames' output ranges are not read: the sheets' are the call's)
+    std::vector<sjpeg_hip_ragged_frame> src(c.frames, c.frames + c.nframes);
+    for (sjpeg_hip_ragged_frame& f : src) { f.out_offset = 0; f.out_capacity = 0; }
+    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, src.data())) return rc;
+    const int ns = plan.nsheets;
+    if (!o.packed && o.out_stride > UINT64_MAX / static_cast<uint64_t>(ns)) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": out_stride * nsheets overflows");
+    }
+    MetaCtx ctx;
+    if (c.meta != nullptr) { if (int rc = check_metadata(who, ns, c.meta, c.meta_per_frame, &ctx)) return rc; }
+    std::vector<sjpeg_hip_ragged_frame> made(static_cast<size_t>(ns));
+    auto made_sheets = [&](uint8_t* base) {
+      sheet_plan_frames(plan, base, made.data());
+      for (int k = 0; k < ns; ++k) {
+        made[k].out_offset = o.packed ? 0 : static_cast<uint64_t>(k) * o.out_stride;
+        // (packed: a sheet may take what is always enough for it)
+        const size_t header = 2048 + (c.meta != nullptr && !ctx.entries.empty() ? ctx.of(k).block.size() : 0);
+        made[k].out_capacity = o.packed ? sjpeg_hip_frame_bound(plan.width, plan.height, SJPEG_HIP_YUV444, header) : o.out_stride;
+      }
+    };
+    // (the inner flow's own checks on the sheets, standing at a placeholder address until there is memory)
+    made_sheets(reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)));
+    if (int rc = full_checks(who, plan.out_format, ns, made.data(), *c.params)) return rc;
+    // ---- device work
+    uint8_t* base = nullptr;
+    if (int rc = engine_sheet(c.e, who, plan, nullptr, &base, o.stream)) return rc;
+    made_sheets(base);
+    RaggedCall inner = c;
+    inner.format = plan.out_format; inner.nframes = ns; inner.frames = made.data();
+    const MetaScope scope(c.e, c.meta != nullptr ? &ctx : nullptr);
+    return full_flow(inner);
+  } catch (...) {
+    return set_error(SJPEG_HIP_ENOMEM, who + ": out of host memory");
+  }
+}
+
+bool all_ones(const uint8_t* v, int nframes) {
+  for (int f = 0; v != nullptr && f < nframes; ++f) if (v[f] != 1) return false;
+  return true;
+}
+bool all_own_size(const int32_t (*sizes)[2], int nframes, const sjpeg_hip_ragged_frame* frames) {
+  for (int f = 0; sizes != nullptr && f < nframes; ++f) {
+    if (sizes[f][0] != frames[f].width || sizes[f][1] != frames[f].height) return false;
+  }
+  return true;
+}
+// 0 where every value is lo..hi (NULL: none to check), else the message names the first frame whose is not
+int per_frame_range(const std::string& who, const uint8_t* v, int nframes, const char* what, int hi, const char* tail) {
+  for (int f = 0; v != nullptr && f < nframes; ++f) {
+    if (v[f] < 1 || v[f] > hi) {
+      return set_error(SJPEG_HIP_EINVAL, who + ": frame " + std::to_string(f) + ": " + what + " " + std::to_string(v[f]) + " is not one of 1.." +
+                                             std::to_string(hi) + tail);
+    }
+  }
+  return 0;
+}
+int orientations_check(const std::string& who, const uint8_t* orientations, int nframes) {
+  return per_frame_range(who, orientations, nframes, "orientation", 8, " (EXIF tag 0x0112)");
+}
+
+// The route rules.  factors NULL or all 1: exactly the _full_meta_ call on the caller's frames.
+int reduced_entry(const RaggedCall& c, const uint8_t* factors) {
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = per_frame_range(*c.who, factors, c.nframes, "factor", SJPEG_HIP_REDUCE_MAX, "")) return rc;
+  if (all_ones(factors, c.nframes)) return full_entry(c);
+  return planned_flow<ReduceKind>(c, Shape{factors});
+}
+// sizes NULL or every size its frame's own: the _full_meta_ call again
+int resized_entry(const RaggedCall& c, const int32_t (*sizes)[2]) {
+  if (int rc = encode_prologue(c)) return rc;
+  if (all_own_size(sizes, c.nframes, c.frames)) return full_entry(c);
+  return planned_flow<ResizeKind>(c, Shape{nullptr, sizes});
+}
+// orientations NULL or all 1 and no flatten: exactly the resized call on the same arguments (so any format at its own
+// sizes still passes through to the _full_meta_ call).  With a flatten every frame goes through the kernel: the inner
+// call never sees the alpha format.
+int oriented_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations) {
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  if (flatten == nullptr && all_ones(orientations, c.nframes)) {
+    c.who = &kResized[c.out.packed];
+    return resized_entry(c, sizes);
+  }
+  return planned_flow<ResizeKind>(c, Shape{nullptr, sizes, orientations, flatten});
+}
+// flatten NULL: exactly the oriented call
+int flattened_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations) {
+  c.who = flatten != nullptr ? &kFlattened[c.out.packed] : &kOriented[c.out.packed];
+  return oriented_entry(c, flatten, sizes, orientations);
+}
+// every size the frame's own and every orientation 1 (or both NULL): the _full_meta_ call on the caller's planes
+int yuv_resized_entry(const RaggedCall& c, const int32_t (*sizes)[2], const uint8_t* orientations) {
+  if (int rc = encode_prologue(c, false, nullptr, true)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  if (all_ones(orientations, c.nframes) && all_own_size(sizes, c.nframes, c.frames)) return full_entry(c);
+  return planned_flow<YuvResizeKind>(c, Shape{nullptr, sizes, orientations});
+}
+// no pass-through; flatten NULL: the sheet entry under its own name
+int sheet_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                const uint8_t* orientations) {
+  c.who = flatten != nullptr ? &kSheetFlat[c.out.packed] : &kSheet[c.out.packed];
+  if (int rc = encode_prologue(c, true, sheet)) return rc;
+  return sheet_flow(c, Shape{nullptr, sizes, orientations, flatten, sheet});
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- pictures reduced by their factors: thumbnails and pyramid levels
+int sjpeg_hip_reduce_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const uint8_t* factors, void* d_reduced, size_t reduced_bytes,
+                                sjpeg_hip_ragged_frame* reduced_frames, int* reduced_format, void* stream) {
+  static const std::string who = "sjpeg_hip_reduce_ragged_src";
+  static constexpr ShapeWords w = {"frames, factors, d_reduced, reduced_frames or reduced_format", "d_reduced", "reduced_bytes",
+                                   "reduced pictures", "sjpeg_hip_reduce_ragged_bytes"};
+  return shape_body<ReduceKind>(who, w, e, format, nframes, frames, Shape{factors}, factors == nullptr, d_reduced, reduced_bytes,
+                                reduced_frames, nullptr, reduced_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_reduced_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                        const sjpeg_hip_ragged_params* params, const uint8_t* factors,
+                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                        int* modes, float* q_out, float* value_out, void* stream) {
+  return reduced_entry({&kReduced[0], e, format, nframes, frames, params, meta, meta_per_frame,
+                        {d_out, d_sizes, modes, q_out, value_out, stream}}, factors);
+}
+
+int sjpeg_hip_encode_ragged_reduced_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                               const sjpeg_hip_ragged_params* params, const uint8_t* factors,
+                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                               float* q_out, float* value_out, void* stream) {
+  return reduced_entry({&kReduced[1], e, format, nframes, frames, params, meta, meta_per_frame,
+                        RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, factors);
+}
+
+// ---- ... resized to their sizes: thumbnails that fit a box
+int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const int32_t (*sizes)[2], void* d_resized, size_t resized_bytes,
+                                sjpeg_hip_ragged_frame* resized_frames, int* resized_format, void* stream) {
+  static const std::string who = "sjpeg_hip_resize_ragged_src";
+  static constexpr ShapeWords w = {"frames, sizes, d_resized, resized_frames or resized_format", "d_resized", "resized_bytes",
+                                   "resized pictures", "sjpeg_hip_resize_ragged_bytes"};
+  return shape_body<ResizeKind>(who, w, e, format, nframes, frames, Shape{nullptr, sizes}, sizes == nullptr, d_resized, resized_bytes,
+                                resized_frames, nullptr, resized_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                        const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                        int* modes, float* q_out, float* value_out, void* stream) {
+  return resized_entry({&kResized[0], e, format, nframes, frames, params, meta, meta_per_frame,
+                        {d_out, d_sizes, modes, q_out, value_out, stream}}, sizes);
+}
+
+int sjpeg_hip_encode_ragged_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                               const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                               const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                               float* q_out, float* value_out, void* stream) {
+  return resized_entry({&kResized[1], e, format, nframes, frames, params, meta, meta_per_frame,
+                        RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes);
+}
+
+// ---- ... and turned upright by their EXIF orientations in the same ONE launch (orient_math.h): the kernel stores every
+// tile where it lands in the upright picture
+int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
+                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_orient_ragged_src";
+  return shape_body<ResizeKind>(who, kOrientWords, e, format, nframes, frames, Shape{nullptr, sizes, orientations}, false, d_out,
+                                out_bytes, out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_oriented_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                         const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                         int* modes, float* q_out, float* value_out, void* stream) {
+  return oriented_entry({&kOriented[0], e, format, nframes, frames, params, meta, meta_per_frame,
+                         {d_out, d_sizes, modes, q_out, value_out, stream}}, nullptr, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_oriented_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                int* modes, float* q_out, float* value_out, void* stream) {
+  return oriented_entry({&kOriented[1], e, format, nframes, frames, params, meta, meta_per_frame,
+                         RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, nullptr, sizes,
+                        orientations);
+}
+
+// ---- ... and flattened over a background as they are staged (flatten_math.h), still ONE launch: RGBA pictures.  The
+// shape entry wants its flatten (`flatten` goes into the plan, whose checks of it come with its others).
+int sjpeg_hip_flatten_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                 const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                                 size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_flatten_ragged_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (flatten == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
+  return shape_body<ResizeKind>(who, kOrientWords, e, format, nframes, frames, Shape{nullptr, sizes, orientations, flatten}, false, d_out,
+                                out_bytes, out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_flattened_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                          const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                          int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                          void* stream) {
+  return flattened_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                          {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_flattened_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                 const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                                 int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return flattened_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                          RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten, sizes,
+                         orientations);
+}
+
+// ---- ... and decoded video: NV12, NV21 and planar YUV resized and turned plane by plane, every plane a picture of its
+// own, still ONE launch; the inner flow codes the planes as planar 4:2:0 or 4:4:4
+int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                    const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
+                                    sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_resize_ragged_yuv_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "resized planes", "sjpeg_hip_resize_ragged_yuv_bytes"};
+  return shape_body<YuvResizeKind>(who, w, e, format, nframes, frames, Shape{nullptr, sizes, orientations}, false, d_out, out_bytes,
+                                   out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_yuv_resized_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                            const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes,
+                                            int* modes, float* q_out, float* value_out, void* stream) {
+  return yuv_resized_entry({&kYuvResized[0], e, format, nframes, frames, params, meta, meta_per_frame,
+                            {d_out, d_sizes, modes, q_out, value_out, stream}}, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_yuv_resized_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                   const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                   const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                   int* modes, float* q_out, float* value_out, void* stream) {
+  return yuv_resized_entry({&kYuvResized[1], e, format, nframes, frames, params, meta, meta_per_frame,
+                            RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes,
+                           orientations);
+}
+
+// ---- ... and contact sheets: the batch resized, turned and placed into grid pictures; one set of entries for both
+// families of formats
+int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                               const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
+                               size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_src";
+  return shape_body<SheetKind>(who, kSheetWords, e, format, nframes, frames, Shape{nullptr, sizes, orientations, nullptr, sheet},
+                               sheet == nullptr || nsheets == nullptr, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+}
+
+int sjpeg_hip_sheet_ragged_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                    const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                    const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
+                                    int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_flat_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (flatten == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
+  return shape_body<SheetKind>(who, kSheetWords, e, format, nframes, frames, Shape{nullptr, sizes, orientations, flatten, sheet},
+                               sheet == nullptr || nsheets == nullptr, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                                      const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                      size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      RaggedOut{d_out, d_sizes, modes, q_out, value_out, stream}.strided_by(out_stride)}, sheet, nullptr, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_sheet_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                           const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                           const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                           const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
+                                           uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      RaggedOut{d_out, d_sizes, modes, q_out, value_out, stream}.strided_by(out_stride)}, sheet, flatten, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_sheet_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                             int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                             uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet, nullptr, sizes,
+                     orientations);
+}
+
+int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                  const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                  const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                                  const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                  void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                  int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet, flatten, sizes,
+                     orientations);
+}
+
+}  // extern "C"

@@ -3637,197 +3637,6 @@ int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, co
 
 extern "C" {
 
-// Pictures of a ragged batch reduced by their factors into the caller's buffer (sjpeg_hip.h): one launch of reduce.hip's
-// kernel.  Every check comes before `e` is touched.
-int sjpeg_hip_reduce_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                const uint8_t* factors, void* d_reduced, size_t reduced_bytes,
-                                sjpeg_hip_ragged_frame* reduced_frames, int* reduced_format, void* stream) {
-  static const std::string who = "sjpeg_hip_reduce_ragged_src";
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (frames == nullptr || factors == nullptr || d_reduced == nullptr || reduced_frames == nullptr || reduced_format == nullptr) {
-    return fail(SJPEG_HIP_EINVAL, who + ": frames, factors, d_reduced, reduced_frames or reduced_format == NULL");
-  }
-  if ((reinterpret_cast<uintptr_t>(d_reduced) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_reduced must be a multiple of 16");
-  try {
-    sjpeg_internal::ReducePlan plan;
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::reduce_plan(who, format, nframes, frames, factors, &plan)) return rc;
-    if (reduced_bytes < plan.bytes) {
-      return fail(SJPEG_HIP_EINVAL, who + ": reduced_bytes " + std::to_string(reduced_bytes) + " is below the " + std::to_string(plan.bytes) +
-                                        " bytes the reduced pictures take (sjpeg_hip_reduce_ragged_bytes)");
-    }
-    if (int rc = sjpeg_internal::engine_reduce(e, who, plan, static_cast<uint8_t*>(d_reduced), nullptr, stream)) return rc;
-    sjpeg_internal::reduce_plan_frames(plan, frames, static_cast<uint8_t*>(d_reduced), reduced_frames);
-    *reduced_format = plan.reduced_format;
-    return 0;
-  } catch (...) {
-    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
-  }
-}
-
-// ... and resized to their sizes (resize.hip), with the same order of checks
-int sjpeg_hip_resize_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                const int32_t (*sizes)[2], void* d_resized, size_t resized_bytes,
-                                sjpeg_hip_ragged_frame* resized_frames, int* resized_format, void* stream) {
-  static const std::string who = "sjpeg_hip_resize_ragged_src";
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (frames == nullptr || sizes == nullptr || d_resized == nullptr || resized_frames == nullptr || resized_format == nullptr) {
-    return fail(SJPEG_HIP_EINVAL, who + ": frames, sizes, d_resized, resized_frames or resized_format == NULL");
-  }
-  if ((reinterpret_cast<uintptr_t>(d_resized) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_resized must be a multiple of 16");
-  try {
-    sjpeg_internal::ResizePlan plan;
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, nullptr, &plan)) return rc;
-    if (resized_bytes < plan.bytes) {
-      return fail(SJPEG_HIP_EINVAL, who + ": resized_bytes " + std::to_string(resized_bytes) + " is below the " + std::to_string(plan.bytes) +
-                                        " bytes the resized pictures take (sjpeg_hip_resize_ragged_bytes)");
-    }
-    if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_resized), nullptr, stream)) return rc;
-    sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_resized), resized_frames);
-    *resized_format = plan.resized_format;
-    return 0;
-  } catch (...) {
-    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
-  }
-}
-
-// ... and resized, then turned upright by their EXIF orientations, in the same ONE launch (orient_math.h): the checks
-// of the resize in its order, the orientations with the sizes.  One body for the oriented entry and the flattened one
-// (sjpeg_hip_flatten_ragged_src: `flatten` goes into the plan, whose checks of it come with its others).
-static int orient_ragged_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                               const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
-                               size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
-    return fail(SJPEG_HIP_EINVAL, who + ": frames, d_out, out_frames or out_format == NULL");
-  }
-  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
-  try {
-    sjpeg_internal::ResizePlan plan;
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::resize_plan(who, format, nframes, frames, sizes, orientations, &plan, flatten)) return rc;
-    if (out_bytes < plan.bytes) {
-      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
-                                        " bytes the oriented pictures take (sjpeg_hip_orient_ragged_bytes)");
-    }
-    if (int rc = sjpeg_internal::engine_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
-    sjpeg_internal::resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
-    *out_format = plan.resized_format;
-    return 0;
-  } catch (...) {
-    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
-  }
-}
-
-int sjpeg_hip_orient_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
-                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_orient_ragged_src";
-  return orient_ragged_entry(who, e, format, nframes, frames, nullptr, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
-}
-
-// ... and flattened over a background as they are staged (flatten_math.h), still ONE launch
-int sjpeg_hip_flatten_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                 const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
-                                 size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_flatten_ragged_src";
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (flatten == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
-  return orient_ragged_entry(who, e, format, nframes, frames, flatten, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
-}
-
-// ... and the YUV-plane formats: every plane resized and turned as a picture of its own, still ONE launch; the checks
-// of the oriented entry in its order
-int sjpeg_hip_resize_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                    const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out, size_t out_bytes,
-                                    sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_resize_ragged_yuv_src";
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (frames == nullptr || d_out == nullptr || out_frames == nullptr || out_format == nullptr) {
-    return fail(SJPEG_HIP_EINVAL, who + ": frames, d_out, out_frames or out_format == NULL");
-  }
-  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
-  try {
-    sjpeg_internal::YuvResizePlan plan;
-    if (int rc = sjpeg_internal::yuv_format_check(who, format)) return rc;
-    const SourceLayout* const L = source_layout(format);
-    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan)) return rc;
-    if (out_bytes < plan.bytes) {
-      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
-                                        " bytes the resized planes take (sjpeg_hip_resize_ragged_yuv_bytes)");
-    }
-    if (int rc = sjpeg_internal::engine_yuv_resize(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
-    sjpeg_internal::yuv_resize_plan_frames(plan, frames, static_cast<uint8_t*>(d_out), out_frames);
-    *out_format = plan.resized_format;
-    return 0;
-  } catch (...) {
-    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
-  }
-}
-
-// ... and resized, turned and placed into contact sheets (sheet_plan.cc): one set of entries for both families of
-// formats; every check before `e` is touched.  One body again for the sheet entry and the flattened one.
-static int sheet_ragged_entry(const std::string& who, sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                              const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
-                              const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
-                              int* nsheets, int* out_format, void* stream) {
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (frames == nullptr || sheet == nullptr || d_out == nullptr || sheet_frames == nullptr || nsheets == nullptr || out_format == nullptr) {
-    return fail(SJPEG_HIP_EINVAL, who + ": frames, sheet, d_out, sheet_frames, nsheets or out_format == NULL");
-  }
-  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(SJPEG_HIP_EINVAL, who + ": d_out must be a multiple of 16");
-  try {
-    sjpeg_internal::SheetPlan plan;
-    const SourceLayout* const L = source_layout(format);
-    if (L == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": unknown source format");
-    if (nframes < 1 || nframes > 65535) return fail(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = sjpeg_internal::ragged_check(who, format, L->implied != 0 ? L->implied : SJPEG_HIP_YUV444, nframes, frames)) return rc;
-    if (int rc = sjpeg_internal::sheet_plan(who, format, nframes, frames, sheet, sizes, orientations, &plan, flatten)) return rc;
-    if (out_bytes < plan.bytes) {
-      return fail(SJPEG_HIP_EINVAL, who + ": bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(plan.bytes) +
-                                        " bytes the sheets take (sjpeg_hip_sheet_ragged_bytes)");
-    }
-    if (int rc = sjpeg_internal::engine_sheet(e, who, plan, static_cast<uint8_t*>(d_out), nullptr, stream)) return rc;
-    sjpeg_internal::sheet_plan_frames(plan, static_cast<uint8_t*>(d_out), sheet_frames);
-    *nsheets = plan.nsheets;
-    *out_format = plan.out_format;
-    return 0;
-  } catch (...) {
-    return fail(SJPEG_HIP_ENOMEM, "out of host memory");
-  }
-}
-
-int sjpeg_hip_sheet_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                               const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations, void* d_out,
-                               size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_sheet_ragged_src";
-  return sheet_ragged_entry(who, e, format, nframes, frames, sheet, nullptr, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets,
-                            out_format, stream);
-}
-
-int sjpeg_hip_sheet_ragged_flat_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
-                                    const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
-                                    const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
-                                    int* nsheets, int* out_format, void* stream) {
-  static const std::string who = "sjpeg_hip_sheet_ragged_flat_src";
-  if (e == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": engine == NULL");
-  if (flatten == nullptr) return fail(SJPEG_HIP_EINVAL, who + ": flatten == NULL");
-  return sheet_ragged_entry(who, e, format, nframes, frames, sheet, flatten, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets,
-                            out_format, stream);
-}
-
 // ---- exchange step of the multi-device batch path: the coded frames of one call, back to back ----
 // (BASELINE.json config #4; the reference is single-threaded and has no counterpart.)  One
 // launch, no host round trip: every workgroup sums the (16-byte aligned) sizes of the frames in
