@@ -988,7 +988,9 @@ int sjpeg_hip_exif_reset_orientation(uint8_t* exif, size_t size);
  *     apart -- the layout of the reduced pictures, per plane.  Padding may hold anything and lies inside the buffer.
  * THE CONTRACT: the JPEG of a frame is byte for byte what sjpeg_hip_encode_ragged_full_meta_src makes of the three
  * planes so defined handed over in the output format.  yuv_mode is the format's own, 4:2:0 or 4:4:4; anything else is
- * the inner call's "yuv_mode does not match the source format".
+ * the inner call's "yuv_mode does not match the source format".  The samples are coded as they are, no colour
+ * conversion: right for full-range BT.601 frames, which is what a JFIF file holds.  BT.709 and limited-range frames:
+ * the _yuv_converted_ and _yuv_colour entries further down ("video colour converted inside the ragged call").
  *
  * sjpeg_hip_yuv_plane_size (host only): the size of plane 0..2 (Y, U, V) of a width x height picture (1..65535 each)
  *   in one of the four formats; SJPEG_HIP_EINVAL for any other format, the message names it.
@@ -1226,6 +1228,111 @@ int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* engine, int 
                                                   uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
                                                   int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
                                                   void* stream);
+
+/* ---- video colour converted inside the ragged call: BT.709 and studio range ----
+ * A JFIF file is full-range BT.601 YCbCr.  Decoded video mostly is not: HD content is BT.709, and nearly all video is
+ * studio range (Y 16..235, chroma 16..240).  The YUV entries above code the samples as they are -- right for full-range
+ * BT.601 frames only; a thumbnail of anything else is displayed washed out, its saturated colours shifted in hue.  The
+ * entries below convert the MADE planes -- the thumbnails, not the sources -- to JFIF's colour: ONE more launch behind
+ * the resize launch on the call's stream, in place.  The source is described per call or per frame by its matrix
+ * (SJPEG_HIP_MATRIX_BT601 / _BT709) and its range (SJPEG_HIP_RANGE_FULL / _LIMITED).
+ * THE CONTRACT, exact and in integers.  P is what sjpeg_hip_resize_ragged_yuv_src makes of a frame: upright planar Y
+ * (uw x uh), U and V (cw x ch).  The converted picture P' is defined from P alone; floor is a true floor, clamp8 clamps
+ * to 0..255, u = U[j][i] - 128, v = V[j][i] - 128:
+ *   chroma sample (i, j):  U' = clamp8(128 + floor((k11 * u + k12 * v + 8192) / 16384))
+ *                          V' = clamp8(128 + floor((k21 * u + k22 * v + 8192) / 16384))
+ *   luma sample (x, y):    Y' = clamp8(floor((k00 * (Y - y0) + k01 * u + k02 * v + 8192) / 16384)), u and v the
+ *     UNCONVERTED chroma at (x / s, y / s), s = 2 for the 4:2:0 formats and 1 for SJPEG_HIP_SRC_YUV444: the nearest
+ *     chroma sample, the one whose block the luma sample lies in (cw = (uw + 1) / 2: always inside the plane, after a
+ *     transposing orientation too).  Every sum fits 32 bits.
+ *   The tables, Q14: rows Y, U, V of the output, columns Y, U, V of the source; the chroma rows never read luma.
+ *     BT.601 full:     y0 0,  the identity: no pass, the bytes of P
+ *     BT.601 limited:  y0 16, {19077, 0, 0}, {0, 18651, 0}, {0, 0, 18651}
+ *     BT.709 limited:  y0 16, {19077, 1895, 3657}, {0, 18462, -2064}, {0, -1351, 18342}
+ *     BT.709 full:     y0 0,  {16384, 1664, 3213}, {0, 16218, -1813}, {0, -1187, 16112}
+ *   They are rint(M * 16384), M = source Y'CbCr -> R'G'B' with the source's Kr, Kb (BT.601: 0.299, 0.114; BT.709:
+ *   0.2126, 0.0722), then R'G'B' -> full-range BT.601 YCbCr, the columns scaled by 255/219 (Y) and 255/224 (chroma) for
+ *   a limited-range source.  Against the exactly rounded real result the integer formula is off by at most 1.
+ * The JPEG of a frame is byte for byte what sjpeg_hip_encode_ragged_full_meta_src makes of P' handed over as
+ * SJPEG_HIP_SRC_YUV420 (SJPEG_HIP_SRC_YUV444 for a 4:4:4 source).  In a sheet only the thumbnails' rectangles are
+ * converted: `background` stays as given, (Y, U, V) in the output's colour.
+ *
+ * colour, colour_per_frame: used as meta / meta_per_frame are -- [1] for all frames, or [nframes].  colour == NULL, or
+ *   BT.601 full range for every frame: the entry IS its counterpart above -- the same bytes, no extra device work, its
+ *   messages.  Otherwise every size and orientation goes through the resize kernel, ratio 1 included (the caller's
+ *   planes are never written), then the colour launch over the frames that need it, then ONE inner call.
+ * sjpeg_hip_yuv_colour_samples (host only): the formula as code, for bindings and tests: yuv_out[k] = P' of the one-
+ *   sample picture yuv_in[k] = (Y, U, V); yuv_out may be yuv_in.
+ * sjpeg_hip_convert_ragged_yuv_src: the arguments of sjpeg_hip_resize_ragged_yuv_src plus the colour; P' in the same
+ *   layout, sized by sjpeg_hip_resize_ragged_yuv_bytes.
+ * sjpeg_hip_encode_ragged_yuv_converted_src / _yuv_converted_packed_src: the _yuv_resized_ entries plus the colour.
+ * sjpeg_hip_sheet_ragged_yuv_colour_src, sjpeg_hip_encode_ragged_sheet_yuv_colour_src / _sheet_yuv_colour_packed_src:
+ *   the three sheet entries, for the four YUV-plane formats, plus the colour; places and bytes: sjpeg_hip_sheet_places
+ *   and sjpeg_hip_sheet_ragged_bytes as they are.
+ * SJPEG_HIP_EINVAL before any device work, the frame named as the ragged entries name it: a matrix or a range above 1,
+ *   a reserved byte that is not 0, an RGB-like or gray format (the message names it), samples == NULL, and every check
+ *   the counterpart entry makes. */
+enum { SJPEG_HIP_MATRIX_BT601 = 0, SJPEG_HIP_MATRIX_BT709 = 1 };
+enum { SJPEG_HIP_RANGE_FULL = 0, SJPEG_HIP_RANGE_LIMITED = 1 };
+typedef struct sjpeg_hip_yuv_colour {
+  uint8_t matrix;                 /* SJPEG_HIP_MATRIX_* of the SOURCE */
+  uint8_t range;                  /* SJPEG_HIP_RANGE_* of the SOURCE */
+  uint8_t reserved[2];            /* 0 */
+} sjpeg_hip_yuv_colour;           /* 4 bytes */
+int sjpeg_hip_yuv_colour_samples(const sjpeg_hip_yuv_colour* colour, size_t n, const uint8_t (*yuv_in)[3] /*[n]*/,
+                                 uint8_t (*yuv_out)[3] /*[n]*/);
+int sjpeg_hip_convert_ragged_yuv_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                     const uint8_t* orientations /*host [nframes], or NULL*/,
+                                     const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                     void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/,
+                                     int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_yuv_converted_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                              const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                              const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                              const uint8_t* orientations /*host [nframes], or NULL*/,
+                                              const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                              const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                              void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                              int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_yuv_converted_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                     const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                     const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                     const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                                     const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                     void* d_packed, size_t packed_capacity,
+                                                     uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                     int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                     void* stream);
+int sjpeg_hip_sheet_ragged_yuv_colour_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_sheet* sheet,
+                                          const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                          const uint8_t* orientations /*host [nframes], or NULL*/,
+                                          const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                          void* d_out, size_t bytes, sjpeg_hip_ragged_frame* sheet_frames /*host out [nsheets]*/,
+                                          int* nsheets, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_sheet_yuv_colour_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                 const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                 const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                 const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                                 const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                                 void* d_out, size_t out_stride, uint64_t* d_sizes /*[nsheets]*/,
+                                                 int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                                        const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                        const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                        const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                        const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                                        const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                                        void* d_packed, size_t packed_capacity,
+                                                        uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
+                                                        int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
+                                                        void* stream);
 
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that

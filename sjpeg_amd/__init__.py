@@ -995,6 +995,11 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_sheet_src", "sjpeg_hip_encode_ragged_sheet_packed_src",
     "sjpeg_hip_flatten_ragged_src", "sjpeg_hip_encode_ragged_flattened_src", "sjpeg_hip_encode_ragged_flattened_packed_src",
     "sjpeg_hip_sheet_ragged_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_packed_src",
+    # (bound by sjpeg_amd/video.py)
+    "sjpeg_hip_yuv_colour_samples", "sjpeg_hip_convert_ragged_yuv_src",
+    "sjpeg_hip_encode_ragged_yuv_converted_src", "sjpeg_hip_encode_ragged_yuv_converted_packed_src",
+    "sjpeg_hip_sheet_ragged_yuv_colour_src", "sjpeg_hip_encode_ragged_sheet_yuv_colour_src",
+    "sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src",
 ]
 
 
@@ -3221,7 +3226,8 @@ def encode_yuv_sheets(frames, fmt=SRC_NV12, sheet=None, sizes=None, orientations
     """encode_sheets for decoded video, shaped like encode_yuv_frames: frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 or
     (y, u, v) for SRC_YUV420 / SRC_YUV444, each resized plane by plane (sizes None: fitted into its cell), turned and
     stored into its cell -- chroma at half the luma's place for the 4:2:0 formats, whose Sheet takes even cells, gutter
-    and margin; background is (Y, U, V).  No colour conversion: the sheets are coded 4:2:0 (SRC_YUV444: 4:4:4).
+    and margin; background is (Y, U, V).  No colour conversion: the sheets are coded 4:2:0 (SRC_YUV444: 4:4:4) --
+    sjpeg_amd.video.encode_video_sheets converts BT.709 and limited-range frames to JFIF's colour inside the call.
     Returns (JPEGs, places) as encode_sheets -- the storyboard behind a scrub bar in one call."""
     who = "encode_yuv_sheets"
     planes, dims, dev = _yuv_frames(who, frames, fmt)
@@ -3240,7 +3246,8 @@ def encode_yuv_frames(frames, fmt=SRC_NV12, sizes=None, box=None, orientations=N
     formats -- frames[k] = (y, uv) for SRC_NV12 / SRC_NV21 ([H, W] and [(H + 1) // 2, 2 * ((W + 1) // 2)] uint8 CUDA
     tensors) or (y, u, v) for SRC_YUV420 / SRC_YUV444 --, each resized to sizes[k] = (w, h) or fitted into box = (bw, bh)
     (fit_size; the box is the UPRIGHT one) and turned upright by orientations (one EXIF value 1..8 or one per frame),
-    in one ragged call with no colour conversion: the frames are coded 4:2:0 (SRC_YUV444: 4:4:4) as they are sampled.
+    in one ragged call with no colour conversion: the frames are coded 4:2:0 (SRC_YUV444: 4:4:4) as they are sampled
+    (right for full-range BT.601 frames; sjpeg_amd.video.encode_video_frames converts BT.709 and limited-range ones).
     quality: one value or one per frame; target_size / target_psnr: a per-frame search as encode_images_full;
     packed=True: through the packed entry and one device-to-host copy; metadata: as encode_images."""
     import torch

@@ -13,6 +13,7 @@
 #include "pixel_elem.h"
 #include "sjpeg_hip.h"
 #include "source_layout.h"
+#include "yuv_colour_math.h"
 
 namespace sjpeg_internal {
 
@@ -266,6 +267,39 @@ int resize_ragged_placed_launch(int format, const float* pscale, const float* pb
 int yuv_resize_ragged_placed_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
 // the engine's half, as engine_resize: the background fill, then the placed resize, both on `stream`
 int engine_sheet(sjpeg_hip_engine* e, const std::string& who, const SheetPlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
+
+// ---- video colour conversion (sjpeg_hip_convert_ragged_yuv_src; yuv_colour_plan.cc, yuv_colour.hip): the made planes
+// of the YUV plan above, or the thumbnails' rectangles of a sheet, converted in place to JFIF's colour by ONE launch
+// behind the resize launch.  One descriptor per frame; a workgroup finds its frame by the binary search over tile_base.
+// A tile is 256 consecutive LANES of the frame in row-major order, a lane four chroma samples of a row -- one dword of
+// U and one of V -- and the luma samples above them.  A frame with identity colour has no tiles.
+struct YuvColourFrame {
+  uint8_t *y, *u, *v;                    // the planes' first samples (a placed frame's: inside its sheet planes)
+  unsigned y_stride, c_stride;           // bytes between the rows of Y, and of U and V
+  int uw, uh, cw, ch;                    // the upright luma and chroma sizes
+  int s;                                 // luma samples a chroma sample, each way: 2 (4:2:0) or 1 (4:4:4)
+  int lead;                              // placed: the bytes from the dword boundary in front of u to u, 0..3 (else 0)
+  unsigned groups, tile_base;            // lanes a chroma row; the frame's first workgroup in the flat grid
+  YuvColourTable table;
+};
+struct YuvColourPlan {
+  std::vector<YuvColourFrame> frames;    // [nframes]; y, u, v from the buffer's start, as the plans count
+  unsigned tiles = 0;
+  bool placed = false;                   // the frames are a sheet's thumbnails: only their own bytes are stored
+};
+// 0 for colours the entries take (NULL: none to check), else SJPEG_HIP_EINVAL: a matrix or range above 1, a reserved
+// byte that is not 0; the message names the frame (colour_per_frame == 0: colour[0] is every frame's)
+int yuv_colour_check(const std::string& who, int nframes, const sjpeg_hip_yuv_colour* colour, int colour_per_frame);
+// NULL, or BT.601 full range for every frame: there is nothing to convert
+bool yuv_colour_all_identity(int nframes, const sjpeg_hip_yuv_colour* colour, int colour_per_frame);
+// The colours checked, then a descriptor per frame of `planes` -- the plan of yuv_resize_plan, or the placed one of a
+// sheet_plan of a YUV-plane format.
+int yuv_colour_plan(const std::string& who, const YuvResizePlan& planes, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                    YuvColourPlan* plan);
+int yuv_colour_launch(bool placed, const YuvColourFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
+// The engine's half (scan_engine.hip): the descriptors rebased to `base`, uploaded into a buffer of their own and the
+// kernel launched on `stream`, behind the resize launch that made the planes.  No tiles: nothing is done.
+int engine_yuv_colour(sjpeg_hip_engine* e, const std::string& who, const YuvColourPlan& plan, uint8_t* base, void* stream);
 
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own

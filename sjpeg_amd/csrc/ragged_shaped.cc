@@ -28,6 +28,8 @@ struct Shape {
   const uint8_t* orientations = nullptr;
   const sjpeg_hip_flatten* flatten = nullptr;
   const sjpeg_hip_sheet* sheet = nullptr;
+  const sjpeg_hip_yuv_colour* colour = nullptr;
+  int colour_per_frame = 0;
 };
 
 // ---- the plan kinds: the plan function, the format of what it makes, the made pictures as frames at `base` and how
@@ -79,6 +81,37 @@ struct SheetKind : PerFrameKind {                // (its frames count sheets: ou
   static constexpr auto run = engine_sheet;
 };
 
+// ... and the two whose planes are converted to JFIF's colour behind the resize launch (yuv_colour_plan.cc): the plan of
+// the kind they extend plus the colour launch's, the engine's half of the one and then of the other
+struct YuvColourKind : YuvResizeKind {
+  struct Plan : YuvResizePlan { YuvColourPlan colour; };
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = YuvResizeKind::plan(who, format, n, fr, s, p)) return rc;
+    return yuv_colour_plan(who, *p, s.colour, s.colour_per_frame, &p->colour);
+  }
+  static int run(sjpeg_hip_engine* e, const std::string& who, const Plan& p, uint8_t* d_out, uint8_t** base, void* stream) {
+    uint8_t* at = nullptr;
+    if (int rc = engine_yuv_resize(e, who, p, d_out, &at, stream)) return rc;
+    if (base != nullptr) *base = at;
+    return engine_yuv_colour(e, who, p.colour, at, stream);
+  }
+};
+struct SheetColourKind : SheetKind {             // (the thumbnails' rectangles alone: the background stays as given)
+  struct Plan : SheetPlan { YuvColourPlan colour; };
+  static constexpr bool yuv_only = true;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = yuv_format_check(who, format)) return rc;
+    if (int rc = SheetKind::plan(who, format, n, fr, s, p)) return rc;
+    return yuv_colour_plan(who, p->planes, s.colour, s.colour_per_frame, &p->colour);
+  }
+  static int run(sjpeg_hip_engine* e, const std::string& who, const Plan& p, uint8_t* d_out, uint8_t** base, void* stream) {
+    uint8_t* at = nullptr;
+    if (int rc = engine_sheet(e, who, p, d_out, &at, stream)) return rc;
+    if (base != nullptr) *base = at;
+    return engine_yuv_colour(e, who, p.colour, at, stream);
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -128,7 +161,8 @@ int shape_body(const std::string& who, const ShapeWords& w, sjpeg_hip_engine* e,
 const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPEG_ENTRY_NAMES("resized"),
                   kOriented[2] = SJPEG_ENTRY_NAMES("oriented"), kFlattened[2] = SJPEG_ENTRY_NAMES("flattened"),
                   kYuvResized[2] = SJPEG_ENTRY_NAMES("yuv_resized"), kSheet[2] = SJPEG_ENTRY_NAMES("sheet"),
-                  kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat");
+                  kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat"), kYuvConverted[2] = SJPEG_ENTRY_NAMES("yuv_converted"),
+                  kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -175,12 +209,13 @@ int planned_flow(const RaggedCall& c, const Shape& s) {
 
 // The contact sheets' flow differs: params, meta, modes, q_out and value_out count SHEETS, whose output ranges the flow
 // makes itself -- sheet s at d_out + s * out_stride with capacity out_stride, or packed with what is always enough.
+template <class K = SheetKind>
 int sheet_flow(const RaggedCall& c, const Shape& s) {
   const std::string& who = *c.who;
   const RaggedOut& o = c.out;
   try {
-    SheetPlan plan;
-    if (int rc = SheetKind::plan(who, c.format, c.nframes, c.frames, s, &plan)) return rc;
+    typename K::Plan plan;
+    if (int rc = K::plan(who, c.format, c.nframes, c.frames, s, &plan)) return rc;
     const SourceLayout* const L = source_layout(c.format);
     if (L->implied != 0 && c.params->yuv_mode != L->implied) {
       return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + SheetKind::mode_hint(plan));
@@ -210,7 +245,7 @@ int sheet_flow(const RaggedCall& c, const Shape& s) {
     if (int rc = full_checks(who, plan.out_format, ns, made.data(), *c.params)) return rc;
     // ---- device work
     uint8_t* base = nullptr;
-    if (int rc = engine_sheet(c.e, who, plan, nullptr, &base, o.stream)) return rc;
+    if (int rc = K::run(c.e, who, plan, nullptr, &base, o.stream)) return rc;
     made_sheets(base);
     RaggedCall inner = c;
     inner.format = plan.out_format; inner.nframes = ns; inner.frames = made.data();
@@ -288,6 +323,28 @@ int sheet_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flat
   c.who = flatten != nullptr ? &kSheetFlat[c.out.packed] : &kSheet[c.out.packed];
   if (int rc = encode_prologue(c, true, sheet)) return rc;
   return sheet_flow(c, Shape{nullptr, sizes, orientations, flatten, sheet});
+}
+// colour NULL or the identity for every frame: exactly the yuv_resized call on the same arguments.  Otherwise every
+// frame goes through the resize kernel, at its own size and orientation 1 too: the colour launch works in place, and
+// the caller's planes are not its to write.
+int yuv_converted_entry(RaggedCall c, const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour,
+                        int colour_per_frame) {
+  c.who = &kYuvConverted[c.out.packed];
+  if (int rc = encode_prologue(c, false, nullptr, true)) return rc;
+  if (yuv_colour_all_identity(c.nframes, colour, colour_per_frame)) {
+    c.who = &kYuvResized[c.out.packed];
+    return yuv_resized_entry(c, sizes, orientations);
+  }
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  return planned_flow<YuvColourKind>(c, Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame});
+}
+// ... the sheet call, for the YUV-plane formats
+int sheet_colour_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations,
+                       const sjpeg_hip_yuv_colour* colour, int colour_per_frame) {
+  c.who = &kSheetColour[c.out.packed];
+  if (int rc = encode_prologue(c, true, sheet, true)) return rc;
+  if (yuv_colour_all_identity(c.nframes, colour, colour_per_frame)) return sheet_entry(c, sheet, nullptr, sizes, orientations);
+  return sheet_flow<SheetColourKind>(c, Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame});
 }
 
 }  // namespace
@@ -495,6 +552,80 @@ int sjpeg_hip_encode_ragged_sheet_flat_packed_src(sjpeg_hip_engine* e, int forma
   return sheet_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                       RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet, flatten, sizes,
                      orientations);
+}
+
+// ---- ... and video colour: the made planes, or the thumbnails' rectangles of a sheet, converted to JFIF's full-range
+// BT.601 by ONE more launch behind the resize launch (yuv_colour.hip)
+int sjpeg_hip_convert_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                     const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour,
+                                     int colour_per_frame, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* out_frames,
+                                     int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_convert_ragged_yuv_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "converted planes", "sjpeg_hip_resize_ragged_yuv_bytes"};
+  // (nothing to convert: the resize entry itself; colour is [nframes] only where nframes is a count)
+  if (colour == nullptr || (nframes >= 1 && nframes <= 65535 && yuv_colour_all_identity(nframes, colour, colour_per_frame))) {
+    return sjpeg_hip_resize_ragged_yuv_src(e, format, nframes, frames, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
+  }
+  return shape_body<YuvColourKind>(who, w, e, format, nframes, frames, Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame},
+                                   false, d_out, out_bytes, out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_yuv_converted_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                              const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                              const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_metadata* meta,
+                                              int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                              void* stream) {
+  return yuv_converted_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                              {d_out, d_sizes, modes, q_out, value_out, stream}}, sizes, orientations, colour, colour_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_yuv_converted_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                     const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2],
+                                                     const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                                                     const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                                     size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                                     float* q_out, float* value_out, void* stream) {
+  return yuv_converted_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                              RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes,
+                             orientations, colour, colour_per_frame);
+}
+
+int sjpeg_hip_sheet_ragged_yuv_colour_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                          const sjpeg_hip_yuv_colour* colour, int colour_per_frame, void* d_out, size_t out_bytes,
+                                          sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_yuv_colour_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = yuv_format_check(who, format)) return rc;
+  if (colour == nullptr || (nframes >= 1 && nframes <= 65535 && yuv_colour_all_identity(nframes, colour, colour_per_frame))) {
+    return sjpeg_hip_sheet_ragged_src(e, format, nframes, frames, sheet, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets, out_format,
+                                      stream);
+  }
+  return shape_body<SheetColourKind>(who, kSheetWords, e, format, nframes, frames,
+                                     Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame},
+                                     sheet == nullptr || nsheets == nullptr, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_yuv_colour_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                                                 const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                                                 const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, size_t out_stride,
+                                                 uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_colour_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                             RaggedOut{d_out, d_sizes, modes, q_out, value_out, stream}.strided_by(out_stride)}, sheet, sizes, orientations, colour,
+                            colour_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                        const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                        const int32_t (*sizes)[2], const uint8_t* orientations,
+                                                        const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                                                        const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                                        size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes,
+                                                        float* q_out, float* value_out, void* stream) {
+  return sheet_colour_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                             RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet, sizes,
+                            orientations, colour, colour_per_frame);
 }
 
 }  // extern "C"

@@ -244,6 +244,9 @@ struct sjpeg_hip_engine {
   // blocks out in --, and the kernel's frame descriptors.  A later call writes them behind everything the earlier one
   // queued: the engine's ordering, as for every scratch buffer.
   DevBuf<uint4> reduced, reduce_desc;
+  // ... and the descriptors of the colour launch that may follow the resize launch of the same call (yuv_colour.hip): a
+  // buffer of their own, so that their upload never lands on descriptors the resize kernel is still to read
+  DevBuf<uint4> colour_desc;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;
@@ -688,7 +691,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
-  e->reduced.release(); e->reduce_desc.release();
+  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -714,7 +717,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
-  e->reduced.release(); e->reduce_desc.release();
+  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -858,7 +861,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
   return lanes + b(e->tables) + b(e->header) + b(e->seg_words) + b(e->seg_nbits) + b(e->pool) + b(e->pool_ctr) + b(e->seg_xbase) +
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
          b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) + b(e->hdr_stage) +
-         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor) + b(e->reduced) + b(e->reduce_desc);
+         b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor) + b(e->reduced) + b(e->reduce_desc) + b(e->colour_desc);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,
@@ -3633,6 +3636,27 @@ int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, co
   }
   if (base != nullptr) *base = sheets;
   return rc;
+}
+
+// ... and of the video colour conversion (yuv_colour_plan.cc): the launch behind the resize launch of the same call, on
+// the same stream, over the planes that one made at `base`
+int sjpeg_internal::engine_yuv_colour(sjpeg_hip_engine* e, const std::string& who, const YuvColourPlan& plan, uint8_t* base, void* stream) {
+  if (plan.tiles == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<YuvColourFrame> desc = plan.frames;
+  for (YuvColourFrame& d : desc) {
+    d.y = base + reinterpret_cast<uintptr_t>(d.y);
+    d.u = base + reinterpret_cast<uintptr_t>(d.u);
+    d.v = base + reinterpret_cast<uintptr_t>(d.v);
+  }
+  const size_t desc_bytes = sizeof(YuvColourFrame) * desc.size();
+  if (int rc = e->colour_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (int rc = upload(e, e->colour_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (yuv_colour_launch(plan.placed, reinterpret_cast<const YuvColourFrame*>(e->colour_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, who + ": yuv_colour_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
 }
 
 extern "C" {
