@@ -1334,6 +1334,108 @@ int sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src(sjpeg_hip_engine* engine
                                                         int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
                                                         void* stream);
 
+/* ---- 10-bit video: P010 and 16-bit YUV planes in the ragged call ----
+ * GPU decoders write HEVC Main10, AV1 10-bit and VP9 profile 2 as P010 -- NV12's plane layout with little-endian 16-bit
+ * words, the sample in the high bits --, software decoders yuv420p10le / yuv420p12le -- planar, the sample in the low
+ * bits.  The entries below take such frames as the decoder wrote them: the resize kernel stages the 16-bit words, sums
+ * them exactly and rounds ONCE into the made 8-bit planes; there is no narrowing pass over the full-size planes.
+ * A DEEP source is one of the four YUV-plane formats (SJPEG_HIP_SRC_NV12, _NV21, _YUV420, _YUV444: the format says
+ * where the samples lie, in samples) whose every sample is a little-endian 16-bit word x.  The depth is a second axis
+ * beside the format, one per call: bytes = 2, and shift = how many low bits of a word lie below the byte.
+ *   P010, P012, P016:  SJPEG_HIP_SRC_NV12,   shift 8        yuv420p10le:  SJPEG_HIP_SRC_YUV420, shift 2
+ *   yuv444p10le:       SJPEG_HIP_SRC_YUV444, shift 2        yuv420p12le:  SJPEG_HIP_SRC_YUV420, shift 4
+ * THE CONTRACT, exact and in integers.  A sample of a made plane comes from its cell's weighted sum S of source WORDS,
+ * the cells and weights those of the resize above on the W w' x H h' grid; the weights sum to A = W H.  With s = shift:
+ *   byte = min(255, floor((2 S + A 2^s) / (A 2^(s+1))))
+ * -- the exact area average of the words, divided by 2^s, rounded half up once, then clamped.  The clamp is needed: a
+ * full-scale P010 picture gives 256 before it.  At the frame's own size this is min(255, (x + 2^(s-1)) >> s); for s = 0
+ * it is min(255, x).  Bits above the nominal depth of a low-aligned source are no error: they take part as they are
+ * and the clamp bounds the result.  Bounds: a row's horizontal sum is at most 65535 * 65535 < 2^32, a cell's sum is
+ * below 2^48, the numerator below 2^50.
+ * Everything behind that is the contracts above applied to the made 8-bit planes: the orientation, the placed store
+ * into sheets, the Q14 colour conversion (a 10-bit limited-range sample 64..940 lands on 16..235, so BT.709 / limited
+ * works as it does for bytes).  There is no BT.2020 matrix and no PQ / HLG tone mapping: HDR frames are coded by their
+ * code values.  The JPEG of a frame is byte for byte what the _yuv_converted_ entry makes of the made planes' bytes.
+ *
+ * depth: host, one per call.  colour, colour_per_frame: as above; colour == NULL: none.  There is NO pass-through: the
+ *   inner flow cannot read words, so every frame goes through the kernel, at its own size and orientation 1 too.
+ * sjpeg_hip_yuv16_samples (host only): the own-size formula as code: out[k] = min(255, (in[k] + 2^(s-1)) >> s).
+ * sjpeg_hip_convert_ragged_yuv16_src: sjpeg_hip_convert_ragged_yuv_src plus the depth; the made planes are bytes, in
+ *   the same layout, so sjpeg_hip_resize_ragged_yuv_bytes sizes the buffer for this entry too.
+ * sjpeg_hip_encode_ragged_yuv16_src / _yuv16_packed_src: the _yuv_converted_ entries plus the depth.
+ * sjpeg_hip_sheet_ragged_yuv16_src, sjpeg_hip_encode_ragged_sheet_yuv16_src / _sheet_yuv16_packed_src: the three
+ *   _yuv_colour sheet entries plus the depth; places and bytes by sjpeg_hip_sheet_places / sjpeg_hip_sheet_ragged_bytes.
+ * A frame's planes: row_stride in BYTES as ever, |row_stride| at least twice the 8-bit row; every plane pointer and
+ *   row stride a multiple of 2.
+ * SJPEG_HIP_EINVAL before any device work: depth == NULL, bytes other than 2, a shift above 8, a reserved byte that is
+ *   not 0 (the field is named); an RGB-like or gray format (named); a NULL plane, a short row, a plane or row stride
+ *   that is not a multiple of the element size (2 bytes) -- frame and plane named; and every check the counterpart
+ *   entry makes. */
+typedef struct sjpeg_hip_yuv_depth {
+  uint8_t bytes;                  /* 2 (the only value taken; 1 and others are refused by name) */
+  uint8_t shift;                  /* 0..8: how many low bits of a word lie below the byte */
+  uint8_t reserved[2];            /* 0 */
+} sjpeg_hip_yuv_depth;            /* 4 bytes */
+int sjpeg_hip_yuv16_samples(const sjpeg_hip_yuv_depth* depth, size_t n, const uint16_t* in /*[n]*/, uint8_t* out /*[n]*/);
+int sjpeg_hip_convert_ragged_yuv16_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                       const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                       const uint8_t* orientations /*host [nframes], or NULL*/,
+                                       const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                       const sjpeg_hip_yuv_depth* depth,
+                                       void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/,
+                                       int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_yuv16_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                      const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                      const uint8_t* orientations /*host [nframes], or NULL*/,
+                                      const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                      const sjpeg_hip_yuv_depth* depth,
+                                      const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                      void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                      int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_yuv16_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                             const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                             const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                             const uint8_t* orientations /*host [nframes], or NULL*/,
+                                             const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                             const sjpeg_hip_yuv_depth* depth,
+                                             const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                             void* d_packed, size_t packed_capacity,
+                                             uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                             int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                             void* stream);
+int sjpeg_hip_sheet_ragged_yuv16_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_sheet* sheet,
+                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                     const uint8_t* orientations /*host [nframes], or NULL*/,
+                                     const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                     const sjpeg_hip_yuv_depth* depth,
+                                     void* d_out, size_t bytes, sjpeg_hip_ragged_frame* sheet_frames /*host out [nsheets]*/,
+                                     int* nsheets, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_sheet_yuv16_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                            const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                            const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                            const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                            const uint8_t* orientations /*host [nframes], or NULL*/,
+                                            const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                            const sjpeg_hip_yuv_depth* depth,
+                                            const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                            void* d_out, size_t out_stride, uint64_t* d_sizes /*[nsheets]*/,
+                                            int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_sheet_yuv16_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                   const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                                   const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                   const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                   const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                   const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                                   const sjpeg_hip_yuv_depth* depth,
+                                                   const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity,
+                                                   uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
+                                                   int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
+                                                   void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

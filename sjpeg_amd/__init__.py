@@ -1000,6 +1000,10 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_yuv_converted_src", "sjpeg_hip_encode_ragged_yuv_converted_packed_src",
     "sjpeg_hip_sheet_ragged_yuv_colour_src", "sjpeg_hip_encode_ragged_sheet_yuv_colour_src",
     "sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src",
+    "sjpeg_hip_yuv16_samples", "sjpeg_hip_convert_ragged_yuv16_src",
+    "sjpeg_hip_encode_ragged_yuv16_src", "sjpeg_hip_encode_ragged_yuv16_packed_src",
+    "sjpeg_hip_sheet_ragged_yuv16_src", "sjpeg_hip_encode_ragged_sheet_yuv16_src",
+    "sjpeg_hip_encode_ragged_sheet_yuv16_packed_src",
 ]
 
 

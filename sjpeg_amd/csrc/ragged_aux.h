@@ -200,6 +200,8 @@ struct YuvResizePlan {
   std::vector<YuvPlane> planes;          // frame after frame
   size_t bytes = 0;
   unsigned tiles = 0;
+  bool deep = false;                     // the source planes hold 16-bit samples (the kernel's deep instantiations)
+  unsigned shift = 0;                    // ... whose byte lies this many bits up (sjpeg_hip_yuv_depth)
 };
 // the size of plane 0..2 of a width x height picture of a YUV-plane format, as the encoder reads it
 inline void yuv_plane_dims(const SourceLayout& L, int width, int height, int plane, int* pw, int* ph) {
@@ -214,13 +216,19 @@ int yuv_format_check(const std::string& who, int format);
 // Checks the format (one of the four YUV-plane ones: anything else is refused by name), the sizes and the orientations
 // as resize_plan does, then plans: every plane by resize_plan's tw / th rule, the planes of frame after frame Y, U, V
 // in reduce_round.h's layout, each turned as a picture of its own.  The frames' planes and strides are the caller's to
-// check (ragged_check).
+// check (ragged_check).  depth (NULL: planes of bytes): checked by yuv_depth_check, then the plan is marked deep -- the
+// descriptors are the same (a pair's off[] counts samples); the made planes are bytes, so layout and bytes are too.
 int yuv_resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                    const uint8_t* orientations, YuvResizePlan* plan);
+                    const uint8_t* orientations, YuvResizePlan* plan, const sjpeg_hip_yuv_depth* depth = nullptr);
+// 0 for a depth the deep entries take, else SJPEG_HIP_EINVAL naming the field: depth == NULL, bytes other than 2, a
+// shift above 8, a reserved byte that is not 0
+int yuv_depth_check(const std::string& who, const sjpeg_hip_yuv_depth* depth);
 // the made pictures as frames of plan.resized_format at `base`: three planes, their strides, the upright size
 void yuv_resize_plan_frames(const YuvResizePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
 int yuv_resize_ragged_launch(const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
-// the engine's half, as engine_resize
+// ... of a deep plan (placed: a sheet's descriptors)
+int yuv_resize_ragged_deep_launch(bool placed, unsigned shift, const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
+// the engine's half, as engine_resize; a deep plan runs the deep launch
 int engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
 
 // ---- contact sheets (sjpeg_hip_sheet_ragged_src; sheet_plan.cc, resize.hip): the thumbnails of the two plans above,
@@ -258,7 +266,8 @@ int sheet_check(const std::string& who, const sjpeg_hip_sheet* sheet, int format
 // rewritten to its place.  flatten (NULL: none): handed to resize_plan; a YUV-plane format has no alpha and is
 // refused by name.
 int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_sheet* sheet,
-               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten = nullptr);
+               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten = nullptr,
+               const sjpeg_hip_yuv_depth* depth = nullptr);   // (depth: handed to yuv_resize_plan)
 // the sheets as frames of plan.out_format at `base` (out_offset, out_capacity: 0)
 void sheet_plan_frames(const SheetPlan& plan, uint8_t* base, sjpeg_hip_ragged_frame* out /*[nsheets]*/);
 int sheet_fill_launch(const SheetFill& fill, uint8_t* base, hipStream_t st);
@@ -357,8 +366,10 @@ size_t engine_scratch_limit(const sjpeg_hip_engine* e);   // SJPEG_HIP_SCRATCH_L
 int engine_device(const sjpeg_hip_engine* e);
 // n sizes of engine-owned device memory (the search's sub-calls leave their sizes there, queued on the call's stream)
 int engine_search_sizes(sjpeg_hip_engine* e, size_t n, uint64_t** d_sizes);
-// the checks of a ragged encode's format, yuv_mode and frames (output ranges included); the message names the frame
-int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames);
+// the checks of a ragged encode's format, yuv_mode and frames (output ranges included); the message names the frame.
+// esz: the size of a sample where it is not the format's own -- 2 for the deep entries, whose planes hold 16-bit
+// samples: the same rules with rows twice as long, planes and strides multiples of 2
+int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames, int esz = 0);
 // the counted bits of frames[0, nframes) with the first plan, no host wait: ~0 for a frame that overflowed it (checked
 // as sjpeg_hip_scan_counted_bits_ragged_src)
 int counted_bits_first(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,

@@ -1,8 +1,8 @@
 // ragged_shaped.cc -- the ragged entries on pictures that are SHAPED inside the call: reduced by a factor (reduce.hip),
 // resized to a size, turned upright by an EXIF orientation and flattened over a background (resize.hip), the same for
-// the YUV-plane formats (yuv_resize_plan.cc), and placed into contact sheets (sheet_plan.cc).  Per family a shape entry
-// -- the made pictures into the caller's buffer -- and an encode entry with its packed twin: the pictures into the
-// engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
+// the YUV-plane formats (yuv_resize_plan.cc), their samples bytes or 16-bit words, and placed into contact sheets
+// (sheet_plan.cc).  Per family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
+// its packed twin: the pictures into the engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
 //
 // Every entry fills a call description (ragged_aux.h: RaggedCall, RaggedOut) and names a plan KIND below; the bodies
 // -- shape_body, planned_flow, sheet_flow -- are written once against those.  A route that needs no kernel (factors all
@@ -30,6 +30,7 @@ struct Shape {
   const sjpeg_hip_sheet* sheet = nullptr;
   const sjpeg_hip_yuv_colour* colour = nullptr;
   int colour_per_frame = 0;
+  const sjpeg_hip_yuv_depth* depth = nullptr;
 };
 
 // ---- the plan kinds: the plan function, the format of what it makes, the made pictures as frames at `base` and how
@@ -37,6 +38,7 @@ struct Shape {
 using Frame = sjpeg_hip_ragged_frame;
 struct PerFrameKind {                            // (one made picture per frame; the format is any the plan takes)
   static constexpr bool yuv_only = false;
+  static constexpr int esz = 0;                  // (the size of a sample where it is not the format's own: ragged_check)
   template <class P> static int count(const P&, int nframes) { return nframes; }
   template <class P> static const char* mode_hint(const P&) { return " (gray pictures are coded 4:0:0 only)"; }
 };
@@ -112,6 +114,26 @@ struct SheetColourKind : SheetKind {             // (the thumbnails' rectangles 
   }
 };
 
+// ... and the two on planes of 16-bit samples (sjpeg_hip_yuv_depth): the same plans marked deep, so the engine's half
+// runs the kernel's deep instantiations; the made planes are bytes, and everything behind them is the colour kinds'
+struct YuvDeepKind : YuvColourKind {
+  static constexpr int esz = 2;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = yuv_depth_check(who, s.depth)) return rc;
+    if (int rc = yuv_resize_plan(who, format, n, fr, s.sizes, s.orientations, p, s.depth)) return rc;
+    return yuv_colour_plan(who, *p, s.colour, s.colour_per_frame, &p->colour);
+  }
+};
+struct SheetDeepKind : SheetColourKind {
+  static constexpr int esz = 2;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = yuv_format_check(who, format)) return rc;
+    if (int rc = yuv_depth_check(who, s.depth)) return rc;
+    if (int rc = sheet_plan(who, format, n, fr, s.sheet, s.sizes, s.orientations, p, nullptr, s.depth)) return rc;
+    return yuv_colour_plan(who, p->planes, s.colour, s.colour_per_frame, &p->colour);
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -140,7 +162,7 @@ int shape_body(const std::string& who, const ShapeWords& w, sjpeg_hip_engine* e,
     const SourceLayout* const L = source_layout(format);
     if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
     if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
-    if (int rc = ragged_check(who, format, source_mode(L), nframes, frames)) return rc;
+    if (int rc = ragged_check(who, format, source_mode(L), nframes, frames, K::esz)) return rc;
     if (int rc = K::plan(who, format, nframes, frames, s, &plan)) return rc;
     if (bytes < plan.bytes) {
       return set_error(SJPEG_HIP_EINVAL, who + ": " + w.bytes + " " + std::to_string(bytes) + " is below the " + std::to_string(plan.bytes) +
@@ -162,7 +184,8 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kOriented[2] = SJPEG_ENTRY_NAMES("oriented"), kFlattened[2] = SJPEG_ENTRY_NAMES("flattened"),
                   kYuvResized[2] = SJPEG_ENTRY_NAMES("yuv_resized"), kSheet[2] = SJPEG_ENTRY_NAMES("sheet"),
                   kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat"), kYuvConverted[2] = SJPEG_ENTRY_NAMES("yuv_converted"),
-                  kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour");
+                  kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour"), kYuv16[2] = SJPEG_ENTRY_NAMES("yuv16"),
+                  kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -186,7 +209,7 @@ int planned_flow(const RaggedCall& c, const Shape& s) {
     if (L->implied != 0 && c.params->yuv_mode != L->implied) {
       return set_error(SJPEG_HIP_EINVAL, who + ": yuv_mode does not match the source format" + K::mode_hint(plan));
     }
-    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, c.frames)) return rc;
+    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, c.frames, K::esz)) return rc;
     std::vector<sjpeg_hip_ragged_frame> made(static_cast<size_t>(c.nframes));
     K::frames(plan, c.frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), made.data());
     unplace(c.out, &made);
@@ -223,7 +246,7 @@ int sheet_flow(const RaggedCall& c, const Shape& s) {
     // (the source frames' output ranges are not read: the sheets' are the call's)
     std::vector<sjpeg_hip_ragged_frame> src(c.frames, c.frames + c.nframes);
     for (sjpeg_hip_ragged_frame& f : src) { f.out_offset = 0; f.out_capacity = 0; }
-    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, src.data())) return rc;
+    if (int rc = ragged_check(who, c.format, source_mode(L), c.nframes, src.data(), K::esz)) return rc;
     const int ns = plan.nsheets;
     if (!o.packed && o.out_stride > UINT64_MAX / static_cast<uint64_t>(ns)) {
       return set_error(SJPEG_HIP_EINVAL, who + ": out_stride * nsheets overflows");
@@ -345,6 +368,24 @@ int sheet_colour_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const int32_t
   if (int rc = encode_prologue(c, true, sheet, true)) return rc;
   if (yuv_colour_all_identity(c.nframes, colour, colour_per_frame)) return sheet_entry(c, sheet, nullptr, sizes, orientations);
   return sheet_flow<SheetColourKind>(c, Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame});
+}
+
+// 16-bit samples: no pass-through -- the inner flow cannot read words, so every frame goes through the kernel, at its
+// own size and orientation 1 too.  colour NULL: none.
+int yuv16_entry(RaggedCall c, const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                const sjpeg_hip_yuv_depth* depth) {
+  c.who = &kYuv16[c.out.packed];
+  if (int rc = encode_prologue(c, false, nullptr, true)) return rc;
+  if (int rc = yuv_depth_check(*c.who, depth)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  return planned_flow<YuvDeepKind>(c, Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame, depth});
+}
+int sheet_yuv16_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations,
+                      const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth) {
+  c.who = &kSheetYuv16[c.out.packed];
+  if (int rc = encode_prologue(c, true, sheet, true)) return rc;
+  if (int rc = yuv_depth_check(*c.who, depth)) return rc;
+  return sheet_flow<SheetDeepKind>(c, Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame, depth});
 }
 
 }  // namespace
@@ -626,6 +667,78 @@ int sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src(sjpeg_hip_engine* e, int
   return sheet_colour_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                              RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet, sizes,
                             orientations, colour, colour_per_frame);
+}
+
+// ---- ... and 10-bit video: the YUV-plane formats with 16-bit samples (P010 and its kin, yuv420p10le / 12le) through the
+// kernel's deep instantiations; each entry its colour counterpart plus the depth
+int sjpeg_hip_convert_ragged_yuv16_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                       const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour,
+                                       int colour_per_frame, const sjpeg_hip_yuv_depth* depth, void* d_out, size_t out_bytes,
+                                       sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_convert_ragged_yuv16_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "converted planes", "sjpeg_hip_resize_ragged_yuv_bytes"};
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = yuv_depth_check(who, depth)) return rc;
+  return shape_body<YuvDeepKind>(who, w, e, format, nframes, frames,
+                                 Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame, depth}, false, d_out, out_bytes,
+                                 out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_yuv16_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                      const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth,
+                                      const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes,
+                                      float* q_out, float* value_out, void* stream) {
+  return yuv16_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      {d_out, d_sizes, modes, q_out, value_out, stream}}, sizes, orientations, colour, colour_per_frame, depth);
+}
+
+int sjpeg_hip_encode_ragged_yuv16_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                             const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                             const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth,
+                                             const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed, size_t packed_capacity,
+                                             uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                             void* stream) {
+  return yuv16_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                      RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes,
+                     orientations, colour, colour_per_frame, depth);
+}
+
+int sjpeg_hip_sheet_ragged_yuv16_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                     const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                     const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth,
+                                     void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames, int* nsheets, int* out_format,
+                                     void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_yuv16_src";
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = yuv_format_check(who, format)) return rc;
+  if (int rc = yuv_depth_check(who, depth)) return rc;
+  return shape_body<SheetDeepKind>(who, kSheetWords, e, format, nframes, frames,
+                                   Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame, depth},
+                                   sheet == nullptr || nsheets == nullptr, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_yuv16_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                            const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet, const int32_t (*sizes)[2],
+                                            const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                                            const sjpeg_hip_yuv_depth* depth, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                            void* d_out, size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                            void* stream) {
+  return sheet_yuv16_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                            RaggedOut{d_out, d_sizes, modes, q_out, value_out, stream}.strided_by(out_stride)}, sheet, sizes, orientations,
+                           colour, colour_per_frame, depth);
+}
+
+int sjpeg_hip_encode_ragged_sheet_yuv16_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                   const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                   const int32_t (*sizes)[2], const uint8_t* orientations,
+                                                   const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                                                   const sjpeg_hip_yuv_depth* depth, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                   int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_yuv16_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                            RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet,
+                           sizes, orientations, colour, colour_per_frame, depth);
 }
 
 }  // extern "C"

@@ -36,6 +36,17 @@
 // global load and the LDS store, a float pixel as its four elements become bytes --, so the staged bytes are those of
 // the flattened picture and everything behind the stage is as it is for SJPEG_HIP_SRC_RGB.  The sums are over bytes
 // b <= 255 as before: the 32-bit and 64-bit bounds above hold unchanged.
+//
+// Deep video (sjpeg_hip_convert_ragged_yuv16_src; sjpeg_hip.h, "10-bit video"): the DEEP instantiations of the YUV-plane
+// kernel read planes of little-endian 16-bit samples -- P010 and its kin, yuv420p10le / 12le.  A row's segment is staged
+// as the 16-bit elements it is, whole dwords and at most one trailing element, so the stage holds half as many samples:
+// 8192 of a one-channel plane, 4096 pairs of a P010 UV plane, and the chunked path starts at half the width.  The sum
+// loop reads uint16 from LDS: adjacent lanes still read adjacent samples, now two halves of one dword where four lanes
+// read the four bytes of one, so the 32 lanes the LDS serves together span twice as many banks as with bytes -- at
+// most 64 samples (P is the largest power of two in W / w', so 32 lanes' cells span less than 2 x 32 columns), 32
+// dwords: each in a bank of its own, as before.  A row's sum is at most 65535 W < 2^32 and a cell's 65535 W H < 2^48:
+// h stays 32 bits and acc 64.  A finished row is rounded ONCE, by resize_round_deep with the launch's shift, into the
+// byte tile; from there on nothing differs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -81,6 +92,7 @@ struct ResizeArgs {
 typedef uint32_t __attribute__((aligned(1))) Dword1;
 typedef const __attribute__((address_space(1))) Dword1* GlobalDwords;
 typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
+typedef const __attribute__((address_space(1))) uint16_t* GlobalWords;
 typedef __attribute__((address_space(1))) uint32_t* GlobalOut;
 typedef __attribute__((address_space(1))) uint8_t* GlobalOutBytes;
 
@@ -95,6 +107,23 @@ __device__ __forceinline__ void stage_bytes(const uint8_t* g, uint8_t* l, unsign
   for (unsigned i = lane; i < nd; i += lanes) ld[i] = gd[i];
   const unsigned i = (nd << 2) + lane;
   if (i < nb) l[i] = ((GlobalBytes)(g))[i];
+}
+
+// nw 16-bit samples of a source row at g (a multiple of 2) into LDS at l (a multiple of 4): whole dwords, then at most
+// one trailing sample -- every byte read is one of the 2 nw, and no dword reaches past the last sample
+__device__ __forceinline__ void stage_words(const uint8_t* g, uint8_t* l, unsigned nw, unsigned lane, unsigned lanes) {
+  const unsigned nd = nw >> 1;
+  GlobalDwords const gd = (GlobalDwords)(g);
+  uint32_t* const ld = reinterpret_cast<uint32_t*>(l);
+  for (unsigned i = lane; i < nd; i += lanes) ld[i] = gd[i];
+  if ((nw & 1u) != 0u && lane == 0u) reinterpret_cast<uint16_t*>(l)[nw - 1u] = ((GlobalWords)(g))[nw - 1u];
+}
+
+// a staged sample: a byte, or (deep) a 16-bit word
+template <bool kDeep>
+__device__ __forceinline__ uint32_t staged_sample(const uint8_t* p) {
+  if constexpr (kDeep) return *reinterpret_cast<const uint16_t*>(p);
+  else return *p;
 }
 
 // The flat instantiations' arguments: the launch's flatten, wave-uniform like the rest
@@ -128,9 +157,20 @@ struct YuvResizeArgs {
   const YuvPlane* planes;
   int nplanes;
 };
-template <bool kYuv, bool kFlat = false> struct ResizeArgsOf { typedef ResizeArgs type; };
-template <> struct ResizeArgsOf<true, false> { typedef YuvResizeArgs type; };
-template <> struct ResizeArgsOf<false, true> { typedef FlatResizeArgs type; };
+// ... and the deep instantiations': the launch's depth
+struct YuvDeepResizeArgs : YuvResizeArgs {
+  uint32_t shift;                // sjpeg_hip_yuv_depth: how many low bits of a word lie below the byte, 0..8
+};
+template <bool kYuv, bool kFlat = false, bool kDeep = false> struct ResizeArgsOf { typedef ResizeArgs type; };
+template <> struct ResizeArgsOf<true, false, false> { typedef YuvResizeArgs type; };
+template <> struct ResizeArgsOf<false, true, false> { typedef FlatResizeArgs type; };
+template <> struct ResizeArgsOf<true, false, true> { typedef YuvDeepResizeArgs type; };
+// a finished cell's sum rounded into its byte
+template <bool kDeep, class Args>
+__device__ __forceinline__ uint32_t round_sample(uint64_t S, uint32_t W, uint32_t H, const Args& a) {
+  if constexpr (kDeep) return sjpeg_internal::resize_round_deep(S, W, H, a.shift);
+  else return sjpeg_internal::resize_round(S, W, H);
+}
 __device__ __forceinline__ int desc_count(const ResizeArgs& a) { return a.nframes; }
 __device__ __forceinline__ int desc_count(const YuvResizeArgs& a) { return a.nplanes; }
 __device__ __forceinline__ const ResizeFrame& desc_at(const ResizeArgs& a, int i) { return a.frames[i]; }
@@ -147,9 +187,14 @@ __device__ __forceinline__ const ResizeFrame& desc_at(const YuvResizeArgs& a, in
 // kFlat: the frames are of an alpha format (BGRA / RGBA bytes: the packed class; float RGBA: the element class) and
 // are flattened as they are staged.  A compile-time flag again, with arguments of its own: the four instantiations
 // without it hold what they held before; there is no flat YUV instantiation.
-template <bool kYuv, bool kPlaced, bool kFlat = false>
-__global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv, kFlat>::type a) {
+// kDeep: the planes are of 16-bit samples (the YUV-plane formats alone).  A compile-time flag once more: what differs
+// is the staged element (esz bytes), the sample the sum loop reads and the rounding; the six instantiations without it
+// hold what they held before.
+template <bool kYuv, bool kPlaced, bool kFlat = false, bool kDeep = false>
+__global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv, kFlat, kDeep>::type a) {
   static_assert(!(kYuv && kFlat), "the YUV-plane formats have no alpha");
+  static_assert(kYuv || !kDeep, "16-bit samples: the YUV-plane formats alone");
+  constexpr unsigned esz = kDeep ? 2u : 1u;                        // bytes a staged sample
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
   const unsigned wg = blockIdx.x, tid = threadIdx.x;
@@ -186,15 +231,15 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   // The staged rows: packed pixels as they lie in memory, else a run of bytes per channel; `cap` pixels fit, a longer
   // segment goes in chunks of a single row
   const bool packed = cls == kResizePacked;
-  const unsigned lstep = packed ? pix_step : 1u;
-  const unsigned cap = packed ? kStageBytes / lstep : (kStageBytes / channels) & ~3u;
+  const unsigned lstep = (packed ? pix_step : 1u) * esz;
+  const unsigned cap = packed ? kStageBytes / lstep : (kStageBytes / (channels * esz)) & ~3u;
   const unsigned seg = xe - xs, clen_max = min(seg, cap);
-  const unsigned cpitch = packed ? 0u : align4(clen_max);
+  const unsigned cpitch = packed ? 0u : align4(clen_max * esz);
   const unsigned rpitch = packed ? align4(clen_max * lstep) : cpitch * channels;
   const unsigned R = seg > cap ? 1u : kStageBytes / rpitch;
   unsigned coff[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) coff[c] = packed ? static_cast<unsigned>(d.off[c]) : static_cast<unsigned>(c) * cpitch;
+  for (int c = 0; c < 3; ++c) coff[c] = packed ? static_cast<unsigned>(d.off[c]) * esz : static_cast<unsigned>(c) * cpitch;
   // who stages what: a wave a row, or the whole workgroup the one row of a chunk
   const unsigned slanes = R == 1u ? 256u : 64u, slane = tid & (slanes - 1u), srow = tid / slanes, srows = 256u / slanes;
 
@@ -236,13 +281,21 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
             }
           }
         } else if (packed) {
-          stage_bytes(row + static_cast<long long>(xc) * lstep, l, clen * lstep, slane, slanes);
+          if constexpr (kDeep) {
+            stage_words(row + static_cast<long long>(xc) * lstep, l, clen * 2u, slane, slanes);   // (a pair: one dword)
+          } else {
+            stage_bytes(row + static_cast<long long>(xc) * lstep, l, clen * lstep, slane, slanes);
+          }
         } else {
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             if (c >= static_cast<int>(channels)) continue;
             if (kYuv || cls == kResizePlanes) {
-              stage_bytes(row + d.off[c] + xc, l + c * cpitch, clen, slane, slanes);
+              if constexpr (kDeep) {
+                stage_words(row + (d.off[c] + static_cast<long long>(xc)) * 2, l + c * cpitch, clen, slane, slanes);
+              } else {
+                stage_bytes(row + d.off[c] + xc, l + c * cpitch, clen, slane, slanes);
+              }
               continue;
             }
             // the float formats element by element: never an element that is not a used sample of a pixel of the picture
@@ -263,9 +316,9 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
         for (uint32_t x = lo + p; x < hi; x += P) {
           const uint32_t w = resize_weight(ox0 + j, x, W, w2);
           const uint8_t* const px = stage + r * rpitch + (x - xc) * lstep;
-          h[0] += w * px[coff[0]];
-          if (three) { h[1] += w * px[coff[1]]; h[2] += w * px[coff[2]]; }
-          if (two) h[1] += w * px[coff[1]];
+          h[0] += w * staged_sample<kDeep>(px + coff[0]);
+          if (three) { h[1] += w * staged_sample<kDeep>(px + coff[1]); h[2] += w * staged_sample<kDeep>(px + coff[2]); }
+          if (two) h[1] += w * staged_sample<kDeep>(px + coff[1]);
         }
         if (!last) continue;
         for (unsigned m = P >> 1; m != 0u; m >>= 1) {
@@ -281,12 +334,12 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
           for (int c = 0; c < 3; ++c) acc[c] += static_cast<uint64_t>(wy) * h[c];
           if ((y + 1u) * h2 >= (yo + 1u) * H) {
             uint8_t* const o = tile + (yo - oy0) * tpitch + j * channels;
-            o[0] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[0], W, H));
+            o[0] = static_cast<uint8_t>(round_sample<kDeep>(acc[0], W, H, a));
             if (three) {
-              o[1] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[1], W, H));
-              o[2] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[2], W, H));
+              o[1] = static_cast<uint8_t>(round_sample<kDeep>(acc[1], W, H, a));
+              o[2] = static_cast<uint8_t>(round_sample<kDeep>(acc[2], W, H, a));
             }
-            if (two) o[1] = static_cast<uint8_t>(sjpeg_internal::resize_round(acc[1], W, H));
+            if (two) o[1] = static_cast<uint8_t>(round_sample<kDeep>(acc[1], W, H, a));
             ++yo;
             const uint32_t wn = yo < oy0 + th ? resize_weight(yo, y, H, h2) : 0u;
 #pragma unroll
@@ -455,6 +508,20 @@ int yuv_resize_ragged_placed_launch(const YuvPlane* d_planes, int nplanes, unsig
   a.planes = d_planes;
   a.nplanes = nplanes;
   hipLaunchKernelGGL((resize_ragged_kernel<true, true>), dim3(tiles), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the deep instantiations (16-bit samples, sjpeg_hip_yuv_depth's shift launch-wide), unplaced or placed
+int yuv_resize_ragged_deep_launch(bool placed, unsigned shift, const YuvPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st) {
+  YuvDeepResizeArgs a;
+  a.planes = d_planes;
+  a.nplanes = nplanes;
+  a.shift = shift;
+  if (placed) {
+    hipLaunchKernelGGL((resize_ragged_kernel<true, true, false, true>), dim3(tiles), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((resize_ragged_kernel<true, false, false, true>), dim3(tiles), dim3(256), 0, st, a);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

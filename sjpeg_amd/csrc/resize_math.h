@@ -44,6 +44,21 @@ SJPEG_RESIZE_HD inline uint32_t resize_round(uint64_t S, uint32_t W, uint32_t H)
   return static_cast<uint32_t>(q);
 }
 
+// The same for 16-bit samples whose byte lies `shift` = 0..8 bits up (sjpeg_hip_yuv_depth): min(255, floor((2 S +
+// A 2^s) / (A 2^(s+1)))), A = W H -- the exact average of the words, divided by 2^s, rounded half up ONCE, then
+// clamped (a full-scale picture gives 256 before the clamp).  S is at most 65535 A < 2^48, so the numerator is below
+// 2^50 and the divisor at most 2^41.  A quotient of 256 or more is decided by one compare of exact values (256 d <
+// 2^49); below that the quotient is at most 255 and the float estimate with its two exact compares is resize_round's,
+// bound for bound (q * d < 2^49).
+SJPEG_RESIZE_HD inline uint32_t resize_round_deep(uint64_t S, uint32_t W, uint32_t H, uint32_t shift) {
+  const uint64_t area = static_cast<uint64_t>(W) * H, d = (2u * area) << shift, n = 2u * S + (area << shift);
+  if (n >= 256u * d) return 255u;
+  uint64_t q = static_cast<uint64_t>(static_cast<float>(n) / static_cast<float>(d));
+  while (q * d > n) --q;
+  while ((q + 1u) * d <= n) ++q;
+  return static_cast<uint32_t>(q);
+}
+
 }  // namespace sjpeg_internal
 
 #endif  // SJPEG_AMD_RESIZE_MATH_H_

@@ -1413,9 +1413,10 @@ int ragged_format(const std::string& who, int format, int yuv_mode, ScanArgs* a,
 // Every frame of a ragged call of a known format checked (the message names the frame); its geometry into (*geo)[f].
 // out_ranges: the frames' output ranges are checked too (the encodes; the analysis passes ignore them).
 int ragged_frames(const std::string& who, int format, int yuv_mode, int nframes,
-                  const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo) {
+                  const sjpeg_hip_ragged_frame* frames, bool out_ranges, std::vector<FrameGeo>* geo, int esz = 0) {
   geo->resize(nframes);
-  const SourceLayout& L = *source_layout(format);
+  SourceLayout L = *source_layout(format);
+  if (esz != 0) L.esz = esz;                     // (the deep entries: the format's planes with samples of esz bytes)
   for (int f = 0; f < nframes; ++f) {
     const sjpeg_hip_ragged_frame& fr = frames[f];
     const std::string w = who + ": frame " + std::to_string(f) + ": ";
@@ -2083,13 +2084,13 @@ bool append_frame_header(int width, int height, int yuv_mode, const uint8_t quan
                                         fm != nullptr ? fm->block.size() : 0, headers);
 }
 
-int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames) {
+int ragged_check(const std::string& who, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames, int esz) {
   ScanArgs a;
   int cls = 0;
   const SourceLayout* layout = nullptr;
   std::vector<FrameGeo> geo;
   if (int rc = ragged_format(who, format, yuv_mode, &a, &cls, &layout)) return rc;
-  return ragged_frames(who, format, yuv_mode, nframes, frames, true, &geo);
+  return ragged_frames(who, format, yuv_mode, nframes, frames, true, &geo, esz);
 }
 size_t engine_scratch_limit(const sjpeg_hip_engine* e) { return e->scratch_limit; }
 int engine_device(const sjpeg_hip_engine* e) { return e->device; }
@@ -3594,7 +3595,8 @@ int sjpeg_internal::engine_yuv_resize(sjpeg_hip_engine* e, const std::string& wh
                                       void* stream) {
   return engine_make_pictures(e, who, "resized", plan.planes, plan.bytes, d_out, base, stream,
                               [&](const YuvPlane* d_planes, int n, hipStream_t st) {
-    if (yuv_resize_ragged_launch(d_planes, n, plan.tiles, st) != 0) {
+    if ((plan.deep ? yuv_resize_ragged_deep_launch(false, plan.shift, d_planes, n, plan.tiles, st)
+                   : yuv_resize_ragged_launch(d_planes, n, plan.tiles, st)) != 0) {
       return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
     }
     return 0;
@@ -3617,7 +3619,8 @@ int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, co
     rc = engine_make_pictures(e, who, "sheet", plan.planes.planes, plan.bytes, d_out, &sheets, stream,
                               [&](const YuvPlane* d_planes, int n, hipStream_t st) {
       if (int rcf = fill(st)) return rcf;
-      if (yuv_resize_ragged_placed_launch(d_planes, n, plan.planes.tiles, st) != 0) {
+      if ((plan.planes.deep ? yuv_resize_ragged_deep_launch(true, plan.planes.shift, d_planes, n, plan.planes.tiles, st)
+                            : yuv_resize_ragged_placed_launch(d_planes, n, plan.planes.tiles, st)) != 0) {
         return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
       }
       return 0;

@@ -51,7 +51,8 @@ int sheet_check(const std::string& who, const sjpeg_hip_sheet* sheet, int format
 }
 
 int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const sjpeg_hip_sheet* sheet,
-               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten) {
+               const int32_t (*sizes)[2], const uint8_t* orientations, SheetPlan* plan, const sjpeg_hip_flatten* flatten,
+               const sjpeg_hip_yuv_depth* depth) {
   int SW = 0, SH = 0;
   if (int rc = sheet_check(who, sheet, format, &SW, &SH)) return rc;
   const SourceLayout* const L = source_layout(format);
@@ -76,7 +77,7 @@ int sheet_plan(const std::string& who, int format, int nframes, const sjpeg_hip_
   }
   *plan = SheetPlan();
   if (yuv) {
-    if (int rc = yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan->planes)) return rc;
+    if (int rc = yuv_resize_plan(who, format, nframes, frames, sizes, orientations, &plan->planes, depth)) return rc;
   } else {
     if (int rc = resize_plan(who, format, nframes, frames, sizes, orientations, &plan->rgb, flatten)) return rc;
   }

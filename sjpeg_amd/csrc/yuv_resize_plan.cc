@@ -9,6 +9,7 @@
 #include "orient_math.h"
 #include "ragged_aux.h"
 #include "reduce_round.h"
+#include "resize_math.h"
 #include "sjpeg_hip.h"
 #include "source_layout.h"
 
@@ -35,9 +36,21 @@ int yuv_format_check(const std::string& who, int format) {
                                          "and turned by sjpeg_hip_orient_ragged_src and sjpeg_hip_encode_ragged_oriented_src)");
 }
 
+int yuv_depth_check(const std::string& who, const sjpeg_hip_yuv_depth* depth) {
+  if (depth == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": depth == NULL");
+  if (depth->bytes != 2) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": depth: bytes " + std::to_string(depth->bytes) + " is not 2 (samples of one byte go to the entries "
+                                           "without a depth)");
+  }
+  if (depth->shift > 8) return set_error(SJPEG_HIP_EINVAL, who + ": depth: shift " + std::to_string(depth->shift) + " is not one of 0..8");
+  if (depth->reserved[0] != 0 || depth->reserved[1] != 0) return set_error(SJPEG_HIP_EINVAL, who + ": depth: reserved must be 0");
+  return 0;
+}
+
 int yuv_resize_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
-                    const uint8_t* orientations, YuvResizePlan* plan) {
+                    const uint8_t* orientations, YuvResizePlan* plan, const sjpeg_hip_yuv_depth* depth) {
   if (int rc = yuv_format_check(who, format)) return rc;
+  if (depth != nullptr) { if (int rc = yuv_depth_check(who, depth)) return rc; }
   const SourceLayout* const L = source_layout(format);
   if (nframes < 1 || nframes > 65535) return set_error(SJPEG_HIP_EINVAL, who + ": nframes must be 1..65535");
   for (int f = 0; f < nframes; ++f) {
@@ -61,6 +74,8 @@ int yuv_resize_plan(const std::string& who, int format, int nframes, const sjpeg
   plan->format = format;
   plan->resized_format = L->implied == SJPEG_HIP_YUV444 ? SJPEG_HIP_SRC_YUV444 : SJPEG_HIP_SRC_YUV420;
   plan->nframes = nframes;
+  plan->deep = depth != nullptr;
+  plan->shift = depth != nullptr ? depth->shift : 0u;
   plan->planes.clear();
   plan->planes.reserve(static_cast<size_t>(nframes) * (semi ? 2 : 3));
   size_t at = 0;
@@ -138,6 +153,16 @@ void yuv_resize_plan_frames(const YuvResizePlan& plan, const sjpeg_hip_ragged_fr
 }  // namespace sjpeg_internal
 
 extern "C" {
+
+int sjpeg_hip_yuv16_samples(const sjpeg_hip_yuv_depth* depth, size_t n, const uint16_t* in, uint8_t* out) {
+  static const std::string who = "sjpeg_hip_yuv16_samples";
+  using sjpeg_internal::set_error;
+  if (int rc = sjpeg_internal::yuv_depth_check(who, depth)) return rc;
+  if (n != 0 && (in == nullptr || out == nullptr)) return set_error(SJPEG_HIP_EINVAL, who + ": in or out == NULL");
+  // (a one-sample picture: S = x, A = 1)
+  for (size_t i = 0; i < n; ++i) out[i] = static_cast<uint8_t>(sjpeg_internal::resize_round_deep(in[i], 1u, 1u, depth->shift));
+  return 0;
+}
 
 int sjpeg_hip_yuv_plane_size(int format, int width, int height, int plane, int* plane_width, int* plane_height) {
   static const std::string who = "sjpeg_hip_yuv_plane_size";

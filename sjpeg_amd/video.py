@@ -3,7 +3,13 @@ ragged call").  A JFIF file is full-range BT.601 YCbCr; a decoded H.264 or HEVC 
 studio range.  encode_yuv_frames / encode_yuv_sheets code the samples as they are; the calls here say what the SOURCE
 is -- a VideoColour, one for all frames or one per frame -- and the library converts the made thumbnails, not the
 sources, by one more launch behind the resize launch.  The arithmetic is exact and in integers: yuv_colour_samples is
-the formula on single samples."""
+the formula on single samples.
+
+10-bit video: convert_deep_frames, encode_deep_video_frames, make_deep_video_sheets and encode_deep_video_sheets are
+the same four calls on frames of 16-bit samples -- P010 as a GPU decoder writes HEVC Main10, AV1 10-bit and VP9
+profile 2, yuv420p10le / 12le as a software decoder does -- described by a VideoDepth.  The resize kernel reads the
+words, sums them exactly and rounds once into the 8-bit planes everything else works on; yuv16_samples is that formula
+on single samples.  No BT.2020 matrix and no PQ / HLG tone mapping: HDR frames are coded by their code values."""
 import ctypes as C
 
 import numpy as np
@@ -52,6 +58,41 @@ class VideoColour:
         return _ColourStruct(self.matrix, self.range)
 
 
+class _DepthStruct(C.Structure):
+    """struct sjpeg_hip_yuv_depth"""
+    _fields_ = [("bytes", C.c_uint8), ("shift", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class VideoDepth:
+    """How the 16-bit samples of a deep frame carry their value: `bits` significant bits (8..16), align "msb" -- in the
+    word's high bits, as P010 / P012 / P016 -- or "lsb" -- in its low bits, as yuv420p10le.  The library is told bytes
+    = 2 and shift = the low bits of a word that lie below the made byte: 8 for "msb", bits - 8 for "lsb".
+    VideoDepth.P010, .P016, .YUV10 and .YUV12 are the usual four."""
+
+    def __init__(self, bits=10, align="msb"):
+        if isinstance(bits, bool) or not isinstance(bits, int) or not 8 <= bits <= 16:
+            raise SjpegError(f"VideoDepth: bits {bits!r} is not one of 8..16")
+        if align not in ("msb", "lsb"):
+            raise SjpegError(f"VideoDepth: align {align!r} is not 'msb' or 'lsb'")
+        self.bits, self.align = bits, align
+        self.bytes, self.shift = 2, 8 if align == "msb" else bits - 8
+
+    def __eq__(self, other):
+        return isinstance(other, VideoDepth) and (self.bits, self.align) == (other.bits, other.align)
+
+    def __hash__(self):
+        return hash((self.bits, self.align))
+
+    def __repr__(self):
+        return "VideoDepth(%d, %r)" % (self.bits, self.align)
+
+    def _struct(self):
+        return _DepthStruct(self.bytes, self.shift)
+
+
+VideoDepth.P010, VideoDepth.P016 = VideoDepth(10, "msb"), VideoDepth(16, "msb")
+VideoDepth.YUV10, VideoDepth.YUV12 = VideoDepth(10, "lsb"), VideoDepth(12, "lsb")
+
 _bound = False
 
 
@@ -77,6 +118,17 @@ def _lib():
         plain = list(getattr(L, f"sjpeg_hip_encode_ragged_sheet{packed}_src").argtypes)          # (..., params, sheet, sizes, orientations, meta, ...)
         fn = getattr(L, f"sjpeg_hip_encode_ragged_sheet_yuv_colour{packed}_src")
         fn.restype, fn.argtypes = C.c_int, plain[:8] + colour + plain[8:]
+    # the deep entries: their colour counterparts with the depth behind the colour
+    L.sjpeg_hip_yuv16_samples.restype = C.c_int
+    L.sjpeg_hip_yuv16_samples.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    for stem, deep, at in (("convert_ragged_yuv", "convert_ragged_yuv16", 8), ("sheet_ragged_yuv_colour", "sheet_ragged_yuv16", 9),
+                           ("encode_ragged_yuv_converted", "encode_ragged_yuv16", 9),
+                           ("encode_ragged_yuv_converted_packed", "encode_ragged_yuv16_packed", 9),
+                           ("encode_ragged_sheet_yuv_colour", "encode_ragged_sheet_yuv16", 10),
+                           ("encode_ragged_sheet_yuv_colour_packed", "encode_ragged_sheet_yuv16_packed", 10)):
+        plain = list(getattr(L, f"sjpeg_hip_{stem}_src").argtypes)
+        fn = getattr(L, f"sjpeg_hip_{deep}_src")
+        fn.restype, fn.argtypes = C.c_int, plain[:at] + [C.c_void_p] + plain[at:]
     _bound = True
     return L
 
@@ -130,14 +182,77 @@ def _size_list(who, n, dims, sizes, box, orientations):
             for k, (w, h) in enumerate(dims)]
 
 
+def _deep_frames(who, frames, fmt):
+    """sj._yuv_frames for frames of 16-bit samples: every plane a CUDA tensor of a 2-byte integer dtype (the bits are read
+    as unsigned) [rows, samples] with stride 1 along a row; the UV plane of SRC_NV12 / SRC_NV21 may be [rows, pairs, 2]"""
+    import torch
+    frames = [tuple(fr) for fr in frames]
+    if not frames:
+        raise SjpegError(f"{who}: no frames")
+    nplanes = 2 if fmt in (SRC_NV12, sj.SRC_NV21) else 3 if fmt in (sj.SRC_YUV420, SRC_YUV444) else 0
+    if nplanes == 0:
+        raise SjpegError(f"{who}: fmt {fmt} is not SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444")
+    for k, fr in enumerate(frames):
+        if len(fr) != nplanes:
+            raise SjpegError(f"{who}: frame {k} has {len(fr)} planes, the format takes {nplanes}")
+        for i, p in enumerate(fr):
+            ok = isinstance(p, torch.Tensor) and p.is_cuda and p.element_size() == 2 and not p.is_floating_point() and not p.is_complex()
+            pair = ok and nplanes == 2 and i == 1 and p.dim() == 3 and p.shape[2] == 2 and p.stride(2) == 1 and p.stride(1) == 2
+            if not ok or not (pair or (p.dim() == 2 and p.stride(1) == 1)):
+                raise SjpegError(f"{who}: frame {k}: a plane is a CUDA tensor of a 2-byte integer dtype [rows, samples] with stride 1 along "
+                                 "a row (the UV plane of a semi-planar format may be [rows, pairs, 2])")
+    return [list(fr) for fr in frames], [(int(fr[0].shape[1]), int(fr[0].shape[0])) for fr in frames], frames[0][0].device
+
+
+def _read_frames(who, frames, fmt, depth):
+    """(planes, dims, device, the depth's struct or None, what stands behind the colour in the C call) of a call's frames:
+    bytes (depth None) or 16-bit samples"""
+    if depth is None:
+        return sj._yuv_frames(who, frames, fmt) + (None, [])
+    if not isinstance(depth, VideoDepth):
+        raise SjpegError(f"{who}: depth {depth!r} is not a VideoDepth")
+    st = depth._struct()
+    return _deep_frames(who, frames, fmt) + (st, [C.addressof(st)])
+
+
+def yuv16_samples(words, depth=VideoDepth.P010):
+    """sjpeg_hip_yuv16_samples: what a deep call makes of a sample at the frame's own size, host only: words, an array
+    of a 2-byte integer dtype (the bits are read as unsigned), to uint8 of the same shape: min(255, (x + 2^(s-1)) >> s)."""
+    who = "yuv16_samples"
+    if not isinstance(depth, VideoDepth):
+        raise SjpegError(f"{who}: depth {depth!r} is not a VideoDepth")
+    src = np.ascontiguousarray(words)
+    if src.dtype.kind not in "iu" or src.dtype.itemsize != 2:
+        raise SjpegError(f"{who}: words is an array of a 2-byte integer dtype")
+    src = src.view(np.uint16)
+    out = np.empty(src.shape, np.uint8)
+    st = depth._struct()
+    if _lib().sjpeg_hip_yuv16_samples(C.addressof(st), src.size, src.ctypes.data, out.ctypes.data) != 0:
+        raise SjpegError(f"sjpeg_hip_yuv16_samples failed: {sj.last_error()}")
+    return out
+
+
 def convert_yuv_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, box=None, orientations=None, engine=None, out=None):
     """sjpeg_hip_convert_ragged_yuv_src: the planes Engine.resize_ragged_yuv makes of the frames (frames, fmt, sizes /
     box, orientations as encode_video_frames), converted from `colour` to JFIF's in place by one more launch.  Returns
     (out_fmt, pictures, buf) as resize_ragged_yuv: picture k a tuple (y, u, v) of uint8 views into buf, which any ragged
     entry takes as SRC_YUV420 / SRC_YUV444 planes.  Asynchronous on the current torch stream."""
+    return _convert("convert_yuv_frames", frames, fmt, colour, sizes, box, orientations, engine, out, None)
+
+
+def convert_deep_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, box=None, orientations=None, engine=None, out=None,
+                        depth=VideoDepth.P010):
+    """sjpeg_hip_convert_ragged_yuv16_src: convert_yuv_frames of frames of 16-bit samples (depth: a VideoDepth) -- planes
+    of any 2-byte integer dtype, the UV plane of P010 [rows, pairs, 2] or [rows, 2 * pairs].  The made planes are uint8:
+    every sample the exact area average of the words, divided by 2^shift and rounded half up once, clamped to 255; then
+    converted from `colour` (None: not at all).  Every frame goes through the kernel, at its own size too."""
+    return _convert("convert_deep_frames", frames, fmt, colour, sizes, box, orientations, engine, out, depth)
+
+
+def _convert(who, frames, fmt, colour, sizes, box, orientations, engine, out, depth):
     import torch
-    who = "convert_yuv_frames"
-    planes, dims, dev = sj._yuv_frames(who, frames, fmt)
+    planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
+    symbol = "sjpeg_hip_convert_ragged_yuv16_src" if deep else "sjpeg_hip_convert_ragged_yuv_src"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     sizes = _size_list(who, n, dims, sizes, box, orientations)
@@ -153,9 +268,8 @@ def convert_yuv_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, b
         out = sj._made_out(who, planes, need, out)
         made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        eng._chk(L.sjpeg_hip_convert_ragged_yuv_src(eng._h, fmt, n, cframes, sj._address(arr), sj._address(oarr), caddr, per_frame,
-                                                    out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), eng._stream()),
-                 "sjpeg_hip_convert_ragged_yuv_src")
+        eng._chk(getattr(L, symbol)(eng._h, fmt, n, cframes, sj._address(arr), sj._address(oarr), caddr, per_frame, *deep,
+                                    out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), eng._stream()), symbol)
     return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
 
 
@@ -163,9 +277,19 @@ def make_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), si
     """sjpeg_hip_sheet_ragged_yuv_colour_src: the uint8 contact sheets Engine.sheet_ragged makes of the frames, the
     thumbnails' rectangles converted from `colour` to JFIF's, the background as given.  Returns (out_fmt, sheets, buf):
     sheet s a tuple (y, u, v) of uint8 views into buf."""
+    return _make_sheets("make_video_sheets", frames, fmt, sheet, colour, sizes, orientations, engine, out, None)
+
+
+def make_deep_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), sizes=None, orientations=None, engine=None, out=None,
+                           depth=VideoDepth.P010):
+    """sjpeg_hip_sheet_ragged_yuv16_src: make_video_sheets of frames of 16-bit samples, as convert_deep_frames reads them."""
+    return _make_sheets("make_deep_video_sheets", frames, fmt, sheet, colour, sizes, orientations, engine, out, depth)
+
+
+def _make_sheets(who, frames, fmt, sheet, colour, sizes, orientations, engine, out, depth):
     import torch
-    who = "make_video_sheets"
-    planes, dims, dev = sj._yuv_frames(who, frames, fmt)
+    planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
+    symbol = "sjpeg_hip_sheet_ragged_yuv16_src" if deep else "sjpeg_hip_sheet_ragged_yuv_colour_src"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     if sizes is not None and len(sizes) != n:
@@ -183,9 +307,9 @@ def make_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), si
         made = (RaggedFrame * max((n + per - 1) // per, 1))()
         ns, rfmt = C.c_int(0), C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        eng._chk(L.sjpeg_hip_sheet_ragged_yuv_colour_src(eng._h, fmt, n, cframes, C.addressof(st), sj._address(arr), sj._address(oarr), caddr,
-                                                         per_frame, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns),
-                                                         C.byref(rfmt), eng._stream()), "sjpeg_hip_sheet_ragged_yuv_colour_src")
+        eng._chk(getattr(L, symbol)(eng._h, fmt, n, cframes, C.addressof(st), sj._address(arr), sj._address(oarr), caddr, per_frame, *deep,
+                                    out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt), eng._stream()),
+                 symbol)
     return int(rfmt.value), sj._frame_views(out, list(made)[:ns.value], rfmt.value), out
 
 
@@ -196,9 +320,25 @@ def encode_video_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, 
     upright and converted to JFIF's full-range BT.601 inside the one ragged call; frame k's JPEG is byte for byte what
     encode_yuv_frames makes of the planes convert_yuv_frames returns.  VideoColour("bt601", "full") for every frame is
     exactly encode_yuv_frames.  Returns the JPEGs (list of bytes)."""
+    return _encode_frames("encode_video_frames", frames, fmt, colour, sizes, box, orientations, quality, method, target_size, target_psnr,
+                          packed, metadata, engine, None)
+
+
+def encode_deep_video_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, box=None, orientations=None, quality=75.0,
+                             method=4, target_size=None, target_psnr=None, packed=False, metadata=None, engine=None,
+                             depth=VideoDepth.P010):
+    """The thumbnail call for 10-bit video: encode_video_frames of frames of 16-bit samples as the decoder wrote them
+    (depth: a VideoDepth; planes as convert_deep_frames takes them), with no narrowing pass in front.  Frame k's JPEG is
+    byte for byte what encode_yuv_frames makes of the planes convert_deep_frames returns.  colour None: no conversion."""
+    return _encode_frames("encode_deep_video_frames", frames, fmt, colour, sizes, box, orientations, quality, method, target_size,
+                          target_psnr, packed, metadata, engine, depth)
+
+
+def _encode_frames(who, frames, fmt, colour, sizes, box, orientations, quality, method, target_size, target_psnr, packed, metadata, engine,
+                   depth):
     import torch
-    who = "encode_video_frames"
-    planes, dims, dev = sj._yuv_frames(who, frames, fmt)
+    planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
+    stem = "sjpeg_hip_encode_ragged_yuv16" if deep else "sjpeg_hip_encode_ragged_yuv_converted"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     sizes = _size_list(who, n, dims, sizes, box, orientations)
@@ -214,14 +354,14 @@ def encode_video_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, 
     with torch.cuda.device(dev):
         call = eng._oriented_call(who, planes, dims, sizes, orientations, yuv_mode, sj._quality_quant(qs), method, None, 0x78, 12, 1,
                                   search, None, metadata)
-        special = (call.sizes, call.orientations, caddr, per_frame)
+        special = (call.sizes, call.orientations, caddr, per_frame, *deep)
         if packed:
             out, packed_capacity, meta = sj._packed_out(who, n, planes, call.capacities, None, None)
-            eng._packed("sjpeg_hip_encode_ragged_yuv_converted_packed_src", fmt, planes, dims, call, special, out, packed_capacity, meta)
+            eng._packed(stem + "_packed_src", fmt, planes, dims, call, special, out, packed_capacity, meta)
             eng.wait()
             return sj._fetch_packed(out, meta[:n], meta[n:], n, "frame")
         cframes, out, sizes_out, offsets = sj._ragged_frames(planes, dims, call.capacities, None, None, None)
-        out, sz, offs = eng._unpacked("sjpeg_hip_encode_ragged_yuv_converted_src", fmt, cframes, call, special, out, sizes_out, offsets)[:3]
+        out, sz, offs = eng._unpacked(stem + "_src", fmt, cframes, call, special, out, sizes_out, offsets)[:3]
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return sj._fetch_ragged(out, sz, offs)
 
@@ -231,9 +371,23 @@ def encode_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), 
     """encode_yuv_sheets WITH the colour put right: its arguments plus colour, one VideoColour or one per frame.  Only
     the thumbnails' rectangles are converted; the Sheet's background stays as given, (Y, U, V) in JFIF's colour.
     Returns (JPEGs, places) as encode_yuv_sheets."""
+    return _encode_sheets("encode_video_sheets", frames, fmt, sheet, colour, sizes, orientations, quality, method, target_size, target_psnr,
+                          packed, metadata, engine, None)
+
+
+def encode_deep_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), sizes=None, orientations=None, quality=75.0,
+                             method=4, target_size=None, target_psnr=None, packed=False, metadata=None, engine=None,
+                             depth=VideoDepth.P010):
+    """encode_video_sheets of frames of 16-bit samples, as encode_deep_video_frames reads them."""
+    return _encode_sheets("encode_deep_video_sheets", frames, fmt, sheet, colour, sizes, orientations, quality, method, target_size,
+                          target_psnr, packed, metadata, engine, depth)
+
+
+def _encode_sheets(who, frames, fmt, sheet, colour, sizes, orientations, quality, method, target_size, target_psnr, packed, metadata, engine,
+                   depth):
     import torch
-    who = "encode_video_sheets"
-    planes, dims, dev = sj._yuv_frames(who, frames, fmt)
+    planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
+    stem = "sjpeg_hip_encode_ragged_sheet_yuv16" if deep else "sjpeg_hip_encode_ragged_sheet_yuv_colour"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     keep, caddr, per_frame = _colour_args(who, n, colour)
@@ -250,20 +404,20 @@ def encode_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), 
     with torch.cuda.device(dev):
         ns, call, special = eng._sheet_call(who, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, sj._quality_quant(qs), int(method),
                                             None, 0x78, 12, 1, search, metadata)
-        special += [caddr, per_frame]
+        special += [caddr, per_frame, *deep]
         cframes, _, _, _ = sj._ragged_frames(planes, dims, None, None, None, None)
         if packed:
             out, packed_capacity, meta = sj._packed_out(who, ns, planes, call.capacities, None, None)
-            eng._chk(L.sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src(
+            eng._chk(getattr(L, stem + "_packed_src")(
                 eng._h, fmt, n, cframes, call.params, *special, *call.meta, out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns,
-                meta.data_ptr(), *call.results, eng._stream()), "sjpeg_hip_encode_ragged_sheet_yuv_colour_packed_src")
+                meta.data_ptr(), *call.results, eng._stream()), stem + "_packed_src")
             eng.wait()
             return sj._fetch_packed(out, meta[:ns], meta[ns:], ns, "sheet"), places
         out_stride = (call.capacities[0] + 15) & ~15
         out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
         sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
-        eng._chk(L.sjpeg_hip_encode_ragged_sheet_yuv_colour_src(
+        eng._chk(getattr(L, stem + "_src")(
             eng._h, fmt, n, cframes, call.params, *special, *call.meta, out.data_ptr(), out_stride, sizes_out.data_ptr(), *call.results,
-            eng._stream()), "sjpeg_hip_encode_ragged_sheet_yuv_colour_src")
+            eng._stream()), stem + "_src")
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return sj._fetch_ragged(out, sizes_out, [s * out_stride for s in range(ns)]), places
