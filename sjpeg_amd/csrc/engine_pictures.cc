@@ -1,0 +1,132 @@
+// engine_pictures.cc -- the engine's half of the entries that MAKE pictures for a ragged call: reduction, resize, the
+// YUV-plane resize, contact sheets and the video colour conversion.  The plans come from the *_plan.cc files, the kernels
+// and their launch functions live in reduce.hip, resize.hip and yuv_colour.hip (ragged_aux.h); here the call is ordered
+// behind the engine's earlier work, the engine's memory is sized and the descriptors go up.  Host only.
+#include "engine.h"
+
+using namespace sjpeg_internal;
+
+// ---- ragged reduction and resize (reduce.hip, resize.hip).  The two share the engine's memory for the pictures they
+// make and for their descriptors; `launch` starts the kernel over the uploaded descriptors.
+template <class Frame>
+static void picture_rebase(Frame& d, uint8_t* base) { d.dst = base + reinterpret_cast<uintptr_t>(d.dst); }
+static void picture_rebase(sjpeg_internal::YuvPlane& p, uint8_t* base) {
+  p.r.dst = base + reinterpret_cast<uintptr_t>(p.r.dst);
+  if (p.channels == 2) p.dst2 = base + reinterpret_cast<uintptr_t>(p.dst2);
+}
+
+template <class Frame, class Launch>
+static int engine_make_pictures(sjpeg_hip_engine* e, const std::string& who, const char* what, std::vector<Frame> desc, size_t bytes,
+                                uint8_t* d_pictures, uint8_t** base, void* stream, Launch launch) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ragged_ordered(e, st)) return rc;
+  if (d_pictures == nullptr) {
+    if (e->reduced.ensure(bytes / 16 + 1) != 0) {
+      return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(bytes) + " bytes of " + what + " pictures");
+    }
+    d_pictures = reinterpret_cast<uint8_t*>(e->reduced.p);
+  }
+  if (base != nullptr) *base = d_pictures;
+  for (Frame& d : desc) picture_rebase(d, d_pictures);
+  const size_t desc_bytes = sizeof(Frame) * desc.size();
+  if (int rc = e->reduce_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (int rc = upload(e, e->reduce_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  return launch(reinterpret_cast<const Frame*>(e->reduce_desc.p), static_cast<int>(desc.size()), st);
+}
+
+int sjpeg_internal::engine_reduce(sjpeg_hip_engine* e, const std::string& who, const ReducePlan& plan, uint8_t* d_reduced, uint8_t** base,
+                                  void* stream) {
+  return engine_make_pictures(e, who, "reduced", plan.frames, plan.bytes, d_reduced, base, stream,
+                              [&](const ReduceFrame* d_frames, int n, hipStream_t st) {
+    if (reduce_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": reduce_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
+int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base,
+                                  void* stream) {
+  return engine_make_pictures(e, who, "resized", plan.frames, plan.bytes, d_resized, base, stream,
+                              [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
+    const int rc = plan.flat ? resize_ragged_flat_launch(false, plan.format, e->pscale, e->pbias, plan.flatten, d_frames, n, plan.tiles, st)
+                             : resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st);
+    if (rc != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
+// ... and of the YUV-plane formats: a descriptor per plane, the kernel's other instantiation
+int sjpeg_internal::engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base,
+                                      void* stream) {
+  return engine_make_pictures(e, who, "resized", plan.planes, plan.bytes, d_out, base, stream,
+                              [&](const YuvPlane* d_planes, int n, hipStream_t st) {
+    if ((plan.deep ? yuv_resize_ragged_deep_launch(false, plan.shift, d_planes, n, plan.tiles, st)
+                   : yuv_resize_ragged_launch(d_planes, n, plan.tiles, st)) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
+// ... and of the contact sheets (sheet_plan.cc): the background of every sheet, then the placed descriptors of either
+// plan, both on the call's stream -- stream order is the only ordering relied on
+int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, const SheetPlan& plan, uint8_t* d_out, uint8_t** base,
+                                 void* stream) {
+  uint8_t* sheets = nullptr;
+  auto fill = [&](hipStream_t st) {
+    if (sheet_fill_launch(plan.fill, sheets, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": sheet_fill_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  };
+  int rc;
+  if (plan.yuv) {
+    rc = engine_make_pictures(e, who, "sheet", plan.planes.planes, plan.bytes, d_out, &sheets, stream,
+                              [&](const YuvPlane* d_planes, int n, hipStream_t st) {
+      if (int rcf = fill(st)) return rcf;
+      if ((plan.planes.deep ? yuv_resize_ragged_deep_launch(true, plan.planes.shift, d_planes, n, plan.planes.tiles, st)
+                            : yuv_resize_ragged_placed_launch(d_planes, n, plan.planes.tiles, st)) != 0) {
+        return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+      }
+      return 0;
+    });
+  } else {
+    rc = engine_make_pictures(e, who, "sheet", plan.rgb.frames, plan.bytes, d_out, &sheets, stream,
+                              [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
+      if (int rcf = fill(st)) return rcf;
+      const int rcl = plan.rgb.flat ? resize_ragged_flat_launch(true, plan.format, e->pscale, e->pbias, plan.rgb.flatten, d_frames, n, plan.rgb.tiles, st)
+                                    : resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st);
+      if (rcl != 0) {
+        return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+      }
+      return 0;
+    });
+  }
+  if (base != nullptr) *base = sheets;
+  return rc;
+}
+
+// ... and of the video colour conversion (yuv_colour_plan.cc): the launch behind the resize launch of the same call, on
+// the same stream, over the planes that one made at `base`
+int sjpeg_internal::engine_yuv_colour(sjpeg_hip_engine* e, const std::string& who, const YuvColourPlan& plan, uint8_t* base, void* stream) {
+  if (plan.tiles == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<YuvColourFrame> desc = plan.frames;
+  for (YuvColourFrame& d : desc) {
+    d.y = base + reinterpret_cast<uintptr_t>(d.y);
+    d.u = base + reinterpret_cast<uintptr_t>(d.u);
+    d.v = base + reinterpret_cast<uintptr_t>(d.v);
+  }
+  const size_t desc_bytes = sizeof(YuvColourFrame) * desc.size();
+  if (int rc = e->colour_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (int rc = upload(e, e->colour_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (yuv_colour_launch(plan.placed, reinterpret_cast<const YuvColourFrame*>(e->colour_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, who + ": yuv_colour_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
+}

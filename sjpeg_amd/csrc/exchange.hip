@@ -1,6 +1,7 @@
 // exchange.hip -- the exchange step of the multi-device batch path behind include/sjpeg_hip.h:
 // communicators and sjpeg_hip_gather_streams() on RCCL (xGMI inside a node).  The reference is
 // single-threaded and single-device: no counterpart there (BASELINE.json config #4).
+// At the end of the file: sjpeg_hip_compact_streams(), the kernel that puts a call's coded frames back to back for it.
 // RCCL is resolved at run time with dlopen / dlsym -- the library carries no link dependency on the
 // 570 MB librccl, and a process that never gathers never loads it.
 // A communicator carries the table of transport functions it was made with: RCCL's (one process per GPU), or
@@ -586,6 +587,66 @@ int sjpeg_hip_gather_streams(sjpeg_hip_comm* c, int root, const void* d_packed, 
                                           " bytes to gather, capacity " + std::to_string(gathered_capacity) + " -- nothing was sent");
   }
   return sjpeg_hip_gather_bytes(c, root, d_packed, per_max, h_rows, h_rank_offsets, d_gathered, gathered_capacity, stream);
+}
+
+// ---- exchange step of the multi-device batch path: the coded frames of one call, back to back ----
+// (BASELINE.json config #4; the reference is single-threaded and has no counterpart.)  One
+// launch, no host round trip: every workgroup sums the (16-byte aligned) sizes of the frames in
+// front of its own and copies 16 bytes per thread.
+
+__global__ __launch_bounds__(256) void compact_streams_kernel(const uint8_t* out, size_t out_stride, const unsigned long long* sizes,
+                                                              int nframes, uint8_t* packed, unsigned long long capacity,
+                                                              unsigned long long* offsets) {
+  const int f = blockIdx.y, tid = threadIdx.x;
+  __shared__ unsigned long long part[4];
+  unsigned long long s = 0;
+  for (int g = tid; g < f; g += 256) s += (sizes[g] + 15ull) & ~15ull;
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  if ((tid & 63) == 0) part[tid >> 6] = s;
+  __syncthreads();
+  const unsigned long long off = part[0] + part[1] + part[2] + part[3];
+  const unsigned long long n = sizes[f], n16 = (n + 15ull) & ~15ull;
+  if (blockIdx.x == 0 && tid == 0) {
+    offsets[f] = off;
+    // bytes needed, whether they fit or not; bit 63 says they did not (SJPEG_HIP_PACKED_OVERFLOW: the exchange
+    // reads it in the rank's row and refuses on every rank)
+    if (f == nframes - 1) offsets[nframes] = (off + n16) | (off + n16 > capacity ? (1ull << 63) : 0ull);
+  }
+  if (off + n16 > capacity) return;                            // the caller sees it in offsets[nframes]
+  const uint4* const src = reinterpret_cast<const uint4*>(out + static_cast<size_t>(f) * out_stride);
+  uint4* const dst = reinterpret_cast<uint4*>(packed + off);
+  const size_t nch = static_cast<size_t>(n16 >> 4);
+  for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + tid; i < nch; i += static_cast<size_t>(gridDim.x) * 256) {
+    uint4 v = src[i];
+    if (i == nch - 1 && (n & 15ull) != 0ull) {                 // zero the padding behind the last byte
+      uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      const uint32_t keep = static_cast<uint32_t>(n & 15ull);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t lo = 4u * k;
+        w[k] = keep <= lo ? 0u : (keep >= lo + 4u ? w[k] : (w[k] & ((1u << (8u * (keep - lo))) - 1u)));
+      }
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    dst[i] = v;
+  }
+}
+
+int sjpeg_hip_compact_streams(const void* d_out, size_t out_stride, const uint64_t* d_sizes, int nframes,
+                              void* d_packed, size_t packed_capacity, uint64_t* d_offsets, void* stream) {
+  if (d_out == nullptr || d_sizes == nullptr || d_packed == nullptr || d_offsets == nullptr) {
+    return xfail(SJPEG_HIP_EINVAL, "sjpeg_hip_compact_streams: NULL argument");
+  }
+  if (nframes <= 0 || nframes > 65535) return xfail(SJPEG_HIP_EINVAL, "sjpeg_hip_compact_streams: nframes must be 1 .. 65535");
+  if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_packed) & 15u) != 0 || (out_stride & 15u) != 0) {
+    return xfail(SJPEG_HIP_EINVAL, "sjpeg_hip_compact_streams: d_out, d_packed and out_stride must be multiples of 16");
+  }
+  hipLaunchKernelGGL(compact_streams_kernel, dim3(64, nframes), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const uint8_t*>(d_out), out_stride, reinterpret_cast<const unsigned long long*>(d_sizes), nframes,
+                     static_cast<uint8_t*>(d_packed), static_cast<unsigned long long>(packed_capacity),
+                     reinterpret_cast<unsigned long long*>(d_offsets));
+  XHIP_TRY(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// ragged_aux.h -- what the ragged riskiness and sharp conversions (riskiness.hip, sharp_yuv.hip) and the search
-// (ragged_full.cc) share with the engine's ragged entry points (scan_engine.hip).  Internal: not part of
-// include/sjpeg_hip.h.
+// ragged_aux.h -- what the ragged riskiness and sharp conversions (riskiness.hip, sharp_yuv.hip), the picture-making
+// kernels and their plans, and the search (ragged_full.cc) share with the engine's ragged launch layer (scan_engine.hip)
+// and the flows over it (ragged_flows.cc, engine_pictures.cc).  Internal: not part of include/sjpeg_hip.h.  The files
+// that need the engine object itself include engine.h, which includes this.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -17,15 +18,15 @@
 
 namespace sjpeg_internal {
 
-// ---- sizes and mode helpers the ragged flows share (scan_engine.hip, ragged_full.cc)
+// ---- sizes and mode helpers the ragged flows share (ragged_flows.cc, ragged_full.cc)
 // a frame's share of device scratch: its kept histogram, its adaptation sums and totals (adapt_sums_kernel: [2][64]
 // [deltas][2] int64, [2][64][2] int32), its symbol counts; a segment's partial of the statistics pass and its kept blocks
-// (9 rows of 16 bytes for each of the workgroup's 256 threads: scan_engine.hip asserts it against scan_device.h's
-// kKeptSegWords)
+// (9 rows of 16 bytes for each of the workgroup's 256 threads), a persistent group's partial of the histogram pass (16-bit
+// counters [2][64][128]): scan_engine.hip asserts the three against the kernels' constants
 constexpr size_t kHist = 2 * 64 * 128 * sizeof(uint32_t);
 constexpr size_t kSums = 2 * 64 * sjpeg_host::kAdaptDeltas * 2 * sizeof(int64_t), kTot = 2 * 64 * 2 * sizeof(int32_t);
 constexpr size_t kFreq = 2 * 272 * sizeof(uint32_t), kStatsPartial = kFreq;
-constexpr size_t kKeptSegBytes = 256 * 9 * 16;
+constexpr size_t kKeptSegBytes = 256 * 9 * 16, kHistPartial = 2 * 64 * 128 * sizeof(uint16_t);
 
 // SjpegYUVMode (include/sjpeg.h); 1, 3 and 4 are SJPEG_HIP_YUV420 / 444 / 400
 enum { kYuvAuto = 0, kYuv420 = 1, kYuvSharp = 2, kYuv444 = 3, kYuv400 = 4 };
@@ -121,7 +122,7 @@ void reduce_plan_frames(const ReducePlan& plan, const sjpeg_hip_ragged_frame* fr
 // the flat grid over d_frames[nframes] (device memory, dst already absolute)
 int reduce_ragged_launch(int format, const float* pscale, const float* pbias, const ReduceFrame* d_frames, int nframes, unsigned tiles,
                          hipStream_t st);
-// The engine's half (scan_engine.hip): the call ordered behind the engine's earlier work, the descriptors uploaded, the
+// The engine's half (engine_pictures.cc): the call ordered behind the engine's earlier work, the descriptors uploaded, the
 // kernel launched on `stream`.  d_reduced == NULL: into the engine's own memory for reduced pictures -- one allocation
 // of plan.bytes, apart from the arena of the sharp planes, counted by sjpeg_hip_engine_scratch_bytes and released by
 // sjpeg_hip_engine_trim; *base says where.
@@ -180,7 +181,7 @@ int resize_ragged_launch(int format, const float* pscale, const float* pbias, co
 // ... of a flat plan (placed: a sheet's descriptors)
 int resize_ragged_flat_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten& flatten,
                               const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
-// The engine's half (scan_engine.hip), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
+// The engine's half (engine_pictures.cc), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
 // pictures (the two kinds of call share it and its descriptors' buffer).  A flat plan runs the flat launch.
 int engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base, void* stream);
 
@@ -306,7 +307,7 @@ bool yuv_colour_all_identity(int nframes, const sjpeg_hip_yuv_colour* colour, in
 int yuv_colour_plan(const std::string& who, const YuvResizePlan& planes, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
                     YuvColourPlan* plan);
 int yuv_colour_launch(bool placed, const YuvColourFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
-// The engine's half (scan_engine.hip): the descriptors rebased to `base`, uploaded into a buffer of their own and the
+// The engine's half (engine_pictures.cc): the descriptors rebased to `base`, uploaded into a buffer of their own and the
 // kernel launched on `stream`, behind the resize launch that made the planes.  No tiles: nothing is done.
 int engine_yuv_colour(sjpeg_hip_engine* e, const std::string& who, const YuvColourPlan& plan, uint8_t* base, void* stream);
 
@@ -350,7 +351,7 @@ inline const FrameMeta* frame_meta(const sjpeg_hip_engine* e, int f) {
 bool append_frame_header(int width, int height, int yuv_mode, const uint8_t quant[2][64], const sjpeg_hip_huffman_spec* specs,
                          const FrameMeta* fm, std::vector<uint8_t>* headers);
 
-// the entry points' flows with a sink (the public functions pass NULL); scan_engine.hip and ragged_full.cc
+// the entry points' flows with a sink (the public functions pass NULL); ragged_flows.cc and ragged_full.cc
 int ragged_batch_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframes, const sjpeg_hip_ragged_frame* frames,
                       const uint8_t (*quant)[2][64], int quant_per_frame, const uint8_t* min_quant, int q_bias, int method,
                       int qdelta_max_luma, int qdelta_max_chroma, void* d_out, uint64_t* d_sizes, void* stream,
@@ -360,7 +361,8 @@ int ragged_search_flow(sjpeg_hip_engine* e, int format, int yuv_mode, int nframe
                        int qdelta_max_luma, int qdelta_max_chroma, const sjpeg_hip_search* search, int search_per_frame,
                        float* q_out, float* value_out, void* d_out, uint64_t* d_sizes, void* stream, const PackedSink* sink);
 
-// ---- the search over a ragged batch (ragged_full.cc) and what it takes from the engine (scan_engine.hip)
+// ---- the search over a ragged batch (ragged_full.cc) and what it takes from the engine (scan_engine.hip: the launch
+// layer; ragged_flows.cc: the flows)
 int set_error(int code, const std::string& msg);          // sjpeg_hip_last_error() of the calling thread
 size_t engine_scratch_limit(const sjpeg_hip_engine* e);   // SJPEG_HIP_SCRATCH_LIMIT_BYTES
 int engine_device(const sjpeg_hip_engine* e);

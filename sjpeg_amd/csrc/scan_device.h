@@ -1,7 +1,7 @@
 // Constants, launch arguments and device helpers shared by the kernels of scan_engine.hip
 // (geometry, LDS carve, scans, packed int16 arithmetic, the colour conversion of every source layout).
 // Part of the single translation unit scan_engine.hip: included there inside its anonymous
-// namespace, after <hip/hip_runtime.h> and sjpeg_hip.h; not a stand-alone header.
+// namespace, after <hip/hip_runtime.h>, sjpeg_hip.h and engine.h; not a stand-alone header.
 
 // ------------------------------------------------------------------------------------
 // geometry
@@ -24,30 +24,7 @@ template <> struct Geo<SJPEG_HIP_YUV400> {
   static constexpr int kBpm = 1, kMcuPx = 8, kSegMcus = 246;    // 247; 246 coded blocks
 };
 
-// device copy of sjpeg_hip_scan_tables, pre-digested
-// Laid out as the kernels stage it: two contiguous groups copied to LDS 16 bytes per thread.
-struct alignas(16) DevTables {
-  // group A (1152 B, lives in the idle bit window until the DC codes are done)
-  uint4 q[2][32];          // per natural-order PAIR (2j, 2j+1): {iq0 | iq1<<16, bias0*iq0, bias1*iq1, q0 | q1<<16}
-  uint32_t dc[2][12];
-  // bits a block's AC entries (sign-magnitude pairs) must NOT have for the lean walk to be provably
-  // in place: levels of n <= n_safe bits, n_safe = largest n with len(0, n') + n' <= 16 for all n' <= n
-  uint32_t safe_mask[2];
-  // the AC code words the lean walk needs beside the merged ones: {EOB, ZRL} per table ((code << 16) | length)
-  uint32_t eob_zrl[2][2];
-  uint32_t pad_a[2];
-  // group B (3456 B)
-  uint32_t ac[2][256];
-  // Lean entropy walk, indexed [run & 15][clz(level) - 22] (level 1..1023 <=> clz 31..22):
-  // (code << n) | (code length + n) << 27, i.e. everything of a run/size symbol but the n suffix
-  // bits, in one word.  Run-major: the symbols a picture is made of (runs 0..3, 1..7 level bits) are
-  // 28 words in a row, one LDS bank each -- size-major (rows of 16 runs) they shared eight banks.
-  uint32_t acm[2][16][10];
-  // 1, 2 or 3 ZRL codes as a left-aligned 64-bit pattern {high word, low word, bits, 0} (index 0 unused):
-  // what the stitch puts in front of a part whose first run is 16 or longer
-  uint4 zrlpat[2][4];
-  uint8_t tlen[2][256];    // trellis quantization: AC code lengths the rate is priced with
-};
+// DevTables, the device copy of sjpeg_hip_scan_tables: engine.h (the engine holds copies of it)
 constexpr int kTablesA16 = 72, kTablesB16 = 216;      // uint4 per group
 static_assert(sizeof(uint4) * kTablesA16 == 1152 && sizeof(DevTables) == 1152 + 3456 + 512, "DevTables layout");
 

@@ -1,6 +1,8 @@
 """Compares the gfx950 kernels of two builds of libsjpeg_amd.so: every kernel symbol that exists in both is
 disassembled and compared instruction by instruction, pc-relative operands (branch targets, the literals of the
-s_add_u32 / s_addc_u32 pair directly behind an s_getpc_b64) and addresses masked.  Needs no GPU:
+s_add_u32 / s_addc_u32 pair directly behind an s_getpc_b64) and addresses masked; the alignment padding behind a
+kernel's last instruction (s_nop, s_code_end, objdump's "..." for a run of them) is not part of it -- how much there is
+depends on what follows the kernel in its code object, and a kernel may move to another one.  Needs no GPU:
 
     python tools/kernel_disasm_diff.py OLD/libsjpeg_amd.so NEW/libsjpeg_amd.so > profiles/r09/packed_disasm.txt
 
@@ -78,6 +80,9 @@ def kernels(co):
         if line.startswith("s_getpc_b64"):
             after_getpc = 2
         out[cur].append(line)
+    for body in out.values():                # the padding up to the next symbol, or to the section's end
+        while body and (body[-1] in ("s_nop 0", "...") or body[-1].startswith("s_code_end")):
+            body.pop()
     return out
 
 
@@ -92,7 +97,7 @@ def main(old, new):
     changed = [k for k in both if ko[k] != kn[k]]
     print(f"gfx950 kernels: {len(ko)} in the old build, {len(kn)} in the new one, {len(both)} in both")
     print("masked: addresses, branch targets, the literals of the s_add_u32 / s_addc_u32 pair directly behind an "
-          "s_getpc_b64 (no other scalar add); compared instruction by instruction\n")
+          "s_getpc_b64 (no other scalar add); compared instruction by instruction, trailing alignment padding dropped\n")
     for k in both:
         print(f"{'DIFFERS' if k in changed else 'same   '} {len(kn[k]):6d} instructions  {k}")
     print("\nonly in the new build:")

@@ -16,7 +16,10 @@ SAN="-fsanitize=address,undefined -fno-sanitize=enum -fno-omit-frame-pointer -g 
 for f in host_api jpeg_host jpeg_tools; do
   g++ -std=c++17 -fPIC -ffp-contract=off $SAN -I"$ROOT/include" -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -c "$C/$f.cc" -o "$W/$f.o"
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic "$C/scan_engine.o" "$C/sharp_yuv.o" "$C/riskiness.o" "$C/exchange.o" \
+# (the tree's other objects: the Makefile's list, with the three sanitized ones in place of theirs)
+OTHERS=$(make -s -C "$C" print-other-objs)
+for f in host_api jpeg_host jpeg_tools; do OTHERS=${OTHERS//$C\/$f.o/}; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic "$C/scan_engine.o" $OTHERS \
     "$W/host_api.o" "$W/jpeg_host.o" "$W/jpeg_tools.o" -ldl -o "$W/libsjpeg_amd.so"
 cp "$C/riskiness.bin" "$W/"
 g++ -std=c++17 $SAN -I"$ROOT/include" "$ROOT/tests/cxx/api_test.cc" -o "$W/api_test" -L"$W" -lsjpeg_amd -lpthread \

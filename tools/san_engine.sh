@@ -1,7 +1,8 @@
 #!/bin/bash
-# AddressSanitizer on the HOST half of scan_engine.hip (the engine: buffers, streams, child engines and the state machine of
-# the batch path's lanes, uploads through pinned blocks) -- tools/san_check.sh covers the .cc files of the drop-in API only.
-# The device code is compiled as usual (-fno-gpu-sanitize).  Built here (hipcc cross-compiles), run on the GPU box:
+# AddressSanitizer on the engine's host code: the host half of scan_engine.hip (buffers, streams, uploads through pinned
+# blocks) and the flows over it (batch_flow.cc: child engines and the state machine of the batch path's lanes;
+# ragged_flows.cc; engine_pictures.cc) -- tools/san_check.sh covers the .cc files of the drop-in API only.
+# The device code is compiled as usual (-fno-gpu-sanitize); the library's other objects are the tree's.  Built here (hipcc cross-compiles), run on the GPU box:
 #   tools/san_engine.sh build && gpurun --timeout 900 -- 'bash tools/san_engine.sh run'
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -9,10 +10,18 @@ C=$ROOT/sjpeg_amd/csrc
 RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 if [ "${1:-build}" = build ]; then
   make -s -C "$C"
+  OTHERS=$(make -s -C "$C" print-other-objs)
+  FLOWS=""
+  for f in batch_flow ragged_flows engine_pictures; do
+    OTHERS=${OTHERS//$C\/$f.o/}
+    /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off -fsanitize=address -shared-libsan -fno-omit-frame-pointer -I"$ROOT/include" \
+        -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -x c++ -c "$C/$f.cc" -o /tmp/${f}_asan.o
+    FLOWS="$FLOWS /tmp/${f}_asan.o"
+  done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -fsanitize=address -shared-libsan -fno-gpu-sanitize \
       -fno-omit-frame-pointer -I"$ROOT/include" -c "$C/scan_engine.hip" -o /tmp/scan_engine_asan.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -shared-libsan -Wl,-Bsymbolic /tmp/scan_engine_asan.o "$C/sharp_yuv.o" "$C/riskiness.o" \
-      "$C/exchange.o" "$C/host_api.o" "$C/jpeg_host.o" "$C/jpeg_tools.o" -ldl -o "$ROOT/tools/lib_asan.bin"
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -shared-libsan -Wl,-Bsymbolic /tmp/scan_engine_asan.o $FLOWS $OTHERS \
+      -ldl -o "$ROOT/tools/lib_asan.bin"
   SAN="-fsanitize=address -shared-libasan -fno-omit-frame-pointer -g -O1"
   /opt/rocm/lib/llvm/bin/clang++ -std=c++17 $SAN -I"$ROOT/include" -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ "$ROOT/tests/cxx/batch_lanes_test.cc" \
       -o "$ROOT/tools/batch_lanes_test_asan.bin" "$ROOT/tools/lib_asan.bin" -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
