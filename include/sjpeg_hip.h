@@ -1436,6 +1436,120 @@ int sjpeg_hip_encode_ragged_sheet_yuv16_packed_src(sjpeg_hip_engine* engine, int
                                                    int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
                                                    void* stream);
 
+/* ---- resize in linear light: gamma-correct thumbnails in the ragged call ----
+ * A downscaler that averages gamma-encoded values darkens fine detail: a 0/255 checkerboard reduced 2:1 comes out as
+ * 128, and the light it emitted corresponds to byte 188.  Every entry above averages the stored bytes -- exact, but in
+ * coded light.  The entries below average the LIGHT the bytes stand for, as libvips' `thumbnail --linear` and
+ * ImageMagick's `-colorspace RGB -resize` do, still in ONE launch and still with one right answer in integers.
+ * `light` is an int:
+ *   SJPEG_HIP_LIGHT_CODED (0): average the bytes as they are.  This is every entry above.
+ *   SJPEG_HIP_LIGHT_LINEAR_SRGB (1): the definition below.
+ *   Anything else is SJPEG_HIP_EINVAL.
+ * THE TABLE.  L[b], for b = 0..255, is floor(65535 * f(b / 255) + 1/2).  f is the sRGB decoding function of
+ * IEC 61966-2-1:
+ *   f(c) = c / 12.92 for c <= 0.04045
+ *   f(c) = ((c + 0.055) / 1.055) ^ 2.4 otherwise
+ * The table is 256 literal uint16_t constants (sjpeg_amd/csrc/light_math.h) that host and kernel share; there is no
+ * pow at run time, on either side.  Check values: L[0..5] = 0, 20, 40, 60, 80, 99; L[252..255] = 63795, 64372, 64952,
+ * 65535; strictly increasing, smallest step 19; sum 5217863; SHA-256 of the 256 values as little-endian uint16
+ * fdb7af3c01815a2118db8e50aac3c2304205ccc3f381f8976c588642c1aa60b6.  No entry lies closer than 0.0016 to a rounding
+ * tie, so a double-precision evaluation gives the same table.
+ * THE AVERAGE.  The resize's own wx, wy, W, H, w', h', unchanged.  b(x, y, c) is the byte the resize sees there
+ * today; for a flattened call that is the flattened byte.
+ *   A = W * H
+ *   S = sum over y of wy(y', y) * sum over x of wx(x', x) * L[b(x, y, c)]
+ *     (a row's inner sum is at most 65535 W < 2^32 and S <= 65535 A < 2^48: the bounds of the 16-bit video path)
+ *   out = the number of k in 1..255 with 2 S >= (L[k-1] + L[k]) * A
+ * So out is the byte whose linear value is nearest the exact average; a tie goes to the larger byte.  The compare is
+ * on exact 64-bit products: (L[k-1] + L[k]) < 2^17 and A < 2^32, so both sides stay below 2^49.  Consequences:
+ *   A picture at its own size is itself (S = L[b] A).
+ *   A constant picture is itself at any size.
+ *   out is monotone in S.
+ *   The eight orientations still commute with the average.
+ *   A linear resize by a whole number is NOT the Reduced picture (sjpeg_hip_reduce_ragged_src): that averages bytes.
+ * Known answers (the byte average in brackets): 0 and 255 in equal parts 188 [128]; 0 and 255 at 3:1 137 [64]; 100
+ * and 200 in equal parts 160 [150].
+ * ORDER OF STEPS: 1. the pixel transform of the float formats; 2. flatten, on bytes in coded light exactly as above
+ * (browsers and PNG viewers composite this way; a flattened linear call makes what the linear call makes of the
+ * flattened picture F); 3. L[]; 4. the average; 5. the inverse; 6. the turn; 7. the placement.  A sheet's background
+ * and gutters are bytes, as given, and are never converted.
+ * FORMATS: every format the resize takes goes through the same curve -- RGB, BGRA, RGBA, planar RGB, the float kinds
+ * in both layouts, gray.  The YUV-plane formats are refused with SJPEG_HIP_EINVAL, naming the format: their samples
+ * are not RGB light.
+ * JPEG CONTRACT, the family's usual one: the JPEG is byte for byte what the same call makes of the uint8 picture so
+ * defined, handed over as SJPEG_HIP_SRC_RGB (the gray formats: SJPEG_HIP_SRC_GRAY, 4:0:0 only).  SJPEG_YUV_AUTO, the
+ * search and the metadata act on the made picture.
+ *
+ * sjpeg_hip_linear_ragged_src: sjpeg_hip_flatten_ragged_src's arguments, with `flatten` allowed to be NULL, plus
+ *   `light` behind it.  Same output layout, same size (sjpeg_hip_orient_ragged_bytes), ONE launch.
+ * sjpeg_hip_encode_ragged_linear_src / _linear_packed_src: the _flattened_ entries plus `light`.
+ * sjpeg_hip_sheet_ragged_linear_src, sjpeg_hip_encode_ragged_sheet_linear_src / _sheet_linear_packed_src: the
+ *   _sheet_flat_ entries plus `light` (flatten may be NULL).
+ * light == SJPEG_HIP_LIGHT_CODED is a pass-through: exactly the flattened, oriented or sheet call on the same
+ *   arguments, with that entry's name in the messages.  With SJPEG_HIP_LIGHT_LINEAR_SRGB EVERY frame goes through the
+ *   kernel, also at its own size with orientation 1; that case is a copy, because the inverse is exact.
+ * SJPEG_HIP_EINVAL before any device work: a light that is neither value; a YUV-plane format (named); gray with a
+ *   yuv_mode other than 4:0:0; and every check the corresponding coded-light entry makes.
+ * Host only, for bindings and tests:
+ *   sjpeg_hip_light_table: the 256 table values of `light` (SJPEG_HIP_LIGHT_CODED: the bytes themselves, L[b] = b).
+ *   sjpeg_hip_light_round: *byte = out for a cell sum S of a W x H picture (SJPEG_HIP_LIGHT_CODED: the byte average
+ *     rounded half up, as the entries above round); S above L[255] W H, W or H outside 1..65535 or a NULL pointer is
+ *     SJPEG_HIP_EINVAL. */
+#define SJPEG_HIP_LIGHT_CODED 0
+#define SJPEG_HIP_LIGHT_LINEAR_SRGB 1
+int sjpeg_hip_light_table(int light, uint16_t table[256]);
+int sjpeg_hip_light_round(int light, uint64_t S, uint32_t W, uint32_t H, uint32_t* byte);
+int sjpeg_hip_linear_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                int light, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_linear_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                       const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                       const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/, int light,
+                                       const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                       const uint8_t* orientations /*host [nframes], or NULL*/,
+                                       const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                       void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                       int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_linear_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                              const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                              int light, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                              const uint8_t* orientations /*host [nframes], or NULL*/,
+                                              const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                              void* d_packed, size_t packed_capacity,
+                                              uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                              int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                              void* stream);
+int sjpeg_hip_sheet_ragged_linear_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_sheet* sheet,
+                                      const sjpeg_hip_flatten* flatten /*or NULL*/, int light,
+                                      const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                      const uint8_t* orientations /*host [nframes], or NULL*/, void* d_out, size_t bytes,
+                                      sjpeg_hip_ragged_frame* sheet_frames /*host out [nsheets]*/, int* nsheets, int* out_format,
+                                      void* stream);
+int sjpeg_hip_encode_ragged_sheet_linear_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                             const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const sjpeg_hip_flatten* flatten /*or NULL*/, int light,
+                                             const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                             const uint8_t* orientations /*host [nframes], or NULL*/,
+                                             const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                             void* d_out, size_t out_stride, uint64_t* d_sizes /*[nsheets]*/,
+                                             int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_sheet_linear_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                    const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset, out_capacity ignored*/,
+                                                    const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                    const sjpeg_hip_flatten* flatten /*or NULL*/, int light,
+                                                    const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                    const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                    const struct sjpeg_hip_metadata* meta /*host: [nsheets], [1] or NULL*/, int meta_per_frame,
+                                                    void* d_packed, size_t packed_capacity,
+                                                    uint64_t* d_offsets /*[nsheets + 1]*/, uint64_t* d_sizes /*[nsheets]*/,
+                                                    int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
+                                                    void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

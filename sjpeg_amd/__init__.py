@@ -1004,6 +1004,11 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_yuv16_src", "sjpeg_hip_encode_ragged_yuv16_packed_src",
     "sjpeg_hip_sheet_ragged_yuv16_src", "sjpeg_hip_encode_ragged_sheet_yuv16_src",
     "sjpeg_hip_encode_ragged_sheet_yuv16_packed_src",
+    # (bound by sjpeg_amd/light.py)
+    "sjpeg_hip_light_table", "sjpeg_hip_light_round", "sjpeg_hip_linear_ragged_src",
+    "sjpeg_hip_encode_ragged_linear_src", "sjpeg_hip_encode_ragged_linear_packed_src",
+    "sjpeg_hip_sheet_ragged_linear_src", "sjpeg_hip_encode_ragged_sheet_linear_src",
+    "sjpeg_hip_encode_ragged_sheet_linear_packed_src",
 ]
 
 

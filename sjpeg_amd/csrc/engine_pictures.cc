@@ -50,8 +50,11 @@ int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, c
                                   void* stream) {
   return engine_make_pictures(e, who, "resized", plan.frames, plan.bytes, d_resized, base, stream,
                               [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
-    const int rc = plan.flat ? resize_ragged_flat_launch(false, plan.format, e->pscale, e->pbias, plan.flatten, d_frames, n, plan.tiles, st)
-                             : resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st);
+    const int rc = plan.light != SJPEG_HIP_LIGHT_CODED
+                       ? resize_ragged_linear_launch(false, plan.format, e->pscale, e->pbias, plan.flat ? &plan.flatten : nullptr, d_frames, n,
+                                                     plan.tiles, st)
+                   : plan.flat ? resize_ragged_flat_launch(false, plan.format, e->pscale, e->pbias, plan.flatten, d_frames, n, plan.tiles, st)
+                               : resize_ragged_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.tiles, st);
     if (rc != 0) {
       return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
     }
@@ -98,8 +101,11 @@ int sjpeg_internal::engine_sheet(sjpeg_hip_engine* e, const std::string& who, co
     rc = engine_make_pictures(e, who, "sheet", plan.rgb.frames, plan.bytes, d_out, &sheets, stream,
                               [&](const ResizeFrame* d_frames, int n, hipStream_t st) {
       if (int rcf = fill(st)) return rcf;
-      const int rcl = plan.rgb.flat ? resize_ragged_flat_launch(true, plan.format, e->pscale, e->pbias, plan.rgb.flatten, d_frames, n, plan.rgb.tiles, st)
-                                    : resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st);
+      const int rcl = plan.rgb.light != SJPEG_HIP_LIGHT_CODED
+                          ? resize_ragged_linear_launch(true, plan.format, e->pscale, e->pbias, plan.rgb.flat ? &plan.rgb.flatten : nullptr, d_frames,
+                                                        n, plan.rgb.tiles, st)
+                      : plan.rgb.flat ? resize_ragged_flat_launch(true, plan.format, e->pscale, e->pbias, plan.rgb.flatten, d_frames, n, plan.rgb.tiles, st)
+                                      : resize_ragged_placed_launch(plan.format, e->pscale, e->pbias, d_frames, n, plan.rgb.tiles, st);
       if (rcl != 0) {
         return fail(SJPEG_HIP_ERUNTIME, who + ": resize_ragged_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
       }

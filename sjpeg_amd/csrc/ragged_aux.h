@@ -161,6 +161,7 @@ struct ResizePlan {
   unsigned tiles = 0;
   bool flat = false;                     // the frames are flattened as they are staged (the kernel's flat instantiations)
   sjpeg_hip_flatten flatten = {};        // ... by this
+  int light = 0;                         // SJPEG_HIP_LIGHT_*: other than CODED, the kernel's linear instantiations
 };
 // Checks the sizes (sizes[f] = (w', h'), 1..the source's each; NULL: every frame at its own size) and the format (an
 // RGB-like or gray one), then plans; the message names the frame.  The frames' planes and strides are the caller's to
@@ -181,8 +182,15 @@ int resize_ragged_launch(int format, const float* pscale, const float* pbias, co
 // ... of a flat plan (placed: a sheet's descriptors)
 int resize_ragged_flat_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten& flatten,
                               const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
+// ... of a plan in linear light (flatten NULL: not flat; placed: a sheet's descriptors)
+int resize_ragged_linear_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten* flatten,
+                                const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
+// 0 for a light the linear entries take and a format whose samples are RGB light, else SJPEG_HIP_EINVAL: a light that
+// is not SJPEG_HIP_LIGHT_CODED or _LINEAR_SRGB, a YUV-plane format (named)
+int light_check(const std::string& who, int light, int format);
 // The engine's half (engine_pictures.cc), as engine_reduce: d_resized == NULL: into the engine's memory for reduced
-// pictures (the two kinds of call share it and its descriptors' buffer).  A flat plan runs the flat launch.
+// pictures (the two kinds of call share it and its descriptors' buffer).  A flat plan runs the flat launch, a plan in
+// linear light the linear one.
 int engine_resize(sjpeg_hip_engine* e, const std::string& who, const ResizePlan& plan, uint8_t* d_resized, uint8_t** base, void* stream);
 
 // ---- ragged resize of the YUV-plane formats (sjpeg_hip_resize_ragged_yuv_src; yuv_resize_plan.cc, resize.hip): one

@@ -31,7 +31,13 @@ struct Shape {
   const sjpeg_hip_yuv_colour* colour = nullptr;
   int colour_per_frame = 0;
   const sjpeg_hip_yuv_depth* depth = nullptr;
+  int light = SJPEG_HIP_LIGHT_CODED;
 };
+Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
+  Shape s{nullptr, sizes, orientations, flatten, sheet};
+  s.light = light;
+  return s;
+}
 
 // ---- the plan kinds: the plan function, the format of what it makes, the made pictures as frames at `base` and how
 // many they are, the engine's half, and the hint behind a refused yuv_mode
@@ -134,6 +140,25 @@ struct SheetDeepKind : SheetColourKind {
   }
 };
 
+// ... and the two in linear light (sjpeg_hip_linear_ragged_src): the resize and sheet plans marked with the light, so
+// the engine's half runs the kernel's linear instantiations; a YUV-plane format is refused by name in front of the plan
+struct LinearKind : ResizeKind {
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = light_check(who, s.light, format)) return rc;
+    if (int rc = ResizeKind::plan(who, format, n, fr, s, p)) return rc;
+    p->light = s.light;
+    return 0;
+  }
+};
+struct SheetLinearKind : SheetKind {
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = light_check(who, s.light, format)) return rc;
+    if (int rc = SheetKind::plan(who, format, n, fr, s, p)) return rc;
+    p->rgb.light = s.light;
+    return 0;
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -185,7 +210,8 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kYuvResized[2] = SJPEG_ENTRY_NAMES("yuv_resized"), kSheet[2] = SJPEG_ENTRY_NAMES("sheet"),
                   kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat"), kYuvConverted[2] = SJPEG_ENTRY_NAMES("yuv_converted"),
                   kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour"), kYuv16[2] = SJPEG_ENTRY_NAMES("yuv16"),
-                  kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16");
+                  kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
+                  kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -386,6 +412,27 @@ int sheet_yuv16_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const int32_t 
   if (int rc = encode_prologue(c, true, sheet, true)) return rc;
   if (int rc = yuv_depth_check(*c.who, depth)) return rc;
   return sheet_flow<SheetDeepKind>(c, Shape{nullptr, sizes, orientations, nullptr, sheet, colour, colour_per_frame, depth});
+}
+
+
+// Linear light.  light == SJPEG_HIP_LIGHT_CODED: exactly the flattened call (which hands on to the oriented one without
+// a flatten) on the same arguments.  Otherwise no pass-through: every frame goes through the kernel, at its own size
+// and orientation 1 too -- a copy, because the inverse is exact.
+int linear_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2], const uint8_t* orientations) {
+  if (light == SJPEG_HIP_LIGHT_CODED) return flattened_entry(c, flatten, sizes, orientations);
+  c.who = &kLinear[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = light_check(*c.who, light, c.format)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  return planned_flow<LinearKind>(c, linear_shape(sizes, orientations, flatten, nullptr, light));
+}
+int sheet_linear_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2],
+                       const uint8_t* orientations) {
+  if (light == SJPEG_HIP_LIGHT_CODED) return sheet_entry(c, sheet, flatten, sizes, orientations);
+  c.who = &kSheetLinear[c.out.packed];
+  if (int rc = encode_prologue(c, true, sheet)) return rc;
+  if (int rc = light_check(*c.who, light, c.format)) return rc;
+  return sheet_flow<SheetLinearKind>(c, linear_shape(sizes, orientations, flatten, sheet, light));
 }
 
 }  // namespace
@@ -739,6 +786,80 @@ int sjpeg_hip_encode_ragged_sheet_yuv16_packed_src(sjpeg_hip_engine* e, int form
   return sheet_yuv16_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                             RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet,
                            sizes, orientations, colour, colour_per_frame, depth);
+}
+
+// ---- ... and the resize in linear light: the flattened and sheet entries plus `light` (light_math.h), through the
+// kernel's linear instantiations; flatten may be NULL
+int sjpeg_hip_linear_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_linear_ragged_src";
+  if (light == SJPEG_HIP_LIGHT_CODED) {
+    if (flatten == nullptr) return sjpeg_hip_orient_ragged_src(e, format, nframes, frames, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
+    return sjpeg_hip_flatten_ragged_src(e, format, nframes, frames, flatten, sizes, orientations, d_out, out_bytes, out_frames, out_format, stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = light_check(who, light, format)) return rc;
+  return shape_body<LinearKind>(who, kOrientWords, e, format, nframes, frames, linear_shape(sizes, orientations, flatten, nullptr, light), false,
+                                d_out, out_bytes, out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_linear_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                       const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, int light,
+                                       const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                       int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                       void* stream) {
+  return linear_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                       {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, light, sizes, orientations);
+}
+
+int sjpeg_hip_encode_ragged_linear_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, int light,
+                                              const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_metadata* meta,
+                                              int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                              uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return linear_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                       RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten, light,
+                      sizes, orientations);
+}
+
+int sjpeg_hip_sheet_ragged_linear_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_sheet* sheet, const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2],
+                                      const uint8_t* orientations, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* sheet_frames,
+                                      int* nsheets, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_sheet_ragged_linear_src";
+  if (light == SJPEG_HIP_LIGHT_CODED) {
+    if (flatten == nullptr) {
+      return sjpeg_hip_sheet_ragged_src(e, format, nframes, frames, sheet, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+    }
+    return sjpeg_hip_sheet_ragged_flat_src(e, format, nframes, frames, sheet, flatten, sizes, orientations, d_out, out_bytes, sheet_frames, nsheets,
+                                           out_format, stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = light_check(who, light, format)) return rc;
+  return shape_body<SheetLinearKind>(who, kSheetWords, e, format, nframes, frames, linear_shape(sizes, orientations, flatten, sheet, light),
+                                     sheet == nullptr || nsheets == nullptr, d_out, out_bytes, sheet_frames, nsheets, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_sheet_linear_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                             const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                             const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2],
+                                             const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                             size_t out_stride, uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_linear_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                             RaggedOut{d_out, d_sizes, modes, q_out, value_out, stream}.strided_by(out_stride)}, sheet, flatten, light, sizes,
+                            orientations);
+}
+
+int sjpeg_hip_encode_ragged_sheet_linear_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                    const sjpeg_hip_ragged_params* params, const sjpeg_hip_sheet* sheet,
+                                                    const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2],
+                                                    const uint8_t* orientations, const sjpeg_hip_metadata* meta, int meta_per_frame,
+                                                    void* d_packed, size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                    int* modes, float* q_out, float* value_out, void* stream) {
+  return sheet_linear_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                             RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet,
+                            flatten, light, sizes, orientations);
 }
 
 }  // extern "C"

@@ -47,6 +47,16 @@
 // dwords: each in a bank of its own, as before.  A row's sum is at most 65535 W < 2^32 and a cell's 65535 W H < 2^48:
 // h stays 32 bits and acc 64.  A finished row is rounded ONCE, by resize_round_deep with the launch's shift, into the
 // byte tile; from there on nothing differs.
+//
+// Linear light (sjpeg_hip_linear_ragged_src; light_math.h): the LINEAR instantiations of the RGB-like and gray kernel
+// average the light the bytes stand for.  The table L[] lies in LDS, 512 bytes, copied once per workgroup.  A byte is
+// converted WHERE THE SEGMENT IS STAGED -- behind the flatten, which stays on bytes -- so the stage holds 16-bit linear
+// words, always as a run of words per channel whatever the source's layout (a packed pixel is taken apart on the way:
+// three byte-pitched words would put 32 lanes' reads on 48 dwords, two to a bank for half of them; a run per channel
+// puts them on 16).  The sum loop is then the deep one, sample for sample and bound for bound: a row's sum at most
+// 65535 W < 2^32, a cell's 65535 W H < 2^48.  `cap`, for every staging class alike, is the 16 384 bytes over two
+// bytes a sample and channel: 2728 pixels of three channels, 8192 of gray; the chunked path starts there.  A finished
+// cell goes back to a byte by light_round, the exact inverse, on the lane that rounds today.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -55,6 +65,7 @@
 #include <vector>
 
 #include "flatten_math.h"
+#include "light_math.h"
 #include "orient_math.h"
 #include "pixel_elem.h"
 #include "ragged_aux.h"
@@ -165,11 +176,58 @@ template <bool kYuv, bool kFlat = false, bool kDeep = false> struct ResizeArgsOf
 template <> struct ResizeArgsOf<true, false, false> { typedef YuvResizeArgs type; };
 template <> struct ResizeArgsOf<false, true, false> { typedef FlatResizeArgs type; };
 template <> struct ResizeArgsOf<true, false, true> { typedef YuvDeepResizeArgs type; };
-// a finished cell's sum rounded into its byte
-template <bool kDeep, class Args>
-__device__ __forceinline__ uint32_t round_sample(uint64_t S, uint32_t W, uint32_t H, const Args& a) {
-  if constexpr (kDeep) return sjpeg_internal::resize_round_deep(S, W, H, a.shift);
+// a finished cell's sum rounded into its byte (ltab: the linear instantiations' table in LDS)
+template <bool kDeep, bool kLinear, class Args>
+__device__ __forceinline__ uint32_t round_sample(uint64_t S, uint32_t W, uint32_t H, const Args& a, const uint16_t* ltab) {
+  if constexpr (kLinear) return sjpeg_internal::light_round(S, W, H, ltab);
+  else if constexpr (kDeep) return sjpeg_internal::resize_round_deep(S, W, H, a.shift);
   else return sjpeg_internal::resize_round(S, W, H);
+}
+
+// nb bytes of one channel's run of a source row at g into the words at l (a multiple of 4), each through the table:
+// whole dwords, the last 1..3 bytes one by one -- every byte read is one of the nb
+__device__ __forceinline__ void stage_bytes_linear(const uint8_t* g, uint16_t* l, unsigned nb, unsigned lane, unsigned lanes,
+                                                   const uint16_t* ltab) {
+  const unsigned nd = nb >> 2;
+  GlobalDwords const gd = (GlobalDwords)(g);
+  uint32_t* const ld = reinterpret_cast<uint32_t*>(l);
+  for (unsigned i = lane; i < nd; i += lanes) {
+    const uint32_t v = gd[i];
+    ld[2u * i] = ltab[v & 255u] | (static_cast<uint32_t>(ltab[(v >> 8) & 255u]) << 16);
+    ld[2u * i + 1u] = ltab[(v >> 16) & 255u] | (static_cast<uint32_t>(ltab[v >> 24]) << 16);
+  }
+  const unsigned i = (nd << 2) + lane;
+  if (i < nb) l[i] = ltab[((GlobalBytes)(g))[i]];
+}
+
+// npix three-byte pixels of a source row at g, taken apart into the three runs of words at l, l + wpitch and
+// l + 2 wpitch (8-byte aligned each; channel c's byte lies o[c] = 0..2 bytes into a pixel).  Four pixels a lane: their
+// 12 bytes as three dwords, and per channel the four words as ONE 8-byte store -- adjacent lanes adjacent 8 bytes of a
+// run --; the last 1..3 pixels byte by byte.  Every byte read is one of the 3 npix.
+__device__ __forceinline__ void stage_pixels3_linear(const uint8_t* g, uint16_t* l, unsigned wpitch, unsigned npix, unsigned lane,
+                                                     unsigned lanes, unsigned o0, unsigned o1, const uint16_t* ltab) {
+  const unsigned ng = npix >> 2, o2 = 3u - o0 - o1;
+  GlobalDwords const gd = (GlobalDwords)(g);
+  for (unsigned i = lane; i < ng; i += lanes) {
+    const uint64_t lo = gd[3u * i] | (static_cast<uint64_t>(gd[3u * i + 1u]) << 32);
+    const uint32_t hi = gd[3u * i + 2u];
+    auto word = [&](unsigned j) -> uint32_t {                      // the light of byte j = 0..11 of the twelve
+      return ltab[j < 8u ? static_cast<uint32_t>(lo >> (8u * j)) & 255u : (hi >> (8u * (j - 8u))) & 255u];
+    };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const unsigned o = c == 0 ? o0 : c == 1 ? o1 : o2;
+      *reinterpret_cast<uint2*>(l + c * wpitch + 4u * i) =
+          make_uint2(word(o) | (word(o + 3u) << 16), word(o + 6u) | (word(o + 9u) << 16));
+    }
+  }
+  const unsigned k = (ng << 2) + lane;
+  if (k < npix) {
+    GlobalBytes const gb = (GlobalBytes)(g) + 3u * k;
+    l[k] = ltab[gb[o0]];
+    l[wpitch + k] = ltab[gb[o1]];
+    l[2u * wpitch + k] = ltab[gb[o2]];
+  }
 }
 __device__ __forceinline__ int desc_count(const ResizeArgs& a) { return a.nframes; }
 __device__ __forceinline__ int desc_count(const YuvResizeArgs& a) { return a.nplanes; }
@@ -190,14 +248,25 @@ __device__ __forceinline__ const ResizeFrame& desc_at(const YuvResizeArgs& a, in
 // kDeep: the planes are of 16-bit samples (the YUV-plane formats alone).  A compile-time flag once more: what differs
 // is the staged element (esz bytes), the sample the sum loop reads and the rounding; the six instantiations without it
 // hold what they held before.
-template <bool kYuv, bool kPlaced, bool kFlat = false, bool kDeep = false>
+// kLinear: the average is of linear light (the RGB-like and gray formats alone, plain or flat).  A compile-time flag
+// like the others: what differs is the table in LDS, the staged sample -- a 16-bit linear word in a run per channel --
+// and the rounding; the eight instantiations without it hold what they held before.
+template <bool kYuv, bool kPlaced, bool kFlat = false, bool kDeep = false, bool kLinear = false>
 __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename ResizeArgsOf<kYuv, kFlat, kDeep>::type a) {
   static_assert(!(kYuv && kFlat), "the YUV-plane formats have no alpha");
   static_assert(kYuv || !kDeep, "16-bit samples: the YUV-plane formats alone");
-  constexpr unsigned esz = kDeep ? 2u : 1u;                        // bytes a staged sample
+  static_assert(!(kYuv && kLinear), "linear light: the YUV-plane formats' samples are not RGB light");
+  constexpr bool kWide = kDeep || kLinear;                         // the stage holds 16-bit words
+  constexpr unsigned esz = kWide ? 2u : 1u;                        // bytes a staged sample
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileBytes];
+  __shared__ __attribute__((aligned(16))) uint16_t light[kLinear ? 256 : 1];
   const unsigned wg = blockIdx.x, tid = threadIdx.x;
+  const uint16_t* ltab = nullptr;
+  if constexpr (kLinear) {
+    light[tid] = sjpeg_internal::kLightSrgb[tid];                  // (256 threads, 256 entries; the barrier is below)
+    ltab = light;
+  }
   int flo = 0, fhi = desc_count(a) - 1;
   while (flo < fhi) {
     const int mid = (flo + fhi + 1) >> 1;
@@ -230,11 +299,13 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   const uint32_t ys = resize_first(oy0, H, h2), ye = resize_first(oy0 + th - 1u, H, h2) + resize_count(oy0 + th - 1u, H, h2);
   // The staged rows: packed pixels as they lie in memory, else a run of bytes per channel; `cap` pixels fit, a longer
   // segment goes in chunks of a single row
-  const bool packed = cls == kResizePacked;
+  // (linear: a run of words per channel whatever the source's class)
+  const bool packed = !kLinear && cls == kResizePacked;
   const unsigned lstep = (packed ? pix_step : 1u) * esz;
   const unsigned cap = packed ? kStageBytes / lstep : (kStageBytes / (channels * esz)) & ~3u;
   const unsigned seg = xe - xs, clen_max = min(seg, cap);
-  const unsigned cpitch = packed ? 0u : align4(clen_max * esz);
+  // (linear: a run starts at a multiple of 8, for the 8-byte stores of four words; cap * 2 is one, so nothing grows)
+  const unsigned cpitch = packed ? 0u : kLinear ? (clen_max * esz + 7u) & ~7u : align4(clen_max * esz);
   const unsigned rpitch = packed ? align4(clen_max * lstep) : cpitch * channels;
   const unsigned R = seg > cap ? 1u : kStageBytes / rpitch;
   unsigned coff[3];
@@ -249,6 +320,7 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
   const bool transposed = sjpeg_internal::orient_transposes(orient);
   const unsigned tpitch = align4(static_cast<unsigned>(d.tw) * channels) | (transposed ? 4u : 0u);
   for (unsigned i = tid; i < th * tpitch / 4u; i += 256u) reinterpret_cast<uint32_t*>(tile)[i] = 0u;   // (the rows' padding)
+  if constexpr (kLinear) __syncthreads();                          // (the table is read while the first rows are staged)
 
   uint32_t h[3] = {0u, 0u, 0u};
   uint64_t acc[3] = {0ull, 0ull, 0ull};
@@ -260,7 +332,50 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
       for (unsigned r = srow; r < nr; r += srows) {
         const uint8_t* const row = d.src + static_cast<long long>(yb + r) * d.row_stride;
         uint8_t* const l = stage + r * rpitch;
-        if constexpr (kFlat) {
+        if constexpr (kLinear) {
+          // the same reads as below, class by class; every byte -- the flattened one of a flat frame -- through the
+          // table into its channel's run of words
+          uint16_t* const lw = reinterpret_cast<uint16_t*>(l);
+          const unsigned wpitch = cpitch >> 1;
+          if (cls == kResizePacked && pix_step == 4) {
+            // (four-byte pixels: row + xc * 4 is a pixel boundary; alpha is the last byte)
+            GlobalDwords const gd = (GlobalDwords)(row + static_cast<long long>(xc) * 4);
+            const unsigned sh[3] = {static_cast<unsigned>(d.off[0]) * 8u, static_cast<unsigned>(d.off[1]) * 8u, static_cast<unsigned>(d.off[2]) * 8u};
+            for (unsigned k = slane; k < clen; k += slanes) {
+              const uint32_t v = gd[k];
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                uint32_t b = (v >> sh[c]) & 255u;
+                if constexpr (kFlat) b = sjpeg_internal::flatten_byte(v >> 24, b, a.bg[c], a.premultiplied != 0);
+                lw[c * wpitch + k] = ltab[b];
+              }
+            }
+          } else if (cls == kResizePacked) {
+            stage_pixels3_linear(row + static_cast<long long>(xc) * 3, lw, wpitch, clen, slane, slanes, static_cast<unsigned>(d.off[0]),
+                                 static_cast<unsigned>(d.off[1]), ltab);
+          } else if (cls == kResizePlanes) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              if (c < static_cast<int>(channels)) stage_bytes_linear(row + d.off[c] + xc, lw + c * wpitch, clen, slane, slanes, ltab);
+            }
+          } else {
+            // the float formats, a pixel at a time: never an element that is not a used sample of a pixel of the picture
+            for (unsigned k = slane; k < clen; k += slanes) {
+              const uint8_t* const px = row + static_cast<long long>(xc + k) * a.pix_step;
+              uint32_t al = 0u;
+              if constexpr (kFlat) {
+                al = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(px + 3 * (a.pix_step >> 2), a.kind, a.ascale, a.abias));
+              }
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                if (c >= static_cast<int>(channels)) continue;
+                uint32_t b = static_cast<uint32_t>(sjpeg_internal::elem_load_u8(px + d.off[c], a.kind, a.pscale[c], a.pbias[c]));
+                if constexpr (kFlat) b = sjpeg_internal::flatten_byte(al, b, a.bg[c], a.premultiplied != 0);
+                lw[c * wpitch + k] = ltab[b];
+              }
+            }
+          }
+        } else if constexpr (kFlat) {
           if (packed) {
             // (four-byte pixels: row + xc * 4 is a pixel boundary and l a multiple of 4)
             const unsigned sh[3] = {coff[0] * 8u, coff[1] * 8u, coff[2] * 8u};
@@ -316,9 +431,9 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
         for (uint32_t x = lo + p; x < hi; x += P) {
           const uint32_t w = resize_weight(ox0 + j, x, W, w2);
           const uint8_t* const px = stage + r * rpitch + (x - xc) * lstep;
-          h[0] += w * staged_sample<kDeep>(px + coff[0]);
-          if (three) { h[1] += w * staged_sample<kDeep>(px + coff[1]); h[2] += w * staged_sample<kDeep>(px + coff[2]); }
-          if (two) h[1] += w * staged_sample<kDeep>(px + coff[1]);
+          h[0] += w * staged_sample<kWide>(px + coff[0]);
+          if (three) { h[1] += w * staged_sample<kWide>(px + coff[1]); h[2] += w * staged_sample<kWide>(px + coff[2]); }
+          if (two) h[1] += w * staged_sample<kWide>(px + coff[1]);
         }
         if (!last) continue;
         for (unsigned m = P >> 1; m != 0u; m >>= 1) {
@@ -334,12 +449,12 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const typename Resiz
           for (int c = 0; c < 3; ++c) acc[c] += static_cast<uint64_t>(wy) * h[c];
           if ((y + 1u) * h2 >= (yo + 1u) * H) {
             uint8_t* const o = tile + (yo - oy0) * tpitch + j * channels;
-            o[0] = static_cast<uint8_t>(round_sample<kDeep>(acc[0], W, H, a));
+            o[0] = static_cast<uint8_t>(round_sample<kDeep, kLinear>(acc[0], W, H, a, ltab));
             if (three) {
-              o[1] = static_cast<uint8_t>(round_sample<kDeep>(acc[1], W, H, a));
-              o[2] = static_cast<uint8_t>(round_sample<kDeep>(acc[2], W, H, a));
+              o[1] = static_cast<uint8_t>(round_sample<kDeep, kLinear>(acc[1], W, H, a, ltab));
+              o[2] = static_cast<uint8_t>(round_sample<kDeep, kLinear>(acc[2], W, H, a, ltab));
             }
-            if (two) o[1] = static_cast<uint8_t>(round_sample<kDeep>(acc[1], W, H, a));
+            if (two) o[1] = static_cast<uint8_t>(round_sample<kDeep, kLinear>(acc[1], W, H, a, ltab));
             ++yo;
             const uint32_t wn = yo < oy0 + th ? resize_weight(yo, y, H, h2) : 0u;
 #pragma unroll
@@ -482,6 +597,40 @@ int resize_ragged_flat_launch(bool placed, int format, const float* pscale, cons
     hipLaunchKernelGGL((resize_ragged_kernel<false, true, true>), dim3(tiles), dim3(256), 0, st, a);
   } else {
     hipLaunchKernelGGL((resize_ragged_kernel<false, false, true>), dim3(tiles), dim3(256), 0, st, a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the linear instantiations (sjpeg_hip_linear_ragged_src): the arguments of the plain launch, or of the flat one
+int resize_ragged_linear_launch(bool placed, int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten* flatten,
+                                const ResizeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st) {
+  const SourceLayout& L = *source_layout(format);
+  FlatResizeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frames = d_frames;
+  a.nframes = nframes;
+  a.kind = L.kind;
+  a.channels = L.rgb_like ? 3 : 1;
+  a.pix_step = L.plane[0].step * L.esz;
+  a.cls = L.kind != kElemU8 ? kResizeElems : (L.one_pitch || a.channels == 1) ? kResizePlanes : kResizePacked;
+  for (int c = 0; c < 3; ++c) { a.pscale[c] = pscale[c]; a.pbias[c] = pbias[c]; }
+  if (flatten != nullptr) {
+    for (int c = 0; c < 3; ++c) a.bg[c] = flatten->background[c];
+    a.premultiplied = flatten->premultiplied;
+    a.ascale = flatten->alpha_scale;
+    a.abias = flatten->alpha_bias;
+    if (placed) {
+      hipLaunchKernelGGL((resize_ragged_kernel<false, true, true, false, true>), dim3(tiles), dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((resize_ragged_kernel<false, false, true, false, true>), dim3(tiles), dim3(256), 0, st, a);
+    }
+  } else {
+    const ResizeArgs& plain = a;
+    if (placed) {
+      hipLaunchKernelGGL((resize_ragged_kernel<false, true, false, false, true>), dim3(tiles), dim3(256), 0, st, plain);
+    } else {
+      hipLaunchKernelGGL((resize_ragged_kernel<false, false, false, false, true>), dim3(tiles), dim3(256), 0, st, plain);
+    }
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "light_math.h"
 #include "orient_math.h"
 #include "ragged_aux.h"
 #include "reduce_round.h"
@@ -49,6 +50,18 @@ int flatten_check(const std::string& who, int format, const sjpeg_hip_flatten& f
   }
   if (L->kind != kElemU8 && !(std::isfinite(flatten.alpha_scale) && std::isfinite(flatten.alpha_bias))) {
     return set_error(SJPEG_HIP_EINVAL, who + ": flatten: alpha_scale and alpha_bias must be finite");
+  }
+  return 0;
+}
+
+int light_check(const std::string& who, int light, int format) {
+  if (light != SJPEG_HIP_LIGHT_CODED && light != SJPEG_HIP_LIGHT_LINEAR_SRGB) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": light " + std::to_string(light) + " is not SJPEG_HIP_LIGHT_CODED (0) or SJPEG_HIP_LIGHT_LINEAR_SRGB (1)");
+  }
+  const SourceLayout* const L = source_layout(format);
+  if (light != SJPEG_HIP_LIGHT_CODED && L != nullptr && !resizable(*L)) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": light: the samples of " + source_format_name(format) +
+                                           " are not RGB light (linear light takes an RGB-like or a gray format)");
   }
   return 0;
 }
@@ -171,6 +184,27 @@ int sjpeg_hip_fit_size(int width, int height, int box_width, int box_height, int
   }
   *fitted_width = static_cast<int>(w < 1 ? 1 : w);
   *fitted_height = static_cast<int>(h < 1 ? 1 : h);
+  return 0;
+}
+
+int sjpeg_hip_light_table(int light, uint16_t table[256]) {
+  static const std::string who = "sjpeg_hip_light_table";
+  if (table == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": table == NULL");
+  if (int rc = sjpeg_internal::light_check(who, light, -1)) return rc;
+  for (int b = 0; b < 256; ++b) table[b] = light == SJPEG_HIP_LIGHT_CODED ? static_cast<uint16_t>(b) : sjpeg_internal::kLightSrgb[b];
+  return 0;
+}
+
+int sjpeg_hip_light_round(int light, uint64_t S, uint32_t W, uint32_t H, uint32_t* byte) {
+  static const std::string who = "sjpeg_hip_light_round";
+  if (byte == nullptr) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": byte == NULL");
+  if (int rc = sjpeg_internal::light_check(who, light, -1)) return rc;
+  if (W < 1 || H < 1 || W > 65535 || H > 65535) {
+    return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": bad dimensions " + std::to_string(W) + "x" + std::to_string(H));
+  }
+  const uint64_t top = (light == SJPEG_HIP_LIGHT_CODED ? 255ull : 65535ull) * W * H;
+  if (S > top) return sjpeg_internal::set_error(SJPEG_HIP_EINVAL, who + ": S " + std::to_string(S) + " is above the " + std::to_string(top) + " of a full-scale cell");
+  *byte = light == SJPEG_HIP_LIGHT_CODED ? sjpeg_internal::resize_round(S, W, H) : sjpeg_internal::light_round(S, W, H, sjpeg_internal::kLightSrgb);
   return 0;
 }
 
