@@ -1550,6 +1550,120 @@ int sjpeg_hip_encode_ragged_sheet_linear_packed_src(sjpeg_hip_engine* engine, in
                                                     int* modes, float* q_out, float* value_out /*host [nsheets], each may be NULL*/,
                                                     void* stream);
 
+/* ---- unsharp mask: thumbnails sharpened inside the ragged call ----
+ * An area average is a box filter: a 1080p frame brought to 320 x 180 comes out soft, and every thumbnailer sharpens
+ * behind its resize (vipsthumbnail --sharpen, ImageMagick's -thumbnail ... -unsharp, an image CDN's sharpen=).  The
+ * entries below do it in ONE more small launch behind the launch that makes the pictures, on the made bytes, with one
+ * right answer in integers.  ("sharp" elsewhere in this header is the reference's sharp YUV conversion; this is
+ * "unsharp" throughout.)
+ * THE DEFINITION.  A made plane is rows of bytes with a channel step c: 3 for interleaved RGB, 1 for gray and for a Y,
+ * U or V plane.  Sample p at byte x of row y has the 3 x 3 neighbourhood n[i][j] of the samples of its channel at
+ * x - c, x, x + c in rows y - 1, y, y + 1; the edge is replicated: an index outside the picture takes the nearest
+ * sample of that channel inside it.  With the weights w = [1 2 1] x [1 2 1] (sum 16):
+ *   S   = sum of w[i][j] * n[i][j]                  (0 .. 16 * 255)
+ *   D   = 16 * p - S                                (-4080 .. 4080: sixteen times p minus the blur)
+ *   out = p                                         if |D| < 16 * threshold
+ *   out = min(255, max(0, floor((512 * p + amount * D + 256) / 512)))   otherwise
+ * amount is 0..255 in 32nds (32: the classic 2 p - blur), threshold 0..255 in byte levels (0: every sample is
+ * sharpened); floor is toward minus infinity (an arithmetic shift by 9); everything fits an int32:
+ * |amount * D| <= 1 040 400.  Consequences:
+ *   amount == 0 is the identity; so is threshold 255 (p itself has weight 4 in S, so |D| <= 12 * 255 < 16 * 255).
+ *   A constant picture and a 1 x 1 picture come back unchanged.
+ *   The kernel is symmetric under the eight EXIF orientations: sharpening commutes with the turn.
+ * Known answers: every row 100 100 100 100 200 200 200 200 with amount 32, threshold 0 gives 100 100 100 75 225 200
+ * 200 200, with amount 64 .. 50 250 ..; with threshold 26 the rows are unchanged, with 25 sharpened (|D| = 400 = 16 *
+ * 25); the row 10 12 with amount 32 gives 10 13 (the tie rounds up); a 4 x 4 checkerboard with 100 at (0, 0) and 200
+ * beside it, amount 32, has the first row 63 250 50 238.
+ * ORDER OF STEPS.  RGB-like and gray formats: pixel transform, flatten, light table, average, inverse, turn, unsharp.
+ * Video: resize, turn, colour conversion, unsharp on Y ONLY -- U and V are, byte for byte, what the entry without
+ * unsharp makes.  What the filter reads are the made bytes, whatever made them.
+ * JPEG CONTRACT, the family's usual one: frame k's JPEG is byte for byte what the _full_ call makes of the uint8
+ * picture the shape entry below returns.  What is written into a made row's padding is unspecified.
+ *
+ * sjpeg_hip_unsharp: amount and threshold as above -- every value of either is valid --; a reserved byte that is not 0
+ *   is SJPEG_HIP_EINVAL, naming the frame.  One for the call (unsharp_per_frame == 0: unsharp[0]) or one per frame.
+ * sjpeg_hip_unsharp_ragged_src: sjpeg_hip_linear_ragged_src's arguments plus `unsharp, unsharp_per_frame` behind the
+ *   orientations.  Same output layout, same size (sjpeg_hip_orient_ragged_bytes).
+ * sjpeg_hip_encode_ragged_unsharp_src / _unsharp_packed_src: the _linear_ encode entries plus the two.
+ * sjpeg_hip_unsharp_ragged_yuv_src, sjpeg_hip_encode_ragged_yuv_unsharp_src / _yuv_unsharp_packed_src: the _yuv16
+ *   entries plus the two behind `depth`; depth == NULL: planes of bytes (the _yuv_converted_ entries' path).
+ * unsharp == NULL, or amount 0 for every frame, is a pass-through: exactly the corresponding entry above on the same
+ *   arguments, with that entry's name in the messages.  Otherwise EVERY frame goes through the resize kernel, at its
+ *   own size with orientation 1 too, so "sharpen only" works for any source format; the made pictures stay in the
+ *   engine's memory and the sharpened ones go to the caller's buffer or, for the encodes, into engine memory of their
+ *   own (counted by sjpeg_hip_engine_scratch_bytes, released by sjpeg_hip_engine_trim).
+ * SJPEG_HIP_EINVAL before any device work: a reserved byte (the frame named); a YUV-plane format given to the RGB
+ *   entries, or another format given to the _yuv_ ones (named, the other entry pointed at); and every check the
+ *   corresponding entry above makes.  Contact sheets are not sharpened here.
+ * Host only, for bindings and tests:
+ *   sjpeg_hip_unsharp_sample: *byte = out for the neighbourhood n[3 * i + j] (n[4] is p); a NULL pointer or an amount
+ *     or threshold outside 0..255 is SJPEG_HIP_EINVAL. */
+typedef struct sjpeg_hip_unsharp {
+  uint8_t amount;                 /* 0..255 in 32nds: 32 is out = 2 p - blur */
+  uint8_t threshold;              /* 0..255 in byte levels: a sample closer than this to its blur is left alone */
+  uint8_t reserved[2];            /* 0 */
+} sjpeg_hip_unsharp;              /* 4 bytes */
+int sjpeg_hip_unsharp_sample(int amount, int threshold, const uint8_t n[9], uint32_t* byte);
+int sjpeg_hip_unsharp_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                 int light, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                 const uint8_t* orientations /*host [nframes], or NULL*/,
+                                 const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                 void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format,
+                                 void* stream);
+int sjpeg_hip_encode_ragged_unsharp_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                        const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                        const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/, int light,
+                                        const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                        const uint8_t* orientations /*host [nframes], or NULL*/,
+                                        const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                        const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                        void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                        int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_unsharp_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                               const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                               const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                               int light, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                               const uint8_t* orientations /*host [nframes], or NULL*/,
+                                               const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                               const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                               void* d_packed, size_t packed_capacity,
+                                               uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                               int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                               void* stream);
+int sjpeg_hip_unsharp_ragged_yuv_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                     const uint8_t* orientations /*host [nframes], or NULL*/,
+                                     const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                     const sjpeg_hip_yuv_depth* depth /*or NULL: planes of bytes*/,
+                                     const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                     void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/,
+                                     int* out_format, void* stream);
+int sjpeg_hip_encode_ragged_yuv_unsharp_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                            const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                            const uint8_t* orientations /*host [nframes], or NULL*/,
+                                            const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                            const sjpeg_hip_yuv_depth* depth /*or NULL: planes of bytes*/,
+                                            const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                            const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                            void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                            int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_yuv_unsharp_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                   const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                   const sjpeg_hip_ragged_params* params,
+                                                   const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                   const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                   const sjpeg_hip_yuv_colour* colour /*host: [nframes], [1] or NULL*/, int colour_per_frame,
+                                                   const sjpeg_hip_yuv_depth* depth /*or NULL: planes of bytes*/,
+                                                   const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                                   const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                   void* d_packed, size_t packed_capacity,
+                                                   uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                   int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                   void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

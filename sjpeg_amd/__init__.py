@@ -1009,6 +1009,10 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_linear_src", "sjpeg_hip_encode_ragged_linear_packed_src",
     "sjpeg_hip_sheet_ragged_linear_src", "sjpeg_hip_encode_ragged_sheet_linear_src",
     "sjpeg_hip_encode_ragged_sheet_linear_packed_src",
+    # (bound by sjpeg_amd/unsharp.py)
+    "sjpeg_hip_unsharp_sample", "sjpeg_hip_unsharp_ragged_src", "sjpeg_hip_encode_ragged_unsharp_src",
+    "sjpeg_hip_encode_ragged_unsharp_packed_src", "sjpeg_hip_unsharp_ragged_yuv_src",
+    "sjpeg_hip_encode_ragged_yuv_unsharp_src", "sjpeg_hip_encode_ragged_yuv_unsharp_packed_src",
 ]
 
 

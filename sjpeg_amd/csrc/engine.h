@@ -215,6 +215,9 @@ struct sjpeg_hip_engine {
   // ... and the descriptors of the colour launch that may follow the resize launch of the same call (yuv_colour.hip): a
   // buffer of their own, so that their upload never lands on descriptors the resize kernel is still to read
   DevBuf<uint4> colour_desc;
+  // ... and the unsharp launch behind either (unsharp.hip), which works out of place: the FINAL pictures of an encode
+  // entry -- the made ones stay in `reduced` while it reads them -- and its descriptors, again buffers of their own
+  DevBuf<uint4> final_pictures, unsharp_desc;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;

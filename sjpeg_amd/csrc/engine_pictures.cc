@@ -1,6 +1,7 @@
 // engine_pictures.cc -- the engine's half of the entries that MAKE pictures for a ragged call: reduction, resize, the
-// YUV-plane resize, contact sheets and the video colour conversion.  The plans come from the *_plan.cc files, the kernels
-// and their launch functions live in reduce.hip, resize.hip and yuv_colour.hip (ragged_aux.h); here the call is ordered
+// YUV-plane resize, contact sheets, the video colour conversion and the unsharp mask.  The plans come from the *_plan.cc
+// files, the kernels and their launch functions live in reduce.hip, resize.hip, yuv_colour.hip and unsharp.hip
+// (ragged_aux.h); here the call is ordered
 // behind the engine's earlier work, the engine's memory is sized and the descriptors go up.  Host only.
 #include "engine.h"
 
@@ -133,6 +134,34 @@ int sjpeg_internal::engine_yuv_colour(sjpeg_hip_engine* e, const std::string& wh
   if (int rc = sync_uploads(e, st)) return rc;
   if (yuv_colour_launch(plan.placed, reinterpret_cast<const YuvColourFrame*>(e->colour_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
     return fail(SJPEG_HIP_ERUNTIME, who + ": yuv_colour_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
+}
+
+// ... and of the unsharp mask (unsharp_plan.cc): the launch behind the launches that made the pictures at src_base, on
+// the same stream, out of place.  Both buffers are sized before a pointer into either is taken.
+int sjpeg_internal::engine_unsharp(sjpeg_hip_engine* e, const std::string& who, const UnsharpPlan& plan, const uint8_t* src_base, uint8_t* d_out,
+                                   uint8_t** base, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<UnsharpPlane> desc = plan.planes;
+  const size_t desc_bytes = sizeof(UnsharpPlane) * desc.size();
+  if (d_out == nullptr) {
+    if (e->final_pictures.ensure(plan.bytes / 16 + 1) != 0) {
+      return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(plan.bytes) + " bytes of sharpened pictures");
+    }
+  }
+  if (int rc = e->unsharp_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (d_out == nullptr) d_out = reinterpret_cast<uint8_t*>(e->final_pictures.p);
+  if (base != nullptr) *base = d_out;
+  for (UnsharpPlane& d : desc) {
+    d.src = src_base + reinterpret_cast<uintptr_t>(d.src);
+    d.dst = d_out + reinterpret_cast<uintptr_t>(d.dst);
+  }
+  if (plan.tiles == 0) return 0;
+  if (int rc = upload(e, e->unsharp_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (unsharp_launch(reinterpret_cast<const UnsharpPlane*>(e->unsharp_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, who + ": unsharp_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
   }
   return 0;
 }

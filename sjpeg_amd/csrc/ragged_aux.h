@@ -319,6 +319,46 @@ int yuv_colour_launch(bool placed, const YuvColourFrame* d_frames, int nframes, 
 // kernel launched on `stream`, behind the resize launch that made the planes.  No tiles: nothing is done.
 int engine_yuv_colour(sjpeg_hip_engine* e, const std::string& who, const YuvColourPlan& plan, uint8_t* base, void* stream);
 
+// ---- unsharp mask (sjpeg_hip_unsharp_ragged_src; unsharp_plan.cc, unsharp.hip): the made pictures of any plan above
+// but a sheet's, sharpened by ONE launch behind the launch that made them, out of place -- read at one base, written in
+// the same layout at another.  One descriptor per PLANE to write, a plane rows of bytes with a channel step; the flat
+// grid runs over the tiles of every plane of every frame, a workgroup finds its plane by the binary search over
+// tile_base.  A tile is kUnsharpTileDwords dwords x kUnsharpTileRows rows of the plane, a plane's tiles in row-major
+// order.  A plane with amount 0 (U and V) is copied by the same code.
+constexpr unsigned kUnsharpTileDwords = 64, kUnsharpTileRows = 16;
+struct UnsharpPlane {
+  const uint8_t* src;                    // the made plane's first sample: a multiple of 4 (the plan: from the buffer's start)
+  uint8_t* dst;                          // ... and where the sharpened one goes
+  unsigned width_bytes, rows;            // the samples of a row (a pixel of interleaved RGB: three), the rows
+  unsigned src_stride, dst_stride;       // bytes between rows: multiples of 4, each at least width_bytes rounded up to 4
+  unsigned step;                         // bytes between two samples of a channel: 3 (interleaved RGB) or 1
+  unsigned amount, threshold;            // sjpeg_hip_unsharp's, 0..255 each
+  unsigned tile_base;                    // the plane's first workgroup in the flat grid
+};
+struct UnsharpPlan {
+  std::vector<UnsharpPlane> planes;      // frame after frame; src == dst: the offset from the pictures' base
+  unsigned tiles = 0;
+  size_t bytes = 0;                      // what the pictures take from their base: the plan's that made them (the kind sets it)
+};
+// 0 for parameters the entries take (NULL: none to check), else SJPEG_HIP_EINVAL: a reserved byte that is not 0; the
+// message names the frame (unsharp_per_frame == 0: unsharp[0] is every frame's)
+int unsharp_check(const std::string& who, int nframes, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame);
+// NULL, or amount 0 for every frame: there is nothing to sharpen
+bool unsharp_all_zero(int nframes, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame);
+// The parameters checked, then the descriptors of `made` -- nframes made pictures of `format` (SJPEG_HIP_SRC_RGB, _GRAY,
+// _YUV420 or _YUV444, anything else is refused) standing at `base`, as a plan kind's frames() reports them: one plane
+// of step 3, one of step 1, or Y, U, V of step 1 with U's and V's amount 0.  A plane or stride that is no multiple of
+// 4, a stride below the row and a batch of more than 0x7fffffff tiles are refused, naming the frame.
+int unsharp_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* made, const uint8_t* base,
+                 const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, UnsharpPlan* plan);
+int unsharp_launch(const UnsharpPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
+// The engine's half (engine_pictures.cc): the descriptors rebased -- src to src_base, dst to d_out --, uploaded into a
+// buffer of their own and the kernel launched on `stream`, behind the launch that made the pictures.  d_out == NULL:
+// into the engine's memory for FINAL pictures, plan.bytes of it -- apart from the one for reduced pictures, where the made
+// ones stay; counted by sjpeg_hip_engine_scratch_bytes and released by sjpeg_hip_engine_trim; *base says where.
+int engine_unsharp(sjpeg_hip_engine* e, const std::string& who, const UnsharpPlan& plan, const uint8_t* src_base, uint8_t* d_out, uint8_t** base,
+                   void* stream);
+
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
 // out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's

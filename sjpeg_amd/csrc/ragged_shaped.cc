@@ -1,7 +1,8 @@
 // ragged_shaped.cc -- the ragged entries on pictures that are SHAPED inside the call: reduced by a factor (reduce.hip),
 // resized to a size, turned upright by an EXIF orientation and flattened over a background (resize.hip), the same for
 // the YUV-plane formats (yuv_resize_plan.cc), their samples bytes or 16-bit words, and placed into contact sheets
-// (sheet_plan.cc).  Per family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
+// (sheet_plan.cc), and sharpened by the unsharp mask behind any of it but a sheet (unsharp_plan.cc, unsharp.hip).  Per
+// family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
 // its packed twin: the pictures into the engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
 //
 // Every entry fills a call description (ragged_aux.h: RaggedCall, RaggedOut) and names a plan KIND below; the bodies
@@ -32,6 +33,8 @@ struct Shape {
   int colour_per_frame = 0;
   const sjpeg_hip_yuv_depth* depth = nullptr;
   int light = SJPEG_HIP_LIGHT_CODED;
+  const sjpeg_hip_unsharp* unsharp = nullptr;
+  int unsharp_per_frame = 0;
 };
 Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
   Shape s{nullptr, sizes, orientations, flatten, sheet};
@@ -159,6 +162,29 @@ struct SheetLinearKind : SheetKind {
   }
 };
 
+// ... and any per-frame kind K with the unsharp mask behind it (unsharp_plan.cc, unsharp.hip): K's plan, then the
+// unsharp plan of the pictures K makes -- read off K's own frames, standing at a placeholder address --; K's pictures
+// into the engine's memory, then the unsharp launch from there to the caller's buffer or the engine's final pictures.
+// The layout is K's: frames and format are K's
+template <class K>
+struct UnsharpKind : K {
+  struct Plan : K::Plan { UnsharpPlan unsharp; };
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = K::plan(who, format, n, fr, s, p)) return rc;
+    uint8_t* const at = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16));
+    std::vector<Frame> made(static_cast<size_t>(n));
+    K::frames(*p, fr, at, made.data());
+    if (int rc = unsharp_plan(who, K::format(*p), n, made.data(), at, s.unsharp, s.unsharp_per_frame, &p->unsharp)) return rc;
+    p->unsharp.bytes = p->bytes;
+    return 0;
+  }
+  static int run(sjpeg_hip_engine* e, const std::string& who, const Plan& p, uint8_t* d_out, uint8_t** base, void* stream) {
+    uint8_t* staged = nullptr;
+    if (int rc = K::run(e, who, p, nullptr, &staged, stream)) return rc;
+    return engine_unsharp(e, who, p.unsharp, staged, d_out, base, stream);
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -211,7 +237,8 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kSheetFlat[2] = SJPEG_ENTRY_NAMES("sheet_flat"), kYuvConverted[2] = SJPEG_ENTRY_NAMES("yuv_converted"),
                   kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour"), kYuv16[2] = SJPEG_ENTRY_NAMES("yuv16"),
                   kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
-                  kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear");
+                  kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear"), kUnsharp[2] = SJPEG_ENTRY_NAMES("unsharp"),
+                  kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -433,6 +460,59 @@ int sheet_linear_entry(RaggedCall c, const sjpeg_hip_sheet* sheet, const sjpeg_h
   if (int rc = encode_prologue(c, true, sheet)) return rc;
   if (int rc = light_check(*c.who, light, c.format)) return rc;
   return sheet_flow<SheetLinearKind>(c, linear_shape(sizes, orientations, flatten, sheet, light));
+}
+
+// The unsharp mask.  unsharp NULL or amount 0 for every frame: exactly the linear call (which hands on to the flattened
+// one in coded light) or, for the YUV-plane formats, the yuv16 call or without a depth the yuv_converted one, on the
+// same arguments.  Otherwise no pass-through: every frame goes through the resize kernel, at its own size and
+// orientation 1 too -- the unsharp launch reads the made pictures, whatever the source format.  A format of the other
+// family is refused by name and pointed at the entries that take it.
+bool nothing_to_sharpen(int nframes, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  // (unsharp is [nframes] only where nframes is a count)
+  return unsharp == nullptr || ((unsharp_per_frame == 0 || (nframes >= 1 && nframes <= 65535)) && unsharp_all_zero(nframes, unsharp, unsharp_per_frame));
+}
+int unsharp_family_check(const std::string& who, int format, bool yuv) {
+  const SourceLayout* const L = source_layout(format);
+  if (L == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": unknown source format");
+  const bool planes = L->cls == kSrcPlanes && L->planes >= 2;
+  if (planes == yuv) return 0;
+  if (yuv) {
+    return set_error(SJPEG_HIP_EINVAL, who + ": " + source_format_name(format) + " is not a YUV-plane format (RGB-like and gray pictures are "
+                                           "sharpened by sjpeg_hip_unsharp_ragged_src and sjpeg_hip_encode_ragged_unsharp_src)");
+  }
+  return set_error(SJPEG_HIP_EINVAL, who + ": " + source_format_name(format) + " is a YUV-plane format (decoded video is sharpened by "
+                                         "sjpeg_hip_unsharp_ragged_yuv_src and sjpeg_hip_encode_ragged_yuv_unsharp_src)");
+}
+Shape unsharp_shape(Shape s, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  s.unsharp = unsharp; s.unsharp_per_frame = unsharp_per_frame;
+  return s;
+}
+int unsharp_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2], const uint8_t* orientations,
+                  const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) return linear_entry(c, flatten, light, sizes, orientations);
+  c.who = &kUnsharp[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = unsharp_family_check(*c.who, c.format, false)) return rc;
+  if (int rc = light_check(*c.who, light, c.format)) return rc;
+  if (int rc = unsharp_check(*c.who, c.nframes, unsharp, unsharp_per_frame)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  return planned_flow<UnsharpKind<LinearKind>>(c, unsharp_shape(linear_shape(sizes, orientations, flatten, nullptr, light), unsharp, unsharp_per_frame));
+}
+int yuv_unsharp_entry(RaggedCall c, const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour, int colour_per_frame,
+                      const sjpeg_hip_yuv_depth* depth, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) {
+    if (depth == nullptr) return yuv_converted_entry(c, sizes, orientations, colour, colour_per_frame);
+    return yuv16_entry(c, sizes, orientations, colour, colour_per_frame, depth);
+  }
+  c.who = &kYuvUnsharp[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = unsharp_family_check(*c.who, c.format, true)) return rc;
+  if (depth != nullptr) { if (int rc = yuv_depth_check(*c.who, depth)) return rc; }
+  if (int rc = unsharp_check(*c.who, c.nframes, unsharp, unsharp_per_frame)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  const Shape s = unsharp_shape(Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame, depth}, unsharp, unsharp_per_frame);
+  if (depth == nullptr) return planned_flow<UnsharpKind<YuvColourKind>>(c, s);
+  return planned_flow<UnsharpKind<YuvDeepKind>>(c, s);
 }
 
 }  // namespace
@@ -860,6 +940,94 @@ int sjpeg_hip_encode_ragged_sheet_linear_packed_src(sjpeg_hip_engine* e, int for
   return sheet_linear_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                              RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sheet,
                             flatten, light, sizes, orientations);
+}
+
+// ---- ... and the unsharp mask behind any of it: the linear entries and the yuv16 entries plus `unsharp`; ONE more
+// launch over the made pictures (unsharp.hip), out of place
+int sjpeg_hip_unsharp_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                 const sjpeg_hip_flatten* flatten, int light, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                 const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, void* d_out, size_t out_bytes,
+                                 sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_unsharp_ragged_src";
+  if (nothing_to_sharpen(nframes, unsharp, unsharp_per_frame)) {
+    return sjpeg_hip_linear_ragged_src(e, format, nframes, frames, flatten, light, sizes, orientations, d_out, out_bytes, out_frames, out_format,
+                                       stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = unsharp_family_check(who, format, false)) return rc;
+  if (int rc = light_check(who, light, format)) return rc;
+  return shape_body<UnsharpKind<LinearKind>>(who, kOrientWords, e, format, nframes, frames,
+                                             unsharp_shape(linear_shape(sizes, orientations, flatten, nullptr, light), unsharp, unsharp_per_frame),
+                                             false, d_out, out_bytes, out_frames, nullptr, out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_unsharp_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                        const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, int light,
+                                        const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_unsharp* unsharp,
+                                        int unsharp_per_frame, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                        uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return unsharp_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                        {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, light, sizes, orientations, unsharp, unsharp_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_unsharp_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                               const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, int light,
+                                               const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_unsharp* unsharp,
+                                               int unsharp_per_frame, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed,
+                                               size_t packed_capacity, uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out,
+                                               float* value_out, void* stream) {
+  return unsharp_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                        RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten, light,
+                       sizes, orientations, unsharp, unsharp_per_frame);
+}
+
+int sjpeg_hip_unsharp_ragged_yuv_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                     const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_yuv_colour* colour,
+                                     int colour_per_frame, const sjpeg_hip_yuv_depth* depth, const sjpeg_hip_unsharp* unsharp,
+                                     int unsharp_per_frame, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* out_frames,
+                                     int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_unsharp_ragged_yuv_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "sharpened planes", "sjpeg_hip_resize_ragged_yuv_bytes"};
+  if (nothing_to_sharpen(nframes, unsharp, unsharp_per_frame)) {
+    if (depth == nullptr) {
+      return sjpeg_hip_convert_ragged_yuv_src(e, format, nframes, frames, sizes, orientations, colour, colour_per_frame, d_out, out_bytes,
+                                              out_frames, out_format, stream);
+    }
+    return sjpeg_hip_convert_ragged_yuv16_src(e, format, nframes, frames, sizes, orientations, colour, colour_per_frame, depth, d_out, out_bytes,
+                                              out_frames, out_format, stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (int rc = unsharp_family_check(who, format, true)) return rc;
+  const Shape s = unsharp_shape(Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame, depth}, unsharp, unsharp_per_frame);
+  if (depth == nullptr) {
+    return shape_body<UnsharpKind<YuvColourKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format,
+                                                  stream);
+  }
+  if (int rc = yuv_depth_check(who, depth)) return rc;
+  return shape_body<UnsharpKind<YuvDeepKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format,
+                                              stream);
+}
+
+int sjpeg_hip_encode_ragged_yuv_unsharp_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                            const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                            const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth,
+                                            const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, const sjpeg_hip_metadata* meta,
+                                            int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                            void* stream) {
+  return yuv_unsharp_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                            {d_out, d_sizes, modes, q_out, value_out, stream}}, sizes, orientations, colour, colour_per_frame, depth, unsharp,
+                           unsharp_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_yuv_unsharp_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                   const sjpeg_hip_ragged_params* params, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                                   const sjpeg_hip_yuv_colour* colour, int colour_per_frame, const sjpeg_hip_yuv_depth* depth,
+                                                   const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, const sjpeg_hip_metadata* meta,
+                                                   int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                   uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return yuv_unsharp_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                            RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes,
+                           orientations, colour, colour_per_frame, depth, unsharp, unsharp_per_frame);
 }
 
 }  // extern "C"
