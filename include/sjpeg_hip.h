@@ -1664,6 +1664,119 @@ int sjpeg_hip_encode_ragged_yuv_unsharp_packed_src(sjpeg_hip_engine* engine, int
                                                    int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                    void* stream);
 
+/* ---- resampling with Pillow's filters: Lanczos, bicubic, bilinear, Hamming and box windows, enlarging too ----
+ * Every shape entry above makes its picture with one filter, the exact area average: it only shrinks, it is soft, and
+ * it is this library's own answer.  The thumbnails of Python services and dataset pipelines were made by
+ * PIL.Image.resize(size, LANCZOS | BICUBIC | BILINEAR | HAMMING | BOX); the entries below make THOSE bytes -- Pillow
+ * 12.2.0's, for pictures of bytes -- in ONE launch of a kernel of its own over the batch, to sizes smaller or larger
+ * than the source on either axis.
+ * THE DEFINITION (one right answer, in integers, given the tables).  A picture of bytes, channels independent, is
+ * resampled along x, then along y, with a uint8 intermediate between the passes.  A pass whose input and output size
+ * agree is not run; both agreeing is the identity.  Along an axis from `in` to `out` samples with filter f of support
+ * s, all in IEEE double:
+ *   scale = in / out; fs = max(scale, 1.0); support = s * fs; ksize = 2 * (int)ceil(support) + 1
+ *   for output index xx:  center = (xx + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5));  n = min(in, (int)(center + support + 0.5)) - xmin
+ *     w[x] = f((x + xmin - center + 0.5) / fs) for x < n;  ww = the sum of w in index order
+ *     k[x] = w[x] / ww (left as w[x] when ww == 0)
+ *     K[x] = (int)(k[x] * 2^22 + 0.5) for k >= 0, else (int)(k[x] * 2^22 - 0.5)        (C truncation)
+ *   out[xx] = min(255, max(0, (2^21 + sum over x < n of K[x] * b[xmin + x]) >> 22))     (int32, arithmetic shift)
+ * The filters (x is made |x| first, except for lanczos):
+ *   box, support 0.5:      1 for -0.5 < x <= 0.5 on the signed x
+ *   bilinear, support 1:   1 - x for x < 1
+ *   hamming, support 1:    1 at 0, 0 for x >= 1, else sin(pi x) / (pi x) * (0.54f + 0.46f * cos(pi x)) -- the two
+ *                          constants are floats promoted to double
+ *   bicubic, support 2:    a = -0.5: ((a + 2) x - (a + 3)) x x + 1 for x < 1, (((x - 5) x + 8) x - 4) a for x < 2
+ *   lanczos, support 3:    sinc(x) * sinc(x / 3) for -3 <= x < 3, sinc(0) = 1, sinc(x) = sin(pi x) / (pi x)
+ * The tables are made on the host -- they need the host's sin and cos -- and uploaded, once per (filter, in, out) that
+ * occurs in a call; the kernel is integers only.  Two bounds are CHECKED for every table a call builds, and the kernel
+ * relies on them: every |K| < 2^23 (both factors of a product fit 24 bits), and 2^21 + 255 * max(sum of the positive
+ * K, sum of the |negative K|) < 2^31 for every sample.  Measured, not proven: over in 1..69, 100, 257, 1000, 1920, 3840
+ * and out 1..69, 100, 180, 320, 1000, 4000 and the five filters the largest |K| is 5 392 348 and the largest sum
+ * 1 377 229 532.  A table that breaks one is refused with SJPEG_HIP_EINVAL, the frame and the axis named.
+ * THE CAP.  An axis whose ksize is above 385 -- Lanczos shrinking by more than 64, box by more than 384 -- is refused
+ * before any device work, the frame, the axis, its ksize and the cap named.  Below the cap every size is taken, 1 x 1
+ * sources and 1 x 1 results included.
+ * Known answers (tests/golden/resample_pillow.npz, recorded from Pillow 12.2.0): the row 0 255 brought to 4 samples is
+ * 0 0 255 255 (box), 0 64 191 255 (bilinear), 0 19 236 255 (hamming), 0 53 202 255 (bicubic), 0 59 196 255 (lanczos);
+ * the row 10 20 30 40 250 240 230 220 brought to 2 samples is 25 235, 57 207, 38 224, 47 217, 46 220 in that order;
+ * the bilinear table of 7 -> 3 samples has the windows {0, 4}, {1, 5}, {4, 3} and its middle row is 246724 986895
+ * 1727066 986895 246724.
+ * FORMATS AND ORDER OF STEPS.  Every RGB-like and gray format the resize takes: pixel transform, flatten (optional, as
+ * in the _flattened_ entries; without it a fourth sample is dropped), resample, turn, unsharp (optional).  What the
+ * filter reads is the byte the encoder sees.  `sizes` are in the STORED orientation, 1..65535 each, and may exceed
+ * the source on either axis (NULL: every frame at its own size); the upright picture is U = turn(R), R the resampled
+ * stored picture -- the family's "resize, then turn".  It is NOT exif_transpose followed by resize: two passes with a
+ * rounded intermediate do not commute with the turn.  unsharp (NULL or amount 0 for every frame: none) is the launch
+ * of the _unsharp_ entries, unchanged, behind the resample launch.  There is no linear light and there are no contact
+ * sheets here: the entries have no `light` and no sheet argument.  The YUV-plane formats, bytes or 16-bit samples, are
+ * refused by name.
+ * EVERY frame goes through the kernel: a frame at its own size is copied (turned, flattened), as with unsharp.
+ * JPEG CONTRACT, the family's usual one: frame k's JPEG is byte for byte what the _full_ call makes of the uint8
+ * picture the shape entry below returns.  What is written into a made row's padding is unspecified.
+ *
+ * sjpeg_hip_resample: the filter, one of SJPEG_HIP_RESAMPLE_*; reserved must be 0.  One for the call
+ *   (resample_per_frame == 0: resample[0]) or one per frame, so filters mix inside a launch.
+ * sjpeg_hip_resample_ragged_bytes: the bytes the made pictures take, in the layout of the oriented pictures
+ *   (sjpeg_hip_orient_ragged_bytes: interleaved RGB or gray, rows whole dwords apart, pictures at multiples of 16); 0
+ *   for a batch the call refuses.
+ * sjpeg_hip_resample_ragged_src: the uint8 pictures into d_out; out_frames and out_format as the other shape entries.
+ * sjpeg_hip_encode_ragged_resampled_src / _resampled_packed_src: the _unsharp_ encode entries' arguments without
+ *   `light`, plus `resample, resample_per_frame` in front of the unsharp.
+ * The tables, the made pictures and the sharpened ones are engine memory, counted by sjpeg_hip_engine_scratch_bytes and
+ *   released by sjpeg_hip_engine_trim.
+ * SJPEG_HIP_EINVAL before any device work, the frame named: resample == NULL; a filter that is none of the five; a
+ *   reserved byte; a size below 1 or above 65535; an axis above the cap; a YUV-plane format (named); and the checks
+ *   of the flattened and unsharp entries on their arguments.
+ * Host only, for bindings and tests:
+ *   sjpeg_hip_resample_ksize: ksize of an axis (filter, in, out: 1..65535 each); 0 with the error set otherwise.
+ *   sjpeg_hip_resample_table: bounds[xx] = {xmin, n} and K[xx * ksize + x] (x >= n: 0) of an axis, whatever its ksize;
+ *     K_capacity counts int32s and must be at least out * ksize.  A table that breaks a bound is SJPEG_HIP_EINVAL. */
+#define SJPEG_HIP_RESAMPLE_BOX 0
+#define SJPEG_HIP_RESAMPLE_BILINEAR 1
+#define SJPEG_HIP_RESAMPLE_HAMMING 2
+#define SJPEG_HIP_RESAMPLE_BICUBIC 3
+#define SJPEG_HIP_RESAMPLE_LANCZOS 4
+typedef struct sjpeg_hip_resample {
+  uint8_t filter;                 /* SJPEG_HIP_RESAMPLE_* */
+  uint8_t reserved[3];            /* 0 */
+} sjpeg_hip_resample;             /* 4 bytes */
+int sjpeg_hip_resample_ksize(int filter, int in, int out);
+int sjpeg_hip_resample_table(int filter, int in, int out, int32_t (*bounds)[2] /*[out]*/, int32_t* K /*[out * ksize]*/, size_t K_capacity);
+size_t sjpeg_hip_resample_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                       const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                       const uint8_t* orientations /*host [nframes], or NULL*/);
+int sjpeg_hip_resample_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                  const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                  const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                  const uint8_t* orientations /*host [nframes], or NULL*/,
+                                  const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                  const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                  void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format,
+                                  void* stream);
+int sjpeg_hip_encode_ragged_resampled_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                          const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                          const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                          const uint8_t* orientations /*host [nframes], or NULL*/,
+                                          const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                          const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                          const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                          void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                          int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_resampled_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                 const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                 const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                 const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                                 const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                                 const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                 void* d_packed, size_t packed_capacity,
+                                                 uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                 int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                 void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -1013,6 +1013,9 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_unsharp_sample", "sjpeg_hip_unsharp_ragged_src", "sjpeg_hip_encode_ragged_unsharp_src",
     "sjpeg_hip_encode_ragged_unsharp_packed_src", "sjpeg_hip_unsharp_ragged_yuv_src",
     "sjpeg_hip_encode_ragged_yuv_unsharp_src", "sjpeg_hip_encode_ragged_yuv_unsharp_packed_src",
+    # (bound by sjpeg_amd/resample.py)
+    "sjpeg_hip_resample_ksize", "sjpeg_hip_resample_table", "sjpeg_hip_resample_ragged_bytes", "sjpeg_hip_resample_ragged_src",
+    "sjpeg_hip_encode_ragged_resampled_src", "sjpeg_hip_encode_ragged_resampled_packed_src",
 ]
 
 

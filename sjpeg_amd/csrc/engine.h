@@ -218,6 +218,8 @@ struct sjpeg_hip_engine {
   // ... and the unsharp launch behind either (unsharp.hip), which works out of place: the FINAL pictures of an encode
   // entry -- the made ones stay in `reduced` while it reads them -- and its descriptors, again buffers of their own
   DevBuf<uint4> final_pictures, unsharp_desc;
+  // ... and the tables of a resampling call (resample.hip): bounds and coefficients of every axis, once per key
+  DevBuf<uint4> resample_tables;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;

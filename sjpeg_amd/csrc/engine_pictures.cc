@@ -63,6 +63,34 @@ int sjpeg_internal::engine_resize(sjpeg_hip_engine* e, const std::string& who, c
   });
 }
 
+// ... and of resampling with Pillow's filters (resample_plan.cc, resample.hip): the call's tables into engine memory of
+// their own, the descriptors' table pointers rebased to it, then as the two above
+int sjpeg_internal::engine_resample(sjpeg_hip_engine* e, const std::string& who, const ResamplePlan& plan, uint8_t* d_out, uint8_t** base,
+                                    void* stream) {
+  hipStream_t st0 = static_cast<hipStream_t>(stream);
+  if (int rc = ragged_ordered(e, st0)) return rc;
+  const size_t table_bytes = plan.tables.size() * sizeof(int32_t);
+  if (e->resample_tables.ensure(table_bytes / 16 + 1) != 0) {
+    return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(table_bytes) + " bytes of resampling tables");
+  }
+  if (int rc = upload(e, e->resample_tables.p, plan.tables.data(), table_bytes, st0)) return rc;
+  std::vector<ResampleFrame> desc = plan.frames;
+  const uint8_t* const tables = reinterpret_cast<const uint8_t*>(e->resample_tables.p);
+  for (ResampleFrame& d : desc) {
+    d.xb = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.xb));
+    d.xk = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.xk));
+    d.yb = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.yb));
+    d.yk = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.yk));
+  }
+  return engine_make_pictures(e, who, "resampled", std::move(desc), plan.bytes, d_out, base, stream,
+                              [&](const ResampleFrame* d_frames, int n, hipStream_t st) {
+    if (resample_launch(plan.format, e->pscale, e->pbias, plan.flat ? &plan.flatten : nullptr, d_frames, n, plan.tiles, st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": resample_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+  });
+}
+
 // ... and of the YUV-plane formats: a descriptor per plane, the kernel's other instantiation
 int sjpeg_internal::engine_yuv_resize(sjpeg_hip_engine* e, const std::string& who, const YuvResizePlan& plan, uint8_t* d_out, uint8_t** base,
                                       void* stream) {

@@ -359,6 +359,59 @@ int unsharp_launch(const UnsharpPlane* d_planes, int nplanes, unsigned tiles, hi
 int engine_unsharp(sjpeg_hip_engine* e, const std::string& who, const UnsharpPlan& plan, const uint8_t* src_base, uint8_t* d_out, uint8_t** base,
                    void* stream);
 
+// ---- resampling with Pillow's filters (sjpeg_hip_resample_ragged_src; resample_plan.cc, resample.hip,
+// resample_math.h): every frame resampled along x, then along y, by the tables of its two axes, to a size that may be
+// larger or smaller on either axis, then turned.  One descriptor per frame; the flat grid runs over the tiles of every
+// frame, a workgroup finds its frame by the binary search over tile_base.  A tile is tw x kResampleTileRows samples of
+// the resampled STORED picture (tw one of kResampleTileCols, 16, 8, 4: the widest whose segment -- the union of its
+// x-windows -- is at most kResampleSegmentMax source pixels), a frame's tiles in row-major order.  The tables of a call
+// lie in ONE buffer of int32: per (filter, in, out) that occurs, once, the bounds {xmin, n} of every output sample and
+// then its ksize coefficients; a pass that is not run (in == out) has the identity table, one tap of 2^22.  An axis
+// whose ksize is above kResampleKsizeMax is refused.
+constexpr unsigned kResampleTileCols = 32, kResampleTileRows = 16, kResampleStageBytes = 16384, kResampleSegmentMax = 4096;
+constexpr int kResampleKsizeMax = 385;
+struct ResampleFrame {
+  const uint8_t* src;                    // plane 0, row 0
+  long long row_stride;                  // may be negative
+  long long off[3];                      // where R, G and B (gray: the value, thrice) lie from src (layout_rgb_offsets)
+  uint8_t* dst;                          // the made picture: a multiple of 16 (the plan: from the buffer's start)
+  const int32_t *xb, *xk, *yb, *yk;      // the axes' bounds and coefficients (the plan: int32s from the tables' start)
+  int W, H, w2, h2;                      // the source's and the resampled stored picture's size
+  int ksx, ksy;                          // coefficients a row of xk, yk
+  int tw;                                // the tile's width
+  unsigned tiles_x, dst_stride;          // tiles a row of tiles; bytes between the made picture's rows
+  unsigned tile_base, orient;            // the frame's first workgroup in the flat grid; its EXIF orientation, 1..8
+};
+struct ResamplePlan {
+  int format = 0, resized_format = 0;
+  std::vector<ResampleFrame> frames;
+  std::vector<int32_t> tables;           // what goes up: every table of the call, once
+  int ntables = 0;                       // ... how many (identity tables included)
+  size_t bytes = 0;
+  unsigned tiles = 0;
+  bool flat = false;                     // the frames are flattened as they are staged
+  sjpeg_hip_flatten flatten = {};
+};
+// 0 for parameters the entries take, else SJPEG_HIP_EINVAL: resample == NULL, a filter that is none of
+// SJPEG_HIP_RESAMPLE_*, a reserved byte that is not 0; the message names the frame (resample_per_frame == 0:
+// resample[0] is every frame's)
+int resample_check(const std::string& who, int nframes, const sjpeg_hip_resample* resample, int resample_per_frame);
+// Checks the format (an RGB-like or gray one: a YUV-plane format is refused by name), the parameters, the sizes
+// (sizes[f] = (w', h'), 1..65535 each, in the STORED orientation; NULL: every frame at its own size), the orientations
+// and the flatten as resize_plan does, every axis's ksize against the cap and every table against resample_math.h's
+// two bounds, then plans; the message names the frame and the axis.  The picture in the buffer is the upright one, in
+// reduce_round.h's layout.  The frames' planes and strides are the caller's to check (ragged_check).
+int resample_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                  const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_flatten* flatten,
+                  ResamplePlan* plan);
+void resample_plan_frames(const ResamplePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
+// flatten NULL: not flat
+int resample_launch(int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten* flatten, const ResampleFrame* d_frames,
+                    int nframes, unsigned tiles, hipStream_t st);
+// The engine's half (engine_pictures.cc), as engine_resize; the tables go into engine memory of their own, counted by
+// sjpeg_hip_engine_scratch_bytes and released by sjpeg_hip_engine_trim
+int engine_resample(sjpeg_hip_engine* e, const std::string& who, const ResamplePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
+
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own
 // out_offset, as ever) and hands it down to ragged_encode(), whose launches place their frames behind the engine's

@@ -1,7 +1,8 @@
 // ragged_shaped.cc -- the ragged entries on pictures that are SHAPED inside the call: reduced by a factor (reduce.hip),
 // resized to a size, turned upright by an EXIF orientation and flattened over a background (resize.hip), the same for
 // the YUV-plane formats (yuv_resize_plan.cc), their samples bytes or 16-bit words, and placed into contact sheets
-// (sheet_plan.cc), and sharpened by the unsharp mask behind any of it but a sheet (unsharp_plan.cc, unsharp.hip).  Per
+// (sheet_plan.cc), sharpened by the unsharp mask behind any of it but a sheet (unsharp_plan.cc, unsharp.hip), and
+// resampled with Pillow's filters, enlarging too (resample_plan.cc, resample.hip).  Per
 // family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
 // its packed twin: the pictures into the engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
 //
@@ -35,6 +36,8 @@ struct Shape {
   int light = SJPEG_HIP_LIGHT_CODED;
   const sjpeg_hip_unsharp* unsharp = nullptr;
   int unsharp_per_frame = 0;
+  const sjpeg_hip_resample* resample = nullptr;
+  int resample_per_frame = 0;
 };
 Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
   Shape s{nullptr, sizes, orientations, flatten, sheet};
@@ -162,6 +165,18 @@ struct SheetLinearKind : SheetKind {
   }
 };
 
+// ... and the one that resamples with Pillow's filters (sjpeg_hip_resample_ragged_src; resample_plan.cc, resample.hip):
+// a kernel and tables of its own, the resize kind's layout -- sizes may exceed the source, there is no light
+struct ResampleKind : PerFrameKind {
+  using Plan = ResamplePlan;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return resample_plan(who, format, n, fr, s.sizes, s.orientations, s.resample, s.resample_per_frame, s.flatten, p);
+  }
+  static int format(const Plan& p) { return p.resized_format; }
+  static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { resample_plan_frames(p, fr, base, out); }
+  static constexpr auto run = engine_resample;
+};
+
 // ... and any per-frame kind K with the unsharp mask behind it (unsharp_plan.cc, unsharp.hip): K's plan, then the
 // unsharp plan of the pictures K makes -- read off K's own frames, standing at a placeholder address --; K's pictures
 // into the engine's memory, then the unsharp launch from there to the caller's buffer or the engine's final pictures.
@@ -238,7 +253,7 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour"), kYuv16[2] = SJPEG_ENTRY_NAMES("yuv16"),
                   kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
                   kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear"), kUnsharp[2] = SJPEG_ENTRY_NAMES("unsharp"),
-                  kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp");
+                  kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp"), kResampled[2] = SJPEG_ENTRY_NAMES("resampled");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -513,6 +528,27 @@ int yuv_unsharp_entry(RaggedCall c, const int32_t (*sizes)[2], const uint8_t* or
   const Shape s = unsharp_shape(Shape{nullptr, sizes, orientations, nullptr, nullptr, colour, colour_per_frame, depth}, unsharp, unsharp_per_frame);
   if (depth == nullptr) return planned_flow<UnsharpKind<YuvColourKind>>(c, s);
   return planned_flow<UnsharpKind<YuvDeepKind>>(c, s);
+}
+
+// Resampling with Pillow's filters.  No pass-through: every frame goes through the resample kernel, at its own size too
+// (a copy: the identity tables).  unsharp NULL or amount 0 for every frame: the made pictures are the call's; otherwise
+// the unsharp launch runs behind the resample launch, unchanged.
+Shape resample_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_resample* resample,
+                     int resample_per_frame, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  Shape s{nullptr, sizes, orientations, flatten};
+  s.resample = resample; s.resample_per_frame = resample_per_frame;
+  s.unsharp = unsharp; s.unsharp_per_frame = unsharp_per_frame;
+  return s;
+}
+int resampled_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                    const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  c.who = &kResampled[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = resample_check(*c.who, c.nframes, resample, resample_per_frame)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  const Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, unsharp, unsharp_per_frame);
+  if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) return planned_flow<ResampleKind>(c, s);
+  return planned_flow<UnsharpKind<ResampleKind>>(c, s);
 }
 
 }  // namespace
@@ -1028,6 +1064,48 @@ int sjpeg_hip_encode_ragged_yuv_unsharp_packed_src(sjpeg_hip_engine* e, int form
   return yuv_unsharp_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                             RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, sizes,
                            orientations, colour, colour_per_frame, depth, unsharp, unsharp_per_frame);
+}
+
+// ---- ... and resampling with Pillow's filters: box, bilinear, Hamming, bicubic and Lanczos windows, enlarging too; ONE
+// launch of a kernel of its own (resample.hip), optionally the unsharp launch behind it
+int sjpeg_hip_resample_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                  const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                  const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_unsharp* unsharp,
+                                  int unsharp_per_frame, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format,
+                                  void* stream) {
+  static const std::string who = "sjpeg_hip_resample_ragged_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "resampled pictures", "sjpeg_hip_resample_ragged_bytes"};
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (resample == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": resample == NULL");
+  const Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, unsharp, unsharp_per_frame);
+  if (nothing_to_sharpen(nframes, unsharp, unsharp_per_frame)) {
+    return shape_body<ResampleKind>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format, stream);
+  }
+  return shape_body<UnsharpKind<ResampleKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format,
+                                               stream);
+}
+
+int sjpeg_hip_encode_ragged_resampled_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                          const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                          const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame,
+                                          const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, const sjpeg_hip_metadata* meta,
+                                          int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                          void* stream) {
+  return resampled_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                          {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, sizes, orientations, resample, resample_per_frame, unsharp,
+                         unsharp_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_resampled_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                 const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                 const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_resample* resample,
+                                                 int resample_per_frame, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame,
+                                                 const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_packed, size_t packed_capacity,
+                                                 uint64_t* d_offsets, uint64_t* d_sizes, int* modes, float* q_out, float* value_out,
+                                                 void* stream) {
+  return resampled_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                          RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten, sizes,
+                         orientations, resample, resample_per_frame, unsharp, unsharp_per_frame);
 }
 
 }  // extern "C"
