@@ -1712,6 +1712,9 @@ int sjpeg_hip_encode_ragged_yuv_unsharp_packed_src(sjpeg_hip_engine* engine, int
  * sheets here: the entries have no `light` and no sheet argument.  The YUV-plane formats, bytes or 16-bit samples, are
  * refused by name.
  * EVERY frame goes through the kernel: a frame at its own size is copied (turned, flattened), as with unsharp.
+ * A picture more than 100 times as tall as wide that is brought to fewer rows is resampled along x first here too;
+ * Pillow resamples such a picture along y first, so for it these entries do not make Pillow's bytes (the box entries
+ * below refuse it).
  * JPEG CONTRACT, the family's usual one: frame k's JPEG is byte for byte what the _full_ call makes of the uint8
  * picture the shape entry below returns.  What is written into a made row's padding is unspecified.
  *
@@ -1776,6 +1779,116 @@ int sjpeg_hip_encode_ragged_resampled_packed_src(sjpeg_hip_engine* engine, int f
                                                  uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
                                                  int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                  void* stream);
+
+/* ---- ... from a source box and behind a reduce: Image.thumbnail and ImageOps.fit ----
+ * The thumbnails of Python services mostly do not come from a bare resize.  Image.thumbnail(box) -- BICUBIC,
+ * reducing_gap 2.0 -- first runs Image.reduce, an integer box average with Pillow's own rounding, where the source is
+ * at least 2 * gap times the target, and resizes the small picture from a FRACTIONAL source box; ImageOps.fit, crop to
+ * fill, is a resize from a fractional crop.  The entries below make those bytes -- Pillow 12.2.0's -- of the same
+ * formats, in the same order of steps and under the same JPEG contract as the _resampled_ entries above.  The reduce is
+ * also what makes large shrinks cheap, and it lifts THE CAP: the cap applies to the window behind the reduce, so 4000 ->
+ * 40 samples with Lanczos and reducing_gap 2.0 is a factor 50 and a window of 13.
+ * THE DEFINITION of the box entries (sjpeg_amd/csrc/resample_math.h states it once, for the host, the kernel and the
+ * tests).  A frame has the stored picture P of W x H bytes per channel (behind the pixel transform and the flatten),
+ * the target (w2, h2), the filter of support s, a source box (l, t, r, b) in doubles, in P's samples, and a
+ * reducing_gap g.  "double" is IEEE double as Python does it, int() truncates toward zero.
+ *   1. The box: 0 <= l, 0 <= t, r <= W, b <= H, r - l > 0, b - t > 0, else refused.  (Pillow takes an empty box; these
+ *      entries do not.)  The all-zero box is (0, 0, W, H).
+ *   2. The reduce, where g is not 0: fx = int((r - l) / w2 / g) or 1, fy likewise.  Both 1: nothing.  Else, with
+ *      sx = (r - l) / w2, sy = (b - t) / h2 and u = s - 0.5, the safe box is R = (max(0, int(l - u sx)),
+ *      max(0, int(t - u sy)), min(W, ceil(r + u sx)), min(H, ceil(b + u sy))); the reduced picture has
+ *      ceil((R2 - R0) / fx) x ceil((R3 - R1) / fy) samples, each of a block of n = fx * fy source samples from (R0, R1)
+ *      on, fewer on the right and bottom edge: ((S + n / 2) * m(n)) >> 24 in uint32, S the block's sum, n / 2 the
+ *      integer quotient, m(n) = (uint32)(4294967296.0f / (float)(256 * n)) -- a FLOAT32 division, truncated; it is not
+ *      floor(2^24 / n), and the sample is not the exact half-up average of the _reduced_ entries.  The box becomes
+ *      ((l - R0) / fx, (t - R1) / fy, (r - R0) / fx, (b - R1) / fy) in double, and P, W, H are the reduced picture's.
+ *   3. H > 100 * W and h2 < H: refused -- Pillow resamples such a picture along y first.
+ *   4. The tables, of the box rounded to float32, bf: the x pass runs if w2 != W or bf[0] != 0 or bf[2] != W, the y pass
+ *      likewise; a pass that does not run has the identity table.  scale = (double)(float)(bf[2] - bf[0]) / w2, the
+ *      subtraction in float32; fs, support and ksize as above; center = (double)bf[0] + (xx + 0.5) * scale;
+ *      xmin = max(0, int(center - support + 0.5)), xmax = min(W, int(center + support + 0.5)).  The windows are clamped
+ *      to the PICTURE, not to the box: samples outside the box are read, as Pillow reads them.  Weights, normalisation
+ *      and rounding as above; both bounds and the windows are checked for every table.
+ *   5. The x pass, the uint8 intermediate, the y pass, the turn and the unsharp mask as above.
+ * With the all-zero box and g = 0 the picture is byte for byte that of the _resampled_ entries; a g whose factors are
+ * both 1 changes nothing.  Boxes and sizes are in the STORED orientation.
+ * ONE LAUNCH.  A call none of whose frames is reduced runs the kernel of the _resampled_ entries (its tables satisfy
+ * what that kernel relies on).  A call with a reduced frame runs ALL its frames through a kernel of its own
+ * (resample_box.hip) that sums every block as it stages it; there a frame with factors 1 x 1 has m = 2^24.
+ *
+ * sjpeg_hip_resample_box: box and reducing_gap (0: none, else 1.0 .. 65536.0).  One for the call (box_per_frame == 0:
+ *   box[0]) or one per frame.  A factor above 255 is refused.
+ * sjpeg_hip_resample_box_ragged_src, sjpeg_hip_encode_ragged_resampled_box_src / _box_packed_src: the _resampled_
+ *   entries' arguments plus `box, box_per_frame` behind the resample; the made pictures take what
+ *   sjpeg_hip_resample_ragged_bytes says -- their layout depends on sizes and orientations alone -- or, where that
+ *   function refuses an axis by the cap that the reduce lifts, sjpeg_hip_resample_box_ragged_bytes.
+ * SJPEG_HIP_EINVAL before any device work, the frame named: box == NULL; a box that is empty or leaves the picture; a
+ *   reducing_gap that is neither 0 nor in 1.0 .. 65536.0; a factor above 255; the tall picture of step 3; and
+ *   everything the _resampled_ entries refuse, the cap taken behind the reduce.
+ * Host only, for bindings and tests (0, or SJPEG_HIP_EINVAL with the error set):
+ *   sjpeg_hip_thumbnail_size: the size Image.thumbnail((bw, bh)) gives a width x height picture: the box sides floored
+ *     (each at least 1), never larger than the picture, the aspect kept by Pillow's round_aspect.
+ *   sjpeg_hip_fit_crop: ImageOps.fit's crop box of a width x height picture for the size out_width x out_height.
+ *   sjpeg_hip_resample_box_decide: what steps 1 to 3 come to for one frame: the factors, the safe box, the reduced
+ *     picture's size, the four multipliers (interior, right edge, bottom edge, corner) and the box in that picture.
+ *   sjpeg_hip_resample_box_ksize, sjpeg_hip_resample_box_table: sjpeg_hip_resample_ksize and _table of step 4, of an
+ *     axis of `in` samples and the box ends b0 < b1 inside it, given as float32. */
+typedef struct sjpeg_hip_resample_box {
+  double box[4];                  /* left, top, right, bottom in the stored picture's samples; all 0: the whole picture */
+  double reducing_gap;            /* 0: no reduce */
+} sjpeg_hip_resample_box;         /* 40 bytes */
+typedef struct sjpeg_hip_resample_box_decision {
+  int32_t factor[2];              /* fx, fy */
+  int32_t safe_box[4];            /* R; factors 1 x 1: the whole picture */
+  int32_t reduced_size[2];        /* W, H of the picture the tables are of */
+  uint32_t multiplier[4];         /* m of an interior, right-edge, bottom-edge and corner block */
+  double inner_box[4];            /* the box in the reduced picture's samples */
+} sjpeg_hip_resample_box_decision;
+int sjpeg_hip_thumbnail_size(int width, int height, double box_width, double box_height, int32_t size[2] /*out*/);
+int sjpeg_hip_fit_crop(int width, int height, int out_width, int out_height, double bleed, double centering_x, double centering_y,
+                       double box[4] /*out*/);
+int sjpeg_hip_resample_box_decide(int filter, int width, int height, int out_width, int out_height, const sjpeg_hip_resample_box* box,
+                                  sjpeg_hip_resample_box_decision* decision /*out*/);
+int sjpeg_hip_resample_box_ksize(int filter, int in, int out, float b0, float b1);
+int sjpeg_hip_resample_box_table(int filter, int in, int out, float b0, float b1, int32_t (*bounds)[2] /*[out]*/,
+                                 int32_t* K /*[out * ksize]*/, size_t K_capacity);
+size_t sjpeg_hip_resample_box_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                           const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                           const uint8_t* orientations /*host [nframes], or NULL*/,
+                                           const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame);
+int sjpeg_hip_resample_box_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                      const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                      const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                      const uint8_t* orientations /*host [nframes], or NULL*/,
+                                      const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                      const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                      const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                      void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format,
+                                      void* stream);
+int sjpeg_hip_encode_ragged_resampled_box_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                              const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                              const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                              const uint8_t* orientations /*host [nframes], or NULL*/,
+                                              const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                              const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                              const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                              const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                              void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                              int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_resampled_box_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                     const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                     const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                     const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                     const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                     const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                                     const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                                     const sjpeg_hip_unsharp* unsharp /*host: [nframes], [1] or NULL*/, int unsharp_per_frame,
+                                                     const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                     void* d_packed, size_t packed_capacity,
+                                                     uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                     int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                     void* stream);
 
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that

@@ -1016,6 +1016,9 @@ EXPORTED_C_SYMBOLS = [
     # (bound by sjpeg_amd/resample.py)
     "sjpeg_hip_resample_ksize", "sjpeg_hip_resample_table", "sjpeg_hip_resample_ragged_bytes", "sjpeg_hip_resample_ragged_src",
     "sjpeg_hip_encode_ragged_resampled_src", "sjpeg_hip_encode_ragged_resampled_packed_src",
+    "sjpeg_hip_thumbnail_size", "sjpeg_hip_fit_crop", "sjpeg_hip_resample_box_decide", "sjpeg_hip_resample_box_ksize",
+    "sjpeg_hip_resample_box_table", "sjpeg_hip_resample_box_ragged_bytes", "sjpeg_hip_resample_box_ragged_src",
+    "sjpeg_hip_encode_ragged_resampled_box_src", "sjpeg_hip_encode_ragged_resampled_box_packed_src",
 ]
 
 

@@ -11,6 +11,7 @@ using namespace sjpeg_internal;
 // make and for their descriptors; `launch` starts the kernel over the uploaded descriptors.
 template <class Frame>
 static void picture_rebase(Frame& d, uint8_t* base) { d.dst = base + reinterpret_cast<uintptr_t>(d.dst); }
+static void picture_rebase(sjpeg_internal::ResampleBoxFrame& d, uint8_t* base) { d.r.dst = base + reinterpret_cast<uintptr_t>(d.r.dst); }
 static void picture_rebase(sjpeg_internal::YuvPlane& p, uint8_t* base) {
   p.r.dst = base + reinterpret_cast<uintptr_t>(p.r.dst);
   if (p.channels == 2) p.dst2 = base + reinterpret_cast<uintptr_t>(p.dst2);
@@ -81,6 +82,18 @@ int sjpeg_internal::engine_resample(sjpeg_hip_engine* e, const std::string& who,
     d.xk = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.xk));
     d.yb = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.yb));
     d.yk = reinterpret_cast<const int32_t*>(tables + reinterpret_cast<uintptr_t>(d.yk));
+  }
+  if (!plan.stages.empty()) {
+    // a box call with a reduced frame: every frame with its stage, through the kernel that reduces as it stages
+    std::vector<ResampleBoxFrame> boxed(desc.size());
+    for (size_t f = 0; f < desc.size(); ++f) { boxed[f].r = desc[f]; boxed[f].s = plan.stages[f]; }
+    return engine_make_pictures(e, who, "resampled", std::move(boxed), plan.bytes, d_out, base, stream,
+                                [&](const ResampleBoxFrame* d_frames, int n, hipStream_t st) {
+      if (resample_box_launch(plan.format, e->pscale, e->pbias, plan.flat ? &plan.flatten : nullptr, d_frames, n, plan.tiles, st) != 0) {
+        return fail(SJPEG_HIP_ERUNTIME, who + ": resample_box_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+      }
+      return 0;
+    });
   }
   return engine_make_pictures(e, who, "resampled", std::move(desc), plan.bytes, d_out, base, stream,
                               [&](const ResampleFrame* d_frames, int n, hipStream_t st) {

@@ -382,9 +382,23 @@ struct ResampleFrame {
   unsigned tiles_x, dst_stride;          // tiles a row of tiles; bytes between the made picture's rows
   unsigned tile_base, orient;            // the frame's first workgroup in the flat grid; its EXIF orientation, 1..8
 };
+// ... and of the box entries (sjpeg_hip_resample_box_ragged_src; resample_box.hip), where a frame is REDUCED as it is
+// staged: sample (X, Y) of the picture the tables are of -- r.W x r.H -- is Pillow's reduce of the block of fx x fy
+// source samples at (x0 + X * fx, y0 + Y * fy), cut off at x0 + w and y0 + h.  m: the multipliers of an interior, a
+// right-edge, a bottom-edge and a corner block (resample_math.h).  fx = fy = 1: the picture itself, m = 2^24.  A
+// descriptor of its own: ResampleFrame keeps its size, and resample.hip's kernel its instructions.
+struct ResampleStage {
+  int fx, fy, x0, y0, w, h;
+  uint32_t m[4];
+};
+struct ResampleBoxFrame {
+  ResampleFrame r;
+  ResampleStage s;
+};
 struct ResamplePlan {
   int format = 0, resized_format = 0;
   std::vector<ResampleFrame> frames;
+  std::vector<ResampleStage> stages;     // a box call with a frame that is reduced: every frame's; else empty
   std::vector<int32_t> tables;           // what goes up: every table of the call, once
   int ntables = 0;                       // ... how many (identity tables included)
   size_t bytes = 0;
@@ -404,10 +418,21 @@ int resample_check(const std::string& who, int nframes, const sjpeg_hip_resample
 int resample_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
                   const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_flatten* flatten,
                   ResamplePlan* plan);
+// ... and of the box entries: every frame has a source box and a reducing_gap (box[f], or box[0] for all; sjpeg_hip.h,
+// "THE DEFINITION of the box entries").  The box, the gap, a factor above kResampleFactorMax and a picture that Pillow
+// would resample along y first are refused, naming the frame; the tables are of the reduced picture and of the box
+// rounded to float32, one per (filter, in, out, box ends), held to the same bounds and window checks; the cap on ksize
+// applies behind the reduce.  No frame reduced: plan->stages is empty and the plan is one for resample.hip's kernel.
+int resample_box_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                      const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box,
+                      int box_per_frame, const sjpeg_hip_flatten* flatten, ResamplePlan* plan);
 void resample_plan_frames(const ResamplePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
 // flatten NULL: not flat
 int resample_launch(int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten* flatten, const ResampleFrame* d_frames,
                     int nframes, unsigned tiles, hipStream_t st);
+// ... the same over frames that are reduced as they are staged (resample_box.hip)
+int resample_box_launch(int format, const float* pscale, const float* pbias, const sjpeg_hip_flatten* flatten, const ResampleBoxFrame* d_frames,
+                        int nframes, unsigned tiles, hipStream_t st);
 // The engine's half (engine_pictures.cc), as engine_resize; the tables go into engine memory of their own, counted by
 // sjpeg_hip_engine_scratch_bytes and released by sjpeg_hip_engine_trim
 int engine_resample(sjpeg_hip_engine* e, const std::string& who, const ResamplePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);

@@ -38,6 +38,8 @@ struct Shape {
   int unsharp_per_frame = 0;
   const sjpeg_hip_resample* resample = nullptr;
   int resample_per_frame = 0;
+  const sjpeg_hip_resample_box* box = nullptr;
+  int box_per_frame = 0;
 };
 Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
   Shape s{nullptr, sizes, orientations, flatten, sheet};
@@ -176,6 +178,12 @@ struct ResampleKind : PerFrameKind {
   static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { resample_plan_frames(p, fr, base, out); }
   static constexpr auto run = engine_resample;
 };
+// ... from a source box and behind a reduce (sjpeg_hip_resample_box_ragged_src; resample_box.hip where a frame is reduced)
+struct ResampleBoxKind : ResampleKind {
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    return resample_box_plan(who, format, n, fr, s.sizes, s.orientations, s.resample, s.resample_per_frame, s.box, s.box_per_frame, s.flatten, p);
+  }
+};
 
 // ... and any per-frame kind K with the unsharp mask behind it (unsharp_plan.cc, unsharp.hip): K's plan, then the
 // unsharp plan of the pictures K makes -- read off K's own frames, standing at a placeholder address --; K's pictures
@@ -253,7 +261,8 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kSheetColour[2] = SJPEG_ENTRY_NAMES("sheet_yuv_colour"), kYuv16[2] = SJPEG_ENTRY_NAMES("yuv16"),
                   kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
                   kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear"), kUnsharp[2] = SJPEG_ENTRY_NAMES("unsharp"),
-                  kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp"), kResampled[2] = SJPEG_ENTRY_NAMES("resampled");
+                  kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp"), kResampled[2] = SJPEG_ENTRY_NAMES("resampled"),
+                  kResampledBox[2] = SJPEG_ENTRY_NAMES("resampled_box");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -549,6 +558,20 @@ int resampled_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_
   const Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, unsharp, unsharp_per_frame);
   if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) return planned_flow<ResampleKind>(c, s);
   return planned_flow<UnsharpKind<ResampleKind>>(c, s);
+}
+// ... from a source box and behind a reduce: the same, the plan the box kind's
+int resampled_box_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                        const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                        const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame) {
+  c.who = &kResampledBox[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = resample_check(*c.who, c.nframes, resample, resample_per_frame)) return rc;
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, *c.who + ": box == NULL");
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, unsharp, unsharp_per_frame);
+  s.box = box; s.box_per_frame = box_per_frame;
+  if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) return planned_flow<ResampleBoxKind>(c, s);
+  return planned_flow<UnsharpKind<ResampleBoxKind>>(c, s);
 }
 
 }  // namespace
@@ -1106,6 +1129,49 @@ int sjpeg_hip_encode_ragged_resampled_packed_src(sjpeg_hip_engine* e, int format
   return resampled_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                           RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten, sizes,
                          orientations, resample, resample_per_frame, unsharp, unsharp_per_frame);
+}
+
+// ---- ... from a source box and behind a reduce: Image.thumbnail and ImageOps.fit
+int sjpeg_hip_resample_box_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                      const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                      const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box,
+                                      int box_per_frame, const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, void* d_out, size_t out_bytes,
+                                      sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_resample_box_ragged_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "resampled pictures", "sjpeg_hip_resample_box_ragged_bytes"};
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (resample == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": resample == NULL");
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": box == NULL");
+  Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, unsharp, unsharp_per_frame);
+  s.box = box; s.box_per_frame = box_per_frame;
+  if (nothing_to_sharpen(nframes, unsharp, unsharp_per_frame)) {
+    return shape_body<ResampleBoxKind>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format, stream);
+  }
+  return shape_body<UnsharpKind<ResampleBoxKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format,
+                                                  stream);
+}
+
+int sjpeg_hip_encode_ragged_resampled_box_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                              const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                              const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame,
+                                              const sjpeg_hip_resample_box* box, int box_per_frame, const sjpeg_hip_unsharp* unsharp,
+                                              int unsharp_per_frame, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                              uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return resampled_box_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                              {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, sizes, orientations, resample, resample_per_frame, box,
+                             box_per_frame, unsharp, unsharp_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_resampled_box_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                     const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                     const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_resample* resample,
+                                                     int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                                     const sjpeg_hip_unsharp* unsharp, int unsharp_per_frame, const sjpeg_hip_metadata* meta,
+                                                     int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                     uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return resampled_box_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                              RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten,
+                             sizes, orientations, resample, resample_per_frame, box, box_per_frame, unsharp, unsharp_per_frame);
 }
 
 }  // extern "C"

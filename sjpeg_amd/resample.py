@@ -6,7 +6,16 @@ given the tables -- in ONE launch over the batch, to sizes smaller or larger tha
 tables are built on the host (resample_table shows one) and uploaded once per (filter, in, out) of a call.  Order of
 steps: pixel transform, flatten, resample, turn, unsharp.  sizes are in the STORED orientation: the upright picture is
 turn(resample(stored)) -- NOT exif_transpose followed by resize, which rounds its intermediate along the other axis.
-There is no linear light and there are no contact sheets here; the YUV-plane formats are refused."""
+There is no linear light and there are no contact sheets here; the YUV-plane formats are refused.
+
+Thumbnails are mostly not made by a bare resize.  source_box= and reducing_gap= make the bytes of Image.resize(size,
+filter, box=, reducing_gap=): a fractional source box inside the tables, and Pillow's integer reduce -- its own
+rounding, not this library's half-up average -- in front of the resample where the source is at least 2 * gap times the
+target, summed as the rows are staged.  thumbnail_images / encode_thumbnails follow Image.thumbnail and fit_images /
+encode_fitted_images ImageOps.fit; thumbnail_size and fit_crop are their size and crop rules.  With an orientation,
+boxes and sizes are in the STORED orientation and the result is turn(...) of what Pillow makes of the stored picture.
+A picture more than 100 times as tall as wide brought to fewer rows is resampled along y first by Pillow: the calls with
+a source_box or a reducing_gap refuse it; the plain calls do not, and for such a picture they do not make Pillow's bytes."""
 import ctypes as C
 import enum
 
@@ -29,6 +38,17 @@ class Filter(enum.IntEnum):
     HAMMING = 2
     BICUBIC = 3
     LANCZOS = 4
+
+
+class _BoxStruct(C.Structure):
+    """struct sjpeg_hip_resample_box"""
+    _fields_ = [("box", C.c_double * 4), ("reducing_gap", C.c_double)]
+
+
+class _DecisionStruct(C.Structure):
+    """struct sjpeg_hip_resample_box_decision"""
+    _fields_ = [("factor", C.c_int32 * 2), ("safe_box", C.c_int32 * 4), ("reduced_size", C.c_int32 * 2), ("multiplier", C.c_uint32 * 4),
+                ("inner_box", C.c_double * 4)]
 
 
 class _ResampleStruct(C.Structure):
@@ -56,6 +76,23 @@ def _lib():
         plain = list(getattr(L, f"sjpeg_hip_{older}_src").argtypes)
         fn = getattr(L, f"sjpeg_hip_{mine}_src")
         fn.restype, fn.argtypes = C.c_int, plain[:at] + plain[at + 1:at + 3] + two + plain[at + 3:]
+    L.sjpeg_hip_resample_box_ksize.restype = C.c_int
+    L.sjpeg_hip_resample_box_ksize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.sjpeg_hip_resample_box_table.restype = C.c_int
+    L.sjpeg_hip_resample_box_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.sjpeg_hip_thumbnail_size.restype = C.c_int
+    L.sjpeg_hip_thumbnail_size.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+    L.sjpeg_hip_fit_crop.restype = C.c_int
+    L.sjpeg_hip_fit_crop.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    L.sjpeg_hip_resample_box_decide.restype = C.c_int
+    L.sjpeg_hip_resample_box_decide.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.sjpeg_hip_resample_box_ragged_bytes.restype = C.c_size_t
+    L.sjpeg_hip_resample_box_ragged_bytes.argtypes = list(L.sjpeg_hip_resample_ragged_bytes.argtypes) + two
+    # (..., resample, resample_per_frame, unsharp, ...): box, box_per_frame behind the resample
+    for mine, at in (("resample_ragged", 9), ("encode_ragged_resampled", 10), ("encode_ragged_resampled_packed", 10)):
+        plain = list(getattr(L, f"sjpeg_hip_{mine}_src").argtypes)
+        fn = getattr(L, "sjpeg_hip_" + mine.replace("resample_ragged", "resample_box_ragged").replace("resampled", "resampled_box") + "_src")
+        fn.restype, fn.argtypes = C.c_int, plain[:at] + two + plain[at:]
     _bound = True
     return L
 
@@ -103,24 +140,118 @@ def resample_table(filter, n_in, n_out):
     return bounds, K
 
 
+def resample_box_table(filter, n_in, n_out, b0, b1):
+    """sjpeg_hip_resample_box_table: resample_table of an axis of n_in samples brought to n_out from its part [b0, b1),
+    the two ends rounded to float32 as Pillow's C layer receives them.  Host only."""
+    L = _lib()
+    b0, b1 = float(np.float32(b0)), float(np.float32(b1))
+    ks = L.sjpeg_hip_resample_box_ksize(_filter("resample_box_table", filter), int(n_in), int(n_out), b0, b1)
+    if ks == 0:
+        raise SjpegError(f"sjpeg_hip_resample_box_ksize failed: {_last_error()}")
+    bounds, K = np.zeros((int(n_out), 2), np.int32), np.zeros((int(n_out), ks), np.int32)
+    if L.sjpeg_hip_resample_box_table(int(filter), int(n_in), int(n_out), b0, b1, bounds.ctypes.data, K.ctypes.data, K.size) != 0:
+        raise SjpegError(f"sjpeg_hip_resample_box_table failed: {_last_error()}")
+    return bounds, K
+
+
+def thumbnail_size(width, height, box):
+    """sjpeg_hip_thumbnail_size: the size Image.thumbnail(box) gives a width x height picture.  Host only."""
+    try:
+        bw, bh = box
+    except (TypeError, ValueError):
+        raise SjpegError(f"thumbnail_size: box {box!r} is not a pair (width, height)")
+    out = (C.c_int32 * 2)()
+    if _lib().sjpeg_hip_thumbnail_size(int(width), int(height), float(bw), float(bh), out) != 0:
+        raise SjpegError(f"sjpeg_hip_thumbnail_size failed: {_last_error()}")
+    return int(out[0]), int(out[1])
+
+
+def fit_crop(width, height, size, bleed=0.0, centering=(0.5, 0.5)):
+    """sjpeg_hip_fit_crop: the crop box (left, top, right, bottom), in doubles, that ImageOps.fit(im, size, bleed=,
+    centering=) resizes a width x height picture from.  Host only."""
+    out = (C.c_double * 4)()
+    if _lib().sjpeg_hip_fit_crop(int(width), int(height), int(size[0]), int(size[1]), float(bleed), float(centering[0]), float(centering[1]),
+                                 out) != 0:
+        raise SjpegError(f"sjpeg_hip_fit_crop failed: {_last_error()}")
+    return tuple(float(v) for v in out)
+
+
+def box_decision(filter, width, height, size, source_box=None, reducing_gap=None):
+    """sjpeg_hip_resample_box_decide: what the plan decides for one frame, as a dict: factor (fx, fy), safe_box,
+    reduced_size, multiplier (interior, right edge, bottom edge, corner) and inner_box.  Host only."""
+    b = _BoxStruct((C.c_double * 4)(*(source_box if source_box is not None else (0, 0, 0, 0))), float(reducing_gap or 0.0))
+    d = _DecisionStruct()
+    if _lib().sjpeg_hip_resample_box_decide(_filter("box_decision", filter), int(width), int(height), int(size[0]), int(size[1]), C.addressof(b),
+                                            C.addressof(d)) != 0:
+        raise SjpegError(f"sjpeg_hip_resample_box_decide failed: {_last_error()}")
+    return {"factor": tuple(d.factor), "safe_box": tuple(d.safe_box), "reduced_size": tuple(d.reduced_size), "multiplier": tuple(d.multiplier),
+            "inner_box": tuple(d.inner_box)}
+
+
+def _box_args(who, n, source_box, reducing_gap):
+    """(the struct array, its address, whether there is one per frame) of source_box -- None, one (l, t, r, b) or one
+    per frame -- and reducing_gap -- None, one number or one per frame --; (None, None, 0) where neither is given: the
+    call is the plain one"""
+    if source_box is None and reducing_gap is None:
+        return None, None, 0
+    def one_box(b):
+        if b is None:
+            return (0.0, 0.0, 0.0, 0.0)
+        try:
+            l, t, r, bt = (float(v) for v in b)
+        except (TypeError, ValueError):
+            raise SjpegError(f"{who}: source_box {b!r} is not (left, top, right, bottom)")
+        return (l, t, r, bt)
+    def one_gap(g):
+        if g is None:
+            return 0.0
+        if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not float(g) >= 1.0:
+            raise SjpegError(f"{who}: reducing_gap {g!r} is not None or a number of 1.0 or more")
+        return float(g)
+    number = (int, float, np.integer, np.floating)
+    boxes_many = source_box is not None and not (len(source_box) == 4 and all(isinstance(v, number) for v in source_box))
+    gaps_many = isinstance(reducing_gap, (tuple, list, np.ndarray))
+    if boxes_many and len(source_box) != n:
+        raise SjpegError(f"{who}: source_box is one box or a sequence of one per frame ({n})")
+    if gaps_many and len(reducing_gap) != n:
+        raise SjpegError(f"{who}: reducing_gap is one number or a sequence of one per frame ({n})")
+    count = n if boxes_many or gaps_many else 1
+    arr = (_BoxStruct * count)()
+    for k in range(count):
+        arr[k].box[:] = one_box(source_box[k] if boxes_many else source_box)
+        arr[k].reducing_gap = one_gap(reducing_gap[k] if gaps_many else reducing_gap)
+    return arr, C.addressof(arr), 1 if count == n and (boxes_many or gaps_many) else 0
+
+
 # ---- the ragged level: fmt, planes_per_frame and dims as Engine.encode_ragged takes them
 
 def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filter.LANCZOS, orientations=None, flatten=None, unsharp=None,
-                    out=None):
+                    out=None, source_box=None, reducing_gap=None):
     """sjpeg_hip_resample_ragged_src: the pictures of a ragged batch resampled to sizes[k] = (w, h) (None: their own; the
     STORED orientation; larger or smaller than the source) with `filter` (one Filter or one per frame), turned upright
-    and optionally sharpened.  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
+    and optionally sharpened.  source_box / reducing_gap (one or one per frame): sjpeg_hip_resample_box_ragged_src, the
+    pictures of Image.resize(size, filter, box=, reducing_gap=).  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
     who = "resample_ragged"
     n = len(dims)
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
     L = _lib()
     rkeep, raddr, rper = _filter_args(who, n, filter)
+    bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = li._flat_struct(who, flatten)
     # (a batch the library refuses has need == 0: the call below says why)
+    if bkeep is not None:
+        need = L.sjpeg_hip_resample_box_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper)
+        out = sj._made_out(who, planes_per_frame, need, out)
+        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
+        engine._chk(L.sjpeg_hip_resample_box_ragged_src(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr,
+                                                        bper, uaddr, uper, out.data_ptr(), int(out.numel()) if need else 0, made,
+                                                        C.byref(rfmt), engine._stream()),
+                    "sjpeg_hip_resample_box_ragged_src")
+        return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
     need = L.sjpeg_hip_resample_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr))
     out = sj._made_out(who, planes_per_frame, need, out)
     made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
@@ -132,7 +263,7 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
 
 def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, filter=Filter.LANCZOS,
                             flatten=None, unsharp=None, search=None, metadata=None, packed=False, min_quant=None, q_bias=0x78, dmax_luma=12,
-                            dmax_chroma=1):
+                            dmax_chroma=1, source_box=None, reducing_gap=None):
     """sjpeg_hip_encode_ragged_resampled_src / _resampled_packed_src.  Frame k's bytes are those Engine.encode_ragged_full
     makes of the uint8 picture resample_ragged returns.  Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_resampled"
@@ -143,32 +274,42 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
     call = engine._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                                  dmax_chroma, search, None, metadata)
     keep, faddr = li._flat_struct(who, flatten)
+    bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
     special = (faddr, call.sizes, call.orientations, raddr, rper, uaddr, uper)
+    stem = "sjpeg_hip_encode_ragged_resampled"
+    if bkeep is not None:
+        special, stem = special[:5] + (baddr, bper) + special[5:], stem + "_box"
     if packed:
         out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
-        return sj._split_meta(n, *engine._packed("sjpeg_hip_encode_ragged_resampled_packed_src", fmt, planes_per_frame, dims, call, special, out,
-                                                 packed_capacity, meta))
+        return sj._split_meta(n, *engine._packed(stem + "_packed_src", fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta))
     frames, out, sizes_out, offsets = sj._ragged_frames(planes_per_frame, dims, call.capacities, None, None, None)
-    return engine._unpacked("sjpeg_hip_encode_ragged_resampled_src", fmt, frames, call, special, out, sizes_out, offsets)
+    return engine._unpacked(stem + "_src", fmt, frames, call, special, out, sizes_out, offsets)
 
 
 # ---- the picture level: images as resize_images / flatten_images take them
 
-def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, flatten=None, engine=None, layout="hwc"):
+def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, flatten=None, engine=None, layout="hwc", source_box=None,
+                    reducing_gap=None, _shape=None):
     """The uint8 pictures PIL.Image.resize(sizes[k], filter) makes of `images`, as views of ONE device buffer from one
     launch: images, orientations, flatten and layout as resize_images / orient_images / flatten_images take them; sizes
     one (w, h) or one per picture, in the STORED orientation, each side 1..65535 -- larger than the source too; filter
-    one Filter or one per picture.  Returns uint8 CUDA tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k]; gray
+    one Filter or one per picture.  source_box=(l, t, r, b) in doubles, in the stored picture's samples, and
+    reducing_gap= (None, or 1.0 and more), each one value or one per picture: the pictures of Image.resize(sizes[k],
+    filter, box=, reducing_gap=).  Returns uint8 CUDA tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k]; gray
     FloatPixels: [h_k, w_k]), rows padded to a multiple of 4 bytes."""
     import torch
     who = "resample_images"
     planes, dims, dev, fmt, fp = li._read(who, images, layout, flatten)
     orientations = sj._orientation_list(who, len(dims), orientations)
+    if _shape is not None:                       # (thumbnail_images, fit_images: sizes and boxes follow from the pictures' own)
+        sizes, source_box = _shape(dims)
     sizes = li._sizes(who, dims, sizes, None, orientations)
     _filter_args(who, len(dims), filter)
+    _box_args(who, len(dims), source_box, reducing_gap)
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
-        rfmt, made, _ = resample_ragged(eng, fmt, planes, dims, sizes, filter, orientations, flatten)
+        rfmt, made, _ = resample_ragged(eng, fmt, planes, dims, sizes, filter, orientations, flatten, source_box=source_box,
+                                        reducing_gap=reducing_gap)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in made] if layout == "chw" and rfmt == sj.SRC_RGB else made
@@ -176,19 +317,23 @@ def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, fla
 
 def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS, unsharp=None, metadata=None, packed=False, orientations=None,
                             flatten=None, quality=75.0, yuv_mode=YUV_420, method=4, use_trellis=False, target_size=None, target_psnr=None,
-                            layout="hwc", engine=None):
+                            layout="hwc", engine=None, source_box=None, reducing_gap=None, _shape=None):
     """The thumbnail call with Pillow's filters: JPEGs (list of bytes), picture k's byte for byte what encode_images_full
     makes of the picture resample_images returns for the same arguments (sharpened by `unsharp`, an unsharp.Unsharp or
     one per picture, where given).  box=(bw, bh) fits the upright picture into the box and never enlarges; sizes= is
-    explicit and may enlarge.  The other arguments as unsharp.encode_unsharp_images takes them."""
+    explicit and may enlarge.  source_box= and reducing_gap= as resample_images takes them.  The other arguments as
+    unsharp.encode_unsharp_images takes them."""
     import torch
     who = "encode_resampled_images"
     planes, dims, dev, fmt, fp = li._read(who, images, layout, flatten)
     n = len(dims)
     sj._gray_mode(who, fmt, int(yuv_mode))
     orientations = sj._orientation_list(who, n, orientations)
+    if _shape is not None:
+        sizes, source_box = _shape(dims)
     sizes = li._sizes(who, dims, sizes, box, orientations)
     _filter_args(who, n, filter)
+    _box_args(who, n, source_box, reducing_gap)
     un._unsharp_args(who, n, unsharp)
     method = li._method(who, method, use_trellis)
     sj._one_target(who, target_size, target_psnr)
@@ -199,6 +344,48 @@ def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS,
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
         res = encode_ragged_resampled(eng, fmt, planes, dims, sizes, orientations, int(yuv_mode), sj._quality_quant(qs), method, filter, flatten,
-                                      unsharp, search, metadata, packed)
+                                      unsharp, search, metadata, packed, source_box=source_box, reducing_gap=reducing_gap)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return sj._fetch_packed(res[0], res[1], res[2], n, "image") if packed else sj._fetch_ragged(res[0], res[1], res[2])
+
+
+# ---- Image.thumbnail and ImageOps.fit: sizes and source boxes that follow from the pictures' own sizes
+
+def _thumbnail_shape(box):
+    """(sizes, source boxes) of Image.thumbnail(box): the whole picture said outright, so that the call goes through the
+    box entries and their refusals also where nothing is reduced"""
+    return lambda dims: ([thumbnail_size(w, h, box) for w, h in dims], [(0.0, 0.0, float(w), float(h)) for w, h in dims])
+
+
+def _fit_shape(size, bleed, centering):
+    """(sizes, source boxes) of ImageOps.fit(size, bleed=, centering=).  (left + width may leave the picture by one
+    rounding of a double; Pillow's float32 box does not see that, so the crop is held inside the picture.)"""
+    size = (int(size[0]), int(size[1]))
+    return lambda dims: ([size] * len(dims), [tuple(min(v, float(lim)) for v, lim in zip(fit_crop(w, h, size, bleed, centering), (w, h, w, h)))
+                                              for w, h in dims])
+
+
+def thumbnail_images(images, box, filter=Filter.BICUBIC, reducing_gap=2.0, **kw):
+    """The pictures im.thumbnail(box, filter, reducing_gap=) leaves of `images`: thumbnail_size's sizes -- the aspect
+    kept, never larger than the picture --, Pillow's reduce where a side is at least 2 * reducing_gap times its target,
+    then the resample.  box is in the STORED orientation.  The other arguments as resample_images takes them."""
+    return resample_images(images, None, filter, reducing_gap=reducing_gap, _shape=_thumbnail_shape(box), **kw)
+
+
+def encode_thumbnails(images, box, filter=Filter.BICUBIC, reducing_gap=2.0, **kw):
+    """JPEGs of the pictures thumbnail_images makes, byte for byte what encode_images_full makes of them.  The other
+    arguments as encode_resampled_images takes them (but sizes and box)."""
+    return encode_resampled_images(images, filter=filter, reducing_gap=reducing_gap, _shape=_thumbnail_shape(box), **kw)
+
+
+def fit_images(images, size, filter=Filter.BICUBIC, bleed=0.0, centering=(0.5, 0.5), **kw):
+    """The pictures ImageOps.fit(im, size, filter, bleed, centering) makes of `images`: cropped to the ratio of size
+    around the centering -- a fractional crop, fit_crop's -- and resized to it.  size and the crop are in the STORED
+    orientation.  The other arguments as resample_images takes them."""
+    return resample_images(images, None, filter, _shape=_fit_shape(size, bleed, centering), **kw)
+
+
+def encode_fitted_images(images, size, filter=Filter.BICUBIC, bleed=0.0, centering=(0.5, 0.5), **kw):
+    """JPEGs of the pictures fit_images makes, byte for byte what encode_images_full makes of them.  The other arguments
+    as encode_resampled_images takes them (but sizes and box)."""
+    return encode_resampled_images(images, filter=filter, _shape=_fit_shape(size, bleed, centering), **kw)
