@@ -1890,6 +1890,89 @@ int sjpeg_hip_encode_ragged_resampled_box_packed_src(sjpeg_hip_engine* engine, i
                                                      int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                      void* stream);
 
+/* ---- ... and filtered behind it: Pillow's GaussianBlur, BoxBlur and UnsharpMask ----
+ * A Python thumbnailer does not stop at thumbnail(): it ends in filter(ImageFilter.UnsharpMask(2, 150, 3)), or in
+ * filter(GaussianBlur(r)) for a blurred placeholder.  The entries below run that last link inside the call and make
+ * Pillow 12.2.0's bytes.  (The _unsharp entries above are a 3 x 3 mask of this library's own definition; they do not.)
+ * THE FILTER runs over the MADE upright bytes, whatever made them: filter(turn(resample(flatten(stored)))), RGB or gray.
+ * It is the last step, where the unsharp launch of the _resampled_box_ entries stands; rx and ry are the upright
+ * picture's.  THE DEFINITION (sjpeg_amd/csrc/pillow_filter_math.h states it once, for the host, the kernel and the
+ * tests); every band of an RGB picture is filtered alike:
+ *   One box pass along a line of n samples of one channel, float radius fr > 0 (a float32): r = (int) fr,
+ *     ww = (uint32) (16777216.0f / (fr * 2.0f + 1.0f)) -- the sum and the division in FLOAT32, truncated; divided in
+ *     double, radii 0.3 and 2.7 make other bytes --, fw = (2^24 - (2 r + 1) ww) / 2, and
+ *     out[x] = (ww * SUM(d = -r .. r) in[c(x + d)] + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + 2^23) >> 24 in uint32,
+ *     c() clamping an index into 0 .. n - 1: edges are replicated.
+ *   Box blur (rx, ry): one pass along every row with rx, then one along every column of that uint8 result with ry.  An
+ *     axis whose radius is 0 is skipped.
+ *   Gaussian blur (sx, sy): THREE passes along the rows, each rounded to uint8, then three along the columns, with
+ *     fr = g(sigma): s2 = sigma * sigma / 3; L = sqrt(12 s2 + 1); l = floor((L - 1) / 2);
+ *     a = (2 l + 1) (l (l + 1) - 3 s2) / (6 (s2 - (l + 1) (l + 1))); fr = l + a -- every operation rounded to FLOAT32 but
+ *     sqrt and floor, which take and return double.  (In doubles many sigmas give another radius.)  Sigma 1 gives 0.25,
+ *     sigma 2 gives 1.375.  An axis whose fr is 0 is skipped.
+ *   Unsharp mask (radius, percent, threshold): b the Gaussian blur (radius, radius) of the picture; per sample d = p - b;
+ *     |d| > threshold (STRICTLY): clip(p + d * percent / 100, 0, 255), the division C's, toward zero; else p.
+ * TWO LAUNCHES over the batch's tiles behind the launch that made the pictures, never one per pass or per picture:
+ * every pass along the rows into engine scratch of the made pictures' layout, every pass along the columns (and the
+ * unsharp combine) from there into the output.  On the device there are only integers.
+ *
+ * sjpeg_hip_pillow_filter: kind 0 none, 1 box blur, 2 Gaussian blur, 3 unsharp mask; threshold and percent for kind 3;
+ *   radius_x, radius_y: box radii (kind 1) or sigmas (2, 3; kind 3: both equal).  One for the call
+ *   (filter_per_frame == 0: filter[0]) or one per frame, kinds mixed.
+ * sjpeg_hip_filter_ragged_src, sjpeg_hip_encode_ragged_filtered_src / _filtered_packed_src: the _resampled_box_
+ *   entries' arguments with `unsharp, unsharp_per_frame` replaced by `filter, filter_per_frame`; same layout, same
+ *   bytes function, same JPEG contract.  filter == NULL, or kind 0 for every frame: exactly the _resampled_box_ entry
+ *   without unsharp -- byte for byte, its messages under its name, no launch more.
+ * SJPEG_HIP_EINVAL before any device work, the frame named: a kind above 3; a radius that is negative or not finite; an
+ *   axis whose integer box radius r exceeds 63 -- a box radius of 64 or a sigma above about 64: Pillow has no such
+ *   limit, the kernel's staging has --; kind 3 with radius_x != radius_y; a reserved byte that is not 0; made pictures
+ *   that are neither RGB nor gray; and everything the _resampled_box_ entries refuse.  Every axis is also held to
+ *   (2 r + 1) * ww <= 2^24, which the uint32 above relies on.
+ * Host only, for bindings and tests (0, or SJPEG_HIP_EINVAL with the error set):
+ *   sjpeg_hip_pillow_filter_weights: r, ww, fw and the number of passes of ONE axis of a kind (1..3) with `radius`;
+ *     passes 0: the axis is skipped.  The same refusals. */
+typedef struct sjpeg_hip_pillow_filter {
+  uint8_t kind;                   /* 0 none, 1 box blur, 2 Gaussian blur, 3 unsharp mask */
+  uint8_t threshold;              /* kind 3: 0..255 */
+  uint16_t percent;               /* kind 3 */
+  float radius_x, radius_y;       /* along the rows, along the columns of the upright picture */
+  uint8_t reserved[4];            /* must be 0 */
+} sjpeg_hip_pillow_filter;        /* 16 bytes */
+int sjpeg_hip_pillow_filter_weights(int kind, float radius, uint32_t* r, uint32_t* ww, uint32_t* fw, uint32_t* passes /*out*/);
+int sjpeg_hip_filter_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                const uint8_t* orientations /*host [nframes], or NULL*/,
+                                const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format,
+                                void* stream);
+int sjpeg_hip_encode_ragged_filtered_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                         const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                         const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                         const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                         const uint8_t* orientations /*host [nframes], or NULL*/,
+                                         const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                         const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                         const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                         const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                         void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                         int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_filtered_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                                const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                                const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                                const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity,
+                                                uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

@@ -1019,6 +1019,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_thumbnail_size", "sjpeg_hip_fit_crop", "sjpeg_hip_resample_box_decide", "sjpeg_hip_resample_box_ksize",
     "sjpeg_hip_resample_box_table", "sjpeg_hip_resample_box_ragged_bytes", "sjpeg_hip_resample_box_ragged_src",
     "sjpeg_hip_encode_ragged_resampled_box_src", "sjpeg_hip_encode_ragged_resampled_box_packed_src",
+    "sjpeg_hip_pillow_filter_weights", "sjpeg_hip_filter_ragged_src", "sjpeg_hip_encode_ragged_filtered_src",
+    "sjpeg_hip_encode_ragged_filtered_packed_src",
 ]
 
 

@@ -220,6 +220,9 @@ struct sjpeg_hip_engine {
   DevBuf<uint4> final_pictures, unsharp_desc;
   // ... and the tables of a resampling call (resample.hip): bounds and coefficients of every axis, once per key
   DevBuf<uint4> resample_tables;
+  // ... and of Pillow's filters behind the box entries (pillow_filter.hip): the bytes between the launch along the rows
+  // and the one along the columns, in the made pictures' layout, and the two launches' descriptors
+  DevBuf<uint4> filter_mid, filter_desc;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;

@@ -1,7 +1,7 @@
 // engine_pictures.cc -- the engine's half of the entries that MAKE pictures for a ragged call: reduction, resize, the
-// YUV-plane resize, contact sheets, the video colour conversion and the unsharp mask.  The plans come from the *_plan.cc
-// files, the kernels and their launch functions live in reduce.hip, resize.hip, yuv_colour.hip and unsharp.hip
-// (ragged_aux.h); here the call is ordered
+// YUV-plane resize, contact sheets, the video colour conversion, the unsharp mask and Pillow's filters.  The plans come
+// from the *_plan.cc files, the kernels and their launch functions live in reduce.hip, resize.hip, yuv_colour.hip,
+// unsharp.hip and pillow_filter.hip (ragged_aux.h); here the call is ordered
 // behind the engine's earlier work, the engine's memory is sized and the descriptors go up.  Host only.
 #include "engine.h"
 
@@ -203,6 +203,38 @@ int sjpeg_internal::engine_unsharp(sjpeg_hip_engine* e, const std::string& who, 
   if (int rc = sync_uploads(e, st)) return rc;
   if (unsharp_launch(reinterpret_cast<const UnsharpPlane*>(e->unsharp_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
     return fail(SJPEG_HIP_ERUNTIME, who + ": unsharp_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+  }
+  return 0;
+}
+
+// ... and of Pillow's filters (pillow_filter_plan.cc): the two launches behind the launch that made the pictures at
+// src_base, on the same stream -- along the rows into the engine's scratch of the same layout, along the columns from
+// there out of place.  Every buffer is sized before a pointer into any is taken.
+int sjpeg_internal::engine_pillow_filter(sjpeg_hip_engine* e, const std::string& who, const PillowFilterPlan& plan, const uint8_t* src_base,
+                                         uint8_t* d_out, uint8_t** base, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<PillowFilterPlane> desc = plan.planes;
+  const size_t desc_bytes = sizeof(PillowFilterPlane) * desc.size();
+  if ((d_out == nullptr && e->final_pictures.ensure(plan.bytes / 16 + 1) != 0) || e->filter_mid.ensure(plan.bytes / 16 + 1) != 0) {
+    return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(plan.bytes) + " bytes of filtered pictures");
+  }
+  if (int rc = e->filter_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (d_out == nullptr) d_out = reinterpret_cast<uint8_t*>(e->final_pictures.p);
+  if (base != nullptr) *base = d_out;
+  uint8_t* const mid = reinterpret_cast<uint8_t*>(e->filter_mid.p);
+  for (PillowFilterPlane& d : desc) {
+    d.made = src_base + reinterpret_cast<uintptr_t>(d.made);
+    d.mid = mid + reinterpret_cast<uintptr_t>(d.mid);
+    d.dst = d_out + reinterpret_cast<uintptr_t>(d.dst);
+  }
+  if (plan.tiles[0] == 0 || plan.tiles[1] == 0) return 0;
+  if (int rc = upload(e, e->filter_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  for (int launch = 0; launch < 2; ++launch) {
+    if (pillow_filter_launch(launch, reinterpret_cast<const PillowFilterPlane*>(e->filter_desc.p), static_cast<int>(desc.size()), plan.tiles[launch],
+                             st) != 0) {
+      return fail(SJPEG_HIP_ERUNTIME, who + ": pillow_filter_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
+    }
   }
   return 0;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "jpeg_host.h"
+#include "pillow_filter_math.h"
 #include "pixel_elem.h"
 #include "sjpeg_hip.h"
 #include "source_layout.h"
@@ -436,6 +437,48 @@ int resample_box_launch(int format, const float* pscale, const float* pbias, con
 // The engine's half (engine_pictures.cc), as engine_resize; the tables go into engine memory of their own, counted by
 // sjpeg_hip_engine_scratch_bytes and released by sjpeg_hip_engine_trim
 int engine_resample(sjpeg_hip_engine* e, const std::string& who, const ResamplePlan& plan, uint8_t* d_out, uint8_t** base, void* stream);
+
+// ---- Pillow's BoxBlur, GaussianBlur and UnsharpMask (sjpeg_hip_filter_ragged_src; pillow_filter_plan.cc,
+// pillow_filter.hip, pillow_filter_math.h): the made RGB or gray pictures of the box entries filtered by TWO launches
+// behind the launch that made them -- every pass along the rows from the made pictures to a scratch buffer of the same
+// layout, every pass along the columns from there to the output, the unsharp combine fused into the second.  One
+// descriptor per frame; each launch is a flat grid over the tiles of every frame, a workgroup finds its frame by the
+// binary search over tile_base[launch].  A frame of kind 0, and an axis that is skipped, is copied by the same code.
+struct PillowFilterPlane {
+  const uint8_t* made;                   // the made picture's first sample: a multiple of 4 (the plan: from the buffer's start)
+  uint8_t* mid;                          // ... the same place in the scratch buffer between the two launches
+  uint8_t* dst;                          // ... and in the output
+  unsigned width, rows;                  // pixels a row, rows
+  unsigned stride;                       // bytes between rows, in all three: a multiple of 4, at least the row rounded up to 4
+  unsigned step;                         // bytes a pixel: 3 (interleaved RGB) or 1
+  unsigned kind, percent, threshold;     // sjpeg_hip_pillow_filter's
+  PillowFilterAxis axis[2];              // along the rows, along the columns
+  unsigned tile_base[2];                 // the frame's first workgroup in the row launch's and the column launch's grid
+};
+struct PillowFilterPlan {
+  std::vector<PillowFilterPlane> planes; // frame after frame; made == mid == dst: the offset from the pictures' base
+  unsigned tiles[2] = {0, 0};            // the grids of the row launch and the column launch
+  size_t bytes = 0;                      // what the pictures take from their base: the plan's that made them (the kind sets it)
+};
+// 0 for parameters the entries take (NULL: none to check), else SJPEG_HIP_EINVAL naming the frame (filter_per_frame == 0:
+// filter[0] is every frame's): an unknown kind, a radius that is negative or not finite, an axis whose integer box
+// radius exceeds kPillowFilterRadiusMax or whose weights break pillow_filter_axis_bound, kind 3 with two radii, a
+// reserved byte that is not 0
+int pillow_filter_check(const std::string& who, int nframes, const sjpeg_hip_pillow_filter* filter, int filter_per_frame);
+// NULL, or kind 0 for every frame (reserved bytes 0): there is nothing to filter
+bool pillow_filter_all_none(int nframes, const sjpeg_hip_pillow_filter* filter, int filter_per_frame);
+// The parameters checked, then the descriptors of `made` -- nframes made pictures of `format` (SJPEG_HIP_SRC_RGB or
+// _GRAY, anything else is refused) standing at `base`, as a plan kind's frames() reports them -- and the two grids.  A
+// plane or stride that is no multiple of 4, a stride below the row and more than 0x7fffffff tiles are refused.
+int pillow_filter_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* made, const uint8_t* base,
+                       const sjpeg_hip_pillow_filter* filter, int filter_per_frame, PillowFilterPlan* plan);
+// launch 0: along the rows, made -> mid; launch 1: along the columns, mid (and made) -> dst
+int pillow_filter_launch(int launch, const PillowFilterPlane* d_planes, int nplanes, unsigned tiles, hipStream_t st);
+// The engine's half (engine_pictures.cc), as engine_unsharp: the descriptors rebased -- made to src_base, mid to the
+// engine's scratch of the made pictures' layout, dst to d_out (NULL: the engine's memory for FINAL pictures) --,
+// uploaded into a buffer of their own and the two launches on `stream`.
+int engine_pillow_filter(sjpeg_hip_engine* e, const std::string& who, const PillowFilterPlan& plan, const uint8_t* src_base, uint8_t* d_out,
+                         uint8_t** base, void* stream);
 
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own

@@ -2,7 +2,8 @@
 // resized to a size, turned upright by an EXIF orientation and flattened over a background (resize.hip), the same for
 // the YUV-plane formats (yuv_resize_plan.cc), their samples bytes or 16-bit words, and placed into contact sheets
 // (sheet_plan.cc), sharpened by the unsharp mask behind any of it but a sheet (unsharp_plan.cc, unsharp.hip), and
-// resampled with Pillow's filters, enlarging too (resample_plan.cc, resample.hip).  Per
+// resampled with Pillow's filters, enlarging too (resample_plan.cc, resample.hip), and filtered by Pillow's BoxBlur,
+// GaussianBlur or UnsharpMask behind that (pillow_filter_plan.cc, pillow_filter.hip).  Per
 // family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
 // its packed twin: the pictures into the engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
 //
@@ -40,6 +41,8 @@ struct Shape {
   int resample_per_frame = 0;
   const sjpeg_hip_resample_box* box = nullptr;
   int box_per_frame = 0;
+  const sjpeg_hip_pillow_filter* filter = nullptr;
+  int filter_per_frame = 0;
 };
 Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
   Shape s{nullptr, sizes, orientations, flatten, sheet};
@@ -208,6 +211,28 @@ struct UnsharpKind : K {
   }
 };
 
+// ... and any per-frame kind K with Pillow's filters behind it (pillow_filter_plan.cc, pillow_filter.hip): as
+// UnsharpKind, the plan read off K's own frames at a placeholder address; K's pictures into the engine's memory, then
+// the two filter launches from there to the caller's buffer or the engine's final pictures
+template <class K>
+struct FilterKind : K {
+  struct Plan : K::Plan { PillowFilterPlan filter; };
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = K::plan(who, format, n, fr, s, p)) return rc;
+    uint8_t* const at = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16));
+    std::vector<Frame> made(static_cast<size_t>(n));
+    K::frames(*p, fr, at, made.data());
+    if (int rc = pillow_filter_plan(who, K::format(*p), n, made.data(), at, s.filter, s.filter_per_frame, &p->filter)) return rc;
+    p->filter.bytes = p->bytes;
+    return 0;
+  }
+  static int run(sjpeg_hip_engine* e, const std::string& who, const Plan& p, uint8_t* d_out, uint8_t** base, void* stream) {
+    uint8_t* staged = nullptr;
+    if (int rc = K::run(e, who, p, nullptr, &staged, stream)) return rc;
+    return engine_pillow_filter(e, who, p.filter, staged, d_out, base, stream);
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -262,7 +287,7 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
                   kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear"), kUnsharp[2] = SJPEG_ENTRY_NAMES("unsharp"),
                   kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp"), kResampled[2] = SJPEG_ENTRY_NAMES("resampled"),
-                  kResampledBox[2] = SJPEG_ENTRY_NAMES("resampled_box");
+                  kResampledBox[2] = SJPEG_ENTRY_NAMES("resampled_box"), kFiltered[2] = SJPEG_ENTRY_NAMES("filtered");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -572,6 +597,31 @@ int resampled_box_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const in
   s.box = box; s.box_per_frame = box_per_frame;
   if (nothing_to_sharpen(c.nframes, unsharp, unsharp_per_frame)) return planned_flow<ResampleBoxKind>(c, s);
   return planned_flow<UnsharpKind<ResampleBoxKind>>(c, s);
+}
+
+// Pillow's filters behind the box entries.  filter NULL or kind 0 for every frame: exactly the resampled_box call
+// without unsharp on the same arguments, under its name.  Otherwise the two filter launches run behind the resample
+// launch over every frame, those of kind 0 copied.
+bool nothing_to_filter(int nframes, const sjpeg_hip_pillow_filter* filter, int filter_per_frame) {
+  // (filter is [nframes] only where nframes is a count)
+  return filter == nullptr || ((filter_per_frame == 0 || (nframes >= 1 && nframes <= 65535)) && pillow_filter_all_none(nframes, filter, filter_per_frame));
+}
+int filtered_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                   const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                   const sjpeg_hip_pillow_filter* filter, int filter_per_frame) {
+  if (nothing_to_filter(c.nframes, filter, filter_per_frame)) {
+    return resampled_box_entry(c, flatten, sizes, orientations, resample, resample_per_frame, box, box_per_frame, nullptr, 0);
+  }
+  c.who = &kFiltered[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = resample_check(*c.who, c.nframes, resample, resample_per_frame)) return rc;
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, *c.who + ": box == NULL");
+  if (int rc = pillow_filter_check(*c.who, c.nframes, filter, filter_per_frame)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, nullptr, 0);
+  s.box = box; s.box_per_frame = box_per_frame;
+  s.filter = filter; s.filter_per_frame = filter_per_frame;
+  return planned_flow<FilterKind<ResampleBoxKind>>(c, s);
 }
 
 }  // namespace
@@ -1172,6 +1222,51 @@ int sjpeg_hip_encode_ragged_resampled_box_packed_src(sjpeg_hip_engine* e, int fo
   return resampled_box_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                               RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten,
                              sizes, orientations, resample, resample_per_frame, box, box_per_frame, unsharp, unsharp_per_frame);
+}
+
+// ---- ... and filtered by Pillow's BoxBlur, GaussianBlur or UnsharpMask behind it: two launches (pillow_filter.hip)
+int sjpeg_hip_filter_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                const sjpeg_hip_pillow_filter* filter, int filter_per_frame, void* d_out, size_t out_bytes,
+                                sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_filter_ragged_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "filtered pictures", "sjpeg_hip_resample_box_ragged_bytes"};
+  if (nothing_to_filter(nframes, filter, filter_per_frame)) {
+    return sjpeg_hip_resample_box_ragged_src(e, format, nframes, frames, flatten, sizes, orientations, resample, resample_per_frame, box,
+                                             box_per_frame, nullptr, 0, d_out, out_bytes, out_frames, out_format, stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (resample == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": resample == NULL");
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": box == NULL");
+  Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, nullptr, 0);
+  s.box = box; s.box_per_frame = box_per_frame;
+  s.filter = filter; s.filter_per_frame = filter_per_frame;
+  return shape_body<FilterKind<ResampleBoxKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr, out_format,
+                                                 stream);
+}
+
+int sjpeg_hip_encode_ragged_filtered_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                         const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                         const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame,
+                                         const sjpeg_hip_resample_box* box, int box_per_frame, const sjpeg_hip_pillow_filter* filter,
+                                         int filter_per_frame, const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out,
+                                         uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return filtered_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                         {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, sizes, orientations, resample, resample_per_frame, box,
+                        box_per_frame, filter, filter_per_frame);
+}
+
+int sjpeg_hip_encode_ragged_filtered_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_resample* resample,
+                                                int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                                const sjpeg_hip_pillow_filter* filter, int filter_per_frame, const sjpeg_hip_metadata* meta,
+                                                int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return filtered_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                         RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten,
+                        sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame);
 }
 
 }  // extern "C"

@@ -15,7 +15,12 @@ target, summed as the rows are staged.  thumbnail_images / encode_thumbnails fol
 encode_fitted_images ImageOps.fit; thumbnail_size and fit_crop are their size and crop rules.  With an orientation,
 boxes and sizes are in the STORED orientation and the result is turn(...) of what Pillow makes of the stored picture.
 A picture more than 100 times as tall as wide brought to fewer rows is resampled along y first by Pillow: the calls with
-a source_box or a reducing_gap refuse it; the plain calls do not, and for such a picture they do not make Pillow's bytes."""
+a source_box or a reducing_gap refuse it; the plain calls do not, and for such a picture they do not make Pillow's bytes.
+
+The chain of a Python thumbnailer ends in im.filter(...).  post= (a PillowFilter, or one per picture) runs Pillow
+12.2.0's BoxBlur, GaussianBlur or UnsharpMask over the made upright picture as the call's last step --
+filter(turn(resample(flatten(stored)))) -- in two launches over the batch (sjpeg_hip.h, "Pillow's GaussianBlur, BoxBlur
+and UnsharpMask"); it goes through the box entries and excludes unsharp=, the 3 x 3 mask of this library's own."""
 import ctypes as C
 import enum
 
@@ -93,6 +98,13 @@ def _lib():
         plain = list(getattr(L, f"sjpeg_hip_{mine}_src").argtypes)
         fn = getattr(L, "sjpeg_hip_" + mine.replace("resample_ragged", "resample_box_ragged").replace("resampled", "resampled_box") + "_src")
         fn.restype, fn.argtypes = C.c_int, plain[:at] + two + plain[at:]
+    # (..., box, box_per_frame, unsharp, unsharp_per_frame, ...): the filter stands where the unsharp stood
+    for boxed, mine in (("resample_box_ragged", "filter_ragged"), ("encode_ragged_resampled_box", "encode_ragged_filtered"),
+                        ("encode_ragged_resampled_box_packed", "encode_ragged_filtered_packed")):
+        fn = getattr(L, f"sjpeg_hip_{mine}_src")
+        fn.restype, fn.argtypes = C.c_int, list(getattr(L, f"sjpeg_hip_{boxed}_src").argtypes)
+    L.sjpeg_hip_pillow_filter_weights.restype = C.c_int
+    L.sjpeg_hip_pillow_filter_weights.argtypes = [C.c_int, C.c_float] + [C.c_void_p] * 4
     _bound = True
     return L
 
@@ -223,14 +235,110 @@ def _box_args(who, n, source_box, reducing_gap):
     return arr, C.addressof(arr), 1 if count == n and (boxes_many or gaps_many) else 0
 
 
+# ---- Pillow's filters behind the resample: post=
+
+class _FilterStruct(C.Structure):
+    """struct sjpeg_hip_pillow_filter"""
+    _fields_ = [("kind", C.c_uint8), ("threshold", C.c_uint8), ("percent", C.c_uint16), ("radius_x", C.c_float), ("radius_y", C.c_float),
+                ("reserved", C.c_uint8 * 4)]
+
+
+class PillowFilter:
+    """What post= takes: PIL.ImageFilter's BoxBlur, GaussianBlur or UnsharpMask of Pillow 12.2.0, run over the made
+    upright picture as the last step of the call -- filter(turn(resample(flatten(stored)))) -- in two launches over the
+    batch.  radius is a number or (x, y), the upright picture's axes; an axis whose integer box radius exceeds 63 (a box
+    radius of 64, a sigma above about 64) is refused, which Pillow does not."""
+    NONE, BOX, GAUSSIAN, UNSHARP = 0, 1, 2, 3
+
+    def __init__(self, kind, radius=(0.0, 0.0), percent=0, threshold=0):
+        who = "PillowFilter"
+        if isinstance(radius, (int, float, np.integer, np.floating)) and not isinstance(radius, bool):
+            radius = (radius, radius)
+        try:
+            rx, ry = (float(v) for v in radius)
+        except (TypeError, ValueError):
+            raise SjpegError(f"{who}: radius {radius!r} is not a number or a pair (x, y)")
+        if kind not in (0, 1, 2, 3):
+            raise SjpegError(f"{who}: kind {kind!r} is not one of 0..3 (none, box, gaussian, unsharp mask)")
+        for name, v, hi in (("percent", percent, 65535), ("threshold", threshold, 255)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+                raise SjpegError(f"{who}: {name} {v!r} is not an integer of 0..{hi}")
+        self.kind, self.radius, self.percent, self.threshold = int(kind), (rx, ry), int(percent), int(threshold)
+
+    @classmethod
+    def none(cls):
+        """the picture as it is made (a frame of a mixed batch that is not filtered)"""
+        return cls(cls.NONE)
+
+    @classmethod
+    def box_blur(cls, radius):
+        """ImageFilter.BoxBlur(radius)"""
+        return cls(cls.BOX, radius)
+
+    @classmethod
+    def gaussian_blur(cls, radius=2):
+        """ImageFilter.GaussianBlur(radius)"""
+        return cls(cls.GAUSSIAN, radius)
+
+    @classmethod
+    def unsharp_mask(cls, radius=2, percent=150, threshold=3):
+        """ImageFilter.UnsharpMask(radius, percent, threshold)"""
+        if not isinstance(radius, (int, float, np.integer, np.floating)) or isinstance(radius, bool):
+            raise SjpegError(f"PillowFilter: an unsharp mask has one radius, not {radius!r}")
+        return cls(cls.UNSHARP, radius, percent, threshold)
+
+    def __repr__(self):
+        return f"PillowFilter(kind={self.kind}, radius={self.radius}, percent={self.percent}, threshold={self.threshold})"
+
+    def _struct(self):
+        return _FilterStruct(self.kind, self.threshold, self.percent, self.radius[0], self.radius[1])
+
+
+def _post_args(who, n, post, unsharp=None):
+    """(the struct array, its address, whether there is one per frame) of post -- None, one PillowFilter or one per
+    frame (None in a sequence: that frame is not filtered); (None, None, 0) for None"""
+    if post is None:
+        return None, None, 0
+    if unsharp is not None:
+        raise SjpegError(f"{who}: post= and unsharp= are both given: a call has one last step, Pillow's filter (post=) or the 3 x 3 mask (unsharp=)")
+    if isinstance(post, PillowFilter):
+        arr = (_FilterStruct * 1)(post._struct())
+        return arr, C.addressof(arr), 0
+    try:
+        ps = list(post)
+    except TypeError:
+        raise SjpegError(f"{who}: post {post!r} is not a PillowFilter or a sequence of one per frame")
+    if len(ps) != n or not all(p is None or isinstance(p, PillowFilter) for p in ps):
+        raise SjpegError(f"{who}: post is one PillowFilter or a sequence of one (or None) per frame ({n})")
+    arr = (_FilterStruct * n)(*[(p if p is not None else PillowFilter.none())._struct() for p in ps])
+    return arr, C.addressof(arr), 1
+
+
+def pillow_filter_weights(kind, radius):
+    """sjpeg_hip_pillow_filter_weights: (r, ww, fw, passes) of one axis of a kind (PillowFilter.BOX, GAUSSIAN or
+    UNSHARP) with `radius`, a box radius or a sigma; passes 0: the axis is skipped.  Host only."""
+    out = [C.c_uint32() for _ in range(4)]
+    if _lib().sjpeg_hip_pillow_filter_weights(int(kind), float(np.float32(radius)), *[C.addressof(v) for v in out]) != 0:
+        raise SjpegError(f"sjpeg_hip_pillow_filter_weights failed: {_last_error()}")
+    return tuple(int(v.value) for v in out)
+
+
+def _whole_box():
+    """the box entries' own words for a call without source_box and reducing_gap: the picture of the plain entries"""
+    arr = (_BoxStruct * 1)()
+    return arr, C.addressof(arr), 0
+
+
 # ---- the ragged level: fmt, planes_per_frame and dims as Engine.encode_ragged takes them
 
 def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filter.LANCZOS, orientations=None, flatten=None, unsharp=None,
-                    out=None, source_box=None, reducing_gap=None):
+                    out=None, source_box=None, reducing_gap=None, post=None):
     """sjpeg_hip_resample_ragged_src: the pictures of a ragged batch resampled to sizes[k] = (w, h) (None: their own; the
     STORED orientation; larger or smaller than the source) with `filter` (one Filter or one per frame), turned upright
     and optionally sharpened.  source_box / reducing_gap (one or one per frame): sjpeg_hip_resample_box_ragged_src, the
-    pictures of Image.resize(size, filter, box=, reducing_gap=).  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
+    pictures of Image.resize(size, filter, box=, reducing_gap=).  post (one PillowFilter or one per frame):
+    sjpeg_hip_filter_ragged_src, Pillow's BoxBlur, GaussianBlur or UnsharpMask over the upright pictures; it goes
+    through the box entries, and not with unsharp.  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
     who = "resample_ragged"
     n = len(dims)
     if sizes is not None and len(sizes) != n:
@@ -238,7 +346,13 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
     L = _lib()
     rkeep, raddr, rper = _filter_args(who, n, filter)
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
+    pkeep, paddr, pper = _post_args(who, n, post, unsharp)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
+    entry = "sjpeg_hip_resample_box_ragged_src"
+    if pkeep is not None:
+        if bkeep is None:
+            bkeep, baddr, bper = _whole_box()
+        uaddr, uper, entry = paddr, pper, "sjpeg_hip_filter_ragged_src"
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = li._flat_struct(who, flatten)
@@ -247,10 +361,9 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
         need = L.sjpeg_hip_resample_box_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper)
         out = sj._made_out(who, planes_per_frame, need, out)
         made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-        engine._chk(L.sjpeg_hip_resample_box_ragged_src(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr,
-                                                        bper, uaddr, uper, out.data_ptr(), int(out.numel()) if need else 0, made,
-                                                        C.byref(rfmt), engine._stream()),
-                    "sjpeg_hip_resample_box_ragged_src")
+        engine._chk(getattr(L, entry)(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr, bper, uaddr, uper,
+                                      out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
+                    entry)
         return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
     need = L.sjpeg_hip_resample_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr))
     out = sj._made_out(who, planes_per_frame, need, out)
@@ -263,22 +376,28 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
 
 def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, filter=Filter.LANCZOS,
                             flatten=None, unsharp=None, search=None, metadata=None, packed=False, min_quant=None, q_bias=0x78, dmax_luma=12,
-                            dmax_chroma=1, source_box=None, reducing_gap=None):
-    """sjpeg_hip_encode_ragged_resampled_src / _resampled_packed_src.  Frame k's bytes are those Engine.encode_ragged_full
-    makes of the uint8 picture resample_ragged returns.  Returns (out, sizes, offsets, modes, q, value)."""
+                            dmax_chroma=1, source_box=None, reducing_gap=None, post=None):
+    """sjpeg_hip_encode_ragged_resampled_src / _resampled_packed_src (source_box, reducing_gap: the _resampled_box_
+    entries; post: the _filtered_ ones).  Frame k's bytes are those Engine.encode_ragged_full makes of the uint8 picture
+    resample_ragged returns.  Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_resampled"
     _lib()
     n = len(dims)
     rkeep, raddr, rper = _filter_args(who, n, filter)
+    pkeep, paddr, pper = _post_args(who, n, post, unsharp)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
     call = engine._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                                  dmax_chroma, search, None, metadata)
     keep, faddr = li._flat_struct(who, flatten)
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
+    if pkeep is not None and bkeep is None:
+        bkeep, baddr, bper = _whole_box()
     special = (faddr, call.sizes, call.orientations, raddr, rper, uaddr, uper)
     stem = "sjpeg_hip_encode_ragged_resampled"
     if bkeep is not None:
         special, stem = special[:5] + (baddr, bper) + special[5:], stem + "_box"
+    if pkeep is not None:
+        special, stem = special[:7] + (paddr, pper), "sjpeg_hip_encode_ragged_filtered"
     if packed:
         out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
         return sj._split_meta(n, *engine._packed(stem + "_packed_src", fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta))
@@ -289,14 +408,15 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
 # ---- the picture level: images as resize_images / flatten_images take them
 
 def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, flatten=None, engine=None, layout="hwc", source_box=None,
-                    reducing_gap=None, _shape=None):
+                    reducing_gap=None, post=None, _shape=None):
     """The uint8 pictures PIL.Image.resize(sizes[k], filter) makes of `images`, as views of ONE device buffer from one
     launch: images, orientations, flatten and layout as resize_images / orient_images / flatten_images take them; sizes
     one (w, h) or one per picture, in the STORED orientation, each side 1..65535 -- larger than the source too; filter
     one Filter or one per picture.  source_box=(l, t, r, b) in doubles, in the stored picture's samples, and
     reducing_gap= (None, or 1.0 and more), each one value or one per picture: the pictures of Image.resize(sizes[k],
-    filter, box=, reducing_gap=).  Returns uint8 CUDA tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k]; gray
-    FloatPixels: [h_k, w_k]), rows padded to a multiple of 4 bytes."""
+    filter, box=, reducing_gap=).  post= (one PillowFilter or one per picture, None among them: not filtered): the made
+    upright pictures through im.filter(BoxBlur | GaussianBlur | UnsharpMask), Pillow's bytes again.  Returns uint8 CUDA
+    tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k]; gray FloatPixels: [h_k, w_k]), rows padded to a multiple of 4 bytes."""
     import torch
     who = "resample_images"
     planes, dims, dev, fmt, fp = li._read(who, images, layout, flatten)
@@ -306,10 +426,11 @@ def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, fla
     sizes = li._sizes(who, dims, sizes, None, orientations)
     _filter_args(who, len(dims), filter)
     _box_args(who, len(dims), source_box, reducing_gap)
+    _post_args(who, len(dims), post)
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
         rfmt, made, _ = resample_ragged(eng, fmt, planes, dims, sizes, filter, orientations, flatten, source_box=source_box,
-                                        reducing_gap=reducing_gap)
+                                        reducing_gap=reducing_gap, post=post)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in made] if layout == "chw" and rfmt == sj.SRC_RGB else made
@@ -317,12 +438,12 @@ def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, fla
 
 def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS, unsharp=None, metadata=None, packed=False, orientations=None,
                             flatten=None, quality=75.0, yuv_mode=YUV_420, method=4, use_trellis=False, target_size=None, target_psnr=None,
-                            layout="hwc", engine=None, source_box=None, reducing_gap=None, _shape=None):
+                            layout="hwc", engine=None, source_box=None, reducing_gap=None, post=None, _shape=None):
     """The thumbnail call with Pillow's filters: JPEGs (list of bytes), picture k's byte for byte what encode_images_full
     makes of the picture resample_images returns for the same arguments (sharpened by `unsharp`, an unsharp.Unsharp or
     one per picture, where given).  box=(bw, bh) fits the upright picture into the box and never enlarges; sizes= is
-    explicit and may enlarge.  source_box= and reducing_gap= as resample_images takes them.  The other arguments as
-    unsharp.encode_unsharp_images takes them."""
+    explicit and may enlarge.  source_box=, reducing_gap= and post= as resample_images takes them; post= together with
+    unsharp= is an error.  The other arguments as unsharp.encode_unsharp_images takes them."""
     import torch
     who = "encode_resampled_images"
     planes, dims, dev, fmt, fp = li._read(who, images, layout, flatten)
@@ -334,6 +455,7 @@ def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS,
     sizes = li._sizes(who, dims, sizes, box, orientations)
     _filter_args(who, n, filter)
     _box_args(who, n, source_box, reducing_gap)
+    _post_args(who, n, post, unsharp)
     un._unsharp_args(who, n, unsharp)
     method = li._method(who, method, use_trellis)
     sj._one_target(who, target_size, target_psnr)
@@ -344,7 +466,7 @@ def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS,
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
         res = encode_ragged_resampled(eng, fmt, planes, dims, sizes, orientations, int(yuv_mode), sj._quality_quant(qs), method, filter, flatten,
-                                      unsharp, search, metadata, packed, source_box=source_box, reducing_gap=reducing_gap)
+                                      unsharp, search, metadata, packed, source_box=source_box, reducing_gap=reducing_gap, post=post)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return sj._fetch_packed(res[0], res[1], res[2], n, "image") if packed else sj._fetch_ragged(res[0], res[1], res[2])
 
