@@ -1973,6 +1973,122 @@ int sjpeg_hip_encode_ragged_filtered_packed_src(sjpeg_hip_engine* engine, int fo
                                                 int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
                                                 void* stream);
 
+/* ---- ... and composed behind that: Pillow's ImageOps.pad / expand and the paste of an RGBA overlay ----
+ * Between filter() and save() a Python thumbnailer often has two more links: ImageOps.pad(im, (256, 256), color=...) --
+ * a fixed tile, a letterboxed square -- and im.paste(logo, (x, y), logo), a watermark or badge.  The entries below run
+ * both inside the call and make Pillow 12.2.0's bytes.  COMPOSE is the last link, over the MADE upright bytes:
+ * compose(filter(turn(resample(flatten(stored))))), RGB or gray; every coordinate is the UPRIGHT picture's.
+ * THE DEFINITION (sjpeg_amd/csrc/compose_math.h states it once, for the host, the kernel and the tests):
+ *   Canvas: canvas_width x canvas_height samples filled with colour (a gray picture: colour[0]); the made w x h picture
+ *     is copied to (px, py) and must lie wholly inside.  canvas_width == canvas_height == 0: the picture's own size, no
+ *     fill.  mode 0: (px, py) as given.  mode 1: Pillow's pad rule from the centering (cx, cy), each clamped into 0..1:
+ *     px = round((canvas_width - w) * cx), py likewise, round() Python's (half to even, on the double).
+ *   Overlay places: behind the canvas, places[first_place .. first_place + nplaces) IN LIST ORDER (two overlapping
+ *     overlays do not commute).  A place puts overlays[overlay] with its top-left at (ox, oy) ON THE CANVAS: anchor 0
+ *     top-left (ox = x, oy = y), 1 top-right (ox = cw - ow - x), 2 bottom-left (oy = ch - oh - y), 3 bottom-right
+ *     (both), 4 centre (ox = floor((cw - ow) / 2) + x, oy likewise) -- (x, y) the margin inward from the anchor, so ONE
+ *     struct for the call means "pad to 256 x 256, logo 8 from the bottom-right corner" over pictures of every size.
+ *     The overlay is clipped to the canvas; it may lie partly or wholly outside, where it does nothing; it covers the
+ *     padding as it covers the picture.  Every covered sample: out = blend(out, src, a), a the overlay's alpha,
+ *     t = out * (255 - a) + src * a + 128; blend = ((t >> 8) + t) >> 8 -- (out * (255 - a) + src * a + 127) / 255, which
+ *     is Pillow's paste with the overlay as mask and Image.alpha_composite over an opaque base alike; NOT the sum of two
+ *     rounded products.  src is the overlay's channel on an RGB picture, and on a gray one its luma
+ *     (19595 R + 38470 G + 7471 B + 32768) >> 16.
+ *   Overlays: straight-alpha RGBA bytes on the device, given once per call and referenced by index -- one logo serves
+ *     every frame and is never copied.
+ * ONE LAUNCH over the tiles of every canvas of the batch behind the launches that made the pictures, out of place.
+ *
+ * sjpeg_hip_compose_ragged_bytes: what the canvases take in d_out (0: the call would be refused).
+ * sjpeg_hip_compose_ragged_src, sjpeg_hip_encode_ragged_composed_src / _composed_packed_src: the _filtered_ entries'
+ *   arguments plus compose ([nframes]; compose_per_frame == 0: compose[0] for every frame; NULL), overlays [noverlays]
+ *   and places [nplaces].  The usual layout: every canvas at a multiple of 16, rows whole dwords apart; out_frames carry
+ *   the CANVAS sizes.  Frame k's JPEG is byte for byte what sjpeg_hip_encode_ragged_full_src makes of the canvas.
+ *   compose == NULL, or every frame an identity (canvas 0 x 0 or the picture's own size at (0, 0), and no places):
+ *   exactly the _filtered_ entry -- byte for byte, its messages under its name, no launch more.  A call none of whose
+ *   frames has a filter runs no filter launch.
+ * SJPEG_HIP_EINVAL before any device work, the frame (or overlay, or place) named: a canvas side outside 1..65535
+ *   unless both are 0; a picture not wholly inside its canvas; centerings that are not finite; a mode above 1 or an
+ *   anchor above 4; first_place + nplaces beyond the call's nplaces; more than 8 places for one frame; an overlay index
+ *   out of range; an overlay with a NULL pointer or one that is no multiple of 4, a side outside 1..65535, a stride
+ *   below 4 * width or no multiple of 4; a reserved byte that is not 0; made pictures that are neither RGB nor gray; and
+ *   everything the _filtered_ entries refuse.
+ * Host only, for bindings and tests (0, or SJPEG_HIP_EINVAL with the error set):
+ *   sjpeg_hip_contain_size: ImageOps.contain's target (out[0], out[1]) of a width x height picture in box_width x
+ *     box_height -- the box where width / height == box_width / box_height in doubles, else (box_width,
+ *     round(height / width * box_width)) or (round(width / height * box_height), box_height); a target side of 0
+ *     (1000 x 1 into 10 x 10) is refused, as Pillow raises.
+ *   sjpeg_hip_pad_place: (out[0], out[1]) = (px, py) of mode 1 for a width x height picture on a canvas.
+ *   sjpeg_hip_compose_sample: blend(dst, src, a) of one sample; gray != 0: src is the luma of (r, g, b), else r. */
+typedef struct sjpeg_hip_overlay {
+  const void* rgba;               /* device: R, G, B, A bytes a pixel, straight alpha; a multiple of 4 */
+  int32_t width, height;          /* 1..65535 each */
+  int64_t stride;                 /* bytes between rows: a multiple of 4, at least 4 * width */
+} sjpeg_hip_overlay;              /* 24 bytes */
+typedef struct sjpeg_hip_overlay_place {
+  int32_t overlay;                /* index into the call's overlays */
+  int32_t x, y;                   /* the margin inward from the anchor; may be negative */
+  uint8_t anchor;                 /* 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right, 4 centre */
+  uint8_t reserved[3];            /* must be 0 */
+} sjpeg_hip_overlay_place;        /* 16 bytes */
+typedef struct sjpeg_hip_compose {
+  int32_t canvas_width, canvas_height; /* 1..65535 each, or both 0: the picture's own size */
+  uint8_t mode;                   /* 0: the picture at (px, py); 1: by the centering (cx, cy), Pillow's pad rule */
+  uint8_t colour[3];              /* the canvas's R, G, B; a gray picture uses colour[0] */
+  int32_t px, py;                 /* mode 0 */
+  uint8_t reserved[4];            /* must be 0 */
+  double cx, cy;                  /* mode 1: clamped into 0..1 */
+  int32_t first_place, nplaces;   /* this frame's places: places[first_place .. first_place + nplaces), at most 8 */
+} sjpeg_hip_compose;              /* 48 bytes */
+int sjpeg_hip_contain_size(int width, int height, int box_width, int box_height, int32_t* out /*[2]*/);
+int sjpeg_hip_pad_place(int width, int height, int canvas_width, int canvas_height, double cx, double cy, int32_t* out /*[2]*/);
+int sjpeg_hip_compose_sample(int dst, int r, int g, int b, int a, int gray);
+size_t sjpeg_hip_compose_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                      const int32_t (*sizes)[2] /*or NULL*/, const uint8_t* orientations /*or NULL*/,
+                                      const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                      const sjpeg_hip_compose* compose /*host: [nframes], [1] or NULL*/, int compose_per_frame);
+int sjpeg_hip_compose_ragged_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                 const sjpeg_hip_ragged_frame* frames /*[nframes], host*/, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                 const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                 const uint8_t* orientations /*host [nframes], or NULL*/,
+                                 const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                 const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                 const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                 const sjpeg_hip_compose* compose /*host: [nframes], [1] or NULL*/, int compose_per_frame,
+                                 const sjpeg_hip_overlay* overlays /*host [noverlays], or NULL*/, int noverlays,
+                                 const sjpeg_hip_overlay_place* places /*host [nplaces], or NULL*/, int nplaces,
+                                 void* d_out, size_t bytes, sjpeg_hip_ragged_frame* out_frames /*host out [nframes]*/, int* out_format,
+                                 void* stream);
+int sjpeg_hip_encode_ragged_composed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                         const sjpeg_hip_ragged_frame* frames /*[nframes], host*/,
+                                         const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                         const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                         const uint8_t* orientations /*host [nframes], or NULL*/,
+                                         const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                         const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                         const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                         const sjpeg_hip_compose* compose /*host: [nframes], [1] or NULL*/, int compose_per_frame,
+                                         const sjpeg_hip_overlay* overlays /*host [noverlays], or NULL*/, int noverlays,
+                                         const sjpeg_hip_overlay_place* places /*host [nplaces], or NULL*/, int nplaces,
+                                         const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                         void* d_out, uint64_t* d_sizes /*[nframes]*/,
+                                         int* modes, float* q_out, float* value_out /*host, each may be NULL*/, void* stream);
+int sjpeg_hip_encode_ragged_composed_packed_src(sjpeg_hip_engine* engine, int format, int nframes,
+                                                const sjpeg_hip_ragged_frame* frames /*[nframes], host; out_offset ignored*/,
+                                                const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten /*or NULL*/,
+                                                const int32_t (*sizes)[2] /*host int32[nframes][2], or NULL*/,
+                                                const uint8_t* orientations /*host [nframes], or NULL*/,
+                                                const sjpeg_hip_resample* resample /*host: [nframes] or [1]*/, int resample_per_frame,
+                                                const sjpeg_hip_resample_box* box /*host: [nframes] or [1]*/, int box_per_frame,
+                                                const sjpeg_hip_pillow_filter* filter /*host: [nframes], [1] or NULL*/, int filter_per_frame,
+                                                const sjpeg_hip_compose* compose /*host: [nframes], [1] or NULL*/, int compose_per_frame,
+                                                const sjpeg_hip_overlay* overlays /*host [noverlays], or NULL*/, int noverlays,
+                                                const sjpeg_hip_overlay_place* places /*host [nplaces], or NULL*/, int nplaces,
+                                                const struct sjpeg_hip_metadata* meta /*host: [nframes], [1] or NULL*/, int meta_per_frame,
+                                                void* d_packed, size_t packed_capacity,
+                                                uint64_t* d_offsets /*[nframes + 1]*/, uint64_t* d_sizes /*[nframes]*/,
+                                                int* modes, float* q_out, float* value_out /*host, each may be NULL*/,
+                                                void* stream);
+
 /* ---- host-side helpers (tiny CPU work, no device needed) -----------------------------
  * They produce exactly what the reference's host code would hand to its hot loop, so that
  * a non-C++ binding can drive sjpeg_hip_encode_scan() without re-implementing them. */

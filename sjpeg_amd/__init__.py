@@ -1021,6 +1021,8 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_resampled_box_src", "sjpeg_hip_encode_ragged_resampled_box_packed_src",
     "sjpeg_hip_pillow_filter_weights", "sjpeg_hip_filter_ragged_src", "sjpeg_hip_encode_ragged_filtered_src",
     "sjpeg_hip_encode_ragged_filtered_packed_src",
+    "sjpeg_hip_contain_size", "sjpeg_hip_pad_place", "sjpeg_hip_compose_sample", "sjpeg_hip_compose_ragged_bytes",
+    "sjpeg_hip_compose_ragged_src", "sjpeg_hip_encode_ragged_composed_src", "sjpeg_hip_encode_ragged_composed_packed_src",
 ]
 
 

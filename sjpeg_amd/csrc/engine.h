@@ -223,6 +223,9 @@ struct sjpeg_hip_engine {
   // ... and of Pillow's filters behind the box entries (pillow_filter.hip): the bytes between the launch along the rows
   // and the one along the columns, in the made pictures' layout, and the two launches' descriptors
   DevBuf<uint4> filter_mid, filter_desc;
+  // ... and of the compose stage behind any of them (compose.hip): the canvases where the caller gave no buffer -- memory
+  // of their own, so that the launch is out of place whatever made the pictures -- and the launch's descriptors
+  DevBuf<uint4> composed, compose_desc;
   // the batch search (sjpeg_hip_encode_ragged_search_src): the sizes of its sub-calls on their way to the caller's
   // order -- the engine's, as everything a call leaves queued on its stream
   DevBuf<uint64_t> search_sizes;

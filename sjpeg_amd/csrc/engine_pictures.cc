@@ -1,7 +1,7 @@
 // engine_pictures.cc -- the engine's half of the entries that MAKE pictures for a ragged call: reduction, resize, the
-// YUV-plane resize, contact sheets, the video colour conversion, the unsharp mask and Pillow's filters.  The plans come
-// from the *_plan.cc files, the kernels and their launch functions live in reduce.hip, resize.hip, yuv_colour.hip,
-// unsharp.hip and pillow_filter.hip (ragged_aux.h); here the call is ordered
+// YUV-plane resize, contact sheets, the video colour conversion, the unsharp mask, Pillow's filters and the compose
+// stage.  The plans come from the *_plan.cc files, the kernels and their launch functions live in reduce.hip,
+// resize.hip, yuv_colour.hip, unsharp.hip, pillow_filter.hip and compose.hip (ragged_aux.h); here the call is ordered
 // behind the engine's earlier work, the engine's memory is sized and the descriptors go up.  Host only.
 #include "engine.h"
 
@@ -235,6 +235,33 @@ int sjpeg_internal::engine_pillow_filter(sjpeg_hip_engine* e, const std::string&
                              st) != 0) {
       return fail(SJPEG_HIP_ERUNTIME, who + ": pillow_filter_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
     }
+  }
+  return 0;
+}
+
+// ... and of the compose stage (compose_plan.cc): the one launch behind the launches that made the pictures at
+// src_base, on the same stream, into the caller's buffer or the engine's memory for composed pictures -- never where
+// the made pictures stand.  Every buffer is sized before a pointer into any is taken.
+int sjpeg_internal::engine_compose(sjpeg_hip_engine* e, const std::string& who, const ComposePlan& plan, const uint8_t* src_base, uint8_t* d_out,
+                                   uint8_t** base, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<ComposeFrame> desc = plan.frames;
+  const size_t desc_bytes = sizeof(ComposeFrame) * desc.size();
+  if (d_out == nullptr && e->composed.ensure(plan.bytes / 16 + 1) != 0) {
+    return fail(SJPEG_HIP_ENOMEM, who + ": no device memory for " + std::to_string(plan.bytes) + " bytes of composed pictures");
+  }
+  if (int rc = e->compose_desc.ensure(desc_bytes / 16 + 1)) return rc;
+  if (d_out == nullptr) d_out = reinterpret_cast<uint8_t*>(e->composed.p);
+  if (base != nullptr) *base = d_out;
+  for (ComposeFrame& d : desc) {
+    d.made = src_base + reinterpret_cast<uintptr_t>(d.made);
+    d.dst = d_out + reinterpret_cast<uintptr_t>(d.dst);
+  }
+  if (plan.tiles == 0) return 0;
+  if (int rc = upload(e, e->compose_desc.p, desc.data(), desc_bytes, st)) return rc;
+  if (int rc = sync_uploads(e, st)) return rc;
+  if (compose_launch(reinterpret_cast<const ComposeFrame*>(e->compose_desc.p), static_cast<int>(desc.size()), plan.tiles, st) != 0) {
+    return fail(SJPEG_HIP_ERUNTIME, who + ": compose_kernel launch failed: " + hipGetErrorString(hipGetLastError()));
   }
   return 0;
 }

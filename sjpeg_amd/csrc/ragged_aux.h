@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "compose_math.h"
 #include "jpeg_host.h"
 #include "pillow_filter_math.h"
 #include "pixel_elem.h"
@@ -479,6 +480,59 @@ int pillow_filter_launch(int launch, const PillowFilterPlane* d_planes, int npla
 // uploaded into a buffer of their own and the two launches on `stream`.
 int engine_pillow_filter(sjpeg_hip_engine* e, const std::string& who, const PillowFilterPlan& plan, const uint8_t* src_base, uint8_t* d_out,
                          uint8_t** base, void* stream);
+
+// ---- compose: a canvas and overlays behind the made pictures (sjpeg_hip_compose_ragged_src; compose_plan.cc,
+// compose.hip, compose_math.h): the made RGB or gray pictures of the box or the filtered entries copied onto canvases
+// of their own layout and overlays blended over them by ONE launch -- a flat grid over the tiles of every canvas, a
+// workgroup finds its frame by the binary search over tile_base.  One descriptor per frame with its places resolved:
+// the anchors are gone, an overlay's top-left is a canvas coordinate.  A frame without compose is a canvas of the
+// picture's own size: copied by the same launch.
+struct ComposePlace {
+  const uint8_t* rgba;                   // the overlay's first pixel: a multiple of 4
+  int ox, oy;                            // its top-left on the canvas; may be negative or beyond the canvas
+  unsigned ow, oh;                       // its size in pixels
+  unsigned stride;                       // bytes between its rows: a multiple of 4
+  unsigned unused;
+};
+struct ComposeFrame {
+  const uint8_t* made;                   // the made picture's first sample: a multiple of 4 (the plan: from the pictures' base)
+  uint8_t* dst;                          // the canvas's first sample: a multiple of 16 (the plan: from the canvases' base)
+  unsigned cw, ch;                       // the canvas, pixels and rows
+  unsigned w, h, px, py;                 // the picture and where it lies: px + w <= cw, py + h <= ch
+  unsigned src_stride, dst_stride;       // bytes between rows: multiples of 4
+  unsigned step;                         // bytes a pixel: 3 (interleaved RGB) or 1
+  unsigned colour;                       // the canvas's colour: R | G << 8 | B << 16 (gray: R alone is used)
+  unsigned nplaces;                      // 0..kComposePlacesMax
+  unsigned tile_base;                    // the frame's first workgroup in the grid
+  ComposePlace place[kComposePlacesMax];
+};
+struct ComposePlan {
+  std::vector<ComposeFrame> frames;      // frame after frame
+  unsigned tiles = 0;                    // the grid
+  size_t bytes = 0;                      // what the canvases take from their base
+  bool identity = true;                  // every frame is its picture at its own size and has no place
+};
+// 0 for structs the entries take, else SJPEG_HIP_EINVAL naming the frame, overlay or place: what can be said without
+// the pictures -- reserved bytes, modes, anchors, canvas sides, centerings, the place ranges, overlay indices, overlays
+int compose_check(const std::string& who, int nframes, const sjpeg_hip_compose* compose, int compose_per_frame, const sjpeg_hip_overlay* overlays,
+                  int noverlays, const sjpeg_hip_overlay_place* places, int nplaces);
+// NULL, or every frame's canvas 0 x 0 with the picture at (0, 0) and no place (reserved bytes 0): nothing to compose
+// whatever the pictures are
+bool compose_all_none(int nframes, const sjpeg_hip_compose* compose, int compose_per_frame);
+// The structs checked, then the descriptors over `made` -- nframes made pictures of `format` (SJPEG_HIP_SRC_RGB or
+// _GRAY, anything else is refused) standing at `base` --: the canvases in the usual layout from offset 0, the places
+// resolved, the grid.  A picture that leaves its canvas is refused, naming the frame.
+int compose_plan(const std::string& who, int format, int nframes, const sjpeg_hip_ragged_frame* made, const uint8_t* base,
+                 const sjpeg_hip_compose* compose, int compose_per_frame, const sjpeg_hip_overlay* overlays, int noverlays,
+                 const sjpeg_hip_overlay_place* places, int nplaces, ComposePlan* plan);
+// the canvases as frames at `base`; out_offset and out_capacity are the caller's frames'
+void compose_plan_frames(const ComposePlan& plan, const sjpeg_hip_ragged_frame* frames, uint8_t* base, sjpeg_hip_ragged_frame* out);
+int compose_launch(const ComposeFrame* d_frames, int nframes, unsigned tiles, hipStream_t st);
+// The engine's half (engine_pictures.cc): the descriptors rebased -- made to src_base, dst to d_out (NULL: the engine's
+// memory for COMPOSED pictures, so that the launch is out of place whatever made the pictures) --, uploaded into a
+// buffer of their own, and the launch on `stream`
+int engine_compose(sjpeg_hip_engine* e, const std::string& who, const ComposePlan& plan, const uint8_t* src_base, uint8_t* d_out, uint8_t** base,
+                   void* stream);
 
 // ---- packed output of the ragged encodes (sjpeg_hip_encode_ragged_packed_src): where the frames of a call go when they
 // lie back to back in one buffer.  Every ragged flow takes it as one optional argument (NULL: the frames' own

@@ -3,7 +3,8 @@
 // the YUV-plane formats (yuv_resize_plan.cc), their samples bytes or 16-bit words, and placed into contact sheets
 // (sheet_plan.cc), sharpened by the unsharp mask behind any of it but a sheet (unsharp_plan.cc, unsharp.hip), and
 // resampled with Pillow's filters, enlarging too (resample_plan.cc, resample.hip), and filtered by Pillow's BoxBlur,
-// GaussianBlur or UnsharpMask behind that (pillow_filter_plan.cc, pillow_filter.hip).  Per
+// GaussianBlur or UnsharpMask behind that (pillow_filter_plan.cc, pillow_filter.hip), and composed behind that: onto a
+// canvas, under overlays (compose_plan.cc, compose.hip).  Per
 // family a shape entry -- the made pictures into the caller's buffer -- and an encode entry with
 // its packed twin: the pictures into the engine's memory and ONE _full_ call (ragged_full.cc) over them.  Host code only.
 //
@@ -43,6 +44,12 @@ struct Shape {
   int box_per_frame = 0;
   const sjpeg_hip_pillow_filter* filter = nullptr;
   int filter_per_frame = 0;
+  const sjpeg_hip_compose* compose = nullptr;
+  int compose_per_frame = 0;
+  const sjpeg_hip_overlay* overlays = nullptr;
+  int noverlays = 0;
+  const sjpeg_hip_overlay_place* places = nullptr;
+  int nplaces = 0;
 };
 Shape linear_shape(const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_flatten* flatten, const sjpeg_hip_sheet* sheet, int light) {
   Shape s{nullptr, sizes, orientations, flatten, sheet};
@@ -233,6 +240,40 @@ struct FilterKind : K {
   }
 };
 
+// ... and any per-frame kind K with the compose stage behind it (compose_plan.cc, compose.hip): K's plan, then the
+// compose plan over the pictures K makes, read off K's own frames at a placeholder address; K's pictures into the
+// engine's memory, then the one compose launch from there to the caller's buffer or the engine's composed pictures.
+// Unlike UnsharpKind and FilterKind it OWNS frames(), bytes and the sizes: the canvases are not K's layout
+template <class K>
+struct ComposeKind : PerFrameKind {
+  struct Plan {
+    typename K::Plan made;
+    ComposePlan compose;
+    size_t bytes = 0;
+  };
+  static constexpr bool yuv_only = K::yuv_only;
+  static constexpr int esz = K::esz;
+  static int plan(const std::string& who, int format, int n, const Frame* fr, const Shape& s, Plan* p) {
+    if (int rc = K::plan(who, format, n, fr, s, &p->made)) return rc;
+    uint8_t* const at = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16));
+    std::vector<Frame> made(static_cast<size_t>(n));
+    K::frames(p->made, fr, at, made.data());
+    if (int rc = compose_plan(who, K::format(p->made), n, made.data(), at, s.compose, s.compose_per_frame, s.overlays, s.noverlays, s.places,
+                              s.nplaces, &p->compose)) {
+      return rc;
+    }
+    p->bytes = p->compose.bytes;
+    return 0;
+  }
+  static int format(const Plan& p) { return K::format(p.made); }
+  static void frames(const Plan& p, const Frame* fr, uint8_t* base, Frame* out) { compose_plan_frames(p.compose, fr, base, out); }
+  static int run(sjpeg_hip_engine* e, const std::string& who, const Plan& p, uint8_t* d_out, uint8_t** base, void* stream) {
+    uint8_t* staged = nullptr;
+    if (int rc = K::run(e, who, p.made, nullptr, &staged, stream)) return rc;
+    return engine_compose(e, who, p.compose, staged, d_out, base, stream);
+  }
+};
+
 int source_mode(const SourceLayout* L) { return L->implied != 0 ? L->implied : SJPEG_HIP_YUV444; }
 
 // ---- the shape entries: the made pictures into the caller's buffer
@@ -287,7 +328,8 @@ const std::string kReduced[2] = SJPEG_ENTRY_NAMES("reduced"), kResized[2] = SJPE
                   kSheetYuv16[2] = SJPEG_ENTRY_NAMES("sheet_yuv16"), kLinear[2] = SJPEG_ENTRY_NAMES("linear"),
                   kSheetLinear[2] = SJPEG_ENTRY_NAMES("sheet_linear"), kUnsharp[2] = SJPEG_ENTRY_NAMES("unsharp"),
                   kYuvUnsharp[2] = SJPEG_ENTRY_NAMES("yuv_unsharp"), kResampled[2] = SJPEG_ENTRY_NAMES("resampled"),
-                  kResampledBox[2] = SJPEG_ENTRY_NAMES("resampled_box"), kFiltered[2] = SJPEG_ENTRY_NAMES("filtered");
+                  kResampledBox[2] = SJPEG_ENTRY_NAMES("resampled_box"), kFiltered[2] = SJPEG_ENTRY_NAMES("filtered"),
+                  kComposed[2] = SJPEG_ENTRY_NAMES("composed");
 #undef SJPEG_ENTRY_NAMES
 
 // a packed call's frames go where the placement kernel says: their out_offset is not read
@@ -622,6 +664,78 @@ int filtered_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t
   s.box = box; s.box_per_frame = box_per_frame;
   s.filter = filter; s.filter_per_frame = filter_per_frame;
   return planned_flow<FilterKind<ResampleBoxKind>>(c, s);
+}
+
+// The compose stage behind the filtered entries.  compose NULL, or every frame an identity -- a canvas of 0 x 0, or of
+// the made picture's own size with the picture at (0, 0), and no place --: exactly the filtered call on the same
+// arguments, under its name.  Otherwise one compose launch runs behind the launches that made the pictures; a call
+// none of whose frames has a filter runs no filter launch.
+struct ComposeArgs {
+  const sjpeg_hip_compose* compose;
+  int compose_per_frame;
+  const sjpeg_hip_overlay* overlays;
+  int noverlays;
+  const sjpeg_hip_overlay_place* places;
+  int nplaces;
+};
+// whether every frame is an identity; a call with a canvas that the box plan refuses is not: this entry says why
+bool nothing_to_compose(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2], const uint8_t* orientations,
+                        const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                        const sjpeg_hip_flatten* flatten, const ComposeArgs& a) {
+  if (a.compose == nullptr) return true;
+  if (a.compose_per_frame != 0 && (nframes < 1 || nframes > 65535)) return false;      // (compose is [nframes] only where nframes is a count)
+  if (compose_all_none(nframes, a.compose, a.compose_per_frame)) return true;
+  // a frame with a canvas: an identity where the canvas is the made picture's size -- which the plan knows
+  const int n = a.compose_per_frame != 0 ? nframes : 1;
+  for (int f = 0; f < n; ++f) if (a.compose[f].nplaces != 0) return false;
+  if (frames == nullptr || resample == nullptr || box == nullptr || nframes < 1 || nframes > 65535 || source_layout(format) == nullptr) return false;
+  static const std::string quiet = "sjpeg_hip_compose_ragged_src";
+  if (compose_check(quiet, nframes, a.compose, a.compose_per_frame, a.overlays, a.noverlays, a.places, a.nplaces) != 0) return false;
+  try {
+    ResamplePlan made;
+    if (resample_box_plan(quiet, format, nframes, frames, sizes, orientations, resample, resample_per_frame, box, box_per_frame, flatten, &made) != 0) {
+      return false;
+    }
+    std::vector<Frame> pictures(static_cast<size_t>(nframes));
+    resample_plan_frames(made, frames, reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(16)), pictures.data());
+    for (int f = 0; f < nframes; ++f) {
+      const sjpeg_hip_compose& c = a.compose[a.compose_per_frame != 0 ? f : 0];
+      const bool own = c.canvas_width == 0 && c.canvas_height == 0;
+      if (!own && (c.canvas_width != pictures[f].width || c.canvas_height != pictures[f].height)) return false;
+      if (c.mode == 0 && (c.px != 0 || c.py != 0)) return false;
+    }
+    return true;
+  } catch (...) {
+    return false;
+  }
+}
+Shape composed_shape(const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_resample* resample,
+                     int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame, const sjpeg_hip_pillow_filter* filter,
+                     int filter_per_frame, const ComposeArgs& a) {
+  Shape s = resample_shape(sizes, orientations, flatten, resample, resample_per_frame, nullptr, 0);
+  s.box = box; s.box_per_frame = box_per_frame;
+  s.filter = filter; s.filter_per_frame = filter_per_frame;
+  s.compose = a.compose; s.compose_per_frame = a.compose_per_frame;
+  s.overlays = a.overlays; s.noverlays = a.noverlays;
+  s.places = a.places; s.nplaces = a.nplaces;
+  return s;
+}
+int composed_entry(RaggedCall c, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                   const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                   const sjpeg_hip_pillow_filter* filter, int filter_per_frame, const ComposeArgs& a) {
+  if (nothing_to_compose(c.format, c.nframes, c.frames, sizes, orientations, resample, resample_per_frame, box, box_per_frame, flatten, a)) {
+    return filtered_entry(c, flatten, sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame);
+  }
+  c.who = &kComposed[c.out.packed];
+  if (int rc = encode_prologue(c)) return rc;
+  if (int rc = resample_check(*c.who, c.nframes, resample, resample_per_frame)) return rc;
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, *c.who + ": box == NULL");
+  if (int rc = pillow_filter_check(*c.who, c.nframes, filter, filter_per_frame)) return rc;
+  if (int rc = compose_check(*c.who, c.nframes, a.compose, a.compose_per_frame, a.overlays, a.noverlays, a.places, a.nplaces)) return rc;
+  if (int rc = orientations_check(*c.who, orientations, c.nframes)) return rc;
+  const Shape s = composed_shape(flatten, sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame, a);
+  if (nothing_to_filter(c.nframes, filter, filter_per_frame)) return planned_flow<ComposeKind<ResampleBoxKind>>(c, s);
+  return planned_flow<ComposeKind<FilterKind<ResampleBoxKind>>>(c, s);
 }
 
 }  // namespace
@@ -1267,6 +1381,86 @@ int sjpeg_hip_encode_ragged_filtered_packed_src(sjpeg_hip_engine* e, int format,
   return filtered_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
                          RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten,
                         sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame);
+}
+
+// ---- ... and composed behind that: a canvas and overlays by one launch (compose.hip)
+size_t sjpeg_hip_compose_ragged_bytes(int format, int nframes, const sjpeg_hip_ragged_frame* frames, const int32_t (*sizes)[2],
+                                      const uint8_t* orientations, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                      const sjpeg_hip_compose* compose, int compose_per_frame) {
+  if (frames == nullptr || box == nullptr || nframes < 1 || nframes > 65535) return 0;
+  try {
+    // (the layout depends on neither the filter nor the overlays: the places are counted, not read)
+    const sjpeg_hip_resample filter = {SJPEG_HIP_RESAMPLE_BOX, {0, 0, 0}};
+    Shape s = resample_shape(sizes, orientations, nullptr, &filter, 0, nullptr, 0);
+    s.box = box; s.box_per_frame = box_per_frame;
+    std::vector<sjpeg_hip_compose> bare;
+    if (compose != nullptr) {
+      bare.assign(compose, compose + (compose_per_frame != 0 ? nframes : 1));
+      for (sjpeg_hip_compose& c : bare) {
+        if (c.nplaces < 0 || c.nplaces > kComposePlacesMax || c.first_place < 0) return 0;
+        c.first_place = 0; c.nplaces = 0;
+      }
+      s.compose = bare.data(); s.compose_per_frame = compose_per_frame;
+    }
+    ComposeKind<ResampleBoxKind>::Plan plan;
+    if (ComposeKind<ResampleBoxKind>::plan("sjpeg_hip_compose_ragged_bytes", format, nframes, frames, s, &plan) != 0) return 0;
+    return plan.bytes;
+  } catch (...) {
+    return 0;
+  }
+}
+
+int sjpeg_hip_compose_ragged_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                 const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2], const uint8_t* orientations,
+                                 const sjpeg_hip_resample* resample, int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                 const sjpeg_hip_pillow_filter* filter, int filter_per_frame, const sjpeg_hip_compose* compose,
+                                 int compose_per_frame, const sjpeg_hip_overlay* overlays, int noverlays, const sjpeg_hip_overlay_place* places,
+                                 int nplaces, void* d_out, size_t out_bytes, sjpeg_hip_ragged_frame* out_frames, int* out_format, void* stream) {
+  static const std::string who = "sjpeg_hip_compose_ragged_src";
+  static constexpr ShapeWords w = {kOrientWords.pointers, "d_out", "bytes", "composed pictures", "sjpeg_hip_compose_ragged_bytes"};
+  const ComposeArgs a = {compose, compose_per_frame, overlays, noverlays, places, nplaces};
+  if (nothing_to_compose(format, nframes, frames, sizes, orientations, resample, resample_per_frame, box, box_per_frame, flatten, a)) {
+    return sjpeg_hip_filter_ragged_src(e, format, nframes, frames, flatten, sizes, orientations, resample, resample_per_frame, box, box_per_frame,
+                                       filter, filter_per_frame, d_out, out_bytes, out_frames, out_format, stream);
+  }
+  if (e == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": engine == NULL");
+  if (resample == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": resample == NULL");
+  if (box == nullptr) return set_error(SJPEG_HIP_EINVAL, who + ": box == NULL");
+  const Shape s = composed_shape(flatten, sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame, a);
+  if (nothing_to_filter(nframes, filter, filter_per_frame)) {
+    return shape_body<ComposeKind<ResampleBoxKind>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr,
+                                                    out_format, stream);
+  }
+  return shape_body<ComposeKind<FilterKind<ResampleBoxKind>>>(who, w, e, format, nframes, frames, s, false, d_out, out_bytes, out_frames, nullptr,
+                                                              out_format, stream);
+}
+
+int sjpeg_hip_encode_ragged_composed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                         const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten, const int32_t (*sizes)[2],
+                                         const uint8_t* orientations, const sjpeg_hip_resample* resample, int resample_per_frame,
+                                         const sjpeg_hip_resample_box* box, int box_per_frame, const sjpeg_hip_pillow_filter* filter,
+                                         int filter_per_frame, const sjpeg_hip_compose* compose, int compose_per_frame,
+                                         const sjpeg_hip_overlay* overlays, int noverlays, const sjpeg_hip_overlay_place* places, int nplaces,
+                                         const sjpeg_hip_metadata* meta, int meta_per_frame, void* d_out, uint64_t* d_sizes, int* modes,
+                                         float* q_out, float* value_out, void* stream) {
+  return composed_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                         {d_out, d_sizes, modes, q_out, value_out, stream}}, flatten, sizes, orientations, resample, resample_per_frame, box,
+                        box_per_frame, filter, filter_per_frame, {compose, compose_per_frame, overlays, noverlays, places, nplaces});
+}
+
+int sjpeg_hip_encode_ragged_composed_packed_src(sjpeg_hip_engine* e, int format, int nframes, const sjpeg_hip_ragged_frame* frames,
+                                                const sjpeg_hip_ragged_params* params, const sjpeg_hip_flatten* flatten,
+                                                const int32_t (*sizes)[2], const uint8_t* orientations, const sjpeg_hip_resample* resample,
+                                                int resample_per_frame, const sjpeg_hip_resample_box* box, int box_per_frame,
+                                                const sjpeg_hip_pillow_filter* filter, int filter_per_frame, const sjpeg_hip_compose* compose,
+                                                int compose_per_frame, const sjpeg_hip_overlay* overlays, int noverlays,
+                                                const sjpeg_hip_overlay_place* places, int nplaces, const sjpeg_hip_metadata* meta,
+                                                int meta_per_frame, void* d_packed, size_t packed_capacity, uint64_t* d_offsets,
+                                                uint64_t* d_sizes, int* modes, float* q_out, float* value_out, void* stream) {
+  return composed_entry({nullptr, e, format, nframes, frames, params, meta, meta_per_frame,
+                         RaggedOut{d_packed, d_sizes, modes, q_out, value_out, stream}.packed_into(packed_capacity, d_offsets)}, flatten,
+                        sizes, orientations, resample, resample_per_frame, box, box_per_frame, filter, filter_per_frame,
+                        {compose, compose_per_frame, overlays, noverlays, places, nplaces});
 }
 
 }  // extern "C"

@@ -544,7 +544,7 @@ void sjpeg_hip_engine_destroy(sjpeg_hip_engine* e) {
   e->ubuf.release(); e->chunk_ff.release(); e->partial.release(); e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->risk_table.release(); e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
-  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release(); e->final_pictures.release(); e->unsharp_desc.release(); e->resample_tables.release(); e->filter_mid.release(); e->filter_desc.release();
+  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release(); e->final_pictures.release(); e->unsharp_desc.release(); e->resample_tables.release(); e->filter_mid.release(); e->filter_desc.release(); e->composed.release(); e->compose_desc.release();
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& sg : e->stage) {
     if (sg.busy) (void)hipEventSynchronize(sg.ev);
@@ -570,7 +570,7 @@ int sjpeg_hip_engine_trim(sjpeg_hip_engine* e) {
   e->seg_off.release(); e->chunk_off.release(); e->hdr_off.release(); e->stamps.release();
   e->frame_flags.release(); e->ragged.release(); e->hdr_stage.release();
   e->auto_buf.release(); e->sharp_arena.release(); e->search_sizes.release(); e->pack_cursor.release();
-  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release(); e->final_pictures.release(); e->unsharp_desc.release(); e->resample_tables.release(); e->filter_mid.release(); e->filter_desc.release();
+  e->reduced.release(); e->reduce_desc.release(); e->colour_desc.release(); e->final_pictures.release(); e->unsharp_desc.release(); e->resample_tables.release(); e->filter_mid.release(); e->filter_desc.release(); e->composed.release(); e->compose_desc.release();
   e->tables.release(); e->header.release();        // (per-frame tables of a large batch are scratch like the rest)
   for (auto& sg : e->stage) {                      // ... and so are the pinned blocks they were uploaded through
     // (their copies are done: the device was waited for above; the event is waited for all the same, so that the
@@ -715,7 +715,7 @@ size_t sjpeg_hip_engine_scratch_bytes(sjpeg_hip_engine* e) {
          b(e->ubuf) + b(e->chunk_ff) + b(e->partial) + b(e->replay) + b(e->seg_off) + b(e->chunk_off) + b(e->stamps) +
          b(e->hdr_off) + b(e->seg_words2) + b(e->seg_nbits2) + b(e->pool2) + b(e->pool_ctr2) + b(e->seg_xbase2) + b(e->ragged) + b(e->hdr_stage) +
          b(e->risk_table) + b(e->auto_buf) + b(e->sharp_arena) + b(e->search_sizes) + b(e->pack_cursor) + b(e->reduced) + b(e->reduce_desc) + b(e->colour_desc) +
-         b(e->final_pictures) + b(e->unsharp_desc) + b(e->resample_tables) + b(e->filter_mid) + b(e->filter_desc);
+         b(e->final_pictures) + b(e->unsharp_desc) + b(e->resample_tables) + b(e->filter_mid) + b(e->filter_desc) + b(e->composed) + b(e->compose_desc);
 }
 
 int sjpeg_hip_scan_coeffs_src(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int width, int height,

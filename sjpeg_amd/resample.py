@@ -20,7 +20,12 @@ a source_box or a reducing_gap refuse it; the plain calls do not, and for such a
 The chain of a Python thumbnailer ends in im.filter(...).  post= (a PillowFilter, or one per picture) runs Pillow
 12.2.0's BoxBlur, GaussianBlur or UnsharpMask over the made upright picture as the call's last step --
 filter(turn(resample(flatten(stored)))) -- in two launches over the batch (sjpeg_hip.h, "Pillow's GaussianBlur, BoxBlur
-and UnsharpMask"); it goes through the box entries and excludes unsharp=, the 3 x 3 mask of this library's own."""
+and UnsharpMask"); it goes through the box entries and excludes unsharp=, the 3 x 3 mask of this library's own.
+
+Two links often stand between filter and save: ImageOps.pad / expand and im.paste(logo, (x, y), logo).  compose= (a
+Compose, or one per picture) runs both as the call's very last step, in ONE launch over the batch's canvases --
+compose(filter(turn(resample(flatten(stored))))) -- in the UPRIGHT picture's coordinates and to Pillow's bytes
+(sjpeg_hip.h, "composed behind that").  pad_images / encode_padded_images are ImageOps.pad of the upright picture."""
 import ctypes as C
 import enum
 
@@ -105,6 +110,21 @@ def _lib():
         fn.restype, fn.argtypes = C.c_int, list(getattr(L, f"sjpeg_hip_{boxed}_src").argtypes)
     L.sjpeg_hip_pillow_filter_weights.restype = C.c_int
     L.sjpeg_hip_pillow_filter_weights.argtypes = [C.c_int, C.c_float] + [C.c_void_p] * 4
+    # (..., filter, filter_per_frame, ...): compose, overlays and places, each with its count, behind the filter
+    six = [C.c_void_p, C.c_int] * 3
+    for filtered, mine, at in (("filter_ragged", "compose_ragged", 13), ("encode_ragged_filtered", "encode_ragged_composed", 14),
+                               ("encode_ragged_filtered_packed", "encode_ragged_composed_packed", 14)):
+        plain = list(getattr(L, f"sjpeg_hip_{filtered}_src").argtypes)
+        fn = getattr(L, f"sjpeg_hip_{mine}_src")
+        fn.restype, fn.argtypes = C.c_int, plain[:at] + six + plain[at:]
+    L.sjpeg_hip_compose_ragged_bytes.restype = C.c_size_t
+    L.sjpeg_hip_compose_ragged_bytes.argtypes = list(L.sjpeg_hip_resample_box_ragged_bytes.argtypes) + two
+    L.sjpeg_hip_contain_size.restype = C.c_int
+    L.sjpeg_hip_contain_size.argtypes = [C.c_int] * 4 + [C.c_void_p]
+    L.sjpeg_hip_pad_place.restype = C.c_int
+    L.sjpeg_hip_pad_place.argtypes = [C.c_int] * 4 + [C.c_double] * 2 + [C.c_void_p]
+    L.sjpeg_hip_compose_sample.restype = C.c_int
+    L.sjpeg_hip_compose_sample.argtypes = [C.c_int] * 6
     _bound = True
     return L
 
@@ -329,16 +349,236 @@ def _whole_box():
     return arr, C.addressof(arr), 0
 
 
+# ---- a canvas and overlays behind everything else: compose=
+
+class _OverlayStruct(C.Structure):
+    """struct sjpeg_hip_overlay"""
+    _fields_ = [("rgba", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int64)]
+
+
+class _PlaceStruct(C.Structure):
+    """struct sjpeg_hip_overlay_place"""
+    _fields_ = [("overlay", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("anchor", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class _ComposeStruct(C.Structure):
+    """struct sjpeg_hip_compose"""
+    _fields_ = [("canvas_width", C.c_int32), ("canvas_height", C.c_int32), ("mode", C.c_uint8), ("colour", C.c_uint8 * 3), ("px", C.c_int32),
+                ("py", C.c_int32), ("reserved", C.c_uint8 * 4), ("cx", C.c_double), ("cy", C.c_double), ("first_place", C.c_int32),
+                ("nplaces", C.c_int32)]
+
+
+ANCHORS = {"top-left": 0, "top-right": 1, "bottom-left": 2, "bottom-right": 3, "centre": 4, "center": 4}
+PLACES_MAX = 8           # overlay places one picture may have
+
+
+class Overlay:
+    """A watermark, logo or badge: a uint8 CUDA tensor [h, w, 4] of straight-alpha R, G, B, A bytes, of any row stride
+    that is a multiple of 4 bytes -- a crop of a larger tensor is one.  It is given to the call once, referenced by
+    every picture that places it, and never copied."""
+
+    def __init__(self, tensor):
+        import torch
+        who = "Overlay"
+        if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.uint8 or not tensor.is_cuda or tensor.dim() != 3 or tensor.shape[2] != 4:
+            raise SjpegError(f"{who}: not a uint8 CUDA tensor [h, w, 4]")
+        h, w = int(tensor.shape[0]), int(tensor.shape[1])
+        if not (1 <= w <= 65535 and 1 <= h <= 65535):
+            raise SjpegError(f"{who}: width {w} or height {h} is not one of 1..65535")
+        if tensor.stride(2) != 1 or tensor.stride(1) != 4 or (h > 1 and (tensor.stride(0) < 4 * w or tensor.stride(0) % 4 != 0)) or tensor.data_ptr() % 4 != 0:
+            raise SjpegError(f"{who}: pixels must be 4 bytes apart, rows a multiple of 4 bytes and at least 4 * width apart, the first pixel at a multiple of 4")
+        self.tensor, self.width, self.height = tensor, w, h
+        self.stride = int(tensor.stride(0)) if h > 1 else 4 * w
+
+    def _struct(self):
+        return _OverlayStruct(self.tensor.data_ptr(), self.width, self.height, self.stride)
+
+
+def _colour(who, colour):
+    if isinstance(colour, (int, np.integer)) and not isinstance(colour, bool):
+        colour = (colour,) * 3
+    try:
+        c = tuple(int(v) for v in colour)
+    except (TypeError, ValueError):
+        c = ()
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise SjpegError(f"{who}: colour {colour!r} is not one byte or (r, g, b) bytes")
+    return c
+
+
+def _pair(who, name, v, kind=int):
+    try:
+        a, b = v
+        return kind(a), kind(b)
+    except (TypeError, ValueError):
+        raise SjpegError(f"{who}: {name} {v!r} is not a pair")
+
+
+class Compose:
+    """What compose= takes: the call's last step over the made UPRIGHT picture.  canvas=(cw, ch) filled with colour (a
+    gray picture uses colour[0]) with the picture at at=(px, py) or, by ImageOps.pad's rule, at
+    round((cw - w) * cx), round((ch - h) * cy) for centering=(cx, cy) (neither given: centred); canvas None: the picture's
+    own size.  Then overlays, in list order: (overlay, (x, y), anchor) pastes the Overlay -- as
+    im.paste(logo, (ox, oy), logo) does -- with (x, y) the margin inward from the anchor "top-left", "top-right",
+    "bottom-left", "bottom-right" or "centre" of the CANVAS; clipped to it, over padding and picture alike.  One Compose
+    can serve pictures of every size."""
+
+    def __init__(self, canvas=None, at=None, centering=None, colour=(0, 0, 0), overlays=(), _border=None):
+        who = "Compose"
+        if at is not None and centering is not None:
+            raise SjpegError(f"{who}: at= and centering= are both given")
+        self.canvas = None if canvas is None else _pair(who, "canvas", canvas)
+        self.at = None if at is None else _pair(who, "at", at)
+        self.centering = None if centering is None else _pair(who, "centering", centering, float)
+        self.colour, self.border = _colour(who, colour), _border
+        self.overlays = []
+        for item in overlays:
+            try:
+                ov, xy, anchor = item if len(item) == 3 else (item[0], item[1], "top-left")
+            except (TypeError, IndexError, ValueError):
+                raise SjpegError(f"{who}: an overlay place is (overlay, (x, y), anchor), not {item!r}")
+            if not isinstance(ov, Overlay):
+                raise SjpegError(f"{who}: {ov!r} is not an Overlay")
+            code = ANCHORS.get(anchor, anchor) if isinstance(anchor, str) else anchor
+            if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= int(code) <= 4:
+                raise SjpegError(f"{who}: anchor {anchor!r} is not one of {sorted(set(ANCHORS))}")
+            self.overlays.append((ov, _pair(who, "an overlay's (x, y)", xy), int(code)))
+        if len(self.overlays) > PLACES_MAX:
+            raise SjpegError(f"{who}: {len(self.overlays)} overlay places are more than {PLACES_MAX}")
+
+    @classmethod
+    def pad(cls, size, colour=(0, 0, 0), centering=(0.5, 0.5), overlays=()):
+        """the canvas of ImageOps.pad(im, size, color=colour, centering=centering), for a picture that fits into size"""
+        return cls(canvas=size, centering=centering, colour=colour, overlays=overlays)
+
+    @classmethod
+    def expand(cls, border=0, fill=0, overlays=()):
+        """ImageOps.expand(im, border, fill): border one number, (left-right, top-bottom) or (left, top, right, bottom)"""
+        b = (border,) * 4 if isinstance(border, (int, np.integer)) else tuple(border)
+        if len(b) == 2:
+            b = b + b
+        if len(b) != 4 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0 for v in b):
+            raise SjpegError(f"Compose.expand: border {border!r} is not one, two or four numbers of 0 and more")
+        return cls(colour=fill, overlays=overlays, _border=tuple(int(v) for v in b))
+
+    def _struct(self, size, first_place):
+        """for an upright picture of `size` (a border needs it; None where the picture is not known: the ragged level)"""
+        c = _ComposeStruct()
+        canvas, at = self.canvas, self.at
+        if self.border is not None:
+            if size is None:
+                raise SjpegError("Compose.expand: the picture's size is not known here; give canvas= and at=")
+            l, t, r, b = self.border
+            canvas, at = (size[0] + l + r, size[1] + t + b), (l, t)
+        if canvas is not None:
+            c.canvas_width, c.canvas_height = canvas
+        c.colour[:] = self.colour
+        if self.centering is not None:
+            c.mode, c.cx, c.cy = 1, self.centering[0], self.centering[1]
+        elif at is not None:
+            c.px, c.py = at
+        elif canvas is not None:
+            c.mode, c.cx, c.cy = 1, 0.5, 0.5
+        c.first_place, c.nplaces = first_place, len(self.overlays)
+        return c
+
+
+def _upright_sizes(dims, sizes, orientations):
+    """the made upright pictures' sizes of a call: sizes[k] (None: the picture's own) turned by orientations[k]"""
+    out = []
+    for k, d in enumerate(dims):
+        w, h = (int(v) for v in (sizes[k] if sizes is not None else d))
+        out.append((h, w) if orientations is not None and int(orientations[k]) >= 5 else (w, h))
+    return out
+
+
+class _ComposeArgs:
+    """what a C call takes for compose=: the six arguments, what they point into, and the canvases' sizes"""
+
+    def __init__(self, who, n, compose, made_sizes):
+        self.given = compose is not None
+        self.args = (None, 0, None, 0, None, 0)
+        self.canvases = list(made_sizes) if made_sizes is not None else None
+        if compose is None:
+            return
+        one = isinstance(compose, Compose)
+        if one:
+            cs = [compose]
+        else:
+            try:
+                cs = list(compose)
+            except TypeError:
+                raise SjpegError(f"{who}: compose {compose!r} is not a Compose or a sequence of one per frame")
+            if len(cs) != n or not all(c is None or isinstance(c, Compose) for c in cs):
+                raise SjpegError(f"{who}: compose is one Compose or a sequence of one (or None) per frame ({n})")
+        if one and compose.border is not None:                    # (a border makes a canvas of every picture's own)
+            one, cs = False, [compose] * n
+        overlays, index, places, structs = [], {}, [], []
+        for k, c in enumerate(cs):
+            c = c if c is not None else Compose()
+            structs.append(c._struct(None if made_sizes is None or one else made_sizes[k], len(places)))
+            for ov, (x, y), anchor in c.overlays:
+                if id(ov) not in index:
+                    index[id(ov)] = len(overlays)
+                    overlays.append(ov)
+                places.append(_PlaceStruct(index[id(ov)], x, y, anchor))
+        self.carr = (_ComposeStruct * len(structs))(*structs)
+        self.oarr = (_OverlayStruct * max(len(overlays), 1))(*[o._struct() for o in overlays])
+        self.parr = (_PlaceStruct * max(len(places), 1))(*places)
+        self.keep = overlays
+        self.args = (C.addressof(self.carr), 0 if one else 1, C.addressof(self.oarr) if overlays else None, len(overlays),
+                     C.addressof(self.parr) if places else None, len(places))
+        if self.canvases is not None:
+            for k in range(n):
+                c = structs[0 if one else k]
+                if c.canvas_width or c.canvas_height:
+                    self.canvases[k] = (int(c.canvas_width), int(c.canvas_height))
+
+
+def _compose_args(who, n, compose, dims, sizes, orientations, unsharp=None):
+    """_ComposeArgs of compose -- None, one Compose or one per frame -- over the made upright pictures of the call"""
+    if compose is not None and unsharp is not None:
+        raise SjpegError(f"{who}: compose= and unsharp= are both given: the compose stage stands behind Pillow's filter (post=), not the 3 x 3 mask")
+    return _ComposeArgs(who, n, compose, _upright_sizes(dims, sizes, orientations) if compose is not None else None)
+
+
+def contain_size(width, height, box):
+    """sjpeg_hip_contain_size: the size ImageOps.contain(im, box) resizes a width x height picture to.  Host only."""
+    bw, bh = _pair("contain_size", "box", box)
+    out = (C.c_int32 * 2)()
+    if _lib().sjpeg_hip_contain_size(int(width), int(height), bw, bh, out) != 0:
+        raise SjpegError(f"sjpeg_hip_contain_size failed: {_last_error()}")
+    return int(out[0]), int(out[1])
+
+
+def pad_place(width, height, canvas, centering=(0.5, 0.5)):
+    """sjpeg_hip_pad_place: where ImageOps.pad puts a width x height picture on `canvas` for `centering`.  Host only."""
+    cw, ch = _pair("pad_place", "canvas", canvas)
+    cx, cy = _pair("pad_place", "centering", centering, float)
+    out = (C.c_int32 * 2)()
+    if _lib().sjpeg_hip_pad_place(int(width), int(height), cw, ch, cx, cy, out) != 0:
+        raise SjpegError(f"sjpeg_hip_pad_place failed: {_last_error()}")
+    return int(out[0]), int(out[1])
+
+
+def compose_sample(dst, src, alpha, gray=False):
+    """sjpeg_hip_compose_sample: one sample of the paste -- dst under src with alpha; gray: src is (r, g, b), its luma
+    is blended.  Host only."""
+    r, g, b = (src if gray else (src, 0, 0))
+    return int(_lib().sjpeg_hip_compose_sample(int(dst), int(r), int(g), int(b), int(alpha), 1 if gray else 0))
+
+
 # ---- the ragged level: fmt, planes_per_frame and dims as Engine.encode_ragged takes them
 
 def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filter.LANCZOS, orientations=None, flatten=None, unsharp=None,
-                    out=None, source_box=None, reducing_gap=None, post=None):
+                    out=None, source_box=None, reducing_gap=None, post=None, compose=None):
     """sjpeg_hip_resample_ragged_src: the pictures of a ragged batch resampled to sizes[k] = (w, h) (None: their own; the
     STORED orientation; larger or smaller than the source) with `filter` (one Filter or one per frame), turned upright
     and optionally sharpened.  source_box / reducing_gap (one or one per frame): sjpeg_hip_resample_box_ragged_src, the
     pictures of Image.resize(size, filter, box=, reducing_gap=).  post (one PillowFilter or one per frame):
     sjpeg_hip_filter_ragged_src, Pillow's BoxBlur, GaussianBlur or UnsharpMask over the upright pictures; it goes
-    through the box entries, and not with unsharp.  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
+    through the box entries, and not with unsharp.  compose (one Compose or one per frame): sjpeg_hip_compose_ragged_src,
+    the canvases with their overlays; not with unsharp either.  Returns (fmt, pictures, buf) as Engine.orient_ragged does."""
     who = "resample_ragged"
     n = len(dims)
     if sizes is not None and len(sizes) != n:
@@ -348,8 +588,9 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
     pkeep, paddr, pper = _post_args(who, n, post, unsharp)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
+    comp = _compose_args(who, n, compose, dims, sizes, orientations, unsharp)
     entry = "sjpeg_hip_resample_box_ragged_src"
-    if pkeep is not None:
+    if pkeep is not None or comp.given:
         if bkeep is None:
             bkeep, baddr, bper = _whole_box()
         uaddr, uper, entry = paddr, pper, "sjpeg_hip_filter_ragged_src"
@@ -357,6 +598,15 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = li._flat_struct(who, flatten)
     # (a batch the library refuses has need == 0: the call below says why)
+    if comp.given:
+        entry = "sjpeg_hip_compose_ragged_src"
+        need = L.sjpeg_hip_compose_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper, *comp.args[:2])
+        out = sj._made_out(who, planes_per_frame, need, out)
+        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
+        engine._chk(getattr(L, entry)(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr, bper, uaddr, uper,
+                                      *comp.args, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
+                    entry)
+        return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
     if bkeep is not None:
         need = L.sjpeg_hip_resample_box_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper)
         out = sj._made_out(who, planes_per_frame, need, out)
@@ -376,9 +626,9 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
 
 def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, filter=Filter.LANCZOS,
                             flatten=None, unsharp=None, search=None, metadata=None, packed=False, min_quant=None, q_bias=0x78, dmax_luma=12,
-                            dmax_chroma=1, source_box=None, reducing_gap=None, post=None):
+                            dmax_chroma=1, source_box=None, reducing_gap=None, post=None, compose=None):
     """sjpeg_hip_encode_ragged_resampled_src / _resampled_packed_src (source_box, reducing_gap: the _resampled_box_
-    entries; post: the _filtered_ ones).  Frame k's bytes are those Engine.encode_ragged_full makes of the uint8 picture
+    entries; post: the _filtered_ ones; compose: the _composed_ ones, the default capacities the canvases' bounds).  Frame k's bytes are those Engine.encode_ragged_full makes of the uint8 picture
     resample_ragged returns.  Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_resampled"
     _lib()
@@ -386,18 +636,25 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
     rkeep, raddr, rper = _filter_args(who, n, filter)
     pkeep, paddr, pper = _post_args(who, n, post, unsharp)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
+    comp = _compose_args(who, n, compose, dims, sizes, orientations, unsharp)
+    capacities = None
+    if comp.given:
+        bound_mode = sj._bound_mode(yuv_mode)
+        capacities = lambda msizes: [sj.frame_bound(w, h, bound_mode, 2048 + m) for (w, h), m in zip(comp.canvases, msizes)]
     call = engine._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
-                                 dmax_chroma, search, None, metadata)
+                                 dmax_chroma, search, capacities, metadata)
     keep, faddr = li._flat_struct(who, flatten)
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
-    if pkeep is not None and bkeep is None:
+    if (pkeep is not None or comp.given) and bkeep is None:
         bkeep, baddr, bper = _whole_box()
     special = (faddr, call.sizes, call.orientations, raddr, rper, uaddr, uper)
     stem = "sjpeg_hip_encode_ragged_resampled"
     if bkeep is not None:
         special, stem = special[:5] + (baddr, bper) + special[5:], stem + "_box"
-    if pkeep is not None:
+    if pkeep is not None or comp.given:
         special, stem = special[:7] + (paddr, pper), "sjpeg_hip_encode_ragged_filtered"
+    if comp.given:
+        special, stem = special + comp.args, "sjpeg_hip_encode_ragged_composed"
     if packed:
         out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
         return sj._split_meta(n, *engine._packed(stem + "_packed_src", fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta))
@@ -408,14 +665,15 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
 # ---- the picture level: images as resize_images / flatten_images take them
 
 def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, flatten=None, engine=None, layout="hwc", source_box=None,
-                    reducing_gap=None, post=None, _shape=None):
+                    reducing_gap=None, post=None, compose=None, _shape=None):
     """The uint8 pictures PIL.Image.resize(sizes[k], filter) makes of `images`, as views of ONE device buffer from one
     launch: images, orientations, flatten and layout as resize_images / orient_images / flatten_images take them; sizes
     one (w, h) or one per picture, in the STORED orientation, each side 1..65535 -- larger than the source too; filter
     one Filter or one per picture.  source_box=(l, t, r, b) in doubles, in the stored picture's samples, and
     reducing_gap= (None, or 1.0 and more), each one value or one per picture: the pictures of Image.resize(sizes[k],
     filter, box=, reducing_gap=).  post= (one PillowFilter or one per picture, None among them: not filtered): the made
-    upright pictures through im.filter(BoxBlur | GaussianBlur | UnsharpMask), Pillow's bytes again.  Returns uint8 CUDA
+    upright pictures through im.filter(BoxBlur | GaussianBlur | UnsharpMask), Pillow's bytes again.  compose= (one
+    Compose or one per picture, None among them): the canvases with their overlays behind that.  Returns uint8 CUDA
     tensors [h_k, w_k, 3] (layout="chw": [3, h_k, w_k]; gray FloatPixels: [h_k, w_k]), rows padded to a multiple of 4 bytes."""
     import torch
     who = "resample_images"
@@ -427,10 +685,11 @@ def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, fla
     _filter_args(who, len(dims), filter)
     _box_args(who, len(dims), source_box, reducing_gap)
     _post_args(who, len(dims), post)
+    _compose_args(who, len(dims), compose, dims, sizes, orientations)
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
         rfmt, made, _ = resample_ragged(eng, fmt, planes, dims, sizes, filter, orientations, flatten, source_box=source_box,
-                                        reducing_gap=reducing_gap, post=post)
+                                        reducing_gap=reducing_gap, post=post, compose=compose)
         if engine is None:
             torch.cuda.current_stream().synchronize()        # (the engine made here goes away with the call)
     return [p.permute(2, 0, 1) for p in made] if layout == "chw" and rfmt == sj.SRC_RGB else made
@@ -438,12 +697,12 @@ def resample_images(images, sizes, filter=Filter.LANCZOS, orientations=None, fla
 
 def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS, unsharp=None, metadata=None, packed=False, orientations=None,
                             flatten=None, quality=75.0, yuv_mode=YUV_420, method=4, use_trellis=False, target_size=None, target_psnr=None,
-                            layout="hwc", engine=None, source_box=None, reducing_gap=None, post=None, _shape=None):
+                            layout="hwc", engine=None, source_box=None, reducing_gap=None, post=None, compose=None, _shape=None):
     """The thumbnail call with Pillow's filters: JPEGs (list of bytes), picture k's byte for byte what encode_images_full
     makes of the picture resample_images returns for the same arguments (sharpened by `unsharp`, an unsharp.Unsharp or
     one per picture, where given).  box=(bw, bh) fits the upright picture into the box and never enlarges; sizes= is
-    explicit and may enlarge.  source_box=, reducing_gap= and post= as resample_images takes them; post= together with
-    unsharp= is an error.  The other arguments as unsharp.encode_unsharp_images takes them."""
+    explicit and may enlarge.  source_box=, reducing_gap=, post= and compose= as resample_images takes them; post= or
+    compose= together with unsharp= is an error.  The other arguments as unsharp.encode_unsharp_images takes them."""
     import torch
     who = "encode_resampled_images"
     planes, dims, dev, fmt, fp = li._read(who, images, layout, flatten)
@@ -456,6 +715,7 @@ def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS,
     _filter_args(who, n, filter)
     _box_args(who, n, source_box, reducing_gap)
     _post_args(who, n, post, unsharp)
+    _compose_args(who, n, compose, dims, sizes, orientations, unsharp)
     un._unsharp_args(who, n, unsharp)
     method = li._method(who, method, use_trellis)
     sj._one_target(who, target_size, target_psnr)
@@ -466,7 +726,8 @@ def encode_resampled_images(images, sizes=None, box=None, filter=Filter.LANCZOS,
     eng = sj._engine_for(engine, dev, fp)
     with torch.cuda.device(dev):
         res = encode_ragged_resampled(eng, fmt, planes, dims, sizes, orientations, int(yuv_mode), sj._quality_quant(qs), method, filter, flatten,
-                                      unsharp, search, metadata, packed, source_box=source_box, reducing_gap=reducing_gap, post=post)
+                                      unsharp, search, metadata, packed, source_box=source_box, reducing_gap=reducing_gap, post=post,
+                                      compose=compose)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         return sj._fetch_packed(res[0], res[1], res[2], n, "image") if packed else sj._fetch_ragged(res[0], res[1], res[2])
 
@@ -511,3 +772,37 @@ def encode_fitted_images(images, size, filter=Filter.BICUBIC, bleed=0.0, centeri
     """JPEGs of the pictures fit_images makes, byte for byte what encode_images_full makes of them.  The other arguments
     as encode_resampled_images takes them (but sizes and box)."""
     return encode_resampled_images(images, filter=filter, _shape=_fit_shape(size, bleed, centering), **kw)
+
+
+# ---- ImageOps.pad: contain's size, then a canvas
+
+def _upright(d, o):
+    return (d[1], d[0]) if o is not None and int(o) >= 5 else (d[0], d[1])
+
+
+def _pad_shape(size, orientations):
+    """(sizes, source boxes) of ImageOps.contain(size) of the UPRIGHT pictures, handed on in the stored orientation: no
+    reducing gap and the whole picture, as contain calls resize"""
+    def shape(dims):
+        ol = sj._orientation_list("pad_images", len(dims), orientations)
+        sizes = []
+        for k, d in enumerate(dims):
+            o = None if ol is None else ol[k]
+            sizes.append(_upright(contain_size(*_upright(d, o), size), o))
+        return sizes, None
+    return shape
+
+
+def pad_images(images, size, filter=Filter.BICUBIC, colour=(0, 0, 0), centering=(0.5, 0.5), orientations=None, overlays=(), **kw):
+    """The pictures ImageOps.pad(im, size, filter, color=colour, centering=centering) makes of the UPRIGHT `images`:
+    contain_size's sizes -- the aspect kept, enlarging too --, then the canvas of `size` with the picture at pad_place's
+    place; overlays=[(overlay, (x, y), anchor), ...] are pasted onto it.  The other arguments as resample_images takes them."""
+    return resample_images(images, None, filter, orientations=orientations, compose=Compose.pad(size, colour, centering, overlays),
+                           _shape=_pad_shape(size, orientations), **kw)
+
+
+def encode_padded_images(images, size, filter=Filter.BICUBIC, colour=(0, 0, 0), centering=(0.5, 0.5), orientations=None, overlays=(), **kw):
+    """JPEGs of the pictures pad_images makes, byte for byte what encode_images_full makes of them.  The other arguments
+    as encode_resampled_images takes them (but sizes and box)."""
+    return encode_resampled_images(images, filter=filter, orientations=orientations, compose=Compose.pad(size, colour, centering, overlays),
+                                   _shape=_pad_shape(size, orientations), **kw)
