@@ -27,6 +27,7 @@
 //   K4 scan_chunk_offsets per frame: exclusive scan of 0xFF counts, final size
 //   K5 stuff_chunks       0xFF -> 0xFF00 byte stuffing (src/bit_writer.h:172-196) into
 //                         the caller's output slot, header in front, FF D9 behind
+//                         (launches that are not fused: stuff_chunks_wave, one wave per chunk)
 //
 // The reference never emits restart markers, so bit-exactness needs exactly this
 // bit-level stitching.
@@ -57,6 +58,7 @@
 #include "sjpeg_hip.h"
 #include "jpeg_host.h"
 #include "engine.h"
+#include "stuff_wave_body.h"
 
 using namespace sjpeg_internal;      // (the engine's types and the launch layer's declarations: engine.h)
 
@@ -1122,7 +1124,8 @@ static int encode_scan_one(sjpeg_hip_engine* e, const sjpeg_hip_source* src, int
   }
   if (s.fused_k4 == 2) hipLaunchKernelGGL(stuff_chunks<2>, dim3(gx, nframes), dim3(kThreads), 0, hs, s);
   else if (s.fused_k4) hipLaunchKernelGGL(stuff_chunks<1>, dim3(gx, nframes), dim3(kThreads), 0, hs, s);
-  else hipLaunchKernelGGL(stuff_chunks<0>, dim3(gx, nframes), dim3(kThreads), 0, hs, s);
+  // (not fused: one wave per chunk over max_chunks, four to a workgroup -- the chunk count is on the device)
+  else hipLaunchKernelGGL(stuff_chunks_wave, dim3((max_chunks + 3u) / 4u, nframes), dim3(kThreads), 0, hs, s);
   HIP_TRY(hipGetLastError());
   dbg_mark("encode: K5 launched");
   if (a.rst && g.nseg - 1 + rst_tail > 0) {
@@ -2151,9 +2154,7 @@ int sjpeg_hip_stitch_bands(sjpeg_hip_engine* e, int nbands, const uint32_t* d_wo
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(scan_chunk_offsets<>, dim3(1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
-  uint32_t gx = 4096u;
-  if (gx > max_chunks) gx = max_chunks;
-  hipLaunchKernelGGL(stuff_chunks<false>, dim3(gx, 1), dim3(kThreads), 0, st, s);
+  hipLaunchKernelGGL(stuff_chunks_wave, dim3((max_chunks + 3u) / 4u, 1), dim3(kThreads), 0, st, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }

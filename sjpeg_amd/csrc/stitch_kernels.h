@@ -151,19 +151,8 @@ __global__ __launch_bounds__(kThreads) void scan_seg_offsets(const StitchArgs a_
 // ------------------------------------------------------------------------------------
 // K3: place every segment in the continuous bit stream, and count 0xFF bytes per 4 KiB chunk
 
-// 0x80 in every byte of w that equals 0xFF (exact, no carries between bytes)
-__device__ __forceinline__ uint32_t ff_bytes(uint32_t w) {
-  // low seven bits all set <=> + 1 carries into bit 7 (never out of the byte), and bit 7 itself set
-  return ((w & 0x7f7f7f7fu) + 0x01010101u) & w & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t count_ff(uint32_t w, int nbytes /*valid leading bytes, MSB first*/) {
-  uint32_t n = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    if (b < nbytes && ((w >> (24 - 8 * b)) & 0xffu) == 0xffu) ++n;
-  }
-  return n;
-}
+// (ff_bytes -- 0x80 in every byte of a word that equals 0xFF -- and count_ff -- the 0xFF bytes among a word's valid
+// leading ones -- live in stuff_wave_body.h, which the host reads too)
 
 // One WAVE per SEGMENT (scatter form): a segment knows where its bits go (seg_off); its
 // words are read coalesced, funnel-shifted to the destination alignment, and every word of the
@@ -876,6 +865,54 @@ __global__ __launch_bounds__(kThreads) void stuff_chunks(const StitchArgs a_in) 
   }
 }
 
+// K5 of the launches that are not fused (K2 and K4 ran as kernels: pipelined mode, packed output, restart mode, bands,
+// more than 8 192 segments): ONE WAVE PER CHUNK, no LDS, no barrier, no atomics -- at 64 registers its waves fit beside
+// K1's four workgroups on a SIMD, where a workgroup of stuff_chunks, holding 8 KiB of LDS, ran INSTEAD of one of K1's.
+// The wave takes its chunk as four sub-blocks of 1 KiB, a lane 16 bytes of each; all four loads go out before the
+// first is used.  Per sub-block the lanes count their 0xFF bytes, the wave scans the counts (DPP), and every lane
+// writes its own bytes straight to the output, the count of the sub-blocks in front carried in a scalar register.
+// The invariant (stuff_wave_body.h, where the lane's part is written for the kernel and the host alike, and
+// tests/cxx/stuff_wave_emul.cc, which holds it to it): every byte of a frame's body is written exactly once, by the
+// lane that owns its source byte; a 0x00 is written by the lane that owns the 0xFF in front of it; no lane ever stores
+// past its last byte.  Nothing is staged, no lane completes a neighbour's bytes, and no order between lanes matters.
+// The grid covers max_chunks (the count is only known on the device): a wave whose chunk lies behind the frame's last
+// leaves at once.  Reads what stuff_chunks<0> reads.
+__global__ __launch_bounds__(kThreads, 8) void stuff_chunks_wave(const StitchArgs a) {
+  const int frame = blockIdx.y;
+  const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t chunk = blockIdx.x * (kThreads / 64) + wave;
+  const unsigned long long T = a.seg_off[static_cast<size_t>(frame) * (a.nseg + 1) + a.nseg];
+  const unsigned long long U = (T + 7) >> 3;
+  const unsigned long long nchunks = (U + kChunkBytes - 1) / kChunkBytes;
+  if (chunk >= nchunks || a.sizes[frame] == 0) return;      // (size 0: did not fit, see K4 -- nchunks may pass max_chunks)
+  const uint32_t* const ub = a.ubuf + static_cast<size_t>(frame) * a.ubuf_words + static_cast<size_t>(chunk) * kChunkWords;
+  const unsigned long long left = U - static_cast<unsigned long long>(chunk) * kChunkBytes;
+  const uint32_t rest = left < kChunkBytes ? static_cast<uint32_t>(left) : static_cast<uint32_t>(kChunkBytes);
+  const uint32_t hsize = a.hdr_off ? a.hdr_off[frame + 1] - a.hdr_off[frame] : a.header_size;
+  uint8_t* const base = frame_out(a, frame) + hsize + static_cast<unsigned long long>(chunk) * kChunkBytes +
+                        a.chunk_off[static_cast<size_t>(frame) * a.max_chunks + chunk];
+  constexpr uint32_t kSub = kChunkBytes / 4;                  // a sub-block: 64 lanes of 16 bytes
+  uint4 q[4];
+  int valid[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t at = k * kSub + 16u * lane;
+    valid[k] = stuff_valid(rest, at);
+    // (a lane behind the stream's end reads the chunk's first bytes, which are there, and uses none of them: the
+    // scratch need not hold the whole of its last chunk)
+    q[k] = *reinterpret_cast<const uint4*>(ub + ((valid[k] != 0 ? at : 0u) >> 2));
+  }
+  uint32_t running = 0;                                      // 0xFF bytes of the sub-blocks in front (wave-uniform)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const StuffLane l = stuff_lane(q[k].x, q[k].y, q[k].z, q[k].w);
+    const uint32_t count = stuff_count(l, valid[k]);
+    const uint32_t incl = wave_inclusive_scan(count);
+    stuff_store(base, k * kSub + 16u * lane + running + (incl - count), l, valid[k], count);
+    running += static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incl), 63));
+  }
+}
 
 // ------------------------------------------------------------------------------------
 // K6 (restart mode only): the RSTn markers.  K1 left 16 zero bits behind every restart interval but
