@@ -88,10 +88,6 @@ def sharp_yuv(fmt, frames):
     u = torch.empty((f, ch, cw), dtype=torch.uint8, device=frames.device)
     v = torch.empty((f, ch, cw), dtype=torch.uint8, device=frames.device)
     L = lib()
-    L.sjpeg_hip_sharp_workspace.restype = C.c_size_t
-    L.sjpeg_hip_sharp_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.sjpeg_hip_sharp_yuv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
     wsz = L.sjpeg_hip_sharp_workspace(w, h, f)
     work = torch.empty(max(wsz, 16), dtype=torch.uint8, device=frames.device)
     rc = L.sjpeg_hip_sharp_yuv(C.byref(src), w, h, f, y.data_ptr(), u.data_ptr(), v.data_ptr(), h * w, ch * cw,
@@ -501,6 +497,15 @@ def _flatten_struct(who, flatten):
     return flatten._struct()
 
 
+def _flatten_segment(who, flatten, keep):
+    """what a shaped call takes for its `flatten`: {"flatten": the address of the Flatten's struct sjpeg_hip_flatten, or
+    None for None}; the struct goes into the list `keep`, which has to outlive the call"""
+    if flatten is None:
+        return {"flatten": None}
+    keep.append(_flatten_struct(who, flatten))
+    return {"flatten": C.addressof(keep[-1])}
+
+
 class Flattened:
     """Pictures with an alpha channel to be coded over a background -- PNG and WebP uploads, logos, cut-outs, a
     renderer's RGBA16F, a matting network's colour plus matte -- wherever Oriented is taken: Flattened(images,
@@ -683,6 +688,8 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
+from sjpeg_amd import _binding  # noqa: E402  (it takes the structures above)
+
 _lib = None
 
 
@@ -700,248 +707,7 @@ def lib() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `make -C sjpeg_amd/csrc` "
                           "(or __graft_entry__.build()); there is no pure-Python fallback")
     L = C.CDLL(LIB_PATH, mode=os.RTLD_LOCAL | os.RTLD_NOW)
-    L.SjpegVersion.restype = C.c_uint32
-    L.SjpegHipLastError.restype = C.c_char_p
-    L.SjpegEncode.restype = C.c_size_t
-    L.SjpegEncode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_u8p), C.c_float,
-                              C.c_int, C.c_int]
-    L.SjpegCompress.restype = C.c_size_t
-    L.SjpegCompress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(_u8p)]
-    L.SjpegFreeBuffer.argtypes = [_u8p]
-    L.SjpegDimensions.restype = C.c_bool
-    L.SjpegDimensions.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 3
-    L.SjpegFindQuantizer.restype = C.c_int
-    L.SjpegFindQuantizer.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.SjpegEstimateQuality.restype = C.c_float
-    L.SjpegEstimateQuality.argtypes = [C.c_void_p, C.c_bool]
-    L.SjpegQuantMatrix.argtypes = [C.c_float, C.c_bool, C.c_void_p]
-    L.sjpeg_hip_abi_version.restype = C.c_int
-    L.sjpeg_hip_device_count.restype = C.c_int
-    L.sjpeg_hip_last_error.restype = C.c_char_p
-    L.sjpeg_hip_engine_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.sjpeg_hip_engine_destroy.argtypes = [C.c_void_p]
-    L.sjpeg_hip_frame_bound.restype = C.c_size_t
-    L.sjpeg_hip_frame_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t]
-    L.sjpeg_hip_encode_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.POINTER(ScanTables),
-                                        C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_coeffs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.POINTER(ScanTables),
-                                        C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_quality_matrices.argtypes = [C.c_float, C.c_void_p]
-    L.sjpeg_hip_finalize_quant.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ScanTables)]
-    L.sjpeg_hip_default_huffman.argtypes = [C.POINTER(ScanTables)]
-    L.sjpeg_hip_make_header.restype = C.c_size_t
-    L.sjpeg_hip_make_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_scan_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_symbol_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                              C.c_int, C.c_int, C.c_int, C.POINTER(ScanTables),
-                                              C.c_void_p, C.c_void_p]
-    srcp = C.POINTER(Source)
-    L.sjpeg_hip_encode_scan_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.POINTER(ScanTables), C.c_void_p, C.c_size_t, C.c_int,
-                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_coeffs_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.POINTER(ScanTables), C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_histogram_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_adapt_sums.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p]
-    L.sjpeg_hip_adapt_sums.restype = C.c_int
-    L.sjpeg_hip_adapt_quant_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                             C.c_int, C.c_int, C.c_void_p]
-    L.sjpeg_hip_adapt_quant_sums.restype = None
-    L.sjpeg_hip_encode_batch_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_size_t, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_encode_batch_src.restype = C.c_int
-    L.sjpeg_hip_engine_set_pipelined.argtypes = [C.c_void_p, C.c_int]
-    L.sjpeg_hip_engine_set_pipelined.restype = C.c_int
-    L.sjpeg_hip_engine_set_pixel_transform.argtypes = [C.c_void_p, C.c_float, C.c_float]
-    L.sjpeg_hip_engine_set_pixel_transform.restype = C.c_int
-    L.sjpeg_hip_engine_get_pixel_transform.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.sjpeg_hip_engine_get_pixel_transform.restype = C.c_int
-    L.sjpeg_hip_engine_set_pixel_transform3.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.sjpeg_hip_engine_set_pixel_transform3.restype = C.c_int
-    L.sjpeg_hip_engine_get_pixel_transform3.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.sjpeg_hip_engine_get_pixel_transform3.restype = C.c_int
-    L.sjpeg_hip_engine_wait.argtypes = [C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_engine_wait.restype = C.c_int
-    L.sjpeg_hip_encode_scan_multi.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.c_int,
-                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_encode_scan_multi.restype = C.c_int
-    L.sjpeg_hip_scan_symbol_stats_multi.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_symbol_stats_multi.restype = C.c_int
-    L.sjpeg_hip_scan_symbol_stats_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  C.POINTER(ScanTables), C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_quant_error_src.argtypes = [C.c_void_p, srcp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.POINTER(ScanTables), C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_engine_entropy_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.sjpeg_hip_segment_count.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.sjpeg_hip_band_bound.restype = C.c_size_t
-    L.sjpeg_hip_band_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.sjpeg_hip_encode_band_src.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_stitch_bands.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p,
-                                         C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_adapt_quant.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_int, C.c_int, C.POINTER(ScanTables)]
-    L.sjpeg_hip_optimize_huffman.argtypes = [C.c_void_p, C.c_int, C.POINTER(HuffmanSpec),
-                                             C.POINTER(ScanTables)]
-    L.sjpeg_hip_make_header_ex.restype = C.c_size_t
-    L.sjpeg_hip_make_header_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.POINTER(HuffmanSpec), C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_engine_set_timing.argtypes = [C.c_void_p, C.c_int]
-    L.sjpeg_hip_engine_last_scan_ms.restype = C.c_float
-    L.sjpeg_hip_engine_last_scan_ms.argtypes = [C.c_void_p]
-    L.sjpeg_hip_engine_last_total_ms.restype = C.c_float
-    L.sjpeg_hip_engine_last_total_ms.argtypes = [C.c_void_p]
-    L.sjpeg_hip_encode_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
-                                              C.c_int, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_void_p]
-    L.sjpeg_hip_encode_ragged_src.restype = C.c_int
-    L.sjpeg_hip_scan_histogram_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                      C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_histogram_ragged_src.restype = C.c_int
-    L.sjpeg_hip_scan_symbol_stats_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_symbol_stats_ragged_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_batch_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_encode_ragged_batch_src.restype = C.c_int
-    L.sjpeg_hip_riskiness_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
-                                                 C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_riskiness_ragged_src.restype = C.c_int
-    L.sjpeg_hip_riskiness_verdict.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_float)]
-    L.sjpeg_hip_riskiness_verdict.restype = C.c_int
-    L.sjpeg_hip_sharp_ragged_workspace.argtypes = [C.c_int, C.POINTER(RaggedFrame)]
-    L.sjpeg_hip_sharp_ragged_workspace.restype = C.c_size_t
-    L.sjpeg_hip_sharp_yuv_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sjpeg_hip_sharp_yuv_ragged.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_auto_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_encode_ragged_auto_src.restype = C.c_int
-    L.sjpeg_hip_scan_quant_error_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_quant_error_ragged_src.restype = C.c_int
-    L.sjpeg_hip_scan_counted_bits_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_scan_counted_bits_ragged_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_search_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                     C.POINTER(SearchParams), C.c_int, C.POINTER(C.c_float),
-                                                     C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_encode_ragged_search_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_trellis_src.argtypes = list(L.sjpeg_hip_encode_ragged_auto_src.argtypes)
-    L.sjpeg_hip_encode_ragged_trellis_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_packed_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                     C.POINTER(RaggedParams), C.c_void_p, C.c_size_t, C.c_void_p,
-                                                     C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float),
-                                                     C.POINTER(C.c_float), C.c_void_p]
-    L.sjpeg_hip_encode_ragged_packed_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_full_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame),
-                                                   C.POINTER(RaggedParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
-                                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
-    L.sjpeg_hip_encode_ragged_full_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_full_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_full_packed_src.restype = C.c_int
-    L.sjpeg_hip_engine_search_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.sjpeg_hip_engine_search_stats.restype = C.c_int
-    L.sjpeg_hip_metadata_size.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
-    L.sjpeg_hip_metadata_size.restype = C.c_int
-    full = list(L.sjpeg_hip_encode_ragged_full_src.argtypes)
-    L.sjpeg_hip_encode_ragged_full_meta_src.argtypes = full[:5] + [C.c_void_p, C.c_int] + full[5:]
-    L.sjpeg_hip_encode_ragged_full_meta_src.restype = C.c_int
-    full = list(L.sjpeg_hip_encode_ragged_full_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes = full[:5] + [C.c_void_p, C.c_int] + full[5:]
-    L.sjpeg_hip_encode_ragged_full_meta_packed_src.restype = C.c_int
-    L.sjpeg_hip_reduced_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sjpeg_hip_reduced_size.restype = C.c_int
-    L.sjpeg_hip_reduce_ragged_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p]
-    L.sjpeg_hip_reduce_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_reduce_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p,
-                                              C.c_size_t, C.POINTER(RaggedFrame), C.POINTER(C.c_int), C.c_void_p]
-    L.sjpeg_hip_reduce_ragged_src.restype = C.c_int
-    full = list(L.sjpeg_hip_encode_ragged_full_meta_src.argtypes)
-    L.sjpeg_hip_encode_ragged_reduced_src.argtypes = full[:5] + [C.c_void_p] + full[5:]
-    L.sjpeg_hip_encode_ragged_reduced_src.restype = C.c_int
-    full = list(L.sjpeg_hip_encode_ragged_full_meta_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes = full[:5] + [C.c_void_p] + full[5:]
-    L.sjpeg_hip_encode_ragged_reduced_packed_src.restype = C.c_int
-    L.sjpeg_hip_fit_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sjpeg_hip_fit_size.restype = C.c_int
-    L.sjpeg_hip_resize_ragged_bytes.argtypes = list(L.sjpeg_hip_reduce_ragged_bytes.argtypes)
-    L.sjpeg_hip_resize_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_resize_ragged_src.argtypes = list(L.sjpeg_hip_reduce_ragged_src.argtypes)
-    L.sjpeg_hip_resize_ragged_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_resized_src.argtypes = list(L.sjpeg_hip_encode_ragged_reduced_src.argtypes)
-    L.sjpeg_hip_encode_ragged_resized_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_reduced_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_resized_packed_src.restype = C.c_int
-    L.sjpeg_hip_oriented_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sjpeg_hip_oriented_size.restype = C.c_int
-    L.sjpeg_hip_orient_ragged_bytes.argtypes = list(L.sjpeg_hip_resize_ragged_bytes.argtypes) + [C.c_void_p]
-    L.sjpeg_hip_orient_ragged_bytes.restype = C.c_size_t
-    plain = list(L.sjpeg_hip_resize_ragged_src.argtypes)
-    L.sjpeg_hip_orient_ragged_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
-    L.sjpeg_hip_orient_ragged_src.restype = C.c_int
-    plain = list(L.sjpeg_hip_encode_ragged_resized_src.argtypes)
-    L.sjpeg_hip_encode_ragged_oriented_src.argtypes = plain[:6] + [C.c_void_p] + plain[6:]
-    L.sjpeg_hip_encode_ragged_oriented_src.restype = C.c_int
-    plain = list(L.sjpeg_hip_encode_ragged_resized_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes = plain[:6] + [C.c_void_p] + plain[6:]
-    L.sjpeg_hip_encode_ragged_oriented_packed_src.restype = C.c_int
-    L.sjpeg_hip_yuv_plane_size.restype = C.c_int
-    L.sjpeg_hip_yuv_plane_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sjpeg_hip_resize_ragged_yuv_bytes.restype = C.c_size_t
-    L.sjpeg_hip_resize_ragged_yuv_bytes.argtypes = list(L.sjpeg_hip_orient_ragged_bytes.argtypes)
-    L.sjpeg_hip_resize_ragged_yuv_src.restype = C.c_int
-    L.sjpeg_hip_resize_ragged_yuv_src.argtypes = list(L.sjpeg_hip_orient_ragged_src.argtypes)
-    L.sjpeg_hip_encode_ragged_yuv_resized_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_yuv_resized_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_src.argtypes)
-    L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_yuv_resized_packed_src.argtypes = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
-    L.sjpeg_hip_sheet_size.restype = C.c_int
-    L.sjpeg_hip_sheet_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sjpeg_hip_sheet_places.restype = C.c_int
-    L.sjpeg_hip_sheet_places.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_sheet_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_sheet_ragged_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_sheet_ragged_src.restype = C.c_int
-    L.sjpeg_hip_sheet_ragged_src.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RaggedFrame), C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.POINTER(RaggedFrame), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                             C.c_void_p]
-    plain = list(L.sjpeg_hip_encode_ragged_oriented_src.argtypes)           # (..., d_out, d_sizes, ...)
-    L.sjpeg_hip_encode_ragged_sheet_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_sheet_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:10] + [C.c_size_t] + plain[10:]
-    plain = list(L.sjpeg_hip_encode_ragged_oriented_packed_src.argtypes)
-    L.sjpeg_hip_encode_ragged_sheet_packed_src.restype = C.c_int
-    L.sjpeg_hip_encode_ragged_sheet_packed_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
-    # (the flattened entries: the oriented and sheet ones plus `flatten`)
-    plain = list(L.sjpeg_hip_orient_ragged_src.argtypes)
-    L.sjpeg_hip_flatten_ragged_src.restype = C.c_int
-    L.sjpeg_hip_flatten_ragged_src.argtypes = plain[:4] + [C.c_void_p] + plain[4:]
-    for packed in ("", "_packed"):
-        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_oriented{packed}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_encode_ragged_flattened{packed}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:5] + [C.c_void_p] + plain[5:]
-        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_sheet{packed}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_encode_ragged_sheet_flat{packed}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:6] + [C.c_void_p] + plain[6:]
-    plain = list(L.sjpeg_hip_sheet_ragged_src.argtypes)
-    L.sjpeg_hip_sheet_ragged_flat_src.restype = C.c_int
-    L.sjpeg_hip_sheet_ragged_flat_src.argtypes = plain[:5] + [C.c_void_p] + plain[5:]
-    L.sjpeg_hip_exif_orientation.argtypes = [C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_exif_orientation.restype = C.c_int
-    L.sjpeg_hip_exif_reset_orientation.argtypes = [C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_exif_reset_orientation.restype = C.c_int
+    _binding.apply(L, EXPORTED_C_SYMBOLS)
     _lib = L
     return L
 
@@ -995,7 +761,7 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_sheet_src", "sjpeg_hip_encode_ragged_sheet_packed_src",
     "sjpeg_hip_flatten_ragged_src", "sjpeg_hip_encode_ragged_flattened_src", "sjpeg_hip_encode_ragged_flattened_packed_src",
     "sjpeg_hip_sheet_ragged_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_src", "sjpeg_hip_encode_ragged_sheet_flat_packed_src",
-    # (bound by sjpeg_amd/video.py)
+    # (called from sjpeg_amd/video.py)
     "sjpeg_hip_yuv_colour_samples", "sjpeg_hip_convert_ragged_yuv_src",
     "sjpeg_hip_encode_ragged_yuv_converted_src", "sjpeg_hip_encode_ragged_yuv_converted_packed_src",
     "sjpeg_hip_sheet_ragged_yuv_colour_src", "sjpeg_hip_encode_ragged_sheet_yuv_colour_src",
@@ -1004,16 +770,16 @@ EXPORTED_C_SYMBOLS = [
     "sjpeg_hip_encode_ragged_yuv16_src", "sjpeg_hip_encode_ragged_yuv16_packed_src",
     "sjpeg_hip_sheet_ragged_yuv16_src", "sjpeg_hip_encode_ragged_sheet_yuv16_src",
     "sjpeg_hip_encode_ragged_sheet_yuv16_packed_src",
-    # (bound by sjpeg_amd/light.py)
+    # (called from sjpeg_amd/light.py)
     "sjpeg_hip_light_table", "sjpeg_hip_light_round", "sjpeg_hip_linear_ragged_src",
     "sjpeg_hip_encode_ragged_linear_src", "sjpeg_hip_encode_ragged_linear_packed_src",
     "sjpeg_hip_sheet_ragged_linear_src", "sjpeg_hip_encode_ragged_sheet_linear_src",
     "sjpeg_hip_encode_ragged_sheet_linear_packed_src",
-    # (bound by sjpeg_amd/unsharp.py)
+    # (called from sjpeg_amd/unsharp.py)
     "sjpeg_hip_unsharp_sample", "sjpeg_hip_unsharp_ragged_src", "sjpeg_hip_encode_ragged_unsharp_src",
     "sjpeg_hip_encode_ragged_unsharp_packed_src", "sjpeg_hip_unsharp_ragged_yuv_src",
     "sjpeg_hip_encode_ragged_yuv_unsharp_src", "sjpeg_hip_encode_ragged_yuv_unsharp_packed_src",
-    # (bound by sjpeg_amd/resample.py)
+    # (called from sjpeg_amd/resample.py)
     "sjpeg_hip_resample_ksize", "sjpeg_hip_resample_table", "sjpeg_hip_resample_ragged_bytes", "sjpeg_hip_resample_ragged_src",
     "sjpeg_hip_encode_ragged_resampled_src", "sjpeg_hip_encode_ragged_resampled_packed_src",
     "sjpeg_hip_thumbnail_size", "sjpeg_hip_fit_crop", "sjpeg_hip_resample_box_decide", "sjpeg_hip_resample_box_ksize",
@@ -1034,9 +800,7 @@ def restart_interval(yuv_mode: int) -> int:
 def header_add_restart(header: bytes, yuv_mode: int) -> bytes:
     """The header with the DRI segment of the restart mode in front of SOS."""
     buf = (C.c_uint8 * (len(header) + 6)).from_buffer_copy(header + b"\0" * 6)
-    f = lib().sjpeg_hip_header_add_restart
-    f.restype = C.c_size_t
-    n = f(buf, C.c_size_t(len(header)), C.c_size_t(len(header) + 6), int(yuv_mode))
+    n = lib().sjpeg_hip_header_add_restart(buf, C.c_size_t(len(header)), C.c_size_t(len(header) + 6), int(yuv_mode))
     if n == 0:
         raise SjpegError("sjpeg_hip_header_add_restart failed")
     return bytes(buf[:n])
@@ -1143,10 +907,7 @@ def last_error() -> str:
 def host_trim() -> int:
     """Releases the device memory the host API caches for the calling thread (sjpeg_hip_host_trim);
     returns the number of bytes given back."""
-    f = lib().sjpeg_hip_host_trim
-    f.restype = C.c_size_t
-    f.argtypes = []
-    return int(f())
+    return int(lib().sjpeg_hip_host_trim())
 
 
 def set_riskiness_table(table: bytes) -> None:
@@ -1161,10 +922,7 @@ def SjpegRiskiness(rgb: np.ndarray):
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     h, w = rgb.shape[0], rgb.shape[1]
     risk = C.c_float(0)
-    L = lib()
-    L.SjpegRiskiness.restype = C.c_int
-    L.SjpegRiskiness.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-    mode = L.SjpegRiskiness(rgb.ctypes.data, w, h, 3 * w, C.byref(risk))
+    mode = lib().SjpegRiskiness(rgb.ctypes.data, w, h, 3 * w, C.byref(risk))
     return int(mode), float(risk.value)
 
 
@@ -1287,8 +1045,6 @@ def adapt_quant_on_device(hists_dev, yuv_mode, quant, min_quant=None, dmax_luma=
     out = torch.from_numpy(np.broadcast_to(q0, (f, 2, 64)).copy()).to(hists_dev.device)
     L = lib()
     st = torch.cuda.current_stream().cuda_stream
-    L.sjpeg_hip_adapt_decide.restype = C.c_int
-    L.sjpeg_hip_adapt_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     rc = L.sjpeg_hip_adapt_sums(hists_dev.contiguous().data_ptr(), f, q0.ctypes.data, mqp, sums.data_ptr(), totlast.data_ptr(), st)
     if rc == 0:
         rc = L.sjpeg_hip_adapt_decide(sums.data_ptr(), totlast.data_ptr(), f, q0.ctypes.data, yuv_mode, dmax_luma, dmax_chroma,
@@ -1339,11 +1095,7 @@ def make_header_meta(w, h, yuv_mode, quant, specs=None, app_markers=b"", exif=b"
     cap = 4096 + len(app_markers) + len(exif) + len(iccp) + len(xmp) + 64 * (len(iccp) // 65000 + len(xmp) // 65000 + 4)
     buf = np.zeros(cap, np.uint8)
     q = np.ascontiguousarray(quant, np.uint8).reshape(2, 64)
-    L = lib()
-    L.sjpeg_hip_make_header_meta.restype = C.c_size_t
-    L.sjpeg_hip_make_header_meta.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t]
-    n = L.sjpeg_hip_make_header_meta(w, h, yuv_mode, q.ctypes.data, specs, C.byref(m), buf.ctypes.data, cap)
+    n = lib().sjpeg_hip_make_header_meta(w, h, yuv_mode, q.ctypes.data, specs, C.byref(m), buf.ctypes.data, cap)
     return buf[:n].tobytes() if n else None
 
 
@@ -1466,18 +1218,12 @@ class Engine:
 
     def scratch_bytes(self) -> int:
         """Device memory the engine holds right now (sjpeg_hip_engine_scratch_bytes)."""
-        f = lib().sjpeg_hip_engine_scratch_bytes
-        f.restype = C.c_size_t
-        f.argtypes = [C.c_void_p]
-        return int(f(self._h))
+        return int(lib().sjpeg_hip_engine_scratch_bytes(self._h))
 
     def trim(self) -> None:
         """Give the engine's scratch back to the device (sjpeg_hip_engine_trim); the next call
         allocates what it needs again."""
-        f = lib().sjpeg_hip_engine_trim
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p]
-        self._chk(f(self._h), "sjpeg_hip_engine_trim")
+        self._chk(lib().sjpeg_hip_engine_trim(self._h), "sjpeg_hip_engine_trim")
 
     @staticmethod
     def _stream():
@@ -1529,13 +1275,9 @@ class Engine:
         f, h, w, _ = frames.shape
         assert out.is_cuda and out.dtype.itemsize == 1 and out.numel() >= f * out_stride and offsets.numel() >= f + 1
         src, _ = make_source(SRC_RGB, [frames.view(f, h, w * 3)])
-        L = lib()
-        L.sjpeg_hip_encode_scan_packed_src.argtypes = [
-            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int,
-            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        rc = L.sjpeg_hip_encode_scan_packed_src(self._h, C.byref(src), w, h, yuv_mode, f, C.byref(tables), header,
-                                                len(header), int(append_eoi), out.data_ptr(), int(out_stride),
-                                                sizes.data_ptr(), offsets.data_ptr(), self._stream())
+        rc = lib().sjpeg_hip_encode_scan_packed_src(self._h, C.byref(src), w, h, yuv_mode, f, C.byref(tables), header,
+                                                    len(header), int(append_eoi), out.data_ptr(), int(out_stride),
+                                                    sizes.data_ptr(), offsets.data_ptr(), self._stream())
         if rc != 0:
             raise SjpegError(f"sjpeg_hip_encode_scan_packed_src: {lib().sjpeg_hip_last_error().decode()}")
         return out, sizes, offsets
@@ -1968,12 +1710,9 @@ class Engine:
         by the caller's frame numbers, offsets[n] the bytes used, or with PACKED_OVERFLOW (bit 63: the int64 is
         negative) the bytes a second try needs; a frame that was dropped has size 0 -- and, with a search,
         (..., q, value) as encode_ragged_search.  The encode is asynchronous on the current torch stream."""
-        out, meta, modes, q_out, v_out = self._encode_ragged_packed(fmt, planes_per_frame, dims, yuv_mode, quant, method,
-                                                                    min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                                                                    capacities, packed_capacity, out)
-        n = len(dims)
-        res = (out, meta[:n], meta[n:], modes)
-        return res if search is None else res + (q_out, v_out)
+        res = self._encode_ragged_packed(fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                                         dmax_chroma, search, capacities, packed_capacity, out)
+        return res[:4] if search is None else res
 
     def _full_call(self, who, n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities,
                    metadata, factors=None, sizes=None, orientations=None, resized=False):
@@ -2009,28 +1748,60 @@ class Engine:
                          (None if marr is None else C.cast(marr, C.c_void_p), meta_per_frame), capacities,
                          ((C.c_int * n)(), (C.c_float * n)(), (C.c_float * n)()), (params, q, mq, sarr, marr, mkeep, fac, arr, oarr))
 
-    def _unpacked(self, symbol, fmt, frames, call, special, out, sizes, offsets):
-        """the C call of an unpacked full-style entry and its return tuple; special: what stands between params and the
-        metadata in its argument list"""
-        self._chk(getattr(lib(), symbol)(self._h, fmt, len(frames), frames, call.params, *special, *call.meta, out.data_ptr(),
-                                         sizes.data_ptr(), *call.results, self._stream()), symbol)
-        return (out, sizes, list(offsets)) + call.answers()
+    def _call_shaped(self, symbol, fmt, frames, call, segments, tail, outs):
+        """the C call of a shaped encode: the head, params, the entry's segments by name, the call's metadata and the
+        tail `tail` -- outs, then the result arrays and the stream"""
+        values = dict(segments() if callable(segments) else segments, head=(self._h, fmt, len(frames), frames), params=call.params)
+        values[tail] = outs + call.results + (self._stream(),)
+        if call.meta != ():
+            values["meta"] = call.meta
+        self._chk(_binding.call(lib(), symbol, values), symbol)
 
-    def _packed(self, symbol, fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta):
-        """... of a packed one, with out, packed_capacity and meta as _packed_out made them: (out, meta -- sizes and
-        offsets as ONE tensor --, modes, q, value)"""
+    def _encode_shaped(self, who, stem, fmt, planes_per_frame, dims, call, segments, packed, out=None, offsets=None,
+                       sizes_out=None, packed_capacity=None, one_tensor=False):
+        """The one body of "encode shaped pictures": sjpeg_hip_encode_ragged_<stem>_src, or packed its _packed_src twin
+        (stem "": sjpeg_hip_encode_ragged_packed_src, the one entry without a family's name), with the call
+        Engine._full_call built and the family's segments by name (a function of no arguments where they are to be made
+        once the output stands).  Returns (out, sizes, offsets, modes, q, value) -- unpacked: offsets a list; packed:
+        sizes [n] and offsets [n + 1] views of ONE int64 device tensor (one_tensor: that tensor in their place)."""
         n = len(dims)
+        symbol = "sjpeg_hip_encode_ragged" + (f"_{stem}" if stem else "") + ("_packed_src" if packed else "_src")
+        if not packed:
+            frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes_out)
+            self._call_shaped(symbol, fmt, frames, call, segments, "unpacked", (out.data_ptr(), sizes_out.data_ptr()))
+            return (out, sizes_out, list(offsets)) + call.answers()
+        out, packed_capacity, meta = _packed_out(who, n, planes_per_frame, call.capacities, packed_capacity, out)
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, call.capacities, out, [0] * n, meta)   # (out_offset ignored)
-        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, call.params, *special, *call.meta, out.data_ptr(),
-                                         packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr(), *call.results,
-                                         self._stream()), symbol)
-        return (out, meta) + call.answers()
+        self._call_shaped(symbol, fmt, frames, call, segments, "packed",
+                          (out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * n, meta.data_ptr()))
+        return ((out, meta) if one_tensor else (out, meta[:n], meta[n:])) + call.answers()
+
+    def _encode_sheets_shaped(self, who, stem, fmt, planes_per_frame, dims, ns, call, segments, packed, out_stride=None, out=None,
+                              packed_capacity=None):
+        """... and of "encode contact sheets": sjpeg_hip_encode_ragged_<stem>_src / _packed_src with what Engine._sheet_call
+        built.  params, the metadata and the results count the ns SHEETS; the unpacked form writes sheet s at s * out_stride."""
+        import torch
+        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
+        if packed:
+            out, packed_capacity, meta = _packed_out(who, ns, planes_per_frame, call.capacities, packed_capacity, out)
+            self._call_shaped(f"sjpeg_hip_encode_ragged_{stem}_packed_src", fmt, frames, call, segments, "packed",
+                              (out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr()))
+            return (out, meta[:ns], meta[ns:]) + call.answers()
+        out_stride = (call.capacities[0] + 15) & ~15 if out_stride is None else int(out_stride)
+        dev = _ragged_device(planes_per_frame)
+        if out is None:
+            out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < out_stride * ns:
+            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of out_stride bytes a sheet")
+        sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
+        self._call_shaped(f"sjpeg_hip_encode_ragged_{stem}_src", fmt, frames, call, segments, "strided",
+                          (out.data_ptr(), out_stride, sizes_out.data_ptr()))
+        return (out, sizes_out, [s * out_stride for s in range(ns)]) + call.answers()
 
     def _encode_ragged_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
-                              dmax_chroma, search, capacities, packed_capacity, out,
-                              symbol="sjpeg_hip_encode_ragged_packed_src", metadata=None):
-        """encode_ragged_packed with sizes and offsets as ONE int64 tensor [2 n + 1] (one copy brings both home).
-        symbol: that entry point, or its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments); with
+                              dmax_chroma, search, capacities, packed_capacity, out, stem="", metadata=None, one_tensor=False):
+        """encode_ragged_packed (one_tensor: sizes and offsets as ONE int64 tensor [2 n + 1], which one copy brings home).
+        stem "": that entry point; "full": its twin sjpeg_hip_encode_ragged_full_packed_src (the same arguments); with
         metadata (as encode_ragged_full takes it) the twin's sjpeg_hip_encode_ragged_full_meta_packed_src."""
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n:
@@ -2042,9 +1813,9 @@ class Engine:
         if call.meta[0] is None:
             call.meta = ()                       # (these entries have a form without the metadata arguments)
         else:
-            symbol = "sjpeg_hip_encode_ragged_full_meta_packed_src"
-        out, packed_capacity, meta = _packed_out("encode_ragged_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
-        return self._packed(symbol, fmt, planes_per_frame, dims, call, (), out, packed_capacity, meta)
+            stem = "full_meta"
+        return self._encode_shaped("encode_ragged_packed", stem, fmt, planes_per_frame, dims, call, {}, True, out=out,
+                                   packed_capacity=packed_capacity, one_tensor=one_tensor)
 
     def encode_ragged_full(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None, q_bias=0x78,
                            dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None, offsets=None, sizes=None,
@@ -2062,11 +1833,10 @@ class Engine:
             raise SjpegError("encode_ragged_full: one entry of planes_per_frame and dims per frame, at least one frame")
         call = self._full_call("encode_ragged_full", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                                dmax_chroma, search, capacities, metadata)
-        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes)
-        symbol = "sjpeg_hip_encode_ragged_full_meta_src"
+        stem = "full_meta"
         if call.meta[0] is None:
-            symbol, call.meta = "sjpeg_hip_encode_ragged_full_src", ()       # (the form without the metadata arguments)
-        return self._unpacked(symbol, fmt, frames, call, (), out, sizes, offsets)
+            stem, call.meta = "full", ()         # (the form without the metadata arguments)
+        return self._encode_shaped("encode_ragged_full", stem, fmt, planes_per_frame, dims, call, {}, False, out, offsets, sizes)
 
     def encode_ragged_full_packed(self, fmt, planes_per_frame, dims, yuv_mode, quant, method=4, min_quant=None,
                                   q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2074,11 +1844,8 @@ class Engine:
         """sjpeg_hip_encode_ragged_full_packed_src: encode_ragged_full into ONE packed buffer, with the arguments and
         the layout of encode_ragged_packed.  Returns (out, sizes, offsets, modes, q, value).  metadata: as
         encode_ragged_full (sjpeg_hip_encode_ragged_full_meta_packed_src)."""
-        out, meta, modes, q_out, v_out = self._encode_ragged_packed(
-            fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-            capacities, packed_capacity, out, symbol="sjpeg_hip_encode_ragged_full_packed_src", metadata=metadata)
-        n = len(dims)
-        return out, meta[:n], meta[n:], modes, q_out, v_out
+        return self._encode_ragged_packed(fmt, planes_per_frame, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
+                                          dmax_chroma, search, capacities, packed_capacity, out, stem="full", metadata=metadata)
 
     def reduce_ragged(self, fmt, planes_per_frame, dims, factors, out=None):
         """sjpeg_hip_reduce_ragged_src: the pictures of a ragged batch (fmt, planes_per_frame, dims as encode_ragged; any
@@ -2092,20 +1859,46 @@ class Engine:
             raise SjpegError("reduce_ragged: one factor per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         fac = (C.c_uint8 * n)(*[min(max(int(f), 0), 255) for f in factors])
-        return self._make_pictures("reduce_ragged", "reduce_ragged", fmt, planes_per_frame, frames, (C.cast(fac, C.c_void_p),), out)
+        return self._make_pictures("reduce_ragged", "reduce_ragged", "reduce_ragged", fmt, planes_per_frame, frames,
+                                   {"factors": C.cast(fac, C.c_void_p)}, {}, out)
 
-    def _make_pictures(self, who, bytes_stem, fmt, planes_per_frame, frames, special, out, flat=None):
-        """the C calls of a picture-making entry -- sjpeg_hip_<bytes_stem>_bytes, then sjpeg_hip_<who>_src -- and its
-        return tuple; special: the entry's own arrays (flat: the struct sjpeg_hip_flatten in front of them)"""
+    def _make_pictures(self, who, stem, bytes_stem, fmt, planes_per_frame, frames, shape, more, out, nsheets=None):
+        """The one body of "make pictures": sjpeg_hip_<bytes_stem>_bytes on the segments `shape`, the buffer, then
+        sjpeg_hip_<stem>_src on `shape` and `more` -- the segments the bytes do not depend on; a function of no arguments
+        where they are to be made once the buffer stands --, and the return tuple
+        (format, views, buffer).  nsheets: the most contact sheets a sheet entry may make (None: one picture a frame)."""
         n = len(frames)
-        need = getattr(lib(), f"sjpeg_hip_{bytes_stem}_bytes")(fmt, n, frames, *special)
+        need = _binding.call(lib(), f"sjpeg_hip_{bytes_stem}_bytes", dict(shape, bytes_head=(fmt, n, frames)))
         out = _made_out(who, planes_per_frame, need, out)
-        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
+        more = more() if callable(more) else more
+        made, ns, rfmt = (RaggedFrame * (n if nsheets is None else nsheets))(), C.c_int(0), C.c_int(-1)
         # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(getattr(lib(), f"sjpeg_hip_{who}_src")(
-            self._h, fmt, n, frames, *(() if flat is None else (C.addressof(flat),)), *special, out.data_ptr(),
-            int(out.numel()) if need else 0, made, C.byref(rfmt), self._stream()), f"sjpeg_hip_{who}_src")
-        return int(rfmt.value), _frame_views(out, made, rfmt.value), out
+        tail = (out.data_ptr(), int(out.numel()) if need else 0, made) + (() if nsheets is None else (C.byref(ns),)) + \
+            (C.byref(rfmt), self._stream())
+        values = dict(shape, **more, head=(self._h, fmt, n, frames))
+        values["pictures" if nsheets is None else "sheets"] = tail
+        self._chk(_binding.call(lib(), f"sjpeg_hip_{stem}_src", values), f"sjpeg_hip_{stem}_src")
+        return int(rfmt.value), _frame_views(out, made if nsheets is None else list(made)[:ns.value], rfmt.value), out
+
+    def _encode_sized(self, who, stem, lists, fmt, planes_per_frame, dims, enc, packed, factors=None, sizes=None, orientations=None,
+                      flatten=None, **outs):
+        """The reduced, resized, oriented, flattened and YUV-resized encodes and their packed forms: the check of the
+        per-frame lists (named `lists` in its text), the call with the bounds of the pictures as they are CODED, and the
+        segments the entry takes.  enc: (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
+        capacities, metadata) as Engine._full_call takes them; outs: the caller's out, offsets, sizes_out, packed_capacity."""
+        n = len(dims)
+        given = factors if stem == "reduced" else sizes
+        if n == 0 or len(planes_per_frame) != n or (given is not None and len(given) != n):
+            raise SjpegError(f"{who}: one entry of planes_per_frame, {lists} per frame, at least one frame")
+        call = self._full_call(who, n, dims, *enc, factors=factors, sizes=sizes, orientations=orientations, resized=stem != "reduced")
+        pieces, keep = _binding.SHAPED[f"sjpeg_hip_encode_ragged_{stem}_src"][1], []
+
+        def segments():
+            values = {name: getattr(call, name) for name in ("factors", "sizes", "orientations") if name in pieces}
+            if "flatten" in pieces:              # (the flattened entries: `flatten`, or NULL, behind params)
+                values.update(_flatten_segment(who, flatten, keep))
+            return values
+        return self._encode_shaped(who, stem, fmt, planes_per_frame, dims, call, segments, packed, **outs)
 
     def encode_ragged_reduced(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
                               q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
@@ -2115,27 +1908,18 @@ class Engine:
         Frame k's bytes are those encode_ragged_full makes of the reduced uint8 picture (Engine.reduce_ragged returns
         it).  dims are the SOURCE sizes; the default capacities are the bounds of the reduced ones.  Returns
         (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
-        n = len(dims)
-        if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
-            raise SjpegError("encode_ragged_reduced: one entry of planes_per_frame, dims and factors per frame, at least one frame")
-        call = self._full_call("encode_ragged_reduced", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                               capacities, metadata, factors=factors)
-        frames, out, sizes, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes)
-        return self._unpacked("sjpeg_hip_encode_ragged_reduced_src", fmt, frames, call, (call.factors,), out, sizes, offsets)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_reduced", "reduced", "dims and factors", fmt, planes_per_frame, dims, enc, False,
+                                  factors=factors, out=out, offsets=offsets, sizes_out=sizes)
 
     def encode_ragged_reduced_packed(self, fmt, planes_per_frame, dims, factors, yuv_mode, quant, method=4, min_quant=None,
                                      q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
                                      packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_reduced_packed_src: encode_ragged_reduced into ONE packed buffer, with the arguments
         and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
-        n = len(dims)
-        if n == 0 or len(planes_per_frame) != n or (factors is not None and len(factors) != n):
-            raise SjpegError("encode_ragged_reduced_packed: one entry of planes_per_frame, dims and factors per frame, at least one frame")
-        call = self._full_call("encode_ragged_reduced_packed", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                               capacities, metadata, factors=factors)
-        out, packed_capacity, meta = _packed_out("encode_ragged_reduced_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
-        return _split_meta(n, *self._packed("sjpeg_hip_encode_ragged_reduced_packed_src", fmt, planes_per_frame, dims, call, (call.factors,), out,
-                                            packed_capacity, meta))
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_reduced_packed", "reduced", "dims and factors", fmt, planes_per_frame, dims, enc, True,
+                                  factors=factors, out=out, packed_capacity=packed_capacity)
 
     def resize_ragged(self, fmt, planes_per_frame, dims, sizes, out=None):
         """sjpeg_hip_resize_ragged_src: the pictures of a ragged batch (fmt, planes_per_frame, dims as encode_ragged; any
@@ -2146,7 +1930,8 @@ class Engine:
             raise SjpegError("resize_ragged: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         arr = _sizes_array("resize_ragged", sizes)
-        return self._make_pictures("resize_ragged", "resize_ragged", fmt, planes_per_frame, frames, (arr.ctypes.data,), out)
+        return self._make_pictures("resize_ragged", "resize_ragged", "resize_ragged", fmt, planes_per_frame, frames,
+                                   {"sizes": arr.ctypes.data}, {}, out)
 
     def encode_ragged_resized(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
                               q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None, out=None,
@@ -2156,55 +1941,48 @@ class Engine:
         pictures.  Frame k's bytes are those encode_ragged_full makes of the resized uint8 picture (Engine.resize_ragged
         returns it).  dims are the SOURCE sizes; the default capacities are the bounds of the resized ones; sizes_out:
         the `sizes` tensor of encode_ragged_full.  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
-        n = len(dims)
-        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
-            raise SjpegError("encode_ragged_resized: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
-        call = self._full_call("encode_ragged_resized", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                               capacities, metadata, sizes=sizes, resized=True)
-        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes_out)
-        return self._unpacked("sjpeg_hip_encode_ragged_resized_src", fmt, frames, call, (call.sizes,), out, sizes_out, offsets)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_resized", "resized", "dims and sizes", fmt, planes_per_frame, dims, enc, False,
+                                  sizes=sizes, out=out, offsets=offsets, sizes_out=sizes_out)
 
     def encode_ragged_resized_packed(self, fmt, planes_per_frame, dims, sizes, yuv_mode, quant, method=4, min_quant=None,
                                      q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
                                      packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_resized_packed_src: encode_ragged_resized into ONE packed buffer, with the arguments
         and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
-        n = len(dims)
-        if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
-            raise SjpegError("encode_ragged_resized_packed: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
-        call = self._full_call("encode_ragged_resized_packed", n, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                               capacities, metadata, sizes=sizes, resized=True)
-        out, packed_capacity, meta = _packed_out("encode_ragged_resized_packed", n, planes_per_frame, call.capacities, packed_capacity, out)
-        return _split_meta(n, *self._packed("sjpeg_hip_encode_ragged_resized_packed_src", fmt, planes_per_frame, dims, call, (call.sizes,), out,
-                                            packed_capacity, meta))
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_resized_packed", "resized", "dims and sizes", fmt, planes_per_frame, dims, enc, True,
+                                  sizes=sizes, out=out, packed_capacity=packed_capacity)
 
     def orient_ragged(self, fmt, planes_per_frame, dims, sizes, orientations, out=None):
         """sjpeg_hip_orient_ragged_src: the pictures of a ragged batch resized to sizes[k] = (w, h) (None: their own
         sizes; the STORED orientation) and turned upright by orientations[k] (EXIF 1..8; None: all 1) in one launch.
         Returns (fmt, pictures, buf) as resize_ragged does: picture k is [h, w, 3] or [h, w] for 1..4, [w, h, ...] for
         5..8.  Row and picture padding of buf may hold anything."""
-        return self._orient_ragged("orient_ragged", fmt, planes_per_frame, dims, None, sizes, orientations, out)
+        return self._orient_ragged("orient_ragged", fmt, planes_per_frame, dims, {}, sizes, orientations, out)
 
     def flatten_ragged(self, fmt, planes_per_frame, dims, flatten, sizes=None, orientations=None, out=None):
         """sjpeg_hip_flatten_ragged_src: orient_ragged of pictures with an alpha channel (fmt SRC_BGRA, SRC_RGBA or
         SRC_RGBA_F32 / _F16 / _BF16), every pixel laid over the Flatten `flatten`'s background as its row is staged --
         flatten, resize and turn in ONE launch; sizes None and orientations None: the flattened pictures themselves.
         Returns (SRC_RGB, pictures, buf) as orient_ragged."""
-        return self._orient_ragged("flatten_ragged", fmt, planes_per_frame, dims, _flatten_struct("flatten_ragged", flatten), sizes,
-                                   orientations, out)
+        flat = _flatten_struct("flatten_ragged", flatten)
+        return self._orient_ragged("flatten_ragged", fmt, planes_per_frame, dims, {"flatten": C.addressof(flat)}, sizes, orientations, out)
 
-    def _orient_ragged(self, who, fmt, planes_per_frame, dims, flat, sizes, orientations, out):
-        """orient_ragged and flatten_ragged (flat: its struct sjpeg_hip_flatten): one argument list, two entries"""
+    def _orient_ragged(self, who, fmt, planes_per_frame, dims, more, sizes, orientations, out, bytes_stem="orient_ragged"):
+        """orient_ragged, flatten_ragged (more: its struct sjpeg_hip_flatten) and resize_ragged_yuv: sjpeg_hip_<who>_src"""
         n = len(dims)
         if sizes is not None and len(sizes) != n:
             raise SjpegError(f"{who}: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
         arr, oarr = _shape_arrays(who, n, sizes, orientations)
-        return self._make_pictures(who, "orient_ragged", fmt, planes_per_frame, frames, (_address(arr), _address(oarr)), out, flat)
+        return self._make_pictures(who, who, bytes_stem, fmt, planes_per_frame, frames,
+                                   {"sizes": _address(arr), "orientations": _address(oarr)}, more, out)
 
     def _oriented_call(self, who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
                        dmax_luma, dmax_chroma, search, capacities, metadata):
-        """what the two oriented encodes share: their check, and the call with the bounds of the UPRIGHT sizes"""
+        """what the encodes of resized and turned pictures share: their check, and the call with the bounds of the UPRIGHT
+        sizes"""
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError(f"{who}: one entry of planes_per_frame, dims, sizes and orientations per frame, at least one frame")
@@ -2219,9 +1997,9 @@ class Engine:
         pictures.  Frame k's bytes are those encode_ragged_full makes of the upright uint8 picture (Engine.orient_ragged
         returns it).  sizes are in the STORED orientation (None: the pictures' own); the default capacities are the
         bounds of the upright sizes.  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full."""
-        return self._encode_oriented("encode_ragged_oriented", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant,
-                                     method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
-                                     sizes_out, metadata)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_oriented", "oriented", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, False,
+                                  sizes=sizes, orientations=orientations, out=out, offsets=offsets, sizes_out=sizes_out)
 
     def encode_ragged_flattened(self, fmt, planes_per_frame, dims, flatten, sizes, orientations, yuv_mode, quant, method=4,
                                 min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2230,52 +2008,27 @@ class Engine:
         Flatten `flatten`'s background in the same launch (None: exactly encode_ragged_oriented).  Frame k's bytes are
         those encode_ragged_full makes of the uint8 picture Engine.flatten_ragged returns; YUV_AUTO, a search and the
         metadata act on that picture.  Returns (out, sizes, offsets, modes, q, value)."""
-        return self._encode_oriented("encode_ragged_flattened", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant,
-                                     method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
-                                     sizes_out, metadata, flatten=flatten, flattened=True)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_flattened", "flattened", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, False,
+                                  sizes=sizes, orientations=orientations, flatten=flatten, out=out, offsets=offsets, sizes_out=sizes_out)
 
     def encode_ragged_flattened_packed(self, fmt, planes_per_frame, dims, flatten, sizes, orientations, yuv_mode, quant, method=4,
                                        min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
                                        capacities=None, packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_flattened_packed_src: encode_ragged_flattened into ONE packed buffer, with the
         arguments and the returns of encode_ragged_oriented_packed."""
-        return self._encode_oriented_packed("encode_ragged_flattened_packed", fmt, planes_per_frame, dims, sizes, orientations,
-                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                                            capacities, packed_capacity, out, metadata, flatten=flatten, flattened=True)
-
-    def _encode_oriented(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant,
-                         q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets, sizes_out, metadata, flatten=None,
-                         flattened=False):
-        """the oriented encode and the one of the YUV-plane formats: one argument list, two entries (sjpeg_hip_<who>_src)"""
-        call = self._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
-                                   dmax_luma, dmax_chroma, search, capacities, metadata)
-        frames, out, sizes_out, offsets = _ragged_frames(planes_per_frame, dims, call.capacities, out, offsets, sizes_out)
-        # (the flattened entries: `flatten`, or NULL, behind params)
-        flat = None if flatten is None else _flatten_struct(who, flatten)
-        special = ((None if flat is None else C.addressof(flat),) if flattened else ()) + (call.sizes, call.orientations)
-        return self._unpacked(f"sjpeg_hip_{who}_src", fmt, frames, call, special, out, sizes_out, offsets)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_flattened_packed", "flattened", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, True,
+                                  sizes=sizes, orientations=orientations, flatten=flatten, out=out, packed_capacity=packed_capacity)
 
     def encode_ragged_oriented_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                       min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
                                       capacities=None, packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_oriented_packed_src: encode_ragged_oriented into ONE packed buffer, with the
         arguments and the layout of encode_ragged_full_packed.  Returns (out, sizes, offsets, modes, q, value)."""
-        return self._encode_oriented_packed("encode_ragged_oriented_packed", fmt, planes_per_frame, dims, sizes, orientations,
-                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                                            capacities, packed_capacity, out, metadata)
-
-    def _encode_oriented_packed(self, who, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method,
-                                min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, packed_capacity, out, metadata,
-                                flatten=None, flattened=False):
-        """... and their packed forms (sjpeg_hip_<who>_src)"""
-        call = self._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias,
-                                   dmax_luma, dmax_chroma, search, capacities, metadata)
-        n = len(dims)
-        out, packed_capacity, meta = _packed_out(who, n, planes_per_frame, call.capacities, packed_capacity, out)
-        flat = None if flatten is None else _flatten_struct(who, flatten)
-        special = ((None if flat is None else C.addressof(flat),) if flattened else ()) + (call.sizes, call.orientations)
-        return _split_meta(n, *self._packed(f"sjpeg_hip_{who}_src", fmt, planes_per_frame, dims, call, special, out,
-                                            packed_capacity, meta))
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_oriented_packed", "oriented", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, True,
+                                  sizes=sizes, orientations=orientations, out=out, packed_capacity=packed_capacity)
 
     def resize_ragged_yuv(self, fmt, planes_per_frame, dims, sizes, orientations=None, out=None):
         """sjpeg_hip_resize_ragged_yuv_src: decoded video frames (fmt SRC_NV12, SRC_NV21, SRC_YUV420 or SRC_YUV444;
@@ -2284,13 +2037,7 @@ class Engine:
         as a picture of its own, in one launch.  Returns (out_fmt, pictures, buf): SRC_YUV420 or SRC_YUV444 -- always
         planar --, picture k a tuple (y, u, v) of uint8 views into buf ([h, w] each; rows padded to a multiple of 4
         bytes, planes at multiples of 16), which any ragged entry takes as its planes.  out as resize_ragged."""
-        n = len(dims)
-        if sizes is not None and len(sizes) != n:
-            raise SjpegError("resize_ragged_yuv: one size per frame")
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        arr, oarr = _shape_arrays("resize_ragged_yuv", n, sizes, orientations)
-        return self._make_pictures("resize_ragged_yuv", "resize_ragged_yuv", fmt, planes_per_frame, frames,
-                                   (_address(arr), _address(oarr)), out)
+        return self._orient_ragged("resize_ragged_yuv", fmt, planes_per_frame, dims, {}, sizes, orientations, out, "resize_ragged_yuv")
 
     def encode_ragged_yuv_resized(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                   min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, capacities=None,
@@ -2301,18 +2048,18 @@ class Engine:
         Engine.resize_ragged_yuv returns, handed over in its out_fmt; yuv_mode is the format's own (YUV_420, or YUV_444
         for SRC_YUV444).  sizes None or the frames' own and orientations None or all 1: exactly encode_ragged_full on
         the caller's frames."""
-        return self._encode_oriented("encode_ragged_yuv_resized", fmt, planes_per_frame, dims, sizes, orientations, yuv_mode,
-                                     quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, out, offsets,
-                                     sizes_out, metadata)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_yuv_resized", "yuv_resized", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, False,
+                                  sizes=sizes, orientations=orientations, out=out, offsets=offsets, sizes_out=sizes_out)
 
     def encode_ragged_yuv_resized_packed(self, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4,
                                          min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
                                          capacities=None, packed_capacity=None, out=None, metadata=None):
         """sjpeg_hip_encode_ragged_yuv_resized_packed_src: encode_ragged_yuv_resized into ONE packed buffer, with the
         arguments and the returns of encode_ragged_oriented_packed."""
-        return self._encode_oriented_packed("encode_ragged_yuv_resized_packed", fmt, planes_per_frame, dims, sizes, orientations,
-                                            yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                                            capacities, packed_capacity, out, metadata)
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, capacities, metadata)
+        return self._encode_sized("encode_ragged_yuv_resized_packed", "yuv_resized", "dims, sizes and orientations", fmt, planes_per_frame, dims, enc, True,
+                                  sizes=sizes, orientations=orientations, out=out, packed_capacity=packed_capacity)
 
     def sheet_ragged(self, fmt, planes_per_frame, dims, sheet, sizes=None, orientations=None, out=None, flatten=None):
         """sjpeg_hip_sheet_ragged_src: the pictures of a ragged batch (any format the resize entries take, the YUV-plane
@@ -2323,30 +2070,19 @@ class Engine:
         uint8 CUDA tensor of at least sjpeg_hip_sheet_ragged_bytes bytes at a multiple of 16 (None: made here).
         flatten (a Flatten; None: today's call): sjpeg_hip_sheet_ragged_flat_src -- pictures of an alpha format laid over
         the flatten's background, which is a field of its own beside the sheet's."""
-        who = "sheet_ragged"
+        who, keep = "sheet_ragged", []
         n = len(dims)
         if sizes is not None and len(sizes) != n:
             raise SjpegError(f"{who}: one size per frame")
         frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        st = _sheet_struct(who, sheet)
-        arr, oarr = _shape_arrays(who, n, sizes, orientations)
-        need = lib().sjpeg_hip_sheet_ragged_bytes(fmt, n, frames, C.addressof(st), _address(arr), _address(oarr))
-        out = _made_out(who, planes_per_frame, need, out)
-        per = max(int(sheet.cols) * int(sheet.rows), 1)
-        made = (RaggedFrame * max((n + per - 1) // per, 1))()
-        ns, rfmt = C.c_int(0), C.c_int(-1)
-        flat = None if flatten is None else _flatten_struct(who, flatten)
-        symbol = "sjpeg_hip_sheet_ragged_src" if flat is None else "sjpeg_hip_sheet_ragged_flat_src"
-        # (a batch the library refuses has need == 0: the call below says why)
-        self._chk(getattr(lib(), symbol)(self._h, fmt, n, frames, C.addressof(st), *(() if flat is None else (C.addressof(flat),)),
-                                         _address(arr), _address(oarr), out.data_ptr(), int(out.numel()) if need else 0, made,
-                                         C.byref(ns), C.byref(rfmt), self._stream()), symbol)
-        return int(rfmt.value), _frame_views(out, list(made)[:ns.value], rfmt.value), out
+        shape, nsheets, skeep = _sheet_shape(who, n, sheet, sizes, orientations)
+        return self._make_pictures(who, "sheet_ragged" if flatten is None else "sheet_ragged_flat", "sheet_ragged", fmt, planes_per_frame, frames,
+                                   shape, lambda: {} if flatten is None else _flatten_segment(who, flatten, keep), out, nsheets)
 
     def _sheet_call(self, who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method, min_quant,
                     q_bias, dmax_luma, dmax_chroma, search, metadata):
-        """what the two sheet encodes share: the sheets' number and bound, the call (params and metadata count SHEETS),
-        and what stands behind params: the struct sjpeg_hip_sheet, the sizes and the orientations"""
+        """what the sheet encodes share: the sheets' number and bound, the call (params and metadata count SHEETS), and
+        the segments every one of them has: the struct sjpeg_hip_sheet, the sizes and the orientations"""
         n = len(dims)
         if n == 0 or len(planes_per_frame) != n or (sizes is not None and len(sizes) != n):
             raise SjpegError(f"{who}: one entry of planes_per_frame, dims and sizes per frame, at least one frame")
@@ -2357,15 +2093,15 @@ class Engine:
                                lambda msizes: [frame_bound(sw, sh, _bound_mode(yuv_mode), 2048 + max(msizes))] * ns, metadata)
         arr, oarr = _shape_arrays(who, n, sizes, orientations)
         call.keep += (st, arr, oarr)
-        return ns, call, [C.addressof(st), _address(arr), _address(oarr)]
+        return ns, call, {"sheet": C.addressof(st), "sizes": _address(arr), "orientations": _address(oarr)}
 
-    def _sheet_symbol(self, who, flatten, special):
-        """the entry of a sheet encode: with a Flatten, sjpeg_hip_<who>_flat..._src and its struct behind the sheet's"""
-        if flatten is None:
-            return f"sjpeg_hip_{who}_src", None
-        flat = _flatten_struct(who, flatten)
-        special.insert(1, C.addressof(flat))
-        return f"sjpeg_hip_{who}_src".replace("_sheet", "_sheet_flat"), flat
+    def _encode_sheet(self, who, packed, fmt, planes_per_frame, dims, sheet, sizes, orientations, enc, flatten, **outs):
+        """encode_ragged_sheet and its packed form; with a Flatten, the _sheet_flat entries and its struct behind the sheet's"""
+        ns, call, segments = self._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, *enc)
+        keep = []
+        return self._encode_sheets_shaped(
+            who, "sheet" if flatten is None else "sheet_flat", fmt, planes_per_frame, dims, ns, call,
+            lambda: segments if flatten is None else dict(segments, **_flatten_segment(who, flatten, keep)), packed, **outs)
 
     def encode_ragged_sheet(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                             min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None, out_stride=None, out=None,
@@ -2376,22 +2112,9 @@ class Engine:
         for gray ones, the format's own for YUV frames.  Sheet s is written at out[s * out_stride:] (default: the bound
         of a sheet).  Returns (out, sizes, offsets, modes, q, value) as encode_ragged_full, one entry per sheet.
         flatten (a Flatten; None: today's call): sjpeg_hip_encode_ragged_sheet_flat_src, as sheet_ragged."""
-        import torch
-        who = "encode_ragged_sheet"
-        ns, call, special = self._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method,
-                                             min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
-        out_stride = (call.capacities[0] + 15) & ~15 if out_stride is None else int(out_stride)
-        dev = _ragged_device(planes_per_frame)
-        if out is None:
-            out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < out_stride * ns:
-            raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of out_stride bytes a sheet")
-        sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        symbol, flat = self._sheet_symbol(who, flatten, special)
-        self._chk(getattr(lib(), symbol)(self._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(),
-                                         out_stride, sizes_out.data_ptr(), *call.results, self._stream()), symbol)
-        return (out, sizes_out, [s * out_stride for s in range(ns)]) + call.answers()
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
+        return self._encode_sheet("encode_ragged_sheet", False, fmt, planes_per_frame, dims, sheet, sizes, orientations, enc, flatten,
+                                  out_stride=out_stride, out=out)
 
     def encode_ragged_sheet_packed(self, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4,
                                    min_quant=None, q_bias=0x78, dmax_luma=12, dmax_chroma=1, search=None,
@@ -2399,16 +2122,9 @@ class Engine:
         """sjpeg_hip_encode_ragged_sheet_packed_src: encode_ragged_sheet into ONE packed buffer, the sheets back to back,
         with the layout of encode_ragged_full_packed over the sheets.  Returns (out, sizes, offsets, modes, q, value):
         sizes [nsheets] and offsets [nsheets + 1] device tensors.  flatten: as encode_ragged_sheet."""
-        who = "encode_ragged_sheet_packed"
-        ns, call, special = self._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method,
-                                             min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
-        out, packed_capacity, meta = _packed_out(who, ns, planes_per_frame, call.capacities, packed_capacity, out)
-        frames, _, _, _ = _ragged_frames(planes_per_frame, dims, None, None, None, None)
-        symbol, flat = self._sheet_symbol(who, flatten, special)
-        self._chk(getattr(lib(), symbol)(self._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(),
-                                         packed_capacity, meta.data_ptr() + 8 * ns, meta.data_ptr(), *call.results,
-                                         self._stream()), symbol)
-        return (out, meta[:ns], meta[ns:]) + call.answers()
+        enc = (yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search, metadata)
+        return self._encode_sheet("encode_ragged_sheet_packed", True, fmt, planes_per_frame, dims, sheet, sizes, orientations, enc, flatten,
+                                  packed_capacity=packed_capacity, out=out)
 
     def search_stats(self):
         """sjpeg_hip_engine_search_stats: six host counters of the engine's most recent encode_ragged_full /
@@ -2452,6 +2168,15 @@ def _shape_arrays(who, n, sizes, orientations):
             None if orientations is None else _orientations_array(who, n, orientations))
 
 
+def _sheet_shape(who, n, sheet, sizes, orientations):
+    """What the contact-sheet makers share: (the segments their _bytes entry takes -- the struct sjpeg_hip_sheet, the
+    sizes and the orientations --, the most sheets n frames make, what the segments point into)"""
+    st = _sheet_struct(who, sheet)
+    arr, oarr = _shape_arrays(who, n, sizes, orientations)
+    per = max(int(sheet.cols) * int(sheet.rows), 1)
+    return {"sheet": C.addressof(st), "sizes": _address(arr), "orientations": _address(oarr)}, max((n + per - 1) // per, 1), (st, arr, oarr)
+
+
 def _packed_out(who, n, planes_per_frame, capacities, packed_capacity, out):
     """The output of a packed call: (out, packed_capacity, the int64 tensor [2 n + 1] of sizes and offsets).
     packed_capacity defaults to len(out), or to the capacities' sum, each rounded up to 16, which always fits."""
@@ -2465,11 +2190,6 @@ def _packed_out(who, n, planes_per_frame, capacities, packed_capacity, out):
     if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < packed_capacity:
         raise SjpegError(f"{who}: out must be a contiguous uint8 CUDA tensor of packed_capacity bytes")
     return out, packed_capacity, torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
-
-
-def _split_meta(n, out, meta, *answers):
-    """a packed call's return tuple: sizes [n] and offsets [n + 1] as views of the one tensor"""
-    return (out, meta[:n], meta[n:]) + answers
 
 
 def _made_out(who, planes_per_frame, need, out):
@@ -2985,7 +2705,7 @@ def _encode_images_full(layout, images, quality, yuv_mode, method, use_trellis, 
     with torch.cuda.device(dev):
         if packed:
             return _encode_images_packed(eng, planes, dims, yuv_mode, _quality_quant(qs), method, min_quant, q_bias,
-                                         dmax_luma, dmax_chroma, search, "sjpeg_hip_encode_ragged_full_packed_src", fmt=fmt,
+                                         dmax_luma, dmax_chroma, search, "full", fmt=fmt,
                                          metadata=metadata)
         out, sizes, offs, _, _, _ = eng.encode_ragged_full(fmt, planes, dims, yuv_mode, _quality_quant(qs), method,
                                                            min_quant, q_bias, dmax_luma, dmax_chroma, search,
@@ -3324,7 +3044,7 @@ def _first_pool(dims, yuv_mode):
 
 
 def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant, q_bias, dmax_luma, dmax_chroma, search,
-                          symbol="sjpeg_hip_encode_ragged_packed_src", fmt=SRC_RGB, metadata=None):
+                          stem="", fmt=SRC_RGB, metadata=None):
     """encode_images through the packed call: a small first pool, one copy of sizes and offsets, one of the pool; the
     pictures a full pool dropped go through a second packed call whose pool is the sum of their bounds."""
     import torch
@@ -3340,7 +3060,7 @@ def _encode_images_packed(eng, planes, dims, yuv_mode, quant, method, min_quant,
             fmt, [planes[k] for k in which], [dims[k] for k in which], yuv_mode,
             [quant[k] for k in which] if isinstance(quant, list) else quant, method, min_quant, q_bias, dmax_luma,
             dmax_chroma, None if search is None else [search[k] for k in which], [bounds[k] for k in which], pool, None,
-            symbol, None if metadata is None else [metas[k] for k in which])
+            stem, None if metadata is None else [metas[k] for k in which], one_tensor=True)
         eng.wait()                               # (pipelined mode: the output is complete after this)
         meta = meta.cpu().numpy()                # sizes and offsets together
         sz, off, end = meta[:m], meta[m:2 * m], int(meta[2 * m])

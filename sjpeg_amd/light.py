@@ -11,33 +11,11 @@ import ctypes as C
 import numpy as np
 
 import sjpeg_amd as sj
-from sjpeg_amd import YUV_420, YUV_AUTO, RaggedFrame, SjpegError, lib
+from sjpeg_amd import YUV_420, YUV_AUTO, SjpegError, lib
 
 CODED, LINEAR_SRGB = 0, 1                # SJPEG_HIP_LIGHT_*
 
-_bound = False
-
-
-def _lib():
-    """the library with the argument types of the entries this module binds: the flattened ones plus `light`"""
-    global _bound
-    L = lib()
-    if _bound:
-        return L
-    L.sjpeg_hip_light_table.restype = C.c_int
-    L.sjpeg_hip_light_table.argtypes = [C.c_int, C.c_void_p]
-    L.sjpeg_hip_light_round.restype = C.c_int
-    L.sjpeg_hip_light_round.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
-    for flat, linear, at in (("flatten_ragged", "linear_ragged", 5), ("sheet_ragged_flat", "sheet_ragged_linear", 6),
-                             ("encode_ragged_flattened", "encode_ragged_linear", 6),
-                             ("encode_ragged_flattened_packed", "encode_ragged_linear_packed", 6),
-                             ("encode_ragged_sheet_flat", "encode_ragged_sheet_linear", 7),
-                             ("encode_ragged_sheet_flat_packed", "encode_ragged_sheet_linear_packed", 7)):
-        plain = list(getattr(L, f"sjpeg_hip_{flat}_src").argtypes)    # (..., flatten, sizes, orientations, ...)
-        fn = getattr(L, f"sjpeg_hip_{linear}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + [C.c_int] + plain[at:]
-    _bound = True
-    return L
+_lib = lib                               # (the one table of sjpeg_amd._binding binds every entry when the library loads)
 
 
 def _light(who, light):
@@ -82,19 +60,12 @@ def linear_ragged(engine, fmt, planes_per_frame, dims, sizes=None, orientations=
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
     light = _light(who, light)
-    L = _lib()
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = _flat_struct(who, flatten)
-    # (a flattened picture has the bytes of the same call on SRC_RGB frames; a batch the library refuses has need == 0:
-    # the call below says why)
-    need = L.sjpeg_hip_orient_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr))
-    out = sj._made_out(who, planes_per_frame, need, out)
-    made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-    engine._chk(L.sjpeg_hip_linear_ragged_src(engine._h, fmt, n, frames, faddr, light, sj._address(arr), sj._address(oarr), out.data_ptr(),
-                                              int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
-                "sjpeg_hip_linear_ragged_src")
-    return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
+    # (a flattened picture has the bytes of the same call on SRC_RGB frames)
+    return engine._make_pictures(who, who, "orient_ragged", fmt, planes_per_frame, frames, {"sizes": sj._address(arr), "orientations": sj._address(oarr)},
+                                 {"flatten": faddr, "light": light}, out)
 
 
 def encode_ragged_linear(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, flatten=None,
@@ -105,18 +76,11 @@ def encode_ragged_linear(engine, fmt, planes_per_frame, dims, sizes, orientation
     returns.  Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_linear"
     light = _light(who, light)
-    _lib()
     call = engine._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                                  dmax_chroma, search, None, metadata)
     keep, faddr = _flat_struct(who, flatten)
-    special = (faddr, light, call.sizes, call.orientations)
-    n = len(dims)
-    if packed:
-        out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
-        return sj._split_meta(n, *engine._packed("sjpeg_hip_encode_ragged_linear_packed_src", fmt, planes_per_frame, dims, call, special, out,
-                                                 packed_capacity, meta))
-    frames, out, sizes_out, offsets = sj._ragged_frames(planes_per_frame, dims, call.capacities, None, None, None)
-    return engine._unpacked("sjpeg_hip_encode_ragged_linear_src", fmt, frames, call, special, out, sizes_out, offsets)
+    return engine._encode_shaped(who, "linear", fmt, planes_per_frame, dims, call,
+                                 {"flatten": faddr, "light": light, "sizes": call.sizes, "orientations": call.orientations}, packed)
 
 
 def sheet_ragged_linear(engine, fmt, planes_per_frame, dims, sheet, sizes=None, orientations=None, flatten=None, light=LINEAR_SRGB,
@@ -128,49 +92,22 @@ def sheet_ragged_linear(engine, fmt, planes_per_frame, dims, sheet, sizes=None, 
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
     light = _light(who, light)
-    L = _lib()
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
-    st = sj._sheet_struct(who, sheet)
-    arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
+    shape, nsheets, skeep = sj._sheet_shape(who, n, sheet, sizes, orientations)
     keep, faddr = _flat_struct(who, flatten)
-    need = L.sjpeg_hip_sheet_ragged_bytes(fmt, n, frames, C.addressof(st), sj._address(arr), sj._address(oarr))
-    out = sj._made_out(who, planes_per_frame, need, out)
-    per = max(int(sheet.cols) * int(sheet.rows), 1)
-    made = (RaggedFrame * max((n + per - 1) // per, 1))()
-    ns, rfmt = C.c_int(0), C.c_int(-1)
-    engine._chk(L.sjpeg_hip_sheet_ragged_linear_src(engine._h, fmt, n, frames, C.addressof(st), faddr, light, sj._address(arr),
-                                                    sj._address(oarr), out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns),
-                                                    C.byref(rfmt), engine._stream()), "sjpeg_hip_sheet_ragged_linear_src")
-    return int(rfmt.value), sj._frame_views(out, list(made)[:ns.value], rfmt.value), out
+    return engine._make_pictures(who, who, "sheet_ragged", fmt, planes_per_frame, frames, shape, {"flatten": faddr, "light": light}, out, nsheets)
 
 
 def encode_ragged_sheet_linear(engine, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, method=4, flatten=None,
                                light=LINEAR_SRGB, search=None, metadata=None, packed=False):
     """sjpeg_hip_encode_ragged_sheet_linear_src / _sheet_linear_packed_src: Engine.encode_ragged_sheet (packed: its packed
     twin) of the sheets sheet_ragged_linear makes.  Returns (out, sizes, offsets, modes, q, value), one entry per sheet."""
-    import torch
     who = "encode_ragged_sheet_linear"
     light = _light(who, light)
-    L = _lib()
-    ns, call, special = engine._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, int(method), None,
-                                           0x78, 12, 1, search, metadata)
+    ns, call, segments = engine._sheet_call(who, fmt, planes_per_frame, dims, sheet, sizes, orientations, yuv_mode, quant, int(method), None,
+                                            0x78, 12, 1, search, metadata)
     keep, faddr = _flat_struct(who, flatten)
-    special[1:1] = [faddr, light]
-    frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
-    if packed:
-        out, packed_capacity, meta = sj._packed_out(who, ns, planes_per_frame, call.capacities, None, None)
-        engine._chk(L.sjpeg_hip_encode_ragged_sheet_linear_packed_src(
-            engine._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns,
-            meta.data_ptr(), *call.results, engine._stream()), "sjpeg_hip_encode_ragged_sheet_linear_packed_src")
-        return (out, meta[:ns], meta[ns:]) + call.answers()
-    out_stride = (call.capacities[0] + 15) & ~15
-    dev = sj._ragged_device(planes_per_frame)
-    out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
-    sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
-    engine._chk(L.sjpeg_hip_encode_ragged_sheet_linear_src(
-        engine._h, fmt, len(dims), frames, call.params, *special, *call.meta, out.data_ptr(), out_stride, sizes_out.data_ptr(), *call.results,
-        engine._stream()), "sjpeg_hip_encode_ragged_sheet_linear_src")
-    return (out, sizes_out, [s * out_stride for s in range(ns)]) + call.answers()
+    return engine._encode_sheets_shaped(who, "sheet_linear", fmt, planes_per_frame, dims, ns, call, dict(segments, flatten=faddr, light=light), packed)
 
 
 # ---- the picture level: images as resize_images / flatten_images / make_sheets take them

@@ -34,9 +34,7 @@ import numpy as np
 import sjpeg_amd as sj
 import sjpeg_amd.light as li
 import sjpeg_amd.unsharp as un
-from sjpeg_amd import YUV_420, RaggedFrame, SjpegError
-
-_bound = False
+from sjpeg_amd import YUV_420, SjpegError
 
 KSIZE_MAX = 385          # an axis whose window is longer is refused (Lanczos shrinking by more than 64, box by more than 384)
 
@@ -66,67 +64,7 @@ class _ResampleStruct(C.Structure):
     _fields_ = [("filter", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
-def _lib():
-    """the library with the argument types of the entries this module binds: the unsharp ones without `light`, plus
-    (resample, resample_per_frame) in front of the unsharp"""
-    global _bound
-    L = un._lib()
-    if _bound:
-        return L
-    L.sjpeg_hip_resample_ksize.restype = C.c_int
-    L.sjpeg_hip_resample_ksize.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.sjpeg_hip_resample_table.restype = C.c_int
-    L.sjpeg_hip_resample_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_resample_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_resample_ragged_bytes.argtypes = list(L.sjpeg_hip_orient_ragged_bytes.argtypes)
-    two = [C.c_void_p, C.c_int]
-    # (..., flatten, light, sizes, orientations, unsharp, unsharp_per_frame, ...): light goes, resample comes
-    for older, mine, at in (("unsharp_ragged", "resample_ragged", 5), ("encode_ragged_unsharp", "encode_ragged_resampled", 6),
-                            ("encode_ragged_unsharp_packed", "encode_ragged_resampled_packed", 6)):
-        plain = list(getattr(L, f"sjpeg_hip_{older}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_{mine}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + plain[at + 1:at + 3] + two + plain[at + 3:]
-    L.sjpeg_hip_resample_box_ksize.restype = C.c_int
-    L.sjpeg_hip_resample_box_ksize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
-    L.sjpeg_hip_resample_box_table.restype = C.c_int
-    L.sjpeg_hip_resample_box_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.sjpeg_hip_thumbnail_size.restype = C.c_int
-    L.sjpeg_hip_thumbnail_size.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
-    L.sjpeg_hip_fit_crop.restype = C.c_int
-    L.sjpeg_hip_fit_crop.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
-    L.sjpeg_hip_resample_box_decide.restype = C.c_int
-    L.sjpeg_hip_resample_box_decide.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.sjpeg_hip_resample_box_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_resample_box_ragged_bytes.argtypes = list(L.sjpeg_hip_resample_ragged_bytes.argtypes) + two
-    # (..., resample, resample_per_frame, unsharp, ...): box, box_per_frame behind the resample
-    for mine, at in (("resample_ragged", 9), ("encode_ragged_resampled", 10), ("encode_ragged_resampled_packed", 10)):
-        plain = list(getattr(L, f"sjpeg_hip_{mine}_src").argtypes)
-        fn = getattr(L, "sjpeg_hip_" + mine.replace("resample_ragged", "resample_box_ragged").replace("resampled", "resampled_box") + "_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + two + plain[at:]
-    # (..., box, box_per_frame, unsharp, unsharp_per_frame, ...): the filter stands where the unsharp stood
-    for boxed, mine in (("resample_box_ragged", "filter_ragged"), ("encode_ragged_resampled_box", "encode_ragged_filtered"),
-                        ("encode_ragged_resampled_box_packed", "encode_ragged_filtered_packed")):
-        fn = getattr(L, f"sjpeg_hip_{mine}_src")
-        fn.restype, fn.argtypes = C.c_int, list(getattr(L, f"sjpeg_hip_{boxed}_src").argtypes)
-    L.sjpeg_hip_pillow_filter_weights.restype = C.c_int
-    L.sjpeg_hip_pillow_filter_weights.argtypes = [C.c_int, C.c_float] + [C.c_void_p] * 4
-    # (..., filter, filter_per_frame, ...): compose, overlays and places, each with its count, behind the filter
-    six = [C.c_void_p, C.c_int] * 3
-    for filtered, mine, at in (("filter_ragged", "compose_ragged", 13), ("encode_ragged_filtered", "encode_ragged_composed", 14),
-                               ("encode_ragged_filtered_packed", "encode_ragged_composed_packed", 14)):
-        plain = list(getattr(L, f"sjpeg_hip_{filtered}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_{mine}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + six + plain[at:]
-    L.sjpeg_hip_compose_ragged_bytes.restype = C.c_size_t
-    L.sjpeg_hip_compose_ragged_bytes.argtypes = list(L.sjpeg_hip_resample_box_ragged_bytes.argtypes) + two
-    L.sjpeg_hip_contain_size.restype = C.c_int
-    L.sjpeg_hip_contain_size.argtypes = [C.c_int] * 4 + [C.c_void_p]
-    L.sjpeg_hip_pad_place.restype = C.c_int
-    L.sjpeg_hip_pad_place.argtypes = [C.c_int] * 4 + [C.c_double] * 2 + [C.c_void_p]
-    L.sjpeg_hip_compose_sample.restype = C.c_int
-    L.sjpeg_hip_compose_sample.argtypes = [C.c_int] * 6
-    _bound = True
-    return L
+_lib = sj.lib                            # (the one table of sjpeg_amd._binding binds every entry when the library loads)
 
 
 def _last_error():
@@ -583,45 +521,38 @@ def resample_ragged(engine, fmt, planes_per_frame, dims, sizes=None, filter=Filt
     n = len(dims)
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
-    L = _lib()
     rkeep, raddr, rper = _filter_args(who, n, filter)
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
     pkeep, paddr, pper = _post_args(who, n, post, unsharp)
     ukeep, uaddr, uper = un._unsharp_args(who, n, unsharp)
     comp = _compose_args(who, n, compose, dims, sizes, orientations, unsharp)
-    entry = "sjpeg_hip_resample_box_ragged_src"
-    if pkeep is not None or comp.given:
-        if bkeep is None:
-            bkeep, baddr, bper = _whole_box()
-        uaddr, uper, entry = paddr, pper, "sjpeg_hip_filter_ragged_src"
+    if (pkeep is not None or comp.given) and bkeep is None:
+        bkeep, baddr, bper = _whole_box()
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = li._flat_struct(who, flatten)
-    # (a batch the library refuses has need == 0: the call below says why)
-    if comp.given:
-        entry = "sjpeg_hip_compose_ragged_src"
-        need = L.sjpeg_hip_compose_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper, *comp.args[:2])
-        out = sj._made_out(who, planes_per_frame, need, out)
-        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-        engine._chk(getattr(L, entry)(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr, bper, uaddr, uper,
-                                      *comp.args, out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
-                    entry)
-        return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
-    if bkeep is not None:
-        need = L.sjpeg_hip_resample_box_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr), baddr, bper)
-        out = sj._made_out(who, planes_per_frame, need, out)
-        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-        engine._chk(getattr(L, entry)(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, baddr, bper, uaddr, uper,
-                                      out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
-                    entry)
-        return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
-    need = L.sjpeg_hip_resample_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr))
-    out = sj._made_out(who, planes_per_frame, need, out)
-    made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-    engine._chk(L.sjpeg_hip_resample_ragged_src(engine._h, fmt, n, frames, faddr, sj._address(arr), sj._address(oarr), raddr, rper, uaddr, uper,
-                                                out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
-                "sjpeg_hip_resample_ragged_src")
-    return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
+    family, shape, more = _entry(faddr, (raddr, rper), (baddr, bper) if bkeep is not None else None, (uaddr, uper),
+                                 (paddr, pper) if pkeep is not None or comp.given else None, comp)
+    shape.update(sizes=sj._address(arr), orientations=sj._address(oarr))
+    return engine._make_pictures(who, family[0], family[1], fmt, planes_per_frame, frames, shape, more, out)
+
+
+def _entry(faddr, resample, box, unsharp, post, comp):
+    """Which family a call goes through -- the plain resample; with a box (an (address, per-frame flag) pair) the box
+    entries; with post the filter entries, which have it where the others have the unsharp; with a compose the compose
+    entries --: (the stems of its picture-making entry, of the _bytes entry that goes with it and of its encodes, the
+    segments the _bytes entry takes besides sizes and orientations, the other segments)"""
+    shape, more = {}, {"flatten": faddr, "resample": resample}
+    if box is None:
+        return ("resample_ragged", "resample_ragged", "resampled"), shape, dict(more, unsharp=unsharp)
+    shape["box"] = box
+    if post is None:
+        return ("resample_box_ragged", "resample_box_ragged", "resampled_box"), shape, dict(more, unsharp=unsharp)
+    more["filter"] = post
+    if not comp.given:
+        return ("filter_ragged", "resample_box_ragged", "filtered"), shape, more
+    shape["compose"] = comp.args[:2]
+    return ("compose_ragged", "compose_ragged", "composed"), shape, dict(more, overlays=comp.args[2:4], places=comp.args[4:])
 
 
 def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, filter=Filter.LANCZOS,
@@ -631,7 +562,6 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
     entries; post: the _filtered_ ones; compose: the _composed_ ones, the default capacities the canvases' bounds).  Frame k's bytes are those Engine.encode_ragged_full makes of the uint8 picture
     resample_ragged returns.  Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_resampled"
-    _lib()
     n = len(dims)
     rkeep, raddr, rper = _filter_args(who, n, filter)
     pkeep, paddr, pper = _post_args(who, n, post, unsharp)
@@ -647,19 +577,10 @@ def encode_ragged_resampled(engine, fmt, planes_per_frame, dims, sizes, orientat
     bkeep, baddr, bper = _box_args(who, n, source_box, reducing_gap)
     if (pkeep is not None or comp.given) and bkeep is None:
         bkeep, baddr, bper = _whole_box()
-    special = (faddr, call.sizes, call.orientations, raddr, rper, uaddr, uper)
-    stem = "sjpeg_hip_encode_ragged_resampled"
-    if bkeep is not None:
-        special, stem = special[:5] + (baddr, bper) + special[5:], stem + "_box"
-    if pkeep is not None or comp.given:
-        special, stem = special[:7] + (paddr, pper), "sjpeg_hip_encode_ragged_filtered"
-    if comp.given:
-        special, stem = special + comp.args, "sjpeg_hip_encode_ragged_composed"
-    if packed:
-        out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
-        return sj._split_meta(n, *engine._packed(stem + "_packed_src", fmt, planes_per_frame, dims, call, special, out, packed_capacity, meta))
-    frames, out, sizes_out, offsets = sj._ragged_frames(planes_per_frame, dims, call.capacities, None, None, None)
-    return engine._unpacked(stem + "_src", fmt, frames, call, special, out, sizes_out, offsets)
+    family, shape, more = _entry(faddr, (raddr, rper), (baddr, bper) if bkeep is not None else None, (uaddr, uper),
+                                 (paddr, pper) if pkeep is not None or comp.given else None, comp)
+    return engine._encode_shaped(who, family[2], fmt, planes_per_frame, dims, call,
+                                 dict(shape, **more, sizes=call.sizes, orientations=call.orientations), packed)
 
 
 # ---- the picture level: images as resize_images / flatten_images take them

@@ -12,10 +12,7 @@ import numpy as np
 import sjpeg_amd as sj
 import sjpeg_amd.light as li
 import sjpeg_amd.video as vi
-from sjpeg_amd import YUV_420, YUV_444, RaggedFrame, SjpegError
-
-_bound = False
-
+from sjpeg_amd import YUV_420, YUV_444, SjpegError
 
 class _UnsharpStruct(C.Structure):
     """struct sjpeg_hip_unsharp"""
@@ -45,26 +42,7 @@ class Unsharp:
         return _UnsharpStruct(self.amount, self.threshold)
 
 
-def _lib():
-    """the library with the argument types of the entries this module binds: the linear and the yuv16 ones plus
-    (unsharp, unsharp_per_frame)"""
-    global _bound
-    li._lib()
-    L = vi._lib()
-    if _bound:
-        return L
-    L.sjpeg_hip_unsharp_sample.restype = C.c_int
-    L.sjpeg_hip_unsharp_sample.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    two = [C.c_void_p, C.c_int]
-    for older, mine, at in (("linear_ragged", "unsharp_ragged", 8), ("encode_ragged_linear", "encode_ragged_unsharp", 9),
-                            ("encode_ragged_linear_packed", "encode_ragged_unsharp_packed", 9),
-                            ("convert_ragged_yuv16", "unsharp_ragged_yuv", 9), ("encode_ragged_yuv16", "encode_ragged_yuv_unsharp", 10),
-                            ("encode_ragged_yuv16_packed", "encode_ragged_yuv_unsharp_packed", 10)):
-        plain = list(getattr(L, f"sjpeg_hip_{older}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_{mine}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + two + plain[at:]
-    _bound = True
-    return L
+_lib = sj.lib                            # (the one table of sjpeg_amd._binding binds every entry when the library loads)
 
 
 def _unsharp_args(who, n, unsharp):
@@ -117,19 +95,12 @@ def unsharp_ragged(engine, fmt, planes_per_frame, dims, sizes=None, orientations
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
     light = li._light(who, light)
-    L = _lib()
     ukeep, uaddr, per_frame = _unsharp_args(who, n, unsharp)
     frames, _, _, _ = sj._ragged_frames(planes_per_frame, dims, None, None, None, None)
     arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
     keep, faddr = li._flat_struct(who, flatten)
-    # (a batch the library refuses has need == 0: the call below says why)
-    need = L.sjpeg_hip_orient_ragged_bytes(fmt, n, frames, sj._address(arr), sj._address(oarr))
-    out = sj._made_out(who, planes_per_frame, need, out)
-    made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-    engine._chk(L.sjpeg_hip_unsharp_ragged_src(engine._h, fmt, n, frames, faddr, light, sj._address(arr), sj._address(oarr), uaddr, per_frame,
-                                               out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), engine._stream()),
-                "sjpeg_hip_unsharp_ragged_src")
-    return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
+    return engine._make_pictures(who, who, "orient_ragged", fmt, planes_per_frame, frames, {"sizes": sj._address(arr), "orientations": sj._address(oarr)},
+                                 {"flatten": faddr, "light": light, "unsharp": (uaddr, per_frame)}, out)
 
 
 def encode_ragged_unsharp(engine, fmt, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method=4, flatten=None, light=li.CODED,
@@ -140,19 +111,14 @@ def encode_ragged_unsharp(engine, fmt, planes_per_frame, dims, sizes, orientatio
     Returns (out, sizes, offsets, modes, q, value)."""
     who = "encode_ragged_unsharp"
     light = li._light(who, light)
-    _lib()
     n = len(dims)
     ukeep, uaddr, per_frame = _unsharp_args(who, n, unsharp)
     call = engine._oriented_call(who, planes_per_frame, dims, sizes, orientations, yuv_mode, quant, method, min_quant, q_bias, dmax_luma,
                                  dmax_chroma, search, None, metadata)
     keep, faddr = li._flat_struct(who, flatten)
-    special = (faddr, light, call.sizes, call.orientations, uaddr, per_frame)
-    if packed:
-        out, packed_capacity, meta = sj._packed_out(who, n, planes_per_frame, call.capacities, None, None)
-        return sj._split_meta(n, *engine._packed("sjpeg_hip_encode_ragged_unsharp_packed_src", fmt, planes_per_frame, dims, call, special, out,
-                                                 packed_capacity, meta))
-    frames, out, sizes_out, offsets = sj._ragged_frames(planes_per_frame, dims, call.capacities, None, None, None)
-    return engine._unpacked("sjpeg_hip_encode_ragged_unsharp_src", fmt, frames, call, special, out, sizes_out, offsets)
+    return engine._encode_shaped(who, "unsharp", fmt, planes_per_frame, dims, call,
+                                 {"flatten": faddr, "light": light, "sizes": call.sizes, "orientations": call.orientations,
+                                  "unsharp": (uaddr, per_frame)}, packed)
 
 
 # ---- the picture level: images as resize_images / flatten_images take them
@@ -219,7 +185,6 @@ def unsharp_video_frames(frames, fmt=sj.SRC_NV12, colour=vi.VideoColour(), sizes
     makes, Y sharpened by one more launch, U and V as they were.  Returns (out_fmt, pictures, buf) as they do."""
     import torch
     who = "unsharp_video_frames"
-    _lib()
     planes, dims, dev, dkeep, deep = vi._read_frames(who, frames, fmt, depth)
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
@@ -229,17 +194,12 @@ def unsharp_video_frames(frames, fmt=sj.SRC_NV12, colour=vi.VideoColour(), sizes
     keep, caddr, cper = vi._colour_args(who, n, colour)
     ukeep, uaddr, uper = _unsharp_args(who, n, unsharp)
     eng = sj._engine_for(engine, dev)
-    L = _lib()
     with torch.cuda.device(dev):
         cframes, _, _, _ = sj._ragged_frames(planes, dims, None, None, None, None)
         arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
-        need = L.sjpeg_hip_resize_ragged_yuv_bytes(fmt, n, cframes, sj._address(arr), sj._address(oarr))
-        out = sj._made_out(who, planes, need, out)
-        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-        eng._chk(L.sjpeg_hip_unsharp_ragged_yuv_src(eng._h, fmt, n, cframes, sj._address(arr), sj._address(oarr), caddr, cper,
-                                                    deep[0] if deep else None, uaddr, uper, out.data_ptr(), int(out.numel()) if need else 0,
-                                                    made, C.byref(rfmt), eng._stream()), "sjpeg_hip_unsharp_ragged_yuv_src")
-    return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
+        return eng._make_pictures(who, "unsharp_ragged_yuv", "resize_ragged_yuv", fmt, planes, cframes,
+                                  {"sizes": sj._address(arr), "orientations": sj._address(oarr)},
+                                  {"colour": (caddr, cper), "depth": deep.get("depth"), "unsharp": (uaddr, uper)}, out)
 
 
 def encode_unsharp_video_frames(frames, fmt=sj.SRC_NV12, colour=vi.VideoColour(), sizes=None, box=None, orientations=None, unsharp=Unsharp(),
@@ -250,7 +210,6 @@ def encode_unsharp_video_frames(frames, fmt=sj.SRC_NV12, colour=vi.VideoColour()
     encode_yuv_frames makes of the planes unsharp_video_frames returns.  Returns the JPEGs (list of bytes)."""
     import torch
     who = "encode_unsharp_video_frames"
-    _lib()
     planes, dims, dev, dkeep, deep = vi._read_frames(who, frames, fmt, depth)
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
@@ -264,17 +223,11 @@ def encode_unsharp_video_frames(frames, fmt=sj.SRC_NV12, colour=vi.VideoColour()
         raise SjpegError(f"{who}: one quality per frame")
     yuv_mode = YUV_444 if fmt == sj.SRC_YUV444 else YUV_420
     eng = sj._engine_for(engine, dev)
-    stem = "sjpeg_hip_encode_ragged_yuv_unsharp"
     with torch.cuda.device(dev):
         call = eng._oriented_call(who, planes, dims, sizes, orientations, yuv_mode, sj._quality_quant(qs), method, None, 0x78, 12, 1,
                                   search, None, metadata)
-        special = (call.sizes, call.orientations, caddr, cper, deep[0] if deep else None, uaddr, uper)
-        if packed:
-            out, packed_capacity, meta = sj._packed_out(who, n, planes, call.capacities, None, None)
-            eng._packed(stem + "_packed_src", fmt, planes, dims, call, special, out, packed_capacity, meta)
-            eng.wait()
-            return sj._fetch_packed(out, meta[:n], meta[n:], n, "frame")
-        cframes, out, sizes_out, offsets = sj._ragged_frames(planes, dims, call.capacities, None, None, None)
-        out, sz, offs = eng._unpacked(stem + "_src", fmt, cframes, call, special, out, sizes_out, offsets)[:3]
+        res = eng._encode_shaped(who, "yuv_unsharp", fmt, planes, dims, call,
+                                 {"sizes": call.sizes, "orientations": call.orientations, "colour": (caddr, cper), "depth": deep.get("depth"),
+                                  "unsharp": (uaddr, uper)}, packed)
         eng.wait()                               # (pipelined mode: the output is complete after this)
-        return sj._fetch_ragged(out, sz, offs)
+        return sj._fetch_packed(res[0], res[1], res[2], n, "frame") if packed else sj._fetch_ragged(res[0], res[1], res[2])

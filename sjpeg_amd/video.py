@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 import sjpeg_amd as sj
-from sjpeg_amd import SRC_NV12, SRC_YUV444, YUV_420, YUV_444, RaggedFrame, SjpegError, lib
+from sjpeg_amd import SRC_NV12, SRC_YUV444, YUV_420, YUV_444, SjpegError, lib
 
 MATRIX_BT601, MATRIX_BT709 = 0, 1        # SJPEG_HIP_MATRIX_*
 RANGE_FULL, RANGE_LIMITED = 0, 1         # SJPEG_HIP_RANGE_*
@@ -93,44 +93,7 @@ class VideoDepth:
 VideoDepth.P010, VideoDepth.P016 = VideoDepth(10, "msb"), VideoDepth(16, "msb")
 VideoDepth.YUV10, VideoDepth.YUV12 = VideoDepth(10, "lsb"), VideoDepth(12, "lsb")
 
-_bound = False
-
-
-def _lib():
-    """the library with the argument types of the entries this module binds"""
-    global _bound
-    L = lib()
-    if _bound:
-        return L
-    L.sjpeg_hip_yuv_colour_samples.restype = C.c_int
-    L.sjpeg_hip_yuv_colour_samples.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    colour = [C.c_void_p, C.c_int]
-    plain = list(L.sjpeg_hip_resize_ragged_yuv_src.argtypes)            # (..., sizes, orientations, d_out, ...)
-    L.sjpeg_hip_convert_ragged_yuv_src.restype = C.c_int
-    L.sjpeg_hip_convert_ragged_yuv_src.argtypes = plain[:6] + colour + plain[6:]
-    plain = list(L.sjpeg_hip_sheet_ragged_src.argtypes)                 # (..., sheet, sizes, orientations, d_out, ...)
-    L.sjpeg_hip_sheet_ragged_yuv_colour_src.restype = C.c_int
-    L.sjpeg_hip_sheet_ragged_yuv_colour_src.argtypes = plain[:7] + colour + plain[7:]
-    for packed in ("", "_packed"):
-        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_yuv_resized{packed}_src").argtypes)    # (..., params, sizes, orientations, meta, ...)
-        fn = getattr(L, f"sjpeg_hip_encode_ragged_yuv_converted{packed}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:7] + colour + plain[7:]
-        plain = list(getattr(L, f"sjpeg_hip_encode_ragged_sheet{packed}_src").argtypes)          # (..., params, sheet, sizes, orientations, meta, ...)
-        fn = getattr(L, f"sjpeg_hip_encode_ragged_sheet_yuv_colour{packed}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:8] + colour + plain[8:]
-    # the deep entries: their colour counterparts with the depth behind the colour
-    L.sjpeg_hip_yuv16_samples.restype = C.c_int
-    L.sjpeg_hip_yuv16_samples.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    for stem, deep, at in (("convert_ragged_yuv", "convert_ragged_yuv16", 8), ("sheet_ragged_yuv_colour", "sheet_ragged_yuv16", 9),
-                           ("encode_ragged_yuv_converted", "encode_ragged_yuv16", 9),
-                           ("encode_ragged_yuv_converted_packed", "encode_ragged_yuv16_packed", 9),
-                           ("encode_ragged_sheet_yuv_colour", "encode_ragged_sheet_yuv16", 10),
-                           ("encode_ragged_sheet_yuv_colour_packed", "encode_ragged_sheet_yuv16_packed", 10)):
-        plain = list(getattr(L, f"sjpeg_hip_{stem}_src").argtypes)
-        fn = getattr(L, f"sjpeg_hip_{deep}_src")
-        fn.restype, fn.argtypes = C.c_int, plain[:at] + [C.c_void_p] + plain[at:]
-    _bound = True
-    return L
+_lib = lib                               # (the one table of sjpeg_amd._binding binds every entry when the library loads)
 
 
 def _colour_args(who, n, colour):
@@ -205,14 +168,14 @@ def _deep_frames(who, frames, fmt):
 
 
 def _read_frames(who, frames, fmt, depth):
-    """(planes, dims, device, the depth's struct or None, what stands behind the colour in the C call) of a call's frames:
-    bytes (depth None) or 16-bit samples"""
+    """(planes, dims, device, the depth's struct or None, the `depth` segment of the C call where it has one) of a call's
+    frames: bytes (depth None) or 16-bit samples"""
     if depth is None:
-        return sj._yuv_frames(who, frames, fmt) + (None, [])
+        return sj._yuv_frames(who, frames, fmt) + (None, {})
     if not isinstance(depth, VideoDepth):
         raise SjpegError(f"{who}: depth {depth!r} is not a VideoDepth")
     st = depth._struct()
-    return _deep_frames(who, frames, fmt) + (st, [C.addressof(st)])
+    return _deep_frames(who, frames, fmt) + (st, {"depth": C.addressof(st)})
 
 
 def yuv16_samples(words, depth=VideoDepth.P010):
@@ -252,7 +215,7 @@ def convert_deep_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, 
 def _convert(who, frames, fmt, colour, sizes, box, orientations, engine, out, depth):
     import torch
     planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
-    symbol = "sjpeg_hip_convert_ragged_yuv16_src" if deep else "sjpeg_hip_convert_ragged_yuv_src"
+    stem = "convert_ragged_yuv16" if deep else "convert_ragged_yuv"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     sizes = _size_list(who, n, dims, sizes, box, orientations)
@@ -260,17 +223,11 @@ def _convert(who, frames, fmt, colour, sizes, box, orientations, engine, out, de
         raise SjpegError(f"{who}: one size per frame")
     keep, caddr, per_frame = _colour_args(who, n, colour)
     eng = sj._engine_for(engine, dev)
-    L = _lib()
     with torch.cuda.device(dev):
         cframes, _, _, _ = sj._ragged_frames(planes, dims, None, None, None, None)
         arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
-        need = L.sjpeg_hip_resize_ragged_yuv_bytes(fmt, n, cframes, sj._address(arr), sj._address(oarr))
-        out = sj._made_out(who, planes, need, out)
-        made, rfmt = (RaggedFrame * n)(), C.c_int(-1)
-        # (a batch the library refuses has need == 0: the call below says why)
-        eng._chk(getattr(L, symbol)(eng._h, fmt, n, cframes, sj._address(arr), sj._address(oarr), caddr, per_frame, *deep,
-                                    out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(rfmt), eng._stream()), symbol)
-    return int(rfmt.value), sj._frame_views(out, made, rfmt.value), out
+        return eng._make_pictures(who, stem, "resize_ragged_yuv", fmt, planes, cframes, {"sizes": sj._address(arr), "orientations": sj._address(oarr)},
+                                  dict(deep, colour=(caddr, per_frame)), out)
 
 
 def make_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), sizes=None, orientations=None, engine=None, out=None):
@@ -289,28 +246,17 @@ def make_deep_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(
 def _make_sheets(who, frames, fmt, sheet, colour, sizes, orientations, engine, out, depth):
     import torch
     planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
-    symbol = "sjpeg_hip_sheet_ragged_yuv16_src" if deep else "sjpeg_hip_sheet_ragged_yuv_colour_src"
+    stem = "sheet_ragged_yuv16" if deep else "sheet_ragged_yuv_colour"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     if sizes is not None and len(sizes) != n:
         raise SjpegError(f"{who}: one size per frame")
     keep, caddr, per_frame = _colour_args(who, n, colour)
     eng = sj._engine_for(engine, dev)
-    L = _lib()
     with torch.cuda.device(dev):
         cframes, _, _, _ = sj._ragged_frames(planes, dims, None, None, None, None)
-        st = sj._sheet_struct(who, sheet)
-        arr, oarr = sj._shape_arrays(who, n, sizes, orientations)
-        need = L.sjpeg_hip_sheet_ragged_bytes(fmt, n, cframes, C.addressof(st), sj._address(arr), sj._address(oarr))
-        out = sj._made_out(who, planes, need, out)
-        per = max(int(sheet.cols) * int(sheet.rows), 1)
-        made = (RaggedFrame * max((n + per - 1) // per, 1))()
-        ns, rfmt = C.c_int(0), C.c_int(-1)
-        # (a batch the library refuses has need == 0: the call below says why)
-        eng._chk(getattr(L, symbol)(eng._h, fmt, n, cframes, C.addressof(st), sj._address(arr), sj._address(oarr), caddr, per_frame, *deep,
-                                    out.data_ptr(), int(out.numel()) if need else 0, made, C.byref(ns), C.byref(rfmt), eng._stream()),
-                 symbol)
-    return int(rfmt.value), sj._frame_views(out, list(made)[:ns.value], rfmt.value), out
+        shape, nsheets, skeep = sj._sheet_shape(who, n, sheet, sizes, orientations)
+        return eng._make_pictures(who, stem, "sheet_ragged", fmt, planes, cframes, shape, dict(deep, colour=(caddr, per_frame)), out, nsheets)
 
 
 def encode_video_frames(frames, fmt=SRC_NV12, colour=VideoColour(), sizes=None, box=None, orientations=None, quality=75.0,
@@ -338,7 +284,7 @@ def _encode_frames(who, frames, fmt, colour, sizes, box, orientations, quality, 
                    depth):
     import torch
     planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
-    stem = "sjpeg_hip_encode_ragged_yuv16" if deep else "sjpeg_hip_encode_ragged_yuv_converted"
+    stem = "yuv16" if deep else "yuv_converted"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     sizes = _size_list(who, n, dims, sizes, box, orientations)
@@ -350,20 +296,13 @@ def _encode_frames(who, frames, fmt, colour, sizes, box, orientations, quality, 
         raise SjpegError(f"{who}: one quality per frame")
     yuv_mode = YUV_444 if fmt == SRC_YUV444 else YUV_420
     eng = sj._engine_for(engine, dev)
-    L = _lib()
     with torch.cuda.device(dev):
         call = eng._oriented_call(who, planes, dims, sizes, orientations, yuv_mode, sj._quality_quant(qs), method, None, 0x78, 12, 1,
                                   search, None, metadata)
-        special = (call.sizes, call.orientations, caddr, per_frame, *deep)
-        if packed:
-            out, packed_capacity, meta = sj._packed_out(who, n, planes, call.capacities, None, None)
-            eng._packed(stem + "_packed_src", fmt, planes, dims, call, special, out, packed_capacity, meta)
-            eng.wait()
-            return sj._fetch_packed(out, meta[:n], meta[n:], n, "frame")
-        cframes, out, sizes_out, offsets = sj._ragged_frames(planes, dims, call.capacities, None, None, None)
-        out, sz, offs = eng._unpacked(stem + "_src", fmt, cframes, call, special, out, sizes_out, offsets)[:3]
+        res = eng._encode_shaped(who, stem, fmt, planes, dims, call,
+                                 dict(deep, sizes=call.sizes, orientations=call.orientations, colour=(caddr, per_frame)), packed)
         eng.wait()                               # (pipelined mode: the output is complete after this)
-        return sj._fetch_ragged(out, sz, offs)
+        return sj._fetch_packed(res[0], res[1], res[2], n, "frame") if packed else sj._fetch_ragged(res[0], res[1], res[2])
 
 
 def encode_video_sheets(frames, fmt=SRC_NV12, sheet=None, colour=VideoColour(), sizes=None, orientations=None, quality=75.0,
@@ -387,7 +326,7 @@ def _encode_sheets(who, frames, fmt, sheet, colour, sizes, orientations, quality
                    depth):
     import torch
     planes, dims, dev, dkeep, deep = _read_frames(who, frames, fmt, depth)
-    stem = "sjpeg_hip_encode_ragged_sheet_yuv16" if deep else "sjpeg_hip_encode_ragged_sheet_yuv_colour"
+    stem = "sheet_yuv16" if deep else "sheet_yuv_colour"
     n = len(dims)
     orientations = sj._orientation_list(who, n, orientations)
     keep, caddr, per_frame = _colour_args(who, n, colour)
@@ -400,24 +339,10 @@ def _encode_sheets(who, frames, fmt, sheet, colour, sizes, orientations, quality
     sj._one_target(who, target_size, target_psnr)
     search = sj._target_search(who, "sheet", ns, target_size, target_psnr)
     yuv_mode = YUV_444 if fmt == SRC_YUV444 else YUV_420
-    L = _lib()
     with torch.cuda.device(dev):
-        ns, call, special = eng._sheet_call(who, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, sj._quality_quant(qs), int(method),
-                                            None, 0x78, 12, 1, search, metadata)
-        special += [caddr, per_frame, *deep]
-        cframes, _, _, _ = sj._ragged_frames(planes, dims, None, None, None, None)
-        if packed:
-            out, packed_capacity, meta = sj._packed_out(who, ns, planes, call.capacities, None, None)
-            eng._chk(getattr(L, stem + "_packed_src")(
-                eng._h, fmt, n, cframes, call.params, *special, *call.meta, out.data_ptr(), packed_capacity, meta.data_ptr() + 8 * ns,
-                meta.data_ptr(), *call.results, eng._stream()), stem + "_packed_src")
-            eng.wait()
-            return sj._fetch_packed(out, meta[:ns], meta[ns:], ns, "sheet"), places
-        out_stride = (call.capacities[0] + 15) & ~15
-        out = torch.empty(max(out_stride * ns, 1), dtype=torch.uint8, device=dev)
-        sizes_out = torch.zeros(ns, dtype=torch.int64, device=dev)
-        eng._chk(getattr(L, stem + "_src")(
-            eng._h, fmt, n, cframes, call.params, *special, *call.meta, out.data_ptr(), out_stride, sizes_out.data_ptr(), *call.results,
-            eng._stream()), stem + "_src")
+        ns, call, segments = eng._sheet_call(who, fmt, planes, dims, sheet, sizes, orientations, yuv_mode, sj._quality_quant(qs), int(method),
+                                             None, 0x78, 12, 1, search, metadata)
+        res = eng._encode_sheets_shaped(who, stem, fmt, planes, dims, ns, call, dict(segments, **deep, colour=(caddr, per_frame)), packed)
         eng.wait()                               # (pipelined mode: the output is complete after this)
-        return sj._fetch_ragged(out, sizes_out, [s * out_stride for s in range(ns)]), places
+        jpegs = sj._fetch_packed(res[0], res[1], res[2], ns, "sheet") if packed else sj._fetch_ragged(res[0], res[1], res[2])
+    return jpegs, places
