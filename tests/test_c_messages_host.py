@@ -1,8 +1,8 @@
 """What the shaped ragged entries of the C layer answer to the calls they refuse on the host, without a GPU: the calls of
-tests/golden/make_c_messages.py (every fault of each of the 25 entries alone, every pair of faults one call can hold,
+tests/golden/make_c_messages.py (every fault of each of the 62 entries alone, every pair of faults one call can hold,
 each on every route of its entry) replayed on this build.  Return code and sjpeg_hip_last_error() must be those recorded
-in tests/golden/c_messages.json with the library as it was before the entries were written against one call
-description (sjpeg_amd/csrc/ragged_shaped.cc), byte for byte: there is no list of excepted cases.  Every call is one
+in tests/golden/c_messages.json with the library of the commit before each change to the entries
+(sjpeg_amd/csrc/ragged_shaped.cc), byte for byte: there is no list of excepted cases.  Every call is one
 that is refused before the engine is read -- the generator's docstring says how that is kept so."""
 import importlib.util
 import json
@@ -20,8 +20,13 @@ with open(os.path.join(GOLDEN, "c_messages.json")) as _f:
 
 
 def test_every_entry_is_recorded_and_refused():
-    assert list(RECORDED["cases"]) == list(gen.ENTRIES) and len(gen.ENTRIES) == 25
-    assert all(rc != 0 for rc, _ in gen.recorded_answers(RECORDED))
+    assert list(RECORDED["cases"]) == list(gen.ENTRIES) and len(gen.ENTRIES) == 62
+    # (a refusal: an error code -- or the 0 bytes of sjpeg_hip_compose_ragged_bytes, whose rows alone hold such answers)
+    answers = gen.recorded_answers(RECORDED)
+    for entry, row in RECORDED["cases"].items():
+        labels = [label for label, _ in gen.cases(entry)]
+        codes = {answers[i][0] for i in gen.from_numbers(labels, gen.expand(row["answers"]))}
+        assert codes == ({0} if entry == gen.BYTES_ENTRY else {gen.EINVAL}), entry
 
 
 @pytest.mark.parametrize("entry", list(gen.ENTRIES))

@@ -1,12 +1,18 @@
-"""The shaped ragged entries of the C layer called directly through ctypes: for each of the seven families (reduced,
-resized, oriented, flattened, YUV resized, sheets, flattened sheets) and each route of it, the fused encode entry must
+"""The shaped ragged entries of the C layer called directly through ctypes: for each of the nineteen families (reduced,
+resized, oriented, flattened, YUV resized, sheets, flattened sheets; video colour, 16-bit planes and linear light with
+their sheets, unsharp on either kind of format, the two resample families, Pillow's filters, compose) and each route of
+it, the fused encode entry must
 make byte for byte what the two-step call makes -- the family's SHAPE entry into a caller's buffer, then
 sjpeg_hip_encode_ragged_full_meta_src (packed: _full_meta_packed_src) on the frames it reports.  Compared: the streams,
 sizes, offsets, modes, q_out and value_out, unpacked and packed.
 
 The batch is three pictures of odd, unequal sizes (33 x 17, 16 x 16, 8 x 50: the smallest at which a wrong frame count,
 base, stride or sink shows); the shapes factor 2, a fit into 20 x 11, orientation 6 and a 2 x 2 sheet of 16 x 16 cells
-(three pictures leave a cell empty); RGBA for the flattened entries, NV12 for the YUV ones.  What is coded first (picture
+(three pictures leave a cell empty); RGBA for the flattened entries, NV12 for the YUV ones, the same planes as 16-bit
+words with the byte six bits up (P010) where a depth is given.  The resample families make 20 x 11, 16 x 16 and 8 x 20
+from source boxes cut one pixel in on each side, the first turned by orientation 6; the filter is a Gaussian blur of
+radius 1, the canvas 24 x 24 with the picture at (2, 3) under one overlay placed from the bottom-right corner.  What is
+coded first (picture
 0, or the one sheet) has a size search of four passes, so that q_out and value_out carry something; the metadata is
 per frame.  A route that an encode entry passes through (factors NULL or all 1, sizes NULL or the frames' own) is stated
 to the shape entry by its explicit equivalent where that entry refuses the NULL."""
@@ -19,6 +25,7 @@ import torch
 
 import sjpeg_amd as sj
 from oracle import synth
+from sjpeg_amd import resample, unsharp, video
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +65,16 @@ def pictures():
         frames[k].plane[0], frames[k].row_stride[0] = y.data_ptr(), w
         frames[k].plane[1], frames[k].row_stride[1] = uv.data_ptr(), 2 * cw
     out[sj.SRC_NV12] = (dev, frames)
+    # ... and the same planes as 16-bit words, the byte six bits up: strides in bytes
+    deep, frames16 = [(p.to(torch.int16) << 6).contiguous() for p in dev], (sj.RaggedFrame * N)()
+    for k, (w, h) in enumerate(DIMS):
+        frames16[k].width, frames16[k].height = w, h
+        for i in range(2):
+            frames16[k].plane[i], frames16[k].row_stride[i] = deep[2 * k + i].data_ptr(), 2 * frames[k].row_stride[i]
+    out[P010] = (deep, frames16)
+    logo = torch.from_numpy(np.ascontiguousarray(synth.g_noise(4, 4, 99))).cuda()
+    logo = torch.cat([logo, torch.full((4, 4, 1), 160, dtype=torch.uint8, device="cuda")], dim=2).contiguous()
+    out["logo"] = logo
     torch.cuda.synchronize()
     return out
 
@@ -98,8 +115,79 @@ FAMILIES = {
     "sheet_flat": ("sjpeg_hip_sheet_ragged_flat_src", sj.SRC_RGBA, ("sheet", "flatten", "sizes", "orientations"),
                    {"flatten": FLATTEN, "sizes": SHEET_SIZES, "orientations": ORIENTS}),
 }
+# ... and the twelve newer families.  Their own arguments are the axes; sizes and orientations are one axis of two
+# values (both NULL, or SIZES' fit and orientation 6) where a route can end in the _full_meta_ entries, else the second;
+# the resample families have their own sizes, which may change a picture's proportions
+P010 = "NV12 in 16-bit words"                    # (a key of `pictures`: the format is NV12, the depth says the rest)
+SHAPED = {"p-": (None, None), "p<": (SIZES["s<"], ORIENTS["o6"])}
+RESAMPLED = {"p<": ([[20, 11], [16, 16], [8, 20]], ORIENTS["o6"])}
+UPRIGHT = [[11, 20], [16, 16], [8, 20]]          # (what RESAMPLED makes)
+IN_CELL = {"p<": (SHEET_SIZES["s<"], ORIENTS["o6"])}
+COLOUR = {"c-": None, "c=": [(0, 0)] * N, "c7": [(1, 1), (0, 0), (1, 0)]}                   # (matrix, range)
+DEPTH = {"d-": None, "d+": (2, 6)}                                                           # (bytes, shift)
+LIGHT = {"l0": 0, "l1": 1}
+UNSHARP = {"u-": None, "u0": [(0, 0)] * N, "u+": [(128, 2), (0, 0), (64, 0)]}                # (amount, threshold)
+FILTER = {"k-": None, "k0": [(0, 0.0)] * N, "kg": [(2, 1.0), (0, 0.0), (2, 1.0)]}            # (kind, radius)
+COMPOSE = {"x-": None, "x=": [(w, h, 0, 0, 0) for w, h in UPRIGHT], "x+": [(24, 24, 2, 3, 1)] * N}     # (canvas, px, py, nplaces)
+_YUV, _LIN, _RES = ("sizes", "orientations", "colour"), ("flatten", "light", "sizes", "orientations"), ("flatten", "sizes", "orientations", "resample")
+FAMILIES.update({
+    "yuv_converted": ("sjpeg_hip_convert_ragged_yuv_src", sj.SRC_NV12, _YUV, {"shape": SHAPED, "colour": COLOUR}),
+    "sheet_yuv_colour": ("sjpeg_hip_sheet_ragged_yuv_colour_src", sj.SRC_NV12, ("sheet",) + _YUV, {"shape": IN_CELL, "colour": COLOUR}),
+    "yuv16": ("sjpeg_hip_convert_ragged_yuv16_src", sj.SRC_NV12, _YUV + ("depth",), {"shape": SHAPED, "colour": COLOUR, "depth": {"d+": (2, 6)}}),
+    "sheet_yuv16": ("sjpeg_hip_sheet_ragged_yuv16_src", sj.SRC_NV12, ("sheet",) + _YUV + ("depth",),
+                    {"shape": IN_CELL, "colour": COLOUR, "depth": {"d+": (2, 6)}}),
+    "linear": ("sjpeg_hip_linear_ragged_src", sj.SRC_RGBA, _LIN, {"shape": SHAPED, "flatten": FLATTEN, "light": LIGHT}),
+    "sheet_linear": ("sjpeg_hip_sheet_ragged_linear_src", sj.SRC_RGBA, ("sheet",) + _LIN, {"shape": IN_CELL, "flatten": FLATTEN, "light": LIGHT}),
+    "unsharp": ("sjpeg_hip_unsharp_ragged_src", sj.SRC_RGBA, _LIN + ("unsharp",),
+                {"shape": SHAPED, "flatten": FLATTEN, "light": LIGHT, "unsharp": UNSHARP}),
+    "yuv_unsharp": ("sjpeg_hip_unsharp_ragged_yuv_src", sj.SRC_NV12, _YUV + ("depth", "unsharp"),
+                    {"shape": SHAPED, "colour": COLOUR, "depth": DEPTH, "unsharp": UNSHARP}),
+    "resampled": ("sjpeg_hip_resample_ragged_src", sj.SRC_RGBA, _RES + ("unsharp",), {"shape": RESAMPLED, "flatten": FLATTEN, "unsharp": UNSHARP}),
+    "resampled_box": ("sjpeg_hip_resample_box_ragged_src", sj.SRC_RGBA, _RES + ("box", "unsharp"),
+                      {"shape": RESAMPLED, "flatten": FLATTEN, "unsharp": UNSHARP}),
+    "filtered": ("sjpeg_hip_filter_ragged_src", sj.SRC_RGBA, _RES + ("box", "filter"), {"shape": RESAMPLED, "flatten": FLATTEN, "filter": FILTER}),
+    "composed": ("sjpeg_hip_compose_ragged_src", sj.SRC_RGBA, _RES + ("box", "filter", "compose", "overlays", "places"),
+                 {"shape": RESAMPLED, "flatten": FLATTEN, "filter": FILTER, "compose": COMPOSE}),
+})
+SHEET_FAMILIES = ("sheet", "sheet_flat", "sheet_yuv_colour", "sheet_yuv16", "sheet_linear")
 # (no flatten: the route of the entry without one, so the two-step call starts with that entry's shape entry)
 UNFLATTENED = {"flattened": "sjpeg_hip_orient_ragged_src", "sheet_flat": "sjpeg_hip_sheet_ragged_src"}
+
+
+def _structs(cls, rows, write):
+    arr = (cls * len(rows))()
+    for st, row in zip(arr, rows):
+        write(st, row)
+    return arr
+
+
+def _newer_args(route, logo):
+    """name -> the C values of the newer families' segments on a route, and what keeps them alive"""
+    def pair(arr, second=1):
+        return (C.addressof(arr), second) if arr is not None else (None, 0)
+
+    def fill(cls, rows, fields):
+        return None if rows is None else _structs(cls, rows, lambda st, row: [setattr(st, f, v) for f, v in zip(fields, row)])
+
+    def filt(st, row):
+        st.kind, st.radius_x, st.radius_y = row[0], row[1], row[1]
+
+    colour = fill(video._ColourStruct, route.get("colour"), ("matrix", "range"))
+    depth = video._DepthStruct(*route["depth"]) if route.get("depth") else None
+    sharp = fill(unsharp._UnsharpStruct, route.get("unsharp"), ("amount", "threshold"))
+    lanczos = resample._ResampleStruct(4)
+    boxes = _structs(resample._BoxStruct, [(1.0, 1.0, w - 1.0, h - 1.0) for w, h in DIMS], lambda st, row: st.box.__setitem__(slice(0, 4), row))
+    filters = None if route.get("filter") is None else _structs(resample._FilterStruct, route["filter"], filt)
+    compose = fill(resample._ComposeStruct, route.get("compose"), ("canvas_width", "canvas_height", "px", "py", "nplaces"))
+    placed = compose is not None and compose[0].nplaces != 0
+    overlay = resample._OverlayStruct(logo.data_ptr(), 4, 4, 16)
+    place = resample._PlaceStruct(0, 1, 2, 3)    # (overlay 0, one in and two up from the bottom-right corner)
+    for st in compose if compose is not None else ():
+        st.colour[:] = (200, 30, 90)
+    keep = (colour, depth, sharp, lanczos, boxes, filters, compose, overlay, place)
+    return {"colour": pair(colour), "depth": C.addressof(depth) if depth is not None else None, "light": route.get("light", 0),
+            "unsharp": pair(sharp), "resample": pair(lanczos, 0), "box": pair(boxes), "filter": pair(filters), "compose": pair(compose),
+            "overlays": pair(overlay if placed else None), "places": pair(place if placed else None)}, keep
 
 
 def test_the_fitted_size_is_the_one_the_routes_use():
@@ -162,6 +250,11 @@ def _check(rc, what):
     assert rc == 0, (what, sj.lib().sjpeg_hip_last_error().decode())
 
 
+def _flat(values):
+    """the positional arguments of segments that take one value or a tuple of two"""
+    return [v for value in values for v in (value if isinstance(value, tuple) else (value,))]
+
+
 def _routes(family):
     """(label, {argument: value}) of every route of a family"""
     axes = FAMILIES[family][3]
@@ -173,8 +266,10 @@ def _run(engine, pictures, family, route, packed):
     """(fused answer, two-step answer) of one route"""
     L = sj.lib()
     shape_entry, fmt, order, _ = FAMILIES[family]
-    frames = pictures[fmt][1]
-    sheet_family = family in ("sheet", "sheet_flat")
+    frames = pictures[P010 if route.get("depth") else fmt][1]
+    sheet_family = family in SHEET_FAMILIES
+    if "shape" in route:
+        route = dict(route, sizes=route["shape"][0], orientations=route["shape"][1])
     factors, sizes, orients = _u8(route.get("factors")), _i32(route.get("sizes")), _u8(route.get("orientations"))
     flatten = sj._FlattenStruct((C.c_uint8 * 3)(17, 128, 250), 0, 255.0, 0.0) if route.get("flatten") else None
     sheet = sj._SheetStruct(2, 2, CELL, CELL, 2, 2, (C.c_uint8 * 3)(10, 20, 30), 0)
@@ -186,6 +281,8 @@ def _run(engine, pictures, family, route, packed):
     ones, own = _u8([1] * N), _i32([list(d) for d in DIMS])
     fused_args = {"factors": _ptr(factors), "sizes": _ptr(sizes), "orientations": _ptr(orients), "sheet": C.addressof(sheet),
                   "flatten": C.addressof(flatten) if flatten is not None else None}
+    newer, keep = _newer_args(route, pictures["logo"])
+    fused_args.update(newer)
     shape_args = dict(fused_args)
     if family == "reduced" and factors is None:
         shape_args["factors"] = _ptr(ones)
@@ -198,13 +295,13 @@ def _run(engine, pictures, family, route, packed):
     # ---- fused
     fused = _Out(n, packed)
     entry = "sjpeg_hip_encode_ragged_%s%s_src" % (family, "_packed" if packed else "")
-    _check(getattr(L, entry)(engine._h, fmt, N, frames, C.byref(p.params), *[fused_args[name] for name in order], C.addressof(p.meta), 1,
+    _check(getattr(L, entry)(engine._h, fmt, N, frames, C.byref(p.params), *_flat(fused_args[name] for name in order), C.addressof(p.meta), 1,
                              *fused.args(strided=sheet_family)), entry)
     got = fused.answer()
     # ---- two steps: the shape entry into a caller's buffer ...
     made, nmade, made_fmt = (sj.RaggedFrame * N)(), C.c_int(N), C.c_int(-1)
     pictures_buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
-    args = [shape_args[name] for name in shape_order]
+    args = _flat(shape_args[name] for name in shape_order)
     tail = [pictures_buf.data_ptr(), pictures_buf.numel(), made] + ([C.byref(nmade)] if sheet_family else []) + [C.byref(made_fmt),
                                                                                                                  sj.Engine._stream()]
     _check(getattr(L, shape_entry)(engine._h, fmt, N, frames, *args, *tail), shape_entry)
